@@ -35,6 +35,8 @@ other ranks wait at one barrier), and the line carries `config.ranks` (rank -> d
 `config.backend_world` gathered inside the run, so that a multi-GPU line can be audited from its JSON.
 `--legs` restricts the run to some legs (profiling: `--legs batchseq --graph 0 --inflight 1` launches only batch chains,
 one at a time — what `roofline` is quoted on; profiles/collect.sh).
+`--dump-outputs DIR` writes the candidates of the last timed step as DIR/<name>.npy (same arguments, same input frames:
+two builds can be compared output for output).
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -47,12 +49,10 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# Frames in flight run on one HIP stream each; the runtime multiplexes streams onto 4 hardware queues by
-# default, which serialises the 4th stream behind another one.  Measured on MI355X: 4 frames in flight,
-# 4 queues 727 frames/s, 8 queues 865 (3 in flight: 825 / 832).  Must be set before the HIP runtime starts.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 PREWARM_S = 1.5       # fixed wall time every rank spends running frames before --warmup / the timed region
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: at most this much in all (larger outputs: a fixed, seeded sample of the candidates)
+DUMP_SEED = 20260
 # Version of the JSON line's keys.  1 = rounds 1-4 (a step = one batch of 8 on one handle).  2 = round 5 (a step = one batch on EACH of the S
 # handles in flight, default batch 16: `frames_per_step_per_gpu`, `ms_per_step` changed meaning; `frame_ms` = per-batch completion pacing).
 # 3 = round 6: `frame_ms` renamed `batch_completion_ms` (it never was a frame latency), `child_legs` reports how the child-process legs ended.
@@ -96,6 +96,32 @@ def cpu_info():
     return model, (len(cores) or nthreads), nthreads
 
 
+def dump_outputs(path, frames_out):
+    """--dump-outputs DIR: the candidates the timed path handed back in its last step, frame after frame in the order the
+    frames were enqueued, as DIR/<name>.npy.  `frame_counts` = candidates per frame; one row per candidate in `score`,
+    `component`, `level`, `nparts`, `boxes` [n, max_parts, 4] and `locs` [n, max_parts, 3] (integers as float32: exact below
+    2^24).  Over DUMP_MAX_BYTES the rows are a seeded sample, and `sample_index` says which rows of the step they are."""
+    heads = np.concatenate([f[0] for f in frames_out])
+    rows = {"score": heads["score"],
+            "component": heads["component"].astype(np.float32),
+            "level": heads["level"].astype(np.float32),
+            "nparts": heads["nparts"].astype(np.float32),
+            "boxes": np.concatenate([f[1] for f in frames_out]).astype(np.float32),
+            "locs": np.concatenate([f[2] for f in frames_out]).astype(np.float32)}
+    n = len(heads)
+    row_bytes = sum(a.nbytes for a in rows.values()) / max(n, 1)
+    out = {"frame_counts": np.array([len(f[0]) for f in frames_out], np.float64)}
+    if n * row_bytes > DUMP_MAX_BYTES:
+        keep = int((DUMP_MAX_BYTES - (1 << 20)) // (row_bytes + 8))
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False))
+        rows = {k: a[idx] for k, a in rows.items()}
+        out["sample_index"] = idx.astype(np.float64)
+    out.update(rows)
+    os.makedirs(path, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+
+
 def respawn_command(argv, n, port=None):
     """`python bench.py --gpus N` outside torchrun: the command that runs the same arguments as N ranks on this node."""
     import socket
@@ -134,6 +160,8 @@ def main_group(args):
     t0 = time.perf_counter()
     outs = g.detect_batch([frames[i % 8] for i in range(args.steps * N)])
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outs[-N:])       # a step = one frame per device
     line = {"metric": f"detect() frames/sec, {W}x{H}, 26-part person model", "value": round(args.steps * N / dt, 3), "unit": "frames/s",
             "n_gpus": N, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
@@ -180,6 +208,9 @@ def main():
     ap.add_argument("--graph", type=int, default=int(os.environ.get("PBD_GRAPH", "1")), help="pbd_options.graph: replay a captured hipGraph per frame")
     ap.add_argument("--no-prewarm", action="store_true", help="skip the fixed pre-warm (profiling runs)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL; gloo for CPU-side smoke runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the candidates of the last timed step (what the callers of the timed path received; "
+                         "rank 0's with N > 1) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (see dump_outputs)")
     ap.add_argument("--legs", default="all",
                     help="comma-separated subset of timed,h2d,mfma32,split16,single,seq,batchseq,cpu (default all).  timed = the K steps `value` is quoted "
                          "on; h2d = the same with pinned host images; single = the handles fed one frame per call; seq = sequential "
@@ -193,6 +224,10 @@ def main():
         raise SystemExit(f"--legs: unknown leg(s) {sorted(legs - set(ALL_LEGS))}; choose from {ALL_LEGS}")
     if args.no_cpu_baseline:
         legs.discard("cpu")
+    if args.steps < 1:
+        raise SystemExit(f"--steps {args.steps}: at least one timed step")
+    if args.dump_outputs and "timed" not in legs and not args.group:
+        raise SystemExit("--dump-outputs writes what the timed leg computed: --legs must include `timed`")
 
     import torch
     import torch.distributed as dist
@@ -265,11 +300,14 @@ def main():
         if world > 1:
             gathered_last[0] = gather_candidates(out, handles[0].max_parts, capacity=cap * B_gather[0], device=cdev, dst=0)
 
+    frame_counts = {}   # handle -> candidates per frame of its latest batch (the frame boundaries --dump-outputs writes)
+
     def collect_one(hd, B):
         """the step's candidates: one frame's, or the batch's (concatenated: (level, component, root) order inside a frame)"""
         if B == 1:
             return hd.collect(cap)
         outs_b = hd.collect_batch(cap)
+        frame_counts[hd] = [len(o[0]) for o in outs_b]
         return tuple(np.concatenate([o[k] for o in outs_b]) for k in range(3))
 
     def run(nsteps, collect_out=None, stamps=None, host=False, B=B, solo=False):
@@ -357,6 +395,13 @@ def main():
     outs, per_frame_ms, per_frame_ms_h2d = [], [0.0], [0.0]
     if "timed" in legs:
         dt, outs, per_frame_ms = timed(args.steps, host=False)
+        if args.dump_outputs and rank == 0:
+            # the last step = the last batch of each of the S handles, handles[0] .. handles[S - 1] in enqueue order
+            last = []
+            for hd_j, out in zip(handles, outs[-S:]):
+                starts = np.cumsum([0] + (frame_counts[hd_j] if B > 1 else [len(out[0])]))
+                last += [tuple(a[s:e] for a in out) for s, e in zip(starts[:-1], starts[1:])]
+            dump_outputs(args.dump_outputs, last)
     # ---- the same K steps handing over pinned host images: H2D inside every step ----
     if "h2d" in legs:
         dt_h2d, _, per_frame_ms_h2d = timed(args.steps, host=True)

@@ -3,7 +3,7 @@ import os
 os.environ.setdefault("PBD_LIBRARY", os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "partsbaseddetector_amd", "libpbd_hip_probes.so"))  # `make -C partsbaseddetector_amd/csrc probes`
 import ctypes as C
 import sys
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from partsbaseddetector_amd import capi
 from partsbaseddetector_amd.model import make_image, make_person_model
 m = make_person_model(); m.thresh = 3e38

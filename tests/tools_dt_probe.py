@@ -4,7 +4,7 @@ os.environ.setdefault("PBD_LIBRARY", os.path.join(os.path.dirname(os.path.abspat
 import ctypes as C
 import sys
 import numpy as np
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from partsbaseddetector_amd import capi
 from partsbaseddetector_amd.model import make_tree_model
 

@@ -4,7 +4,6 @@ import os
 import sys
 import threading
 import time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from partsbaseddetector_amd import capi

@@ -6,7 +6,6 @@ import sys
 import threading
 import time
 import numpy as np
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from partsbaseddetector_amd import capi
