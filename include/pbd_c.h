@@ -53,15 +53,16 @@ enum {
  */
 typedef struct pbd_model_desc {
   int32_t nfilters;      /* Model::filters().size()                            */
-  int32_t kh, kw;        /* filter rows / cols, 1..9, UNIFORM over the bank: the reference allows a size per filter
-                            (include/Parts.hpp:185-187) but every model its tools write is uniform; a mixed bank is
-                            not representable here (the C++ adaptor refuses it with PBD_ERR_UNSUPPORTED)             */
+  int32_t kh, kw;        /* filter rows / cols, 1..9, uniform over the bank (pbd_create).  The reference takes a size per
+                            filter (src/SpatialConvolutionEngine.cpp:133-159, include/Parts.hpp:185-187), and its own
+                            converter writes such models (matlab/modelTransfer.m, VOC path: a root filter per component
+                            plus part filters of another size): those go through pbd_create_sized with kh = kw = 0 */
   int32_t flen;          /* Model::flen()  (32)                                */
   int32_t norient;       /* Model::norient() (18)                              */
   int32_t sbin;          /* Model::binsize()                                   */
   int32_t interval;      /* Model::nscales() (levels per octave)               */
   float thresh;          /* Model::thresh()                                    */
-  const float* filters;  /* [nfilters][kh][kw*flen]                            */
+  const float* filters;  /* [nfilters][kh][kw*flen] (pbd_create_sized: back to back, each its own size) */
   int32_t ndefs;
   const float* defw;     /* [ndefs][4]  = {wxx, wx, wyy, wy}                   */
   const int32_t* anchors;/* [ndefs][2]  = {x, y}, 0-based                      */
@@ -147,14 +148,16 @@ typedef struct pbd_options {
  * or a new entry point, fields are never inserted.  pbd_abi_version() returns the version the LIBRARY was built with;
  * a binding compares it with the header it was compiled against (round 2 inserted `graph` in front of reserved[],
  * which nothing could detect).                                                                                       */
-#define PBD_ABI_VERSION 4
+#define PBD_ABI_VERSION 5
 int pbd_abi_version(void);
 /* Version history: 3 = rounds 3-4.  4 (round 5) = PBD_CONV_AUTO resolves to PBD_CONV_SPLIT for float handles (numerics of
  * AUTO change in the last bits: rounds 3-4 resolved to PBD_CONV_MFMA, and before that to EXACT for banks other than 5 x 5),
  * PBD_CONV_SPLIT, PBD_CONV_SPLIT_F16, pbd_detect_image / pbd_pyramid_image / pbd_get_level_image_raw (PBD_DEPTH_*), pbd_tune_plan, pbd_options.reserved[0] = nms_sz, pbd_get_conv_mode, pbd_get_stage_state, pbd_group_comm_size.  Struct layouts unchanged.
  * Round 6 keeps version 4 (no entry point, layout or result changed); refinements of existing entries: pbd_set_level_features refuses
  * features outside a split bank's domain (PBD_ERR_ARG), pbd_tune_plan drops the handle's plan on return, pbd_detect_image replays a
- * hipGraph under pbd_options.graph.                                                                                             */
+ * hipGraph under pbd_options.graph.
+ * 5 = pbd_create_sized, pbd_group_create_sized, pbd_get_filter_size (filter banks with a size per filter); also marks the round-6
+ * refinements above.  Struct layouts unchanged; results of uniform banks unchanged.                                            */
 
 /* ---- output record: include/Candidate.hpp:56-111 --------------------------
  * One candidate = head + max_parts boxes (x, y, width, height as cv::Rect)
@@ -181,6 +184,19 @@ int pbd_set_levels(pbd_handle* h, const int32_t* levels, int n);
  * incl. SpatialConvolutionEngine::setFilters (src/SpatialConvolutionEngine.cpp:133-159)
  * and Parts construction (include/Parts.hpp:229-235).                        */
 int pbd_create(const pbd_model_desc* model, const pbd_options* opt, pbd_handle** out);
+/* A size per filter (SpatialConvolutionEngine::setFilters builds one FilterEngine per filter at its own size).
+ * fsize[nfilters][2] = {rows kh, cols kw} of each filter, 1..9 each (else PBD_ERR_UNSUPPORTED); model->filters holds the filters
+ * back to back (filter n at offset sum_{i<n} kh_i*kw_i*flen, each kh_i x (kw_i*flen) interleaved); model->kh / kw must be 0 and
+ * fsize non-null (else PBD_ERR_ARG).  Validation happens before any HIP call, as in pbd_create.
+ * A bank whose filters all have one size is exactly the pbd_create handle of that size (same kernels, same bits).  A mixed bank is
+ * run as size groups (filters of one kh x kw), each on the kernel a uniform bank of that size runs in the handle's conv mode; the
+ * conv mode resolves from the total filter count as in pbd_create.  The stage entry points (pbd_pdf, pbd_get/set_level_response*,
+ * pbd_dp_min, pbd_dp_argmin) keep the caller's filter order.  Part boxes are sized by the filter of the mixture a part chose, with
+ * the reference's quirk kept: xsize() and ysize() both return the filter's rows (include/Parts.hpp:185-187), so a box is
+ * kh x kh scaled even where kw != kh.                                                                                           */
+int pbd_create_sized(const pbd_model_desc* model, const int32_t* fsize, const pbd_options* opt, pbd_handle** out);
+/* rows / cols of filter `filter` (caller's order) of a handle made by either constructor */
+int pbd_get_filter_size(const pbd_handle* h, int filter, int32_t* kh, int32_t* kw);
 int pbd_destroy(pbd_handle* h);
 const char* pbd_last_error(const pbd_handle* h);
 int pbd_max_parts(const pbd_handle* h);
@@ -258,6 +274,9 @@ typedef struct pbd_group pbd_group;
 /* opt->device is ignored (devices[] decides); every other option applies to all members                     */
 int pbd_group_create(const pbd_model_desc* model, const pbd_options* opt, const int32_t* devices, int ndevices,
                      int gather_mode, pbd_group** out);
+/* pbd_group_create with a size per filter: every member is made by pbd_create_sized (same fsize rules) */
+int pbd_group_create_sized(const pbd_model_desc* model, const int32_t* fsize, const pbd_options* opt, const int32_t* devices,
+                           int ndevices, int gather_mode, pbd_group** out);
 int pbd_group_destroy(pbd_group* g);
 const char* pbd_group_last_error(const pbd_group* g);
 int pbd_group_size(const pbd_group* g);
@@ -371,7 +390,8 @@ int pbd_get_stage_ms(const pbd_handle* h, float ms[6]);
 /* enable per-stage events (adds host syncs between stages; off by default)   */
 int pbd_set_profiling(pbd_handle* h, int on);
 /* algorithmic bytes / flops of the last frame geometry (SURVEY §8d formulas):
- * [0] B_hog [1] B_pdf [2] F_pdf [3] B_dp [4] cells [5] dt_elements            */
+ * [0] B_hog [1] B_pdf [2] F_pdf [3] B_dp [4] cells [5] dt_elements
+ * (filter taps: the sum of kh_i * kw_i over the filters, for mixed banks too) */
 int pbd_get_work(const pbd_handle* h, double work[6]);
 /* device memory held by the handle: the buffers and work tables of the current frame geometry (everything a
  * re-plan frees) and the model-sized allocations made at create.  Either pointer may be NULL.                     */

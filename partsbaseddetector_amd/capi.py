@@ -43,8 +43,9 @@ EXPORTS = [
     "pbd_detect_batch_u8", "pbd_detect_batch_enqueue_u8", "pbd_detect_batch_enqueue_dev_u8", "pbd_detect_batch_collect",
     "pbd_get_stage_state", "pbd_get_conv_mode", "pbd_group_comm_size",
     "pbd_detect_image", "pbd_pyramid_image", "pbd_get_level_image_raw", "pbd_tune_plan",
+    "pbd_create_sized", "pbd_group_create_sized", "pbd_get_filter_size",
 ]
-PBD_ABI_VERSION = 4
+PBD_ABI_VERSION = 5
 
 
 class pbd_options(C.Structure):
@@ -98,14 +99,21 @@ class Handle:
     """Owns one pbd_handle (one GPU, one stream)."""
 
     def __init__(self, model, device=0, conv_mode=PBD_CONV_AUTO, max_candidates=4096, dt_correct_ptr=0,
-                 level_begin=0, level_end=0, dp_groups=0, dtype=np.float32, graph=0, dp_mode=0, nms_sz=0):
+                 level_begin=0, level_end=0, dp_groups=0, dtype=np.float32, graph=0, dp_mode=0, nms_sz=0, sized=False):
         """dtype: np.float32 = PartsBasedDetector<float>, np.float64 = PartsBasedDetector<double>.
         nms_sz > 0: score-map NMS of the root planes on the device in front of the back-tracking (pbd_options.reserved[0]).
         dp_mode: 0 = messages folded by the parent's x pass where the model allows it (default), 1 = the
-        three-kernel structure (x pass, y pass, reduce) for every model.  dp_groups: ignored (kept for callers)."""
+        three-kernel structure (x pass, y pass, reduce) for every model.  dp_groups: ignored (kept for callers).
+        A model whose filters differ in size is created through pbd_create_sized, a uniform one through pbd_create
+        (sized=True: pbd_create_sized for any model)."""
         self.L = lib()
         self.model = model
-        self.desc = model.to_desc()
+        # a size per filter (pbd_create_sized) only where the bank is mixed: uniform banks keep pbd_create
+        self.fsize = None
+        if model.is_uniform() and not sized:
+            self.desc = model.to_desc()
+        else:
+            self.desc, self.fsize = model.to_desc_sized()
         self.dtype = np.dtype(dtype)
         if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
             raise ValueError("dtype must be float32 or float64")
@@ -114,7 +122,10 @@ class Handle:
         opt = pbd_options(device, conv_mode, max_candidates, dt_correct_ptr, level_begin, level_end,
                           PBD_SCALAR_F64 if self._f64 else PBD_SCALAR_F32, graph, (C.c_int32 * 2)(nms_sz, dp_mode))
         self.h = C.c_void_p()
-        rc = self.L.pbd_create(C.byref(self.desc), C.byref(opt), C.byref(self.h))
+        if self.fsize is None:
+            rc = self.L.pbd_create(C.byref(self.desc), C.byref(opt), C.byref(self.h))
+        else:
+            rc = self.L.pbd_create_sized(C.byref(self.desc), _p(self.fsize, C.c_int32), C.byref(opt), C.byref(self.h))
         if rc != PBD_OK:
             msg = self.L.pbd_last_error(self.h).decode() if self.h else "allocation failed"
             if self.h:
@@ -128,6 +139,12 @@ class Handle:
         if getattr(self, "h", None):
             self.L.pbd_destroy(self.h)
             self.h = None
+
+    def filter_size(self, n):
+        """(kh, kw) of filter n (pbd_get_filter_size)."""
+        kh, kw = C.c_int32(), C.c_int32()
+        self._chk(self.L.pbd_get_filter_size(self.h, n, C.byref(kh), C.byref(kw)))
+        return kh.value, kw.value
 
     def __del__(self):
         try:
@@ -455,13 +472,21 @@ class Group:
                  dtype=np.float32, graph=0, nms_sz=0):
         self.L = lib()
         self.model = model
-        self.desc = model.to_desc()
+        self.fsize = None
+        if model.is_uniform():
+            self.desc = model.to_desc()
+        else:
+            self.desc, self.fsize = model.to_desc_sized()
         f64 = np.dtype(dtype) == np.dtype(np.float64)
         opt = pbd_options(0, conv_mode, max_candidates, 0, 0, 0, PBD_SCALAR_F64 if f64 else PBD_SCALAR_F32, graph,
                           (C.c_int32 * 2)(int(nms_sz), 0))
         dv = np.ascontiguousarray(list(devices), np.int32)
         self.g = C.c_void_p()
-        rc = self.L.pbd_group_create(C.byref(self.desc), C.byref(opt), _p(dv, C.c_int32), len(dv), gather, C.byref(self.g))
+        if self.fsize is None:
+            rc = self.L.pbd_group_create(C.byref(self.desc), C.byref(opt), _p(dv, C.c_int32), len(dv), gather, C.byref(self.g))
+        else:
+            rc = self.L.pbd_group_create_sized(C.byref(self.desc), _p(self.fsize, C.c_int32), C.byref(opt), _p(dv, C.c_int32), len(dv),
+                                               gather, C.byref(self.g))
         if rc != PBD_OK:
             msg = self.L.pbd_group_last_error(self.g).decode() if self.g else "allocation failed"
             if self.g:

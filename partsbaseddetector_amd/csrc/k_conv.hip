@@ -264,8 +264,9 @@ __global__ __launch_bounds__(256) void k_conv_exact_f64(const ConvTile* __restri
   }
 }
 
-// generic-size fallback (runtime kh, kw <= 9)
-template <typename T>
+// generic-size fallback (runtime kh, kw <= 9).  MIX: a size group of a mixed bank (pbd_create_sized) — the tile's pad = n0 | (nf_g << 16):
+// planes n0 .. n0 + nf_g - 1 of a level block of `nf` planes, wT the group's own (ConvTile, pbd_internal.hpp)
+template <typename T, bool MIX = false>
 __global__ __launch_bounds__(256) void k_conv_exact_generic(const ConvTile* __restrict__ tiles,
                                                             const LevelDev* __restrict__ levels,
                                                             const T* __restrict__ feat,
@@ -293,7 +294,9 @@ __global__ __launch_bounds__(256) void k_conv_exact_generic(const ConvTile* __re
   const bool valid = (oy < H && ox < W);
   const T* fbase = ft + (ly * TW + lx) * CSTR;
   T* R = resp + lv.cell_off * nf;
-  for (int n = blockIdx.y; n < nf; n += gridDim.y) {
+  int nfw = nf;   // planes this launch writes
+  if constexpr (MIX) { R += (size_t)(t.pad & 0xFFFF) * H * W; nfw = t.pad >> 16; }
+  for (int n = blockIdx.y; n < nfw; n += gridDim.y) {
     T tot = (T)0;
     for (int c = 0; c < PBD_FLEN; ++c) {
       T acc = (T)0;
@@ -308,8 +311,15 @@ __global__ __launch_bounds__(256) void k_conv_exact_generic(const ConvTile* __re
 
 template <typename T>
 static void launch_conv_exact_t(const ConvTile* tiles, int ntiles, const LevelDev* levels, const T* feat,
-                                const T* wT, T* resp, int nf, int nfpad, int kh, int kw, hipStream_t s) {
+                                const T* wT, T* resp, int nf, int nfpad, int kh, int kw, hipStream_t s, int nf_stride) {
   const size_t lds = sizeof(T) * (CT + kh - 1) * (CT + kw - 1) * CSTR;
+  if (nf_stride > 0) {   // a size group of a mixed bank: the run-time-size kernel for every size (the reference's summation order whatever the size)
+    static LdsOptIn optinm;
+    optinm.ensure((const void*)k_conv_exact_generic<T, true>, lds);
+    dim3 grid(ntiles, nf < 16 ? nf : 16);
+    hipLaunchKernelGGL((k_conv_exact_generic<T, true>), grid, dim3(256), lds, s, tiles, levels, feat, wT, resp, nf_stride, nfpad, kh, kw);
+    return;
+  }
   if constexpr (sizeof(T) == 8) {
     if (kh == 5 && kw == 5) {
       constexpr int GPW = 4;
@@ -339,10 +349,10 @@ static void launch_conv_exact_t(const ConvTile* tiles, int ntiles, const LevelDe
 
 // ts = sizeof(T): 4 -> SpatialConvolutionEngine(CV_32F), 8 -> CV_64F
 void launch_conv_exact(const ConvTile* tiles, int ntiles, const LevelDev* levels, const void* feat, const void* wT,
-                       void* resp, int ts, int nf, int nfpad, int kh, int kw, hipStream_t s) {
+                       void* resp, int ts, int nf, int nfpad, int kh, int kw, hipStream_t s, int nf_stride) {
   if (ntiles <= 0) return;
-  if (ts == 8) launch_conv_exact_t<double>(tiles, ntiles, levels, (const double*)feat, (const double*)wT, (double*)resp, nf, nfpad, kh, kw, s);
-  else launch_conv_exact_t<float>(tiles, ntiles, levels, (const float*)feat, (const float*)wT, (float*)resp, nf, nfpad, kh, kw, s);
+  if (ts == 8) launch_conv_exact_t<double>(tiles, ntiles, levels, (const double*)feat, (const double*)wT, (double*)resp, nf, nfpad, kh, kw, s, nf_stride);
+  else launch_conv_exact_t<float>(tiles, ntiles, levels, (const float*)feat, (const float*)wT, (float*)resp, nf, nfpad, kh, kw, s, nf_stride);
 }
 
 // ---------------------------------------------------------------------------
@@ -495,7 +505,8 @@ template <> struct Mfma16<float> {
 // issue rate with two waves per SIMD: tests/tools/mfma_rate_probe.hip)
 // KH_T / KW_T > 0: compile-time filter size (the 5x5 bank of the person / face models: tap loops and tile geometry fold);
 // 0: the size comes from the kernel arguments (any kh x kw <= 9 x 9, src/SpatialConvolutionEngine.cpp:133-159 takes any).
-template <typename T, int KH_T, int KW_T, int NHALF, int WPE, int NTW = 1, bool B4 = false>   // WPE: waves per SIMD the register allocation must allow; NTW: 16-filter n-tiles per workgroup
+// MIX: a size group of a mixed bank, as in k_conv_exact_generic (run-time size only).
+template <typename T, int KH_T, int KW_T, int NHALF, int WPE, int NTW = 1, bool B4 = false, bool MIX = false>   // WPE: waves per SIMD the register allocation must allow; NTW: 16-filter n-tiles per workgroup
 __global__ __launch_bounds__(256, WPE) void k_conv_mfma16(const ConvTile* __restrict__ tiles,
                                                      const LevelDev* __restrict__ levels,
                                                      const T* __restrict__ feat, const T* __restrict__ wT,
@@ -660,6 +671,8 @@ __global__ __launch_bounds__(256, WPE) void k_conv_mfma16(const ConvTile* __rest
   // (a store instruction then writes whole 64-B row segments of one response plane).  The slab is private to the
   // wave and a wave's LDS operations execute in order, so the n-tiles simply follow each other.
   T* R = resp + lv.cell_off * nf;
+  int nfw = nf;   // planes this launch writes
+  if constexpr (MIX) { R += (size_t)(t.pad & 0xFFFF) * H * W; nfw = t.pad >> 16; }
   T* tr = ft + wave * (16 * 65);           // per-wave [16 filters][64 cells + 1]
   // lane -> slot (M-tile lane >> 4, row lane & 15) -> packed cell -> (row, column) of the level
   const int pc = 16 * (wave + 4 * (lane >> 4)) + (lane & 15);
@@ -678,7 +691,7 @@ __global__ __launch_bounds__(256, WPE) void k_conv_mfma16(const ConvTile* __rest
       const unsigned cellb = (unsigned)(py * W + pxx) * (unsigned)sizeof(T);      // < 2^31 (plan_frame: a level has < 2^28 cells)
       for (int j = 0; j < 16; ++j) {
         const int fn = nbase + 16 * nt + j;
-        if (fn < nf) {
+        if (fn < nfw) {
           char* plane = (char*)(R + (size_t)fn * H * W);
           *(T*)(plane + cellb) = tr[j * 65 + lane];
         }
@@ -691,16 +704,17 @@ __global__ __launch_bounds__(256, WPE) void k_conv_mfma16(const ConvTile* __rest
 
 int g_conv_lds_req_kb = 0;   // set by pbd_api.cpp from PBD_CONV_LDS_KB in probe / tuning builds
 // KH_T = KW_T = 5: the compile-time 5x5 instantiation; 0: any kh x kw (run-time tap loop)
-template <typename T, int NHALF, int WPE, int NTW = 1, bool B4 = false, int KH_T = 5, int KW_T = 5>
+template <typename T, int NHALF, int WPE, int NTW = 1, bool B4 = false, int KH_T = 5, int KW_T = 5, bool MIX = false>
 static void launch_conv_mfma16_t(const ConvTile* tiles, int ntiles, const LevelDev* levels, const T* feat,
-                                 const T* wT, T* resp, int nf, int nfpad, hipStream_t s, int kh = 5, int kw = 5) {
+                                 const T* wT, T* resp, int nf, int nfpad, hipStream_t s, int kh = 5, int kw = 5, int nf_stride = 0) {
   size_t lds = std::max(sizeof(T) * (CT + kh - 1) * (CT + kw - 1) * (PBD_FLEN / NHALF + (sizeof(T) == 4 ? 2 : 1)), sizeof(T) * 4 * 16 * 65);
   if (g_conv_lds_req_kb > 0) lds = std::max(lds, (size_t)g_conv_lds_req_kb * 1024);   // tuning builds: occupancy cap by LDS request
   static LdsOptIn optin;   // one per instantiation
-  optin.ensure((const void*)k_conv_mfma16<T, KH_T, KW_T, NHALF, WPE, NTW, B4>, lds);
+  optin.ensure((const void*)k_conv_mfma16<T, KH_T, KW_T, NHALF, WPE, NTW, B4, MIX>, lds);
   dim3 grid((ntiles + 7) / 8 * 8, (nf + 16 * NTW - 1) / (16 * NTW));   // tiles padded to a multiple of 8 (XCD-aware mapping in the kernel)
   static const int prio_mode = PBD_PROBE_ENV("PBD_CONV_PRIO") ? atoi(PBD_PROBE_ENV("PBD_CONV_PRIO")) : 0;   // probe build only
-  hipLaunchKernelGGL((k_conv_mfma16<T, KH_T, KW_T, NHALF, WPE, NTW, B4>), grid, dim3(256), lds, s, tiles, levels, feat, wT, resp, nf, nfpad | (prio_mode << 16), ntiles, kh, kw);
+  hipLaunchKernelGGL((k_conv_mfma16<T, KH_T, KW_T, NHALF, WPE, NTW, B4, MIX>), grid, dim3(256), lds, s, tiles, levels, feat, wT, resp, MIX ? nf_stride : nf,
+                     nfpad | (prio_mode << 16), ntiles, kh, kw);
 }
 
 // ---------------------------------------------------------------------------
@@ -927,8 +941,12 @@ void launch_conv_glds_f32(const ConvTile* tiles, int ntiles, const LevelDev* lev
 }
 
 void launch_conv_mfma_f64(const ConvTile* tiles, int ntiles, const LevelDev* levels, const double* feat,
-                          const double* wT, const double* w4u, double* resp, int nf, int nfpad, int kh, int kw, hipStream_t s) {
+                          const double* wT, const double* w4u, double* resp, int nf, int nfpad, int kh, int kw, hipStream_t s, int nf_stride) {
   if (ntiles <= 0) return;
+  if (nf_stride > 0) {   // a size group of a mixed bank: the run-time-size configuration for every size
+    launch_conv_mfma16_t<double, 4, 2, 1, true, 0, 0, true>(tiles, ntiles, levels, feat, w4u, resp, nf, nfpad, s, kh, kw, nf_stride);
+    return;
+  }
   if (kh != 5 || kw != 5) {   // any other filter size: the same kernel with a run-time tap loop (16-byte B loads from the [tap][group][k][n][u] copy)
     launch_conv_mfma16_t<double, 4, 2, 1, true, 0, 0>(tiles, ntiles, levels, feat, w4u, resp, nf, nfpad, s, kh, kw);
     return;
@@ -951,8 +969,12 @@ void launch_conv_mfma_f64(const ConvTile* tiles, int ntiles, const LevelDev* lev
 // double-buffered staging (next channel group prefetched into registers across the K loop, second LDS buffer):
 // 0.51-0.71 ms vs 0.39 ms.
 void launch_conv_mfma16_f32(const ConvTile* tiles, int ntiles, const LevelDev* levels, const float* feat,
-                            const float* wT, const float* w4u, float* resp, int nf, int nfpad, int nhalf, hipStream_t s, int kh, int kw) {
+                            const float* wT, const float* w4u, float* resp, int nf, int nfpad, int nhalf, hipStream_t s, int kh, int kw, int nf_stride) {
   if (ntiles <= 0) return;
+  if (nf_stride > 0) {   // a size group of a mixed bank: the run-time-size configuration for every size
+    launch_conv_mfma16_t<float, 2, 3, 2, true, 0, 0, true>(tiles, ntiles, levels, feat, w4u, resp, nf, nfpad, s, kh, kw, nf_stride);
+    return;
+  }
   if (kh != 5 || kw != 5) {   // any other filter size (3x3 .. 9x9): the default configuration (two n-tiles, 16-byte B loads) with a run-time tap loop
     launch_conv_mfma16_t<float, 2, 3, 2, true, 0, 0>(tiles, ntiles, levels, feat, w4u, resp, nf, nfpad, s, kh, kw);
     return;

@@ -157,7 +157,9 @@ void conv_split16_filters(const float* filters, int nf, int kh, int kw, std::vec
 }
 
 // NS: parts per operand — 3: bfloat16 parts, six products (PBD_CONV_SPLIT); 2: scaled binary16 parts, three products (PBD_CONV_SPLIT_F16, below)
-template <int NT, int NW, int PIN, int NS = 3>
+// MIX: one size group of a mixed bank (pbd_create_sized): the tile's pad = n0 | (nf_g << 16) — planes n0 .. n0 + nf_g - 1 of a level block
+// of `nf` planes; filt / oscale are the group's own (ConvTile, pbd_internal.hpp)
+template <int NT, int NW, int PIN, int NS = 3, bool MIX = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, PIN ? 1 : 2))) void k_conv_split32(const ConvTile* __restrict__ tiles, const LevelDev* __restrict__ levels,
                                                              const uint16_t* __restrict__ feat, const uint16_t* __restrict__ filt,
                                                              float* __restrict__ resp, int nf, int ntl_bank, int ntile0, int ngroups,
@@ -332,6 +334,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, PIN 
   // D[i = filter 32 nt + (r & 3) + 8 (r >> 2) + 4 kg][j = cell pos of M-tile m]
   float* Rl = resp + lv.cell_off * nf;
   const size_t HW = (size_t)H * W;
+  int nfw = nf;                                          // planes this launch writes
+  if constexpr (MIX) { Rl += (size_t)(t.pad & 0xFFFF) * HW; nfw = t.pad >> 16; }
 #pragma unroll
   for (int m = 0; m < 2; ++m) {
     if (m < mvalid && cval[m]) {
@@ -341,7 +345,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, PIN 
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int fo = (r & 3) + 8 * (r >> 2);
-          if (32 * (ntb + nt) + 4 * kg + fo < nf) pl[(size_t)fo * HW] = NS == 3 ? acc[nt][m][r] : acc[nt][m][r] * oscale[32 * (ntb + nt) + 4 * kg + fo];   // (a power of two: exact)
+          if (32 * (ntb + nt) + 4 * kg + fo < nfw) pl[(size_t)fo * HW] = NS == 3 ? acc[nt][m][r] : acc[nt][m][r] * oscale[32 * (ntb + nt) + 4 * kg + fo];   // (a power of two: exact)
         }
       }
     }
@@ -595,30 +599,32 @@ void launch_conv_split_persistent(const ConvTile* tiles, int ntiles, const Level
   }
 }
 
-template <int NT, int NW, int PIN, int NS = 3>
+// MIX: a size group of a mixed bank (nf: the group's filters, nf_stride: the planes of a level block; tiles: the group's list)
+template <int NT, int NW, int PIN, int NS = 3, bool MIX = false>
 static void launch_conv_split_t(const ConvTile* tiles, int ntiles, const LevelDev* levels, const uint16_t* feat_split, const uint16_t* wS,
-                                float* resp, int nf, int ntl_bank, int ntile0, int ngroups, int kh, int kw, hipStream_t s, const float* oscale = nullptr) {
+                                float* resp, int nf, int ntl_bank, int ntile0, int ngroups, int kh, int kw, hipStream_t s, const float* oscale = nullptr,
+                                int nf_stride = 0) {
   constexpr int ROWS = 4 * NW, NHALVES = 16 / ROWS;
   const size_t lds = (size_t)(16 + kw - 1) * (ROWS + kh - 1) * 64 * NS;
   static LdsOptIn optin;
-  optin.ensure((const void*)k_conv_split32<NT, NW, PIN, NS>, lds);
+  optin.ensure((const void*)k_conv_split32<NT, NW, PIN, NS, MIX>, lds);
   const int grid = (ntiles + 7) / 8 * 8 * NHALVES * ngroups;
-  hipLaunchKernelGGL((k_conv_split32<NT, NW, PIN, NS>), dim3(grid), dim3(64 * NW), lds, s, tiles, levels, feat_split, wS, resp, nf, ntl_bank,
-                     ntile0, ngroups, ntiles, kh, kw, oscale);
+  hipLaunchKernelGGL((k_conv_split32<NT, NW, PIN, NS, MIX>), dim3(grid), dim3(64 * NW), lds, s, tiles, levels, feat_split, wS, resp, MIX ? nf_stride : nf,
+                     ntl_bank, ntile0, ngroups, ntiles, kh, kw, oscale);
 }
 // PBD_CONV_SPLIT_F16: the default form of the six-product bank (4 wavefronts per workgroup, dealt loads, groups of five n-tiles) over two parts
 // variant (tuning builds, PBD_SPLIT_VARIANT): 4 = hipcc's own schedule at two wavefronts per SIMD, 7 / 8 = groups of four / three n-tiles
-template <int PIN>
+template <int PIN, bool MIX = false>
 static void launch_conv_split16_g(const ConvTile* tiles, int ntiles, const LevelDev* levels, const uint16_t* feat_split, const uint16_t* wS,
-                                  float* resp, int nf, int kh, int kw, const float* oscale, int G, hipStream_t s) {
+                                  float* resp, int nf, int kh, int kw, const float* oscale, int G, hipStream_t s, int nf_stride = 0) {
   const int ntl = conv_split_ntiles(nf), full = ntl / G, rest = ntl - G * full;
   auto go = [&](int nt, int ntile0, int ngroups) {
     switch (nt) {
-      case 1: launch_conv_split_t<1, 4, PIN, 2>(tiles, ntiles, levels, feat_split, wS, resp, nf, ntl, ntile0, ngroups, kh, kw, s, oscale); break;
-      case 2: launch_conv_split_t<2, 4, PIN, 2>(tiles, ntiles, levels, feat_split, wS, resp, nf, ntl, ntile0, ngroups, kh, kw, s, oscale); break;
-      case 3: launch_conv_split_t<3, 4, PIN, 2>(tiles, ntiles, levels, feat_split, wS, resp, nf, ntl, ntile0, ngroups, kh, kw, s, oscale); break;
-      case 4: launch_conv_split_t<4, 4, PIN, 2>(tiles, ntiles, levels, feat_split, wS, resp, nf, ntl, ntile0, ngroups, kh, kw, s, oscale); break;
-      case 5: launch_conv_split_t<5, 4, PIN, 2>(tiles, ntiles, levels, feat_split, wS, resp, nf, ntl, ntile0, ngroups, kh, kw, s, oscale); break;
+      case 1: launch_conv_split_t<1, 4, PIN, 2, MIX>(tiles, ntiles, levels, feat_split, wS, resp, nf, ntl, ntile0, ngroups, kh, kw, s, oscale, nf_stride); break;
+      case 2: launch_conv_split_t<2, 4, PIN, 2, MIX>(tiles, ntiles, levels, feat_split, wS, resp, nf, ntl, ntile0, ngroups, kh, kw, s, oscale, nf_stride); break;
+      case 3: launch_conv_split_t<3, 4, PIN, 2, MIX>(tiles, ntiles, levels, feat_split, wS, resp, nf, ntl, ntile0, ngroups, kh, kw, s, oscale, nf_stride); break;
+      case 4: launch_conv_split_t<4, 4, PIN, 2, MIX>(tiles, ntiles, levels, feat_split, wS, resp, nf, ntl, ntile0, ngroups, kh, kw, s, oscale, nf_stride); break;
+      case 5: launch_conv_split_t<5, 4, PIN, 2, MIX>(tiles, ntiles, levels, feat_split, wS, resp, nf, ntl, ntile0, ngroups, kh, kw, s, oscale, nf_stride); break;
       default: break;
     }
   };
@@ -626,14 +632,15 @@ static void launch_conv_split16_g(const ConvTile* tiles, int ntiles, const Level
   if (rest) go(rest, G * full, 1);
 }
 void launch_conv_split16(const ConvTile* tiles, int ntiles, const LevelDev* levels, const uint16_t* feat_split, const uint16_t* wS,
-                         float* resp, int nf, int kh, int kw, const float* oscale, int variant, hipStream_t s) {
+                         float* resp, int nf, int kh, int kw, const float* oscale, int variant, hipStream_t s, int nf_stride) {
   if (ntiles <= 0) return;
-  if (variant == 4) launch_conv_split16_g<0>(tiles, ntiles, levels, feat_split, wS, resp, nf, kh, kw, oscale, 5, s);
+  if (nf_stride > 0) launch_conv_split16_g<2, true>(tiles, ntiles, levels, feat_split, wS, resp, nf, kh, kw, oscale, 5, s, nf_stride);   // a size group of a mixed bank: the default form
+  else if (variant == 4) launch_conv_split16_g<0>(tiles, ntiles, levels, feat_split, wS, resp, nf, kh, kw, oscale, 5, s);
   else launch_conv_split16_g<2>(tiles, ntiles, levels, feat_split, wS, resp, nf, kh, kw, oscale, variant == 7 ? 4 : variant == 8 ? 3 : 5, s);
 }
-template <int NW, int PIN>
+template <int NW, int PIN, bool MIX = false>
 static void launch_conv_split_nw(const ConvTile* tiles, int ntiles, const LevelDev* levels, const uint16_t* feat_split, const uint16_t* wS,
-                                 float* resp, int nf, int kh, int kw, hipStream_t s, int G = 5) {
+                                 float* resp, int nf, int kh, int kw, hipStream_t s, int G = 5, int nf_stride = 0) {
   // groups of G = five n-tiles (160 filters: the person bank's 156 in one pass), then the remainder with its own instantiation
   // (G = 4 / 3: tuning variants — fewer accumulators per wavefront, two wavefronts per SIMD, every tile staged once per group)
   // (banks of more than 160 filters: balanced groups — 208 filters as 4 + 3 n-tiles instead of 5 + 2 — measured the same, 0.300 vs 0.302 ms per frame: what a
@@ -642,11 +649,11 @@ static void launch_conv_split_nw(const ConvTile* tiles, int ntiles, const LevelD
   const int full = ntl / G, rest = ntl - G * full;
   auto go = [&](int nt, int ntile0, int ngroups) {
     switch (nt) {
-      case 1: launch_conv_split_t<1, NW, PIN>(tiles, ntiles, levels, feat_split, wS, resp, nf, ntl, ntile0, ngroups, kh, kw, s); break;
-      case 2: launch_conv_split_t<2, NW, PIN>(tiles, ntiles, levels, feat_split, wS, resp, nf, ntl, ntile0, ngroups, kh, kw, s); break;
-      case 3: launch_conv_split_t<3, NW, PIN>(tiles, ntiles, levels, feat_split, wS, resp, nf, ntl, ntile0, ngroups, kh, kw, s); break;
-      case 4: launch_conv_split_t<4, NW, PIN>(tiles, ntiles, levels, feat_split, wS, resp, nf, ntl, ntile0, ngroups, kh, kw, s); break;
-      case 5: launch_conv_split_t<5, NW, PIN>(tiles, ntiles, levels, feat_split, wS, resp, nf, ntl, ntile0, ngroups, kh, kw, s); break;
+      case 1: launch_conv_split_t<1, NW, PIN, 3, MIX>(tiles, ntiles, levels, feat_split, wS, resp, nf, ntl, ntile0, ngroups, kh, kw, s, nullptr, nf_stride); break;
+      case 2: launch_conv_split_t<2, NW, PIN, 3, MIX>(tiles, ntiles, levels, feat_split, wS, resp, nf, ntl, ntile0, ngroups, kh, kw, s, nullptr, nf_stride); break;
+      case 3: launch_conv_split_t<3, NW, PIN, 3, MIX>(tiles, ntiles, levels, feat_split, wS, resp, nf, ntl, ntile0, ngroups, kh, kw, s, nullptr, nf_stride); break;
+      case 4: launch_conv_split_t<4, NW, PIN, 3, MIX>(tiles, ntiles, levels, feat_split, wS, resp, nf, ntl, ntile0, ngroups, kh, kw, s, nullptr, nf_stride); break;
+      case 5: launch_conv_split_t<5, NW, PIN, 3, MIX>(tiles, ntiles, levels, feat_split, wS, resp, nf, ntl, ntile0, ngroups, kh, kw, s, nullptr, nf_stride); break;
       default: break;
     }
   };
@@ -663,9 +670,10 @@ static void launch_conv_split_nw(const ConvTile* tiles, int ntiles, const LevelD
 // (tests/tools/mfma_valu_overlap_probe.hip: 0.5-0.75 of the shorter one hidden; fp32 FMAs: none).
 // variant (tuning builds, PBD_SPLIT_VARIANT): 1 = loads as a block, 2 / 3 = the two-wavefront forms of 0 / 1, 4 / 5 = hipcc's schedule (4 / 2 wavefronts)
 void launch_conv_split(const ConvTile* tiles, int ntiles, const LevelDev* levels, const uint16_t* feat_split, const uint16_t* wS,
-                       float* resp, int nf, int kh, int kw, int variant, hipStream_t s) {
+                       float* resp, int nf, int kh, int kw, int variant, hipStream_t s, int nf_stride) {
   if (ntiles <= 0) return;
-  if (variant == 1) launch_conv_split_nw<4, 1>(tiles, ntiles, levels, feat_split, wS, resp, nf, kh, kw, s);
+  if (nf_stride > 0) launch_conv_split_nw<4, 2, true>(tiles, ntiles, levels, feat_split, wS, resp, nf, kh, kw, s, 5, nf_stride);   // a size group of a mixed bank: the default form
+  else if (variant == 1) launch_conv_split_nw<4, 1>(tiles, ntiles, levels, feat_split, wS, resp, nf, kh, kw, s);
   else if (variant == 2) launch_conv_split_nw<2, 2>(tiles, ntiles, levels, feat_split, wS, resp, nf, kh, kw, s);
   else if (variant == 3) launch_conv_split_nw<2, 1>(tiles, ntiles, levels, feat_split, wS, resp, nf, kh, kw, s);
   else if (variant == 4) launch_conv_split_nw<4, 0>(tiles, ntiles, levels, feat_split, wS, resp, nf, kh, kw, s);

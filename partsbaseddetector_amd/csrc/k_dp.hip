@@ -804,7 +804,7 @@ template <typename T>
 __global__ __launch_bounds__(64) void k_backtrack(const int* __restrict__ count, const CandRec* __restrict__ rec,
                                                   int capacity, const BackLevel* __restrict__ back, int ncomp,
                                                   const int* __restrict__ parent, const int* __restrict__ plane0,
-                                                  const int* __restrict__ nparts, int max_parts, int kh,
+                                                  const int* __restrict__ nparts, int max_parts, const int* __restrict__ mix_rows,
                                                   char* __restrict__ out, size_t out_stride,
                                                   const int* __restrict__ flat, const int* __restrict__ depth, int max_depth,
                                                   int nflat, const unsigned long long* __restrict__ scr_base,
@@ -859,9 +859,12 @@ __global__ __launch_bounds__(64) void k_backtrack(const int* __restrict__ count,
     __syncthreads();
   }
   const T scale = B.scale;                             // `T scale = scales[n]` (:198): Point * T rounds with cvRound
-  const int sz = t_round((T)kh * scale);               // Point(xsize,ysize)*scale
   for (int p = lane; p < max_parts; p += 64) {
     if (p < np) {
+      // Point(xsize, ysize) * scale (src/DynamicProgram.cpp:238-240) with the size of the filter of the mixture the part chose
+      // (mix_rows: [flat part][mixture] rows of that filter).  The reference's quirk is kept: xsize() AND ysize() both return
+      // the filter's .rows (include/Parts.hpp:185-187), so a box is rows x rows scaled even for a filter with cols != rows.
+      const int sz = t_round((T)mix_rows[flat[r.comp * max_parts + p] * PBD_MAX_MIX + (lm[p] & (PBD_MAX_MIX - 1))] * scale);   // (mask: tables handed in by a caller stay inside the row)
       const int x = lx[p], y = ly[p];
       locs[p * 3] = x; locs[p * 3 + 1] = y; locs[p * 3 + 2] = lm[p];
       const int x1 = t_round((T)(x - 1) * scale), y1 = t_round((T)(y - 1) * scale);
@@ -877,13 +880,13 @@ __global__ __launch_bounds__(64) void k_backtrack(const int* __restrict__ count,
 }
 
 void launch_backtrack(const int* count, const CandRec* rec, int capacity, const BackLevel* back, int ncomp,
-                      const int* parent, const int* plane0, const int* nparts, int max_parts, int kh, char* out,
+                      const int* parent, const int* plane0, const int* nparts, int max_parts, const int* mix_rows, char* out,
                       size_t out_stride, int ts, const int* flat, const int* depth, int max_depth, int nflat,
                       const unsigned long long* scr_base, const int16_t* ix, const int16_t* iy, int correct_ptr,
                       const int16_t* extx, const int16_t* exty, const unsigned long long* ext_base, int* count_out, hipStream_t s) {
   const int nblk = std::min(capacity, 2048);   // 8 blocks of one wavefront per CU; more candidates than that are taken in further sweeps
-  if (ts == 8) hipLaunchKernelGGL(k_backtrack<double>, dim3(nblk), dim3(64), 0, s, count, rec, capacity, back, ncomp, parent, plane0, nparts, max_parts, kh, out, out_stride, flat, depth, max_depth, nflat, scr_base, ix, iy, correct_ptr, extx, exty, ext_base, count_out);
-  else hipLaunchKernelGGL(k_backtrack<float>, dim3(nblk), dim3(64), 0, s, count, rec, capacity, back, ncomp, parent, plane0, nparts, max_parts, kh, out, out_stride, flat, depth, max_depth, nflat, scr_base, ix, iy, correct_ptr, extx, exty, ext_base, count_out);
+  if (ts == 8) hipLaunchKernelGGL(k_backtrack<double>, dim3(nblk), dim3(64), 0, s, count, rec, capacity, back, ncomp, parent, plane0, nparts, max_parts, mix_rows, out, out_stride, flat, depth, max_depth, nflat, scr_base, ix, iy, correct_ptr, extx, exty, ext_base, count_out);
+  else hipLaunchKernelGGL(k_backtrack<float>, dim3(nblk), dim3(64), 0, s, count, rec, capacity, back, ncomp, parent, plane0, nparts, max_parts, mix_rows, out, out_stride, flat, depth, max_depth, nflat, scr_base, ix, iy, correct_ptr, extx, exty, ext_base, count_out);
 }
 
 // ---------------------------------------------------------------------------

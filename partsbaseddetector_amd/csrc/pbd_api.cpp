@@ -90,7 +90,7 @@ static int ingest_model(pbd_handle* h, const pbd_model_desc* m) {
     return fail(h, PBD_ERR_ARG, "model: null pointer");
   if (m->flen != PBD_FLEN || m->norient != PBD_NORIENT)
     return fail(h, PBD_ERR_UNSUPPORTED, "model: only flen=32 / norient=18 HOG is supported");
-  if (m->nfilters <= 0 || m->kh <= 0 || m->kw <= 0 || m->kh > 9 || m->kw > 9 || m->sbin <= 0 || m->interval <= 0 ||
+  if (m->nfilters <= 0 || (!h->mixed && (m->kh <= 0 || m->kw <= 0 || m->kh > 9 || m->kw > 9)) || m->sbin <= 0 || m->interval <= 0 ||
       m->interval > 16 || m->ncomponents <= 0)
     return fail(h, PBD_ERR_ARG, "model: bad sizes");
   if (m->ndefs < 0 || m->nbias <= 0) return fail(h, PBD_ERR_ARG, "model: ndefs >= 0 and nbias > 0 required");
@@ -109,7 +109,12 @@ static int ingest_model(pbd_handle* h, const pbd_model_desc* m) {
   h->filterid.assign(m->filterid, m->filterid + nm);
   h->defid.assign(m->defid, m->defid + nm);
   h->biasid.assign(m->biasid, m->biasid + nm);
-  h->filters.assign(m->filters, m->filters + (size_t)m->nfilters * m->kh * m->kw * m->flen);
+  size_t nweights = (size_t)m->nfilters * m->kh * m->kw * m->flen;   // mixed banks (pbd_create_sized): sum of kh_i kw_i flen
+  if (h->mixed) {
+    nweights = 0;
+    for (int n = 0; n < m->nfilters; ++n) nweights += (size_t)h->fkh[n] * h->fkw[n] * m->flen;
+  }
+  h->filters.assign(m->filters, m->filters + nweights);
   h->defw.assign(m->defw, m->defw + (size_t)m->ndefs * 4);
   h->anchors.assign(m->anchors, m->anchors + (size_t)m->ndefs * 2);
   h->biasw.assign(m->biasw, m->biasw + m->nbias);
@@ -257,65 +262,98 @@ static int ingest_model(pbd_handle* h, const pbd_model_desc* m) {
   return PBD_OK;
 }
 
-static int upload_model(pbd_handle* h) {
+// The weights of one bank of nf filters of ONE size (the whole model, or one size group of a mixed bank) in every layout the filter-bank
+// kernels read: g.nfpad, g.d_wT (transposed, converted to T, the 16-byte B copies and the border cell), and for a split bank g.d_wS /
+// g.d_oscale.  *bytes: device bytes held.
+static int upload_bank(pbd_handle* h, const float* filt, int nf, int kh, int kw, SizeGroup& g, size_t* bytes) {
   const pbd_model_desc& m = h->md;
+  g.kh = kh; g.kw = kw; g.nf = nf;
   // filters transposed to [tap][c][nfpad] (n contiguous): scalar loads in the VALU kernel,
   // B-operand rows in the MFMA kernel.  nfpad is a multiple of 160 (5 x 32-wide MFMA n-tiles).
-  h->nfpad = ((m.nfilters + 159) / 160) * 160;
+  g.nfpad = ((nf + 159) / 160) * 160;
   // + one trailing border cell (0, and 1 in the truncation channel flen - 1): the source the persistent filter-bank kernel
   // streams out-of-level cells from (src/SpatialConvolutionEngine.cpp:147-155)
-  const size_t wt_n = (size_t)m.kh * m.kw * m.flen * h->nfpad;
+  const size_t wt_n = (size_t)kh * kw * m.flen * g.nfpad;
   std::vector<float> wT(3 * wt_n + m.flen, 0.f);
   wT[wt_n + m.flen - 1] = 1.f;
   // ... and the same filters once more as [tap][16-channel half][k = 0..3][nfpad][s = 0..3] = channel 16 half + 4 k + s: the lane
   // (k, filter) of the persistent kernel's B operand reads its four k-steps of a tap with ONE 16-byte load (eight
   // global_load_dword per 32 MFMAs cost the MFMA pipe a quarter of its rate: tests/tools/mfma_rate_probe.hip)
   if (m.flen == PBD_FLEN)
-    for (int n = 0; n < m.nfilters; ++n)
-      for (int tap = 0; tap < m.kh * m.kw; ++tap)
+    for (int n = 0; n < nf; ++n)
+      for (int tap = 0; tap < kh * kw; ++tap)
         for (int c = 0; c < m.flen; ++c)
         {
-          const float w = h->filters[((size_t)n * m.kh * m.kw + tap) * m.flen + c];
-          wT[wt_n + m.flen + ((((size_t)tap * 2 + c / 16) * 4 + (c % 16) / 4) * h->nfpad + n) * 4 + c % 4] = w;     // k = (c % 16) / 4, s = c % 4
+          const float w = filt[((size_t)n * kh * kw + tap) * m.flen + c];
+          wT[wt_n + m.flen + ((((size_t)tap * 2 + c / 16) * 4 + (c % 16) / 4) * g.nfpad + n) * 4 + c % 4] = w;     // k = (c % 16) / 4, s = c % 4
           // third copy, [tap][half][k][nfpad][u] with channel = 16 half + 4 u + k: the B operand of k_conv_mfma16<.., B4>
-          wT[2 * wt_n + m.flen + ((((size_t)tap * 2 + c / 16) * 4 + c % 4) * h->nfpad + n) * 4 + (c % 16) / 4] = w;
+          wT[2 * wt_n + m.flen + ((((size_t)tap * 2 + c / 16) * 4 + c % 4) * g.nfpad + n) * 4 + (c % 16) / 4] = w;
         }
-  for (int n = 0; n < m.nfilters; ++n)
-    for (int i = 0; i < m.kh; ++i)
-      for (int j = 0; j < m.kw; ++j)
+  for (int n = 0; n < nf; ++n)
+    for (int i = 0; i < kh; ++i)
+      for (int j = 0; j < kw; ++j)
         for (int c = 0; c < m.flen; ++c)
-          wT[((size_t)(i * m.kw + j) * m.flen + c) * h->nfpad + n] =
-              h->filters[(((size_t)n * m.kh + i) * m.kw + j) * m.flen + c];
-  HIPCHK(h, hipMalloc(&h->d_wT, wT.size() * h->ts));
+          wT[((size_t)(i * kw + j) * m.flen + c) * g.nfpad + n] =
+              filt[(((size_t)n * kh + i) * kw + j) * m.flen + c];
+  HIPCHK(h, hipMalloc(&g.d_wT, wT.size() * h->ts));
   if (h->ts == 8) {   // filters convertTo(DataType<double>), src/PartsBasedDetector.cpp:113-117 (exact widening)
     std::vector<double> wd(wT.begin(), wT.end());
     // the double filter bank's 16-byte B layout replaces the (unused) float copy behind the border cell:
     // [tap][8-channel group][k][nfpad][u = 0, 1], channel = 8 group + 4 u + k (k_conv_mfma16<double, 4, .., B4>)
     if (m.flen == PBD_FLEN)
-      for (int n = 0; n < m.nfilters; ++n)
-        for (int tap = 0; tap < m.kh * m.kw; ++tap)
+      for (int n = 0; n < nf; ++n)
+        for (int tap = 0; tap < kh * kw; ++tap)
           for (int c = 0; c < m.flen; ++c)
-            wd[wt_n + m.flen + ((((size_t)tap * 4 + c / 8) * 4 + c % 4) * h->nfpad + n) * 2 + (c % 8) / 4] =
-                (double)h->filters[((size_t)n * m.kh * m.kw + tap) * m.flen + c];
-    HIPCHK(h, hipMemcpy(h->d_wT, wd.data(), wd.size() * sizeof(double), hipMemcpyHostToDevice));
+            wd[wt_n + m.flen + ((((size_t)tap * 4 + c / 8) * 4 + c % 4) * g.nfpad + n) * 2 + (c % 8) / 4] =
+                (double)filt[((size_t)n * kh * kw + tap) * m.flen + c];
+    HIPCHK(h, hipMemcpy(g.d_wT, wd.data(), wd.size() * sizeof(double), hipMemcpyHostToDevice));
   } else {
-    HIPCHK(h, hipMemcpy(h->d_wT, wT.data(), wT.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(g.d_wT, wT.data(), wT.size() * sizeof(float), hipMemcpyHostToDevice));
   }
   size_t split_bytes = 0;
-  h->split_parts = h->conv_mode == PBD_CONV_SPLIT ? 3 : h->conv_mode == PBD_CONV_SPLIT_F16 ? 2 : 0;
   if (h->split_parts) {   // the three exact bfloat16 parts of every weight (or two binary16 parts of the scaled weight), in the MFMA operand order of k_conv_split32
     std::vector<uint16_t> wS;
-    if (h->split_parts == 3) conv_split_filters(h->filters.data(), m.nfilters, m.kh, m.kw, wS);
+    if (h->split_parts == 3) conv_split_filters(filt, nf, kh, kw, wS);
     else {
       std::vector<float> osc;
-      conv_split16_filters(h->filters.data(), m.nfilters, m.kh, m.kw, wS, osc);
-      HIPCHK(h, hipMalloc((void**)&h->d_split_oscale, osc.size() * sizeof(float)));
-      HIPCHK(h, hipMemcpy(h->d_split_oscale, osc.data(), osc.size() * sizeof(float), hipMemcpyHostToDevice));
+      conv_split16_filters(filt, nf, kh, kw, wS, osc);
+      HIPCHK(h, hipMalloc((void**)&g.d_oscale, osc.size() * sizeof(float)));
+      HIPCHK(h, hipMemcpy(g.d_oscale, osc.data(), osc.size() * sizeof(float), hipMemcpyHostToDevice));
       split_bytes += osc.size() * sizeof(float);
     }
     split_bytes += wS.size() * sizeof(uint16_t);
-    HIPCHK(h, hipMalloc((void**)&h->d_wS, wS.size() * sizeof(uint16_t)));
-    HIPCHK(h, hipMemcpy(h->d_wS, wS.data(), wS.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMalloc((void**)&g.d_wS, wS.size() * sizeof(uint16_t)));
+    HIPCHK(h, hipMemcpy(g.d_wS, wS.data(), wS.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+  }
+  *bytes = wT.size() * h->ts + split_bytes;
+  return PBD_OK;
+}
+
+static int upload_model(pbd_handle* h) {
+  const pbd_model_desc& m = h->md;
+  size_t bank_bytes = 0;
+  h->split_parts = h->conv_mode == PBD_CONV_SPLIT ? 3 : h->conv_mode == PBD_CONV_SPLIT_F16 ? 2 : 0;
+  if (!h->mixed) {
+    SizeGroup g;
+    int rc = upload_bank(h, h->filters.data(), m.nfilters, m.kh, m.kw, g, &bank_bytes);
+    h->d_wT = g.d_wT; h->d_wS = g.d_wS; h->d_split_oscale = g.d_oscale; h->nfpad = g.nfpad;
+    if (rc) return rc;
+  } else {
+    // size groups: runs of one kh x kw in the internal (size-sorted) filter order, each uploaded as a uniform bank of its own
+    size_t off = 0;
+    for (int n = 0; n < m.nfilters;) {
+      int e = n;
+      while (e < m.nfilters && h->fkh[e] == h->fkh[n] && h->fkw[e] == h->fkw[n]) ++e;
+      h->groups.emplace_back();
+      SizeGroup& g = h->groups.back();
+      g.n0 = n;
+      size_t b = 0;
+      int rc = upload_bank(h, h->filters.data() + off, e - n, h->fkh[n], h->fkw[n], g, &b);
+      if (rc) return rc;
+      bank_bytes += b;
+      off += (size_t)(e - n) * h->fkh[n] * h->fkw[n] * m.flen;
+      n = e;
+    }
   }
   // orientation-snap table of the HOG kernel (k_hog.hip): 511 x 511 bytes, computed on the device by the reference's own
   // comparison chain in T
@@ -352,6 +390,15 @@ static int upload_model(pbd_handle* h) {
   HIPCHK(h, hipMemcpy(h->d_parent, par.data(), par.size() * sizeof(int), hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->d_plane0, pl0.data(), pl0.size() * sizeof(int), hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->d_nparts, npv.data(), npv.size() * sizeof(int), hipMemcpyHostToDevice));
+  // rows of the filter of every (flat part, mixture): the box size of back-tracking (entries beyond a part's K repeat its last mixture)
+  std::vector<int> mix_rows(h->parts.size() * PBD_MAX_MIX, 0);
+  for (size_t fp = 0; fp < h->parts.size(); ++fp)
+    for (int k = 0; k < PBD_MAX_MIX; ++k) {
+      const int fid = h->parts[fp].filterid[std::min(k, h->parts[fp].K - 1)];
+      mix_rows[fp * PBD_MAX_MIX + k] = h->mixed ? h->fkh[fid] : m.kh;
+    }
+  HIPCHK(h, hipMalloc(&h->d_mix_rows, mix_rows.size() * sizeof(int)));
+  HIPCHK(h, hipMemcpy(h->d_mix_rows, mix_rows.data(), mix_rows.size() * sizeof(int), hipMemcpyHostToDevice));
   // candidates
   const int cap = h->opt.max_candidates;
   h->cand_stride = sizeof(pbd_candidate_head) + (size_t)mp * 28;
@@ -360,8 +407,8 @@ static int upload_model(pbd_handle* h) {
   HIPCHK(h, hipMalloc(&h->d_cand_out, h->cand_stride * cap));
   HIPCHK(h, hipHostMalloc((void**)&h->h_cand_out, h->cand_stride * cap));
   HIPCHK(h, hipHostMalloc((void**)&h->h_cand_count, sizeof(int) * 4));
-  h->model_bytes = wT.size() * h->ts + hog_binlut_bytes() + bw.size() * sizeof(float) + (par.size() * 4 + npv.size()) * sizeof(int) + sizeof(int) +
-                   sizeof(CandRec) * cap + h->cand_stride * cap + split_bytes;
+  h->model_bytes = bank_bytes + hog_binlut_bytes() + bw.size() * sizeof(float) + (par.size() * 4 + npv.size()) * sizeof(int) + sizeof(int) +
+                   sizeof(CandRec) * cap + h->cand_stride * cap + mix_rows.size() * sizeof(int);
   return PBD_OK;
 }
 
@@ -638,6 +685,13 @@ static int plan_frame(pbd_handle* h, int w, int hgt, int cn, int batch = 1, int 
   h->n_conv_tiles = (int)ct.size();
   if ((rc = dev_upload(h, &h->d_hog_tiles, ht))) return rc;
   if ((rc = dev_upload(h, &h->d_conv_tiles, ct))) return rc;
+  if (h->mixed) {   // one copy of the list per size group, the group's planes in the tiles' pad (ConvTile)
+    std::vector<ConvTile> cm;
+    cm.reserve(ct.size() * h->groups.size());
+    for (const SizeGroup& g : h->groups)
+      for (ConvTile t : ct) { t.pad = g.n0 | (g.nf << 16); cm.push_back(t); }
+    if ((rc = dev_upload(h, &h->d_conv_tiles_mix, cm))) return rc;
+  }
 
   // ---- DP tables ---------------------------------------------------------------
   size_t act_cells = 0;
@@ -1042,8 +1096,41 @@ static int run_hog(pbd_handle* h) {
   return PBD_OK;
 }
 
+// A mixed bank: each size group runs the kernel a uniform bank of its size and the handle's mode runs (the run-time-size
+// instantiation, MIX: writing planes n0 .. n0 + nf_g - 1 of every level block of md.nfilters planes), one launch per group.
+static int run_pdf_mixed(pbd_handle* h) {
+  const pbd_model_desc& m = h->md;
+  if (h->split_parts && !h->feat_split_ok) {
+    if (h->split_parts == 2) launch_feat_split16((const float*)h->d_feat, h->d_feat_split, h->cells, h->stream);
+    else launch_feat_split((const float*)h->d_feat, h->d_feat_split, h->cells, h->stream);
+    h->feat_split_ok = true;
+  }
+  for (size_t gi = 0; gi < h->groups.size(); ++gi) {
+    const SizeGroup& g = h->groups[gi];
+    const ConvTile* tiles = h->d_conv_tiles_mix + gi * h->n_conv_tiles;
+    const size_t wt_n = (size_t)g.kh * g.kw * m.flen * g.nfpad;
+    if (h->conv_mode == PBD_CONV_SPLIT_F16)
+      launch_conv_split16(tiles, h->n_conv_tiles, h->d_levels, h->d_feat_split, g.d_wS, (float*)h->d_resp, g.nf, g.kh, g.kw, g.d_oscale, 0, h->stream, m.nfilters);
+    else if (h->conv_mode == PBD_CONV_SPLIT)
+      launch_conv_split(tiles, h->n_conv_tiles, h->d_levels, h->d_feat_split, g.d_wS, (float*)h->d_resp, g.nf, g.kh, g.kw, 0, h->stream, m.nfilters);
+    else if (h->conv_mode == PBD_CONV_MFMA && h->ts == 8)
+      launch_conv_mfma_f64(tiles, h->n_conv_tiles, h->d_levels, (const double*)h->d_feat, (const double*)g.d_wT, (const double*)g.d_wT + wt_n + m.flen,
+                           (double*)h->d_resp, g.nf, g.nfpad, g.kh, g.kw, h->stream, m.nfilters);
+    else if (h->conv_mode == PBD_CONV_MFMA)
+      launch_conv_mfma16_f32(tiles, h->n_conv_tiles, h->d_levels, (const float*)h->d_feat, (const float*)g.d_wT,
+                             (const float*)g.d_wT + 2 * wt_n + m.flen, (float*)h->d_resp, g.nf, g.nfpad, 20, h->stream, g.kh, g.kw, m.nfilters);
+    else
+      launch_conv_exact(tiles, h->n_conv_tiles, h->d_levels, h->d_feat, g.d_wT, h->d_resp, h->ts, g.nf, g.nfpad, g.kh, g.kw, h->stream, m.nfilters);
+  }
+  LAUNCHCHK(h, "filter bank");
+  h->have_resp = true;
+  compact_mark_resp(h, true);
+  return PBD_OK;
+}
+
 static int run_pdf(pbd_handle* h) {
   const pbd_model_desc& m = h->md;
+  if (h->mixed) return run_pdf_mixed(h);
   if (h->conv_mode == PBD_CONV_SPLIT_F16) {
     if (!h->feat_split_ok) {
       launch_feat_split16((const float*)h->d_feat, h->d_feat_split, h->cells, h->stream);
@@ -1159,7 +1246,7 @@ static int run_argmin_enqueue(pbd_handle* h) {
   // records beyond a first block.  Group members keep the device buffer: the all-gather reads it.
   const bool zero_copy = PBD_ARGMIN_ZERO_COPY && !h->d_gsend;
   launch_backtrack(h->d_cand_count, h->d_cand_rec, h->opt.max_candidates, h->d_back, h->md.ncomponents, h->d_parent,
-                   h->d_plane0, h->d_nparts, h->max_parts, h->md.kh, zero_copy ? h->h_cand_out : h->d_cand_out, h->cand_stride, h->ts, h->d_flat,
+                   h->d_plane0, h->d_nparts, h->max_parts, h->d_mix_rows, zero_copy ? h->h_cand_out : h->d_cand_out, h->cand_stride, h->ts, h->d_flat,
                    h->d_depth, h->max_depth, (int)h->parts.size(), h->d_scr_base, h->d_dt_ixT, h->d_dt_iy,
                    h->opt.dt_correct_ptr, h->ext_ptr ? h->d_extx : nullptr, h->d_exty, h->d_ext_base, zero_copy ? h->h_cand_count : nullptr, h->stream);
   LAUNCHCHK(h, "argmin");
@@ -1326,7 +1413,9 @@ static void read_stage_times(pbd_handle* h) {
 #pragma GCC visibility push(default)
 extern "C" {
 
-int pbd_create(const pbd_model_desc* model, const pbd_options* opt, pbd_handle** out) {
+// pbd_create / pbd_create_sized.  fsize != null: a size per filter (fsize[n] = {kh, kw}); all equal -> exactly the uniform handle,
+// else a mixed bank (pbd_handle::mixed): the filters stably sorted by (kh, kw) into size groups, filter ids remapped to that order.
+static int create_impl(const pbd_model_desc* model, const int32_t* fsize, const pbd_options* opt, pbd_handle** out, bool sized) {
   if (!out) return PBD_ERR_ARG;
   *out = nullptr;
   pbd_handle* h = new (std::nothrow) pbd_handle();
@@ -1338,8 +1427,49 @@ int pbd_create(const pbd_model_desc* model, const pbd_options* opt, pbd_handle**
   h->opt = o;
   if (o.scalar_type != PBD_SCALAR_F32 && o.scalar_type != PBD_SCALAR_F64) return fail(h, PBD_ERR_ARG, "scalar_type: PBD_SCALAR_F32 or PBD_SCALAR_F64");
   h->ts = (o.scalar_type == PBD_SCALAR_F64) ? 8 : 4;
+  pbd_model_desc sdesc;
+  std::vector<float> sorted;
+  if (sized && !fsize) return fail(h, PBD_ERR_ARG, "pbd_create_sized: fsize is null");
+  if (sized) {
+    if (!model || !model->filters) return fail(h, PBD_ERR_ARG, "model: null pointer");
+    if (model->kh != 0 || model->kw != 0) return fail(h, PBD_ERR_ARG, "pbd_create_sized: model->kh / kw must be 0 (the sizes come from fsize)");
+    if (model->nfilters <= 0) return fail(h, PBD_ERR_ARG, "model: bad sizes");
+    if (model->flen != PBD_FLEN || model->norient != PBD_NORIENT)
+      return fail(h, PBD_ERR_UNSUPPORTED, "model: only flen=32 / norient=18 HOG is supported");
+    const int nf = model->nfilters;
+    for (int n = 0; n < nf; ++n)
+      if (fsize[2 * n] < 1 || fsize[2 * n] > 9 || fsize[2 * n + 1] < 1 || fsize[2 * n + 1] > 9)
+        return fail(h, PBD_ERR_UNSUPPORTED, "pbd_create_sized: filter " + std::to_string(n) + ": sides of 1..9 cells");
+    sdesc = *model;
+    bool uniform = true;
+    for (int n = 1; n < nf; ++n) uniform = uniform && fsize[2 * n] == fsize[0] && fsize[2 * n + 1] == fsize[1];
+    if (uniform) {
+      sdesc.kh = fsize[0]; sdesc.kw = fsize[1];
+    } else {
+      std::vector<int> ord(nf);
+      for (int n = 0; n < nf; ++n) ord[n] = n;
+      std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) {
+        return fsize[2 * a] != fsize[2 * b] ? fsize[2 * a] < fsize[2 * b] : fsize[2 * a + 1] < fsize[2 * b + 1]; });
+      std::vector<size_t> off(nf + 1, 0);
+      for (int n = 0; n < nf; ++n) off[n + 1] = off[n] + (size_t)fsize[2 * n] * fsize[2 * n + 1] * PBD_FLEN;
+      h->mixed = true;
+      h->fperm.assign(nf, 0);
+      for (int i = 0; i < nf; ++i) {
+        const int c = ord[i];
+        h->fperm[c] = i;
+        h->fkh.push_back(fsize[2 * c]); h->fkw.push_back(fsize[2 * c + 1]);
+        sorted.insert(sorted.end(), model->filters + off[c], model->filters + off[c + 1]);
+      }
+      sdesc.filters = sorted.data();
+    }
+    model = &sdesc;
+  }
   int rc = ingest_model(h, model);
   if (rc) return rc;
+  if (h->mixed) {   // filter ids (validated by ingest_model) into the size-sorted order
+    for (int& f : h->filterid) f = h->fperm[f];
+    for (PartInfo& P : h->parts) for (int& f : P.filterid) f = h->fperm[f];
+  }
   if (o.reserved[0] < 0 || o.reserved[0] > 1024) return fail(h, PBD_ERR_ARG, "reserved[0] (nms_sz): 0 = off, or the window of the score-map NMS");
   h->nms_sz = o.reserved[0];
   h->conv_mode = o.conv_mode;
@@ -1375,12 +1505,24 @@ int pbd_create(const pbd_model_desc* model, const pbd_options* opt, pbd_handle**
   return upload_model(h);
 }
 
+int pbd_create(const pbd_model_desc* model, const pbd_options* opt, pbd_handle** out) { return create_impl(model, nullptr, opt, out, false); }
+int pbd_create_sized(const pbd_model_desc* model, const int32_t* fsize, const pbd_options* opt, pbd_handle** out) {
+  return create_impl(model, fsize, opt, out, true);
+}
+int pbd_get_filter_size(const pbd_handle* h, int filter, int32_t* kh, int32_t* kw) {
+  if (!h || !kh || !kw || filter < 0 || filter >= h->md.nfilters) return PBD_ERR_ARG;
+  if (h->mixed) { *kh = h->fkh[h->fperm[filter]]; *kw = h->fkw[h->fperm[filter]]; }
+  else { *kh = h->md.kh; *kw = h->md.kw; }
+  return PBD_OK;
+}
+
 int pbd_destroy(pbd_handle* h) {
   if (!h) return PBD_ERR_ARG;
   if (h->stream) hipStreamSynchronize(h->stream);
   free_frame(h);
   hipFree(h->d_wT); hipFree(h->d_wS); hipFree(h->d_split_oscale); hipFree(h->d_biasw); hipFree(h->d_hog_lut); hipFree(h->d_parent); hipFree(h->d_plane0); hipFree(h->d_nparts);
-  hipFree(h->d_flat); hipFree(h->d_depth);
+  hipFree(h->d_flat); hipFree(h->d_depth); hipFree(h->d_mix_rows);
+  for (SizeGroup& g : h->groups) { hipFree(g.d_wT); hipFree(g.d_wS); hipFree(g.d_oscale); }
   hipFree(h->d_cand_count); hipFree(h->d_cand_rec); hipFree(h->d_cand_out);
   if (h->h_cand_out) hipHostFree(h->h_cand_out);
   if (h->h_cand_count) hipHostFree(h->h_cand_count);
@@ -1759,6 +1901,7 @@ static int get_level_response_(pbd_handle* h, int level, int filter, void* out, 
   CHECK_SCALAR(h, ts);
   if (!h->have_resp) return fail(h, PBD_ERR_STATE, "responses not computed");
   if (filter < 0 || filter >= h->md.nfilters) return fail(h, PBD_ERR_ARG, "filter out of range");
+  if (!h->fperm.empty()) filter = h->fperm[filter];   // mixed bank: the caller's filter -> its plane in the size-sorted order
   const Level& L = h->lv[level];
   if (!L.active) return fail(h, PBD_ERR_STATE, "level is not processed by this handle (pbd_set_levels / level_begin..level_end)");
   const size_t HW = (size_t)L.cw * L.ch;
@@ -1771,6 +1914,7 @@ static int set_level_response_(pbd_handle* h, int level, int filter, const void*
   CHECK_LEVEL(h, level);
   CHECK_SCALAR(h, ts);
   if (filter < 0 || filter >= h->md.nfilters) return fail(h, PBD_ERR_ARG, "filter out of range");
+  if (!h->fperm.empty()) filter = h->fperm[filter];
   const Level& L = h->lv[level];
   const size_t HW = (size_t)L.cw * L.ch;
   ON_DEVICE(h);
@@ -2219,8 +2363,10 @@ int pbd_get_work(const pbd_handle* h, double work[6]) {
     per_cell += ts * h->parts[p0].K + ts + 4;
   }
   work[0] = pix + 32.0 * ts * C;
-  work[1] = 32.0 * ts * C + ts * m.nfilters * C + ts * m.nfilters * m.kh * m.kw * m.flen;
-  work[2] = 2.0 * C * m.nfilters * m.kh * m.kw * m.flen;
+  double taps = (double)m.nfilters * m.kh * m.kw;   // sum over the filters of kh_i kw_i (mixed banks: per filter)
+  if (h->mixed) { taps = 0; for (int n = 0; n < m.nfilters; ++n) taps += (double)h->fkh[n] * h->fkw[n]; }
+  work[1] = 32.0 * ts * C + ts * m.nfilters * C + ts * taps * m.flen;
+  work[2] = 2.0 * C * taps * m.flen;
   work[3] = C * per_cell;
   work[4] = C;
   work[5] = C * dtmaps;

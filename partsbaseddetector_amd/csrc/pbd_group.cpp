@@ -154,8 +154,19 @@ static int frame_impl(pbd_group* g, const uint8_t* im, int w, int hgt, int cn, i
 #pragma GCC visibility push(default)
 extern "C" {
 
+static int group_create(const pbd_model_desc* model, const int32_t* fsize, bool sized, const pbd_options* opt, const int32_t* devices, int ndev,
+                        int gather_mode, pbd_group** out);
 int pbd_group_create(const pbd_model_desc* model, const pbd_options* opt, const int32_t* devices, int ndev, int gather_mode,
                      pbd_group** out) {
+  return group_create(model, nullptr, false, opt, devices, ndev, gather_mode, out);
+}
+// pbd_create_sized's members (a size per filter)
+int pbd_group_create_sized(const pbd_model_desc* model, const int32_t* fsize, const pbd_options* opt, const int32_t* devices, int ndev,
+                           int gather_mode, pbd_group** out) {
+  return group_create(model, fsize, true, opt, devices, ndev, gather_mode, out);
+}
+static int group_create(const pbd_model_desc* model, const int32_t* fsize, bool sized, const pbd_options* opt, const int32_t* devices, int ndev,
+                        int gather_mode, pbd_group** out) {
   if (!out) return PBD_ERR_ARG;
   *out = nullptr;
   pbd_group* g = new (std::nothrow) pbd_group();
@@ -169,7 +180,7 @@ int pbd_group_create(const pbd_model_desc* model, const pbd_options* opt, const 
   for (int i = 0; i < ndev; ++i) {
     o.device = devices[i];
     pbd_handle* h = nullptr;
-    int rc = pbd_create(model, &o, &h);
+    int rc = sized ? pbd_create_sized(model, fsize, &o, &h) : pbd_create(model, &o, &h);
     if (rc != PBD_OK) {
       std::string msg = "member " + std::to_string(i) + " (device " + std::to_string(devices[i]) + "): " + pbd_last_error(h);
       if (h) pbd_destroy(h);

@@ -43,6 +43,9 @@ struct LevelDev {    // per level, device copy
   int iw, ih, bw, bh, cw, ch;
   unsigned long long img_off, cell_off;
 };
+// pad: 0 in a uniform bank's tile list.  Mixed banks (pbd_create_sized) keep one copy of the list per size group with
+// pad = n0 | (nf_g << 16): the group writes response planes n0 .. n0 + nf_g - 1 of the level's block (the MIX kernel
+// instantiations read it; their `nf` argument is then the level block's plane count, the whole bank's)
 struct ConvTile { int level, y0, x0, pad; };
 
 // Score data is T = float or double (the handle's instantiation, pbd_options.scalar_type); the work
@@ -151,6 +154,13 @@ struct PartInfo {
   bool leaf;
 };
 
+// one size group of a mixed bank: filters of one kh x kw, contiguous in the handle's internal filter order (planes n0 .. n0 + nf - 1);
+// its weights in the layouts a uniform bank of those filters has (nfpad, the wT copies, the split parts and scales)
+struct SizeGroup {
+  int kh = 0, kw = 0, n0 = 0, nf = 0, nfpad = 0;
+  void* d_wT = nullptr; uint16_t* d_wS = nullptr; float* d_oscale = nullptr;
+};
+
 struct pbd_handle {
   // model
   pbd_model_desc md;         // pointers into the vectors below
@@ -165,6 +175,13 @@ struct pbd_handle {
   std::vector<int> comp_plane0;
   std::string err;
   int conv_mode = PBD_CONV_EXACT;
+  // mixed banks (pbd_create_sized with more than one filter size): md.kh = md.kw = 0, the filters sorted by size internally
+  // (stable: size groups in order of (kh, kw)); filterid / filters / response planes are in the INTERNAL order, the stage entry
+  // points translate the caller's filter index with fperm
+  bool mixed = false;
+  std::vector<int> fkh, fkw;     // [internal filter] rows / cols
+  std::vector<int> fperm;        // [caller filter] -> internal filter (empty: identity)
+  std::vector<SizeGroup> groups;
 
   // device model
   int ts = 4;                // sizeof(T): 4 = PartsBasedDetector<float>, 8 = PartsBasedDetector<double>
@@ -176,6 +193,7 @@ struct pbd_handle {
   int* d_parent = nullptr;   // [ncomp][max_parts] parent of each part
   int* d_plane0 = nullptr;   // [ncomp][max_parts] local plane0 of each part
   int* d_nparts = nullptr;
+  int* d_mix_rows = nullptr; // [nflat parts][PBD_MAX_MIX] rows of the filter of each mixture (k_backtrack's box size)
 
   // frame plan
   int fw = 0, fh = 0, fcn = 0, nlevels = 0;     // nlevels: levels of ONE frame
@@ -220,6 +238,7 @@ struct pbd_handle {
   LevelDev* d_levels = nullptr;
   HogTile* d_hog_tiles = nullptr; int n_hog_tiles = 0; int hog_tc = 16;
   ConvTile* d_conv_tiles = nullptr; int n_conv_tiles = 0;
+  ConvTile* d_conv_tiles_mix = nullptr;   // mixed banks: [group][n_conv_tiles], pad = n0 | (nf_g << 16)
   // DP tables (all rounds back to back)
   DtMap* d_dtmaps = nullptr; DtTask* d_dttasks = nullptr;   // a task carries its group descriptor
   ReduceJob* d_redjobs = nullptr; ReduceBlock* d_redblocks = nullptr; RootJob* d_rootjobs = nullptr; BackLevel* d_back = nullptr;
@@ -337,7 +356,7 @@ void launch_hog_binlut(uint8_t* lut, int ts, hipStream_t s);      // evaluated i
 // split-product filter bank (k_conv_split.hip): fp32 features -> three exact bfloat16 parts; kh x kw x 32 filters, float responses
 void launch_feat_split(const float* feat, uint16_t* out, size_t ncells, hipStream_t s);
 void launch_conv_split(const ConvTile* tiles, int ntiles, const LevelDev* levels, const uint16_t* feat_split, const uint16_t* wS,
-                       float* resp, int nf, int kh, int kw, int variant, hipStream_t s);
+                       float* resp, int nf, int kh, int kw, int variant, hipStream_t s, int nf_stride = 0);
 void launch_conv_split_persistent(const ConvTile* tiles, int ntiles, const LevelDev* levels, const uint16_t* feat_split, const uint16_t* wS,
                                   float* resp, int nf, int ncu, hipStream_t s);   // 5 x 5 banks: persistent workgroups, staging hidden under the MFMAs (tuning variant, not adopted)
 void conv_split_filters(const float* filters, int nf, int kh, int kw, std::vector<uint16_t>& out);   // host: the d_wS layout
@@ -345,18 +364,18 @@ void conv_split_filters(const float* filters, int nf, int kh, int kw, std::vecto
 void launch_feat_split16(const float* feat, uint16_t* out, size_t ncells, hipStream_t s);
 void conv_split16_filters(const float* filters, int nf, int kh, int kw, std::vector<uint16_t>& out, std::vector<float>& oscale);   // oscale[filter]: the response scale
 void launch_conv_split16(const ConvTile* tiles, int ntiles, const LevelDev* levels, const uint16_t* feat_split, const uint16_t* wS,
-                         float* resp, int nf, int kh, int kw, const float* oscale, int variant, hipStream_t s);
+                         float* resp, int nf, int kh, int kw, const float* oscale, int variant, hipStream_t s, int nf_stride = 0);
 void launch_conv_exact(const ConvTile* tiles, int ntiles, const LevelDev* levels, const void* feat,
-                       const void* wT, void* resp, int ts, int nf, int nfpad, int kh, int kw, hipStream_t s);
+                       const void* wT, void* resp, int ts, int nf, int nfpad, int kh, int kw, hipStream_t s, int nf_stride = 0);
 void launch_conv_mfma(const ConvTile* tiles, int ntiles, const LevelDev* levels, const float* feat,
                       const float* wT, float* resp, int nf, int nfpad, int kh, int kw, hipStream_t s);
 void launch_conv_mfma_f64(const ConvTile* tiles, int ntiles, const LevelDev* levels, const double* feat,
-                          const double* wT, const double* w4u, double* resp, int nf, int nfpad, int kh, int kw, hipStream_t s);
+                          const double* wT, const double* w4u, double* resp, int nf, int nfpad, int kh, int kw, hipStream_t s, int nf_stride = 0);
 extern int g_conv_lds_req_kb;
 void launch_conv_glds_f32(const ConvTile* tiles, int ntiles, const LevelDev* levels, const float* feat, const float* wT,
                           float* resp, int nf, int nfpad, const float* border, int wg_per_cu, int ncu, hipStream_t s);
 void launch_conv_mfma16_f32(const ConvTile* tiles, int ntiles, const LevelDev* levels, const float* feat,
-                            const float* wT, const float* w4u, float* resp, int nf, int nfpad, int nhalf, hipStream_t s, int kh, int kw);
+                            const float* wT, const float* w4u, float* resp, int nf, int nfpad, int nhalf, hipStream_t s, int kh, int kw, int nf_stride = 0);
 void launch_dt_pass(const DtTask* tasks, int ntasks, const DtMap* maps, const FoldJob* folds, const unsigned long long* foldx, const float* biasw, size_t lds,
                     int ts, int nt, int fm, hipStream_t s);
 size_t dt_lds_bytes(int stride, int lpb, int ts, int nt);
@@ -367,7 +386,7 @@ void launch_root(const RootJob* jobs, const ReduceBlock* blocks, int nblocks, do
                  const char* rootv_base, hipStream_t s);
 void launch_nms_roots(const RootJob* jobs, int njobs, unsigned maxcells, const char* rootv_base, int ts, int sz, uint8_t* mask, hipStream_t s);
 void launch_backtrack(const int* count, const CandRec* rec, int capacity, const BackLevel* back, int ncomp,
-                      const int* parent, const int* plane0, const int* nparts, int max_parts, int kh,
+                      const int* parent, const int* plane0, const int* nparts, int max_parts, const int* mix_rows,
                       char* out, size_t out_stride, int ts, const int* flat, const int* depth, int max_depth, int nflat,
                       const unsigned long long* scr_base, const int16_t* ix, const int16_t* iy, int correct_ptr,
                       const int16_t* extx, const int16_t* exty, const unsigned long long* ext_base, int* count_out, hipStream_t s);

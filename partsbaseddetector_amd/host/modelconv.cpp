@@ -20,7 +20,13 @@ int main(int argc, char** argv) {
   bool ok;
   if (is_fs(argv[2])) { FileStorageModel out; out.assign(*in); ok = out.serialize(argv[2]); }
   else { BinaryModel out; out.assign(*in); ok = out.serialize(argv[2]); }
-  if (!ok) { printf("Error serializing file\n"); return -4; }
+  if (!ok) {
+    bool mixed = false;
+    for (const Mat& f : in->filters()) mixed = mixed || f.rows != in->filters()[0].rows || f.cols != in->filters()[0].cols;
+    if (mixed && !is_fs(argv[2])) printf("Error serializing file: the binary format carries one filter size and this model's filters have several (write .xml / .yml)\n");
+    else printf("Error serializing file\n");
+    return -4;
+  }
   printf("%d filters, %d components, interval %d, sbin %d, thresh %g\n", (int)in->filters().size(), in->ncomponents(),
          in->nscales(), in->binsize(), in->thresh());
   return 0;

@@ -190,10 +190,15 @@ class BinaryModel : public Model {
     fclose(f);
     return ok;
   }
+  // The dump carries ONE kh, kw (header): a bank of mixed sizes is refused (false, no file written) — writing kh_0 * kw_0 * flen floats
+  // of every filter would read past the end of any filter smaller than the first
   bool serialize(const std::string& filename) const {
+    if (filtersw_.empty()) return false;
+    const int kh = filtersw_[0].rows, kw = filtersw_[0].cols / flen_;
+    for (const Mat& m : filtersw_)
+      if (m.rows != kh || m.cols != filtersw_[0].cols) return false;
     FILE* f = fopen(filename.c_str(), "wb");
     if (!f) return false;
-    const int kh = filtersw_[0].rows, kw = filtersw_[0].cols / flen_;
     int32_t hd[12] = {(int32_t)filtersw_.size(), kh, kw, flen_, norient_, binsize_, nscales_, (int32_t)defw_.size(),
                       (int32_t)biasw_.size(), (int32_t)filterid_.size(), 0, 0};
     fwrite("PBDMODL1", 1, 8, f); fwrite(hd, 4, 12, f); fwrite(&thresh_, 4, 1, f);
@@ -284,16 +289,19 @@ class Device {
   }
   std::vector<float> filters, defw, biasw;
   std::vector<int32_t> anchors, part_offset, parentid, mix_offset, filterid, defid, biasid;
+  std::vector<int32_t> fsize;   // mixed banks: {kh, kw} per filter (pbd_create_sized); empty for a uniform bank
   Device(Model& m, int device, int conv_mode, int scalar_type = PBD_SCALAR_F32, int max_cand = 4096) {
     pbd_model_desc d{};
+    // The reference's engine takes a size per filter (src/SpatialConvolutionEngine.cpp:133-159, include/Parts.hpp:185-187): a uniform
+    // bank goes through pbd_create (desc kh x kw), a mixed one (e.g. matlab/modelTransfer.m's VOC path) through pbd_create_sized
     const int kh = m.filters()[0].rows, kw = m.filters()[0].cols / m.flen();
-    // The reference's engine takes a size per filter (src/SpatialConvolutionEngine.cpp:133-159, include/Parts.hpp:185-187); the
-    // C ABI describes a bank by ONE kh x kw (every model the reference's tools write is uniform: matlab/modelTransfer.m): a bank of
-    // mixed sizes is refused here instead of being read with the first filter's size
-    for (Mat& f : m.filters())
-      if (f.rows != kh || f.cols != kw * m.flen())
-        throw Exception(PBD_ERR_UNSUPPORTED, "distributeModel: filters of different sizes in one bank (pbd_model_desc carries one kh x kw)");
-    for (Mat& f : m.filters()) filters.insert(filters.end(), f.ptr<float>(), f.ptr<float>() + (size_t)kh * kw * m.flen());
+    bool uniform = true;
+    for (Mat& f : m.filters()) {
+      uniform = uniform && f.rows == kh && f.cols == kw * m.flen();
+      fsize.push_back(f.rows); fsize.push_back(f.cols / m.flen());
+      filters.insert(filters.end(), f.ptr<float>(), f.ptr<float>() + (size_t)f.rows * f.cols);
+    }
+    if (uniform) fsize.clear();
     for (vectorf& w : m.def()) defw.insert(defw.end(), w.begin(), w.begin() + 4);
     for (Point& a : m.anchors()) { anchors.push_back(a.x); anchors.push_back(a.y); }
     biasw = m.bias();
@@ -311,7 +319,7 @@ class Device {
       }
       part_offset.push_back((int32_t)parentid.size());
     }
-    d.nfilters = (int)m.filters().size(); d.kh = kh; d.kw = kw; d.flen = m.flen(); d.norient = m.norient();
+    d.nfilters = (int)m.filters().size(); d.kh = uniform ? kh : 0; d.kw = uniform ? kw : 0; d.flen = m.flen(); d.norient = m.norient();
     d.sbin = m.binsize(); d.interval = m.nscales(); d.thresh = m.thresh();
     d.filters = filters.data(); d.ndefs = (int)m.def().size(); d.defw = defw.data(); d.anchors = anchors.data();
     d.nbias = (int)biasw.size(); d.biasw = biasw.data(); d.ncomponents = (int)m.filterid().size();
@@ -321,7 +329,7 @@ class Device {
     opt.device = device; opt.conv_mode = conv_mode; opt.scalar_type = scalar_type; opt.max_candidates = max_cand;
     scalar = scalar_type; max_candidates = max_cand > 0 ? max_cand : 4096;
     if (pbd_abi_version() != PBD_ABI_VERSION) throw Exception(PBD_ERR_UNSUPPORTED, "libpbd_hip.so was built for another pbd_c.h (pbd_abi_version)");
-    const int rc = pbd_create(&d, &opt, &h);
+    const int rc = uniform ? pbd_create(&d, &opt, &h) : pbd_create_sized(&d, fsize.data(), &opt, &h);
     if (rc != PBD_OK) { std::string msg = h ? pbd_last_error(h) : "pbd_create failed"; if (h) pbd_destroy(h); h = nullptr; throw Exception(rc, msg); }
   }
   ~Device() { if (h) pbd_destroy(h); }

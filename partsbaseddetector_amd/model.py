@@ -63,9 +63,22 @@ class Model:
     def max_parts(self) -> int:
         return max(self.nparts(c) for c in range(self.ncomponents))
 
+    def filter_sizes(self) -> np.ndarray:
+        """[nfilters, 2] int32: (rows kh, cols kw) of every filter."""
+        return np.asarray([(f.shape[0], f.shape[1] // self.flen) for f in self.filtersw], np.int32).reshape(-1, 2)
+
+    def is_uniform(self) -> bool:
+        """True when every filter has one size (what pbd_create and the binary dump take)."""
+        fs = self.filter_sizes()
+        return bool((fs == fs[0]).all())
+
     def save(self, path: str) -> None:
-        """Flat little-endian dump read by pbd::BinaryModel (partsbaseddetector_amd/host/pbd_host.hpp)."""
+        """Flat little-endian dump read by pbd::BinaryModel (partsbaseddetector_amd/host/pbd_host.hpp).
+        The format has ONE kh, kw: a mixed bank is refused (ValueError) before the file is opened."""
         import struct
+        if not self.is_uniform():
+            raise ValueError("binary model dump: the format carries one filter size; this model's filters have "
+                             f"several ({sorted(set(map(tuple, self.filter_sizes().tolist())))}) — use save_filestorage")
         kh = self.filtersw[0].shape[0]
         kw = self.filtersw[0].shape[1] // self.flen
         with open(path, "wb") as f:
@@ -176,13 +189,28 @@ class Model:
             f.write("\n".join(o) + "\n")
 
     def to_desc(self) -> pbd_model_desc:
-        """Flatten into the C ABI descriptor (arrays kept alive on self)."""
+        """Flatten into the C ABI descriptor (arrays kept alive on self).  Uniform banks only (pbd_create)."""
         kh = self.filtersw[0].shape[0]
         kw = self.filtersw[0].shape[1] // self.flen
         for f in self.filtersw:
             if f.shape != (kh, kw * self.flen):
                 raise ValueError("all filters must have the same size")
         filt = np.ascontiguousarray(np.stack(self.filtersw).astype(np.float32))
+        return self._desc(filt, kh, kw)
+
+    def to_desc_sized(self):
+        """(desc, fsize) for pbd_create_sized: the filters back to back, each at its own size; desc.kh = desc.kw = 0 and
+        fsize[n] = (kh_n, kw_n).  Any bank, uniform or mixed (arrays kept alive on self)."""
+        for f in self.filtersw:
+            if f.ndim != 2 or f.shape[1] % self.flen:
+                raise ValueError("a filter must be kh x (kw*flen)")
+        fsize = np.ascontiguousarray(self.filter_sizes())
+        filt = np.ascontiguousarray(np.concatenate([np.asarray(f, np.float32).ravel() for f in self.filtersw]))
+        d = self._desc(filt, 0, 0)
+        self._keep.append(fsize)
+        return d, fsize
+
+    def _desc(self, filt, kh, kw) -> pbd_model_desc:
         defw = np.ascontiguousarray(np.asarray(self.defw, np.float32).reshape(-1, 4))
         anchors = np.ascontiguousarray(np.asarray(self.anchors, np.int32).reshape(-1, 2))
         biasw = np.ascontiguousarray(np.asarray(self.biasw, np.float32))
@@ -256,6 +284,49 @@ def make_person_model(seed=1234, K=6, thresh=0.0, interval=10, sbin=4) -> Model:
     """26 parts x K mixtures: 156 filters / 150 deformations / 901 biases for K=6."""
     return make_tree_model(PERSON_TREE, K, seed=seed, thresh=thresh, interval=interval, sbin=sbin,
                            name=f"person26x{K}")
+
+
+def make_mixed_person_model(seed=1234, K=6, root=(7, 7), odd_sizes=((3, 5), (6, 4)), thresh=0.0, interval=10,
+                            sbin=4) -> Model:
+    """make_person_model with a size per filter: the K root filters root[0] x root[1], the filters of parts 1 .. len(odd_sizes) the
+    sizes of odd_sizes (all K mixtures of a part one size), every other filter 5 x 5."""
+    m = make_person_model(seed=seed, K=K, thresh=thresh, interval=interval, sbin=sbin)
+    rng = np.random.default_rng(seed + 1)
+    sizes = {0: tuple(root)}
+    sizes.update({1 + i: tuple(sz) for i, sz in enumerate(odd_sizes)})
+    for p, (kh, kw) in sizes.items():
+        new = _filters(rng, K, kh, kw, m.flen)
+        for k in range(K):
+            m.filtersw[m.filterid[0][p][k]] = new[k]
+    m.name = f"person26x{K}-mixed"
+    return m
+
+
+def make_voc_like_model(seed=11, roots=((6, 4), (7, 7), (5, 8)), part_size=(4, 4), nparts=(6, 5, 6), thresh=0.0,
+                        interval=5, sbin=4) -> Model:
+    """The layout matlab/modelTransfer.m modelTransferVOC2Face (:76-150) writes for a Felzenszwalb VOC model: one component per
+    root, a star tree (every part's parent is the root), one mixture per part, a root filter of the component's own size and part
+    filters of another size (here 4 x 4, an even size).  Filters of component c: its root, then its parts; a bias per component
+    root and per part (1 x 1 bias matrices), a deformation per part.  Sides stay within the library's 1..9."""
+    rng = np.random.default_rng(seed)
+    flen = 32
+    filt, filterid, defid, biasid, parentid = [], [], [], [], []
+    ndefs = 0
+    biasw = []
+    for c, rs in enumerate(roots):
+        P = nparts[c % len(nparts)]
+        f0 = len(filt)
+        filt += _filters(rng, 1, rs[0], rs[1], flen) + _filters(rng, P - 1, part_size[0], part_size[1], flen)
+        filterid.append([[f0 + p] for p in range(P)])
+        defid.append([[] if p == 0 else [ndefs + p - 1] for p in range(P)])
+        ndefs += P - 1
+        b0 = len(biasw)
+        biasw += [float(x) for x in rng.normal(0.0, 0.1, P)]
+        biasid.append([[b0 + p] for p in range(P)])
+        parentid.append([-1] + [0] * (P - 1))
+    defw, anchors = _defs(rng, ndefs, max_anchor=3)
+    return Model(filt, np.asarray(biasw, np.float32), anchors, defw, filterid, biasid, defid, parentid, interval,
+                 thresh, sbin, 18, flen, "voc-like")
 
 
 def make_face_like_model(seed=77, ncomp=13, nfilters=146, part_counts=(39, 68), thresh=0.0, interval=5,
