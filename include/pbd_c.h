@@ -157,7 +157,9 @@ int pbd_abi_version(void);
  * features outside a split bank's domain (PBD_ERR_ARG), pbd_tune_plan drops the handle's plan on return, pbd_detect_image replays a
  * hipGraph under pbd_options.graph.
  * 5 = pbd_create_sized, pbd_group_create_sized, pbd_get_filter_size (filter banks with a size per filter); also marks the round-6
- * refinements above.  Struct layouts unchanged; results of uniform banks unchanged.                                            */
+ * refinements above.  Struct layouts unchanged; results of uniform banks unchanged.
+ * Version 5 also gains, purely additively (no layout moved, no existing result changed; a binding finds them by symbol): the
+ * candidate filter entry points pbd_set_candidate_filter, pbd_group_set_candidate_filter and pbd_candidates_filter.            */
 
 /* ---- output record: include/Candidate.hpp:56-111 --------------------------
  * One candidate = head + max_parts boxes (x, y, width, height as cv::Rect)
@@ -382,6 +384,27 @@ int pbd_candidates_sort(pbd_candidate_head* heads, int32_t* boxes, int32_t* locs
                         int count, int max_parts);
 int pbd_candidates_nms(pbd_candidate_head* heads, int32_t* boxes, int32_t* locs,
                        int count, int max_parts, int im_w, int im_h, float overlap, int* kept);
+
+/* ---- the same post-step on the device (ros/Node.cpp:192-196, cells/detect.cpp:237-238) ----------------------------------
+ * Modes: PBD_CAND_RAW (default) = detect's output as it is; PBD_CAND_SORT = Candidate::sort; PBD_CAND_SORT_NMS = sort, then
+ * nonMaximaSuppression(im, candidates, overlap) with the frame's size.  Every whole-path detect entry point of a handle with a
+ * mode set (pbd_detect_u8 / _dev_u8 / _enqueue_* + collect, pbd_detect_image, the pbd_detect_batch_* family; the group's two)
+ * returns, per frame, exactly what the two host functions above make of the RAW output; counts become the kept counts.  The
+ * step runs on the GPU behind the back-tracking, in the frame's stream and graph.  PBD_ERR_CAPACITY: if the records before
+ * filtering overflow pbd_options.max_candidates, as with RAW (count = records needed); if the kept records exceed `capacity`,
+ * count = kept.  The stage entry points (pbd_dp_argmin) stay unfiltered.  Applies to frames enqueued after the call; any finite
+ * overlap (negative: every non-empty box is rejected).  PBD_ERR_ARG: unknown mode, non-finite overlap; PBD_ERR_STATE: a frame
+ * is pending, or the handle is a group member (set it on the group).  A captured graph is dropped and captured again.      */
+enum { PBD_CAND_RAW = 0, PBD_CAND_SORT = 1, PBD_CAND_SORT_NMS = 2 };
+int pbd_set_candidate_filter(pbd_handle* h, int mode, float overlap);
+/* every member; the level-sharded pbd_group_detect_u8 filters the union of the members' records on member 0          */
+int pbd_group_set_candidate_filter(pbd_group* g, int mode, float overlap);
+/* Stand-alone: the caller's `count` host records (max_parts = the handle's) through the same device kernel, in place, ties
+ * broken by input position: bit-identical to pbd_candidates_sort then (mode 2) pbd_candidates_nms(im_w, im_h, overlap);
+ * *kept = records left.  PBD_ERR_ARG: non-finite scores (their host order is undefined), nparts outside 0..max_parts in
+ * mode 2, boxes NULL or im_w / im_h <= 0 in mode 2.  boxes / locs may be NULL in mode 1.  Synchronous.                  */
+int pbd_candidates_filter(pbd_handle* h, int mode, float overlap, int im_w, int im_h, pbd_candidate_head* heads,
+                          int32_t* boxes, int32_t* locs, int count, int* kept);
 
 /* ---- instrumentation --------------------------------------------------------
  * GPU time (ms, hipEvent) of the stages of the last synchronous detect:

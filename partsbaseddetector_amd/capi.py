@@ -22,6 +22,7 @@ PBD_OK, PBD_ERR_ARG, PBD_ERR_UNSUPPORTED, PBD_ERR_CAPACITY, PBD_ERR_HIP, PBD_ERR
 PBD_GATHER_AUTO, PBD_GATHER_HOST, PBD_GATHER_RCCL = 0, 1, 2
 PBD_CONV_AUTO, PBD_CONV_EXACT, PBD_CONV_MFMA, PBD_CONV_SPLIT, PBD_CONV_SPLIT_F16 = 0, 1, 2, 3, 4
 PBD_SCALAR_F32, PBD_SCALAR_F64 = 0, 1
+PBD_CAND_RAW, PBD_CAND_SORT, PBD_CAND_SORT_NMS = 0, 1, 2   # pbd_set_candidate_filter: detect's output / Candidate::sort / sort + NMS
 PBD_DEPTH_8U, PBD_DEPTH_16U, PBD_DEPTH_32F, PBD_DEPTH_64F = 0, 2, 5, 6          # cv::Mat::depth() (src/HOGFeatures.cpp:136-146)
 DEPTH_OF = {np.dtype(np.uint8): PBD_DEPTH_8U, np.dtype(np.uint16): PBD_DEPTH_16U, np.dtype(np.float32): PBD_DEPTH_32F,
             np.dtype(np.float64): PBD_DEPTH_64F}
@@ -44,6 +45,7 @@ EXPORTS = [
     "pbd_get_stage_state", "pbd_get_conv_mode", "pbd_group_comm_size",
     "pbd_detect_image", "pbd_pyramid_image", "pbd_get_level_image_raw", "pbd_tune_plan",
     "pbd_create_sized", "pbd_group_create_sized", "pbd_get_filter_size",
+    "pbd_set_candidate_filter", "pbd_group_set_candidate_filter", "pbd_candidates_filter",
 ]
 PBD_ABI_VERSION = 5
 
@@ -99,13 +101,16 @@ class Handle:
     """Owns one pbd_handle (one GPU, one stream)."""
 
     def __init__(self, model, device=0, conv_mode=PBD_CONV_AUTO, max_candidates=4096, dt_correct_ptr=0,
-                 level_begin=0, level_end=0, dp_groups=0, dtype=np.float32, graph=0, dp_mode=0, nms_sz=0, sized=False):
+                 level_begin=0, level_end=0, dp_groups=0, dtype=np.float32, graph=0, dp_mode=0, nms_sz=0, sized=False,
+                 cand_filter=None):
         """dtype: np.float32 = PartsBasedDetector<float>, np.float64 = PartsBasedDetector<double>.
         nms_sz > 0: score-map NMS of the root planes on the device in front of the back-tracking (pbd_options.reserved[0]).
         dp_mode: 0 = messages folded by the parent's x pass where the model allows it (default), 1 = the
         three-kernel structure (x pass, y pass, reduce) for every model.  dp_groups: ignored (kept for callers).
         A model whose filters differ in size is created through pbd_create_sized, a uniform one through pbd_create
-        (sized=True: pbd_create_sized for any model)."""
+        (sized=True: pbd_create_sized for any model).
+        cand_filter=(mode, overlap): pbd_set_candidate_filter — every detect returns Candidate::sort (PBD_CAND_SORT) or sort +
+        nonMaximaSuppression(overlap) (PBD_CAND_SORT_NMS) of its output, computed on the GPU."""
         self.L = lib()
         self.model = model
         # a size per filter (pbd_create_sized) only where the bank is mixed: uniform banks keep pbd_create
@@ -134,6 +139,24 @@ class Handle:
             raise PbdError(rc, msg)
         self.max_parts = self.L.pbd_max_parts(self.h)
         self.conv_mode = self.L.pbd_get_conv_mode(self.h)      # what PBD_CONV_AUTO resolved to
+        if cand_filter is not None:
+            self.set_candidate_filter(*cand_filter)
+
+    def set_candidate_filter(self, mode, overlap=0.0):
+        """pbd_set_candidate_filter: PBD_CAND_RAW / PBD_CAND_SORT / PBD_CAND_SORT_NMS for the frames enqueued from now on."""
+        self._chk(self.L.pbd_set_candidate_filter(self.h, int(mode), C.c_float(overlap)))
+
+    def candidates_filter(self, heads, boxes, locs, im_w, im_h, mode=PBD_CAND_SORT_NMS, overlap=0.0):
+        """pbd_candidates_filter: the records through the device kernel; returns the kept (heads, boxes, locs)."""
+        heads = np.ascontiguousarray(heads, HEAD_DTYPE).copy()
+        boxes = None if boxes is None else np.ascontiguousarray(boxes, np.int32).copy()
+        locs = None if locs is None else np.ascontiguousarray(locs, np.int32).copy()
+        kept = C.c_int(0)
+        self._chk(self.L.pbd_candidates_filter(self.h, int(mode), C.c_float(overlap), int(im_w), int(im_h),
+                                               heads.ctypes.data_as(C.c_void_p), _p(boxes, C.c_int32), _p(locs, C.c_int32),
+                                               len(heads), C.byref(kept)))
+        k = kept.value
+        return heads[:k], None if boxes is None else boxes[:k], None if locs is None else locs[:k]
 
     def close(self):
         if getattr(self, "h", None):
@@ -469,7 +492,7 @@ class Group:
     """pbd_group: one process driving several GPUs (include/pbd_c.h).  devices may repeat an ordinal."""
 
     def __init__(self, model, devices, gather=PBD_GATHER_AUTO, conv_mode=PBD_CONV_AUTO, max_candidates=4096,
-                 dtype=np.float32, graph=0, nms_sz=0):
+                 dtype=np.float32, graph=0, nms_sz=0, cand_filter=None):
         self.L = lib()
         self.model = model
         self.fsize = None
@@ -497,6 +520,12 @@ class Group:
         self.gather_mode = self.L.pbd_group_gather_mode(self.g)
         self.comm_size = self.L.pbd_group_comm_size(self.g)       # ranks of the RCCL communicator (0: host gather)
         self.max_parts = self.L.pbd_max_parts(C.c_void_p(self.L.pbd_group_member(self.g, 0)))
+        if cand_filter is not None:
+            self.set_candidate_filter(*cand_filter)
+
+    def set_candidate_filter(self, mode, overlap=0.0):
+        """pbd_group_set_candidate_filter: every member; detect() filters the union of the members' levels."""
+        self._chk(self.L.pbd_group_set_candidate_filter(self.g, int(mode), C.c_float(overlap)))
 
     def close(self):
         if getattr(self, "g", None):

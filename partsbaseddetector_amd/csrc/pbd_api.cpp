@@ -441,6 +441,7 @@ static void free_frame(pbd_handle* h) {
   h->frame_allocs.clear();
   h->frame_bytes = 0;
   h->d_extx = h->d_exty = nullptr; h->d_ext_base = nullptr; h->ext_ptr = false;
+  h->d_cf_mask = nullptr; h->cf_mask_bytes = 0;
   h->fw = h->fh = h->fcn = 0; h->fdepth = 0; h->fesz = 1;
   h->have_pyr = h->have_feat = h->have_resp = h->have_dp = false;
   h->min_ran = false;
@@ -1232,7 +1233,43 @@ static int run_dp_min(pbd_handle* h) {
   return PBD_OK;
 }
 
-static int run_argmin_enqueue(pbd_handle* h) {
+static int cand_mode_now(const pbd_handle* h) { return h->cand_defer ? PBD_CAND_RAW : h->cand_mode; }
+static CandFilterArgs cand_args(pbd_handle* h, int mode, float overlap, int im_w, int im_h) {
+  CandFilterArgs a{};
+  a.capacity = h->opt.max_candidates; a.stride = h->cand_stride; a.mp = h->max_parts;
+  a.ts = h->ts; a.ncomp = h->md.ncomponents;
+  a.nms = mode == PBD_CAND_SORT_NMS; a.overlap = (double)overlap; a.im_w = im_w; a.im_h = im_h;
+  a.keys = h->d_cf_keys; a.idx = h->d_cf_idx; a.box = h->d_cf_box; a.st = h->d_cf_st;
+  return a;
+}
+// the filter's scratch: model-sized once (first use), the per-frame masks with the frame plan.  Called outside any capture;
+// a (re)allocation drops a captured graph (its launches point at the old buffers).
+static int cand_filter_buffers(pbd_handle* h, bool masks) {
+  const size_t cap = (size_t)h->opt.max_candidates;
+  if (!h->d_cf_keys) {
+    HIPCHK(h, hipMalloc(&h->d_cf_keys, sizeof(unsigned long long) * 2 * cap));
+    HIPCHK(h, hipMalloc(&h->d_cf_idx, sizeof(unsigned) * 2 * cap));
+    HIPCHK(h, hipMalloc(&h->d_cf_box, sizeof(int) * 4 * cap));
+    HIPCHK(h, hipMalloc(&h->d_cf_st, cap));
+    HIPCHK(h, hipMalloc(&h->d_cf_cnt, sizeof(int) * (2 + 2 * PBD_MAX_BATCH)));
+    HIPCHK(h, hipHostMalloc((void**)&h->h_cf_cnt, sizeof(int) * (2 + 2 * PBD_MAX_BATCH)));
+    HIPCHK(h, hipMalloc(&h->d_cand_raw, h->cand_stride * cap));
+    h->model_bytes += (sizeof(unsigned long long) * 2 + sizeof(unsigned) * 2 + sizeof(int) * 4 + 1) * cap + h->cand_stride * cap;
+    if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
+  }
+  if (masks && h->fw > 0) {
+    const size_t need = cand_filter_mask_bytes(h->fw, h->fh) * h->batch;
+    if (need > h->cf_mask_bytes) {
+      int rc = dev_alloc(h, &h->d_cf_mask, need / sizeof(unsigned long long));
+      if (rc) return rc;
+      h->cf_mask_bytes = need;
+      if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
+    }
+  }
+  return PBD_OK;
+}
+
+static int run_argmin_enqueue(pbd_handle* h, bool filter = false) {
   if (h->root_dirty) {   // root tables injected since min(): the hits are those of the tables now on the device
     hipMemsetAsync(h->d_cand_count, 0, sizeof(int), h->stream);
     if (h->nms_sz > 0) nms_and_rescan(h);
@@ -1244,6 +1281,34 @@ static int run_argmin_enqueue(pbd_handle* h) {
   // Round 6: a handle that is not a member of an RCCL-gathering group lets the back-tracking kernel write the records and the count straight
   // into its pinned host buffers (hipHostMalloc: device-mapped, coherent): no copy nodes behind the kernel, and never a second copy for
   // records beyond a first block.  Group members keep the device buffer: the all-gather reads it.
+  const int cm = filter ? cand_mode_now(h) : PBD_CAND_RAW;
+  h->out_filtered = cm != PBD_CAND_RAW;
+  if (h->out_filtered) {
+    // Candidate::sort (+ nonMaximaSuppression) behind the back-tracking: k_backtrack writes the device buffer, k_cand_filter the kept
+    // records in final order + the per-frame counts — straight into the pinned host buffers, or, for a member of an RCCL-gathering group,
+    // into the device buffer the all-gather block is packed from
+    const bool dev_out = h->d_gsend != nullptr;
+    char* raw = dev_out ? h->d_cand_raw : h->d_cand_out;
+    launch_backtrack(h->d_cand_count, h->d_cand_rec, h->opt.max_candidates, h->d_back, h->md.ncomponents, h->d_parent,
+                     h->d_plane0, h->d_nparts, h->max_parts, h->d_mix_rows, raw, h->cand_stride, h->ts, h->d_flat,
+                     h->d_depth, h->max_depth, (int)h->parts.size(), h->d_scr_base, h->d_dt_ixT, h->d_dt_iy,
+                     h->opt.dt_correct_ptr, h->ext_ptr ? h->d_extx : nullptr, h->d_exty, h->d_ext_base, nullptr, h->stream);
+    CandFilterArgs a = cand_args(h, cm, h->cand_overlap, h->fw, h->fh);
+    a.in = raw; a.in_count = h->d_cand_count; a.nlevels = h->nlevels;
+    a.back = h->d_back; a.rootv_base = h->d_rootv; a.gmask = h->d_cf_mask;
+    a.out = dev_out ? h->d_cand_out : h->h_cand_out;
+    a.cnt_out = dev_out ? h->d_cf_cnt : h->h_cf_cnt;
+    launch_cand_filter(a, h->batch, h->stream);
+    LAUNCHCHK(h, "argmin + candidate filter");
+    h->pending = true;
+    h->out_on_host = !dev_out;
+    if (!dev_out) return PBD_OK;
+    h->first_copy = kFirstCopy * h->batch;
+    const int first = std::min(h->first_copy, h->opt.max_candidates);
+    HIPCHK(h, hipMemcpyAsync(h->d_gsend, h->d_cf_cnt + 1, sizeof(int), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_gsend + 16, h->d_cand_out, h->cand_stride * first, hipMemcpyDeviceToDevice, h->stream));
+    return PBD_OK;
+  }
   const bool zero_copy = PBD_ARGMIN_ZERO_COPY && !h->d_gsend;
   launch_backtrack(h->d_cand_count, h->d_cand_rec, h->opt.max_candidates, h->d_back, h->md.ncomponents, h->d_parent,
                    h->d_plane0, h->d_nparts, h->max_parts, h->d_mix_rows, zero_copy ? h->h_cand_out : h->d_cand_out, h->cand_stride, h->ts, h->d_flat,
@@ -1295,7 +1360,7 @@ int pbd_i_finish_frame(pbd_handle* h, int found) {
 // Candidate records (cand_stride bytes each, possibly from several handles of one group: recs[i] points at record i)
 // -> the caller's arrays, ordered like a single-threaded reference run: level, component, row-major root location.
 int pbd_i_emit(pbd_handle* h, const std::vector<const char*>& recs, pbd_candidate_head* heads, int32_t* boxes,
-               int32_t* locs, int capacity) {
+               int32_t* locs, int capacity, bool ordered) {
   const int mp = h->max_parts, n = (int)recs.size();
   std::vector<int> order(n);
   for (int i = 0; i < n; ++i) order[i] = i;
@@ -1305,6 +1370,7 @@ int pbd_i_emit(pbd_handle* h, const std::vector<const char*>& recs, pbd_candidat
     const int32_t* lc = (const int32_t*)(o + sizeof(pbd_candidate_head)) + (size_t)mp * 4;
     return k == 0 ? hd->level : k == 1 ? hd->component : k == 2 ? lc[1] : lc[0];
   };
+  if (!ordered)
   std::sort(order.begin(), order.end(), [&](int a, int b) {
     for (int k = 0; k < 4; ++k) { int ka = key(a, k), kb = key(b, k); if (ka != kb) return ka < kb; }
     return false;
@@ -1320,18 +1386,20 @@ int pbd_i_emit(pbd_handle* h, const std::vector<const char*>& recs, pbd_candidat
   return PBD_OK;
 }
 
+int pbd_i_found(const pbd_handle* h) { return h->out_filtered ? h->h_cf_cnt[1] : h->h_cand_count[0]; }
+
 static int collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* count) {
   if (!h->pending) return fail(h, PBD_ERR_STATE, "collect without a pending detect");
   if (h->d_gsend) return fail(h, PBD_ERR_STATE, "handle belongs to an RCCL-gathering pbd_group: collect through the group");
   if (h->batch > 1) return fail(h, PBD_ERR_STATE, "a batch of frames is pending: collect it with pbd_detect_batch_collect");
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  const int found = h->h_cand_count[0];
+  const int found = pbd_i_found(h);
   if (count) *count = found;
   int rc = pbd_i_finish_frame(h, found);
   if (rc) return rc;
   std::vector<const char*> recs((size_t)found);
   for (int i = 0; i < found; ++i) recs[i] = h->h_cand_out + h->cand_stride * i;
-  return pbd_i_emit(h, recs, heads, boxes, locs, capacity);
+  return pbd_i_emit(h, recs, heads, boxes, locs, capacity, h->out_filtered);
 }
 int pbd_i_collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* count) {
   int rc = collect(h, heads, boxes, locs, capacity, count);
@@ -1352,7 +1420,7 @@ static int enqueue_stages(pbd_handle* h, const uint8_t* d_src, int stride) {
   if (prof) hipEventRecord(h->ev[3], h->stream);
   if ((rc = run_dp_min(h))) return rc;
   if (prof) hipEventRecord(h->ev[4], h->stream);
-  if ((rc = run_argmin_enqueue(h))) return rc;
+  if ((rc = run_argmin_enqueue(h, true))) return rc;
   if (prof) hipEventRecord(h->ev[5], h->stream);
   return PBD_OK;
 }
@@ -1365,6 +1433,11 @@ static int enqueue_stages(pbd_handle* h, const uint8_t* d_src, int stride) {
 // events) and level groups on extra streams use the eager path.
 static int enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride) {
   const bool graphable = h->opt.graph && !h->profiling;   // (frames of any depth: the launches depend on the plan only; round 5 replayed 8-bit plans only)
+  if (cand_mode_now(h) != PBD_CAND_RAW) {
+    int rc = cand_filter_buffers(h, cand_mode_now(h) == PBD_CAND_SORT_NMS);
+    if (rc) return rc;
+  }
+  h->out_filtered = cand_mode_now(h) != PBD_CAND_RAW;   // (a replayed graph does not pass through run_argmin_enqueue)
   if (!graphable || h->frames_on_plan == 0) {
     h->frames_on_plan++;
     return enqueue_stages(h, d_src, stride);
@@ -1526,6 +1599,8 @@ int pbd_destroy(pbd_handle* h) {
   hipFree(h->d_cand_count); hipFree(h->d_cand_rec); hipFree(h->d_cand_out);
   if (h->h_cand_out) hipHostFree(h->h_cand_out);
   if (h->h_cand_count) hipHostFree(h->h_cand_count);
+  hipFree(h->d_cand_raw); hipFree(h->d_cf_keys); hipFree(h->d_cf_idx); hipFree(h->d_cf_box); hipFree(h->d_cf_st); hipFree(h->d_cf_cnt);
+  if (h->h_cf_cnt) hipHostFree(h->h_cf_cnt);
   for (int i = 0; i < 8; ++i) if (h->ev[i]) hipEventDestroy(h->ev[i]);
   if (h->ev_dp0) hipEventDestroy(h->ev_dp0);
   if (h->ev_dp1) hipEventDestroy(h->ev_dp1);
@@ -1683,12 +1758,17 @@ int pbd_detect_batch_collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* 
   if (h->d_gsend) return fail(h, PBD_ERR_STATE, "handle belongs to an RCCL-gathering pbd_group: collect through the group");
   ON_DEVICE(h);
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  const int found = h->h_cand_count[0];
+  const bool filt = h->out_filtered;
+  const int found = filt ? h->h_cf_cnt[0] : h->h_cand_count[0];
   int rc = pbd_i_finish_frame(h, found);
   read_stage_times(h);
   if (rc) return rc;
   const int mp = h->max_parts, n1 = h->nlevels, B = h->batch;
   std::vector<std::vector<const char*>> per(B);
+  if (filt) {   // frame f's kept records, in final order, at its offset
+    for (int f = 0; f < B; ++f)
+      for (int j = 0; j < h->h_cf_cnt[2 + f]; ++j) per[f].push_back(h->h_cand_out + h->cand_stride * ((size_t)h->h_cf_cnt[2 + B + f] + j));
+  } else
   for (int i = 0; i < found; ++i) {
     const char* r = h->h_cand_out + h->cand_stride * i;
     per[((const pbd_candidate_head*)r)->level / n1].push_back(r);
@@ -1697,7 +1777,7 @@ int pbd_detect_batch_collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* 
   for (int f = 0; f < B; ++f) {
     counts[f] = (int)per[f].size();
     pbd_candidate_head* hf = heads + (size_t)f * capacity;
-    rc = pbd_i_emit(h, per[f], hf, boxes ? boxes + (size_t)f * capacity * mp * 4 : nullptr, locs ? locs + (size_t)f * capacity * mp * 3 : nullptr, capacity);
+    rc = pbd_i_emit(h, per[f], hf, boxes ? boxes + (size_t)f * capacity * mp * 4 : nullptr, locs ? locs + (size_t)f * capacity * mp * 3 : nullptr, capacity, filt);
     if (rc == PBD_ERR_CAPACITY) { status = rc; continue; }
     if (rc) return rc;
     for (int i = 0; i < counts[f]; ++i) hf[i].level -= f * n1;   // virtual level -> the frame's own pyramid level
@@ -2327,6 +2407,85 @@ int pbd_candidates_nms(pbd_candidate_head* heads, int32_t* boxes, int32_t* locs,
   }
   *kept = keep;
   return PBD_OK;
+}
+
+// ---- the post-step on the device (k_cand.hip) -------------------------------------
+static bool cand_mode_ok(int mode, float overlap) {
+  return (mode == PBD_CAND_RAW || mode == PBD_CAND_SORT || mode == PBD_CAND_SORT_NMS) && std::isfinite(overlap);
+}
+int pbd_set_candidate_filter(pbd_handle* h, int mode, float overlap) {
+  if (!h) return PBD_ERR_ARG;
+  if (!cand_mode_ok(mode, overlap)) return fail(h, PBD_ERR_ARG, "candidate filter: mode PBD_CAND_RAW / _SORT / _SORT_NMS, finite overlap");
+  if (h->in_group) return fail(h, PBD_ERR_STATE, "handle belongs to a pbd_group: set the filter on the group");
+  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (mode != h->cand_mode || overlap != h->cand_overlap) {   // the filter's launch (or its absence) is part of a captured graph
+    if (h->gexec) { ON_DEVICE(h); hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
+  }
+  h->cand_mode = mode;
+  h->cand_overlap = overlap;
+  return PBD_OK;
+}
+
+extern "C++" int pbd_i_filter_host(pbd_handle* h, int mode, float overlap, int im_w, int im_h, pbd_candidate_head* heads, int32_t* boxes,
+                                   int32_t* locs, int count, int* kept) {
+  if (mode == PBD_CAND_RAW || count == 0) { *kept = count; return PBD_OK; }
+  ON_DEVICE(h);
+  const int mp = h->max_parts;
+  const size_t st = h->cand_stride, n = (size_t)count;
+  std::vector<char> rec(st * n, 0);
+  for (size_t i = 0; i < n; ++i) {
+    char* o = rec.data() + st * i;
+    memcpy(o, heads + i, sizeof(pbd_candidate_head));
+    if (boxes) memcpy(o + sizeof(pbd_candidate_head), boxes + i * mp * 4, sizeof(int32_t) * mp * 4);
+    if (locs) memcpy(o + sizeof(pbd_candidate_head) + sizeof(int32_t) * mp * 4, locs + i * mp * 3, sizeof(int32_t) * mp * 3);
+  }
+  const size_t mask = cand_filter_mask_bytes(im_w, im_h);
+  char *d_in = nullptr, *d_out = nullptr; int* d_cnt = nullptr; unsigned long long* d_keys = nullptr; unsigned* d_idx = nullptr;
+  int* d_box = nullptr; uint8_t* d_st = nullptr; unsigned long long* d_mask = nullptr;
+  auto release = [&]() { hipFree(d_in); hipFree(d_out); hipFree(d_cnt); hipFree(d_keys); hipFree(d_idx); hipFree(d_box); hipFree(d_st); hipFree(d_mask); };
+  hipError_t e = hipSuccess;
+  auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+  chk(hipMalloc(&d_in, st * n)); chk(hipMalloc(&d_out, st * n)); chk(hipMalloc(&d_cnt, sizeof(int) * 5));
+  chk(hipMalloc(&d_keys, 16 * n)); chk(hipMalloc(&d_idx, 8 * n)); chk(hipMalloc(&d_box, 16 * n)); chk(hipMalloc(&d_st, n));
+  if (mask && mode == PBD_CAND_SORT_NMS) chk(hipMalloc(&d_mask, mask));
+  chk(hipMemcpyAsync(d_in, rec.data(), st * n, hipMemcpyHostToDevice, h->stream));
+  chk(hipMemcpyAsync(d_cnt, &count, sizeof(int), hipMemcpyHostToDevice, h->stream));
+  if (e == hipSuccess) {
+    CandFilterArgs a = cand_args(h, mode, overlap, im_w, im_h);
+    a.in = d_in; a.in_count = d_cnt; a.capacity = count; a.nlevels = 0; a.back = nullptr;
+    a.keys = d_keys; a.idx = d_idx; a.box = d_box; a.st = d_st; a.gmask = d_mask;
+    a.out = d_out; a.cnt_out = d_cnt + 1;
+    launch_cand_filter(a, 1, h->stream);
+    chk(hipGetLastError());
+  }
+  int cnt[4] = {0, 0, 0, 0};
+  chk(hipMemcpyAsync(cnt, d_cnt + 1, sizeof(int) * 4, hipMemcpyDeviceToHost, h->stream));
+  chk(hipMemcpyAsync(rec.data(), d_out, st * n, hipMemcpyDeviceToHost, h->stream));
+  chk(hipStreamSynchronize(h->stream));
+  release();
+  if (e != hipSuccess) return fail(h, PBD_ERR_HIP, std::string("candidate filter: ") + hipGetErrorString(e));
+  const int k = cnt[1];
+  for (int i = 0; i < k; ++i) {
+    const char* o = rec.data() + st * i;
+    memcpy(heads + i, o, sizeof(pbd_candidate_head));
+    if (boxes) memcpy(boxes + (size_t)i * mp * 4, o + sizeof(pbd_candidate_head), sizeof(int32_t) * mp * 4);
+    if (locs) memcpy(locs + (size_t)i * mp * 3, o + sizeof(pbd_candidate_head) + sizeof(int32_t) * mp * 4, sizeof(int32_t) * mp * 3);
+  }
+  *kept = k;
+  return PBD_OK;
+}
+
+int pbd_candidates_filter(pbd_handle* h, int mode, float overlap, int im_w, int im_h, pbd_candidate_head* heads, int32_t* boxes,
+                          int32_t* locs, int count, int* kept) {
+  if (!h) return PBD_ERR_ARG;
+  if (!cand_mode_ok(mode, overlap)) return fail(h, PBD_ERR_ARG, "candidate filter: mode PBD_CAND_RAW / _SORT / _SORT_NMS, finite overlap");
+  if (!kept || count < 0 || (count > 0 && !heads)) return fail(h, PBD_ERR_ARG, "heads / kept / count");
+  if (mode == PBD_CAND_SORT_NMS && (!boxes || im_w <= 0 || im_h <= 0)) return fail(h, PBD_ERR_ARG, "NMS needs boxes and the image size");
+  for (int i = 0; i < count; ++i) {
+    if (!std::isfinite(heads[i].score)) return fail(h, PBD_ERR_ARG, "non-finite score: its order is undefined");
+    if (mode == PBD_CAND_SORT_NMS && (heads[i].nparts < 0 || heads[i].nparts > h->max_parts)) return fail(h, PBD_ERR_ARG, "nparts outside 0..max_parts");
+  }
+  return pbd_i_filter_host(h, mode, overlap, im_w, im_h, heads, boxes, locs, count, kept);
 }
 
 // ---- instrumentation ---------------------------------------------------------

@@ -8,6 +8,7 @@
 // load-time dependency on it) followed by ONE D2H on member 0, or one small D2H per member (host concatenation).
 #include <dlfcn.h>
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <set>
@@ -59,6 +60,7 @@ struct pbd_group {
   char* h_recv = nullptr;              // pinned, size() blocks (filled from member 0)
   size_t block = 0;                    // bytes of one {count, pad, first records} block
   int shard_w = 0, shard_h = 0, shard_cn = 0;   // geometry the members' level sets were computed for (0: all levels)
+  int cand_mode = PBD_CAND_RAW; float cand_overlap = 0.f;   // pbd_group_set_candidate_filter
   // scratch of one gather
   std::vector<int> found;
   std::vector<std::vector<char>> extra;   // records beyond the block (rare), per member
@@ -119,7 +121,7 @@ static int gather(pbd_group* g, const std::vector<char>& active) {
       pbd_handle* h = g->m[i];
       GHIP(g, hipSetDevice(g->dev[i]));
       GHIP(g, hipStreamSynchronize(h->stream));
-      g->found[i] = h->h_cand_count[0];
+      g->found[i] = pbd_i_found(h);
       GMEMBER(g, i, pbd_i_finish_frame(h, g->found[i]));
     }
   }
@@ -186,6 +188,7 @@ static int group_create(const pbd_model_desc* model, const int32_t* fsize, bool 
       if (h) pbd_destroy(h);
       return gfail(g, rc, msg);
     }
+    h->in_group = true;
     g->m.push_back(h);
     g->dev.push_back(devices[i]);
   }
@@ -251,6 +254,27 @@ int pbd_group_comm_size(const pbd_group* g) {
   int n = 0;
   return g->rccl.CommCount(g->comms[0], &n) == 0 ? n : -1;
 }
+// every member gets the setting (checked first: nothing changes unless all accept); pbd_group_detect_u8 defers it to the union
+int pbd_group_set_candidate_filter(pbd_group* g, int mode, float overlap) {
+  if (!g) return PBD_ERR_ARG;
+  if (!(mode == PBD_CAND_RAW || mode == PBD_CAND_SORT || mode == PBD_CAND_SORT_NMS) || !std::isfinite(overlap))
+    return gfail(g, PBD_ERR_ARG, "candidate filter: mode PBD_CAND_RAW / _SORT / _SORT_NMS, finite overlap");
+  for (pbd_handle* h : g->m)
+    if (h->pending) return gfail(g, PBD_ERR_STATE, "a frame is in flight");
+  for (size_t i = 0; i < g->m.size(); ++i) {
+    pbd_handle* h = g->m[i];
+    if ((mode != h->cand_mode || overlap != h->cand_overlap) && h->gexec) {
+      GHIP(g, hipSetDevice(g->dev[i]));
+      hipGraphExecDestroy(h->gexec);
+      h->gexec = nullptr;
+    }
+    h->cand_mode = mode;
+    h->cand_overlap = overlap;
+  }
+  g->cand_mode = mode;
+  g->cand_overlap = overlap;
+  return PBD_OK;
+}
 pbd_handle* pbd_group_member(pbd_group* g, int i) { return (g && i >= 0 && i < (int)g->m.size()) ? g->m[i] : nullptr; }
 
 static int all_levels(pbd_group* g) {   // undo a level sharding left behind by pbd_group_detect_u8
@@ -258,6 +282,7 @@ static int all_levels(pbd_group* g) {   // undo a level sharding left behind by 
   for (size_t i = 0; i < g->m.size(); ++i) {
     hipSetDevice(g->dev[i]);
     GMEMBER(g, i, pbd_set_levels(g->m[i], nullptr, 0));
+    g->m[i]->cand_defer = false;   // (set_levels dropped the plan and its graph)
   }
   g->shard_w = g->shard_h = g->shard_cn = 0;
   return PBD_OK;
@@ -294,7 +319,7 @@ static int batch_impl(pbd_group* g, const uint8_t* const* ims, int nframes, int 
     std::vector<const char*> recs((size_t)g->found[i]);
     for (int j = 0; j < g->found[i]; ++j) recs[j] = rec_ptr(g, i, j);
     int r = pbd_i_emit(g->m[i], recs, heads + (size_t)f * capacity, boxes ? boxes + (size_t)f * capacity * mp * 4 : nullptr,
-                       locs ? locs + (size_t)f * capacity * mp * 3 : nullptr, capacity);
+                       locs ? locs + (size_t)f * capacity * mp * 3 : nullptr, capacity, g->m[i]->out_filtered);
     if (r == PBD_ERR_CAPACITY) { status = gfail(g, r, "frame " + std::to_string(f) + ": output capacity too small"); return PBD_OK; }
     if (r) return gfail(g, r, pbd_last_error(g->m[i]));
     return PBD_OK;
@@ -308,7 +333,7 @@ static int batch_impl(pbd_group* g, const uint8_t* const* ims, int nframes, int 
       pbd_handle* h = g->m[i];
       GHIP(g, hipSetDevice(g->dev[i]));
       GHIP(g, hipStreamSynchronize(h->stream));
-      g->found[i] = h->h_cand_count[0];
+      g->found[i] = pbd_i_found(h);
       GMEMBER(g, i, pbd_i_finish_frame(h, g->found[i]));
       const int f = frame_of[i];
       frame_of[i] = -1;
@@ -366,6 +391,7 @@ static int frame_impl(pbd_group* g, const uint8_t* im, int w, int hgt, int cn, i
       hipSetDevice(g->dev[i]);
       if (sets[i].empty()) sets[i].push_back(nl - 1);   // more members than levels: a duplicate of the smallest level, dropped below
       GMEMBER(g, i, pbd_set_levels(g->m[i], sets[i].data(), (int)sets[i].size()));
+      g->m[i]->cand_defer = true;    // the members return their levels unfiltered: the group filters the union below
     }
     g->shard_w = w; g->shard_h = hgt; g->shard_cn = cn;
   }
@@ -382,8 +408,28 @@ static int frame_impl(pbd_group* g, const uint8_t* im, int w, int hgt, int cn, i
       const int32_t* lc = (const int32_t*)(r + sizeof(pbd_candidate_head)) + (size_t)mp * 4;
       if (seen.insert({hd->level, hd->component, lc[1], lc[0]}).second) recs.push_back(r);
     }
-  if (count) *count = (int)recs.size();
-  rc = pbd_i_emit(g->m[0], recs, heads, boxes, locs, capacity);
+  if (g->cand_mode == PBD_CAND_RAW) {
+    if (count) *count = (int)recs.size();
+    rc = pbd_i_emit(g->m[0], recs, heads, boxes, locs, capacity);
+    if (rc) return gfail(g, rc, pbd_last_error(g->m[0]));
+    return PBD_OK;
+  }
+  // the union in the single-handle order, then the same kernel on member 0 (one small H2D of the gathered records) — the host
+  // functions applied to the unfiltered group output
+  const int nr = (int)recs.size();
+  std::vector<pbd_candidate_head> hh((size_t)std::max(nr, 1));
+  std::vector<int32_t> bb((size_t)std::max(nr, 1) * mp * 4), ll((size_t)std::max(nr, 1) * mp * 3);
+  rc = pbd_i_emit(g->m[0], recs, hh.data(), bb.data(), ll.data(), nr);
   if (rc) return gfail(g, rc, pbd_last_error(g->m[0]));
+  int kept = 0;
+  GHIP(g, hipSetDevice(g->dev[0]));
+  GMEMBER(g, 0, pbd_i_filter_host(g->m[0], g->cand_mode, g->cand_overlap, w, hgt, hh.data(), bb.data(), ll.data(), nr, &kept));
+  if (count) *count = kept;
+  if (kept > capacity) return gfail(g, PBD_ERR_CAPACITY, "output capacity too small");
+  for (int i = 0; i < kept; ++i) {
+    heads[i] = hh[i];
+    if (boxes) memcpy(boxes + (size_t)i * mp * 4, &bb[(size_t)i * mp * 4], sizeof(int32_t) * mp * 4);
+    if (locs) memcpy(locs + (size_t)i * mp * 3, &ll[(size_t)i * mp * 3], sizeof(int32_t) * mp * 3);
+  }
   return PBD_OK;
 }

@@ -290,7 +290,17 @@ struct pbd_handle {
   int16_t* d_extx = nullptr; int16_t* d_exty = nullptr; unsigned long long* d_ext_base = nullptr;
   bool ext_ptr = false;
   bool root_dirty = false;   // pbd_set_root since the last min(): argmin re-thresholds the root tables first
+  // candidate filter (pbd_set_candidate_filter): Candidate::sort (+ nonMaximaSuppression) by k_cand_filter behind k_backtrack
+  int cand_mode = PBD_CAND_RAW; float cand_overlap = 0.f;
+  bool in_group = false;     // member of a pbd_group: the group sets the filter
+  bool cand_defer = false;   // member of a level-sharded pbd_group_detect_u8: unfiltered, the group filters the union on member 0
+  bool out_filtered = false; // the pending frame's records went through k_cand_filter (counts in h_cf_cnt / d_cf_cnt)
+  char* d_cand_raw = nullptr;                           // back-tracking output of RCCL-gathering members when filtering
+  unsigned long long* d_cf_keys = nullptr; unsigned* d_cf_idx = nullptr; int* d_cf_box = nullptr; uint8_t* d_cf_st = nullptr;
+  int* d_cf_cnt = nullptr; int* h_cf_cnt = nullptr;    // [2 + 2 * PBD_MAX_BATCH] (k_cand.hip); h_: pinned
+  unsigned long long* d_cf_mask = nullptr; size_t cf_mask_bytes = 0;   // per-frame masks too large for LDS (frame plan)
 };
+#define PBD_MAX_BATCH 64
 
 // ---- scalar helpers: the reference's std:: overloads resolve on T ---------------
 #ifdef __HIPCC__
@@ -339,7 +349,10 @@ int pbd_i_enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride);         
 int pbd_i_collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* count);
 int pbd_i_finish_frame(pbd_handle* h, int found);
 int pbd_i_emit(pbd_handle* h, const std::vector<const char*>& recs, pbd_candidate_head* heads, int32_t* boxes,
-               int32_t* locs, int capacity);
+               int32_t* locs, int capacity, bool ordered = false);   // ordered: the records are in final order already (k_cand_filter)
+int pbd_i_found(const pbd_handle* h);   // records the pending frame left on the host side (filtered: the kept count)
+int pbd_i_filter_host(pbd_handle* h, int mode, float overlap, int im_w, int im_h, pbd_candidate_head* heads, int32_t* boxes,
+                      int32_t* locs, int count, int* kept);   // pbd_candidates_filter without the argument checks
 #define PBD_FIRST_COPY 192   // candidate records fetched (or gathered) together with the count
 
 // ---- kernel launchers (k_*.hip) ----------------------------------------------
@@ -395,3 +408,18 @@ int dt_debug_trace(unsigned long long* t, unsigned* hw, int* nlaunch);   // prob
 void hog_debug_read(unsigned long long* out);
 void conv_debug_read(unsigned long long* out);
 void launch_nms_map(const float* src, int rows, int cols, int sz, uint8_t* dst, hipStream_t s);
+// candidate sort + painted-box NMS (k_cand.hip): one workgroup per frame
+struct CandFilterArgs {
+  const char* in; const int* in_count; int capacity;   // records (stride bytes each) and their device count
+  size_t stride; int mp;
+  int nlevels;                  // frame of a record = level / nlevels (0: one frame)
+  const BackLevel* back;        // tie key: root element offset through back[level * ncomp + comp]; null: input position
+  const char* rootv_base; int ts, ncomp;
+  int nms; double overlap; int im_w, im_h;
+  unsigned long long* keys; unsigned* idx;   // [2 * capacity]
+  int* box; unsigned char* st;               // [capacity][4], [capacity]
+  unsigned long long* gmask;                 // [nframes][cand_filter_mask_bytes / 8] when the mask does not fit LDS
+  char* out; int* cnt_out;                   // kept records; counts [2 + 2 * nframes]
+};
+size_t cand_filter_mask_bytes(int w, int h);
+void launch_cand_filter(const CandFilterArgs& a, int nframes, hipStream_t s);

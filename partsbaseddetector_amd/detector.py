@@ -207,8 +207,10 @@ class PartsBasedDetector:
     or np.float64 (ros/Node.hpp:121, cells/detect.cpp:93) picks the instantiation."""
 
     def __init__(self, device: int = 0, conv_mode: int = capi.PBD_CONV_AUTO, max_candidates: int = 4096,
-                 level_begin: int = 0, level_end: int = 0, dtype=np.float32):
+                 level_begin: int = 0, level_end: int = 0, dtype=np.float32, cand_filter=None):
+        """cand_filter=(mode, overlap): see setCandidateFilter."""
         self._device, self._conv, self._cap = device, conv_mode, max_candidates
+        self._cand_filter = cand_filter
         self._dtype = np.dtype(dtype)
         self._lb, self._le = level_begin, level_end
         self._h: Optional[capi.Handle] = None
@@ -221,11 +223,20 @@ class PartsBasedDetector:
     def distributeModel(self, model: Model) -> None:
         """src/PartsBasedDetector.cpp:102-127."""
         self._name = model.name
-        self._h = capi.Handle(model, self._device, self._conv, self._cap, 0, self._lb, self._le, dtype=self._dtype)
+        self._h = capi.Handle(model, self._device, self._conv, self._cap, 0, self._lb, self._le, dtype=self._dtype,
+                              cand_filter=self._cand_filter)
         self.features_ = HOGFeatures(self._h)
         self.convolution_engine_ = SpatialConvolutionEngine(self._h)
         self.convolution_engine_.setFilters(model.filtersw)
         self.dp_ = DynamicProgram(self._h)
+
+    def setCandidateFilter(self, mode: int, overlap: float = 0.0) -> None:
+        """Candidate.sort (capi.PBD_CAND_SORT), or sort + Candidate.nonMaximaSuppression(overlap) (capi.PBD_CAND_SORT_NMS), of
+        every detect() on the GPU — what the reference's callers run after detect() (ros/Node.cpp:192-196); capi.PBD_CAND_RAW
+        (the default) turns it off.  Kept across distributeModel()."""
+        if self._h is not None:
+            self._h.set_candidate_filter(mode, overlap)
+        self._cand_filter = (mode, overlap)
 
     @property
     def handle(self) -> capi.Handle:

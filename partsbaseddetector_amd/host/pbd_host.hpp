@@ -334,6 +334,8 @@ class Device {
   }
   ~Device() { if (h) pbd_destroy(h); }
   void check(int rc) const { if (rc != PBD_OK) throw Exception(rc, pbd_last_error(h)); }
+  // Candidate::sort (+ nonMaximaSuppression(overlap)) of every detect() on the GPU: PBD_CAND_RAW / _SORT / _SORT_NMS
+  void setCandidateFilter(int mode, float overlap = 0.f) { check(pbd_set_candidate_filter(h, mode, overlap)); }
 };
 
 // ---- include/IFeatures.hpp:49-73 --------------------------------------------------------------
@@ -579,6 +581,7 @@ class PartsBasedDetector {
   DynamicProgram<T> dp_;
   Parts parts_;
   int device_, conv_mode_, ncomponents_ = 0;
+  int cand_mode_ = PBD_CAND_RAW; float cand_overlap_ = 0.f;
  public:
   int max_candidates_ = 4096;
   explicit PartsBasedDetector(int device = 0, int conv_mode = PBD_CONV_AUTO, int max_candidates = 4096)
@@ -600,6 +603,14 @@ class PartsBasedDetector {
     convolution_engine_->setFilters(model.filters());
     parts_ = Parts(model);                         // :121-122
     dp_ = DynamicProgram<T>(dev_);
+    if (cand_mode_ != PBD_CAND_RAW) dev_->setCandidateFilter(cand_mode_, cand_overlap_);
+  }
+  // What the reference's callers do after detect() — Candidate::sort, then Candidate::nonMaximaSuppression(im, candidates,
+  // overlap) (ros/Node.cpp:192-196, cells/detect.cpp:237-238) — done by the GPU inside detect(): PBD_CAND_SORT or
+  // PBD_CAND_SORT_NMS (PBD_CAND_RAW: off, the default).  Kept across distributeModel().
+  void setCandidateFilter(int mode, float overlap = 0.f) {
+    if (dev_) dev_->setCandidateFilter(mode, overlap);
+    cand_mode_ = mode; cand_overlap_ = overlap;
   }
   void detect(const Mat& im, vectorCandidate& candidates) { detect(im, Mat(), candidates); }
   // src/PartsBasedDetector.cpp:69-95: fused path, everything stays in HBM; `depth` ignored (:91-93)
