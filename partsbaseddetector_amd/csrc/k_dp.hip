@@ -67,19 +67,6 @@ void dt_debug_read(unsigned long long* out) {
 void dt_debug_read(unsigned long long* out) { for (int i = 0; i < 8; ++i) out[i] = 0; }
 #endif
 
-// LDS per block: a header (per-line and per-lane descriptors, segment table), ONE table of exact reciprocals
-// 1/dx, dx < len (double[S], shared by all lines whatever their map: dt_core.hpp), and per line
-// {(y, z) : T2[S]; B : u8[S] (S <= 256) or u16[S]}.
-// 9 bytes per line element for float: the lines resident on a CU are bounded by these bytes.
-#define DT_SEGS 72                                   // SEG entries: P + 1 <= 65 starts, then {0, len} for a line redone as one segment
-__host__ __device__ inline size_t dt_hdr_bytes(int nt, int ts, int its, int lpb) {   // per line 16 B, per lane T + 4 IT
-  return ((size_t)lpb * 16 + DT_SEGS * 4 + (size_t)nt * (ts + 4 * its) + 15) & ~(size_t)15;
-}
-size_t dt_lds_bytes(int stride, int lpb, int ts, int nt) {   // ts = sizeof(T): (y, z) is a float or a double pair
-  const int its = stride <= 256 ? 1 : 2;
-  return (size_t)lpb * stride * (2 * ts + its) + dt_hdr_bytes(nt, ts, its, lpb) + (((size_t)stride + 1) & ~(size_t)1) * 8 + 16;
-}
-
 // ---- message fold (fold mode) -------------------------------------------------------------------------------
 // The reference sends a child's message as soon as the child has been transformed (src/DynamicProgram.cpp:134-156):
 //   for every parent mixture m: weighted[k] = sdt_k + bias(k)[m] (:139), (maxv, maxi) = reduceMax (:143: init -inf,

@@ -9,10 +9,8 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <new>
 #include "pbd_internal.hpp"
-#include "dt_core.hpp"   // dt_segments: the planner and the kernels share one definition
 
 #define HIPCHK(h, call)                                                                  \
   do {                                                                                   \
@@ -47,221 +45,8 @@ static int fail(pbd_handle* h, int code, const std::string& msg) {
 #define ON_DEVICE(h) do { HIPCHK(h, hipSetDevice((h)->opt.device)); CLEAR_STICKY(); } while (0)
 
 // ---------------------------------------------------------------------------
-// pyramid geometry — HOGFeatures<T>::pyramid, src/HOGFeatures.cpp:98-127,174-175
-// ---------------------------------------------------------------------------
-static inline int cv_round_f(float v) { return (int)std::lrint((double)v); }
-
-static int compute_geometry(int w, int h, int sbin, int interval, int* nlevels, Level* lv) {
-  const float sf = (float)std::pow(2.0, (double)(1.0f / (float)interval));  // HOGFeatures.hpp:78
-  const float fw = (float)w, fh = (float)h;
-  const float mn = fh < fw ? fh : fw;
-  const float r = std::log(mn / (5.0f * (float)sbin)) / std::log(sf);          // :99 (float math)
-  const int n = (int)(1.0f + std::floor(r));
-  if (n < interval || n > PBD_MAX_LEVELS) return -1;
-  for (int i = 0; i < interval; ++i) {
-    const float f = (float)(1.0f / std::pow((double)sf, (double)i));            // :116
-    lv[i].iw = cv_round_f(fw * f);
-    lv[i].ih = cv_round_f(fh * f);
-    lv[i].scale = (float)(std::pow((double)sf, (double)i) * (double)sbin);      // :118
-    for (int j = i + interval; j < n; j += interval) {
-      lv[j].iw = (lv[j - interval].iw + 1) / 2;                                 // :122 pyrDown
-      lv[j].ih = (lv[j - interval].ih + 1) / 2;
-      lv[j].scale = 2 * lv[j - interval].scale;                                 // :124
-    }
-  }
-  for (int l = 0; l < n; ++l) {
-    lv[l].bw = (int)std::round((float)lv[l].iw / (float)sbin);                  // :174
-    lv[l].bh = (int)std::round((float)lv[l].ih / (float)sbin);
-    lv[l].cw = std::max(lv[l].bw - 2, 0);                                       // :175
-    lv[l].ch = std::max(lv[l].bh - 2, 0);
-  }
-  *nlevels = n;
-  return 0;
-}
-
-// ---------------------------------------------------------------------------
 // model
 // ---------------------------------------------------------------------------
-static int nmix_of(const pbd_handle* h, int fp) { return h->mix_offset[fp + 1] - h->mix_offset[fp]; }
-
-static int ingest_model(pbd_handle* h, const pbd_model_desc* m) {
-  if (!m || !m->filters || !m->defw || !m->anchors || !m->biasw || !m->part_offset || !m->parentid ||
-      !m->mix_offset || !m->filterid || !m->defid || !m->biasid)
-    return fail(h, PBD_ERR_ARG, "model: null pointer");
-  if (m->flen != PBD_FLEN || m->norient != PBD_NORIENT)
-    return fail(h, PBD_ERR_UNSUPPORTED, "model: only flen=32 / norient=18 HOG is supported");
-  if (m->nfilters <= 0 || (!h->mixed && (m->kh <= 0 || m->kw <= 0 || m->kh > 9 || m->kw > 9)) || m->sbin <= 0 || m->interval <= 0 ||
-      m->interval > 16 || m->ncomponents <= 0)
-    return fail(h, PBD_ERR_ARG, "model: bad sizes");
-  if (m->ndefs < 0 || m->nbias <= 0) return fail(h, PBD_ERR_ARG, "model: ndefs >= 0 and nbias > 0 required");
-  const int nc = m->ncomponents;
-  if (m->part_offset[0] != 0) return fail(h, PBD_ERR_ARG, "model: part_offset[0] must be 0");
-  for (int c = 0; c < nc; ++c)
-    if (m->part_offset[c + 1] <= m->part_offset[c]) return fail(h, PBD_ERR_ARG, "model: part_offset must be strictly increasing");
-  h->part_offset.assign(m->part_offset, m->part_offset + nc + 1);
-  const int np = h->part_offset[nc];
-  if (m->mix_offset[0] != 0) return fail(h, PBD_ERR_ARG, "model: mix_offset[0] must be 0");
-  for (int fp = 0; fp < np; ++fp)
-    if (m->mix_offset[fp + 1] <= m->mix_offset[fp]) return fail(h, PBD_ERR_ARG, "model: mix_offset must be strictly increasing");
-  h->parentid.assign(m->parentid, m->parentid + np);
-  h->mix_offset.assign(m->mix_offset, m->mix_offset + np + 1);
-  const int nm = h->mix_offset[np];
-  h->filterid.assign(m->filterid, m->filterid + nm);
-  h->defid.assign(m->defid, m->defid + nm);
-  h->biasid.assign(m->biasid, m->biasid + nm);
-  size_t nweights = (size_t)m->nfilters * m->kh * m->kw * m->flen;   // mixed banks (pbd_create_sized): sum of kh_i kw_i flen
-  if (h->mixed) {
-    nweights = 0;
-    for (int n = 0; n < m->nfilters; ++n) nweights += (size_t)h->fkh[n] * h->fkw[n] * m->flen;
-  }
-  h->filters.assign(m->filters, m->filters + nweights);
-  h->defw.assign(m->defw, m->defw + (size_t)m->ndefs * 4);
-  h->anchors.assign(m->anchors, m->anchors + (size_t)m->ndefs * 2);
-  h->biasw.assign(m->biasw, m->biasw + m->nbias);
-  h->md = *m;
-  h->md.filters = h->filters.data(); h->md.defw = h->defw.data(); h->md.anchors = h->anchors.data();
-  h->md.biasw = h->biasw.data(); h->md.part_offset = h->part_offset.data(); h->md.parentid = h->parentid.data();
-  h->md.mix_offset = h->mix_offset.data(); h->md.filterid = h->filterid.data(); h->md.defid = h->defid.data();
-  h->md.biasid = h->biasid.data();
-
-  h->parts.resize(np);
-  h->comp_plane0.assign(nc + 1, 0);
-  h->max_parts = 0;
-  int slot_next = 0, plane_next = 0;
-  bool aliasing = false;
-  for (int c = 0; c < nc; ++c) {
-    const int p0 = h->part_offset[c], cnp = h->part_offset[c + 1] - p0;
-    if (cnp <= 0) return fail(h, PBD_ERR_ARG, "model: empty component");
-    if (cnp > 256) return fail(h, PBD_ERR_UNSUPPORTED, "model: more than 256 parts in a component");   // BT_MAXP (k_backtrack)
-    h->max_parts = std::max(h->max_parts, cnp);
-    h->comp_plane0[c] = plane_next;
-    std::map<int, int> slot_of;   // filter id -> slot (ncscores is indexed by filter id, DynamicProgram.cpp:93)
-    std::map<int, int> uses;
-    std::vector<int> nchild(cnp, 0);
-    for (int p = 1; p < cnp; ++p) {
-      const int par = h->parentid[p0 + p];
-      if (par < 0 || par >= p) return fail(h, PBD_ERR_ARG, "model: parts must be ordered parent < child");
-      nchild[par]++;
-    }
-    for (int p = 0; p < cnp; ++p) {
-      PartInfo& P = h->parts[p0 + p];
-      P.comp = c; P.p = p; P.parent = (p == 0) ? -1 : h->parentid[p0 + p];
-      P.K = nmix_of(h, p0 + p);
-      if (P.K <= 0 || P.K > PBD_MAX_MIX) return fail(h, PBD_ERR_UNSUPPORTED, "model: 1..16 mixtures per part");
-      P.leaf = (nchild[p] == 0);
-      const int fm0 = h->mix_offset[p0 + p];
-      for (int m2 = 0; m2 < P.K; ++m2) {
-        const int fid = h->filterid[fm0 + m2];
-        if (fid < 0 || fid >= m->nfilters) return fail(h, PBD_ERR_ARG, "model: filterid out of range");
-        P.filterid.push_back(fid);
-        P.defid.push_back(h->defid[fm0 + m2]);
-        P.biasid.push_back(h->biasid[fm0 + m2]);
-        if (!slot_of.count(fid)) slot_of[fid] = slot_next++;
-        P.slot.push_back(slot_of[fid]);
-        if (++uses[fid] > 1) aliasing = true;
-        if (p > 0) {
-          const int did = h->defid[fm0 + m2];
-          if (did < 0 || did >= m->ndefs) return fail(h, PBD_ERR_ARG, "model: defid out of range");
-          if (h->defw[did * 4] == 0.f || h->defw[did * 4 + 2] == 0.f)
-            return fail(h, PBD_ERR_ARG, "model: quadratic deformation weights must be non-zero "
-                                        "(include/DistanceTransform.hpp:99 divides by 2a)");
-        }
-        const int bid = h->biasid[fm0 + m2];
-        const int L = (p == 0) ? 1 : nmix_of(h, p0 + h->parentid[p0 + p]);
-        if (bid < 0 || bid + L > m->nbias) return fail(h, PBD_ERR_ARG, "model: biasid out of range");
-      }
-      P.plane0 = -1;
-      if (p > 0) {
-        P.plane0 = plane_next;
-        plane_next += nmix_of(h, p0 + P.parent);
-      }
-    }
-  }
-  h->comp_plane0[nc] = plane_next;
-  h->nslots = slot_next;
-  h->nplanes = plane_next;
-
-  // ---- round schedule -------------------------------------------------------
-  // DT of a part runs once all its children have sent their message (DynamicProgram.cpp:95 walks
-  // p = P-1..1 with parent < child): round = height of the part.  Messages into one parent are
-  // float adds in DESCENDING child order (:156); to keep those bits, a child's message is folded
-  // no earlier than every higher-indexed sibling's (reduce round = max over them), and siblings
-  // folded in the same round go through ONE reduce job that adds them in that order.
-  // fold mode (messages folded by the consumer, no accumulated planes): needs every part's accumulator to be its own
-  // (no filter id shared inside a component: the reference's ncscores is indexed by FILTER id, so two parts with
-  // one id would share an accumulator) and its mixtures / its children's to fit the register arrays of the fold
-  {
-    std::vector<int> fuse(m->nfilters, 0);
-    h->unique_filters = true;
-    for (int fm = 0; fm < nm; ++fm) if (++fuse[h->filterid[fm]] > 1) h->unique_filters = false;   // (also across components: face-like models share a pool)
-  }
-  h->fold = !aliasing && h->opt.reserved[1] != 1;
-  if (const char* e = PBD_PROBE_ENV("PBD_DP_MODE")) h->fold = h->fold && atoi(e) != 1;   // A/B: the three-kernel structure
-  {
-    std::vector<int> nchild_flat(np, 0);
-    for (int fp = 0; fp < np; ++fp) {
-      if (h->parts[fp].K > PBD_FOLD_MAXMIX) h->fold = false;
-      h->fold_mix = std::max(h->fold_mix, h->parts[fp].K);
-      if (h->parts[fp].p > 0 && ++nchild_flat[h->part_offset[h->parts[fp].comp] + h->parts[fp].parent] > PBD_MAX_CH) h->fold = false;
-    }
-  }
-  h->rounds.clear();
-  h->red_rounds.clear();
-  if (aliasing) {  // shared filter ids inside a component: keep the reference's strictly sequential order
-    for (int c = 0; c < nc; ++c)
-      for (int p = h->part_offset[c + 1] - h->part_offset[c] - 1; p > 0; --p) {
-        h->rounds.push_back(std::vector<int>(1, h->part_offset[c] + p));
-        h->red_rounds.push_back({std::vector<int>(1, h->part_offset[c] + p)});
-      }
-  } else {
-    std::vector<int> height(np, 0), rround(np, 0);
-    int nrounds = 0;
-    for (int c = 0; c < nc; ++c) {
-      const int p0 = h->part_offset[c], cnp = h->part_offset[c + 1] - p0;
-      for (int p = cnp - 1; p > 0; --p) {  // children before parents (parent < child)
-        const int par = h->parts[p0 + p].parent;
-        height[p0 + par] = std::max(height[p0 + par], height[p0 + p] + 1);
-      }
-      for (int p = cnp - 1; p > 0; --p) {  // descending index: higher siblings first
-        int rr = height[p0 + p];
-        for (int q = p + 1; q < cnp; ++q)
-          if (h->parts[p0 + q].parent == h->parts[p0 + p].parent) rr = std::max(rr, rround[p0 + q]);
-        rround[p0 + p] = rr;
-        nrounds = std::max(nrounds, rr + 1);
-      }
-    }
-    h->rounds.assign(nrounds, {});
-    std::vector<std::vector<int>> red(nrounds);
-    for (int fp = 0; fp < np; ++fp) {
-      if (h->parts[fp].p == 0) continue;
-      h->rounds[height[fp]].push_back(fp);
-      red[rround[fp]].push_back(fp);
-    }
-    // waves: at most PBD_MAX_CH children of one parent per reduce job; overflow goes to a later wave
-    h->red_rounds.assign(nrounds, {});
-    for (int r = 0; r < nrounds; ++r) {
-      std::vector<int> rest(red[r].rbegin(), red[r].rend());  // descending flat index
-      while (!rest.empty()) {
-        std::vector<int> wave, next;
-        std::map<int, int> cnt;
-        for (int fp : rest) {
-          const int parent_fp = h->part_offset[h->parts[fp].comp] + h->parts[fp].parent;
-          if (cnt[parent_fp] < PBD_MAX_CH && !std::count_if(next.begin(), next.end(), [&](int g) {
-                return h->part_offset[h->parts[g].comp] + h->parts[g].parent == parent_fp; })) {
-            cnt[parent_fp]++;
-            wave.push_back(fp);
-          } else {
-            next.push_back(fp);
-          }
-        }
-        h->red_rounds[r].push_back(wave);
-        rest.swap(next);
-      }
-    }
-  }
-  return PBD_OK;
-}
-
 // The weights of one bank of nf filters of ONE size (the whole model, or one size group of a mixed bank) in every layout the filter-bank
 // kernels read: g.nfpad, g.d_wT (transposed, converted to T, the 16-byte B copies and the border cell), and for a split bank g.d_wS /
 // g.d_oscale.  *bytes: device bytes held.
@@ -332,27 +117,20 @@ static int upload_bank(pbd_handle* h, const float* filt, int nf, int kh, int kw,
 static int upload_model(pbd_handle* h) {
   const pbd_model_desc& m = h->md;
   size_t bank_bytes = 0;
-  h->split_parts = h->conv_mode == PBD_CONV_SPLIT ? 3 : h->conv_mode == PBD_CONV_SPLIT_F16 ? 2 : 0;
   if (!h->mixed) {
     SizeGroup g;
     int rc = upload_bank(h, h->filters.data(), m.nfilters, m.kh, m.kw, g, &bank_bytes);
     h->d_wT = g.d_wT; h->d_wS = g.d_wS; h->d_split_oscale = g.d_oscale; h->nfpad = g.nfpad;
     if (rc) return rc;
   } else {
-    // size groups: runs of one kh x kw in the internal (size-sorted) filter order, each uploaded as a uniform bank of its own
+    // size groups (plan_model): each uploaded as a uniform bank of its own
     size_t off = 0;
-    for (int n = 0; n < m.nfilters;) {
-      int e = n;
-      while (e < m.nfilters && h->fkh[e] == h->fkh[n] && h->fkw[e] == h->fkw[n]) ++e;
-      h->groups.emplace_back();
-      SizeGroup& g = h->groups.back();
-      g.n0 = n;
+    for (SizeGroup& g : h->groups) {
       size_t b = 0;
-      int rc = upload_bank(h, h->filters.data() + off, e - n, h->fkh[n], h->fkw[n], g, &b);
+      int rc = upload_bank(h, h->filters.data() + off, g.nf, g.kh, g.kw, g, &b);
       if (rc) return rc;
       bank_bytes += b;
-      off += (size_t)(e - n) * h->fkh[n] * h->fkw[n] * m.flen;
-      n = e;
+      off += (size_t)g.nf * g.kh * g.kw * m.flen;
     }
   }
   // orientation-snap table of the HOG kernel (k_hog.hip): 511 x 511 bytes, computed on the device by the reference's own
@@ -462,92 +240,18 @@ static bool all_active_set(const pbd_handle* h, const std::vector<char>& v, int 
   return true;
 }
 
-// DT block geometry under an LDS budget.  stride = LDS elements per line: >= len + 1 and ODD — the (y, z) pairs of
-// element e of consecutive lines are then 2 * (stride mod 32) banks apart instead of in the same banks (lanes of
-// different lines work on similar element indices at the same time: with an even stride of 160 every LDS access
-// of the scan was an lpb-way bank conflict); lpb = lines per block: 4 .. lanes of the block (plain), or a whole
-// number of rows x the K mixtures of the part (fold: unit = K).
-static int dt_stride_for(int len) { return (len + 1) | 1; }
-static int dt_lpb_for(int stride, int len, int unit, size_t budget, int ts, int nt, int seg, bool round_lanes) {
-  const int lmin = unit > 1 ? unit : 4;
-  int lpb = std::min(nt, 128);   // at most one line per lane
-  if (unit > 1) lpb = std::max(unit, lpb / unit * unit);
-  while (lpb > lmin && dt_lds_bytes(stride, lpb, ts, nt) > budget) lpb -= (unit > 1 ? unit : 1);
-  // plain: the nt / lpb lanes of a line are a whole number, so 45 lines that fit would leave 128 - 2 * 45 lanes idle and
-  // every line with two segments where 42 lines get three: the largest lpb <= the fit that uses all lanes
-  if (round_lanes && unit <= 1 && lpb > lmin) lpb = std::max(lmin, nt / ((nt + lpb - 1) / lpb));
-  // The nt / lpb lanes that share a line scan one segment of it each (dt_core.hpp), and a block lasts as long as
-  // its segments are: with a target segment length, lines are given up for lanes per line where the budget
-  // would put so many lines into a block that each is left with one or two lanes.
-  if (seg > 0) {
-    const int P = std::max(1, std::min(nt / 4, (len + seg - 1) / seg));
-    int cap = std::max(lmin, nt / P);
-    if (unit > 1) cap = std::max(unit, cap / unit * unit);
-    lpb = std::min(lpb, cap);
-  }
-  return lpb;
-}
-// fold >= 0: the group is one part at one level, a block = whole rows of its nmaps mixtures
-// round_lanes: plain groups only — the largest lines-per-block <= the fit that leaves no lane idle (a per-launch choice of plan_frame)
-static DtGroup dt_group(int map0, int nmaps, int nlines, int len, size_t budget, int ts, int nt, int seg, int fold = -1, bool round_lanes = true) {
-  DtGroup g{};
-  g.map0 = map0; g.nmaps = nmaps; g.nlines = nlines; g.len = len; g.fold = fold;
-  g.stride = dt_stride_for(len);
-  g.lpb = dt_lpb_for(g.stride, len, fold >= 0 ? nmaps : 1, budget, ts, nt, seg, round_lanes);
-  // wave-uniform quotients of the block's index arithmetic, as constants (pbd_internal.hpp)
-  g.nsub = nt / g.lpb;
-  g.P = dt_segments(g.nsub, len);
-  g.chunk = (len + g.nsub - 1) / g.nsub;
-  g.magic_lpb = dt_magic((unsigned)g.lpb);
-  g.magic_nlines = dt_magic((unsigned)nlines);
-  g.magic_P = dt_magic((unsigned)g.P);
-  return g;
-}
-// maps: the descriptor table the group indexes (plain groups: a block whose lines are contiguous in memory gets their address, DtTask::src0)
-static void dt_add_tasks(const DtGroup& g, std::vector<DtTask>& out, const std::vector<DtMap>* maps = nullptr, int ts = 4) {
-  if (g.fold >= 0) {
-    const int R = g.lpb / g.nmaps;
-    for (int r0 = 0; r0 < g.nlines; r0 += R) out.push_back(DtTask{r0, std::min(R, g.nlines - r0) * g.nmaps, 0, r0, g, nullptr});
-  } else {
-    const int total = g.nmaps * g.nlines;
-    const size_t map_bytes = (size_t)g.nlines * g.len * ts;
-    for (int g0 = 0; g0 < total; g0 += g.lpb) {
-      DtTask t{g0, std::min(g.lpb, total - g0), g0 / g.nlines, g0 % g.nlines, g, nullptr};
-      if (maps && g.len > 1) {
-        const int mlast = (g0 + t.nl - 1) / g.nlines;
-        bool contig = true;
-        for (int m = t.m0; m < mlast && contig; ++m)
-          contig = (const char*)(*maps)[(size_t)g.map0 + m + 1].src == (const char*)(*maps)[(size_t)g.map0 + m].src + map_bytes;
-        if (contig) t.src0 = (const char*)(*maps)[(size_t)g.map0 + t.m0].src + (size_t)t.l0 * g.len * ts;
-      }
-      out.push_back(t);
-    }
-  }
-}
-// DtGroup::fused (dt_core.hpp: dt_isect's FUSED form, the read-out's fused sum): float maps whose a and b are converted floats — the model's
-// weights always (dt_map), pbd_dt2d's caller may hand in any double — on lines short enough for the products to be exact in fp64
-static void dt_mark_fused(std::vector<DtTask>& tasks, const DtMap* maps, int ts) {   // (and the group's pointer layout: DT_G_NATURAL)
-  for (DtTask& t : tasks) {
-    DtGroup& g = t.g;
-    bool ok = ts == 4 && g.len <= DT_FUSE_MAXLEN;
-    for (int m = 0; m < g.nmaps && ok; ++m) {
-      const DtMap& mp = maps[g.map0 + m];
-      ok = (double)(float)mp.a == mp.a && (double)(float)mp.b == mp.b && (long long)g.len + std::abs((long long)mp.os) <= DT_FUSE_MAXLEN;
-    }
-    // (the pointer layout is a property of the pass: every map of a group has the same)
-    g.fused = (ok ? DT_G_FUSED : 0) | (g.nmaps > 0 && maps[g.map0].ptr_natural ? DT_G_NATURAL : 0);
-  }
-}
-static DtMap dt_map(const void* src, void* dst, int16_t* ptr, float wq, float wl, int os, int natural) {
-  DtMap m{};
-  m.src = src; m.dst = dst; m.ptr = ptr;
-  m.a = -(double)wq; m.b = -(double)wl;      // Quadratic fx(-w0, -w1), fy(-w2, -w3) (src/DynamicProgram.cpp:125-127)
-  m.r2a = 1.0 / (2.0 * m.a);                 // IEEE division (dt_core.hpp: dt_isect)
-  m.os = os; m.ptr_natural = natural;
-  return m;
+// Probe and tune builds: the planner's DT knobs from the environment (product builds: the defaults)
+static PlanKnobs read_plan_knobs() {
+  PlanKnobs k;
+  if (const char* e = PBD_PROBE_ENV("PBD_DT_NT")) k.dt_nt = std::max(64, std::min(256, atoi(e) & ~63));
+  if (const char* e = PBD_PROBE_ENV("PBD_DT_SEG")) k.dt_seg = atoi(e);
+  if (const char* e = PBD_PROBE_ENV("PBD_DT_BUDGET_KB")) k.dt_budget_kb = atoi(e);
+  if (const char* e = PBD_PROBE_ENV("PBD_DT_BUDGET_B")) k.dt_budget_b = atoi(e);
+  if (const char* e = PBD_PROBE_ENV("PBD_DT_XCD_CHUNK")) k.xcd_chunk = atoi(e);
+  return k;
 }
 
-static int depth_esz(int depth) { return depth == PBD_DEPTH_8U ? 1 : depth == PBD_DEPTH_16U ? 2 : depth == PBD_DEPTH_32F ? 4 : depth == PBD_DEPTH_64F ? 8 : 0; }
+// The frame plan of one geometry (pbd_plan.cpp): buffers, then every work table, uploaded once and reused
 static int plan_frame(pbd_handle* h, int w, int hgt, int cn, int batch = 1, int depth = PBD_DEPTH_8U) {
   if (h->fw == w && h->fh == hgt && h->fcn == cn && h->batch == batch && h->fdepth == depth) return PBD_OK;
   if (cn != 1 && cn != 3) return fail(h, PBD_ERR_UNSUPPORTED, "image: 1 or 3 channels");
@@ -557,521 +261,53 @@ static int plan_frame(pbd_handle* h, int w, int hgt, int cn, int batch = 1, int 
   if (batch < 1 || batch > 64) return fail(h, PBD_ERR_ARG, "batch: 1..64 frames");
   hipStreamSynchronize(h->stream);
   free_frame(h);
-  const pbd_model_desc& m = h->md;
-  int n = 0;
-  h->lv.assign((size_t)PBD_MAX_LEVELS * batch, Level{});
-  if (w < 3 || hgt < 3 || compute_geometry(w, hgt, m.sbin, m.interval, &n, h->lv.data()))
-    return fail(h, PBD_ERR_ARG, "image too small: the pyramid needs at least `interval` levels "
-                                "(src/HOGFeatures.cpp:99,114)");
-  const int n1 = n;             // levels of one frame
-  h->nlevels = n1; h->batch = batch; h->nvl = n1 * batch;
-  h->first_copy = kFirstCopy * batch;
-  h->lv.resize(h->nvl);
-  for (int f = 1; f < batch; ++f)
-    for (int l = 0; l < n1; ++l) h->lv[f * n1 + l] = h->lv[l];
-  n = h->nvl;                   // from here on `n` counts the virtual levels (frame f's level l = f * n1 + l)
-  int lb = h->opt.level_begin, le = h->opt.level_end;
-  if (le <= 0 || le > n1) le = n1;
-  if (lb < 0) lb = 0;
-  size_t cells = 0, pyr = 0;
-  for (int vl = 0; vl < n; ++vl) {
-    Level& L = h->lv[vl];
-    const int l = vl % n1;
-    L.active = (l >= lb && l < le) && (h->level_set.empty() || (l < (int)h->level_set.size() && h->level_set[l]));
-    if (L.cw > 32767 || L.ch > 32767) return fail(h, PBD_ERR_UNSUPPORTED, "level too large for 16-bit pointers");
-    // the fold loader addresses a level's planes with 32-bit offsets: cell * sizeof(T) and plane * cells + cell (<= 8 planes of a child)
-    if ((size_t)L.cw * L.ch >= ((size_t)1 << 28)) return fail(h, PBD_ERR_UNSUPPORTED, "level too large (2^28 cells)");
-    L.img_off = pyr; pyr += (size_t)L.iw * L.ih * cn * esz;
-    L.cell_off = cells; cells += (size_t)L.cw * L.ch;
-  }
-  h->cells = cells; h->pyr_bytes = pyr;
-  if (cells >= (1u << 31)) return fail(h, PBD_ERR_UNSUPPORTED, "frame too large");
-  int rc;
-  if ((rc = dev_alloc(h, &h->d_img, (size_t)w * hgt * cn * esz * batch))) return rc;
-  {  // image pyramid jobs: the first octave of every frame from the frame (tightly packed, back to back), then the chains
-    std::vector<PyrJob> jobs;
-    h->pyr_launches.clear();
-    pbd_handle::PyrLaunch R{0, 0, 1, 1, 1};
-    for (int f = 0; f < batch; ++f)
-      for (int i = 0; i < m.interval; ++i) {
-        const Level& L = h->lv[f * n1 + i];
-        jobs.push_back(PyrJob{(unsigned long long)f * w * hgt * cn * esz, (unsigned long long)L.img_off, w, hgt, L.iw, L.ih});
-        R.maxpix = std::max(R.maxpix, L.iw * L.ih);
-      }
-    R.njobs = (int)jobs.size();
-    h->pyr_launches.push_back(R);
-    for (int base = m.interval; base < n1; base += m.interval) {
-      pbd_handle::PyrLaunch D{(int)jobs.size(), 0, 1, 1, 1};
-      for (int f = 0; f < batch; ++f)
-        for (int j = base; j < std::min(base + m.interval, n1); ++j) {
-          const Level &S = h->lv[f * n1 + j - m.interval], &L = h->lv[f * n1 + j];
-          jobs.push_back(PyrJob{(unsigned long long)S.img_off, (unsigned long long)L.img_off, S.iw, S.ih, L.iw, L.ih});
-          D.maxpix = std::max(D.maxpix, L.iw * L.ih);
-          D.maxw = std::max(D.maxw, L.iw); D.maxh = std::max(D.maxh, L.ih);
-        }
-      D.njobs = (int)jobs.size() - D.job0;
-      h->pyr_launches.push_back(D);
-    }
-    if ((rc = dev_upload(h, &h->d_pyrjobs, jobs))) return rc;
-  }
-  const size_t ts = (size_t)h->ts;   // sizeof(T); T buffers are char* addressed as elements * ts
-  if ((rc = dev_alloc(h, &h->d_resp, cells * m.nfilters * ts))) return rc;
-  // Memory plan.  Default: every stage buffer has its own allocation and stays valid after detect() (the parity
-  // tests read features / responses / tables of a finished frame).  Compact (fold structure, every filter id used by
-  // one mixture only; chosen automatically for large frames — the responses alone over 400 MB, e.g. 1920x1080 —
-  // or forced with dp_mode 2): buffers that are never live together share memory:
-  //   * a mixture's distance-transformed scores overwrite its own raw response plane (its x pass has consumed the
-  //     plane before its y pass writes it; nothing else reads the raw plane of a non-root part);
-  //   * the level images + HOG features (dead once the filter bank has run) share one region with the x pass's
-  //     per-round output + the Ik planes (first written by the DP);
-  // 1920x1080, person model: 1.47 GB instead of 3.3 GB.  After min() the image / feature / response getters of a
-  // compact handle answer PBD_ERR_STATE (the buffers have been reused).
-  size_t act_cells0 = 0;
-  for (int l = 0; l < n; ++l) if (h->lv[l].active) act_cells0 += (size_t)h->lv[l].cw * h->lv[l].ch;
-  size_t maxK0 = 1;
-  for (auto& rnd : h->rounds) { size_t k = 0; for (int fp : rnd) k += h->parts[fp].K; maxK0 = std::max(maxK0, k); }
-  h->compact = h->fold && h->unique_filters && (h->opt.reserved[1] == 2 || (h->opt.reserved[1] == 0 && cells * m.nfilters * ts > ((size_t)400 << 20)));
-  const size_t pk_bytes = cells * std::max(h->nplanes, 1), feat_bytes = cells * PBD_FLEN * ts;
-  const size_t al = 256, pyr_al = (pyr + al - 1) / al * al, pk_al = (pk_bytes + al - 1) / al * al;
-  if (h->compact) {
-    char* u = nullptr;
-    if ((rc = dev_alloc(h, &u, std::max(pyr_al + feat_bytes, pk_al + maxK0 * act_cells0 * ts)))) return rc;
-    h->d_pyr = (uint8_t*)u; h->d_feat = u + pyr_al;
-    h->d_pk = (uint8_t*)u; h->d_dt_tmpT = u + pk_al;
-  } else {
-    if ((rc = dev_alloc(h, &h->d_pyr, pyr))) return rc;
-    if ((rc = dev_alloc(h, &h->d_feat, feat_bytes))) return rc;
-    if ((rc = dev_alloc(h, &h->d_pk, pk_bytes))) return rc;
-  }
-  h->d_feat_split = nullptr;   // (PBD_CONV_SPLIT: placed below, once the DT planes are known — the compact plan shares their memory)
-  if ((rc = dev_alloc(h, &h->d_rootv, cells * m.ncomponents * ts))) return rc;
-  if ((rc = dev_alloc(h, &h->d_rooti, cells * m.ncomponents))) return rc;
-  if (h->nms_sz > 0 && (rc = dev_alloc(h, &h->d_nms_mask, cells * m.ncomponents))) return rc;
-
-  std::vector<LevelDev> ld(n);
-  for (int l = 0; l < n; ++l) {
-    const Level& L = h->lv[l];
-    ld[l] = LevelDev{L.iw, L.ih, L.bw, L.bh, L.cw, L.ch, (unsigned long long)L.img_off, (unsigned long long)L.cell_off};
-  }
-  if ((rc = dev_upload(h, &h->d_levels, ld))) return rc;
-
-  // HOG tiles: TC x TC cells; shrink the tile until its LDS footprint fits
-  h->hog_tc = 16;
-  const int hog_bpp = esz == 1 ? 3 : cn * esz;    // (8-bit frames: the tile side does not depend on the channel count)
-  if (const char* e = PBD_PROBE_ENV("PBD_HOG_TC")) h->hog_tc = std::max(2, std::min(16, atoi(e)));   // tuning builds
-  while (h->hog_tc > 2 && hog_lds_bytes(m.sbin, h->hog_tc, h->ts, hog_bpp) > 150 * 1024) h->hog_tc /= 2;
-  if (hog_lds_bytes(m.sbin, h->hog_tc, h->ts, hog_bpp) > 150 * 1024) return fail(h, PBD_ERR_UNSUPPORTED, "sbin too large");
-  std::vector<HogTile> ht;
-  std::vector<ConvTile> ct;
-  for (int l = 0; l < n; ++l) {
-    const Level& L = h->lv[l];
-    if (!L.active || L.cw == 0 || L.ch == 0) continue;
-    for (int y = 0; y < L.ch; y += h->hog_tc)
-      for (int x = 0; x < L.cw; x += h->hog_tc) ht.push_back(HogTile{l, y, x, 0});
-    for (int y = 0; y < L.ch; y += 16)
-      for (int x = 0; x < L.cw; x += 16) ct.push_back(ConvTile{l, y, x, 0});
-  }
-  // The filter bank runs tile position 8 g + x of this list on XCD x (k_conv.hip: groups of 8 tiles, all n-tiles of a
-  // tile on one XCD).  Horizontally adjacent tiles write the two halves of the same 128-byte lines of every response
-  // plane (a tile row is 64 bytes); in list order they sat on DIFFERENT XCDs, whose L2s cannot merge the halves
-  // (WRITE_SIZE 124 MB for 88 MB of responses).  Pairs of neighbours (2k, 2k + 1) go to the same XCD, one group apart.
-  {
-    std::vector<ConvTile> o(ct);
-    const size_t full = ct.size() / 16 * 16;
-    for (size_t b = 0; b < full; b += 16)
-      for (size_t x = 0; x < 8; ++x) { o[b + x] = ct[b + 2 * x]; o[b + 8 + x] = ct[b + 2 * x + 1]; }
-    ct.swap(o);
-  }
-  h->n_hog_tiles = (int)ht.size();
-  h->n_conv_tiles = (int)ct.size();
-  if ((rc = dev_upload(h, &h->d_hog_tiles, ht))) return rc;
-  if ((rc = dev_upload(h, &h->d_conv_tiles, ct))) return rc;
-  if (h->mixed) {   // one copy of the list per size group, the group's planes in the tiles' pad (ConvTile)
-    std::vector<ConvTile> cm;
-    cm.reserve(ct.size() * h->groups.size());
-    for (const SizeGroup& g : h->groups)
-      for (ConvTile t : ct) { t.pad = g.n0 | (g.nf << 16); cm.push_back(t); }
-    if ((rc = dev_upload(h, &h->d_conv_tiles_mix, cm))) return rc;
-  }
-
-  // ---- DP tables ---------------------------------------------------------------
-  size_t act_cells = 0;
-  for (int l = 0; l < n; ++l) if (h->lv[l].active) act_cells += (size_t)h->lv[l].cw * h->lv[l].ch;
-  size_t allmaps = 0;
-  for (const PartInfo& P : h->parts) if (P.p > 0) allmaps += P.K;
-  std::vector<size_t> roundK(h->rounds.size(), 0);   // maps transformed in round r (per level)
-  size_t maxK = 1;
-  for (size_t r = 0; r < h->rounds.size(); ++r) {
-    for (int fp : h->rounds[r]) roundK[r] += h->parts[fp].K;
-    maxK = std::max(maxK, roundK[r]);
-  }
-  const bool fold = h->fold;
-  // DT planes.  The passes' own pointer planes (int16) stay for the whole frame: back-tracking composes Ix / Iy from
-  // them.  Score planes — fold: the x pass's output lives only until the round's y pass (one round's worth, reused
-  // by every round), the y pass's output (the message source) keeps its own plane until the parent's x pass has
-  // read it; legacy: both kept per map (a message may wait several rounds for a higher-indexed sibling), plus the
-  // accumulated part scores.
-  h->dt_cap_elems = std::max<size_t>(1, allmaps * act_cells);
-  const size_t tmp_elems = fold ? std::max<size_t>(1, maxK * act_cells) : h->dt_cap_elems;
-  h->d_dt_sdt = nullptr;
-  if (!h->compact) {
-    if ((rc = dev_alloc(h, &h->d_dt_tmpT, tmp_elems * ts))) return rc;
-    if ((rc = dev_alloc(h, &h->d_dt_sdt, h->dt_cap_elems * ts))) return rc;
-  }
-  if ((rc = dev_alloc(h, &h->d_dt_ixT, h->dt_cap_elems))) return rc;
-  if ((rc = dev_alloc(h, &h->d_dt_iy, h->dt_cap_elems))) return rc;
-  if (!fold && (rc = dev_alloc(h, &h->d_acc, cells * h->nslots * ts))) return rc;
-  if (h->split_parts) {
-    // the features' bfloat16 parts (192 B per cell; binary16: 128 B) live from HOG to the end of the filter bank; the x pass's pointer planes from min()
-    // to argmin(): the compact plan (whose stage buffers already refuse to be read once a later stage has reused them) puts both in
-    // one region where the planes are large enough (person model: 300 B per cell); the default plan keeps them apart (pdf() may be
-    // called again after min() there)
-    const size_t split_elems = cells * h->split_parts * PBD_FLEN;
-    if (h->compact && h->dt_cap_elems >= split_elems) h->d_feat_split = (uint16_t*)h->d_dt_ixT;
-    else if ((rc = dev_alloc(h, &h->d_feat_split, split_elems))) return rc;
-  }
-
-  // DT LDS budget per block unless the longest line needs more at the minimum number of lines per block
-  int maxlen = 1;
-  for (int l = 0; l < n; ++l) if (h->lv[l].active) maxlen = std::max(maxlen, std::max(h->lv[l].cw, h->lv[l].ch));
-  // block geometry, measured on MI355X (profiles/sweep_dt.sh).  float, lines with 16-bit links: two wavefronts and
-  // 25 KB per block = 6 blocks = 3 wavefronts per SIMD (20 .. 40 KB swept); double (17 B per line element, an IEEE division
-  // per intersection): one wavefront and 20 KB = 8 blocks per CU (0.93 ms against 1.28 with the float geometry)
-  // Round 4 (profiles/experiments/README.md, seven frame sizes): while every line of the frame is short enough for byte links
-  // (stride <= 256: 9 B per line element), float blocks of FOUR wavefronts and 40 KB — 4 blocks = 4 wavefronts per SIMD — beat
-  // the two-wavefront / 25 KB blocks by 2-8 % of dp_min in batches (640x480: 0.328 -> 0.314 ms per frame, 0.600 -> 0.581 alone);
-  // with 16-bit links (10 B per element: 1280x720, 1920x1080) they lose 9-12 %, and there the geometry above stays.
-  const bool byte_links = dt_stride_for(maxlen) <= 256;
-  // double (17 B per line element): two wavefronts and 40 KB per block — round 4, session 34: 0.473 / 0.721 ms per frame (batches / alone)
-  // against 0.485 / 0.770 with one wavefront and 20 KB; round 5, session 3: 0.477 against 0.497 in batches, 893 against 879 frames/s
-  // pbd_tune_plan: the other geometry measured on this handle's own frames (results are bit-identical under any geometry)
-  const bool big_blocks = h->ts == 4 && h->dt_geom ? h->dt_geom == 1 : byte_links;
-  h->dt_nt = h->ts == 8 ? 128 : (big_blocks ? 256 : PBD_DT_NT_DEFAULT);
-  if (const char* e = PBD_PROBE_ENV("PBD_DT_NT")) h->dt_nt = std::max(64, std::min(256, atoi(e) & ~63));
-  h->dt_nt_x = h->dt_nt;      // lanes of a fold x-pass block
-  if (const char* e = PBD_PROBE_ENV("PBD_DT_NT_X")) h->dt_nt_x = std::max(64, std::min(256, atoi(e) & ~63));
-  if (const char* e = PBD_PROBE_ENV("PBD_DT_SEG")) h->dt_seg = atoi(e);
-  size_t dt_base = (h->ts == 8 ? 40 : (big_blocks ? 40 : 25)) * 1024;
-  if (const char* e = PBD_PROBE_ENV("PBD_DT_BUDGET_KB")) dt_base = (size_t)atoi(e) * 1024;
-  if (const char* e = PBD_PROBE_ENV("PBD_DT_BUDGET_B")) dt_base = (size_t)atoi(e);
-  int max_mix = 4;
-  if (fold) for (const PartInfo& P : h->parts) max_mix = std::max(max_mix, P.K);
-  const size_t dt_need = dt_lds_bytes(dt_stride_for(maxlen), max_mix, h->ts, h->dt_nt);   // the longest line at the fewest lines a block can hold
-  if (dt_need > 160 * 1024) return fail(h, PBD_ERR_UNSUPPORTED, "pyramid level too large for the LDS-resident distance transform");
-  h->dt_lds = std::max(dt_base, dt_need);
-  // A launch with fewer maps than the fullest round of the frame (the person tree: rounds of 4, 4, 4, 4, 2, 2, 2, 2, 1
-  // parts) would leave LDS — and lanes — idle at the full budget, while every launch lasts as long as its blocks'
-  // segments are: its blocks get proportionally FEWER lines (about the same number of blocks as the fullest launch),
-  // i.e. more lanes per line and shorter segments.
-  bool thin = false;
-  size_t thin_min = 10 * 1024;
-  if (const char* e = PBD_PROBE_ENV("PBD_DT_THIN")) thin = atoi(e) != 0;
-  if (const char* e = PBD_PROBE_ENV("PBD_DT_THIN_MIN_KB")) thin_min = (size_t)atoi(e) * 1024;
-  auto launch_budget = [&](size_t K_launch) {
-    size_t bgt = h->dt_lds;
-    if (thin && K_launch < maxK) bgt = std::max(thin_min, (size_t)((double)dt_base * (double)K_launch / (double)maxK));
-    return std::min(std::max(bgt, dt_need), h->dt_lds);
-  };
-  std::vector<DtMap> maps;
-  std::vector<DtTask> tasks;
-  std::vector<FoldJob> folds;
-  std::vector<unsigned long long> foldx;               // pbd_handle::d_foldx
-  std::vector<ReduceJob> red;
-  std::vector<ReduceBlock> redblk;
-  h->rl.clear();
-  std::vector<char> slot_init((size_t)h->nslots, 0);  // legacy: ncscores[fid].empty() emulation (same for every level)
-  // plane offset of (part, level, mixture) in the per-map DT planes: parts in flat order, levels inside
-  std::vector<size_t> part_scr(h->parts.size(), 0);
-  { size_t o = 0; for (size_t fp = 0; fp < h->parts.size(); ++fp) if (h->parts[fp].p > 0) { part_scr[fp] = o; o += (size_t)h->parts[fp].K * act_cells; } }
-  std::vector<size_t> lvl_scr(n, 0);  // prefix of active cells
-  { size_t o = 0; for (int l = 0; l < n; ++l) { lvl_scr[l] = o; if (h->lv[l].active) o += (size_t)h->lv[l].cw * h->lv[l].ch; } }
-  auto scr_of = [&](int fp, int l, int mm) {
-    return part_scr[fp] + (size_t)h->parts[fp].K * lvl_scr[l] + (size_t)mm * h->lv[l].cw * h->lv[l].ch;
-  };
-  auto resp_plane = [&](int l, int fid) { return h->d_resp + (h->lv[l].cell_off * m.nfilters + (size_t)fid * h->lv[l].cw * h->lv[l].ch) * ts; };
-  // compact: the transformed scores of (part, mixture) live in the mixture's own response plane
-  auto sdt_plane = [&](int fp, int l, int mm) { return h->compact ? resp_plane(l, h->parts[fp].filterid[mm]) : h->d_dt_sdt + scr_of(fp, l, mm) * ts; };
-  // children of every part, descending flat index (the order their messages are added in, src/DynamicProgram.cpp:95)
-  std::vector<std::vector<int>> children(h->parts.size());
-  for (int fp = (int)h->parts.size() - 1; fp >= 0; --fp)
-    if (h->parts[fp].p > 0) children[h->part_offset[h->parts[fp].comp] + h->parts[fp].parent].push_back(fp);
-  auto make_fold = [&](int fp, int l) {   // FoldJob of part fp at level l (its children's messages); -1 without children
-    if (children[fp].empty()) return -1;
-    const Level& L = h->lv[l];
-    const size_t HW = (size_t)L.cw * L.ch;
-    FoldJob J{};
-    for (int c : children[fp]) {
-      const PartInfo& C = h->parts[c];
-      FoldChild& F = J.ch[J.nch++];
-      F.K = C.K;
-      for (int k = 0; k < PBD_FOLD_MAXMIX; ++k) F.sdt[k] = sdt_plane(c, l, std::min(k, C.K - 1));
-      const int Lp = h->parts[fp].K;
-      for (int k = 0; k < PBD_FOLD_MAXMIX; ++k)
-        for (int mm = 0; mm < PBD_FOLD_MAXMIX; ++mm)
-          F.bias[k][mm] = h->biasw[C.biasid[std::min(k, C.K - 1)] + std::min(mm, Lp - 1)];
-      F.ok = h->d_pk + L.cell_off * h->nplanes + (size_t)C.plane0 * HW;
-    }
-    folds.push_back(J);
-    return (int)folds.size() - 1;
-  };
-  // Workgroup b runs on XCD b % 8, each with its own L2.  A block writes its lines transposed, i.e. runs of a few
-  // elements — a fraction of a 128-byte line; the neighbouring runs belong to the next tasks of the same map.
-  // Order a launch's table so that `xcd_chunk` consecutive tasks share an XCD and the partial lines merge in one
-  // L2 instead of going out to HBM from several.
-  int xchunk = h->xcd_chunk;
-  if (const char* e = PBD_PROBE_ENV("PBD_DT_XCD_CHUNK")) xchunk = atoi(e);
-  auto xcd_order = [xchunk](std::vector<DtTask>& v) {
-    const int c = xchunk;
-    if (c <= 0) return;
-    const size_t win = (size_t)8 * c, full = v.size() / win * win;
-    std::vector<DtTask> o(v);
-    for (size_t b = 0; b < full; ++b) {
-      const size_t xcd = b & 7, idx = b >> 3;
-      o[b] = v[((idx / c) * 8 + xcd) * c + idx % c];
-    }
-    v.swap(o);
-  };
-  auto launch_lds = [&](const std::vector<DtTask>& v, int nt) {
-    size_t lds = 0;
-    for (const DtTask& t : v) lds = std::max(lds, dt_lds_bytes(t.g.stride, t.g.lpb, h->ts, nt));
-    if (const char* e = PBD_PROBE_ENV("PBD_DT_LDS_REQUEST_KB")) lds = std::max(lds, (size_t)atoi(e) * 1024);   // occupancy probe
-    return lds;
-  };
-  const bool dbg_plan = PBD_PROBE_ENV("PBD_DEBUG_PLAN") != nullptr;
-  // A launch whose blocks do not all fit on the chip at once lasts two block times instead of one (measured: the
-  // fold x pass of the 4-part rounds, 1772 blocks for 1536 slots at 25 KB: 100 us instead of 45).  Blocks that hold
-  // whole rows of all mixtures quantise badly (12 lines where 15 would fit), so such a launch gets the smallest
-  // larger budget at which its blocks are resident together (fewer, larger blocks; fewer blocks per CU).
+  FrameSpec fs;
+  fs.w = w; fs.h = hgt; fs.cn = cn; fs.batch = batch; fs.depth = depth; fs.level_set = h->level_set;
+  FrameLayout lay;
+  int rc = plan_layout(*h, fs, lay, &h->err);
+  if (rc) return rc;
+  std::vector<char*> regions(lay.regions.size(), nullptr);
+  for (size_t i = 0; i < regions.size(); ++i)
+    if ((rc = dev_alloc(h, &regions[i], lay.regions[i]))) return rc;
+  const FrameBases b = frame_bases(lay, regions.data());
   int ncu = 256;
   { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, h->opt.device) == hipSuccess && pr.multiProcessorCount > 0) ncu = pr.multiProcessorCount; }
   h->ncu = ncu;
-  auto count_blocks = [&](const std::vector<int>& rnd, size_t budget, bool fold_x, bool ypass, bool round_lanes, size_t* lds_out) {
-    size_t nb = 0, lds = 0;
-    for (int l = 0; l < n; ++l) {
-      const Level& L = h->lv[l];
-      if (!L.active || L.cw == 0 || L.ch == 0) continue;
-      const int len = ypass ? L.ch : L.cw, nlines = ypass ? L.cw : L.ch;
-      if (fold_x) {
-        for (int fp : rnd) {
-          const DtGroup g = dt_group(0, h->parts[fp].K, nlines, len, budget, h->ts, h->dt_nt, h->dt_seg, 0);
-          nb += (size_t)(nlines + g.lpb / g.nmaps - 1) / (g.lpb / g.nmaps);
-          lds = std::max(lds, dt_lds_bytes(g.stride, g.lpb, h->ts, h->dt_nt));
-        }
-      } else {
-        int nm = 0;
-        for (int fp : rnd) nm += h->parts[fp].K;
-        const DtGroup g = dt_group(0, nm, nlines, len, budget, h->ts, h->dt_nt, h->dt_seg, -1, round_lanes);
-        nb += ((size_t)nm * nlines + g.lpb - 1) / g.lpb;
-        lds = std::max(lds, dt_lds_bytes(g.stride, g.lpb, h->ts, h->dt_nt));
-      }
-    }
-    *lds_out = lds;
-    return nb;
-  };
-  // Launch geometry: the base budget with full-lane lines per block if all blocks of the launch are then resident at
-  // once; else the same without the rounding; else the smallest larger budget that makes them resident (fewer, larger
-  // blocks; up to 1.6 x); else the base.  (Measured: budgets BELOW the base — more, shorter blocks, 8 per CU — are
-  // slower: dp_min 0.79 / 0.82 ms fold / three-kernel against 0.72 / 0.76, more contention per CU.)
-  struct Geo { size_t budget; bool round; };
-  auto launch_geometry = [&](const std::vector<int>& rnd, size_t base, bool fold_x, bool ypass) {
-    const Geo dflt{base, true};
-    // fold launches keep the base budget: their blocks hold whole rows of all mixtures and quantise badly (1772 blocks
-    // for 1536 slots in the 4-part rounds), but the budgets that make them resident at once (36-40 KB, 4 per CU) cost
-    // more with four frames in flight than the second wave of blocks does (measured: 1 170 frames/s and dp_min 0.70 ms
-    // at 40 KB, 1 181 / 0.73 at 28 KB, 1 235 / 0.725 at the base 25 KB)
-    if (fold_x || PBD_PROBE_ENV("PBD_DT_NO_RESIDENT")) return dflt;
-    const int waves_blk = std::max(1, h->dt_nt / 64);
-    auto resident = [&](size_t b, bool rnd_lanes) {
-      size_t lds = 0;
-      const size_t nb = count_blocks(rnd, b, fold_x, ypass, rnd_lanes, &lds);
-      const size_t per_cu = std::min<size_t>(160 * 1024 / std::max<size_t>(lds, 1), 24 / waves_blk);
-      return nb <= per_cu * ncu;
-    };
-    if (resident(base, true)) return dflt;
-    if (!fold_x && resident(base, false)) return Geo{base, false};
-    for (size_t b = base + 1024; b <= base * 8 / 5 && b <= 150 * 1024; b += 1024) {
-      if (resident(b, true)) return Geo{b, true};
-      if (!fold_x && resident(b, false)) return Geo{b, false};
-    }
-    return dflt;
-  };
-  for (size_t r = 0; r < h->rounds.size(); ++r) {
-    const std::vector<int>& rnd = h->rounds[r];
-    pbd_handle::RoundLaunch R{};
-    const bool fold_x = fold && r > 0;   // round 0 = the leaves: their lines are their raw responses
-    if (rnd.empty()) { h->rl.push_back(R); continue; }
-    size_t budget_x = launch_budget(roundK[r]), budget = budget_x;
-    Geo geox = launch_geometry(rnd, budget_x, fold_x, false), geoy = launch_geometry(rnd, budget, false, true);
-    if (const char* e = PBD_PROBE_ENV("PBD_DT_BUDGET_X_KB")) { if (fold_x) geox = Geo{std::max(dt_need, (size_t)atoi(e) * 1024), true}; }
-    budget_x = geox.budget; budget = geoy.budget;
-    std::vector<DtTask> xt, yt;
-    for (int l = 0; l < n && !rnd.empty(); ++l) {
-      const Level& L = h->lv[l];
-      if (!L.active || L.cw == 0 || L.ch == 0) continue;
-      const size_t HW = (size_t)L.cw * L.ch;
-      const int gx_map0 = (int)maps.size();
-      int gx_nmaps = 0;
-      std::vector<DtMap> ymaps;
-      size_t tmp_round = 0;   // fold: maps of this level in front of the part's, in the round's x-pass output (level-major: all maps of a
-                              // level back to back, so that every block of the y pass reads ONE contiguous run — DtTask::src0)
-      for (int fp : rnd) {
-        const PartInfo& P = h->parts[fp];
-        const int part_map0 = (int)maps.size();
-        for (int mm = 0; mm < P.K; ++mm) {
-          const int fid = P.filterid[mm], did = P.defid[mm];
-          const size_t so = scr_of(fp, l, mm);
-          const size_t to = fold ? roundK[r] * lvl_scr[l] + (tmp_round + (size_t)mm) * HW : so;
-          const char* src = (!fold && slot_init[P.slot[mm]]) ? h->d_acc + (L.cell_off * h->nslots + (size_t)P.slot[mm] * HW) * ts
-                                                            : resp_plane(l, fid);
-          const float* wv = &h->defw[(size_t)did * 4];
-          maps.push_back(dt_map(src, h->d_dt_tmpT + to * ts, h->d_dt_ixT + so, wv[0], wv[1], h->anchors[did * 2], 1));
-          ymaps.push_back(dt_map(h->d_dt_tmpT + to * ts, sdt_plane(fp, l, mm), h->d_dt_iy + so, wv[2], wv[3], h->anchors[did * 2 + 1], 0));
-          gx_nmaps++;
-        }
-        tmp_round += (size_t)P.K;
-        if (fold_x) dt_add_tasks(dt_group(part_map0, P.K, L.ch, L.cw, budget_x, h->ts, h->dt_nt_x, h->dt_seg, make_fold(fp, l)), xt);
-      }
-      if (!fold_x) dt_add_tasks(dt_group(gx_map0, gx_nmaps, L.ch, L.cw, budget_x, h->ts, h->dt_nt, h->dt_seg, -1, geox.round), xt, &maps, h->ts);
-      const DtGroup gy = dt_group((int)maps.size(), gx_nmaps, L.cw, L.ch, budget, h->ts, h->dt_nt, h->dt_seg, -1, geoy.round);
-      for (auto& my : ymaps) maps.push_back(my);
-      dt_add_tasks(gy, yt, &maps, h->ts);
-      if (dbg_plan)
-        fprintf(stderr, "plan: round %zu level %d  x: len %d lines %d maps %d lpb %d  y: len %d lines %d lpb %d  (budget %zu)\n", r, l,
-                L.cw, L.ch, gx_nmaps, xt.empty() ? 0 : xt.back().g.lpb, gy.len, gy.nlines, gy.lpb, budget);
-    }
-    if (const char* e = PBD_PROBE_ENV("PBD_DEBUG_DUP")) {   // scaling probe: every DT block issued n times (identical outputs)
-      const int ndup = atoi(e);
-      const std::vector<DtTask> x0 = xt, y0 = yt;
-      for (int i = 1; i < ndup; ++i) { xt.insert(xt.end(), x0.begin(), x0.end()); yt.insert(yt.end(), y0.begin(), y0.end()); }
-    }
-    if (PBD_PROBE_ENV("PBD_DT_REVERSE")) { std::reverse(xt.begin(), xt.end()); std::reverse(yt.begin(), yt.end()); }   // probe: coarse levels' blocks first
-    dt_mark_fused(xt, maps.data(), h->ts);
-    dt_mark_fused(yt, maps.data(), h->ts);
-    xcd_order(xt);
-    xcd_order(yt);
-    R.lds_x = launch_lds(xt, fold_x ? h->dt_nt_x : h->dt_nt); R.lds_y = launch_lds(yt, h->dt_nt); R.fold_x = fold_x ? 1 : 0;
-    if (dbg_plan) fprintf(stderr, "plan: round %zu: %zu x blocks (%zu B LDS%s), %zu y blocks (%zu B)\n", r, xt.size(), R.lds_x, fold_x ? ", fold" : "", yt.size(), R.lds_y);
-    if (fold_x) {   // the loader's first addresses of every fold x task, in task order (pbd_handle::d_foldx)
-      R.foldx0 = foldx.size();
-      for (const DtTask& t : xt) {
-        const DtGroup& g = t.g;
-        for (int mm = 0; mm < 8; ++mm) foldx.push_back((unsigned long long)(uintptr_t)maps[(size_t)g.map0 + std::min(mm, g.nmaps - 1)].src);
-        const unsigned long long* cq = (const unsigned long long*)&folds[(size_t)g.fold].ch[0];   // sdt[8], ok (k_dp.hip: fold_child_qw)
-        for (int i = 0; i < 9; ++i) foldx.push_back(cq[i]);
-        foldx.push_back((unsigned long long)folds[(size_t)g.fold].nch);
-      }
-    }
-    R.xtask0 = (int)tasks.size(); R.nxtasks = (int)xt.size();
-    tasks.insert(tasks.end(), xt.begin(), xt.end());
-    R.ytask0 = (int)tasks.size(); R.nytasks = (int)yt.size();
-    tasks.insert(tasks.end(), yt.begin(), yt.end());
-    // legacy: reduce waves of this round (slot state is advanced once per wave)
-    for (size_t wi = 0; !fold && wi < h->red_rounds[r].size(); ++wi) {
-      const std::vector<int>& wave = h->red_rounds[r][wi];
-      pbd_handle::ReduceWave Wv{(int)redblk.size(), 0};
-      std::vector<int> parents;  // distinct parents, in first-appearance order
-      for (int fp : wave) {
-        const int pf = h->part_offset[h->parts[fp].comp] + h->parts[fp].parent;
-        if (std::find(parents.begin(), parents.end(), pf) == parents.end()) parents.push_back(pf);
-      }
-      for (int l = 0; l < n; ++l) {
-        const Level& L = h->lv[l];
-        if (!L.active || L.cw == 0 || L.ch == 0) continue;
-        const size_t HW = (size_t)L.cw * L.ch;
-        for (int pf : parents) {
-          const PartInfo& Par = h->parts[pf];
-          ReduceJob J{};
-          J.H = L.ch; J.W = L.cw; J.L = Par.K;
-          for (int pm = 0; pm < Par.K; ++pm) {
-            char* accp = h->d_acc + (L.cell_off * h->nslots + (size_t)Par.slot[pm] * HW) * ts;
-            J.par_in[pm] = slot_init[Par.slot[pm]] ? accp : resp_plane(l, Par.filterid[pm]);
-            J.par_out[pm] = accp;
-          }
-          for (int fp : wave) {  // `wave` is in descending child order
-            const PartInfo& P = h->parts[fp];
-            if (h->part_offset[P.comp] + P.parent != pf) continue;
-            ReduceChild& C = J.ch[J.nch++];
-            C.sdt = sdt_plane(fp, l, 0);
-            C.ok = h->d_pk + L.cell_off * h->nplanes + (size_t)P.plane0 * HW;
-            C.K = P.K;
-            for (int mm = 0; mm < P.K; ++mm) C.bias_off[mm] = P.biasid[mm];
-          }
-          for (unsigned c0 = 0; c0 < (unsigned)HW; c0 += 256) redblk.push_back(ReduceBlock{(int)red.size(), c0});
-          red.push_back(J);
-        }
-      }
-      for (int pf : parents)
-        for (int pm = 0; pm < h->parts[pf].K; ++pm) slot_init[h->parts[pf].slot[pm]] = 1;
-      Wv.nblks = (int)redblk.size() - Wv.blk0;
-      R.waves.push_back(Wv);
-    }
-    h->rl.push_back(R);
-  }
-
-  // root jobs + backtracking info
-  std::vector<RootJob> rj;
-  std::vector<ReduceBlock> rootblk;   // k_root's blocks: (job, first cell)
-  std::vector<BackLevel> bl((size_t)n * m.ncomponents);
-  unsigned rcells = 0;
-  for (int l = 0; l < n; ++l) {
-    const Level& L = h->lv[l];
-    const size_t HW = (size_t)L.cw * L.ch;
-    for (int c = 0; c < m.ncomponents; ++c) {
-      BackLevel& B = bl[(size_t)l * m.ncomponents + c];
-      const size_t po = L.cell_off * h->nplanes + (size_t)h->comp_plane0[c] * HW;
-      B.pk = h->d_pk + po;
-      B.rootv = h->d_rootv + (L.cell_off * m.ncomponents + (size_t)c * HW) * ts;
-      B.rooti = h->d_rooti + L.cell_off * m.ncomponents + (size_t)c * HW;
-      B.H = L.ch; B.W = L.cw; B.scale = L.scale;
-      if (!L.active || HW == 0) continue;
-      const PartInfo& R0 = h->parts[h->part_offset[c]];
-      RootJob J{};
-      for (int kk = 0; kk < PBD_MAX_MIX; ++kk) {   // entries beyond K repeat mixture K - 1 (the fold's register arrays are never predicated)
-        const int k = std::min(kk, R0.K - 1);
-        J.score[kk] = (!fold && slot_init[R0.slot[k]]) ? h->d_acc + (L.cell_off * h->nslots + (size_t)R0.slot[k] * HW) * ts
-                                                       : resp_plane(l, R0.filterid[k]);
-      }
-      J.rootv = (void*)B.rootv; J.rooti = (int*)B.rooti;
-      J.H = L.ch; J.W = L.cw; J.K = R0.K; J.level = l; J.comp = c;
-      J.bias = h->biasw[R0.biasid[0]];  // root.bias(0)[0], DynamicProgram.cpp:165
-      J.cell0 = rcells;
-      J.fold = fold ? make_fold(h->part_offset[c], l) : -1;   // fold: the root's messages are folded by k_root
-      rcells += (unsigned)HW;
-      for (unsigned c0 = 0; c0 < (unsigned)HW; c0 += 256) rootblk.push_back(ReduceBlock{(int)rj.size(), c0});
-      rj.push_back(J);
-    }
-  }
-  if ((rc = dev_upload(h, &h->d_dtmaps, maps))) return rc;
-  if ((rc = dev_upload(h, &h->d_dttasks, tasks))) return rc;
-  if ((rc = dev_upload(h, &h->d_foldjobs, folds))) return rc;
-  if ((rc = dev_upload(h, &h->d_foldx, foldx))) return rc;
-  if ((rc = dev_upload(h, &h->d_redjobs, red))) return rc;
-  if ((rc = dev_upload(h, &h->d_redblocks, redblk))) return rc;
-  h->n_rootjobs = (int)rj.size();
-  h->root_cells = rcells;
-  h->root_maxcells = 0;
-  for (const RootJob& J : rj) h->root_maxcells = std::max(h->root_maxcells, (unsigned)J.H * (unsigned)J.W);
-  if ((rc = dev_upload(h, &h->d_rootjobs, rj))) return rc;
-  h->n_rootblocks = (int)rootblk.size();
-  if ((rc = dev_upload(h, &h->d_rootblocks, rootblk))) return rc;
-  if ((rc = dev_upload(h, &h->d_back, bl))) return rc;
-  // where the DT pointer planes of (level, part) live: back-tracking composes Ix / Iy from them on the fly
-  h->scr_base.assign((size_t)n * h->parts.size(), 0);
-  for (int l = 0; l < n; ++l)
-    for (size_t fp = 0; fp < h->parts.size(); ++fp)
-      if (h->parts[fp].p > 0 && h->lv[l].active) h->scr_base[(size_t)l * h->parts.size() + fp] = scr_of((int)fp, l, 0);
-  if ((rc = dev_upload(h, &h->d_scr_base, h->scr_base))) return rc;
+  FrameTables t;
+  if ((rc = plan_tables(*h, fs, lay, b, ncu, h->dt_geom, h->knobs, t, &h->err))) return rc;
+  if ((rc = dev_upload(h, &h->d_pyrjobs, t.pyrjobs)) || (rc = dev_upload(h, &h->d_levels, t.levels)) ||
+      (rc = dev_upload(h, &h->d_hog_tiles, t.hog_tiles)) || (rc = dev_upload(h, &h->d_conv_tiles, t.conv_tiles)) ||
+      (h->mixed && (rc = dev_upload(h, &h->d_conv_tiles_mix, t.conv_tiles_mix))) ||
+      (rc = dev_upload(h, &h->d_dtmaps, t.maps)) || (rc = dev_upload(h, &h->d_dttasks, t.tasks)) ||
+      (rc = dev_upload(h, &h->d_foldjobs, t.folds)) || (rc = dev_upload(h, &h->d_foldx, t.foldx)) ||
+      (rc = dev_upload(h, &h->d_redjobs, t.red)) || (rc = dev_upload(h, &h->d_redblocks, t.redblk)) ||
+      (rc = dev_upload(h, &h->d_rootjobs, t.rootjobs)) || (rc = dev_upload(h, &h->d_rootblocks, t.rootblk)) ||
+      (rc = dev_upload(h, &h->d_back, t.back)) || (rc = dev_upload(h, &h->d_scr_base, t.scr_base)))
+    return rc;
+  h->lv = lay.lv; h->nlevels = lay.nlevels; h->batch = batch; h->nvl = lay.nvl;
+  h->first_copy = kFirstCopy * batch;
+  h->cells = lay.cells; h->pyr_bytes = lay.pyr_bytes; h->compact = lay.compact; h->dt_cap_elems = lay.dt_cap_elems;
+  h->d_img = (uint8_t*)b.p[FB_IMG]; h->d_pyr = (uint8_t*)b.p[FB_PYR]; h->d_feat = b.p[FB_FEAT]; h->d_resp = b.p[FB_RESP];
+  h->d_pk = (uint8_t*)b.p[FB_PK]; h->d_rootv = b.p[FB_ROOTV]; h->d_rooti = (int*)b.p[FB_ROOTI]; h->d_nms_mask = (uint8_t*)b.p[FB_NMS_MASK];
+  h->d_dt_tmpT = b.p[FB_DT_TMPT]; h->d_dt_sdt = b.p[FB_DT_SDT]; h->d_dt_ixT = (int16_t*)b.p[FB_DT_IXT]; h->d_dt_iy = (int16_t*)b.p[FB_DT_IY];
+  h->d_acc = b.p[FB_ACC]; h->d_feat_split = (uint16_t*)b.p[FB_FEAT_SPLIT];
+  h->pyr_launches = std::move(t.pyr_launches);
+  h->hog_tc = t.hog_tc; h->n_hog_tiles = (int)t.hog_tiles.size(); h->n_conv_tiles = (int)t.conv_tiles.size();
+  h->dt_nt = t.dt_nt; h->dt_lds = t.dt_lds;
+  h->rl = std::move(t.rl);
+  h->n_rootjobs = (int)t.rootjobs.size(); h->n_rootblocks = (int)t.rootblk.size();
+  h->root_cells = t.root_cells; h->root_maxcells = t.root_maxcells;
+  h->scr_base = std::move(t.scr_base);
   h->fw = w; h->fh = hgt; h->fcn = cn; h->fdepth = depth; h->fesz = esz;
   return PBD_OK;
 }
-
 // ---------------------------------------------------------------------------
 // stages
 // ---------------------------------------------------------------------------
 static int run_image_pyramid(pbd_handle* h, const uint8_t* d_src, int stride) {
   // one launch for the first octave of every frame of the batch (cv::resize), one per octave step below it (cv::pyrDown)
   for (size_t i = 0; i < h->pyr_launches.size(); ++i) {
-    const pbd_handle::PyrLaunch& P = h->pyr_launches[i];
+    const PyrLaunch& P = h->pyr_launches[i];
     if (h->fdepth != PBD_DEPTH_8U) {   // 16-bit / float / double frames (pbd_detect_image): the plain per-element kernels
       if (i == 0) launch_resize_any(h->d_pyrjobs + P.job0, P.njobs, P.maxpix, h->fcn, h->fdepth, stride, d_src, h->d_pyr, h->stream);
       else launch_pyrdown_any(h->d_pyrjobs + P.job0, P.njobs, P.maxpix, h->fcn, h->fdepth, h->d_pyr, h->stream);
@@ -1201,7 +437,7 @@ static int run_dp_min(pbd_handle* h) {
   // messages) + y pass per round, the root's messages folded by k_root: 2 * rounds + 1 launches; legacy (models that
   // alias a filter id inside a component, or more than 8 mixtures): + the round's reduce launches.
   for (auto& R : h->rl) {
-    launch_dt_pass(h->d_dttasks + R.xtask0, R.nxtasks, h->d_dtmaps, R.fold_x ? h->d_foldjobs : nullptr, R.fold_x ? h->d_foldx + R.foldx0 : nullptr, h->d_biasw, R.lds_x, h->ts, R.fold_x ? h->dt_nt_x : h->dt_nt, h->fold_mix, h->stream);
+    launch_dt_pass(h->d_dttasks + R.xtask0, R.nxtasks, h->d_dtmaps, R.fold_x ? h->d_foldjobs : nullptr, R.fold_x ? h->d_foldx + R.foldx0 : nullptr, h->d_biasw, R.lds_x, h->ts, h->dt_nt, h->fold_mix, h->stream);
     launch_dt_pass(h->d_dttasks + R.ytask0, R.nytasks, h->d_dtmaps, nullptr, nullptr, h->d_biasw, R.lds_y, h->ts, h->dt_nt, 0, h->stream);
     for (auto& Wv : R.waves)
       launch_reduce(h->d_redjobs, h->d_redblocks + Wv.blk0, Wv.nblks, h->d_biasw, h->opt.dt_correct_ptr, h->ts, h->stream);
@@ -1494,78 +730,10 @@ static int create_impl(const pbd_model_desc* model, const int32_t* fsize, const 
   pbd_handle* h = new (std::nothrow) pbd_handle();
   if (!h) return PBD_ERR_ARG;
   *out = h;  // returned even on failure so that pbd_last_error() can be read; destroy it either way
-  pbd_options o{};
-  if (opt) o = *opt;
-  if (o.max_candidates <= 0) o.max_candidates = 4096;
-  h->opt = o;
-  if (o.scalar_type != PBD_SCALAR_F32 && o.scalar_type != PBD_SCALAR_F64) return fail(h, PBD_ERR_ARG, "scalar_type: PBD_SCALAR_F32 or PBD_SCALAR_F64");
-  h->ts = (o.scalar_type == PBD_SCALAR_F64) ? 8 : 4;
-  pbd_model_desc sdesc;
-  std::vector<float> sorted;
-  if (sized && !fsize) return fail(h, PBD_ERR_ARG, "pbd_create_sized: fsize is null");
-  if (sized) {
-    if (!model || !model->filters) return fail(h, PBD_ERR_ARG, "model: null pointer");
-    if (model->kh != 0 || model->kw != 0) return fail(h, PBD_ERR_ARG, "pbd_create_sized: model->kh / kw must be 0 (the sizes come from fsize)");
-    if (model->nfilters <= 0) return fail(h, PBD_ERR_ARG, "model: bad sizes");
-    if (model->flen != PBD_FLEN || model->norient != PBD_NORIENT)
-      return fail(h, PBD_ERR_UNSUPPORTED, "model: only flen=32 / norient=18 HOG is supported");
-    const int nf = model->nfilters;
-    for (int n = 0; n < nf; ++n)
-      if (fsize[2 * n] < 1 || fsize[2 * n] > 9 || fsize[2 * n + 1] < 1 || fsize[2 * n + 1] > 9)
-        return fail(h, PBD_ERR_UNSUPPORTED, "pbd_create_sized: filter " + std::to_string(n) + ": sides of 1..9 cells");
-    sdesc = *model;
-    bool uniform = true;
-    for (int n = 1; n < nf; ++n) uniform = uniform && fsize[2 * n] == fsize[0] && fsize[2 * n + 1] == fsize[1];
-    if (uniform) {
-      sdesc.kh = fsize[0]; sdesc.kw = fsize[1];
-    } else {
-      std::vector<int> ord(nf);
-      for (int n = 0; n < nf; ++n) ord[n] = n;
-      std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) {
-        return fsize[2 * a] != fsize[2 * b] ? fsize[2 * a] < fsize[2 * b] : fsize[2 * a + 1] < fsize[2 * b + 1]; });
-      std::vector<size_t> off(nf + 1, 0);
-      for (int n = 0; n < nf; ++n) off[n + 1] = off[n] + (size_t)fsize[2 * n] * fsize[2 * n + 1] * PBD_FLEN;
-      h->mixed = true;
-      h->fperm.assign(nf, 0);
-      for (int i = 0; i < nf; ++i) {
-        const int c = ord[i];
-        h->fperm[c] = i;
-        h->fkh.push_back(fsize[2 * c]); h->fkw.push_back(fsize[2 * c + 1]);
-        sorted.insert(sorted.end(), model->filters + off[c], model->filters + off[c + 1]);
-      }
-      sdesc.filters = sorted.data();
-    }
-    model = &sdesc;
-  }
-  int rc = ingest_model(h, model);
+  int rc = plan_model(*h, model, fsize, sized, opt, &h->err);
   if (rc) return rc;
-  if (h->mixed) {   // filter ids (validated by ingest_model) into the size-sorted order
-    for (int& f : h->filterid) f = h->fperm[f];
-    for (PartInfo& P : h->parts) for (int& f : P.filterid) f = h->fperm[f];
-  }
-  if (o.reserved[0] < 0 || o.reserved[0] > 1024) return fail(h, PBD_ERR_ARG, "reserved[0] (nms_sz): 0 = off, or the window of the score-map NMS");
-  h->nms_sz = o.reserved[0];
-  h->conv_mode = o.conv_mode;
-  if (h->conv_mode == PBD_CONV_AUTO)
-    // measured on MI355X for N = 26 .. 312 5x5x32 filters at 640x480 (profiles/history/archive/r03b_conv_modes.json): the fp32 MFMA
-    // implicit GEMM beats the direct VALU correlation at every N (26 filters: 0.11 vs 0.38 ms; 156: 0.40 vs 1.62;
-    // 312: 0.76 vs 2.89) — the contraction is K = 800 deep whatever N is, so one 16-filter n-tile already pays.
-    // The VALU kernel remains the bit-exact parity path (PBD_CONV_EXACT) and what banks of fewer than 16 filters get.
-    // Any filter size goes the same way (3x3 .. 9x9: the contraction is kh * kw * 32 >= 288 deep; run-time tap loop of the same kernel).
-    // Round 5: float handles take the split-product bank (k_conv_split.hip: the fp32 products as six exact bfloat16 partial
-    // products on the bf16 matrix units, fp32 accumulators — errors of the fp32 MFMA chain's size, 2-3x its speed, and off the
-    // vector ALU's pipe); a weight outside bfloat16's finite range (|w| >= 3e38: no trained model) keeps the fp32 MFMA bank.
-    {
-      bool splittable = h->ts == 4 && model->flen == PBD_FLEN;
-      for (size_t i = 0; splittable && i < h->filters.size(); ++i) splittable = std::fabs(h->filters[i]) < 3.0e38f;
-      h->conv_mode = model->nfilters >= 16 ? (splittable ? PBD_CONV_SPLIT : PBD_CONV_MFMA) : PBD_CONV_EXACT;
-    }
-  if ((h->conv_mode == PBD_CONV_SPLIT || h->conv_mode == PBD_CONV_SPLIT_F16) && (h->ts != 4 || model->flen != PBD_FLEN))
-    return fail(h, PBD_ERR_UNSUPPORTED, "PBD_CONV_SPLIT / PBD_CONV_SPLIT_F16: float handles (32-channel HOG features)");
-  if (h->conv_mode == PBD_CONV_SPLIT || h->conv_mode == PBD_CONV_SPLIT_F16)
-    for (size_t i = 0; i < h->filters.size(); ++i)
-      if (!(std::fabs(h->filters[i]) < 3.0e38f)) return fail(h, PBD_ERR_UNSUPPORTED, "PBD_CONV_SPLIT: a filter weight outside bfloat16's finite range");
-  if (h->conv_mode < PBD_CONV_AUTO || h->conv_mode > PBD_CONV_SPLIT_F16) return fail(h, PBD_ERR_ARG, "conv_mode: PBD_CONV_*");
+  h->knobs = read_plan_knobs();
+  const pbd_options& o = h->opt;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(h, PBD_ERR_HIP, "no HIP device visible");
   if (o.device < 0 || o.device >= ndev) return fail(h, PBD_ERR_ARG, "bad device ordinal");
@@ -2226,13 +1394,11 @@ static int dt2d_(pbd_handle* h, const void* in, int rows, int cols, double ax, d
   // block size of THIS call's two launches: a local — the handle's dt_nt belongs to the frame plan, whose uploaded tasks carry
   // the geometry derived from it (nsub, P, chunk); overwriting it here made a detect() after a pbd_dt2d launch 128-lane blocks
   // over 256-lane tasks
-  int nt = tsz == 8 ? 64 : PBD_DT_NT_DEFAULT;
-  if (const char* e = PBD_PROBE_ENV("PBD_DT_NT")) nt = std::max(64, std::min(256, atoi(e) & ~63));
-  size_t dt_base = 40 * 1024;
-  if (const char* e = PBD_PROBE_ENV("PBD_DT_BUDGET_KB")) dt_base = (size_t)atoi(e) * 1024;
+  const int nt = h->knobs.dt_nt ? h->knobs.dt_nt : tsz == 8 ? 64 : PBD_DT_NT_DEFAULT;
+  const size_t dt_base = h->knobs.dt_budget_kb >= 0 ? (size_t)h->knobs.dt_budget_kb * 1024 : 40 * 1024;
   const size_t budget = std::max<size_t>(dt_base, dt_lds_bytes(dt_stride_for(std::max(rows, cols)), 4, tsz, nt));
   if (budget > 160 * 1024) return fail(h, PBD_ERR_UNSUPPORTED, "map too large for the LDS-resident distance transform");
-  DtGroup groups[2] = {dt_group(0, 1, rows, cols, budget, tsz, nt, h->dt_seg), dt_group(1, 1, cols, rows, budget, tsz, nt, h->dt_seg)};
+  DtGroup groups[2] = {dt_group(0, 1, rows, cols, budget, tsz, nt, h->knobs.dt_seg, true), dt_group(1, 1, cols, rows, budget, tsz, nt, h->knobs.dt_seg, false)};
   std::vector<DtTask> tasks;
   dt_add_tasks(groups[0], tasks);
   const int nx = (int)tasks.size();
