@@ -159,7 +159,9 @@ int pbd_abi_version(void);
  * 5 = pbd_create_sized, pbd_group_create_sized, pbd_get_filter_size (filter banks with a size per filter); also marks the round-6
  * refinements above.  Struct layouts unchanged; results of uniform banks unchanged.
  * Version 5 also gains, purely additively (no layout moved, no existing result changed; a binding finds them by symbol): the
- * candidate filter entry points pbd_set_candidate_filter, pbd_group_set_candidate_filter and pbd_candidates_filter.            */
+ * candidate filter entry points pbd_set_candidate_filter, pbd_group_set_candidate_filter and pbd_candidates_filter; and the
+ * depth-pruning entry points pbd_set_depth_filter, pbd_detect_rgbd_u8, pbd_detect_rgbd_enqueue_dev_u8, pbd_detect_batch_rgbd_u8,
+ * pbd_detect_batch_rgbd_enqueue_dev_u8 and pbd_candidates_depth_filter.                                                       */
 
 /* ---- output record: include/Candidate.hpp:56-111 --------------------------
  * One candidate = head + max_parts boxes (x, y, width, height as cv::Rect)
@@ -405,6 +407,56 @@ int pbd_group_set_candidate_filter(pbd_group* g, int mode, float overlap);
  * mode 2, boxes NULL or im_w / im_h <= 0 in mode 2.  boxes / locs may be NULL in mode 1.  Synchronous.                  */
 int pbd_candidates_filter(pbd_handle* h, int mode, float overlap, int im_w, int im_h, pbd_candidate_head* heads,
                           int32_t* boxes, int32_t* locs, int count, int* kept);
+
+/* ---- depth-consistency pruning: SearchSpacePruning<T>::filterCandidatesByDepth (src/SearchSpacePruning.cpp:73-94) -------
+ * The reference's detect(im, depth, candidates) has the call commented out (src/PartsBasedDetector.cpp:91-93, zfactor 0.03);
+ * here it is an opt-in per-handle step on the GPU, behind the back-tracking and in front of the candidate filter above.
+ * A candidate of component c is kept iff nparts(c) >= 2 and for every part p in 1 .. nparts(c) - 1 it is NOT true that
+ *   mc > 0 and mp > 0 and (double)|mc - mp| > sqrt((double)ax * ax + (double)ay * ay) * (double)zfactor,
+ * mc / mp = median of the depth image over box p / over the box of its parent (parentid), |mc - mp| computed in T, and
+ * (ax, ay) = anchors[defid[first mixture of part p]] — anchor(0), mixture 0, NOT the mixture the part chose (include/Parts.hpp:183).
+ * Kept from the reference:
+ *   - single-part components are always dropped: its descending `p >= 1` loop never reaches the `p == 1` push;
+ *   - the median is Math::median<T> (include/Math.hpp:63-72): the element of rank floor(n / 2) in ascending order — the upper
+ *     median for even n;
+ *   - the break only ends the loop early: the result is the AND over p.
+ * Defined here where the reference is undefined: -0.0 == +0.0; NaN pixels order above +inf, and a NaN median fails both > 0.
+ * Deviation: each box is intersected with the depth image (the reference's depth(box) throws once a box leaves the image,
+ * which boxes of parts near the frame edge routinely do); an empty intersection (or w <= 0 / h <= 0) is "no data", median 0,
+ * so the pair is not tested.
+ * The depth image's element type is T: PBD_DEPTH_32F for float handles, PBD_DEPTH_64F for double handles (Math::median<T>
+ * reads it as T; a 16-bit depth map is converted by the caller first, as src/demo.cpp does); else PBD_ERR_UNSUPPORTED.
+ *
+ * pbd_set_depth_filter: off by default; any finite zfactor (negative: every pair with both medians > 0 fails), else
+ * PBD_ERR_ARG.  PBD_ERR_STATE while a frame is pending; PBD_ERR_UNSUPPORTED for a pbd_group member (groups are out of scope).
+ * The depth-carrying entry points below take a depth image of the frame's w x hgt, stride in BYTES.  With the setting off (or
+ * a NULL depth: an empty Mat) each is exactly its plain counterpart, depth ignored as in the reference's detect().  With it
+ * on, the frame's records are pruned; then, with a candidate filter mode set, sorted (and suppressed) — the result equals
+ * pbd_candidates_sort / pbd_candidates_nms of the depth-pruned RAW output.  Counts are kept counts; PBD_ERR_CAPACITY as for
+ * the plain entry points (records before pruning over pbd_options.max_candidates; kept records over `capacity`).
+ * Depth-carrying frames run their launches eagerly, never through a captured graph (a graph stays for the plain frames), so a
+ * change of the setting applies to the next frame.  The plain entry points (and pbd_detect_image: non-8-bit colour frames
+ * have no depth-carrying variant) take no depth and are never pruned.  pbd_set_levels handles prune their own records.    */
+int pbd_set_depth_filter(pbd_handle* h, int on, float zfactor);
+int pbd_detect_rgbd_u8(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride, const void* depth, int depth_type,
+                       int dstride, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* count);
+/* then pbd_detect_collect */
+int pbd_detect_rgbd_enqueue_dev_u8(pbd_handle* h, const void* d_im, int w, int hgt, int cn, int stride, const void* d_depth,
+                                   int depth_type, int dstride);
+/* depths[f] may be NULL: frame f is not pruned */
+int pbd_detect_batch_rgbd_u8(pbd_handle* h, const uint8_t* const* ims, const void* const* depths, int nframes, int w, int hgt,
+                             int cn, int stride, int depth_type, int dstride, pbd_candidate_head* heads, int32_t* boxes,
+                             int32_t* locs, int capacity, int* counts);
+/* d_depths: nframes depth images packed back to back (stride w * element size); NULL with the setting on: PBD_ERR_ARG.
+ * Then pbd_detect_batch_collect. */
+int pbd_detect_batch_rgbd_enqueue_dev_u8(pbd_handle* h, const void* d_ims, const void* d_depths, int nframes, int w, int hgt,
+                                         int cn, int depth_type);
+/* Stand-alone: the caller's `count` host records (max_parts = the handle's; boxes required, locs may be NULL) against a host
+ * depth image of any size dw x dh (NULL only with dw or dh 0: every box is then "no data"), filtered in place, stably, through
+ * the same device kernels; *kept = records left.  PBD_ERR_ARG: non-finite zfactor, a component out of range, or an nparts
+ * that differs from the handle's model for that component.  Synchronous.                                                   */
+int pbd_candidates_depth_filter(pbd_handle* h, float zfactor, const void* depth, int depth_type, int dw, int dh, int dstride,
+                                pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int count, int* kept);
 
 /* ---- instrumentation --------------------------------------------------------
  * GPU time (ms, hipEvent) of the stages of the last synchronous detect:

@@ -46,6 +46,8 @@ EXPORTS = [
     "pbd_detect_image", "pbd_pyramid_image", "pbd_get_level_image_raw", "pbd_tune_plan",
     "pbd_create_sized", "pbd_group_create_sized", "pbd_get_filter_size",
     "pbd_set_candidate_filter", "pbd_group_set_candidate_filter", "pbd_candidates_filter",
+    "pbd_set_depth_filter", "pbd_detect_rgbd_u8", "pbd_detect_rgbd_enqueue_dev_u8", "pbd_detect_batch_rgbd_u8",
+    "pbd_detect_batch_rgbd_enqueue_dev_u8", "pbd_candidates_depth_filter",
 ]
 PBD_ABI_VERSION = 5
 
@@ -157,6 +159,82 @@ class Handle:
                                                len(heads), C.byref(kept)))
         k = kept.value
         return heads[:k], None if boxes is None else boxes[:k], None if locs is None else locs[:k]
+
+    # ---- depth-consistency pruning (SearchSpacePruning::filterCandidatesByDepth) -------------------------------
+    def set_depth_filter(self, on=True, zfactor=0.03):
+        """pbd_set_depth_filter: the *_rgbd_* detects prune their records by the depth image (0.03: the reference's commented-out call)."""
+        self._chk(self.L.pbd_set_depth_filter(self.h, int(bool(on)), C.c_float(zfactor)))
+
+    @property
+    def depth_dtype(self):
+        """element type of the depth images this handle takes: T"""
+        return np.dtype(np.float64 if self._f64 else np.float32)
+
+    def _zimg(self, depth, dtype=None):
+        """(array, PBD_DEPTH_*, stride in bytes) of a 2-D depth image; dtype=None: the handle's T"""
+        if depth is None:
+            return None, DEPTH_OF[self.depth_dtype], 0
+        d = np.ascontiguousarray(depth, dtype if dtype is not None else self.depth_dtype)
+        return d, DEPTH_OF.get(d.dtype, 7), d.shape[1] * d.itemsize
+
+    def detect_rgbd(self, im: np.ndarray, depth, capacity=4096, depth_dtype=None):
+        """pbd_detect_rgbd_u8: depth = an HxW array (converted to T unless depth_dtype is given), or None"""
+        im = np.ascontiguousarray(im, np.uint8)
+        hgt, w = im.shape[:2]
+        cn = 1 if im.ndim == 2 else im.shape[2]
+        d, dt, ds = self._zimg(depth, depth_dtype)
+        heads, boxes, locs = self._bufs(capacity)
+        cnt = C.c_int(0)
+        self._chk(self.L.pbd_detect_rgbd_u8(self.h, _p(im, C.c_uint8), w, hgt, cn, w * cn,
+                                            None if d is None else d.ctypes.data_as(C.c_void_p), dt, ds,
+                                            heads.ctypes.data_as(C.c_void_p), _p(boxes, C.c_int32), _p(locs, C.c_int32),
+                                            capacity, C.byref(cnt)))
+        return self._out(heads, boxes, locs, cnt.value)
+
+    def enqueue_rgbd_dev(self, dptr: int, w, hgt, cn, d_depth: int, dstride=None, stride=None, depth_type=None):
+        """pbd_detect_rgbd_enqueue_dev_u8 (device image and depth; d_depth 0: none); collect with collect()"""
+        dt = DEPTH_OF[self.depth_dtype] if depth_type is None else depth_type
+        self._chk(self.L.pbd_detect_rgbd_enqueue_dev_u8(self.h, C.c_void_p(dptr), w, hgt, cn, stride or w * cn,
+                                                        C.c_void_p(d_depth or None), dt, dstride or w * self.depth_dtype.itemsize))
+
+    def detect_batch_rgbd(self, frames, depths, capacity=4096, depth_dtype=None):
+        """pbd_detect_batch_rgbd_u8: depths[f] an HxW array or None"""
+        frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+        if not frames or len(depths) != len(frames) or any(f.shape != frames[0].shape for f in frames):
+            raise ValueError("detect_batch_rgbd: one depth (or None) per frame, frames of one shape")
+        hgt, w = frames[0].shape[:2]
+        cn = 1 if frames[0].ndim == 2 else frames[0].shape[2]
+        zs = [self._zimg(d, depth_dtype) for d in depths]
+        if any(z[0] is not None and z[0].shape != (hgt, w) for z in zs):
+            raise ValueError("detect_batch_rgbd: depth images of the frames' size")
+        dt = next((z[1] for z in zs if z[0] is not None), DEPTH_OF[self.depth_dtype])
+        ptrs = (C.c_void_p * len(frames))(*[f.ctypes.data for f in frames])
+        dptrs = (C.c_void_p * len(frames))(*[None if z[0] is None else z[0].ctypes.data for z in zs])
+        return self._batch_out(len(frames), capacity, lambda hd, bx, lc, cnt: self.L.pbd_detect_batch_rgbd_u8(
+            self.h, ptrs, dptrs, len(frames), w, hgt, cn, w * cn, dt, w * np.dtype(self.depth_dtype if depth_dtype is None else depth_dtype).itemsize,
+            hd, bx, lc, capacity, cnt))
+
+    def enqueue_batch_rgbd_dev(self, dptr: int, d_depths: int, nframes, w, hgt, cn, depth_type=None):
+        """frames and depth images back to back in device memory; collect with collect_batch"""
+        self._nb = nframes
+        dt = DEPTH_OF[self.depth_dtype] if depth_type is None else depth_type
+        self._chk(self.L.pbd_detect_batch_rgbd_enqueue_dev_u8(self.h, C.c_void_p(dptr), C.c_void_p(d_depths or None), nframes,
+                                                              w, hgt, cn, dt))
+
+    def candidates_depth_filter(self, heads, boxes, locs, depth, zfactor=0.03, depth_dtype=None):
+        """pbd_candidates_depth_filter: the records pruned by `depth` (HxW, any size; None: empty) on the device; returns the
+        kept (heads, boxes, locs), stable"""
+        heads = np.ascontiguousarray(heads, HEAD_DTYPE).copy()
+        boxes = np.ascontiguousarray(boxes, np.int32).copy()
+        locs = None if locs is None else np.ascontiguousarray(locs, np.int32).copy()
+        d, dt, ds = self._zimg(depth, depth_dtype)
+        dh, dw = (0, 0) if d is None else d.shape
+        kept = C.c_int(0)
+        self._chk(self.L.pbd_candidates_depth_filter(self.h, C.c_float(zfactor), None if d is None else d.ctypes.data_as(C.c_void_p),
+                                                     dt, dw, dh, ds, heads.ctypes.data_as(C.c_void_p), _p(boxes, C.c_int32),
+                                                     _p(locs, C.c_int32), len(heads), C.byref(kept)))
+        k = kept.value
+        return heads[:k], boxes[:k], None if locs is None else locs[:k]
 
     def close(self):
         if getattr(self, "h", None):

@@ -505,6 +505,60 @@ static int cand_filter_buffers(pbd_handle* h, bool masks) {
   return PBD_OK;
 }
 
+// ---- depth-consistency pruning (k_zfilter.hip) ----------------------------------------------------------------------
+// per (component, part): parentid and norm(anchor(0)) * zfactor, the reference's double expression (src/SearchSpacePruning.cpp:82-88):
+// anchor(0) = anchors[defid[first mixture of the part]] (include/Parts.hpp:183), whatever mixture the candidate chose
+static void zf_table(const pbd_handle* h, float zfactor, std::vector<int>& npart, std::vector<int>& par, std::vector<double>& thr) {
+  const int nc = h->md.ncomponents, mp = h->max_parts;
+  npart.assign((size_t)nc, 0); par.assign((size_t)nc * mp, 0); thr.assign((size_t)nc * mp, 0.0);
+  for (int c = 0; c < nc; ++c) {
+    const int f0 = h->part_offset[c], np = h->part_offset[c + 1] - f0;
+    npart[c] = np;
+    for (int p = 1; p < np; ++p) {
+      const int did = h->defid[h->mix_offset[f0 + p]];
+      const double ax = h->anchors[did * 2], ay = h->anchors[did * 2 + 1];
+      par[(size_t)c * mp + p] = h->parentid[f0 + p];
+      thr[(size_t)c * mp + p] = std::sqrt(ax * ax + ay * ay) * (double)zfactor;
+    }
+  }
+}
+// the pruning's device state: allocated on the first depth-carrying frame with the setting on; the table follows zfactor.
+// Called outside any capture (depth-carrying frames run their launches eagerly).
+static int zf_buffers(pbd_handle* h) {
+  int rc = cand_filter_buffers(h, cand_mode_now(h) == PBD_CAND_SORT_NMS);   // (d_cand_raw: the back-tracking's device output)
+  if (rc) return rc;
+  const size_t cap = (size_t)h->opt.max_candidates, nc = (size_t)h->md.ncomponents, mp = (size_t)h->max_parts;
+  if (!h->d_zf_med) {
+    HIPCHK(h, hipMalloc(&h->d_zf_npart, sizeof(int) * nc));
+    HIPCHK(h, hipMalloc(&h->d_zf_par, sizeof(int) * nc * mp));
+    HIPCHK(h, hipMalloc(&h->d_zf_thr, sizeof(double) * nc * mp));
+    HIPCHK(h, hipMalloc(&h->d_zf_med, sizeof(unsigned long long) * cap * mp));
+    HIPCHK(h, hipMalloc(&h->d_zf_large, sizeof(unsigned) * cap * mp));
+    HIPCHK(h, hipMalloc(&h->d_zf_cnt, sizeof(int) * 2));
+    HIPCHK(h, hipMalloc(&h->d_zf_out, h->cand_stride * cap));
+    h->model_bytes += (sizeof(int) + sizeof(double)) * nc * mp + sizeof(int) * nc + (sizeof(unsigned long long) + sizeof(unsigned)) * cap * mp
+                      + sizeof(int) * 2 + h->cand_stride * cap;
+    h->zf_thr_factor = std::nanf("");
+  }
+  if (!(h->zf_thr_factor == h->zf_factor)) {
+    std::vector<int> npart, par; std::vector<double> thr;
+    zf_table(h, h->zf_factor, npart, par, thr);
+    HIPCHK(h, hipMemcpy(h->d_zf_npart, npart.data(), sizeof(int) * nc, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->d_zf_par, par.data(), sizeof(int) * nc * mp, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->d_zf_thr, thr.data(), sizeof(double) * nc * mp, hipMemcpyHostToDevice));
+    h->zf_thr_factor = h->zf_factor;
+  }
+  return PBD_OK;
+}
+static ZFilterArgs zf_args(pbd_handle* h) {
+  ZFilterArgs z{};
+  z.capacity = h->opt.max_candidates; z.stride = h->cand_stride; z.mp = h->max_parts;
+  z.npart = h->d_zf_npart; z.par = h->d_zf_par; z.thr = h->d_zf_thr;
+  z.med = h->d_zf_med; z.large = h->d_zf_large; z.nlarge = (unsigned*)(h->d_zf_cnt + 1); z.cnt = h->d_zf_cnt;
+  return z;
+}
+static int zf_type(const pbd_handle* h) { return h->ts == 8 ? PBD_DEPTH_64F : PBD_DEPTH_32F; }
+
 static int run_argmin_enqueue(pbd_handle* h, bool filter = false) {
   if (h->root_dirty) {   // root tables injected since min(): the hits are those of the tables now on the device
     hipMemsetAsync(h->d_cand_count, 0, sizeof(int), h->stream);
@@ -519,6 +573,33 @@ static int run_argmin_enqueue(pbd_handle* h, bool filter = false) {
   // records beyond a first block.  Group members keep the device buffer: the all-gather reads it.
   const int cm = filter ? cand_mode_now(h) : PBD_CAND_RAW;
   h->out_filtered = cm != PBD_CAND_RAW;
+  if (filter && h->zf_frame) {
+    // depth pruning behind the back-tracking: k_backtrack writes the device buffer, k_zfilter the kept records — straight into the
+    // pinned host buffers (the count follows by a copy), or into the buffer k_cand_filter then sorts (and suppresses) as usual
+    launch_backtrack(h->d_cand_count, h->d_cand_rec, h->opt.max_candidates, h->d_back, h->md.ncomponents, h->d_parent,
+                     h->d_plane0, h->d_nparts, h->max_parts, h->d_mix_rows, h->d_cand_raw, h->cand_stride, h->ts, h->d_flat,
+                     h->d_depth, h->max_depth, (int)h->parts.size(), h->d_scr_base, h->d_dt_ixT, h->d_dt_iy,
+                     h->opt.dt_correct_ptr, h->ext_ptr ? h->d_extx : nullptr, h->d_exty, h->d_ext_base, nullptr, h->stream);
+    HIPCHK(h, hipMemsetAsync(h->d_zf_cnt, 0, sizeof(int) * 2, h->stream));
+    ZFilterArgs z = zf_args(h);
+    z.in = h->d_cand_raw; z.in_count = h->d_cand_count; z.nlevels = h->nlevels;
+    z.zimg = h->zf_img; z.zpitch = h->zf_pitch; z.zfbytes = h->zf_fbytes; z.zw = h->fw; z.zh = h->fh; z.has = h->zf_has;
+    z.out = h->out_filtered ? h->d_zf_out : h->h_cand_out;
+    launch_zfilter(z, h->ts, h->stream);
+    if (h->out_filtered) {
+      CandFilterArgs a = cand_args(h, cm, h->cand_overlap, h->fw, h->fh);
+      a.in = h->d_zf_out; a.in_count = h->d_zf_cnt; a.nlevels = h->nlevels;
+      a.back = h->d_back; a.rootv_base = h->d_rootv; a.gmask = h->d_cf_mask;
+      a.out = h->h_cand_out; a.cnt_out = h->h_cf_cnt;
+      launch_cand_filter(a, h->batch, h->stream);
+    } else {
+      HIPCHK(h, hipMemcpyAsync(h->h_cand_count, h->d_zf_cnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    }
+    LAUNCHCHK(h, "argmin + depth filter");
+    h->pending = true;
+    h->out_on_host = true;
+    return PBD_OK;
+  }
   if (h->out_filtered) {
     // Candidate::sort (+ nonMaximaSuppression) behind the back-tracking: k_backtrack writes the device buffer, k_cand_filter the kept
     // records in final order + the per-frame counts — straight into the pinned host buffers, or, for a member of an RCCL-gathering group,
@@ -674,6 +755,11 @@ static int enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride) {
     if (rc) return rc;
   }
   h->out_filtered = cand_mode_now(h) != PBD_CAND_RAW;   // (a replayed graph does not pass through run_argmin_enqueue)
+  if (h->zf_frame) {   // depth-carrying frames run eagerly: the depth pointers are per frame; a captured graph stays for plain frames
+    int rc = zf_buffers(h);
+    if (rc) return rc;
+    return enqueue_stages(h, d_src, stride);
+  }
   if (!graphable || h->frames_on_plan == 0) {
     h->frames_on_plan++;
     return enqueue_stages(h, d_src, stride);
@@ -769,6 +855,8 @@ int pbd_destroy(pbd_handle* h) {
   if (h->h_cand_count) hipHostFree(h->h_cand_count);
   hipFree(h->d_cand_raw); hipFree(h->d_cf_keys); hipFree(h->d_cf_idx); hipFree(h->d_cf_box); hipFree(h->d_cf_st); hipFree(h->d_cf_cnt);
   if (h->h_cf_cnt) hipHostFree(h->h_cf_cnt);
+  hipFree(h->d_zf_npart); hipFree(h->d_zf_par); hipFree(h->d_zf_thr); hipFree(h->d_zf_med); hipFree(h->d_zf_large); hipFree(h->d_zf_cnt);
+  hipFree(h->d_zf_out); hipFree(h->d_zimg);
   for (int i = 0; i < 8; ++i) if (h->ev[i]) hipEventDestroy(h->ev[i]);
   if (h->ev_dp0) hipEventDestroy(h->ev_dp0);
   if (h->ev_dp1) hipEventDestroy(h->ev_dp1);
@@ -1652,6 +1740,181 @@ int pbd_candidates_filter(pbd_handle* h, int mode, float overlap, int im_w, int 
     if (mode == PBD_CAND_SORT_NMS && (heads[i].nparts < 0 || heads[i].nparts > h->max_parts)) return fail(h, PBD_ERR_ARG, "nparts outside 0..max_parts");
   }
   return pbd_i_filter_host(h, mode, overlap, im_w, im_h, heads, boxes, locs, count, kept);
+}
+
+// ---- depth-consistency pruning (k_zfilter.hip) --------------------------------------------------------------------
+int pbd_set_depth_filter(pbd_handle* h, int on, float zfactor) {
+  if (!h) return PBD_ERR_ARG;
+  if (!std::isfinite(zfactor)) return fail(h, PBD_ERR_ARG, "depth filter: zfactor must be finite");
+  if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "depth filter: pbd_group members are not supported (detect through a handle of its own)");
+  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  h->zf_on = on != 0;      // (depth-carrying frames never replay a captured graph: nothing captured depends on the setting)
+  h->zf_factor = zfactor;
+  return PBD_OK;
+}
+
+// the depth arguments of a depth-carrying frame: element type T, rows of >= w elements, stride a multiple of the element size
+static int zf_check(pbd_handle* h, int depth_type, long long dstride, int w) {
+  if (depth_type != zf_type(h))
+    return fail(h, PBD_ERR_UNSUPPORTED, h->ts == 8 ? "depth image: PBD_DEPTH_64F for a double handle (Math::median<T> reads it as T)"
+                                                   : "depth image: PBD_DEPTH_32F for a float handle (Math::median<T> reads it as T)");
+  if (dstride < (long long)w * h->ts || dstride % h->ts) return fail(h, PBD_ERR_ARG, "depth stride: bytes, >= w * element size and a multiple of it");
+  return PBD_OK;
+}
+static int zf_image_buffer(pbd_handle* h, size_t bytes) {
+  if (bytes <= h->zimg_bytes) return PBD_OK;
+  if (h->d_zimg) { hipFree(h->d_zimg); h->model_bytes -= h->zimg_bytes; h->d_zimg = nullptr; h->zimg_bytes = 0; }
+  HIPCHK(h, hipMalloc(&h->d_zimg, bytes));
+  h->zimg_bytes = bytes; h->model_bytes += bytes;
+  return PBD_OK;
+}
+// enqueue_all for a frame whose depth images are set in h->zf_*: the flag lives only across the call
+static int zf_enqueue(pbd_handle* h, const uint8_t* d_src, int stride) {
+  h->zf_frame = true;
+  int rc = enqueue_all(h, d_src, stride);
+  h->zf_frame = false;
+  return rc;
+}
+
+int pbd_detect_rgbd_enqueue_dev_u8(pbd_handle* h, const void* d_im, int w, int hgt, int cn, int stride, const void* d_depth,
+                                   int depth_type, int dstride) {
+  if (!h) return PBD_ERR_ARG;
+  if (!h->zf_on || !d_depth) return pbd_detect_enqueue_dev_u8(h, d_im, w, hgt, cn, stride);
+  if (!d_im) return PBD_ERR_ARG;
+  int rc = zf_check(h, depth_type, dstride, w);
+  if (rc) return rc;
+  if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
+  if (stride < w * cn) return fail(h, PBD_ERR_ARG, "stride < w*cn");
+  ON_DEVICE(h);
+  if ((rc = plan_frame(h, w, hgt, cn))) return rc;
+  h->zf_img = (const char*)d_depth; h->zf_pitch = (size_t)dstride; h->zf_fbytes = 0; h->zf_has = 1;
+  return zf_enqueue(h, (const uint8_t*)d_im, stride);
+}
+
+int pbd_detect_rgbd_u8(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride, const void* depth, int depth_type,
+                       int dstride, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* count) {
+  if (!h) return PBD_ERR_ARG;
+  if (!h->zf_on || !depth) return pbd_detect_u8(h, im, w, hgt, cn, stride, heads, boxes, locs, capacity, count);
+  if (!im) return PBD_ERR_ARG;
+  int rc = zf_check(h, depth_type, dstride, w);
+  if (rc) return rc;
+  if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
+  if ((rc = upload_image(h, im, w, hgt, cn, stride))) return rc;
+  const size_t row = (size_t)w * h->ts;
+  if ((rc = zf_image_buffer(h, row * hgt))) return rc;
+  HIPCHK(h, hipMemcpy2DAsync(h->d_zimg, row, depth, dstride, row, hgt, hipMemcpyHostToDevice, h->stream));
+  h->zf_img = h->d_zimg; h->zf_pitch = row; h->zf_fbytes = 0; h->zf_has = 1;
+  if ((rc = zf_enqueue(h, h->d_img, w * cn))) return rc;
+  return pbd_detect_collect(h, heads, boxes, locs, capacity, count);
+}
+
+int pbd_detect_batch_rgbd_enqueue_dev_u8(pbd_handle* h, const void* d_ims, const void* d_depths, int nframes, int w, int hgt, int cn,
+                                         int depth_type) {
+  if (!h) return PBD_ERR_ARG;
+  if (!h->zf_on) return pbd_detect_batch_enqueue_dev_u8(h, d_ims, nframes, w, hgt, cn);
+  if (!d_depths) return fail(h, PBD_ERR_ARG, "device batch: the depth images are one packed buffer (NULL: use pbd_detect_batch_enqueue_dev_u8)");
+  if (!d_ims || nframes < 1) return PBD_ERR_ARG;
+  int rc = zf_check(h, depth_type, (long long)w * h->ts, w);
+  if (rc) return rc;
+  if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
+  ON_DEVICE(h);
+  if ((rc = plan_frame(h, w, hgt, cn, nframes))) return rc;
+  h->zf_img = (const char*)d_depths; h->zf_pitch = (size_t)w * h->ts; h->zf_fbytes = h->zf_pitch * hgt;
+  h->zf_has = nframes >= 64 ? ~0ull : (1ull << nframes) - 1;
+  return zf_enqueue(h, (const uint8_t*)d_ims, w * cn);
+}
+
+int pbd_detect_batch_rgbd_u8(pbd_handle* h, const uint8_t* const* ims, const void* const* depths, int nframes, int w, int hgt, int cn,
+                             int stride, int depth_type, int dstride, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs,
+                             int capacity, int* counts) {
+  if (!h) return PBD_ERR_ARG;
+  unsigned long long has = 0;
+  for (int f = 0; depths && f < nframes && f < 64; ++f) if (depths[f]) has |= 1ull << f;
+  if (!h->zf_on || !has) return pbd_detect_batch_u8(h, ims, nframes, w, hgt, cn, stride, heads, boxes, locs, capacity, counts);
+  int rc = zf_check(h, depth_type, dstride, w);
+  if (rc) return rc;
+  if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
+  if (!ims || nframes < 1 || nframes > 64) return fail(h, PBD_ERR_ARG, "batch: 1..64 frames");
+  ON_DEVICE(h);
+  const size_t row = (size_t)w * h->ts, fb = row * hgt;
+  if ((rc = zf_image_buffer(h, fb * nframes))) return rc;
+  for (int f = 0; f < nframes; ++f)
+    if (depths[f]) HIPCHK(h, hipMemcpy2DAsync(h->d_zimg + fb * f, row, depths[f], dstride, row, hgt, hipMemcpyHostToDevice, h->stream));
+  h->zf_img = h->d_zimg; h->zf_pitch = row; h->zf_fbytes = fb; h->zf_has = has;
+  h->zf_frame = true;
+  rc = pbd_detect_batch_enqueue_u8(h, ims, nframes, w, hgt, cn, stride);
+  h->zf_frame = false;
+  if (rc) return rc;
+  return pbd_detect_batch_collect(h, heads, boxes, locs, capacity, counts);
+}
+
+int pbd_candidates_depth_filter(pbd_handle* h, float zfactor, const void* depth, int depth_type, int dw, int dh, int dstride,
+                                pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int count, int* kept) {
+  if (!h) return PBD_ERR_ARG;
+  if (!std::isfinite(zfactor)) return fail(h, PBD_ERR_ARG, "depth filter: zfactor must be finite");
+  if (!kept || count < 0 || (count > 0 && (!heads || !boxes))) return fail(h, PBD_ERR_ARG, "heads / boxes / kept / count");
+  if (dw < 0 || dh < 0 || (!depth && dw > 0 && dh > 0)) return fail(h, PBD_ERR_ARG, "depth image: NULL only with an empty size");
+  const bool empty = !depth || dw == 0 || dh == 0;
+  if (depth_type != zf_type(h)) return zf_check(h, depth_type, dstride, dw);
+  if (!empty) { int rc = zf_check(h, depth_type, dstride, dw); if (rc) return rc; }
+  for (int i = 0; i < count; ++i) {
+    const int c = heads[i].component;
+    if (c < 0 || c >= h->md.ncomponents) return fail(h, PBD_ERR_ARG, "component out of range");
+    if (heads[i].nparts != h->part_offset[c + 1] - h->part_offset[c]) return fail(h, PBD_ERR_ARG, "nparts differs from the model's component");
+  }
+  if (count == 0) { *kept = 0; return PBD_OK; }
+  ON_DEVICE(h);
+  const int mp = h->max_parts, nc = h->md.ncomponents;
+  const size_t st = h->cand_stride, n = (size_t)count, row = (size_t)dw * h->ts;
+  std::vector<char> rec(st * n, 0);
+  for (size_t i = 0; i < n; ++i) {
+    char* o = rec.data() + st * i;
+    memcpy(o, heads + i, sizeof(pbd_candidate_head));
+    memcpy(o + sizeof(pbd_candidate_head), boxes + i * mp * 4, sizeof(int32_t) * mp * 4);
+  }
+  std::vector<int> npart, par; std::vector<double> thr;
+  zf_table(h, zfactor, npart, par, thr);
+  char *d_in = nullptr, *d_img = nullptr; int *d_cnt = nullptr, *d_np = nullptr, *d_par = nullptr; double* d_thr = nullptr;
+  unsigned long long* d_med = nullptr; unsigned* d_large = nullptr; uint8_t* d_flags = nullptr;
+  hipError_t e = hipSuccess;
+  auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+  chk(hipMalloc(&d_in, st * n)); chk(hipMalloc(&d_cnt, sizeof(int) * 3)); chk(hipMalloc(&d_flags, n));
+  chk(hipMalloc(&d_np, sizeof(int) * nc)); chk(hipMalloc(&d_par, sizeof(int) * nc * mp)); chk(hipMalloc(&d_thr, sizeof(double) * nc * mp));
+  chk(hipMalloc(&d_med, sizeof(unsigned long long) * n * mp)); chk(hipMalloc(&d_large, sizeof(unsigned) * n * mp));
+  if (!empty) chk(hipMalloc(&d_img, row * dh));
+  const int cnt3[3] = {count, 0, 0};
+  chk(hipMemcpy(d_in, rec.data(), st * n, hipMemcpyHostToDevice));
+  chk(hipMemcpy(d_cnt, cnt3, sizeof(cnt3), hipMemcpyHostToDevice));
+  chk(hipMemcpy(d_np, npart.data(), sizeof(int) * nc, hipMemcpyHostToDevice));
+  chk(hipMemcpy(d_par, par.data(), sizeof(int) * nc * mp, hipMemcpyHostToDevice));
+  chk(hipMemcpy(d_thr, thr.data(), sizeof(double) * nc * mp, hipMemcpyHostToDevice));
+  if (!empty) chk(hipMemcpy2D(d_img, row, depth, dstride, row, dh, hipMemcpyHostToDevice));
+  std::vector<uint8_t> flags(n, 0);
+  if (e == hipSuccess) {
+    ZFilterArgs z{};
+    z.in = d_in; z.in_count = d_cnt; z.capacity = count; z.stride = st; z.mp = mp; z.nlevels = 0;
+    z.zimg = d_img; z.zpitch = row; z.zfbytes = 0; z.zw = empty ? 0 : dw; z.zh = empty ? 0 : dh; z.has = 1;
+    z.npart = d_np; z.par = d_par; z.thr = d_thr; z.med = d_med; z.large = d_large; z.nlarge = (unsigned*)(d_cnt + 2);
+    z.cnt = d_cnt + 1; z.flags = d_flags;
+    launch_zfilter(z, h->ts, h->stream);
+    chk(hipGetLastError());
+  }
+  chk(hipMemcpyAsync(flags.data(), d_flags, n, hipMemcpyDeviceToHost, h->stream));
+  chk(hipStreamSynchronize(h->stream));
+  hipFree(d_in); hipFree(d_img); hipFree(d_cnt); hipFree(d_np); hipFree(d_par); hipFree(d_thr); hipFree(d_med); hipFree(d_large); hipFree(d_flags);
+  if (e != hipSuccess) return fail(h, PBD_ERR_HIP, std::string("depth filter: ") + hipGetErrorString(e));
+  int k = 0;
+  for (int i = 0; i < count; ++i) {   // stable compaction in place
+    if (!flags[i]) continue;
+    if (k != i) {
+      heads[k] = heads[i];
+      memmove(boxes + (size_t)k * mp * 4, boxes + (size_t)i * mp * 4, sizeof(int32_t) * mp * 4);
+      if (locs) memmove(locs + (size_t)k * mp * 3, locs + (size_t)i * mp * 3, sizeof(int32_t) * mp * 3);
+    }
+    ++k;
+  }
+  *kept = k;
+  return PBD_OK;
 }
 
 // ---- instrumentation ---------------------------------------------------------

@@ -142,6 +142,16 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   unsigned long long* d_cf_keys = nullptr; unsigned* d_cf_idx = nullptr; int* d_cf_box = nullptr; uint8_t* d_cf_st = nullptr;
   int* d_cf_cnt = nullptr; int* h_cf_cnt = nullptr;    // [2 + 2 * PBD_MAX_BATCH] (k_cand.hip); h_: pinned
   unsigned long long* d_cf_mask = nullptr; size_t cf_mask_bytes = 0;   // per-frame masks too large for LDS (frame plan)
+  // depth-consistency pruning (pbd_set_depth_filter): k_zfilter.hip behind k_backtrack.  Named z* / zf*: d_depth and max_depth
+  // above are the part tree's depth.  Allocated on the first depth-carrying frame with the setting on.
+  bool zf_on = false; float zf_factor = 0.f;
+  bool zf_frame = false;            // the frame being enqueued carries depth (set by the *_rgbd_* entry points around enqueue_all)
+  const char* zf_img = nullptr; size_t zf_pitch = 0, zf_fbytes = 0; unsigned long long zf_has = 0;   // that frame's depth images
+  int* d_zf_npart = nullptr; int* d_zf_par = nullptr; double* d_zf_thr = nullptr; float zf_thr_factor = 0.f;   // [ncomp], [ncomp * mp] x 2
+  unsigned long long* d_zf_med = nullptr; unsigned* d_zf_large = nullptr;   // [capacity * mp] each
+  int* d_zf_cnt = nullptr;          // [0] kept records, [1] boxes listed for k_zmed_large
+  char* d_zf_out = nullptr;         // kept records in front of k_cand_filter
+  char* d_zimg = nullptr; size_t zimg_bytes = 0;   // host depth images, uploaded
 };
 #define PBD_MAX_BATCH 64
 
@@ -264,3 +274,17 @@ struct CandFilterArgs {
 };
 size_t cand_filter_mask_bytes(int w, int h);
 void launch_cand_filter(const CandFilterArgs& a, int nframes, hipStream_t s);
+// depth-consistency pruning (k_zfilter.hip)
+struct ZFilterArgs {
+  const char* in; const int* in_count; int capacity;   // records (stride bytes each) and their device count
+  size_t stride; int mp;
+  int nlevels;                  // frame of a record = level / nlevels (0: one frame)
+  const char* zimg; size_t zpitch, zfbytes;   // depth (element type T) of frame f at zimg + f * zfbytes, rows zpitch bytes apart
+  int zw, zh; unsigned long long has;         // depth image size; frames that carry depth (bit f)
+  const int* npart; const int* par; const double* thr;   // [ncomp] nparts; [ncomp * mp] parentid, norm(anchor(0)) * zfactor
+  unsigned long long* med;      // [capacity * mp] median keys
+  unsigned* large; unsigned* nlarge;          // [capacity * mp] boxes for k_zmed_large, their count
+  char* out; int* cnt;          // kept records (any order) and their count; or
+  unsigned char* flags;         // non-null: a keep flag per record instead (the stand-alone primitive)
+};
+void launch_zfilter(const ZFilterArgs& a, int ts, hipStream_t s);

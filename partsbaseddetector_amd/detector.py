@@ -211,6 +211,7 @@ class PartsBasedDetector:
         """cand_filter=(mode, overlap): see setCandidateFilter."""
         self._device, self._conv, self._cap = device, conv_mode, max_candidates
         self._cand_filter = cand_filter
+        self._zfactor: Optional[float] = None   # setDepthFilter: None = off
         self._dtype = np.dtype(dtype)
         self._lb, self._le = level_begin, level_end
         self._h: Optional[capi.Handle] = None
@@ -229,6 +230,16 @@ class PartsBasedDetector:
         self.convolution_engine_ = SpatialConvolutionEngine(self._h)
         self.convolution_engine_.setFilters(model.filtersw)
         self.dp_ = DynamicProgram(self._h)
+        if self._zfactor is not None:
+            self._h.set_depth_filter(True, self._zfactor)
+
+    def setDepthFilter(self, zfactor: Optional[float] = 0.03) -> None:
+        """SearchSpacePruning.filterCandidatesByDepth(parts, candidates, depth, zfactor) inside every detect(im, depth) with a
+        non-empty depth image — the call the reference leaves commented out (src/PartsBasedDetector.cpp:91-93, zfactor 0.03) —
+        on the GPU; None turns it off (the default: depth is ignored).  Kept across distributeModel()."""
+        if self._h is not None:
+            self._h.set_depth_filter(zfactor is not None, 0.0 if zfactor is None else zfactor)
+        self._zfactor = zfactor
 
     def setCandidateFilter(self, mode: int, overlap: float = 0.0) -> None:
         """Candidate.sort (capi.PBD_CAND_SORT), or sort + Candidate.nonMaximaSuppression(overlap) (capi.PBD_CAND_SORT_NMS), of
@@ -245,9 +256,15 @@ class PartsBasedDetector:
         return self._h
 
     def detect(self, im: np.ndarray, depth=None, candidates: Optional[List[Candidate]] = None) -> List[Candidate]:
-        """src/PartsBasedDetector.cpp:69-95.  `depth` is accepted and ignored like the
-        reference (:91-93); results are APPENDED to `candidates` (DynamicProgram.cpp:250)."""
+        """src/PartsBasedDetector.cpp:69-95.  `depth` is ignored like the reference (:91-93) unless setDepthFilter() is on: then
+        a non-empty depth image (HxW, converted to T) prunes the 8-bit frame's candidates on the GPU.  Results are APPENDED to
+        `candidates` (DynamicProgram.cpp:250)."""
         out = candidates if candidates is not None else []
+        if self._zfactor is not None and depth is not None and np.asarray(depth).size > 0:
+            if np.asarray(im).dtype != np.uint8:
+                raise capi.PbdError(capi.PBD_ERR_UNSUPPORTED, "depth pruning: 8-bit colour frames only")
+            out.extend(Candidate._unpack(*self.handle.detect_rgbd(im, depth, self._cap)))
+            return out
         # (the image's dtype is its depth: uint8 -> pbd_detect_u8, the other accepted depths -> pbd_detect_image; unsupported ones raise)
         res = self.handle.detect(im, self._cap) if np.asarray(im).dtype == np.uint8 else self.handle.detect_image(im, self._cap)
         out.extend(Candidate._unpack(*res))

@@ -336,6 +336,8 @@ class Device {
   void check(int rc) const { if (rc != PBD_OK) throw Exception(rc, pbd_last_error(h)); }
   // Candidate::sort (+ nonMaximaSuppression(overlap)) of every detect() on the GPU: PBD_CAND_RAW / _SORT / _SORT_NMS
   void setCandidateFilter(int mode, float overlap = 0.f) { check(pbd_set_candidate_filter(h, mode, overlap)); }
+  // SearchSpacePruning::filterCandidatesByDepth inside every detect(im, depth) with a non-empty depth image, on the GPU
+  void setDepthFilter(bool on, float zfactor) { check(pbd_set_depth_filter(h, on ? 1 : 0, zfactor)); }
 };
 
 // ---- include/IFeatures.hpp:49-73 --------------------------------------------------------------
@@ -572,6 +574,41 @@ class DynamicProgram {
 };
 
 // ---- include/PartsBasedDetector.hpp:152-175 ----------------------------------------------------
+// ---- include/SearchSpacePruning.hpp: filterCandidatesByDepth (src/SearchSpacePruning.cpp:73-94) on the device -----------------
+// The depth Mat's element type is T (Math::median<T> reads it as T); boxes are clipped to it (pbd_c.h: the one deviation).
+// filterResponseByDepth is a no-op in the reference (it computes Z and discards it) and is not provided.
+template <typename T>
+class SearchSpacePruning {
+  std::shared_ptr<Device> dev_;
+ public:
+  explicit SearchSpacePruning(std::shared_ptr<Device> dev) : dev_(std::move(dev)) {}
+  void filterCandidatesByDepth(Parts& parts, vectorCandidate& candidates, const Mat& depth, const float zfactor) {
+    const int n = (int)candidates.size(), mp = pbd_max_parts(dev_->h);
+    if (n == 0) return;
+    std::vector<pbd_candidate_head> heads((size_t)n);
+    std::vector<int32_t> boxes((size_t)n * mp * 4, 0);
+    for (int i = 0; i < n; ++i) {
+      const Candidate& c = candidates[i];
+      const int np = parts.nparts(c.component());
+      if ((int)c.parts().size() != np) throw Exception(PBD_ERR_ARG, "filterCandidatesByDepth: a candidate's part count differs from its component's");
+      heads[i] = pbd_candidate_head{c.score(), c.component(), i, np};   // level: the input position, to map the kept ones back
+      for (int p = 0; p < np; ++p) {
+        const Rect& r = c.parts()[p];
+        int32_t* b = &boxes[((size_t)i * mp + p) * 4];
+        b[0] = r.x; b[1] = r.y; b[2] = r.width; b[3] = r.height;
+      }
+    }
+    int kept = 0;
+    dev_->check(pbd_candidates_depth_filter(dev_->h, zfactor, depth.empty() ? nullptr : depth.ptr<uint8_t>(), depth.depth(),
+                                            depth.empty() ? 0 : depth.cols, depth.empty() ? 0 : depth.rows, (int)depth.step(),
+                                            heads.data(), boxes.data(), nullptr, n, &kept));
+    vectorCandidate out;
+    out.reserve((size_t)kept);
+    for (int k = 0; k < kept; ++k) out.push_back(candidates[heads[k].level]);
+    candidates.swap(out);
+  }
+};
+
 template <typename T>
 class PartsBasedDetector {
   std::string name_;
@@ -582,6 +619,7 @@ class PartsBasedDetector {
   Parts parts_;
   int device_, conv_mode_, ncomponents_ = 0;
   int cand_mode_ = PBD_CAND_RAW; float cand_overlap_ = 0.f;
+  bool depth_on_ = false; float zfactor_ = 0.03f;
  public:
   int max_candidates_ = 4096;
   explicit PartsBasedDetector(int device = 0, int conv_mode = PBD_CONV_AUTO, int max_candidates = 4096)
@@ -604,6 +642,14 @@ class PartsBasedDetector {
     parts_ = Parts(model);                         // :121-122
     dp_ = DynamicProgram<T>(dev_);
     if (cand_mode_ != PBD_CAND_RAW) dev_->setCandidateFilter(cand_mode_, cand_overlap_);
+    if (depth_on_) dev_->setDepthFilter(true, zfactor_);
+  }
+  // SearchSpacePruning<T>::filterCandidatesByDepth(parts, candidates, depth, zfactor), the call the reference leaves commented out
+  // in detect() (src/PartsBasedDetector.cpp:91-93, zfactor 0.03), done by the GPU inside detect(im, depth, candidates) for a
+  // non-empty depth of element type T; off (the default): depth is ignored.  Kept across distributeModel().
+  void setDepthFilter(bool on, float zfactor = 0.03f) {
+    if (dev_) dev_->setDepthFilter(on, zfactor);
+    depth_on_ = on; zfactor_ = zfactor;
   }
   // What the reference's callers do after detect() — Candidate::sort, then Candidate::nonMaximaSuppression(im, candidates,
   // overlap) (ros/Node.cpp:192-196, cells/detect.cpp:237-238) — done by the GPU inside detect(): PBD_CAND_SORT or
@@ -613,13 +659,21 @@ class PartsBasedDetector {
     cand_mode_ = mode; cand_overlap_ = overlap;
   }
   void detect(const Mat& im, vectorCandidate& candidates) { detect(im, Mat(), candidates); }
-  // src/PartsBasedDetector.cpp:69-95: fused path, everything stays in HBM; `depth` ignored (:91-93)
-  void detect(const Mat& im, const Mat& /*depth*/, vectorCandidate& candidates) {
+  // src/PartsBasedDetector.cpp:69-95: fused path, everything stays in HBM; `depth` ignored (:91-93) unless setDepthFilter is on
+  void detect(const Mat& im, const Mat& depth, vectorCandidate& candidates) {
     if (!dev_) throw Exception(PBD_ERR_STATE, "detect() before distributeModel()");
     const int cap = dev_->max_candidates, mp = pbd_max_parts(dev_->h);
     std::vector<pbd_candidate_head> heads(cap);
     std::vector<int32_t> boxes((size_t)cap * mp * 4), locs((size_t)cap * mp * 3);
     int n = 0;
+    if (depth_on_ && !depth.empty()) {   // depth-carrying frames: 8-bit colour only
+      if (im.depth() != PBD_8U) throw Exception(PBD_ERR_UNSUPPORTED, "depth pruning: 8-bit colour frames only");
+      if (depth.rows != im.rows || depth.cols != im.cols) throw Exception(PBD_ERR_ARG, "depth image: the frame's size");
+      dev_->check(pbd_detect_rgbd_u8(dev_->h, im.ptr<uint8_t>(), im.cols, im.rows, im.channels(), (int)im.step(), depth.ptr<uint8_t>(),
+                                     depth.depth(), (int)depth.step(), heads.data(), boxes.data(), locs.data(), cap, &n));
+      append_candidates(candidates, heads, boxes, locs, n, mp);
+      return;
+    }
     // (CV_8U forwards to pbd_detect_u8; CV_16U / CV_32F / CV_64F: src/HOGFeatures.cpp:136-146; anything else: PBD_ERR_UNSUPPORTED = StsUnsupportedFormat)
     dev_->check(pbd_detect_image(dev_->h, im.ptr<uint8_t>(), im.depth(), im.cols, im.rows, im.channels(), (int)im.step(),
                                  heads.data(), boxes.data(), locs.data(), cap, &n));
