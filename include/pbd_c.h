@@ -161,7 +161,8 @@ int pbd_abi_version(void);
  * Version 5 also gains, purely additively (no layout moved, no existing result changed; a binding finds them by symbol): the
  * candidate filter entry points pbd_set_candidate_filter, pbd_group_set_candidate_filter and pbd_candidates_filter; and the
  * depth-pruning entry points pbd_set_depth_filter, pbd_detect_rgbd_u8, pbd_detect_rgbd_enqueue_dev_u8, pbd_detect_batch_rgbd_u8,
- * pbd_detect_batch_rgbd_enqueue_dev_u8 and pbd_candidates_depth_filter.                                                       */
+ * pbd_detect_batch_rgbd_enqueue_dev_u8 and pbd_candidates_depth_filter; and the 3-D box entry points pbd_set_box3d,
+ * pbd_get_box3d and pbd_candidates_box3d (with the structs pbd_camera and pbd_box3d).                                        */
 
 /* ---- output record: include/Candidate.hpp:56-111 --------------------------
  * One candidate = head + max_parts boxes (x, y, width, height as cv::Rect)
@@ -457,6 +458,74 @@ int pbd_detect_batch_rgbd_enqueue_dev_u8(pbd_handle* h, const void* d_ims, const
  * that differs from the handle's model for that component.  Synchronous.                                                   */
 int pbd_candidates_depth_filter(pbd_handle* h, float zfactor, const void* depth, int depth_type, int dw, int dh, int dstride,
                                 pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int count, int* kept);
+
+/* ---- 3-D bounding boxes: Candidate::boundingBox3D (include/Candidate.hpp:140-215) + PointCloudClusterer::computeBoundingBoxes
+ * (include/PointCloudClusterer.hpp:53-150) ------------------------------------------------------------------------------------
+ * Per record, with boundingBox() = bb (:105-111, the union of the UNCLIPPED part rects: min of x / y, max of x + w / y + h) and
+ * boundingBoxNorm() = bbn (:117-130):
+ *   - bbn: centroids cvRound((tl + br) * 0.5) (round half to even) of the nparts rects; cv::meanStdDev in double over them,
+ *     mean = sum * (1. / n), std = sqrt(max(sqsum * (1. / n) - mean^2, 0)) (OpenCV 2.4 multiplies by the reciprocal);
+ *     Rect(xm - 1.5 sx, ym - 1.5 sy, 3 sx, 3 sy), each argument truncated toward zero;
+ *   - boxes: the nparts part rects, then bbn, each & (0, 0, im_w, im_h) (an empty intersection is Rect()), scaled to the
+ *     depth image by s = (dw / im_w, dh / im_h) in double, x, y, w and h each truncated;
+ *   - points: the depth pixels under the boxes, box by box, with multiplicity where boxes overlap, that are != 0 and not NaN
+ *     (negative values and +-inf count).  The record is INVALID when the first box with a non-empty ROI has no such pixel
+ *     (the reference's in-loop points.empty() return of NaN).  Deviation: a record none of whose boxes has a non-empty ROI is
+ *     invalid too (the reference asserts inside cv::resize there);
+ *   - the N sorted points through cv::resize(.., Size(1, 400)), INTER_LINEAR, restated from OpenCV 2.4's resizeGeneric_ for
+ *     a float column: N == 400 copies; else for each row dy, scale = 1. / (400. / N) (scale_y = 1. / inv_scale_y),
+ *     fy = (float)((dy + 0.5) * scale - 0.5), sy = floor(fy), fy -= sy; rows sy and sy + 1 clamped to [0, N - 1] (fy not
+ *     reset at the edges); value = S0 * (1.f - fy) + S1 * fy in float (two products, one add, no FMA);
+ *   - dpoints = filter2D(points, dog), dog = filter2D(getGaussianKernel(35, 4, CV_32F), (-1, 0, 1) as a column): direct
+ *     correlation over dog's nonzero taps in raster order, a float accumulator from 0.0f, one multiply then one add per tap,
+ *     BORDER_REFLECT_101 (getGaussianKernel as OpenCV 2.4: t = exp(-0.5 / 16 * x * x) stored as float, summed in double,
+ *     each (float)(cf * (1. / sum)); computed on the host);
+ *   - from row 200, the walk up and down while (double)fabs(dpoints[m]) <= 0.035 (:197-208) gives rows dmin / dmax;
+ *     zmin = points[dmin], zmax = points[dmax];
+ *   - the cube (bb.x, bb.y, zmin) .. (bb.br, zmax) is skipped when it contains a NaN (PointCloudClusterer.hpp:80-87: invalid,
+ *     or zmax - zmin NaN, e.g. inf - inf): valid = 0, the Rect3d stays (0, 0, 0, 0, 0, 0), no centres;
+ *   - else, with ray(u, v) = ((u - cx - tx) / fx, (v - cy - ty) / fy, 1) in double
+ *     (image_geometry::PinholeCameraModel::projectPixelTo3dRay): tl = ray(bb.x, bb.y) * zmin, br = ray(bb.x + bb.w, bb.y + bb.h)
+ *     * (zmin + (zmax - zmin)), and Rect3d(tl, br) (include/Rect3.hpp:62-64): x3d, y3d, z3d = tl; width3d, height3d, depth3d
+ *     = br - tl;
+ *   - part centres (:97-141): each part & (0, 0, im_w, im_h) (empty: Rect()); centre (x + w / 2, y + h / 2) in int; avg = the
+ *     double sum of the depth pixels over the reference's TRANSPOSED window — rows x .. x + h - 1, columns y .. y + w - 1,
+ *     at image coordinates, not scaled (kept quirk) — divided by w * h when that is nonzero; centre = ray(centre) * avg.
+ *     Deviation: window pixels outside the depth image read as 0 and still count in w * h (the reference reads out of bounds).
+ *     The sum's order is the device's: equal to the reference's wherever every partial sum is exact.
+ * Depth: Mat_<float> reads it: PBD_DEPTH_32F as is, PBD_DEPTH_64F rounded to float first (also for the centres: the reference
+ * reinterprets non-float bytes there); anything else PBD_ERR_UNSUPPORTED.  None of the OpenCV 2.4 arithmetic above is pinned
+ * by a run of OpenCV.                                                                                            */
+typedef struct pbd_camera {
+  double fx, fy, cx, cy, tx, ty;   /* image_geometry::PinholeCameraModel: fx(), fy(), cx(), cy(), Tx(), Ty()                   */
+} pbd_camera;
+typedef struct pbd_box3d {
+  int32_t valid;                   /* 0: skipped ("contains nans"): Rect3d zero, centres zero                                  */
+  int32_t x, y, width, height;     /* the image-space cube: bb                                                                 */
+  float zmin, zmax;                /* points[dmin], points[dmax] (NaN when the record had no points)                           */
+  int32_t reserved;
+  double x3d, y3d, z3d, width3d, height3d, depth3d;   /* the projected Rect3d                                                  */
+} pbd_box3d;                       /* 80 bytes                                                                                 */
+/* Stand-alone: the caller's `count` host records (heads + boxes, max_parts = the handle's) against a host depth image of any
+ * size dw x dh (NULL only with dw or dh 0: every record is then invalid), for an image of im_w x im_h, through the device
+ * kernel; out[count]; centres (may be NULL): 3 * max_parts doubles per record, zero beyond nparts.  PBD_ERR_ARG: a NULL camera,
+ * non-finite intrinsics or fx / fy zero, nparts outside 1 .. max_parts, im_w or im_h <= 0.  Synchronous.                    */
+int pbd_candidates_box3d(pbd_handle* h, const pbd_camera* cam, const void* depth, int depth_type, int dw, int dh, int dstride,
+                         int im_w, int im_h, const pbd_candidate_head* heads, const int32_t* boxes, int count, pbd_box3d* out,
+                         double* centres);
+/* In-frame step, off by default: with it on, the depth-carrying entry points (pbd_detect_rgbd_u8, pbd_detect_rgbd_enqueue_dev_u8
+ * + pbd_detect_collect, pbd_detect_batch_rgbd_u8, pbd_detect_batch_rgbd_enqueue_dev_u8 + pbd_detect_batch_collect) compute one
+ * pbd_box3d per returned record, with its centres, on the device, in the frame's stream, behind the depth pruning and the
+ * candidate filter, from the depth already resident for the frame (the depth filter need not be on; the image is the frame:
+ * im = depth size).  The plain entry points, graphs and every existing result are unchanged.  cam is copied; NULL with on:
+ * PBD_ERR_ARG.  PBD_ERR_STATE while a frame is pending; PBD_ERR_UNSUPPORTED for a pbd_group member.
+ * pbd_get_box3d: after the detect / collect returned, frame `frame`'s results (entry i = the i-th record returned for that
+ * frame; centres as for pbd_candidates_box3d, may be NULL); *count = its records (PBD_ERR_CAPACITY over `capacity`).
+ * PBD_ERR_STATE after a frame that did not compute them (a plain frame, the setting off, a batch frame whose depth was NULL, a
+ * frame out of range) or while a frame is pending; PBD_ERR_UNSUPPORTED for a pbd_group member.  Buffers are allocated on first
+ * use and count in pbd_get_footprint.                                                                                        */
+int pbd_set_box3d(pbd_handle* h, int on, const pbd_camera* cam);
+int pbd_get_box3d(pbd_handle* h, int frame, pbd_box3d* out, double* centres, int capacity, int* count);
 
 /* ---- instrumentation --------------------------------------------------------
  * GPU time (ms, hipEvent) of the stages of the last synchronous detect:

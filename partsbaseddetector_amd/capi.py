@@ -48,6 +48,7 @@ EXPORTS = [
     "pbd_set_candidate_filter", "pbd_group_set_candidate_filter", "pbd_candidates_filter",
     "pbd_set_depth_filter", "pbd_detect_rgbd_u8", "pbd_detect_rgbd_enqueue_dev_u8", "pbd_detect_batch_rgbd_u8",
     "pbd_detect_batch_rgbd_enqueue_dev_u8", "pbd_candidates_depth_filter",
+    "pbd_set_box3d", "pbd_get_box3d", "pbd_candidates_box3d",
 ]
 PBD_ABI_VERSION = 5
 
@@ -60,6 +61,32 @@ class pbd_options(C.Structure):
 
 class pbd_candidate_head(C.Structure):
     _fields_ = [("score", C.c_float), ("component", C.c_int32), ("level", C.c_int32), ("nparts", C.c_int32)]
+
+
+class pbd_camera(C.Structure):
+    """image_geometry::PinholeCameraModel's fx(), fy(), cx(), cy(), Tx(), Ty()"""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("tx", C.c_double),
+                ("ty", C.c_double)]
+
+
+class pbd_box3d(C.Structure):
+    _fields_ = [("valid", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("zmin", C.c_float), ("zmax", C.c_float), ("reserved", C.c_int32), ("x3d", C.c_double), ("y3d", C.c_double),
+                ("z3d", C.c_double), ("width3d", C.c_double), ("height3d", C.c_double), ("depth3d", C.c_double)]
+
+
+BOX3D_DTYPE = np.dtype([("valid", np.int32), ("x", np.int32), ("y", np.int32), ("width", np.int32), ("height", np.int32),
+                        ("zmin", np.float32), ("zmax", np.float32), ("reserved", np.int32), ("x3d", np.float64),
+                        ("y3d", np.float64), ("z3d", np.float64), ("width3d", np.float64), ("height3d", np.float64),
+                        ("depth3d", np.float64)])
+
+
+def camera(cam) -> pbd_camera:
+    """a pbd_camera from one, or from (fx, fy, cx, cy[, tx, ty])"""
+    if isinstance(cam, pbd_camera):
+        return cam
+    v = [float(x) for x in cam]
+    return pbd_camera(*(v + [0.0] * (6 - len(v))))
 
 
 HEAD_DTYPE = np.dtype([("score", np.float32), ("component", np.int32), ("level", np.int32), ("nparts", np.int32)])
@@ -235,6 +262,42 @@ class Handle:
                                                      _p(locs, C.c_int32), len(heads), C.byref(kept)))
         k = kept.value
         return heads[:k], boxes[:k], None if locs is None else locs[:k]
+
+    # ---- 3-D boxes (Candidate::boundingBox3D + PointCloudClusterer::computeBoundingBoxes) -----------------------------
+    def set_box3d(self, on=True, cam=None):
+        """pbd_set_box3d: the *_rgbd_* detects compute a pbd_box3d (and part centres) per returned record; cam: a pbd_camera or
+        (fx, fy, cx, cy[, tx, ty])"""
+        c = None if cam is None else camera(cam)
+        self._chk(self.L.pbd_set_box3d(self.h, int(bool(on)), None if c is None else C.byref(c)))
+
+    def get_box3d(self, frame=0, capacity=None):
+        """pbd_get_box3d: (boxes as a BOX3D_DTYPE array, centres [n, max_parts, 3]) of frame `frame` of the last collect"""
+        cnt = C.c_int(0)
+        rc = self.L.pbd_get_box3d(self.h, frame, None, None, 0, C.byref(cnt))
+        if rc not in (PBD_OK, PBD_ERR_CAPACITY):
+            self._chk(rc)
+        n = cnt.value if capacity is None else capacity
+        out = np.zeros(n, BOX3D_DTYPE)
+        cen = np.zeros((n, self.max_parts, 3), np.float64)
+        self._chk(self.L.pbd_get_box3d(self.h, frame, out.ctypes.data_as(C.c_void_p), _p(cen, C.c_double), n, C.byref(cnt)))
+        return out[:cnt.value], cen[:cnt.value]
+
+    def candidates_box3d(self, heads, boxes, depth, im_w, im_h, cam, depth_dtype=None):
+        """pbd_candidates_box3d: (boxes as a BOX3D_DTYPE array, centres [n, max_parts, 3]) of the records against `depth` (HxW, any
+        size; None: empty; converted to the handle's T unless depth_dtype is given)"""
+        heads = np.ascontiguousarray(heads, HEAD_DTYPE)
+        bx = np.zeros((len(heads), self.max_parts, 4), np.int32)
+        b = np.asarray(boxes, np.int32)
+        bx[:, :b.shape[1]] = b[:, :self.max_parts]
+        d, dt, ds = self._zimg(depth, depth_dtype)
+        dh, dw = (0, 0) if d is None else d.shape
+        out = np.zeros(len(heads), BOX3D_DTYPE)
+        cen = np.zeros((len(heads), self.max_parts, 3), np.float64)
+        c = camera(cam)
+        self._chk(self.L.pbd_candidates_box3d(self.h, C.byref(c), None if d is None else d.ctypes.data_as(C.c_void_p), dt, dw, dh,
+                                              ds, int(im_w), int(im_h), heads.ctypes.data_as(C.c_void_p), _p(bx, C.c_int32),
+                                              len(heads), out.ctypes.data_as(C.c_void_p), _p(cen, C.c_double)))
+        return out, cen
 
     def close(self):
         if getattr(self, "h", None):

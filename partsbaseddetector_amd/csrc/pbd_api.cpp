@@ -7,6 +7,7 @@
 // candidates of a frame) orders the output like a single-threaded reference run.
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -559,6 +560,59 @@ static ZFilterArgs zf_args(pbd_handle* h) {
 }
 static int zf_type(const pbd_handle* h) { return h->ts == 8 ? PBD_DEPTH_64F : PBD_DEPTH_32F; }
 
+// ---- 3-D boxes (k_box3d.hip) ------------------------------------------------------------------------------------------
+// dog = filter2D(getGaussianKernel(35, 4, CV_32F), (-1, 0, 1) as a column), OpenCV 2.4's arithmetic; its nonzero taps in raster order
+static void b3_taps(Box3dArgs& a) {
+  const int n = 35;
+  float g[35], dog[35];
+  double sum = 0;
+  for (int i = 0; i < n; ++i) {
+    const double x = i - (n - 1) * 0.5;
+    g[i] = (float)std::exp(-0.5 / (4.0 * 4.0) * x * x);
+    sum += g[i];
+  }
+  sum = 1. / sum;
+  for (int i = 0; i < n; ++i) g[i] = (float)(g[i] * sum);
+  for (int i = 0; i < n; ++i) {   // taps -1 and +1 (0 skipped: a zero coefficient), BORDER_REFLECT_101
+    const int im = i - 1 < 0 ? 1 - i : i - 1, ip = i + 1 >= n ? 2 * (n - 1) - (i + 1) : i + 1;
+    float s = 0.0f;
+    s = s + -1.0f * g[im];
+    s = s + 1.0f * g[ip];
+    dog[i] = s;
+  }
+  a.ntaps = 0;
+  for (int i = 0; i < n; ++i)
+    if (dog[i] != 0.0f) { a.tap_off[a.ntaps] = i - (n - 1) / 2; a.tap[a.ntaps] = dog[i]; a.ntaps++; }
+}
+static bool b3_cam_ok(const pbd_camera* c) {
+  return c && std::isfinite(c->fx) && std::isfinite(c->fy) && std::isfinite(c->cx) && std::isfinite(c->cy) && std::isfinite(c->tx) &&
+         std::isfinite(c->ty) && c->fx != 0.0 && c->fy != 0.0;
+}
+static int b3_buffers(pbd_handle* h) {
+  if (h->h_b3) return PBD_OK;
+  const size_t cap = (size_t)h->opt.max_candidates, mp = (size_t)h->max_parts;
+  HIPCHK(h, hipHostMalloc((void**)&h->h_b3, sizeof(pbd_box3d) * cap));
+  HIPCHK(h, hipHostMalloc((void**)&h->h_b3c, sizeof(double) * cap * mp * 3));
+  h->model_bytes += sizeof(pbd_box3d) * cap + sizeof(double) * cap * mp * 3;
+  return PBD_OK;
+}
+// the frame's final records (behind the depth pruning and the candidate filter) -> one box per record slot, pinned
+static int run_box3d(pbd_handle* h) {
+  Box3dArgs a{};
+  a.stride = h->cand_stride; a.mp = h->max_parts; a.capacity = h->opt.max_candidates;
+  a.nlevels = h->nlevels;
+  if (h->out_filtered) { a.recs = h->h_cand_out; a.cf = h->h_cf_cnt; a.count = h->h_cf_cnt; a.nframes = h->batch; }
+  else if (h->zf_on) { a.recs = h->h_cand_out; a.count = h->d_zf_cnt; }
+  else { a.recs = (PBD_ARGMIN_ZERO_COPY && !h->d_gsend) ? h->h_cand_out : h->d_cand_out; a.count = h->d_cand_count; }
+  a.zimg = h->zf_img; a.zpitch = h->zf_pitch; a.zfbytes = h->zf_fbytes; a.zw = h->fw; a.zh = h->fh; a.has = h->b3_has;
+  a.im_w = h->fw; a.im_h = h->fh; a.cam = h->b3_cam;
+  b3_taps(a);
+  a.out = h->h_b3; a.centres = h->h_b3c;
+  launch_box3d(a, h->ts, h->stream);
+  LAUNCHCHK(h, "box3d");
+  return PBD_OK;
+}
+
 static int run_argmin_enqueue(pbd_handle* h, bool filter = false) {
   if (h->root_dirty) {   // root tables injected since min(): the hits are those of the tables now on the device
     hipMemsetAsync(h->d_cand_count, 0, sizeof(int), h->stream);
@@ -573,7 +627,7 @@ static int run_argmin_enqueue(pbd_handle* h, bool filter = false) {
   // records beyond a first block.  Group members keep the device buffer: the all-gather reads it.
   const int cm = filter ? cand_mode_now(h) : PBD_CAND_RAW;
   h->out_filtered = cm != PBD_CAND_RAW;
-  if (filter && h->zf_frame) {
+  if (filter && h->zf_frame && h->zf_on) {
     // depth pruning behind the back-tracking: k_backtrack writes the device buffer, k_zfilter the kept records — straight into the
     // pinned host buffers (the count follows by a copy), or into the buffer k_cand_filter then sorts (and suppresses) as usual
     launch_backtrack(h->d_cand_count, h->d_cand_rec, h->opt.max_candidates, h->d_back, h->md.ncomponents, h->d_parent,
@@ -677,7 +731,7 @@ int pbd_i_finish_frame(pbd_handle* h, int found) {
 // Candidate records (cand_stride bytes each, possibly from several handles of one group: recs[i] points at record i)
 // -> the caller's arrays, ordered like a single-threaded reference run: level, component, row-major root location.
 int pbd_i_emit(pbd_handle* h, const std::vector<const char*>& recs, pbd_candidate_head* heads, int32_t* boxes,
-               int32_t* locs, int capacity, bool ordered) {
+               int32_t* locs, int capacity, bool ordered, std::vector<int>* order_out) {
   const int mp = h->max_parts, n = (int)recs.size();
   std::vector<int> order(n);
   for (int i = 0; i < n; ++i) order[i] = i;
@@ -692,6 +746,7 @@ int pbd_i_emit(pbd_handle* h, const std::vector<const char*>& recs, pbd_candidat
     for (int k = 0; k < 4; ++k) { int ka = key(a, k), kb = key(b, k); if (ka != kb) return ka < kb; }
     return false;
   });
+  if (order_out) *order_out = order;
   if (n > capacity) return fail(h, PBD_ERR_CAPACITY, "output capacity too small");
   for (int i = 0; i < n; ++i) {
     const char* o = recs[order[i]];
@@ -705,6 +760,25 @@ int pbd_i_emit(pbd_handle* h, const std::vector<const char*>& recs, pbd_candidat
 
 int pbd_i_found(const pbd_handle* h) { return h->out_filtered ? h->h_cf_cnt[1] : h->h_cand_count[0]; }
 
+// ---- 3-D boxes of a collected frame: the pinned per-slot results, in the order the records are returned ---------------------
+static void b3_begin(pbd_handle* h, int nframes) {
+  h->b3_res.assign((size_t)nframes, {}); h->b3_cen.assign((size_t)nframes, {}); h->b3_res_on.assign((size_t)nframes, 0);
+  h->b3_ready = true;
+}
+static void b3_gather(pbd_handle* h, int f, const std::vector<const char*>& recs, const std::vector<int>& order) {
+  if (!((h->b3_has >> f) & 1ull)) return;
+  const size_t n = recs.size(), m3 = (size_t)h->max_parts * 3;
+  std::vector<pbd_box3d>& o = h->b3_res[f];
+  std::vector<double>& c = h->b3_cen[f];
+  o.resize(n); c.resize(n * m3);
+  for (size_t i = 0; i < n; ++i) {
+    const size_t slot = (size_t)(recs[order[i]] - h->h_cand_out) / h->cand_stride;
+    o[i] = h->h_b3[slot];
+    memcpy(c.data() + i * m3, h->h_b3c + slot * m3, sizeof(double) * m3);
+  }
+  h->b3_res_on[f] = 1;
+}
+
 static int collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* count) {
   if (!h->pending) return fail(h, PBD_ERR_STATE, "collect without a pending detect");
   if (h->d_gsend) return fail(h, PBD_ERR_STATE, "handle belongs to an RCCL-gathering pbd_group: collect through the group");
@@ -716,13 +790,21 @@ static int collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int
   if (rc) return rc;
   std::vector<const char*> recs((size_t)found);
   for (int i = 0; i < found; ++i) recs[i] = h->h_cand_out + h->cand_stride * i;
-  return pbd_i_emit(h, recs, heads, boxes, locs, capacity, h->out_filtered);
+  std::vector<int> order;
+  rc = pbd_i_emit(h, recs, heads, boxes, locs, capacity, h->out_filtered, h->b3_frame ? &order : nullptr);
+  if (rc) return rc;
+  if (h->b3_frame) {
+    b3_begin(h, 1);
+    b3_gather(h, 0, recs, order);
+  }
+  return PBD_OK;
 }
 int pbd_i_collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* count) {
   int rc = collect(h, heads, boxes, locs, capacity, count);
   return rc;
 }
 
+static int run_box3d(pbd_handle* h);
 static int enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride);
 int pbd_i_enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride) { return enqueue_all(h, d_src, stride); }
 static int enqueue_stages(pbd_handle* h, const uint8_t* d_src, int stride) {
@@ -739,6 +821,7 @@ static int enqueue_stages(pbd_handle* h, const uint8_t* d_src, int stride) {
   if (prof) hipEventRecord(h->ev[4], h->stream);
   if ((rc = run_argmin_enqueue(h, true))) return rc;
   if (prof) hipEventRecord(h->ev[5], h->stream);
+  if (h->b3_frame && (rc = run_box3d(h))) return rc;
   return PBD_OK;
 }
 
@@ -755,8 +838,12 @@ static int enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride) {
     if (rc) return rc;
   }
   h->out_filtered = cand_mode_now(h) != PBD_CAND_RAW;   // (a replayed graph does not pass through run_argmin_enqueue)
+  h->b3_ready = false;
+  h->b3_frame = h->zf_frame && h->b3_on;
+  h->b3_has = h->b3_frame ? h->zf_has : 0;
   if (h->zf_frame) {   // depth-carrying frames run eagerly: the depth pointers are per frame; a captured graph stays for plain frames
-    int rc = zf_buffers(h);
+    int rc = h->zf_on ? zf_buffers(h) : PBD_OK;
+    if (!rc && h->b3_frame) rc = b3_buffers(h);
     if (rc) return rc;
     return enqueue_stages(h, d_src, stride);
   }
@@ -857,6 +944,8 @@ int pbd_destroy(pbd_handle* h) {
   if (h->h_cf_cnt) hipHostFree(h->h_cf_cnt);
   hipFree(h->d_zf_npart); hipFree(h->d_zf_par); hipFree(h->d_zf_thr); hipFree(h->d_zf_med); hipFree(h->d_zf_large); hipFree(h->d_zf_cnt);
   hipFree(h->d_zf_out); hipFree(h->d_zimg);
+  if (h->h_b3) hipHostFree(h->h_b3);
+  if (h->h_b3c) hipHostFree(h->h_b3c);
   for (int i = 0; i < 8; ++i) if (h->ev[i]) hipEventDestroy(h->ev[i]);
   if (h->ev_dp0) hipEventDestroy(h->ev_dp0);
   if (h->ev_dp1) hipEventDestroy(h->ev_dp1);
@@ -1030,12 +1119,16 @@ int pbd_detect_batch_collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* 
     per[((const pbd_candidate_head*)r)->level / n1].push_back(r);
   }
   int status = PBD_OK;
+  if (h->b3_frame) b3_begin(h, B);
+  std::vector<int> order;
   for (int f = 0; f < B; ++f) {
     counts[f] = (int)per[f].size();
     pbd_candidate_head* hf = heads + (size_t)f * capacity;
-    rc = pbd_i_emit(h, per[f], hf, boxes ? boxes + (size_t)f * capacity * mp * 4 : nullptr, locs ? locs + (size_t)f * capacity * mp * 3 : nullptr, capacity, filt);
+    rc = pbd_i_emit(h, per[f], hf, boxes ? boxes + (size_t)f * capacity * mp * 4 : nullptr, locs ? locs + (size_t)f * capacity * mp * 3 : nullptr, capacity, filt,
+                    h->b3_frame ? &order : nullptr);
     if (rc == PBD_ERR_CAPACITY) { status = rc; continue; }
     if (rc) return rc;
+    if (h->b3_frame) b3_gather(h, f, per[f], order);
     for (int i = 0; i < counts[f]; ++i) hf[i].level -= f * n1;   // virtual level -> the frame's own pyramid level
   }
   return status;
@@ -1779,7 +1872,7 @@ static int zf_enqueue(pbd_handle* h, const uint8_t* d_src, int stride) {
 int pbd_detect_rgbd_enqueue_dev_u8(pbd_handle* h, const void* d_im, int w, int hgt, int cn, int stride, const void* d_depth,
                                    int depth_type, int dstride) {
   if (!h) return PBD_ERR_ARG;
-  if (!h->zf_on || !d_depth) return pbd_detect_enqueue_dev_u8(h, d_im, w, hgt, cn, stride);
+  if ((!h->zf_on && !h->b3_on) || !d_depth) return pbd_detect_enqueue_dev_u8(h, d_im, w, hgt, cn, stride);
   if (!d_im) return PBD_ERR_ARG;
   int rc = zf_check(h, depth_type, dstride, w);
   if (rc) return rc;
@@ -1794,7 +1887,7 @@ int pbd_detect_rgbd_enqueue_dev_u8(pbd_handle* h, const void* d_im, int w, int h
 int pbd_detect_rgbd_u8(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride, const void* depth, int depth_type,
                        int dstride, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* count) {
   if (!h) return PBD_ERR_ARG;
-  if (!h->zf_on || !depth) return pbd_detect_u8(h, im, w, hgt, cn, stride, heads, boxes, locs, capacity, count);
+  if ((!h->zf_on && !h->b3_on) || !depth) return pbd_detect_u8(h, im, w, hgt, cn, stride, heads, boxes, locs, capacity, count);
   if (!im) return PBD_ERR_ARG;
   int rc = zf_check(h, depth_type, dstride, w);
   if (rc) return rc;
@@ -1811,7 +1904,7 @@ int pbd_detect_rgbd_u8(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn,
 int pbd_detect_batch_rgbd_enqueue_dev_u8(pbd_handle* h, const void* d_ims, const void* d_depths, int nframes, int w, int hgt, int cn,
                                          int depth_type) {
   if (!h) return PBD_ERR_ARG;
-  if (!h->zf_on) return pbd_detect_batch_enqueue_dev_u8(h, d_ims, nframes, w, hgt, cn);
+  if (!h->zf_on && !h->b3_on) return pbd_detect_batch_enqueue_dev_u8(h, d_ims, nframes, w, hgt, cn);
   if (!d_depths) return fail(h, PBD_ERR_ARG, "device batch: the depth images are one packed buffer (NULL: use pbd_detect_batch_enqueue_dev_u8)");
   if (!d_ims || nframes < 1) return PBD_ERR_ARG;
   int rc = zf_check(h, depth_type, (long long)w * h->ts, w);
@@ -1830,7 +1923,7 @@ int pbd_detect_batch_rgbd_u8(pbd_handle* h, const uint8_t* const* ims, const voi
   if (!h) return PBD_ERR_ARG;
   unsigned long long has = 0;
   for (int f = 0; depths && f < nframes && f < 64; ++f) if (depths[f]) has |= 1ull << f;
-  if (!h->zf_on || !has) return pbd_detect_batch_u8(h, ims, nframes, w, hgt, cn, stride, heads, boxes, locs, capacity, counts);
+  if ((!h->zf_on && !h->b3_on) || !has) return pbd_detect_batch_u8(h, ims, nframes, w, hgt, cn, stride, heads, boxes, locs, capacity, counts);
   int rc = zf_check(h, depth_type, dstride, w);
   if (rc) return rc;
   if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
@@ -1914,6 +2007,87 @@ int pbd_candidates_depth_filter(pbd_handle* h, float zfactor, const void* depth,
     ++k;
   }
   *kept = k;
+  return PBD_OK;
+}
+
+// ---- 3-D boxes (k_box3d.hip) --------------------------------------------------------------------------------------------
+static_assert(sizeof(pbd_camera) == 48, "pbd_camera layout");
+static_assert(sizeof(pbd_box3d) == 80 && offsetof(pbd_box3d, zmin) == 20 && offsetof(pbd_box3d, x3d) == 32, "pbd_box3d layout");
+
+int pbd_set_box3d(pbd_handle* h, int on, const pbd_camera* cam) {
+  if (!h) return PBD_ERR_ARG;
+  if (on && !b3_cam_ok(cam)) return fail(h, PBD_ERR_ARG, "box3d: a camera with finite intrinsics and nonzero fx, fy");
+  if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "box3d: pbd_group members are not supported (detect through a handle of its own)");
+  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  h->b3_on = on != 0;
+  if (on) h->b3_cam = *cam;
+  return PBD_OK;
+}
+
+int pbd_get_box3d(pbd_handle* h, int frame, pbd_box3d* out, double* centres, int capacity, int* count) {
+  if (!h || !count || capacity < 0 || (capacity > 0 && !out)) return PBD_ERR_ARG;
+  if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "box3d: pbd_group members are not supported");
+  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (!h->b3_ready || frame < 0 || frame >= (int)h->b3_res_on.size() || !h->b3_res_on[frame])
+    return fail(h, PBD_ERR_STATE, "box3d: the last frame did not compute 3-D boxes for this frame (plain entry point, setting off, or no depth)");
+  const std::vector<pbd_box3d>& r = h->b3_res[frame];
+  const int n = (int)r.size();
+  *count = n;
+  if (n > capacity) return fail(h, PBD_ERR_CAPACITY, "output capacity too small");
+  std::copy(r.begin(), r.end(), out);
+  if (centres) std::copy(h->b3_cen[frame].begin(), h->b3_cen[frame].end(), centres);
+  return PBD_OK;
+}
+
+int pbd_candidates_box3d(pbd_handle* h, const pbd_camera* cam, const void* depth, int depth_type, int dw, int dh, int dstride,
+                         int im_w, int im_h, const pbd_candidate_head* heads, const int32_t* boxes, int count, pbd_box3d* out,
+                         double* centres) {
+  if (!h) return PBD_ERR_ARG;
+  if (!b3_cam_ok(cam)) return fail(h, PBD_ERR_ARG, "box3d: a camera with finite intrinsics and nonzero fx, fy");
+  if (im_w <= 0 || im_h <= 0) return fail(h, PBD_ERR_ARG, "box3d: im_w, im_h > 0");
+  if (count < 0 || (count > 0 && (!heads || !boxes || !out))) return fail(h, PBD_ERR_ARG, "heads / boxes / out / count");
+  if (dw < 0 || dh < 0 || (!depth && dw > 0 && dh > 0)) return fail(h, PBD_ERR_ARG, "depth image: NULL only with an empty size");
+  if (depth_type != PBD_DEPTH_32F && depth_type != PBD_DEPTH_64F)
+    return fail(h, PBD_ERR_UNSUPPORTED, "box3d: depth PBD_DEPTH_32F or PBD_DEPTH_64F (Mat_<float> reads it)");
+  const int esz = depth_type == PBD_DEPTH_64F ? 8 : 4;
+  const bool empty = !depth || dw == 0 || dh == 0;
+  if (!empty && (dstride < (long long)dw * esz || dstride % esz)) return fail(h, PBD_ERR_ARG, "depth stride: bytes, >= dw * element size and a multiple of it");
+  const int mp = h->max_parts;
+  for (int i = 0; i < count; ++i)
+    if (heads[i].nparts < 1 || heads[i].nparts > mp) return fail(h, PBD_ERR_ARG, "nparts outside 1 .. max_parts");
+  if (count == 0) return PBD_OK;
+  ON_DEVICE(h);
+  const size_t st = sizeof(pbd_candidate_head) + sizeof(int32_t) * 4 * mp, n = (size_t)count, row = (size_t)dw * esz;
+  std::vector<char> rec(st * n, 0);
+  for (size_t i = 0; i < n; ++i) {
+    memcpy(rec.data() + st * i, heads + i, sizeof(pbd_candidate_head));
+    memcpy(rec.data() + st * i + sizeof(pbd_candidate_head), boxes + i * mp * 4, sizeof(int32_t) * mp * 4);
+  }
+  char *d_in = nullptr, *d_img = nullptr; int* d_cnt = nullptr; pbd_box3d* d_out = nullptr; double* d_cen = nullptr;
+  hipError_t e = hipSuccess;
+  auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+  chk(hipMalloc(&d_in, st * n)); chk(hipMalloc(&d_cnt, sizeof(int))); chk(hipMalloc(&d_out, sizeof(pbd_box3d) * n));
+  if (centres) chk(hipMalloc(&d_cen, sizeof(double) * n * mp * 3));
+  if (!empty) chk(hipMalloc(&d_img, row * dh));
+  chk(hipMemcpy(d_in, rec.data(), st * n, hipMemcpyHostToDevice));
+  chk(hipMemcpy(d_cnt, &count, sizeof(int), hipMemcpyHostToDevice));
+  if (!empty) chk(hipMemcpy2D(d_img, row, depth, dstride, row, dh, hipMemcpyHostToDevice));
+  if (e == hipSuccess) {
+    Box3dArgs a{};
+    a.recs = d_in; a.stride = st; a.mp = mp; a.count = d_cnt; a.capacity = count; a.nlevels = 0;
+    a.zimg = d_img; a.zpitch = row; a.zfbytes = 0; a.zw = empty ? 0 : dw; a.zh = empty ? 0 : dh; a.has = 1;
+    a.im_w = im_w; a.im_h = im_h; a.cam = *cam;
+    b3_taps(a);
+    a.out = d_out; a.centres = d_cen;
+    if (depth_type == PBD_DEPTH_64F) launch_box3d(a, 8, h->stream);
+    else launch_box3d(a, 4, h->stream);
+    chk(hipGetLastError());
+  }
+  chk(hipMemcpyAsync(out, d_out, sizeof(pbd_box3d) * n, hipMemcpyDeviceToHost, h->stream));
+  if (centres) chk(hipMemcpyAsync(centres, d_cen, sizeof(double) * n * mp * 3, hipMemcpyDeviceToHost, h->stream));
+  chk(hipStreamSynchronize(h->stream));
+  hipFree(d_in); hipFree(d_img); hipFree(d_cnt); hipFree(d_out); hipFree(d_cen);
+  if (e != hipSuccess) return fail(h, PBD_ERR_HIP, std::string("box3d: ") + hipGetErrorString(e));
   return PBD_OK;
 }
 

@@ -152,6 +152,15 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   int* d_zf_cnt = nullptr;          // [0] kept records, [1] boxes listed for k_zmed_large
   char* d_zf_out = nullptr;         // kept records in front of k_cand_filter
   char* d_zimg = nullptr; size_t zimg_bytes = 0;   // host depth images, uploaded
+  // 3-D boxes (pbd_set_box3d): k_box3d.hip behind the depth pruning and the candidate filter of depth-carrying frames.  Results
+  // land in pinned host buffers indexed by record slot; the collect reorders them like the records it returns.
+  bool b3_on = false; pbd_camera b3_cam{};
+  bool b3_frame = false;            // the pending frame computes boxes (its depth frames: zf_has)
+  unsigned long long b3_has = 0;
+  pbd_box3d* h_b3 = nullptr; double* h_b3c = nullptr;   // [capacity], [capacity * mp * 3]: pinned
+  float* d_b3_taps = nullptr;
+  bool b3_ready = false;            // results of the last collected frame, per frame in the order returned
+  std::vector<std::vector<pbd_box3d>> b3_res; std::vector<std::vector<double>> b3_cen; std::vector<char> b3_res_on;
 };
 #define PBD_MAX_BATCH 64
 
@@ -202,7 +211,8 @@ int pbd_i_enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride);         
 int pbd_i_collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* count);
 int pbd_i_finish_frame(pbd_handle* h, int found);
 int pbd_i_emit(pbd_handle* h, const std::vector<const char*>& recs, pbd_candidate_head* heads, int32_t* boxes,
-               int32_t* locs, int capacity, bool ordered = false);   // ordered: the records are in final order already (k_cand_filter)
+               int32_t* locs, int capacity, bool ordered = false,    // ordered: the records are in final order already (k_cand_filter)
+               std::vector<int>* order_out = nullptr);               // order_out: the record emitted i-th is recs[order[i]]
 int pbd_i_found(const pbd_handle* h);   // records the pending frame left on the host side (filtered: the kept count)
 int pbd_i_filter_host(pbd_handle* h, int mode, float overlap, int im_w, int im_h, pbd_candidate_head* heads, int32_t* boxes,
                       int32_t* locs, int count, int* kept);   // pbd_candidates_filter without the argument checks
@@ -288,3 +298,18 @@ struct ZFilterArgs {
   unsigned char* flags;         // non-null: a keep flag per record instead (the stand-alone primitive)
 };
 void launch_zfilter(const ZFilterArgs& a, int ts, hipStream_t s);
+// 3-D boxes (k_box3d.hip)
+#define PBD_B3_MAXTAPS 35
+struct Box3dArgs {
+  const char* recs; size_t stride; int mp;    // records and their device count (count > capacity: nothing to do)
+  const int* count; int capacity;
+  const int* cf; int nframes;                 // non-null: k_cand_filter's counts; frame f's records at [cf[2+nf+f], +cf[2+f])
+  int nlevels;                                // else frame of a record = level / nlevels (0: one frame)
+  const char* zimg; size_t zpitch, zfbytes;   // depth (element type T) of frame f at zimg + f * zfbytes
+  int zw, zh; unsigned long long has;         // depth image size; frames that carry depth (bit f)
+  int im_w, im_h;
+  pbd_camera cam;
+  int ntaps; int tap_off[PBD_B3_MAXTAPS]; float tap[PBD_B3_MAXTAPS];   // dog's nonzero taps: offsets from the centre, values
+  pbd_box3d* out; double* centres;            // [capacity], [capacity * mp * 3] (centres may be null)
+};
+void launch_box3d(const Box3dArgs& a, int ts, hipStream_t s);

@@ -38,6 +38,8 @@ class Candidate:
     component: int
     level: int = -1
     locs: Optional[np.ndarray] = None  # [nparts, 3] (x, y, mixture) in cells of `level`
+    box3d: Optional[np.ndarray] = None          # setBoundingBoxes3D: this record's pbd_box3d (capi.BOX3D_DTYPE)
+    part_centers: Optional[np.ndarray] = None   # setBoundingBoxes3D: [nparts, 3] (empty when the box was skipped)
 
     def score(self) -> float:
         return float(self.confidence[0]) if len(self.confidence) else float("-inf")
@@ -61,6 +63,18 @@ class Candidate:
             h = max(y + h, int(q[1] + q[3])) - y1
             x, y = x1, y1
         return x, y, w, h
+
+    def boundingBoxNorm(self):
+        """Candidate::boundingBoxNorm (:117-130): cvRound centroids (half to even), cv::meanStdDev (sums times 1. / n), Rect of
+        doubles truncated toward zero"""
+        p = np.asarray(self.parts, np.int64)
+        out = []
+        for c in (np.rint((2 * p[:, 0] + p[:, 2]) * 0.5), np.rint((2 * p[:, 1] + p[:, 3]) * 0.5)):
+            sc = 1.0 / len(c)
+            m = float(np.sum(c)) * sc
+            out.append((m, float(np.sqrt(max(float(np.sum(c * c)) * sc - m * m, 0.0)))))
+        (mx, sx), (my, sy) = out
+        return int(mx - 1.5 * sx), int(my - 1.5 * sy), int(3 * sx), int(3 * sy)
 
     @staticmethod
     def _pack(cands: List["Candidate"]):
@@ -212,6 +226,7 @@ class PartsBasedDetector:
         self._device, self._conv, self._cap = device, conv_mode, max_candidates
         self._cand_filter = cand_filter
         self._zfactor: Optional[float] = None   # setDepthFilter: None = off
+        self._camera = None                      # setBoundingBoxes3D: None = off
         self._dtype = np.dtype(dtype)
         self._lb, self._le = level_begin, level_end
         self._h: Optional[capi.Handle] = None
@@ -232,6 +247,35 @@ class PartsBasedDetector:
         self.dp_ = DynamicProgram(self._h)
         if self._zfactor is not None:
             self._h.set_depth_filter(True, self._zfactor)
+        if self._camera is not None:
+            self._h.set_box3d(True, self._camera)
+
+    def setBoundingBoxes3D(self, camera=None) -> None:
+        """camera = (fx, fy, cx, cy[, tx, ty]) or a capi.pbd_camera: every detect(im, depth) with a non-empty depth image attaches
+        to each returned Candidate its `box3d` (Candidate::boundingBox3D projected as PointCloudClusterer::computeBoundingBoxes
+        does, capi.BOX3D_DTYPE) and `part_centers`, computed on the GPU; None turns it off (the default).  Kept across
+        distributeModel()."""
+        cam = None if camera is None else capi.camera(camera)
+        if self._h is not None:
+            self._h.set_box3d(cam is not None, cam)
+        self._camera = cam
+
+    def computeBoundingBoxes(self, im_shape, depth, candidates: List[Candidate], camera):
+        """PointCloudClusterer::computeBoundingBoxes (include/PointCloudClusterer.hpp:53-150) without its point cloud: per candidate
+        the Rect3d (x, y, z, width, height, depth) — (0, 0, 0, 0, 0, 0) for a skipped one ("contains nans") — and its part
+        centres ([nparts, 3]; empty when skipped), through pbd_candidates_box3d.  depth: HxW float32 / float64 (any size)."""
+        if not candidates:
+            return [], []
+        h, w = im_shape[:2]
+        d = np.asarray(depth)
+        heads, boxes, _ = Candidate._pack(candidates)
+        out, cen = self.handle.candidates_box3d(heads, boxes, d, w, h, camera, depth_dtype=d.dtype)
+        rects, centers = [], []
+        for i, c in enumerate(candidates):
+            o = out[i]
+            rects.append(tuple(float(o[k]) for k in ("x3d", "y3d", "z3d", "width3d", "height3d", "depth3d")))
+            centers.append(cen[i, :len(c.parts)].copy() if o["valid"] else np.zeros((0, 3)))
+        return rects, centers
 
     def setDepthFilter(self, zfactor: Optional[float] = 0.03) -> None:
         """SearchSpacePruning.filterCandidatesByDepth(parts, candidates, depth, zfactor) inside every detect(im, depth) with a
@@ -260,10 +304,16 @@ class PartsBasedDetector:
         a non-empty depth image (HxW, converted to T) prunes the 8-bit frame's candidates on the GPU.  Results are APPENDED to
         `candidates` (DynamicProgram.cpp:250)."""
         out = candidates if candidates is not None else []
-        if self._zfactor is not None and depth is not None and np.asarray(depth).size > 0:
+        if (self._zfactor is not None or self._camera is not None) and depth is not None and np.asarray(depth).size > 0:
             if np.asarray(im).dtype != np.uint8:
-                raise capi.PbdError(capi.PBD_ERR_UNSUPPORTED, "depth pruning: 8-bit colour frames only")
-            out.extend(Candidate._unpack(*self.handle.detect_rgbd(im, depth, self._cap)))
+                raise capi.PbdError(capi.PBD_ERR_UNSUPPORTED, "depth pruning / 3-D boxes: 8-bit colour frames only")
+            got = Candidate._unpack(*self.handle.detect_rgbd(im, depth, self._cap))
+            if self._camera is not None:
+                b3, cen = self.handle.get_box3d(0)
+                for i, c in enumerate(got):
+                    c.box3d = b3[i].copy()
+                    c.part_centers = cen[i, :len(c.parts)].copy() if b3[i]["valid"] else np.zeros((0, 3))
+            out.extend(got)
             return out
         # (the image's dtype is its depth: uint8 -> pbd_detect_u8, the other accepted depths -> pbd_detect_image; unsupported ones raise)
         res = self.handle.detect(im, self._cap) if np.asarray(im).dtype == np.uint8 else self.handle.detect_image(im, self._cap)
