@@ -162,7 +162,8 @@ int pbd_abi_version(void);
  * candidate filter entry points pbd_set_candidate_filter, pbd_group_set_candidate_filter and pbd_candidates_filter; and the
  * depth-pruning entry points pbd_set_depth_filter, pbd_detect_rgbd_u8, pbd_detect_rgbd_enqueue_dev_u8, pbd_detect_batch_rgbd_u8,
  * pbd_detect_batch_rgbd_enqueue_dev_u8 and pbd_candidates_depth_filter; and the 3-D box entry points pbd_set_box3d,
- * pbd_get_box3d and pbd_candidates_box3d (with the structs pbd_camera and pbd_box3d).                                        */
+ * pbd_get_box3d and pbd_candidates_box3d (with the structs pbd_camera and pbd_box3d); and the object-cluster entry points
+ * pbd_set_cluster3d, pbd_get_cluster3d and pbd_candidates_cluster3d (with the struct pbd_cluster3d).                          */
 
 /* ---- output record: include/Candidate.hpp:56-111 --------------------------
  * One candidate = head + max_parts boxes (x, y, width, height as cv::Rect)
@@ -526,6 +527,58 @@ int pbd_candidates_box3d(pbd_handle* h, const pbd_camera* cam, const void* depth
  * use and count in pbd_get_footprint.                                                                                        */
 int pbd_set_box3d(pbd_handle* h, int on, const pbd_camera* cam);
 int pbd_get_box3d(pbd_handle* h, int frame, pbd_box3d* out, double* centres, int capacity, int* count);
+
+/* ---- object clusters: PointCloudClusterer::clusterObjects (include/PointCloudClusterer.hpp:156-290) -------------------------
+ * Per record, from its Rect3d (x3d .. depth3d of its pbd_box3d; a skipped record has all zeros) and an organized cloud of
+ * cw x ch points (point index = row * cw + col):
+ *   - crop (:190-215): volume() = width3d * height3d * depth3d >= 1e-6, in double on the UNEXPANDED box (kept quirk: a negative
+ *     extent on one axis gives a negative volume and skips the record); failing it the record has no points.  Else the box is
+ *     expanded, x -= 0.1 * width3d (y, z alike), then width3d *= 1.2 (height3d, depth3d alike); min = (float)tl() and
+ *     max = (float)br(), computed in double then rounded (CropBox's Eigen::Vector4f).  A point is kept iff x, y and z are all
+ *     finite and min <= p <= max on every axis as float compares (CropBox, identity transform, inclusive faces; kept quirk: an
+ *     axis with min > max keeps nothing);
+ *   - Euclidean clusters (:224-245, EuclideanClusterExtraction, min size 1, no max): the connected components of the graph on
+ *     the cropped points joining two points iff d2 <= r2, d2 = ((dx * dx) + (dy * dy)) + (dz * dz) in float in that order
+ *     without FMA, r2 = tol * tol in float.  Deviation: PCL searches an organized cloud through OrganizedNeighbor, whose window
+ *     comes from a projection matrix it estimates from the cloud; this is the exact epsilon-graph that search intends;
+ *   - the largest cluster (:250-262).  Defined here: ties go to the cluster with the smallest point index, PCL's discovery
+ *     order (PCL leaves them to an unstable std::sort);
+ *   - its centroid (:264-278).  Deviation: summed in double (any order), divided by the count, reported in double (PCL sums in
+ *     float in index order); NaN when nothing was cropped;
+ *   - its point indices, ascending (:283-285, ExtractIndices).
+ * None of this PCL behaviour is pinned by a run of PCL.                                                          */
+typedef struct pbd_cluster3d {
+  int32_t cropped;                 /* points inside the expanded box                                                         */
+  int32_t nclusters;               /* Euclidean clusters among them                                                          */
+  int32_t size;                    /* points of the kept cluster; 0: none                                                    */
+  int32_t first;                   /* its smallest point index; -1: none                                                     */
+  double cx, cy, cz;               /* its centroid; NaN when none                                                            */
+} pbd_cluster3d;                   /* 40 bytes                                                                               */
+/* Stand-alone: the caller's organized host cloud (x, y, z floats at the start of each point; point_stride >= 12 and row_stride
+ * in BYTES, both multiples of 4, so PCL PointXYZ (16 B) and PointXYZRGB (32 B) buffers go in as they are) against `count`
+ * pbd_box3d through the device kernel; out[count].  indices: the kept clusters' points, record after record, each list
+ * ascending, at the exclusive prefix sum of out[].size; *idx_total = their number.  indices NULL: a size query (idx_total may
+ * then be NULL too); more than idx_capacity: PBD_ERR_CAPACITY with out[] and *idx_total set.  PBD_ERR_ARG: a non-finite or
+ * <= 0 tolerance, a stride below 12 (points) or below (cw - 1) * point_stride + 12 (rows) or not a multiple of 4, a NULL cloud
+ * with cw * ch > 0, negative sizes.  Synchronous.                                                                             */
+int pbd_candidates_cluster3d(pbd_handle* h, const void* cloud, int cw, int ch, int point_stride, int row_stride,
+                             const pbd_box3d* boxes, int count, float tolerance, pbd_cluster3d* out, int32_t* indices,
+                             int idx_capacity, int* idx_total);
+/* In-frame step, off by default: with it on, the frames that compute 3-D boxes (pbd_set_box3d) also compute one pbd_cluster3d
+ * per returned record on the device, in the frame's stream, right behind k_box3d, from the frame's cloud: the frame's depth
+ * image (cw x ch = the frame) through the camera given to pbd_set_box3d.  For depth d (PBD_DEPTH_64F rounded to float first):
+ * z = d, x = (float)(((u - cx - tx) / fx) * d), y = (float)(((v - cy - ty) / fy) * d) computed in double; d == 0 or a
+ * non-finite d gives no point (NaN: depth_image_proc / openni).  The plain entry points, graphs and every existing result are
+ * unchanged.  tolerance: the reference's 0.010; PBD_ERR_ARG when on and non-finite or <= 0.  PBD_ERR_STATE while a frame is
+ * pending; PBD_ERR_UNSUPPORTED for a pbd_group member.
+ * pbd_get_cluster3d: after the detect / collect returned, frame `frame`'s results (entry i = the i-th record returned for that
+ * frame; indices as for pbd_candidates_cluster3d); *count = its records (PBD_ERR_CAPACITY over `capacity`, or over
+ * idx_capacity with *idx_total set).  PBD_ERR_STATE after a frame that computed no 3-D boxes or clusters, or while a frame is
+ * pending; PBD_ERR_UNSUPPORTED for a pbd_group member.  Scratch (one whole frame's points per concurrent record) is allocated
+ * on first use and counts in pbd_get_footprint.                                                                               */
+int pbd_set_cluster3d(pbd_handle* h, int on, float tolerance);
+int pbd_get_cluster3d(pbd_handle* h, int frame, pbd_cluster3d* out, int capacity, int* count, int32_t* indices, int idx_capacity,
+                      int* idx_total);
 
 /* ---- instrumentation --------------------------------------------------------
  * GPU time (ms, hipEvent) of the stages of the last synchronous detect:

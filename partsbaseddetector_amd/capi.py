@@ -49,6 +49,7 @@ EXPORTS = [
     "pbd_set_depth_filter", "pbd_detect_rgbd_u8", "pbd_detect_rgbd_enqueue_dev_u8", "pbd_detect_batch_rgbd_u8",
     "pbd_detect_batch_rgbd_enqueue_dev_u8", "pbd_candidates_depth_filter",
     "pbd_set_box3d", "pbd_get_box3d", "pbd_candidates_box3d",
+    "pbd_set_cluster3d", "pbd_get_cluster3d", "pbd_candidates_cluster3d",
 ]
 PBD_ABI_VERSION = 5
 
@@ -79,6 +80,10 @@ BOX3D_DTYPE = np.dtype([("valid", np.int32), ("x", np.int32), ("y", np.int32), (
                         ("zmin", np.float32), ("zmax", np.float32), ("reserved", np.int32), ("x3d", np.float64),
                         ("y3d", np.float64), ("z3d", np.float64), ("width3d", np.float64), ("height3d", np.float64),
                         ("depth3d", np.float64)])
+
+
+CLUSTER3D_DTYPE = np.dtype([("cropped", np.int32), ("nclusters", np.int32), ("size", np.int32), ("first", np.int32),
+                            ("cx", np.float64), ("cy", np.float64), ("cz", np.float64)])
 
 
 def camera(cam) -> pbd_camera:
@@ -298,6 +303,51 @@ class Handle:
                                               ds, int(im_w), int(im_h), heads.ctypes.data_as(C.c_void_p), _p(bx, C.c_int32),
                                               len(heads), out.ctypes.data_as(C.c_void_p), _p(cen, C.c_double)))
         return out, cen
+
+    # ---- object clusters (PointCloudClusterer::clusterObjects) ---------------------------------------------------------
+    def set_cluster3d(self, on=True, tolerance=0.01):
+        """pbd_set_cluster3d: the frames that compute 3-D boxes also compute the object cluster of every returned record"""
+        self._chk(self.L.pbd_set_cluster3d(self.h, int(bool(on)), C.c_float(tolerance)))
+
+    def get_cluster3d(self, frame=0):
+        """pbd_get_cluster3d: (results as a CLUSTER3D_DTYPE array, the kept clusters' indices one after the other) of frame
+        `frame` of the last collect; record i's indices start at the exclusive prefix sum of results["size"]"""
+        cnt, tot = C.c_int(0), C.c_int(0)
+        rc = self.L.pbd_get_cluster3d(self.h, frame, None, 0, C.byref(cnt), None, 0, C.byref(tot))
+        if rc not in (PBD_OK, PBD_ERR_CAPACITY):
+            self._chk(rc)
+        out = np.zeros(cnt.value, CLUSTER3D_DTYPE)
+        idx = np.zeros(max(tot.value, 1), np.int32)
+        self._chk(self.L.pbd_get_cluster3d(self.h, frame, out.ctypes.data_as(C.c_void_p), len(out), C.byref(cnt),
+                                           _p(idx, C.c_int32), len(idx), C.byref(tot)))
+        return out[:cnt.value], idx[:tot.value]
+
+    def candidates_cluster3d(self, cloud, boxes3d, tolerance=0.01):
+        """pbd_candidates_cluster3d: (results as a CLUSTER3D_DTYPE array, the kept clusters' indices one after the other) of the
+        pbd_box3d records `boxes3d` (BOX3D_DTYPE) against the organized cloud, an [h, w, 3] float32 array (cluster3d_raw takes
+        strided buffers such as PCL's PointXYZ / PointXYZRGB)"""
+        c = np.ascontiguousarray(cloud, np.float32)
+        if c.ndim != 3 or c.shape[2] != 3:
+            raise ValueError("cloud: [h, w, 3] float32")
+        ch, cw = c.shape[:2]
+        return self._cluster3d(c, cw, ch, 12, 12 * cw, np.ascontiguousarray(boxes3d, BOX3D_DTYPE), tolerance)
+
+    def cluster3d_raw(self, buf, cw, ch, point_stride, row_stride, boxes3d, tolerance=0.01):
+        """pbd_candidates_cluster3d on a raw buffer with explicit geometry (strides in bytes)"""
+        return self._cluster3d(np.ascontiguousarray(buf), cw, ch, point_stride, row_stride,
+                               np.ascontiguousarray(boxes3d, BOX3D_DTYPE), tolerance)
+
+    def _cluster3d(self, c, cw, ch, ps, rs, b, tol):
+        out = np.zeros(len(b), CLUSTER3D_DTYPE)
+        tot = C.c_int(0)
+        cp = c.ctypes.data_as(C.c_void_p) if c.size else None
+        self._chk(self.L.pbd_candidates_cluster3d(self.h, cp, int(cw), int(ch), int(ps), int(rs), b.ctypes.data_as(C.c_void_p),
+                                                  len(b), C.c_float(tol), out.ctypes.data_as(C.c_void_p), None, 0, C.byref(tot)))
+        idx = np.zeros(max(tot.value, 1), np.int32)
+        self._chk(self.L.pbd_candidates_cluster3d(self.h, cp, int(cw), int(ch), int(ps), int(rs), b.ctypes.data_as(C.c_void_p),
+                                                  len(b), C.c_float(tol), out.ctypes.data_as(C.c_void_p), _p(idx, C.c_int32),
+                                                  len(idx), C.byref(tot)))
+        return out, idx[:tot.value]
 
     def close(self):
         if getattr(self, "h", None):

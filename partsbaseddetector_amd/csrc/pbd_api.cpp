@@ -610,6 +610,110 @@ static int run_box3d(pbd_handle* h) {
   a.out = h->h_b3; a.centres = h->h_b3c;
   launch_box3d(a, h->ts, h->stream);
   LAUNCHCHK(h, "box3d");
+  if (h->cl3_frame) {   // the object clusters of the same records, right behind
+    Cluster3dArgs c{};
+    c.recs = a.recs; c.stride = a.stride; c.count = a.count; c.capacity = a.capacity; c.cf = a.cf; c.nframes = a.nframes;
+    c.nlevels = a.nlevels; c.has = a.has;
+    c.boxes = h->h_b3;
+    c.cloud = h->zf_img; c.pstride = h->ts; c.rstride = h->zf_pitch; c.fbytes = h->zf_fbytes; c.cw = h->fw; c.ch = h->fh;
+    c.cam = h->b3_cam; c.tol = h->cl3_tol;
+    c.scratch = h->d_cl3_scratch; c.slot_bytes = cluster3d_slot_bytes(h->cl3_pcap); c.pcap = h->cl3_pcap;
+    c.out = h->h_cl3; c.pool = h->d_cl3_pool; c.pool_cap = h->cl3_pool_cap; c.pool_used = h->d_cl3_used;
+    HIPCHK(h, hipMemsetAsync(h->d_cl3_used, 0, sizeof(unsigned long long), h->stream));
+    launch_cluster3d(c, h->ts, std::min(h->cl3_slots, a.capacity), h->stream);
+    LAUNCHCHK(h, "cluster3d");
+    h->cl3_args = c;
+  }
+  return PBD_OK;
+}
+
+// ---- object clusters (k_cluster3d.hip) --------------------------------------------------------------------------------
+// Scratch: one slot of a whole cloud's points per concurrent record, as many slots as fit this budget (at least one, at most one
+// per record and PBD_CL3_MAX_SLOTS), so that no record can fail for lack of scratch.
+#define PBD_CL3_SCRATCH_BUDGET ((size_t)256 << 20)
+#define PBD_CL3_MAX_SLOTS 256
+static int cl3_slots(int pcap, long long records) {
+  const size_t s = PBD_CL3_SCRATCH_BUDGET / cluster3d_slot_bytes(pcap);
+  return (int)std::max<long long>(1, std::min<long long>({(long long)s, records, (long long)PBD_CL3_MAX_SLOTS}));
+}
+static int cl3_buffers(pbd_handle* h) {
+  const size_t cap = (size_t)h->opt.max_candidates;
+  if (!h->h_cl3) {
+    HIPCHK(h, hipHostMalloc((void**)&h->h_cl3, sizeof(Cl3Res) * cap));
+    HIPCHK(h, hipMalloc(&h->d_cl3_used, sizeof(unsigned long long)));
+    h->model_bytes += sizeof(Cl3Res) * cap + sizeof(unsigned long long);
+  }
+  const int pcap = h->fw * h->fh;
+  if (pcap > h->cl3_pcap) {
+    if (h->d_cl3_scratch) { hipFree(h->d_cl3_scratch); h->d_cl3_scratch = nullptr; h->model_bytes -= h->cl3_scratch_bytes; }
+    h->cl3_pcap = 0; h->cl3_scratch_bytes = 0;
+    const int slots = cl3_slots(pcap, (long long)cap);
+    const size_t bytes = cluster3d_slot_bytes(pcap) * slots;
+    HIPCHK(h, hipMalloc(&h->d_cl3_scratch, bytes));
+    h->cl3_pcap = pcap; h->cl3_slots = slots; h->cl3_scratch_bytes = bytes; h->model_bytes += bytes;
+  }
+  const unsigned long long pool = 4ull * (unsigned long long)pcap;   // grows when a frame's kept clusters need more (cl3_resolve)
+  if (h->cl3_pool_cap < pool) {
+    if (h->d_cl3_pool) { hipFree(h->d_cl3_pool); h->d_cl3_pool = nullptr; h->model_bytes -= sizeof(int) * h->cl3_pool_cap; }
+    h->cl3_pool_cap = 0;
+    HIPCHK(h, hipMalloc(&h->d_cl3_pool, sizeof(int) * pool));
+    h->cl3_pool_cap = pool; h->model_bytes += sizeof(int) * pool;
+  }
+  return PBD_OK;
+}
+// After the launch `a` (synchronised): the records `lst` = (record, frame) pairs in output order -> res[] and their kept clusters'
+// indices one after the other in idx[].  Records whose indices did not fit the pool run again, alone, into a pool grown to what
+// they need (and at least what the launch claimed in all, so that the next launch fits); `pool` / `pool_cap` follow the growth.
+static int cl3_resolve(pbd_handle* h, Cluster3dArgs a, int src, int slots, int*& pool, unsigned long long& pool_cap, bool owned,
+                       const std::vector<int>& lst, std::vector<pbd_cluster3d>& res, std::vector<int32_t>& idx) {
+  unsigned long long used = 0;
+  HIPCHK(h, hipMemcpy(&used, a.pool_used, sizeof(used), hipMemcpyDeviceToHost));
+  std::vector<int32_t> first((size_t)std::min(used, pool_cap));
+  if (!first.empty()) HIPCHK(h, hipMemcpy(first.data(), pool, sizeof(int32_t) * first.size(), hipMemcpyDeviceToHost));
+  const size_t n = lst.size() / 2;
+  std::vector<int> spill;
+  std::vector<char> again(n, 0);
+  unsigned long long need = 0;
+  for (size_t k = 0; k < n; ++k) {
+    const Cl3Res& r = a.out[lst[2 * k]];
+    if (r.off < 0 && r.r.size > 0) { spill.push_back(lst[2 * k]); spill.push_back(lst[2 * k + 1]); need += r.r.size; again[k] = 1; }
+  }
+  std::vector<int32_t> second;
+  if (!spill.empty()) {
+    const unsigned long long ncap = std::max(need, used);
+    if (ncap > pool_cap) {
+      hipFree(pool); pool = nullptr;
+      if (owned) h->model_bytes -= sizeof(int) * pool_cap;
+      pool_cap = 0;
+      HIPCHK(h, hipMalloc(&pool, sizeof(int) * ncap));
+      pool_cap = ncap;
+      if (owned) h->model_bytes += sizeof(int) * ncap;
+    }
+    int* d_list = nullptr;
+    HIPCHK(h, hipMalloc(&d_list, sizeof(int) * spill.size()));
+    hipError_t e = hipMemcpy(d_list, spill.data(), sizeof(int) * spill.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemsetAsync(a.pool_used, 0, sizeof(unsigned long long), h->stream);
+    if (e == hipSuccess) {
+      a.list = d_list; a.nlist = (int)(spill.size() / 2); a.pool = pool; a.pool_cap = pool_cap;
+      launch_cluster3d(a, src, std::min(slots, a.nlist), h->stream);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    second.resize((size_t)need);
+    if (e == hipSuccess && need) e = hipMemcpy(second.data(), pool, sizeof(int32_t) * need, hipMemcpyDeviceToHost);
+    hipFree(d_list);
+    if (e != hipSuccess) return fail(h, PBD_ERR_HIP, std::string("cluster3d: ") + hipGetErrorString(e));
+  }
+  res.resize(n);
+  idx.clear();
+  for (size_t k = 0; k < n; ++k) {
+    const Cl3Res& r = a.out[lst[2 * k]];
+    res[k] = r.r;
+    if (r.r.size <= 0) continue;
+    const std::vector<int32_t>& from = again[k] ? second : first;
+    if (r.off < 0 || (unsigned long long)r.off + r.r.size > from.size()) return fail(h, PBD_ERR_HIP, "cluster3d: a record's indices are missing");
+    idx.insert(idx.end(), from.begin() + r.off, from.begin() + r.off + r.r.size);
+  }
   return PBD_OK;
 }
 
@@ -764,6 +868,9 @@ int pbd_i_found(const pbd_handle* h) { return h->out_filtered ? h->h_cf_cnt[1] :
 static void b3_begin(pbd_handle* h, int nframes) {
   h->b3_res.assign((size_t)nframes, {}); h->b3_cen.assign((size_t)nframes, {}); h->b3_res_on.assign((size_t)nframes, 0);
   h->b3_ready = true;
+  h->cl3_ready = false;
+  h->cl3_slot.assign((size_t)nframes, {}); h->cl3_res.assign((size_t)nframes, {}); h->cl3_idx.assign((size_t)nframes, {});
+  h->cl3_res_on.assign((size_t)nframes, 0);
 }
 static void b3_gather(pbd_handle* h, int f, const std::vector<const char*>& recs, const std::vector<int>& order) {
   if (!((h->b3_has >> f) & 1ull)) return;
@@ -775,8 +882,34 @@ static void b3_gather(pbd_handle* h, int f, const std::vector<const char*>& recs
     const size_t slot = (size_t)(recs[order[i]] - h->h_cand_out) / h->cand_stride;
     o[i] = h->h_b3[slot];
     memcpy(c.data() + i * m3, h->h_b3c + slot * m3, sizeof(double) * m3);
+    if (h->cl3_frame) h->cl3_slot[f].push_back((int)slot);
   }
   h->b3_res_on[f] = 1;
+}
+// the object clusters of the frames b3_gather listed (the collect synchronised the stream)
+static int b3_end(pbd_handle* h) {
+  if (!h->cl3_frame) return PBD_OK;
+  std::vector<int> lst;
+  const int nf = (int)h->cl3_slot.size();
+  for (int f = 0; f < nf; ++f)
+    if (h->b3_res_on[f]) for (int s : h->cl3_slot[f]) { lst.push_back(s); lst.push_back(f); }
+  std::vector<pbd_cluster3d> res;
+  std::vector<int32_t> idx;
+  int rc = cl3_resolve(h, h->cl3_args, h->ts, h->cl3_slots, h->d_cl3_pool, h->cl3_pool_cap, true, lst, res, idx);
+  if (rc) return rc;
+  size_t r0 = 0, i0 = 0;
+  for (int f = 0; f < nf; ++f) {
+    if (!h->b3_res_on[f]) continue;
+    const size_t m = h->cl3_slot[f].size();
+    size_t ni = 0;
+    for (size_t k = 0; k < m; ++k) ni += (size_t)std::max(res[r0 + k].size, 0);
+    h->cl3_res[f].assign(res.begin() + r0, res.begin() + r0 + m);
+    h->cl3_idx[f].assign(idx.begin() + i0, idx.begin() + i0 + ni);
+    h->cl3_res_on[f] = 1;
+    r0 += m; i0 += ni;
+  }
+  h->cl3_ready = true;
+  return PBD_OK;
 }
 
 static int collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* count) {
@@ -796,6 +929,7 @@ static int collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int
   if (h->b3_frame) {
     b3_begin(h, 1);
     b3_gather(h, 0, recs, order);
+    if ((rc = b3_end(h))) return rc;
   }
   return PBD_OK;
 }
@@ -838,12 +972,14 @@ static int enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride) {
     if (rc) return rc;
   }
   h->out_filtered = cand_mode_now(h) != PBD_CAND_RAW;   // (a replayed graph does not pass through run_argmin_enqueue)
-  h->b3_ready = false;
+  h->b3_ready = false; h->cl3_ready = false;
   h->b3_frame = h->zf_frame && h->b3_on;
+  h->cl3_frame = h->b3_frame && h->cl3_on;
   h->b3_has = h->b3_frame ? h->zf_has : 0;
   if (h->zf_frame) {   // depth-carrying frames run eagerly: the depth pointers are per frame; a captured graph stays for plain frames
     int rc = h->zf_on ? zf_buffers(h) : PBD_OK;
     if (!rc && h->b3_frame) rc = b3_buffers(h);
+    if (!rc && h->cl3_frame) rc = cl3_buffers(h);
     if (rc) return rc;
     return enqueue_stages(h, d_src, stride);
   }
@@ -946,6 +1082,8 @@ int pbd_destroy(pbd_handle* h) {
   hipFree(h->d_zf_out); hipFree(h->d_zimg);
   if (h->h_b3) hipHostFree(h->h_b3);
   if (h->h_b3c) hipHostFree(h->h_b3c);
+  if (h->h_cl3) hipHostFree(h->h_cl3);
+  hipFree(h->d_cl3_scratch); hipFree(h->d_cl3_pool); hipFree(h->d_cl3_used);
   for (int i = 0; i < 8; ++i) if (h->ev[i]) hipEventDestroy(h->ev[i]);
   if (h->ev_dp0) hipEventDestroy(h->ev_dp0);
   if (h->ev_dp1) hipEventDestroy(h->ev_dp1);
@@ -1131,6 +1269,7 @@ int pbd_detect_batch_collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* 
     if (h->b3_frame) b3_gather(h, f, per[f], order);
     for (int i = 0; i < counts[f]; ++i) hf[i].level -= f * n1;   // virtual level -> the frame's own pyramid level
   }
+  if (h->b3_frame && (rc = b3_end(h))) return rc;
   return status;
 }
 int pbd_detect_batch_u8(pbd_handle* h, const uint8_t* const* ims, int nframes, int w, int hgt, int cn, int stride,
@@ -2089,6 +2228,103 @@ int pbd_candidates_box3d(pbd_handle* h, const pbd_camera* cam, const void* depth
   hipFree(d_in); hipFree(d_img); hipFree(d_cnt); hipFree(d_out); hipFree(d_cen);
   if (e != hipSuccess) return fail(h, PBD_ERR_HIP, std::string("box3d: ") + hipGetErrorString(e));
   return PBD_OK;
+}
+
+// ---- object clusters (k_cluster3d.hip) ----------------------------------------------------------------------------------
+static_assert(sizeof(pbd_cluster3d) == 40 && offsetof(pbd_cluster3d, first) == 12 && offsetof(pbd_cluster3d, cx) == 16,
+              "pbd_cluster3d layout");
+static bool cl3_tol_ok(float t) { return std::isfinite(t) && t > 0.f; }
+
+int pbd_set_cluster3d(pbd_handle* h, int on, float tolerance) {
+  if (!h) return PBD_ERR_ARG;
+  if (on && !cl3_tol_ok(tolerance)) return fail(h, PBD_ERR_ARG, "cluster3d: a finite tolerance > 0");
+  if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "cluster3d: pbd_group members are not supported (detect through a handle of its own)");
+  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  h->cl3_on = on != 0;
+  if (on) h->cl3_tol = tolerance;
+  return PBD_OK;
+}
+
+// results + their indices (the exclusive prefix sum of size) -> the caller's arrays
+static int cl3_copy_out(pbd_handle* h, const std::vector<int32_t>& idx, int32_t* indices, int idx_capacity, int* idx_total) {
+  if (idx_total) *idx_total = (int)idx.size();
+  if (!indices) return PBD_OK;
+  if ((long long)idx.size() > (long long)idx_capacity) return fail(h, PBD_ERR_CAPACITY, "cluster3d: index capacity too small");
+  std::copy(idx.begin(), idx.end(), indices);
+  return PBD_OK;
+}
+
+int pbd_get_cluster3d(pbd_handle* h, int frame, pbd_cluster3d* out, int capacity, int* count, int32_t* indices, int idx_capacity,
+                      int* idx_total) {
+  if (!h || !count || capacity < 0 || (capacity > 0 && !out) || (indices && (idx_capacity < 0 || !idx_total))) return PBD_ERR_ARG;
+  if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "cluster3d: pbd_group members are not supported");
+  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (!h->cl3_ready || frame < 0 || frame >= (int)h->cl3_res_on.size() || !h->cl3_res_on[frame])
+    return fail(h, PBD_ERR_STATE, "cluster3d: the last frame did not compute object clusters for this frame (plain entry point, "
+                                  "3-D boxes or clusters off, or no depth)");
+  const std::vector<pbd_cluster3d>& r = h->cl3_res[frame];
+  const int n = (int)r.size();
+  *count = n;
+  if (idx_total) *idx_total = (int)h->cl3_idx[frame].size();
+  if (n > capacity) return fail(h, PBD_ERR_CAPACITY, "output capacity too small");
+  std::copy(r.begin(), r.end(), out);
+  return cl3_copy_out(h, h->cl3_idx[frame], indices, idx_capacity, idx_total);
+}
+
+int pbd_candidates_cluster3d(pbd_handle* h, const void* cloud, int cw, int ch, int point_stride, int row_stride,
+                             const pbd_box3d* boxes, int count, float tolerance, pbd_cluster3d* out, int32_t* indices,
+                             int idx_capacity, int* idx_total) {
+  if (!h) return PBD_ERR_ARG;
+  if (!cl3_tol_ok(tolerance)) return fail(h, PBD_ERR_ARG, "cluster3d: a finite tolerance > 0");
+  if (cw < 0 || ch < 0 || (long long)cw * ch > (1ll << 30)) return fail(h, PBD_ERR_ARG, "cluster3d: cloud size");
+  const long long npts = (long long)cw * ch;
+  if (point_stride < 12 || point_stride % 4) return fail(h, PBD_ERR_ARG, "cluster3d: point stride: bytes, >= 12 and a multiple of 4");
+  if (npts > 0 && (!cloud || row_stride % 4 || (long long)row_stride < (long long)(cw - 1) * point_stride + 12))
+    return fail(h, PBD_ERR_ARG, "cluster3d: a cloud (NULL only when empty), row stride: bytes, >= (cw - 1) * point stride + 12, a multiple of 4");
+  if (count < 0 || (count > 0 && (!boxes || !out))) return fail(h, PBD_ERR_ARG, "boxes / out / count");
+  if (indices && (idx_capacity < 0 || !idx_total)) return fail(h, PBD_ERR_ARG, "indices: idx_capacity >= 0 and idx_total");
+  if (count == 0) return cl3_copy_out(h, {}, indices, idx_capacity, idx_total);
+  ON_DEVICE(h);
+  const int pcap = (int)std::max<long long>(npts, 1);
+  const int slots = cl3_slots(pcap, count);
+  const size_t bytes = npts ? (size_t)(ch - 1) * row_stride + (size_t)(cw - 1) * point_stride + 12 : 0, n = (size_t)count;
+  char *d_cloud = nullptr, *d_scr = nullptr; int* d_cnt = nullptr; pbd_box3d* d_box = nullptr; Cl3Res* h_res = nullptr;
+  int* d_pool = nullptr; unsigned long long* d_used = nullptr;
+  unsigned long long pool_cap = std::min<unsigned long long>((unsigned long long)count * (unsigned long long)npts, 4ull * (unsigned long long)pcap);
+  pool_cap = std::max<unsigned long long>(pool_cap, 1);
+  hipError_t e = hipSuccess;
+  auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+  if (bytes) chk(hipMalloc(&d_cloud, bytes));
+  chk(hipMalloc(&d_scr, cluster3d_slot_bytes(pcap) * slots)); chk(hipMalloc(&d_cnt, sizeof(int)));
+  chk(hipMalloc(&d_box, sizeof(pbd_box3d) * n)); chk(hipHostMalloc((void**)&h_res, sizeof(Cl3Res) * n));
+  chk(hipMalloc(&d_pool, sizeof(int) * pool_cap)); chk(hipMalloc(&d_used, sizeof(unsigned long long)));
+  if (bytes) chk(hipMemcpy(d_cloud, cloud, bytes, hipMemcpyHostToDevice));
+  chk(hipMemcpy(d_cnt, &count, sizeof(int), hipMemcpyHostToDevice));
+  chk(hipMemcpy(d_box, boxes, sizeof(pbd_box3d) * n, hipMemcpyHostToDevice));
+  chk(hipMemset(d_used, 0, sizeof(unsigned long long)));
+  Cluster3dArgs a{};
+  a.count = d_cnt; a.capacity = count; a.has = 1; a.boxes = d_box;
+  a.cloud = d_cloud; a.pstride = (size_t)point_stride; a.rstride = (size_t)row_stride; a.cw = cw; a.ch = ch; a.tol = tolerance;
+  a.scratch = d_scr; a.slot_bytes = cluster3d_slot_bytes(pcap); a.pcap = pcap;
+  a.out = h_res; a.pool = d_pool; a.pool_cap = pool_cap; a.pool_used = d_used;
+  if (e == hipSuccess) {
+    launch_cluster3d(a, 0, slots, h->stream);
+    chk(hipGetLastError());
+  }
+  chk(hipStreamSynchronize(h->stream));
+  int rc = PBD_OK;
+  std::vector<pbd_cluster3d> res;
+  std::vector<int32_t> idx;
+  if (e == hipSuccess) {
+    std::vector<int> lst(2 * n);
+    for (size_t i = 0; i < n; ++i) { lst[2 * i] = (int)i; lst[2 * i + 1] = 0; }
+    rc = cl3_resolve(h, a, 0, slots, d_pool, pool_cap, false, lst, res, idx);
+  }
+  hipFree(d_cloud); hipFree(d_scr); hipFree(d_cnt); hipFree(d_box); hipHostFree(h_res); hipFree(d_pool); hipFree(d_used);
+  if (e != hipSuccess) return fail(h, PBD_ERR_HIP, std::string("cluster3d: ") + hipGetErrorString(e));
+  if (rc) return rc;
+  std::copy(res.begin(), res.end(), out);
+  return cl3_copy_out(h, idx, indices, idx_capacity, idx_total);
 }
 
 // ---- instrumentation ---------------------------------------------------------

@@ -34,6 +34,24 @@
 
 struct CandRec { int level, comp, y, x; };
 
+// object clusters (k_cluster3d.hip): one record's result in the slot of its record
+struct Cl3Res { pbd_cluster3d r; long long off; };   // off: the kept cluster's indices in the pool; -1: they did not fit
+
+struct Cluster3dArgs {
+  const char* recs; size_t stride;            // records (frame mapping as Box3dArgs) and their device count
+  const int* count; int capacity;
+  const int* cf; int nframes; int nlevels;
+  unsigned long long has;
+  const int* list; int nlist;                 // non-null: only these (record, frame) pairs
+  const pbd_box3d* boxes;                     // [capacity] by record
+  const char* cloud; size_t pstride, rstride, fbytes; int cw, ch;   // frame f's cloud at cloud + f * fbytes
+  pbd_camera cam;                             // depth source: the pinhole model (pstride unused)
+  float tol;
+  char* scratch; size_t slot_bytes; int pcap; // one slot of pcap points per workgroup
+  Cl3Res* out;                                // [capacity]
+  int* pool; unsigned long long pool_cap; unsigned long long* pool_used;
+};
+
 struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated description, part topology, filter-bank mode)
   std::vector<char> level_set;   // pbd_set_levels: levels this handle processes (empty = all), intersected with [level_begin, level_end)
   std::string err;
@@ -161,6 +179,17 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   float* d_b3_taps = nullptr;
   bool b3_ready = false;            // results of the last collected frame, per frame in the order returned
   std::vector<std::vector<pbd_box3d>> b3_res; std::vector<std::vector<double>> b3_cen; std::vector<char> b3_res_on;
+  // object clusters (pbd_set_cluster3d): k_cluster3d.hip right behind k_box3d.  Results per record slot (pinned); the kept
+  // clusters' indices in a device pool claimed per record, gathered (and overflowing records run again) by the collect.
+  bool cl3_on = false; float cl3_tol = 0.01f;
+  bool cl3_frame = false;           // the pending frame computes clusters (the frames of b3_has)
+  Cl3Res* h_cl3 = nullptr;           // [capacity]: pinned
+  char* d_cl3_scratch = nullptr; size_t cl3_scratch_bytes = 0; int cl3_slots = 0, cl3_pcap = 0;
+  int* d_cl3_pool = nullptr; unsigned long long cl3_pool_cap = 0; unsigned long long* d_cl3_used = nullptr;
+  Cluster3dArgs cl3_args{};         // the pending frame's launch (the collect runs overflowing records again with it)
+  bool cl3_ready = false;           // results of the last collected frame, per frame in the order returned
+  std::vector<std::vector<int>> cl3_slot;   // [frame] the record slots in the order returned
+  std::vector<std::vector<pbd_cluster3d>> cl3_res; std::vector<std::vector<int32_t>> cl3_idx; std::vector<char> cl3_res_on;
 };
 #define PBD_MAX_BATCH 64
 
@@ -313,3 +342,7 @@ struct Box3dArgs {
   pbd_box3d* out; double* centres;            // [capacity], [capacity * mp * 3] (centres may be null)
 };
 void launch_box3d(const Box3dArgs& a, int ts, hipStream_t s);
+// object clusters (k_cluster3d.hip)
+size_t cluster3d_slot_bytes(int pcap);
+// src: 0 = xyz floats (pstride, rstride bytes), 4 / 8 = a depth image of float / double
+void launch_cluster3d(const Cluster3dArgs& a, int src, int nblocks, hipStream_t s);

@@ -40,6 +40,8 @@ class Candidate:
     locs: Optional[np.ndarray] = None  # [nparts, 3] (x, y, mixture) in cells of `level`
     box3d: Optional[np.ndarray] = None          # setBoundingBoxes3D: this record's pbd_box3d (capi.BOX3D_DTYPE)
     part_centers: Optional[np.ndarray] = None   # setBoundingBoxes3D: [nparts, 3] (empty when the box was skipped)
+    centre3d: Optional[np.ndarray] = None       # setObjectClusters: the kept cluster's centroid (3 doubles, NaN when none)
+    cluster: Optional[np.ndarray] = None        # setObjectClusters: its point indices (row * w + col), ascending, int32
 
     def score(self) -> float:
         return float(self.confidence[0]) if len(self.confidence) else float("-inf")
@@ -227,6 +229,7 @@ class PartsBasedDetector:
         self._cand_filter = cand_filter
         self._zfactor: Optional[float] = None   # setDepthFilter: None = off
         self._camera = None                      # setBoundingBoxes3D: None = off
+        self._cluster_tol: Optional[float] = None   # setObjectClusters: None = off
         self._dtype = np.dtype(dtype)
         self._lb, self._le = level_begin, level_end
         self._h: Optional[capi.Handle] = None
@@ -249,6 +252,8 @@ class PartsBasedDetector:
             self._h.set_depth_filter(True, self._zfactor)
         if self._camera is not None:
             self._h.set_box3d(True, self._camera)
+        if self._cluster_tol is not None:
+            self._h.set_cluster3d(True, self._cluster_tol)
 
     def setBoundingBoxes3D(self, camera=None) -> None:
         """camera = (fx, fy, cx, cy[, tx, ty]) or a capi.pbd_camera: every detect(im, depth) with a non-empty depth image attaches
@@ -259,6 +264,27 @@ class PartsBasedDetector:
         if self._h is not None:
             self._h.set_box3d(cam is not None, cam)
         self._camera = cam
+
+    def setObjectClusters(self, tolerance: Optional[float] = 0.01) -> None:
+        """With setBoundingBoxes3D on, every detect(im, depth) with a non-empty depth image also attaches to each returned Candidate
+        the object PointCloudClusterer::clusterObjects keeps for its box: `centre3d` (the largest Euclidean cluster's centroid,
+        NaN when none) and `cluster` (its point indices in the frame's cloud), computed on the GPU from the depth image through
+        the camera (pbd_c.h states the cloud rule).  None turns it off (the default).  Kept across distributeModel()."""
+        if self._h is not None:
+            self._h.set_cluster3d(tolerance is not None, 0.01 if tolerance is None else tolerance)
+        self._cluster_tol = tolerance
+
+    def cluster_objects(self, cloud, boxes3d, tolerance=0.01):
+        """PointCloudClusterer::clusterObjects (include/PointCloudClusterer.hpp:156-290) through pbd_candidates_cluster3d: cloud an
+        organized [h, w, 3] float32 cloud, boxes3d the records' pbd_box3d (capi.BOX3D_DTYPE, e.g. Candidate.box3d, or what
+        get_box3d returns) -> (clusters, centres): per record its kept cluster's point indices (row * w + col, ascending; empty
+        when none) and its centroid (3 doubles, NaN when none)."""
+        b = np.ascontiguousarray(np.asarray(boxes3d).reshape(-1), capi.BOX3D_DTYPE)
+        res, idx = self.handle.candidates_cluster3d(cloud, b, tolerance)
+        starts = np.concatenate([[0], np.cumsum(res["size"], dtype=np.int64)])
+        clusters = [idx[starts[i]:starts[i + 1]].copy() for i in range(len(res))]
+        centres = [np.array([r["cx"], r["cy"], r["cz"]], np.float64) for r in res]
+        return clusters, centres
 
     def computeBoundingBoxes(self, im_shape, depth, candidates: List[Candidate], camera):
         """PointCloudClusterer::computeBoundingBoxes (include/PointCloudClusterer.hpp:53-150) without its point cloud: per candidate
@@ -313,6 +339,12 @@ class PartsBasedDetector:
                 for i, c in enumerate(got):
                     c.box3d = b3[i].copy()
                     c.part_centers = cen[i, :len(c.parts)].copy() if b3[i]["valid"] else np.zeros((0, 3))
+                if self._cluster_tol is not None:
+                    res, idx = self.handle.get_cluster3d(0)
+                    starts = np.concatenate([[0], np.cumsum(res["size"], dtype=np.int64)])
+                    for i, c in enumerate(got):
+                        c.centre3d = np.array([res[i]["cx"], res[i]["cy"], res[i]["cz"]], np.float64)
+                        c.cluster = idx[starts[i]:starts[i + 1]].copy()
             out.extend(got)
             return out
         # (the image's dtype is its depth: uint8 -> pbd_detect_u8, the other accepted depths -> pbd_detect_image; unsupported ones raise)
