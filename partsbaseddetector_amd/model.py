@@ -280,6 +280,48 @@ def make_tree_model(parents, K, seed=1234, kh=5, kw=5, sbin=4, interval=10, thre
                  18, flen, name)
 
 
+def make_tree_model_k(parents, Ks, seed=1234, kh=5, kw=5, sbin=4, interval=10, thresh=0.0, shared=(), quantised=False,
+                      name="tree-k") -> Model:
+    """One component, `len(parents)` parts, Ks[p] mixtures for part p (src/DynamicProgram.cpp:99-100 allows any count per part).
+
+    buildmodel.m layout with a count per part: the filters of part p back to back (filter sum(Ks[:p]) + k), one deformation
+    row per child mixture, and for child p with parent count L = Ks[parents[p]] an L x K bias block at `base`:
+    biasid[p][k] = base + k*L, so bias(k)[m] = biasw[base + k*L + m]; a single scalar root bias (= 0).
+    `shared` (True, or an iterable of parts): every mixture of such a part has one deformation row and one bias row, whose
+    entries are all equal — with equal responses its K weighted maps tie exactly.  `quantised`: biases are multiples of 1/4 and
+    deformations dyadic (1/32 or 1/16 quadratic, 0 or +-1/128 linear), so sums of them and of small-integer responses are exact."""
+    rng = np.random.default_rng(seed)
+    P = len(parents)
+    assert len(Ks) == P and parents[0] == -1 and all(0 <= parents[p] < p for p in range(1, P)) and min(Ks) >= 1
+    flen = 32
+    shared = set(range(P)) if shared is True else set(shared)
+    f0 = np.concatenate([[0], np.cumsum(Ks)]).astype(int)
+    filt = _filters(rng, int(f0[-1]), kh, kw, flen)
+    filterid = [[[int(f0[p]) + k for k in range(Ks[p])] for p in range(P)]]
+    defid, biasid, rows = [[[]]], [[[0]]], 0
+    biasw = [0.0]
+    for p in range(1, P):
+        K, L = Ks[p], Ks[parents[p]]
+        nd = 1 if p in shared else K
+        defid[0].append([rows + (0 if p in shared else k) for k in range(K)])
+        rows += nd
+        base = len(biasw)
+        if p in shared:
+            v = float(rng.integers(-4, 5)) * 0.25 if quantised else float(rng.normal(0.0, 0.1))
+            biasw += [v] * L
+            biasid[0].append([base] * K)
+        else:
+            vals = rng.integers(-4, 5, K * L) * 0.25 if quantised else rng.normal(0.0, 0.1, K * L)
+            biasw += [float(x) for x in vals]
+            biasid[0].append([base + k * L for k in range(K)])
+    defw, anchors = _defs(rng, rows)
+    if quantised:
+        defw = np.stack([rng.choice([1 / 32, 1 / 16], rows), rng.choice([-1 / 128, 0.0, 1 / 128], rows),
+                         rng.choice([1 / 32, 1 / 16], rows), rng.choice([-1 / 128, 0.0, 1 / 128], rows)], axis=1).astype(np.float32)
+    return Model(filt, np.asarray(biasw, np.float32), anchors, defw.reshape(-1, 4), filterid, biasid, defid, [list(parents)],
+                 interval, thresh, sbin, 18, flen, name)
+
+
 def make_person_model(seed=1234, K=6, thresh=0.0, interval=10, sbin=4) -> Model:
     """26 parts x K mixtures: 156 filters / 150 deformations / 901 biases for K=6."""
     return make_tree_model(PERSON_TREE, K, seed=seed, thresh=thresh, interval=interval, sbin=sbin,

@@ -132,3 +132,24 @@ def divergence_margin(model, comp, maps, locs_ref, locs_got):
         obj = tmp - w[2] * dy * dy - w[3] * dy
         return p, "y", abs(float(obj[yo] - obj[yg])), sub
     return None
+
+
+def pointer_planes(model, comp, maps):
+    """Ix, Iy, Ik [planes, H, W] in the oracle's plane order (plane of (p, m) = sum of the parents' mixture counts of the parts
+    1 .. p-1, plus m) from level_maps' intermediates: Ik is the FIRST maximum over the child's K weighted maps for parent
+    mixture m (Math::reduceMax: strict >; K == 1: 0), Ix / Iy the chosen mixture's DT pointers (reducePickIndex)."""
+    fid, bid, par = model.filterid[comp], model.biasid[comp], model.parentid[comp]
+    T = maps["rootv"].dtype.type
+    Ix, Iy, Ik = [], [], []
+    for p in range(1, model.nparts(comp)):
+        K = len(fid[p])
+        ix, iy = np.stack(maps["ix"][p]), np.stack(maps["iy"][p])
+        for m in range(len(fid[par[p]])):
+            wv = np.stack([(maps["sdt"][p][mm] + T(model.biasw[bid[p][mm] + m])).astype(T) for mm in range(K)])
+            k = np.zeros(wv.shape[1:], np.int32) if K == 1 else np.argmax(wv, axis=0).astype(np.int32)
+            Ik.append(k)
+            Ix.append(np.take_along_axis(ix, k[None], 0)[0]); Iy.append(np.take_along_axis(iy, k[None], 0)[0])
+    H, W = maps["rootv"].shape
+    if not Ik:
+        return (np.zeros((0, H, W), np.int32),) * 3
+    return np.stack(Ix), np.stack(Iy), np.stack(Ik)

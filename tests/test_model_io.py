@@ -88,3 +88,29 @@ def test_filestorage_reader_literal_defid(tmp_path):
                 assert set(lit.defid[0][p]) == {0} and any(v != 0 for v in m.defid[0][p]) or p == 1 and list(m.defid[0][p])[0] == 0, (ext, p, lit.defid[0][p])
             else:
                 assert list(lit.defid[0][p]) == list(m.defid[0][p]), (ext, p, lit.defid[0][p])
+
+
+@pytest.mark.parametrize("ext", [".xml", ".yaml"])
+def test_roundtrip_mixture_count_per_part(tmp_path, ext):
+    """A model whose parts have 1 to 8 mixtures (one L x K bias block per child, a part with one shared deformation and bias row):
+    the binary dump, and the reference's FileStorage layout through the C++ reader and writer, keep every per-part index list."""
+    from partsbaseddetector_amd.model import make_tree_model_k
+    assert os.path.exists(CONV), "build() did not produce pbd_modelconv"
+    m = make_tree_model_k([-1, 0, 0, 1, 1, 2], [1, 3, 6, 1, 8, 2], seed=8, shared=[5], thresh=-0.5)
+    m.name = "Synthetic"
+    m.save(str(tmp_path / "m.bin"))
+    back = Model.load(str(tmp_path / "m.bin"))
+    _same(m, back)
+    assert back.biasid == m.biasid and back.defid == m.defid
+    src = tmp_path / ("model" + ext)
+    m.save_filestorage(str(src))
+    _conv(src, tmp_path / "a.bin")
+    a = Model.load(str(tmp_path / "a.bin"))
+    _same(m, a)
+    assert a.biasid == m.biasid and [len(f) for f in a.filterid[0]] == [1, 3, 6, 1, 8, 2]
+    for ext2 in (".xml", ".yml"):
+        _conv(tmp_path / "a.bin", tmp_path / ("b" + ext2))
+        _conv(tmp_path / ("b" + ext2), tmp_path / "c.bin")
+        c = Model.load(str(tmp_path / "c.bin"))
+        _same(m, c)
+        assert c.biasid == m.biasid and c.defid[0][1:] == m.defid[0][1:]

@@ -85,3 +85,19 @@ def test_plan_errors(planner):
     assert plan(planner, PERSON, w=40, h=30)[0] == capi.PBD_ERR_ARG
     rc, _, rep = plan(planner, PERSON, w=140000, h=48)
     assert rc == capi.PBD_ERR_UNSUPPORTED and "16-bit pointers" in rep, rep
+
+
+@pytest.mark.parametrize("name,kw", [("foldmix7", dict()), ("siblings_1_to_8", dict(f64=True)), ("root1_children_many", dict(batch=4)),
+                                     ("L6_child_K1", dict(nms_sz=2)), ("foldmix5", dict(dp_mode=1)), ("k10_among_small", dict()),
+                                     ("two_profiles", dict())])
+def test_plan_invariants_mixture_count_per_part(planner, name, kw):
+    """Parts with different mixture counts (tests/mixture_models.py): the tables pass every check; the fold takes them up to 8
+    mixtures a part (fold_mix = the largest count), a part of 10 mixtures or dp_mode 1 takes the three-kernel structure.
+    (No footprint pin: none of these was measured on an MI355X.)"""
+    from tests.mixture_models import het_model, two_profiles
+    model = two_profiles() if name == "two_profiles" else het_model(name)
+    rc, fb, rep = plan(planner, model, **kw)
+    assert rc == capi.PBD_OK, rep
+    assert fb > 0 and not rep.startswith("compact"), rep
+    legacy = name == "k10_among_small" or kw.get("dp_mode") == 1
+    assert (re.search(r" 0 reduce jobs", rep) is None) == legacy and (re.search(r" 0 folds", rep) is not None) == legacy, rep
