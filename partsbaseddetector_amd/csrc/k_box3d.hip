@@ -76,7 +76,7 @@ __device__ __forceinline__ void b3_pixels(const Box3dArgs& a, const char* img, c
     const unsigned dy = B3_NT / bw, dx = B3_NT - dy * bw;
     unsigned yy = threadIdx.x / bw, xx = threadIdx.x - yy * bw;
     for (unsigned q = threadIdx.x; q < n; q += B3_NT) {
-      f(b, b3_px<T>(img, a.zpitch, r.x + (int)xx, r.y + (int)yy));
+      f(b, b3_px<T>(img, a.z.pitch, r.x + (int)xx, r.y + (int)yy));
       yy += dy; xx += dx;
       if (xx >= bw) { xx -= bw; ++yy; }
     }
@@ -100,25 +100,17 @@ __global__ void __launch_bounds__(B3_NT) k_box3d(Box3dArgs a) {
   __shared__ int s_bb[4];
 
   const int tid = threadIdx.x;
-  int total = *a.count;
-  if (total > a.capacity) return;                  // overflowed frame: it fails with PBD_ERR_CAPACITY
+  int total = *a.in.count;
+  if (total > a.in.capacity) return;                  // overflowed frame: it fails with PBD_ERR_CAPACITY
   for (int i = blockIdx.x; i < total; i += gridDim.x) {
-    const pbd_candidate_head* hd = (const pbd_candidate_head*)(a.recs + a.stride * (size_t)i);
-    int f = 0;
-    if (a.cf) {   // filtered output: frame f's records sit at [start_f, start_f + kept_f)
-      f = -1;
-      for (int k = 0; k < a.nframes; ++k)
-        if (i >= a.cf[2 + a.nframes + k] && i < a.cf[2 + a.nframes + k] + a.cf[2 + k]) { f = k; break; }
-      if (f < 0) continue;
-    } else if (a.nlevels) {
-      f = hd->level / a.nlevels;
-    }
-    if (!((a.has >> f) & 1ull)) continue;
+    const pbd_candidate_head* hd = (const pbd_candidate_head*)(a.in.p + a.in.stride * (size_t)i);
+    const int f = record_frame(a.in, i);
+    if (f < 0 || !((a.z.has >> f) & 1ull)) continue;
     const int np = hd->nparts;
     const int* pb = (const int*)(hd + 1);
     pbd_box3d* out = a.out + i;
-    double* cen = a.centres ? a.centres + (size_t)i * a.mp * 3 : nullptr;
-    if (cen) for (int k = tid; k < a.mp * 3; k += B3_NT) cen[k] = 0.0;
+    double* cen = a.centres ? a.centres + (size_t)i * a.in.mp * 3 : nullptr;
+    if (cen) for (int k = tid; k < a.in.mp * 3; k += B3_NT) cen[k] = 0.0;
     // ---- boxes (thread 0): bb, bbn, scaled ROIs
     if (tid == 0) {
       int x0 = pb[0], y0 = pb[1], x1 = pb[0] + pb[2], y1 = pb[1] + pb[3];
@@ -134,7 +126,7 @@ __global__ void __launch_bounds__(B3_NT) k_box3d(Box3dArgs a) {
       const double mx = sx * sc, my = sy * sc;
       const double dx = sqrt(fmax(qx * sc - mx * mx, 0.)), dy = sqrt(fmax(qy * sc - my * my, 0.));
       const int nx = (int)(mx - 1.5 * dx), ny = (int)(my - 1.5 * dy), nw = (int)(3 * dx), nh = (int)(3 * dy);
-      const double scx = (double)a.zw / (double)a.im_w, scy = (double)a.zh / (double)a.im_h;
+      const double scx = (double)a.z.w / (double)a.im_w, scy = (double)a.z.h / (double)a.im_h;
       s_first = -1;
       for (int p = 0; p <= np; ++p) {
         int rx, ry, rw, rh;
@@ -147,8 +139,8 @@ __global__ void __launch_bounds__(B3_NT) k_box3d(Box3dArgs a) {
         if (cw <= 0 || ch <= 0) o = B3Box{0, 0, 0, 0};
         o.x = (int)(o.x * scx); o.y = (int)(o.y * scy); o.w = (int)(o.w * scx); o.h = (int)(o.h * scy);
         // (inside the depth image by construction; clipped again so that no rounding can read outside it)
-        const int ex = min(o.x + o.w, a.zw), ey = min(o.y + o.h, a.zh);
-        o.x = min(max(o.x, 0), a.zw); o.y = min(max(o.y, 0), a.zh);
+        const int ex = min(o.x + o.w, a.z.w), ey = min(o.y + o.h, a.z.h);
+        o.x = min(max(o.x, 0), a.z.w); o.y = min(max(o.y, 0), a.z.h);
         o.w = ex - o.x; o.h = ey - o.y;
         if (o.w <= 0 || o.h <= 0) o = B3Box{0, 0, 0, 0};
         else if (s_first < 0) s_first = p;
@@ -158,7 +150,7 @@ __global__ void __launch_bounds__(B3_NT) k_box3d(Box3dArgs a) {
     }
     for (int k = tid; k < B3_BINS; k += B3_NT) hist[k] = 0;
     __syncthreads();
-    const char* img = a.zimg + a.zfbytes * (size_t)f;
+    const char* img = a.z.img + a.z.fbytes * (size_t)f;
     // ---- pass 0: the top B3_DIG0 key bits of every valid pixel; the first non-empty box's valid count
     {
       unsigned firstc = 0;
@@ -347,7 +339,7 @@ __global__ void __launch_bounds__(B3_NT) k_box3d(Box3dArgs a) {
         const unsigned n = (unsigned)w * (unsigned)h;
         for (unsigned q = tid; q < n; q += B3_NT) {
           const int row = x + (int)(q / (unsigned)w), col = y + (int)(q % (unsigned)w);
-          if (row < a.zh && col < a.zw) s += (double)b3_px<T>(img, a.zpitch, col, row);
+          if (row < a.z.h && col < a.z.w) s += (double)b3_px<T>(img, a.z.pitch, col, row);
         }
         s = b3_dsum(s, dws);
         if (tid == 0) {
@@ -366,8 +358,8 @@ __global__ void __launch_bounds__(B3_NT) k_box3d(Box3dArgs a) {
 }
 
 void launch_box3d(const Box3dArgs& a, int ts, hipStream_t s) {
-  const int nb = a.capacity < B3_BLOCKS ? (a.capacity > 0 ? a.capacity : 1) : B3_BLOCKS;
-  const size_t lds = sizeof(B3Box) * (size_t)(a.mp + 1);
+  const int nb = a.in.capacity < B3_BLOCKS ? (a.in.capacity > 0 ? a.in.capacity : 1) : B3_BLOCKS;
+  const size_t lds = sizeof(B3Box) * (size_t)(a.in.mp + 1);
   if (ts == 8) hipLaunchKernelGGL(k_box3d<double>, dim3(nb), dim3(B3_NT), lds, s, a);
   else hipLaunchKernelGGL(k_box3d<float>, dim3(nb), dim3(B3_NT), lds, s, a);
 }

@@ -84,8 +84,8 @@ __global__ __launch_bounds__(CF_NT) void k_cand_filter(CandFilterArgs a) {
   __shared__ long long s_ws[CF_NT / 64];
   __shared__ int s_ctr, s_next, s_stop, s_nk;
   const int tid = threadIdx.x, lane = tid & 63, f = blockIdx.x, nf = gridDim.x;
-  const int raw = *a.in_count;
-  if (raw > a.capacity) {   // a truncated list cannot be suppressed exactly: the host reports PBD_ERR_CAPACITY with the count
+  const int raw = *a.in.count;
+  if (raw > a.in.capacity) {   // a truncated list cannot be suppressed exactly: the host reports PBD_ERR_CAPACITY with the count
     if (tid == 0) {
       if (f == 0) { a.cnt_out[0] = raw; a.cnt_out[1] = raw; }
       a.cnt_out[2 + f] = 0; a.cnt_out[2 + nf + f] = 0;
@@ -93,10 +93,10 @@ __global__ __launch_bounds__(CF_NT) void k_cand_filter(CandFilterArgs a) {
     return;
   }
   const int n = raw;
-  const size_t stride = a.stride;
-  const int loc_off = 16 + a.mp * 16;   // locs[0] = root (x, y, mixture)
+  const size_t stride = a.in.stride;
+  const int loc_off = 16 + a.in.mp * 16;   // locs[0] = root (x, y, mixture)
   auto frame_of = [&](int i) -> int {
-    return a.nlevels ? ((const pbd_candidate_head*)(a.in + stride * i))->level / a.nlevels : 0;
+    return a.in.nlevels ? ((const pbd_candidate_head*)(a.in.p + stride * i))->level / a.in.nlevels : 0;
   };
   // ---- this frame's records: how many, and how many of the frames in front of it
   int before = 0, mine = 0;
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(CF_NT) void k_cand_filter(CandFilterArgs a) {
   // ---- keys
   for (int i = tid; i < n; i += CF_NT) {
     if (frame_of(i) != f) continue;
-    const char* r = a.in + stride * i;
+    const char* r = a.in.p + stride * i;
     const pbd_candidate_head* hd = (const pbd_candidate_head*)r;
     unsigned lo = (unsigned)i;
     if (a.back) {
@@ -165,7 +165,7 @@ __global__ __launch_bounds__(CF_NT) void k_cand_filter(CandFilterArgs a) {
   const bool trivial = !(ov >= 0.0 && ov < 1.0);   // >= 1: nothing is rejected (painted <= area); < 0: every non-empty box is
   for (int p = tid; p < m; p += CF_NT) {
     if (!nms) { st[p] = 1; continue; }
-    const char* r = a.in + stride * ord[p];
+    const char* r = a.in.p + stride * ord[p];
     const int* b = (const int*)(r + 16);
     const int np = ((const pbd_candidate_head*)r)->nparts;
     int x = b[0], y = b[1], bw = b[2], bh = b[3];
@@ -263,7 +263,7 @@ __global__ __launch_bounds__(CF_NT) void k_cand_filter(CandFilterArgs a) {
   }
   // ---- the kept records, in final order
   const int spw = (int)(stride / 4);
-  const int* src = (const int*)a.in;
+  const int* src = (const int*)a.in.p;
   int* dst = (int*)(a.out + stride * start);
   for (long long w = tid; w < (long long)kept * spw; w += CF_NT) {
     const int j = (int)(w / spw), k = (int)(w - (long long)j * spw);

@@ -82,12 +82,12 @@ __device__ __forceinline__ float cl_fmin(float v, float* ws) {
 // point `q` (row-major over cw x ch) of frame f: the caller's cloud (SRC 0) or the depth image of element type T (SRC 1)
 template <int SRC, typename T>
 __device__ __forceinline__ void cl_point(const Cluster3dArgs& a, const char* base, int q, float& x, float& y, float& z) {
-  const int v = q / a.cw, u = q - v * a.cw;
+  const int v = q / a.z.w, u = q - v * a.z.w;
   if (SRC == 0) {
-    const float* p = (const float*)(base + (size_t)v * a.rstride + (size_t)u * a.pstride);
+    const float* p = (const float*)(base + (size_t)v * a.z.pitch + (size_t)u * a.pstride);
     x = p[0]; y = p[1]; z = p[2];
   } else {
-    const float d = (float)*(const T*)(base + (size_t)v * a.rstride + (size_t)u * sizeof(T));   // 64F rounds to float first
+    const float d = (float)*(const T*)(base + (size_t)v * a.z.pitch + (size_t)u * sizeof(T));   // 64F rounds to float first
     if (d == 0.f || !isfinite(d)) { x = y = z = __int_as_float(0x7fc00000); return; }
     const double dd = (double)d;
     x = (float)(((u - a.cam.cx - a.cam.tx) / a.cam.fx) * dd);
@@ -112,8 +112,8 @@ __global__ void __launch_bounds__(CL_NT) k_cluster3d(Cluster3dArgs a) {
   __shared__ int s_ncl;
 
   const int tid = threadIdx.x;
-  const int total = a.list ? a.nlist : *a.count;
-  if (!a.list && total > a.capacity) return;   // overflowed frame: it fails with PBD_ERR_CAPACITY
+  const int total = a.list ? a.nlist : *a.in.count;
+  if (!a.list && total > a.in.capacity) return;   // overflowed frame: it fails with PBD_ERR_CAPACITY
   char* slot = a.scratch + a.slot_bytes * blockIdx.x;
   int* idx = (int*)slot;                              // [pcap] point index of each kept point, ascending
   float* px = (float*)(idx + a.pcap);                 // [pcap] x, y, z
@@ -122,19 +122,12 @@ __global__ void __launch_bounds__(CL_NT) k_cluster3d(Cluster3dArgs a) {
   int* par = (int*)(pz + a.pcap);                     // [pcap] union-find parent
   int* nxt = par + a.pcap;                            // [pcap] chain of the hash table, then the size of each root
   int* head = nxt + a.pcap;                           // [1 << tlog_max]
-  const int npts = a.cw * a.ch;
+  const int npts = a.z.w * a.z.h;
   for (int j = blockIdx.x; j < total; j += gridDim.x) {
-    int i = j, f = 0;
+    int i = j, f;
     if (a.list) { i = a.list[2 * j]; f = a.list[2 * j + 1]; }
-    else if (a.cf) {   // filtered output: frame f's records sit at [start_f, start_f + kept_f)
-      f = -1;
-      for (int k = 0; k < a.nframes; ++k)
-        if (i >= a.cf[2 + a.nframes + k] && i < a.cf[2 + a.nframes + k] + a.cf[2 + k]) { f = k; break; }
-      if (f < 0) continue;
-    } else if (a.nlevels) {
-      f = ((const pbd_candidate_head*)(a.recs + a.stride * (size_t)i))->level / a.nlevels;
-    }
-    if (!((a.has >> f) & 1ull)) continue;
+    else f = record_frame(a.in, i);
+    if (f < 0 || !((a.z.has >> f) & 1ull)) continue;
     const pbd_box3d bx = a.boxes[i];
     Cl3Res res;
     res.r.cropped = 0; res.r.nclusters = 0; res.r.size = 0; res.r.first = -1;
@@ -149,7 +142,7 @@ __global__ void __launch_bounds__(CL_NT) k_cluster3d(Cluster3dArgs a) {
     const double ex = bx.x3d - bx.width3d * 0.1, ey = bx.y3d - bx.height3d * 0.1, ez = bx.z3d - bx.depth3d * 0.1;
     const double ew = bx.width3d * 1.2, eh = bx.height3d * 1.2, ed = bx.depth3d * 1.2;
     const float x0 = (float)ex, y0 = (float)ey, z0 = (float)ez, x1 = (float)(ex + ew), y1 = (float)(ey + eh), z1 = (float)(ez + ed);
-    const char* base = a.cloud + a.fbytes * (size_t)f;
+    const char* base = a.z.img + a.z.fbytes * (size_t)f;
     // ---- 1. crop, compacted in point order
     int n = 0;
     float mnx = INFINITY, mny = INFINITY, mnz = INFINITY, mxx = -INFINITY, mxy = -INFINITY, mxz = -INFINITY;

@@ -121,16 +121,16 @@ __device__ typename ZKey<T>::K zselect(const char* img, size_t pitch, int x0, in
 }
 
 __device__ __forceinline__ const pbd_candidate_head* zrec(const ZFilterArgs& a, unsigned i) {
-  return (const pbd_candidate_head*)(a.in + a.stride * i);
+  return (const pbd_candidate_head*)(a.in.p + a.in.stride * i);
 }
-__device__ __forceinline__ int zframe(const ZFilterArgs& a, const pbd_candidate_head* hd) { return a.nlevels ? hd->level / a.nlevels : 0; }
+__device__ __forceinline__ int zframe(const ZFilterArgs& a, const pbd_candidate_head* hd) { return a.in.nlevels ? hd->level / a.in.nlevels : 0; }
 
 // box p of record i clipped to the depth image: false when there is nothing to select in
 __device__ __forceinline__ bool zbox(const ZFilterArgs& a, const pbd_candidate_head* hd, int p, int* x0, int* y0, unsigned* bw, unsigned* n) {
   const int* b = (const int*)(hd + 1) + p * 4;
   const long long bx = b[0], by = b[1], ex = bx + b[2], ey = by + b[3];
   const long long cx0 = bx > 0 ? bx : 0, cy0 = by > 0 ? by : 0;
-  const long long cx1 = ex < a.zw ? ex : a.zw, cy1 = ey < a.zh ? ey : a.zh;
+  const long long cx1 = ex < a.z.w ? ex : a.z.w, cy1 = ey < a.z.h ? ey : a.z.h;
   if (b[2] <= 0 || b[3] <= 0 || cx1 <= cx0 || cy1 <= cy0) return false;
   *x0 = (int)cx0; *y0 = (int)cy0; *bw = (unsigned)(cx1 - cx0);
   *n = (unsigned)((cx1 - cx0) * (cy1 - cy0));
@@ -142,15 +142,15 @@ __global__ void __launch_bounds__(ZF_SMALL_NT) k_zmed_small(ZFilterArgs a) {
   typedef typename ZKey<T>::K K;
   __shared__ unsigned hist[1 << ZF_DIG_SMALL];
   __shared__ unsigned res[2];
-  const int cnt = *a.in_count;
-  if (cnt > a.capacity) return;
-  const unsigned items = (unsigned)cnt * (unsigned)a.mp;
+  const int cnt = *a.in.count;
+  if (cnt > a.in.capacity) return;
+  const unsigned items = (unsigned)cnt * (unsigned)a.in.mp;
   for (unsigned it = blockIdx.x; it < items; it += gridDim.x) {
-    const unsigned i = it / a.mp;
-    const int p = (int)(it - i * a.mp);
+    const unsigned i = it / a.in.mp;
+    const int p = (int)(it - i * a.in.mp);
     const pbd_candidate_head* hd = zrec(a, i);
     const int np = a.npart[hd->component], f = zframe(a, hd);
-    if (np < 2 || p >= np || !((a.has >> f) & 1ull)) continue;
+    if (np < 2 || p >= np || !((a.z.has >> f) & 1ull)) continue;
     int x0 = 0, y0 = 0;
     unsigned bw = 0, n = 0;
     if (!zbox(a, hd, p, &x0, &y0, &bw, &n)) {
@@ -161,7 +161,7 @@ __global__ void __launch_bounds__(ZF_SMALL_NT) k_zmed_small(ZFilterArgs a) {
       if (threadIdx.x == 0) a.large[atomicAdd(a.nlarge, 1u)] = it;
       continue;
     }
-    const K k = zselect<T, ZF_SMALL_NT, ZF_DIG_SMALL>(a.zimg + a.zfbytes * f, a.zpitch, x0, y0, bw, n, hist, nullptr, res);
+    const K k = zselect<T, ZF_SMALL_NT, ZF_DIG_SMALL>(a.z.img + a.z.fbytes * f, a.z.pitch, x0, y0, bw, n, hist, nullptr, res);
     if (threadIdx.x == 0) a.med[it] = k;
   }
 }
@@ -175,21 +175,21 @@ __global__ void __launch_bounds__(ZF_LARGE_NT) k_zmed_large(ZFilterArgs a) {
   const unsigned nl = *a.nlarge;
   for (unsigned j = blockIdx.x; j < nl; j += gridDim.x) {
     const unsigned it = a.large[j];
-    const unsigned i = it / a.mp;
-    const int p = (int)(it - i * a.mp);
+    const unsigned i = it / a.in.mp;
+    const int p = (int)(it - i * a.in.mp);
     const pbd_candidate_head* hd = zrec(a, i);
     int x0 = 0, y0 = 0;
     unsigned bw = 0, n = 0;
     zbox(a, hd, p, &x0, &y0, &bw, &n);   // non-empty: k_zmed_small listed it
-    const K k = zselect<T, ZF_LARGE_NT, ZF_DIG_LARGE>(a.zimg + a.zfbytes * zframe(a, hd), a.zpitch, x0, y0, bw, n, hist, ws, res);
+    const K k = zselect<T, ZF_LARGE_NT, ZF_DIG_LARGE>(a.z.img + a.z.fbytes * zframe(a, hd), a.z.pitch, x0, y0, bw, n, hist, ws, res);
     if (threadIdx.x == 0) a.med[it] = k;
   }
 }
 
 template <typename T>
 __global__ void __launch_bounds__(64) k_zkeep(ZFilterArgs a) {
-  const int cnt = *a.in_count;
-  if (cnt > a.capacity) {   // the back-tracking overflowed: pass the count on, the frame fails with PBD_ERR_CAPACITY
+  const int cnt = *a.in.count;
+  if (cnt > a.in.capacity) {   // the back-tracking overflowed: pass the count on, the frame fails with PBD_ERR_CAPACITY
     if (blockIdx.x == 0 && threadIdx.x == 0 && a.cnt) *a.cnt = cnt;
     return;
   }
@@ -198,15 +198,15 @@ __global__ void __launch_bounds__(64) k_zkeep(ZFilterArgs a) {
     const pbd_candidate_head* hd = zrec(a, (unsigned)i);
     const int c = hd->component, np = a.npart[c];
     bool keep = true;
-    if ((a.has >> zframe(a, hd)) & 1ull) {
+    if ((a.z.has >> zframe(a, hd)) & 1ull) {
       bool bad = false;
-      const size_t row = (size_t)i * a.mp;
+      const size_t row = (size_t)i * a.in.mp;
       for (int p = 1 + lane; p < np; p += 64) {
         const T mc = ZKey<T>::val(a.med[row + p]);
-        const T mq = ZKey<T>::val(a.med[row + a.par[c * a.mp + p]]);
+        const T mq = ZKey<T>::val(a.med[row + a.par[c * a.in.mp + p]]);
         T d = mc - mq;   // |mc - mp| in T, then promoted (src/SearchSpacePruning.cpp:87)
         d = d < (T)0 ? -d : d;
-        if (mc > (T)0 && mq > (T)0 && (double)d > a.thr[c * a.mp + p]) bad = true;
+        if (mc > (T)0 && mq > (T)0 && (double)d > a.thr[c * a.in.mp + p]) bad = true;
       }
       keep = np >= 2 && __ballot(bad) == 0ull;
     }
@@ -219,16 +219,16 @@ __global__ void __launch_bounds__(64) k_zkeep(ZFilterArgs a) {
     if (lane == 0) slot = (unsigned)atomicAdd(a.cnt, 1);
     slot = __shfl(slot, 0, 64);
     const unsigned* src = (const unsigned*)hd;
-    unsigned* dst = (unsigned*)(a.out + a.stride * slot);
-    for (size_t w = lane; w < a.stride / 4; w += 64) dst[w] = src[w];
+    unsigned* dst = (unsigned*)(a.out + a.in.stride * slot);
+    for (size_t w = lane; w < a.in.stride / 4; w += 64) dst[w] = src[w];
   }
 }
 
 // a.cnt (kept count) and a.nlarge must be zero on the stream in front of the launch (the caller's memset)
 void launch_zfilter(const ZFilterArgs& a, int ts, hipStream_t s) {
-  const int items = a.capacity * a.mp;
+  const int items = a.in.capacity * a.in.mp;
   const int sb = items < ZF_SMALL_BLOCKS ? (items > 0 ? items : 1) : ZF_SMALL_BLOCKS;
-  const int kb = a.capacity < ZF_KEEP_BLOCKS ? (a.capacity > 0 ? a.capacity : 1) : ZF_KEEP_BLOCKS;
+  const int kb = a.in.capacity < ZF_KEEP_BLOCKS ? (a.in.capacity > 0 ? a.in.capacity : 1) : ZF_KEEP_BLOCKS;
   if (ts == 8) {
     hipLaunchKernelGGL(k_zmed_small<double>, dim3(sb), dim3(ZF_SMALL_NT), 0, s, a);
     hipLaunchKernelGGL(k_zmed_large<double>, dim3(ZF_LARGE_BLOCKS), dim3(ZF_LARGE_NT), 0, s, a);

@@ -13,38 +13,6 @@
 #include <new>
 #include "pbd_internal.hpp"
 
-#define HIPCHK(h, call)                                                                  \
-  do {                                                                                   \
-    hipError_t e_ = (call);                                                              \
-    if (e_ != hipSuccess) {                                                              \
-      (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);                      \
-      return PBD_ERR_HIP;                                                                \
-    }                                                                                    \
-  } while (0)
-
-static int fail(pbd_handle* h, int code, const std::string& msg) {
-  if (h) h->err = msg;
-  return code;
-}
-
-// Kernel launches return nothing: a launch the runtime rejected (wrong current device, a dynamic-LDS request over
-// the opt-in, a bad grid) would otherwise leave the previous frame's buffers in place and detect() would return
-// stale candidates with PBD_OK.  Checked after every stage.
-#define LAUNCHCHK(h, what)                                                               \
-  do {                                                                                   \
-    hipError_t e_ = hipGetLastError();                                                   \
-    if (e_ != hipSuccess) {                                                              \
-      (h)->err = std::string(what) + ": kernel launch failed: " + hipGetErrorString(e_); \
-      return PBD_ERR_HIP;                                                                \
-    }                                                                                    \
-  } while (0)
-// hipGetLastError() is the calling THREAD's sticky last error: an unrelated HIP call of the caller that failed
-// earlier (or one of ours whose result was deliberately ignored) would be reported as this frame's launch failure.
-// Every entry point that launches clears it first, so LAUNCHCHK only ever sees the library's own launches.
-#define CLEAR_STICKY() ((void)hipGetLastError())
-// every ABI entry that launches or copies runs on the handle's device, whatever the caller's current device is
-#define ON_DEVICE(h) do { HIPCHK(h, hipSetDevice((h)->opt.device)); CLEAR_STICKY(); } while (0)
-
 // ---------------------------------------------------------------------------
 // model
 // ---------------------------------------------------------------------------
@@ -180,7 +148,7 @@ static int upload_model(pbd_handle* h) {
   HIPCHK(h, hipMemcpy(h->d_mix_rows, mix_rows.data(), mix_rows.size() * sizeof(int), hipMemcpyHostToDevice));
   // candidates
   const int cap = h->opt.max_candidates;
-  h->cand_stride = sizeof(pbd_candidate_head) + (size_t)mp * 28;
+  h->cand_stride = pbd_rec_bytes(mp);
   HIPCHK(h, hipMalloc(&h->d_cand_count, sizeof(int)));
   HIPCHK(h, hipMalloc(&h->d_cand_rec, sizeof(CandRec) * cap));
   HIPCHK(h, hipMalloc(&h->d_cand_out, h->cand_stride * cap));
@@ -196,16 +164,6 @@ static int upload_model(pbd_handle* h) {
 // ---------------------------------------------------------------------------
 static const int kFirstCopy = PBD_FIRST_COPY;  // records fetched together with the count (per frame of the plan; grows, pbd_i_finish_frame)
 template <typename T>
-static int dev_alloc(pbd_handle* h, T** p, size_t n) {
-  void* q = nullptr;
-  hipError_t e = hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T));
-  if (e != hipSuccess) { h->err = std::string("hipMalloc: ") + hipGetErrorString(e); return PBD_ERR_HIP; }
-  h->frame_allocs.push_back(q);
-  h->frame_bytes += std::max<size_t>(n, 1) * sizeof(T);
-  *p = (T*)q;
-  return PBD_OK;
-}
-template <typename T>
 static int dev_upload(pbd_handle* h, T** p, const std::vector<T>& v) {
   int rc = dev_alloc(h, p, v.size());
   if (rc) return rc;
@@ -214,7 +172,7 @@ static int dev_upload(pbd_handle* h, T** p, const std::vector<T>& v) {
 }
 
 static void free_frame(pbd_handle* h) {
-  if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }   // the captured launches point into the buffers freed below
+  drop_graph(h);   // the captured launches point into the buffers freed below
   h->frames_on_plan = 0;
   for (void* p : h->frame_allocs) hipFree(p);
   h->frame_allocs.clear();
@@ -470,253 +428,6 @@ static int run_dp_min(pbd_handle* h) {
   return PBD_OK;
 }
 
-static int cand_mode_now(const pbd_handle* h) { return h->cand_defer ? PBD_CAND_RAW : h->cand_mode; }
-static CandFilterArgs cand_args(pbd_handle* h, int mode, float overlap, int im_w, int im_h) {
-  CandFilterArgs a{};
-  a.capacity = h->opt.max_candidates; a.stride = h->cand_stride; a.mp = h->max_parts;
-  a.ts = h->ts; a.ncomp = h->md.ncomponents;
-  a.nms = mode == PBD_CAND_SORT_NMS; a.overlap = (double)overlap; a.im_w = im_w; a.im_h = im_h;
-  a.keys = h->d_cf_keys; a.idx = h->d_cf_idx; a.box = h->d_cf_box; a.st = h->d_cf_st;
-  return a;
-}
-// the filter's scratch: model-sized once (first use), the per-frame masks with the frame plan.  Called outside any capture;
-// a (re)allocation drops a captured graph (its launches point at the old buffers).
-static int cand_filter_buffers(pbd_handle* h, bool masks) {
-  const size_t cap = (size_t)h->opt.max_candidates;
-  if (!h->d_cf_keys) {
-    HIPCHK(h, hipMalloc(&h->d_cf_keys, sizeof(unsigned long long) * 2 * cap));
-    HIPCHK(h, hipMalloc(&h->d_cf_idx, sizeof(unsigned) * 2 * cap));
-    HIPCHK(h, hipMalloc(&h->d_cf_box, sizeof(int) * 4 * cap));
-    HIPCHK(h, hipMalloc(&h->d_cf_st, cap));
-    HIPCHK(h, hipMalloc(&h->d_cf_cnt, sizeof(int) * (2 + 2 * PBD_MAX_BATCH)));
-    HIPCHK(h, hipHostMalloc((void**)&h->h_cf_cnt, sizeof(int) * (2 + 2 * PBD_MAX_BATCH)));
-    HIPCHK(h, hipMalloc(&h->d_cand_raw, h->cand_stride * cap));
-    h->model_bytes += (sizeof(unsigned long long) * 2 + sizeof(unsigned) * 2 + sizeof(int) * 4 + 1) * cap + h->cand_stride * cap;
-    if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
-  }
-  if (masks && h->fw > 0) {
-    const size_t need = cand_filter_mask_bytes(h->fw, h->fh) * h->batch;
-    if (need > h->cf_mask_bytes) {
-      int rc = dev_alloc(h, &h->d_cf_mask, need / sizeof(unsigned long long));
-      if (rc) return rc;
-      h->cf_mask_bytes = need;
-      if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
-    }
-  }
-  return PBD_OK;
-}
-
-// ---- depth-consistency pruning (k_zfilter.hip) ----------------------------------------------------------------------
-// per (component, part): parentid and norm(anchor(0)) * zfactor, the reference's double expression (src/SearchSpacePruning.cpp:82-88):
-// anchor(0) = anchors[defid[first mixture of the part]] (include/Parts.hpp:183), whatever mixture the candidate chose
-static void zf_table(const pbd_handle* h, float zfactor, std::vector<int>& npart, std::vector<int>& par, std::vector<double>& thr) {
-  const int nc = h->md.ncomponents, mp = h->max_parts;
-  npart.assign((size_t)nc, 0); par.assign((size_t)nc * mp, 0); thr.assign((size_t)nc * mp, 0.0);
-  for (int c = 0; c < nc; ++c) {
-    const int f0 = h->part_offset[c], np = h->part_offset[c + 1] - f0;
-    npart[c] = np;
-    for (int p = 1; p < np; ++p) {
-      const int did = h->defid[h->mix_offset[f0 + p]];
-      const double ax = h->anchors[did * 2], ay = h->anchors[did * 2 + 1];
-      par[(size_t)c * mp + p] = h->parentid[f0 + p];
-      thr[(size_t)c * mp + p] = std::sqrt(ax * ax + ay * ay) * (double)zfactor;
-    }
-  }
-}
-// the pruning's device state: allocated on the first depth-carrying frame with the setting on; the table follows zfactor.
-// Called outside any capture (depth-carrying frames run their launches eagerly).
-static int zf_buffers(pbd_handle* h) {
-  int rc = cand_filter_buffers(h, cand_mode_now(h) == PBD_CAND_SORT_NMS);   // (d_cand_raw: the back-tracking's device output)
-  if (rc) return rc;
-  const size_t cap = (size_t)h->opt.max_candidates, nc = (size_t)h->md.ncomponents, mp = (size_t)h->max_parts;
-  if (!h->d_zf_med) {
-    HIPCHK(h, hipMalloc(&h->d_zf_npart, sizeof(int) * nc));
-    HIPCHK(h, hipMalloc(&h->d_zf_par, sizeof(int) * nc * mp));
-    HIPCHK(h, hipMalloc(&h->d_zf_thr, sizeof(double) * nc * mp));
-    HIPCHK(h, hipMalloc(&h->d_zf_med, sizeof(unsigned long long) * cap * mp));
-    HIPCHK(h, hipMalloc(&h->d_zf_large, sizeof(unsigned) * cap * mp));
-    HIPCHK(h, hipMalloc(&h->d_zf_cnt, sizeof(int) * 2));
-    HIPCHK(h, hipMalloc(&h->d_zf_out, h->cand_stride * cap));
-    h->model_bytes += (sizeof(int) + sizeof(double)) * nc * mp + sizeof(int) * nc + (sizeof(unsigned long long) + sizeof(unsigned)) * cap * mp
-                      + sizeof(int) * 2 + h->cand_stride * cap;
-    h->zf_thr_factor = std::nanf("");
-  }
-  if (!(h->zf_thr_factor == h->zf_factor)) {
-    std::vector<int> npart, par; std::vector<double> thr;
-    zf_table(h, h->zf_factor, npart, par, thr);
-    HIPCHK(h, hipMemcpy(h->d_zf_npart, npart.data(), sizeof(int) * nc, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(h->d_zf_par, par.data(), sizeof(int) * nc * mp, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(h->d_zf_thr, thr.data(), sizeof(double) * nc * mp, hipMemcpyHostToDevice));
-    h->zf_thr_factor = h->zf_factor;
-  }
-  return PBD_OK;
-}
-static ZFilterArgs zf_args(pbd_handle* h) {
-  ZFilterArgs z{};
-  z.capacity = h->opt.max_candidates; z.stride = h->cand_stride; z.mp = h->max_parts;
-  z.npart = h->d_zf_npart; z.par = h->d_zf_par; z.thr = h->d_zf_thr;
-  z.med = h->d_zf_med; z.large = h->d_zf_large; z.nlarge = (unsigned*)(h->d_zf_cnt + 1); z.cnt = h->d_zf_cnt;
-  return z;
-}
-static int zf_type(const pbd_handle* h) { return h->ts == 8 ? PBD_DEPTH_64F : PBD_DEPTH_32F; }
-
-// ---- 3-D boxes (k_box3d.hip) ------------------------------------------------------------------------------------------
-// dog = filter2D(getGaussianKernel(35, 4, CV_32F), (-1, 0, 1) as a column), OpenCV 2.4's arithmetic; its nonzero taps in raster order
-static void b3_taps(Box3dArgs& a) {
-  const int n = 35;
-  float g[35], dog[35];
-  double sum = 0;
-  for (int i = 0; i < n; ++i) {
-    const double x = i - (n - 1) * 0.5;
-    g[i] = (float)std::exp(-0.5 / (4.0 * 4.0) * x * x);
-    sum += g[i];
-  }
-  sum = 1. / sum;
-  for (int i = 0; i < n; ++i) g[i] = (float)(g[i] * sum);
-  for (int i = 0; i < n; ++i) {   // taps -1 and +1 (0 skipped: a zero coefficient), BORDER_REFLECT_101
-    const int im = i - 1 < 0 ? 1 - i : i - 1, ip = i + 1 >= n ? 2 * (n - 1) - (i + 1) : i + 1;
-    float s = 0.0f;
-    s = s + -1.0f * g[im];
-    s = s + 1.0f * g[ip];
-    dog[i] = s;
-  }
-  a.ntaps = 0;
-  for (int i = 0; i < n; ++i)
-    if (dog[i] != 0.0f) { a.tap_off[a.ntaps] = i - (n - 1) / 2; a.tap[a.ntaps] = dog[i]; a.ntaps++; }
-}
-static bool b3_cam_ok(const pbd_camera* c) {
-  return c && std::isfinite(c->fx) && std::isfinite(c->fy) && std::isfinite(c->cx) && std::isfinite(c->cy) && std::isfinite(c->tx) &&
-         std::isfinite(c->ty) && c->fx != 0.0 && c->fy != 0.0;
-}
-static int b3_buffers(pbd_handle* h) {
-  if (h->h_b3) return PBD_OK;
-  const size_t cap = (size_t)h->opt.max_candidates, mp = (size_t)h->max_parts;
-  HIPCHK(h, hipHostMalloc((void**)&h->h_b3, sizeof(pbd_box3d) * cap));
-  HIPCHK(h, hipHostMalloc((void**)&h->h_b3c, sizeof(double) * cap * mp * 3));
-  h->model_bytes += sizeof(pbd_box3d) * cap + sizeof(double) * cap * mp * 3;
-  return PBD_OK;
-}
-// the frame's final records (behind the depth pruning and the candidate filter) -> one box per record slot, pinned
-static int run_box3d(pbd_handle* h) {
-  Box3dArgs a{};
-  a.stride = h->cand_stride; a.mp = h->max_parts; a.capacity = h->opt.max_candidates;
-  a.nlevels = h->nlevels;
-  if (h->out_filtered) { a.recs = h->h_cand_out; a.cf = h->h_cf_cnt; a.count = h->h_cf_cnt; a.nframes = h->batch; }
-  else if (h->zf_on) { a.recs = h->h_cand_out; a.count = h->d_zf_cnt; }
-  else { a.recs = (PBD_ARGMIN_ZERO_COPY && !h->d_gsend) ? h->h_cand_out : h->d_cand_out; a.count = h->d_cand_count; }
-  a.zimg = h->zf_img; a.zpitch = h->zf_pitch; a.zfbytes = h->zf_fbytes; a.zw = h->fw; a.zh = h->fh; a.has = h->b3_has;
-  a.im_w = h->fw; a.im_h = h->fh; a.cam = h->b3_cam;
-  b3_taps(a);
-  a.out = h->h_b3; a.centres = h->h_b3c;
-  launch_box3d(a, h->ts, h->stream);
-  LAUNCHCHK(h, "box3d");
-  if (h->cl3_frame) {   // the object clusters of the same records, right behind
-    Cluster3dArgs c{};
-    c.recs = a.recs; c.stride = a.stride; c.count = a.count; c.capacity = a.capacity; c.cf = a.cf; c.nframes = a.nframes;
-    c.nlevels = a.nlevels; c.has = a.has;
-    c.boxes = h->h_b3;
-    c.cloud = h->zf_img; c.pstride = h->ts; c.rstride = h->zf_pitch; c.fbytes = h->zf_fbytes; c.cw = h->fw; c.ch = h->fh;
-    c.cam = h->b3_cam; c.tol = h->cl3_tol;
-    c.scratch = h->d_cl3_scratch; c.slot_bytes = cluster3d_slot_bytes(h->cl3_pcap); c.pcap = h->cl3_pcap;
-    c.out = h->h_cl3; c.pool = h->d_cl3_pool; c.pool_cap = h->cl3_pool_cap; c.pool_used = h->d_cl3_used;
-    HIPCHK(h, hipMemsetAsync(h->d_cl3_used, 0, sizeof(unsigned long long), h->stream));
-    launch_cluster3d(c, h->ts, std::min(h->cl3_slots, a.capacity), h->stream);
-    LAUNCHCHK(h, "cluster3d");
-    h->cl3_args = c;
-  }
-  return PBD_OK;
-}
-
-// ---- object clusters (k_cluster3d.hip) --------------------------------------------------------------------------------
-// Scratch: one slot of a whole cloud's points per concurrent record, as many slots as fit this budget (at least one, at most one
-// per record and PBD_CL3_MAX_SLOTS), so that no record can fail for lack of scratch.
-#define PBD_CL3_SCRATCH_BUDGET ((size_t)256 << 20)
-#define PBD_CL3_MAX_SLOTS 256
-static int cl3_slots(int pcap, long long records) {
-  const size_t s = PBD_CL3_SCRATCH_BUDGET / cluster3d_slot_bytes(pcap);
-  return (int)std::max<long long>(1, std::min<long long>({(long long)s, records, (long long)PBD_CL3_MAX_SLOTS}));
-}
-static int cl3_buffers(pbd_handle* h) {
-  const size_t cap = (size_t)h->opt.max_candidates;
-  if (!h->h_cl3) {
-    HIPCHK(h, hipHostMalloc((void**)&h->h_cl3, sizeof(Cl3Res) * cap));
-    HIPCHK(h, hipMalloc(&h->d_cl3_used, sizeof(unsigned long long)));
-    h->model_bytes += sizeof(Cl3Res) * cap + sizeof(unsigned long long);
-  }
-  const int pcap = h->fw * h->fh;
-  if (pcap > h->cl3_pcap) {
-    if (h->d_cl3_scratch) { hipFree(h->d_cl3_scratch); h->d_cl3_scratch = nullptr; h->model_bytes -= h->cl3_scratch_bytes; }
-    h->cl3_pcap = 0; h->cl3_scratch_bytes = 0;
-    const int slots = cl3_slots(pcap, (long long)cap);
-    const size_t bytes = cluster3d_slot_bytes(pcap) * slots;
-    HIPCHK(h, hipMalloc(&h->d_cl3_scratch, bytes));
-    h->cl3_pcap = pcap; h->cl3_slots = slots; h->cl3_scratch_bytes = bytes; h->model_bytes += bytes;
-  }
-  const unsigned long long pool = 4ull * (unsigned long long)pcap;   // grows when a frame's kept clusters need more (cl3_resolve)
-  if (h->cl3_pool_cap < pool) {
-    if (h->d_cl3_pool) { hipFree(h->d_cl3_pool); h->d_cl3_pool = nullptr; h->model_bytes -= sizeof(int) * h->cl3_pool_cap; }
-    h->cl3_pool_cap = 0;
-    HIPCHK(h, hipMalloc(&h->d_cl3_pool, sizeof(int) * pool));
-    h->cl3_pool_cap = pool; h->model_bytes += sizeof(int) * pool;
-  }
-  return PBD_OK;
-}
-// After the launch `a` (synchronised): the records `lst` = (record, frame) pairs in output order -> res[] and their kept clusters'
-// indices one after the other in idx[].  Records whose indices did not fit the pool run again, alone, into a pool grown to what
-// they need (and at least what the launch claimed in all, so that the next launch fits); `pool` / `pool_cap` follow the growth.
-static int cl3_resolve(pbd_handle* h, Cluster3dArgs a, int src, int slots, int*& pool, unsigned long long& pool_cap, bool owned,
-                       const std::vector<int>& lst, std::vector<pbd_cluster3d>& res, std::vector<int32_t>& idx) {
-  unsigned long long used = 0;
-  HIPCHK(h, hipMemcpy(&used, a.pool_used, sizeof(used), hipMemcpyDeviceToHost));
-  std::vector<int32_t> first((size_t)std::min(used, pool_cap));
-  if (!first.empty()) HIPCHK(h, hipMemcpy(first.data(), pool, sizeof(int32_t) * first.size(), hipMemcpyDeviceToHost));
-  const size_t n = lst.size() / 2;
-  std::vector<int> spill;
-  std::vector<char> again(n, 0);
-  unsigned long long need = 0;
-  for (size_t k = 0; k < n; ++k) {
-    const Cl3Res& r = a.out[lst[2 * k]];
-    if (r.off < 0 && r.r.size > 0) { spill.push_back(lst[2 * k]); spill.push_back(lst[2 * k + 1]); need += r.r.size; again[k] = 1; }
-  }
-  std::vector<int32_t> second;
-  if (!spill.empty()) {
-    const unsigned long long ncap = std::max(need, used);
-    if (ncap > pool_cap) {
-      hipFree(pool); pool = nullptr;
-      if (owned) h->model_bytes -= sizeof(int) * pool_cap;
-      pool_cap = 0;
-      HIPCHK(h, hipMalloc(&pool, sizeof(int) * ncap));
-      pool_cap = ncap;
-      if (owned) h->model_bytes += sizeof(int) * ncap;
-    }
-    int* d_list = nullptr;
-    HIPCHK(h, hipMalloc(&d_list, sizeof(int) * spill.size()));
-    hipError_t e = hipMemcpy(d_list, spill.data(), sizeof(int) * spill.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemsetAsync(a.pool_used, 0, sizeof(unsigned long long), h->stream);
-    if (e == hipSuccess) {
-      a.list = d_list; a.nlist = (int)(spill.size() / 2); a.pool = pool; a.pool_cap = pool_cap;
-      launch_cluster3d(a, src, std::min(slots, a.nlist), h->stream);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    second.resize((size_t)need);
-    if (e == hipSuccess && need) e = hipMemcpy(second.data(), pool, sizeof(int32_t) * need, hipMemcpyDeviceToHost);
-    hipFree(d_list);
-    if (e != hipSuccess) return fail(h, PBD_ERR_HIP, std::string("cluster3d: ") + hipGetErrorString(e));
-  }
-  res.resize(n);
-  idx.clear();
-  for (size_t k = 0; k < n; ++k) {
-    const Cl3Res& r = a.out[lst[2 * k]];
-    res[k] = r.r;
-    if (r.r.size <= 0) continue;
-    const std::vector<int32_t>& from = again[k] ? second : first;
-    if (r.off < 0 || (unsigned long long)r.off + r.r.size > from.size()) return fail(h, PBD_ERR_HIP, "cluster3d: a record's indices are missing");
-    idx.insert(idx.end(), from.begin() + r.off, from.begin() + r.off + r.r.size);
-  }
-  return PBD_OK;
-}
-
 static int run_argmin_enqueue(pbd_handle* h, bool filter = false) {
   if (h->root_dirty) {   // root tables injected since min(): the hits are those of the tables now on the device
     hipMemsetAsync(h->d_cand_count, 0, sizeof(int), h->stream);
@@ -728,67 +439,24 @@ static int run_argmin_enqueue(pbd_handle* h, bool filter = false) {
   }
   // Round 6: a handle that is not a member of an RCCL-gathering group lets the back-tracking kernel write the records and the count straight
   // into its pinned host buffers (hipHostMalloc: device-mapped, coherent): no copy nodes behind the kernel, and never a second copy for
-  // records beyond a first block.  Group members keep the device buffer: the all-gather reads it.
-  const int cm = filter ? cand_mode_now(h) : PBD_CAND_RAW;
+  // records beyond a first block.  Group members keep the device buffer: the all-gather reads it.  In front of a post-stage (depth
+  // pruning, candidate filter: pbd_post.cpp) the records go to the device buffer it reads.
+  const int cm = filter ? pbd_i_cand_mode(h) : PBD_CAND_RAW;
   h->out_filtered = cm != PBD_CAND_RAW;
-  if (filter && h->zf_frame && h->zf_on) {
-    // depth pruning behind the back-tracking: k_backtrack writes the device buffer, k_zfilter the kept records — straight into the
-    // pinned host buffers (the count follows by a copy), or into the buffer k_cand_filter then sorts (and suppresses) as usual
-    launch_backtrack(h->d_cand_count, h->d_cand_rec, h->opt.max_candidates, h->d_back, h->md.ncomponents, h->d_parent,
-                     h->d_plane0, h->d_nparts, h->max_parts, h->d_mix_rows, h->d_cand_raw, h->cand_stride, h->ts, h->d_flat,
-                     h->d_depth, h->max_depth, (int)h->parts.size(), h->d_scr_base, h->d_dt_ixT, h->d_dt_iy,
-                     h->opt.dt_correct_ptr, h->ext_ptr ? h->d_extx : nullptr, h->d_exty, h->d_ext_base, nullptr, h->stream);
-    HIPCHK(h, hipMemsetAsync(h->d_zf_cnt, 0, sizeof(int) * 2, h->stream));
-    ZFilterArgs z = zf_args(h);
-    z.in = h->d_cand_raw; z.in_count = h->d_cand_count; z.nlevels = h->nlevels;
-    z.zimg = h->zf_img; z.zpitch = h->zf_pitch; z.zfbytes = h->zf_fbytes; z.zw = h->fw; z.zh = h->fh; z.has = h->zf_has;
-    z.out = h->out_filtered ? h->d_zf_out : h->h_cand_out;
-    launch_zfilter(z, h->ts, h->stream);
-    if (h->out_filtered) {
-      CandFilterArgs a = cand_args(h, cm, h->cand_overlap, h->fw, h->fh);
-      a.in = h->d_zf_out; a.in_count = h->d_zf_cnt; a.nlevels = h->nlevels;
-      a.back = h->d_back; a.rootv_base = h->d_rootv; a.gmask = h->d_cf_mask;
-      a.out = h->h_cand_out; a.cnt_out = h->h_cf_cnt;
-      launch_cand_filter(a, h->batch, h->stream);
-    } else {
-      HIPCHK(h, hipMemcpyAsync(h->h_cand_count, h->d_zf_cnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    }
-    LAUNCHCHK(h, "argmin + depth filter");
-    h->pending = true;
-    h->out_on_host = true;
-    return PBD_OK;
-  }
-  if (h->out_filtered) {
-    // Candidate::sort (+ nonMaximaSuppression) behind the back-tracking: k_backtrack writes the device buffer, k_cand_filter the kept
-    // records in final order + the per-frame counts — straight into the pinned host buffers, or, for a member of an RCCL-gathering group,
-    // into the device buffer the all-gather block is packed from
-    const bool dev_out = h->d_gsend != nullptr;
-    char* raw = dev_out ? h->d_cand_raw : h->d_cand_out;
-    launch_backtrack(h->d_cand_count, h->d_cand_rec, h->opt.max_candidates, h->d_back, h->md.ncomponents, h->d_parent,
-                     h->d_plane0, h->d_nparts, h->max_parts, h->d_mix_rows, raw, h->cand_stride, h->ts, h->d_flat,
-                     h->d_depth, h->max_depth, (int)h->parts.size(), h->d_scr_base, h->d_dt_ixT, h->d_dt_iy,
-                     h->opt.dt_correct_ptr, h->ext_ptr ? h->d_extx : nullptr, h->d_exty, h->d_ext_base, nullptr, h->stream);
-    CandFilterArgs a = cand_args(h, cm, h->cand_overlap, h->fw, h->fh);
-    a.in = raw; a.in_count = h->d_cand_count; a.nlevels = h->nlevels;
-    a.back = h->d_back; a.rootv_base = h->d_rootv; a.gmask = h->d_cf_mask;
-    a.out = dev_out ? h->d_cand_out : h->h_cand_out;
-    a.cnt_out = dev_out ? h->d_cf_cnt : h->h_cf_cnt;
-    launch_cand_filter(a, h->batch, h->stream);
-    LAUNCHCHK(h, "argmin + candidate filter");
-    h->pending = true;
-    h->out_on_host = !dev_out;
-    if (!dev_out) return PBD_OK;
-    h->first_copy = kFirstCopy * h->batch;
-    const int first = std::min(h->first_copy, h->opt.max_candidates);
-    HIPCHK(h, hipMemcpyAsync(h->d_gsend, h->d_cf_cnt + 1, sizeof(int), hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_gsend + 16, h->d_cand_out, h->cand_stride * first, hipMemcpyDeviceToDevice, h->stream));
-    return PBD_OK;
-  }
+  const bool zf = filter && h->zf_frame && h->zf_on;
+  const bool post = zf || h->out_filtered;
   const bool zero_copy = PBD_ARGMIN_ZERO_COPY && !h->d_gsend;
+  char* out = h->h_cand_out;
+  int* count_out = h->h_cand_count;
+  if (post || !zero_copy) {
+    out = post && (zf || h->d_gsend) ? h->d_cand_raw : h->d_cand_out;
+    count_out = nullptr;
+  }
   launch_backtrack(h->d_cand_count, h->d_cand_rec, h->opt.max_candidates, h->d_back, h->md.ncomponents, h->d_parent,
-                   h->d_plane0, h->d_nparts, h->max_parts, h->d_mix_rows, zero_copy ? h->h_cand_out : h->d_cand_out, h->cand_stride, h->ts, h->d_flat,
+                   h->d_plane0, h->d_nparts, h->max_parts, h->d_mix_rows, out, h->cand_stride, h->ts, h->d_flat,
                    h->d_depth, h->max_depth, (int)h->parts.size(), h->d_scr_base, h->d_dt_ixT, h->d_dt_iy,
-                   h->opt.dt_correct_ptr, h->ext_ptr ? h->d_extx : nullptr, h->d_exty, h->d_ext_base, zero_copy ? h->h_cand_count : nullptr, h->stream);
+                   h->opt.dt_correct_ptr, h->ext_ptr ? h->d_extx : nullptr, h->d_exty, h->d_ext_base, count_out, h->stream);
+  if (post) return pbd_i_post_enqueue(h, cm, zf, out);
   LAUNCHCHK(h, "argmin");
   if (zero_copy) { h->pending = true; h->out_on_host = true; return PBD_OK; }
   h->out_on_host = false;
@@ -825,7 +493,7 @@ int pbd_i_finish_frame(pbd_handle* h, int found) {
       // that the following frames need no second copy and no second synchronisation.  The copy's size is baked into a
       // captured graph: drop it, the next frame captures again (host cost of one capture, once).
       h->first_copy = std::min(h->opt.max_candidates, n + n / 4 + 16);
-      if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
+      drop_graph(h);
     }
   }
   if (found > h->opt.max_candidates) return fail(h, PBD_ERR_CAPACITY, "device candidate capacity exceeded; raise pbd_options.max_candidates");
@@ -840,9 +508,8 @@ int pbd_i_emit(pbd_handle* h, const std::vector<const char*>& recs, pbd_candidat
   std::vector<int> order(n);
   for (int i = 0; i < n; ++i) order[i] = i;
   auto key = [&](int i, int k) -> int {
-    const char* o = recs[i];
-    const pbd_candidate_head* hd = (const pbd_candidate_head*)o;
-    const int32_t* lc = (const int32_t*)(o + sizeof(pbd_candidate_head)) + (size_t)mp * 4;
+    const pbd_candidate_head* hd = (const pbd_candidate_head*)recs[i];
+    const int32_t* lc = pbd_rec_locs(recs[i], mp);
     return k == 0 ? hd->level : k == 1 ? hd->component : k == 2 ? lc[1] : lc[0];
   };
   if (!ordered)
@@ -852,65 +519,11 @@ int pbd_i_emit(pbd_handle* h, const std::vector<const char*>& recs, pbd_candidat
   });
   if (order_out) *order_out = order;
   if (n > capacity) return fail(h, PBD_ERR_CAPACITY, "output capacity too small");
-  for (int i = 0; i < n; ++i) {
-    const char* o = recs[order[i]];
-    if (heads) heads[i] = *(const pbd_candidate_head*)o;
-    const int32_t* b = (const int32_t*)(o + sizeof(pbd_candidate_head));
-    if (boxes) memcpy(boxes + (size_t)i * mp * 4, b, sizeof(int32_t) * mp * 4);
-    if (locs) memcpy(locs + (size_t)i * mp * 3, b + (size_t)mp * 4, sizeof(int32_t) * mp * 3);
-  }
+  for (int i = 0; i < n; ++i) pbd_rec_get(recs[order[i]], mp, heads, boxes, locs, i);
   return PBD_OK;
 }
 
 int pbd_i_found(const pbd_handle* h) { return h->out_filtered ? h->h_cf_cnt[1] : h->h_cand_count[0]; }
-
-// ---- 3-D boxes of a collected frame: the pinned per-slot results, in the order the records are returned ---------------------
-static void b3_begin(pbd_handle* h, int nframes) {
-  h->b3_res.assign((size_t)nframes, {}); h->b3_cen.assign((size_t)nframes, {}); h->b3_res_on.assign((size_t)nframes, 0);
-  h->b3_ready = true;
-  h->cl3_ready = false;
-  h->cl3_slot.assign((size_t)nframes, {}); h->cl3_res.assign((size_t)nframes, {}); h->cl3_idx.assign((size_t)nframes, {});
-  h->cl3_res_on.assign((size_t)nframes, 0);
-}
-static void b3_gather(pbd_handle* h, int f, const std::vector<const char*>& recs, const std::vector<int>& order) {
-  if (!((h->b3_has >> f) & 1ull)) return;
-  const size_t n = recs.size(), m3 = (size_t)h->max_parts * 3;
-  std::vector<pbd_box3d>& o = h->b3_res[f];
-  std::vector<double>& c = h->b3_cen[f];
-  o.resize(n); c.resize(n * m3);
-  for (size_t i = 0; i < n; ++i) {
-    const size_t slot = (size_t)(recs[order[i]] - h->h_cand_out) / h->cand_stride;
-    o[i] = h->h_b3[slot];
-    memcpy(c.data() + i * m3, h->h_b3c + slot * m3, sizeof(double) * m3);
-    if (h->cl3_frame) h->cl3_slot[f].push_back((int)slot);
-  }
-  h->b3_res_on[f] = 1;
-}
-// the object clusters of the frames b3_gather listed (the collect synchronised the stream)
-static int b3_end(pbd_handle* h) {
-  if (!h->cl3_frame) return PBD_OK;
-  std::vector<int> lst;
-  const int nf = (int)h->cl3_slot.size();
-  for (int f = 0; f < nf; ++f)
-    if (h->b3_res_on[f]) for (int s : h->cl3_slot[f]) { lst.push_back(s); lst.push_back(f); }
-  std::vector<pbd_cluster3d> res;
-  std::vector<int32_t> idx;
-  int rc = cl3_resolve(h, h->cl3_args, h->ts, h->cl3_slots, h->d_cl3_pool, h->cl3_pool_cap, true, lst, res, idx);
-  if (rc) return rc;
-  size_t r0 = 0, i0 = 0;
-  for (int f = 0; f < nf; ++f) {
-    if (!h->b3_res_on[f]) continue;
-    const size_t m = h->cl3_slot[f].size();
-    size_t ni = 0;
-    for (size_t k = 0; k < m; ++k) ni += (size_t)std::max(res[r0 + k].size, 0);
-    h->cl3_res[f].assign(res.begin() + r0, res.begin() + r0 + m);
-    h->cl3_idx[f].assign(idx.begin() + i0, idx.begin() + i0 + ni);
-    h->cl3_res_on[f] = 1;
-    r0 += m; i0 += ni;
-  }
-  h->cl3_ready = true;
-  return PBD_OK;
-}
 
 static int collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* count) {
   if (!h->pending) return fail(h, PBD_ERR_STATE, "collect without a pending detect");
@@ -927,18 +540,16 @@ static int collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int
   rc = pbd_i_emit(h, recs, heads, boxes, locs, capacity, h->out_filtered, h->b3_frame ? &order : nullptr);
   if (rc) return rc;
   if (h->b3_frame) {
-    b3_begin(h, 1);
-    b3_gather(h, 0, recs, order);
-    if ((rc = b3_end(h))) return rc;
+    pbd_i_b3_begin(h, 1);
+    pbd_i_b3_gather(h, 0, recs, order);
+    if ((rc = pbd_i_b3_end(h))) return rc;
   }
   return PBD_OK;
 }
 int pbd_i_collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* count) {
-  int rc = collect(h, heads, boxes, locs, capacity, count);
-  return rc;
+  return collect(h, heads, boxes, locs, capacity, count);
 }
 
-static int run_box3d(pbd_handle* h);
 static int enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride);
 int pbd_i_enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride) { return enqueue_all(h, d_src, stride); }
 static int enqueue_stages(pbd_handle* h, const uint8_t* d_src, int stride) {
@@ -955,7 +566,7 @@ static int enqueue_stages(pbd_handle* h, const uint8_t* d_src, int stride) {
   if (prof) hipEventRecord(h->ev[4], h->stream);
   if ((rc = run_argmin_enqueue(h, true))) return rc;
   if (prof) hipEventRecord(h->ev[5], h->stream);
-  if (h->b3_frame && (rc = run_box3d(h))) return rc;
+  if (h->b3_frame && (rc = pbd_i_run_box3d(h))) return rc;
   return PBD_OK;
 }
 
@@ -967,22 +578,10 @@ static int enqueue_stages(pbd_handle* h, const uint8_t* d_src, int stride) {
 // events) and level groups on extra streams use the eager path.
 static int enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride) {
   const bool graphable = h->opt.graph && !h->profiling;   // (frames of any depth: the launches depend on the plan only; round 5 replayed 8-bit plans only)
-  if (cand_mode_now(h) != PBD_CAND_RAW) {
-    int rc = cand_filter_buffers(h, cand_mode_now(h) == PBD_CAND_SORT_NMS);
-    if (rc) return rc;
-  }
-  h->out_filtered = cand_mode_now(h) != PBD_CAND_RAW;   // (a replayed graph does not pass through run_argmin_enqueue)
-  h->b3_ready = false; h->cl3_ready = false;
-  h->b3_frame = h->zf_frame && h->b3_on;
-  h->cl3_frame = h->b3_frame && h->cl3_on;
-  h->b3_has = h->b3_frame ? h->zf_has : 0;
-  if (h->zf_frame) {   // depth-carrying frames run eagerly: the depth pointers are per frame; a captured graph stays for plain frames
-    int rc = h->zf_on ? zf_buffers(h) : PBD_OK;
-    if (!rc && h->b3_frame) rc = b3_buffers(h);
-    if (!rc && h->cl3_frame) rc = cl3_buffers(h);
-    if (rc) return rc;
-    return enqueue_stages(h, d_src, stride);
-  }
+  int rc = pbd_i_post_buffers(h);
+  if (rc) return rc;
+  // depth-carrying frames run eagerly: the depth pointers are per frame; a captured graph stays for plain frames
+  if (h->zf_frame) return enqueue_stages(h, d_src, stride);
   if (!graphable || h->frames_on_plan == 0) {
     h->frames_on_plan++;
     return enqueue_stages(h, d_src, stride);
@@ -995,7 +594,7 @@ static int enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride) {
   if (!h->gexec) {
     hipGraph_t graph = nullptr;
     HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    int rc = enqueue_stages(h, h->d_img, (int)row);
+    rc = enqueue_stages(h, h->d_img, (int)row);
     hipError_t e = hipStreamEndCapture(h->stream, &graph);
     if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
     if (e != hipSuccess) return fail(h, PBD_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
@@ -1028,6 +627,11 @@ static void read_stage_times(pbd_handle* h) {
 // ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
+// the layouts of include/pbd_c.h that capi.py's ctypes / numpy mirrors rely on
+static_assert(sizeof(pbd_camera) == 48, "pbd_camera layout");
+static_assert(sizeof(pbd_box3d) == 80 && offsetof(pbd_box3d, zmin) == 20 && offsetof(pbd_box3d, x3d) == 32, "pbd_box3d layout");
+static_assert(sizeof(pbd_cluster3d) == 40 && offsetof(pbd_cluster3d, first) == 12 && offsetof(pbd_cluster3d, cx) == 16,
+              "pbd_cluster3d layout");
 #pragma GCC visibility push(default)
 extern "C" {
 
@@ -1076,14 +680,7 @@ int pbd_destroy(pbd_handle* h) {
   hipFree(h->d_cand_count); hipFree(h->d_cand_rec); hipFree(h->d_cand_out);
   if (h->h_cand_out) hipHostFree(h->h_cand_out);
   if (h->h_cand_count) hipHostFree(h->h_cand_count);
-  hipFree(h->d_cand_raw); hipFree(h->d_cf_keys); hipFree(h->d_cf_idx); hipFree(h->d_cf_box); hipFree(h->d_cf_st); hipFree(h->d_cf_cnt);
-  if (h->h_cf_cnt) hipHostFree(h->h_cf_cnt);
-  hipFree(h->d_zf_npart); hipFree(h->d_zf_par); hipFree(h->d_zf_thr); hipFree(h->d_zf_med); hipFree(h->d_zf_large); hipFree(h->d_zf_cnt);
-  hipFree(h->d_zf_out); hipFree(h->d_zimg);
-  if (h->h_b3) hipHostFree(h->h_b3);
-  if (h->h_b3c) hipHostFree(h->h_b3c);
-  if (h->h_cl3) hipHostFree(h->h_cl3);
-  hipFree(h->d_cl3_scratch); hipFree(h->d_cl3_pool); hipFree(h->d_cl3_used);
+  for (const pbd_handle::ModelBuf& b : h->model_allocs) { if (b.pinned) hipHostFree(b.p); else hipFree(b.p); }
   for (int i = 0; i < 8; ++i) if (h->ev[i]) hipEventDestroy(h->ev[i]);
   if (h->ev_dp0) hipEventDestroy(h->ev_dp0);
   if (h->ev_dp1) hipEventDestroy(h->ev_dp1);
@@ -1257,7 +854,7 @@ int pbd_detect_batch_collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* 
     per[((const pbd_candidate_head*)r)->level / n1].push_back(r);
   }
   int status = PBD_OK;
-  if (h->b3_frame) b3_begin(h, B);
+  if (h->b3_frame) pbd_i_b3_begin(h, B);
   std::vector<int> order;
   for (int f = 0; f < B; ++f) {
     counts[f] = (int)per[f].size();
@@ -1266,10 +863,10 @@ int pbd_detect_batch_collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* 
                     h->b3_frame ? &order : nullptr);
     if (rc == PBD_ERR_CAPACITY) { status = rc; continue; }
     if (rc) return rc;
-    if (h->b3_frame) b3_gather(h, f, per[f], order);
+    if (h->b3_frame) pbd_i_b3_gather(h, f, per[f], order);
     for (int i = 0; i < counts[f]; ++i) hf[i].level -= f * n1;   // virtual level -> the frame's own pyramid level
   }
-  if (h->b3_frame && (rc = b3_end(h))) return rc;
+  if (h->b3_frame && (rc = pbd_i_b3_end(h))) return rc;
   return status;
 }
 int pbd_detect_batch_u8(pbd_handle* h, const uint8_t* const* ims, int nframes, int w, int hgt, int cn, int stride,
@@ -1841,165 +1438,7 @@ int pbd_nms_map(pbd_handle* h, const float* src, int rows, int cols, int sz, uin
   return PBD_OK;
 }
 
-// ---- host-side post-processing (include/Candidate.hpp:91-99, 277-304) --------
-int pbd_candidates_sort(pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int count, int mp) {
-  if (!heads || count < 0 || mp <= 0) return PBD_ERR_ARG;
-  std::vector<int> order(count);
-  for (int i = 0; i < count; ++i) order[i] = i;
-  // Candidate::descending; stable, so equal scores keep detect() order (std::sort leaves it unspecified)
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return heads[a].score > heads[b].score; });
-  std::vector<pbd_candidate_head> h2(count);
-  std::vector<int32_t> b2(boxes ? (size_t)count * mp * 4 : 0), l2(locs ? (size_t)count * mp * 3 : 0);
-  for (int i = 0; i < count; ++i) {
-    h2[i] = heads[order[i]];
-    if (boxes) memcpy(&b2[(size_t)i * mp * 4], boxes + (size_t)order[i] * mp * 4, sizeof(int32_t) * mp * 4);
-    if (locs) memcpy(&l2[(size_t)i * mp * 3], locs + (size_t)order[i] * mp * 3, sizeof(int32_t) * mp * 3);
-  }
-  if (count) memcpy(heads, h2.data(), sizeof(pbd_candidate_head) * count);
-  if (boxes && count) memcpy(boxes, b2.data(), b2.size() * sizeof(int32_t));
-  if (locs && count) memcpy(locs, l2.data(), l2.size() * sizeof(int32_t));
-  return PBD_OK;
-}
-
-int pbd_candidates_nms(pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int count, int mp, int im_w, int im_h,
-                       float overlap, int* kept) {
-  if (!heads || !boxes || !kept || count < 0 || mp <= 0 || im_w <= 0 || im_h <= 0) return PBD_ERR_ARG;
-  std::vector<uint8_t> scratch((size_t)im_w * im_h, 0);
-  int keep = 0;
-  for (int n = 0; n < count; ++n) {
-    const int32_t* b = boxes + (size_t)n * mp * 4;
-    int x = b[0], y = b[1], bw = b[2], bh = b[3];  // Candidate::boundingBox(): union of the part rects
-    for (int p = 0; p < heads[n].nparts; ++p) {
-      const int32_t* q = b + p * 4;
-      const int x1 = std::min(x, q[0]), y1 = std::min(y, q[1]);
-      bw = std::max(x + bw, q[0] + q[2]) - x1;
-      bh = std::max(y + bh, q[1] + q[3]) - y1;
-      x = x1; y = y1;
-    }
-    int ix1 = std::max(x, 0), iy1 = std::max(y, 0);  // & bounds
-    int iw = std::min(x + bw, im_w) - ix1, ih = std::min(y + bh, im_h) - iy1;
-    if (iw <= 0 || ih <= 0) ix1 = iy1 = iw = ih = 0;
-    double sum = 0;
-    for (int yy = iy1; yy < iy1 + ih; ++yy)
-      for (int xx = ix1; xx < ix1 + iw; ++xx) sum += scratch[(size_t)yy * im_w + xx];
-    if (sum / (double)(iw * ih) > (double)overlap) continue;  // :296
-    for (int yy = iy1; yy < iy1 + ih; ++yy) memset(&scratch[(size_t)yy * im_w + ix1], 1, iw);
-    if (keep != n) {
-      heads[keep] = heads[n];
-      memmove(boxes + (size_t)keep * mp * 4, boxes + (size_t)n * mp * 4, sizeof(int32_t) * mp * 4);
-      if (locs) memmove(locs + (size_t)keep * mp * 3, locs + (size_t)n * mp * 3, sizeof(int32_t) * mp * 3);
-    }
-    keep++;
-  }
-  *kept = keep;
-  return PBD_OK;
-}
-
-// ---- the post-step on the device (k_cand.hip) -------------------------------------
-static bool cand_mode_ok(int mode, float overlap) {
-  return (mode == PBD_CAND_RAW || mode == PBD_CAND_SORT || mode == PBD_CAND_SORT_NMS) && std::isfinite(overlap);
-}
-int pbd_set_candidate_filter(pbd_handle* h, int mode, float overlap) {
-  if (!h) return PBD_ERR_ARG;
-  if (!cand_mode_ok(mode, overlap)) return fail(h, PBD_ERR_ARG, "candidate filter: mode PBD_CAND_RAW / _SORT / _SORT_NMS, finite overlap");
-  if (h->in_group) return fail(h, PBD_ERR_STATE, "handle belongs to a pbd_group: set the filter on the group");
-  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
-  if (mode != h->cand_mode || overlap != h->cand_overlap) {   // the filter's launch (or its absence) is part of a captured graph
-    if (h->gexec) { ON_DEVICE(h); hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
-  }
-  h->cand_mode = mode;
-  h->cand_overlap = overlap;
-  return PBD_OK;
-}
-
-extern "C++" int pbd_i_filter_host(pbd_handle* h, int mode, float overlap, int im_w, int im_h, pbd_candidate_head* heads, int32_t* boxes,
-                                   int32_t* locs, int count, int* kept) {
-  if (mode == PBD_CAND_RAW || count == 0) { *kept = count; return PBD_OK; }
-  ON_DEVICE(h);
-  const int mp = h->max_parts;
-  const size_t st = h->cand_stride, n = (size_t)count;
-  std::vector<char> rec(st * n, 0);
-  for (size_t i = 0; i < n; ++i) {
-    char* o = rec.data() + st * i;
-    memcpy(o, heads + i, sizeof(pbd_candidate_head));
-    if (boxes) memcpy(o + sizeof(pbd_candidate_head), boxes + i * mp * 4, sizeof(int32_t) * mp * 4);
-    if (locs) memcpy(o + sizeof(pbd_candidate_head) + sizeof(int32_t) * mp * 4, locs + i * mp * 3, sizeof(int32_t) * mp * 3);
-  }
-  const size_t mask = cand_filter_mask_bytes(im_w, im_h);
-  char *d_in = nullptr, *d_out = nullptr; int* d_cnt = nullptr; unsigned long long* d_keys = nullptr; unsigned* d_idx = nullptr;
-  int* d_box = nullptr; uint8_t* d_st = nullptr; unsigned long long* d_mask = nullptr;
-  auto release = [&]() { hipFree(d_in); hipFree(d_out); hipFree(d_cnt); hipFree(d_keys); hipFree(d_idx); hipFree(d_box); hipFree(d_st); hipFree(d_mask); };
-  hipError_t e = hipSuccess;
-  auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-  chk(hipMalloc(&d_in, st * n)); chk(hipMalloc(&d_out, st * n)); chk(hipMalloc(&d_cnt, sizeof(int) * 5));
-  chk(hipMalloc(&d_keys, 16 * n)); chk(hipMalloc(&d_idx, 8 * n)); chk(hipMalloc(&d_box, 16 * n)); chk(hipMalloc(&d_st, n));
-  if (mask && mode == PBD_CAND_SORT_NMS) chk(hipMalloc(&d_mask, mask));
-  chk(hipMemcpyAsync(d_in, rec.data(), st * n, hipMemcpyHostToDevice, h->stream));
-  chk(hipMemcpyAsync(d_cnt, &count, sizeof(int), hipMemcpyHostToDevice, h->stream));
-  if (e == hipSuccess) {
-    CandFilterArgs a = cand_args(h, mode, overlap, im_w, im_h);
-    a.in = d_in; a.in_count = d_cnt; a.capacity = count; a.nlevels = 0; a.back = nullptr;
-    a.keys = d_keys; a.idx = d_idx; a.box = d_box; a.st = d_st; a.gmask = d_mask;
-    a.out = d_out; a.cnt_out = d_cnt + 1;
-    launch_cand_filter(a, 1, h->stream);
-    chk(hipGetLastError());
-  }
-  int cnt[4] = {0, 0, 0, 0};
-  chk(hipMemcpyAsync(cnt, d_cnt + 1, sizeof(int) * 4, hipMemcpyDeviceToHost, h->stream));
-  chk(hipMemcpyAsync(rec.data(), d_out, st * n, hipMemcpyDeviceToHost, h->stream));
-  chk(hipStreamSynchronize(h->stream));
-  release();
-  if (e != hipSuccess) return fail(h, PBD_ERR_HIP, std::string("candidate filter: ") + hipGetErrorString(e));
-  const int k = cnt[1];
-  for (int i = 0; i < k; ++i) {
-    const char* o = rec.data() + st * i;
-    memcpy(heads + i, o, sizeof(pbd_candidate_head));
-    if (boxes) memcpy(boxes + (size_t)i * mp * 4, o + sizeof(pbd_candidate_head), sizeof(int32_t) * mp * 4);
-    if (locs) memcpy(locs + (size_t)i * mp * 3, o + sizeof(pbd_candidate_head) + sizeof(int32_t) * mp * 4, sizeof(int32_t) * mp * 3);
-  }
-  *kept = k;
-  return PBD_OK;
-}
-
-int pbd_candidates_filter(pbd_handle* h, int mode, float overlap, int im_w, int im_h, pbd_candidate_head* heads, int32_t* boxes,
-                          int32_t* locs, int count, int* kept) {
-  if (!h) return PBD_ERR_ARG;
-  if (!cand_mode_ok(mode, overlap)) return fail(h, PBD_ERR_ARG, "candidate filter: mode PBD_CAND_RAW / _SORT / _SORT_NMS, finite overlap");
-  if (!kept || count < 0 || (count > 0 && !heads)) return fail(h, PBD_ERR_ARG, "heads / kept / count");
-  if (mode == PBD_CAND_SORT_NMS && (!boxes || im_w <= 0 || im_h <= 0)) return fail(h, PBD_ERR_ARG, "NMS needs boxes and the image size");
-  for (int i = 0; i < count; ++i) {
-    if (!std::isfinite(heads[i].score)) return fail(h, PBD_ERR_ARG, "non-finite score: its order is undefined");
-    if (mode == PBD_CAND_SORT_NMS && (heads[i].nparts < 0 || heads[i].nparts > h->max_parts)) return fail(h, PBD_ERR_ARG, "nparts outside 0..max_parts");
-  }
-  return pbd_i_filter_host(h, mode, overlap, im_w, im_h, heads, boxes, locs, count, kept);
-}
-
-// ---- depth-consistency pruning (k_zfilter.hip) --------------------------------------------------------------------
-int pbd_set_depth_filter(pbd_handle* h, int on, float zfactor) {
-  if (!h) return PBD_ERR_ARG;
-  if (!std::isfinite(zfactor)) return fail(h, PBD_ERR_ARG, "depth filter: zfactor must be finite");
-  if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "depth filter: pbd_group members are not supported (detect through a handle of its own)");
-  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
-  h->zf_on = on != 0;      // (depth-carrying frames never replay a captured graph: nothing captured depends on the setting)
-  h->zf_factor = zfactor;
-  return PBD_OK;
-}
-
-// the depth arguments of a depth-carrying frame: element type T, rows of >= w elements, stride a multiple of the element size
-static int zf_check(pbd_handle* h, int depth_type, long long dstride, int w) {
-  if (depth_type != zf_type(h))
-    return fail(h, PBD_ERR_UNSUPPORTED, h->ts == 8 ? "depth image: PBD_DEPTH_64F for a double handle (Math::median<T> reads it as T)"
-                                                   : "depth image: PBD_DEPTH_32F for a float handle (Math::median<T> reads it as T)");
-  if (dstride < (long long)w * h->ts || dstride % h->ts) return fail(h, PBD_ERR_ARG, "depth stride: bytes, >= w * element size and a multiple of it");
-  return PBD_OK;
-}
-static int zf_image_buffer(pbd_handle* h, size_t bytes) {
-  if (bytes <= h->zimg_bytes) return PBD_OK;
-  if (h->d_zimg) { hipFree(h->d_zimg); h->model_bytes -= h->zimg_bytes; h->d_zimg = nullptr; h->zimg_bytes = 0; }
-  HIPCHK(h, hipMalloc(&h->d_zimg, bytes));
-  h->zimg_bytes = bytes; h->model_bytes += bytes;
-  return PBD_OK;
-}
+// ---- frames with a depth image (the depth pruning, 3-D boxes and object clusters of pbd_post.cpp behind back-tracking) ----
 // enqueue_all for a frame whose depth images are set in h->zf_*: the flag lives only across the call
 static int zf_enqueue(pbd_handle* h, const uint8_t* d_src, int stride) {
   h->zf_frame = true;
@@ -2013,7 +1452,7 @@ int pbd_detect_rgbd_enqueue_dev_u8(pbd_handle* h, const void* d_im, int w, int h
   if (!h) return PBD_ERR_ARG;
   if ((!h->zf_on && !h->b3_on) || !d_depth) return pbd_detect_enqueue_dev_u8(h, d_im, w, hgt, cn, stride);
   if (!d_im) return PBD_ERR_ARG;
-  int rc = zf_check(h, depth_type, dstride, w);
+  int rc = pbd_i_depth_check(h, depth_type, dstride, w);
   if (rc) return rc;
   if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
   if (stride < w * cn) return fail(h, PBD_ERR_ARG, "stride < w*cn");
@@ -2028,12 +1467,12 @@ int pbd_detect_rgbd_u8(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn,
   if (!h) return PBD_ERR_ARG;
   if ((!h->zf_on && !h->b3_on) || !depth) return pbd_detect_u8(h, im, w, hgt, cn, stride, heads, boxes, locs, capacity, count);
   if (!im) return PBD_ERR_ARG;
-  int rc = zf_check(h, depth_type, dstride, w);
+  int rc = pbd_i_depth_check(h, depth_type, dstride, w);
   if (rc) return rc;
   if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
   if ((rc = upload_image(h, im, w, hgt, cn, stride))) return rc;
   const size_t row = (size_t)w * h->ts;
-  if ((rc = zf_image_buffer(h, row * hgt))) return rc;
+  if ((rc = model_grow(h, &h->d_zimg, h->zimg_bytes, row * hgt))) return rc;
   HIPCHK(h, hipMemcpy2DAsync(h->d_zimg, row, depth, dstride, row, hgt, hipMemcpyHostToDevice, h->stream));
   h->zf_img = h->d_zimg; h->zf_pitch = row; h->zf_fbytes = 0; h->zf_has = 1;
   if ((rc = zf_enqueue(h, h->d_img, w * cn))) return rc;
@@ -2046,7 +1485,7 @@ int pbd_detect_batch_rgbd_enqueue_dev_u8(pbd_handle* h, const void* d_ims, const
   if (!h->zf_on && !h->b3_on) return pbd_detect_batch_enqueue_dev_u8(h, d_ims, nframes, w, hgt, cn);
   if (!d_depths) return fail(h, PBD_ERR_ARG, "device batch: the depth images are one packed buffer (NULL: use pbd_detect_batch_enqueue_dev_u8)");
   if (!d_ims || nframes < 1) return PBD_ERR_ARG;
-  int rc = zf_check(h, depth_type, (long long)w * h->ts, w);
+  int rc = pbd_i_depth_check(h, depth_type, (long long)w * h->ts, w);
   if (rc) return rc;
   if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
   ON_DEVICE(h);
@@ -2063,13 +1502,13 @@ int pbd_detect_batch_rgbd_u8(pbd_handle* h, const uint8_t* const* ims, const voi
   unsigned long long has = 0;
   for (int f = 0; depths && f < nframes && f < 64; ++f) if (depths[f]) has |= 1ull << f;
   if ((!h->zf_on && !h->b3_on) || !has) return pbd_detect_batch_u8(h, ims, nframes, w, hgt, cn, stride, heads, boxes, locs, capacity, counts);
-  int rc = zf_check(h, depth_type, dstride, w);
+  int rc = pbd_i_depth_check(h, depth_type, dstride, w);
   if (rc) return rc;
   if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
   if (!ims || nframes < 1 || nframes > 64) return fail(h, PBD_ERR_ARG, "batch: 1..64 frames");
   ON_DEVICE(h);
   const size_t row = (size_t)w * h->ts, fb = row * hgt;
-  if ((rc = zf_image_buffer(h, fb * nframes))) return rc;
+  if ((rc = model_grow(h, &h->d_zimg, h->zimg_bytes, fb * nframes))) return rc;
   for (int f = 0; f < nframes; ++f)
     if (depths[f]) HIPCHK(h, hipMemcpy2DAsync(h->d_zimg + fb * f, row, depths[f], dstride, row, hgt, hipMemcpyHostToDevice, h->stream));
   h->zf_img = h->d_zimg; h->zf_pitch = row; h->zf_fbytes = fb; h->zf_has = has;
@@ -2080,252 +1519,6 @@ int pbd_detect_batch_rgbd_u8(pbd_handle* h, const uint8_t* const* ims, const voi
   return pbd_detect_batch_collect(h, heads, boxes, locs, capacity, counts);
 }
 
-int pbd_candidates_depth_filter(pbd_handle* h, float zfactor, const void* depth, int depth_type, int dw, int dh, int dstride,
-                                pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int count, int* kept) {
-  if (!h) return PBD_ERR_ARG;
-  if (!std::isfinite(zfactor)) return fail(h, PBD_ERR_ARG, "depth filter: zfactor must be finite");
-  if (!kept || count < 0 || (count > 0 && (!heads || !boxes))) return fail(h, PBD_ERR_ARG, "heads / boxes / kept / count");
-  if (dw < 0 || dh < 0 || (!depth && dw > 0 && dh > 0)) return fail(h, PBD_ERR_ARG, "depth image: NULL only with an empty size");
-  const bool empty = !depth || dw == 0 || dh == 0;
-  if (depth_type != zf_type(h)) return zf_check(h, depth_type, dstride, dw);
-  if (!empty) { int rc = zf_check(h, depth_type, dstride, dw); if (rc) return rc; }
-  for (int i = 0; i < count; ++i) {
-    const int c = heads[i].component;
-    if (c < 0 || c >= h->md.ncomponents) return fail(h, PBD_ERR_ARG, "component out of range");
-    if (heads[i].nparts != h->part_offset[c + 1] - h->part_offset[c]) return fail(h, PBD_ERR_ARG, "nparts differs from the model's component");
-  }
-  if (count == 0) { *kept = 0; return PBD_OK; }
-  ON_DEVICE(h);
-  const int mp = h->max_parts, nc = h->md.ncomponents;
-  const size_t st = h->cand_stride, n = (size_t)count, row = (size_t)dw * h->ts;
-  std::vector<char> rec(st * n, 0);
-  for (size_t i = 0; i < n; ++i) {
-    char* o = rec.data() + st * i;
-    memcpy(o, heads + i, sizeof(pbd_candidate_head));
-    memcpy(o + sizeof(pbd_candidate_head), boxes + i * mp * 4, sizeof(int32_t) * mp * 4);
-  }
-  std::vector<int> npart, par; std::vector<double> thr;
-  zf_table(h, zfactor, npart, par, thr);
-  char *d_in = nullptr, *d_img = nullptr; int *d_cnt = nullptr, *d_np = nullptr, *d_par = nullptr; double* d_thr = nullptr;
-  unsigned long long* d_med = nullptr; unsigned* d_large = nullptr; uint8_t* d_flags = nullptr;
-  hipError_t e = hipSuccess;
-  auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-  chk(hipMalloc(&d_in, st * n)); chk(hipMalloc(&d_cnt, sizeof(int) * 3)); chk(hipMalloc(&d_flags, n));
-  chk(hipMalloc(&d_np, sizeof(int) * nc)); chk(hipMalloc(&d_par, sizeof(int) * nc * mp)); chk(hipMalloc(&d_thr, sizeof(double) * nc * mp));
-  chk(hipMalloc(&d_med, sizeof(unsigned long long) * n * mp)); chk(hipMalloc(&d_large, sizeof(unsigned) * n * mp));
-  if (!empty) chk(hipMalloc(&d_img, row * dh));
-  const int cnt3[3] = {count, 0, 0};
-  chk(hipMemcpy(d_in, rec.data(), st * n, hipMemcpyHostToDevice));
-  chk(hipMemcpy(d_cnt, cnt3, sizeof(cnt3), hipMemcpyHostToDevice));
-  chk(hipMemcpy(d_np, npart.data(), sizeof(int) * nc, hipMemcpyHostToDevice));
-  chk(hipMemcpy(d_par, par.data(), sizeof(int) * nc * mp, hipMemcpyHostToDevice));
-  chk(hipMemcpy(d_thr, thr.data(), sizeof(double) * nc * mp, hipMemcpyHostToDevice));
-  if (!empty) chk(hipMemcpy2D(d_img, row, depth, dstride, row, dh, hipMemcpyHostToDevice));
-  std::vector<uint8_t> flags(n, 0);
-  if (e == hipSuccess) {
-    ZFilterArgs z{};
-    z.in = d_in; z.in_count = d_cnt; z.capacity = count; z.stride = st; z.mp = mp; z.nlevels = 0;
-    z.zimg = d_img; z.zpitch = row; z.zfbytes = 0; z.zw = empty ? 0 : dw; z.zh = empty ? 0 : dh; z.has = 1;
-    z.npart = d_np; z.par = d_par; z.thr = d_thr; z.med = d_med; z.large = d_large; z.nlarge = (unsigned*)(d_cnt + 2);
-    z.cnt = d_cnt + 1; z.flags = d_flags;
-    launch_zfilter(z, h->ts, h->stream);
-    chk(hipGetLastError());
-  }
-  chk(hipMemcpyAsync(flags.data(), d_flags, n, hipMemcpyDeviceToHost, h->stream));
-  chk(hipStreamSynchronize(h->stream));
-  hipFree(d_in); hipFree(d_img); hipFree(d_cnt); hipFree(d_np); hipFree(d_par); hipFree(d_thr); hipFree(d_med); hipFree(d_large); hipFree(d_flags);
-  if (e != hipSuccess) return fail(h, PBD_ERR_HIP, std::string("depth filter: ") + hipGetErrorString(e));
-  int k = 0;
-  for (int i = 0; i < count; ++i) {   // stable compaction in place
-    if (!flags[i]) continue;
-    if (k != i) {
-      heads[k] = heads[i];
-      memmove(boxes + (size_t)k * mp * 4, boxes + (size_t)i * mp * 4, sizeof(int32_t) * mp * 4);
-      if (locs) memmove(locs + (size_t)k * mp * 3, locs + (size_t)i * mp * 3, sizeof(int32_t) * mp * 3);
-    }
-    ++k;
-  }
-  *kept = k;
-  return PBD_OK;
-}
-
-// ---- 3-D boxes (k_box3d.hip) --------------------------------------------------------------------------------------------
-static_assert(sizeof(pbd_camera) == 48, "pbd_camera layout");
-static_assert(sizeof(pbd_box3d) == 80 && offsetof(pbd_box3d, zmin) == 20 && offsetof(pbd_box3d, x3d) == 32, "pbd_box3d layout");
-
-int pbd_set_box3d(pbd_handle* h, int on, const pbd_camera* cam) {
-  if (!h) return PBD_ERR_ARG;
-  if (on && !b3_cam_ok(cam)) return fail(h, PBD_ERR_ARG, "box3d: a camera with finite intrinsics and nonzero fx, fy");
-  if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "box3d: pbd_group members are not supported (detect through a handle of its own)");
-  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
-  h->b3_on = on != 0;
-  if (on) h->b3_cam = *cam;
-  return PBD_OK;
-}
-
-int pbd_get_box3d(pbd_handle* h, int frame, pbd_box3d* out, double* centres, int capacity, int* count) {
-  if (!h || !count || capacity < 0 || (capacity > 0 && !out)) return PBD_ERR_ARG;
-  if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "box3d: pbd_group members are not supported");
-  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
-  if (!h->b3_ready || frame < 0 || frame >= (int)h->b3_res_on.size() || !h->b3_res_on[frame])
-    return fail(h, PBD_ERR_STATE, "box3d: the last frame did not compute 3-D boxes for this frame (plain entry point, setting off, or no depth)");
-  const std::vector<pbd_box3d>& r = h->b3_res[frame];
-  const int n = (int)r.size();
-  *count = n;
-  if (n > capacity) return fail(h, PBD_ERR_CAPACITY, "output capacity too small");
-  std::copy(r.begin(), r.end(), out);
-  if (centres) std::copy(h->b3_cen[frame].begin(), h->b3_cen[frame].end(), centres);
-  return PBD_OK;
-}
-
-int pbd_candidates_box3d(pbd_handle* h, const pbd_camera* cam, const void* depth, int depth_type, int dw, int dh, int dstride,
-                         int im_w, int im_h, const pbd_candidate_head* heads, const int32_t* boxes, int count, pbd_box3d* out,
-                         double* centres) {
-  if (!h) return PBD_ERR_ARG;
-  if (!b3_cam_ok(cam)) return fail(h, PBD_ERR_ARG, "box3d: a camera with finite intrinsics and nonzero fx, fy");
-  if (im_w <= 0 || im_h <= 0) return fail(h, PBD_ERR_ARG, "box3d: im_w, im_h > 0");
-  if (count < 0 || (count > 0 && (!heads || !boxes || !out))) return fail(h, PBD_ERR_ARG, "heads / boxes / out / count");
-  if (dw < 0 || dh < 0 || (!depth && dw > 0 && dh > 0)) return fail(h, PBD_ERR_ARG, "depth image: NULL only with an empty size");
-  if (depth_type != PBD_DEPTH_32F && depth_type != PBD_DEPTH_64F)
-    return fail(h, PBD_ERR_UNSUPPORTED, "box3d: depth PBD_DEPTH_32F or PBD_DEPTH_64F (Mat_<float> reads it)");
-  const int esz = depth_type == PBD_DEPTH_64F ? 8 : 4;
-  const bool empty = !depth || dw == 0 || dh == 0;
-  if (!empty && (dstride < (long long)dw * esz || dstride % esz)) return fail(h, PBD_ERR_ARG, "depth stride: bytes, >= dw * element size and a multiple of it");
-  const int mp = h->max_parts;
-  for (int i = 0; i < count; ++i)
-    if (heads[i].nparts < 1 || heads[i].nparts > mp) return fail(h, PBD_ERR_ARG, "nparts outside 1 .. max_parts");
-  if (count == 0) return PBD_OK;
-  ON_DEVICE(h);
-  const size_t st = sizeof(pbd_candidate_head) + sizeof(int32_t) * 4 * mp, n = (size_t)count, row = (size_t)dw * esz;
-  std::vector<char> rec(st * n, 0);
-  for (size_t i = 0; i < n; ++i) {
-    memcpy(rec.data() + st * i, heads + i, sizeof(pbd_candidate_head));
-    memcpy(rec.data() + st * i + sizeof(pbd_candidate_head), boxes + i * mp * 4, sizeof(int32_t) * mp * 4);
-  }
-  char *d_in = nullptr, *d_img = nullptr; int* d_cnt = nullptr; pbd_box3d* d_out = nullptr; double* d_cen = nullptr;
-  hipError_t e = hipSuccess;
-  auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-  chk(hipMalloc(&d_in, st * n)); chk(hipMalloc(&d_cnt, sizeof(int))); chk(hipMalloc(&d_out, sizeof(pbd_box3d) * n));
-  if (centres) chk(hipMalloc(&d_cen, sizeof(double) * n * mp * 3));
-  if (!empty) chk(hipMalloc(&d_img, row * dh));
-  chk(hipMemcpy(d_in, rec.data(), st * n, hipMemcpyHostToDevice));
-  chk(hipMemcpy(d_cnt, &count, sizeof(int), hipMemcpyHostToDevice));
-  if (!empty) chk(hipMemcpy2D(d_img, row, depth, dstride, row, dh, hipMemcpyHostToDevice));
-  if (e == hipSuccess) {
-    Box3dArgs a{};
-    a.recs = d_in; a.stride = st; a.mp = mp; a.count = d_cnt; a.capacity = count; a.nlevels = 0;
-    a.zimg = d_img; a.zpitch = row; a.zfbytes = 0; a.zw = empty ? 0 : dw; a.zh = empty ? 0 : dh; a.has = 1;
-    a.im_w = im_w; a.im_h = im_h; a.cam = *cam;
-    b3_taps(a);
-    a.out = d_out; a.centres = d_cen;
-    if (depth_type == PBD_DEPTH_64F) launch_box3d(a, 8, h->stream);
-    else launch_box3d(a, 4, h->stream);
-    chk(hipGetLastError());
-  }
-  chk(hipMemcpyAsync(out, d_out, sizeof(pbd_box3d) * n, hipMemcpyDeviceToHost, h->stream));
-  if (centres) chk(hipMemcpyAsync(centres, d_cen, sizeof(double) * n * mp * 3, hipMemcpyDeviceToHost, h->stream));
-  chk(hipStreamSynchronize(h->stream));
-  hipFree(d_in); hipFree(d_img); hipFree(d_cnt); hipFree(d_out); hipFree(d_cen);
-  if (e != hipSuccess) return fail(h, PBD_ERR_HIP, std::string("box3d: ") + hipGetErrorString(e));
-  return PBD_OK;
-}
-
-// ---- object clusters (k_cluster3d.hip) ----------------------------------------------------------------------------------
-static_assert(sizeof(pbd_cluster3d) == 40 && offsetof(pbd_cluster3d, first) == 12 && offsetof(pbd_cluster3d, cx) == 16,
-              "pbd_cluster3d layout");
-static bool cl3_tol_ok(float t) { return std::isfinite(t) && t > 0.f; }
-
-int pbd_set_cluster3d(pbd_handle* h, int on, float tolerance) {
-  if (!h) return PBD_ERR_ARG;
-  if (on && !cl3_tol_ok(tolerance)) return fail(h, PBD_ERR_ARG, "cluster3d: a finite tolerance > 0");
-  if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "cluster3d: pbd_group members are not supported (detect through a handle of its own)");
-  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
-  h->cl3_on = on != 0;
-  if (on) h->cl3_tol = tolerance;
-  return PBD_OK;
-}
-
-// results + their indices (the exclusive prefix sum of size) -> the caller's arrays
-static int cl3_copy_out(pbd_handle* h, const std::vector<int32_t>& idx, int32_t* indices, int idx_capacity, int* idx_total) {
-  if (idx_total) *idx_total = (int)idx.size();
-  if (!indices) return PBD_OK;
-  if ((long long)idx.size() > (long long)idx_capacity) return fail(h, PBD_ERR_CAPACITY, "cluster3d: index capacity too small");
-  std::copy(idx.begin(), idx.end(), indices);
-  return PBD_OK;
-}
-
-int pbd_get_cluster3d(pbd_handle* h, int frame, pbd_cluster3d* out, int capacity, int* count, int32_t* indices, int idx_capacity,
-                      int* idx_total) {
-  if (!h || !count || capacity < 0 || (capacity > 0 && !out) || (indices && (idx_capacity < 0 || !idx_total))) return PBD_ERR_ARG;
-  if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "cluster3d: pbd_group members are not supported");
-  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
-  if (!h->cl3_ready || frame < 0 || frame >= (int)h->cl3_res_on.size() || !h->cl3_res_on[frame])
-    return fail(h, PBD_ERR_STATE, "cluster3d: the last frame did not compute object clusters for this frame (plain entry point, "
-                                  "3-D boxes or clusters off, or no depth)");
-  const std::vector<pbd_cluster3d>& r = h->cl3_res[frame];
-  const int n = (int)r.size();
-  *count = n;
-  if (idx_total) *idx_total = (int)h->cl3_idx[frame].size();
-  if (n > capacity) return fail(h, PBD_ERR_CAPACITY, "output capacity too small");
-  std::copy(r.begin(), r.end(), out);
-  return cl3_copy_out(h, h->cl3_idx[frame], indices, idx_capacity, idx_total);
-}
-
-int pbd_candidates_cluster3d(pbd_handle* h, const void* cloud, int cw, int ch, int point_stride, int row_stride,
-                             const pbd_box3d* boxes, int count, float tolerance, pbd_cluster3d* out, int32_t* indices,
-                             int idx_capacity, int* idx_total) {
-  if (!h) return PBD_ERR_ARG;
-  if (!cl3_tol_ok(tolerance)) return fail(h, PBD_ERR_ARG, "cluster3d: a finite tolerance > 0");
-  if (cw < 0 || ch < 0 || (long long)cw * ch > (1ll << 30)) return fail(h, PBD_ERR_ARG, "cluster3d: cloud size");
-  const long long npts = (long long)cw * ch;
-  if (point_stride < 12 || point_stride % 4) return fail(h, PBD_ERR_ARG, "cluster3d: point stride: bytes, >= 12 and a multiple of 4");
-  if (npts > 0 && (!cloud || row_stride % 4 || (long long)row_stride < (long long)(cw - 1) * point_stride + 12))
-    return fail(h, PBD_ERR_ARG, "cluster3d: a cloud (NULL only when empty), row stride: bytes, >= (cw - 1) * point stride + 12, a multiple of 4");
-  if (count < 0 || (count > 0 && (!boxes || !out))) return fail(h, PBD_ERR_ARG, "boxes / out / count");
-  if (indices && (idx_capacity < 0 || !idx_total)) return fail(h, PBD_ERR_ARG, "indices: idx_capacity >= 0 and idx_total");
-  if (count == 0) return cl3_copy_out(h, {}, indices, idx_capacity, idx_total);
-  ON_DEVICE(h);
-  const int pcap = (int)std::max<long long>(npts, 1);
-  const int slots = cl3_slots(pcap, count);
-  const size_t bytes = npts ? (size_t)(ch - 1) * row_stride + (size_t)(cw - 1) * point_stride + 12 : 0, n = (size_t)count;
-  char *d_cloud = nullptr, *d_scr = nullptr; int* d_cnt = nullptr; pbd_box3d* d_box = nullptr; Cl3Res* h_res = nullptr;
-  int* d_pool = nullptr; unsigned long long* d_used = nullptr;
-  unsigned long long pool_cap = std::min<unsigned long long>((unsigned long long)count * (unsigned long long)npts, 4ull * (unsigned long long)pcap);
-  pool_cap = std::max<unsigned long long>(pool_cap, 1);
-  hipError_t e = hipSuccess;
-  auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-  if (bytes) chk(hipMalloc(&d_cloud, bytes));
-  chk(hipMalloc(&d_scr, cluster3d_slot_bytes(pcap) * slots)); chk(hipMalloc(&d_cnt, sizeof(int)));
-  chk(hipMalloc(&d_box, sizeof(pbd_box3d) * n)); chk(hipHostMalloc((void**)&h_res, sizeof(Cl3Res) * n));
-  chk(hipMalloc(&d_pool, sizeof(int) * pool_cap)); chk(hipMalloc(&d_used, sizeof(unsigned long long)));
-  if (bytes) chk(hipMemcpy(d_cloud, cloud, bytes, hipMemcpyHostToDevice));
-  chk(hipMemcpy(d_cnt, &count, sizeof(int), hipMemcpyHostToDevice));
-  chk(hipMemcpy(d_box, boxes, sizeof(pbd_box3d) * n, hipMemcpyHostToDevice));
-  chk(hipMemset(d_used, 0, sizeof(unsigned long long)));
-  Cluster3dArgs a{};
-  a.count = d_cnt; a.capacity = count; a.has = 1; a.boxes = d_box;
-  a.cloud = d_cloud; a.pstride = (size_t)point_stride; a.rstride = (size_t)row_stride; a.cw = cw; a.ch = ch; a.tol = tolerance;
-  a.scratch = d_scr; a.slot_bytes = cluster3d_slot_bytes(pcap); a.pcap = pcap;
-  a.out = h_res; a.pool = d_pool; a.pool_cap = pool_cap; a.pool_used = d_used;
-  if (e == hipSuccess) {
-    launch_cluster3d(a, 0, slots, h->stream);
-    chk(hipGetLastError());
-  }
-  chk(hipStreamSynchronize(h->stream));
-  int rc = PBD_OK;
-  std::vector<pbd_cluster3d> res;
-  std::vector<int32_t> idx;
-  if (e == hipSuccess) {
-    std::vector<int> lst(2 * n);
-    for (size_t i = 0; i < n; ++i) { lst[2 * i] = (int)i; lst[2 * i + 1] = 0; }
-    rc = cl3_resolve(h, a, 0, slots, d_pool, pool_cap, false, lst, res, idx);
-  }
-  hipFree(d_cloud); hipFree(d_scr); hipFree(d_cnt); hipFree(d_box); hipHostFree(h_res); hipFree(d_pool); hipFree(d_used);
-  if (e != hipSuccess) return fail(h, PBD_ERR_HIP, std::string("cluster3d: ") + hipGetErrorString(e));
-  if (rc) return rc;
-  std::copy(res.begin(), res.end(), out);
-  return cl3_copy_out(h, idx, indices, idx_capacity, idx_total);
-}
 
 // ---- instrumentation ---------------------------------------------------------
 int pbd_get_stage_ms(const pbd_handle* h, float ms[6]) {

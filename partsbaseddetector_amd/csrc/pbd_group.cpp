@@ -265,8 +265,7 @@ int pbd_group_set_candidate_filter(pbd_group* g, int mode, float overlap) {
     pbd_handle* h = g->m[i];
     if ((mode != h->cand_mode || overlap != h->cand_overlap) && h->gexec) {
       GHIP(g, hipSetDevice(g->dev[i]));
-      hipGraphExecDestroy(h->gexec);
-      h->gexec = nullptr;
+      drop_graph(h);
     }
     h->cand_mode = mode;
     h->cand_overlap = overlap;
@@ -405,7 +404,7 @@ static int frame_impl(pbd_group* g, const uint8_t* im, int w, int hgt, int cn, i
     for (int j = 0; j < g->found[i]; ++j) {
       const char* r = rec_ptr(g, i, j);
       const pbd_candidate_head* hd = (const pbd_candidate_head*)r;
-      const int32_t* lc = (const int32_t*)(r + sizeof(pbd_candidate_head)) + (size_t)mp * 4;
+      const int32_t* lc = pbd_rec_locs(r, mp);
       if (seen.insert({hd->level, hd->component, lc[1], lc[0]}).second) recs.push_back(r);
     }
   if (g->cand_mode == PBD_CAND_RAW) {
@@ -417,19 +416,17 @@ static int frame_impl(pbd_group* g, const uint8_t* im, int w, int hgt, int cn, i
   // the union in the single-handle order, then the same kernel on member 0 (one small H2D of the gathered records) — the host
   // functions applied to the unfiltered group output
   const int nr = (int)recs.size();
-  std::vector<pbd_candidate_head> hh((size_t)std::max(nr, 1));
-  std::vector<int32_t> bb((size_t)std::max(nr, 1) * mp * 4), ll((size_t)std::max(nr, 1) * mp * 3);
-  rc = pbd_i_emit(g->m[0], recs, hh.data(), bb.data(), ll.data(), nr);
+  const size_t st = g->m[0]->cand_stride;
+  std::vector<int> order;
+  rc = pbd_i_emit(g->m[0], recs, nullptr, nullptr, nullptr, nr, false, &order);
   if (rc) return gfail(g, rc, pbd_last_error(g->m[0]));
+  std::vector<char> packed(st * nr);
+  for (int i = 0; i < nr; ++i) memcpy(packed.data() + st * i, recs[order[i]], st);
   int kept = 0;
   GHIP(g, hipSetDevice(g->dev[0]));
-  GMEMBER(g, 0, pbd_i_filter_host(g->m[0], g->cand_mode, g->cand_overlap, w, hgt, hh.data(), bb.data(), ll.data(), nr, &kept));
+  GMEMBER(g, 0, pbd_i_filter_host(g->m[0], g->cand_mode, g->cand_overlap, w, hgt, packed.data(), nr, &kept));
   if (count) *count = kept;
   if (kept > capacity) return gfail(g, PBD_ERR_CAPACITY, "output capacity too small");
-  for (int i = 0; i < kept; ++i) {
-    heads[i] = hh[i];
-    if (boxes) memcpy(boxes + (size_t)i * mp * 4, &bb[(size_t)i * mp * 4], sizeof(int32_t) * mp * 4);
-    if (locs) memcpy(locs + (size_t)i * mp * 3, &ll[(size_t)i * mp * 3], sizeof(int32_t) * mp * 3);
-  }
+  for (int i = 0; i < kept; ++i) pbd_rec_get(packed.data() + st * i, mp, heads, boxes, locs, i);
   return PBD_OK;
 }

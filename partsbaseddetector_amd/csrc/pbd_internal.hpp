@@ -15,6 +15,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 #include <string>
 #include <vector>
 #include "../../include/pbd_c.h"
@@ -34,18 +35,40 @@
 
 struct CandRec { int level, comp, y, x; };
 
+// ---- what every post-stage kernel reads (k_cand / k_zfilter / k_box3d / k_cluster3d) --------------------------------------
+// A record is a pbd_candidate_head, then mp * 4 box ints, then mp * 3 loc ints (pbd_rec_bytes).
+// The records of a frame or a batch: `count` (device) records at p (count > capacity: the back-tracking overflowed).
+struct RecordSet {
+  const char* p; size_t stride; int mp;
+  const int* count; int capacity;
+  const int* cf; int nframes;   // non-null: k_cand_filter's counts; frame f's records at [cf[2+nf+f], +cf[2+f])
+  int nlevels;                  // else frame of a record = level / nlevels (0: one frame)
+};
+// Frame f's depth image (element type T) at img + f * fbytes, w x h, rows pitch bytes apart; has: frames that carry depth (bit f)
+struct DepthFrames {
+  const char* img; size_t pitch, fbytes; int w, h; unsigned long long has;
+};
+#ifdef __HIPCC__
+// the frame record i belongs to; -1: none (filtered output beyond every frame's kept records)
+__device__ __forceinline__ int record_frame(const RecordSet& r, int i) {
+  if (r.cf) {   // filtered output: frame f's records sit at [start_f, start_f + kept_f)
+    for (int k = 0; k < r.nframes; ++k)
+      if (i >= r.cf[2 + r.nframes + k] && i < r.cf[2 + r.nframes + k] + r.cf[2 + k]) return k;
+    return -1;
+  }
+  return r.nlevels ? ((const pbd_candidate_head*)(r.p + r.stride * (size_t)i))->level / r.nlevels : 0;
+}
+#endif
+
 // object clusters (k_cluster3d.hip): one record's result in the slot of its record
 struct Cl3Res { pbd_cluster3d r; long long off; };   // off: the kept cluster's indices in the pool; -1: they did not fit
 
 struct Cluster3dArgs {
-  const char* recs; size_t stride;            // records (frame mapping as Box3dArgs) and their device count
-  const int* count; int capacity;
-  const int* cf; int nframes; int nlevels;
-  unsigned long long has;
+  RecordSet in;
+  DepthFrames z; size_t pstride;              // the xyz cloud (points pstride bytes apart), or the depth image (the pinhole model)
   const int* list; int nlist;                 // non-null: only these (record, frame) pairs
   const pbd_box3d* boxes;                     // [capacity] by record
-  const char* cloud; size_t pstride, rstride, fbytes; int cw, ch;   // frame f's cloud at cloud + f * fbytes
-  pbd_camera cam;                             // depth source: the pinhole model (pstride unused)
+  pbd_camera cam;                             // depth source: the pinhole model
   float tol;
   char* scratch; size_t slot_bytes; int pcap; // one slot of pcap points per workgroup
   Cl3Res* out;                                // [capacity]
@@ -144,6 +167,8 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   hipGraphExec_t gexec = nullptr;   // pbd_options.graph: the frame's launches, captured once per geometry
   int frames_on_plan = 0;           // frames enqueued since the last plan_frame
   std::vector<void*> frame_allocs;  // everything freed on re-plan
+  struct ModelBuf { void* p; size_t bytes; bool pinned; };
+  std::vector<ModelBuf> model_allocs;   // the post-stages' buffers (pbd_post.cpp model_alloc): held until pbd_destroy
   size_t frame_bytes = 0, model_bytes = 0;   // device memory held for the frame plan / the model (pbd_get_footprint)
   // pointer tables handed in by the caller (pbd_set_dp_pointers: a DynamicProgram::argmin fed tables that this handle's
   // min() did not produce): composed Ix / Iy per (level, component, plane), allocated on first use; back-tracking
@@ -176,7 +201,6 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   bool b3_frame = false;            // the pending frame computes boxes (its depth frames: zf_has)
   unsigned long long b3_has = 0;
   pbd_box3d* h_b3 = nullptr; double* h_b3c = nullptr;   // [capacity], [capacity * mp * 3]: pinned
-  float* d_b3_taps = nullptr;
   bool b3_ready = false;            // results of the last collected frame, per frame in the order returned
   std::vector<std::vector<pbd_box3d>> b3_res; std::vector<std::vector<double>> b3_cen; std::vector<char> b3_res_on;
   // object clusters (pbd_set_cluster3d): k_cluster3d.hip right behind k_box3d.  Results per record slot (pinned); the kept
@@ -184,7 +208,7 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   bool cl3_on = false; float cl3_tol = 0.01f;
   bool cl3_frame = false;           // the pending frame computes clusters (the frames of b3_has)
   Cl3Res* h_cl3 = nullptr;           // [capacity]: pinned
-  char* d_cl3_scratch = nullptr; size_t cl3_scratch_bytes = 0; int cl3_slots = 0, cl3_pcap = 0;
+  char* d_cl3_scratch = nullptr; int cl3_slots = 0, cl3_pcap = 0;
   int* d_cl3_pool = nullptr; unsigned long long cl3_pool_cap = 0; unsigned long long* d_cl3_used = nullptr;
   Cluster3dArgs cl3_args{};         // the pending frame's launch (the collect runs overflowing records again with it)
   bool cl3_ready = false;           // results of the last collected frame, per frame in the order returned
@@ -192,6 +216,67 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   std::vector<std::vector<pbd_cluster3d>> cl3_res; std::vector<std::vector<int32_t>> cl3_idx; std::vector<char> cl3_res_on;
 };
 #define PBD_MAX_BATCH 64
+
+// ---- host error plumbing shared by pbd_api.cpp, pbd_post.cpp ---------------------------
+#define HIPCHK(h, call)                                                                  \
+  do {                                                                                   \
+    hipError_t e_ = (call);                                                              \
+    if (e_ != hipSuccess) {                                                              \
+      (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);                      \
+      return PBD_ERR_HIP;                                                                \
+    }                                                                                    \
+  } while (0)
+
+static inline int fail(pbd_handle* h, int code, const std::string& msg) {
+  if (h) h->err = msg;
+  return code;
+}
+
+// Kernel launches return nothing: a launch the runtime rejected (wrong current device, a dynamic-LDS request over
+// the opt-in, a bad grid) would otherwise leave the previous frame's buffers in place and detect() would return
+// stale candidates with PBD_OK.  Checked after every stage.
+#define LAUNCHCHK(h, what)                                                               \
+  do {                                                                                   \
+    hipError_t e_ = hipGetLastError();                                                   \
+    if (e_ != hipSuccess) {                                                              \
+      (h)->err = std::string(what) + ": kernel launch failed: " + hipGetErrorString(e_); \
+      return PBD_ERR_HIP;                                                                \
+    }                                                                                    \
+  } while (0)
+// hipGetLastError() is the calling THREAD's sticky last error: an unrelated HIP call of the caller that failed
+// earlier (or one of ours whose result was deliberately ignored) would be reported as this frame's launch failure.
+// Every entry point that launches clears it first, so LAUNCHCHK only ever sees the library's own launches.
+#define CLEAR_STICKY() ((void)hipGetLastError())
+// every ABI entry that launches or copies runs on the handle's device, whatever the caller's current device is
+#define ON_DEVICE(h) do { HIPCHK(h, hipSetDevice((h)->opt.device)); CLEAR_STICKY(); } while (0)
+
+// a captured frame's launches point at the buffers and settings they were captured with: dropped when either changes
+static inline void drop_graph(pbd_handle* h) {
+  if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
+}
+
+// ---- candidate records ---------------------------------------------------------
+inline size_t pbd_rec_bytes(int mp) { return sizeof(pbd_candidate_head) + (size_t)mp * 28; }
+inline const int32_t* pbd_rec_locs(const char* r, int mp) { return (const int32_t*)(r + sizeof(pbd_candidate_head)) + (size_t)mp * 4; }
+// element i of the caller's heads / boxes / locs -> record r, and back; a null array is skipped
+inline void pbd_rec_put(char* r, int mp, const pbd_candidate_head* heads, const int32_t* boxes, const int32_t* locs, size_t i) {
+  if (heads) memcpy(r, heads + i, sizeof(pbd_candidate_head));
+  if (boxes) memcpy(r + sizeof(pbd_candidate_head), boxes + i * mp * 4, sizeof(int32_t) * mp * 4);
+  if (locs) memcpy((char*)pbd_rec_locs(r, mp), locs + i * mp * 3, sizeof(int32_t) * mp * 3);
+}
+inline void pbd_rec_get(const char* r, int mp, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, size_t i) {
+  if (heads) memcpy(heads + i, r, sizeof(pbd_candidate_head));
+  if (boxes) memcpy(boxes + i * mp * 4, r + sizeof(pbd_candidate_head), sizeof(int32_t) * mp * 4);
+  if (locs) memcpy(locs + i * mp * 3, pbd_rec_locs(r, mp), sizeof(int32_t) * mp * 3);
+}
+// stable in-place compaction of the caller's arrays: element i stays when keep[i]; returns how many stayed
+inline int pbd_rec_compact(pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int count, int mp, const uint8_t* keep) {
+  std::vector<char> r(pbd_rec_bytes(mp));
+  int k = 0;
+  for (int i = 0; i < count; ++i)
+    if (keep[i]) { pbd_rec_put(r.data(), mp, heads, boxes, locs, i); pbd_rec_get(r.data(), mp, heads, boxes, locs, k++); }
+  return k;
+}
 
 // ---- scalar helpers: the reference's std:: overloads resolve on T ---------------
 #ifdef __HIPCC__
@@ -243,9 +328,58 @@ int pbd_i_emit(pbd_handle* h, const std::vector<const char*>& recs, pbd_candidat
                int32_t* locs, int capacity, bool ordered = false,    // ordered: the records are in final order already (k_cand_filter)
                std::vector<int>* order_out = nullptr);               // order_out: the record emitted i-th is recs[order[i]]
 int pbd_i_found(const pbd_handle* h);   // records the pending frame left on the host side (filtered: the kept count)
-int pbd_i_filter_host(pbd_handle* h, int mode, float overlap, int im_w, int im_h, pbd_candidate_head* heads, int32_t* boxes,
-                      int32_t* locs, int count, int* kept);   // pbd_candidates_filter without the argument checks
 #define PBD_FIRST_COPY 192   // candidate records fetched (or gathered) together with the count
+
+// ---- the post-stages behind back-tracking (pbd_post.cpp) ----------------------------------
+inline int pbd_i_cand_mode(const pbd_handle* h) { return h->cand_defer ? PBD_CAND_RAW : h->cand_mode; }   // the filter this handle runs
+int pbd_i_post_buffers(pbd_handle* h);   // enqueue_all, outside any capture: the frame's post-stage flags and buffers
+// behind launch_backtrack (into `raw`): depth pruning and / or the candidate filter (mode cm) into the output buffers
+int pbd_i_post_enqueue(pbd_handle* h, int cm, bool zf, char* raw);
+int pbd_i_run_box3d(pbd_handle* h);      // 3-D boxes (+ object clusters) of the frame's final records
+// the collect: each frame's 3-D boxes in the order returned (recs[order[i]]), then the clusters of the frames gathered
+void pbd_i_b3_begin(pbd_handle* h, int nframes);
+void pbd_i_b3_gather(pbd_handle* h, int f, const std::vector<const char*>& recs, const std::vector<int>& order);
+int pbd_i_b3_end(pbd_handle* h);
+// pbd_candidates_filter without the argument checks: `count` packed records filtered in place (kept ones first, final order)
+int pbd_i_filter_host(pbd_handle* h, int mode, float overlap, int im_w, int im_h, char* recs, int count, int* kept);
+int pbd_i_depth_check(pbd_handle* h, int depth_type, long long dstride, int w);   // a depth-carrying frame's depth arguments
+// Frame-plan buffers: counted in frame_bytes, freed on re-plan (pbd_api.cpp free_frame)
+template <typename T>
+int dev_alloc(pbd_handle* h, T** p, size_t n) {
+  void* q = nullptr;
+  hipError_t e = hipMalloc(&q, (n > 1 ? n : 1) * sizeof(T));
+  if (e != hipSuccess) { h->err = std::string("hipMalloc: ") + hipGetErrorString(e); return PBD_ERR_HIP; }
+  h->frame_allocs.push_back(q);
+  h->frame_bytes += (n > 1 ? n : 1) * sizeof(T);
+  *p = (T*)q;
+  return PBD_OK;
+}
+// Model-lifetime buffers (device, or pinned host): counted in model_bytes (counted = false: not part of the footprint), freed by
+// pbd_destroy
+template <typename T>
+int model_alloc(pbd_handle* h, T** p, size_t n, bool pinned = false, bool counted = true) {
+  void* q = nullptr;
+  hipError_t e = pinned ? hipHostMalloc(&q, sizeof(T) * n) : hipMalloc(&q, sizeof(T) * n);
+  if (e != hipSuccess) return fail(h, PBD_ERR_HIP, std::string(pinned ? "hipHostMalloc: " : "hipMalloc: ") + hipGetErrorString(e));
+  h->model_allocs.push_back({q, counted ? sizeof(T) * n : 0, pinned});
+  h->model_bytes += h->model_allocs.back().bytes;
+  *p = (T*)q;
+  return PBD_OK;
+}
+inline void model_free(pbd_handle* h, void* p) {
+  for (auto b = h->model_allocs.begin(); b != h->model_allocs.end(); ++b)
+    if (b->p == p) { if (b->pinned) hipHostFree(p); else hipFree(p); h->model_bytes -= b->bytes; h->model_allocs.erase(b); return; }
+}
+// *p holds `have` units; grown (not kept) to `need` units of n elements (n = 0: need elements)
+template <typename T, typename C>
+int model_grow(pbd_handle* h, T** p, C& have, C need, size_t n = 0) {
+  if (need <= have) return PBD_OK;
+  if (*p) { model_free(h, *p); *p = nullptr; }
+  have = 0;
+  int rc = model_alloc(h, p, n ? n : (size_t)need);
+  if (!rc) have = need;
+  return rc;
+}
 
 // ---- kernel launchers (k_*.hip) ----------------------------------------------
 void launch_resize(const PyrJob* jobs, int njobs, int maxpix, int cn, int sstride, const uint8_t* src, uint8_t* pyr, hipStream_t s);
@@ -300,9 +434,7 @@ void conv_debug_read(unsigned long long* out);
 void launch_nms_map(const float* src, int rows, int cols, int sz, uint8_t* dst, hipStream_t s);
 // candidate sort + painted-box NMS (k_cand.hip): one workgroup per frame
 struct CandFilterArgs {
-  const char* in; const int* in_count; int capacity;   // records (stride bytes each) and their device count
-  size_t stride; int mp;
-  int nlevels;                  // frame of a record = level / nlevels (0: one frame)
+  RecordSet in;                 // (cf unused: one workgroup per frame of nlevels levels)
   const BackLevel* back;        // tie key: root element offset through back[level * ncomp + comp]; null: input position
   const char* rootv_base; int ts, ncomp;
   int nms; double overlap; int im_w, im_h;
@@ -315,11 +447,8 @@ size_t cand_filter_mask_bytes(int w, int h);
 void launch_cand_filter(const CandFilterArgs& a, int nframes, hipStream_t s);
 // depth-consistency pruning (k_zfilter.hip)
 struct ZFilterArgs {
-  const char* in; const int* in_count; int capacity;   // records (stride bytes each) and their device count
-  size_t stride; int mp;
-  int nlevels;                  // frame of a record = level / nlevels (0: one frame)
-  const char* zimg; size_t zpitch, zfbytes;   // depth (element type T) of frame f at zimg + f * zfbytes, rows zpitch bytes apart
-  int zw, zh; unsigned long long has;         // depth image size; frames that carry depth (bit f)
+  RecordSet in;                 // (cf unused)
+  DepthFrames z;
   const int* npart; const int* par; const double* thr;   // [ncomp] nparts; [ncomp * mp] parentid, norm(anchor(0)) * zfactor
   unsigned long long* med;      // [capacity * mp] median keys
   unsigned* large; unsigned* nlarge;          // [capacity * mp] boxes for k_zmed_large, their count
@@ -330,12 +459,8 @@ void launch_zfilter(const ZFilterArgs& a, int ts, hipStream_t s);
 // 3-D boxes (k_box3d.hip)
 #define PBD_B3_MAXTAPS 35
 struct Box3dArgs {
-  const char* recs; size_t stride; int mp;    // records and their device count (count > capacity: nothing to do)
-  const int* count; int capacity;
-  const int* cf; int nframes;                 // non-null: k_cand_filter's counts; frame f's records at [cf[2+nf+f], +cf[2+f])
-  int nlevels;                                // else frame of a record = level / nlevels (0: one frame)
-  const char* zimg; size_t zpitch, zfbytes;   // depth (element type T) of frame f at zimg + f * zfbytes
-  int zw, zh; unsigned long long has;         // depth image size; frames that carry depth (bit f)
+  RecordSet in;
+  DepthFrames z;
   int im_w, im_h;
   pbd_camera cam;
   int ntaps; int tap_off[PBD_B3_MAXTAPS]; float tap[PBD_B3_MAXTAPS];   // dog's nonzero taps: offsets from the centre, values

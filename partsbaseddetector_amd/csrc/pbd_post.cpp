@@ -1,0 +1,715 @@
+// pbd_post.cpp — the stages behind back-tracking: candidate sort + NMS (k_cand.hip), depth-consistency pruning
+// (k_zfilter.hip), 3-D boxes (k_box3d.hip) and object clusters (k_cluster3d.hip).  Their handle buffers, their launches
+// behind k_backtrack, the collect's gathering of their results and their C entry points (pbd_set_*, pbd_get_box3d,
+// pbd_get_cluster3d, pbd_candidates_*).  pbd_api.cpp calls in through the pbd_i_* functions of pbd_internal.hpp.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include "pbd_internal.hpp"
+
+// ---- the scratch of one stand-alone call ---------------------------------------------------------------------------------
+// Device and pinned buffers, freed when it goes out of scope; the first HIP error is kept and every later step is skipped.
+// Copies run on the handle's stream; finish() synchronises it once and reports the error under the caller's prefix.
+namespace {
+struct Scratch {
+  pbd_handle* h;
+  hipError_t e = hipSuccess;
+  std::vector<std::pair<void*, bool>> bufs;   // (buffer, pinned)
+  explicit Scratch(pbd_handle* hd) : h(hd) {}
+  ~Scratch() { for (auto& b : bufs) { if (b.second) hipHostFree(b.first); else hipFree(b.first); } }
+  bool ok() const { return e == hipSuccess; }
+  void chk(hipError_t r) { if (e == hipSuccess) e = r; }
+  template <typename T> T* alloc(size_t n, bool pinned) {   // n = 0: no buffer (nullptr)
+    void* p = nullptr;
+    if (!ok() || n == 0) return nullptr;
+    chk(pinned ? hipHostMalloc(&p, sizeof(T) * n) : hipMalloc(&p, sizeof(T) * n));
+    if (p) bufs.push_back({p, pinned});
+    return (T*)p;
+  }
+  template <typename T> T* dev(size_t n) { return alloc<T>(n, false); }
+  void up(void* d, const void* s, size_t bytes) { if (ok() && bytes) chk(hipMemcpyAsync(d, s, bytes, hipMemcpyHostToDevice, h->stream)); }
+  void up2d(void* d, size_t dpitch, const void* s, size_t spitch, size_t row, size_t rows) {
+    if (ok() && row && rows) chk(hipMemcpy2DAsync(d, dpitch, s, spitch, row, rows, hipMemcpyHostToDevice, h->stream));
+  }
+  void down(void* d, const void* s, size_t bytes) { if (ok() && bytes) chk(hipMemcpyAsync(d, s, bytes, hipMemcpyDeviceToHost, h->stream)); }
+  void zero(void* d, size_t bytes) { if (ok()) chk(hipMemsetAsync(d, 0, bytes, h->stream)); }
+  void launched() { if (ok()) chk(hipGetLastError()); }
+  int finish(const char* what) {
+    chk(hipStreamSynchronize(h->stream));
+    return ok() ? PBD_OK : fail(h, PBD_ERR_HIP, std::string(what) + hipGetErrorString(e));
+  }
+};
+}  // namespace
+
+// the depth image of a stand-alone call: NULL only with an empty size
+static int depth_image_args(pbd_handle* h, const void* depth, int dw, int dh, bool* empty) {
+  if (dw < 0 || dh < 0 || (!depth && dw > 0 && dh > 0)) return fail(h, PBD_ERR_ARG, "depth image: NULL only with an empty size");
+  *empty = !depth || dw == 0 || dh == 0;
+  return PBD_OK;
+}
+
+// ---- candidate sort + NMS (k_cand.hip) -----------------------------------------------------------------------------------
+static CandFilterArgs cand_args(pbd_handle* h, int mode, float overlap, int im_w, int im_h) {
+  CandFilterArgs a{};
+  a.in.capacity = h->opt.max_candidates; a.in.stride = h->cand_stride; a.in.mp = h->max_parts;
+  a.ts = h->ts; a.ncomp = h->md.ncomponents;
+  a.nms = mode == PBD_CAND_SORT_NMS; a.overlap = (double)overlap; a.im_w = im_w; a.im_h = im_h;
+  a.keys = h->d_cf_keys; a.idx = h->d_cf_idx; a.box = h->d_cf_box; a.st = h->d_cf_st;
+  return a;
+}
+// the filter's scratch: model-sized once (first use), the per-frame masks with the frame plan.  Called outside any capture;
+// a (re)allocation drops a captured graph (its launches point at the old buffers).
+static int cand_filter_buffers(pbd_handle* h, bool masks) {
+  const size_t cap = (size_t)h->opt.max_candidates;
+  if (!h->d_cf_keys) {
+    int rc;
+    if ((rc = model_alloc(h, &h->d_cf_keys, 2 * cap)) || (rc = model_alloc(h, &h->d_cf_idx, 2 * cap)) ||
+        (rc = model_alloc(h, &h->d_cf_box, 4 * cap)) || (rc = model_alloc(h, &h->d_cf_st, cap)) ||
+        (rc = model_alloc(h, &h->d_cand_raw, h->cand_stride * cap)) ||
+        (rc = model_alloc(h, &h->d_cf_cnt, 2 + 2 * PBD_MAX_BATCH, false, false)) ||   // (the counts were never part of the footprint)
+        (rc = model_alloc(h, &h->h_cf_cnt, 2 + 2 * PBD_MAX_BATCH, true, false)))
+      return rc;
+    drop_graph(h);
+  }
+  if (masks && h->fw > 0) {
+    const size_t need = cand_filter_mask_bytes(h->fw, h->fh) * h->batch;
+    if (need > h->cf_mask_bytes) {
+      int rc = dev_alloc(h, &h->d_cf_mask, need / sizeof(unsigned long long));
+      if (rc) return rc;
+      h->cf_mask_bytes = need;
+      drop_graph(h);
+    }
+  }
+  return PBD_OK;
+}
+
+// ---- depth-consistency pruning (k_zfilter.hip) ----------------------------------------------------------------------
+// per (component, part): parentid and norm(anchor(0)) * zfactor, the reference's double expression (src/SearchSpacePruning.cpp:82-88):
+// anchor(0) = anchors[defid[first mixture of the part]] (include/Parts.hpp:183), whatever mixture the candidate chose
+static void zf_table(const pbd_handle* h, float zfactor, std::vector<int>& npart, std::vector<int>& par, std::vector<double>& thr) {
+  const int nc = h->md.ncomponents, mp = h->max_parts;
+  npart.assign((size_t)nc, 0); par.assign((size_t)nc * mp, 0); thr.assign((size_t)nc * mp, 0.0);
+  for (int c = 0; c < nc; ++c) {
+    const int f0 = h->part_offset[c], np = h->part_offset[c + 1] - f0;
+    npart[c] = np;
+    for (int p = 1; p < np; ++p) {
+      const int did = h->defid[h->mix_offset[f0 + p]];
+      const double ax = h->anchors[did * 2], ay = h->anchors[did * 2 + 1];
+      par[(size_t)c * mp + p] = h->parentid[f0 + p];
+      thr[(size_t)c * mp + p] = std::sqrt(ax * ax + ay * ay) * (double)zfactor;
+    }
+  }
+}
+// the pruning's device state: allocated on the first depth-carrying frame with the setting on; the table follows zfactor.
+// Called outside any capture (depth-carrying frames run their launches eagerly).
+static int zf_buffers(pbd_handle* h) {
+  int rc = cand_filter_buffers(h, pbd_i_cand_mode(h) == PBD_CAND_SORT_NMS);   // (d_cand_raw: the back-tracking's device output)
+  if (rc) return rc;
+  const size_t cap = (size_t)h->opt.max_candidates, nc = (size_t)h->md.ncomponents, mp = (size_t)h->max_parts;
+  if (!h->d_zf_med) {
+    if ((rc = model_alloc(h, &h->d_zf_npart, nc)) || (rc = model_alloc(h, &h->d_zf_par, nc * mp)) ||
+        (rc = model_alloc(h, &h->d_zf_thr, nc * mp)) || (rc = model_alloc(h, &h->d_zf_med, cap * mp)) ||
+        (rc = model_alloc(h, &h->d_zf_large, cap * mp)) || (rc = model_alloc(h, &h->d_zf_cnt, 2)) ||
+        (rc = model_alloc(h, &h->d_zf_out, h->cand_stride * cap)))
+      return rc;
+    h->zf_thr_factor = std::nanf("");
+  }
+  if (!(h->zf_thr_factor == h->zf_factor)) {
+    std::vector<int> npart, par; std::vector<double> thr;
+    zf_table(h, h->zf_factor, npart, par, thr);
+    HIPCHK(h, hipMemcpy(h->d_zf_npart, npart.data(), sizeof(int) * nc, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->d_zf_par, par.data(), sizeof(int) * nc * mp, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->d_zf_thr, thr.data(), sizeof(double) * nc * mp, hipMemcpyHostToDevice));
+    h->zf_thr_factor = h->zf_factor;
+  }
+  return PBD_OK;
+}
+static int zf_type(const pbd_handle* h) { return h->ts == 8 ? PBD_DEPTH_64F : PBD_DEPTH_32F; }
+// the depth arguments of a depth-carrying frame: element type T, rows of >= w elements, stride a multiple of the element size
+int pbd_i_depth_check(pbd_handle* h, int depth_type, long long dstride, int w) {
+  if (depth_type != zf_type(h))
+    return fail(h, PBD_ERR_UNSUPPORTED, h->ts == 8 ? "depth image: PBD_DEPTH_64F for a double handle (Math::median<T> reads it as T)"
+                                                   : "depth image: PBD_DEPTH_32F for a float handle (Math::median<T> reads it as T)");
+  if (dstride < (long long)w * h->ts || dstride % h->ts) return fail(h, PBD_ERR_ARG, "depth stride: bytes, >= w * element size and a multiple of it");
+  return PBD_OK;
+}
+
+// ---- 3-D boxes (k_box3d.hip) ------------------------------------------------------------------------------------------
+// dog = filter2D(getGaussianKernel(35, 4, CV_32F), (-1, 0, 1) as a column), OpenCV 2.4's arithmetic; its nonzero taps in raster order
+static void b3_taps(Box3dArgs& a) {
+  const int n = 35;
+  float g[35], dog[35];
+  double sum = 0;
+  for (int i = 0; i < n; ++i) {
+    const double x = i - (n - 1) * 0.5;
+    g[i] = (float)std::exp(-0.5 / (4.0 * 4.0) * x * x);
+    sum += g[i];
+  }
+  sum = 1. / sum;
+  for (int i = 0; i < n; ++i) g[i] = (float)(g[i] * sum);
+  for (int i = 0; i < n; ++i) {   // taps -1 and +1 (0 skipped: a zero coefficient), BORDER_REFLECT_101
+    const int im = i - 1 < 0 ? 1 - i : i - 1, ip = i + 1 >= n ? 2 * (n - 1) - (i + 1) : i + 1;
+    float s = 0.0f;
+    s = s + -1.0f * g[im];
+    s = s + 1.0f * g[ip];
+    dog[i] = s;
+  }
+  a.ntaps = 0;
+  for (int i = 0; i < n; ++i)
+    if (dog[i] != 0.0f) { a.tap_off[a.ntaps] = i - (n - 1) / 2; a.tap[a.ntaps] = dog[i]; a.ntaps++; }
+}
+static bool b3_cam_ok(const pbd_camera* c) {
+  return c && std::isfinite(c->fx) && std::isfinite(c->fy) && std::isfinite(c->cx) && std::isfinite(c->cy) && std::isfinite(c->tx) &&
+         std::isfinite(c->ty) && c->fx != 0.0 && c->fy != 0.0;
+}
+static int b3_buffers(pbd_handle* h) {
+  if (h->h_b3) return PBD_OK;
+  const size_t cap = (size_t)h->opt.max_candidates, mp = (size_t)h->max_parts;
+  int rc;
+  if ((rc = model_alloc(h, &h->h_b3, cap, true)) || (rc = model_alloc(h, &h->h_b3c, cap * mp * 3, true))) return rc;
+  return PBD_OK;
+}
+
+// ---- object clusters (k_cluster3d.hip) --------------------------------------------------------------------------------
+// Scratch: one slot of a whole cloud's points per concurrent record, as many slots as fit this budget (at least one, at most one
+// per record and PBD_CL3_MAX_SLOTS), so that no record can fail for lack of scratch.
+#define PBD_CL3_SCRATCH_BUDGET ((size_t)256 << 20)
+#define PBD_CL3_MAX_SLOTS 256
+static int cl3_slots(int pcap, long long records) {
+  const size_t s = PBD_CL3_SCRATCH_BUDGET / cluster3d_slot_bytes(pcap);
+  return (int)std::max<long long>(1, std::min<long long>({(long long)s, records, (long long)PBD_CL3_MAX_SLOTS}));
+}
+static int cl3_buffers(pbd_handle* h) {
+  const size_t cap = (size_t)h->opt.max_candidates;
+  int rc;
+  if (!h->h_cl3 && ((rc = model_alloc(h, &h->h_cl3, cap, true)) || (rc = model_alloc(h, &h->d_cl3_used, 1)))) return rc;
+  const int pcap = h->fw * h->fh;
+  if (pcap > h->cl3_pcap) {
+    const int slots = cl3_slots(pcap, (long long)cap);
+    if ((rc = model_grow(h, &h->d_cl3_scratch, h->cl3_pcap, pcap, cluster3d_slot_bytes(pcap) * slots))) return rc;
+    h->cl3_slots = slots;
+  }
+  // grows when a frame's kept clusters need more (cl3_resolve)
+  return model_grow(h, &h->d_cl3_pool, h->cl3_pool_cap, 4ull * (unsigned long long)pcap);
+}
+// After the launch `a` (synchronised): the records `lst` = (record, frame) pairs in output order -> res[] and their kept clusters'
+// indices one after the other in idx[].  Records whose indices did not fit the pool run again, alone, into a pool grown to what
+// they need (and at least what the launch claimed in all, so that the next launch fits): the handle's own pool, or (s_pool) one of
+// the caller's scratch.
+static int cl3_resolve(pbd_handle* h, Cluster3dArgs a, int src, int slots, Scratch* s_pool, const std::vector<int>& lst,
+                       std::vector<pbd_cluster3d>& res, std::vector<int32_t>& idx) {
+  Scratch s(h);
+  unsigned long long used = 0;
+  s.down(&used, a.pool_used, sizeof(used));
+  int rc = s.finish("cluster3d: ");
+  if (rc) return rc;
+  std::vector<int32_t> first((size_t)std::min(used, a.pool_cap));
+  s.down(first.data(), a.pool, sizeof(int32_t) * first.size());
+  if ((rc = s.finish("cluster3d: "))) return rc;   // (before a growth frees the pool)
+  const size_t n = lst.size() / 2;
+  std::vector<int> spill;
+  std::vector<char> again(n, 0);
+  unsigned long long need = 0;
+  for (size_t k = 0; k < n; ++k) {
+    const Cl3Res& r = a.out[lst[2 * k]];
+    if (r.off < 0 && r.r.size > 0) { spill.push_back(lst[2 * k]); spill.push_back(lst[2 * k + 1]); need += r.r.size; again[k] = 1; }
+  }
+  std::vector<int32_t> second((size_t)need);
+  if (!spill.empty()) {
+    const unsigned long long ncap = std::max(need, used);
+    if (ncap > a.pool_cap) {
+      if (s_pool) { a.pool = s_pool->dev<int>(ncap); s.chk(s_pool->e); a.pool_cap = ncap; }
+      else {
+        if ((rc = model_grow(h, &h->d_cl3_pool, h->cl3_pool_cap, ncap))) return rc;
+        a.pool = h->d_cl3_pool; a.pool_cap = h->cl3_pool_cap;
+      }
+    }
+    int* d_list = s.dev<int>(spill.size());
+    s.up(d_list, spill.data(), sizeof(int) * spill.size());
+    s.zero(a.pool_used, sizeof(unsigned long long));
+    if (s.ok()) {
+      a.list = d_list; a.nlist = (int)(spill.size() / 2);
+      launch_cluster3d(a, src, std::min(slots, a.nlist), h->stream);
+      s.launched();
+    }
+    s.down(second.data(), a.pool, sizeof(int32_t) * need);
+  }
+  if ((rc = s.finish("cluster3d: "))) return rc;
+  res.resize(n);
+  idx.clear();
+  for (size_t k = 0; k < n; ++k) {
+    const Cl3Res& r = a.out[lst[2 * k]];
+    res[k] = r.r;
+    if (r.r.size <= 0) continue;
+    const std::vector<int32_t>& from = again[k] ? second : first;
+    if (r.off < 0 || (unsigned long long)r.off + r.r.size > from.size()) return fail(h, PBD_ERR_HIP, "cluster3d: a record's indices are missing");
+    idx.insert(idx.end(), from.begin() + r.off, from.begin() + r.off + r.r.size);
+  }
+  return PBD_OK;
+}
+
+// ---- behind the back-tracking ---------------------------------------------------------------------------------------------
+int pbd_i_post_buffers(pbd_handle* h) {
+  const int cm = pbd_i_cand_mode(h);
+  if (cm != PBD_CAND_RAW) {
+    int rc = cand_filter_buffers(h, cm == PBD_CAND_SORT_NMS);
+    if (rc) return rc;
+  }
+  h->out_filtered = cm != PBD_CAND_RAW;   // (a replayed graph does not pass through pbd_i_post_enqueue)
+  h->b3_ready = false; h->cl3_ready = false;
+  h->b3_frame = h->zf_frame && h->b3_on;
+  h->cl3_frame = h->b3_frame && h->cl3_on;
+  h->b3_has = h->b3_frame ? h->zf_has : 0;
+  if (!h->zf_frame) return PBD_OK;
+  int rc = h->zf_on ? zf_buffers(h) : PBD_OK;
+  if (!rc && h->b3_frame) rc = b3_buffers(h);
+  if (!rc && h->cl3_frame) rc = cl3_buffers(h);
+  return rc;
+}
+
+int pbd_i_post_enqueue(pbd_handle* h, int cm, bool zf, char* raw) {
+  const bool dev_out = h->d_gsend != nullptr;   // member of an RCCL-gathering group (never a depth-pruning handle)
+  RecordSet in{};
+  in.p = raw; in.stride = h->cand_stride; in.mp = h->max_parts; in.count = h->d_cand_count; in.capacity = h->opt.max_candidates;
+  in.nlevels = h->nlevels;
+  if (zf) {
+    // depth pruning: k_zfilter writes the kept records straight into the pinned host buffers (the count follows by a copy), or into
+    // the buffer k_cand_filter then sorts (and suppresses) as usual
+    HIPCHK(h, hipMemsetAsync(h->d_zf_cnt, 0, sizeof(int) * 2, h->stream));
+    ZFilterArgs z{};
+    z.in = in;
+    z.z.img = h->zf_img; z.z.pitch = h->zf_pitch; z.z.fbytes = h->zf_fbytes; z.z.w = h->fw; z.z.h = h->fh; z.z.has = h->zf_has;
+    z.npart = h->d_zf_npart; z.par = h->d_zf_par; z.thr = h->d_zf_thr;
+    z.med = h->d_zf_med; z.large = h->d_zf_large; z.nlarge = (unsigned*)(h->d_zf_cnt + 1); z.cnt = h->d_zf_cnt;
+    z.out = h->out_filtered ? h->d_zf_out : h->h_cand_out;
+    launch_zfilter(z, h->ts, h->stream);
+    if (!h->out_filtered) HIPCHK(h, hipMemcpyAsync(h->h_cand_count, h->d_zf_cnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    in.p = h->d_zf_out; in.count = h->d_zf_cnt;
+  }
+  if (h->out_filtered) {
+    // Candidate::sort (+ nonMaximaSuppression): k_cand_filter writes the kept records in final order + the per-frame counts — straight
+    // into the pinned host buffers, or, for a member of an RCCL-gathering group, into the device buffer the all-gather block is packed from
+    CandFilterArgs a = cand_args(h, cm, h->cand_overlap, h->fw, h->fh);
+    a.in = in;
+    a.back = h->d_back; a.rootv_base = h->d_rootv; a.gmask = h->d_cf_mask;
+    a.out = dev_out ? h->d_cand_out : h->h_cand_out;
+    a.cnt_out = dev_out ? h->d_cf_cnt : h->h_cf_cnt;
+    launch_cand_filter(a, h->batch, h->stream);
+  }
+  LAUNCHCHK(h, zf ? "argmin + depth filter" : "argmin + candidate filter");
+  h->pending = true;
+  h->out_on_host = !dev_out;
+  if (!dev_out) return PBD_OK;
+  h->first_copy = PBD_FIRST_COPY * h->batch;
+  const int first = std::min(h->first_copy, h->opt.max_candidates);
+  HIPCHK(h, hipMemcpyAsync(h->d_gsend, h->d_cf_cnt + 1, sizeof(int), hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->d_gsend + 16, h->d_cand_out, h->cand_stride * first, hipMemcpyDeviceToDevice, h->stream));
+  return PBD_OK;
+}
+
+// the frame's final records (behind the depth pruning and the candidate filter) -> one box per record slot, pinned
+int pbd_i_run_box3d(pbd_handle* h) {
+  Box3dArgs a{};
+  a.in.stride = h->cand_stride; a.in.mp = h->max_parts; a.in.capacity = h->opt.max_candidates;
+  a.in.nlevels = h->nlevels;
+  if (h->out_filtered) { a.in.p = h->h_cand_out; a.in.cf = h->h_cf_cnt; a.in.count = h->h_cf_cnt; a.in.nframes = h->batch; }
+  else if (h->zf_on) { a.in.p = h->h_cand_out; a.in.count = h->d_zf_cnt; }
+  else { a.in.p = (PBD_ARGMIN_ZERO_COPY && !h->d_gsend) ? h->h_cand_out : h->d_cand_out; a.in.count = h->d_cand_count; }
+  a.z.img = h->zf_img; a.z.pitch = h->zf_pitch; a.z.fbytes = h->zf_fbytes; a.z.w = h->fw; a.z.h = h->fh; a.z.has = h->b3_has;
+  a.im_w = h->fw; a.im_h = h->fh; a.cam = h->b3_cam;
+  b3_taps(a);
+  a.out = h->h_b3; a.centres = h->h_b3c;
+  launch_box3d(a, h->ts, h->stream);
+  LAUNCHCHK(h, "box3d");
+  if (h->cl3_frame) {   // the object clusters of the same records, right behind
+    Cluster3dArgs c{};
+    c.in = a.in; c.z = a.z; c.pstride = h->ts;
+    c.boxes = h->h_b3;
+    c.cam = h->b3_cam; c.tol = h->cl3_tol;
+    c.scratch = h->d_cl3_scratch; c.slot_bytes = cluster3d_slot_bytes(h->cl3_pcap); c.pcap = h->cl3_pcap;
+    c.out = h->h_cl3; c.pool = h->d_cl3_pool; c.pool_cap = h->cl3_pool_cap; c.pool_used = h->d_cl3_used;
+    HIPCHK(h, hipMemsetAsync(h->d_cl3_used, 0, sizeof(unsigned long long), h->stream));
+    launch_cluster3d(c, h->ts, std::min(h->cl3_slots, a.in.capacity), h->stream);
+    LAUNCHCHK(h, "cluster3d");
+    h->cl3_args = c;
+  }
+  return PBD_OK;
+}
+
+// ---- 3-D boxes of a collected frame: the pinned per-slot results, in the order the records are returned ---------------------
+void pbd_i_b3_begin(pbd_handle* h, int nframes) {
+  h->b3_res.assign((size_t)nframes, {}); h->b3_cen.assign((size_t)nframes, {}); h->b3_res_on.assign((size_t)nframes, 0);
+  h->b3_ready = true;
+  h->cl3_ready = false;
+  h->cl3_slot.assign((size_t)nframes, {}); h->cl3_res.assign((size_t)nframes, {}); h->cl3_idx.assign((size_t)nframes, {});
+  h->cl3_res_on.assign((size_t)nframes, 0);
+}
+void pbd_i_b3_gather(pbd_handle* h, int f, const std::vector<const char*>& recs, const std::vector<int>& order) {
+  if (!((h->b3_has >> f) & 1ull)) return;
+  const size_t n = recs.size(), m3 = (size_t)h->max_parts * 3;
+  std::vector<pbd_box3d>& o = h->b3_res[f];
+  std::vector<double>& c = h->b3_cen[f];
+  o.resize(n); c.resize(n * m3);
+  for (size_t i = 0; i < n; ++i) {
+    const size_t slot = (size_t)(recs[order[i]] - h->h_cand_out) / h->cand_stride;
+    o[i] = h->h_b3[slot];
+    memcpy(c.data() + i * m3, h->h_b3c + slot * m3, sizeof(double) * m3);
+    if (h->cl3_frame) h->cl3_slot[f].push_back((int)slot);
+  }
+  h->b3_res_on[f] = 1;
+}
+// the object clusters of the frames pbd_i_b3_gather listed (the collect synchronised the stream)
+int pbd_i_b3_end(pbd_handle* h) {
+  if (!h->cl3_frame) return PBD_OK;
+  std::vector<int> lst;
+  const int nf = (int)h->cl3_slot.size();
+  for (int f = 0; f < nf; ++f)
+    if (h->b3_res_on[f]) for (int s : h->cl3_slot[f]) { lst.push_back(s); lst.push_back(f); }
+  std::vector<pbd_cluster3d> res;
+  std::vector<int32_t> idx;
+  int rc = cl3_resolve(h, h->cl3_args, h->ts, h->cl3_slots, nullptr, lst, res, idx);
+  if (rc) return rc;
+  size_t r0 = 0, i0 = 0;
+  for (int f = 0; f < nf; ++f) {
+    if (!h->b3_res_on[f]) continue;
+    const size_t m = h->cl3_slot[f].size();
+    size_t ni = 0;
+    for (size_t k = 0; k < m; ++k) ni += (size_t)std::max(res[r0 + k].size, 0);
+    h->cl3_res[f].assign(res.begin() + r0, res.begin() + r0 + m);
+    h->cl3_idx[f].assign(idx.begin() + i0, idx.begin() + i0 + ni);
+    h->cl3_res_on[f] = 1;
+    r0 += m; i0 += ni;
+  }
+  h->cl3_ready = true;
+  return PBD_OK;
+}
+
+// ---- the stand-alone device round trip of the candidate filter --------------------------------------------------------------
+int pbd_i_filter_host(pbd_handle* h, int mode, float overlap, int im_w, int im_h, char* recs, int count, int* kept) {
+  if (mode == PBD_CAND_RAW || count == 0) { *kept = count; return PBD_OK; }
+  ON_DEVICE(h);
+  const size_t st = h->cand_stride, n = (size_t)count, mask = cand_filter_mask_bytes(im_w, im_h);
+  Scratch s(h);
+  char* d_in = s.dev<char>(st * n);
+  char* d_out = s.dev<char>(st * n);
+  int* d_cnt = s.dev<int>(5);
+  CandFilterArgs a = cand_args(h, mode, overlap, im_w, im_h);
+  a.in.p = d_in; a.in.count = d_cnt; a.in.capacity = count; a.in.nlevels = 0; a.back = nullptr;
+  a.keys = s.dev<unsigned long long>(2 * n); a.idx = s.dev<unsigned>(2 * n); a.box = s.dev<int>(4 * n); a.st = s.dev<uint8_t>(n);
+  a.gmask = mode == PBD_CAND_SORT_NMS ? s.dev<unsigned long long>(mask / 8) : nullptr;
+  a.out = d_out; a.cnt_out = d_cnt + 1;
+  s.up(d_in, recs, st * n);
+  s.up(d_cnt, &count, sizeof(int));
+  if (s.ok()) {
+    launch_cand_filter(a, 1, h->stream);
+    s.launched();
+  }
+  int cnt[4] = {0, 0, 0, 0};
+  s.down(cnt, d_cnt + 1, sizeof(cnt));
+  s.down(recs, d_out, st * n);
+  int rc = s.finish("candidate filter: ");
+  if (rc) return rc;
+  *kept = cnt[1];
+  return PBD_OK;
+}
+
+// ---- C ABI ------------------------------------------------------------------------------------------------------------------
+#pragma GCC visibility push(default)
+extern "C" {
+
+// ---- host-side post-processing (include/Candidate.hpp:91-99, 277-304) --------
+int pbd_candidates_sort(pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int count, int mp) {
+  if (!heads || count < 0 || mp <= 0) return PBD_ERR_ARG;
+  std::vector<int> order(count);
+  for (int i = 0; i < count; ++i) order[i] = i;
+  // Candidate::descending; stable, so equal scores keep detect() order (std::sort leaves it unspecified)
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return heads[a].score > heads[b].score; });
+  const size_t st = pbd_rec_bytes(mp);
+  std::vector<char> rec(st * count);
+  for (int i = 0; i < count; ++i) pbd_rec_put(rec.data() + st * i, mp, heads, boxes, locs, i);
+  for (int i = 0; i < count; ++i) pbd_rec_get(rec.data() + st * order[i], mp, heads, boxes, locs, i);
+  return PBD_OK;
+}
+
+int pbd_candidates_nms(pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int count, int mp, int im_w, int im_h,
+                       float overlap, int* kept) {
+  if (!heads || !boxes || !kept || count < 0 || mp <= 0 || im_w <= 0 || im_h <= 0) return PBD_ERR_ARG;
+  std::vector<uint8_t> scratch((size_t)im_w * im_h, 0), keep((size_t)count, 0);
+  for (int n = 0; n < count; ++n) {
+    const int32_t* b = boxes + (size_t)n * mp * 4;
+    int x = b[0], y = b[1], bw = b[2], bh = b[3];  // Candidate::boundingBox(): union of the part rects
+    for (int p = 0; p < heads[n].nparts; ++p) {
+      const int32_t* q = b + p * 4;
+      const int x1 = std::min(x, q[0]), y1 = std::min(y, q[1]);
+      bw = std::max(x + bw, q[0] + q[2]) - x1;
+      bh = std::max(y + bh, q[1] + q[3]) - y1;
+      x = x1; y = y1;
+    }
+    int ix1 = std::max(x, 0), iy1 = std::max(y, 0);  // & bounds
+    int iw = std::min(x + bw, im_w) - ix1, ih = std::min(y + bh, im_h) - iy1;
+    if (iw <= 0 || ih <= 0) ix1 = iy1 = iw = ih = 0;
+    double sum = 0;
+    for (int yy = iy1; yy < iy1 + ih; ++yy)
+      for (int xx = ix1; xx < ix1 + iw; ++xx) sum += scratch[(size_t)yy * im_w + xx];
+    if (sum / (double)(iw * ih) > (double)overlap) continue;  // :296
+    for (int yy = iy1; yy < iy1 + ih; ++yy) memset(&scratch[(size_t)yy * im_w + ix1], 1, iw);
+    keep[n] = 1;
+  }
+  *kept = pbd_rec_compact(heads, boxes, locs, count, mp, keep.data());
+  return PBD_OK;
+}
+
+// ---- the post-step on the device (k_cand.hip) -------------------------------------
+static bool cand_mode_ok(int mode, float overlap) {
+  return (mode == PBD_CAND_RAW || mode == PBD_CAND_SORT || mode == PBD_CAND_SORT_NMS) && std::isfinite(overlap);
+}
+int pbd_set_candidate_filter(pbd_handle* h, int mode, float overlap) {
+  if (!h) return PBD_ERR_ARG;
+  if (!cand_mode_ok(mode, overlap)) return fail(h, PBD_ERR_ARG, "candidate filter: mode PBD_CAND_RAW / _SORT / _SORT_NMS, finite overlap");
+  if (h->in_group) return fail(h, PBD_ERR_STATE, "handle belongs to a pbd_group: set the filter on the group");
+  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if ((mode != h->cand_mode || overlap != h->cand_overlap) && h->gexec) {   // the filter's launch (or its absence) is part of a captured graph
+    ON_DEVICE(h);
+    drop_graph(h);
+  }
+  h->cand_mode = mode;
+  h->cand_overlap = overlap;
+  return PBD_OK;
+}
+
+int pbd_candidates_filter(pbd_handle* h, int mode, float overlap, int im_w, int im_h, pbd_candidate_head* heads, int32_t* boxes,
+                          int32_t* locs, int count, int* kept) {
+  if (!h) return PBD_ERR_ARG;
+  if (!cand_mode_ok(mode, overlap)) return fail(h, PBD_ERR_ARG, "candidate filter: mode PBD_CAND_RAW / _SORT / _SORT_NMS, finite overlap");
+  if (!kept || count < 0 || (count > 0 && !heads)) return fail(h, PBD_ERR_ARG, "heads / kept / count");
+  if (mode == PBD_CAND_SORT_NMS && (!boxes || im_w <= 0 || im_h <= 0)) return fail(h, PBD_ERR_ARG, "NMS needs boxes and the image size");
+  for (int i = 0; i < count; ++i) {
+    if (!std::isfinite(heads[i].score)) return fail(h, PBD_ERR_ARG, "non-finite score: its order is undefined");
+    if (mode == PBD_CAND_SORT_NMS && (heads[i].nparts < 0 || heads[i].nparts > h->max_parts)) return fail(h, PBD_ERR_ARG, "nparts outside 0..max_parts");
+  }
+  if (mode == PBD_CAND_RAW || count == 0) { *kept = count; return PBD_OK; }
+  const int mp = h->max_parts;
+  const size_t st = h->cand_stride;
+  std::vector<char> rec(st * count, 0);
+  for (int i = 0; i < count; ++i) pbd_rec_put(rec.data() + st * i, mp, heads, boxes, locs, i);
+  int k = 0, rc = pbd_i_filter_host(h, mode, overlap, im_w, im_h, rec.data(), count, &k);
+  if (rc) return rc;
+  for (int i = 0; i < k; ++i) pbd_rec_get(rec.data() + st * i, mp, heads, boxes, locs, i);
+  *kept = k;
+  return PBD_OK;
+}
+
+// ---- depth-consistency pruning (k_zfilter.hip) --------------------------------------------------------------------
+int pbd_set_depth_filter(pbd_handle* h, int on, float zfactor) {
+  if (!h) return PBD_ERR_ARG;
+  if (!std::isfinite(zfactor)) return fail(h, PBD_ERR_ARG, "depth filter: zfactor must be finite");
+  if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "depth filter: pbd_group members are not supported (detect through a handle of its own)");
+  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  h->zf_on = on != 0;      // (depth-carrying frames never replay a captured graph: nothing captured depends on the setting)
+  h->zf_factor = zfactor;
+  return PBD_OK;
+}
+
+int pbd_candidates_depth_filter(pbd_handle* h, float zfactor, const void* depth, int depth_type, int dw, int dh, int dstride,
+                                pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int count, int* kept) {
+  if (!h) return PBD_ERR_ARG;
+  if (!std::isfinite(zfactor)) return fail(h, PBD_ERR_ARG, "depth filter: zfactor must be finite");
+  if (!kept || count < 0 || (count > 0 && (!heads || !boxes))) return fail(h, PBD_ERR_ARG, "heads / boxes / kept / count");
+  bool empty;
+  int rc = depth_image_args(h, depth, dw, dh, &empty);
+  if (rc) return rc;
+  if (depth_type != zf_type(h) || !empty) { if ((rc = pbd_i_depth_check(h, depth_type, dstride, dw))) return rc; }   // (the handle's type only)
+  for (int i = 0; i < count; ++i) {
+    const int c = heads[i].component;
+    if (c < 0 || c >= h->md.ncomponents) return fail(h, PBD_ERR_ARG, "component out of range");
+    if (heads[i].nparts != h->part_offset[c + 1] - h->part_offset[c]) return fail(h, PBD_ERR_ARG, "nparts differs from the model's component");
+  }
+  if (count == 0) { *kept = 0; return PBD_OK; }
+  ON_DEVICE(h);
+  const int mp = h->max_parts, nc = h->md.ncomponents;
+  const size_t st = h->cand_stride, n = (size_t)count, row = (size_t)dw * h->ts;
+  std::vector<char> rec(st * n, 0);
+  for (size_t i = 0; i < n; ++i) pbd_rec_put(rec.data() + st * i, mp, heads, boxes, nullptr, i);
+  std::vector<int> npart, par; std::vector<double> thr;
+  zf_table(h, zfactor, npart, par, thr);
+  const int cnt3[3] = {count, 0, 0};
+  Scratch s(h);
+  ZFilterArgs z{};
+  z.in.p = s.dev<char>(st * n); z.in.capacity = count; z.in.stride = st; z.in.mp = mp; z.in.nlevels = 0;
+  z.z.img = empty ? nullptr : s.dev<char>(row * dh); z.z.pitch = row; z.z.fbytes = 0; z.z.w = empty ? 0 : dw; z.z.h = empty ? 0 : dh; z.z.has = 1;
+  int* d_cnt = s.dev<int>(3); int* d_np = s.dev<int>(nc); int* d_par = s.dev<int>((size_t)nc * mp); double* d_thr = s.dev<double>((size_t)nc * mp);
+  z.in.count = d_cnt; z.cnt = d_cnt + 1; z.nlarge = (unsigned*)(d_cnt + 2);
+  z.npart = d_np; z.par = d_par; z.thr = d_thr;
+  z.med = s.dev<unsigned long long>(n * mp); z.large = s.dev<unsigned>(n * mp); z.flags = s.dev<uint8_t>(n);
+  s.up((void*)z.in.p, rec.data(), st * n);
+  s.up(d_cnt, cnt3, sizeof(cnt3));
+  s.up(d_np, npart.data(), sizeof(int) * nc);
+  s.up(d_par, par.data(), sizeof(int) * nc * mp);
+  s.up(d_thr, thr.data(), sizeof(double) * nc * mp);
+  if (!empty) s.up2d((void*)z.z.img, row, depth, dstride, row, dh);
+  if (s.ok()) {
+    launch_zfilter(z, h->ts, h->stream);
+    s.launched();
+  }
+  std::vector<uint8_t> flags(n, 0);
+  s.down(flags.data(), z.flags, n);
+  if ((rc = s.finish("depth filter: "))) return rc;
+  *kept = pbd_rec_compact(heads, boxes, locs, count, mp, flags.data());
+  return PBD_OK;
+}
+
+// ---- 3-D boxes (k_box3d.hip) --------------------------------------------------------------------------------------------
+
+int pbd_set_box3d(pbd_handle* h, int on, const pbd_camera* cam) {
+  if (!h) return PBD_ERR_ARG;
+  if (on && !b3_cam_ok(cam)) return fail(h, PBD_ERR_ARG, "box3d: a camera with finite intrinsics and nonzero fx, fy");
+  if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "box3d: pbd_group members are not supported (detect through a handle of its own)");
+  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  h->b3_on = on != 0;
+  if (on) h->b3_cam = *cam;
+  return PBD_OK;
+}
+
+int pbd_get_box3d(pbd_handle* h, int frame, pbd_box3d* out, double* centres, int capacity, int* count) {
+  if (!h || !count || capacity < 0 || (capacity > 0 && !out)) return PBD_ERR_ARG;
+  if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "box3d: pbd_group members are not supported");
+  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (!h->b3_ready || frame < 0 || frame >= (int)h->b3_res_on.size() || !h->b3_res_on[frame])
+    return fail(h, PBD_ERR_STATE, "box3d: the last frame did not compute 3-D boxes for this frame (plain entry point, setting off, or no depth)");
+  const std::vector<pbd_box3d>& r = h->b3_res[frame];
+  const int n = (int)r.size();
+  *count = n;
+  if (n > capacity) return fail(h, PBD_ERR_CAPACITY, "output capacity too small");
+  std::copy(r.begin(), r.end(), out);
+  if (centres) std::copy(h->b3_cen[frame].begin(), h->b3_cen[frame].end(), centres);
+  return PBD_OK;
+}
+
+int pbd_candidates_box3d(pbd_handle* h, const pbd_camera* cam, const void* depth, int depth_type, int dw, int dh, int dstride,
+                         int im_w, int im_h, const pbd_candidate_head* heads, const int32_t* boxes, int count, pbd_box3d* out,
+                         double* centres) {
+  if (!h) return PBD_ERR_ARG;
+  if (!b3_cam_ok(cam)) return fail(h, PBD_ERR_ARG, "box3d: a camera with finite intrinsics and nonzero fx, fy");
+  if (im_w <= 0 || im_h <= 0) return fail(h, PBD_ERR_ARG, "box3d: im_w, im_h > 0");
+  if (count < 0 || (count > 0 && (!heads || !boxes || !out))) return fail(h, PBD_ERR_ARG, "heads / boxes / out / count");
+  bool empty;
+  int rc = depth_image_args(h, depth, dw, dh, &empty);
+  if (rc) return rc;
+  if (depth_type != PBD_DEPTH_32F && depth_type != PBD_DEPTH_64F)   // (either type, whatever the handle's)
+    return fail(h, PBD_ERR_UNSUPPORTED, "box3d: depth PBD_DEPTH_32F or PBD_DEPTH_64F (Mat_<float> reads it)");
+  const int esz = depth_type == PBD_DEPTH_64F ? 8 : 4;
+  if (!empty && (dstride < (long long)dw * esz || dstride % esz)) return fail(h, PBD_ERR_ARG, "depth stride: bytes, >= dw * element size and a multiple of it");
+  const int mp = h->max_parts;
+  for (int i = 0; i < count; ++i)
+    if (heads[i].nparts < 1 || heads[i].nparts > mp) return fail(h, PBD_ERR_ARG, "nparts outside 1 .. max_parts");
+  if (count == 0) return PBD_OK;
+  ON_DEVICE(h);
+  const size_t st = h->cand_stride, n = (size_t)count, row = (size_t)dw * esz;
+  std::vector<char> rec(st * n, 0);
+  for (size_t i = 0; i < n; ++i) pbd_rec_put(rec.data() + st * i, mp, heads, boxes, nullptr, i);
+  Scratch s(h);
+  Box3dArgs a{};
+  a.in.p = s.dev<char>(st * n); a.in.stride = st; a.in.mp = mp; a.in.count = s.dev<int>(1); a.in.capacity = count; a.in.nlevels = 0;
+  a.z.img = empty ? nullptr : s.dev<char>(row * dh); a.z.pitch = row; a.z.fbytes = 0; a.z.w = empty ? 0 : dw; a.z.h = empty ? 0 : dh; a.z.has = 1;
+  a.im_w = im_w; a.im_h = im_h; a.cam = *cam;
+  b3_taps(a);
+  a.out = s.dev<pbd_box3d>(n); a.centres = centres ? s.dev<double>(n * mp * 3) : nullptr;
+  s.up((void*)a.in.p, rec.data(), st * n);
+  s.up((void*)a.in.count, &count, sizeof(int));
+  if (!empty) s.up2d((void*)a.z.img, row, depth, dstride, row, dh);
+  if (s.ok()) {
+    launch_box3d(a, esz, h->stream);
+    s.launched();
+  }
+  s.down(out, a.out, sizeof(pbd_box3d) * n);
+  if (centres) s.down(centres, a.centres, sizeof(double) * n * mp * 3);
+  return s.finish("box3d: ");
+}
+
+// ---- object clusters (k_cluster3d.hip) ----------------------------------------------------------------------------------
+static bool cl3_tol_ok(float t) { return std::isfinite(t) && t > 0.f; }
+
+int pbd_set_cluster3d(pbd_handle* h, int on, float tolerance) {
+  if (!h) return PBD_ERR_ARG;
+  if (on && !cl3_tol_ok(tolerance)) return fail(h, PBD_ERR_ARG, "cluster3d: a finite tolerance > 0");
+  if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "cluster3d: pbd_group members are not supported (detect through a handle of its own)");
+  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  h->cl3_on = on != 0;
+  if (on) h->cl3_tol = tolerance;
+  return PBD_OK;
+}
+
+// results + their indices (the exclusive prefix sum of size) -> the caller's arrays
+static int cl3_copy_out(pbd_handle* h, const std::vector<int32_t>& idx, int32_t* indices, int idx_capacity, int* idx_total) {
+  if (idx_total) *idx_total = (int)idx.size();
+  if (!indices) return PBD_OK;
+  if ((long long)idx.size() > (long long)idx_capacity) return fail(h, PBD_ERR_CAPACITY, "cluster3d: index capacity too small");
+  std::copy(idx.begin(), idx.end(), indices);
+  return PBD_OK;
+}
+
+int pbd_get_cluster3d(pbd_handle* h, int frame, pbd_cluster3d* out, int capacity, int* count, int32_t* indices, int idx_capacity,
+                      int* idx_total) {
+  if (!h || !count || capacity < 0 || (capacity > 0 && !out) || (indices && (idx_capacity < 0 || !idx_total))) return PBD_ERR_ARG;
+  if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "cluster3d: pbd_group members are not supported");
+  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (!h->cl3_ready || frame < 0 || frame >= (int)h->cl3_res_on.size() || !h->cl3_res_on[frame])
+    return fail(h, PBD_ERR_STATE, "cluster3d: the last frame did not compute object clusters for this frame (plain entry point, "
+                                  "3-D boxes or clusters off, or no depth)");
+  const std::vector<pbd_cluster3d>& r = h->cl3_res[frame];
+  const int n = (int)r.size();
+  *count = n;
+  if (idx_total) *idx_total = (int)h->cl3_idx[frame].size();
+  if (n > capacity) return fail(h, PBD_ERR_CAPACITY, "output capacity too small");
+  std::copy(r.begin(), r.end(), out);
+  return cl3_copy_out(h, h->cl3_idx[frame], indices, idx_capacity, idx_total);
+}
+
+int pbd_candidates_cluster3d(pbd_handle* h, const void* cloud, int cw, int ch, int point_stride, int row_stride,
+                             const pbd_box3d* boxes, int count, float tolerance, pbd_cluster3d* out, int32_t* indices,
+                             int idx_capacity, int* idx_total) {
+  if (!h) return PBD_ERR_ARG;
+  if (!cl3_tol_ok(tolerance)) return fail(h, PBD_ERR_ARG, "cluster3d: a finite tolerance > 0");
+  if (cw < 0 || ch < 0 || (long long)cw * ch > (1ll << 30)) return fail(h, PBD_ERR_ARG, "cluster3d: cloud size");
+  const long long npts = (long long)cw * ch;
+  if (point_stride < 12 || point_stride % 4) return fail(h, PBD_ERR_ARG, "cluster3d: point stride: bytes, >= 12 and a multiple of 4");
+  if (npts > 0 && (!cloud || row_stride % 4 || (long long)row_stride < (long long)(cw - 1) * point_stride + 12))
+    return fail(h, PBD_ERR_ARG, "cluster3d: a cloud (NULL only when empty), row stride: bytes, >= (cw - 1) * point stride + 12, a multiple of 4");
+  if (count < 0 || (count > 0 && (!boxes || !out))) return fail(h, PBD_ERR_ARG, "boxes / out / count");
+  if (indices && (idx_capacity < 0 || !idx_total)) return fail(h, PBD_ERR_ARG, "indices: idx_capacity >= 0 and idx_total");
+  if (count == 0) return cl3_copy_out(h, {}, indices, idx_capacity, idx_total);
+  ON_DEVICE(h);
+  const int pcap = (int)std::max<long long>(npts, 1);
+  const int slots = cl3_slots(pcap, count);
+  const size_t bytes = npts ? (size_t)(ch - 1) * row_stride + (size_t)(cw - 1) * point_stride + 12 : 0, n = (size_t)count;
+  unsigned long long pool_cap = std::min<unsigned long long>((unsigned long long)count * (unsigned long long)npts, 4ull * (unsigned long long)pcap);
+  pool_cap = std::max<unsigned long long>(pool_cap, 1);
+  Scratch s(h);
+  Cluster3dArgs a{};
+  a.in.count = s.dev<int>(1); a.in.capacity = count;
+  a.z.img = s.dev<char>(bytes); a.z.pitch = (size_t)row_stride; a.z.w = cw; a.z.h = ch; a.z.has = 1; a.pstride = (size_t)point_stride;
+  pbd_box3d* d_box = s.dev<pbd_box3d>(n);
+  a.boxes = d_box; a.tol = tolerance;
+  a.scratch = s.dev<char>(cluster3d_slot_bytes(pcap) * slots); a.slot_bytes = cluster3d_slot_bytes(pcap); a.pcap = pcap;
+  a.out = s.alloc<Cl3Res>(n, true); a.pool = s.dev<int>(pool_cap); a.pool_cap = pool_cap; a.pool_used = s.dev<unsigned long long>(1);
+  s.up((void*)a.z.img, cloud, bytes);
+  s.up((void*)a.in.count, &count, sizeof(int));
+  s.up(d_box, boxes, sizeof(pbd_box3d) * n);
+  s.zero(a.pool_used, sizeof(unsigned long long));
+  if (s.ok()) {
+    launch_cluster3d(a, 0, slots, h->stream);
+    s.launched();
+  }
+  int rc = s.finish("cluster3d: ");
+  if (rc) return rc;
+  std::vector<int> lst(2 * n);
+  for (size_t i = 0; i < n; ++i) { lst[2 * i] = (int)i; lst[2 * i + 1] = 0; }
+  std::vector<pbd_cluster3d> res;
+  std::vector<int32_t> idx;
+  if ((rc = cl3_resolve(h, a, 0, slots, &s, lst, res, idx))) return rc;
+  std::copy(res.begin(), res.end(), out);
+  return cl3_copy_out(h, idx, indices, idx_capacity, idx_total);
+}
+
+}  // extern "C"
+#pragma GCC visibility pop
