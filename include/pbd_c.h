@@ -611,6 +611,11 @@ int pbd_dp_timer(pbd_handle* h, int reset, double* avg_ms, int* nframes);
  * debug: 100 MHz wall-clock stamps of block 0 of the last distance-transform launch at its six
  * phase boundaries (setup, line load, envelope scan, read-out, pointer store, end)            */
 int pbd_debug_dt_stamps(unsigned long long out[8]);
+/* debug: how often k_dt_pass took its rare paths since the last call (the call resets them): [0] blocks that entered validation
+ * rounds, [1] rounds run (summed over blocks), [2] the most rounds in one block, [3] stitches redone, [4] boundaries judged stale
+ * only because their left neighbour's F moved, [5] lines flagged in a local scan (suspect quotient), [6] lines flagged in a
+ * speculative or redone stitch (lost invariant / suspect quotient), [7] lines redone sequentially                            */
+int pbd_debug_dt_counters(unsigned long long out[8]);
 /* same for the HOG kernel: tile staging, gradient, histogram, energy+normalisers, features */
 int pbd_debug_hog_stamps(unsigned long long out[8]);
 /* same for the MFMA filter bank: tile staging, K loop, barrier, epilogue                    */

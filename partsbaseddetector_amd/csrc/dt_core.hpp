@@ -60,6 +60,9 @@ DT_HD unsigned long long dt_bits(double d) { unsigned long long u; memcpy(&u, &d
 #ifndef DT_COUNT_ITER
 #define DT_COUNT_ITER() ((void)0)   // host-side statistics hook (tests/tools)
 #endif
+#ifndef DT_NOTE_STITCH_FLAG
+#define DT_NOTE_STITCH_FLAG(lost, suspect) ((void)0)   // host-side hook (tests/tools): why a stitch flags its line — a lost invariant, a suspect quotient
+#endif
 template <typename T> struct alignas(2 * sizeof(T)) DtPair { T x, y; };
 // Sticky per-lane "suspect quotient" state: an unsigned MINIMUM accumulated once per intersection (zero = flagged): the two
 // tests of dt_isect are arithmetic zero-tests folded into one three-operand minimum per step — no compares, no mask
@@ -257,6 +260,7 @@ DT_HD bool dt_stitch1(DtPair<T>* __restrict__ YZ, IT* __restrict__ B, const doub
   B[f] = (IT)fb;
   f_out = f;
   dmin_out = dmin;
+  DT_NOTE_STITCH_FLAG(bad, DT_SUSPECT_MINE(suspect));
   return bad || DT_SUSPECT_MINE(suspect);
 }
 

@@ -35,7 +35,15 @@
 // debug: per-phase timestamps (100 MHz wall clock) of block 0 of the last k_dt_pass launch
 #ifdef PBD_PROBES
 __device__ unsigned long long pbd_dt_dbg[8];
-#define DT_COUNT_REDO() atomicAdd(&pbd_dt_dbg[7], 1ull)
+// path counters of k_dt_pass since the last read (pbd_debug_dt_counters): [0] blocks that entered validation rounds, [1] rounds run, summed over
+// blocks, [2] the most rounds in one block, [3] stitches redone, [4] boundaries judged stale only because their neighbour's F moved (dmin > F_spec,
+// dmin <= F_new), [5] lines flagged in a local scan, [6] lines flagged in a speculative or redone stitch, [7] lines redone sequentially
+__device__ unsigned long long pbd_dt_cnt[8];
+#define DT_COUNT_REDO() do { atomicAdd(&pbd_dt_dbg[7], 1ull); atomicAdd(&pbd_dt_cnt[7], 1ull); } while (0)
+#define DT_COUNT(i, c) do { if (c) atomicAdd(&pbd_dt_cnt[i], 1ull); } while (0)
+#define DT_COUNT_ROUNDS(n) do { if (threadIdx.x == 0) { atomicAdd(&pbd_dt_cnt[1], (unsigned long long)(n)); \
+    atomicMax(&pbd_dt_cnt[2], (unsigned long long)(n)); } } while (0)
+#define DT_PROBE_ONLY(...) __VA_ARGS__
 // block trace: (start, end) wall clock and hardware id of every block of the first 40 launches since the last read
 #define DT_TRACE_L 40
 #define DT_TRACE_B 4096
@@ -60,11 +68,20 @@ void dt_debug_read(unsigned long long* out) {
   const unsigned long long z = 0;
   hipMemcpyToSymbol(HIP_SYMBOL(pbd_dt_dbg), &z, sizeof(z), 7 * sizeof(unsigned long long));   // [7]: lines redone sequentially since the last read
 }
+void dt_debug_counters(unsigned long long* out) {
+  hipMemcpyFromSymbol(out, HIP_SYMBOL(pbd_dt_cnt), sizeof(unsigned long long) * 8);
+  const unsigned long long z[8] = {};
+  hipMemcpyToSymbol(HIP_SYMBOL(pbd_dt_cnt), z, sizeof(z));
+}
 #else
 #define DT_STAMP(i) do { } while (0)
 #define DT_COUNT_REDO() do { } while (0)
+#define DT_COUNT(i, c) do { } while (0)
+#define DT_COUNT_ROUNDS(n) do { } while (0)
+#define DT_PROBE_ONLY(...)
 #define DT_TRACE(k) do { } while (0)
 void dt_debug_read(unsigned long long* out) { for (int i = 0; i < 8; ++i) out[i] = 0; }
+void dt_debug_counters(unsigned long long* out) { for (int i = 0; i < 8; ++i) out[i] = 0; }
 #endif
 
 // ---- message fold (fold mode) -------------------------------------------------------------------------------
@@ -203,6 +220,7 @@ __device__ __forceinline__ void dt_block(char* smem, const DtTask& t, const DtGr
   int* SEG = FIX + lpb;                        // [P + 1 <= 65] start of every segment (len and P are uniform over the block), [DT_SEGS - 2..]: {0, len}
   int* ANY = SEG + DT_SEGS - 6;                // [2] a line has a stale stitch (even / odd validation round)
   int* NFLAG = SEG + DT_SEGS - 4;              // [1] a line of the block is flagged for the sequential redo
+  static_assert(DT_SEGS - 6 > 64, "ANY / NFLAG must lie beyond the P + 1 <= 65 segment starts");
   T* ZLO = (T*)(SEG + DT_SEGS);                // [NT] per lane (p * lpb + line): z of the segment's lowest surviving element — what the read-out needs; while
                                                // validation rounds run (rare path): that element's LOCAL z, before the stitch patched it (the stitch's lane keeps
                                                // it in a register and stores it only if the block has a stale stitch: 4 B per lane less LDS than a table of its
@@ -375,6 +393,7 @@ __device__ __forceinline__ void dt_block(char* smem, const DtTask& t, const DtGr
   }
   __syncthreads();
   DT_STAMP(3);
+  DT_PROBE_ONLY(const bool scan_flagged = mine && p == 0 && FLAG[line]; DT_COUNT(5, scan_flagged);)
   // ---- stitch the segments into the sequential result: every boundary by its own lane, concurrently ----
   T zs_mine = (T)0;                                // the local z of this lane's F (a redo restores it: dt_stitch_redo)
   const bool stitched = mine && p >= 1 && p < P && !FLAG[line];
@@ -408,6 +427,7 @@ __device__ __forceinline__ void dt_block(char* smem, const DtTask& t, const DtGr
     __syncthreads();
     DT_STAMP(6);
     if (ANY[0]) {                                  // (block-uniform; rare)
+      DT_COUNT(0, lane == 0);
       if (stitched) ZLO[lane] = zs_mine;           // the table holds the stitches' local z while the rounds run (the segments' entries are published again below)
       __syncthreads();
       for (int round = 0;; ++round) {
@@ -421,14 +441,16 @@ __device__ __forceinline__ void dt_block(char* smem, const DtTask& t, const DtGr
                               : dt_stitch_redo<EX, false, T, IT>(YZl, Bl, RDX, mp.r2a, SEG[ps], SEG[ps + 1], mp.a, mp.b, (int)FT[ls], f, zs, bs);
           FT[ls] = (IT)f; BSAVE[ls] = (IT)bs;
           DMIN[ls] = (IT)SEG[ps];                  // final: never stale again (every F to its left lies below its segment) — its saved z is not needed again
+          DT_COUNT(3, true);
           if (bad) { FLAG[line] = 1; *NFLAG = 1; }
         }
         if (lane < lpb) FIXn[lane] = 0x7fffffff;   // the next round's tables (last read a round ago)
         if (lane == 0) ANY[(round + 1) & 1] = 0;
         __syncthreads();
         if (cand && !FLAG[line] && dt_stitch_stale((int)DMIN[lane], fspec_prev, (int)FT[lane - lpb])) { atomicMin(&FIXn[line], p); ANY[(round + 1) & 1] = 1; }
+        DT_COUNT(4, cand && !FLAG[line] && (int)DMIN[lane] > fspec_prev && (int)DMIN[lane] <= (int)FT[lane - lpb]);
         __syncthreads();
-        if (!ANY[(round + 1) & 1]) break;
+        if (!ANY[(round + 1) & 1]) { DT_COUNT_ROUNDS(round + 1); break; }
       }
       if (mine && p < P && !FLAG[line]) {          // the segments' entries once more (a redo moves F)
         const int f = (int)FT[lane];
@@ -443,6 +465,7 @@ __device__ __forceinline__ void dt_block(char* smem, const DtTask& t, const DtGr
   if (*NFLAG) {                                    // (block-uniform)
     if (mine && p == 0 && FLAG[line]) {
       DT_COUNT_REDO();
+      DT_COUNT(6, !scan_flagged);
       dt_seg_scan<true, false, T, IT>(YZl, Bl, RDX, mp.r2a, 0, len, mp.a, mp.b);
       BELOW[line] = Bl[0];
       ZLO[line] = YZl[0].y;

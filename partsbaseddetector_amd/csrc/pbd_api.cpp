@@ -1572,6 +1572,7 @@ int pbd_get_work(const pbd_handle* h, double work[6]) {
 extern "C" int pbd_debug_dt_trace(unsigned long long* t, unsigned* hw, int* nlaunch) { return dt_debug_trace(t, hw, nlaunch); }
 #endif
 int pbd_debug_dt_stamps(unsigned long long* out) { if (!out) return PBD_ERR_ARG; dt_debug_read(out); return PROBE_RC; }
+int pbd_debug_dt_counters(unsigned long long* out) { if (!out) return PBD_ERR_ARG; dt_debug_counters(out); return PROBE_RC; }
 int pbd_debug_hog_stamps(unsigned long long* out) { if (!out) return PBD_ERR_ARG; hog_debug_read(out); return PROBE_RC; }
 int pbd_debug_conv_stamps(unsigned long long* out) { if (!out) return PBD_ERR_ARG; conv_debug_read(out); return PROBE_RC; }
 

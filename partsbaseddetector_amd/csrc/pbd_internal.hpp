@@ -428,6 +428,7 @@ void launch_backtrack(const int* count, const CandRec* rec, int capacity, const 
                       const unsigned long long* scr_base, const int16_t* ix, const int16_t* iy, int correct_ptr,
                       const int16_t* extx, const int16_t* exty, const unsigned long long* ext_base, int* count_out, hipStream_t s);
 void dt_debug_read(unsigned long long* out);
+void dt_debug_counters(unsigned long long* out);   // probe build: k_dt_pass path counters, read and reset (zeros elsewhere)
 int dt_debug_trace(unsigned long long* t, unsigned* hw, int* nlaunch);   // probe build only
 void hog_debug_read(unsigned long long* out);
 void conv_debug_read(unsigned long long* out);

@@ -40,7 +40,7 @@ int main(int argc, char** argv) {
       for (int p = 0; p <= P; ++p) seg[p] = dt_seg_start(p, P, len);
       for (int p = 0; p < P; ++p) {
         // count scan steps: replicate the loop count = pushes + pops = (n-1) + pops
-        dt_seg_scan<false, float, uint8_t>(YZ.data(), B.data(), R.data(), i2a, seg[p], seg[p + 1], a, b);
+        dt_seg_scan<false, false, float, uint8_t>(YZ.data(), B.data(), R.data(), i2a, seg[p], seg[p + 1], a, b);
         int pops = 0;
         for (int e = seg[p]; e < seg[p + 1]; ++e) if ((int)B[e] > e) pops++;
         scan.push_back((seg[p + 1] - seg[p] - 1) + pops);
@@ -49,7 +49,7 @@ int main(int argc, char** argv) {
       for (int p = P - 1; p >= 1; --p) {
         int f_, dmin, bs; float zs;
         g_iter = 0;
-        dt_stitch1<false, float, uint8_t>(YZ.data(), B.data(), R.data(), i2a, seg[p], seg[p + 1], a, b, f_, dmin, zs, bs);
+        dt_stitch1<false, false, float, uint8_t>(YZ.data(), B.data(), R.data(), i2a, seg[p], seg[p + 1], a, b, f_, dmin, zs, bs);
         stit.push_back(g_iter);
       }
     }

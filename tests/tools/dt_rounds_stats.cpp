@@ -37,12 +37,12 @@ int main(int argc, char** argv) {
         std::vector<IT> B(S + 2);
         for (int i = 0; i < len; ++i) YZ[i].x = data[(size_t)l * len + i];
         bool flag = false;
-        for (int p = 0; p < P; ++p) flag |= dt_seg_scan<false, float, IT>(YZ.data(), B.data(), R.data(), i2a, seg[p], seg[p + 1], a, b);
+        for (int p = 0; p < P; ++p) flag |= dt_seg_scan<false, false, float, IT>(YZ.data(), B.data(), R.data(), i2a, seg[p], seg[p + 1], a, b);
         if (flag || P < 3) continue;
         std::vector<int> F(P, 0), DM(P, 0), BS(P, 0), FS(P, 0);
         std::vector<float> ZS(P, 0);
         bool bad = false;
-        for (int p = P - 1; p >= 1; --p) { int f_, dm, bs; float zs; bad |= dt_stitch1<false, float, IT>(YZ.data(), B.data(), R.data(), i2a, seg[p], seg[p + 1], a, b, f_, dm, zs, bs); F[p] = f_; DM[p] = dm; ZS[p] = zs; BS[p] = bs; }
+        for (int p = P - 1; p >= 1; --p) { int f_, dm, bs; float zs; bad |= dt_stitch1<false, false, float, IT>(YZ.data(), B.data(), R.data(), i2a, seg[p], seg[p + 1], a, b, f_, dm, zs, bs); F[p] = f_; DM[p] = dm; ZS[p] = zs; BS[p] = bs; }
         if (bad) continue;
         for (int p = 2; p < P; ++p) FS[p] = F[p - 1];
         int rounds = 0;
@@ -58,7 +58,7 @@ int main(int argc, char** argv) {
             const int p = st[i];
             int f_, dm, bs = BS[p]; float zs = ZS[p];
             YZ[F[p]].y = zs; B[F[p]] = (IT)bs;
-            dt_stitch1<false, float, IT>(YZ.data(), B.data(), R.data(), i2a, seg[p], seg[p + 1], a, b, f_, dm, zs, bs);
+            dt_stitch1<false, false, float, IT>(YZ.data(), B.data(), R.data(), i2a, seg[p], seg[p + 1], a, b, f_, dm, zs, bs);
             F[p] = f_; ZS[p] = zs; BS[p] = bs; DM[p] = dm; FS[p] = Fstart[p - 1];
           }
           DM[st[0]] = seg[st[0]];          // the lowest stale boundary had only final boundaries to its left: final, never stale again
