@@ -163,13 +163,15 @@ int pbd_abi_version(void);
  * depth-pruning entry points pbd_set_depth_filter, pbd_detect_rgbd_u8, pbd_detect_rgbd_enqueue_dev_u8, pbd_detect_batch_rgbd_u8,
  * pbd_detect_batch_rgbd_enqueue_dev_u8 and pbd_candidates_depth_filter; and the 3-D box entry points pbd_set_box3d,
  * pbd_get_box3d and pbd_candidates_box3d (with the structs pbd_camera and pbd_box3d); and the object-cluster entry points
- * pbd_set_cluster3d, pbd_get_cluster3d and pbd_candidates_cluster3d (with the struct pbd_cluster3d).                          */
+ * pbd_set_cluster3d, pbd_get_cluster3d and pbd_candidates_cluster3d (with the struct pbd_cluster3d); and the per-part score entry
+ * points pbd_set_part_scores, pbd_get_part_scores and pbd_candidates_part_scores (with the struct pbd_part_score).               */
 
 /* ---- output record: include/Candidate.hpp:56-111 --------------------------
  * One candidate = head + max_parts boxes (x, y, width, height as cv::Rect)
  * + max_parts part locations (x, y, mixture) in cells of its pyramid level.
  * max_parts = pbd_max_parts(handle).  Part confidences are the reference's:
- * root = rootv, every other part 0.0 (src/DynamicProgram.cpp:241-244).
+ * root = rootv, every other part 0.0 (src/DynamicProgram.cpp:241-244).  The
+ * opt-in step pbd_set_part_scores (below) computes what each part contributes.
  */
 typedef struct pbd_candidate_head {
   float score;        /* Candidate::score()                                    */
@@ -579,6 +581,51 @@ int pbd_candidates_cluster3d(pbd_handle* h, const void* cloud, int cw, int ch, i
 int pbd_set_cluster3d(pbd_handle* h, int on, float tolerance);
 int pbd_get_cluster3d(pbd_handle* h, int frame, pbd_cluster3d* out, int capacity, int* count, int32_t* indices, int idx_capacity,
                       int* idx_total);
+
+/* ---- per-part scores: the decomposition of a detection's score --------------------------------------------------------------
+ * The record promises "bounding box and detection confidence for each part" (include/Candidate.hpp:54-72); the reference stores
+ * the root score for part 0 and the literal 0.0 for every other part (src/DynamicProgram.cpp:241-244).  This opt-in step computes,
+ * on the GPU, what each part of a returned record contributes.  For a record at level n of component c with part locations
+ * (x_p, y_p, m_p) — the locs the detect entry points return — and q the parent of part p:
+ *   app_p  = resp[n][filterid[p][m_p]](y_p, x_p): the handle's own response value (type T), widened to double;
+ *   def_p  = (a_x * (dx * dx) + b_x * dx) + (a_y * (dy * dy) + b_y * dy) for p >= 1, 0 for the root, with
+ *            dx = x_q + anchor_x - x_p, dy = y_q + anchor_y - y_p (ints, squared as ints), (a_x, b_x, a_y, b_y) = (-w0, -w1, -w2,
+ *            -w3) of defw[defid[p][m_p]] (negated as float, then widened) and the anchor of the same defid — the CHILD's mixture
+ *            selects both; in double, products and sums in the order written, never fused: Quadratic::operator()
+ *            (include/DistanceTransform.hpp:102-104) at the displacement the distance transform reads out (:175);
+ *   bias_p = biasw[biasid[p][m_p] + m_q] for p >= 1 — the child's mixture picks the base, the PARENT's mixture is the offset
+ *            (include/Parts.hpp:172-175, src/DynamicProgram.cpp:138-140); bias_0 = biasw[biasid[0][0]], the root's scalar (:165-170).
+ * score_p = app_p + def_p + bias_p and total = the sum of score_p in part order are left to the caller (doubles for both handle
+ * types).  With pbd_options.dt_correct_ptr = 1 the total reproduces the record's root score up to the DP's own rounding in T
+ * (4 * nparts * eps_T * sum(|app| + |def| + |bias|)); with the reference's pointer composition (0, the default) the returned
+ * part locations are not the arg-max, so the total is at most the root score and usually below it.
+ *
+ * pbd_set_part_scores: off by default.  With it on, EVERY whole-path detect of the handle (pbd_detect_u8 / _dev_u8 / _enqueue_* +
+ * collect, pbd_detect_image, the pbd_detect_batch_* family, the *_rgbd_* entry points; eager or a captured graph, which is dropped
+ * and captured again when the setting changes) scores the records it returns, behind the depth pruning and the candidate filter,
+ * in the frame's stream.  No record, count or struct of detect() changes.  PBD_ERR_STATE while a frame is pending;
+ * PBD_ERR_UNSUPPORTED for a pbd_group member.  The stage entry point pbd_dp_argmin scores nothing.
+ * The step reads the raw response planes after min().  A frame on the compact memory plan (pbd_options.reserved[1] = 2, or automatic
+ * for large frames) has overwritten them: its detect succeeds as ever, the step is skipped, and pbd_get_part_scores answers
+ * PBD_ERR_UNSUPPORTED with a message that names the plan (handles that need the scores keep dp_mode 0 or 1).
+ * pbd_get_part_scores: after the detect / collect returned, frame `frame`'s results: out[i * max_parts + p] for the i-th record
+ * returned for that frame, zero beyond the record's nparts; *count = its records (PBD_ERR_CAPACITY over `capacity`, *count = needed).
+ * PBD_ERR_STATE after a frame that did not compute them (setting off, pbd_dp_argmin, a frame out of range) or while a frame is
+ * pending.  Buffers (24 bytes per part of max_candidates records, pinned, and two small model tables) are allocated on first use
+ * and count in pbd_get_footprint.
+ * pbd_candidates_part_scores: stand-alone — the caller's `count` host records (heads + locs, max_parts = the handle's) scored
+ * against the response planes now resident for the handle's current frame plan (after a detect, pbd_pdf, or pbd_set_level_response
+ * of planes of the caller's own), through the same kernel; out[count * max_parts].  `level` indexes the plan's levels: for a batch
+ * plan frame f's level l is f * nlevels + l.  PBD_ERR_ARG, with nothing read, for a component out of range, an nparts that differs
+ * from the model's, a level outside the plan or not processed by the handle, or an (x, y, mixture) outside its level's cells / the
+ * part's mixtures.  PBD_ERR_STATE without resident responses (a compact plan after min(): the message names the plan) or while a
+ * frame is pending.  Synchronous.                                                                                              */
+typedef struct pbd_part_score {
+  double app, def, bias;           /* appearance (response), deformation, bias of one part                                     */
+} pbd_part_score;                  /* 24 bytes                                                                                 */
+int pbd_set_part_scores(pbd_handle* h, int on);
+int pbd_get_part_scores(pbd_handle* h, int frame, pbd_part_score* out, int capacity, int* count);
+int pbd_candidates_part_scores(pbd_handle* h, const pbd_candidate_head* heads, const int32_t* locs, int count, pbd_part_score* out);
 
 /* ---- instrumentation --------------------------------------------------------
  * GPU time (ms, hipEvent) of the stages of the last synchronous detect:

@@ -50,6 +50,7 @@ EXPORTS = [
     "pbd_detect_batch_rgbd_enqueue_dev_u8", "pbd_candidates_depth_filter",
     "pbd_set_box3d", "pbd_get_box3d", "pbd_candidates_box3d",
     "pbd_set_cluster3d", "pbd_get_cluster3d", "pbd_candidates_cluster3d",
+    "pbd_set_part_scores", "pbd_get_part_scores", "pbd_candidates_part_scores",
 ]
 PBD_ABI_VERSION = 5
 
@@ -348,6 +349,34 @@ class Handle:
                                                   len(b), C.c_float(tol), out.ctypes.data_as(C.c_void_p), _p(idx, C.c_int32),
                                                   len(idx), C.byref(tot)))
         return out, idx[:tot.value]
+
+    # ---- per-part scores (the decomposition of a detection's score) ------------------------------------------------------
+    def set_part_scores(self, on=True):
+        """pbd_set_part_scores: every detect also computes (app, def, bias) of every part of every returned record"""
+        self._chk(self.L.pbd_set_part_scores(self.h, int(bool(on))))
+
+    def part_scores(self, frame=0):
+        """pbd_get_part_scores: [count, max_parts, 3] float64 (app, def, bias; zero beyond a record's nparts) of frame `frame` of
+        the last detect / collect, in the order its records were returned"""
+        cnt = C.c_int(0)
+        rc = self.L.pbd_get_part_scores(self.h, frame, None, 0, C.byref(cnt))
+        if rc not in (PBD_OK, PBD_ERR_CAPACITY):
+            self._chk(rc)
+        out = np.zeros((cnt.value, self.max_parts, 3), np.float64)
+        self._chk(self.L.pbd_get_part_scores(self.h, frame, _p(out, C.c_double), len(out), C.byref(cnt)))
+        return out[:cnt.value]
+
+    def candidates_part_scores(self, heads, locs):
+        """pbd_candidates_part_scores: [n, max_parts, 3] float64 of the caller's records against the response planes resident for
+        the handle's frame (level: the plan's level; frame f of a batch plan: f * nlevels + l)"""
+        heads = np.ascontiguousarray(heads, HEAD_DTYPE)
+        lc = np.zeros((len(heads), self.max_parts, 3), np.int32)
+        l = np.asarray(locs, np.int32).reshape(len(heads), -1, 3)
+        lc[:, :l.shape[1]] = l[:, :self.max_parts]
+        out = np.zeros((len(heads), self.max_parts, 3), np.float64)
+        self._chk(self.L.pbd_candidates_part_scores(self.h, heads.ctypes.data_as(C.c_void_p), _p(lc, C.c_int32), len(heads),
+                                                    _p(out, C.c_double)))
+        return out
 
     def close(self):
         if getattr(self, "h", None):

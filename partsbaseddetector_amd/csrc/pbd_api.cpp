@@ -537,8 +537,12 @@ static int collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int
   std::vector<const char*> recs((size_t)found);
   for (int i = 0; i < found; ++i) recs[i] = h->h_cand_out + h->cand_stride * i;
   std::vector<int> order;
-  rc = pbd_i_emit(h, recs, heads, boxes, locs, capacity, h->out_filtered, h->b3_frame ? &order : nullptr);
+  rc = pbd_i_emit(h, recs, heads, boxes, locs, capacity, h->out_filtered, h->b3_frame || h->ps_frame ? &order : nullptr);
   if (rc) return rc;
+  if (h->ps_frame) {
+    pbd_i_ps_begin(h, 1);
+    pbd_i_ps_gather(h, 0, recs, order);
+  }
   if (h->b3_frame) {
     pbd_i_b3_begin(h, 1);
     pbd_i_b3_gather(h, 0, recs, order);
@@ -566,6 +570,7 @@ static int enqueue_stages(pbd_handle* h, const uint8_t* d_src, int stride) {
   if (prof) hipEventRecord(h->ev[4], h->stream);
   if ((rc = run_argmin_enqueue(h, true))) return rc;
   if (prof) hipEventRecord(h->ev[5], h->stream);
+  if (h->ps_frame && (rc = pbd_i_run_part_scores(h))) return rc;
   if (h->b3_frame && (rc = pbd_i_run_box3d(h))) return rc;
   return PBD_OK;
 }
@@ -630,6 +635,7 @@ static void read_stage_times(pbd_handle* h) {
 // the layouts of include/pbd_c.h that capi.py's ctypes / numpy mirrors rely on
 static_assert(sizeof(pbd_camera) == 48, "pbd_camera layout");
 static_assert(sizeof(pbd_box3d) == 80 && offsetof(pbd_box3d, zmin) == 20 && offsetof(pbd_box3d, x3d) == 32, "pbd_box3d layout");
+static_assert(sizeof(pbd_part_score) == 24 && offsetof(pbd_part_score, bias) == 16, "pbd_part_score layout");
 static_assert(sizeof(pbd_cluster3d) == 40 && offsetof(pbd_cluster3d, first) == 12 && offsetof(pbd_cluster3d, cx) == 16,
               "pbd_cluster3d layout");
 #pragma GCC visibility push(default)
@@ -855,15 +861,17 @@ int pbd_detect_batch_collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* 
   }
   int status = PBD_OK;
   if (h->b3_frame) pbd_i_b3_begin(h, B);
+  if (h->ps_frame) pbd_i_ps_begin(h, B);
   std::vector<int> order;
   for (int f = 0; f < B; ++f) {
     counts[f] = (int)per[f].size();
     pbd_candidate_head* hf = heads + (size_t)f * capacity;
     rc = pbd_i_emit(h, per[f], hf, boxes ? boxes + (size_t)f * capacity * mp * 4 : nullptr, locs ? locs + (size_t)f * capacity * mp * 3 : nullptr, capacity, filt,
-                    h->b3_frame ? &order : nullptr);
+                    h->b3_frame || h->ps_frame ? &order : nullptr);
     if (rc == PBD_ERR_CAPACITY) { status = rc; continue; }
     if (rc) return rc;
     if (h->b3_frame) pbd_i_b3_gather(h, f, per[f], order);
+    if (h->ps_frame) pbd_i_ps_gather(h, f, per[f], order);
     for (int i = 0; i < counts[f]; ++i) hf[i].level -= f * n1;   // virtual level -> the frame's own pyramid level
   }
   if (h->b3_frame && (rc = pbd_i_b3_end(h))) return rc;
@@ -1286,6 +1294,7 @@ int pbd_dp_argmin(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int3
       return fail(h, PBD_ERR_STATE, "argmin(): no min() on this frame and not every root table has been handed in (pbd_set_root)");
   }
   ON_DEVICE(h);
+  h->ps_frame = h->ps_ready = false;   // (the stage entry point scores nothing: pbd_candidates_part_scores does, on its records)
   int rc = run_argmin_enqueue(h);
   if (rc) { h->pending = false; return rc; }
   return collect(h, heads, boxes, locs, capacity, count);

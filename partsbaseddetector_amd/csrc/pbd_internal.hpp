@@ -35,7 +35,7 @@
 
 struct CandRec { int level, comp, y, x; };
 
-// ---- what every post-stage kernel reads (k_cand / k_zfilter / k_box3d / k_cluster3d) --------------------------------------
+// ---- what every post-stage kernel reads (k_cand / k_zfilter / k_box3d / k_cluster3d / k_partscore) ------------------------
 // A record is a pbd_candidate_head, then mp * 4 box ints, then mp * 3 loc ints (pbd_rec_bytes).
 // The records of a frame or a batch: `count` (device) records at p (count > capacity: the back-tracking overflowed).
 struct RecordSet {
@@ -214,6 +214,15 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   bool cl3_ready = false;           // results of the last collected frame, per frame in the order returned
   std::vector<std::vector<int>> cl3_slot;   // [frame] the record slots in the order returned
   std::vector<std::vector<pbd_cluster3d>> cl3_res; std::vector<std::vector<int32_t>> cl3_idx; std::vector<char> cl3_res_on;
+  // per-part scores (pbd_set_part_scores): k_partscore.hip behind the depth pruning and the candidate filter of EVERY frame (plain
+  // and depth-carrying, eager and captured).  Results per record slot (pinned); the collect reorders them like the records.
+  bool ps_on = false;
+  bool ps_frame = false;            // the pending frame computes them (setting on, and a plan that keeps the raw response planes)
+  bool ps_compact = false;          // ... it did not because the plan is the compact one (pbd_get_part_scores names it)
+  struct PsMix* d_ps_mix = nullptr; int* d_ps_mix0 = nullptr;   // [flat mixtures], [flat parts + 1]: the model tables of k_partscore
+  double* h_ps = nullptr;           // [capacity * mp * 3]: pinned
+  bool ps_ready = false;            // results of the last collected frame, per frame in the order returned
+  std::vector<std::vector<double>> ps_res; std::vector<char> ps_res_on;
 };
 #define PBD_MAX_BATCH 64
 
@@ -336,6 +345,9 @@ int pbd_i_post_buffers(pbd_handle* h);   // enqueue_all, outside any capture: th
 // behind launch_backtrack (into `raw`): depth pruning and / or the candidate filter (mode cm) into the output buffers
 int pbd_i_post_enqueue(pbd_handle* h, int cm, bool zf, char* raw);
 int pbd_i_run_box3d(pbd_handle* h);      // 3-D boxes (+ object clusters) of the frame's final records
+int pbd_i_run_part_scores(pbd_handle* h);   // per-part scores of the frame's final records
+void pbd_i_ps_begin(pbd_handle* h, int nframes);   // the collect: each frame's part scores in the order returned, like the 3-D boxes
+void pbd_i_ps_gather(pbd_handle* h, int f, const std::vector<const char*>& recs, const std::vector<int>& order);
 // the collect: each frame's 3-D boxes in the order returned (recs[order[i]]), then the clusters of the frames gathered
 void pbd_i_b3_begin(pbd_handle* h, int nframes);
 void pbd_i_b3_gather(pbd_handle* h, int f, const std::vector<const char*>& recs, const std::vector<int>& order);
@@ -468,6 +480,19 @@ struct Box3dArgs {
   pbd_box3d* out; double* centres;            // [capacity], [capacity * mp * 3] (centres may be null)
 };
 void launch_box3d(const Box3dArgs& a, int ts, hipStream_t s);
+// per-part scores (k_partscore.hip)
+struct PsMix { int filter, bias, ax, ay; float w[4]; };   // one (part, mixture): response plane, bias base, anchor, (-w0, -w1, -w2, -w3) of its deformation (root: zeros)
+struct PartScoreArgs {
+  RecordSet in;
+  const LevelDev* levels; int nvl;              // the plan's (virtual) levels
+  const char* resp; int nfilters;               // T: the raw response planes, level l at cell_off[l] * nfilters
+  int ncomp, nbias;
+  const int* nparts; const int* parent; const int* flat;   // [ncomp]; [ncomp * mp] parent, flat part
+  const int* mix0; const PsMix* mix;            // [flat parts + 1] first flat mixture; [flat mixtures]
+  const float* biasw;
+  double* out;                                  // [capacity][mp][3]: app, def, bias; zero beyond nparts
+};
+void launch_partscore(const PartScoreArgs& a, int ts, hipStream_t s);
 // object clusters (k_cluster3d.hip)
 size_t cluster3d_slot_bytes(int pcap);
 // src: 0 = xyz floats (pstride, rstride bytes), 4 / 8 = a depth image of float / double

@@ -1,7 +1,7 @@
 // pbd_post.cpp — the stages behind back-tracking: candidate sort + NMS (k_cand.hip), depth-consistency pruning
-// (k_zfilter.hip), 3-D boxes (k_box3d.hip) and object clusters (k_cluster3d.hip).  Their handle buffers, their launches
-// behind k_backtrack, the collect's gathering of their results and their C entry points (pbd_set_*, pbd_get_box3d,
-// pbd_get_cluster3d, pbd_candidates_*).  pbd_api.cpp calls in through the pbd_i_* functions of pbd_internal.hpp.
+// (k_zfilter.hip), 3-D boxes (k_box3d.hip), object clusters (k_cluster3d.hip) and per-part scores (k_partscore.hip).  Their handle
+// buffers, their launches behind k_backtrack, the collect's gathering of their results and their C entry points (pbd_set_*,
+// pbd_get_box3d, pbd_get_cluster3d, pbd_get_part_scores, pbd_candidates_*).  pbd_api.cpp calls in through the pbd_i_* functions of pbd_internal.hpp.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -248,7 +248,58 @@ static int cl3_resolve(pbd_handle* h, Cluster3dArgs a, int src, int slots, Scrat
   return PBD_OK;
 }
 
+// ---- per-part scores (k_partscore.hip) --------------------------------------------------------------------------------
+// the model tables (per flat mixture: response plane, bias base, anchor, negated deformation weights) and the pinned results
+static int ps_tables(pbd_handle* h) {
+  if (h->d_ps_mix) return PBD_OK;
+  const size_t nm = h->filterid.size(), nfp = h->parts.size();
+  std::vector<PsMix> mix(nm);
+  for (size_t fp = 0; fp < nfp; ++fp)
+    for (int fm = h->mix_offset[fp]; fm < h->mix_offset[fp + 1]; ++fm) {
+      PsMix& M = mix[fm];
+      M = PsMix{h->filterid[fm], h->biasid[fm], 0, 0, {0.f, 0.f, 0.f, 0.f}};
+      if (h->parts[fp].p == 0) continue;   // (a root has no deformation: its defid is ignored)
+      const int did = h->defid[fm];
+      M.ax = h->anchors[did * 2]; M.ay = h->anchors[did * 2 + 1];
+      for (int k = 0; k < 4; ++k) M.w[k] = -h->defw[(size_t)did * 4 + k];
+    }
+  int rc;
+  if ((rc = model_alloc(h, &h->d_ps_mix0, nfp + 1)) || (rc = model_alloc(h, &h->d_ps_mix, nm))) return rc;
+  HIPCHK(h, hipMemcpy(h->d_ps_mix0, h->mix_offset.data(), sizeof(int) * (nfp + 1), hipMemcpyHostToDevice));
+  HIPCHK(h, hipMemcpy(h->d_ps_mix, mix.data(), sizeof(PsMix) * nm, hipMemcpyHostToDevice));
+  return PBD_OK;
+}
+static int ps_buffers(pbd_handle* h) {
+  int rc = ps_tables(h);
+  if (rc || h->h_ps) return rc;
+  return model_alloc(h, &h->h_ps, (size_t)h->opt.max_candidates * h->max_parts * 3, true);
+}
+// everything of the launch but the records and the output
+static PartScoreArgs ps_args(const pbd_handle* h) {
+  PartScoreArgs a{};
+  a.levels = h->d_levels; a.nvl = h->nvl;
+  a.resp = h->d_resp; a.nfilters = h->md.nfilters;
+  a.ncomp = h->md.ncomponents; a.nbias = (int)h->biasw.size();
+  a.nparts = h->d_nparts; a.parent = h->d_parent; a.flat = h->d_flat;
+  a.mix0 = h->d_ps_mix0; a.mix = h->d_ps_mix; a.biasw = h->d_biasw;
+  return a;
+}
+static const char* const kPsCompact =
+    "part scores: this frame runs the compact memory plan (dp_mode 2, or automatic for large frames), whose min() overwrites the "
+    "raw response planes the scores are read from";
+
 // ---- behind the back-tracking ---------------------------------------------------------------------------------------------
+// the frame's final records (behind the depth pruning and the candidate filter), where the launches behind them read them
+static RecordSet final_records(const pbd_handle* h) {
+  RecordSet in{};
+  in.stride = h->cand_stride; in.mp = h->max_parts; in.capacity = h->opt.max_candidates;
+  in.nlevels = h->nlevels;
+  if (h->out_filtered) { in.p = h->h_cand_out; in.cf = h->h_cf_cnt; in.count = h->h_cf_cnt; in.nframes = h->batch; }
+  else if (h->zf_frame && h->zf_on) { in.p = h->h_cand_out; in.count = h->d_zf_cnt; }
+  else { in.p = (PBD_ARGMIN_ZERO_COPY && !h->d_gsend) ? h->h_cand_out : h->d_cand_out; in.count = h->d_cand_count; }
+  return in;
+}
+
 int pbd_i_post_buffers(pbd_handle* h) {
   const int cm = pbd_i_cand_mode(h);
   if (cm != PBD_CAND_RAW) {
@@ -260,6 +311,13 @@ int pbd_i_post_buffers(pbd_handle* h) {
   h->b3_frame = h->zf_frame && h->b3_on;
   h->cl3_frame = h->b3_frame && h->cl3_on;
   h->b3_has = h->b3_frame ? h->zf_has : 0;
+  h->ps_ready = false;
+  h->ps_compact = h->ps_on && h->compact;   // (the stale planes are never read: the step is skipped and the getter says why)
+  h->ps_frame = h->ps_on && !h->compact;
+  if (h->ps_frame) {
+    int rc = ps_buffers(h);
+    if (rc) return rc;
+  }
   if (!h->zf_frame) return PBD_OK;
   int rc = h->zf_on ? zf_buffers(h) : PBD_OK;
   if (!rc && h->b3_frame) rc = b3_buffers(h);
@@ -310,11 +368,7 @@ int pbd_i_post_enqueue(pbd_handle* h, int cm, bool zf, char* raw) {
 // the frame's final records (behind the depth pruning and the candidate filter) -> one box per record slot, pinned
 int pbd_i_run_box3d(pbd_handle* h) {
   Box3dArgs a{};
-  a.in.stride = h->cand_stride; a.in.mp = h->max_parts; a.in.capacity = h->opt.max_candidates;
-  a.in.nlevels = h->nlevels;
-  if (h->out_filtered) { a.in.p = h->h_cand_out; a.in.cf = h->h_cf_cnt; a.in.count = h->h_cf_cnt; a.in.nframes = h->batch; }
-  else if (h->zf_on) { a.in.p = h->h_cand_out; a.in.count = h->d_zf_cnt; }
-  else { a.in.p = (PBD_ARGMIN_ZERO_COPY && !h->d_gsend) ? h->h_cand_out : h->d_cand_out; a.in.count = h->d_cand_count; }
+  a.in = final_records(h);
   a.z.img = h->zf_img; a.z.pitch = h->zf_pitch; a.z.fbytes = h->zf_fbytes; a.z.w = h->fw; a.z.h = h->fh; a.z.has = h->b3_has;
   a.im_w = h->fw; a.im_h = h->fh; a.cam = h->b3_cam;
   b3_taps(a);
@@ -334,6 +388,30 @@ int pbd_i_run_box3d(pbd_handle* h) {
     h->cl3_args = c;
   }
   return PBD_OK;
+}
+
+// the frame's final records -> three doubles per part and record slot, pinned
+int pbd_i_run_part_scores(pbd_handle* h) {
+  PartScoreArgs a = ps_args(h);
+  a.in = final_records(h);
+  a.out = h->h_ps;
+  launch_partscore(a, h->ts, h->stream);
+  LAUNCHCHK(h, "part scores");
+  return PBD_OK;
+}
+void pbd_i_ps_begin(pbd_handle* h, int nframes) {
+  h->ps_res.assign((size_t)nframes, {}); h->ps_res_on.assign((size_t)nframes, 0);
+  h->ps_ready = true;
+}
+void pbd_i_ps_gather(pbd_handle* h, int f, const std::vector<const char*>& recs, const std::vector<int>& order) {
+  const size_t n = recs.size(), m3 = (size_t)h->max_parts * 3;
+  std::vector<double>& o = h->ps_res[f];
+  o.resize(n * m3);
+  for (size_t i = 0; i < n; ++i) {
+    const size_t slot = (size_t)(recs[order[i]] - h->h_cand_out) / h->cand_stride;
+    memcpy(o.data() + i * m3, h->h_ps + slot * m3, sizeof(double) * m3);
+  }
+  h->ps_res_on[f] = 1;
 }
 
 // ---- 3-D boxes of a collected frame: the pinned per-slot results, in the order the records are returned ---------------------
@@ -709,6 +787,77 @@ int pbd_candidates_cluster3d(pbd_handle* h, const void* cloud, int cw, int ch, i
   if ((rc = cl3_resolve(h, a, 0, slots, &s, lst, res, idx))) return rc;
   std::copy(res.begin(), res.end(), out);
   return cl3_copy_out(h, idx, indices, idx_capacity, idx_total);
+}
+
+// ---- per-part scores (k_partscore.hip) ------------------------------------------------------------------------------------
+int pbd_set_part_scores(pbd_handle* h, int on) {
+  if (!h) return PBD_ERR_ARG;
+  if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "part scores: pbd_group members are not supported (detect through a handle of its own)");
+  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if ((on != 0) != h->ps_on && h->gexec) {   // the step's launch (or its absence) is part of a captured graph
+    ON_DEVICE(h);
+    drop_graph(h);
+  }
+  h->ps_on = on != 0;
+  if (!h->ps_on) h->ps_ready = h->ps_compact = false;
+  return PBD_OK;
+}
+
+int pbd_get_part_scores(pbd_handle* h, int frame, pbd_part_score* out, int capacity, int* count) {
+  if (!h || !count || capacity < 0 || (capacity > 0 && !out)) return PBD_ERR_ARG;
+  if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "part scores: pbd_group members are not supported");
+  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (h->ps_compact) return fail(h, PBD_ERR_UNSUPPORTED, kPsCompact);
+  if (!h->ps_ready || frame < 0 || frame >= (int)h->ps_res_on.size() || !h->ps_res_on[frame])
+    return fail(h, PBD_ERR_STATE, "part scores: the last frame did not compute them for this frame (setting off, a stage entry point, or a frame out of range)");
+  const std::vector<double>& r = h->ps_res[frame];
+  const size_t m3 = (size_t)h->max_parts * 3;
+  const int n = (int)(r.size() / m3);
+  *count = n;
+  if (n > capacity) return fail(h, PBD_ERR_CAPACITY, "output capacity too small");
+  if (n) memcpy(out, r.data(), sizeof(double) * r.size());
+  return PBD_OK;
+}
+
+int pbd_candidates_part_scores(pbd_handle* h, const pbd_candidate_head* heads, const int32_t* locs, int count, pbd_part_score* out) {
+  if (!h) return PBD_ERR_ARG;
+  if (count < 0 || (count > 0 && (!heads || !locs || !out))) return fail(h, PBD_ERR_ARG, "heads / locs / out / count");
+  if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "part scores: pbd_group members are not supported");
+  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (h->fw == 0) return fail(h, PBD_ERR_STATE, "part scores: no frame planned");
+  if (!h->have_resp) return fail(h, PBD_ERR_STATE, h->compact ? kPsCompact : "part scores: responses not computed");
+  const int mp = h->max_parts;
+  for (int i = 0; i < count; ++i) {
+    const int c = heads[i].component, l = heads[i].level;
+    if (c < 0 || c >= h->md.ncomponents) return fail(h, PBD_ERR_ARG, "component out of range");
+    const int f0 = h->part_offset[c], np = h->part_offset[c + 1] - f0;
+    if (heads[i].nparts != np) return fail(h, PBD_ERR_ARG, "nparts differs from the model's component");
+    if (l < 0 || l >= h->nvl || !h->lv[l].active) return fail(h, PBD_ERR_ARG, "level outside the levels this handle processes");
+    const int32_t* lc = locs + (size_t)i * mp * 3;
+    for (int p = 0; p < np; ++p)
+      if (lc[p * 3] < 0 || lc[p * 3] >= h->lv[l].cw || lc[p * 3 + 1] < 0 || lc[p * 3 + 1] >= h->lv[l].ch || lc[p * 3 + 2] < 0 ||
+          lc[p * 3 + 2] >= h->parts[f0 + p].K)
+        return fail(h, PBD_ERR_ARG, "part location (x, y, mixture) outside its level's cells / the part's mixtures");
+  }
+  if (count == 0) return PBD_OK;
+  ON_DEVICE(h);
+  int rc = ps_tables(h);
+  if (rc) return rc;
+  const size_t st = h->cand_stride, n = (size_t)count, m3 = (size_t)mp * 3;
+  std::vector<char> rec(st * n, 0);
+  for (size_t i = 0; i < n; ++i) pbd_rec_put(rec.data() + st * i, mp, heads, nullptr, locs, i);
+  Scratch s(h);
+  PartScoreArgs a = ps_args(h);
+  a.in.p = s.dev<char>(st * n); a.in.stride = st; a.in.mp = mp; a.in.count = s.dev<int>(1); a.in.capacity = count; a.in.nlevels = 0;
+  a.out = s.dev<double>(n * m3);
+  s.up((void*)a.in.p, rec.data(), st * n);
+  s.up((void*)a.in.count, &count, sizeof(int));
+  if (s.ok()) {
+    launch_partscore(a, h->ts, h->stream);
+    s.launched();
+  }
+  s.down(out, a.out, sizeof(double) * n * m3);
+  return s.finish("part scores: ");
 }
 
 }  // extern "C"

@@ -42,6 +42,11 @@ class Candidate:
     part_centers: Optional[np.ndarray] = None   # setBoundingBoxes3D: [nparts, 3] (empty when the box was skipped)
     centre3d: Optional[np.ndarray] = None       # setObjectClusters: the kept cluster's centroid (3 doubles, NaN when none)
     cluster: Optional[np.ndarray] = None        # setObjectClusters: its point indices (row * w + col), ascending, int32
+    part_scores: Optional[np.ndarray] = None    # setPartScores: [nparts, 3] float64 (app, def, bias) of every part
+
+    def partScores(self) -> Optional[np.ndarray]:
+        """The three terms of every part's score, score_p = app + def + bias ([nparts, 3] float64); None with setPartScores off."""
+        return self.part_scores
 
     def score(self) -> float:
         return float(self.confidence[0]) if len(self.confidence) else float("-inf")
@@ -92,14 +97,20 @@ class Candidate:
         return heads, boxes, locs
 
     @staticmethod
-    def _unpack(heads, boxes, locs) -> List["Candidate"]:
+    def _unpack(heads, boxes, locs, part_scores=None) -> List["Candidate"]:
+        """part_scores ([n, max_parts, 3], setPartScores): confidence[p] = (float)score_p for p >= 1; confidence[0] stays the
+        root score, which callers sort and suppress by"""
         out = []
         for i in range(len(heads)):
             n = int(heads[i]["nparts"])
             conf = np.zeros(n, np.float32)
+            ps = None
+            if part_scores is not None:
+                ps = np.asarray(part_scores[i][:n], np.float64).copy()
+                conf[:] = ((ps[:, 0] + ps[:, 1]) + ps[:, 2]).astype(np.float32)
             conf[0] = heads[i]["score"]
             out.append(Candidate(boxes[i, :n].copy(), conf, int(heads[i]["component"]), int(heads[i]["level"]),
-                                 locs[i, :n].copy()))
+                                 locs[i, :n].copy(), part_scores=ps))
         return out
 
     @staticmethod
@@ -230,6 +241,7 @@ class PartsBasedDetector:
         self._zfactor: Optional[float] = None   # setDepthFilter: None = off
         self._camera = None                      # setBoundingBoxes3D: None = off
         self._cluster_tol: Optional[float] = None   # setObjectClusters: None = off
+        self._part_scores = False                # setPartScores
         self._dtype = np.dtype(dtype)
         self._lb, self._le = level_begin, level_end
         self._h: Optional[capi.Handle] = None
@@ -254,6 +266,19 @@ class PartsBasedDetector:
             self._h.set_box3d(True, self._camera)
         if self._cluster_tol is not None:
             self._h.set_cluster3d(True, self._cluster_tol)
+        if self._part_scores:
+            self._h.set_part_scores(True)
+
+    def setPartScores(self, on: bool = True) -> None:
+        """Every detect() fills Candidate.confidence[p], p >= 1, with the part's own score (appearance + deformation + bias of
+        the returned configuration, computed on the GPU) instead of the reference's 0.0, and Candidate.partScores() with the three
+        terms; confidence[0] stays the root score.  Off (the default): zeros, as the reference.  Kept across distributeModel()."""
+        if self._h is not None:
+            self._h.set_part_scores(on)
+        self._part_scores = bool(on)
+
+    def _ps(self):
+        return self.handle.part_scores(0) if self._part_scores else None
 
     def setBoundingBoxes3D(self, camera=None) -> None:
         """camera = (fx, fy, cx, cy[, tx, ty]) or a capi.pbd_camera: every detect(im, depth) with a non-empty depth image attaches
@@ -333,7 +358,7 @@ class PartsBasedDetector:
         if (self._zfactor is not None or self._camera is not None) and depth is not None and np.asarray(depth).size > 0:
             if np.asarray(im).dtype != np.uint8:
                 raise capi.PbdError(capi.PBD_ERR_UNSUPPORTED, "depth pruning / 3-D boxes: 8-bit colour frames only")
-            got = Candidate._unpack(*self.handle.detect_rgbd(im, depth, self._cap))
+            got = Candidate._unpack(*self.handle.detect_rgbd(im, depth, self._cap), self._ps())
             if self._camera is not None:
                 b3, cen = self.handle.get_box3d(0)
                 for i, c in enumerate(got):
@@ -349,5 +374,5 @@ class PartsBasedDetector:
             return out
         # (the image's dtype is its depth: uint8 -> pbd_detect_u8, the other accepted depths -> pbd_detect_image; unsupported ones raise)
         res = self.handle.detect(im, self._cap) if np.asarray(im).dtype == np.uint8 else self.handle.detect_image(im, self._cap)
-        out.extend(Candidate._unpack(*res))
+        out.extend(Candidate._unpack(*res, self._ps()))
         return out

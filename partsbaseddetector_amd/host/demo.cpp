@@ -20,8 +20,9 @@ using namespace pbd;
 //             from pdf(), and the tables min() returns are edited before argmin() (a root score raised, part 1's x
 //             pointer at that cell redirected): the candidates must be those of the edited tables.
 template <typename T>
-static void run(Model& model, const Mat& im, bool stagewise, int special = 0, const char* io_file = nullptr) {
+static void run(Model& model, const Mat& im, bool stagewise, int special = 0, const char* io_file = nullptr, bool part_scores = false) {
   PartsBasedDetector<T> pbd(0, PBD_CONV_EXACT);
+  pbd.setPartScores(part_scores);
   pbd.distributeModel(model);
   vectorCandidate candidates;
   if (stagewise) {
@@ -83,12 +84,28 @@ static void run(Model& model, const Mat& im, bool stagewise, int special = 0, co
     printf("%.9g %d %d", c.score(), c.component(), c.level);
     for (const Rect& r : c.parts()) printf(" %d,%d,%d,%d", r.x, r.y, r.width, r.height);
     printf("\n");
+    if (!c.partScores().empty()) {   // --part-scores: the re-scored total beside the root score, and the weakest part
+      double total = 0;
+      size_t weak = 0;
+      std::vector<double> sc;
+      for (const pbd_part_score& s : c.partScores()) { sc.push_back((s.app + s.def) + s.bias); total += sc.back(); }
+      for (size_t p = 1; p < sc.size(); ++p) if (sc[p] < sc[weak]) weak = p;
+      printf("  part scores: total %.9g root %.9g weakest part %zu (%.9g = app %.9g + def %.9g + bias %.9g)\n", total, c.score(), weak,
+             sc[weak], c.partScores()[weak].app, c.partScores()[weak].def, c.partScores()[weak].bias);
+    }
   }
 }
 
 int main(int argc, char** argv) {
+  bool part_scores = false;   // --part-scores (anywhere): per detection, the re-scored total, the root score and the weakest part
+  for (int i = 1; i < argc; ++i)
+    if (std::string(argv[i]) == "--part-scores") {
+      part_scores = true;
+      for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
+      --argc; --i;
+    }
   if (argc < 6 || argc > 8) {
-    printf("Usage: pbd_demo model_file image.raw width height channels [stagewise|double|stagewise-double]\n");
+    printf("Usage: pbd_demo model_file image.raw width height channels [stagewise|double|stagewise-double] [--part-scores]\n");
     exit(-1);
   }
   // determine the type of model to read (src/demo.cpp:63-82)
@@ -113,8 +130,9 @@ int main(int argc, char** argv) {
   if (special && argc != 8) { printf("%s needs a file argument\n", mode.c_str()); exit(-1); }
   const bool stagewise = special || mode.find("stagewise") != std::string::npos;
   try {
-    if (mode.find("double") != std::string::npos) run<double>(model, im, stagewise);
-    else run<float>(model, im, stagewise, special, special ? argv[7] : nullptr);
+    if (part_scores && stagewise) { printf("--part-scores: the fused detect() only\n"); exit(-1); }
+    if (mode.find("double") != std::string::npos) run<double>(model, im, stagewise, 0, nullptr, part_scores);
+    else run<float>(model, im, stagewise, special, special ? argv[7] : nullptr, part_scores);
   } catch (const Exception& e) {
     printf("error %d: %s\n", e.code, e.what());
     return 1;

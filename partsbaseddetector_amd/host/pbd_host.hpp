@@ -82,7 +82,14 @@ class Candidate {
   std::vector<Rect> parts_;
   vectorf confidence_;
   int component_ = 0;
+  std::vector<pbd_part_score> part_scores_;
  public:
+  // PartsBasedDetector::setPartScores: the three terms (app, def, bias) of every part's score; empty with the step off
+  const std::vector<pbd_part_score>& partScores() const { return part_scores_; }
+  void setPartScores(const pbd_part_score* ps, int nparts) {   // confidence()[p], p >= 1, = (float)score_p; [0] stays the root score
+    part_scores_.assign(ps, ps + nparts);
+    for (int p = 1; p < nparts && p < (int)confidence_.size(); ++p) confidence_[p] = (float)((ps[p].app + ps[p].def) + ps[p].bias);
+  }
   int level = -1;                        // extra: pyramid level of the root
   std::vector<int> locs;                 // extra: (x, y, mixture) per part, in cells
   const std::vector<Rect>& parts() const { return parts_; }
@@ -338,6 +345,8 @@ class Device {
   void setCandidateFilter(int mode, float overlap = 0.f) { check(pbd_set_candidate_filter(h, mode, overlap)); }
   // SearchSpacePruning::filterCandidatesByDepth inside every detect(im, depth) with a non-empty depth image, on the GPU
   void setDepthFilter(bool on, float zfactor) { check(pbd_set_depth_filter(h, on ? 1 : 0, zfactor)); }
+  // per-part scores of every record detect() returns, on the GPU
+  void setPartScores(bool on) { check(pbd_set_part_scores(h, on ? 1 : 0)); }
 };
 
 // ---- include/IFeatures.hpp:49-73 --------------------------------------------------------------
@@ -620,6 +629,16 @@ class PartsBasedDetector {
   int device_, conv_mode_, ncomponents_ = 0;
   int cand_mode_ = PBD_CAND_RAW; float cand_overlap_ = 0.f;
   bool depth_on_ = false; float zfactor_ = 0.03f;
+  bool part_scores_on_ = false;
+  // the last detect's per-part scores -> the `n` candidates it appended: fills Candidate::confidence_ of the non-root parts
+  void attach_part_scores(vectorCandidate& candidates, int n, int mp) {
+    if (!part_scores_on_ || n == 0) return;
+    std::vector<pbd_part_score> ps((size_t)n * mp);
+    int got = 0;
+    dev_->check(pbd_get_part_scores(dev_->h, 0, ps.data(), n, &got));
+    Candidate* c = candidates.data() + (candidates.size() - (size_t)n);
+    for (int i = 0; i < got; ++i) c[i].setPartScores(ps.data() + (size_t)i * mp, (int)c[i].parts().size());
+  }
  public:
   int max_candidates_ = 4096;
   explicit PartsBasedDetector(int device = 0, int conv_mode = PBD_CONV_AUTO, int max_candidates = 4096)
@@ -643,6 +662,15 @@ class PartsBasedDetector {
     dp_ = DynamicProgram<T>(dev_);
     if (cand_mode_ != PBD_CAND_RAW) dev_->setCandidateFilter(cand_mode_, cand_overlap_);
     if (depth_on_) dev_->setDepthFilter(true, zfactor_);
+    if (part_scores_on_) dev_->setPartScores(true);
+  }
+  // The record promises a confidence per part (include/Candidate.hpp:54-72); the reference stores 0.0 for every part but the
+  // root (src/DynamicProgram.cpp:241-244).  On: Candidate::confidence()[p], p >= 1, is the part's own score — appearance +
+  // deformation + bias of the returned configuration, computed by the GPU inside detect() — and Candidate::partScores() gives
+  // the three terms; confidence()[0] stays the root score.  Off (the default): zeros.  Kept across distributeModel().
+  void setPartScores(bool on) {
+    if (dev_) dev_->setPartScores(on);
+    part_scores_on_ = on;
   }
   // SearchSpacePruning<T>::filterCandidatesByDepth(parts, candidates, depth, zfactor), the call the reference leaves commented out
   // in detect() (src/PartsBasedDetector.cpp:91-93, zfactor 0.03), done by the GPU inside detect(im, depth, candidates) for a
@@ -672,12 +700,14 @@ class PartsBasedDetector {
       dev_->check(pbd_detect_rgbd_u8(dev_->h, im.ptr<uint8_t>(), im.cols, im.rows, im.channels(), (int)im.step(), depth.ptr<uint8_t>(),
                                      depth.depth(), (int)depth.step(), heads.data(), boxes.data(), locs.data(), cap, &n));
       append_candidates(candidates, heads, boxes, locs, n, mp);
+      attach_part_scores(candidates, n, mp);
       return;
     }
     // (CV_8U forwards to pbd_detect_u8; CV_16U / CV_32F / CV_64F: src/HOGFeatures.cpp:136-146; anything else: PBD_ERR_UNSUPPORTED = StsUnsupportedFormat)
     dev_->check(pbd_detect_image(dev_->h, im.ptr<uint8_t>(), im.depth(), im.cols, im.rows, im.channels(), (int)im.step(),
                                  heads.data(), boxes.data(), locs.data(), cap, &n));
     append_candidates(candidates, heads, boxes, locs, n, mp);
+    attach_part_scores(candidates, n, mp);
   }
 };
 
