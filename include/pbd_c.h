@@ -627,6 +627,41 @@ int pbd_set_part_scores(pbd_handle* h, int on);
 int pbd_get_part_scores(pbd_handle* h, int frame, pbd_part_score* out, int capacity, int* count);
 int pbd_candidates_part_scores(pbd_handle* h, const pbd_candidate_head* heads, const int32_t* locs, int count, pbd_part_score* out);
 
+/* ---- padded feature pyramid with the boundary-occlusion feature (opt-in, off by default; ABI 5, additive) ------------------
+ * The third step PartsBasedDetector::detect()'s author wrote and commented out at the call site (after the score-map NMS,
+ * reserved[0], and the depth pruning, pbd_set_depth_filter):
+ *   copyMakeBorder(feature, padded, 3, 3, 3*flen_, 3*flen_, BORDER_CONSTANT, 0); boundaryOcclusionFeature(padded, flen_, 3);
+ * (src/HOGFeatures.cpp:147-148, body at :57-79).  The models are trained by matlab/detection/featpyramid.m:37-44, which pads every
+ * level with zero cells and sets the last HOG channel to 1 there: channel flen - 1 of every filter is a learned "this cell lies
+ * outside the image" weight, and only a padded pyramid ever shows it a 1.
+ *   * Level l has its interior ih x iw cells as without the step (blocks - 2).  Its planes are (ih + 2 pad) x (iw + 2 pad); interior
+ *     cell (y, x) sits at (y + pad, x + pad): copyMakeBorder(..., pad, pad, pad * flen, pad * flen, BORDER_CONSTANT, 0).  A level
+ *     without interior cells stays empty.
+ *   * Border rule of boundaryOcclusionFeature (src/HOGFeatures.cpp:64-79): rows 0 .. pad - 1 and H - pad .. H - 1, columns
+ *     0 .. pad - 1 and W - pad .. W - 1 of the padded plane hold 0 in channels 0 .. flen - 2 and 1 in channel flen - 1.  Interior
+ *     cells are untouched (their channel flen - 1 is the HOG truncation feature, 0).
+ *   * pad = 3 is the reference's literal; featpyramid.m:11-12 uses max filter size - 2 (3 for 5 x 5 filters, 7 for 9 x 9).
+ *     0 <= pad <= 8; anything else is PBD_ERR_ARG.
+ *   * Boxes: src/DynamicProgram.cpp:239 becomes xy1 = (Point(x, y) - Point(1 + pad, 1 + pad)) * scale, rounded in T as before; sizes
+ *     are unchanged.  This is what matlab/detection/detect.m:266-267 does.  The reference's commented-out C++ lines have no such
+ *     compensation, because they were never live: it is the one place where the step follows the MATLAB ancestor, not a C++ line.
+ *     Boxes may reach further outside the frame than without the step.
+ *   * locs stay coordinates in the level's planes, i.e. PADDED coordinates — the ones the pointer tables and the response getters
+ *     use.  pbd_pyramid_geometry reports padded cell_w / cell_h; pbd_get_level_features / _response / pbd_get_root /
+ *     pbd_get_dp_pointers and the setters address padded planes; pbd_set_level_features takes a full padded plane and uses the
+ *     caller's border as given (the next pbd_pyramid_* / detect writes the rule's border again).
+ *   * scales, the level images and the number of levels do not change.  The filter bank, the DP, the root reduction, the score-map
+ *     NMS and the back-tracking run on the padded planes with no change of their own; the plan's limits (16-bit pointers, the
+ *     distance transform's line length, 2^28 cells per level) are checked on the padded sizes.
+ * pbd_set_boundary_pad: every detect path of the handle from the next frame on (single, enqueue / collect, batches, device
+ * images, pbd_detect_image, *_rgbd_*, the stage entry points; eager or captured).  A different value drops the handle's frame plan
+ * and captured graph, as pbd_tune_plan does on return: stage getters answer PBD_ERR_STATE until the next frame.  PBD_ERR_STATE while
+ * an enqueued frame or batch is not collected.  With 0 the handle behaves exactly as one that never had the step on.
+ * pbd_group_set_boundary_pad forwards to every member (nothing changes unless the value is valid and no member has a frame pending). */
+int pbd_set_boundary_pad(pbd_handle* h, int pad);      /* 0 = off (default) */
+int pbd_get_boundary_pad(const pbd_handle* h);
+int pbd_group_set_boundary_pad(pbd_group* g, int pad); /* forwards to every member */
+
 /* ---- instrumentation --------------------------------------------------------
  * GPU time (ms, hipEvent) of the stages of the last synchronous detect:
  * [0] image pyramid [1] HOG [2] pdf [3] dp min [4] argmin [5] total            */

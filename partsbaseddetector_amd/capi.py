@@ -51,6 +51,7 @@ EXPORTS = [
     "pbd_set_box3d", "pbd_get_box3d", "pbd_candidates_box3d",
     "pbd_set_cluster3d", "pbd_get_cluster3d", "pbd_candidates_cluster3d",
     "pbd_set_part_scores", "pbd_get_part_scores", "pbd_candidates_part_scores",
+    "pbd_set_boundary_pad", "pbd_get_boundary_pad", "pbd_group_set_boundary_pad",
 ]
 PBD_ABI_VERSION = 5
 
@@ -351,6 +352,16 @@ class Handle:
         return out, idx[:tot.value]
 
     # ---- per-part scores (the decomposition of a detection's score) ------------------------------------------------------
+    def set_boundary_pad(self, pad=3):
+        """pbd_set_boundary_pad: `pad` cells of padding (0, and 1 in the last channel) around every pyramid level from the next
+        frame on; 0 = off.  Planes, locs and pyramid_geometry() are then padded; boxes are shifted back by the padding."""
+        self._chk(self.L.pbd_set_boundary_pad(self.h, int(pad)))
+
+    @property
+    def boundary_pad(self):
+        """pbd_get_boundary_pad"""
+        return int(self.L.pbd_get_boundary_pad(self.h))
+
     def set_part_scores(self, on=True):
         """pbd_set_part_scores: every detect also computes (app, def, bias) of every part of every returned record"""
         self._chk(self.L.pbd_set_part_scores(self.h, int(bool(on))))
@@ -746,6 +757,10 @@ class Group:
     def set_candidate_filter(self, mode, overlap=0.0):
         """pbd_group_set_candidate_filter: every member; detect() filters the union of the members' levels."""
         self._chk(self.L.pbd_group_set_candidate_filter(self.g, int(mode), C.c_float(overlap)))
+
+    def set_boundary_pad(self, pad=3):
+        """pbd_group_set_boundary_pad: every member (Handle.set_boundary_pad)."""
+        self._chk(self.L.pbd_group_set_boundary_pad(self.g, int(pad)))
 
     def close(self):
         if getattr(self, "g", None):

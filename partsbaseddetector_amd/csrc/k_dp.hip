@@ -821,7 +821,7 @@ __global__ __launch_bounds__(64) void k_backtrack(const int* __restrict__ count,
                                                   const int16_t* __restrict__ ixs, const int16_t* __restrict__ iys,
                                                   int correct_ptr, const int16_t* __restrict__ extx,
                                                   const int16_t* __restrict__ exty, const unsigned long long* __restrict__ ext_base,
-                                                  int* __restrict__ count_out) {
+                                                  int* __restrict__ count_out, int org) {
   __shared__ int lx[BT_MAXP], ly[BT_MAXP], lm[BT_MAXP];
   const int lane = threadIdx.x;
   const int n = min(*count, capacity);
@@ -877,7 +877,9 @@ __global__ __launch_bounds__(64) void k_backtrack(const int* __restrict__ count,
       const int sz = t_round((T)mix_rows[flat[r.comp * max_parts + p] * PBD_MAX_MIX + (lm[p] & (PBD_MAX_MIX - 1))] * scale);   // (mask: tables handed in by a caller stay inside the row)
       const int x = lx[p], y = ly[p];
       locs[p * 3] = x; locs[p * 3 + 1] = y; locs[p * 3 + 2] = lm[p];
-      const int x1 = t_round((T)(x - 1) * scale), y1 = t_round((T)(y - 1) * scale);
+      // org = 1 + pad: with boundary padding (pbd_set_boundary_pad) the planes carry `pad` cells in front of the image's first cell, and
+      // the origin moves back by them as matlab/detection/detect.m:266-267 does (padx, pady); 1 without — :239 itself
+      const int x1 = t_round((T)(x - org) * scale), y1 = t_round((T)(y - org) * scale);
       const int x2 = x1 + sz - 1, y2 = y1 + sz - 1;
       boxes[p * 4] = min(x1, x2); boxes[p * 4 + 1] = min(y1, y2);
       boxes[p * 4 + 2] = max(x1, x2) - min(x1, x2); boxes[p * 4 + 3] = max(y1, y2) - min(y1, y2);
@@ -893,10 +895,10 @@ void launch_backtrack(const int* count, const CandRec* rec, int capacity, const 
                       const int* parent, const int* plane0, const int* nparts, int max_parts, const int* mix_rows, char* out,
                       size_t out_stride, int ts, const int* flat, const int* depth, int max_depth, int nflat,
                       const unsigned long long* scr_base, const int16_t* ix, const int16_t* iy, int correct_ptr,
-                      const int16_t* extx, const int16_t* exty, const unsigned long long* ext_base, int* count_out, hipStream_t s) {
+                      const int16_t* extx, const int16_t* exty, const unsigned long long* ext_base, int* count_out, int pad, hipStream_t s) {
   const int nblk = std::min(capacity, 2048);   // 8 blocks of one wavefront per CU; more candidates than that are taken in further sweeps
-  if (ts == 8) hipLaunchKernelGGL(k_backtrack<double>, dim3(nblk), dim3(64), 0, s, count, rec, capacity, back, ncomp, parent, plane0, nparts, max_parts, mix_rows, out, out_stride, flat, depth, max_depth, nflat, scr_base, ix, iy, correct_ptr, extx, exty, ext_base, count_out);
-  else hipLaunchKernelGGL(k_backtrack<float>, dim3(nblk), dim3(64), 0, s, count, rec, capacity, back, ncomp, parent, plane0, nparts, max_parts, mix_rows, out, out_stride, flat, depth, max_depth, nflat, scr_base, ix, iy, correct_ptr, extx, exty, ext_base, count_out);
+  if (ts == 8) hipLaunchKernelGGL(k_backtrack<double>, dim3(nblk), dim3(64), 0, s, count, rec, capacity, back, ncomp, parent, plane0, nparts, max_parts, mix_rows, out, out_stride, flat, depth, max_depth, nflat, scr_base, ix, iy, correct_ptr, extx, exty, ext_base, count_out, 1 + pad);
+  else hipLaunchKernelGGL(k_backtrack<float>, dim3(nblk), dim3(64), 0, s, count, rec, capacity, back, ncomp, parent, plane0, nparts, max_parts, mix_rows, out, out_stride, flat, depth, max_depth, nflat, scr_base, ix, iy, correct_ptr, extx, exty, ext_base, count_out, 1 + pad);
 }
 
 // ---------------------------------------------------------------------------

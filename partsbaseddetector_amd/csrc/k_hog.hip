@@ -21,6 +21,7 @@
 // wide staging loads, the tabulated snap, one thread per BLOCK for the histograms and one thread per CELL for the 32
 // features (the 18 contrast-sensitive features, the texture sums and the normalisers are shared work inside a cell).
 #include "pbd_internal.hpp"
+#include "pbd_split.hpp"
 
 // debug: per-phase wall-clock stamps (100 MHz) of block 0 of the last k_hog launch
 #ifdef PBD_PROBES
@@ -329,6 +330,9 @@ __global__ __launch_bounds__(HOG_NT, 5) void k_hog(const HogTile* __restrict__ t
   //      loop accumulates t1..t4); a lane-per-feature mapping recomputed them and ran every wavefront through all three
   //      feature kinds.  Half a tile of cells at a time: the finished features are staged in LDS (row of 33 per cell) and
   //      written out with 32 consecutive lanes per cell (128 B, coalesced). ----
+  // The level's cells are its (bh - 2) x (bw - 2) interior (:175); lv.cw is the PITCH of its feature plane and lv.cell_off the interior's
+  // first cell: with boundary padding (pbd_set_boundary_pad) the plane is wider than the interior and the host has folded the offset
+  // (pad rows + pad cells) into cell_off (FrameTables::hog_levels), so the store below is the same instruction either way.
   T* out = feat + lv.cell_off * PBD_FLEN;
   T* stg = (T*)(smem + L.out_off);
   const int ncell = tc * tc, half = (ncell + 1) / 2;
@@ -336,7 +340,7 @@ __global__ __launch_bounds__(HOG_NT, 5) void k_hog(const HogTile* __restrict__ t
     const int cell = c0 + tid;
     if (tid < half && cell < ncell) {
       const int ly = cell / tc, lx = cell - ly * tc;
-      if (t.cy0 + ly < lv.ch && t.cx0 + lx < lv.cw) {
+      if (t.cy0 + ly < bh - 2 && t.cx0 + lx < bw - 2) {
         const T n1 = ninv[(ly + 1) * NC + lx + 1], n2 = ninv[ly * NC + lx + 1];
         const T n3 = ninv[(ly + 1) * NC + lx], n4 = ninv[ly * NC + lx];
         const T* hsrc = hist + ((ly + 1) * NB + lx + 1);
@@ -371,7 +375,7 @@ __global__ __launch_bounds__(HOG_NT, 5) void k_hog(const HogTile* __restrict__ t
       const int cl = c0 + lc;
       const int ly = cl / tc, lx = cl - ly * tc;
       const int cy = t.cy0 + ly, cx = t.cx0 + lx;
-      if (cl < ncell && cy < lv.ch && cx < lv.cw) {
+      if (cl < ncell && cy < bh - 2 && cx < bw - 2) {
         const T v = stg[lc * (PBD_FLEN + 1) + k];
         const size_t gc = (size_t)cy * lv.cw + cx;
         out[gc * PBD_FLEN + k] = v;
@@ -379,21 +383,9 @@ __global__ __launch_bounds__(HOG_NT, 5) void k_hog(const HogTile* __restrict__ t
           // PBD_CONV_SPLIT: the feature's three exact bfloat16 parts for the split-product filter bank, [cell][split][32] (k_conv_split.hip:
           // v = h + m + l, every subtraction exact) — written here instead of by a separate pass over the features
           if (split && split_parts == 3) {
-            uint16_t* sp = split + (lv.cell_off + gc) * (3 * PBD_FLEN) + k;
-            float r = v;
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-              const unsigned u = __float_as_uint(r);
-              const unsigned hb = (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-              sp[q * PBD_FLEN] = (uint16_t)hb;
-              r = r - __uint_as_float(hb << 16);
-            }
+            feat_split_bf16(v, split + (lv.cell_off + gc) * (3 * PBD_FLEN) + k, PBD_FLEN);
           } else if (split) {   // PBD_CONV_SPLIT_F16: two binary16 parts of v 2^12 (k_feat_split16)
-            _Float16* sp = (_Float16*)split + (lv.cell_off + gc) * (2 * PBD_FLEN) + k;
-            const float x = v * 4096.f;
-            const _Float16 hv = (_Float16)x;
-            sp[0] = hv;
-            sp[PBD_FLEN] = (_Float16)(x - (float)hv);
+            feat_split_f16(v, (_Float16*)split + (lv.cell_off + gc) * (2 * PBD_FLEN) + k, PBD_FLEN);
           }
         }
       }

@@ -235,6 +235,8 @@ static int plan_frame(pbd_handle* h, int w, int hgt, int cn, int batch = 1, int 
   FrameTables t;
   if ((rc = plan_tables(*h, fs, lay, b, ncu, h->dt_geom, h->knobs, t, &h->err))) return rc;
   if ((rc = dev_upload(h, &h->d_pyrjobs, t.pyrjobs)) || (rc = dev_upload(h, &h->d_levels, t.levels)) ||
+      (h->pad > 0 && ((rc = dev_upload(h, &h->d_hog_levels, t.hog_levels)) || (rc = dev_upload(h, &h->d_padjobs, t.padjobs)) ||
+                      (rc = dev_upload(h, &h->d_padblocks, t.padblk)))) ||
       (rc = dev_upload(h, &h->d_hog_tiles, t.hog_tiles)) || (rc = dev_upload(h, &h->d_conv_tiles, t.conv_tiles)) ||
       (h->mixed && (rc = dev_upload(h, &h->d_conv_tiles_mix, t.conv_tiles_mix))) ||
       (rc = dev_upload(h, &h->d_dtmaps, t.maps)) || (rc = dev_upload(h, &h->d_dttasks, t.tasks)) ||
@@ -251,6 +253,8 @@ static int plan_frame(pbd_handle* h, int w, int hgt, int cn, int batch = 1, int 
   h->d_dt_tmpT = b.p[FB_DT_TMPT]; h->d_dt_sdt = b.p[FB_DT_SDT]; h->d_dt_ixT = (int16_t*)b.p[FB_DT_IXT]; h->d_dt_iy = (int16_t*)b.p[FB_DT_IY];
   h->d_acc = b.p[FB_ACC]; h->d_feat_split = (uint16_t*)b.p[FB_FEAT_SPLIT];
   h->pyr_launches = std::move(t.pyr_launches);
+  if (h->pad == 0) { h->d_hog_levels = h->d_levels; h->d_padjobs = nullptr; h->d_padblocks = nullptr; }
+  h->n_padblocks = (int)t.padblk.size();
   h->hog_tc = t.hog_tc; h->n_hog_tiles = (int)t.hog_tiles.size(); h->n_conv_tiles = (int)t.conv_tiles.size();
   h->dt_nt = t.dt_nt; h->dt_lds = t.dt_lds;
   h->rl = std::move(t.rl);
@@ -283,7 +287,10 @@ static int run_image_pyramid(pbd_handle* h, const uint8_t* d_src, int stride) {
 
 static int run_hog(pbd_handle* h) {
   uint16_t* split = h->split_parts ? h->d_feat_split : nullptr;
-  launch_hog(h->d_hog_tiles, h->n_hog_tiles, h->d_levels, h->d_pyr, h->d_feat, h->ts, h->fcn, h->md.sbin, h->hog_tc, h->d_hog_lut, split, h->split_parts, h->fdepth, h->stream);
+  launch_hog(h->d_hog_tiles, h->n_hog_tiles, h->d_hog_levels, h->d_pyr, h->d_feat, h->ts, h->fcn, h->md.sbin, h->hog_tc, h->d_hog_lut, split, h->split_parts, h->fdepth, h->stream);
+  // boundary padding: the border ring of every level, on every frame — the compact plan's DP reuses the feature memory, and
+  // pbd_set_level_features may have left a caller's border there (a frame's result never depends on what ran before it)
+  if (h->pad > 0) launch_featpad(h->d_padjobs, h->d_padblocks, h->n_padblocks, h->d_feat, h->ts, split, h->split_parts, h->stream);
   LAUNCHCHK(h, "HOG");
   h->feat_split_ok = split != nullptr;
   h->have_feat = true;
@@ -455,7 +462,7 @@ static int run_argmin_enqueue(pbd_handle* h, bool filter = false) {
   launch_backtrack(h->d_cand_count, h->d_cand_rec, h->opt.max_candidates, h->d_back, h->md.ncomponents, h->d_parent,
                    h->d_plane0, h->d_nparts, h->max_parts, h->d_mix_rows, out, h->cand_stride, h->ts, h->d_flat,
                    h->d_depth, h->max_depth, (int)h->parts.size(), h->d_scr_base, h->d_dt_ixT, h->d_dt_iy,
-                   h->opt.dt_correct_ptr, h->ext_ptr ? h->d_extx : nullptr, h->d_exty, h->d_ext_base, count_out, h->stream);
+                   h->opt.dt_correct_ptr, h->ext_ptr ? h->d_extx : nullptr, h->d_exty, h->d_ext_base, count_out, h->pad, h->stream);
   if (post) return pbd_i_post_enqueue(h, cm, zf, out);
   LAUNCHCHK(h, "argmin");
   if (zero_copy) { h->pending = true; h->out_on_host = true; return PBD_OK; }
@@ -711,6 +718,19 @@ int pbd_set_levels(pbd_handle* h, const int32_t* levels, int n) {
   free_frame(h);   // the work tables are per geometry AND level set: re-planned on the next frame
   return PBD_OK;
 }
+// Boundary padding (include/pbd_c.h): the plan — buffers, work tables, captured graph — is per padding, dropped like pbd_set_levels does
+int pbd_set_boundary_pad(pbd_handle* h, int pad) {
+  if (!h) return PBD_ERR_ARG;
+  if (pad < 0 || pad > 8) return fail(h, PBD_ERR_ARG, "boundary pad: 0 (off) .. 8 cells");
+  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (pad == h->pad) return PBD_OK;
+  ON_DEVICE(h);
+  hipStreamSynchronize(h->stream);
+  h->pad = pad;
+  free_frame(h);
+  return PBD_OK;
+}
+int pbd_get_boundary_pad(const pbd_handle* h) { return h ? h->pad : 0; }
 int pbd_max_parts(const pbd_handle* h) { return h ? h->max_parts : 0; }
 
 int pbd_set_stream(pbd_handle* h, void* s) {
@@ -947,6 +967,7 @@ int pbd_pyramid_geometry(const pbd_handle* h, int w, int hgt, int* nlevels, int3
   static thread_local Level lv[PBD_MAX_LEVELS];
   int n = 0;
   if (w < 3 || hgt < 3 || compute_geometry(w, hgt, h->md.sbin, h->md.interval, &n, lv)) return PBD_ERR_ARG;
+  pad_geometry(h->pad, n, lv);   // (the planes of a padded handle: what the stage getters and setters address)
   *nlevels = n;
   for (int l = 0; l < n; ++l) {
     if (img_w) img_w[l] = lv[l].iw;

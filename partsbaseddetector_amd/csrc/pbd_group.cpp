@@ -274,6 +274,15 @@ int pbd_group_set_candidate_filter(pbd_group* g, int mode, float overlap) {
   g->cand_overlap = overlap;
   return PBD_OK;
 }
+// every member gets the padding (checked first: nothing changes unless all accept)
+int pbd_group_set_boundary_pad(pbd_group* g, int pad) {
+  if (!g) return PBD_ERR_ARG;
+  if (pad < 0 || pad > 8) return gfail(g, PBD_ERR_ARG, "boundary pad: 0 (off) .. 8 cells");
+  for (pbd_handle* h : g->m)
+    if (h->pending) return gfail(g, PBD_ERR_STATE, "a frame is in flight");
+  for (size_t i = 0; i < g->m.size(); ++i) GMEMBER(g, i, pbd_set_boundary_pad(g->m[i], pad));
+  return PBD_OK;   // (a level sharding of pbd_group_detect_u8 stays: the padding changes the levels' cell counts, not which levels there are)
+}
 pbd_handle* pbd_group_member(pbd_group* g, int i) { return (g && i >= 0 && i < (int)g->m.size()) ? g->m[i] : nullptr; }
 
 static int all_levels(pbd_group* g) {   // undo a level sharding left behind by pbd_group_detect_u8

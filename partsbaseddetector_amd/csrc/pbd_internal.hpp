@@ -130,6 +130,10 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   char* d_dt_tmpT = nullptr; char* d_dt_sdt = nullptr; int16_t* d_dt_ixT = nullptr; int16_t* d_dt_iy = nullptr;
   size_t dt_cap_elems = 0;
   LevelDev* d_levels = nullptr;
+  // boundary padding (pbd_set_boundary_pad; HostModel::pad): k_hog's view of the levels (padded pitch, the interior's first cell; d_levels
+  // itself without padding) and the border ring's work table (k_featpad.hip)
+  LevelDev* d_hog_levels = nullptr;
+  PadJob* d_padjobs = nullptr; ReduceBlock* d_padblocks = nullptr; int n_padblocks = 0;
   HogTile* d_hog_tiles = nullptr; int n_hog_tiles = 0; int hog_tc = 16;
   ConvTile* d_conv_tiles = nullptr; int n_conv_tiles = 0;
   ConvTile* d_conv_tiles_mix = nullptr;   // mixed banks: [group][n_conv_tiles], pad = n0 | (nf_g << 16)
@@ -401,6 +405,8 @@ void launch_hog(const HogTile* tiles, int ntiles, const LevelDev* levels, const 
 // the image depths beyond 8 bits (k_pyramid.hip): job offsets in bytes, sstride in bytes
 void launch_resize_any(const PyrJob* jobs, int njobs, int maxpix, int cn, int depth, int sstride, const uint8_t* src, uint8_t* pyr, hipStream_t s);
 void launch_pyrdown_any(const PyrJob* jobs, int njobs, int maxpix, int cn, int depth, uint8_t* pyr, hipStream_t s);
+// the border ring of the boundary padding (k_featpad.hip): 0, and 1 in channel flen - 1, of every ring cell; split: as launch_hog's
+void launch_featpad(const PadJob* jobs, const ReduceBlock* blocks, int nblocks, void* feat, int ts, uint16_t* split, int split_parts, hipStream_t s);
 size_t hog_binlut_bytes();                                        // orientation-snap table: best_o for every (dx, dy) in [-255, 255]^2
 void launch_hog_binlut(uint8_t* lut, int ts, hipStream_t s);      // evaluated in T (ts = sizeof(T)) with the reference's own chain (k_hog.hip)
 // split-product filter bank (k_conv_split.hip): fp32 features -> three exact bfloat16 parts; kh x kw x 32 filters, float responses
@@ -438,7 +444,7 @@ void launch_backtrack(const int* count, const CandRec* rec, int capacity, const 
                       const int* parent, const int* plane0, const int* nparts, int max_parts, const int* mix_rows,
                       char* out, size_t out_stride, int ts, const int* flat, const int* depth, int max_depth, int nflat,
                       const unsigned long long* scr_base, const int16_t* ix, const int16_t* iy, int correct_ptr,
-                      const int16_t* extx, const int16_t* exty, const unsigned long long* ext_base, int* count_out, hipStream_t s);
+                      const int16_t* extx, const int16_t* exty, const unsigned long long* ext_base, int* count_out, int pad, hipStream_t s);   // pad: the boundary padding (box origin)
 void dt_debug_read(unsigned long long* out);
 void dt_debug_counters(unsigned long long* out);   // probe build: k_dt_pass path counters, read and reset (zeros elsewhere)
 int dt_debug_trace(unsigned long long* t, unsigned* hw, int* nlaunch);   // probe build only

@@ -46,6 +46,11 @@ int compute_geometry(int w, int h, int sbin, int interval, int* nlevels, Level* 
   return 0;
 }
 
+void pad_geometry(int pad, int nlevels, Level* lv) {
+  for (int l = 0; l < nlevels; ++l)
+    if (lv[l].cw > 0 && lv[l].ch > 0) { lv[l].cw += 2 * pad; lv[l].ch += 2 * pad; }
+}
+
 int depth_esz(int depth) { return depth == PBD_DEPTH_8U ? 1 : depth == PBD_DEPTH_16U ? 2 : depth == PBD_DEPTH_32F ? 4 : depth == PBD_DEPTH_64F ? 8 : 0; }
 
 // ---------------------------------------------------------------------------
@@ -330,6 +335,7 @@ int plan_layout(const HostModel& hm, const FrameSpec& f, FrameLayout& out, std::
   if (f.w < 3 || f.h < 3 || compute_geometry(f.w, f.h, m.sbin, m.interval, &n1, lv.data()))
     return fail(err, PBD_ERR_ARG, "image too small: the pyramid needs at least `interval` levels "
                                   "(src/HOGFeatures.cpp:99,114)");
+  pad_geometry(hm.pad, n1, lv.data());
   // A batch of B same-sized frames is planned as B x nlevels "virtual levels" (frame f's level l = f * nlevels + l)
   const int n = n1 * f.batch;
   out.nlevels = n1; out.batch = f.batch; out.nvl = n;
@@ -557,8 +563,8 @@ static int hog_conv_tiles(const HostModel& hm, const FrameSpec& f, const FrameLa
   for (int l = 0; l < lay.nvl; ++l) {
     const Level& L = lay.lv[l];
     if (!has_cells(L)) continue;
-    for (int y = 0; y < L.ch; y += out.hog_tc)
-      for (int x = 0; x < L.cw; x += out.hog_tc) out.hog_tiles.push_back(HogTile{l, y, x, 0});
+    for (int y = 0; y < L.ch - 2 * hm.pad; y += out.hog_tc)   // (the interior: the border ring is k_featpad's)
+      for (int x = 0; x < L.cw - 2 * hm.pad; x += out.hog_tc) out.hog_tiles.push_back(HogTile{l, y, x, 0});
     for (int y = 0; y < L.ch; y += 16)
       for (int x = 0; x < L.cw; x += 16) ct.push_back(ConvTile{l, y, x, 0});
   }
@@ -851,6 +857,17 @@ int plan_tables(const HostModel& hm, const FrameSpec& f, const FrameLayout& lay,
   pyramid_jobs(hm, f, lay, out);
   for (const Level& L : lay.lv)
     out.levels.push_back(LevelDev{L.iw, L.ih, L.bw, L.bh, L.cw, L.ch, (unsigned long long)L.img_off, (unsigned long long)L.cell_off});
+  if (hm.pad > 0)
+    for (int l = 0; l < lay.nvl; ++l) {
+      const Level& L = lay.lv[l];
+      const int pad = hm.pad;
+      out.hog_levels.push_back(LevelDev{L.iw, L.ih, L.bw, L.bh, L.cw, L.ch, (unsigned long long)L.img_off,
+                                        (unsigned long long)(L.cell_off + (size_t)pad * L.cw + pad)});
+      if (!has_cells(L)) continue;
+      const int nring = L.cw * L.ch - (L.cw - 2 * pad) * (L.ch - 2 * pad);
+      for (int r0 = 0; r0 < nring; r0 += PBD_FEATPAD_CPB) out.padblk.push_back(ReduceBlock{(int)out.padjobs.size(), (unsigned)r0});
+      out.padjobs.push_back(PadJob{(unsigned long long)L.cell_off, L.cw, L.ch, pad, nring});
+    }
   int rc = hog_conv_tiles(hm, f, lay, out, err);
   if (!rc) rc = dt_geometry(hm, lay, dt_geom, kn, out, err);
   if (rc) return rc;

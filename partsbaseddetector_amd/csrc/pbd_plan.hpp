@@ -36,6 +36,10 @@ struct LevelDev {    // per level, device copy
 // pad = n0 | (nf_g << 16): the group writes response planes n0 .. n0 + nf_g - 1 of the level's block (the MIX kernel
 // instantiations read it; their `nf` argument is then the level block's plane count, the whole bank's)
 struct ConvTile { int level, y0, x0, pad; };
+// boundary padding (pbd_set_boundary_pad, k_featpad.hip): the border ring of one level — the cells of its cw x ch plane outside the
+// interior (cw - 2 pad) x (ch - 2 pad), nring of them, in row-major order
+struct PadJob { unsigned long long cell_off; int cw, ch, pad, nring; };
+#define PBD_FEATPAD_CPB 64   // ring cells per block of k_featpad (ReduceBlock{job, first ring cell})
 
 // Score data is T = float or double (the handle's instantiation, pbd_options.scalar_type); the work
 // tables carry untyped pointers and the kernels are instantiated for both.
@@ -125,6 +129,7 @@ static_assert(sizeof(PyrJob) == 32, "PyrJob layout");
 static_assert(sizeof(HogTile) == 16, "HogTile layout");
 static_assert(sizeof(LevelDev) == 40, "LevelDev layout");
 static_assert(sizeof(ConvTile) == 16, "ConvTile layout");
+static_assert(sizeof(PadJob) == 24, "PadJob layout");
 static_assert(sizeof(DtMap) == 56, "DtMap layout");
 static_assert(sizeof(DtGroup) == 56, "DtGroup layout");
 static_assert(sizeof(DtTask) == 80, "DtTask layout");
@@ -168,6 +173,7 @@ struct HostModel {
   int ts = 4;                // sizeof(T): 4 = PartsBasedDetector<float>, 8 = PartsBasedDetector<double>
   int conv_mode = PBD_CONV_EXACT;   // resolved: never PBD_CONV_AUTO
   int split_parts = 0;       // 3: PBD_CONV_SPLIT (bfloat16 parts), 2: PBD_CONV_SPLIT_F16 (binary16 parts), 0: no split bank
+  int pad = 0;               // pbd_set_boundary_pad: cells of padding around every level's feature map (0: off, the reference's state)
   int nms_sz = 0;            // pbd_options.reserved[0]: window of the score-map NMS in front of the back-tracking (0: off, the reference's state)
   int max_parts = 0, nslots = 0, nplanes = 0;
   std::vector<PartInfo> parts;                 // flat parts
@@ -232,6 +238,11 @@ struct FrameTables {
   std::vector<PyrJob> pyrjobs;                   // resize jobs, then the pyrDown jobs octave by octave
   std::vector<PyrLaunch> pyr_launches;           // [0]: resize, [1..]: pyrDown octave steps
   std::vector<LevelDev> levels;
+  // boundary padding only (else empty): the levels as k_hog addresses them — cw is the padded pitch and cell_off the interior's first
+  // cell (cell_off + pad * cw + pad), so the kernel's store needs no offset of its own — and the border ring's jobs / blocks
+  std::vector<LevelDev> hog_levels;
+  std::vector<PadJob> padjobs;
+  std::vector<ReduceBlock> padblk;               // k_featpad: one block per PBD_FEATPAD_CPB ring cells of a job
   int hog_tc = 16;
   std::vector<HogTile> hog_tiles;
   std::vector<ConvTile> conv_tiles, conv_tiles_mix;   // mixed banks: [group][conv tile], pad = n0 | (nf_g << 16)
@@ -268,4 +279,7 @@ DtMap dt_map(const void* src, void* dst, int16_t* ptr, float wq, float wl, int o
 
 // pyramid geometry of one frame (HOGFeatures<T>::pyramid): 0, or -1 when the frame has fewer than `interval` or more than PBD_MAX_LEVELS levels
 int compute_geometry(int w, int h, int sbin, int interval, int* nlevels, Level* lv);
+// boundary padding: every level that has cells grows by `pad` cells on each side (copyMakeBorder(feature, padded, pad, pad, pad * flen,
+// pad * flen, ...), src/HOGFeatures.cpp:147); bw / bh stay the HOG blocks, the interior is (bw - 2) x (bh - 2)
+void pad_geometry(int pad, int nlevels, Level* lv);
 int depth_esz(int depth);   // bytes per element of a PBD_DEPTH_* image; 0: unsupported

@@ -1,0 +1,24 @@
+// pbd_split.hpp — a feature's operands for the split-product filter banks (k_conv_split.hip), one definition for every kernel that
+// writes features on the device: k_hog's epilogue (the interior cells) and k_featpad (the border ring of the boundary padding).
+#pragma once
+#include <stdint.h>
+#ifdef __HIPCC__
+// PBD_CONV_SPLIT: v = h + m + l, three exact bfloat16 parts (round to nearest even, every subtraction exact); part q at sp[q * stride]
+__device__ __forceinline__ void feat_split_bf16(float v, uint16_t* sp, int stride) {
+  float r = v;
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    const unsigned u = __float_as_uint(r);
+    const unsigned hb = (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+    sp[q * stride] = (uint16_t)hb;
+    r = r - __uint_as_float(hb << 16);
+  }
+}
+// PBD_CONV_SPLIT_F16: two binary16 parts of v 2^12 (k_feat_split16); part q at sp[q * stride]
+__device__ __forceinline__ void feat_split_f16(float v, _Float16* sp, int stride) {
+  const float x = v * 4096.f;
+  const _Float16 hv = (_Float16)x;
+  sp[0] = hv;
+  sp[stride] = (_Float16)(x - (float)hv);
+}
+#endif

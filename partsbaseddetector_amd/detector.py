@@ -242,6 +242,7 @@ class PartsBasedDetector:
         self._camera = None                      # setBoundingBoxes3D: None = off
         self._cluster_tol: Optional[float] = None   # setObjectClusters: None = off
         self._part_scores = False                # setPartScores
+        self._boundary_pad = 0                   # setBoundaryPad
         self._dtype = np.dtype(dtype)
         self._lb, self._le = level_begin, level_end
         self._h: Optional[capi.Handle] = None
@@ -268,6 +269,26 @@ class PartsBasedDetector:
             self._h.set_cluster3d(True, self._cluster_tol)
         if self._part_scores:
             self._h.set_part_scores(True)
+        if self._boundary_pad:
+            self._h.set_boundary_pad(self._boundary_pad)
+
+    @property
+    def boundary_pad(self) -> int:
+        """cells of boundary padding around every pyramid level (setBoundaryPad); 0 = off"""
+        return self._boundary_pad
+
+    def setBoundaryPad(self, pad: int = 3) -> None:
+        """The step src/HOGFeatures.cpp:147-148 leaves commented out: every pyramid level surrounded by `pad` cells that hold 0 and,
+        in the last channel, 1 — the value the models' last channel is trained on for cells outside the image
+        (matlab/detection/featpyramid.m:37-44) — so that a detection may reach over the frame border.  Boxes are shifted back by the
+        padding (matlab/detection/detect.m:266-267); feature / response planes and part locations are those of the padded levels.
+        0 = off (the default), 3 = the reference's literal, at most 8.  Kept across distributeModel()."""
+        pad = int(pad)
+        if not 0 <= pad <= 8:
+            raise ValueError("setBoundaryPad: 0 (off) .. 8 cells")
+        if self._h is not None:
+            self._h.set_boundary_pad(pad)
+        self._boundary_pad = pad
 
     def setPartScores(self, on: bool = True) -> None:
         """Every detect() fills Candidate.confidence[p], p >= 1, with the part's own score (appearance + deformation + bias of

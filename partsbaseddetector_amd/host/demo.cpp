@@ -20,9 +20,10 @@ using namespace pbd;
 //             from pdf(), and the tables min() returns are edited before argmin() (a root score raised, part 1's x
 //             pointer at that cell redirected): the candidates must be those of the edited tables.
 template <typename T>
-static void run(Model& model, const Mat& im, bool stagewise, int special = 0, const char* io_file = nullptr, bool part_scores = false) {
+static void run(Model& model, const Mat& im, bool stagewise, int special = 0, const char* io_file = nullptr, bool part_scores = false, int pad = 0) {
   PartsBasedDetector<T> pbd(0, PBD_CONV_EXACT);
   pbd.setPartScores(part_scores);
+  pbd.setBoundaryPad(pad);
   pbd.distributeModel(model);
   vectorCandidate candidates;
   if (stagewise) {
@@ -98,14 +99,23 @@ static void run(Model& model, const Mat& im, bool stagewise, int special = 0, co
 
 int main(int argc, char** argv) {
   bool part_scores = false;   // --part-scores (anywhere): per detection, the re-scored total, the root score and the weakest part
+  int pad = 0;                // --pad N (anywhere): N cells of boundary padding around every pyramid level (0: off)
   for (int i = 1; i < argc; ++i)
+    if (std::string(argv[i]) == "--pad") {
+      char* end = nullptr;
+      const long v = i + 1 < argc ? strtol(argv[i + 1], &end, 10) : -1;
+      if (i + 1 >= argc || !*argv[i + 1] || *end || v < 0 || v > 8) { printf("--pad N: 0 (off) .. 8 cells\n"); exit(-1); }
+      pad = (int)v;
+      for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+      argc -= 2; --i;
+    } else
     if (std::string(argv[i]) == "--part-scores") {
       part_scores = true;
       for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
       --argc; --i;
     }
   if (argc < 6 || argc > 8) {
-    printf("Usage: pbd_demo model_file image.raw width height channels [stagewise|double|stagewise-double] [--part-scores]\n");
+    printf("Usage: pbd_demo model_file image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N]\n");
     exit(-1);
   }
   // determine the type of model to read (src/demo.cpp:63-82)
@@ -131,8 +141,8 @@ int main(int argc, char** argv) {
   const bool stagewise = special || mode.find("stagewise") != std::string::npos;
   try {
     if (part_scores && stagewise) { printf("--part-scores: the fused detect() only\n"); exit(-1); }
-    if (mode.find("double") != std::string::npos) run<double>(model, im, stagewise, 0, nullptr, part_scores);
-    else run<float>(model, im, stagewise, special, special ? argv[7] : nullptr, part_scores);
+    if (mode.find("double") != std::string::npos) run<double>(model, im, stagewise, 0, nullptr, part_scores, pad);
+    else run<float>(model, im, stagewise, special, special ? argv[7] : nullptr, part_scores, pad);
   } catch (const Exception& e) {
     printf("error %d: %s\n", e.code, e.what());
     return 1;

@@ -347,6 +347,8 @@ class Device {
   void setDepthFilter(bool on, float zfactor) { check(pbd_set_depth_filter(h, on ? 1 : 0, zfactor)); }
   // per-part scores of every record detect() returns, on the GPU
   void setPartScores(bool on) { check(pbd_set_part_scores(h, on ? 1 : 0)); }
+  // padded feature pyramid with the boundary-occlusion feature (src/HOGFeatures.cpp:147-148): pad cells around every level, 0 = off
+  void setBoundaryPad(int pad) { check(pbd_set_boundary_pad(h, pad)); }
 };
 
 // ---- include/IFeatures.hpp:49-73 --------------------------------------------------------------
@@ -366,6 +368,9 @@ class HipHOGFeatures : public IFeatures {          // include/HOGFeatures.hpp:52
   size_t binsize() const override { return binsize_; }
   size_t nscales() const override { return nscales_; }
   vectorf scales() const override { return scales_; }
+  // The lines src/HOGFeatures.cpp:147-148 leave commented out — copyMakeBorder(feature, padded, 3, 3, ...) + boundaryOcclusionFeature(padded,
+  // flen_, 3) — for every level, on the GPU: pyramid() then hands out the padded features (0 = off, the default; 3 = the reference's literal)
+  void setBoundaryPad(int pad) { dev_->setBoundaryPad(pad); }
   void pyramid(const Mat& im, vectorMat& pyrafeatures) override {   // src/HOGFeatures.cpp:95-151
     // :136-146 dispatches features<uint8_t | uint16_t | float | double> on im.depth(); any other depth: StsUnsupportedFormat (the library refuses it)
     dev_->check(pbd_pyramid_image(dev_->h, im.ptr<uint8_t>(), im.depth(), im.cols, im.rows, im.channels(), (int)im.step()));
@@ -630,6 +635,7 @@ class PartsBasedDetector {
   int cand_mode_ = PBD_CAND_RAW; float cand_overlap_ = 0.f;
   bool depth_on_ = false; float zfactor_ = 0.03f;
   bool part_scores_on_ = false;
+  int boundary_pad_ = 0;
   // the last detect's per-part scores -> the `n` candidates it appended: fills Candidate::confidence_ of the non-root parts
   void attach_part_scores(vectorCandidate& candidates, int n, int mp) {
     if (!part_scores_on_ || n == 0) return;
@@ -663,6 +669,16 @@ class PartsBasedDetector {
     if (cand_mode_ != PBD_CAND_RAW) dev_->setCandidateFilter(cand_mode_, cand_overlap_);
     if (depth_on_) dev_->setDepthFilter(true, zfactor_);
     if (part_scores_on_) dev_->setPartScores(true);
+    if (boundary_pad_) dev_->setBoundaryPad(boundary_pad_);
+  }
+  // The third step detect()'s author left commented out (src/HOGFeatures.cpp:147-148): every pyramid level surrounded by `pad` cells
+  // that hold 0 and, in the last channel, 1 — the "outside the image" value the models are trained with (matlab/detection/
+  // featpyramid.m:37-44) — so that detections may reach over the frame border; boxes are shifted back by the padding
+  // (matlab/detection/detect.m:266-267).  0 (the default): off; 3: the reference's literal.  Kept across distributeModel().
+  void setBoundaryPad(int pad) {
+    if (pad < 0 || pad > 8) throw Exception(PBD_ERR_ARG, "setBoundaryPad: 0 (off) .. 8 cells");
+    if (dev_) dev_->setBoundaryPad(pad);
+    boundary_pad_ = pad;
   }
   // The record promises a confidence per part (include/Candidate.hpp:54-72); the reference stores 0.0 for every part but the
   // root (src/DynamicProgram.cpp:241-244).  On: Candidate::confidence()[p], p >= 1, is the part's own score — appearance +
