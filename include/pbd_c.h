@@ -321,6 +321,13 @@ int pbd_get_level_features(pbd_handle* h, int level, float* out /* cell_h*cell_w
  *  PBD_CONV_SPLIT_F16: |f| < 16 — with PBD_ERR_ARG; nothing is uploaded then)                                          */
 int pbd_set_level_features(pbd_handle* h, int level, const float* in);
 int pbd_get_level_features_f64(pbd_handle* h, int level, double* out);
+/* Read-only: the level image (own depth) and the features of ONE frame of the current plan, 0 <= frame < frames of the plan.  Unlike the
+ * stage entry points these also answer for a batch plan (pbd_detect_batch_*), where frame f's planes are what the batched launches
+ * wrote for it; on a single-frame plan frame is 0 and they equal pbd_get_level_image_raw / pbd_get_level_features.  PBD_ERR_STATE as
+ * for those (stage not computed, compact memory plan after min(), level not processed, wrong scalar type).                            */
+int pbd_get_frame_level_image_raw(pbd_handle* h, int frame, int level, void* out, size_t out_bytes);
+int pbd_get_frame_level_features(pbd_handle* h, int frame, int level, float* out);
+int pbd_get_frame_level_features_f64(pbd_handle* h, int frame, int level, double* out);
 int pbd_set_level_features_f64(pbd_handle* h, int level, const double* in);
 /* declare a frame geometry without running the pyramid (inject features)     */
 int pbd_begin_frame(pbd_handle* h, int w, int hgt, int cn);

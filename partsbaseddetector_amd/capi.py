@@ -52,6 +52,7 @@ EXPORTS = [
     "pbd_set_cluster3d", "pbd_get_cluster3d", "pbd_candidates_cluster3d",
     "pbd_set_part_scores", "pbd_get_part_scores", "pbd_candidates_part_scores",
     "pbd_set_boundary_pad", "pbd_get_boundary_pad", "pbd_group_set_boundary_pad",
+    "pbd_get_frame_level_image_raw", "pbd_get_frame_level_features", "pbd_get_frame_level_features_f64",
 ]
 PBD_ABI_VERSION = 5
 
@@ -592,6 +593,16 @@ class Handle:
         out = np.zeros((g["cell_h"][l], g["cell_w"][l], 32), self.dtype)
         self._chk(self._fn("pbd_get_level_features")(self.h, l, _p(out, self._ct)))
         return out
+
+    def frame_planes(self, frame, l, w, hgt, cn=3, imdtype=np.uint8):
+        """pbd_get_frame_level_image_raw / pbd_get_frame_level_features: (level image, features) of one frame of the current plan — a batch
+        plan included — for a plan of w x hgt x cn frames of pixel type imdtype.  Read-only; needs no earlier pyramid() on this object."""
+        g = self.geometry(w, hgt)
+        img = np.zeros((g["img_h"][l], g["img_w"][l]) + ((cn,) if cn > 1 else ()), np.dtype(imdtype))
+        feat = np.zeros((g["cell_h"][l], g["cell_w"][l], 32), self.dtype)
+        self._chk(self.L.pbd_get_frame_level_image_raw(self.h, int(frame), int(l), img.ctypes.data_as(C.c_void_p), C.c_size_t(img.nbytes)))
+        self._chk(self._fn("pbd_get_frame_level_features")(self.h, int(frame), int(l), _p(feat, self._ct)))
+        return img, feat
 
     def set_level_features(self, l, f):
         f = np.ascontiguousarray(f, self.dtype)

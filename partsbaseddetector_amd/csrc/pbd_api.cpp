@@ -1077,6 +1077,39 @@ static int set_level_features_(pbd_handle* h, int level, const void* in, int ts)
   }
   return PBD_OK;
 }
+// Read-only view of ONE frame of the current plan, batch plans included (frame f's level l is virtual level f * nlevels + l):
+// what k_pyramid / k_hog wrote for that frame.  The single-frame getters above keep refusing batch plans.
+#define CHECK_FRAME_LEVEL(h, frame, level)                                        \
+  if (!(h)) return PBD_ERR_ARG;                                                   \
+  if ((h)->fw == 0) return fail(h, PBD_ERR_STATE, "no frame geometry");           \
+  if ((frame) < 0 || (frame) >= (h)->batch) return fail(h, PBD_ERR_ARG, "frame out of range");   \
+  if ((level) < 0 || (level) >= (h)->nlevels) return fail(h, PBD_ERR_ARG, "level out of range");
+int pbd_get_frame_level_image_raw(pbd_handle* h, int frame, int level, void* out, size_t out_bytes) {
+  CHECK_FRAME_LEVEL(h, frame, level);
+  if (!out) return PBD_ERR_ARG;
+  if (!h->have_pyr) return fail(h, PBD_ERR_STATE, "pyramid not computed");
+  const Level& L = h->lv[(size_t)frame * h->nlevels + level];
+  const size_t bytes = (size_t)L.iw * L.ih * h->fcn * h->fesz;
+  if (out_bytes < bytes) return fail(h, PBD_ERR_CAPACITY, "pbd_get_frame_level_image_raw: iw * ih * cn * element size bytes");
+  ON_DEVICE(h);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemcpy(out, h->d_pyr + L.img_off, bytes, hipMemcpyDeviceToHost));
+  return PBD_OK;
+}
+static int get_frame_level_features_(pbd_handle* h, int frame, int level, void* out, int ts) {
+  CHECK_FRAME_LEVEL(h, frame, level);
+  CHECK_SCALAR(h, ts);
+  if (!out) return PBD_ERR_ARG;
+  if (!h->have_feat) return fail(h, PBD_ERR_STATE, "features not computed");
+  const Level& L = h->lv[(size_t)frame * h->nlevels + level];
+  if (!L.active) return fail(h, PBD_ERR_STATE, "level is not processed by this handle (pbd_set_levels / level_begin..level_end)");
+  ON_DEVICE(h);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemcpy(out, h->d_feat + L.cell_off * PBD_FLEN * ts, (size_t)L.cw * L.ch * PBD_FLEN * ts, hipMemcpyDeviceToHost));
+  return PBD_OK;
+}
+int pbd_get_frame_level_features(pbd_handle* h, int frame, int level, float* out) { return get_frame_level_features_(h, frame, level, out, 4); }
+int pbd_get_frame_level_features_f64(pbd_handle* h, int frame, int level, double* out) { return get_frame_level_features_(h, frame, level, out, 8); }
 int pbd_get_level_features(pbd_handle* h, int level, float* out) { return get_level_features_(h, level, out, 4); }
 int pbd_get_level_features_f64(pbd_handle* h, int level, double* out) { return get_level_features_(h, level, out, 8); }
 int pbd_set_level_features(pbd_handle* h, int level, const float* in) { return set_level_features_(h, level, in, 4); }
