@@ -171,7 +171,44 @@ static int dev_upload(pbd_handle* h, T** p, const std::vector<T>& v) {
   return PBD_OK;
 }
 
-static void free_frame(pbd_handle* h) {
+// ---- stage state: the ONE place the validity flags of the frame's planes change.  A run_* stage calls its transition behind its
+// launches, a replayed graph (enqueue_all) the same four in stage order, and so do the setters that hand a whole stage in.
+// Compact plan: validity of the stage planes the DP overwrites (pbd_internal.hpp).  all = true: a producer stage has just
+// written every plane; false: min() has just reused the memory.
+static void compact_mark_feat(pbd_handle* h, bool all) { if (h->compact) h->feat_ok.assign((size_t)h->nvl, all ? 1 : 0); }
+static void compact_mark_resp(pbd_handle* h, bool all) { if (h->compact) h->resp_ok.assign((size_t)h->nvl * h->md.nfilters, all ? 1 : 0); }
+// nothing of the plan's geometry has been computed or handed in (a new plan, pbd_begin_frame)
+static void reset_stages(pbd_handle* h) {
+  h->have_pyr = h->have_feat = h->have_resp = h->have_dp = false;
+  h->min_ran = false;
+  h->feat_ok.clear(); h->resp_ok.clear(); h->ext_set.clear(); h->root_set.clear();   // (sized again by whoever marks a plane next)
+}
+static void mark_pyramid(pbd_handle* h) {
+  h->have_pyr = true;
+  if (h->compact) h->have_dp = h->min_ran = false;   // the level images + features share their memory with the Ik planes / the x pass's scratch:
+                                                     // the previous min()'s tables are gone (a plane handed in later is then NOT on top of a min())
+}
+// split_written: the split-product bank's copy of the features was written with them (k_hog's epilogue)
+static void mark_features(pbd_handle* h, bool split_written) {
+  h->feat_split_ok = split_written;
+  h->have_feat = true;
+  compact_mark_feat(h, true);
+  if (h->compact) h->have_dp = h->min_ran = false;
+}
+static void mark_responses(pbd_handle* h) { h->have_resp = true; compact_mark_resp(h, true); }
+static void mark_min(pbd_handle* h, bool timed) {
+  h->dp_timed = timed;
+  h->have_dp = h->min_ran = true;
+  h->ext_ptr = h->root_dirty = false;   // back-tracking reads this min()'s own tables again, thresholded by it
+  if (h->compact) {     // their memory now holds the DP's planes: every feature / response plane is stale until produced or handed in again
+    h->have_pyr = h->have_feat = h->have_resp = false;
+    h->feat_split_ok = false;   // (the split bank's copy of the features shared the x pass's pointer planes)
+    compact_mark_feat(h, false);
+    compact_mark_resp(h, false);
+  }
+}
+
+void free_frame(pbd_handle* h) {
   drop_graph(h);   // the captured launches point into the buffers freed below
   h->frames_on_plan = 0;
   for (void* p : h->frame_allocs) hipFree(p);
@@ -180,16 +217,10 @@ static void free_frame(pbd_handle* h) {
   h->d_extx = h->d_exty = nullptr; h->d_ext_base = nullptr; h->ext_ptr = false;
   h->d_cf_mask = nullptr; h->cf_mask_bytes = 0;
   h->fw = h->fh = h->fcn = 0; h->fdepth = 0; h->fesz = 1;
-  h->have_pyr = h->have_feat = h->have_resp = h->have_dp = false;
-  h->min_ran = false;
+  reset_stages(h);
   h->feat_split_ok = false;
-  h->feat_ok.clear(); h->resp_ok.clear(); h->ext_set.clear(); h->root_set.clear();
 }
 
-// Compact plan: validity of the stage planes the DP overwrites (pbd_internal.hpp).  all = true: a producer stage has just
-// written every plane; false: min() has just reused the memory.
-static void compact_mark_feat(pbd_handle* h, bool all) { if (h->compact) h->feat_ok.assign((size_t)h->nvl, all ? 1 : 0); }
-static void compact_mark_resp(pbd_handle* h, bool all) { if (h->compact) h->resp_ok.assign((size_t)h->nvl * h->md.nfilters, all ? 1 : 0); }
 static bool all_active_set(const pbd_handle* h, const std::vector<char>& v, int per_level) {
   if (v.size() != (size_t)h->nvl * per_level) return false;
   for (int l = 0; l < h->nvl; ++l) {
@@ -211,7 +242,7 @@ static PlanKnobs read_plan_knobs() {
 }
 
 // The frame plan of one geometry (pbd_plan.cpp): buffers, then every work table, uploaded once and reused
-static int plan_frame(pbd_handle* h, int w, int hgt, int cn, int batch = 1, int depth = PBD_DEPTH_8U) {
+int plan_frame(pbd_handle* h, int w, int hgt, int cn, int batch, int depth) {
   if (h->fw == w && h->fh == hgt && h->fcn == cn && h->batch == batch && h->fdepth == depth) return PBD_OK;
   if (cn != 1 && cn != 3) return fail(h, PBD_ERR_UNSUPPORTED, "image: 1 or 3 channels");
   const int esz = depth_esz(depth);
@@ -279,9 +310,7 @@ static int run_image_pyramid(pbd_handle* h, const uint8_t* d_src, int stride) {
     else launch_pyrdown(h->d_pyrjobs + P.job0, P.njobs, P.maxw, P.maxh, h->fcn, h->d_pyr, h->stream);
   }
   LAUNCHCHK(h, "image pyramid");
-  h->have_pyr = true;
-  if (h->compact) h->have_dp = h->min_ran = false;   // the level images + features share their memory with the Ik planes / the x pass's scratch:
-                                                     // the previous min()'s tables are gone (a plane handed in later is then NOT on top of a min())
+  mark_pyramid(h);
   return PBD_OK;
 }
 
@@ -292,22 +321,24 @@ static int run_hog(pbd_handle* h) {
   // pbd_set_level_features may have left a caller's border there (a frame's result never depends on what ran before it)
   if (h->pad > 0) launch_featpad(h->d_padjobs, h->d_padblocks, h->n_padblocks, h->d_feat, h->ts, split, h->split_parts, h->stream);
   LAUNCHCHK(h, "HOG");
-  h->feat_split_ok = split != nullptr;
-  h->have_feat = true;
-  compact_mark_feat(h, true);
-  if (h->compact) h->have_dp = h->min_ran = false;
+  mark_features(h, split != nullptr);
   return PBD_OK;
+}
+
+// The split-product banks read the features as bfloat16 / binary16 parts: written by k_hog's epilogue; features handed in by the
+// caller (pbd_set_level_features) are split here, in front of the bank (a pass over 25 MB per frame)
+static void ensure_feat_split(pbd_handle* h) {
+  if (!h->split_parts || h->feat_split_ok) return;
+  if (h->split_parts == 2) launch_feat_split16((const float*)h->d_feat, h->d_feat_split, h->cells, h->stream);
+  else launch_feat_split((const float*)h->d_feat, h->d_feat_split, h->cells, h->stream);
+  h->feat_split_ok = true;
 }
 
 // A mixed bank: each size group runs the kernel a uniform bank of its size and the handle's mode runs (the run-time-size
 // instantiation, MIX: writing planes n0 .. n0 + nf_g - 1 of every level block of md.nfilters planes), one launch per group.
 static int run_pdf_mixed(pbd_handle* h) {
   const pbd_model_desc& m = h->md;
-  if (h->split_parts && !h->feat_split_ok) {
-    if (h->split_parts == 2) launch_feat_split16((const float*)h->d_feat, h->d_feat_split, h->cells, h->stream);
-    else launch_feat_split((const float*)h->d_feat, h->d_feat_split, h->cells, h->stream);
-    h->feat_split_ok = true;
-  }
+  ensure_feat_split(h);
   for (size_t gi = 0; gi < h->groups.size(); ++gi) {
     const SizeGroup& g = h->groups[gi];
     const ConvTile* tiles = h->d_conv_tiles_mix + gi * h->n_conv_tiles;
@@ -326,28 +357,19 @@ static int run_pdf_mixed(pbd_handle* h) {
       launch_conv_exact(tiles, h->n_conv_tiles, h->d_levels, h->d_feat, g.d_wT, h->d_resp, h->ts, g.nf, g.nfpad, g.kh, g.kw, h->stream, m.nfilters);
   }
   LAUNCHCHK(h, "filter bank");
-  h->have_resp = true;
-  compact_mark_resp(h, true);
+  mark_responses(h);
   return PBD_OK;
 }
 
 static int run_pdf(pbd_handle* h) {
   const pbd_model_desc& m = h->md;
   if (h->mixed) return run_pdf_mixed(h);
+  ensure_feat_split(h);
   if (h->conv_mode == PBD_CONV_SPLIT_F16) {
-    if (!h->feat_split_ok) {
-      launch_feat_split16((const float*)h->d_feat, h->d_feat_split, h->cells, h->stream);
-      h->feat_split_ok = true;
-    }
     static const int svariant16 = PBD_PROBE_ENV("PBD_SPLIT_VARIANT") ? atoi(PBD_PROBE_ENV("PBD_SPLIT_VARIANT")) : 0;   // tuning builds
     launch_conv_split16(h->d_conv_tiles, h->n_conv_tiles, h->d_levels, h->d_feat_split, h->d_wS, (float*)h->d_resp, m.nfilters, m.kh, m.kw, h->d_split_oscale, svariant16, h->stream);
   } else if (h->conv_mode == PBD_CONV_SPLIT) {
-    // the features' three exact bfloat16 parts: written by k_hog's epilogue; features handed in by the caller (pbd_set_level_features)
-    // are split here (a pass over 25 MB per frame).  Then the bank on the bf16 matrix units
-    if (!h->feat_split_ok) {
-      launch_feat_split((const float*)h->d_feat, h->d_feat_split, h->cells, h->stream);
-      h->feat_split_ok = true;
-    }
+    // the bank on the bf16 matrix units, over the features' three exact bfloat16 parts
     static const int svariant = PBD_PROBE_ENV("PBD_SPLIT_VARIANT") ? atoi(PBD_PROBE_ENV("PBD_SPLIT_VARIANT")) : 0;   // tuning builds
     if (svariant == 6 && m.kh == 5 && m.kw == 5)
       launch_conv_split_persistent(h->d_conv_tiles, h->n_conv_tiles, h->d_levels, h->d_feat_split, h->d_wS, (float*)h->d_resp, m.nfilters, h->ncu, h->stream);
@@ -383,8 +405,7 @@ static int run_pdf(pbd_handle* h) {
   else
     launch_conv_exact(h->d_conv_tiles, h->n_conv_tiles, h->d_levels, h->d_feat, h->d_wT, h->d_resp, h->ts, m.nfilters, h->nfpad, m.kh, m.kw, h->stream);
   LAUNCHCHK(h, "filter bank");
-  h->have_resp = true;
-  compact_mark_resp(h, true);
+  mark_responses(h);
   return PBD_OK;
 }
 
@@ -420,18 +441,8 @@ static int run_dp_min(pbd_handle* h) {
   launch_root(h->d_rootjobs, h->d_rootblocks, h->n_rootblocks, (double)h->md.thresh, h->d_cand_count, h->d_cand_rec,
               h->opt.max_candidates, h->ts, h->d_foldjobs, h->d_biasw, 0, h->fold_mix, nullptr, nullptr, h->stream);
   if (dpt) hipEventRecord(h->ev_dp1, h->stream);
-  h->dp_timed = dpt;
   LAUNCHCHK(h, "DP min");
-  h->have_dp = true;
-  h->min_ran = true;
-  h->ext_ptr = false;   // back-tracking reads this min()'s own tables again
-  h->root_dirty = false;
-  if (h->compact) {     // their memory now holds the DP's planes: every feature / response plane is stale until produced or handed in again
-    h->have_pyr = h->have_feat = h->have_resp = false;
-    h->feat_split_ok = false;   // (the split bank's copy of the features shared the x pass's pointer planes)
-    compact_mark_feat(h, false);
-    compact_mark_resp(h, false);
-  }
+  mark_min(h, dpt);
   return PBD_OK;
 }
 
@@ -481,88 +492,6 @@ static int run_argmin_enqueue(pbd_handle* h, bool filter = false) {
   return PBD_OK;
 }
 
-// frame finished on the stream: timers, and the records beyond the first block (rare) fetched into h_cand_out.
-// `found` = the device-side count (h_cand_count[0], or the count a group gather delivered).
-int pbd_i_finish_frame(pbd_handle* h, int found) {
-  h->pending = false;
-  if (h->dp_timed && h->have_dp) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, h->ev_dp0, h->ev_dp1) == hipSuccess) { h->dp_ms_sum += ms; h->dp_frames++; }
-  }
-  const int n = std::min(found, h->opt.max_candidates);
-  const int first = h->out_on_host ? n : std::min(h->first_copy, h->opt.max_candidates);   // (zero-copy: every record is on the host already)
-  if (n > first) {
-    HIPCHK(h, hipMemcpyAsync(h->h_cand_out + h->cand_stride * first, h->d_cand_out + h->cand_stride * first,
-                             h->cand_stride * (n - first), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (!h->d_gsend) {
-      // this geometry / threshold yields more records than the first copy carries: size it for what was seen (+25 %), so
-      // that the following frames need no second copy and no second synchronisation.  The copy's size is baked into a
-      // captured graph: drop it, the next frame captures again (host cost of one capture, once).
-      h->first_copy = std::min(h->opt.max_candidates, n + n / 4 + 16);
-      drop_graph(h);
-    }
-  }
-  if (found > h->opt.max_candidates) return fail(h, PBD_ERR_CAPACITY, "device candidate capacity exceeded; raise pbd_options.max_candidates");
-  return PBD_OK;
-}
-
-// Candidate records (cand_stride bytes each, possibly from several handles of one group: recs[i] points at record i)
-// -> the caller's arrays, ordered like a single-threaded reference run: level, component, row-major root location.
-int pbd_i_emit(pbd_handle* h, const std::vector<const char*>& recs, pbd_candidate_head* heads, int32_t* boxes,
-               int32_t* locs, int capacity, bool ordered, std::vector<int>* order_out) {
-  const int mp = h->max_parts, n = (int)recs.size();
-  std::vector<int> order(n);
-  for (int i = 0; i < n; ++i) order[i] = i;
-  auto key = [&](int i, int k) -> int {
-    const pbd_candidate_head* hd = (const pbd_candidate_head*)recs[i];
-    const int32_t* lc = pbd_rec_locs(recs[i], mp);
-    return k == 0 ? hd->level : k == 1 ? hd->component : k == 2 ? lc[1] : lc[0];
-  };
-  if (!ordered)
-  std::sort(order.begin(), order.end(), [&](int a, int b) {
-    for (int k = 0; k < 4; ++k) { int ka = key(a, k), kb = key(b, k); if (ka != kb) return ka < kb; }
-    return false;
-  });
-  if (order_out) *order_out = order;
-  if (n > capacity) return fail(h, PBD_ERR_CAPACITY, "output capacity too small");
-  for (int i = 0; i < n; ++i) pbd_rec_get(recs[order[i]], mp, heads, boxes, locs, i);
-  return PBD_OK;
-}
-
-int pbd_i_found(const pbd_handle* h) { return h->out_filtered ? h->h_cf_cnt[1] : h->h_cand_count[0]; }
-
-static int collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* count) {
-  if (!h->pending) return fail(h, PBD_ERR_STATE, "collect without a pending detect");
-  if (h->d_gsend) return fail(h, PBD_ERR_STATE, "handle belongs to an RCCL-gathering pbd_group: collect through the group");
-  if (h->batch > 1) return fail(h, PBD_ERR_STATE, "a batch of frames is pending: collect it with pbd_detect_batch_collect");
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  const int found = pbd_i_found(h);
-  if (count) *count = found;
-  int rc = pbd_i_finish_frame(h, found);
-  if (rc) return rc;
-  std::vector<const char*> recs((size_t)found);
-  for (int i = 0; i < found; ++i) recs[i] = h->h_cand_out + h->cand_stride * i;
-  std::vector<int> order;
-  rc = pbd_i_emit(h, recs, heads, boxes, locs, capacity, h->out_filtered, h->b3_frame || h->ps_frame ? &order : nullptr);
-  if (rc) return rc;
-  if (h->ps_frame) {
-    pbd_i_ps_begin(h, 1);
-    pbd_i_ps_gather(h, 0, recs, order);
-  }
-  if (h->b3_frame) {
-    pbd_i_b3_begin(h, 1);
-    pbd_i_b3_gather(h, 0, recs, order);
-    if ((rc = pbd_i_b3_end(h))) return rc;
-  }
-  return PBD_OK;
-}
-int pbd_i_collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* count) {
-  return collect(h, heads, boxes, locs, capacity, count);
-}
-
-static int enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride);
-int pbd_i_enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride) { return enqueue_all(h, d_src, stride); }
 static int enqueue_stages(pbd_handle* h, const uint8_t* d_src, int stride) {
   int rc;
   const bool prof = h->profiling;
@@ -588,7 +517,7 @@ static int enqueue_stages(pbd_handle* h, const uint8_t* d_src, int stride) {
 // and every later frame is ONE hipGraphLaunch.  The graph reads the frame from the handle's own image buffer, so
 // an image that lives elsewhere in HBM is copied there first (0.9 MB, on the same stream).  Profiling runs (stage
 // events) and level groups on extra streams use the eager path.
-static int enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride) {
+int enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride) {
   const bool graphable = h->opt.graph && !h->profiling;   // (frames of any depth: the launches depend on the plan only; round 5 replayed 8-bit plans only)
   int rc = pbd_i_post_buffers(h);
   if (rc) return rc;
@@ -599,10 +528,7 @@ static int enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride) {
     return enqueue_stages(h, d_src, stride);
   }
   const size_t row = (size_t)h->fw * h->fcn * h->fesz;
-  if (d_src != h->d_img) {
-    if ((size_t)stride == row) HIPCHK(h, hipMemcpyAsync(h->d_img, d_src, row * h->fh * h->batch, hipMemcpyDeviceToDevice, h->stream));
-    else HIPCHK(h, hipMemcpy2DAsync(h->d_img, row, d_src, stride, row, h->fh, hipMemcpyDeviceToDevice, h->stream));   // (strided sources: single frames only)
-  }
+  if (d_src != h->d_img && (rc = copy_rows(h, h->d_img, d_src, (size_t)stride, row, (size_t)h->fh * h->batch, hipMemcpyDeviceToDevice))) return rc;   // (strided sources: single frames only)
   if (!h->gexec) {
     hipGraph_t graph = nullptr;
     HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
@@ -616,21 +542,16 @@ static int enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride) {
   }
   HIPCHK(h, hipGraphLaunch(h->gexec, h->stream));
   h->frames_on_plan++;
-  h->have_pyr = h->have_feat = h->have_resp = !h->compact;
-  compact_mark_feat(h, false);
-  compact_mark_resp(h, false);
-  // k_hog's epilogue has rewritten the features' split copy; a compact plan's copy shares the x pass's pointer planes and is dead again
-  h->feat_split_ok = h->split_parts != 0 && !h->compact;
-  h->have_dp = true;
-  h->min_ran = true;
-  h->ext_ptr = false;
-  h->root_dirty = false;
-  h->dp_timed = false;
+  // what the replayed stages leave behind: their own transitions, in stage order (graphs are never captured under profiling: no DP timing)
+  mark_pyramid(h);
+  mark_features(h, h->split_parts != 0);
+  mark_responses(h);
+  mark_min(h, false);
   h->pending = true;
   return PBD_OK;
 }
 
-static void read_stage_times(pbd_handle* h) {
+void read_stage_times(pbd_handle* h) {
   if (!h->profiling) return;
   for (int i = 0; i < 5; ++i) hipEventElapsedTime(&h->stage_ms[i], h->ev[i], h->ev[i + 1]);
   hipEventElapsedTime(&h->stage_ms[5], h->ev[0], h->ev[5]);
@@ -742,224 +663,6 @@ int pbd_set_stream(pbd_handle* h, void* s) {
   return PBD_OK;
 }
 
-int pbd_detect_enqueue_dev_u8(pbd_handle* h, const void* d_im, int w, int hgt, int cn, int stride) {
-  if (!h || !d_im) return PBD_ERR_ARG;
-  if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
-  if (stride < w * cn) return fail(h, PBD_ERR_ARG, "stride < w*cn");
-  ON_DEVICE(h);
-  int rc = plan_frame(h, w, hgt, cn);
-  if (rc) return rc;
-  return enqueue_all(h, (const uint8_t*)d_im, stride);
-}
-
-int pbd_detect_collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* count) {
-  if (!h) return PBD_ERR_ARG;
-  ON_DEVICE(h);
-  int rc = collect(h, heads, boxes, locs, capacity, count);
-  read_stage_times(h);
-  return rc;
-}
-
-int pbd_detect_dev_u8(pbd_handle* h, const void* d_im, int w, int hgt, int cn, int stride, pbd_candidate_head* heads,
-                      int32_t* boxes, int32_t* locs, int capacity, int* count) {
-  int rc = pbd_detect_enqueue_dev_u8(h, d_im, w, hgt, cn, stride);
-  if (rc) return rc;
-  return pbd_detect_collect(h, heads, boxes, locs, capacity, count);
-}
-
-static int upload_image(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride);
-extern "C++" int pbd_i_upload_image(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride) { return upload_image(h, im, w, hgt, cn, stride); }
-static int upload_image(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride) {
-  if (stride < w * cn) return fail(h, PBD_ERR_ARG, "stride < w*cn");
-  ON_DEVICE(h);
-  int rc = plan_frame(h, w, hgt, cn);
-  if (rc) return rc;
-  // tightly packed rows: one linear copy (a DMA-engine transfer when `im` is pinned); strided rows: a 2-D copy
-  if (stride == w * cn) HIPCHK(h, hipMemcpyAsync(h->d_img, im, (size_t)w * cn * hgt, hipMemcpyHostToDevice, h->stream));
-  else HIPCHK(h, hipMemcpy2DAsync(h->d_img, (size_t)w * cn, im, stride, (size_t)w * cn, hgt, hipMemcpyHostToDevice, h->stream));
-  return PBD_OK;
-}
-
-int pbd_detect_enqueue_u8(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride) {
-  if (!h || !im) return PBD_ERR_ARG;
-  if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
-  int rc = upload_image(h, im, w, hgt, cn, stride);   // hipMemcpy2DAsync on the handle's stream, in front of the kernels
-  if (rc) return rc;
-  return enqueue_all(h, h->d_img, w * cn);
-}
-
-int pbd_detect_u8(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride, pbd_candidate_head* heads,
-                  int32_t* boxes, int32_t* locs, int capacity, int* count) {
-  int rc = pbd_detect_enqueue_u8(h, im, w, hgt, cn, stride);
-  if (rc) return rc;
-  return pbd_detect_collect(h, heads, boxes, locs, capacity, count);
-}
-
-// ---- images of the other depths the reference accepts (src/HOGFeatures.cpp:136-146): single frames, host images, eager launches ----
-static int upload_image_any(pbd_handle* h, const void* im, int depth, int w, int hgt, int cn, int stride) {
-  const int esz = depth_esz(depth);
-  if (!esz) return fail(h, PBD_ERR_UNSUPPORTED, "Unsupported image type (src/HOGFeatures.cpp:136-146: CV_8U, CV_16U, CV_32F, CV_64F)");
-  const size_t row = (size_t)w * cn * esz;
-  if (stride < 0 || (size_t)stride < row || stride % esz) return fail(h, PBD_ERR_ARG, "stride: bytes, >= w * cn * element size and a multiple of the element size");
-  ON_DEVICE(h);
-  int rc = plan_frame(h, w, hgt, cn, 1, depth);
-  if (rc) return rc;
-  if ((size_t)stride == row) HIPCHK(h, hipMemcpyAsync(h->d_img, im, row * hgt, hipMemcpyHostToDevice, h->stream));
-  else HIPCHK(h, hipMemcpy2DAsync(h->d_img, row, im, stride, row, hgt, hipMemcpyHostToDevice, h->stream));
-  return PBD_OK;
-}
-int pbd_detect_image(pbd_handle* h, const void* im, int depth, int w, int hgt, int cn, int stride, pbd_candidate_head* heads,
-                     int32_t* boxes, int32_t* locs, int capacity, int* count) {
-  if (!h || !im) return PBD_ERR_ARG;
-  if (depth == PBD_DEPTH_8U) return pbd_detect_u8(h, (const uint8_t*)im, w, hgt, cn, stride, heads, boxes, locs, capacity, count);
-  if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
-  int rc = upload_image_any(h, im, depth, w, hgt, cn, stride);
-  if (rc) return rc;
-  if ((rc = enqueue_all(h, h->d_img, w * cn * h->fesz))) return rc;
-  return pbd_detect_collect(h, heads, boxes, locs, capacity, count);
-}
-int pbd_pyramid_image(pbd_handle* h, const void* im, int depth, int w, int hgt, int cn, int stride) {
-  if (!h || !im) return PBD_ERR_ARG;
-  if (depth == PBD_DEPTH_8U) return pbd_pyramid_u8(h, (const uint8_t*)im, w, hgt, cn, stride);
-  int rc = upload_image_any(h, im, depth, w, hgt, cn, stride);
-  if (rc) return rc;
-  if ((rc = run_image_pyramid(h, h->d_img, w * cn * h->fesz))) return rc;
-  if ((rc = run_hog(h))) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return PBD_OK;
-}
-
-// ---- a batch of same-sized frames through ONE handle ---------------------------------------------------------
-// (SURVEY 8b lists pbd_detect_batch_u8; configs[2] hands every GPU 4 frames.)  The frames of a batch are planned as
-// extra "virtual levels" (pbd_internal.hpp), so every stage is one launch — or one chain of launches — for the whole
-// batch: the same kernels, B times the blocks per launch.  Results per frame are identical to pbd_detect_u8.
-int pbd_detect_batch_enqueue_dev_u8(pbd_handle* h, const void* d_ims, int nframes, int w, int hgt, int cn) {
-  if (!h || !d_ims || nframes < 1) return PBD_ERR_ARG;
-  if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
-  ON_DEVICE(h);
-  int rc = plan_frame(h, w, hgt, cn, nframes);
-  if (rc) return rc;
-  return enqueue_all(h, (const uint8_t*)d_ims, w * cn);
-}
-int pbd_detect_batch_enqueue_u8(pbd_handle* h, const uint8_t* const* ims, int nframes, int w, int hgt, int cn, int stride) {
-  if (!h || !ims || nframes < 1) return PBD_ERR_ARG;
-  if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
-  if (stride < w * cn) return fail(h, PBD_ERR_ARG, "stride < w*cn");
-  ON_DEVICE(h);
-  int rc = plan_frame(h, w, hgt, cn, nframes);
-  if (rc) return rc;
-  const size_t fb = (size_t)w * cn * hgt;
-  for (int f = 0; f < nframes; ++f) {
-    if (!ims[f]) return fail(h, PBD_ERR_ARG, "null frame pointer");
-    if (stride == w * cn) HIPCHK(h, hipMemcpyAsync(h->d_img + fb * f, ims[f], fb, hipMemcpyHostToDevice, h->stream));
-    else HIPCHK(h, hipMemcpy2DAsync(h->d_img + fb * f, (size_t)w * cn, ims[f], stride, (size_t)w * cn, hgt, hipMemcpyHostToDevice, h->stream));
-  }
-  return enqueue_all(h, h->d_img, w * cn);
-}
-// frame f's candidates at heads[f * capacity], boxes[f * capacity * max_parts * 4], locs[f * capacity * max_parts * 3];
-// counts[f] = number found in frame f (PBD_ERR_CAPACITY if any exceeds `capacity`)
-int pbd_detect_batch_collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* counts) {
-  if (!h || !heads || !counts || capacity < 0) return PBD_ERR_ARG;
-  if (!h->pending) return fail(h, PBD_ERR_STATE, "collect without a pending detect");
-  if (h->d_gsend) return fail(h, PBD_ERR_STATE, "handle belongs to an RCCL-gathering pbd_group: collect through the group");
-  ON_DEVICE(h);
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  const bool filt = h->out_filtered;
-  const int found = filt ? h->h_cf_cnt[0] : h->h_cand_count[0];
-  int rc = pbd_i_finish_frame(h, found);
-  read_stage_times(h);
-  if (rc) return rc;
-  const int mp = h->max_parts, n1 = h->nlevels, B = h->batch;
-  std::vector<std::vector<const char*>> per(B);
-  if (filt) {   // frame f's kept records, in final order, at its offset
-    for (int f = 0; f < B; ++f)
-      for (int j = 0; j < h->h_cf_cnt[2 + f]; ++j) per[f].push_back(h->h_cand_out + h->cand_stride * ((size_t)h->h_cf_cnt[2 + B + f] + j));
-  } else
-  for (int i = 0; i < found; ++i) {
-    const char* r = h->h_cand_out + h->cand_stride * i;
-    per[((const pbd_candidate_head*)r)->level / n1].push_back(r);
-  }
-  int status = PBD_OK;
-  if (h->b3_frame) pbd_i_b3_begin(h, B);
-  if (h->ps_frame) pbd_i_ps_begin(h, B);
-  std::vector<int> order;
-  for (int f = 0; f < B; ++f) {
-    counts[f] = (int)per[f].size();
-    pbd_candidate_head* hf = heads + (size_t)f * capacity;
-    rc = pbd_i_emit(h, per[f], hf, boxes ? boxes + (size_t)f * capacity * mp * 4 : nullptr, locs ? locs + (size_t)f * capacity * mp * 3 : nullptr, capacity, filt,
-                    h->b3_frame || h->ps_frame ? &order : nullptr);
-    if (rc == PBD_ERR_CAPACITY) { status = rc; continue; }
-    if (rc) return rc;
-    if (h->b3_frame) pbd_i_b3_gather(h, f, per[f], order);
-    if (h->ps_frame) pbd_i_ps_gather(h, f, per[f], order);
-    for (int i = 0; i < counts[f]; ++i) hf[i].level -= f * n1;   // virtual level -> the frame's own pyramid level
-  }
-  if (h->b3_frame && (rc = pbd_i_b3_end(h))) return rc;
-  return status;
-}
-int pbd_detect_batch_u8(pbd_handle* h, const uint8_t* const* ims, int nframes, int w, int hgt, int cn, int stride,
-                        pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* counts) {
-  int rc = pbd_detect_batch_enqueue_u8(h, ims, nframes, w, hgt, cn, stride);
-  if (rc) return rc;
-  return pbd_detect_batch_collect(h, heads, boxes, locs, capacity, counts);
-}
-
-// ---- the planner's one measured rule, re-measured on the caller's own frames ---------------------------------
-// The distance transform's block geometry (lanes and LDS per block) changes the stage's time by a few per cent either way depending on
-// the frame size, the model and whether frames come singly or in batches, and never its results (dt_core.hpp: the same exact
-// algorithm under any segmentation).  plan_frame picks by a rule measured on seven sizes with the person model;
-// pbd_tune_plan runs the caller's frame through both geometries of a float handle — `batch` copies per call, 2 warm-up + 3 timed
-// calls each, the dp_min stage's GPU time from the stage events — and keeps the faster one for every later plan of this handle.
-// im == NULL: back to the rule.  chosen: 1 = 256 lanes / 40 KB, 2 = 128 lanes / 25 KB, 0 = nothing to choose (double handles).
-int pbd_tune_plan(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride, int batch, int* chosen, double ms[2]) {
-  if (!h) return PBD_ERR_ARG;
-  if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
-  // (a member of an RCCL-gathering group collects through the group only: the measurement's own collect() would fail with the frame
-  //  left pending — ADVICE r05)
-  if (h->d_gsend) return fail(h, PBD_ERR_STATE, "handle belongs to an RCCL-gathering pbd_group: tune a handle of its own");
-  if (chosen) *chosen = 0;
-  if (ms) ms[0] = ms[1] = 0.0;
-  ON_DEVICE(h);
-  // the plan is dropped as a whole (buffers, stage flags, captured graph): a stage getter after pbd_tune_plan answers "no frame
-  // geometry" AND the stage flags say so — nothing can run on the last measured geometry
-  auto drop_plan = [&]() { if (h->stream) hipStreamSynchronize(h->stream); h->pending = false; free_frame(h); };
-  if (!im) { h->dt_geom = 0; drop_plan(); return PBD_OK; }
-  if (h->ts != 4) return PBD_OK;
-  if (batch < 1 || batch > 64) return fail(h, PBD_ERR_ARG, "batch: 1..64 frames");
-  const int cap = h->opt.max_candidates;            // per frame (pbd_detect_batch_collect: heads[batch][capacity])
-  std::vector<pbd_candidate_head> heads((size_t)cap * batch);
-  std::vector<int> counts((size_t)batch);
-  std::vector<const uint8_t*> ims((size_t)batch, im);
-  const bool prof = h->profiling;
-  const int before = h->dt_geom;
-  float stage_before[6];
-  for (int i = 0; i < 6; ++i) stage_before[i] = h->stage_ms[i];
-  double t[2] = {0, 0};
-  int rc = PBD_OK;
-  h->profiling = true;
-  for (int g = 1; g <= 2 && !rc; ++g) {
-    h->dt_geom = g; drop_plan();                    // (plan_frame re-plans under the geometry)
-    double v[3] = {0, 0, 0};
-    for (int i = 0; i < 5 && !rc; ++i) {
-      rc = batch == 1 ? pbd_detect_u8(h, im, w, hgt, cn, stride, heads.data(), nullptr, nullptr, cap, counts.data())
-                      : pbd_detect_batch_u8(h, ims.data(), batch, w, hgt, cn, stride, heads.data(), nullptr, nullptr, cap, counts.data());
-      if (rc == PBD_ERR_CAPACITY) rc = PBD_OK;      // (a low threshold: the stage times are what is wanted)
-      if (i >= 2) v[i - 2] = h->stage_ms[3];
-    }
-    std::sort(v, v + 3);
-    t[g - 1] = v[1];
-  }
-  h->profiling = prof;
-  for (int i = 0; i < 6; ++i) h->stage_ms[i] = stage_before[i];   // the caller's last stage times, not the measurement's
-  const std::string err = h->err;
-  h->dt_geom = rc ? before : (t[0] <= t[1] ? 1 : 2);
-  drop_plan();                                      // whatever happened: nothing in flight, no plan of the measurement's call shape left behind
-  if (rc) { h->err = err; return rc; }
-  if (chosen) *chosen = h->dt_geom;
-  if (ms) { ms[0] = t[0]; ms[1] = t[1]; }
-  return PBD_OK;
-}
-
 // ---- stage entry points -----------------------------------------------------
 int pbd_pyramid_geometry(const pbd_handle* h, int w, int hgt, int* nlevels, int32_t* img_w, int32_t* img_h,
                          int32_t* cell_w, int32_t* cell_h, float* scales) {
@@ -984,22 +687,22 @@ int pbd_begin_frame(pbd_handle* h, int w, int hgt, int cn) {
   ON_DEVICE(h);
   int rc = plan_frame(h, w, hgt, cn);
   if (rc) return rc;
-  h->have_pyr = h->have_feat = h->have_resp = h->have_dp = false;
-  h->min_ran = false;
-  compact_mark_feat(h, false);
-  compact_mark_resp(h, false);
-  h->ext_set.clear(); h->root_set.clear();
+  reset_stages(h);
   return PBD_OK;
 }
 
-int pbd_pyramid_u8(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride) {
+// pyramid() on a host image of any depth the reference accepts (src/HOGFeatures.cpp:136-146): level images + HOG features
+int pbd_pyramid_image(pbd_handle* h, const void* im, int depth, int w, int hgt, int cn, int stride) {
   if (!h || !im) return PBD_ERR_ARG;
-  int rc = upload_image(h, im, w, hgt, cn, stride);
+  int rc = enter_frame(h, host_frame(im, w, hgt, cn, stride, depth), false);
   if (rc) return rc;
-  if ((rc = run_image_pyramid(h, h->d_img, w * cn))) return rc;
+  if ((rc = run_image_pyramid(h, h->d_img, w * cn * h->fesz))) return rc;
   if ((rc = run_hog(h))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return PBD_OK;
+}
+int pbd_pyramid_u8(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride) {
+  return pbd_pyramid_image(h, im, PBD_DEPTH_8U, w, hgt, cn, stride);
 }
 
 #define CHECK_LEVEL(h, level)                                                     \
@@ -1066,14 +769,15 @@ static int set_level_features_(pbd_handle* h, int level, const void* in, int ts)
   ON_DEVICE(h);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemcpy(h->d_feat + L.cell_off * PBD_FLEN * ts, in, (size_t)L.cw * L.ch * PBD_FLEN * ts, hipMemcpyHostToDevice));
-  h->feat_split_ok = false;   // (the split-product bank's copy of the features is re-derived in front of the next pdf())
-  if (h->compact) {   // the write went over the Ik planes / the x pass's scratch; the other levels may still be stale
+  // (split_written = false: the split-product bank's copy of the features is re-derived in front of the next pdf())
+  if (h->compact) {   // not mark_features: ONE plane handed in — the write went over the Ik planes / the x pass's scratch; the other levels may still be stale
+    h->feat_split_ok = false;
     h->have_dp = h->min_ran = false;
     if (h->feat_ok.size() != (size_t)h->nvl) compact_mark_feat(h, false);
     h->feat_ok[level] = 1;
     h->have_feat = all_active_set(h, h->feat_ok, 1);
   } else {
-    h->have_feat = true;
+    mark_features(h, false);
   }
   return PBD_OK;
 }
@@ -1147,12 +851,12 @@ static int set_level_response_(pbd_handle* h, int level, int filter, const void*
   ON_DEVICE(h);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemcpy(h->d_resp + (L.cell_off * h->md.nfilters + filter * HW) * ts, in, HW * ts, hipMemcpyHostToDevice));
-  if (h->compact) {   // min() transformed the planes in place: the responses are valid again once EVERY plane has been handed in (or pdf() re-run)
+  if (h->compact) {   // not mark_responses: ONE plane handed in — min() transformed the planes in place: the responses are valid again once EVERY plane has been handed in (or pdf() re-run)
     if (h->resp_ok.size() != (size_t)h->nvl * h->md.nfilters) compact_mark_resp(h, false);
     h->resp_ok[(size_t)level * h->md.nfilters + filter] = 1;
     h->have_resp = all_active_set(h, h->resp_ok, h->md.nfilters);
   } else {
-    h->have_resp = true;
+    mark_responses(h);
   }
   return PBD_OK;
 }
@@ -1309,6 +1013,7 @@ int pbd_set_dp_pointers(pbd_handle* h, int level, int component, int part, int p
   HIPCHK(h, hipMemcpy(h->d_extx + eo, xs.data(), HW * 2, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->d_exty + eo, ys.data(), HW * 2, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->d_pk + eo, ks.data(), HW, hipMemcpyHostToDevice));
+  // not mark_min: tables handed in, with or without a min() of this handle behind them (min_ran, root_dirty, dp_timed keep their values)
   h->ext_ptr = true;
   if (h->compact) {   // d_pk is the memory of the level images + features (and the first call's d_extx / d_exty allocation moved nothing, but the
                       // Ik write above went over them): pyramid() -> set_dp_pointers -> pdf() must not run on clobbered features
@@ -1351,7 +1056,7 @@ int pbd_dp_argmin(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int3
   h->ps_frame = h->ps_ready = false;   // (the stage entry point scores nothing: pbd_candidates_part_scores does, on its records)
   int rc = run_argmin_enqueue(h);
   if (rc) { h->pending = false; return rc; }
-  return collect(h, heads, boxes, locs, capacity, count);
+  return collect_frame(h, heads, boxes, locs, capacity, count);
 }
 
 // ---- stand-alone primitives -------------------------------------------------
@@ -1500,88 +1205,6 @@ int pbd_nms_map(pbd_handle* h, const float* src, int rows, int cols, int sz, uin
   hipFree(d_src); hipFree(d_dst);
   return PBD_OK;
 }
-
-// ---- frames with a depth image (the depth pruning, 3-D boxes and object clusters of pbd_post.cpp behind back-tracking) ----
-// enqueue_all for a frame whose depth images are set in h->zf_*: the flag lives only across the call
-static int zf_enqueue(pbd_handle* h, const uint8_t* d_src, int stride) {
-  h->zf_frame = true;
-  int rc = enqueue_all(h, d_src, stride);
-  h->zf_frame = false;
-  return rc;
-}
-
-int pbd_detect_rgbd_enqueue_dev_u8(pbd_handle* h, const void* d_im, int w, int hgt, int cn, int stride, const void* d_depth,
-                                   int depth_type, int dstride) {
-  if (!h) return PBD_ERR_ARG;
-  if ((!h->zf_on && !h->b3_on) || !d_depth) return pbd_detect_enqueue_dev_u8(h, d_im, w, hgt, cn, stride);
-  if (!d_im) return PBD_ERR_ARG;
-  int rc = pbd_i_depth_check(h, depth_type, dstride, w);
-  if (rc) return rc;
-  if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
-  if (stride < w * cn) return fail(h, PBD_ERR_ARG, "stride < w*cn");
-  ON_DEVICE(h);
-  if ((rc = plan_frame(h, w, hgt, cn))) return rc;
-  h->zf_img = (const char*)d_depth; h->zf_pitch = (size_t)dstride; h->zf_fbytes = 0; h->zf_has = 1;
-  return zf_enqueue(h, (const uint8_t*)d_im, stride);
-}
-
-int pbd_detect_rgbd_u8(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride, const void* depth, int depth_type,
-                       int dstride, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* count) {
-  if (!h) return PBD_ERR_ARG;
-  if ((!h->zf_on && !h->b3_on) || !depth) return pbd_detect_u8(h, im, w, hgt, cn, stride, heads, boxes, locs, capacity, count);
-  if (!im) return PBD_ERR_ARG;
-  int rc = pbd_i_depth_check(h, depth_type, dstride, w);
-  if (rc) return rc;
-  if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
-  if ((rc = upload_image(h, im, w, hgt, cn, stride))) return rc;
-  const size_t row = (size_t)w * h->ts;
-  if ((rc = model_grow(h, &h->d_zimg, h->zimg_bytes, row * hgt))) return rc;
-  HIPCHK(h, hipMemcpy2DAsync(h->d_zimg, row, depth, dstride, row, hgt, hipMemcpyHostToDevice, h->stream));
-  h->zf_img = h->d_zimg; h->zf_pitch = row; h->zf_fbytes = 0; h->zf_has = 1;
-  if ((rc = zf_enqueue(h, h->d_img, w * cn))) return rc;
-  return pbd_detect_collect(h, heads, boxes, locs, capacity, count);
-}
-
-int pbd_detect_batch_rgbd_enqueue_dev_u8(pbd_handle* h, const void* d_ims, const void* d_depths, int nframes, int w, int hgt, int cn,
-                                         int depth_type) {
-  if (!h) return PBD_ERR_ARG;
-  if (!h->zf_on && !h->b3_on) return pbd_detect_batch_enqueue_dev_u8(h, d_ims, nframes, w, hgt, cn);
-  if (!d_depths) return fail(h, PBD_ERR_ARG, "device batch: the depth images are one packed buffer (NULL: use pbd_detect_batch_enqueue_dev_u8)");
-  if (!d_ims || nframes < 1) return PBD_ERR_ARG;
-  int rc = pbd_i_depth_check(h, depth_type, (long long)w * h->ts, w);
-  if (rc) return rc;
-  if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
-  ON_DEVICE(h);
-  if ((rc = plan_frame(h, w, hgt, cn, nframes))) return rc;
-  h->zf_img = (const char*)d_depths; h->zf_pitch = (size_t)w * h->ts; h->zf_fbytes = h->zf_pitch * hgt;
-  h->zf_has = nframes >= 64 ? ~0ull : (1ull << nframes) - 1;
-  return zf_enqueue(h, (const uint8_t*)d_ims, w * cn);
-}
-
-int pbd_detect_batch_rgbd_u8(pbd_handle* h, const uint8_t* const* ims, const void* const* depths, int nframes, int w, int hgt, int cn,
-                             int stride, int depth_type, int dstride, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs,
-                             int capacity, int* counts) {
-  if (!h) return PBD_ERR_ARG;
-  unsigned long long has = 0;
-  for (int f = 0; depths && f < nframes && f < 64; ++f) if (depths[f]) has |= 1ull << f;
-  if ((!h->zf_on && !h->b3_on) || !has) return pbd_detect_batch_u8(h, ims, nframes, w, hgt, cn, stride, heads, boxes, locs, capacity, counts);
-  int rc = pbd_i_depth_check(h, depth_type, dstride, w);
-  if (rc) return rc;
-  if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
-  if (!ims || nframes < 1 || nframes > 64) return fail(h, PBD_ERR_ARG, "batch: 1..64 frames");
-  ON_DEVICE(h);
-  const size_t row = (size_t)w * h->ts, fb = row * hgt;
-  if ((rc = model_grow(h, &h->d_zimg, h->zimg_bytes, fb * nframes))) return rc;
-  for (int f = 0; f < nframes; ++f)
-    if (depths[f]) HIPCHK(h, hipMemcpy2DAsync(h->d_zimg + fb * f, row, depths[f], dstride, row, hgt, hipMemcpyHostToDevice, h->stream));
-  h->zf_img = h->d_zimg; h->zf_pitch = row; h->zf_fbytes = fb; h->zf_has = has;
-  h->zf_frame = true;
-  rc = pbd_detect_batch_enqueue_u8(h, ims, nframes, w, hgt, cn, stride);
-  h->zf_frame = false;
-  if (rc) return rc;
-  return pbd_detect_batch_collect(h, heads, boxes, locs, capacity, counts);
-}
-
 
 // ---- instrumentation ---------------------------------------------------------
 int pbd_get_stage_ms(const pbd_handle* h, float ms[6]) {

@@ -187,12 +187,15 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   bool out_filtered = false; // the pending frame's records went through k_cand_filter (counts in h_cf_cnt / d_cf_cnt)
   char* d_cand_raw = nullptr;                           // back-tracking output of RCCL-gathering members when filtering
   unsigned long long* d_cf_keys = nullptr; unsigned* d_cf_idx = nullptr; int* d_cf_box = nullptr; uint8_t* d_cf_st = nullptr;
-  int* d_cf_cnt = nullptr; int* h_cf_cnt = nullptr;    // [2 + 2 * PBD_MAX_BATCH] (k_cand.hip); h_: pinned
+  // k_cand_filter's counts, B = frames of the plan: [0] the back-tracking's device count (all frames, before the filter), [1] kept in frame 0
+  // (the device count when that overflowed the capacity: nothing is kept then), [2 + f] kept in frame f, [2 + B + f] frame f's first record.
+  // A single-frame collect finds [1] records (pbd_i_found), a batch collect fetches for [0] and splits by [2 + f] / [2 + B + f].
+  int* d_cf_cnt = nullptr; int* h_cf_cnt = nullptr;    // [2 + 2 * PBD_MAX_BATCH]; h_: pinned
   unsigned long long* d_cf_mask = nullptr; size_t cf_mask_bytes = 0;   // per-frame masks too large for LDS (frame plan)
   // depth-consistency pruning (pbd_set_depth_filter): k_zfilter.hip behind k_backtrack.  Named z* / zf*: d_depth and max_depth
   // above are the part tree's depth.  Allocated on the first depth-carrying frame with the setting on.
   bool zf_on = false; float zf_factor = 0.f;
-  bool zf_frame = false;            // the frame being enqueued carries depth (set by the *_rgbd_* entry points around enqueue_all)
+  bool zf_frame = false;            // the frame being enqueued carries depth (set by enter_frame around enqueue_all for a FrameSource with depth images)
   const char* zf_img = nullptr; size_t zf_pitch = 0, zf_fbytes = 0; unsigned long long zf_has = 0;   // that frame's depth images
   int* d_zf_npart = nullptr; int* d_zf_par = nullptr; double* d_zf_thr = nullptr; float zf_thr_factor = 0.f;   // [ncomp], [ncomp * mp] x 2
   unsigned long long* d_zf_med = nullptr; unsigned* d_zf_large = nullptr;   // [capacity * mp] each
@@ -332,10 +335,45 @@ struct LdsOptIn {
 #define PBD_PROBE_ENV(name) ((const char*)nullptr)
 #endif
 
-// ---- internals shared with pbd_group.cpp -----------------------------------------
-int pbd_i_upload_image(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride);   // plan + async H2D
-int pbd_i_enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride);                          // all stages + argmin
-int pbd_i_collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* count);
+// ---- frame entry and collect (pbd_detect.cpp), shared with pbd_api.cpp -----------------------------------
+// Where a frame or a batch of same-sized frames comes from: host frames are uploaded into the plan's image buffer, device frames read in place
+struct DepthSource {              // the depth images of an RGB-D frame or batch (elements of the handle's T)
+  bool on_device;                 // read in place, else ONE host image, uploaded
+  const void* p; int type;        // PBD_DEPTH_*
+  long long stride; size_t fbytes;   // bytes between rows, and between the frames' images of a packed device buffer (0: one frame)
+  unsigned long long has;         // frames that carry depth (bit f)
+};
+struct FrameSource {
+  bool on_device;
+  const void* one;                // a single frame, or a device batch: one packed buffer, frame after frame
+  const uint8_t* const* each;     // or (host batches) a pointer per frame
+  int nframes, w, hgt, cn, stride, depth;   // stride: bytes between rows; depth: PBD_DEPTH_* of the pixels
+  const DepthSource* z;           // RGB-D: the frame runs with the depth-carrying post-stages; else null
+};
+// the three shapes of a source, by name (z: see above)
+inline FrameSource host_frame(const void* im, int w, int hgt, int cn, int stride, int depth, const DepthSource* z = nullptr) {
+  return {false, im, nullptr, 1, w, hgt, cn, stride, depth, z};
+}
+inline FrameSource host_batch(const uint8_t* const* ims, int nframes, int w, int hgt, int cn, int stride, const DepthSource* z = nullptr) {
+  return {false, nullptr, ims, nframes, w, hgt, cn, stride, PBD_DEPTH_8U, z};
+}
+inline FrameSource device_frames(const void* d_ims, int nframes, int w, int hgt, int cn, int stride, const DepthSource* z = nullptr) {
+  return {true, d_ims, nullptr, nframes, w, hgt, cn, stride, PBD_DEPTH_8U, z};
+}
+inline DepthSource depth_images(bool on_device, const void* p, int type, long long stride, size_t fbytes, unsigned long long has) {
+  return {on_device, p, type, stride, fbytes, has};
+}
+// validate -> ON_DEVICE -> plan_frame -> upload -> enqueue_all.  detect = false: the stage entry points' way in (pbd_pyramid_*), up to
+// the upload — a pending frame is no refusal, nothing is enqueued
+int enter_frame(pbd_handle* h, const FrameSource& s, bool detect = true);
+// `rows` rows of row_bytes, src_pitch apart -> packed rows, on the handle's stream: one linear copy when the source is packed too, else a 2-D copy
+int copy_rows(pbd_handle* h, void* dst, const void* src, size_t src_pitch, size_t row_bytes, size_t rows, hipMemcpyKind kind);
+int collect_frame(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* count);   // the pending single frame
+// the plan and the stages (pbd_api.cpp)
+int plan_frame(pbd_handle* h, int w, int hgt, int cn, int batch = 1, int depth = PBD_DEPTH_8U);   // the frame plan of one geometry, kept while it repeats
+void free_frame(pbd_handle* h);                                             // drops the plan: buffers, stage state, captured graph
+int enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride);           // all stages + argmin (+ post-stages), eager or as one graph launch
+void read_stage_times(pbd_handle* h);
 int pbd_i_finish_frame(pbd_handle* h, int found);
 int pbd_i_emit(pbd_handle* h, const std::vector<const char*>& recs, pbd_candidate_head* heads, int32_t* boxes,
                int32_t* locs, int capacity, bool ordered = false,    // ordered: the records are in final order already (k_cand_filter)
