@@ -101,7 +101,8 @@ enum {
                          max |w| 2^e in [2^13, 2^14)) and the THREE products above 2^-22 relative on v_mfma_f32_32x32x16_f16, fp32
                          accumulators, responses scaled back exactly — half the matrix instructions of PBD_CONV_SPLIT.  Operands
                          are carried to 23 of their 24 bits; measured errors against fp64 on HOG features: those of
-                         PBD_CONV_SPLIT.  Domain: |feature| < 16 (HOG features are <= 1; features handed in
+                         PBD_CONV_SPLIT.  Domain: |feature| < 15.99609375 = 65520 / 4096, where the scaled high part
+                         would round to binary16's inf (HOG features are <= 1; features handed in
                          through pbd_set_level_features must respect it), weights finite; a feature below 2^-26 or a
                          weight below 2^-27 max |w| loses relative (not absolute) precision.                      */
 };
@@ -318,7 +319,8 @@ int pbd_pyramid_image(pbd_handle* h, const void* im, int depth, int w, int hgt, 
 int pbd_get_level_image_raw(pbd_handle* h, int level, void* out, size_t out_bytes);
 int pbd_get_level_features(pbd_handle* h, int level, float* out /* cell_h*cell_w*flen */);
 /* (a handle on a split-product bank refuses features outside the bank's domain — PBD_CONV_SPLIT: finite, |f| < 3e38;
- *  PBD_CONV_SPLIT_F16: |f| < 16 — with PBD_ERR_ARG; nothing is uploaded then)                                          */
+ *  PBD_CONV_SPLIT_F16: |f| < 15.99609375 (65520 / 4096: f 2^12 must round to a finite binary16) — with PBD_ERR_ARG; nothing is
+ *  uploaded then)                                                                                                        */
 int pbd_set_level_features(pbd_handle* h, int level, const float* in);
 int pbd_get_level_features_f64(pbd_handle* h, int level, double* out);
 /* Read-only: the level image (own depth) and the features of ONE frame of the current plan, 0 <= frame < frames of the plan.  Unlike the

@@ -29,6 +29,7 @@
 #include <vector>
 #include <cstring>
 #include "pbd_internal.hpp"
+#include "pbd_split.hpp"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -102,12 +103,11 @@ void conv_split_filters(const float* filters, int nf, int kh, int kw, std::vecto
 // fp64 on the person bank (tests/tools_split_products_study.py) max 3.2e-7 / rms 4.1e-8, the six-product bank 3.1e-7 / 3.2e-8,
 // the fp32 MFMA chain 9.1e-7 / 8.2e-8.  Half the matrix instructions of the six-product bank.
 // binary16's range is the price: operands are scaled by powers of two (exact) to sit high in it — features by 2^12 (HOG features
-// are <= 1: the truncation channel; |feature| must stay below 16), every filter's weights by its own 2^e with max |w| 2^e in
+// are <= 1: the truncation channel; |feature| must stay below 65520 / 4096 = 15.99609375, where the high part would round to inf), every filter's weights by its own 2^e with max |w| 2^e in
 // [2^13, 2^14) — and a part below 2^-14 (scaled) is a binary16 subnormal of absolute precision 2^-25: an absolute error of 2^-37
 // per feature, 2^-38 of the filter's max |w| per weight.  A filter's responses are multiplied by 2^-(12 + e) on the way out (exact).  Not the default and not what
 // PBD_CONV_AUTO resolves to: the operands are represented to 23 bits, not 24 — bench.py reports it beside the benched bank.
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int SPLIT16_FEXP = 12;
 __global__ __launch_bounds__(256) void k_feat_split16(const float* __restrict__ feat, uint16_t* __restrict__ out, size_t ngroups) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;    // (cell, channel group g = i & 3)
   if (i >= ngroups) return;

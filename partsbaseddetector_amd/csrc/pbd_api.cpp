@@ -12,6 +12,7 @@
 #include <cstring>
 #include <new>
 #include "pbd_internal.hpp"
+#include "pbd_split.hpp"
 
 // ---------------------------------------------------------------------------
 // model
@@ -758,12 +759,12 @@ static int set_level_features_(pbd_handle* h, int level, const void* in, int ts)
   // and poison every response the MFMA sums it into, where the EXACT / MFMA banks propagate it as ordinary fp32.  HOG features
   // are in [0, 0.4]; a caller's own features are held to the bank's domain here, on the host copy that is being uploaded anyway.
   if (ts == 4 && (h->conv_mode == PBD_CONV_SPLIT || h->conv_mode == PBD_CONV_SPLIT_F16)) {
-    const float lim = h->conv_mode == PBD_CONV_SPLIT_F16 ? 16.0f : 3.0e38f;
+    const float lim = h->conv_mode == PBD_CONV_SPLIT_F16 ? SPLIT16_FMAX : 3.0e38f;   // (binary16: f 2^12 rounds to inf from 65520 on)
     const float* f = (const float*)in;
     const size_t nf = (size_t)L.cw * L.ch * PBD_FLEN;
     for (size_t i = 0; i < nf; ++i)
       if (!(std::fabs(f[i]) < lim))
-        return fail(h, PBD_ERR_ARG, h->conv_mode == PBD_CONV_SPLIT_F16 ? "PBD_CONV_SPLIT_F16: a feature outside the bank's domain (|f| < 16, finite)"
+        return fail(h, PBD_ERR_ARG, h->conv_mode == PBD_CONV_SPLIT_F16 ? "PBD_CONV_SPLIT_F16: a feature outside the bank's domain (|f| < 15.99609375 = 65520 / 4096, finite)"
                                                                         : "PBD_CONV_SPLIT: a feature outside bfloat16's finite range (|f| < 3e38, finite): use PBD_CONV_MFMA / PBD_CONV_EXACT");
   }
   ON_DEVICE(h);

@@ -2,6 +2,11 @@
 // writes features on the device: k_hog's epilogue (the interior cells) and k_featpad (the border ring of the boundary padding).
 #pragma once
 #include <stdint.h>
+// PBD_CONV_SPLIT_F16: features are carried as two binary16 parts of f 2^SPLIT16_FEXP.  binary16 rounds to inf from 65520 on (its largest
+// finite value 65504 plus half a unit in the last place), so the bank's domain is |f| < SPLIT16_FMAX = 15.99609375: from there on the high
+// part is inf and the low part, x - inf, NaN.
+constexpr int SPLIT16_FEXP = 12;
+constexpr float SPLIT16_FMAX = 65520.0f / (float)(1 << SPLIT16_FEXP);
 #ifdef __HIPCC__
 // PBD_CONV_SPLIT: v = h + m + l, three exact bfloat16 parts (round to nearest even, every subtraction exact); part q at sp[q * stride]
 __device__ __forceinline__ void feat_split_bf16(float v, uint16_t* sp, int stride) {
@@ -14,9 +19,9 @@ __device__ __forceinline__ void feat_split_bf16(float v, uint16_t* sp, int strid
     r = r - __uint_as_float(hb << 16);
   }
 }
-// PBD_CONV_SPLIT_F16: two binary16 parts of v 2^12 (k_feat_split16); part q at sp[q * stride]
+// PBD_CONV_SPLIT_F16: two binary16 parts of v 2^SPLIT16_FEXP (k_feat_split16); part q at sp[q * stride]
 __device__ __forceinline__ void feat_split_f16(float v, _Float16* sp, int stride) {
-  const float x = v * 4096.f;
+  const float x = v * (float)(1 << SPLIT16_FEXP);
   const _Float16 hv = (_Float16)x;
   sp[0] = hv;
   sp[stride] = (_Float16)(x - (float)hv);
