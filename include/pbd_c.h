@@ -191,7 +191,8 @@ typedef struct pbd_handle pbd_handle;
 int pbd_set_levels(pbd_handle* h, const int32_t* levels, int n);
 /* PartsBasedDetector<T>::distributeModel (src/PartsBasedDetector.cpp:102-127)
  * incl. SpatialConvolutionEngine::setFilters (src/SpatialConvolutionEngine.cpp:133-159)
- * and Parts construction (include/Parts.hpp:229-235).                        */
+ * and Parts construction (include/Parts.hpp:229-235).
+ * Filter, bias and deformation weights must be finite (PBD_ERR_ARG).         */
 int pbd_create(const pbd_model_desc* model, const pbd_options* opt, pbd_handle** out);
 /* A size per filter (SpatialConvolutionEngine::setFilters builds one FilterEngine per filter at its own size).
  * fsize[nfilters][2] = {rows kh, cols kw} of each filter, 1..9 each (else PBD_ERR_UNSUPPORTED); model->filters holds the filters
@@ -336,6 +337,7 @@ int pbd_begin_frame(pbd_handle* h, int w, int hgt, int cn);
 /* SpatialConvolutionEngine::pdf (src/SpatialConvolutionEngine.cpp:106-124)   */
 int pbd_pdf(pbd_handle* h);
 int pbd_get_level_response(pbd_handle* h, int level, int filter, float* out /* cell_h*cell_w */);
+/* in: finite values only (PBD_ERR_ARG otherwise, the plane is not uploaded): the distance transform's domain, see pbd_dt2d */
 int pbd_set_level_response(pbd_handle* h, int level, int filter, const float* in);
 int pbd_get_level_response_f64(pbd_handle* h, int level, int filter, double* out);
 int pbd_set_level_response_f64(pbd_handle* h, int level, int filter, const double* in);
@@ -372,7 +374,19 @@ int pbd_dp_argmin(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int3
 
 /* ---- stand-alone primitives ------------------------------------------------
  * DistanceTransform<T>::compute (include/DistanceTransform.hpp:202-245) with
- * Quadratic(ax,bx), Quadratic(ay,by) and anchor (osx, osy); host arrays.      */
+ * Quadratic(ax,bx), Quadratic(ay,by) and anchor (osx, osy); host arrays.
+ * DOMAIN: ax, bx, ay, by finite, ax != 0, ay != 0, every score finite, and the
+ * scores of BOTH passes finite (the x pass's a d^2 + b d + y can overflow from
+ * finite arguments).  Inside it the result is the reference's bit for bit
+ * (scores, Ix, Iy; float and double), whatever the magnitudes.  A NaN or an
+ * infinity in the arguments: PBD_ERR_ARG, nothing is launched.  A pass that
+ * left the finite range: PBD_ERR_ARG after the run (the kernel ends on any
+ * input; out / ix / iy are then not the reference's).  PBD_OK means inside
+ * the domain.  DESIGN.md "Input domain of the distance transform".  The score
+ * maps and features handed to pbd_set_level_response / pbd_set_level_features
+ * (PBD_ERR_ARG, nothing is uploaded) and the weights of a model (pbd_create:
+ * PBD_ERR_ARG) must be finite as well; sums that overflow on the device are
+ * outside the domain and are not detected on the frame path.               */
 int pbd_dt2d(pbd_handle* h, const float* in, int rows, int cols,
              double ax, double bx, double ay, double by, int osx, int osy,
              float* out, int32_t* ix, int32_t* iy);

@@ -236,14 +236,19 @@ DT_HD bool dt_stitch1(DtPair<T>* __restrict__ YZ, IT* __restrict__ B, const doub
       s = cheap ? s : si;
     }
     dmin = (!testf && e < dmin) ? e : dmin;
-    const bool pass = (s <= (testf ? zf : ez.y)) && (e != 0);      // :162; only the bottom of the whole stack is protected
+    // :162.  Protected: every entry that links to ITSELF — the bottom of the whole stack (B[0] = 0: the reference's `k > 0`) and, for a speculative
+    // stitch, the still unpatched bottom of a segment further left (z = -inf, B[s] = s).  For finite lines the second never matters (s <= -inf is
+    // false: the walk stops there anyway, stale, and is redone); with s = -inf — a +inf score beside finite ones in a double line — it is what ends
+    // the walk: a pass always moves to a strictly lower element (e_pass = a below-link, or the element F sits on), so the loop ends for every
+    // bit pattern.  The same compare as the `e != 0` it replaces (e_pass is needed below either way).
+    const int e_pass = testf ? fb : eb;
+    const bool pass = (s <= (testf ? zf : ez.y)) && (e_pass != e);
     // pass: F popped (continue below it) or one more pop below the segment; q unchanged, explicit tests from now on.
     // fail, !testf: q is pushed on e: the new F, top of the segment's part of the stack; the next element tests it.
     // fail, testf: F survives q — if the local scan popped it (bf == q: not cheap) the invariant is lost —; q's popper is
     //              the next element to reach F (else none).
     const bool newf = !pass && !testf;
     bad = bad || (!pass && testf && !cheap);
-    const int e_pass = testf ? fb : eb;
     const int nq = testf ? (bq > q ? bq : s1) : q + 1;
     f = newf ? q : f;
     zf = newf ? s : zf;

@@ -767,6 +767,13 @@ static int set_level_features_(pbd_handle* h, int level, const void* in, int ts)
         return fail(h, PBD_ERR_ARG, h->conv_mode == PBD_CONV_SPLIT_F16 ? "PBD_CONV_SPLIT_F16: a feature outside the bank's domain (|f| < 15.99609375 = 65520 / 4096, finite)"
                                                                         : "PBD_CONV_SPLIT: a feature outside bfloat16's finite range (|f| < 3e38, finite): use PBD_CONV_MFMA / PBD_CONV_EXACT");
   }
+  // every bank: finite features only — a NaN / inf feature becomes non-finite responses, which the distance transform does not take (DESIGN.md
+  // "Input domain of the distance transform"); the scan reads the host copy that is uploaded below
+  {
+    const size_t nf = (size_t)L.cw * L.ch * PBD_FLEN;
+    if ((ts == 4 ? pbd_first_nonfinite((const float*)in, nf) : pbd_first_nonfinite((const double*)in, nf)) != nf)
+      return fail(h, PBD_ERR_ARG, "non-finite feature: responses must stay finite for the distance transform");
+  }
   ON_DEVICE(h);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemcpy(h->d_feat + L.cell_off * PBD_FLEN * ts, in, (size_t)L.cw * L.ch * PBD_FLEN * ts, hipMemcpyHostToDevice));
@@ -849,6 +856,10 @@ static int set_level_response_(pbd_handle* h, int level, int filter, const void*
   if (!h->fperm.empty()) filter = h->fperm[filter];
   const Level& L = h->lv[level];
   const size_t HW = (size_t)L.cw * L.ch;
+  if (!in) return fail(h, PBD_ERR_ARG, "null response map");
+  // the distance transform's domain is finite scores (DESIGN.md "Input domain of the distance transform"): scanned on the host copy that is uploaded below
+  if ((ts == 4 ? pbd_first_nonfinite((const float*)in, HW) : pbd_first_nonfinite((const double*)in, HW)) != HW)
+    return fail(h, PBD_ERR_ARG, "non-finite response: the distance transform takes finite scores only");
   ON_DEVICE(h);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemcpy(h->d_resp + (L.cell_off * h->md.nfilters + filter * HW) * ts, in, HW * ts, hipMemcpyHostToDevice));
@@ -1066,8 +1077,13 @@ static int dt2d_(pbd_handle* h, const void* in, int rows, int cols, double ax, d
   if (!h || !in || rows <= 0 || cols <= 0 || rows > 32767 || cols > 32767) return PBD_ERR_ARG;
   CHECK_SCALAR(h, tsz);
   if (ax == 0 || ay == 0) return fail(h, PBD_ERR_ARG, "a must be non-zero");
-  ON_DEVICE(h);
+  if (!std::isfinite(ax) || !std::isfinite(bx) || !std::isfinite(ay) || !std::isfinite(by)) return fail(h, PBD_ERR_ARG, "a and b must be finite");
   const size_t HW = (size_t)rows * cols;
+  // finite scores only (DESIGN.md "Input domain of the distance transform"): nothing non-finite is ever handed to k_dt_pass; the scan reads the
+  // array that is copied below
+  if ((tsz == 4 ? pbd_first_nonfinite((const float*)in, HW) : pbd_first_nonfinite((const double*)in, HW)) != HW)
+    return fail(h, PBD_ERR_ARG, "non-finite score: the distance transform takes finite maps only");
+  ON_DEVICE(h);
   const size_t ts = (size_t)tsz;
   char *d_in, *d_tmp, *d_sdt;
   int16_t *d_ixT, *d_iy;
@@ -1103,7 +1119,13 @@ static int dt2d_(pbd_handle* h, const void* in, int rows, int cols, double ax, d
   HIPCHK(h, hipMemcpyAsync(out, d_sdt, HW * ts, hipMemcpyDeviceToHost, h->stream));   // the y pass's scores, untouched
   HIPCHK(h, hipMemcpyAsync(hx.data(), d_ixT, HW * 2, hipMemcpyDeviceToHost, h->stream));   // the passes' own pointers
   HIPCHK(h, hipMemcpyAsync(hy.data(), d_iy, HW * 2, hipMemcpyDeviceToHost, h->stream));
+  // finite arguments can still leave the domain BETWEEN the passes: the x pass's a d^2 + b d + y may overflow.  The kernel ends on any bit pattern
+  // (dt_core.hpp: dt_stitch1), but only finite lines are the reference's bit for bit, so the x pass's scores come back too and both are scanned
+  std::vector<char> htmp(HW * ts);
+  HIPCHK(h, hipMemcpyAsync(htmp.data(), d_tmp, HW * ts, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  const bool left_domain = tsz == 4 ? pbd_first_nonfinite((const float*)htmp.data(), HW) != HW || pbd_first_nonfinite((const float*)out, HW) != HW
+                                    : pbd_first_nonfinite((const double*)htmp.data(), HW) != HW || pbd_first_nonfinite((const double*)out, HW) != HW;
   for (size_t i = 0; i < HW; ++i) {   // pointer composition of compute() (:233-244), or the true arg-max one
     const int m_ = (int)(i / cols), n_ = (int)(i - (size_t)m_ * cols);
     int x, y;
@@ -1114,6 +1136,8 @@ static int dt2d_(pbd_handle* h, const void* in, int rows, int cols, double ax, d
   }
   hipFree(d_in); hipFree(d_tmp); hipFree(d_sdt); hipFree(d_ixT); hipFree(d_iy);
   hipFree(d_maps); hipFree(d_tasks);
+  if (left_domain)
+    return fail(h, PBD_ERR_ARG, "the scores left the finite range in the x or the y pass (|y| + |a| d^2 + |b| d overflows): outside the distance transform's domain");
   return PBD_OK;
 }
 int pbd_dt2d(pbd_handle* h, const float* in, int rows, int cols, double ax, double bx, double ay, double by, int osx,

@@ -92,6 +92,11 @@ static int ingest_model(HostModel* h, const pbd_model_desc* m, std::string* err)
   h->defw.assign(m->defw, m->defw + (size_t)m->ndefs * 4);
   h->anchors.assign(m->anchors, m->anchors + (size_t)m->ndefs * 2);
   h->biasw.assign(m->biasw, m->biasw + m->nbias);
+  // weights: finite, all of them — a NaN / inf filter weight or bias puts non-finite scores in front of the distance transform, a
+  // non-finite deformation weight is a non-finite quadratic (the DT's input domain, pbd_plan.hpp: pbd_first_nonfinite)
+  if (pbd_first_nonfinite(h->filters.data(), h->filters.size()) != h->filters.size()) return fail(err, PBD_ERR_ARG, "model: non-finite filter weight");
+  if (pbd_first_nonfinite(h->biasw.data(), h->biasw.size()) != h->biasw.size()) return fail(err, PBD_ERR_ARG, "model: non-finite bias");
+  if (pbd_first_nonfinite(h->defw.data(), h->defw.size()) != h->defw.size()) return fail(err, PBD_ERR_ARG, "model: non-finite deformation weight");
   h->md = *m;
   h->md.filters = h->filters.data(); h->md.defw = h->defw.data(); h->md.anchors = h->anchors.data();
   h->md.biasw = h->biasw.data(); h->md.part_offset = h->part_offset.data(); h->md.parentid = h->parentid.data();

@@ -2,6 +2,7 @@
 // two pure phases that build them for one frame geometry (plan_layout: geometry and buffers; plan_tables: every table, from the
 // buffers' base addresses).  Host-only: compiles with plain g++ (no HIP runtime); pbd_api.cpp allocates and uploads.
 #pragma once
+#include <cmath>
 #include <stddef.h>
 #include <stdint.h>
 #include <string>
@@ -191,6 +192,16 @@ struct HostModel {
   std::vector<int> fperm;        // [caller filter] -> internal filter (empty: identity)
   std::vector<SizeGroup> groups; // size groups (kh, kw, n0, nf); the device fields are filled by the upload
 };
+// The distance transform's input domain: FINITE scores and FINITE quadratics (DESIGN.md "Input domain of the distance transform").  Every
+// entry point that takes score maps or weights from the host scans them with this before anything reaches k_dt_pass: a NaN or an
+// infinity makes the reference's own loop compare unordered values, and can keep a speculative stitch of dt_core.hpp from ending.
+// Returns the index of the first non-finite element, or n.
+template <typename T>
+static inline size_t pbd_first_nonfinite(const T* v, size_t n) {
+  size_t i = 0;
+  while (i < n && std::isfinite(v[i])) ++i;
+  return i;
+}
 // pbd_create (sized = false) / pbd_create_sized up to the device: options, model validation and topology, the filter-bank mode.
 // PBD_OK, or an error code with its message in *err.
 int plan_model(HostModel& hm, const pbd_model_desc* model, const int32_t* fsize, bool sized, const pbd_options* opt, std::string* err);

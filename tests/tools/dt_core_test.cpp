@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
+#include <cmath>
 #include <random>
 #include <vector>
 #include "dt_core.hpp"
@@ -102,6 +103,7 @@ static void run_line(const T* src, int len, int lanes, double a, double b, int o
 }
 
 static int g_kind = -1;
+enum { NKINDS = 11 };   // kinds of line: 0-7 of magnitude ~1, 8-10 out in the float range (finite: the distance transform's domain)
 template <typename T>
 static int sweep(long nlines, unsigned seed) {
   std::mt19937_64 rng(seed);
@@ -115,7 +117,7 @@ static int sweep(long nlines, unsigned seed) {
   for (long it = 0; it < nlines; ++it) {
     const int len = (rng() % 4 == 0) ? 1 + (int)(rng() % 500) : lens[rng() % (sizeof(lens) / sizeof(int))];
     const int lanes = lanesv[rng() % (sizeof(lanesv) / sizeof(int))];
-    const int kind = g_kind >= 0 ? g_kind : (int)(rng() % 8);
+    const int kind = g_kind >= 0 ? g_kind : (int)(rng() % NKINDS);
     double scale = 1.5;
     for (int i = 0; i < len; ++i) {
       double v;
@@ -127,7 +129,10 @@ static int sweep(long nlines, unsigned seed) {
         case 4: v = 0.25 * std::round(nd(rng) * 4); break;                   // quarter steps
         case 5: v = (i % 2) ? 1.0 : 0.0; break;                              // alternating
         case 6: v = -0.01 * (i - len / 2.0) * (i - len / 2.0) * (ud(rng) < 0.5 ? 1 : 0.5) + 0.01 * nd(rng); break;  // concave: everything survives
-        default: v = 0.0; break;                                            // constant
+        case 7: v = 0.0; break;                                              // constant
+        case 8: v = std::ldexp((it & 2) ? std::round(nd(rng) * 2) : nd(rng) * scale, 100); break;    // values x 2^100: float quotients leave the range (flagged, redone exactly)
+        case 9: v = std::ldexp((it & 2) ? std::round(nd(rng) * 2) : nd(rng) * scale, -120); break;   // values x 2^-120: quotients below 2^-124 / in the last normal binades
+        default: v = nd(rng) * scale; break;                                 // 10: ordinary values, extreme curvature (below)
       }
       src[i] = (T)v;
     }
@@ -135,7 +140,8 @@ static int sweep(long nlines, unsigned seed) {
     // the model's weights are floats (fused arithmetic allowed for float maps: every second such line runs it); one line in eight gets quadratics
     // that are NOT converted floats (pbd_dt2d's caller may hand in any double): unfused only
     const bool anyd = rng() % 8 == 0;
-    const double a_ = rng() % 3 == 0 ? as[rng() % 10] : 0.005 + 0.045 * ud(rng);
+    static const float far_as[] = {1e-30f, 1e-38f, 1e20f, 1e30f};   // kind 10: curvatures far out, as floats (1e-38f is subnormal: i2a = 1 / (2a) ~ 5e37 is still finite)
+    const double a_ = kind == 10 ? (double)far_as[rng() % 4] : rng() % 3 == 0 ? as[rng() % 10] : 0.005 + 0.045 * ud(rng);
     const double b_ = rng() % 3 == 0 ? 0.0 : (ud(rng) * 0.02 - 0.01) * (rng() % 4 == 0 ? 5 : 1);
     const double a = anyd ? -a_ : -(double)(float)a_;
     const double b = anyd ? -b_ : -(double)(float)b_;

@@ -157,12 +157,18 @@ static void replay_pass(const T* src, const DtTask* tasks, int ntasks, const DtM
 }
 
 // pbd_dt2d's two passes (pbd_api.cpp: dt2d_): out = the y pass's scores [rows][cols], ix / iy composed like pbd_dt2d's
-// (dt_correct_ptr = 0), counts[NCOUNT] accumulated over both passes.  Returns 0, or -1 for arguments pbd_dt2d refuses.
-template <typename T>
+// (dt_correct_ptr = 0), counts[NCOUNT] accumulated over both passes.  Returns 0; -1 for arguments pbd_dt2d refuses; 1 where the x pass's or the
+// y pass's scores left the finite range although the arguments were finite (pbd_dt2d: PBD_ERR_ARG after the run — outside the domain, where only
+// termination is promised).  CHECKED = false (dt_replay_core_*, host only): dt_core.hpp on ANY bit pattern, for the termination tests — the stitch
+// loop ends whatever the line holds; the product never runs such a map (pbd_dt2d refuses it).
+template <typename T, bool CHECKED = true>
 static int replay_dt2d(const T* in, int rows, int cols, double ax, double bx, double ay, double by, int osx, int osy, T* out, int32_t* ix,
                        int32_t* iy, long long* counts) {
   const int tsz = (int)sizeof(T);
   if (rows <= 0 || cols <= 0 || rows > 32767 || cols > 32767 || ax == 0 || ay == 0) return -1;
+  // pbd_dt2d's domain: finite quadratics, finite scores (pbd_plan.hpp: pbd_first_nonfinite) — a map outside it never reaches dt_core.hpp
+  if (!std::isfinite(ax) || !std::isfinite(bx) || !std::isfinite(ay) || !std::isfinite(by)) return -1;
+  if (CHECKED && pbd_first_nonfinite(in, (size_t)rows * cols) != (size_t)rows * cols) return -1;
   const int nt = tsz == 8 ? 64 : PBD_DT_NT_DEFAULT;
   const size_t budget = std::max<size_t>(40 * 1024, dt_lds_bytes(dt_stride_for(std::max(rows, cols)), 4, tsz, nt));
   if (budget > 160 * 1024) return -1;
@@ -185,7 +191,7 @@ static int replay_dt2d(const T* in, int rows, int cols, double ax, double bx, do
     ix[i] = x;
     iy[i] = hy[(size_t)m * cols + x];
   }
-  return 0;
+  return pbd_first_nonfinite(tmp.data(), HW) != HW || pbd_first_nonfinite(out, HW) != HW ? 1 : 0;
 }
 
 extern "C" int dt_replay_ncounts() { return NCOUNT; }
@@ -196,4 +202,13 @@ extern "C" int dt_replay_dt2d(const float* in, int rows, int cols, double ax, do
 extern "C" int dt_replay_dt2d_f64(const double* in, int rows, int cols, double ax, double bx, double ay, double by, int osx, int osy,
                                   double* out, int32_t* ix, int32_t* iy, long long* counts) {
   return replay_dt2d<double>(in, rows, cols, ax, bx, ay, by, osx, osy, out, ix, iy, counts);
+}
+// host only: no domain check in front (see replay_dt2d)
+extern "C" int dt_replay_core_dt2d(const float* in, int rows, int cols, double ax, double bx, double ay, double by, int osx, int osy, float* out,
+                                   int32_t* ix, int32_t* iy, long long* counts) {
+  return replay_dt2d<float, false>(in, rows, cols, ax, bx, ay, by, osx, osy, out, ix, iy, counts);
+}
+extern "C" int dt_replay_core_dt2d_f64(const double* in, int rows, int cols, double ax, double bx, double ay, double by, int osx, int osy,
+                                       double* out, int32_t* ix, int32_t* iy, long long* counts) {
+  return replay_dt2d<double, false>(in, rows, cols, ax, bx, ay, by, osx, osy, out, ix, iy, counts);
 }
