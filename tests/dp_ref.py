@@ -153,3 +153,107 @@ def pointer_planes(model, comp, maps):
     if not Ik:
         return (np.zeros((0, H, W), np.int32),) * 3
     return np.stack(Ix), np.stack(Iy), np.stack(Ik)
+
+
+# ---------------------------------------------------------------- the plain statement, and the same with one slip
+SLIPS = ("zero_order", "ge", "bias_after_max", "anchor_clamp", "child_count")
+
+
+def dt_definition(src, ax, bx, ay, by, osx, osy, dtype, clamp=False):
+    """DistanceTransform<T>::compute by definition: the x pass out(m, n) = max_n' T(ax d^2 + bx d + src(m, n')), d = n + osx - n' (the
+    quadratic evaluated in double as a sq + b d + y, left to right, then narrowed: Quadratic::operator()), the FIRST maximum as pointer; the y
+    pass the same down the columns of the x pass's output; Iy composed as the reference does (Iy'(m, n) = Iy(m, Ix(m, n)), :233-244).
+    clamp (a slip): the read-out position n + os clamped to the map."""
+    def one_pass(a2, a, b, os_):
+        R, N = a2.shape
+        pos = np.arange(N) + os_
+        if clamp:
+            pos = np.clip(pos, 0, N - 1)
+        d = (pos[:, None] - np.arange(N)[None, :]).astype(np.float64)                   # [n, n']
+        with np.errstate(over="ignore"):
+            v = ((a * (d * d) + b * d)[None] + a2.astype(np.float64)[:, None, :]).astype(dtype)   # [r, n, n']
+        ptr = np.argmax(v, axis=2).astype(np.int32)
+        return np.take_along_axis(v, ptr[..., None], 2)[..., 0], ptr
+    src = np.ascontiguousarray(src, dtype)
+    tmp, ix = one_pass(src, ax, bx, osx)
+    outT, iyT = one_pass(np.ascontiguousarray(tmp.T), ay, by, osy)
+    out, iy = np.ascontiguousarray(outT.T), np.ascontiguousarray(iyT.T)
+    return out, ix, np.take_along_axis(iy, ix, 1)
+
+
+def _reduce(wvs, how):
+    """Math::reduceMax over a list of maps -> (max, index).  how: "gt" the first maximum under `>` (K == 1: a copy); slips: "ge" the last,
+    "zero_order" -0.0 ordered below +0.0 (a hardware max, or integer keys)"""
+    if len(wvs) == 1:
+        return wvs[0], np.zeros(wvs[0].shape, np.int32)
+    T = wvs[0].dtype.type
+    best, idx = np.where(wvs[0] > T(-np.inf), wvs[0], T(-np.inf)), np.zeros(wvs[0].shape, np.int32)
+    for k in range(1, len(wvs)):
+        wv = wvs[k]
+        take = wv >= best if how == "ge" else wv > best
+        if how == "zero_order":
+            take = take | ((wv == best) & np.signbit(best) & ~np.signbit(wv))
+        best, idx = np.where(take, wv, best), np.where(take, k, idx).astype(np.int32)
+    return best, idx
+
+
+def plain_level(model, comp, resp, dtype=np.float32, orc=None, slip=None):
+    """DynamicProgram<T>::min for one level as brute-force max-plus: the distance transform by definition (dt_definition; `orc`: the
+    oracle's orc.dt2d instead), the first maximum over the child's mixtures, a deformation row per (part, mixture), any anchor.
+    -> Ix, Iy, Ik [planes, H, W] in the oracle's plane order, rootv, rooti.  slip: one of SLIPS, the statement with that one mistake."""
+    assert slip is None or slip in SLIPS
+    T = np.dtype(dtype).type
+    P = model.nparts(comp)
+    fid, did, bid, par = model.filterid[comp], model.defid[comp], model.biasid[comp], model.parentid[comp]
+    how = slip if slip in ("ge", "zero_order") else "gt"
+    acc = {}
+    planes = {}
+    for p in range(P - 1, 0, -1):
+        K, L = len(fid[p]), len(fid[par[p]])
+        sdt, ix, iy = [], [], []
+        for mm in range(K):
+            src = np.asarray(acc.get(fid[p][mm], resp[fid[p][mm]]), dtype)
+            w, a = model.defw[did[p][mm]], model.anchors[did[p][mm]]
+            q = (-float(w[0]), -float(w[1]), -float(w[2]), -float(w[3]), int(a[0]), int(a[1]))
+            o, x_, y_ = orc.dt2d(src, *q, dtype=dtype) if orc is not None and slip != "anchor_clamp" else \
+                dt_definition(src, *q, dtype, clamp=slip == "anchor_clamp")
+            sdt.append(o); ix.append(x_); iy.append(y_)
+        ix, iy = np.stack(ix), np.stack(iy)
+        planes[p] = []
+        with np.errstate(over="ignore"):
+            for m in range(L):
+                mb = min(m, K - 1) if slip == "child_count" else m          # the slip: K columns of biases where the parent has L
+                if slip == "bias_after_max":
+                    best, k = _reduce(sdt, how)
+                    best = (best + np.asarray(model.biasw, dtype)[np.asarray(bid[p])[k] + mb]).astype(dtype)
+                else:
+                    best, k = _reduce([(sdt[mm] + T(model.biasw[bid[p][mm] + mb])).astype(dtype) for mm in range(K)], how)
+                planes[p].append((np.take_along_axis(ix, k[None], 0)[0], np.take_along_axis(iy, k[None], 0)[0], k))
+                f = fid[par[p]][m]
+                acc[f] = (np.asarray(acc.get(f, resp[f]), dtype) + best).astype(dtype)
+    bias = T(model.biasw[bid[0][0]])
+    with np.errstate(over="ignore"):
+        rv, ri = _reduce([(np.asarray(acc.get(f, resp[f]), dtype) + bias).astype(dtype) for f in fid[0]], how)
+    flat = [t for p in range(1, P) for t in planes[p]]
+    H, W = rv.shape
+    if not flat:
+        return (np.zeros((0, H, W), np.int32),) * 3 + (rv, ri)
+    return tuple(np.stack([t[i] for t in flat]) for i in range(3)) + (rv, ri)
+
+
+def rescore(model, comp, resp, locs):
+    """(score, sum of |terms|) of one configuration locs [P, 3] = (x, y, mixture) in float64: responses at the part locations, the
+    deformation cost of every (parent, child) pair and the biases (matlab/detection/detect.m:139-145)"""
+    fid, did, bid, par = model.filterid[comp], model.defid[comp], model.biasid[comp], model.parentid[comp]
+    terms = [float(model.biasw[bid[0][0]])]
+    for p in range(model.nparts(comp)):
+        x, y, k = (int(v) for v in locs[p])
+        terms.append(float(resp[fid[p][k], y, x]))
+        if p > 0:
+            px, py, pm = (int(v) for v in locs[par[p]])
+            w = np.asarray(model.defw[did[p][k]], np.float64)
+            ax_, ay_ = (int(v) for v in model.anchors[did[p][k]])
+            dx, dy = px + ax_ - x, py + ay_ - y
+            terms += [-w[0] * dx * dx, -w[1] * dx, -w[2] * dy * dy, -w[3] * dy, float(model.biasw[bid[p][k] + pm])]
+    import math
+    return math.fsum(terms), math.fsum(abs(t) for t in terms)
