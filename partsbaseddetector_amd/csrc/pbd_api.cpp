@@ -335,76 +335,46 @@ static void ensure_feat_split(pbd_handle* h) {
   h->feat_split_ok = true;
 }
 
-// A mixed bank: each size group runs the kernel a uniform bank of its size and the handle's mode runs (the run-time-size
-// instantiation, MIX: writing planes n0 .. n0 + nf_g - 1 of every level block of md.nfilters planes), one launch per group.
-static int run_pdf_mixed(pbd_handle* h) {
-  const pbd_model_desc& m = h->md;
-  ensure_feat_split(h);
-  for (size_t gi = 0; gi < h->groups.size(); ++gi) {
-    const SizeGroup& g = h->groups[gi];
-    const ConvTile* tiles = h->d_conv_tiles_mix + gi * h->n_conv_tiles;
-    const size_t wt_n = (size_t)g.kh * g.kw * m.flen * g.nfpad;
-    if (h->conv_mode == PBD_CONV_SPLIT_F16)
-      launch_conv_split16(tiles, h->n_conv_tiles, h->d_levels, h->d_feat_split, g.d_wS, (float*)h->d_resp, g.nf, g.kh, g.kw, g.d_oscale, 0, h->stream, m.nfilters);
-    else if (h->conv_mode == PBD_CONV_SPLIT)
-      launch_conv_split(tiles, h->n_conv_tiles, h->d_levels, h->d_feat_split, g.d_wS, (float*)h->d_resp, g.nf, g.kh, g.kw, 0, h->stream, m.nfilters);
-    else if (h->conv_mode == PBD_CONV_MFMA && h->ts == 8)
-      launch_conv_mfma_f64(tiles, h->n_conv_tiles, h->d_levels, (const double*)h->d_feat, (const double*)g.d_wT, (const double*)g.d_wT + wt_n + m.flen,
-                           (double*)h->d_resp, g.nf, g.nfpad, g.kh, g.kw, h->stream, m.nfilters);
-    else if (h->conv_mode == PBD_CONV_MFMA)
-      launch_conv_mfma16_f32(tiles, h->n_conv_tiles, h->d_levels, (const float*)h->d_feat, (const float*)g.d_wT,
-                             (const float*)g.d_wT + 2 * wt_n + m.flen, (float*)h->d_resp, g.nf, g.nfpad, 20, h->stream, g.kh, g.kw, m.nfilters);
-    else
-      launch_conv_exact(tiles, h->n_conv_tiles, h->d_levels, h->d_feat, g.d_wT, h->d_resp, h->ts, g.nf, g.nfpad, g.kh, g.kw, h->stream, m.nfilters);
-  }
-  LAUNCHCHK(h, "filter bank");
-  mark_responses(h);
-  return PBD_OK;
+// One bank launch by the handle's mode and scalar type: `tiles` over nf filters of kh x kw (wT / wS / oscale: that bank's uploads).  nf_stride > 0:
+// a size group of a mixed bank — the run-time-size instantiation, writing the group's planes of every level block of nf_stride planes
+static void launch_bank(pbd_handle* h, const ConvTile* tiles, int nf, int nfpad, int kh, int kw, const void* wT, const uint16_t* wS,
+                        const float* oscale, int nf_stride) {
+  // wT: [tap][channel][nfpad], a border cell, (float: the [tap][half][k][n][s] copy,) then the [tap][group][k][n][u] copy the MFMA banks load 16 bytes at a time
+  const size_t wt_n = (size_t)kh * kw * h->md.flen * nfpad, cell = h->md.flen;
+  if (h->conv_mode == PBD_CONV_SPLIT_F16)   // ... over two scaled binary16 parts
+    launch_conv_split16(tiles, h->n_conv_tiles, h->d_levels, h->d_feat_split, wS, (float*)h->d_resp, nf, kh, kw, oscale, h->stream, nf_stride);
+  else if (h->conv_mode == PBD_CONV_SPLIT)   // the bank on the bf16 matrix units, over the features' three exact bfloat16 parts
+    launch_conv_split(tiles, h->n_conv_tiles, h->d_levels, h->d_feat_split, wS, (float*)h->d_resp, nf, kh, kw, h->stream, nf_stride);
+  else if (h->conv_mode == PBD_CONV_MFMA && h->ts == 8)
+    launch_conv_mfma_f64(tiles, h->n_conv_tiles, h->d_levels, (const double*)h->d_feat, (const double*)wT + wt_n + cell, (double*)h->d_resp, nf, nfpad, kh, kw, h->stream, nf_stride);
+  else if (h->conv_mode == PBD_CONV_MFMA)
+    launch_conv_mfma16_f32(tiles, h->n_conv_tiles, h->d_levels, (const float*)h->d_feat, (const float*)wT + 2 * wt_n + cell, (float*)h->d_resp, nf, nfpad, kh, kw, h->stream, nf_stride);
+  else
+    launch_conv_exact(tiles, h->n_conv_tiles, h->d_levels, h->d_feat, wT, h->d_resp, h->ts, nf, nfpad, kh, kw, h->stream, nf_stride);
 }
 
+// Tuning and probe libraries (k_conv_variants.hip): the uniform bank of a handle under PBD_MFMA_VARIANT, PBD_SPLIT_VARIANT, PBD_CONV_LDS_KB or, probe
+// build, PBD_MFMA64_QUARTERS / PBD_CONV_PRIO — a measured-and-dropped kernel or configuration; false: no knob is set for the handle's mode, or the bank
+// is mixed: nothing launched.  The product has no such unit.
+#if defined(PBD_TUNE) || defined(PBD_PROBES)
+bool launch_conv_variant(const pbd_handle* h);
+#else
+static bool launch_conv_variant(const pbd_handle*) { return false; }
+#endif
+
+// The filter bank: one launch over the plan's tiles; a mixed bank: one launch per size group, over the group's copy of the tile list
 static int run_pdf(pbd_handle* h) {
   const pbd_model_desc& m = h->md;
-  if (h->mixed) return run_pdf_mixed(h);
   ensure_feat_split(h);
-  if (h->conv_mode == PBD_CONV_SPLIT_F16) {
-    static const int svariant16 = PBD_PROBE_ENV("PBD_SPLIT_VARIANT") ? atoi(PBD_PROBE_ENV("PBD_SPLIT_VARIANT")) : 0;   // tuning builds
-    launch_conv_split16(h->d_conv_tiles, h->n_conv_tiles, h->d_levels, h->d_feat_split, h->d_wS, (float*)h->d_resp, m.nfilters, m.kh, m.kw, h->d_split_oscale, svariant16, h->stream);
-  } else if (h->conv_mode == PBD_CONV_SPLIT) {
-    // the bank on the bf16 matrix units, over the features' three exact bfloat16 parts
-    static const int svariant = PBD_PROBE_ENV("PBD_SPLIT_VARIANT") ? atoi(PBD_PROBE_ENV("PBD_SPLIT_VARIANT")) : 0;   // tuning builds
-    if (svariant == 6 && m.kh == 5 && m.kw == 5)
-      launch_conv_split_persistent(h->d_conv_tiles, h->n_conv_tiles, h->d_levels, h->d_feat_split, h->d_wS, (float*)h->d_resp, m.nfilters, h->ncu, h->stream);
-    else
-    launch_conv_split(h->d_conv_tiles, h->n_conv_tiles, h->d_levels, h->d_feat_split, h->d_wS, (float*)h->d_resp, m.nfilters, m.kh, m.kw, svariant, h->stream);
-  } else if (h->conv_mode == PBD_CONV_MFMA)
-    if (h->ts == 8) launch_conv_mfma_f64(h->d_conv_tiles, h->n_conv_tiles, h->d_levels, (const double*)h->d_feat, (const double*)h->d_wT,
-                                         (const double*)h->d_wT + (size_t)m.kh * m.kw * m.flen * h->nfpad + m.flen, (double*)h->d_resp, m.nfilters, h->nfpad, m.kh, m.kw, h->stream);
-    else {
-      // default (20): 16x16x4 MFMA, tile staged in two channel halves, TWO 16-filter n-tiles per workgroup, B operand by 16-byte
-      // loads from the [tap][half][k][n][u] copy of the filters (k_conv_mfma16<float, 2, 3, 2, true>: 27 KB of LDS per workgroup, so
-      // DT blocks of other frames co-reside on the CU).  Two n-tiles per workgroup: alone the same time as one, but every tile is
-      // staged half as often and with frames in flight that VALU / LDS time goes to the other frames' DT blocks (1 392 vs 1 331
-      // frames/s, batches of 4 on 3 handles).  16-byte B loads: 0.339 vs 0.388 ms sequential, 1 419 vs 1 391 frames/s (eight
-      // global_load_dword per 32 MFMAs cost the MFMA pipe a quarter of its issue rate: tests/tools/mfma_rate_probe.hip).
-      // PBD_MFMA_VARIANT (probe / tuning builds): 0 = the older 32x32x2 kernel, 1 = whole tile, 2 = halves at 5 waves/SIMD, 3 = one
-      // n-tile, 4 = channel quarters, 5-9 = n-tile counts with 4-byte B loads, 10 / 11 / 19 = the persistent double-buffered
-      // kernel k_conv_glds at 2 / 3 / 1 workgroups per CU (0.354 ms sequential, 1 353-1 378 frames/s), 21 / 22 = one n-tile /
-      // 2 waves per SIMD register allocation with 16-byte B loads
-      static const int lds_req = g_conv_lds_req_kb = PBD_PROBE_ENV("PBD_CONV_LDS_KB") ? atoi(PBD_PROBE_ENV("PBD_CONV_LDS_KB")) : 0;
-      (void)lds_req;
-      static const int variant = PBD_PROBE_ENV("PBD_MFMA_VARIANT") ? atoi(PBD_PROBE_ENV("PBD_MFMA_VARIANT")) : 20;
-      if (variant >= 10 && variant < 20 && m.kh == 5 && m.kw == 5 && m.flen == PBD_FLEN)
-        launch_conv_glds_f32(h->d_conv_tiles, h->n_conv_tiles, h->d_levels, (const float*)h->d_feat,
-                             (const float*)h->d_wT + (size_t)m.kh * m.kw * m.flen * h->nfpad + m.flen /* [tap][half][k][n][s] copy */, (float*)h->d_resp, m.nfilters, h->nfpad,
-                             (const float*)h->d_wT + (size_t)m.kh * m.kw * m.flen * h->nfpad /* border cell */, variant == 19 ? 1 : variant == 18 ? 0 : variant - 8, h->ncu, h->stream);
-      else if (variant || m.kh != 5 || m.kw != 5)   // (filters other than 5 x 5: the same kernel with a run-time tap loop)
-        launch_conv_mfma16_f32(h->d_conv_tiles, h->n_conv_tiles, h->d_levels, (const float*)h->d_feat, (const float*)h->d_wT,
-                               (const float*)h->d_wT + 2 * (size_t)m.kh * m.kw * m.flen * h->nfpad + m.flen, (float*)h->d_resp, m.nfilters, h->nfpad, variant, h->stream, m.kh, m.kw);
-      else
-        launch_conv_mfma(h->d_conv_tiles, h->n_conv_tiles, h->d_levels, (const float*)h->d_feat, (const float*)h->d_wT, (float*)h->d_resp, m.nfilters, h->nfpad, m.kh, m.kw, h->stream);
+  const bool variant_ran = launch_conv_variant(h);
+  if (h->mixed) {
+    for (size_t gi = 0; gi < h->groups.size(); ++gi) {
+      const SizeGroup& g = h->groups[gi];
+      launch_bank(h, h->d_conv_tiles_mix + gi * h->n_conv_tiles, g.nf, g.nfpad, g.kh, g.kw, g.d_wT, g.d_wS, g.d_oscale, m.nfilters);
     }
-  else
-    launch_conv_exact(h->d_conv_tiles, h->n_conv_tiles, h->d_levels, h->d_feat, h->d_wT, h->d_resp, h->ts, m.nfilters, h->nfpad, m.kh, m.kw, h->stream);
+  } else if (!variant_ran) {
+    launch_bank(h, h->d_conv_tiles, m.nfilters, h->nfpad, m.kh, m.kw, h->d_wT, h->d_wS, h->d_split_oscale, 0);
+  }
   LAUNCHCHK(h, "filter bank");
   mark_responses(h);
   return PBD_OK;

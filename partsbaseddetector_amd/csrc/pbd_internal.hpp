@@ -450,26 +450,20 @@ void launch_hog_binlut(uint8_t* lut, int ts, hipStream_t s);      // evaluated i
 // split-product filter bank (k_conv_split.hip): fp32 features -> three exact bfloat16 parts; kh x kw x 32 filters, float responses
 void launch_feat_split(const float* feat, uint16_t* out, size_t ncells, hipStream_t s);
 void launch_conv_split(const ConvTile* tiles, int ntiles, const LevelDev* levels, const uint16_t* feat_split, const uint16_t* wS,
-                       float* resp, int nf, int kh, int kw, int variant, hipStream_t s, int nf_stride = 0);
-void launch_conv_split_persistent(const ConvTile* tiles, int ntiles, const LevelDev* levels, const uint16_t* feat_split, const uint16_t* wS,
-                                  float* resp, int nf, int ncu, hipStream_t s);   // 5 x 5 banks: persistent workgroups, staging hidden under the MFMAs (tuning variant, not adopted)
+                       float* resp, int nf, int kh, int kw, hipStream_t s, int nf_stride = 0);
 void conv_split_filters(const float* filters, int nf, int kh, int kw, std::vector<uint16_t>& out);   // host: the d_wS layout
 // PBD_CONV_SPLIT_F16: two scaled binary16 parts per operand, three products (k_conv_split.hip)
 void launch_feat_split16(const float* feat, uint16_t* out, size_t ncells, hipStream_t s);
 void conv_split16_filters(const float* filters, int nf, int kh, int kw, std::vector<uint16_t>& out, std::vector<float>& oscale);   // oscale[filter]: the response scale
 void launch_conv_split16(const ConvTile* tiles, int ntiles, const LevelDev* levels, const uint16_t* feat_split, const uint16_t* wS,
-                         float* resp, int nf, int kh, int kw, const float* oscale, int variant, hipStream_t s, int nf_stride = 0);
+                         float* resp, int nf, int kh, int kw, const float* oscale, hipStream_t s, int nf_stride = 0);
 void launch_conv_exact(const ConvTile* tiles, int ntiles, const LevelDev* levels, const void* feat,
                        const void* wT, void* resp, int ts, int nf, int nfpad, int kh, int kw, hipStream_t s, int nf_stride = 0);
-void launch_conv_mfma(const ConvTile* tiles, int ntiles, const LevelDev* levels, const float* feat,
-                      const float* wT, float* resp, int nf, int nfpad, int kh, int kw, hipStream_t s);
+// the 16x16x4 MFMA banks (k_conv.hip); w4u: the [tap][group][k][n][u] copy of the filters inside d_wT
 void launch_conv_mfma_f64(const ConvTile* tiles, int ntiles, const LevelDev* levels, const double* feat,
-                          const double* wT, const double* w4u, double* resp, int nf, int nfpad, int kh, int kw, hipStream_t s, int nf_stride = 0);
-extern int g_conv_lds_req_kb;
-void launch_conv_glds_f32(const ConvTile* tiles, int ntiles, const LevelDev* levels, const float* feat, const float* wT,
-                          float* resp, int nf, int nfpad, const float* border, int wg_per_cu, int ncu, hipStream_t s);
+                          const double* w4u, double* resp, int nf, int nfpad, int kh, int kw, hipStream_t s, int nf_stride = 0);
 void launch_conv_mfma16_f32(const ConvTile* tiles, int ntiles, const LevelDev* levels, const float* feat,
-                            const float* wT, const float* w4u, float* resp, int nf, int nfpad, int nhalf, hipStream_t s, int kh, int kw, int nf_stride = 0);
+                            const float* w4u, float* resp, int nf, int nfpad, int kh, int kw, hipStream_t s, int nf_stride = 0);
 void launch_dt_pass(const DtTask* tasks, int ntasks, const DtMap* maps, const FoldJob* folds, const unsigned long long* foldx, const float* biasw, size_t lds,
                     int ts, int nt, int fm, hipStream_t s);
 void launch_reduce(const ReduceJob* jobs, const ReduceBlock* blocks, int nblocks, const float* biasw, int correct_ptr,
