@@ -165,7 +165,9 @@ int pbd_abi_version(void);
  * pbd_detect_batch_rgbd_enqueue_dev_u8 and pbd_candidates_depth_filter; and the 3-D box entry points pbd_set_box3d,
  * pbd_get_box3d and pbd_candidates_box3d (with the structs pbd_camera and pbd_box3d); and the object-cluster entry points
  * pbd_set_cluster3d, pbd_get_cluster3d and pbd_candidates_cluster3d (with the struct pbd_cluster3d); and the per-part score entry
- * points pbd_set_part_scores, pbd_get_part_scores and pbd_candidates_part_scores (with the struct pbd_part_score).               */
+ * points pbd_set_part_scores, pbd_get_part_scores and pbd_candidates_part_scores (with the struct pbd_part_score); and the latent
+ * detection entry points pbd_latent_mask, pbd_dp_argbest, pbd_detect_latent_u8, pbd_detect_latent_dev_u8 and
+ * pbd_detect_batch_latent_u8.                                                                                                    */
 
 /* ---- output record: include/Candidate.hpp:56-111 --------------------------
  * One candidate = head + max_parts boxes (x, y, width, height as cv::Rect)
@@ -684,6 +686,60 @@ int pbd_candidates_part_scores(pbd_handle* h, const pbd_candidate_head* heads, c
 int pbd_set_boundary_pad(pbd_handle* h, int pad);      /* 0 = off (default) */
 int pbd_get_boundary_pad(const pbd_handle* h);
 int pbd_group_set_boundary_pad(pbd_group* g, int pad); /* forwards to every member */
+
+/* ---- latent detection: the best pose overlapping given part boxes (ABI 5, additive) ------------------------------------------
+ * detect(im, model, thresh, bbox, overlap) of matlab/detection/detect.m:18-23, 60-101, 115-118, 159-161, 342-376, the MATLAB ancestor
+ * the C++ DynamicProgram was ported from: given one box per part (an annotation, a tracker), the single highest-scoring pose whose
+ * every part overlaps its box by more than `overlap`.  It is how the models are trained (latent positives) and evaluated with a known
+ * person box.  Filtering the thresholded output cannot reproduce it: the constraint acts inside the DP, on every part.
+ * Inputs, per frame: truth[max_parts][4] int32 boxes in the convention the detect entries return (x, y, width, height of
+ *   cv::Rect(xy1, xy2): the box covers pixels x .. x + width, y .. y + height); optional mix[max_parts] int32 (NULL: all free),
+ *   -1 = free, m >= 0 = this part must take mixture m (bbox.m, detect.m:90-93); component, -1 = all; overlap in [0, 1).  Component
+ *   c uses the first nparts(c) rows.
+ * Window of a cell: for part p, mixture m, level n, cell (x, y) the box pbd_dp_argmin would report there — sz = round(rows * scale)
+ *   with the rows of the mixture's filter (rows x rows: the size quirk kept), x1 = round((x - org) * scale), y1 alike, org = 1 +
+ *   the boundary pad, products in T rounded half to even — covering pixels x1 .. x1 + sz - 1, y1 .. y1 + sz - 1.
+ * Overlap (detect.m:360-376), in float64, operations in the order written, never fused, with x2 = x1 + sz - 1 and the truth's
+ *   bx1 = tx, bx2 = tx + tw: w = max(0, min(x2, bx2) - max(x1, bx1) + 1), h alike; inter = h * w; area = sz * sz;
+ *   box = (tw + 1) * (th + 1); the cell is admissible iff inter / (area + box - inter) > overlap.  A returned record's own boxes as
+ *   truth give overlap exactly 1 at that record's cells.
+ * Mask: an inadmissible cell of the response plane of (p, m) becomes (T)-1e10 (detect.m's -INF; exact in float).  With mix[p] = m0
+ *   every plane of part p other than m0 becomes -1e10 throughout and only m0 gets the overlap mask: the part's admissible cells are
+ *   then those of plane m0.
+ * Skip rule (detect.m:60-74): a (level, component) pair in which some part has no admissible cell in any of its mixtures yields
+ *   nothing.  DEVIATION from MATLAB: it tests mixture 1 only, on its stated assumption that all mixtures of a part have one size;
+ *   this library has a size per mixture (pbd_create_sized) and tests them all.
+ * Result: over the remaining pairs the maximum of rootv; ties go to the smallest (level, component, y, x) (MATLAB visits the
+ *   components in a random permutation: any fixed rule conforms).  It is back-tracked as pbd_dp_argmin does, honouring
+ *   dt_correct_ptr.  *found = 0 with PBD_OK when no pair remains.  The model's threshold plays no part (detect.m:20).
+ * Domain: the unmasked terms of a configuration sum to less than 5e9 in magnitude (then every pose with a masked cell scores below
+ *   every pose without one); outside that the result is unspecified.
+ * Limits, each refused with a message: PBD_ERR_UNSUPPORTED when, among the components searched, a filter id is used by two
+ *   different (component, part) slots (the mask is written into the shared plane in place; also two mixtures of a part that is given
+ *   a mixture), when the score-map NMS is on (reserved[0] > 0), and for pbd_group members; PBD_ERR_ARG for a negative width or
+ *   height, overlap outside [0, 1), mix outside the part's mixtures, component out of range; PBD_ERR_STATE while a frame is pending.
+ * All three dp_modes and the compact memory plan work: the mask precedes min().  Latent frames run their launches eagerly, as
+ * depth-carrying frames do; plain frames and their captured graph are untouched.
+ *
+ * Stage entry points.  pbd_latent_mask: after pbd_pdf / pbd_set_level_response, before pbd_dp_min: masks the resident planes
+ * (pbd_get_level_response then returns them masked); admissible (may be NULL): [nlevels * ncomponents], 1 where the pair remains.  The
+ * mask and its flags hold until responses are produced or handed in again.  pbd_dp_argbest: after pbd_dp_min: the result above, as one
+ * record (head, boxes[max_parts][4], locs[max_parts][3]; boxes / locs may be NULL); without a mask on the frame's responses every
+ * pair counts.  A later pbd_dp_argmin thresholds the root tables again.
+ * Whole-path entry points: pbd_detect_u8 / pbd_detect_dev_u8 / pbd_detect_batch_u8 with a truth set per frame (batch: truth
+ * [nframes][max_parts][4], mix [nframes][max_parts] or NULL, heads[nframes], boxes[nframes][max_parts][4], locs alike,
+ * found[nframes]).  The handle's post steps (candidate filter, per-part scores) run on the single record unchanged; the per-part
+ * scores are the detection's feature vector of detect.m:272-308.                                                                */
+int pbd_latent_mask(pbd_handle* h, const int32_t* truth, const int32_t* mix, int component, double overlap, int32_t* admissible);
+int pbd_dp_argbest(pbd_handle* h, pbd_candidate_head* head, int32_t* boxes, int32_t* locs, int* found);
+int pbd_detect_latent_u8(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride, const int32_t* truth, const int32_t* mix,
+                         int component, double overlap, pbd_candidate_head* head, int32_t* boxes, int32_t* locs, int* found);
+int pbd_detect_latent_dev_u8(pbd_handle* h, const void* d_im, int w, int hgt, int cn, int stride, const int32_t* truth,
+                             const int32_t* mix, int component, double overlap, pbd_candidate_head* head, int32_t* boxes,
+                             int32_t* locs, int* found);
+int pbd_detect_batch_latent_u8(pbd_handle* h, const uint8_t* const* ims, int nframes, int w, int hgt, int cn, int stride,
+                               const int32_t* truth, const int32_t* mix, int component, double overlap, pbd_candidate_head* heads,
+                               int32_t* boxes, int32_t* locs, int* found);
 
 /* ---- instrumentation --------------------------------------------------------
  * GPU time (ms, hipEvent) of the stages of the last synchronous detect:

@@ -53,6 +53,7 @@ EXPORTS = [
     "pbd_set_part_scores", "pbd_get_part_scores", "pbd_candidates_part_scores",
     "pbd_set_boundary_pad", "pbd_get_boundary_pad", "pbd_group_set_boundary_pad",
     "pbd_get_frame_level_image_raw", "pbd_get_frame_level_features", "pbd_get_frame_level_features_f64",
+    "pbd_latent_mask", "pbd_dp_argbest", "pbd_detect_latent_u8", "pbd_detect_latent_dev_u8", "pbd_detect_batch_latent_u8",
 ]
 PBD_ABI_VERSION = 5
 
@@ -666,6 +667,74 @@ class Handle:
         self._chk(self.L.pbd_dp_argmin(self.h, heads.ctypes.data_as(C.c_void_p), _p(boxes, C.c_int32),
                                        _p(locs, C.c_int32), capacity, C.byref(cnt)))
         return self._out(heads, boxes, locs, cnt.value)
+
+    # ---- latent detection (detect(im, model, thresh, bbox, overlap) of matlab/detection/detect.m) -------------------------
+    def _latent_args(self, truth, mix, nframes=1):
+        """truth [nframes, <= max_parts, 4] (x, y, width, height) and mix [nframes, <= max_parts] (-1: free) or None, padded to
+        max_parts rows (zero boxes, free mixtures) -> contiguous int32 arrays"""
+        t = np.asarray(truth, np.int32).reshape(nframes, -1, 4)
+        tr = np.zeros((nframes, self.max_parts, 4), np.int32)
+        tr[:, :t.shape[1]] = t[:, :self.max_parts]
+        mx = None
+        if mix is not None:
+            m = np.asarray(mix, np.int32).reshape(nframes, -1)
+            mx = np.full((nframes, self.max_parts), -1, np.int32)
+            mx[:, :m.shape[1]] = m[:, :self.max_parts]
+        return tr, mx
+
+    def latent_mask(self, truth, overlap, mix=None, component=-1):
+        """pbd_latent_mask: masks the resident response planes; returns admissible [nlevels, ncomponents] (1: the pair remains)"""
+        tr, mx = self._latent_args(truth, mix)
+        adm = np.zeros((self._geo["nlevels"], self.model.ncomponents), np.int32)
+        self._chk(self.L.pbd_latent_mask(self.h, _p(tr, C.c_int32), _p(mx, C.c_int32), int(component), C.c_double(overlap),
+                                         _p(adm, C.c_int32)))
+        return adm
+
+    def dp_argbest(self):
+        """pbd_dp_argbest: (heads, boxes, locs) holding one record, or none"""
+        heads, boxes, locs = self._bufs(1)
+        found = C.c_int(0)
+        self._chk(self.L.pbd_dp_argbest(self.h, heads.ctypes.data_as(C.c_void_p), _p(boxes, C.c_int32), _p(locs, C.c_int32),
+                                        C.byref(found)))
+        return self._out(heads, boxes, locs, found.value)
+
+    def detect_latent(self, im: np.ndarray, truth, overlap, mix=None, component=-1):
+        """pbd_detect_latent_u8: (heads, boxes, locs) holding the best pose whose parts overlap `truth`, or none"""
+        im = np.ascontiguousarray(im, np.uint8)
+        hgt, w = im.shape[:2]
+        cn = 1 if im.ndim == 2 else im.shape[2]
+        tr, mx = self._latent_args(truth, mix)
+        heads, boxes, locs = self._bufs(1)
+        found = C.c_int(0)
+        self._chk(self.L.pbd_detect_latent_u8(self.h, _p(im, C.c_uint8), w, hgt, cn, w * cn, _p(tr, C.c_int32), _p(mx, C.c_int32),
+                                              int(component), C.c_double(overlap), heads.ctypes.data_as(C.c_void_p),
+                                              _p(boxes, C.c_int32), _p(locs, C.c_int32), C.byref(found)))
+        return self._out(heads, boxes, locs, found.value)
+
+    def detect_latent_dev(self, dptr: int, w, hgt, cn, truth, overlap, mix=None, component=-1, stride=None):
+        """pbd_detect_latent_dev_u8: the image already in device memory"""
+        tr, mx = self._latent_args(truth, mix)
+        heads, boxes, locs = self._bufs(1)
+        found = C.c_int(0)
+        self._chk(self.L.pbd_detect_latent_dev_u8(self.h, C.c_void_p(dptr), w, hgt, cn, stride or w * cn, _p(tr, C.c_int32),
+                                                  _p(mx, C.c_int32), int(component), C.c_double(overlap),
+                                                  heads.ctypes.data_as(C.c_void_p), _p(boxes, C.c_int32), _p(locs, C.c_int32),
+                                                  C.byref(found)))
+        return self._out(heads, boxes, locs, found.value)
+
+    def detect_batch_latent(self, frames, truths, overlap, mixes=None, component=-1):
+        """pbd_detect_batch_latent_u8: a truth set (and mixture set) per frame -> list of (heads, boxes, locs), one record or none each"""
+        frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+        if not frames or len(truths) != len(frames) or any(f.shape != frames[0].shape for f in frames):
+            raise ValueError("detect_batch_latent: one truth set per frame, frames of one shape")
+        hgt, w = frames[0].shape[:2]
+        cn = 1 if frames[0].ndim == 2 else frames[0].shape[2]
+        tr, mx = self._latent_args(np.stack([np.asarray(t, np.int32) for t in truths]),
+                                   None if mixes is None else np.stack([np.asarray(m, np.int32) for m in mixes]), len(frames))
+        ptrs = (C.c_void_p * len(frames))(*[f.ctypes.data for f in frames])
+        return self._batch_out(len(frames), 1, lambda hd, bx, lc, cnt: self.L.pbd_detect_batch_latent_u8(
+            self.h, ptrs, len(frames), w, hgt, cn, w * cn, _p(tr, C.c_int32), _p(mx, C.c_int32), int(component),
+            C.c_double(overlap), hd, bx, lc, cnt))
 
     # ---- primitives ----------------------------------------------------------------
     def dt2d(self, a: np.ndarray, ax, bx, ay, by, osx, osy):

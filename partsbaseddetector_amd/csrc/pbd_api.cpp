@@ -183,6 +183,7 @@ static void reset_stages(pbd_handle* h) {
   h->have_pyr = h->have_feat = h->have_resp = h->have_dp = false;
   h->min_ran = false;
   h->feat_ok.clear(); h->resp_ok.clear(); h->ext_set.clear(); h->root_set.clear();   // (sized again by whoever marks a plane next)
+  h->lat_masked = false;
 }
 static void mark_pyramid(pbd_handle* h) {
   h->have_pyr = true;
@@ -196,7 +197,10 @@ static void mark_features(pbd_handle* h, bool split_written) {
   compact_mark_feat(h, true);
   if (h->compact) h->have_dp = h->min_ran = false;
 }
-static void mark_responses(pbd_handle* h) { h->have_resp = true; compact_mark_resp(h, true); }
+static void mark_responses(pbd_handle* h) { h->have_resp = true; compact_mark_resp(h, true); h->lat_masked = false; }
+// latent detection: the resident responses now carry a mask, and d_lat_flags its flags, until responses are produced or handed in again
+// (the planes stay valid responses: pbd_get_level_response returns them masked, min() runs on them)
+static void mark_latent_mask(pbd_handle* h, int component) { h->lat_masked = true; h->lat_component = component; }
 static void mark_min(pbd_handle* h, bool timed) {
   h->dp_timed = timed;
   h->have_dp = h->min_ran = true;
@@ -217,6 +221,7 @@ void free_frame(pbd_handle* h) {
   h->frame_bytes = 0;
   h->d_extx = h->d_exty = nullptr; h->d_ext_base = nullptr; h->ext_ptr = false;
   h->d_cf_mask = nullptr; h->cf_mask_bytes = 0;
+  h->d_lat_jobs = nullptr; h->d_lat_blocks = nullptr; h->d_lat_flags = nullptr; h->d_lat_partial = nullptr; h->n_lat_blocks = 0;
   h->fw = h->fh = h->fcn = 0; h->fdepth = 0; h->fesz = 1;
   reset_stages(h);
   h->feat_split_ok = false;
@@ -409,11 +414,132 @@ static int run_dp_min(pbd_handle* h) {
                 h->opt.max_candidates, h->ts, h->d_foldjobs, h->d_biasw, 0, h->fold_mix, nullptr, nullptr, h->stream);
     nms_and_rescan(h);
   } else
-  launch_root(h->d_rootjobs, h->d_rootblocks, h->n_rootblocks, (double)h->md.thresh, h->d_cand_count, h->d_cand_rec,
+  // (a latent frame takes no hit list from the threshold — detect.m:20 —: k_latent_best writes its one candidate)
+  launch_root(h->d_rootjobs, h->d_rootblocks, h->n_rootblocks, h->lat_frame ? (double)INFINITY : (double)h->md.thresh, h->d_cand_count, h->d_cand_rec,
               h->opt.max_candidates, h->ts, h->d_foldjobs, h->d_biasw, 0, h->fold_mix, nullptr, nullptr, h->stream);
   if (dpt) hipEventRecord(h->ev_dp1, h->stream);
   LAUNCHCHK(h, "DP min");
   mark_min(h, dpt);
+  return PBD_OK;
+}
+
+// ---- latent detection (include/pbd_c.h "latent detection"; k_latent.hip) ------------------------------------------------------
+// The argument checks every latent entry makes, before anything is planned, uploaded or launched
+int pbd_i_latent_check(pbd_handle* h, const int32_t* truth, const int32_t* mix, int nframes, int component, double overlap) {
+  if (!truth) return fail(h, PBD_ERR_ARG, "latent detection: null truth boxes");
+  if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "latent detection: not for a pbd_group member");
+  if (h->nms_sz > 0) return fail(h, PBD_ERR_UNSUPPORTED, "latent detection: not with the score-map NMS (pbd_options.reserved[0] > 0)");
+  if (!(overlap >= 0.0 && overlap < 1.0)) return fail(h, PBD_ERR_ARG, "latent detection: overlap must be in [0, 1)");
+  const int nc = h->md.ncomponents, mp = h->max_parts;
+  if (component < -1 || component >= nc) return fail(h, PBD_ERR_ARG, "latent detection: component out of range (-1: all)");
+  if (nframes < 1 || nframes > PBD_MAX_BATCH) return fail(h, PBD_ERR_ARG, "batch: 1..64 frames");
+  if (nframes > h->opt.max_candidates) return fail(h, PBD_ERR_CAPACITY, "latent detection: one record per frame; raise pbd_options.max_candidates");
+  std::vector<int> owner((size_t)h->md.nfilters, -1);   // the (component, part) slot whose planes a filter id's mask is written into
+  for (int c = 0; c < nc; ++c) {
+    if (component >= 0 && c != component) continue;
+    const int p0 = h->part_offset[c], np = h->part_offset[c + 1] - p0;
+    for (int p = 0; p < np; ++p) {
+      const PartInfo& P = h->parts[p0 + p];
+      bool forced = false;
+      for (int f = 0; f < nframes; ++f) {
+        const int32_t* t = truth + ((size_t)f * mp + p) * 4;
+        if (t[2] < 0 || t[3] < 0) return fail(h, PBD_ERR_ARG, "latent detection: a truth box with negative width or height");
+        if (mix) {
+          const int m = mix[(size_t)f * mp + p];
+          if (m < -1 || m >= P.K) return fail(h, PBD_ERR_ARG, "latent detection: mix outside the part's mixtures (-1: free)");
+          forced = forced || m >= 0;
+        }
+      }
+      for (int k = 0; k < P.K; ++k) {
+        int& o = owner[P.filterid[k]];
+        // the mask is written into the plane in place: a plane two slots share would carry both slots' masks (and a forced mixture
+        // would blank the plane of the one it shares a filter with)
+        if (o >= 0 && (o != p0 + p || forced))
+          return fail(h, PBD_ERR_UNSUPPORTED, "latent detection: a filter id is used by two (component, part) slots of the components searched: the mask is written into the shared response plane in place");
+        o = p0 + p;
+      }
+    }
+  }
+  return PBD_OK;
+}
+
+// The frame plan's share (built on the first latent use of a plan): the work table of k_latent_mask — one job per (level, component,
+// part, mixture) plane, one block per 256 cells —, the flags and k_latent_best's partials
+static int latent_tables(pbd_handle* h) {
+  if (h->d_lat_jobs) return PBD_OK;
+  const int nc = h->md.ncomponents, mp = h->max_parts;
+  std::vector<LatJob> jobs;
+  std::vector<ReduceBlock> blocks;
+  for (int l = 0; l < h->nvl; ++l) {
+    const Level& L = h->lv[l];
+    const size_t HW = (size_t)L.cw * L.ch;
+    if (!L.active || HW == 0) continue;
+    for (int c = 0; c < nc; ++c) {
+      const int p0 = h->part_offset[c], np = h->part_offset[c + 1] - p0;
+      for (int p = 0; p < np; ++p)
+        for (int k = 0; k < h->parts[p0 + p].K; ++k) {
+          const int fid = h->parts[p0 + p].filterid[k];
+          LatJob J{};
+          J.plane = h->d_resp + (L.cell_off * h->md.nfilters + (size_t)fid * HW) * h->ts;
+          J.H = L.ch; J.W = L.cw; J.level = l; J.comp = c; J.part = p; J.mix = k;
+          J.rows = h->mixed ? h->fkh[fid] : h->md.kh;
+          J.flag = (l * nc + c) * mp + p;
+          J.scale = L.scale;
+          for (size_t c0 = 0; c0 < HW; c0 += 256) blocks.push_back(ReduceBlock{(int)jobs.size(), (unsigned)c0});
+          jobs.push_back(J);
+        }
+    }
+  }
+  int rc;
+  if ((rc = dev_upload(h, &h->d_lat_jobs, jobs)) || (rc = dev_upload(h, &h->d_lat_blocks, blocks)) ||
+      (rc = dev_alloc(h, &h->d_lat_flags, (size_t)h->nvl * nc * mp)) || (rc = dev_alloc(h, &h->d_lat_partial, (size_t)std::max(h->n_rootblocks, 1))))
+    return rc;
+  h->n_lat_blocks = (int)blocks.size();
+  return PBD_OK;
+}
+
+// On a planned frame: the tables above, and the truth / mixture tables of the frame (or of every frame of the batch), small device
+// arrays uploaded in the handle's stream from a pinned staging copy (the caller's arrays may go away once the entry returns)
+int pbd_i_latent_begin(pbd_handle* h, const LatentSource& s, int nframes) {
+  int rc = latent_tables(h);
+  if (rc) return rc;
+  const int mp = h->max_parts;
+  const size_t cap = (size_t)PBD_MAX_BATCH * mp * 5;
+  if (!h->d_lat_truth && ((rc = model_alloc(h, &h->d_lat_truth, cap)) || (rc = model_alloc(h, &h->h_lat_truth, cap, true, false)))) return rc;
+  const size_t nt = (size_t)nframes * mp * 4, nm = (size_t)nframes * mp;
+  memcpy(h->h_lat_truth, s.truth, nt * sizeof(int));
+  if (s.mix) memcpy(h->h_lat_truth + nt, s.mix, nm * sizeof(int));
+  HIPCHK(h, hipMemcpyAsync(h->d_lat_truth, h->h_lat_truth, (nt + (s.mix ? nm : 0)) * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  h->lat_has_mix = s.mix != nullptr;
+  h->lat_component = s.component; h->lat_overlap = s.overlap;
+  return PBD_OK;
+}
+
+// between pdf() and min(): the mask of the resident response planes, the flags of every (level, component, part)
+static int run_latent_mask(pbd_handle* h, int nframes) {
+  const int nc = h->md.ncomponents, mp = h->max_parts;
+  hipMemsetAsync(h->d_lat_flags, 0, (size_t)h->nvl * nc * mp * sizeof(int), h->stream);
+  LatentMaskArgs a{};
+  a.jobs = h->d_lat_jobs; a.blocks = h->d_lat_blocks;
+  a.truth = h->d_lat_truth; a.mix = h->lat_has_mix ? h->d_lat_truth + (size_t)nframes * mp * 4 : nullptr;
+  a.flags = h->d_lat_flags;
+  a.nlevels = h->nlevels; a.mp = mp; a.component = h->lat_component; a.org = 1 + h->pad;
+  a.overlap = h->lat_overlap;
+  launch_latent_mask(a, h->n_lat_blocks, h->ts, h->stream);
+  LAUNCHCHK(h, "latent mask");
+  mark_latent_mask(h, h->lat_component);
+  return PBD_OK;
+}
+// behind min(): the best root of every frame over its admissible pairs, as the candidate list k_backtrack walks
+static int run_latent_best(pbd_handle* h) {
+  LatentBestArgs a{};
+  a.jobs = h->d_rootjobs; a.blocks = h->d_rootblocks; a.nblocks = h->n_rootblocks;
+  a.flags = h->d_lat_flags; a.nparts = h->d_nparts;
+  a.ncomp = h->md.ncomponents; a.mp = h->max_parts; a.nlevels = h->nlevels; a.nframes = h->batch;
+  a.partial = h->d_lat_partial;
+  a.count = h->d_cand_count; a.rec = h->d_cand_rec;
+  launch_latent_best(a, h->ts, h->stream);
+  LAUNCHCHK(h, "latent best");
   return PBD_OK;
 }
 
@@ -472,10 +598,13 @@ static int enqueue_stages(pbd_handle* h, const uint8_t* d_src, int stride) {
   if ((rc = run_hog(h))) return rc;
   if (prof) hipEventRecord(h->ev[2], h->stream);
   if ((rc = run_pdf(h))) return rc;
+  if (h->lat_frame && (rc = run_latent_mask(h, h->batch))) return rc;   // (a latent frame's stage times: the mask in pdf's, the best root in min()'s)
   if (prof) hipEventRecord(h->ev[3], h->stream);
   if ((rc = run_dp_min(h))) return rc;
+  if (h->lat_frame && (rc = run_latent_best(h))) return rc;
   if (prof) hipEventRecord(h->ev[4], h->stream);
   if ((rc = run_argmin_enqueue(h, true))) return rc;
+  if (h->lat_frame) h->root_dirty = true;   // the hit list is the latent record: a later pbd_dp_argmin thresholds the root tables again
   if (prof) hipEventRecord(h->ev[5], h->stream);
   if (h->ps_frame && (rc = pbd_i_run_part_scores(h))) return rc;
   if (h->b3_frame && (rc = pbd_i_run_box3d(h))) return rc;
@@ -493,7 +622,8 @@ int enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride) {
   int rc = pbd_i_post_buffers(h);
   if (rc) return rc;
   // depth-carrying frames run eagerly: the depth pointers are per frame; a captured graph stays for plain frames
-  if (h->zf_frame) return enqueue_stages(h, d_src, stride);
+  // latent frames too: the mask stage and the best-root reduction are theirs alone, the captured graph stays the plain frames'
+  if (h->zf_frame || h->lat_frame) return enqueue_stages(h, d_src, stride);
   if (!graphable || h->frames_on_plan == 0) {
     h->frames_on_plan++;
     return enqueue_stages(h, d_src, stride);
@@ -837,6 +967,7 @@ static int set_level_response_(pbd_handle* h, int level, int filter, const void*
     if (h->resp_ok.size() != (size_t)h->nvl * h->md.nfilters) compact_mark_resp(h, false);
     h->resp_ok[(size_t)level * h->md.nfilters + filter] = 1;
     h->have_resp = all_active_set(h, h->resp_ok, h->md.nfilters);
+    h->lat_masked = false;
   } else {
     mark_responses(h);
   }
@@ -1023,8 +1154,8 @@ int pbd_get_stage_state(const pbd_handle* h, int32_t state[4]) {
   return PBD_OK;
 }
 
-int pbd_dp_argmin(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* count) {
-  if (!h) return PBD_ERR_ARG;
+// what back-tracking needs of the frame's tables (pbd_dp_argmin, pbd_dp_argbest)
+static int argmin_ready(pbd_handle* h) {
   if (!h->have_dp) return fail(h, PBD_ERR_STATE, "argmin() before min()");
   if (h->batch > 1) return fail(h, PBD_ERR_STATE, "the current plan is a batch of frames: its candidates come from pbd_detect_batch_collect");
   if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
@@ -1034,11 +1165,63 @@ int pbd_dp_argmin(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int3
     if (!all_active_set(h, h->root_set, h->md.ncomponents))
       return fail(h, PBD_ERR_STATE, "argmin(): no min() on this frame and not every root table has been handed in (pbd_set_root)");
   }
+  return PBD_OK;
+}
+
+int pbd_dp_argmin(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* count) {
+  if (!h) return PBD_ERR_ARG;
+  int ready = argmin_ready(h);
+  if (ready) return ready;
   ON_DEVICE(h);
   h->ps_frame = h->ps_ready = false;   // (the stage entry point scores nothing: pbd_candidates_part_scores does, on its records)
   int rc = run_argmin_enqueue(h);
   if (rc) { h->pending = false; return rc; }
   return collect_frame(h, heads, boxes, locs, capacity, count);
+}
+
+// ---- latent detection: the two stage entry points ----------------------------------------------------------------------------
+int pbd_latent_mask(pbd_handle* h, const int32_t* truth, const int32_t* mix, int component, double overlap, int32_t* admissible) {
+  if (!h) return PBD_ERR_ARG;
+  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  int rc = pbd_i_latent_check(h, truth, mix, 1, component, overlap);
+  if (rc) return rc;
+  if (h->fw == 0) return fail(h, PBD_ERR_STATE, "no frame geometry");
+  if (h->batch > 1) return fail(h, PBD_ERR_STATE, "the current plan is a batch of frames (pbd_detect_batch_*): the stage entry points address single-frame plans");
+  if (!h->have_resp) return fail(h, PBD_ERR_STATE, h->compact ? "latent mask: responses are not resident (compact memory plan: min() transforms them in place — run pdf() or hand in every plane again)" : "latent mask before pdf()");
+  ON_DEVICE(h);
+  const LatentSource s{truth, mix, component, overlap};
+  if ((rc = pbd_i_latent_begin(h, s, 1)) || (rc = run_latent_mask(h, 1))) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (admissible) {   // a pair counts when every part of the component has an admissible cell at the level
+    const int nc = h->md.ncomponents, mp = h->max_parts;
+    std::vector<int> fl((size_t)h->nvl * nc * mp);
+    HIPCHK(h, hipMemcpy(fl.data(), h->d_lat_flags, fl.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int l = 0; l < h->nlevels; ++l)
+      for (int c = 0; c < nc; ++c) {
+        int ok = 1;
+        for (int p = 0; p < h->part_offset[c + 1] - h->part_offset[c]; ++p) ok = ok && fl[((size_t)l * nc + c) * mp + p] != 0;
+        admissible[(size_t)l * nc + c] = ok;
+      }
+  }
+  return PBD_OK;
+}
+int pbd_dp_argbest(pbd_handle* h, pbd_candidate_head* head, int32_t* boxes, int32_t* locs, int* found) {
+  if (!h) return PBD_ERR_ARG;
+  int rc = argmin_ready(h);
+  if (rc) return rc;
+  if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "latent detection: not for a pbd_group member");
+  if (h->nms_sz > 0) return fail(h, PBD_ERR_UNSUPPORTED, "latent detection: not with the score-map NMS (pbd_options.reserved[0] > 0)");
+  ON_DEVICE(h);
+  if ((rc = latent_tables(h))) return rc;
+  if (!h->lat_masked)   // no mask on this frame's responses: every pair counts (the unconstrained best pose)
+    HIPCHK(h, hipMemsetAsync(h->d_lat_flags, 1, (size_t)h->nvl * h->md.ncomponents * h->max_parts * sizeof(int), h->stream));
+  h->ps_frame = h->ps_ready = false;
+  if ((rc = run_latent_best(h))) return rc;
+  h->root_dirty = false;                      // the record is the best root of the tables now on the device, whoever wrote them
+  rc = run_argmin_enqueue(h);
+  h->root_dirty = true;                       // ... and a later pbd_dp_argmin thresholds them again
+  if (rc) { h->pending = false; return rc; }
+  return collect_frame(h, head, boxes, locs, 1, found);
 }
 
 // ---- stand-alone primitives -------------------------------------------------

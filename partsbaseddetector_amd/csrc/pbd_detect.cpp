@@ -36,6 +36,13 @@ int enter_frame(pbd_handle* h, const FrameSource& s, bool detect) {
   if (!detect) return PBD_OK;
   const uint8_t* d_src = s.on_device ? (const uint8_t*)s.one : h->d_img;
   const int stride = s.on_device ? s.stride : (int)row;
+  if (s.lat) {   // latent frames: the truth tables in front of the kernels like the image; the flag lives only across the enqueue
+    if ((rc = pbd_i_latent_begin(h, *s.lat, s.nframes))) return rc;
+    h->lat_frame = true;
+    rc = enqueue_all(h, d_src, stride);
+    h->lat_frame = false;
+    return rc;
+  }
   if (!s.z) return enqueue_all(h, d_src, stride);
   const DepthSource& z = *s.z;
   h->zf_img = (const char*)z.p; h->zf_pitch = (size_t)z.stride;
@@ -269,6 +276,36 @@ int pbd_detect_batch_rgbd_u8(pbd_handle* h, const uint8_t* const* ims, const voi
   const DepthSource z = depth_images(true, h->d_zimg, depth_type, (long long)zrow, fb, has);   // (enter_frame repeats the depth and pending checks: they passed above and cannot refuse now)
   if ((rc = enter_frame(h, host_batch(ims, nframes, w, hgt, cn, stride, &z)))) return rc;
   return pbd_detect_batch_collect(h, heads, boxes, locs, capacity, counts);
+}
+
+// ---- latent detection: detect(im, model, thresh, bbox, overlap) of matlab/detection/detect.m ------------------------------------
+// The plain entries with a truth set per frame: one record (or none) per frame.  Arguments are checked before anything is planned.
+static int latent_enter(pbd_handle* h, FrameSource s, const int32_t* truth, const int32_t* mix, int component, double overlap) {
+  if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
+  int rc = pbd_i_latent_check(h, truth, mix, s.nframes, component, overlap);
+  if (rc) return rc;
+  const LatentSource ls{truth, mix, component, overlap};
+  s.lat = &ls;
+  return enter_frame(h, s);
+}
+int pbd_detect_latent_u8(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride, const int32_t* truth, const int32_t* mix,
+                         int component, double overlap, pbd_candidate_head* head, int32_t* boxes, int32_t* locs, int* found) {
+  if (!h || !im) return PBD_ERR_ARG;
+  int rc = latent_enter(h, host_frame(im, w, hgt, cn, stride, PBD_DEPTH_8U), truth, mix, component, overlap);
+  return rc ? rc : pbd_detect_collect(h, head, boxes, locs, 1, found);
+}
+int pbd_detect_latent_dev_u8(pbd_handle* h, const void* d_im, int w, int hgt, int cn, int stride, const int32_t* truth, const int32_t* mix,
+                             int component, double overlap, pbd_candidate_head* head, int32_t* boxes, int32_t* locs, int* found) {
+  if (!h || !d_im) return PBD_ERR_ARG;
+  int rc = latent_enter(h, device_frames(d_im, 1, w, hgt, cn, stride), truth, mix, component, overlap);
+  return rc ? rc : pbd_detect_collect(h, head, boxes, locs, 1, found);
+}
+int pbd_detect_batch_latent_u8(pbd_handle* h, const uint8_t* const* ims, int nframes, int w, int hgt, int cn, int stride,
+                               const int32_t* truth, const int32_t* mix, int component, double overlap, pbd_candidate_head* heads,
+                               int32_t* boxes, int32_t* locs, int* found) {
+  if (!h || !ims || !heads || !found || nframes < 1) return PBD_ERR_ARG;
+  int rc = latent_enter(h, host_batch(ims, nframes, w, hgt, cn, stride), truth, mix, component, overlap);
+  return rc ? rc : pbd_detect_batch_collect(h, heads, boxes, locs, 1, found);
 }
 
 // ---- the planner's one measured rule, re-measured on the caller's own frames ---------------------------------

@@ -35,6 +35,34 @@
 
 struct CandRec { int level, comp, y, x; };
 
+// ---- latent detection (k_latent.hip; include/pbd_c.h "latent detection") ------------------------------------------------------
+// One response plane of the mask stage: mixture `mix` of part `part` (local index) of component `comp` at (virtual) level `level`.
+struct LatJob {
+  void* plane;                   // T [H][W]: the resident response plane, masked in place
+  int H, W, level, comp, part, mix;
+  int rows;                      // rows of the mixture's filter: the window is rows x rows scaled (k_backtrack's size quirk)
+  int flag;                      // index of the (level, component, part) "has an admissible cell" flag
+  float scale; int pad;
+};
+static_assert(sizeof(LatJob) == 48, "LatJob layout");
+struct LatPartial { double v; unsigned long long key; };   // a block's best root: score, (level * ncomp + comp) << 32 | cell; key ~0: none
+struct LatentMaskArgs {
+  const LatJob* jobs; const struct ReduceBlock* blocks;
+  const int* truth; const int* mix;   // [frames][max_parts][4]; [frames][max_parts] or null
+  int* flags;
+  int nlevels, mp, component, org;    // nlevels: levels of ONE frame; org = 1 + boundary pad
+  double overlap;
+};
+struct LatentBestArgs {
+  const struct RootJob* jobs; const struct ReduceBlock* blocks; int nblocks;
+  const int* flags; const int* nparts;
+  int ncomp, mp, nlevels, nframes;
+  LatPartial* partial;                // [nblocks]
+  int* count; CandRec* rec;           // what k_backtrack consumes: one record per frame that has a pose
+};
+// one latent frame or batch: a truth set (and mixture set) per frame
+struct LatentSource { const int32_t* truth; const int32_t* mix; int component; double overlap; };
+
 // ---- what every post-stage kernel reads (k_cand / k_zfilter / k_box3d / k_cluster3d / k_partscore) ------------------------
 // A record is a pbd_candidate_head, then mp * 4 box ints, then mp * 3 loc ints (pbd_rec_bytes).
 // The records of a frame or a batch: `count` (device) records at p (count > capacity: the back-tracking overflowed).
@@ -230,6 +258,15 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   double* h_ps = nullptr;           // [capacity * mp * 3]: pinned
   bool ps_ready = false;            // results of the last collected frame, per frame in the order returned
   std::vector<std::vector<double>> ps_res; std::vector<char> ps_res_on;
+  // latent detection (pbd_latent_mask / pbd_dp_argbest / pbd_detect_latent_*): k_latent.hip between pdf and min, and in front of the
+  // back-tracking.  The work table, the flags and the block partials belong to the frame plan (built on the first latent use of a
+  // plan); the truth / mixture tables are model-lifetime buffers, uploaded per frame in the frame's stream.
+  bool lat_frame = false;           // the frame being enqueued is a latent one (set by enter_frame around enqueue_all)
+  bool lat_masked = false;          // the resident responses carry a mask and d_lat_flags its flags (until responses are produced again)
+  int lat_component = -1; double lat_overlap = 0.0; bool lat_has_mix = false;
+  LatJob* d_lat_jobs = nullptr; ReduceBlock* d_lat_blocks = nullptr; int n_lat_blocks = 0;
+  int* d_lat_flags = nullptr; LatPartial* d_lat_partial = nullptr;
+  int* d_lat_truth = nullptr; int* h_lat_truth = nullptr;   // [PBD_MAX_BATCH][max_parts][5]: 4 box ints per part of every frame, then the mixtures; h_: pinned
 };
 #define PBD_MAX_BATCH 64
 
@@ -349,6 +386,7 @@ struct FrameSource {
   const uint8_t* const* each;     // or (host batches) a pointer per frame
   int nframes, w, hgt, cn, stride, depth;   // stride: bytes between rows; depth: PBD_DEPTH_* of the pixels
   const DepthSource* z;           // RGB-D: the frame runs with the depth-carrying post-stages; else null
+  const LatentSource* lat;        // latent detection: the frame is masked by these boxes and yields its best pose; else null
 };
 // the three shapes of a source, by name (z: see above)
 inline FrameSource host_frame(const void* im, int w, int hgt, int cn, int stride, int depth, const DepthSource* z = nullptr) {
@@ -378,6 +416,10 @@ int pbd_i_finish_frame(pbd_handle* h, int found);
 int pbd_i_emit(pbd_handle* h, const std::vector<const char*>& recs, pbd_candidate_head* heads, int32_t* boxes,
                int32_t* locs, int capacity, bool ordered = false,    // ordered: the records are in final order already (k_cand_filter)
                std::vector<int>* order_out = nullptr);               // order_out: the record emitted i-th is recs[order[i]]
+// latent detection (pbd_api.cpp): the argument checks of every latent entry (nframes truth sets), and — on a planned frame — the work
+// table + the upload of the truth / mixture tables in the handle's stream
+int pbd_i_latent_check(pbd_handle* h, const int32_t* truth, const int32_t* mix, int nframes, int component, double overlap);
+int pbd_i_latent_begin(pbd_handle* h, const LatentSource& s, int nframes);
 int pbd_i_found(const pbd_handle* h);   // records the pending frame left on the host side (filtered: the kept count)
 #define PBD_FIRST_COPY 192   // candidate records fetched (or gathered) together with the count
 
@@ -477,6 +519,9 @@ void launch_backtrack(const int* count, const CandRec* rec, int capacity, const 
                       char* out, size_t out_stride, int ts, const int* flat, const int* depth, int max_depth, int nflat,
                       const unsigned long long* scr_base, const int16_t* ix, const int16_t* iy, int correct_ptr,
                       const int16_t* extx, const int16_t* exty, const unsigned long long* ext_base, int* count_out, int pad, hipStream_t s);   // pad: the boundary padding (box origin)
+// latent detection (k_latent.hip): the overlap mask of every response plane; the best root over the admissible (level, component) pairs
+void launch_latent_mask(const LatentMaskArgs& a, int nblocks, int ts, hipStream_t s);
+void launch_latent_best(const LatentBestArgs& a, int ts, hipStream_t s);
 void dt_debug_read(unsigned long long* out);
 void dt_debug_counters(unsigned long long* out);   // probe build: k_dt_pass path counters, read and reset (zeros elsewhere)
 int dt_debug_trace(unsigned long long* t, unsigned* hw, int* nlaunch);   // probe build only

@@ -228,6 +228,15 @@ class DynamicProgram:
                             h.set_dp_pointers(l, c, p, pm, Ix[l][c][p][pm], Iy[l][c][p][pm], Ik[l][c][p][pm])
         return Candidate._unpack(*h.dp_argmin(capacity))
 
+    def latentMask(self, truth, overlap: float, mix=None, component: int = -1) -> np.ndarray:
+        """Between pdf() and min(): the response planes resident on the device masked by one box per part (capi.Handle.latent_mask);
+        returns admissible [level][component]."""
+        return self._h.latent_mask(truth, overlap, mix, component)
+
+    def argbest(self) -> List[Candidate]:
+        """After min(): the best root over the remaining (level, component) pairs, back-tracked like argmin; one Candidate or none."""
+        return Candidate._unpack(*self._h.dp_argbest())
+
 
 class PartsBasedDetector:
     """PartsBasedDetector<T> (include/PartsBasedDetector.hpp:152-175); dtype = np.float32 (src/demo.cpp:85)
@@ -397,3 +406,10 @@ class PartsBasedDetector:
         res = self.handle.detect(im, self._cap) if np.asarray(im).dtype == np.uint8 else self.handle.detect_image(im, self._cap)
         out.extend(Candidate._unpack(*res, self._ps()))
         return out
+
+    def detect_latent(self, im: np.ndarray, truth, overlap: float, mix=None, component: int = -1) -> List[Candidate]:
+        """detect(im, model, thresh, bbox, overlap) of matlab/detection/detect.m: the single highest-scoring pose whose every part
+        overlaps its box in `truth` ([nparts, 4] rows of x, y, width, height as detect() returns them) by more than `overlap`
+        (in [0, 1)); mix[p] >= 0 fixes part p's mixture (-1 / None: free); component = -1 searches all.  Returns one Candidate or
+        an empty list; the model's threshold plays no part.  With setPartScores on, the Candidate carries its parts' scores."""
+        return Candidate._unpack(*self.handle.detect_latent(im, truth, overlap, mix, component), self._ps())

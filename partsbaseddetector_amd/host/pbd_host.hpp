@@ -725,6 +725,28 @@ class PartsBasedDetector {
     append_candidates(candidates, heads, boxes, locs, n, mp);
     attach_part_scores(candidates, n, mp);
   }
+  // detect(im, model, thresh, bbox, overlap) of matlab/detection/detect.m:18-23: the single highest-scoring pose whose every part
+  // overlaps its box in `truth` (one cv::Rect per part, in the convention detect() returns: x .. x + width) by more than `overlap`
+  // (in [0, 1)), appended to `candidates`; nothing is appended when no pose qualifies.  mix: empty = every mixture free, else per part
+  // -1 = free or the mixture the part must take; component -1: all.  The model's threshold plays no part.  8-bit frames.
+  void detectLatent(const Mat& im, const std::vector<Rect>& truth, double overlap, vectorCandidate& candidates,
+                    const std::vector<int>& mix = std::vector<int>(), int component = -1) {
+    if (!dev_) throw Exception(PBD_ERR_STATE, "detectLatent() before distributeModel()");
+    if (im.depth() != PBD_8U) throw Exception(PBD_ERR_UNSUPPORTED, "latent detection: 8-bit colour frames only");
+    const int mp = pbd_max_parts(dev_->h);
+    std::vector<int32_t> tr((size_t)mp * 4, 0), mx((size_t)mp, -1);
+    for (size_t p = 0; p < truth.size() && p < (size_t)mp; ++p) {
+      tr[p * 4] = truth[p].x; tr[p * 4 + 1] = truth[p].y; tr[p * 4 + 2] = truth[p].width; tr[p * 4 + 3] = truth[p].height;
+    }
+    for (size_t p = 0; p < mix.size() && p < (size_t)mp; ++p) mx[p] = mix[p];
+    std::vector<pbd_candidate_head> heads(1);
+    std::vector<int32_t> boxes((size_t)mp * 4), locs((size_t)mp * 3);
+    int n = 0;
+    dev_->check(pbd_detect_latent_u8(dev_->h, im.ptr<uint8_t>(), im.cols, im.rows, im.channels(), (int)im.step(), tr.data(),
+                                     mix.empty() ? nullptr : mx.data(), component, overlap, heads.data(), boxes.data(), locs.data(), &n));
+    append_candidates(candidates, heads, boxes, locs, n, mp);
+    attach_part_scores(candidates, n, mp);
+  }
 };
 
 inline void Candidate::sort(std::vector<Candidate>& c) {
