@@ -348,6 +348,10 @@ int pbd_dp_min(pbd_handle* h);
 /* Ix/Iy/Ik[level][component][part][parent mixture] as int32 cell_h*cell_w     */
 int pbd_get_dp_pointers(pbd_handle* h, int level, int component, int part, int parent_mix,
                         int32_t* ix, int32_t* iy, int32_t* ik);
+/* Read-only: the same tables of ONE frame of the current plan, 0 <= frame < frames of the plan — also for a batch plan
+ * (pbd_detect_batch_*), like pbd_get_frame_level_features; on a single-frame plan frame is 0 and it equals pbd_get_dp_pointers. */
+int pbd_get_frame_dp_pointers(pbd_handle* h, int frame, int level, int component, int part, int parent_mix,
+                              int32_t* ix, int32_t* iy, int32_t* ik);
 int pbd_get_root(pbd_handle* h, int level, int component, float* rootv, int32_t* rooti);
 int pbd_get_root_f64(pbd_handle* h, int level, int component, double* rootv, int32_t* rooti);
 /* DynamicProgram<T>::argmin takes rootv / rooti / Ix / Iy / Ik as arguments (include/DynamicProgram.hpp:75).  A caller

@@ -53,6 +53,7 @@ EXPORTS = [
     "pbd_set_part_scores", "pbd_get_part_scores", "pbd_candidates_part_scores",
     "pbd_set_boundary_pad", "pbd_get_boundary_pad", "pbd_group_set_boundary_pad",
     "pbd_get_frame_level_image_raw", "pbd_get_frame_level_features", "pbd_get_frame_level_features_f64",
+    "pbd_get_frame_dp_pointers",
     "pbd_latent_mask", "pbd_dp_argbest", "pbd_detect_latent_u8", "pbd_detect_latent_dev_u8", "pbd_detect_batch_latent_u8",
 ]
 PBD_ABI_VERSION = 5
@@ -637,6 +638,15 @@ class Handle:
         ix, iy, ik = (np.zeros(sh, np.int32) for _ in range(3))
         self._chk(self.L.pbd_get_dp_pointers(self.h, l, c, p, m, _p(ix, C.c_int32), _p(iy, C.c_int32),
                                              _p(ik, C.c_int32)))
+        return ix, iy, ik
+
+    def frame_dp_pointers(self, frame, l, c, p, m, w, hgt):
+        """pbd_get_frame_dp_pointers: (Ix, Iy, Ik) of one frame of the current plan — a batch plan included — of w x hgt frames"""
+        g = self.geometry(w, hgt)
+        sh = (g["cell_h"][l], g["cell_w"][l])
+        ix, iy, ik = (np.zeros(sh, np.int32) for _ in range(3))
+        self._chk(self.L.pbd_get_frame_dp_pointers(self.h, int(frame), int(l), c, p, m, _p(ix, C.c_int32), _p(iy, C.c_int32),
+                                                   _p(ik, C.c_int32)))
         return ix, iy, ik
 
     def root(self, l, c):

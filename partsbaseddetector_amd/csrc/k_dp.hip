@@ -15,6 +15,9 @@
 //             input) and the result is written TRANSPOSED (element q of line i at
 //             q*nlines+i), so the x pass (rows) feeds the y pass (columns)
 //             line-contiguously and the y pass lands in row-major layout again.
+//             The pointers (the element each output took its value from) go out in
+//             the same transposed layout in both passes: the x pass's plane is stored
+//             [column][row], the y pass's [row][column].
 // k_reduce    Math::reduceMax over the child mixtures for every parent mixture (Ik;
 //             Ix / Iy are composed from the DT's own pointer planes at back-tracking
 //             time, DistanceTransform.hpp:233-244) and the in-order accumulation
@@ -198,7 +201,7 @@ __device__ __forceinline__ void fold_children(const FoldJob* __restrict__ J, con
 // SEGMENT of it concurrently and the segments are stitched into the sequential result (dt_core.hpp):
 // lane = p * lpb + line.
 // FOLD: the block's lines are nrows consecutive rows x the K mixtures of one part (line = mixture * nrows + row, so
-// that neighbouring lanes write neighbouring rows of one transposed plane) and the loader builds them from the part's
+// that neighbouring lanes write neighbouring rows of one transposed plane — scores and pointers alike) and the loader builds them from the part's
 // raw responses and its children's messages (fold_children).
 template <typename T, typename IT, int FM>   // FM: 0 = plain lines, else fold with at most FM mixtures per part
 __device__ __forceinline__ void dt_block(char* smem, const DtTask& t, const DtGroup& g, const DtMap* __restrict__ maps,
@@ -477,19 +480,14 @@ __device__ __forceinline__ void dt_block(char* smem, const DtTask& t, const DtGr
   // ---- read out (:172-178) ----
   // Output q of a line depends only on the finished stack, so the 64/lpb lanes of a line each take a sub-range of
   // the outputs, all sub-ranges stepping q in lockstep — downwards, along the "below" links: scores go out
-  // transposed (lanes of one sub-range = consecutive lines -> coalesced); pointers go straight to their plane:
-  // transposed like the scores in the y pass, natural (2-byte runs per lane, merged in L2) in the x pass — no
+  // transposed (lanes of one sub-range = consecutive lines -> coalesced); pointers go straight to their plane in the
+  // same layout, in both passes: element (line li, output q) at ptr[q * nlines + li] — one contiguous run per store
+  // instruction, never one 2-byte write per lane.  The x pass's plane is therefore [column][row] with the level's row
+  // count as its pitch (k_backtrack and pbd_get_dp_pointers read it so); the y pass's comes out as [row][column].  No
   // LDS staging, that space holds more lines.
   if (mine) {
     const double a = mp.a, b = mp.b;
-    // pointers: transposed like dst (y pass -> natural layout) or natural (x pass)
-#ifdef PBD_NAT_FROM_MAP   // (A/B builds: the form before round 6's session 31)
-    const bool nat = mp.ptr_natural != 0;
-#else
-    const bool nat = (g.fused & DT_G_NATURAL) != 0;   // (= mp.ptr_natural, uniform over a group: DtGroup::fused)
-#endif
-    int16_t* pp = mp.ptr + (nat ? (size_t)li * len : (size_t)li);
-    const int pst = nat ? 1 : g.nlines;
+    int16_t* pp = mp.ptr + li;
     const int chunk = g.chunk;                   // ceil(len / nsub)
     const int q0 = p * chunk, q1 = min(len, q0 + chunk);
     if (q0 < q1) {
@@ -511,7 +509,7 @@ __device__ __forceinline__ void dt_block(char* smem, const DtTask& t, const DtGr
       int nnx = (int)Bl[nx];
       const int nlines = g.nlines;
       GPW(T) dp = (GPW(T))mp.dst + li + (size_t)(q1 - 1) * nlines;      // running output pointers: no 64-bit multiply per element
-      GPW(int16_t) ppq = (GPW(int16_t))pp + (size_t)(q1 - 1) * pst;
+      GPW(int16_t) ppq = (GPW(int16_t))pp + (size_t)(q1 - 1) * nlines;
       const int os_end = mp.os + q0;           // the sub-range's first output (the loop counts the shifted position down to it)
       ++os;
       auto outputs = [&](auto fused) {         // fused: a * d^2 and b * d are exact (|d| < 2^14, float-born weights): their sum is one fma
@@ -524,7 +522,7 @@ __device__ __forceinline__ void dt_block(char* smem, const DtTask& t, const DtGr
           const double ad2 = a * (d * d);
           *dp = (T)((FZ ? fma(b, d, ad2) : (ad2 + b * d)) + (double)eyz.x);
           *ppq = (int16_t)e;
-          dp -= nlines; ppq -= pst;
+          dp -= nlines; ppq -= nlines;
         } while (os > os_end);
       };
       if constexpr (!EX) { if (fz) outputs(std::true_type{}); else outputs(std::false_type{}); }
@@ -861,8 +859,9 @@ __global__ __launch_bounds__(64) void k_backtrack(const int* __restrict__ count,
         x = extx[eo]; y = exty[eo];
       } else {
         const size_t so = (size_t)scr_base[(size_t)r.level * nflat + flat[r.comp * max_parts + p]] + (size_t)mm * HW;
-        if (!correct_ptr) { x = ixs[so + off]; y = iys[so + (size_t)py * B.W + x]; }
-        else { y = iys[so + off]; x = ixs[so + (size_t)y * B.W + px]; }
+        // the x pass's plane is stored transposed, [column][row] with pitch H (k_dt_pass's read-out); the y pass's is [row][column]
+        if (!correct_ptr) { x = ixs[so + (size_t)px * B.H + py]; y = iys[so + (size_t)py * B.W + x]; }
+        else { y = iys[so + off]; x = ixs[so + (size_t)px * B.H + y]; }
       }
       lx[p] = x; ly[p] = y; lm[p] = mm;
     }

@@ -986,8 +986,8 @@ int pbd_dp_min(pbd_handle* h) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return PBD_OK;
 }
-int pbd_get_dp_pointers(pbd_handle* h, int level, int component, int part, int parent_mix, int32_t* ix, int32_t* iy, int32_t* ik) {
-  CHECK_LEVEL(h, level);
+// level: a level of the plan (a batch plan's frame f, level l: f * nlevels + l), checked by the callers
+static int get_dp_pointers_(pbd_handle* h, int level, int component, int part, int parent_mix, int32_t* ix, int32_t* iy, int32_t* ik) {
   if (!h->have_dp) return fail(h, PBD_ERR_STATE, "min() not run");
   if (component < 0 || component >= h->md.ncomponents) return fail(h, PBD_ERR_ARG, "component out of range");
   const int p0 = h->part_offset[component], cnp = h->part_offset[component + 1] - p0;
@@ -1009,18 +1009,27 @@ int pbd_get_dp_pointers(pbd_handle* h, int level, int component, int part, int p
   HIPCHK(h, hipMemcpy(c.data(), h->d_pk + po, HW, hipMemcpyDeviceToHost));
   HIPCHK(h, hipMemcpy(X.data(), h->d_dt_ixT + so, X.size() * 2, hipMemcpyDeviceToHost));
   HIPCHK(h, hipMemcpy(Y.data(), h->d_dt_iy + so, Y.size() * 2, hipMemcpyDeviceToHost));
-  const int W = L.cw;
+  const int W = L.cw, H = L.ch;   // X: the x pass's planes, stored transposed ([column][row], pitch H); Y: [row][column]
   for (size_t i = 0; i < HW; ++i) {
     const size_t mo = (size_t)c[i] * HW;
     const int m_ = (int)(i / W), n_ = (int)(i - (size_t)m_ * W);
     int x, y;
-    if (!h->opt.dt_correct_ptr) { x = X[mo + i]; y = Y[mo + (size_t)m_ * W + x]; }
-    else { y = Y[mo + i]; x = X[mo + (size_t)y * W + n_]; }
+    if (!h->opt.dt_correct_ptr) { x = X[mo + (size_t)n_ * H + m_]; y = Y[mo + (size_t)m_ * W + x]; }
+    else { y = Y[mo + i]; x = X[mo + (size_t)n_ * H + y]; }
     if (ix) ix[i] = x;
     if (iy) iy[i] = y;
     if (ik) ik[i] = c[i];
   }
   return PBD_OK;
+}
+int pbd_get_dp_pointers(pbd_handle* h, int level, int component, int part, int parent_mix, int32_t* ix, int32_t* iy, int32_t* ik) {
+  CHECK_LEVEL(h, level);
+  return get_dp_pointers_(h, level, component, part, parent_mix, ix, iy, ik);
+}
+// Read-only, batch plans included (like pbd_get_frame_level_features): the tables the batched launches wrote for frame `frame`
+int pbd_get_frame_dp_pointers(pbd_handle* h, int frame, int level, int component, int part, int parent_mix, int32_t* ix, int32_t* iy, int32_t* ik) {
+  CHECK_FRAME_LEVEL(h, frame, level);
+  return get_dp_pointers_(h, frame * h->nlevels + level, component, part, parent_mix, ix, iy, ik);
 }
 static int get_root_(pbd_handle* h, int level, int component, void* rootv, int32_t* rooti, int ts) {
   CHECK_LEVEL(h, level);
@@ -1282,8 +1291,8 @@ static int dt2d_(pbd_handle* h, const void* in, int rows, int cols, double ax, d
   for (size_t i = 0; i < HW; ++i) {   // pointer composition of compute() (:233-244), or the true arg-max one
     const int m_ = (int)(i / cols), n_ = (int)(i - (size_t)m_ * cols);
     int x, y;
-    if (!h->opt.dt_correct_ptr) { x = hx[i]; y = hy[(size_t)m_ * cols + x]; }
-    else { y = hy[i]; x = hx[(size_t)y * cols + n_]; }
+    if (!h->opt.dt_correct_ptr) { x = hx[(size_t)n_ * rows + m_]; y = hy[(size_t)m_ * cols + x]; }   // hx: [column][row] (the x pass writes transposed)
+    else { y = hy[i]; x = hx[(size_t)n_ * rows + y]; }
     if (ix) ix[i] = x;
     if (iy) iy[i] = y;
   }

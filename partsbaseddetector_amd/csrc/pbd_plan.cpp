@@ -472,7 +472,7 @@ static int dt_lpb_for(int stride, int len, int unit, size_t budget, int ts, int 
 DtGroup dt_group(int map0, int nmaps, int nlines, int len, size_t budget, int ts, int nt, int seg, bool natural, int fold, bool round_lanes) {
   DtGroup g{};
   g.map0 = map0; g.nmaps = nmaps; g.nlines = nlines; g.len = len; g.fold = fold;
-  g.fused = natural ? DT_G_NATURAL : 0;   // the pointer layout is a property of the pass (DT_G_FUSED: dt_mark_fused)
+  g.fused = natural ? DT_G_NATURAL : 0;   // marks the x pass (pbd_plan.hpp; DT_G_FUSED: dt_mark_fused)
   g.stride = dt_stride_for(len);
   g.lpb = dt_lpb_for(g.stride, len, fold >= 0 ? nmaps : 1, budget, ts, nt, seg, round_lanes);
   // wave-uniform quotients of the block's index arithmetic, as constants (pbd_internal.hpp)

@@ -47,10 +47,13 @@ struct PadJob { unsigned long long cell_off; int cw, ch, pad, nring; };
 struct DtMap {       // one 1-D pass over one score map
   const void* src;   // T: lines contiguous: line i at src + i*len
   void* dst;         // T: transposed out: element q of line i at dst + q*nlines + i
-  int16_t* ptr;      // same layout as dst
+  int16_t* ptr;      // same layout as dst, in BOTH passes: element q of line i at ptr + q*nlines + i.  An x pass's plane (lines = rows) is therefore
+                     // stored [column][row] with the level's row count as its pitch — k_backtrack and pbd_get_dp_pointers address it so, from the level's
+                     // H alone; a y pass's (lines = columns) comes out [row][column]
   double a, b;       // Quadratic(a, b)
   double r2a;        // RN(1 / (2a)), IEEE division on the host (dt_core.hpp: the reciprocal of an intersection's denominator)
-  int os, ptr_natural;  // ptr_natural: write ptr row-major [line][q] instead of transposed
+  int os, ptr_natural;  // ptr_natural: 1 on an x pass's map.  No kernel reads it: up to round 6 it chose a row-major [line][q] pointer plane (one 2-byte
+                        // write per lane and store); the host replay of a block (tests/tools/dt_replay.cpp) still lays out its private planes by it
 };
 // One group = the maps of one launch that share a geometry: nmaps maps of nlines lines of len elements.
 //   plain:  line gi of the group = line gi % nlines of map gi / nlines (map-major); a block = lpb consecutive lines.
@@ -70,9 +73,9 @@ struct DtGroup {
   unsigned magic_P;          // (p * len) / P           (p * len < 2^21, P <= 64)
   int fused;                 // bit 0 — float maps only: every map of the group has weights that are converted floats, len and len + |os| <= DT_FUSE_MAXLEN: the
                              // intersection's and the read-out's products are exact and fuse into their additions (dt_core.hpp: dt_isect);
-                             // bit 1 — the group's maps write their pointers in natural layout (DtMap::ptr_natural of every map of the group: x passes): the
-                             // block reads it HERE — from the lane's map descriptor hipcc evaluated it right behind the descriptor's load, a full memory round
-                             // trip in front of the loader of every block
+                             // bit 1 — the group is an x pass (DtMap::ptr_natural of every map of the group).  No kernel reads it since the x pass writes its
+                             // pointers transposed like every other output of the chain; the planner keeps setting it on exactly the x passes, which the plan
+                             // check (tests/tools/plan_check.cpp) pins
 };
 #define DT_G_FUSED 1
 #define DT_G_NATURAL 2
@@ -279,7 +282,7 @@ int plan_tables(const HostModel& hm, const FrameSpec& f, const FrameLayout& lay,
 
 // ---- DT task lists (also pbd_dt2d's) ----------------------------------------------------------------------------------------------
 int dt_stride_for(int len);
-// natural: the group's maps write their pointers in natural layout (the x pass; DT_G_NATURAL); fold >= 0: the group is one part at
+// natural: the group is an x pass (DT_G_NATURAL: a marker, see DtGroup::fused); fold >= 0: the group is one part at
 // one level, a block = whole rows of its nmaps mixtures; round_lanes: plain groups only — the largest lines-per-block <= the fit that
 // leaves no lane idle
 DtGroup dt_group(int map0, int nmaps, int nlines, int len, size_t budget, int ts, int nt, int seg, bool natural, int fold = -1,
