@@ -345,7 +345,10 @@ int pbd_get_level_response_f64(pbd_handle* h, int level, int filter, double* out
 int pbd_set_level_response_f64(pbd_handle* h, int level, int filter, const double* in);
 /* DynamicProgram<T>::min (src/DynamicProgram.cpp:66-173)                      */
 int pbd_dp_min(pbd_handle* h);
-/* Ix/Iy/Ik[level][component][part][parent mixture] as int32 cell_h*cell_w     */
+/* Ix/Iy/Ik[level][component][part][parent mixture] as int32 cell_h*cell_w.
+ * A frame entry (pbd_detect_*, pbd_enqueue_*) does not store Ik on the device: its back-tracking picks the mixture at the cells it
+ * visits.  The first getter call after such a frame writes the Ik planes of the whole plan from the resident scores (one small launch),
+ * later calls read them; the bytes returned are those the reference's min() computes.  pbd_dp_min leaves the planes written. */
 int pbd_get_dp_pointers(pbd_handle* h, int level, int component, int part, int parent_mix,
                         int32_t* ix, int32_t* iy, int32_t* ik);
 /* Read-only: the same tables of ONE frame of the current plan, 0 <= frame < frames of the plan — also for a batch plan

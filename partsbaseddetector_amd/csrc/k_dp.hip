@@ -29,6 +29,7 @@
 #include <type_traits>
 #include "pbd_internal.hpp"
 #include "dt_core.hpp"
+#include "fold_pick.hpp"
 
 // pointers that come out of descriptors in memory are generic to the compiler (flat loads and stores, which also
 // count as LDS traffic for s_waitcnt): say that they are global
@@ -101,7 +102,7 @@ void dt_debug_counters(unsigned long long* out) { for (int i = 0; i < 8; ++i) ou
 // block of the child (wave-uniform: scalar loads) is fetched in one straight-line batch — a load inside a (uniform)
 // branch costs one full scalar-memory round trip per branch, which is what made a first version's loader 5x slower
 // than the plain one.  Everything below is branch-free except the loop over the children.
-// A child's plane pointers wait in a VECTOR register, one quad-word per lane (lane k < 8: sdt[k], lanes >= 8: ok), and come out by v_readlane where they are
+// A child's plane pointers wait in a VECTOR register, one quad-word per lane (lane k < 8: sdt[k]; lanes >= 8 hold the Ik base, which the fold does not use), and come out by v_readlane where they are
 // used: fetched by scalar loads at their use (rounds 3-5) every child began with a memory round trip of its own — descriptor -> pointers -> planes —, and
 // fetched early by scalar loads they do not fit the scalar register file beside the bias block (hipcc then serialises the loads, one wait each: tried).  The
 // caller fetches child 0's with whatever else it reads from descriptors; child c + 1's are fetched behind child c's vector loads.  Every lane of the
@@ -115,27 +116,27 @@ __device__ __forceinline__ GP(char) fold_qw_lane(unsigned long long v, int l) {
   return (GP(char))(((unsigned long long)hi << 32) | lo);
 }
 template <typename T, int M, int U>
-__device__ __forceinline__ void fold_children(const FoldJob* __restrict__ J, const float* __restrict__ /*biasw*/, const unsigned (&off)[U],
-                                              unsigned HW, int L, T (&acc)[U][M], unsigned long long cv, int nch) {   // nch = J->nch (k_dt_pass has it from the task's extension record)
+__device__ __forceinline__ void fold_children(const FoldJob* __restrict__ J, const unsigned (&off)[U], T (&acc)[U][M], unsigned long long cv,
+                                              int nch) {   // nch = J->nch (k_dt_pass has it from the task's extension record)
   unsigned ob[U];                                        // byte offsets of the cells inside a plane of T (< 2^32, plan_frame)
 #pragma unroll
   for (int u = 0; u < U; ++u) ob[u] = off[u] * (unsigned)sizeof(T);
   int c = 0;
-  do {                                                   // (a fold job has at least one child: a loop that may run zero times made the
-                                                         // compiler wait, after it, for the children's Ik STORES before the LDS stores)
+  do {                                                   // (a fold job has at least one child: the loop keeps the shape it had while the children's Ik
+                                                         // bytes were stored from here — one that may run zero times made the compiler wait, after it, for
+                                                         // those stores before the LDS stores)
     const FoldChild& C = J->ch[c];
     // everything the child contributes is fetched up front, in straight-line code: the K planes' values of the U
     // cells (uniform base + 32-bit byte offset: no vector arithmetic per load) and the dense K x L bias block
-    GPW(uint8_t) okp = (GPW(uint8_t))fold_qw_lane(cv, 8);
     T sd[U][M];
     // (the offsets pass through an empty asm: hoisted out of the loop over the children they would be kept zero-extended to
-    // 64 bits, and every load / store would pay a 64-bit vector add instead of using the scalar-base + 32-bit-offset form)
-    unsigned obc[U], offc[U];
+    // 64 bits, and every load would pay a 64-bit vector add instead of using the scalar-base + 32-bit-offset form)
+    unsigned obc[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      obc[u] = ob[u]; offc[u] = off[u];
+      obc[u] = ob[u];
 #if defined(__HIP_DEVICE_COMPILE__)
-      asm volatile("" : "+v"(obc[u]), "+v"(offc[u]));
+      asm volatile("" : "+v"(obc[u]));
 #endif
     }
 #pragma unroll
@@ -145,53 +146,25 @@ __device__ __forceinline__ void fold_children(const FoldJob* __restrict__ J, con
       for (int u = 0; u < U; ++u) sd[u][k] = *(GP(T))(pl + obc[u]);
     }
     cv = fold_child_qw(&J->ch[min(c + 1, nch - 1)]);      // the next child's pointers (after the last child: its own again, unused)
-    float bias[M][M];
+    float bias[M][M];                                     // [parent mixture m][child mixture k]: column m of the child's block, as fold_pick takes it
     // (wave-uniform: scalar loads.  Fetching the block with vector loads instead — it overflows the scalar register file and
     // part of it is spilled to vector-register lanes — was measured 9 % slower per fold launch: twelve more vector-memory
     // instructions per child in front of the block's dependent chain)
 #pragma unroll
     for (int k = 0; k < M; ++k)
 #pragma unroll
-      for (int m = 0; m < M; ++m) bias[k][m] = C.bias[k][m];
-    unsigned okoff[M];                                   // offset of plane m of the child's Ik planes (uniform).  Columns beyond L repeat column
-#pragma unroll                                           // L - 1 (plan) and land on plane L - 1 again: the same byte stored twice, no predicate
-    for (int m = 0; m < M; ++m) okoff[m] = (unsigned)min(m, L - 1) * HW;
-    // Math::reduceMax's K == 1 shortcut copies (Math.hpp:154-158): maxv = the one weighted map — NaN and -inf included —,
-    // maxi = 0.  A wave-uniform SELECT at the end, not a branch: a branch here made the compiler wait for plane 0's loads
-    // (the code both sides share) before it issued the loads of the other planes — two memory round trips per child.
-    const bool copy1 = C.K == 1;
+      for (int m = 0; m < M; ++m) bias[m][k] = C.bias[k][m];
+    // Math::reduceMax's K == 1 shortcut copies (Math.hpp:154-158).  Inside fold_pick it is a wave-uniform SELECT at the end, not a
+    // branch: a branch here made the compiler wait for plane 0's loads (the code both sides share) before it issued the loads of
+    // the other planes — two memory round trips per child.  No `k < K` test either: planes / bias rows beyond K repeat mixture K - 1.
+    const int K = C.K;
+    // The winning mixture (Ik, :150) is NOT kept: fold_pick's index is dead here and costs nothing.  k_backtrack picks it again for
+    // the cells it visits, k_ik_fill for whole planes on request (fold_pick.hpp).
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      T v[M];
-      int bi[M];
-      T w0[M];
+    for (int u = 0; u < U; ++u)
 #pragma unroll
-      for (int m = 0; m < M; ++m) {
-        // k = 0 first: Math::reduceMax starts from -inf and takes strict > (first maximum wins): a NaN score leaves -inf
-        w0[m] = sd[u][0] + bias[0][m];                    // DynamicProgram.cpp:139
-        v[m] = w0[m] > (T)-INFINITY ? w0[m] : (T)-INFINITY;
-        bi[m] = 0;
-      }
-#pragma unroll
-      for (int k = 1; k < M; ++k) {
-#pragma unroll
-        for (int m = 0; m < M; ++m) {
-          // (no `k < K` test: planes / bias rows beyond K repeat mixture K - 1, whose value cannot be strictly greater than the
-          // maximum it has already been folded into)
-          const T wv = sd[u][k] + bias[k][m];
-          const bool take = wv > v[m];                  // strict >: first max wins
-          bi[m] = take ? k : bi[m];
-          v[m] = take ? wv : v[m];
-        }
-      }
-#pragma unroll
-      for (int m = 0; m < M; ++m) {
-        // Ik (:150).  Unpredicated: a lane past the block's last cell works on that cell again (its offset was clamped) and
-        // stores the same byte once more
-        *(okp + (okoff[m] + offc[u])) = (uint8_t)bi[m];                // (cells * planes < 2^32, plan_frame; K == 1: rows beyond 0 repeat row 0, bi stays 0)
-        acc[u][m] = acc[u][m] + (copy1 ? w0[m] : v[m]);                // parent.score += maxv (:156), child order kept
-      }
-    }
+      for (int m = 0; m < M; ++m)
+        acc[u][m] = acc[u][m] + fold_pick<T, M>(sd[u], bias[m], K).v;   // parent.score += maxv (:156), child order kept
   } while (++c < nch);
 }
 
@@ -291,7 +264,6 @@ __device__ __forceinline__ void dt_block(char* smem, const DtTask& t, const DtGr
     constexpr int U = sizeof(T) == 8 ? 1 : 3;
     const FoldJob* J = folds + g.fold;
     const int L = g.nmaps;
-    const unsigned HW = (unsigned)g.nlines * (unsigned)len;     // cells of the level (< 2^31, plan_frame)
     // the part's raw response planes (entries beyond L repeat plane L - 1) and the first child's plane pointers (c0qw: fold_children) come from the task's
     // extension record, fetched by k_dt_pass BESIDE the task descriptor: the loader's first loads are one memory round trip behind the kernel's entry, not
     // three (descriptor -> map table / fold job -> planes; round 6)
@@ -325,7 +297,7 @@ __device__ __forceinline__ void dt_block(char* smem, const DtTask& t, const DtGr
         if (e0 == 0)
           for (int dx = lane; dx < len; dx += NT) RDX[dx] = 1.0 / (double)dx;   // entry 0 is never read
       }
-      fold_children<T, M, U>(J, biasw, off, HW, L, acc, c0qw, nch0);
+      fold_children<T, M, U>(J, off, acc, c0qw, nch0);
       const int mstride = nrows * S;                                 // LDS elements between the lines of consecutive mixtures of a row
       // (unpredicated like the plain loader: a lane past the last cell holds the last cell's values and stores them once more.  Round 6
       //  measured the alternative — wavefronts whose slot holds clamped repeats only skip the mixture reduce —: 0.7 % faster alone, 1.6 %
@@ -702,6 +674,37 @@ void launch_reduce(const ReduceJob* jobs, const ReduceBlock* blocks, int nblocks
 }
 
 // ---------------------------------------------------------------------------
+// Ik planes on request (fold plans): the fold does not store the winning child mixtures, so when a caller asks for the tables
+// (pbd_get_dp_pointers, the stage entry pbd_dp_min, a caller's own tables on top of them) they are written here from the children's kept
+// scores: one thread per cell of one (level, child part), every parent mixture in turn, by the fold's own statement (fold_pick).
+// blocks: {job = index into pick, first cell}; a job whose pick entry is PBD_NO_PICK has no blocks.
+// ---------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void k_ik_fill(const char* __restrict__ folds, const unsigned long long* __restrict__ pick,
+                                                 const ReduceBlock* __restrict__ blocks, const unsigned* __restrict__ cells) {
+  const ReduceBlock rb = blocks[blockIdx.x];
+  GP(FoldChild) C = (GP(FoldChild))(folds + pick[rb.job]);
+  const unsigned HW = cells[rb.job], cell = rb.cell0 + threadIdx.x;
+  if (cell >= HW) return;
+  const int K = C->K, L = C->L;
+  T sd[PBD_FOLD_MAXMIX];
+#pragma unroll
+  for (int k = 0; k < PBD_FOLD_MAXMIX; ++k) sd[k] = ((GP(T))C->sdt[k])[cell];   // (entries beyond K repeat plane K - 1: plan)
+  GPW(uint8_t) ok = (GPW(uint8_t))C->ok;
+  for (int m = 0; m < L; ++m) {
+    float bc[PBD_FOLD_MAXMIX];
+#pragma unroll
+    for (int k = 0; k < PBD_FOLD_MAXMIX; ++k) bc[k] = C->bias[k][m];
+    ok[(size_t)m * HW + cell] = (uint8_t)fold_pick<T, PBD_FOLD_MAXMIX>(sd, bc, K).i;
+  }
+}
+void launch_ik_fill(const FoldJob* folds, const unsigned long long* pick, const ReduceBlock* blocks, int nblocks, const unsigned* cells, int ts, hipStream_t s) {
+  if (nblocks <= 0) return;
+  if (ts == 8) hipLaunchKernelGGL(k_ik_fill<double>, dim3(nblocks), dim3(256), 0, s, (const char*)folds, pick, blocks, cells);
+  else hipLaunchKernelGGL(k_ik_fill<float>, dim3(nblocks), dim3(256), 0, s, (const char*)folds, pick, blocks, cells);
+}
+
+// ---------------------------------------------------------------------------
 // root: bias + max over root mixtures, threshold, compaction
 // ---------------------------------------------------------------------------
 // One 256-thread block = 256 consecutive cells of ONE job (level, component): block -> (job, first cell) comes from a host-built
@@ -718,7 +721,7 @@ __global__ __launch_bounds__(256) void k_root(const RootJob* __restrict__ jobs, 
   const unsigned HWr = (unsigned)J.H * (unsigned)J.W;
   const bool live = cell < HWr;
   // (the fold keeps every lane of the block: its children's plane pointers travel in vector-register lanes — fold_child_qw —; lanes past the job's last cell
-  //  work on that cell again and store the same Ik bytes once more)
+  //  work on that cell again and leave at `!live` below)
   if (!live && (rescan || J.fold < 0)) return;
   T v;
   int bi = 0;
@@ -744,7 +747,7 @@ __global__ __launch_bounds__(256) void k_root(const RootJob* __restrict__ jobs, 
     const unsigned offs[1] = {cellc};
 #pragma unroll
     for (int m = 0; m < M; ++m) acc[0][m] = ((GP(T))J.score[m])[cellc];      // (entries beyond K repeat mixture K - 1: plan_frame)
-    fold_children<T, M, 1>(folds + J.fold, biasw, offs, HWr, K, acc, c0qw, folds[J.fold].nch);
+    fold_children<T, M, 1>(folds + J.fold, offs, acc, c0qw, folds[J.fold].nch);
     if (!live) return;
     if (K == 1) {
       v = acc[0][0] + bias;
@@ -805,9 +808,25 @@ void launch_root(const RootJob* jobs, const ReduceBlock* blocks, int nblocks, do
 // child mixture mm = Ik(parent location) the lane reads the DT's own pointer planes of (part, mm),
 //   reference composition (DistanceTransform.hpp:233-244):  x = Ix(py, px),  y = Iy(py, x)
 //   dt_correct_ptr:                                         y = Iy(py, px),  x = Ix(y, px)
+// Ik itself — mm — comes from one of two places (block-uniform):
+//   pick == null   the stored planes B.pk: tables handed in by the caller (pbd_set_dp_pointers), the three-kernel structure (k_reduce
+//                  writes them), or planes k_ik_fill has materialised;
+//   pick != null   a fold plan's own tables: nothing stored them.  The lane loads the K kept scores of its part at the parent's
+//                  cell (independent loads) and the bias column of the parent's mixture, and fold_pick gives the index the fold's
+//                  value came from.  The part's plane pointers do not depend on the parent's location: they are fetched in front
+//                  of the depth loop, so a depth stays three dependent loads deep (scores -> one pass's pointer -> the other's).
 // record = head | boxes[max_parts][4] | locs[max_parts][3]
 // ---------------------------------------------------------------------------
 #define BT_MAXP 256   // parts per component held in LDS
+struct BtChild { GP(char) sdt[PBD_FOLD_MAXMIX]; GP(FoldChild) C; int K; };
+__device__ __forceinline__ BtChild bt_child(const char* folds, const unsigned long long* __restrict__ pick, size_t i) {
+  BtChild c;
+  c.C = (GP(FoldChild))(folds + pick[i]);
+#pragma unroll
+  for (int k = 0; k < PBD_FOLD_MAXMIX; ++k) c.sdt[k] = (GP(char))c.C->sdt[k];   // (entries beyond K repeat plane K - 1: plan)
+  c.K = c.C->K;
+  return c;
+}
 template <typename T>
 __global__ __launch_bounds__(64) void k_backtrack(const int* __restrict__ count, const CandRec* __restrict__ rec,
                                                   int capacity, const BackLevel* __restrict__ back, int ncomp,
@@ -819,7 +838,8 @@ __global__ __launch_bounds__(64) void k_backtrack(const int* __restrict__ count,
                                                   const int16_t* __restrict__ ixs, const int16_t* __restrict__ iys,
                                                   int correct_ptr, const int16_t* __restrict__ extx,
                                                   const int16_t* __restrict__ exty, const unsigned long long* __restrict__ ext_base,
-                                                  int* __restrict__ count_out, int org) {
+                                                  int* __restrict__ count_out, int org,
+                                                  const char* __restrict__ folds, const unsigned long long* __restrict__ pick) {
   __shared__ int lx[BT_MAXP], ly[BT_MAXP], lm[BT_MAXP];
   const int lane = threadIdx.x;
   const int n = min(*count, capacity);
@@ -845,6 +865,8 @@ __global__ __launch_bounds__(64) void k_backtrack(const int* __restrict__ count,
     head->nparts = np;
     lx[0] = r.x; ly[0] = r.y; lm[0] = B.rooti[(size_t)r.y * B.W + r.x];
   }
+  BtChild ch0{};                                     // the lane's first part (p = lane)
+  if (pick && lane >= 1 && lane < np) ch0 = bt_child(folds, pick, (size_t)r.level * nflat + flat[r.comp * max_parts + lane]);
   __syncthreads();
   for (int d = 1; d <= max_depth; ++d) {
     for (int p = lane; p < np; p += 64) {
@@ -852,7 +874,20 @@ __global__ __launch_bounds__(64) void k_backtrack(const int* __restrict__ count,
       const int par = parent[r.comp * max_parts + p];
       const int px = lx[par], py = ly[par], pm = lm[par];
       const size_t off = (size_t)py * B.W + px;
-      const int mm = B.pk[(size_t)(plane0[r.comp * max_parts + p] + pm) * HW + off];           // Ik
+      int mm;
+      if (pick) {
+        const BtChild ch = p == lane ? ch0 : bt_child(folds, pick, (size_t)r.level * nflat + flat[r.comp * max_parts + p]);   // (components of more than 64 parts)
+        T sd[PBD_FOLD_MAXMIX];
+        float bc[PBD_FOLD_MAXMIX];
+#pragma unroll
+        for (int k = 0; k < PBD_FOLD_MAXMIX; ++k) {   // (rows beyond K repeat row K - 1; pm < L)
+          sd[k] = ((GP(T))ch.sdt[k])[off];
+          bc[k] = ch.C->bias[k][pm];
+        }
+        mm = fold_pick<T, PBD_FOLD_MAXMIX>(sd, bc, ch.K).i;
+      } else {
+        mm = B.pk[(size_t)(plane0[r.comp * max_parts + p] + pm) * HW + off];           // Ik
+      }
       int x, y;
       if (extx) {   // tables handed in by the caller (pbd_set_dp_pointers): Ix / Iy are stored composed, per (part, parent mixture)
         const size_t eo = (size_t)ext_base[r.level * ncomp + r.comp] + (size_t)(plane0[r.comp * max_parts + p] + pm) * HW + off;
@@ -894,10 +929,11 @@ void launch_backtrack(const int* count, const CandRec* rec, int capacity, const 
                       const int* parent, const int* plane0, const int* nparts, int max_parts, const int* mix_rows, char* out,
                       size_t out_stride, int ts, const int* flat, const int* depth, int max_depth, int nflat,
                       const unsigned long long* scr_base, const int16_t* ix, const int16_t* iy, int correct_ptr,
-                      const int16_t* extx, const int16_t* exty, const unsigned long long* ext_base, int* count_out, int pad, hipStream_t s) {
+                      const int16_t* extx, const int16_t* exty, const unsigned long long* ext_base, int* count_out, int pad,
+                      const FoldJob* folds, const unsigned long long* pick, hipStream_t s) {   // pick != null: Ik is picked from the fold's kept scores, not read from planes
   const int nblk = std::min(capacity, 2048);   // 8 blocks of one wavefront per CU; more candidates than that are taken in further sweeps
-  if (ts == 8) hipLaunchKernelGGL(k_backtrack<double>, dim3(nblk), dim3(64), 0, s, count, rec, capacity, back, ncomp, parent, plane0, nparts, max_parts, mix_rows, out, out_stride, flat, depth, max_depth, nflat, scr_base, ix, iy, correct_ptr, extx, exty, ext_base, count_out, 1 + pad);
-  else hipLaunchKernelGGL(k_backtrack<float>, dim3(nblk), dim3(64), 0, s, count, rec, capacity, back, ncomp, parent, plane0, nparts, max_parts, mix_rows, out, out_stride, flat, depth, max_depth, nflat, scr_base, ix, iy, correct_ptr, extx, exty, ext_base, count_out, 1 + pad);
+  if (ts == 8) hipLaunchKernelGGL(k_backtrack<double>, dim3(nblk), dim3(64), 0, s, count, rec, capacity, back, ncomp, parent, plane0, nparts, max_parts, mix_rows, out, out_stride, flat, depth, max_depth, nflat, scr_base, ix, iy, correct_ptr, extx, exty, ext_base, count_out, 1 + pad, (const char*)folds, pick);
+  else hipLaunchKernelGGL(k_backtrack<float>, dim3(nblk), dim3(64), 0, s, count, rec, capacity, back, ncomp, parent, plane0, nparts, max_parts, mix_rows, out, out_stride, flat, depth, max_depth, nflat, scr_base, ix, iy, correct_ptr, extx, exty, ext_base, count_out, 1 + pad, (const char*)folds, pick);
 }
 
 // ---------------------------------------------------------------------------

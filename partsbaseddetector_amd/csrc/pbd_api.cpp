@@ -181,13 +181,13 @@ static void compact_mark_resp(pbd_handle* h, bool all) { if (h->compact) h->resp
 // nothing of the plan's geometry has been computed or handed in (a new plan, pbd_begin_frame)
 static void reset_stages(pbd_handle* h) {
   h->have_pyr = h->have_feat = h->have_resp = h->have_dp = false;
-  h->min_ran = false;
+  h->min_ran = h->ik_lazy = false;
   h->feat_ok.clear(); h->resp_ok.clear(); h->ext_set.clear(); h->root_set.clear();   // (sized again by whoever marks a plane next)
   h->lat_masked = false;
 }
 static void mark_pyramid(pbd_handle* h) {
   h->have_pyr = true;
-  if (h->compact) h->have_dp = h->min_ran = false;   // the level images + features share their memory with the Ik planes / the x pass's scratch:
+  if (h->compact) h->have_dp = h->min_ran = h->ik_lazy = false;   // the level images + features share their memory with the Ik planes / the x pass's scratch:
                                                      // the previous min()'s tables are gone (a plane handed in later is then NOT on top of a min())
 }
 // split_written: the split-product bank's copy of the features was written with them (k_hog's epilogue)
@@ -195,7 +195,7 @@ static void mark_features(pbd_handle* h, bool split_written) {
   h->feat_split_ok = split_written;
   h->have_feat = true;
   compact_mark_feat(h, true);
-  if (h->compact) h->have_dp = h->min_ran = false;
+  if (h->compact) h->have_dp = h->min_ran = h->ik_lazy = false;
 }
 static void mark_responses(pbd_handle* h) { h->have_resp = true; compact_mark_resp(h, true); h->lat_masked = false; }
 // latent detection: the resident responses now carry a mask, and d_lat_flags its flags, until responses are produced or handed in again
@@ -204,6 +204,7 @@ static void mark_latent_mask(pbd_handle* h, int component) { h->lat_masked = tru
 static void mark_min(pbd_handle* h, bool timed) {
   h->dp_timed = timed;
   h->have_dp = h->min_ran = true;
+  h->ik_lazy = h->fold;                 // fold plans: the Ik planes are not materialised (ensure_ik); the three-kernel structure's k_reduce has written them
   h->ext_ptr = h->root_dirty = false;   // back-tracking reads this min()'s own tables again, thresholded by it
   if (h->compact) {     // their memory now holds the DP's planes: every feature / response plane is stale until produced or handed in again
     h->have_pyr = h->have_feat = h->have_resp = false;
@@ -221,6 +222,7 @@ void free_frame(pbd_handle* h) {
   h->frame_bytes = 0;
   h->d_extx = h->d_exty = nullptr; h->d_ext_base = nullptr; h->ext_ptr = false;
   h->d_cf_mask = nullptr; h->cf_mask_bytes = 0;
+  h->d_ik_blocks = nullptr; h->d_ik_cells = nullptr; h->n_ik_blocks = 0;
   h->d_lat_jobs = nullptr; h->d_lat_blocks = nullptr; h->d_lat_flags = nullptr; h->d_lat_partial = nullptr; h->n_lat_blocks = 0;
   h->fw = h->fh = h->fcn = 0; h->fdepth = 0; h->fesz = 1;
   reset_stages(h);
@@ -280,8 +282,22 @@ int plan_frame(pbd_handle* h, int w, int hgt, int cn, int batch, int depth) {
       (rc = dev_upload(h, &h->d_foldjobs, t.folds)) || (rc = dev_upload(h, &h->d_foldx, t.foldx)) ||
       (rc = dev_upload(h, &h->d_redjobs, t.red)) || (rc = dev_upload(h, &h->d_redblocks, t.redblk)) ||
       (rc = dev_upload(h, &h->d_rootjobs, t.rootjobs)) || (rc = dev_upload(h, &h->d_rootblocks, t.rootblk)) ||
-      (rc = dev_upload(h, &h->d_back, t.back)) || (rc = dev_upload(h, &h->d_scr_base, t.scr_base)))
+      (rc = dev_upload(h, &h->d_back, t.back)) || (rc = dev_upload(h, &h->d_scr_base, t.scr_base)) ||
+      (rc = dev_upload(h, &h->d_pick, t.pick)))
     return rc;
+  {   // k_ik_fill's work table (fold plans): one job per (level, part) that has a message, one block per 256 cells
+    const size_t nflat = h->parts.size();
+    std::vector<ReduceBlock> blocks;
+    std::vector<unsigned> cells(t.pick.size(), 0);
+    for (size_t i = 0; i < t.pick.size(); ++i) {
+      if (t.pick[i] == PBD_NO_PICK) continue;
+      const Level& L = lay.lv[i / nflat];
+      cells[i] = (unsigned)L.cw * (unsigned)L.ch;
+      for (unsigned c0 = 0; c0 < cells[i]; c0 += 256) blocks.push_back(ReduceBlock{(int)i, c0});
+    }
+    if ((rc = dev_upload(h, &h->d_ik_cells, cells)) || (rc = dev_upload(h, &h->d_ik_blocks, blocks))) return rc;
+    h->n_ik_blocks = (int)blocks.size();
+  }
   h->lv = lay.lv; h->nlevels = lay.nlevels; h->batch = batch; h->nvl = lay.nvl;
   h->first_copy = kFirstCopy * batch;
   h->cells = lay.cells; h->pyr_bytes = lay.pyr_bytes; h->compact = lay.compact; h->dt_cap_elems = lay.dt_cap_elems;
@@ -420,6 +436,18 @@ static int run_dp_min(pbd_handle* h) {
   if (dpt) hipEventRecord(h->ev_dp1, h->stream);
   LAUNCHCHK(h, "DP min");
   mark_min(h, dpt);
+  return PBD_OK;
+}
+
+// Fold plans: the Ik planes of the current min(), written from the children's kept scores when somebody needs the planes themselves —
+// never by a frame entry (enter_frame -> enqueue_all, captured graphs included), whose back-tracking picks Ik for the cells it visits.
+// The kept scores stay intact as long as ik_lazy is set: the one entry that overwrites them under a valid min() (a response plane
+// handed in on the compact plan, whose planes hold them) calls this first.
+static int ensure_ik(pbd_handle* h) {
+  if (!h->ik_lazy || !h->have_dp || !h->min_ran) return PBD_OK;
+  launch_ik_fill(h->d_foldjobs, h->d_pick, h->d_ik_blocks, h->n_ik_blocks, h->d_ik_cells, h->ts, h->stream);
+  LAUNCHCHK(h, "Ik planes");
+  h->ik_lazy = false;
   return PBD_OK;
 }
 
@@ -570,7 +598,8 @@ static int run_argmin_enqueue(pbd_handle* h, bool filter = false) {
   launch_backtrack(h->d_cand_count, h->d_cand_rec, h->opt.max_candidates, h->d_back, h->md.ncomponents, h->d_parent,
                    h->d_plane0, h->d_nparts, h->max_parts, h->d_mix_rows, out, h->cand_stride, h->ts, h->d_flat,
                    h->d_depth, h->max_depth, (int)h->parts.size(), h->d_scr_base, h->d_dt_ixT, h->d_dt_iy,
-                   h->opt.dt_correct_ptr, h->ext_ptr ? h->d_extx : nullptr, h->d_exty, h->d_ext_base, count_out, h->pad, h->stream);
+                   h->opt.dt_correct_ptr, h->ext_ptr ? h->d_extx : nullptr, h->d_exty, h->d_ext_base, count_out, h->pad,
+                   h->d_foldjobs, h->ik_lazy && !h->ext_ptr ? h->d_pick : nullptr, h->stream);
   if (post) return pbd_i_post_enqueue(h, cm, zf, out);
   LAUNCHCHK(h, "argmin");
   if (zero_copy) { h->pending = true; h->out_on_host = true; return PBD_OK; }
@@ -880,7 +909,7 @@ static int set_level_features_(pbd_handle* h, int level, const void* in, int ts)
   // (split_written = false: the split-product bank's copy of the features is re-derived in front of the next pdf())
   if (h->compact) {   // not mark_features: ONE plane handed in — the write went over the Ik planes / the x pass's scratch; the other levels may still be stale
     h->feat_split_ok = false;
-    h->have_dp = h->min_ran = false;
+    h->have_dp = h->min_ran = h->ik_lazy = false;
     if (h->feat_ok.size() != (size_t)h->nvl) compact_mark_feat(h, false);
     h->feat_ok[level] = 1;
     h->have_feat = all_active_set(h, h->feat_ok, 1);
@@ -961,6 +990,7 @@ static int set_level_response_(pbd_handle* h, int level, int filter, const void*
   if ((ts == 4 ? pbd_first_nonfinite((const float*)in, HW) : pbd_first_nonfinite((const double*)in, HW)) != HW)
     return fail(h, PBD_ERR_ARG, "non-finite response: the distance transform takes finite scores only");
   ON_DEVICE(h);
+  if (h->compact) { int rc = ensure_ik(h); if (rc) return rc; }   // the plane holds a mixture's transformed scores, which this min()'s Ik is picked from: planes first
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemcpy(h->d_resp + (L.cell_off * h->md.nfilters + filter * HW) * ts, in, HW * ts, hipMemcpyHostToDevice));
   if (h->compact) {   // not mark_responses: ONE plane handed in — min() transformed the planes in place: the responses are valid again once EVERY plane has been handed in (or pdf() re-run)
@@ -982,6 +1012,7 @@ int pbd_dp_min(pbd_handle* h) {
   if (!h->have_resp) return fail(h, PBD_ERR_STATE, h->compact ? "min(): responses are not resident (compact memory plan: min() transforms them in place — run pdf() or hand in every plane again)" : "min() before pdf()");
   ON_DEVICE(h);
   int rc = run_dp_min(h);
+  if (!rc) rc = ensure_ik(h);   // the stage entry leaves the tables there, Ik planes included (a frame entry does not: its back-tracking picks)
   if (rc) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return PBD_OK;
@@ -1005,6 +1036,7 @@ static int get_dp_pointers_(pbd_handle* h, int level, int component, int part, i
   std::vector<int16_t> X((size_t)P.K * HW), Y((size_t)P.K * HW);
   const size_t so = (size_t)h->scr_base[(size_t)level * h->parts.size() + (p0 + part)];
   ON_DEVICE(h);
+  { int rc = ensure_ik(h); if (rc) return rc; }   // a frame entry's min() has not written the Ik planes
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemcpy(c.data(), h->d_pk + po, HW, hipMemcpyDeviceToHost));
   HIPCHK(h, hipMemcpy(X.data(), h->d_dt_ixT + so, X.size() * 2, hipMemcpyDeviceToHost));
@@ -1086,6 +1118,7 @@ int pbd_set_dp_pointers(pbd_handle* h, int level, int component, int part, int p
   if (!L.active) return fail(h, PBD_ERR_STATE, "level is not processed by this handle");
   const size_t HW = (size_t)L.cw * L.ch;
   ON_DEVICE(h);
+  { int rc = ensure_ik(h); if (rc) return rc; }   // the planes NOT handed in keep this handle's Ik: back-tracking reads all of them from d_pk from here on
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (!h->d_extx) {   // first use on this frame plan: composed planes for every (level, plane), 2 x int16
     const size_t n = h->cells * (size_t)std::max(h->nplanes, 1);

@@ -138,6 +138,10 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   // tables handed in by the caller with no min() of this handle behind them: back-tracking needs every plane and every
   // root table of the active levels before it may run
   bool min_ran = false;                          // this plan's tables (Ik, DT pointer planes, roots) come from run_dp_min
+  // Fold plans: min() does not store the Ik planes.  While ik_lazy, the tables are this handle's own and the children's kept scores
+  // they are a function of are intact: back-tracking picks Ik from those (k_backtrack), and whoever needs the PLANES — a getter, the
+  // stage entry pbd_dp_min, a caller's tables or a response plane about to go on top — has them written first (ensure_ik, pbd_api.cpp).
+  bool ik_lazy = false;
   std::vector<char> ext_set, root_set;           // [level * nplanes + plane], [level * ncomp + comp]
 
   // device frame buffers
@@ -150,6 +154,8 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   uint16_t* d_wS = nullptr;           // PBD_CONV_SPLIT: the filters as [tap][2 k-steps][3 splits][n-tile][2 k-groups][32][8] bfloat16 (per model)
   uint8_t* d_pk = nullptr;
   unsigned long long* d_scr_base = nullptr;   // [nlevels][nflat parts] element offset of mixture 0's DT planes (ix / iy / sdt)
+  unsigned long long* d_pick = nullptr;       // fold plans, [nvl][nflat parts]: FrameTables::pick
+  ReduceBlock* d_ik_blocks = nullptr; unsigned* d_ik_cells = nullptr; int n_ik_blocks = 0;   // k_ik_fill's work table (frame plan)
   std::vector<unsigned long long> scr_base;   // host copy (pbd_get_dp_pointers)
   int* d_flat = nullptr;     // [ncomp][max_parts] flat part index
   int* d_depth = nullptr;    // [ncomp][max_parts] depth of each part in its tree (root = 0)
@@ -518,7 +524,10 @@ void launch_backtrack(const int* count, const CandRec* rec, int capacity, const 
                       const int* parent, const int* plane0, const int* nparts, int max_parts, const int* mix_rows,
                       char* out, size_t out_stride, int ts, const int* flat, const int* depth, int max_depth, int nflat,
                       const unsigned long long* scr_base, const int16_t* ix, const int16_t* iy, int correct_ptr,
-                      const int16_t* extx, const int16_t* exty, const unsigned long long* ext_base, int* count_out, int pad, hipStream_t s);   // pad: the boundary padding (box origin)
+                      const int16_t* extx, const int16_t* exty, const unsigned long long* ext_base, int* count_out, int pad,   // pad: the boundary padding (box origin)
+                      const FoldJob* folds, const unsigned long long* pick, hipStream_t s);   // pick != null: Ik picked from the fold's kept scores (fold_pick.hpp), not read from planes
+// fold plans: the Ik planes written from the children's kept scores (k_dp.hip: k_ik_fill); blocks: {index into pick / cells, first cell}
+void launch_ik_fill(const FoldJob* folds, const unsigned long long* pick, const ReduceBlock* blocks, int nblocks, const unsigned* cells, int ts, hipStream_t s);
 // latent detection (k_latent.hip): the overlap mask of every response plane; the best root over the admissible (level, component) pairs
 void launch_latent_mask(const LatentMaskArgs& a, int nblocks, int ts, hipStream_t s);
 void launch_latent_best(const LatentBestArgs& a, int ts, hipStream_t s);

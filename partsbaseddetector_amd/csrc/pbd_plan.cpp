@@ -639,13 +639,15 @@ struct PlaneAddr {
 };
 
 // FoldJob of part fp at level l (its children's messages, children in descending flat index); -1 without children
-static int make_fold(const HostModel& hm, const PlaneAddr& pa, const std::vector<int>& children, int fp, int l, std::vector<FoldJob>& folds) {
+static int make_fold(const HostModel& hm, const PlaneAddr& pa, const std::vector<int>& children, int fp, int l, FrameTables& out) {
   if (children.empty()) return -1;
+  std::vector<FoldJob>& folds = out.folds;
   FoldJob J{};
   for (int c : children) {
     const PartInfo& C = hm.parts[c];
+    out.pick[(size_t)l * hm.parts.size() + c] = folds.size() * sizeof(FoldJob) + offsetof(FoldJob, ch) + (size_t)J.nch * sizeof(FoldChild);
     FoldChild& F = J.ch[J.nch++];
-    F.K = C.K;
+    F.K = C.K; F.L = hm.parts[fp].K;
     for (int k = 0; k < PBD_FOLD_MAXMIX; ++k) F.sdt[k] = pa.sdt(c, l, std::min(k, C.K - 1));
     const int Lp = hm.parts[fp].K;
     for (int k = 0; k < PBD_FOLD_MAXMIX; ++k)
@@ -750,7 +752,7 @@ static void dt_round(const HostModel& hm, const FrameLayout& lay, const PlaneAdd
         gx_nmaps++;
       }
       tmp_round += (size_t)P.K;
-      if (fold_x) dt_add_tasks(dt_group(part_map0, P.K, L.ch, L.cw, geox.budget, ts, nt, seg, true, make_fold(hm, pa, children[fp], fp, l, out.folds)), xt);
+      if (fold_x) dt_add_tasks(dt_group(part_map0, P.K, L.ch, L.cw, geox.budget, ts, nt, seg, true, make_fold(hm, pa, children[fp], fp, l, out)), xt);
     }
     if (!fold_x) dt_add_tasks(dt_group(gx_map0, gx_nmaps, L.ch, L.cw, geox.budget, ts, nt, seg, true, -1, geox.round), xt, &maps, ts);
     const DtGroup gy = dt_group((int)maps.size(), gx_nmaps, L.cw, L.ch, geoy.budget, ts, nt, seg, false, -1, geoy.round);
@@ -847,7 +849,7 @@ static void root_tables(const HostModel& hm, const FrameLayout& lay, const Plane
       J.H = L.ch; J.W = L.cw; J.K = R0.K; J.level = l; J.comp = c;
       J.bias = hm.biasw[R0.biasid[0]];  // root.bias(0)[0], DynamicProgram.cpp:165
       J.cell0 = out.root_cells;
-      J.fold = hm.fold ? make_fold(hm, pa, children[hm.part_offset[c]], hm.part_offset[c], l, out.folds) : -1;   // fold: the root's messages are folded by k_root
+      J.fold = hm.fold ? make_fold(hm, pa, children[hm.part_offset[c]], hm.part_offset[c], l, out) : -1;   // fold: the root's messages are folded by k_root
       out.root_cells += (unsigned)HW;
       out.root_maxcells = std::max(out.root_maxcells, (unsigned)HW);
       for (unsigned c0 = 0; c0 < (unsigned)HW; c0 += 256) out.rootblk.push_back(ReduceBlock{(int)out.rootjobs.size(), c0});
@@ -881,6 +883,7 @@ int plan_tables(const HostModel& hm, const FrameSpec& f, const FrameLayout& lay,
   std::vector<std::vector<int>> children(hm.parts.size());
   for (int fp = (int)hm.parts.size() - 1; fp >= 0; --fp)
     if (hm.parts[fp].p > 0) children[hm.part_offset[hm.parts[fp].comp] + hm.parts[fp].parent].push_back(fp);
+  if (hm.fold) out.pick.assign((size_t)lay.nvl * hm.parts.size(), PBD_NO_PICK);   // filled by make_fold
   std::vector<char> slot_init((size_t)hm.nslots, 0);  // legacy: ncscores[fid].empty() emulation (same for every level)
   for (size_t r = 0; r < hm.rounds.size(); ++r) {
     RoundLaunch R{};

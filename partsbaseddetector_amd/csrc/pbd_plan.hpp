@@ -100,12 +100,14 @@ struct ReduceChild {     // one child part's distance-transformed mixtures
 struct FoldChild {
   const void* sdt[PBD_FOLD_MAXMIX];   // T [H][W]: distance-transformed scores of child mixture k (one pointer per plane: the planes may
                                       // be the child's own response planes, overwritten in place by its y pass)
-  uint8_t* ok;                        // output Ik: best child mixture per parent mixture, [L][H][W]
-  int K, pad;
+  uint8_t* ok;                        // Ik: best child mixture per parent mixture, [L][H][W].  The fold itself does not write it: k_backtrack picks the
+                                      // mixture again at the cells it visits, k_ik_fill writes the planes when a caller asks for the tables (fold_pick.hpp)
+  int K, L;                           // mixtures of the child, of its parent
   float bias[PBD_FOLD_MAXMIX][PBD_FOLD_MAXMIX];   // bias(k)[m] = biasw[biasid[k] + m] (include/Parts.hpp:172-175), dense: rows beyond K / columns
                                                   // beyond L repeat the last valid one, so the kernel fetches whole rows with wide scalar loads
 };
 struct FoldJob { int nch, pad; FoldChild ch[PBD_MAX_CH]; };
+#define PBD_NO_PICK (~0ull)
 struct ReduceJob {       // one (level, parent): fold the messages of nch children, in the reference's order
   int H, W, L, nch;
   const void* par_in[PBD_MAX_MIX];   // T: parent mixture m: current score (resp plane or acc slot)
@@ -273,6 +275,8 @@ struct FrameTables {
   std::vector<ReduceBlock> rootblk;              // k_root: one 256-thread block per 256 cells of a root job
   std::vector<BackLevel> back;                   // [nvl][ncomponents]
   std::vector<unsigned long long> scr_base;      // [nvl][nflat parts] element offset of mixture 0's DT planes (ix / iy / sdt)
+  std::vector<unsigned long long> pick;          // fold plans, [nvl][nflat parts]: byte offset in `folds` of the FoldChild that carries the part's message at the
+                                                 // level — its kept score planes and its bias block, what the mixture choice is picked from —, PBD_NO_PICK: none
   unsigned root_cells = 0, root_maxcells = 0;
 };
 // dt_geom: pbd_tune_plan's DT block geometry of float handles (0 = the measured rule, 1 = 256 lanes / 40 KB, 2 = 128 lanes / 25 KB);
