@@ -167,7 +167,8 @@ int pbd_abi_version(void);
  * pbd_set_cluster3d, pbd_get_cluster3d and pbd_candidates_cluster3d (with the struct pbd_cluster3d); and the per-part score entry
  * points pbd_set_part_scores, pbd_get_part_scores and pbd_candidates_part_scores (with the struct pbd_part_score); and the latent
  * detection entry points pbd_latent_mask, pbd_dp_argbest, pbd_detect_latent_u8, pbd_detect_latent_dev_u8 and
- * pbd_detect_batch_latent_u8.                                                                                                    */
+ * pbd_detect_batch_latent_u8; and the feature-vector entry points pbd_feature_window_max, pbd_candidates_features,
+ * pbd_candidates_features_f64 and pbd_candidates_features_dev (with the struct pbd_feature_block).                               */
 
 /* ---- output record: include/Candidate.hpp:56-111 --------------------------
  * One candidate = head + max_parts boxes (x, y, width, height as cv::Rect)
@@ -736,7 +737,8 @@ int pbd_group_set_boundary_pad(pbd_group* g, int pad); /* forwards to every memb
  * Whole-path entry points: pbd_detect_u8 / pbd_detect_dev_u8 / pbd_detect_batch_u8 with a truth set per frame (batch: truth
  * [nframes][max_parts][4], mix [nframes][max_parts] or NULL, heads[nframes], boxes[nframes][max_parts][4], locs alike,
  * found[nframes]).  The handle's post steps (candidate filter, per-part scores) run on the single record unchanged; the per-part
- * scores are the detection's feature vector of detect.m:272-308.                                                                */
+ * scores are three scalars per part — what the pose scored, not what it is made of.  The feature vector of detect.m:272-308, the
+ * thing the models are trained from, is pbd_candidates_features below, called after the detect.                                    */
 int pbd_latent_mask(pbd_handle* h, const int32_t* truth, const int32_t* mix, int component, double overlap, int32_t* admissible);
 int pbd_dp_argbest(pbd_handle* h, pbd_candidate_head* head, int32_t* boxes, int32_t* locs, int* found);
 int pbd_detect_latent_u8(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride, const int32_t* truth, const int32_t* mix,
@@ -747,6 +749,62 @@ int pbd_detect_latent_dev_u8(pbd_handle* h, const void* d_im, int w, int hgt, in
 int pbd_detect_batch_latent_u8(pbd_handle* h, const uint8_t* const* ims, int nframes, int w, int hgt, int cn, int stride,
                                const int32_t* truth, const int32_t* mix, int component, double overlap, pbd_candidate_head* heads,
                                int32_t* boxes, int32_t* locs, int* found);
+
+/* ---- feature vectors of detections: what the models are trained from (ABI 5, additive) ------------------------------------------
+ * detect(im, model, thresh, bbox, overlap, id, label) of matlab/detection/detect.m collects, while it back-tracks a pose (:272-308),
+ * the pose's sparse feature vector ex.blocks — per part a bias block, a deformation block and the HOG window under the part's
+ * filter — which qp_write.m stores; its "Crucial DEBUG assertion" (:139-145) checks that the weight vector dotted with that feature
+ * reproduces the DP's score.  This is that feature, gathered on the GPU from the planes already resident.
+ * For a record at plan level n of component c with part locations (x_p, y_p, m_p) and q the parent of p — the conventions of
+ * pbd_part_score above — part p contributes ONE block:
+ *   bias_id   = biasid[p][m_p] + m_q (the child's mixture picks the base, the parent's the offset); the root: biasid[0][0].  Value 1.
+ *   def_id    = defid[p][m_p]; -1 for the root.
+ *   def       = (-(dx * dx), -dx, -(dy * dy), -dy) with dx = x_q + anchor_x - x_p, dy = y_q + anchor_y - y_p, the anchor of the same
+ *               defid (the CHILD's mixture selects both).  Integers, negated as integers and widened to double (a level may be
+ *               65535 cells wide: dx * dx is no float, and a zero stays +0.0).  The root: zeros.
+ *   filter_id = filterid[p][m_p] (the caller's filter order, as pbd_get_filter_size), kh x kw = that filter's size.
+ *   window    : win[i][j][ch] = feat[n](y_p - kh / 2 + i, x_p - kw / 2 + j, ch) for i < kh, j < kw, ch < flen, laid out [kh][kw * flen]
+ *               like the filter itself.  Integer divisions: the anchor of the filter bank (cv::filter2D's normalizeAnchor).  A cell
+ *               outside the level's plane contributes the bank's border value: 0 in channels 0 .. flen - 2 and 1 in channel
+ *               flen - 1.  With pbd_set_boundary_pad on, locs and planes are the padded ones and the same rule applies at the
+ *               padded plane's edge; nothing else changes.  The values are the handle's own feature values in T, copied, not
+ *               recomputed.
+ * Then sum_p (filter . win + defw[def_id] . def + biasw[bias_id]) is the pose's score: with pbd_options.dt_correct_ptr = 1 the
+ * record's root score up to the rounding of the filter bank and the DP (the bound of pbd_part_score plus the bank's summation
+ * error), with the reference's pointer composition at most that.  The dense layout of the weight vector is the binding's business
+ * (partsbaseddetector_amd/model.py: Model.weight_vector).
+ *
+ * pbd_feature_window_max: wmax = the largest kh * kw * flen over the bank (negative: error code).  A record's blocks are
+ * blocks[max_parts], its windows windows[max_parts][wmax]: a smaller window sits at the front of its slot, the tail zero; part slots
+ * beyond the record's nparts hold ids -1 and zeros.
+ * pbd_candidates_features (float windows) / _f64 (double windows; the scalar type must match the handle's, as for
+ * pbd_get_level_features[_f64]: PBD_ERR_STATE otherwise): stand-alone and synchronous — the caller's `count` host records (heads +
+ * locs, max_parts = the handle's) against the features now resident for the handle's current frame plan: after any detect, a latent
+ * or batch detect, pbd_pyramid_*, or pbd_set_level_features.  `level` indexes the plan's levels: on a batch plan frame f's level l
+ * is f * nlevels + l (the pbd_candidates_part_scores convention).  blocks[count * max_parts], windows[count * max_parts * wmax].
+ * pbd_candidates_features_dev: the same kernel into the caller's DEVICE buffers (d_windows in the handle's T, 16-byte aligned), on
+ * the handle's stream: the records are uploaded when it returns, the kernel is enqueued, not finished (synchronise the stream
+ * before reading).  A training loop keeps everything on the GPU that way.  The host variants are this one into a handle-owned
+ * staging buffer of at most PBD_FEATVEC_STAGING_BYTES plus a copy, chunk by chunk; the staging buffer and the record buffer are
+ * allocated on first use and count in pbd_get_footprint.
+ * There is no in-frame opt-in step: a person-model record is 83 KB where its part scores are 624 B, callers select records (NMS,
+ * latent detection) before they want features, and the stand-alone call behind the detect gathers them in one launch.
+ * PBD_ERR_ARG, with nothing written, for a component out of range, an nparts that differs from the model's, a level outside the
+ * plan or not processed by the handle, or an (x, y, mixture) outside its level's cells / the part's mixtures; PBD_ERR_STATE
+ * without resident features (a compact memory plan after min(): the message names the plan) or while a frame is pending;
+ * PBD_ERR_UNSUPPORTED for a pbd_group member.  count == 0 is PBD_OK.                                                              */
+typedef struct pbd_feature_block {
+  int32_t bias_id, def_id, filter_id, kh, kw, reserved;
+  double def[4];
+} pbd_feature_block;                                   /* 56 bytes */
+#define PBD_FEATVEC_STAGING_BYTES ((size_t)16 << 20)
+int pbd_feature_window_max(const pbd_handle* h);
+int pbd_candidates_features(pbd_handle* h, const pbd_candidate_head* heads, const int32_t* locs, int count,
+                            pbd_feature_block* blocks, float* windows);
+int pbd_candidates_features_f64(pbd_handle* h, const pbd_candidate_head* heads, const int32_t* locs, int count,
+                                pbd_feature_block* blocks, double* windows);
+int pbd_candidates_features_dev(pbd_handle* h, const pbd_candidate_head* heads, const int32_t* locs, int count,
+                                pbd_feature_block* d_blocks, void* d_windows);
 
 /* ---- instrumentation --------------------------------------------------------
  * GPU time (ms, hipEvent) of the stages of the last synchronous detect:

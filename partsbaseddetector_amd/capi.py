@@ -55,6 +55,7 @@ EXPORTS = [
     "pbd_get_frame_level_image_raw", "pbd_get_frame_level_features", "pbd_get_frame_level_features_f64",
     "pbd_get_frame_dp_pointers",
     "pbd_latent_mask", "pbd_dp_argbest", "pbd_detect_latent_u8", "pbd_detect_latent_dev_u8", "pbd_detect_batch_latent_u8",
+    "pbd_feature_window_max", "pbd_candidates_features", "pbd_candidates_features_f64", "pbd_candidates_features_dev",
 ]
 PBD_ABI_VERSION = 5
 
@@ -85,6 +86,18 @@ BOX3D_DTYPE = np.dtype([("valid", np.int32), ("x", np.int32), ("y", np.int32), (
                         ("zmin", np.float32), ("zmax", np.float32), ("reserved", np.int32), ("x3d", np.float64),
                         ("y3d", np.float64), ("z3d", np.float64), ("width3d", np.float64), ("height3d", np.float64),
                         ("depth3d", np.float64)])
+
+
+class pbd_feature_block(C.Structure):
+    """one part of a detection's feature vector (include/pbd_c.h): the ids of its bias / deformation / filter blocks, the filter's
+    size and the deformation block -(dx^2, dx, dy^2, dy)"""
+    _fields_ = [("bias_id", C.c_int32), ("def_id", C.c_int32), ("filter_id", C.c_int32), ("kh", C.c_int32), ("kw", C.c_int32),
+                ("reserved", C.c_int32), ("def", C.c_double * 4)]
+
+
+FEATURE_BLOCK_DTYPE = np.dtype([("bias_id", np.int32), ("def_id", np.int32), ("filter_id", np.int32), ("kh", np.int32),
+                                ("kw", np.int32), ("reserved", np.int32), ("def", np.float64, (4,))])
+PBD_FEATVEC_STAGING_BYTES = 16 << 20
 
 
 CLUSTER3D_DTYPE = np.dtype([("cropped", np.int32), ("nclusters", np.int32), ("size", np.int32), ("first", np.int32),
@@ -391,6 +404,40 @@ class Handle:
         self._chk(self.L.pbd_candidates_part_scores(self.h, heads.ctypes.data_as(C.c_void_p), _p(lc, C.c_int32), len(heads),
                                                     _p(out, C.c_double)))
         return out
+
+    # ---- feature vectors of detections (detect.m:272-308) ---------------------------------------------------------------
+    def feature_window_max(self):
+        """pbd_feature_window_max: elements of a window slot, the bank's largest kh * kw * flen"""
+        n = int(self.L.pbd_feature_window_max(self.h))
+        if n < 0:
+            raise PbdError(-n, "pbd_feature_window_max")
+        return n
+
+    def _records(self, heads, locs):
+        heads = np.ascontiguousarray(heads, HEAD_DTYPE)
+        lc = np.zeros((len(heads), self.max_parts, 3), np.int32)
+        if len(heads):   # (an empty selection has no part axis to infer)
+            l = np.asarray(locs, np.int32).reshape(len(heads), -1, 3)
+            lc[:, :l.shape[1]] = l[:, :self.max_parts]
+        return heads, lc
+
+    def candidates_features(self, heads, locs):
+        """pbd_candidates_features[_f64]: (blocks [n, max_parts] FEATURE_BLOCK_DTYPE, windows [n, max_parts, wmax] in the handle's
+        dtype) of the caller's records against the features resident for the handle's frame (level: the plan's level; frame f of
+        a batch plan: f * nlevels + l).  A window is [kh][kw * 32] at the front of its slot."""
+        heads, lc = self._records(heads, locs)
+        blocks = np.zeros((len(heads), self.max_parts), FEATURE_BLOCK_DTYPE)
+        windows = np.zeros((len(heads), self.max_parts, self.feature_window_max()), self.dtype)
+        self._chk(self._fn("pbd_candidates_features")(self.h, heads.ctypes.data_as(C.c_void_p), _p(lc, C.c_int32), len(heads),
+                                                      blocks.ctypes.data_as(C.c_void_p), _p(windows, self._ct)))
+        return blocks, windows
+
+    def candidates_features_dev(self, heads, locs, d_blocks: int, d_windows: int):
+        """pbd_candidates_features_dev: the same into the caller's device buffers (integer device pointers: n * max_parts blocks of 56
+        bytes, n * max_parts * wmax elements of the handle's dtype), on the handle's stream; returns after the launch."""
+        heads, lc = self._records(heads, locs)
+        self._chk(self.L.pbd_candidates_features_dev(self.h, heads.ctypes.data_as(C.c_void_p), _p(lc, C.c_int32), len(heads),
+                                                     C.c_void_p(d_blocks), C.c_void_p(d_windows)))
 
     def close(self):
         if getattr(self, "h", None):

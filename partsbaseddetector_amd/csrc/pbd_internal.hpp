@@ -264,6 +264,11 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   double* h_ps = nullptr;           // [capacity * mp * 3]: pinned
   bool ps_ready = false;            // results of the last collected frame, per frame in the order returned
   std::vector<std::vector<double>> ps_res; std::vector<char> ps_res_on;
+  // feature vectors (pbd_candidates_features*): k_featvec.hip, stand-alone only.  The model table beside k_partscore's, the uploaded
+  // records of a call and the host variants' staging buffer: allocated on first use, held until pbd_destroy
+  struct FvMix* d_fv_mix = nullptr;                // [flat mixtures]
+  char* d_fv_rec = nullptr; size_t fv_rec_cap = 0; // the call's records (bytes)
+  char* d_fv_stage = nullptr;                      // PBD_FEATVEC_STAGING_BYTES: a chunk's blocks, then its windows
   // latent detection (pbd_latent_mask / pbd_dp_argbest / pbd_detect_latent_*): k_latent.hip between pdf and min, and in front of the
   // back-tracking.  The work table, the flags and the block partials belong to the frame plan (built on the first latent use of a
   // plan); the truth / mixture tables are model-lifetime buffers, uploaded per frame in the frame's stream.
@@ -585,6 +590,21 @@ struct PartScoreArgs {
   double* out;                                  // [capacity][mp][3]: app, def, bias; zero beyond nparts
 };
 void launch_partscore(const PartScoreArgs& a, int ts, hipStream_t s);
+// feature vectors (k_featvec.hip)
+struct FvMix { int def, filter, kh, kw; };   // one (part, mixture): its defid, its filter in the CALLER's order and that filter's size
+struct FeatVecArgs {
+  RecordSet in;                                 // (count / cf unused: records rec0 .. rec0 + n - 1 of in.p)
+  int rec0, n;
+  const LevelDev* levels; int nvl;              // the plan's (virtual) levels
+  const char* feat;                             // T: the feature planes, level l at cell_off[l] * flen, [ch][cw][flen]
+  int ncomp, nbias, nfilters;
+  const int* nparts; const int* parent; const int* flat;   // [ncomp]; [ncomp * mp] parent, flat part
+  const int* mix0; const PsMix* mix; const FvMix* fmix;    // [flat parts + 1] first flat mixture; [flat mixtures] x 2
+  int wmax;                                     // elements of a window slot: the bank's largest kh * kw * flen
+  pbd_feature_block* blocks;                    // [n][mp]
+  void* windows;                                // T [n][mp][wmax], 16-byte aligned
+};
+void launch_featvec(const FeatVecArgs& a, int ts, hipStream_t s);
 // object clusters (k_cluster3d.hip)
 size_t cluster3d_slot_bytes(int pcap);
 // src: 0 = xyz floats (pstride, rstride bytes), 4 / 8 = a depth image of float / double

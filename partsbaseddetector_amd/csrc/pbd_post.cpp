@@ -1,7 +1,8 @@
 // pbd_post.cpp — the stages behind back-tracking: candidate sort + NMS (k_cand.hip), depth-consistency pruning
-// (k_zfilter.hip), 3-D boxes (k_box3d.hip), object clusters (k_cluster3d.hip) and per-part scores (k_partscore.hip).  Their handle
-// buffers, their launches behind k_backtrack, the collect's gathering of their results and their C entry points (pbd_set_*,
-// pbd_get_box3d, pbd_get_cluster3d, pbd_get_part_scores, pbd_candidates_*).  pbd_api.cpp calls in through the pbd_i_* functions of pbd_internal.hpp.
+// (k_zfilter.hip), 3-D boxes (k_box3d.hip), object clusters (k_cluster3d.hip), per-part scores (k_partscore.hip) and the stand-alone
+// feature vectors (k_featvec.hip).  Their handle buffers, their launches behind k_backtrack, the collect's gathering of their results
+// and their C entry points (pbd_set_*, pbd_get_box3d, pbd_get_cluster3d, pbd_get_part_scores, pbd_candidates_*).  pbd_api.cpp calls in
+// through the pbd_i_* functions of pbd_internal.hpp.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -287,6 +288,103 @@ static PartScoreArgs ps_args(const pbd_handle* h) {
 static const char* const kPsCompact =
     "part scores: this frame runs the compact memory plan (dp_mode 2, or automatic for large frames), whose min() overwrites the "
     "raw response planes the scores are read from";
+// the range checks of a stand-alone call's records (part scores, feature vectors): nothing of a record that fails is read on the device
+static int check_records(pbd_handle* h, const pbd_candidate_head* heads, const int32_t* locs, int count) {
+  const int mp = h->max_parts;
+  for (int i = 0; i < count; ++i) {
+    const int c = heads[i].component, l = heads[i].level;
+    if (c < 0 || c >= h->md.ncomponents) return fail(h, PBD_ERR_ARG, "component out of range");
+    const int f0 = h->part_offset[c], np = h->part_offset[c + 1] - f0;
+    if (heads[i].nparts != np) return fail(h, PBD_ERR_ARG, "nparts differs from the model's component");
+    if (l < 0 || l >= h->nvl || !h->lv[l].active) return fail(h, PBD_ERR_ARG, "level outside the levels this handle processes");
+    const int32_t* lc = locs + (size_t)i * mp * 3;
+    for (int p = 0; p < np; ++p)
+      if (lc[p * 3] < 0 || lc[p * 3] >= h->lv[l].cw || lc[p * 3 + 1] < 0 || lc[p * 3 + 1] >= h->lv[l].ch || lc[p * 3 + 2] < 0 ||
+          lc[p * 3 + 2] >= h->parts[f0 + p].K)
+        return fail(h, PBD_ERR_ARG, "part location (x, y, mixture) outside its level's cells / the part's mixtures");
+  }
+  return PBD_OK;
+}
+
+// ---- feature vectors (k_featvec.hip) ------------------------------------------------------------------------------------
+// the largest window of the bank in elements, and the table beside k_partscore's: per flat mixture its defid and its filter — the
+// caller's index and the size pbd_get_filter_size answers with (mixed banks keep filterid in their internal order)
+static int fv_wmax(const pbd_handle* h) {
+  int m = h->md.kh * h->md.kw;
+  if (h->mixed) for (size_t n = 0; n < h->fkh.size(); ++n) m = std::max(m, h->fkh[n] * h->fkw[n]);
+  return m * PBD_FLEN;
+}
+static int fv_tables(pbd_handle* h) {
+  int rc = ps_tables(h);
+  if (rc || h->d_fv_mix) return rc;
+  const size_t nm = h->filterid.size();
+  std::vector<int> caller((size_t)h->md.nfilters);
+  for (int n = 0; n < h->md.nfilters; ++n) caller[h->mixed ? h->fperm[n] : n] = n;
+  std::vector<FvMix> mix(nm);
+  for (size_t fm = 0; fm < nm; ++fm) {
+    const int f = h->filterid[fm];
+    mix[fm] = FvMix{h->defid[fm], caller[f], h->mixed ? h->fkh[f] : h->md.kh, h->mixed ? h->fkw[f] : h->md.kw};
+  }
+  if ((rc = model_alloc(h, &h->d_fv_mix, nm))) return rc;
+  HIPCHK(h, hipMemcpy(h->d_fv_mix, mix.data(), sizeof(FvMix) * nm, hipMemcpyHostToDevice));
+  return PBD_OK;
+}
+static const char* const kFvCompact =
+    "feature vectors: this frame runs the compact memory plan (dp_mode 2, or automatic for large frames), whose min() reuses the "
+    "memory of the feature planes the windows are read from";
+// every refusal of the three entry points, in the order of the part scores'; then the tables and the records on the device
+static int fv_begin(pbd_handle* h, const pbd_candidate_head* heads, const int32_t* locs, int count, const void* blocks, const void* windows,
+                    int ts, FeatVecArgs* a) {
+  if (count < 0 || (count > 0 && (!heads || !locs || !blocks || !windows))) return fail(h, PBD_ERR_ARG, "heads / locs / blocks / windows / count");
+  if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "feature vectors: pbd_group members are not supported");
+  if (ts && ts != h->ts) return fail(h, PBD_ERR_STATE, ts == 4 ? "handle is PartsBasedDetector<double>: use the _f64 entry point"
+                                                               : "handle is PartsBasedDetector<float>: use the float entry point");
+  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (h->fw == 0) return fail(h, PBD_ERR_STATE, "feature vectors: no frame planned");
+  if (!h->have_feat) return fail(h, PBD_ERR_STATE, h->compact ? kFvCompact : "feature vectors: features not computed");
+  int rc = check_records(h, heads, locs, count);
+  if (rc || count == 0) return rc;
+  ON_DEVICE(h);
+  if ((rc = fv_tables(h))) return rc;
+  const int mp = h->max_parts;
+  const size_t st = h->cand_stride, n = (size_t)count;
+  if ((rc = model_grow(h, &h->d_fv_rec, h->fv_rec_cap, st * n))) return rc;
+  std::vector<char> rec(st * n, 0);
+  for (size_t i = 0; i < n; ++i) pbd_rec_put(rec.data() + st * i, mp, heads, nullptr, locs, i);
+  HIPCHK(h, hipMemcpyAsync(h->d_fv_rec, rec.data(), st * n, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));   // (`rec` goes out of scope; earlier work on the stream — the frame — is done too)
+  FeatVecArgs& A = *a;
+  A = FeatVecArgs{};
+  A.in.p = h->d_fv_rec; A.in.stride = st; A.in.mp = mp; A.in.capacity = count;
+  A.levels = h->d_levels; A.nvl = h->nvl; A.feat = h->d_feat;
+  A.ncomp = h->md.ncomponents; A.nbias = (int)h->biasw.size(); A.nfilters = h->md.nfilters;
+  A.nparts = h->d_nparts; A.parent = h->d_parent; A.flat = h->d_flat;
+  A.mix0 = h->d_ps_mix0; A.mix = h->d_ps_mix; A.fmix = h->d_fv_mix;
+  A.wmax = fv_wmax(h);
+  return PBD_OK;
+}
+// the host variants: chunks of records through the staging buffer — a chunk's blocks, then (128-byte aligned) its windows
+static int fv_host(pbd_handle* h, const pbd_candidate_head* heads, const int32_t* locs, int count, pbd_feature_block* blocks, void* windows, int ts) {
+  FeatVecArgs a;
+  int rc = fv_begin(h, heads, locs, count, blocks, windows, ts, &a);
+  if (rc || count == 0) return rc;
+  const size_t mp = (size_t)h->max_parts, bbytes = mp * sizeof(pbd_feature_block), wbytes = mp * a.wmax * h->ts;
+  const size_t chunk = std::max<size_t>(1, (PBD_FEATVEC_STAGING_BYTES - 128) / (bbytes + wbytes));
+  if (!h->d_fv_stage && (rc = model_alloc(h, &h->d_fv_stage, std::max<size_t>(PBD_FEATVEC_STAGING_BYTES, bbytes + wbytes + 128)))) return rc;
+  char* d_win = h->d_fv_stage + (chunk * bbytes + 127) / 128 * 128;
+  for (size_t r0 = 0; r0 < (size_t)count; r0 += chunk) {
+    const size_t n = std::min(chunk, (size_t)count - r0);
+    a.rec0 = (int)r0; a.n = (int)n;
+    a.blocks = (pbd_feature_block*)h->d_fv_stage; a.windows = d_win;
+    Scratch s(h);
+    launch_featvec(a, h->ts, h->stream);
+    s.launched();
+    s.down((char*)blocks + r0 * bbytes, h->d_fv_stage, n * bbytes);
+    s.down((char*)windows + r0 * wbytes, d_win, n * wbytes);
+    if ((rc = s.finish("feature vectors: "))) return rc;   // (the next chunk overwrites the staging buffer)
+  }
+  return PBD_OK;
+}
 
 // ---- behind the back-tracking ---------------------------------------------------------------------------------------------
 // the frame's final records (behind the depth pruning and the candidate filter), where the launches behind them read them
@@ -827,22 +925,10 @@ int pbd_candidates_part_scores(pbd_handle* h, const pbd_candidate_head* heads, c
   if (h->fw == 0) return fail(h, PBD_ERR_STATE, "part scores: no frame planned");
   if (!h->have_resp) return fail(h, PBD_ERR_STATE, h->compact ? kPsCompact : "part scores: responses not computed");
   const int mp = h->max_parts;
-  for (int i = 0; i < count; ++i) {
-    const int c = heads[i].component, l = heads[i].level;
-    if (c < 0 || c >= h->md.ncomponents) return fail(h, PBD_ERR_ARG, "component out of range");
-    const int f0 = h->part_offset[c], np = h->part_offset[c + 1] - f0;
-    if (heads[i].nparts != np) return fail(h, PBD_ERR_ARG, "nparts differs from the model's component");
-    if (l < 0 || l >= h->nvl || !h->lv[l].active) return fail(h, PBD_ERR_ARG, "level outside the levels this handle processes");
-    const int32_t* lc = locs + (size_t)i * mp * 3;
-    for (int p = 0; p < np; ++p)
-      if (lc[p * 3] < 0 || lc[p * 3] >= h->lv[l].cw || lc[p * 3 + 1] < 0 || lc[p * 3 + 1] >= h->lv[l].ch || lc[p * 3 + 2] < 0 ||
-          lc[p * 3 + 2] >= h->parts[f0 + p].K)
-        return fail(h, PBD_ERR_ARG, "part location (x, y, mixture) outside its level's cells / the part's mixtures");
-  }
-  if (count == 0) return PBD_OK;
+  int rc = check_records(h, heads, locs, count);
+  if (rc || count == 0) return rc;
   ON_DEVICE(h);
-  int rc = ps_tables(h);
-  if (rc) return rc;
+  if ((rc = ps_tables(h))) return rc;
   const size_t st = h->cand_stride, n = (size_t)count, m3 = (size_t)mp * 3;
   std::vector<char> rec(st * n, 0);
   for (size_t i = 0; i < n; ++i) pbd_rec_put(rec.data() + st * i, mp, heads, nullptr, locs, i);
@@ -858,6 +944,30 @@ int pbd_candidates_part_scores(pbd_handle* h, const pbd_candidate_head* heads, c
   }
   s.down(out, a.out, sizeof(double) * n * m3);
   return s.finish("part scores: ");
+}
+
+// ---- feature vectors (k_featvec.hip) ------------------------------------------------------------------------------------
+int pbd_feature_window_max(const pbd_handle* h) { return h ? fv_wmax(h) : -PBD_ERR_ARG; }
+
+int pbd_candidates_features(pbd_handle* h, const pbd_candidate_head* heads, const int32_t* locs, int count, pbd_feature_block* blocks,
+                            float* windows) {
+  return h ? fv_host(h, heads, locs, count, blocks, windows, 4) : PBD_ERR_ARG;
+}
+int pbd_candidates_features_f64(pbd_handle* h, const pbd_candidate_head* heads, const int32_t* locs, int count, pbd_feature_block* blocks,
+                                double* windows) {
+  return h ? fv_host(h, heads, locs, count, blocks, windows, 8) : PBD_ERR_ARG;
+}
+int pbd_candidates_features_dev(pbd_handle* h, const pbd_candidate_head* heads, const int32_t* locs, int count, pbd_feature_block* d_blocks,
+                                void* d_windows) {
+  if (!h) return PBD_ERR_ARG;
+  if (count > 0 && ((uintptr_t)d_windows % 16 || (uintptr_t)d_blocks % 8)) return fail(h, PBD_ERR_ARG, "feature vectors: d_windows 16-byte, d_blocks 8-byte aligned");
+  FeatVecArgs a;
+  int rc = fv_begin(h, heads, locs, count, d_blocks, d_windows, 0, &a);
+  if (rc || count == 0) return rc;
+  a.rec0 = 0; a.n = count; a.blocks = d_blocks; a.windows = d_windows;
+  launch_featvec(a, h->ts, h->stream);
+  LAUNCHCHK(h, "feature vectors");
+  return PBD_OK;
 }
 
 }  // extern "C"

@@ -413,3 +413,11 @@ class PartsBasedDetector:
         (in [0, 1)); mix[p] >= 0 fixes part p's mixture (-1 / None: free); component = -1 searches all.  Returns one Candidate or
         an empty list; the model's threshold plays no part.  With setPartScores on, the Candidate carries its parts' scores."""
         return Candidate._unpack(*self.handle.detect_latent(im, truth, overlap, mix, component), self._ps())
+
+    def features(self, candidates: List[Candidate]):
+        """The feature vectors of `candidates` (what detect() or detect_latent() of the LAST frame returned, or a selection of them):
+        (blocks [n, max_parts] capi.FEATURE_BLOCK_DTYPE, windows [n, max_parts, wmax] in the handle's dtype), gathered on the GPU
+        from the frame's resident feature planes — the ex.blocks of matlab/detection/detect.m:272-308.  model.dense_feature_vectors
+        scatters them into Model.weight_vector()'s order."""
+        heads, _, locs = Candidate._pack(candidates)
+        return self.handle.candidates_features(heads, locs)

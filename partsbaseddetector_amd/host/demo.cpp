@@ -1,5 +1,5 @@
 // demo.cpp — the reference's canonical caller (src/demo.cpp:55-118) against the MI355X path:
-//   pbd_demo model.bin image.raw width height channels [stagewise|double|stagewise-double]
+//   pbd_demo model.bin image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE]
 //   pbd_demo model.bin image.raw width height channels perturb-features <responses-out.bin>
 //   pbd_demo model.bin image.raw width height channels oracle-responses <responses-in.bin>
 // deserialize -> distributeModel -> detect -> Candidate::sort, then prints the candidates (the
@@ -20,7 +20,8 @@ using namespace pbd;
 //             from pdf(), and the tables min() returns are edited before argmin() (a root score raised, part 1's x
 //             pointer at that cell redirected): the candidates must be those of the edited tables.
 template <typename T>
-static void run(Model& model, const Mat& im, bool stagewise, int special = 0, const char* io_file = nullptr, bool part_scores = false, int pad = 0) {
+static void run(Model& model, const Mat& im, bool stagewise, int special = 0, const char* io_file = nullptr, bool part_scores = false, int pad = 0,
+                const char* features_file = nullptr) {
   PartsBasedDetector<T> pbd(0, PBD_CONV_EXACT);
   pbd.setPartScores(part_scores);
   pbd.setBoundaryPad(pad);
@@ -81,6 +82,36 @@ static void run(Model& model, const Mat& im, bool stagewise, int special = 0, co
   }
   printf("Number of candidates: %ld\n", (long)candidates.size());
   Candidate::sort(candidates);
+  if (features_file) {   // --features FILE: the sorted records' dense feature vectors, one row of doubles each, in the order
+                         // [biasw | defw (ndefs x 4) | the filters back to back] (w . row = the record's score); header: rows, columns (int64)
+    std::vector<pbd_feature_block> blocks;
+    std::vector<T> windows;
+    pbd.features(candidates, blocks, windows);
+    const size_t mp = candidates.empty() ? 0 : blocks.size() / candidates.size(), wmax = blocks.empty() ? 0 : windows.size() / blocks.size();
+    const size_t nb = model.bias().size(), nd = model.def().size();
+    std::vector<size_t> foff;
+    size_t dim = nb + 4 * nd;
+    for (const Mat& f : model.filters()) { foff.push_back(dim); dim += (size_t)f.rows * f.cols; }
+    FILE* f = fopen(features_file, "wb");
+    if (!f) { fprintf(stderr, "cannot open %s\n", features_file); exit(6); }
+    const long long hdr[2] = {(long long)candidates.size(), (long long)dim};
+    fwrite(hdr, sizeof(long long), 2, f);
+    std::vector<double> row(dim);
+    for (size_t i = 0; i < candidates.size(); ++i) {
+      std::fill(row.begin(), row.end(), 0.0);
+      for (size_t p = 0; p < mp; ++p) {
+        const pbd_feature_block& b = blocks[i * mp + p];
+        if (b.bias_id < 0) continue;
+        row[b.bias_id] += 1.0;
+        if (b.def_id >= 0) for (int k = 0; k < 4; ++k) row[nb + 4 * (size_t)b.def_id + k] += b.def[k];
+        const T* win = windows.data() + (i * mp + p) * wmax;
+        for (size_t k = 0; k < (size_t)b.kh * b.kw * model.flen(); ++k) row[foff[b.filter_id] + k] += (double)win[k];
+      }
+      fwrite(row.data(), sizeof(double), dim, f);
+    }
+    fclose(f);
+    printf("Features: %ld x %ld\n", (long)candidates.size(), (long)dim);
+  }
   for (const Candidate& c : candidates) {
     printf("%.9g %d %d", c.score(), c.component(), c.level);
     for (const Rect& r : c.parts()) printf(" %d,%d,%d,%d", r.x, r.y, r.width, r.height);
@@ -99,6 +130,7 @@ static void run(Model& model, const Mat& im, bool stagewise, int special = 0, co
 
 int main(int argc, char** argv) {
   bool part_scores = false;   // --part-scores (anywhere): per detection, the re-scored total, the root score and the weakest part
+  const char* features_file = nullptr;   // --features FILE (anywhere): the detections' dense feature vectors, written to FILE
   int pad = 0;                // --pad N (anywhere): N cells of boundary padding around every pyramid level (0: off)
   for (int i = 1; i < argc; ++i)
     if (std::string(argv[i]) == "--pad") {
@@ -109,13 +141,19 @@ int main(int argc, char** argv) {
       for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
       argc -= 2; --i;
     } else
+    if (std::string(argv[i]) == "--features") {
+      if (i + 1 >= argc || !*argv[i + 1]) { printf("--features FILE\n"); exit(-1); }
+      features_file = argv[i + 1];
+      for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+      argc -= 2; --i;
+    } else
     if (std::string(argv[i]) == "--part-scores") {
       part_scores = true;
       for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
       --argc; --i;
     }
   if (argc < 6 || argc > 8) {
-    printf("Usage: pbd_demo model_file image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N]\n");
+    printf("Usage: pbd_demo model_file image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE]\n");
     exit(-1);
   }
   // determine the type of model to read (src/demo.cpp:63-82)
@@ -141,8 +179,9 @@ int main(int argc, char** argv) {
   const bool stagewise = special || mode.find("stagewise") != std::string::npos;
   try {
     if (part_scores && stagewise) { printf("--part-scores: the fused detect() only\n"); exit(-1); }
-    if (mode.find("double") != std::string::npos) run<double>(model, im, stagewise, 0, nullptr, part_scores, pad);
-    else run<float>(model, im, stagewise, special, special ? argv[7] : nullptr, part_scores, pad);
+    if (features_file && special) { printf("--features: not with %s\n", mode.c_str()); exit(-1); }
+    if (mode.find("double") != std::string::npos) run<double>(model, im, stagewise, 0, nullptr, part_scores, pad, features_file);
+    else run<float>(model, im, stagewise, special, special ? argv[7] : nullptr, part_scores, pad, features_file);
   } catch (const Exception& e) {
     printf("error %d: %s\n", e.code, e.what());
     return 1;

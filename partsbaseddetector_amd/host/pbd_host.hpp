@@ -747,6 +747,28 @@ class PartsBasedDetector {
     append_candidates(candidates, heads, boxes, locs, n, mp);
     attach_part_scores(candidates, n, mp);
   }
+  // The feature vectors of `candidates` — records of the LAST frame's detect() / detectLatent(), or a selection of them — gathered by
+  // the GPU from the frame's resident feature planes: what matlab/detection/detect.m:272-308 collects as ex.blocks.  blocks[i *
+  // max_parts + p] (ids -1 beyond the record's parts), windows[(i * max_parts + p) * wmax ...]: part p's HOG window, [kh][kw * flen] at
+  // the front of its slot of wmax = pbd_feature_window_max() elements.  include/pbd_c.h, pbd_feature_block.
+  typedef pbd_feature_block FeatureBlock;
+  void features(const vectorCandidate& candidates, std::vector<FeatureBlock>& blocks, std::vector<T>& windows) {
+    if (!dev_) throw Exception(PBD_ERR_STATE, "features() before distributeModel()");
+    const size_t n = candidates.size(), mp = (size_t)pbd_max_parts(dev_->h), wmax = (size_t)pbd_feature_window_max(dev_->h);
+    std::vector<pbd_candidate_head> heads(n);
+    std::vector<int32_t> locs(n * mp * 3, 0);
+    for (size_t i = 0; i < n; ++i) {
+      const Candidate& c = candidates[i];
+      heads[i].score = c.score(); heads[i].component = c.component(); heads[i].level = c.level; heads[i].nparts = (int32_t)c.parts().size();
+      std::copy(c.locs.begin(), c.locs.begin() + std::min(c.locs.size(), mp * 3), locs.begin() + i * mp * 3);
+    }
+    blocks.assign(n * mp, FeatureBlock());
+    windows.assign(n * mp * wmax, (T)0);
+    dev_->check(features_entry(heads.data(), locs.data(), (int)n, blocks.data(), windows.data()));
+  }
+ private:
+  int features_entry(const pbd_candidate_head* hd, const int32_t* lc, int n, FeatureBlock* b, float* w) { return pbd_candidates_features(dev_->h, hd, lc, n, b, w); }
+  int features_entry(const pbd_candidate_head* hd, const int32_t* lc, int n, FeatureBlock* b, double* w) { return pbd_candidates_features_f64(dev_->h, hd, lc, n, b, w); }
 };
 
 inline void Candidate::sort(std::vector<Candidate>& c) {

@@ -188,6 +188,23 @@ class Model:
         with open(path, "w") as f:
             f.write("\n".join(o) + "\n")
 
+    def feature_layout(self) -> dict:
+        """Where each block of a detection's feature vector (pbd_feature_block) sits in the dense vector, and in weight_vector():
+        [biasw | defw (ndefs x 4) | the filters back to back, each [kh][kw * flen]].  -> dict(bias=0, deform=nbias,
+        filters=[nfilters] first element of each filter, size=total length).  The MATLAB ancestor addresses its blocks through the
+        `.i` offsets of its model struct; the reference's C++ Model carries none of them, so this order is the port's own."""
+        nb = int(np.asarray(self.biasw).size)
+        nd = int(np.asarray(self.defw).size) // 4
+        sizes = [int(np.asarray(f).size) for f in self.filtersw]
+        off = nb + 4 * nd + np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        return dict(bias=0, deform=nb, filters=off[:-1], size=int(off[-1]))
+
+    def weight_vector(self) -> np.ndarray:
+        """The model's weights as one float64 vector in feature_layout()'s order: w . x of a detection's dense feature vector
+        (dense_feature_vectors) is its score."""
+        return np.concatenate([np.asarray(self.biasw, np.float32).ravel(), np.asarray(self.defw, np.float32).ravel()] +
+                              [np.asarray(f, np.float32).ravel() for f in self.filtersw]).astype(np.float64)
+
     def to_desc(self) -> pbd_model_desc:
         """Flatten into the C ABI descriptor (arrays kept alive on self).  Uniform banks only (pbd_create)."""
         kh = self.filtersw[0].shape[0]
@@ -240,6 +257,40 @@ class Model:
         d.part_offset, d.parentid, d.mix_offset = ip(arrs[0]), ip(arrs[1]), ip(arrs[2])
         d.filterid, d.defid, d.biasid = ip(arrs[3]), ip(arrs[4]), ip(arrs[5])
         return d
+
+
+def dense_feature_vectors(model: Model, blocks, windows) -> np.ndarray:
+    """[n, feature_layout()["size"]] float64: every record's blocks (pbd_feature_block [n, max_parts]) and windows ([n, max_parts,
+    wmax]) scatter-added into Model.feature_layout()'s order — 1 at bias_id, def at its def_id, the window at its filter_id.  Part
+    slots with ids -1 (beyond the record's parts) are skipped.
+    Asserts what matlab/learning/qp_write.m:34-35 asserts: no block index repeats within a record.  That fails for a model that uses
+    one filter id (or one def / bias id) for two parts of one component — the blocks would have to be summed, which the QP's
+    sparse format does not do."""
+    lay = model.feature_layout()
+    sizes = model.filter_sizes()
+    blocks = np.asarray(blocks)
+    n, mp = blocks.shape
+    windows = np.asarray(windows).reshape(n, mp, -1)
+    out = np.zeros((n, lay["size"]), np.float64)
+    for i in range(n):
+        seen = set()
+        for p in range(mp):
+            b = blocks[i, p]
+            if b["bias_id"] < 0:
+                continue
+            ids = [("bias", int(b["bias_id"])), ("filter", int(b["filter_id"]))] + ([("def", int(b["def_id"]))] if b["def_id"] >= 0 else [])
+            assert not seen.intersection(ids), f"record {i}: a block index repeats within the record ({sorted(seen.intersection(ids))})"
+            seen.update(ids)
+            out[i, lay["bias"] + int(b["bias_id"])] += 1.0
+            if b["def_id"] >= 0:
+                o = lay["deform"] + 4 * int(b["def_id"])
+                out[i, o:o + 4] += np.asarray(b["def"], np.float64)
+            f = int(b["filter_id"])
+            kh, kw = int(sizes[f, 0]), int(sizes[f, 1])
+            assert (kh, kw) == (int(b["kh"]), int(b["kw"])), "block size differs from the model's filter"
+            o = int(lay["filters"][f])
+            out[i, o:o + kh * kw * model.flen] += windows[i, p, :kh * kw * model.flen].astype(np.float64)
+    return out
 
 
 # PARSE-style 26-part skeleton, 0-based parents (any tree with parent < child is valid)
