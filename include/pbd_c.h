@@ -168,7 +168,8 @@ int pbd_abi_version(void);
  * points pbd_set_part_scores, pbd_get_part_scores and pbd_candidates_part_scores (with the struct pbd_part_score); and the latent
  * detection entry points pbd_latent_mask, pbd_dp_argbest, pbd_detect_latent_u8, pbd_detect_latent_dev_u8 and
  * pbd_detect_batch_latent_u8; and the feature-vector entry points pbd_feature_window_max, pbd_candidates_features,
- * pbd_candidates_features_f64 and pbd_candidates_features_dev (with the struct pbd_feature_block).                               */
+ * pbd_candidates_features_f64 and pbd_candidates_features_dev (with the struct pbd_feature_block); and the part-wise NMS entry
+ * points pbd_candidates_nms_parts, pbd_set_candidate_nms, pbd_group_set_candidate_nms and pbd_candidates_filter_parts.            */
 
 /* ---- output record: include/Candidate.hpp:56-111 --------------------------
  * One candidate = head + max_parts boxes (x, y, width, height as cv::Rect)
@@ -444,6 +445,49 @@ int pbd_group_set_candidate_filter(pbd_group* g, int mode, float overlap);
  * mode 2, boxes NULL or im_w / im_h <= 0 in mode 2.  boxes / locs may be NULL in mode 1.  Synchronous.                  */
 int pbd_candidates_filter(pbd_handle* h, int mode, float overlap, int im_w, int im_h, pbd_candidate_head* heads,
                           int32_t* boxes, int32_t* locs, int count, int* kept);
+
+/* ---- part-wise overlap NMS: matlab/detection/nms.m, what testmodel.m:15 runs behind every detect as nms(box, 0.3) ---------
+ * A different rule from Candidate::nonMaximaSuppression above: detections are compared part by part and by the box covering
+ * all parts, the intersection is divided by the KEPT detection's area, and the list is first cut to the `top` best.
+ * Input: records in a given order (sorted by the caller, or by the device step), overlap (finite), top >= 0.
+ *  1. Cap (nms.m:18-22): if top > 0 and count > top, only the first `top` records take part; the rest are dropped.
+ *  2. Rectangles: a record with nparts = P has rectangles r = 0 .. P-1, its part boxes (x, y, w, h), and rectangle P, the
+ *     covering box.  Coordinates are int32, their sums and differences 64-bit integers, so junk coordinates of hand-made records
+ *     do not overflow.  A box with w <= 0 or h <= 0 is empty: its area is 0 and it meets nothing.  The covering box is
+ *     (min x, min y, max(x + w), max(y + h)) over the non-empty part boxes, empty if there are none.  area = w * h (nms.m:35,42
+ *     with x2 = x + w - 1); inter(a, b) = max(0, min(ax1, bx1) - max(ax0, bx0)) * max(0, ... y ...).  Both products are formed
+ *     as (double)w * (double)h: the 64-bit product converted to double wherever that product fits 64 bits, and defined beyond.
+ *  3. Greedy loop (nms.m:53-70): walk the records in order; a record not yet rejected is kept.  After keeping i, every later
+ *     undecided record j is rejected iff for some rectangle — the part rectangles r < min(P_i, P_j), or the two covering boxes —
+ *     inter(i_r, j_r) / area(i_r) > (double)overlap, in double.  The divisor is the KEPT record's area; 0 / 0 is NaN and rejects
+ *     nothing, as MATLAB's max skips NaN.
+ *  4. Output: the kept records in order, *kept = their number.
+ * Deviations from nms.m: exactly tied scores keep the order of this library's sort (nms.m's order among ties depends on its
+ * emission order and on whether the cap fired); records of components with different part counts compare their common leading
+ * parts (nms.m assumes one part count); a kept record always leaves the list (nms.m loops forever for overlap >= 1).
+ * Hence overlap >= 1 keeps everything under the cap, and with a negative overlap a kept record rejects every later record
+ * that shares a rectangle index with one of its non-empty rectangles (0 / area = 0 > overlap).  Nothing is special-cased.
+ * Pure host code, in place, like the two functions above.  PBD_ERR_ARG: heads / boxes / kept NULL, count < 0, max_parts <= 0,
+ * top < 0, a non-finite overlap, nparts outside 0..max_parts.                                                              */
+int pbd_candidates_nms_parts(pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int count, int max_parts,
+                             float overlap, int top, int* kept);
+/* What the NMS of PBD_CAND_SORT_NMS is, for frames enqueued afterwards: PBD_NMS_PAINTED (default) = nonMaximaSuppression as
+ * above; PBD_NMS_PARTS = the rule above with the overlap of pbd_set_candidate_filter and this `top` (1000 reproduces nms.m,
+ * 0 = no cap; PAINTED ignores it).  With PARTS every whole-path entry point (single, _dev, enqueue + collect, pbd_detect_image,
+ * the batch family, rgbd, latent; the group's two) returns per frame exactly pbd_candidates_sort then pbd_candidates_nms_parts
+ * of its RAW output; capacity errors as with the painted NMS.  The other modes launch what they launched before.
+ * PBD_ERR_ARG: unknown kind, top < 0; PBD_ERR_STATE: a frame is pending, or the handle is a group member (set it on the
+ * group).  A captured graph is dropped and captured again.                                                                */
+enum { PBD_NMS_PAINTED = 0, PBD_NMS_PARTS = 1 };
+int pbd_set_candidate_nms(pbd_handle* h, int kind, int top);
+/* every member; the level-sharded pbd_group_detect_u8 filters the union of the members' records on member 0          */
+int pbd_group_set_candidate_nms(pbd_group* g, int kind, int top);
+/* Stand-alone: the caller's `count` host records (max_parts = the handle's) through the same device kernels (the sort of
+ * k_cand_filter, ties broken by input position, then k_cand_parts), in place: bit-identical to pbd_candidates_sort then
+ * pbd_candidates_nms_parts(overlap, top).  PBD_ERR_ARG: non-finite scores or overlap, nparts outside 0..max_parts, boxes
+ * NULL, top < 0.  Synchronous.                                                                                          */
+int pbd_candidates_filter_parts(pbd_handle* h, float overlap, int top, pbd_candidate_head* heads, int32_t* boxes,
+                                int32_t* locs, int count, int* kept);
 
 /* ---- depth-consistency pruning: SearchSpacePruning<T>::filterCandidatesByDepth (src/SearchSpacePruning.cpp:73-94) -------
  * The reference's detect(im, depth, candidates) has the call commented out (src/PartsBasedDetector.cpp:91-93, zfactor 0.03);

@@ -23,6 +23,7 @@ PBD_GATHER_AUTO, PBD_GATHER_HOST, PBD_GATHER_RCCL = 0, 1, 2
 PBD_CONV_AUTO, PBD_CONV_EXACT, PBD_CONV_MFMA, PBD_CONV_SPLIT, PBD_CONV_SPLIT_F16 = 0, 1, 2, 3, 4
 PBD_SCALAR_F32, PBD_SCALAR_F64 = 0, 1
 PBD_CAND_RAW, PBD_CAND_SORT, PBD_CAND_SORT_NMS = 0, 1, 2   # pbd_set_candidate_filter: detect's output / Candidate::sort / sort + NMS
+PBD_NMS_PAINTED, PBD_NMS_PARTS = 0, 1   # pbd_set_candidate_nms: the NMS of PBD_CAND_SORT_NMS — Candidate::nonMaximaSuppression / nms.m's part-wise rule
 PBD_DEPTH_8U, PBD_DEPTH_16U, PBD_DEPTH_32F, PBD_DEPTH_64F = 0, 2, 5, 6          # cv::Mat::depth() (src/HOGFeatures.cpp:136-146)
 DEPTH_OF = {np.dtype(np.uint8): PBD_DEPTH_8U, np.dtype(np.uint16): PBD_DEPTH_16U, np.dtype(np.float32): PBD_DEPTH_32F,
             np.dtype(np.float64): PBD_DEPTH_64F}
@@ -56,6 +57,7 @@ EXPORTS = [
     "pbd_get_frame_dp_pointers",
     "pbd_latent_mask", "pbd_dp_argbest", "pbd_detect_latent_u8", "pbd_detect_latent_dev_u8", "pbd_detect_batch_latent_u8",
     "pbd_feature_window_max", "pbd_candidates_features", "pbd_candidates_features_f64", "pbd_candidates_features_dev",
+    "pbd_candidates_nms_parts", "pbd_set_candidate_nms", "pbd_group_set_candidate_nms", "pbd_candidates_filter_parts",
 ]
 PBD_ABI_VERSION = 5
 
@@ -154,7 +156,7 @@ class Handle:
 
     def __init__(self, model, device=0, conv_mode=PBD_CONV_AUTO, max_candidates=4096, dt_correct_ptr=0,
                  level_begin=0, level_end=0, dp_groups=0, dtype=np.float32, graph=0, dp_mode=0, nms_sz=0, sized=False,
-                 cand_filter=None):
+                 cand_filter=None, cand_nms=None):
         """dtype: np.float32 = PartsBasedDetector<float>, np.float64 = PartsBasedDetector<double>.
         nms_sz > 0: score-map NMS of the root planes on the device in front of the back-tracking (pbd_options.reserved[0]).
         dp_mode: 0 = messages folded by the parent's x pass where the model allows it (default), 1 = the
@@ -162,7 +164,8 @@ class Handle:
         A model whose filters differ in size is created through pbd_create_sized, a uniform one through pbd_create
         (sized=True: pbd_create_sized for any model).
         cand_filter=(mode, overlap): pbd_set_candidate_filter — every detect returns Candidate::sort (PBD_CAND_SORT) or sort +
-        nonMaximaSuppression(overlap) (PBD_CAND_SORT_NMS) of its output, computed on the GPU."""
+        nonMaximaSuppression(overlap) (PBD_CAND_SORT_NMS) of its output, computed on the GPU.
+        cand_nms=(kind, top): pbd_set_candidate_nms — what that NMS is (PBD_NMS_PARTS: matlab/detection/nms.m after a cut to `top`)."""
         self.L = lib()
         self.model = model
         # a size per filter (pbd_create_sized) only where the bank is mixed: uniform banks keep pbd_create
@@ -193,6 +196,24 @@ class Handle:
         self.conv_mode = self.L.pbd_get_conv_mode(self.h)      # what PBD_CONV_AUTO resolved to
         if cand_filter is not None:
             self.set_candidate_filter(*cand_filter)
+        if cand_nms is not None:
+            self.set_candidate_nms(*cand_nms)
+
+    def set_candidate_nms(self, kind, top=0):
+        """pbd_set_candidate_nms: PBD_NMS_PAINTED / PBD_NMS_PARTS (top: 1000 = nms.m's cut, 0 = none) for the frames enqueued from now on."""
+        self._chk(self.L.pbd_set_candidate_nms(self.h, int(kind), int(top)))
+
+    def candidates_filter_parts(self, heads, boxes, locs, overlap=0.3, top=1000):
+        """pbd_candidates_filter_parts: sort + nms.m's part-wise NMS of the records through the device kernels; returns the kept
+        (heads, boxes, locs)."""
+        heads = np.ascontiguousarray(heads, HEAD_DTYPE).copy()
+        boxes = None if boxes is None else np.ascontiguousarray(boxes, np.int32).copy()
+        locs = None if locs is None else np.ascontiguousarray(locs, np.int32).copy()
+        kept = C.c_int(0)
+        self._chk(self.L.pbd_candidates_filter_parts(self.h, C.c_float(overlap), int(top), heads.ctypes.data_as(C.c_void_p),
+                                                     _p(boxes, C.c_int32), _p(locs, C.c_int32), len(heads), C.byref(kept)))
+        k = kept.value
+        return heads[:k], None if boxes is None else boxes[:k], None if locs is None else locs[:k]
 
     def set_candidate_filter(self, mode, overlap=0.0):
         """pbd_set_candidate_filter: PBD_CAND_RAW / PBD_CAND_SORT / PBD_CAND_SORT_NMS for the frames enqueued from now on."""
@@ -860,7 +881,7 @@ class Group:
     """pbd_group: one process driving several GPUs (include/pbd_c.h).  devices may repeat an ordinal."""
 
     def __init__(self, model, devices, gather=PBD_GATHER_AUTO, conv_mode=PBD_CONV_AUTO, max_candidates=4096,
-                 dtype=np.float32, graph=0, nms_sz=0, cand_filter=None):
+                 dtype=np.float32, graph=0, nms_sz=0, cand_filter=None, cand_nms=None):
         self.L = lib()
         self.model = model
         self.fsize = None
@@ -890,6 +911,12 @@ class Group:
         self.max_parts = self.L.pbd_max_parts(C.c_void_p(self.L.pbd_group_member(self.g, 0)))
         if cand_filter is not None:
             self.set_candidate_filter(*cand_filter)
+        if cand_nms is not None:
+            self.set_candidate_nms(*cand_nms)
+
+    def set_candidate_nms(self, kind, top=0):
+        """pbd_group_set_candidate_nms: every member (Handle.set_candidate_nms); detect() applies it to the union of the members' levels."""
+        self._chk(self.L.pbd_group_set_candidate_nms(self.g, int(kind), int(top)))
 
     def set_candidate_filter(self, mode, overlap=0.0):
         """pbd_group_set_candidate_filter: every member; detect() filters the union of the members' levels."""
@@ -967,3 +994,16 @@ def candidates_nms(heads, boxes, locs, im_w, im_h, overlap=0.0):
     if rc:
         raise PbdError(rc, "pbd_candidates_nms")
     return heads[:kept.value], boxes[:kept.value], locs[:kept.value]
+
+
+def candidates_nms_parts(heads, boxes, locs, overlap=0.3, top=1000):
+    """matlab/detection/nms.m on sorted records (pbd_candidates_nms_parts, include/pbd_c.h) — host code inside the library."""
+    heads, boxes = heads.copy(), np.ascontiguousarray(boxes, np.int32).copy()
+    locs = None if locs is None else np.ascontiguousarray(locs, np.int32).copy()
+    mp = boxes.shape[1]
+    kept = C.c_int(0)
+    rc = lib().pbd_candidates_nms_parts(heads.ctypes.data_as(C.c_void_p), _p(boxes, C.c_int32), _p(locs, C.c_int32),
+                                        len(heads), mp, C.c_float(overlap), int(top), C.byref(kept))
+    if rc:
+        raise PbdError(rc, "pbd_candidates_nms_parts")
+    return heads[:kept.value], boxes[:kept.value], None if locs is None else locs[:kept.value]

@@ -61,6 +61,7 @@ struct pbd_group {
   size_t block = 0;                    // bytes of one {count, pad, first records} block
   int shard_w = 0, shard_h = 0, shard_cn = 0;   // geometry the members' level sets were computed for (0: all levels)
   int cand_mode = PBD_CAND_RAW; float cand_overlap = 0.f;   // pbd_group_set_candidate_filter
+  int cand_nms = PBD_NMS_PAINTED; int cand_top = 0;         // pbd_group_set_candidate_nms
   // scratch of one gather
   std::vector<int> found;
   std::vector<std::vector<char>> extra;   // records beyond the block (rare), per member
@@ -274,6 +275,25 @@ int pbd_group_set_candidate_filter(pbd_group* g, int mode, float overlap) {
   g->cand_overlap = overlap;
   return PBD_OK;
 }
+// every member gets the setting (checked first: nothing changes unless all accept); pbd_group_detect_u8 applies it to the union
+int pbd_group_set_candidate_nms(pbd_group* g, int kind, int top) {
+  if (!g) return PBD_ERR_ARG;
+  if ((kind != PBD_NMS_PAINTED && kind != PBD_NMS_PARTS) || top < 0) return gfail(g, PBD_ERR_ARG, "candidate NMS: kind PBD_NMS_PAINTED / _PARTS, top >= 0");
+  for (pbd_handle* h : g->m)
+    if (h->pending) return gfail(g, PBD_ERR_STATE, "a frame is in flight");
+  for (size_t i = 0; i < g->m.size(); ++i) {
+    pbd_handle* h = g->m[i];
+    if ((kind != h->cand_nms || top != h->cand_top) && h->gexec) {
+      GHIP(g, hipSetDevice(g->dev[i]));
+      drop_graph(h);
+    }
+    h->cand_nms = kind;
+    h->cand_top = top;
+  }
+  g->cand_nms = kind;
+  g->cand_top = top;
+  return PBD_OK;
+}
 // every member gets the padding (checked first: nothing changes unless all accept)
 int pbd_group_set_boundary_pad(pbd_group* g, int pad) {
   if (!g) return PBD_ERR_ARG;
@@ -433,7 +453,7 @@ static int frame_impl(pbd_group* g, const uint8_t* im, int w, int hgt, int cn, i
   for (int i = 0; i < nr; ++i) memcpy(packed.data() + st * i, recs[order[i]], st);
   int kept = 0;
   GHIP(g, hipSetDevice(g->dev[0]));
-  GMEMBER(g, 0, pbd_i_filter_host(g->m[0], g->cand_mode, g->cand_overlap, w, hgt, packed.data(), nr, &kept));
+  GMEMBER(g, 0, pbd_i_filter_host(g->m[0], g->cand_mode, g->cand_overlap, w, hgt, packed.data(), nr, &kept, g->cand_nms, g->cand_top));
   if (count) *count = kept;
   if (kept > capacity) return gfail(g, PBD_ERR_CAPACITY, "output capacity too small");
   for (int i = 0; i < kept; ++i) pbd_rec_get(packed.data() + st * i, mp, heads, boxes, locs, i);

@@ -226,6 +226,11 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   // A single-frame collect finds [1] records (pbd_i_found), a batch collect fetches for [0] and splits by [2 + f] / [2 + B + f].
   int* d_cf_cnt = nullptr; int* h_cf_cnt = nullptr;    // [2 + 2 * PBD_MAX_BATCH]; h_: pinned
   unsigned long long* d_cf_mask = nullptr; size_t cf_mask_bytes = 0;   // per-frame masks too large for LDS (frame plan)
+  // what the NMS of PBD_CAND_SORT_NMS is (pbd_set_candidate_nms): the painted mask above, or the part-wise rule of nms.m by
+  // k_cand_parts behind k_cand_filter in SORT mode, which then writes into d_cp_stage / d_cp_cnt.  Allocated on first use.
+  int cand_nms = PBD_NMS_PAINTED; int cand_top = 0;
+  char* d_cp_stage = nullptr; int* d_cp_cnt = nullptr;
+  int4* d_cp_rect = nullptr; int* d_cp_np = nullptr; unsigned* d_cp_kept = nullptr; unsigned long long* d_cp_bits = nullptr;
   // depth-consistency pruning (pbd_set_depth_filter): k_zfilter.hip behind k_backtrack.  Named z* / zf*: d_depth and max_depth
   // above are the part tree's depth.  Allocated on the first depth-carrying frame with the setting on.
   bool zf_on = false; float zf_factor = 0.f;
@@ -448,7 +453,9 @@ void pbd_i_b3_begin(pbd_handle* h, int nframes);
 void pbd_i_b3_gather(pbd_handle* h, int f, const std::vector<const char*>& recs, const std::vector<int>& order);
 int pbd_i_b3_end(pbd_handle* h);
 // pbd_candidates_filter without the argument checks: `count` packed records filtered in place (kept ones first, final order)
-int pbd_i_filter_host(pbd_handle* h, int mode, float overlap, int im_w, int im_h, char* recs, int count, int* kept);
+// (kind / top: pbd_set_candidate_nms, what the NMS of mode 2 is)
+int pbd_i_filter_host(pbd_handle* h, int mode, float overlap, int im_w, int im_h, char* recs, int count, int* kept,
+                      int kind = PBD_NMS_PAINTED, int top = 0);
 int pbd_i_depth_check(pbd_handle* h, int depth_type, long long dstride, int w);   // a depth-carrying frame's depth arguments
 // Frame-plan buffers: counted in frame_bytes, freed on re-plan (pbd_api.cpp free_frame)
 template <typename T>
@@ -555,6 +562,18 @@ struct CandFilterArgs {
 };
 size_t cand_filter_mask_bytes(int w, int h);
 void launch_cand_filter(const CandFilterArgs& a, int nframes, hipStream_t s);
+// part-wise overlap NMS (k_cand_parts.hip): one workgroup per frame over the sorted runs k_cand_filter (SORT) left behind
+struct CandPartsArgs {
+  const char* in; size_t stride; int mp;     // the sorted records, frame f's at in + cnt_in[2 + nf + f] * stride
+  const int* cnt_in; int capacity;           // k_cand_filter's count block
+  double overlap; int top;
+  int4* rect;                                // [mp + 2][capacity]: the restaged rectangles
+  int* np; unsigned* kept;                   // [capacity] each: part counts, kept indices
+  unsigned long long* gbits;                 // [cand_parts_bits_words]: undecided bits of frames too long for LDS
+  char* out; int* cnt_out;                   // kept records; counts [2 + 2 * nframes]
+};
+size_t cand_parts_bits_words(int capacity, int nframes);
+void launch_cand_parts(const CandPartsArgs& a, int nframes, hipStream_t s);
 // depth-consistency pruning (k_zfilter.hip)
 struct ZFilterArgs {
   RecordSet in;                 // (cf unused)

@@ -84,6 +84,32 @@ static int cand_filter_buffers(pbd_handle* h, bool masks) {
   return PBD_OK;
 }
 
+// ---- part-wise overlap NMS (k_cand_parts.hip) ----------------------------------------------------------------------------
+static bool parts_nms(const pbd_handle* h, int cm) { return cm == PBD_CAND_SORT_NMS && h->cand_nms == PBD_NMS_PARTS; }
+// the kept record's rectangles and areas travel through dynamic LDS: 40 bytes per rectangle
+static int cand_parts_lds_ok(pbd_handle* h) {
+  return (size_t)(h->max_parts + 1) * 40 <= 32768 ? PBD_OK : fail(h, PBD_ERR_UNSUPPORTED, "parts NMS: more than 818 parts per component");
+}
+static CandPartsArgs cand_parts_args(const pbd_handle* h, float overlap, int top, int capacity) {
+  CandPartsArgs p{};
+  p.stride = h->cand_stride; p.mp = h->max_parts; p.capacity = capacity;
+  p.overlap = (double)overlap; p.top = top;
+  return p;
+}
+// the sort's staging buffer and the rectangle planes: model-sized, on the first frame that needs them.  Called outside any capture.
+static int cand_parts_buffers(pbd_handle* h) {
+  if (h->d_cp_stage) return PBD_OK;
+  const size_t cap = (size_t)h->opt.max_candidates;
+  int rc;
+  if ((rc = cand_parts_lds_ok(h)) || (rc = model_alloc(h, &h->d_cp_stage, h->cand_stride * cap)) ||
+      (rc = model_alloc(h, &h->d_cp_cnt, 2 + 2 * PBD_MAX_BATCH)) || (rc = model_alloc(h, &h->d_cp_rect, (size_t)(h->max_parts + 2) * cap)) ||
+      (rc = model_alloc(h, &h->d_cp_np, cap)) || (rc = model_alloc(h, &h->d_cp_kept, cap)) ||
+      (rc = model_alloc(h, &h->d_cp_bits, cand_parts_bits_words((int)cap, PBD_MAX_BATCH))))
+    return rc;
+  drop_graph(h);
+  return PBD_OK;
+}
+
 // ---- depth-consistency pruning (k_zfilter.hip) ----------------------------------------------------------------------
 // per (component, part): parentid and norm(anchor(0)) * zfactor, the reference's double expression (src/SearchSpacePruning.cpp:82-88):
 // anchor(0) = anchors[defid[first mixture of the part]] (include/Parts.hpp:183), whatever mixture the candidate chose
@@ -104,7 +130,7 @@ static void zf_table(const pbd_handle* h, float zfactor, std::vector<int>& npart
 // the pruning's device state: allocated on the first depth-carrying frame with the setting on; the table follows zfactor.
 // Called outside any capture (depth-carrying frames run their launches eagerly).
 static int zf_buffers(pbd_handle* h) {
-  int rc = cand_filter_buffers(h, pbd_i_cand_mode(h) == PBD_CAND_SORT_NMS);   // (d_cand_raw: the back-tracking's device output)
+  int rc = cand_filter_buffers(h, pbd_i_cand_mode(h) == PBD_CAND_SORT_NMS && !parts_nms(h, pbd_i_cand_mode(h)));   // (d_cand_raw: the back-tracking's device output)
   if (rc) return rc;
   const size_t cap = (size_t)h->opt.max_candidates, nc = (size_t)h->md.ncomponents, mp = (size_t)h->max_parts;
   if (!h->d_zf_med) {
@@ -401,7 +427,8 @@ static RecordSet final_records(const pbd_handle* h) {
 int pbd_i_post_buffers(pbd_handle* h) {
   const int cm = pbd_i_cand_mode(h);
   if (cm != PBD_CAND_RAW) {
-    int rc = cand_filter_buffers(h, cm == PBD_CAND_SORT_NMS);
+    int rc = cand_filter_buffers(h, cm == PBD_CAND_SORT_NMS && !parts_nms(h, cm));
+    if (!rc && parts_nms(h, cm)) rc = cand_parts_buffers(h);
     if (rc) return rc;
   }
   h->out_filtered = cm != PBD_CAND_RAW;   // (a replayed graph does not pass through pbd_i_post_enqueue)
@@ -445,11 +472,22 @@ int pbd_i_post_enqueue(pbd_handle* h, int cm, bool zf, char* raw) {
   if (h->out_filtered) {
     // Candidate::sort (+ nonMaximaSuppression): k_cand_filter writes the kept records in final order + the per-frame counts — straight
     // into the pinned host buffers, or, for a member of an RCCL-gathering group, into the device buffer the all-gather block is packed from
-    CandFilterArgs a = cand_args(h, cm, h->cand_overlap, h->fw, h->fh);
+    // With the part-wise NMS the kernel only sorts, into the staging buffer, and k_cand_parts writes what it would have written
+    const bool parts = parts_nms(h, cm);
+    CandFilterArgs a = cand_args(h, parts ? PBD_CAND_SORT : cm, h->cand_overlap, h->fw, h->fh);
     a.in = in;
     a.back = h->d_back; a.rootv_base = h->d_rootv; a.gmask = h->d_cf_mask;
     a.out = dev_out ? h->d_cand_out : h->h_cand_out;
     a.cnt_out = dev_out ? h->d_cf_cnt : h->h_cf_cnt;
+    if (parts) {
+      CandPartsArgs p = cand_parts_args(h, h->cand_overlap, h->cand_top, h->opt.max_candidates);
+      p.in = h->d_cp_stage; p.cnt_in = h->d_cp_cnt;
+      p.rect = h->d_cp_rect; p.np = h->d_cp_np; p.kept = h->d_cp_kept; p.gbits = h->d_cp_bits;
+      p.out = a.out; p.cnt_out = a.cnt_out;
+      a.out = h->d_cp_stage; a.cnt_out = h->d_cp_cnt;
+      launch_cand_filter(a, h->batch, h->stream);
+      launch_cand_parts(p, h->batch, h->stream);
+    } else
     launch_cand_filter(a, h->batch, h->stream);
   }
   LAUNCHCHK(h, zf ? "argmin + depth filter" : "argmin + candidate filter");
@@ -561,8 +599,14 @@ int pbd_i_b3_end(pbd_handle* h) {
 }
 
 // ---- the stand-alone device round trip of the candidate filter --------------------------------------------------------------
-int pbd_i_filter_host(pbd_handle* h, int mode, float overlap, int im_w, int im_h, char* recs, int count, int* kept) {
+int pbd_i_filter_host(pbd_handle* h, int mode, float overlap, int im_w, int im_h, char* recs, int count, int* kept, int kind, int top) {
   if (mode == PBD_CAND_RAW || count == 0) { *kept = count; return PBD_OK; }
+  const bool parts = mode == PBD_CAND_SORT_NMS && kind == PBD_NMS_PARTS;
+  if (parts) {
+    int rc = cand_parts_lds_ok(h);
+    if (rc) return rc;
+    mode = PBD_CAND_SORT;
+  }
   ON_DEVICE(h);
   const size_t st = h->cand_stride, n = (size_t)count, mask = cand_filter_mask_bytes(im_w, im_h);
   Scratch s(h);
@@ -574,10 +618,19 @@ int pbd_i_filter_host(pbd_handle* h, int mode, float overlap, int im_w, int im_h
   a.keys = s.dev<unsigned long long>(2 * n); a.idx = s.dev<unsigned>(2 * n); a.box = s.dev<int>(4 * n); a.st = s.dev<uint8_t>(n);
   a.gmask = mode == PBD_CAND_SORT_NMS ? s.dev<unsigned long long>(mask / 8) : nullptr;
   a.out = d_out; a.cnt_out = d_cnt + 1;
+  CandPartsArgs p = cand_parts_args(h, overlap, top, count);
+  if (parts) {   // the sorted records go back into d_in's place: a second buffer, and a count block of its own
+    p.in = s.dev<char>(st * n); p.cnt_in = s.dev<int>(4);
+    p.rect = s.dev<int4>((size_t)(h->max_parts + 2) * n); p.np = s.dev<int>(n); p.kept = s.dev<unsigned>(n);
+    p.gbits = s.dev<unsigned long long>(cand_parts_bits_words(count, 1));
+    p.out = d_out; p.cnt_out = d_cnt + 1;
+    a.out = (char*)p.in; a.cnt_out = (int*)p.cnt_in;
+  }
   s.up(d_in, recs, st * n);
   s.up(d_cnt, &count, sizeof(int));
   if (s.ok()) {
     launch_cand_filter(a, 1, h->stream);
+    if (parts) launch_cand_parts(p, 1, h->stream);
     s.launched();
   }
   int cnt[4] = {0, 0, 0, 0};
@@ -635,6 +688,58 @@ int pbd_candidates_nms(pbd_candidate_head* heads, int32_t* boxes, int32_t* locs,
   return PBD_OK;
 }
 
+// nms.m's rule (include/pbd_c.h); k_cand_parts.hip computes the same
+namespace {
+struct PRect { long long x0, y0, x1, y1; };   // empty: all zero
+inline PRect p_part(const int32_t* b) {
+  if (b[2] <= 0 || b[3] <= 0) return PRect{0, 0, 0, 0};
+  return PRect{b[0], b[1], (long long)b[0] + b[2], (long long)b[1] + b[3]};
+}
+inline double p_area(const PRect& r) { return (double)(r.x1 - r.x0) * (double)(r.y1 - r.y0); }
+inline double p_inter(const PRect& a, const PRect& b) {
+  const long long w = std::min(a.x1, b.x1) - std::max(a.x0, b.x0), h = std::min(a.y1, b.y1) - std::max(a.y0, b.y0);
+  return (w > 0 && h > 0) ? (double)w * (double)h : 0.0;
+}
+}  // namespace
+int pbd_candidates_nms_parts(pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int count, int mp, float overlap, int top,
+                             int* kept) {
+  if (!heads || !boxes || !kept || count < 0 || mp <= 0 || top < 0 || !std::isfinite(overlap)) return PBD_ERR_ARG;
+  for (int i = 0; i < count; ++i)
+    if (heads[i].nparts < 0 || heads[i].nparts > mp) return PBD_ERR_ARG;
+  const int n = top > 0 && count > top ? top : count;   // nms.m:18-22
+  const size_t R = (size_t)mp + 1;
+  std::vector<PRect> rect(R * n);   // [record][part .. , covering box at mp]
+  for (int i = 0; i < n; ++i) {
+    PRect c{0, 0, 0, 0};
+    bool any = false;
+    for (int p = 0; p < heads[i].nparts; ++p) {
+      const PRect r = p_part(boxes + ((size_t)i * mp + p) * 4);
+      rect[R * i + p] = r;
+      if (r.x1 == r.x0) continue;
+      c = any ? PRect{std::min(c.x0, r.x0), std::min(c.y0, r.y0), std::max(c.x1, r.x1), std::max(c.y1, r.y1)} : r;
+      any = true;
+    }
+    rect[R * i + mp] = c;
+  }
+  const double ov = (double)overlap;
+  std::vector<uint8_t> keep((size_t)count, 0), gone((size_t)n, 0);
+  for (int i = 0; i < n; ++i) {
+    if (gone[i]) continue;
+    keep[i] = 1;
+    const PRect* ri = &rect[R * i];
+    for (int j = i + 1; j < n; ++j) {
+      if (gone[j]) continue;
+      const PRect* rj = &rect[R * j];
+      bool rej = p_inter(ri[mp], rj[mp]) / p_area(ri[mp]) > ov;
+      const int P = std::min(heads[i].nparts, heads[j].nparts);
+      for (int p = 0; p < P && !rej; ++p) rej = p_inter(ri[p], rj[p]) / p_area(ri[p]) > ov;
+      gone[j] = rej;
+    }
+  }
+  *kept = pbd_rec_compact(heads, boxes, locs, count, mp, keep.data());
+  return PBD_OK;
+}
+
 // ---- the post-step on the device (k_cand.hip) -------------------------------------
 static bool cand_mode_ok(int mode, float overlap) {
   return (mode == PBD_CAND_RAW || mode == PBD_CAND_SORT || mode == PBD_CAND_SORT_NMS) && std::isfinite(overlap);
@@ -650,6 +755,41 @@ int pbd_set_candidate_filter(pbd_handle* h, int mode, float overlap) {
   }
   h->cand_mode = mode;
   h->cand_overlap = overlap;
+  return PBD_OK;
+}
+
+int pbd_set_candidate_nms(pbd_handle* h, int kind, int top) {
+  if (!h) return PBD_ERR_ARG;
+  if ((kind != PBD_NMS_PAINTED && kind != PBD_NMS_PARTS) || top < 0) return fail(h, PBD_ERR_ARG, "candidate NMS: kind PBD_NMS_PAINTED / _PARTS, top >= 0");
+  if (h->in_group) return fail(h, PBD_ERR_STATE, "handle belongs to a pbd_group: set the NMS on the group");
+  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if ((kind != h->cand_nms || top != h->cand_top) && h->gexec) {   // which kernels run behind the sort is part of a captured graph
+    ON_DEVICE(h);
+    drop_graph(h);
+  }
+  h->cand_nms = kind;
+  h->cand_top = top;
+  return PBD_OK;
+}
+
+int pbd_candidates_filter_parts(pbd_handle* h, float overlap, int top, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs,
+                                int count, int* kept) {
+  if (!h) return PBD_ERR_ARG;
+  if (!std::isfinite(overlap) || top < 0) return fail(h, PBD_ERR_ARG, "parts NMS: finite overlap, top >= 0");
+  if (!kept || count < 0 || (count > 0 && (!heads || !boxes))) return fail(h, PBD_ERR_ARG, "heads / boxes / kept / count");
+  for (int i = 0; i < count; ++i) {
+    if (!std::isfinite(heads[i].score)) return fail(h, PBD_ERR_ARG, "non-finite score: its order is undefined");
+    if (heads[i].nparts < 0 || heads[i].nparts > h->max_parts) return fail(h, PBD_ERR_ARG, "nparts outside 0..max_parts");
+  }
+  if (count == 0) { *kept = 0; return PBD_OK; }
+  const int mp = h->max_parts;
+  const size_t st = h->cand_stride;
+  std::vector<char> rec(st * count, 0);
+  for (int i = 0; i < count; ++i) pbd_rec_put(rec.data() + st * i, mp, heads, boxes, locs, i);
+  int k = 0, rc = pbd_i_filter_host(h, PBD_CAND_SORT_NMS, overlap, 1, 1, rec.data(), count, &k, PBD_NMS_PARTS, top);
+  if (rc) return rc;
+  for (int i = 0; i < k; ++i) pbd_rec_get(rec.data() + st * i, mp, heads, boxes, locs, i);
+  *kept = k;
   return PBD_OK;
 }
 

@@ -124,6 +124,12 @@ class Candidate:
         h, w = im_shape[:2]
         return Candidate._unpack(*capi.candidates_nms(*Candidate._pack(candidates), w, h, overlap))
 
+    @staticmethod
+    def nonMaximaSuppressionParts(candidates: List["Candidate"], overlap: float = 0.3, top: int = 1000) -> List["Candidate"]:
+        """matlab/detection/nms.m on sorted candidates: part by part and by the covering box, over the kept detection's area,
+        after a cut to the `top` best (0: none)."""
+        return Candidate._unpack(*capi.candidates_nms_parts(*Candidate._pack(candidates), overlap, top))
+
 
 class HOGFeatures:
     """IFeatures implementation (include/HOGFeatures.hpp:52-88) on the device."""
@@ -243,10 +249,11 @@ class PartsBasedDetector:
     or np.float64 (ros/Node.hpp:121, cells/detect.cpp:93) picks the instantiation."""
 
     def __init__(self, device: int = 0, conv_mode: int = capi.PBD_CONV_AUTO, max_candidates: int = 4096,
-                 level_begin: int = 0, level_end: int = 0, dtype=np.float32, cand_filter=None):
-        """cand_filter=(mode, overlap): see setCandidateFilter."""
+                 level_begin: int = 0, level_end: int = 0, dtype=np.float32, cand_filter=None, cand_nms=None):
+        """cand_filter=(mode, overlap): see setCandidateFilter; cand_nms=(kind, top): see setCandidateNms."""
         self._device, self._conv, self._cap = device, conv_mode, max_candidates
         self._cand_filter = cand_filter
+        self._cand_nms = cand_nms
         self._zfactor: Optional[float] = None   # setDepthFilter: None = off
         self._camera = None                      # setBoundingBoxes3D: None = off
         self._cluster_tol: Optional[float] = None   # setObjectClusters: None = off
@@ -265,7 +272,7 @@ class PartsBasedDetector:
         """src/PartsBasedDetector.cpp:102-127."""
         self._name = model.name
         self._h = capi.Handle(model, self._device, self._conv, self._cap, 0, self._lb, self._le, dtype=self._dtype,
-                              cand_filter=self._cand_filter)
+                              cand_filter=self._cand_filter, cand_nms=self._cand_nms)
         self.features_ = HOGFeatures(self._h)
         self.convolution_engine_ = SpatialConvolutionEngine(self._h)
         self.convolution_engine_.setFilters(model.filtersw)
@@ -365,6 +372,16 @@ class PartsBasedDetector:
         if self._h is not None:
             self._h.set_depth_filter(zfactor is not None, 0.0 if zfactor is None else zfactor)
         self._zfactor = zfactor
+
+    def setCandidateNms(self, kind: int, top: int = 0) -> None:
+        """What the NMS of capi.PBD_CAND_SORT_NMS is: capi.PBD_NMS_PAINTED (default, Candidate.nonMaximaSuppression) or
+        capi.PBD_NMS_PARTS (Candidate.nonMaximaSuppressionParts: matlab/detection/nms.m, which testmodel.m runs as nms(box, 0.3);
+        top = 1000 reproduces its cut, 0 = none).  Kept across distributeModel()."""
+        if kind not in (capi.PBD_NMS_PAINTED, capi.PBD_NMS_PARTS) or top < 0:
+            raise capi.PbdError(capi.PBD_ERR_ARG, "candidate NMS: kind PBD_NMS_PAINTED / _PARTS, top >= 0")
+        if self._h is not None:
+            self._h.set_candidate_nms(kind, top)
+        self._cand_nms = (kind, top)
 
     def setCandidateFilter(self, mode: int, overlap: float = 0.0) -> None:
         """Candidate.sort (capi.PBD_CAND_SORT), or sort + Candidate.nonMaximaSuppression(overlap) (capi.PBD_CAND_SORT_NMS), of

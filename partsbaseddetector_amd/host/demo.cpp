@@ -21,8 +21,12 @@ using namespace pbd;
 //             pointer at that cell redirected): the candidates must be those of the edited tables.
 template <typename T>
 static void run(Model& model, const Mat& im, bool stagewise, int special = 0, const char* io_file = nullptr, bool part_scores = false, int pad = 0,
-                const char* features_file = nullptr) {
+                const char* features_file = nullptr, const float* nms_parts = nullptr) {
   PartsBasedDetector<T> pbd(0, PBD_CONV_EXACT);
+  if (nms_parts && !stagewise) {   // the fused detect() sorts and suppresses on the GPU
+    pbd.setCandidateFilter(PBD_CAND_SORT_NMS, *nms_parts);
+    pbd.setCandidateNms(PBD_NMS_PARTS, 1000);
+  }
   pbd.setPartScores(part_scores);
   pbd.setBoundaryPad(pad);
   pbd.distributeModel(model);
@@ -82,6 +86,10 @@ static void run(Model& model, const Mat& im, bool stagewise, int special = 0, co
   }
   printf("Number of candidates: %ld\n", (long)candidates.size());
   Candidate::sort(candidates);
+  if (nms_parts) {
+    if (stagewise) Candidate::nonMaximaSuppressionParts(candidates, *nms_parts, 1000);
+    printf("Kept by the parts NMS: %ld\n", (long)candidates.size());
+  }
   if (features_file) {   // --features FILE: the sorted records' dense feature vectors, one row of doubles each, in the order
                          // [biasw | defw (ndefs x 4) | the filters back to back] (w . row = the record's score); header: rows, columns (int64)
     std::vector<pbd_feature_block> blocks;
@@ -131,6 +139,7 @@ static void run(Model& model, const Mat& im, bool stagewise, int special = 0, co
 int main(int argc, char** argv) {
   bool part_scores = false;   // --part-scores (anywhere): per detection, the re-scored total, the root score and the weakest part
   const char* features_file = nullptr;   // --features FILE (anywhere): the detections' dense feature vectors, written to FILE
+  float nms_overlap = 0.f; const float* nms_parts = nullptr;   // --nms-parts OVERLAP (anywhere): sort + nms.m's part-wise NMS, the 1000 best
   int pad = 0;                // --pad N (anywhere): N cells of boundary padding around every pyramid level (0: off)
   for (int i = 1; i < argc; ++i)
     if (std::string(argv[i]) == "--pad") {
@@ -138,6 +147,14 @@ int main(int argc, char** argv) {
       const long v = i + 1 < argc ? strtol(argv[i + 1], &end, 10) : -1;
       if (i + 1 >= argc || !*argv[i + 1] || *end || v < 0 || v > 8) { printf("--pad N: 0 (off) .. 8 cells\n"); exit(-1); }
       pad = (int)v;
+      for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+      argc -= 2; --i;
+    } else
+    if (std::string(argv[i]) == "--nms-parts") {
+      char* end = nullptr;
+      const float v = i + 1 < argc ? strtof(argv[i + 1], &end) : 0.f;
+      if (i + 1 >= argc || !*argv[i + 1] || *end || !(v - v == 0.f)) { printf("--nms-parts OVERLAP: a finite number\n"); exit(-1); }
+      nms_overlap = v; nms_parts = &nms_overlap;
       for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
       argc -= 2; --i;
     } else
@@ -153,7 +170,7 @@ int main(int argc, char** argv) {
       --argc; --i;
     }
   if (argc < 6 || argc > 8) {
-    printf("Usage: pbd_demo model_file image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE]\n");
+    printf("Usage: pbd_demo model_file image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE] [--nms-parts OVERLAP]\n");
     exit(-1);
   }
   // determine the type of model to read (src/demo.cpp:63-82)
@@ -180,8 +197,8 @@ int main(int argc, char** argv) {
   try {
     if (part_scores && stagewise) { printf("--part-scores: the fused detect() only\n"); exit(-1); }
     if (features_file && special) { printf("--features: not with %s\n", mode.c_str()); exit(-1); }
-    if (mode.find("double") != std::string::npos) run<double>(model, im, stagewise, 0, nullptr, part_scores, pad, features_file);
-    else run<float>(model, im, stagewise, special, special ? argv[7] : nullptr, part_scores, pad, features_file);
+    if (mode.find("double") != std::string::npos) run<double>(model, im, stagewise, 0, nullptr, part_scores, pad, features_file, nms_parts);
+    else run<float>(model, im, stagewise, special, special ? argv[7] : nullptr, part_scores, pad, features_file, nms_parts);
   } catch (const Exception& e) {
     printf("error %d: %s\n", e.code, e.what());
     return 1;

@@ -117,6 +117,9 @@ class Candidate {
   }
   static void sort(std::vector<Candidate>& c);                                         // :97-99
   static void nonMaximaSuppression(int im_w, int im_h, std::vector<Candidate>& c, float overlap = 0.0f);  // :277-304
+  // matlab/detection/nms.m on sorted candidates (pbd_candidates_nms_parts): part by part and by the covering box, over the kept
+  // detection's area, after a cut to the `top` best (1000: nms.m's; 0: none)
+  static void nonMaximaSuppressionParts(std::vector<Candidate>& c, float overlap = 0.3f, int top = 1000);
 };
 typedef std::vector<Candidate> vectorCandidate;
 
@@ -343,6 +346,8 @@ class Device {
   void check(int rc) const { if (rc != PBD_OK) throw Exception(rc, pbd_last_error(h)); }
   // Candidate::sort (+ nonMaximaSuppression(overlap)) of every detect() on the GPU: PBD_CAND_RAW / _SORT / _SORT_NMS
   void setCandidateFilter(int mode, float overlap = 0.f) { check(pbd_set_candidate_filter(h, mode, overlap)); }
+  // what the NMS of PBD_CAND_SORT_NMS is: PBD_NMS_PAINTED, or PBD_NMS_PARTS = nms.m's part-wise rule after a cut to the `top` best
+  void setCandidateNms(int kind, int top = 0) { check(pbd_set_candidate_nms(h, kind, top)); }
   // SearchSpacePruning::filterCandidatesByDepth inside every detect(im, depth) with a non-empty depth image, on the GPU
   void setDepthFilter(bool on, float zfactor) { check(pbd_set_depth_filter(h, on ? 1 : 0, zfactor)); }
   // per-part scores of every record detect() returns, on the GPU
@@ -633,6 +638,7 @@ class PartsBasedDetector {
   Parts parts_;
   int device_, conv_mode_, ncomponents_ = 0;
   int cand_mode_ = PBD_CAND_RAW; float cand_overlap_ = 0.f;
+  int cand_nms_ = PBD_NMS_PAINTED, cand_top_ = 0;
   bool depth_on_ = false; float zfactor_ = 0.03f;
   bool part_scores_on_ = false;
   int boundary_pad_ = 0;
@@ -667,6 +673,7 @@ class PartsBasedDetector {
     parts_ = Parts(model);                         // :121-122
     dp_ = DynamicProgram<T>(dev_);
     if (cand_mode_ != PBD_CAND_RAW) dev_->setCandidateFilter(cand_mode_, cand_overlap_);
+    if (cand_nms_ != PBD_NMS_PAINTED) dev_->setCandidateNms(cand_nms_, cand_top_);
     if (depth_on_) dev_->setDepthFilter(true, zfactor_);
     if (part_scores_on_) dev_->setPartScores(true);
     if (boundary_pad_) dev_->setBoundaryPad(boundary_pad_);
@@ -701,6 +708,13 @@ class PartsBasedDetector {
   void setCandidateFilter(int mode, float overlap = 0.f) {
     if (dev_) dev_->setCandidateFilter(mode, overlap);
     cand_mode_ = mode; cand_overlap_ = overlap;
+  }
+  // The NMS of PBD_CAND_SORT_NMS: PBD_NMS_PAINTED (default, Candidate::nonMaximaSuppression) or PBD_NMS_PARTS
+  // (Candidate::nonMaximaSuppressionParts(overlap, top): matlab/detection/nms.m, what testmodel.m runs).  Kept across distributeModel().
+  void setCandidateNms(int kind, int top = 0) {
+    if (dev_) dev_->setCandidateNms(kind, top);
+    else if ((kind != PBD_NMS_PAINTED && kind != PBD_NMS_PARTS) || top < 0) throw Exception(PBD_ERR_ARG, "candidate NMS: kind PBD_NMS_PAINTED / _PARTS, top >= 0");
+    cand_nms_ = kind; cand_top_ = top;
   }
   void detect(const Mat& im, vectorCandidate& candidates) { detect(im, Mat(), candidates); }
   // src/PartsBasedDetector.cpp:69-95: fused path, everything stays in HBM; `depth` ignored (:91-93) unless setDepthFilter is on
@@ -790,6 +804,26 @@ inline void Candidate::nonMaximaSuppression(int im_w, int im_h, std::vector<Cand
     keep++;
   }
   c.resize(keep);
+}
+inline void Candidate::nonMaximaSuppressionParts(std::vector<Candidate>& c, float overlap, int top) {
+  size_t mp = 1;
+  for (const Candidate& k : c) mp = std::max(mp, k.parts().size());
+  std::vector<pbd_candidate_head> heads(c.size());
+  std::vector<int32_t> boxes(c.size() * mp * 4, 0);
+  for (size_t n = 0; n < c.size(); ++n) {
+    heads[n] = pbd_candidate_head{c[n].score(), c[n].component(), (int)n, (int)c[n].parts().size()};   // (level: the index, to find the kept ones)
+    for (size_t p = 0; p < c[n].parts().size(); ++p) {
+      const Rect& r = c[n].parts()[p];
+      int32_t* b = &boxes[(n * mp + p) * 4];
+      b[0] = r.x; b[1] = r.y; b[2] = r.width; b[3] = r.height;
+    }
+  }
+  int kept = 0;
+  const int rc = pbd_candidates_nms_parts(heads.data(), boxes.data(), nullptr, (int)c.size(), (int)mp, overlap, top, &kept);
+  if (rc != PBD_OK) throw Exception(rc, "Candidate::nonMaximaSuppressionParts: a finite overlap and top >= 0");
+  for (int k = 0; k < kept; ++k)
+    if (heads[k].level != k) c[k] = c[heads[k].level];
+  c.resize((size_t)kept);
 }
 
 }  // namespace pbd
