@@ -415,6 +415,19 @@ int pbd_resize_u8(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int 
                   uint8_t* out, int ow, int oh);
 int pbd_pyrdown_u8(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride,
                    uint8_t* out);
+/* The MATLAB pyramid's two stages (PBD_PYRAMID_MATLAB, below), stand-alone: interleaved double images (element (y, x, c) at
+ * (y * w + x) * cn + c), cn 1 or 3; `out` sized by the caller for the dimensions stated, which *ow / *oh report.  Bit-exact against
+ * the compiled reference files.
+ *   pbd_resize_area_f64: resize(im, scale) of matlab/mex/resize.cc:82-106 — area-weighted resampling by resize1dtran's
+ *     interpolation cache (:30-66, both `> 1e-3` tests), the rows axis then the columns axis (:101-102), the taps of a destination
+ *     index summed in ascending source order from 0.0 (alphacopy :18-24 on zeroed memory :69).  Result size round(hgt * scale) x
+ *     round(w * scale), C round() (:94-95).  scale > 1: PBD_ERR_ARG, "Invalid scaling factor" (resize.cc:90).
+ *   pbd_reduce_f64: reduce(im) of matlab/mex/reduce.cc:50-70 — the 5-tap binomial of :29 with the edge forms of the first row
+ *     (:24), the last row (:42) and the second-to-last row by the parity test dheight * 2 <= sheight (:35-38), rows pass then columns
+ *     pass, additions in the written order.  Result size round(hgt * .5) x round(w * .5) (:58-59).  A source dimension below 5
+ *     (where the forms would overlap or read outside the image): PBD_ERR_ARG.                                                     */
+int pbd_resize_area_f64(pbd_handle* h, const double* im, int w, int hgt, int cn, double scale, double* out, int* ow, int* oh);
+int pbd_reduce_f64(pbd_handle* h, const double* im, int w, int hgt, int cn, double* out, int* ow, int* oh);
 /* Neubeck-Van Gool block NMS on a score map (src/nms.cpp:84-129)             */
 int pbd_nms_map(pbd_handle* h, const float* src, int rows, int cols, int sz, uint8_t* dst);
 
@@ -738,6 +751,34 @@ int pbd_candidates_part_scores(pbd_handle* h, const pbd_candidate_head* heads, c
 int pbd_set_boundary_pad(pbd_handle* h, int pad);      /* 0 = off (default) */
 int pbd_get_boundary_pad(const pbd_handle* h);
 int pbd_group_set_boundary_pad(pbd_group* g, int pad); /* forwards to every member */
+
+/* ---- pyramid kind: the image pyramid of matlab/detection/featpyramid.m (ABI 5, additive) ----------------------------------------
+ * PBD_PYRAMID_OPENCV (default): HOGFeatures<T>::pyramid, src/HOGFeatures.cpp:95-127 — cv::resize / cv::pyrDown in the pixel type.
+ * PBD_PYRAMID_MATLAB: featpyramid.m:13-34, what the MATLAB side of the reference trains and evaluates on.
+ *   * Geometry, all in double: sc = 2^(1 / interval) (:13); nlevels = 1 + floor(log(min(w, h) / (5 sbin)) / log(sc)) (:15), a frame
+ *     with fewer than `interval` levels is refused as before; level i < interval has factor s_i = 1 / sc^i (:25) and size
+ *     round(hgt * s_i) x round(w * s_i) (resize.cc:94-95, C round(): halves away from zero); level j >= interval has size
+ *     round(0.5 * dim) of level j - interval (reduce.cc:58-59); box scale sbin / s_i, doubled per octave (featpyramid.m:27,32,47),
+ *     converted to float as the last step; cells per level as features.cc computes them.  pbd_pyramid_geometry answers for the
+ *     handle's kind.
+ *   * Level images are DOUBLE whatever the frame's depth (:22, nothing is rounded back to 8 bits between the stages), interleaved
+ *     and row-major; level 0 is the frame converted (resize with scale 1 is the identity); levels < interval by
+ *     pbd_resize_area_f64's definition from the frame, levels >= interval by pbd_reduce_f64's from level j - interval (:25,30).
+ *     A one-channel frame stays one channel (featpyramid.m:19-21 replicates it: three equal channels give the same gradients).
+ *     pbd_get_level_image_raw / pbd_get_frame_level_image_raw return doubles (iw * ih * cn * 8 bytes); pbd_get_level_image
+ *     answers PBD_ERR_STATE.  HOG runs on the double images (the instantiation double frames of pbd_detect_image use).
+ *   * Everything behind the features is unchanged; boxes keep this port's 0-based convention, with the scales above.  With
+ *     pbd_set_boundary_pad the two together are featpyramid.m.
+ *   * 8-bit frames only: pbd_detect_image / pbd_pyramid_image of another depth answer PBD_ERR_UNSUPPORTED, as does pbd_tune_plan
+ *     and a geometry whose double level images (all frames of a batch) exceed 2 GiB.  Groups have no setter.
+ * pbd_set_pyramid_kind: every path of the handle that takes 8-bit frames, from the next frame on (single, enqueue / collect,
+ * batches, device images, *_rgbd_*, latent, the stage entry points; eager or captured).  A different value drops the handle's frame
+ * plan and captured graph like pbd_set_boundary_pad; PBD_ERR_STATE while a frame is pending, PBD_ERR_ARG for an unknown kind.  Back
+ * at PBD_PYRAMID_OPENCV the handle behaves exactly as one that never left it.                                                     */
+#define PBD_PYRAMID_OPENCV 0
+#define PBD_PYRAMID_MATLAB 1
+int pbd_set_pyramid_kind(pbd_handle* h, int kind);
+int pbd_get_pyramid_kind(const pbd_handle* h);
 
 /* ---- latent detection: the best pose overlapping given part boxes (ABI 5, additive) ------------------------------------------
  * detect(im, model, thresh, bbox, overlap) of matlab/detection/detect.m:18-23, 60-101, 115-118, 159-161, 342-376, the MATLAB ancestor

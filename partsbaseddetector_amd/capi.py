@@ -25,6 +25,7 @@ PBD_SCALAR_F32, PBD_SCALAR_F64 = 0, 1
 PBD_CAND_RAW, PBD_CAND_SORT, PBD_CAND_SORT_NMS = 0, 1, 2   # pbd_set_candidate_filter: detect's output / Candidate::sort / sort + NMS
 PBD_NMS_PAINTED, PBD_NMS_PARTS = 0, 1   # pbd_set_candidate_nms: the NMS of PBD_CAND_SORT_NMS — Candidate::nonMaximaSuppression / nms.m's part-wise rule
 PBD_DEPTH_8U, PBD_DEPTH_16U, PBD_DEPTH_32F, PBD_DEPTH_64F = 0, 2, 5, 6          # cv::Mat::depth() (src/HOGFeatures.cpp:136-146)
+PBD_PYRAMID_OPENCV, PBD_PYRAMID_MATLAB = 0, 1   # pbd_set_pyramid_kind: HOGFeatures<T>::pyramid (cv::resize / cv::pyrDown) / matlab/detection/featpyramid.m
 DEPTH_OF = {np.dtype(np.uint8): PBD_DEPTH_8U, np.dtype(np.uint16): PBD_DEPTH_16U, np.dtype(np.float32): PBD_DEPTH_32F,
             np.dtype(np.float64): PBD_DEPTH_64F}
 
@@ -58,6 +59,7 @@ EXPORTS = [
     "pbd_latent_mask", "pbd_dp_argbest", "pbd_detect_latent_u8", "pbd_detect_latent_dev_u8", "pbd_detect_batch_latent_u8",
     "pbd_feature_window_max", "pbd_candidates_features", "pbd_candidates_features_f64", "pbd_candidates_features_dev",
     "pbd_candidates_nms_parts", "pbd_set_candidate_nms", "pbd_group_set_candidate_nms", "pbd_candidates_filter_parts",
+    "pbd_set_pyramid_kind", "pbd_get_pyramid_kind", "pbd_resize_area_f64", "pbd_reduce_f64",
 ]
 PBD_ABI_VERSION = 5
 
@@ -399,6 +401,16 @@ class Handle:
         """pbd_get_boundary_pad"""
         return int(self.L.pbd_get_boundary_pad(self.h))
 
+    def set_pyramid_kind(self, kind=PBD_PYRAMID_MATLAB):
+        """pbd_set_pyramid_kind: PBD_PYRAMID_MATLAB = the image pyramid of matlab/detection/featpyramid.m (area resize + reduce, double
+        level images) for every 8-bit frame from the next one on; PBD_PYRAMID_OPENCV = the default.  geometry() answers for the kind."""
+        self._chk(self.L.pbd_set_pyramid_kind(self.h, int(kind)))
+
+    @property
+    def pyramid_kind(self):
+        """pbd_get_pyramid_kind"""
+        return int(self.L.pbd_get_pyramid_kind(self.h))
+
     def set_part_scores(self, on=True):
         """pbd_set_part_scores: every detect also computes (app, def, bias) of every part of every returned record"""
         self._chk(self.L.pbd_set_part_scores(self.h, int(bool(on))))
@@ -647,7 +659,8 @@ class Handle:
     def level_image_raw(self, l):
         g = self._geo
         shape = (g["img_h"][l], g["img_w"][l]) + ((self._cn,) if self._cn > 1 else ())
-        out = np.zeros(shape, getattr(self, "_imdtype", np.dtype(np.uint8)))
+        dt = np.dtype(np.float64) if self.pyramid_kind == PBD_PYRAMID_MATLAB else getattr(self, "_imdtype", np.dtype(np.uint8))
+        out = np.zeros(shape, dt)
         self._chk(self.L.pbd_get_level_image_raw(self.h, l, out.ctypes.data_as(C.c_void_p), C.c_size_t(out.nbytes)))
         return out
 
@@ -842,6 +855,27 @@ class Handle:
         out = np.zeros((oh, ow) + ((cn,) if cn > 1 else ()), np.uint8)
         self._chk(self.L.pbd_resize_u8(self.h, _p(im, C.c_uint8), w, hgt, cn, w * cn, _p(out, C.c_uint8), ow, oh))
         return out
+
+    def resize_area(self, im: np.ndarray, scale):
+        """pbd_resize_area_f64: resize(im, scale) of matlab/mex/resize.cc on a double image [h, w] or [h, w, 3]"""
+        im = np.ascontiguousarray(im, np.float64)
+        hgt, w = im.shape[:2]
+        cn = 1 if im.ndim == 2 else im.shape[2]
+        out = np.zeros(max(hgt, 1) * max(w, 1) * cn, np.float64)     # scale <= 1: never larger than the source
+        ow, oh = C.c_int(0), C.c_int(0)
+        self._chk(self.L.pbd_resize_area_f64(self.h, _p(im, C.c_double), w, hgt, cn, C.c_double(scale), _p(out, C.c_double),
+                                             C.byref(ow), C.byref(oh)))
+        return out[:oh.value * ow.value * cn].reshape((oh.value, ow.value) + ((cn,) if im.ndim == 3 else ())).copy()
+
+    def reduce(self, im: np.ndarray):
+        """pbd_reduce_f64: reduce(im) of matlab/mex/reduce.cc on a double image [h, w] or [h, w, 3], both dimensions >= 5"""
+        im = np.ascontiguousarray(im, np.float64)
+        hgt, w = im.shape[:2]
+        cn = 1 if im.ndim == 2 else im.shape[2]
+        out = np.zeros(max(hgt, 1) * max(w, 1) * cn, np.float64)
+        ow, oh = C.c_int(0), C.c_int(0)
+        self._chk(self.L.pbd_reduce_f64(self.h, _p(im, C.c_double), w, hgt, cn, _p(out, C.c_double), C.byref(ow), C.byref(oh)))
+        return out[:oh.value * ow.value * cn].reshape((oh.value, ow.value) + ((cn,) if im.ndim == 3 else ())).copy()
 
     def pyrdown(self, im: np.ndarray):
         im = np.ascontiguousarray(im, np.uint8)

@@ -224,7 +224,8 @@ void free_frame(pbd_handle* h) {
   h->d_cf_mask = nullptr; h->cf_mask_bytes = 0;
   h->d_ik_blocks = nullptr; h->d_ik_cells = nullptr; h->n_ik_blocks = 0;
   h->d_lat_jobs = nullptr; h->d_lat_blocks = nullptr; h->d_lat_flags = nullptr; h->d_lat_partial = nullptr; h->n_lat_blocks = 0;
-  h->fw = h->fh = h->fcn = 0; h->fdepth = 0; h->fesz = 1;
+  h->fw = h->fh = h->fcn = 0; h->fdepth = 0; h->fesz = 1; h->ldepth = 0; h->lesz = 1;
+  h->d_matjobs = nullptr; h->d_matruns = nullptr; h->d_mattaps = nullptr;
   reset_stages(h);
   h->feat_split_ok = false;
 }
@@ -274,6 +275,8 @@ int plan_frame(pbd_handle* h, int w, int hgt, int cn, int batch, int depth) {
   FrameTables t;
   if ((rc = plan_tables(*h, fs, lay, b, ncu, h->dt_geom, h->knobs, t, &h->err))) return rc;
   if ((rc = dev_upload(h, &h->d_pyrjobs, t.pyrjobs)) || (rc = dev_upload(h, &h->d_levels, t.levels)) ||
+      (h->pyr_kind == PBD_PYRAMID_MATLAB && ((rc = dev_upload(h, &h->d_matjobs, t.matjobs)) || (rc = dev_upload(h, &h->d_matruns, t.matruns)) ||
+                                             (rc = dev_upload(h, &h->d_mattaps, t.mattaps)))) ||
       (h->pad > 0 && ((rc = dev_upload(h, &h->d_hog_levels, t.hog_levels)) || (rc = dev_upload(h, &h->d_padjobs, t.padjobs)) ||
                       (rc = dev_upload(h, &h->d_padblocks, t.padblk)))) ||
       (rc = dev_upload(h, &h->d_hog_tiles, t.hog_tiles)) || (rc = dev_upload(h, &h->d_conv_tiles, t.conv_tiles)) ||
@@ -315,6 +318,7 @@ int plan_frame(pbd_handle* h, int w, int hgt, int cn, int batch, int depth) {
   h->root_cells = t.root_cells; h->root_maxcells = t.root_maxcells;
   h->scr_base = std::move(t.scr_base);
   h->fw = w; h->fh = hgt; h->fcn = cn; h->fdepth = depth; h->fesz = esz;
+  h->lesz = lay.esz; h->ldepth = h->pyr_kind == PBD_PYRAMID_MATLAB ? PBD_DEPTH_64F : depth;
   return PBD_OK;
 }
 // ---------------------------------------------------------------------------
@@ -324,6 +328,10 @@ static int run_image_pyramid(pbd_handle* h, const uint8_t* d_src, int stride) {
   // one launch for the first octave of every frame of the batch (cv::resize), one per octave step below it (cv::pyrDown)
   for (size_t i = 0; i < h->pyr_launches.size(); ++i) {
     const PyrLaunch& P = h->pyr_launches[i];
+    if (h->pyr_kind == PBD_PYRAMID_MATLAB) {   // featpyramid.m:24-34: area resize of the 8-bit frame into double levels, then reduce (k_pyramid_mat.hip)
+      if (i == 0) launch_resize_area(h->d_matjobs + P.job0, P.njobs, P.maxpix, h->d_matruns, h->d_mattaps, h->fcn, stride, false, d_src, h->d_pyr, h->stream);
+      else launch_reduce_f64(h->d_matjobs + P.job0, P.njobs, P.maxpix, h->fcn, h->d_pyr, h->stream);
+    } else
     if (h->fdepth != PBD_DEPTH_8U) {   // 16-bit / float / double frames (pbd_detect_image): the plain per-element kernels
       if (i == 0) launch_resize_any(h->d_pyrjobs + P.job0, P.njobs, P.maxpix, h->fcn, h->fdepth, stride, d_src, h->d_pyr, h->stream);
       else launch_pyrdown_any(h->d_pyrjobs + P.job0, P.njobs, P.maxpix, h->fcn, h->fdepth, h->d_pyr, h->stream);
@@ -338,7 +346,7 @@ static int run_image_pyramid(pbd_handle* h, const uint8_t* d_src, int stride) {
 
 static int run_hog(pbd_handle* h) {
   uint16_t* split = h->split_parts ? h->d_feat_split : nullptr;
-  launch_hog(h->d_hog_tiles, h->n_hog_tiles, h->d_hog_levels, h->d_pyr, h->d_feat, h->ts, h->fcn, h->md.sbin, h->hog_tc, h->d_hog_lut, split, h->split_parts, h->fdepth, h->stream);
+  launch_hog(h->d_hog_tiles, h->n_hog_tiles, h->d_hog_levels, h->d_pyr, h->d_feat, h->ts, h->fcn, h->md.sbin, h->hog_tc, h->d_hog_lut, split, h->split_parts, h->ldepth, h->stream);
   // boundary padding: the border ring of every level, on every frame — the compact plan's DP reuses the feature memory, and
   // pbd_set_level_features may have left a caller's border there (a frame's result never depends on what ran before it)
   if (h->pad > 0) launch_featpad(h->d_padjobs, h->d_padblocks, h->n_padblocks, h->d_feat, h->ts, split, h->split_parts, h->stream);
@@ -782,6 +790,19 @@ int pbd_set_boundary_pad(pbd_handle* h, int pad) {
   return PBD_OK;
 }
 int pbd_get_boundary_pad(const pbd_handle* h) { return h ? h->pad : 0; }
+// Pyramid kind (include/pbd_c.h): like the padding, the plan — geometry, buffers, work tables, captured graph — is per kind
+int pbd_set_pyramid_kind(pbd_handle* h, int kind) {
+  if (!h) return PBD_ERR_ARG;
+  if (kind != PBD_PYRAMID_OPENCV && kind != PBD_PYRAMID_MATLAB) return fail(h, PBD_ERR_ARG, "pyramid kind: PBD_PYRAMID_OPENCV or PBD_PYRAMID_MATLAB");
+  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (kind == h->pyr_kind) return PBD_OK;
+  ON_DEVICE(h);
+  hipStreamSynchronize(h->stream);
+  h->pyr_kind = kind;
+  free_frame(h);
+  return PBD_OK;
+}
+int pbd_get_pyramid_kind(const pbd_handle* h) { return h ? h->pyr_kind : PBD_PYRAMID_OPENCV; }
 int pbd_max_parts(const pbd_handle* h) { return h ? h->max_parts : 0; }
 
 int pbd_set_stream(pbd_handle* h, void* s) {
@@ -799,7 +820,8 @@ int pbd_pyramid_geometry(const pbd_handle* h, int w, int hgt, int* nlevels, int3
   if (!h || !nlevels) return PBD_ERR_ARG;
   static thread_local Level lv[PBD_MAX_LEVELS];
   int n = 0;
-  if (w < 3 || hgt < 3 || compute_geometry(w, hgt, h->md.sbin, h->md.interval, &n, lv)) return PBD_ERR_ARG;
+  if (w < 3 || hgt < 3 || (h->pyr_kind == PBD_PYRAMID_MATLAB ? compute_geometry_matlab(w, hgt, h->md.sbin, h->md.interval, &n, lv)
+                                                             : compute_geometry(w, hgt, h->md.sbin, h->md.interval, &n, lv))) return PBD_ERR_ARG;
   pad_geometry(h->pad, n, lv);   // (the planes of a padded handle: what the stage getters and setters address)
   *nlevels = n;
   for (int l = 0; l < n; ++l) {
@@ -847,7 +869,7 @@ int pbd_get_level_image(pbd_handle* h, int level, uint8_t* out) {
   const Level& L = h->lv[level];
   ON_DEVICE(h);
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (h->fdepth != PBD_DEPTH_8U) return fail(h, PBD_ERR_STATE, "the planned frame is not 8-bit: pbd_get_level_image_raw");
+  if (h->ldepth != PBD_DEPTH_8U) return fail(h, PBD_ERR_STATE, "the plan's level images are not 8-bit: pbd_get_level_image_raw");
   HIPCHK(h, hipMemcpy(out, h->d_pyr + L.img_off, (size_t)L.iw * L.ih * h->fcn, hipMemcpyDeviceToHost));
   return PBD_OK;
 }
@@ -856,7 +878,7 @@ int pbd_get_level_image_raw(pbd_handle* h, int level, void* out, size_t out_byte
   if (!out) return PBD_ERR_ARG;
   if (!h->have_pyr) return fail(h, PBD_ERR_STATE, "pyramid not computed");
   const Level& L = h->lv[level];
-  const size_t bytes = (size_t)L.iw * L.ih * h->fcn * h->fesz;
+  const size_t bytes = (size_t)L.iw * L.ih * h->fcn * h->lesz;
   if (out_bytes < bytes) return fail(h, PBD_ERR_CAPACITY, "pbd_get_level_image_raw: iw * ih * cn * element size bytes");
   ON_DEVICE(h);
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -930,7 +952,7 @@ int pbd_get_frame_level_image_raw(pbd_handle* h, int frame, int level, void* out
   if (!out) return PBD_ERR_ARG;
   if (!h->have_pyr) return fail(h, PBD_ERR_STATE, "pyramid not computed");
   const Level& L = h->lv[(size_t)frame * h->nlevels + level];
-  const size_t bytes = (size_t)L.iw * L.ih * h->fcn * h->fesz;
+  const size_t bytes = (size_t)L.iw * L.ih * h->fcn * h->lesz;
   if (out_bytes < bytes) return fail(h, PBD_ERR_CAPACITY, "pbd_get_frame_level_image_raw: iw * ih * cn * element size bytes");
   ON_DEVICE(h);
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1412,6 +1434,52 @@ int pbd_pyrdown_u8(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int
   return PBD_OK;
 }
 
+// resize(im, scale) of matlab/mex/resize.cc:82-106 on an interleaved double image
+int pbd_resize_area_f64(pbd_handle* h, const double* im, int w, int hgt, int cn, double scale, double* out, int* ow, int* oh) {
+  if (!h || !im || !out || !ow || !oh || w <= 0 || hgt <= 0 || (cn != 1 && cn != 3) || !(scale > 0)) return PBD_ERR_ARG;
+  if (scale > 1) return fail(h, PBD_ERR_ARG, "Invalid scaling factor (matlab/mex/resize.cc:90)");
+  const int dh = (int)std::round(hgt * scale), dw = (int)std::round(w * scale);   // resize.cc:94-95
+  if (dw <= 0 || dh <= 0 || (long long)w * hgt * cn >= (1ll << 28)) return fail(h, PBD_ERR_ARG, "pbd_resize_area_f64: empty result or image too large");
+  std::vector<MatRun> runs; std::vector<MatTap> taps;
+  if (!resize_taps(hgt, dh, runs, taps) || !resize_taps(w, dw, runs, taps)) return fail(h, PBD_ERR_ARG, "a resize tap outside the image (matlab/mex/resize.cc:53,61)");
+  ON_DEVICE(h);
+  const size_t sb = (size_t)w * hgt * cn * 8, db = (size_t)dw * dh * cn * 8;
+  uint8_t *d_im, *d_out; MatRun* d_runs; MatTap* d_taps;
+  MatJob job{0, 0, w, hgt, dw, dh, 0, dh}, *d_job;
+  HIPCHK(h, hipMalloc(&d_im, sb)); HIPCHK(h, hipMalloc(&d_out, db)); HIPCHK(h, hipMalloc(&d_job, sizeof(job)));
+  HIPCHK(h, hipMalloc(&d_runs, runs.size() * sizeof(MatRun))); HIPCHK(h, hipMalloc(&d_taps, taps.size() * sizeof(MatTap)));
+  HIPCHK(h, hipMemcpy(d_im, im, sb, hipMemcpyHostToDevice));
+  HIPCHK(h, hipMemcpy(d_job, &job, sizeof(job), hipMemcpyHostToDevice));
+  HIPCHK(h, hipMemcpy(d_runs, runs.data(), runs.size() * sizeof(MatRun), hipMemcpyHostToDevice));
+  HIPCHK(h, hipMemcpy(d_taps, taps.data(), taps.size() * sizeof(MatTap), hipMemcpyHostToDevice));
+  launch_resize_area(d_job, 1, dw * dh, d_runs, d_taps, cn, w * cn, true, d_im, d_out, h->stream);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemcpy(out, d_out, db, hipMemcpyDeviceToHost));
+  hipFree(d_im); hipFree(d_out); hipFree(d_job); hipFree(d_runs); hipFree(d_taps);
+  *ow = dw; *oh = dh;
+  return PBD_OK;
+}
+// reduce(im) of matlab/mex/reduce.cc:50-70 on an interleaved double image
+int pbd_reduce_f64(pbd_handle* h, const double* im, int w, int hgt, int cn, double* out, int* ow, int* oh) {
+  if (!h || !im || !out || !ow || !oh || (cn != 1 && cn != 3)) return PBD_ERR_ARG;
+  if (w < 5 || hgt < 5) return fail(h, PBD_ERR_ARG, "pbd_reduce_f64: both dimensions >= 5 (matlab/mex/reduce.cc:24-42 reads rows 0..2 and the last three of each axis)");
+  if ((long long)w * hgt * cn >= (1ll << 28)) return fail(h, PBD_ERR_ARG, "pbd_reduce_f64: image too large");
+  const int dh = (int)std::round(hgt * .5), dw = (int)std::round(w * .5);   // reduce.cc:58-59
+  ON_DEVICE(h);
+  const size_t sb = (size_t)w * hgt * cn * 8, db = (size_t)dw * dh * cn * 8;
+  uint8_t* d_buf;
+  MatJob job{0, (unsigned long long)sb, w, hgt, dw, dh, 0, 0}, *d_job;
+  HIPCHK(h, hipMalloc(&d_buf, sb + db)); HIPCHK(h, hipMalloc(&d_job, sizeof(job)));
+  HIPCHK(h, hipMemcpy(d_buf, im, sb, hipMemcpyHostToDevice));
+  HIPCHK(h, hipMemcpy(d_job, &job, sizeof(job), hipMemcpyHostToDevice));
+  launch_reduce_f64(d_job, 1, dw * dh, cn, d_buf, h->stream);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemcpy(out, d_buf + sb, db, hipMemcpyDeviceToHost));
+  hipFree(d_buf); hipFree(d_job);
+  *ow = dw; *oh = dh;
+  return PBD_OK;
+}
+
 int pbd_nms_map(pbd_handle* h, const float* src, int rows, int cols, int sz, uint8_t* dst) {
   if (!h || !src || !dst || rows <= 0 || cols <= 0 || sz < 0) return PBD_ERR_ARG;
   ON_DEVICE(h);
@@ -1445,7 +1513,7 @@ int pbd_get_work(const pbd_handle* h, double work[6]) {
   for (int l = 0; l < h->nlevels; ++l) {
     if (!h->lv[l].active) continue;
     C += (double)h->lv[l].cw * h->lv[l].ch;
-    pix += (double)h->lv[l].iw * h->lv[l].ih * h->fcn * h->fesz;   // (bytes: pixels of the frame's own depth)
+    pix += (double)h->lv[l].iw * h->lv[l].ih * h->fcn * h->lesz;   // (bytes: pixels of the level images' depth)
   }
   // reference element types (scores of type T: 4 or 8 bytes, int32 pointers)
   const double ts = h->ts;

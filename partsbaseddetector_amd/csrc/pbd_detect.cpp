@@ -321,6 +321,7 @@ int pbd_tune_plan(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int 
   // (a member of an RCCL-gathering group collects through the group only: the measurement's own collect() would fail with the frame
   //  left pending — ADVICE r05)
   if (h->d_gsend) return fail(h, PBD_ERR_STATE, "handle belongs to an RCCL-gathering pbd_group: tune a handle of its own");
+  if (h->pyr_kind == PBD_PYRAMID_MATLAB) return fail(h, PBD_ERR_UNSUPPORTED, "pbd_tune_plan: PBD_PYRAMID_OPENCV handles (tune before pbd_set_pyramid_kind)");
   if (chosen) *chosen = 0;
   if (ms) ms[0] = ms[1] = 0.0;
   ON_DEVICE(h);

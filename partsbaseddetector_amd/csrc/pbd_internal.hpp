@@ -123,6 +123,7 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   int fw = 0, fh = 0, fcn = 0, nlevels = 0;     // nlevels: levels of ONE frame
   int dt_geom = 0;                               // distance-transform block geometry of float handles: 0 = the measured rule (plan_frame), 1 = 256 lanes / 40 KB, 2 = 128 lanes / 25 KB (pbd_tune_plan)
   int fdepth = 0, fesz = 1;                      // depth of the planned frame's pixels (PBD_DEPTH_*: cv::Mat::depth()), bytes per element
+  int ldepth = 0, lesz = 1;                      // the same of the plan's LEVEL images: the frame's, or PBD_DEPTH_64F under PBD_PYRAMID_MATLAB
   // A batch of B same-sized frames is planned as B x nlevels "virtual levels" (frame f's level l = f * nlevels + l):
   // every stage is driven by per-level tables, so one launch of a stage then covers all frames of the batch — four
   // times the blocks per launch, the thin rounds of the DP fill the chip and launch tails are paid once per batch.
@@ -130,6 +131,7 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   std::vector<Level> lv;                        // [nvl]
   PyrJob* d_pyrjobs = nullptr;                  // resize jobs, then the pyrDown jobs octave by octave
   std::vector<PyrLaunch> pyr_launches;          // [0]: resize, [1..]: pyrDown octave steps
+  MatJob* d_matjobs = nullptr; MatRun* d_matruns = nullptr; MatTap* d_mattaps = nullptr;   // PBD_PYRAMID_MATLAB: the jobs pyr_launches index, the resize's tap lists
   size_t cells = 0, pyr_bytes = 0;
   bool have_pyr = false, have_feat = false, have_resp = false, have_dp = false;
   // Compact memory plan only: the DP reuses the feature / response memory, so after min() every plane is stale until it
@@ -500,6 +502,10 @@ void launch_resize(const PyrJob* jobs, int njobs, int maxpix, int cn, int sstrid
 void launch_pyrdown(const PyrJob* jobs, int njobs, int maxw, int maxh, int cn, uint8_t* pyr, hipStream_t s);
 void launch_hog(const HogTile* tiles, int ntiles, const LevelDev* levels, const uint8_t* pyr, void* feat, int ts,
                 int cn, int sbin, int tc, const uint8_t* binlut, uint16_t* split, int split_parts, int depth, hipStream_t s);   // depth: PBD_DEPTH_* of the level images
+// PBD_PYRAMID_MATLAB (k_pyramid_mat.hip): job offsets in bytes, sstride in source elements
+void launch_resize_area(const MatJob* jobs, int njobs, int maxpix, const MatRun* runs, const MatTap* taps, int cn, int sstride,
+                        bool src_f64, const uint8_t* src, uint8_t* pyr, hipStream_t s);
+void launch_reduce_f64(const MatJob* jobs, int njobs, int maxpix, int cn, uint8_t* pyr, hipStream_t s);
 // the image depths beyond 8 bits (k_pyramid.hip): job offsets in bytes, sstride in bytes
 void launch_resize_any(const PyrJob* jobs, int njobs, int maxpix, int cn, int depth, int sstride, const uint8_t* src, uint8_t* pyr, hipStream_t s);
 void launch_pyrdown_any(const PyrJob* jobs, int njobs, int maxpix, int cn, int depth, uint8_t* pyr, hipStream_t s);

@@ -46,6 +46,58 @@ int compute_geometry(int w, int h, int sbin, int interval, int* nlevels, Level* 
   return 0;
 }
 
+// matlab/detection/featpyramid.m:13-34,47 — all in double; the image sizes are what resize.cc:94-95 and reduce.cc:58-59 derive (C round(),
+// halves away from zero); cells as above (features.cc and k_hog agree on them)
+int compute_geometry_matlab(int w, int h, int sbin, int interval, int* nlevels, Level* lv) {
+  const double sc = std::pow(2.0, 1.0 / interval);                                        // featpyramid.m:13
+  const int n = 1 + (int)std::floor(std::log(std::min(w, h) / (5.0 * sbin)) / std::log(sc));   // :15
+  if (n < interval || n > PBD_MAX_LEVELS) return -1;
+  std::vector<double> scale((size_t)n);
+  for (int i = 0; i < interval; ++i) {
+    const double s = 1.0 / std::pow(sc, i);                                               // :25
+    lv[i].ih = (int)std::round(h * s);                                                    // resize.cc:94-95
+    lv[i].iw = (int)std::round(w * s);
+    scale[i] = sbin / s;                                                                  // featpyramid.m:27,47
+    for (int j = i + interval; j < n; j += interval) {
+      if (lv[j - interval].iw < 5 || lv[j - interval].ih < 5) return -1;                  // (reduce.cc:24,42 read three, :29 five source rows)
+      lv[j].ih = (int)std::round(lv[j - interval].ih * .5);                               // reduce.cc:58-59
+      lv[j].iw = (int)std::round(lv[j - interval].iw * .5);
+      scale[j] = 2.0 * scale[j - interval];                                               // featpyramid.m:32,47
+    }
+  }
+  for (int l = 0; l < n; ++l) {
+    lv[l].scale = (float)scale[l];                                                        // the handle's scale type, as the last step
+    lv[l].bw = (int)std::round((float)lv[l].iw / (float)sbin);
+    lv[l].bh = (int)std::round((float)lv[l].ih / (float)sbin);
+    lv[l].cw = std::max(lv[l].bw - 2, 0);
+    lv[l].ch = std::max(lv[l].bh - 2, 0);
+  }
+  *nlevels = n;
+  return 0;
+}
+
+// matlab/mex/resize.cc:30-66, statement by statement; one run per destination index instead of the `di` field
+bool resize_taps(int slen, int dlen, std::vector<MatRun>& runs, std::vector<MatTap>& taps) {
+  const size_t t0 = taps.size();
+  const double scale = (double)dlen / (double)slen;
+  const double invscale = (double)slen / (double)dlen;
+  for (int dy = 0; dy < dlen; ++dy) {
+    const double fsy1 = dy * invscale;
+    const double fsy2 = fsy1 + invscale;
+    const int sy1 = (int)std::ceil(fsy1);
+    const int sy2 = (int)std::floor(fsy2);
+    MatRun r{(int)taps.size(), 0};
+    if (sy1 - fsy1 > 1e-3) taps.push_back(MatTap{(sy1 - fsy1) * scale, sy1 - 1, 0});
+    for (int sy = sy1; sy < sy2; ++sy) taps.push_back(MatTap{scale, sy, 0});
+    if (fsy2 - sy2 > 1e-3) taps.push_back(MatTap{(fsy2 - sy2) * scale, sy2, 0});
+    r.count = (int)taps.size() - r.first;
+    runs.push_back(r);
+  }
+  for (size_t t = t0; t < taps.size(); ++t)
+    if (taps[t].si < 0 || taps[t].si >= slen) return false;   // (resize.cc:53,61 assert it)
+  return true;
+}
+
 void pad_geometry(int pad, int nlevels, Level* lv) {
   for (int l = 0; l < nlevels; ++l)
     if (lv[l].cw > 0 && lv[l].ch > 0) { lv[l].cw += 2 * pad; lv[l].ch += 2 * pad; }
@@ -337,6 +389,14 @@ int plan_layout(const HostModel& hm, const FrameSpec& f, FrameLayout& out, std::
   out = FrameLayout{};
   int n1 = 0;
   std::vector<Level> lv((size_t)PBD_MAX_LEVELS, Level{});
+  const bool matlab = hm.pyr_kind == PBD_PYRAMID_MATLAB;
+  if (matlab && f.depth != PBD_DEPTH_8U)
+    return fail(err, PBD_ERR_UNSUPPORTED, "PBD_PYRAMID_MATLAB: 8-bit frames (the level images are double whatever the frame; pbd_set_pyramid_kind)");
+  if (matlab) {
+    if (f.w < 3 || f.h < 3 || compute_geometry_matlab(f.w, f.h, m.sbin, m.interval, &n1, lv.data()))
+      return fail(err, PBD_ERR_ARG, "image too small: the pyramid needs at least `interval` levels and reduce() sources of 5 x 5 pixels "
+                                    "(matlab/detection/featpyramid.m:15, matlab/mex/reduce.cc:24-42)");
+  } else
   if (f.w < 3 || f.h < 3 || compute_geometry(f.w, f.h, m.sbin, m.interval, &n1, lv.data()))
     return fail(err, PBD_ERR_ARG, "image too small: the pyramid needs at least `interval` levels "
                                   "(src/HOGFeatures.cpp:99,114)");
@@ -344,7 +404,8 @@ int plan_layout(const HostModel& hm, const FrameSpec& f, FrameLayout& out, std::
   // A batch of B same-sized frames is planned as B x nlevels "virtual levels" (frame f's level l = f * nlevels + l)
   const int n = n1 * f.batch;
   out.nlevels = n1; out.batch = f.batch; out.nvl = n;
-  out.esz = depth_esz(f.depth);
+  out.src_esz = depth_esz(f.depth);
+  out.esz = matlab ? 8 : out.src_esz;
   out.lv.resize(n);
   for (int fr = 0; fr < f.batch; ++fr)
     for (int l = 0; l < n1; ++l) out.lv[fr * n1 + l] = lv[l];
@@ -364,6 +425,8 @@ int plan_layout(const HostModel& hm, const FrameSpec& f, FrameLayout& out, std::
     if (L.active) out.act_cells += (size_t)L.cw * L.ch;
   }
   out.cells = cells; out.pyr_bytes = pyr;
+  if (matlab && pyr > PBD_MATPYR_MAX_BYTES)
+    return fail(err, PBD_ERR_UNSUPPORTED, "PBD_PYRAMID_MATLAB: the double level images of this geometry exceed the plan's budget for them (2 GiB)");
   if (cells >= (1u << 31)) return fail(err, PBD_ERR_UNSUPPORTED, "frame too large");
   for (const std::vector<int>& rnd : hm.rounds) {
     size_t k = 0;
@@ -391,7 +454,7 @@ int plan_layout(const HostModel& hm, const FrameSpec& f, FrameLayout& out, std::
     out.buf[b] = BufPlace{(int)out.regions.size(), 0, std::max<size_t>(bytes, 1)};
     out.regions.push_back(out.buf[b].bytes);
   };
-  own(FB_IMG, (size_t)f.w * f.h * f.cn * out.esz * f.batch);
+  own(FB_IMG, (size_t)f.w * f.h * f.cn * out.src_esz * f.batch);
   own(FB_RESP, cells * m.nfilters * ts);
   const size_t pk_bytes = cells * std::max(hm.nplanes, 1), feat_bytes = cells * PBD_FLEN * ts;
   // DT planes.  The passes' own pointer planes (int16) stay for the whole frame: back-tracking composes Ix / Iy from
@@ -538,7 +601,7 @@ static void pyramid_jobs(const HostModel& hm, const FrameSpec& f, const FrameLay
   for (int fr = 0; fr < f.batch; ++fr)
     for (int i = 0; i < interval; ++i) {
       const Level& L = lay.lv[fr * n1 + i];
-      jobs.push_back(PyrJob{(unsigned long long)fr * f.w * f.h * f.cn * lay.esz, (unsigned long long)L.img_off, f.w, f.h, L.iw, L.ih});
+      jobs.push_back(PyrJob{(unsigned long long)fr * f.w * f.h * f.cn * lay.src_esz, (unsigned long long)L.img_off, f.w, f.h, L.iw, L.ih});
       R.maxpix = std::max(R.maxpix, L.iw * L.ih);
     }
   R.njobs = (int)jobs.size();
@@ -555,6 +618,43 @@ static void pyramid_jobs(const HostModel& hm, const FrameSpec& f, const FrameLay
     D.njobs = (int)jobs.size() - D.job0;
     out.pyr_launches.push_back(D);
   }
+}
+
+// PBD_PYRAMID_MATLAB: the same launches — the first octave of every frame (area resize from the 8-bit frame, its tap lists per level
+// and axis shared by the frames of a batch), then one launch per further octave (reduce)
+static bool pyramid_jobs_matlab(const HostModel& hm, const FrameSpec& f, const FrameLayout& lay, FrameTables& out) {
+  const int n1 = lay.nlevels, interval = hm.md.interval;
+  std::vector<MatJob>& jobs = out.matjobs;
+  std::vector<int> yrun0((size_t)interval), xrun0((size_t)interval);
+  for (int i = 0; i < interval; ++i) {
+    const Level& L = lay.lv[i];
+    yrun0[i] = (int)out.matruns.size();
+    if (!resize_taps(f.h, L.ih, out.matruns, out.mattaps)) return false;   // resize.cc:101: the rows axis first
+    xrun0[i] = (int)out.matruns.size();
+    if (!resize_taps(f.w, L.iw, out.matruns, out.mattaps)) return false;   // :102
+  }
+  PyrLaunch R{0, 0, 1, 1, 1};
+  for (int fr = 0; fr < f.batch; ++fr)
+    for (int i = 0; i < interval; ++i) {
+      const Level& L = lay.lv[fr * n1 + i];
+      jobs.push_back(MatJob{(unsigned long long)fr * f.w * f.h * f.cn * lay.src_esz, (unsigned long long)L.img_off, f.w, f.h, L.iw, L.ih, yrun0[i], xrun0[i]});
+      R.maxpix = std::max(R.maxpix, L.iw * L.ih);
+    }
+  R.njobs = (int)jobs.size();
+  out.pyr_launches.push_back(R);
+  for (int base = interval; base < n1; base += interval) {
+    PyrLaunch D{(int)jobs.size(), 0, 1, 1, 1};
+    for (int fr = 0; fr < f.batch; ++fr)
+      for (int j = base; j < std::min(base + interval, n1); ++j) {
+        const Level &S = lay.lv[fr * n1 + j - interval], &L = lay.lv[fr * n1 + j];
+        jobs.push_back(MatJob{(unsigned long long)S.img_off, (unsigned long long)L.img_off, S.iw, S.ih, L.iw, L.ih, 0, 0});
+        D.maxpix = std::max(D.maxpix, L.iw * L.ih);
+        D.maxw = std::max(D.maxw, L.iw); D.maxh = std::max(D.maxh, L.ih);
+      }
+    D.njobs = (int)jobs.size() - D.job0;
+    out.pyr_launches.push_back(D);
+  }
+  return true;
 }
 
 // HOG tiles: TC x TC cells, the tile shrunk until its LDS footprint fits; filter-bank tiles: 16 x 16 cells
@@ -861,7 +961,9 @@ static void root_tables(const HostModel& hm, const FrameLayout& lay, const Plane
 int plan_tables(const HostModel& hm, const FrameSpec& f, const FrameLayout& lay, const FrameBases& b, int ncu, int dt_geom,
                 const PlanKnobs& kn, FrameTables& out, std::string* err) {
   out = FrameTables{};
-  pyramid_jobs(hm, f, lay, out);
+  if (hm.pyr_kind == PBD_PYRAMID_MATLAB) {
+    if (!pyramid_jobs_matlab(hm, f, lay, out)) return fail(err, PBD_ERR_ARG, "PBD_PYRAMID_MATLAB: a resize tap outside the frame (matlab/mex/resize.cc:53,61)");
+  } else pyramid_jobs(hm, f, lay, out);
   for (const Level& L : lay.lv)
     out.levels.push_back(LevelDev{L.iw, L.ih, L.bw, L.bh, L.cw, L.ch, (unsigned long long)L.img_off, (unsigned long long)L.cell_off});
   if (hm.pad > 0)

@@ -28,6 +28,13 @@ struct Level {
 // one image of the pyramid: level image (frame f, level l) from the frame itself (cv::resize, first octave) or from
 // level l - interval (cv::pyrDown); tables in device memory, one launch covers every job of a stage
 struct PyrJob { unsigned long long soff, doff; int sw, sh, dw, dh; };
+// PBD_PYRAMID_MATLAB (k_pyramid_mat.hip): one level image, in double, from the 8-bit frame by the area resize of matlab/mex/resize.cc
+// (first octave) or from level l - interval by the 5-tap reduce of matlab/mex/reduce.cc.  The resize reads resize1dtran's
+// interpolation cache (resize.cc:35-66), built here on the host in double: run yrun0 + dy / xrun0 + dx of the run table lists the
+// taps of destination row dy / column dx, `count` taps from tap `first`, in the order the reference's loop appends them.
+struct MatTap { double alpha; int si, pad; };
+struct MatRun { int first, count; };
+struct MatJob { unsigned long long soff, doff; int sw, sh, dw, dh, yrun0, xrun0; };   // soff / doff: bytes
 struct HogTile { int level, cy0, cx0, pad; };
 struct LevelDev {    // per level, device copy
   int iw, ih, bw, bh, cw, ch;
@@ -132,6 +139,7 @@ struct BackLevel {   // per (level, comp) info for backtracking
 // The kernels read these tables byte for byte: their layouts are pinned.
 static_assert(sizeof(Level) == 56, "Level layout");
 static_assert(sizeof(PyrJob) == 32, "PyrJob layout");
+static_assert(sizeof(MatTap) == 16 && sizeof(MatRun) == 8 && sizeof(MatJob) == 40, "MatTap / MatRun / MatJob layout");
 static_assert(sizeof(HogTile) == 16, "HogTile layout");
 static_assert(sizeof(LevelDev) == 40, "LevelDev layout");
 static_assert(sizeof(ConvTile) == 16, "ConvTile layout");
@@ -180,6 +188,7 @@ struct HostModel {
   int conv_mode = PBD_CONV_EXACT;   // resolved: never PBD_CONV_AUTO
   int split_parts = 0;       // 3: PBD_CONV_SPLIT (bfloat16 parts), 2: PBD_CONV_SPLIT_F16 (binary16 parts), 0: no split bank
   int pad = 0;               // pbd_set_boundary_pad: cells of padding around every level's feature map (0: off, the reference's state)
+  int pyr_kind = PBD_PYRAMID_OPENCV;   // pbd_set_pyramid_kind: PBD_PYRAMID_MATLAB = the pyramid of matlab/detection/featpyramid.m:13-34 (double level images)
   int nms_sz = 0;            // pbd_options.reserved[0]: window of the score-map NMS in front of the back-tracking (0: off, the reference's state)
   int max_parts = 0, nslots = 0, nplanes = 0;
   std::vector<PartInfo> parts;                 // flat parts
@@ -229,7 +238,8 @@ enum FrameBuf { FB_IMG, FB_PYR, FB_FEAT, FB_RESP, FB_PK, FB_ROOTV, FB_ROOTI, FB_
                 FB_ACC, FB_FEAT_SPLIT, FB_COUNT };
 struct BufPlace { int region = -1; size_t offset = 0, bytes = 0; };   // region -1: the plan has no such buffer
 struct FrameLayout {
-  int nlevels = 0, batch = 1, nvl = 0, esz = 1;   // nlevels: levels of ONE frame; nvl = batch * nlevels virtual levels
+  int nlevels = 0, batch = 1, nvl = 0, esz = 1;   // nlevels: levels of ONE frame; nvl = batch * nlevels virtual levels; esz: bytes per element of the LEVEL images
+  int src_esz = 1;                               // bytes per element of the frame itself (PBD_PYRAMID_MATLAB: 8-bit frames, double level images; else esz)
   std::vector<Level> lv;                         // [nvl]
   size_t cells = 0, pyr_bytes = 0;
   size_t act_cells = 0;                          // cells of the active levels
@@ -253,6 +263,10 @@ struct RoundLaunch { int xtask0, nxtasks, ytask0, nytasks; size_t lds_x, lds_y; 
 struct FrameTables {
   std::vector<PyrJob> pyrjobs;                   // resize jobs, then the pyrDown jobs octave by octave
   std::vector<PyrLaunch> pyr_launches;           // [0]: resize, [1..]: pyrDown octave steps
+  // PBD_PYRAMID_MATLAB (pyrjobs then empty; pyr_launches index matjobs): area-resize jobs, then the reduce jobs octave by octave
+  std::vector<MatJob> matjobs;
+  std::vector<MatRun> matruns;
+  std::vector<MatTap> mattaps;
   std::vector<LevelDev> levels;
   // boundary padding only (else empty): the levels as k_hog addresses them — cw is the padded pitch and cell_off the interior's first
   // cell (cell_off + pad * cw + pad), so the kernel's store needs no offset of its own — and the border ring's jobs / blocks
@@ -297,6 +311,13 @@ DtMap dt_map(const void* src, void* dst, int16_t* ptr, float wq, float wl, int o
 
 // pyramid geometry of one frame (HOGFeatures<T>::pyramid): 0, or -1 when the frame has fewer than `interval` or more than PBD_MAX_LEVELS levels
 int compute_geometry(int w, int h, int sbin, int interval, int* nlevels, Level* lv);
+// PBD_PYRAMID_MATLAB: the same for matlab/detection/featpyramid.m:13-34 (levels in double arithmetic, sizes by C round(), box scale
+// sbin / s_i doubled per octave); also -1 where a reduce would read a level with a dimension below 5
+int compute_geometry_matlab(int w, int h, int sbin, int interval, int* nlevels, Level* lv);
+// resize1dtran's interpolation cache for one axis (matlab/mex/resize.cc:30-66): appends dlen runs and their taps; false
+// where a tap's source index falls outside [0, slen) (the reference asserts it cannot)
+bool resize_taps(int slen, int dlen, std::vector<MatRun>& runs, std::vector<MatTap>& taps);
+#define PBD_MATPYR_MAX_BYTES ((size_t)1 << 31)   // PBD_PYRAMID_MATLAB: the level images of a plan (all frames of a batch), in double
 // boundary padding: every level that has cells grows by `pad` cells on each side (copyMakeBorder(feature, padded, pad, pad, pad * flen,
 // pad * flen, ...), src/HOGFeatures.cpp:147); bw / bh stay the HOG blocks, the interior is (bw - 2) x (bh - 2)
 void pad_geometry(int pad, int nlevels, Level* lv);

@@ -259,6 +259,7 @@ class PartsBasedDetector:
         self._cluster_tol: Optional[float] = None   # setObjectClusters: None = off
         self._part_scores = False                # setPartScores
         self._boundary_pad = 0                   # setBoundaryPad
+        self._pyramid_kind = "opencv"            # setPyramidKind
         self._dtype = np.dtype(dtype)
         self._lb, self._le = level_begin, level_end
         self._h: Optional[capi.Handle] = None
@@ -287,6 +288,27 @@ class PartsBasedDetector:
             self._h.set_part_scores(True)
         if self._boundary_pad:
             self._h.set_boundary_pad(self._boundary_pad)
+        if self._pyramid_kind != "opencv":
+            self._h.set_pyramid_kind(self._PYRAMID_KINDS[self._pyramid_kind])
+
+    _PYRAMID_KINDS = {"opencv": capi.PBD_PYRAMID_OPENCV, "matlab": capi.PBD_PYRAMID_MATLAB}
+
+    @property
+    def pyramid_kind(self) -> str:
+        """"opencv" or "matlab" (setPyramidKind)"""
+        return self._pyramid_kind
+
+    def setPyramidKind(self, kind: str = "matlab") -> None:
+        """The image pyramid under the features.  "opencv" (the default): HOGFeatures<T>::pyramid, cv::resize and cv::pyrDown in the
+        pixel type (src/HOGFeatures.cpp:95-127).  "matlab": matlab/detection/featpyramid.m:13-34 — the frame goes to double once,
+        matlab/mex/resize.cc makes the first octave, matlab/mex/reduce.cc every further one, nothing is rounded back to 8 bits —
+        with its level count, level sizes and box scales: the levels the MATLAB pipeline trains and evaluates its models on.
+        8-bit frames only.  With setBoundaryPad the two together are featpyramid.m.  Kept across distributeModel()."""
+        if kind not in self._PYRAMID_KINDS:
+            raise ValueError('setPyramidKind: "opencv" or "matlab"')
+        if self._h is not None:
+            self._h.set_pyramid_kind(self._PYRAMID_KINDS[kind])
+        self._pyramid_kind = kind
 
     @property
     def boundary_pad(self) -> int:

@@ -1,5 +1,5 @@
 // demo.cpp — the reference's canonical caller (src/demo.cpp:55-118) against the MI355X path:
-//   pbd_demo model.bin image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE]
+//   pbd_demo model.bin image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE] [--matlab-pyramid]
 //   pbd_demo model.bin image.raw width height channels perturb-features <responses-out.bin>
 //   pbd_demo model.bin image.raw width height channels oracle-responses <responses-in.bin>
 // deserialize -> distributeModel -> detect -> Candidate::sort, then prints the candidates (the
@@ -21,7 +21,7 @@ using namespace pbd;
 //             pointer at that cell redirected): the candidates must be those of the edited tables.
 template <typename T>
 static void run(Model& model, const Mat& im, bool stagewise, int special = 0, const char* io_file = nullptr, bool part_scores = false, int pad = 0,
-                const char* features_file = nullptr, const float* nms_parts = nullptr) {
+                const char* features_file = nullptr, const float* nms_parts = nullptr, bool matlab_pyramid = false) {
   PartsBasedDetector<T> pbd(0, PBD_CONV_EXACT);
   if (nms_parts && !stagewise) {   // the fused detect() sorts and suppresses on the GPU
     pbd.setCandidateFilter(PBD_CAND_SORT_NMS, *nms_parts);
@@ -29,6 +29,7 @@ static void run(Model& model, const Mat& im, bool stagewise, int special = 0, co
   }
   pbd.setPartScores(part_scores);
   pbd.setBoundaryPad(pad);
+  if (matlab_pyramid) pbd.setPyramidKind(PBD_PYRAMID_MATLAB);
   pbd.distributeModel(model);
   vectorCandidate candidates;
   if (stagewise) {
@@ -140,6 +141,7 @@ int main(int argc, char** argv) {
   bool part_scores = false;   // --part-scores (anywhere): per detection, the re-scored total, the root score and the weakest part
   const char* features_file = nullptr;   // --features FILE (anywhere): the detections' dense feature vectors, written to FILE
   float nms_overlap = 0.f; const float* nms_parts = nullptr;   // --nms-parts OVERLAP (anywhere): sort + nms.m's part-wise NMS, the 1000 best
+  bool matlab_pyramid = false;   // --matlab-pyramid (anywhere): the image pyramid of matlab/detection/featpyramid.m (area resize + reduce, in double)
   int pad = 0;                // --pad N (anywhere): N cells of boundary padding around every pyramid level (0: off)
   for (int i = 1; i < argc; ++i)
     if (std::string(argv[i]) == "--pad") {
@@ -164,13 +166,18 @@ int main(int argc, char** argv) {
       for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
       argc -= 2; --i;
     } else
+    if (std::string(argv[i]) == "--matlab-pyramid") {
+      matlab_pyramid = true;
+      for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
+      --argc; --i;
+    } else
     if (std::string(argv[i]) == "--part-scores") {
       part_scores = true;
       for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
       --argc; --i;
     }
   if (argc < 6 || argc > 8) {
-    printf("Usage: pbd_demo model_file image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE] [--nms-parts OVERLAP]\n");
+    printf("Usage: pbd_demo model_file image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE] [--nms-parts OVERLAP] [--matlab-pyramid]\n");
     exit(-1);
   }
   // determine the type of model to read (src/demo.cpp:63-82)
@@ -197,8 +204,8 @@ int main(int argc, char** argv) {
   try {
     if (part_scores && stagewise) { printf("--part-scores: the fused detect() only\n"); exit(-1); }
     if (features_file && special) { printf("--features: not with %s\n", mode.c_str()); exit(-1); }
-    if (mode.find("double") != std::string::npos) run<double>(model, im, stagewise, 0, nullptr, part_scores, pad, features_file, nms_parts);
-    else run<float>(model, im, stagewise, special, special ? argv[7] : nullptr, part_scores, pad, features_file, nms_parts);
+    if (mode.find("double") != std::string::npos) run<double>(model, im, stagewise, 0, nullptr, part_scores, pad, features_file, nms_parts, matlab_pyramid);
+    else run<float>(model, im, stagewise, special, special ? argv[7] : nullptr, part_scores, pad, features_file, nms_parts, matlab_pyramid);
   } catch (const Exception& e) {
     printf("error %d: %s\n", e.code, e.what());
     return 1;

@@ -354,6 +354,8 @@ class Device {
   void setPartScores(bool on) { check(pbd_set_part_scores(h, on ? 1 : 0)); }
   // padded feature pyramid with the boundary-occlusion feature (src/HOGFeatures.cpp:147-148): pad cells around every level, 0 = off
   void setBoundaryPad(int pad) { check(pbd_set_boundary_pad(h, pad)); }
+  // the image pyramid under the features: PBD_PYRAMID_OPENCV (src/HOGFeatures.cpp:95-127) or PBD_PYRAMID_MATLAB (matlab/detection/featpyramid.m:13-34)
+  void setPyramidKind(int kind) { check(pbd_set_pyramid_kind(h, kind)); }
 };
 
 // ---- include/IFeatures.hpp:49-73 --------------------------------------------------------------
@@ -376,6 +378,9 @@ class HipHOGFeatures : public IFeatures {          // include/HOGFeatures.hpp:52
   // The lines src/HOGFeatures.cpp:147-148 leave commented out — copyMakeBorder(feature, padded, 3, 3, ...) + boundaryOcclusionFeature(padded,
   // flen_, 3) — for every level, on the GPU: pyramid() then hands out the padded features (0 = off, the default; 3 = the reference's literal)
   void setBoundaryPad(int pad) { dev_->setBoundaryPad(pad); }
+  // featpyramid.m:13-34 instead of :95-127 below: the frame in double, matlab/mex/resize.cc for the first octave, matlab/mex/reduce.cc for the
+  // rest, with its own level count, sizes and scales (PBD_PYRAMID_MATLAB; 8-bit frames only).  PBD_PYRAMID_OPENCV: the default
+  void setPyramidKind(int kind) { dev_->setPyramidKind(kind); }
   void pyramid(const Mat& im, vectorMat& pyrafeatures) override {   // src/HOGFeatures.cpp:95-151
     // :136-146 dispatches features<uint8_t | uint16_t | float | double> on im.depth(); any other depth: StsUnsupportedFormat (the library refuses it)
     dev_->check(pbd_pyramid_image(dev_->h, im.ptr<uint8_t>(), im.depth(), im.cols, im.rows, im.channels(), (int)im.step()));
@@ -642,6 +647,7 @@ class PartsBasedDetector {
   bool depth_on_ = false; float zfactor_ = 0.03f;
   bool part_scores_on_ = false;
   int boundary_pad_ = 0;
+  int pyramid_kind_ = PBD_PYRAMID_OPENCV;
   // the last detect's per-part scores -> the `n` candidates it appended: fills Candidate::confidence_ of the non-root parts
   void attach_part_scores(vectorCandidate& candidates, int n, int mp) {
     if (!part_scores_on_ || n == 0) return;
@@ -677,6 +683,17 @@ class PartsBasedDetector {
     if (depth_on_) dev_->setDepthFilter(true, zfactor_);
     if (part_scores_on_) dev_->setPartScores(true);
     if (boundary_pad_) dev_->setBoundaryPad(boundary_pad_);
+    if (pyramid_kind_ != PBD_PYRAMID_OPENCV) dev_->setPyramidKind(pyramid_kind_);
+  }
+  // The image pyramid detect() builds its features on.  PBD_PYRAMID_OPENCV (the default): HOGFeatures<T>::pyramid, cv::resize and
+  // cv::pyrDown in the pixel type (src/HOGFeatures.cpp:95-127).  PBD_PYRAMID_MATLAB: matlab/detection/featpyramid.m:13-34 — the frame
+  // goes to double once, matlab/mex/resize.cc makes the first octave, matlab/mex/reduce.cc every further one — with its level count,
+  // level sizes and box scales: the levels the MATLAB pipeline trains and evaluates its models on.  8-bit frames only.  With
+  // setBoundaryPad the two together are featpyramid.m.  Kept across distributeModel().
+  void setPyramidKind(int kind) {
+    if (kind != PBD_PYRAMID_OPENCV && kind != PBD_PYRAMID_MATLAB) throw Exception(PBD_ERR_ARG, "setPyramidKind: PBD_PYRAMID_OPENCV or PBD_PYRAMID_MATLAB");
+    if (dev_) dev_->setPyramidKind(kind);
+    pyramid_kind_ = kind;
   }
   // The third step detect()'s author left commented out (src/HOGFeatures.cpp:147-148): every pyramid level surrounded by `pad` cells
   // that hold 0 and, in the last channel, 1 — the "outside the image" value the models are trained with (matlab/detection/
