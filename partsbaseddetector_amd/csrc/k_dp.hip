@@ -115,6 +115,8 @@ __device__ __forceinline__ GP(char) fold_qw_lane(unsigned long long v, int l) {
   const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
   return (GP(char))(((unsigned long long)hi << 32) | lo);
 }
+__device__ __forceinline__ float fold_minnum(float a, float b) { return __builtin_fminf(a, b); }
+__device__ __forceinline__ double fold_minnum(double a, double b) { return __builtin_fmin(a, b); }
 template <typename T, int M, int U>
 __device__ __forceinline__ void fold_children(const FoldJob* __restrict__ J, const unsigned (&off)[U], T (&acc)[U][M], unsigned long long cv,
                                               int nch) {   // nch = J->nch (k_dt_pass has it from the task's extension record)
@@ -158,13 +160,47 @@ __device__ __forceinline__ void fold_children(const FoldJob* __restrict__ J, con
     // branch: a branch here made the compiler wait for plane 0's loads (the code both sides share) before it issued the loads of
     // the other planes — two memory round trips per child.  No `k < K` test either: planes / bias rows beyond K repeat mixture K - 1.
     const int K = C.K;
-    // The winning mixture (Ik, :150) is NOT kept: fold_pick's index is dead here and costs nothing.  k_backtrack picks it again for
-    // the cells it visits, k_ik_fill for whole planes on request (fold_pick.hpp).
+    // The winning mixture (Ik, :150) is NOT kept, so the message is taken in its value form (fold_pick.hpp: fold_max): adds and a maximum, no
+    // compare / select chain for an index nobody reads.  k_backtrack picks the index again for the cells it visits, k_ik_fill for whole planes
+    // on request.  The maximum is fold_pick's value unless it is a zero (tied zeros of both signs: the reference keeps the first): the
+    // smallest |value| of the child's U x M results says so (a minimum that skips NaNs: a NaN result comes only from the K == 1 copy, which
+    // both forms share, and is not looked for), and a wavefront with a lane that holds a zero computes the child again by fold_pick — a
+    // wave-uniform branch BEHIND the loads' last use, nothing is fetched inside it.  (float up to 6 mixtures, see below.)
+    if constexpr (sizeof(T) == 4 && M <= 6) {
+      T r[U][M];
 #pragma unroll
-    for (int u = 0; u < U; ++u)
+      for (int u = 0; u < U; ++u)
 #pragma unroll
-      for (int m = 0; m < M; ++m)
-        acc[u][m] = acc[u][m] + fold_pick<T, M>(sd[u], bias[m], K).v;   // parent.score += maxv (:156), child order kept
+        for (int m = 0; m < M; ++m) r[u][m] = fold_max_fast<T, M>(sd[u], bias[m], K);
+      T lo = fold_abs(r[0][0]);
+#pragma unroll
+      for (int i = 1; i < U * M; ++i) lo = fold_minnum(lo, fold_abs(r[i / M][i % M]));
+      if (__builtin_amdgcn_ballot_w64(!fold_max_sure(lo)) != 0) {
+        // (the scores pass through an empty asm: the branch must add again, not keep the fast path's U x M x M sums alive for itself — 70 registers)
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+          for (int k = 0; k < M; ++k) asm volatile("" : "+v"(sd[u][k]));
+#endif
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+          for (int m = 0; m < M; ++m) r[u][m] = fold_pick<T, M>(sd[u], bias[m], K).v;
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int m = 0; m < M; ++m) acc[u][m] = acc[u][m] + r[u][m];   // parent.score += maxv (:156), child order kept
+    } else {
+      // double, and float with 8 mixtures, keep the compare / select form, message by message: double has no three-operand maximum or packed
+      // add to gain, and the value form cost each a wavefront per SIMD (double x 6: 140 registers for 128, float x 8: 135 for 111)
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int m = 0; m < M; ++m)
+          acc[u][m] = acc[u][m] + fold_pick<T, M>(sd[u], bias[m], K).v;   // parent.score += maxv (:156), child order kept
+    }
   } while (++c < nch);
 }
 
@@ -459,7 +495,9 @@ __device__ __forceinline__ void dt_block(char* smem, const DtTask& t, const DtGr
   // LDS staging, that space holds more lines.
   if (mine) {
     const double a = mp.a, b = mp.b;
-    int16_t* pp = mp.ptr + li;
+    // the pointer planes' elements: bytes where the plan says so (DT_G_PTR8: every line of the plan has byte links, so e < 255 here too), else int16 —
+    // the short lines of a plan that also has long ones keep 16 bits, the width is the plan's
+    const bool p8 = sizeof(IT) == 1 && (g.fused & DT_G_PTR8) != 0;   // (block-uniform)
     const int chunk = g.chunk;                   // ceil(len / nsub)
     const int q0 = p * chunk, q1 = min(len, q0 + chunk);
     if (q0 < q1) {
@@ -481,11 +519,13 @@ __device__ __forceinline__ void dt_block(char* smem, const DtTask& t, const DtGr
       int nnx = (int)Bl[nx];
       const int nlines = g.nlines;
       GPW(T) dp = (GPW(T))mp.dst + li + (size_t)(q1 - 1) * nlines;      // running output pointers: no 64-bit multiply per element
-      GPW(int16_t) ppq = (GPW(int16_t))pp + (size_t)(q1 - 1) * nlines;
+      const size_t pe = (size_t)li + (size_t)(q1 - 1) * nlines;       // the sub-range's last output in the pointer plane (elements)
       const int os_end = mp.os + q0;           // the sub-range's first output (the loop counts the shifted position down to it)
       ++os;
-      auto outputs = [&](auto fused) {         // fused: a * d^2 and b * d are exact (|d| < 2^14, float-born weights): their sum is one fma
+      auto outputs = [&](auto fused, auto ptype) {   // fused: a * d^2 and b * d are exact (|d| < 2^14, float-born weights): their sum is one fma
         constexpr bool FZ = decltype(fused)::value;
+        typedef decltype(ptype) PT;            // element of the pointer plane
+        GPW(PT) ppq = (GPW(PT))mp.ptr + pe;
         do {                                   // (q0 < q1: at least one output)
           --os;
           const T fos = (T)os;                 // `z[k+1] < os`: int promoted to T (:174)
@@ -493,12 +533,16 @@ __device__ __forceinline__ void dt_block(char* smem, const DtTask& t, const DtGr
           const double d = (double)(os - e);   // |d| < 2^15: d * d is exact in fp64 (the reference squares the int)
           const double ad2 = a * (d * d);
           *dp = (T)((FZ ? fma(b, d, ad2) : (ad2 + b * d)) + (double)eyz.x);
-          *ppq = (int16_t)e;
+          *ppq = (PT)e;
           dp -= nlines; ppq -= nlines;
         } while (os > os_end);
       };
-      if constexpr (!EX) { if (fz) outputs(std::true_type{}); else outputs(std::false_type{}); }
-      else outputs(std::false_type{});
+      auto widths = [&](auto fused) {
+        if constexpr (sizeof(IT) == 1) { if (p8) { outputs(fused, (uint8_t)0); return; } }
+        outputs(fused, (int16_t)0);
+      };
+      if constexpr (!EX) { if (fz) widths(std::true_type{}); else widths(std::false_type{}); }
+      else widths(std::false_type{});
     }
   }
   DT_STAMP(5);
@@ -835,7 +879,7 @@ __global__ __launch_bounds__(64) void k_backtrack(const int* __restrict__ count,
                                                   char* __restrict__ out, size_t out_stride,
                                                   const int* __restrict__ flat, const int* __restrict__ depth, int max_depth,
                                                   int nflat, const unsigned long long* __restrict__ scr_base,
-                                                  const int16_t* __restrict__ ixs, const int16_t* __restrict__ iys,
+                                                  const void* __restrict__ ixs, const void* __restrict__ iys, int ptr8,   // ptr8: the DT's planes are bytes (the plan's width)
                                                   int correct_ptr, const int16_t* __restrict__ extx,
                                                   const int16_t* __restrict__ exty, const unsigned long long* __restrict__ ext_base,
                                                   int* __restrict__ count_out, int org,
@@ -895,8 +939,9 @@ __global__ __launch_bounds__(64) void k_backtrack(const int* __restrict__ count,
       } else {
         const size_t so = (size_t)scr_base[(size_t)r.level * nflat + flat[r.comp * max_parts + p]] + (size_t)mm * HW;
         // the x pass's plane is stored transposed, [column][row] with pitch H (k_dt_pass's read-out); the y pass's is [row][column]
-        if (!correct_ptr) { x = ixs[so + (size_t)px * B.H + py]; y = iys[so + (size_t)py * B.W + x]; }
-        else { y = iys[so + off]; x = ixs[so + (size_t)px * B.H + y]; }
+        auto at = [&](const void* pl, size_t i) { return ptr8 ? (int)((const uint8_t*)pl)[i] : (int)((const int16_t*)pl)[i]; };
+        if (!correct_ptr) { x = at(ixs, so + (size_t)px * B.H + py); y = at(iys, so + (size_t)py * B.W + x); }
+        else { y = at(iys, so + off); x = at(ixs, so + (size_t)px * B.H + y); }
       }
       lx[p] = x; ly[p] = y; lm[p] = mm;
     }
@@ -928,12 +973,12 @@ __global__ __launch_bounds__(64) void k_backtrack(const int* __restrict__ count,
 void launch_backtrack(const int* count, const CandRec* rec, int capacity, const BackLevel* back, int ncomp,
                       const int* parent, const int* plane0, const int* nparts, int max_parts, const int* mix_rows, char* out,
                       size_t out_stride, int ts, const int* flat, const int* depth, int max_depth, int nflat,
-                      const unsigned long long* scr_base, const int16_t* ix, const int16_t* iy, int correct_ptr,
+                      const unsigned long long* scr_base, const void* ix, const void* iy, int ptr_bytes, int correct_ptr,
                       const int16_t* extx, const int16_t* exty, const unsigned long long* ext_base, int* count_out, int pad,
                       const FoldJob* folds, const unsigned long long* pick, hipStream_t s) {   // pick != null: Ik is picked from the fold's kept scores, not read from planes
   const int nblk = std::min(capacity, 2048);   // 8 blocks of one wavefront per CU; more candidates than that are taken in further sweeps
-  if (ts == 8) hipLaunchKernelGGL(k_backtrack<double>, dim3(nblk), dim3(64), 0, s, count, rec, capacity, back, ncomp, parent, plane0, nparts, max_parts, mix_rows, out, out_stride, flat, depth, max_depth, nflat, scr_base, ix, iy, correct_ptr, extx, exty, ext_base, count_out, 1 + pad, (const char*)folds, pick);
-  else hipLaunchKernelGGL(k_backtrack<float>, dim3(nblk), dim3(64), 0, s, count, rec, capacity, back, ncomp, parent, plane0, nparts, max_parts, mix_rows, out, out_stride, flat, depth, max_depth, nflat, scr_base, ix, iy, correct_ptr, extx, exty, ext_base, count_out, 1 + pad, (const char*)folds, pick);
+  if (ts == 8) hipLaunchKernelGGL(k_backtrack<double>, dim3(nblk), dim3(64), 0, s, count, rec, capacity, back, ncomp, parent, plane0, nparts, max_parts, mix_rows, out, out_stride, flat, depth, max_depth, nflat, scr_base, ix, iy, ptr_bytes == 1, correct_ptr, extx, exty, ext_base, count_out, 1 + pad, (const char*)folds, pick);
+  else hipLaunchKernelGGL(k_backtrack<float>, dim3(nblk), dim3(64), 0, s, count, rec, capacity, back, ncomp, parent, plane0, nparts, max_parts, mix_rows, out, out_stride, flat, depth, max_depth, nflat, scr_base, ix, iy, ptr_bytes == 1, correct_ptr, extx, exty, ext_base, count_out, 1 + pad, (const char*)folds, pick);
 }
 
 // ---------------------------------------------------------------------------

@@ -306,7 +306,7 @@ int plan_frame(pbd_handle* h, int w, int hgt, int cn, int batch, int depth) {
   h->cells = lay.cells; h->pyr_bytes = lay.pyr_bytes; h->compact = lay.compact; h->dt_cap_elems = lay.dt_cap_elems;
   h->d_img = (uint8_t*)b.p[FB_IMG]; h->d_pyr = (uint8_t*)b.p[FB_PYR]; h->d_feat = b.p[FB_FEAT]; h->d_resp = b.p[FB_RESP];
   h->d_pk = (uint8_t*)b.p[FB_PK]; h->d_rootv = b.p[FB_ROOTV]; h->d_rooti = (int*)b.p[FB_ROOTI]; h->d_nms_mask = (uint8_t*)b.p[FB_NMS_MASK];
-  h->d_dt_tmpT = b.p[FB_DT_TMPT]; h->d_dt_sdt = b.p[FB_DT_SDT]; h->d_dt_ixT = (int16_t*)b.p[FB_DT_IXT]; h->d_dt_iy = (int16_t*)b.p[FB_DT_IY];
+  h->d_dt_tmpT = b.p[FB_DT_TMPT]; h->d_dt_sdt = b.p[FB_DT_SDT]; h->d_dt_ixT = b.p[FB_DT_IXT]; h->d_dt_iy = b.p[FB_DT_IY]; h->dt_ptr_bytes = lay.ptr_bytes;
   h->d_acc = b.p[FB_ACC]; h->d_feat_split = (uint16_t*)b.p[FB_FEAT_SPLIT];
   h->pyr_launches = std::move(t.pyr_launches);
   if (h->pad == 0) { h->d_hog_levels = h->d_levels; h->d_padjobs = nullptr; h->d_padblocks = nullptr; }
@@ -605,7 +605,7 @@ static int run_argmin_enqueue(pbd_handle* h, bool filter = false) {
   }
   launch_backtrack(h->d_cand_count, h->d_cand_rec, h->opt.max_candidates, h->d_back, h->md.ncomponents, h->d_parent,
                    h->d_plane0, h->d_nparts, h->max_parts, h->d_mix_rows, out, h->cand_stride, h->ts, h->d_flat,
-                   h->d_depth, h->max_depth, (int)h->parts.size(), h->d_scr_base, h->d_dt_ixT, h->d_dt_iy,
+                   h->d_depth, h->max_depth, (int)h->parts.size(), h->d_scr_base, h->d_dt_ixT, h->d_dt_iy, h->dt_ptr_bytes,
                    h->opt.dt_correct_ptr, h->ext_ptr ? h->d_extx : nullptr, h->d_exty, h->d_ext_base, count_out, h->pad,
                    h->d_foldjobs, h->ik_lazy && !h->ext_ptr ? h->d_pick : nullptr, h->stream);
   if (post) return pbd_i_post_enqueue(h, cm, zf, out);
@@ -1055,21 +1055,23 @@ static int get_dp_pointers_(pbd_handle* h, int level, int component, int part, i
   // Ik is stored; Ix / Iy (reducePickIndex of the composed DT pointers, src/DynamicProgram.cpp:144-149) are
   // composed here from the DT pointer planes of the winning mixture, exactly as k_backtrack does per candidate
   std::vector<uint8_t> c(HW);
-  std::vector<int16_t> X((size_t)P.K * HW), Y((size_t)P.K * HW);
+  const size_t pb = (size_t)h->dt_ptr_bytes;   // the planes' width on the device (bytes while every line of the plan has byte links); widened here
+  std::vector<uint8_t> X((size_t)P.K * HW * pb), Y((size_t)P.K * HW * pb);
+  auto at = [pb](const std::vector<uint8_t>& v, size_t i) { return pb == 1 ? (int)v[i] : (int)((const int16_t*)v.data())[i]; };
   const size_t so = (size_t)h->scr_base[(size_t)level * h->parts.size() + (p0 + part)];
   ON_DEVICE(h);
   { int rc = ensure_ik(h); if (rc) return rc; }   // a frame entry's min() has not written the Ik planes
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemcpy(c.data(), h->d_pk + po, HW, hipMemcpyDeviceToHost));
-  HIPCHK(h, hipMemcpy(X.data(), h->d_dt_ixT + so, X.size() * 2, hipMemcpyDeviceToHost));
-  HIPCHK(h, hipMemcpy(Y.data(), h->d_dt_iy + so, Y.size() * 2, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(X.data(), (const char*)h->d_dt_ixT + so * pb, X.size(), hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(Y.data(), (const char*)h->d_dt_iy + so * pb, Y.size(), hipMemcpyDeviceToHost));
   const int W = L.cw, H = L.ch;   // X: the x pass's planes, stored transposed ([column][row], pitch H); Y: [row][column]
   for (size_t i = 0; i < HW; ++i) {
     const size_t mo = (size_t)c[i] * HW;
     const int m_ = (int)(i / W), n_ = (int)(i - (size_t)m_ * W);
     int x, y;
-    if (!h->opt.dt_correct_ptr) { x = X[mo + (size_t)n_ * H + m_]; y = Y[mo + (size_t)m_ * W + x]; }
-    else { y = Y[mo + i]; x = X[mo + (size_t)n_ * H + y]; }
+    if (!h->opt.dt_correct_ptr) { x = at(X, mo + (size_t)n_ * H + m_); y = at(Y, mo + (size_t)m_ * W + x); }
+    else { y = at(Y, mo + i); x = at(X, mo + (size_t)n_ * H + y); }
     if (ix) ix[i] = x;
     if (iy) iy[i] = y;
     if (ik) ik[i] = c[i];
@@ -1303,9 +1305,10 @@ static int dt2d_(pbd_handle* h, const void* in, int rows, int cols, double ax, d
   ON_DEVICE(h);
   const size_t ts = (size_t)tsz;
   char *d_in, *d_tmp, *d_sdt;
-  int16_t *d_ixT, *d_iy;
+  char *d_ixT, *d_iy;
+  const size_t pb = (size_t)dt_ptr_bytes_for(std::max(rows, cols));   // the pointer planes' width, as a frame plan chooses it: bytes while both passes' lines have byte links
   HIPCHK(h, hipMalloc(&d_in, HW * ts)); HIPCHK(h, hipMalloc(&d_tmp, HW * ts)); HIPCHK(h, hipMalloc(&d_sdt, HW * ts));
-  HIPCHK(h, hipMalloc(&d_ixT, HW * 2)); HIPCHK(h, hipMalloc(&d_iy, HW * 2));
+  HIPCHK(h, hipMalloc(&d_ixT, HW * pb)); HIPCHK(h, hipMalloc(&d_iy, HW * pb));
   HIPCHK(h, hipMemcpyAsync(d_in, in, HW * ts, hipMemcpyHostToDevice, h->stream));
   DtMap maps[2] = {dt_map(d_in, d_tmp, d_ixT, 0.f, 0.f, osx, 1), dt_map(d_tmp, d_sdt, d_iy, 0.f, 0.f, osy, 0)};
   maps[0].a = ax; maps[0].b = bx; maps[0].r2a = 1.0 / (2.0 * ax);   // the caller's quadratics (not the model's -w)
@@ -1323,6 +1326,7 @@ static int dt2d_(pbd_handle* h, const void* in, int rows, int cols, double ax, d
   const int nx = (int)tasks.size();
   dt_add_tasks(groups[1], tasks);
   dt_mark_fused(tasks, maps, tsz);   // (the caller's quadratics: fused arithmetic only if they are converted floats)
+  if (pb == 1) dt_mark_ptr8(tasks);
   DtMap* d_maps; DtTask* d_tasks;
   HIPCHK(h, hipMalloc(&d_maps, sizeof(maps)));
   HIPCHK(h, hipMalloc(&d_tasks, sizeof(DtTask) * tasks.size()));
@@ -1330,12 +1334,13 @@ static int dt2d_(pbd_handle* h, const void* in, int rows, int cols, double ax, d
   HIPCHK(h, hipMemcpyAsync(d_tasks, tasks.data(), sizeof(DtTask) * tasks.size(), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));  // host staging buffers above are pageable
   launch_dt_pass(d_tasks, nx, d_maps, nullptr, nullptr, h->d_biasw, budget, tsz, nt, 0, h->stream);
-  if (PBD_PROBE_ENV("PBD_DEBUG_SKIP_Y")) { hipMemsetAsync(d_sdt, 0, HW * ts, h->stream); hipMemsetAsync(d_iy, 0, HW * 2, h->stream); }   // probe build: leave the x pass as the last DT launch (its stamps are then readable)
+  if (PBD_PROBE_ENV("PBD_DEBUG_SKIP_Y")) { hipMemsetAsync(d_sdt, 0, HW * ts, h->stream); hipMemsetAsync(d_iy, 0, HW * pb, h->stream); }   // probe build: leave the x pass as the last DT launch (its stamps are then readable)
   else launch_dt_pass(d_tasks + nx, (int)tasks.size() - nx, d_maps, nullptr, nullptr, h->d_biasw, budget, tsz, nt, 0, h->stream);
-  std::vector<int16_t> hx(HW), hy(HW);
+  std::vector<uint8_t> hx(HW * pb), hy(HW * pb);
+  auto at = [pb](const std::vector<uint8_t>& v, size_t i) { return pb == 1 ? (int)v[i] : (int)((const int16_t*)v.data())[i]; };
   HIPCHK(h, hipMemcpyAsync(out, d_sdt, HW * ts, hipMemcpyDeviceToHost, h->stream));   // the y pass's scores, untouched
-  HIPCHK(h, hipMemcpyAsync(hx.data(), d_ixT, HW * 2, hipMemcpyDeviceToHost, h->stream));   // the passes' own pointers
-  HIPCHK(h, hipMemcpyAsync(hy.data(), d_iy, HW * 2, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(hx.data(), d_ixT, HW * pb, hipMemcpyDeviceToHost, h->stream));   // the passes' own pointers
+  HIPCHK(h, hipMemcpyAsync(hy.data(), d_iy, HW * pb, hipMemcpyDeviceToHost, h->stream));
   // finite arguments can still leave the domain BETWEEN the passes: the x pass's a d^2 + b d + y may overflow.  The kernel ends on any bit pattern
   // (dt_core.hpp: dt_stitch1), but only finite lines are the reference's bit for bit, so the x pass's scores come back too and both are scanned
   std::vector<char> htmp(HW * ts);
@@ -1346,8 +1351,8 @@ static int dt2d_(pbd_handle* h, const void* in, int rows, int cols, double ax, d
   for (size_t i = 0; i < HW; ++i) {   // pointer composition of compute() (:233-244), or the true arg-max one
     const int m_ = (int)(i / cols), n_ = (int)(i - (size_t)m_ * cols);
     int x, y;
-    if (!h->opt.dt_correct_ptr) { x = hx[(size_t)n_ * rows + m_]; y = hy[(size_t)m_ * cols + x]; }   // hx: [column][row] (the x pass writes transposed)
-    else { y = hy[i]; x = hx[(size_t)n_ * rows + y]; }
+    if (!h->opt.dt_correct_ptr) { x = at(hx, (size_t)n_ * rows + m_); y = at(hy, (size_t)m_ * cols + x); }   // hx: [column][row] (the x pass writes transposed)
+    else { y = at(hy, i); x = at(hx, (size_t)n_ * rows + y); }
     if (ix) ix[i] = x;
     if (iy) iy[i] = y;
   }

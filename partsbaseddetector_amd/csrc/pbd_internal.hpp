@@ -163,7 +163,7 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   int* d_depth = nullptr;    // [ncomp][max_parts] depth of each part in its tree (root = 0)
   int max_depth = 0;
   char* d_rootv = nullptr; int* d_rooti = nullptr;
-  char* d_dt_tmpT = nullptr; char* d_dt_sdt = nullptr; int16_t* d_dt_ixT = nullptr; int16_t* d_dt_iy = nullptr;
+  char* d_dt_tmpT = nullptr; char* d_dt_sdt = nullptr; void* d_dt_ixT = nullptr; void* d_dt_iy = nullptr; int dt_ptr_bytes = 2;   // the DT pointer planes: dt_ptr_bytes per element (FrameLayout::ptr_bytes)
   size_t dt_cap_elems = 0;
   LevelDev* d_levels = nullptr;
   // boundary padding (pbd_set_boundary_pad; HostModel::pad): k_hog's view of the levels (padded pitch, the interior's first cell; d_levels
@@ -541,7 +541,7 @@ void launch_nms_roots(const RootJob* jobs, int njobs, unsigned maxcells, const c
 void launch_backtrack(const int* count, const CandRec* rec, int capacity, const BackLevel* back, int ncomp,
                       const int* parent, const int* plane0, const int* nparts, int max_parts, const int* mix_rows,
                       char* out, size_t out_stride, int ts, const int* flat, const int* depth, int max_depth, int nflat,
-                      const unsigned long long* scr_base, const int16_t* ix, const int16_t* iy, int correct_ptr,
+                      const unsigned long long* scr_base, const void* ix, const void* iy, int ptr_bytes, int correct_ptr,   // ix / iy: the DT's own planes, ptr_bytes wide (FrameLayout::ptr_bytes)
                       const int16_t* extx, const int16_t* exty, const unsigned long long* ext_base, int* count_out, int pad,   // pad: the boundary padding (box origin)
                       const FoldJob* folds, const unsigned long long* pick, hipStream_t s);   // pick != null: Ik picked from the fold's kept scores (fold_pick.hpp), not read from planes
 // fold plans: the Ik planes written from the children's kept scores (k_dp.hip: k_ik_fill); blocks: {index into pick / cells, first cell}

@@ -383,6 +383,11 @@ int plan_model(HostModel& hm, const pbd_model_desc* model, const int32_t* fsize,
 // frame layout
 // ---------------------------------------------------------------------------
 static bool has_cells(const Level& L) { return L.active && L.cw > 0 && L.ch > 0; }
+static int plan_maxlen(const std::vector<Level>& lv) {   // the longest DT line of the plan (a row or a column of an active level)
+  int maxlen = 1;
+  for (const Level& L : lv) if (L.active) maxlen = std::max(maxlen, std::max(L.cw, L.ch));
+  return maxlen;
+}
 
 int plan_layout(const HostModel& hm, const FrameSpec& f, FrameLayout& out, std::string* err) {
   const pbd_model_desc& m = hm.md;
@@ -481,6 +486,10 @@ int plan_layout(const HostModel& hm, const FrameSpec& f, FrameLayout& out, std::
   own(FB_ROOTV, cells * m.ncomponents * ts);
   own(FB_ROOTI, std::max<size_t>(cells * m.ncomponents, 1) * sizeof(int));
   if (hm.nms_sz > 0) own(FB_NMS_MASK, cells * m.ncomponents);
+  // Width of their elements: bytes while every line of the plan has byte links (640x480: a third of what a DT launch writes was pointers), else
+  // int16 — one width for the plan.  The buffers keep two bytes per element either way (byte planes fill their first half): what the change
+  // saves is the traffic of 18 launches a frame, and the plan's footprint and the aliasing below stay what the plan check pins.
+  out.ptr_bytes = dt_ptr_bytes_for(plan_maxlen(out.lv));
   own(FB_DT_IXT, out.dt_cap_elems * sizeof(int16_t));
   own(FB_DT_IY, out.dt_cap_elems * sizeof(int16_t));
   if (!hm.fold) own(FB_ACC, cells * hm.nslots * ts);
@@ -581,7 +590,11 @@ void dt_mark_fused(std::vector<DtTask>& tasks, const DtMap* maps, int ts) {
     if (ok) g.fused |= DT_G_FUSED;
   }
 }
-DtMap dt_map(const void* src, void* dst, int16_t* ptr, float wq, float wl, int os, int natural) {
+int dt_ptr_bytes_for(int maxlen) { return dt_stride_for(maxlen) <= 256 ? 1 : 2; }
+void dt_mark_ptr8(std::vector<DtTask>& tasks) {
+  for (DtTask& t : tasks) t.g.fused |= DT_G_PTR8;
+}
+DtMap dt_map(const void* src, void* dst, void* ptr, float wq, float wl, int os, int natural) {
   DtMap m{};
   m.src = src; m.dst = dst; m.ptr = ptr;
   m.a = -(double)wq; m.b = -(double)wl;      // Quadratic fx(-w0, -w1), fy(-w2, -w3) (src/DynamicProgram.cpp:125-127)
@@ -690,8 +703,7 @@ static int hog_conv_tiles(const HostModel& hm, const FrameSpec& f, const FrameLa
 // DT block size and LDS budget of the frame
 static int dt_geometry(const HostModel& hm, const FrameLayout& lay, int dt_geom, const PlanKnobs& kn, FrameTables& out, std::string* err) {
   // DT LDS budget per block unless the longest line needs more at the minimum number of lines per block
-  int maxlen = 1;
-  for (const Level& L : lay.lv) if (L.active) maxlen = std::max(maxlen, std::max(L.cw, L.ch));
+  const int maxlen = plan_maxlen(lay.lv);
   // block geometry, measured on MI355X (profiles/sweep_dt.sh).  float, lines with 16-bit links: two wavefronts and
   // 25 KB per block = 6 blocks = 3 wavefronts per SIMD (20 .. 40 KB swept); double (17 B per line element, an IEEE division
   // per intersection): one wavefront and 20 KB = 8 blocks per CU (0.93 ms against 1.28 with the float geometry)
@@ -699,7 +711,7 @@ static int dt_geometry(const HostModel& hm, const FrameLayout& lay, int dt_geom,
   // (stride <= 256: 9 B per line element), float blocks of FOUR wavefronts and 40 KB — 4 blocks = 4 wavefronts per SIMD — beat
   // the two-wavefront / 25 KB blocks by 2-8 % of dp_min in batches (640x480: 0.328 -> 0.314 ms per frame, 0.600 -> 0.581 alone);
   // with 16-bit links (10 B per element: 1280x720, 1920x1080) they lose 9-12 %, and there the geometry above stays.
-  const bool byte_links = dt_stride_for(maxlen) <= 256;
+  const bool byte_links = lay.ptr_bytes == 1;   // (= dt_stride_for(maxlen) <= 256: plan_layout)
   // double (17 B per line element): two wavefronts and 40 KB per block — round 4, session 34: 0.473 / 0.721 ms per frame (batches / alone)
   // against 0.485 / 0.770 with one wavefront and 20 KB; round 5, session 3: 0.477 against 0.497 in batches, 893 against 879 frames/s
   // pbd_tune_plan: the other geometry measured on this handle's own frames (results are bit-identical under any geometry)
@@ -847,8 +859,8 @@ static void dt_round(const HostModel& hm, const FrameLayout& lay, const PlaneAdd
         const char* src = (!fold && slot_init[P.slot[mm]]) ? pa.acc(l, P.slot[mm]) : pa.resp(l, fid);
         const float* wv = &hm.defw[(size_t)did * 4];
         char* tmp = pa.b.p[FB_DT_TMPT] + to * ts;
-        maps.push_back(dt_map(src, tmp, (int16_t*)pa.b.p[FB_DT_IXT] + so, wv[0], wv[1], hm.anchors[did * 2], 1));
-        ymaps.push_back(dt_map(tmp, pa.sdt(fp, l, mm), (int16_t*)pa.b.p[FB_DT_IY] + so, wv[2], wv[3], hm.anchors[did * 2 + 1], 0));
+        maps.push_back(dt_map(src, tmp, pa.b.p[FB_DT_IXT] + so * (size_t)lay.ptr_bytes, wv[0], wv[1], hm.anchors[did * 2], 1));
+        ymaps.push_back(dt_map(tmp, pa.sdt(fp, l, mm), pa.b.p[FB_DT_IY] + so * (size_t)lay.ptr_bytes, wv[2], wv[3], hm.anchors[did * 2 + 1], 0));
         gx_nmaps++;
       }
       tmp_round += (size_t)P.K;
@@ -861,6 +873,7 @@ static void dt_round(const HostModel& hm, const FrameLayout& lay, const PlaneAdd
   }
   dt_mark_fused(xt, maps.data(), ts);
   dt_mark_fused(yt, maps.data(), ts);
+  if (lay.ptr_bytes == 1) { dt_mark_ptr8(xt); dt_mark_ptr8(yt); }
   xcd_order(xt, kn.xcd_chunk);
   xcd_order(yt, kn.xcd_chunk);
   R.lds_x = launch_lds(xt, ts, nt); R.lds_y = launch_lds(yt, ts, nt); R.fold_x = fold_x ? 1 : 0;

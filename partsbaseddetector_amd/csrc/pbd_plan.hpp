@@ -54,7 +54,8 @@ struct PadJob { unsigned long long cell_off; int cw, ch, pad, nring; };
 struct DtMap {       // one 1-D pass over one score map
   const void* src;   // T: lines contiguous: line i at src + i*len
   void* dst;         // T: transposed out: element q of line i at dst + q*nlines + i
-  int16_t* ptr;      // same layout as dst, in BOTH passes: element q of line i at ptr + q*nlines + i.  An x pass's plane (lines = rows) is therefore
+  void* ptr;         // uint8_t where the plan's lines all fit byte links (DT_G_PTR8 on every group: FrameLayout::ptr_bytes == 1), else int16_t.
+                     // Same layout as dst, in BOTH passes: element q of line i at ptr + q*nlines + i.  An x pass's plane (lines = rows) is therefore
                      // stored [column][row] with the level's row count as its pitch — k_backtrack and pbd_get_dp_pointers address it so, from the level's
                      // H alone; a y pass's (lines = columns) comes out [row][column]
   double a, b;       // Quadratic(a, b)
@@ -86,6 +87,7 @@ struct DtGroup {
 };
 #define DT_G_FUSED 1
 #define DT_G_NATURAL 2
+#define DT_G_PTR8 4          // bit 2 — the group's pointer planes are bytes (plan-wide: dt_mark_ptr8), else int16_t
 struct DtTask { int g0, nl, m0, l0; DtGroup g;     // g0: first line (plain) / first row (fold); nl: lines of this block; plain: g0 = m0 * nlines + l0
                                                     // (first map of the block, first line inside it); the group travels with the task
   const void* src0; };                              // plain: the block's first line when its nl lines are CONTIGUOUS in memory (consecutive maps of a group
@@ -245,6 +247,8 @@ struct FrameLayout {
   size_t act_cells = 0;                          // cells of the active levels
   size_t maxK = 1;                               // maps transformed in the fullest round (per level)
   size_t dt_cap_elems = 0;                       // elements of the per-map DT planes
+  int ptr_bytes = 2;                             // bytes per element of the DT pointer planes: 1 where every line of the plan has a stride <= 256 (an
+                                                 // element index < 255, k_dt_pass's own byte links), else 2 — one width for the whole plan
   bool compact = false;
   BufPlace buf[FB_COUNT];
   std::vector<size_t> regions;                   // bytes of each region: one allocation each
@@ -307,7 +311,9 @@ DtGroup dt_group(int map0, int nmaps, int nlines, int len, size_t budget, int ts
                  bool round_lanes = true);
 void dt_add_tasks(const DtGroup& g, std::vector<DtTask>& out, const std::vector<DtMap>* maps = nullptr, int ts = 4);
 void dt_mark_fused(std::vector<DtTask>& tasks, const DtMap* maps, int ts);
-DtMap dt_map(const void* src, void* dst, int16_t* ptr, float wq, float wl, int os, int natural);
+DtMap dt_map(const void* src, void* dst, void* ptr, float wq, float wl, int os, int natural);
+int dt_ptr_bytes_for(int maxlen);                      // width of the pointer planes of a plan whose longest line has maxlen elements (1 or 2)
+void dt_mark_ptr8(std::vector<DtTask>& tasks);         // DT_G_PTR8 on every group (a plan of dt_ptr_bytes_for(...) == 1)
 
 // pyramid geometry of one frame (HOGFeatures<T>::pyramid): 0, or -1 when the frame has fewer than `interval` or more than PBD_MAX_LEVELS levels
 int compute_geometry(int w, int h, int sbin, int interval, int* nlevels, Level* lv);
