@@ -169,7 +169,9 @@ int pbd_abi_version(void);
  * detection entry points pbd_latent_mask, pbd_dp_argbest, pbd_detect_latent_u8, pbd_detect_latent_dev_u8 and
  * pbd_detect_batch_latent_u8; and the feature-vector entry points pbd_feature_window_max, pbd_candidates_features,
  * pbd_candidates_features_f64 and pbd_candidates_features_dev (with the struct pbd_feature_block); and the part-wise NMS entry
- * points pbd_candidates_nms_parts, pbd_set_candidate_nms, pbd_group_set_candidate_nms and pbd_candidates_filter_parts.            */
+ * points pbd_candidates_nms_parts, pbd_set_candidate_nms, pbd_group_set_candidate_nms and pbd_candidates_filter_parts; and the
+ * best-pose-per-ground-truth-box entry points pbd_candidates_best_overlap, pbd_candidates_select_gt, pbd_detect_gtbox_u8,
+ * pbd_detect_gtbox_dev_u8 and pbd_detect_batch_gtbox_u8 (with PBD_GT_MAX).                                                          */
 
 /* ---- output record: include/Candidate.hpp:56-111 --------------------------
  * One candidate = head + max_parts boxes (x, y, width, height as cv::Rect)
@@ -834,6 +836,66 @@ int pbd_detect_latent_dev_u8(pbd_handle* h, const void* d_im, int w, int hgt, in
 int pbd_detect_batch_latent_u8(pbd_handle* h, const uint8_t* const* ims, int nframes, int w, int hgt, int cn, int stride,
                                const int32_t* truth, const int32_t* mix, int component, double overlap, pbd_candidate_head* heads,
                                int32_t* boxes, int32_t* locs, int* found);
+
+/* ---- best pose per ground-truth box: matlab/detection/testmodel_gtbox.m and bestoverlap.m (ABI 5, additive) --------------------
+ * The evaluation protocol the models' published numbers come from (testmodel_gtbox.m:17-21): detect at the model's threshold, build
+ * the ground-truth box of the annotated key points, and keep bestoverlap(box, gtbox, 0.3) — the highest-scoring pose whose box of
+ * part CENTRES covers more than `overlap` of the gt box.  Unlike latent detection nothing is constrained inside the DP: the
+ * thresholded output is searched.  On the device only the winners come home, one record per gt box, instead of every record.
+ * Input: `count` records (head + boxes[max_parts][4] int32 (x, y, w, h)) in a given order; ngt boxes gt[g] = (x1, y1, x2, y2) as
+ * doubles; a double overlap.  Everything below is float64, the operations in the order written, never fused.
+ *  1. Centres (bestoverlap.m:11-14): part p < nparts of a record has x2 = x + w - 1, y2 = y + h - 1 (the convention of
+ *     pbd_candidates_nms_parts for the same MATLAB boxes); its centre is cx = .5 * x + .5 * x2, cy alike.  The int32 -> double
+ *     conversions and the halves are exact: nothing rounds here.  w and h take part whatever their sign (MATLAB knows no empty box).
+ *  2. Centre box (:15-18): bx1 = min_p cx, bx2 = max_p cx, by1, by2 alike over the record's nparts parts.  A record with nparts == 0
+ *     matches nothing.
+ *  3. Overlap (:8-9, :20-28): area = (x2 - x1 + 1) * (y2 - y1 + 1) of the gt box; w = min(x2, bx2) - max(x1, bx1) + 1, w < 0 set
+ *     to 0, h alike; inter = w * h; o = inter / area.  Nothing is special-cased: a gt box of area 0 gives 0 / 0 = NaN and matches
+ *     nothing, a negative area gives o <= 0.
+ *  4. Match (:29): the record matches g iff o > overlap — strict, and NaN is false.
+ *  5. Pick (:31-33): among the matching records the one with the largest head.score, compared as the stored float (-0.0 == +0.0);
+ *     among exactly equal scores the first record in the given order wins (MATLAB's max).  best[g] = its index, o[g] = its
+ *     overlap; with no match best[g] = -1 and o[g] = 0.0 (bestoverlap returns [] then).
+ *  6. The boxes of one frame are independent: two gt boxes may pick the same record.
+ * DEVIATION: within a frame "the given order" is this library's RAW order — level, component, root row, root column (what every
+ * detect entry returns) —, where detect_fast.m's find is column-major within a (level, component).  Only exactly tied scores can
+ * tell the two apart.
+ * PBD_ERR_ARG: a non-finite gt coordinate or overlap; a non-finite score in caller-supplied records; nparts outside 0..max_parts;
+ * ngt outside 0..PBD_GT_MAX; NULL where a size is positive.  ngt == 0 or count == 0: PBD_OK with nothing found.
+ *
+ * pbd_candidates_best_overlap: the definition, pure host code, callable without a GPU (like pbd_candidates_nms_parts).
+ * pbd_candidates_select_gt: the caller's host records (max_parts = the handle's) through the device kernels (k_gtbox.hip), ties
+ *   broken by input position: bit-identical to pbd_candidates_best_overlap, best and o alike.  Synchronous; PBD_ERR_STATE while a
+ *   frame is pending.
+ * Whole-path entry points, modelled on the three latent ones: pbd_detect_u8 / pbd_detect_dev_u8 / pbd_detect_batch_u8 with the gt
+ *   boxes of the frame, gt[ngt][4] (batch: gt[nframes][PBD_GT_MAX][4] and ngt[nframes], any of them 0).  The frame runs the ordinary
+ *   path at the model's threshold with the back-tracking writing into a device list; the selection runs behind it, and per gt box
+ *   the winner's whole record is returned: heads[ngt], boxes[ngt][max_parts][4], locs[ngt][max_parts][3] (either may be NULL),
+ *   found[ngt] (1 / 0; the record of an unmatched box is left untouched) and o[ngt] (may be NULL).  Batch outputs carry a leading
+ *   [nframes] and are strided by PBD_GT_MAX (heads[nframes][PBD_GT_MAX] ...); the levels returned are the frame's own.  Each result
+ *   equals pbd_candidates_best_overlap applied to what pbd_detect_u8 returns for the frame (RAW mode), bit for bit.
+ *   *nrecords (may be NULL) = the records in front of the selection (a batch: of all its frames), set before anything can fail:
+ *   PBD_ERR_CAPACITY when they overflow pbd_options.max_candidates — the selection would be incomplete — with the needed count
+ *   there, as the plain entries report it in *count.
+ *   PBD_ERR_UNSUPPORTED, each with a message: a candidate filter mode other than PBD_CAND_RAW, depth pruning, 3-D boxes, object
+ *   clusters or per-part scores switched on (the stand-alone pbd_candidates_* entries work on the returned records afterwards), and
+ *   pbd_group members.  PBD_ERR_STATE while a frame is pending.  All dp_modes and the compact memory plan work: the selection reads
+ *   only the records.  The launches are eager, as those of latent and depth-carrying frames; plain frames and their captured graph
+ *   are untouched.                                                                                                                 */
+#define PBD_GT_MAX 64
+int pbd_candidates_best_overlap(const pbd_candidate_head* heads, const int32_t* boxes, int count, int max_parts, const double* gt,
+                                int ngt, double overlap, int32_t* best, double* o);
+int pbd_candidates_select_gt(pbd_handle* h, const double* gt, int ngt, double overlap, const pbd_candidate_head* heads,
+                             const int32_t* boxes, int count, int32_t* best, double* o);
+int pbd_detect_gtbox_u8(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride, const double* gt, int ngt,
+                        double overlap, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int* found, double* o,
+                        int* nrecords);
+int pbd_detect_gtbox_dev_u8(pbd_handle* h, const void* d_im, int w, int hgt, int cn, int stride, const double* gt, int ngt,
+                            double overlap, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int* found, double* o,
+                            int* nrecords);
+int pbd_detect_batch_gtbox_u8(pbd_handle* h, const uint8_t* const* ims, int nframes, int w, int hgt, int cn, int stride,
+                              const double* gt, const int* ngt, double overlap, pbd_candidate_head* heads, int32_t* boxes,
+                              int32_t* locs, int* found, double* o, int* nrecords);
 
 /* ---- feature vectors of detections: what the models are trained from (ABI 5, additive) ------------------------------------------
  * detect(im, model, thresh, bbox, overlap, id, label) of matlab/detection/detect.m collects, while it back-tracks a pose (:272-308),

@@ -25,6 +25,7 @@ PBD_SCALAR_F32, PBD_SCALAR_F64 = 0, 1
 PBD_CAND_RAW, PBD_CAND_SORT, PBD_CAND_SORT_NMS = 0, 1, 2   # pbd_set_candidate_filter: detect's output / Candidate::sort / sort + NMS
 PBD_NMS_PAINTED, PBD_NMS_PARTS = 0, 1   # pbd_set_candidate_nms: the NMS of PBD_CAND_SORT_NMS — Candidate::nonMaximaSuppression / nms.m's part-wise rule
 PBD_DEPTH_8U, PBD_DEPTH_16U, PBD_DEPTH_32F, PBD_DEPTH_64F = 0, 2, 5, 6          # cv::Mat::depth() (src/HOGFeatures.cpp:136-146)
+PBD_GT_MAX = 64   # gt boxes per frame of the pbd_detect_gtbox_* entries and the pbd_candidates_best_overlap / _select_gt primitives
 PBD_PYRAMID_OPENCV, PBD_PYRAMID_MATLAB = 0, 1   # pbd_set_pyramid_kind: HOGFeatures<T>::pyramid (cv::resize / cv::pyrDown) / matlab/detection/featpyramid.m
 DEPTH_OF = {np.dtype(np.uint8): PBD_DEPTH_8U, np.dtype(np.uint16): PBD_DEPTH_16U, np.dtype(np.float32): PBD_DEPTH_32F,
             np.dtype(np.float64): PBD_DEPTH_64F}
@@ -60,6 +61,8 @@ EXPORTS = [
     "pbd_feature_window_max", "pbd_candidates_features", "pbd_candidates_features_f64", "pbd_candidates_features_dev",
     "pbd_candidates_nms_parts", "pbd_set_candidate_nms", "pbd_group_set_candidate_nms", "pbd_candidates_filter_parts",
     "pbd_set_pyramid_kind", "pbd_get_pyramid_kind", "pbd_resize_area_f64", "pbd_reduce_f64",
+    "pbd_candidates_best_overlap", "pbd_candidates_select_gt", "pbd_detect_gtbox_u8", "pbd_detect_gtbox_dev_u8",
+    "pbd_detect_batch_gtbox_u8",
 ]
 PBD_ABI_VERSION = 5
 
@@ -827,6 +830,76 @@ class Handle:
             self.h, ptrs, len(frames), w, hgt, cn, w * cn, _p(tr, C.c_int32), _p(mx, C.c_int32), int(component),
             C.c_double(overlap), hd, bx, lc, cnt))
 
+    # ---- best pose per ground-truth box (matlab/detection/testmodel_gtbox.m, bestoverlap.m) -------------------------------
+    def candidates_select_gt(self, heads, boxes, gt, overlap=0.3):
+        """pbd_candidates_select_gt: pbd_candidates_best_overlap of host records through the device kernels -> (best[ngt], o[ngt])"""
+        heads = np.ascontiguousarray(heads, HEAD_DTYPE)
+        boxes = np.ascontiguousarray(boxes, np.int32)
+        gt = np.ascontiguousarray(gt, np.float64).reshape(-1, 4)
+        best = np.full(len(gt), -1, np.int32)
+        o = np.zeros(len(gt), np.float64)
+        self._chk(self.L.pbd_candidates_select_gt(self.h, _p(gt, C.c_double), len(gt), C.c_double(overlap),
+                                                  heads.ctypes.data_as(C.c_void_p), _p(boxes, C.c_int32), len(heads),
+                                                  _p(best, C.c_int32), _p(o, C.c_double)))
+        return best, o
+
+    def _gt_out(self, n):
+        return self._bufs(n) + (np.zeros(n, np.int32), np.zeros(n, np.float64))
+
+    def detect_gtbox(self, im: np.ndarray, gt, overlap=0.3):
+        """pbd_detect_gtbox_u8: per gt box (x1, y1, x2, y2) the best pose of the frame on it -> (heads, boxes, locs, found, o), one
+        slot per box (zeros where found is 0); self.gt_records = the frame's records in front of the selection"""
+        im = np.ascontiguousarray(im, np.uint8)
+        hgt, w = im.shape[:2]
+        cn = 1 if im.ndim == 2 else im.shape[2]
+        gt = np.ascontiguousarray(gt, np.float64).reshape(-1, 4)
+        heads, boxes, locs, found, o = self._gt_out(len(gt))
+        nrec = C.c_int(0)
+        rc = self.L.pbd_detect_gtbox_u8(self.h, _p(im, C.c_uint8), w, hgt, cn, w * cn, _p(gt, C.c_double), len(gt), C.c_double(overlap),
+                                        heads.ctypes.data_as(C.c_void_p), _p(boxes, C.c_int32), _p(locs, C.c_int32),
+                                        _p(found, C.c_int32), _p(o, C.c_double), C.byref(nrec))
+        self.gt_records = nrec.value
+        self._chk(rc)
+        return heads, boxes, locs, found, o
+
+    def detect_gtbox_dev(self, dptr: int, w, hgt, cn, gt, overlap=0.3, stride=None):
+        """pbd_detect_gtbox_dev_u8: the image already in device memory"""
+        gt = np.ascontiguousarray(gt, np.float64).reshape(-1, 4)
+        heads, boxes, locs, found, o = self._gt_out(len(gt))
+        nrec = C.c_int(0)
+        rc = self.L.pbd_detect_gtbox_dev_u8(self.h, C.c_void_p(dptr), w, hgt, cn, stride or w * cn, _p(gt, C.c_double), len(gt),
+                                            C.c_double(overlap), heads.ctypes.data_as(C.c_void_p), _p(boxes, C.c_int32),
+                                            _p(locs, C.c_int32), _p(found, C.c_int32), _p(o, C.c_double), C.byref(nrec))
+        self.gt_records = nrec.value
+        self._chk(rc)
+        return heads, boxes, locs, found, o
+
+    def detect_batch_gtbox(self, frames, gts, overlap=0.3):
+        """pbd_detect_batch_gtbox_u8: the gt boxes of every frame (any number up to PBD_GT_MAX, also none) -> per frame what
+        detect_gtbox returns"""
+        frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+        if not frames or len(gts) != len(frames) or any(f.shape != frames[0].shape for f in frames):
+            raise ValueError("detect_batch_gtbox: one set of gt boxes per frame, frames of one shape")
+        gts = [np.asarray(g, np.float64).reshape(-1, 4) for g in gts]
+        if any(len(g) > PBD_GT_MAX for g in gts):
+            raise ValueError("detect_batch_gtbox: at most PBD_GT_MAX gt boxes per frame")
+        nb = len(frames)
+        hgt, w = frames[0].shape[:2]
+        cn = 1 if frames[0].ndim == 2 else frames[0].shape[2]
+        gt = np.zeros((nb, PBD_GT_MAX, 4), np.float64)
+        ngt = np.array([len(g) for g in gts], np.int32)
+        for f, g in enumerate(gts):
+            gt[f, :len(g)] = g
+        heads, boxes, locs, found, o = self._gt_out(nb * PBD_GT_MAX)
+        ptrs = (C.c_void_p * nb)(*[f.ctypes.data for f in frames])
+        nrec = C.c_int(0)
+        rc = self.L.pbd_detect_batch_gtbox_u8(self.h, ptrs, nb, w, hgt, cn, w * cn, _p(gt, C.c_double), _p(ngt, C.c_int32),
+                                              C.c_double(overlap), heads.ctypes.data_as(C.c_void_p), _p(boxes, C.c_int32),
+                                              _p(locs, C.c_int32), _p(found, C.c_int32), _p(o, C.c_double), C.byref(nrec))
+        self.gt_records = nrec.value
+        self._chk(rc)
+        return [tuple(a[f * PBD_GT_MAX:f * PBD_GT_MAX + ngt[f]].copy() for a in (heads, boxes, locs, found, o)) for f in range(nb)]
+
     # ---- primitives ----------------------------------------------------------------
     def dt2d(self, a: np.ndarray, ax, bx, ay, by, osx, osy):
         a = np.ascontiguousarray(a, self.dtype)
@@ -1041,3 +1114,19 @@ def candidates_nms_parts(heads, boxes, locs, overlap=0.3, top=1000):
     if rc:
         raise PbdError(rc, "pbd_candidates_nms_parts")
     return heads[:kept.value], boxes[:kept.value], None if locs is None else locs[:kept.value]
+
+
+def candidates_best_overlap(heads, boxes, gt, overlap=0.3):
+    """matlab/detection/bestoverlap.m per gt box (x1, y1, x2, y2) on records in the given order (pbd_candidates_best_overlap,
+    include/pbd_c.h) — host code inside the library -> (best[ngt] record index or -1, o[ngt])."""
+    heads = np.ascontiguousarray(heads, HEAD_DTYPE)
+    boxes = np.ascontiguousarray(boxes, np.int32)
+    gt = np.ascontiguousarray(gt, np.float64).reshape(-1, 4)
+    mp = boxes.shape[1]
+    best = np.full(len(gt), -1, np.int32)
+    o = np.zeros(len(gt), np.float64)
+    rc = lib().pbd_candidates_best_overlap(heads.ctypes.data_as(C.c_void_p), _p(boxes, C.c_int32), len(heads), mp, _p(gt, C.c_double),
+                                           len(gt), C.c_double(overlap), _p(best, C.c_int32), _p(o, C.c_double))
+    if rc:
+        raise PbdError(rc, "pbd_candidates_best_overlap")
+    return best, o

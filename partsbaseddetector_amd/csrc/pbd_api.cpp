@@ -603,12 +603,15 @@ static int run_argmin_enqueue(pbd_handle* h, bool filter = false) {
     out = post && (zf || h->d_gsend) ? h->d_cand_raw : h->d_cand_out;
     count_out = nullptr;
   }
+  const bool gt = filter && h->gt_frame;   // (its entries refuse every post-stage: cm is RAW, no depth)
+  if (gt) { out = h->d_cand_out; count_out = nullptr; }   // a device list: only the selection's winners reach the host
   launch_backtrack(h->d_cand_count, h->d_cand_rec, h->opt.max_candidates, h->d_back, h->md.ncomponents, h->d_parent,
                    h->d_plane0, h->d_nparts, h->max_parts, h->d_mix_rows, out, h->cand_stride, h->ts, h->d_flat,
                    h->d_depth, h->max_depth, (int)h->parts.size(), h->d_scr_base, h->d_dt_ixT, h->d_dt_iy, h->dt_ptr_bytes,
                    h->opt.dt_correct_ptr, h->ext_ptr ? h->d_extx : nullptr, h->d_exty, h->d_ext_base, count_out, h->pad,
                    h->d_foldjobs, h->ik_lazy && !h->ext_ptr ? h->d_pick : nullptr, h->stream);
   if (post) return pbd_i_post_enqueue(h, cm, zf, out);
+  if (gt) return pbd_i_gt_enqueue(h, out);
   LAUNCHCHK(h, "argmin");
   if (zero_copy) { h->pending = true; h->out_on_host = true; return PBD_OK; }
   h->out_on_host = false;
@@ -660,7 +663,8 @@ int enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride) {
   if (rc) return rc;
   // depth-carrying frames run eagerly: the depth pointers are per frame; a captured graph stays for plain frames
   // latent frames too: the mask stage and the best-root reduction are theirs alone, the captured graph stays the plain frames'
-  if (h->zf_frame || h->lat_frame) return enqueue_stages(h, d_src, stride);
+  // gt-box frames too: the selection behind the back-tracking is theirs alone
+  if (h->zf_frame || h->lat_frame || h->gt_frame) return enqueue_stages(h, d_src, stride);
   if (!graphable || h->frames_on_plan == 0) {
     h->frames_on_plan++;
     return enqueue_stages(h, d_src, stride);

@@ -43,6 +43,13 @@ int enter_frame(pbd_handle* h, const FrameSource& s, bool detect) {
     h->lat_frame = false;
     return rc;
   }
+  if (s.gt) {    // gt-box frames: the boxes in front of the kernels like the image; the flag lives only across the enqueue
+    if ((rc = pbd_i_gt_begin(h, *s.gt, s.nframes))) return rc;
+    h->gt_frame = true;
+    rc = enqueue_all(h, d_src, stride);
+    h->gt_frame = false;
+    return rc;
+  }
   if (!s.z) return enqueue_all(h, d_src, stride);
   const DepthSource& z = *s.z;
   h->zf_img = (const char*)z.p; h->zf_pitch = (size_t)z.stride;
@@ -116,8 +123,22 @@ int pbd_i_found(const pbd_handle* h) { return h->out_filtered ? h->h_cf_cnt[1] :
 // pbd_dp_argmin): the count is frame 0's own (pbd_i_found), set before anything can fail, and the first refusal is returned.  Batch: the
 // device count of all frames (filtered: the records in FRONT of the filter, so the fetch covers every kept one); counts[] are written
 // once the records are on the host, a frame beyond `capacity` is skipped and PBD_ERR_CAPACITY returned after the others.
-static int collect_frames(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* counts, bool single) {
+// A gt-box frame or batch (gt != null, and only then): counts[0] = the records in front of the selection, and once the list is known
+// not to have overflowed, the winners — frame f's at heads[f * PBD_GT_MAX] — with found and o instead of the records.
+struct GtOut { int* found; double* o; };
+static int collect_frames(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* counts, bool single,
+                          const GtOut* gt = nullptr) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (h->gt_pending) {
+    h->gt_pending = false;
+    const int nrec = h->h_cand_count[0];
+    if (counts) *counts = nrec;
+    int rc = pbd_i_finish_frame(h, nrec);
+    if (rc) return rc;
+    if (!gt) return fail(h, PBD_ERR_STATE, "a gt-box frame is collected by the entry that enqueued it");
+    pbd_i_gt_gather(h, heads, boxes, locs, gt->found, gt->o);
+    return PBD_OK;
+  }
   const bool filt = h->out_filtered;
   const int found = single ? pbd_i_found(h) : filt ? h->h_cf_cnt[0] : h->h_cand_count[0];
   if (single && counts) *counts = found;
@@ -306,6 +327,39 @@ int pbd_detect_batch_latent_u8(pbd_handle* h, const uint8_t* const* ims, int nfr
   if (!h || !ims || !heads || !found || nframes < 1) return PBD_ERR_ARG;
   int rc = latent_enter(h, host_batch(ims, nframes, w, hgt, cn, stride), truth, mix, component, overlap);
   return rc ? rc : pbd_detect_batch_collect(h, heads, boxes, locs, 1, found);
+}
+
+// ---- best pose per ground-truth box: testmodel_gtbox.m / bestoverlap.m (include/pbd_c.h) -----------------------------------------
+// The plain entries with the gt boxes of every frame: behind the back-tracking the selection of k_gtbox.hip, and only its winners
+// come home.  Arguments and settings are checked before anything is planned.
+static int gtbox_run(pbd_handle* h, FrameSource s, const double* gt, const int* ngt, double overlap, pbd_candidate_head* heads,
+                     int32_t* boxes, int32_t* locs, int* found, double* o, int* nrecords) {
+  if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
+  int rc = pbd_i_gt_check(h, gt, ngt, s.nframes, overlap, true);
+  if (rc) return rc;
+  const GtSource gs{gt, ngt, overlap};
+  s.gt = &gs;
+  if ((rc = enter_frame(h, s))) return rc;
+  const GtOut out{found, o};
+  rc = collect_frames(h, heads, boxes, locs, PBD_GT_MAX, nrecords, s.nframes == 1, &out);
+  read_stage_times(h);
+  return rc;
+}
+int pbd_detect_gtbox_u8(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride, const double* gt, int ngt, double overlap,
+                        pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int* found, double* o, int* nrecords) {
+  if (!h || !im || (ngt > 0 && (!heads || !found))) return PBD_ERR_ARG;
+  return gtbox_run(h, host_frame(im, w, hgt, cn, stride, PBD_DEPTH_8U), gt, &ngt, overlap, heads, boxes, locs, found, o, nrecords);
+}
+int pbd_detect_gtbox_dev_u8(pbd_handle* h, const void* d_im, int w, int hgt, int cn, int stride, const double* gt, int ngt, double overlap,
+                            pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int* found, double* o, int* nrecords) {
+  if (!h || !d_im || (ngt > 0 && (!heads || !found))) return PBD_ERR_ARG;
+  return gtbox_run(h, device_frames(d_im, 1, w, hgt, cn, stride), gt, &ngt, overlap, heads, boxes, locs, found, o, nrecords);
+}
+int pbd_detect_batch_gtbox_u8(pbd_handle* h, const uint8_t* const* ims, int nframes, int w, int hgt, int cn, int stride, const double* gt,
+                              const int* ngt, double overlap, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int* found,
+                              double* o, int* nrecords) {
+  if (!h || !ims || !heads || !found || nframes < 1) return PBD_ERR_ARG;
+  return gtbox_run(h, host_batch(ims, nframes, w, hgt, cn, stride), gt, ngt, overlap, heads, boxes, locs, found, o, nrecords);
 }
 
 // ---- the planner's one measured rule, re-measured on the caller's own frames ---------------------------------

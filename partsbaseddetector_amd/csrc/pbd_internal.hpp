@@ -88,6 +88,22 @@ __device__ __forceinline__ int record_frame(const RecordSet& r, int i) {
 }
 #endif
 
+// ---- best pose per ground-truth box (k_gtbox.hip; include/pbd_c.h "best pose per ground-truth box") ---------------------------
+#define PBD_GT_BLOCK 256                             // threads of a block of either kernel
+#define PBD_GT_GRID 64                               // blocks of k_gtbox_centres
+#define PBD_GT_SPAN (PBD_GT_GRID * PBD_GT_BLOCK)     // records one pass of its grid covers
+struct GtBoxArgs {
+  RecordSet in;                 // (cf unused)  nlevels 0: one frame, ties go to the input position; else to (level, component, root y, root x)
+  int nframes;
+  const double* gt; const int* ngt; double overlap;   // [nframes][PBD_GT_MAX][4] (x1, y1, x2, y2); [nframes]
+  double4* cbox; unsigned* key; unsigned long long* rank; int* frame;   // [capacity] each: k_gtbox_centres' planes
+  char* out;                    // [nframes * PBD_GT_MAX] record slots: the winners' records (null: none wanted)
+  int* found; double* o;        // [nframes * PBD_GT_MAX]
+  int* best;                    // [nframes * PBD_GT_MAX] the winner's index in `in`, -1: none (null: not wanted)
+};
+// one gt-box frame or batch: the boxes of every frame, PBD_GT_MAX slots per frame
+struct GtSource { const double* gt; const int* ngt; double overlap; };
+
 // object clusters (k_cluster3d.hip): one record's result in the slot of its record
 struct Cl3Res { pbd_cluster3d r; long long off; };   // off: the kept cluster's indices in the pool; -1: they did not fit
 
@@ -285,6 +301,14 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   LatJob* d_lat_jobs = nullptr; ReduceBlock* d_lat_blocks = nullptr; int n_lat_blocks = 0;
   int* d_lat_flags = nullptr; LatPartial* d_lat_partial = nullptr;
   int* d_lat_truth = nullptr; int* h_lat_truth = nullptr;   // [PBD_MAX_BATCH][max_parts][5]: 4 box ints per part of every frame, then the mixtures; h_: pinned
+  // best pose per ground-truth box (pbd_detect_gtbox_*): k_gtbox.hip behind k_backtrack, which then writes into d_cand_out.  The planes
+  // and the tables are model-lifetime buffers (first use); the winners' records, found and o land in pinned memory, slot f * PBD_GT_MAX + g.
+  bool gt_frame = false;            // the frame being enqueued is a gt-box one (set by enter_frame around enqueue_all)
+  bool gt_pending = false;          // ... and is the pending one: the collect returns the winners, not the records
+  int gt_max = 0; double gt_overlap = 0.0;   // the largest ngt of the frame's or batch's frames
+  double4* d_gt_cbox = nullptr; unsigned* d_gt_key = nullptr; unsigned long long* d_gt_rank = nullptr; int* d_gt_frame = nullptr;   // [capacity]
+  double* d_gt = nullptr; double* h_gt = nullptr;   // [PBD_MAX_BATCH][PBD_GT_MAX][4], then the frames' ngt as ints; h_: pinned staging
+  char* h_gt_out = nullptr; int* h_gt_found = nullptr; double* h_gt_o = nullptr;   // [PBD_MAX_BATCH * PBD_GT_MAX] slots: pinned
 };
 #define PBD_MAX_BATCH 64
 
@@ -405,6 +429,7 @@ struct FrameSource {
   int nframes, w, hgt, cn, stride, depth;   // stride: bytes between rows; depth: PBD_DEPTH_* of the pixels
   const DepthSource* z;           // RGB-D: the frame runs with the depth-carrying post-stages; else null
   const LatentSource* lat;        // latent detection: the frame is masked by these boxes and yields its best pose; else null
+  const GtSource* gt;             // best pose per ground-truth box: the selection runs behind the back-tracking; else null
 };
 // the three shapes of a source, by name (z: see above)
 inline FrameSource host_frame(const void* im, int w, int hgt, int cn, int stride, int depth, const DepthSource* z = nullptr) {
@@ -438,6 +463,13 @@ int pbd_i_emit(pbd_handle* h, const std::vector<const char*>& recs, pbd_candidat
 // table + the upload of the truth / mixture tables in the handle's stream
 int pbd_i_latent_check(pbd_handle* h, const int32_t* truth, const int32_t* mix, int nframes, int component, double overlap);
 int pbd_i_latent_begin(pbd_handle* h, const LatentSource& s, int nframes);
+// best pose per ground-truth box (pbd_post.cpp): the argument checks of every entry (gt boxes of nframes frames; whole: the handle's
+// settings too), the buffers + the upload of the boxes in the handle's stream, the launch behind k_backtrack (records in `raw`), and
+// the collect's copy of the winners: frame f's at heads[f * PBD_GT_MAX] etc., levels made the frame's own
+int pbd_i_gt_check(pbd_handle* h, const double* gt, const int* ngt, int nframes, double overlap, bool whole);
+int pbd_i_gt_begin(pbd_handle* h, const GtSource& s, int nframes);
+int pbd_i_gt_enqueue(pbd_handle* h, char* raw);
+void pbd_i_gt_gather(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int* found, double* o);
 int pbd_i_found(const pbd_handle* h);   // records the pending frame left on the host side (filtered: the kept count)
 #define PBD_FIRST_COPY 192   // candidate records fetched (or gathered) together with the count
 
@@ -630,6 +662,7 @@ struct FeatVecArgs {
   void* windows;                                // T [n][mp][wmax], 16-byte aligned
 };
 void launch_featvec(const FeatVecArgs& a, int ts, hipStream_t s);
+void launch_gtbox(const GtBoxArgs& a, int gmax, hipStream_t s);   // k_gtbox.hip: gmax = the largest ngt
 // object clusters (k_cluster3d.hip)
 size_t cluster3d_slot_bytes(int pcap);
 // src: 0 = xyz floats (pstride, rstride bytes), 4 / 8 = a depth image of float / double

@@ -1,12 +1,13 @@
 // pbd_post.cpp — the stages behind back-tracking: candidate sort + NMS (k_cand.hip), depth-consistency pruning
-// (k_zfilter.hip), 3-D boxes (k_box3d.hip), object clusters (k_cluster3d.hip), per-part scores (k_partscore.hip) and the stand-alone
-// feature vectors (k_featvec.hip).  Their handle buffers, their launches behind k_backtrack, the collect's gathering of their results
+// (k_zfilter.hip), 3-D boxes (k_box3d.hip), object clusters (k_cluster3d.hip), per-part scores (k_partscore.hip), the stand-alone
+// feature vectors (k_featvec.hip) and the best pose per ground-truth box (k_gtbox.hip).  Their handle buffers, their launches behind k_backtrack, the collect's gathering of their results
 // and their C entry points (pbd_set_*, pbd_get_box3d, pbd_get_cluster3d, pbd_get_part_scores, pbd_candidates_*).  pbd_api.cpp calls in
 // through the pbd_i_* functions of pbd_internal.hpp.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include "pbd_internal.hpp"
+#include "gt_overlap.hpp"
 
 // ---- the scratch of one stand-alone call ---------------------------------------------------------------------------------
 // Device and pinned buffers, freed when it goes out of scope; the first HIP error is kept and every later step is skipped.
@@ -410,6 +411,99 @@ static int fv_host(pbd_handle* h, const pbd_candidate_head* heads, const int32_t
     if ((rc = s.finish("feature vectors: "))) return rc;   // (the next chunk overwrites the staging buffer)
   }
   return PBD_OK;
+}
+
+// ---- best pose per ground-truth box (k_gtbox.hip) -------------------------------------------------------------------------
+// every refusal that depends on the arguments alone (and, for the whole-path entries, on the handle's settings)
+int pbd_i_gt_check(pbd_handle* h, const double* gt, const int* ngt, int nframes, double overlap, bool whole) {
+  if (whole) {
+    if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "gt boxes: pbd_group members are not supported (detect through a handle of its own)");
+    if (pbd_i_cand_mode(h) != PBD_CAND_RAW)
+      return fail(h, PBD_ERR_UNSUPPORTED, "gt boxes: the selection searches the RAW records: set the candidate filter to PBD_CAND_RAW (pbd_candidates_* work on the returned records)");
+    if (h->zf_on) return fail(h, PBD_ERR_UNSUPPORTED, "gt boxes: not with depth pruning on (pbd_candidates_depth_filter works on the returned records)");
+    if (h->b3_on) return fail(h, PBD_ERR_UNSUPPORTED, "gt boxes: not with 3-D boxes on (pbd_candidates_box3d works on the returned records)");
+    if (h->cl3_on) return fail(h, PBD_ERR_UNSUPPORTED, "gt boxes: not with object clusters on (pbd_candidates_cluster3d works on the returned boxes)");
+    if (h->ps_on) return fail(h, PBD_ERR_UNSUPPORTED, "gt boxes: not with per-part scores on (pbd_candidates_part_scores works on the returned records)");
+  }
+  if (nframes < 1 || nframes > PBD_MAX_BATCH) return fail(h, PBD_ERR_ARG, "batch: 1..64 frames");
+  if (!std::isfinite(overlap)) return fail(h, PBD_ERR_ARG, "gt boxes: overlap must be finite");
+  if (!ngt) return fail(h, PBD_ERR_ARG, "gt boxes: null ngt");
+  for (int f = 0; f < nframes; ++f) {
+    if (ngt[f] < 0 || ngt[f] > PBD_GT_MAX) return fail(h, PBD_ERR_ARG, "gt boxes: ngt outside 0..PBD_GT_MAX");
+    if (ngt[f] > 0 && !gt) return fail(h, PBD_ERR_ARG, "gt boxes: null boxes");
+    for (int k = 0; k < ngt[f] * 4; ++k)
+      if (!std::isfinite(gt[(size_t)f * PBD_GT_MAX * 4 + k])) return fail(h, PBD_ERR_ARG, "gt boxes: a non-finite coordinate");
+  }
+  return PBD_OK;
+}
+// the planes of `cap` records and the tables of PBD_MAX_BATCH frames: model-sized, on first use
+static int gt_buffers(pbd_handle* h) {
+  if (h->d_gt_cbox) return PBD_OK;
+  const size_t cap = (size_t)h->opt.max_candidates, slots = (size_t)PBD_MAX_BATCH * PBD_GT_MAX;
+  int rc;
+  if ((rc = model_alloc(h, &h->d_gt_key, cap)) || (rc = model_alloc(h, &h->d_gt_rank, cap)) || (rc = model_alloc(h, &h->d_gt_frame, cap)) ||
+      (rc = model_alloc(h, &h->d_gt, slots * 4 + PBD_MAX_BATCH)) || (rc = model_alloc(h, &h->h_gt, slots * 4 + PBD_MAX_BATCH, true, false)) ||
+      (rc = model_alloc(h, &h->h_gt_out, h->cand_stride * slots, true, false)) || (rc = model_alloc(h, &h->h_gt_found, slots, true, false)) ||
+      (rc = model_alloc(h, &h->h_gt_o, slots, true, false)) || (rc = model_alloc(h, &h->d_gt_cbox, cap)))
+    return rc;
+  return PBD_OK;
+}
+static GtBoxArgs gt_args(const pbd_handle* h, int nframes, double overlap) {
+  GtBoxArgs a{};
+  a.in.stride = h->cand_stride; a.in.mp = h->max_parts;
+  a.nframes = nframes; a.overlap = overlap;
+  return a;
+}
+// On a planned frame: the in-frame rank packs (virtual level, component, root y, root x) into 16 bits each; then the boxes of every
+// frame, uploaded in the handle's stream from a pinned staging copy (the caller's arrays may go away once the entry returns)
+int pbd_i_gt_begin(pbd_handle* h, const GtSource& s, int nframes) {
+  if (h->nvl > 65536 || h->md.ncomponents > 65536) return fail(h, PBD_ERR_UNSUPPORTED, "gt boxes: more than 65536 (virtual) levels or components");
+  for (const Level& L : h->lv)
+    if (L.cw > 65536 || L.ch > 65536) return fail(h, PBD_ERR_UNSUPPORTED, "gt boxes: a level of more than 65536 cells a side");
+  int rc = gt_buffers(h);
+  if (rc) return rc;
+  const size_t nd = (size_t)nframes * PBD_GT_MAX * 4;
+  int* hn = (int*)(h->h_gt + (size_t)PBD_MAX_BATCH * PBD_GT_MAX * 4);
+  h->gt_max = 0;
+  for (int f = 0; f < nframes; ++f) {
+    if (s.ngt[f]) memcpy(h->h_gt + (size_t)f * PBD_GT_MAX * 4, s.gt + (size_t)f * PBD_GT_MAX * 4, sizeof(double) * 4 * s.ngt[f]);
+    hn[f] = s.ngt[f];
+    h->gt_max = std::max(h->gt_max, s.ngt[f]);
+  }
+  HIPCHK(h, hipMemcpyAsync(h->d_gt, h->h_gt, sizeof(double) * nd, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->d_gt + (size_t)PBD_MAX_BATCH * PBD_GT_MAX * 4, hn, sizeof(int) * nframes, hipMemcpyHostToDevice, h->stream));
+  h->gt_overlap = s.overlap;
+  return PBD_OK;
+}
+// behind launch_backtrack (into `raw`, a device list): the selection, its results straight into pinned memory; the records' count follows
+// by a copy (the collect refuses an overflowed list: the selection would be incomplete)
+int pbd_i_gt_enqueue(pbd_handle* h, char* raw) {
+  GtBoxArgs a = gt_args(h, h->batch, h->gt_overlap);
+  a.in.p = raw; a.in.count = h->d_cand_count; a.in.capacity = h->opt.max_candidates; a.in.nlevels = h->nlevels;
+  a.gt = h->d_gt; a.ngt = (const int*)(h->d_gt + (size_t)PBD_MAX_BATCH * PBD_GT_MAX * 4);
+  a.cbox = h->d_gt_cbox; a.key = h->d_gt_key; a.rank = h->d_gt_rank; a.frame = h->d_gt_frame;
+  a.out = h->h_gt_out; a.found = h->h_gt_found; a.o = h->h_gt_o;
+  launch_gtbox(a, h->gt_max, h->stream);
+  LAUNCHCHK(h, "argmin + gt boxes");
+  HIPCHK(h, hipMemcpyAsync(h->h_cand_count, h->d_cand_count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  h->pending = true; h->gt_pending = true;
+  h->out_on_host = true;   // (nothing of the records themselves is fetched)
+  return PBD_OK;
+}
+// the collect (stream synchronised, the list did not overflow): the winners of every frame -> the caller's arrays
+void pbd_i_gt_gather(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int* found, double* o) {
+  const int mp = h->max_parts;
+  const int* hn = (const int*)(h->h_gt + (size_t)PBD_MAX_BATCH * PBD_GT_MAX * 4);
+  for (int f = 0; f < h->batch; ++f)
+    for (int g = 0; g < hn[f]; ++g) {
+      const size_t slot = (size_t)f * PBD_GT_MAX + g;
+      const bool hit = h->gt_max > 0 && h->h_gt_found[slot] != 0;
+      if (found) found[slot] = hit;
+      if (o) o[slot] = hit ? h->h_gt_o[slot] : 0.0;
+      if (!hit) continue;
+      pbd_rec_get(h->h_gt_out + h->cand_stride * slot, mp, heads, boxes, locs, slot);
+      if (heads) heads[slot].level -= f * h->nlevels;   // virtual level -> the frame's own pyramid level
+    }
 }
 
 // ---- behind the back-tracking ---------------------------------------------------------------------------------------------
@@ -1108,6 +1202,72 @@ int pbd_candidates_features_dev(pbd_handle* h, const pbd_candidate_head* heads, 
   launch_featvec(a, h->ts, h->stream);
   LAUNCHCHK(h, "feature vectors");
   return PBD_OK;
+}
+
+// ---- best pose per ground-truth box (k_gtbox.hip) ---------------------------------------------------------------------------
+// bestoverlap.m's rule (include/pbd_c.h); k_gtbox.hip computes the same from the same text (gt_overlap.hpp)
+int pbd_candidates_best_overlap(const pbd_candidate_head* heads, const int32_t* boxes, int count, int mp, const double* gt, int ngt,
+                                double overlap, int32_t* best, double* o) {
+  if (count < 0 || mp <= 0 || ngt < 0 || ngt > PBD_GT_MAX || !std::isfinite(overlap)) return PBD_ERR_ARG;
+  if ((count > 0 && (!heads || !boxes)) || (ngt > 0 && (!gt || !best || !o))) return PBD_ERR_ARG;
+  for (int k = 0; k < ngt * 4; ++k) if (!std::isfinite(gt[k])) return PBD_ERR_ARG;
+  for (int i = 0; i < count; ++i)
+    if (!std::isfinite(heads[i].score) || heads[i].nparts < 0 || heads[i].nparts > mp) return PBD_ERR_ARG;
+  std::vector<GtCentreBox> cb((size_t)count);
+  for (int i = 0; i < count; ++i)
+    if (heads[i].nparts > 0) cb[i] = gt_centre_box(boxes + (size_t)i * mp * 4, heads[i].nparts);
+  for (int g = 0; g < ngt; ++g) {
+    int b = -1;
+    double ob = 0.0;
+    for (int i = 0; i < count; ++i) {
+      if (heads[i].nparts == 0) continue;
+      const double ov = gt_overlap(gt + (size_t)g * 4, cb[i]);
+      if (!(ov > overlap)) continue;
+      if (b < 0 || heads[i].score > heads[b].score) { b = i; ob = ov; }   // (the first of equal scores stays: MATLAB's max)
+    }
+    best[g] = b; o[g] = ob;
+  }
+  return PBD_OK;
+}
+
+int pbd_candidates_select_gt(pbd_handle* h, const double* gt, int ngt, double overlap, const pbd_candidate_head* heads,
+                             const int32_t* boxes, int count, int32_t* best, double* o) {
+  if (!h) return PBD_ERR_ARG;
+  int rc = pbd_i_gt_check(h, gt, &ngt, 1, overlap, false);
+  if (rc) return rc;
+  if (count < 0 || (count > 0 && (!heads || !boxes)) || (ngt > 0 && (!best || !o))) return fail(h, PBD_ERR_ARG, "heads / boxes / count / best / o");
+  for (int i = 0; i < count; ++i) {
+    if (!std::isfinite(heads[i].score)) return fail(h, PBD_ERR_ARG, "non-finite score: its order is undefined");
+    if (heads[i].nparts < 0 || heads[i].nparts > h->max_parts) return fail(h, PBD_ERR_ARG, "nparts outside 0..max_parts");
+  }
+  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  for (int g = 0; g < ngt; ++g) { best[g] = -1; o[g] = 0.0; }
+  if (ngt == 0 || count == 0) return PBD_OK;
+  ON_DEVICE(h);
+  const int mp = h->max_parts;
+  const size_t st = h->cand_stride, n = (size_t)count;
+  std::vector<char> rec(st * n, 0);
+  for (size_t i = 0; i < n; ++i) pbd_rec_put(rec.data() + st * i, mp, heads, boxes, nullptr, i);
+  Scratch s(h);
+  GtBoxArgs a = gt_args(h, 1, overlap);
+  char* d_rec = s.dev<char>(st * n);
+  int* d_cnt = s.dev<int>(2);
+  double* d_gt = s.dev<double>((size_t)ngt * 4);
+  a.in.p = d_rec; a.in.count = d_cnt; a.in.capacity = count; a.in.nlevels = 0;
+  a.gt = d_gt; a.ngt = d_cnt + 1;
+  a.cbox = s.dev<double4>(n); a.key = s.dev<unsigned>(n); a.rank = s.dev<unsigned long long>(n); a.frame = s.dev<int>(n);
+  a.found = s.dev<int>(PBD_GT_MAX); a.o = s.dev<double>(PBD_GT_MAX); a.best = s.dev<int>(PBD_GT_MAX);
+  const int cnt2[2] = {count, ngt};
+  s.up(d_rec, rec.data(), st * n);
+  s.up(d_cnt, cnt2, sizeof(cnt2));
+  s.up(d_gt, gt, sizeof(double) * 4 * ngt);
+  if (s.ok()) {
+    launch_gtbox(a, ngt, h->stream);
+    s.launched();
+  }
+  s.down(best, a.best, sizeof(int) * ngt);
+  s.down(o, a.o, sizeof(double) * ngt);
+  return s.finish("gt boxes: ");
 }
 
 }  // extern "C"

@@ -130,6 +130,13 @@ class Candidate:
         after a cut to the `top` best (0: none)."""
         return Candidate._unpack(*capi.candidates_nms_parts(*Candidate._pack(candidates), overlap, top))
 
+    @staticmethod
+    def bestOverlap(candidates: List["Candidate"], gt, overlap: float = 0.3):
+        """matlab/detection/bestoverlap.m per gt box (x1, y1, x2, y2): (index of the highest-scoring candidate whose box of part
+        centres covers more than `overlap` of the box, or -1; its overlap) — the first of equal scores."""
+        heads, boxes, _ = Candidate._pack(candidates)
+        return capi.candidates_best_overlap(heads, boxes, gt, overlap)
+
 
 class HOGFeatures:
     """IFeatures implementation (include/HOGFeatures.hpp:52-88) on the device."""
@@ -452,6 +459,16 @@ class PartsBasedDetector:
         (in [0, 1)); mix[p] >= 0 fixes part p's mixture (-1 / None: free); component = -1 searches all.  Returns one Candidate or
         an empty list; the model's threshold plays no part.  With setPartScores on, the Candidate carries its parts' scores."""
         return Candidate._unpack(*self.handle.detect_latent(im, truth, overlap, mix, component), self._ps())
+
+    def detectGtBox(self, im: np.ndarray, gt, overlap: float = 0.3):
+        """matlab/detection/testmodel_gtbox.m:17-21: detect at the model's threshold, then per gt box (x1, y1, x2, y2) the
+        highest-scoring pose whose box of part centres covers more than `overlap` of it (bestoverlap.m) — selected on the GPU, only
+        the winners come home.  Returns (one Candidate or None per gt box, their overlaps).  RAW candidate mode, no depth stages,
+        no per-part scores."""
+        heads, boxes, locs, found, o = self.handle.detect_gtbox(im, gt, overlap)
+        hit = np.flatnonzero(found)
+        cands = iter(Candidate._unpack(heads[hit], boxes[hit], locs[hit]))
+        return [next(cands) if f else None for f in found], o
 
     def features(self, candidates: List[Candidate]):
         """The feature vectors of `candidates` (what detect() or detect_latent() of the LAST frame returned, or a selection of them):

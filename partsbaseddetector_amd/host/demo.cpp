@@ -1,5 +1,6 @@
 // demo.cpp — the reference's canonical caller (src/demo.cpp:55-118) against the MI355X path:
 //   pbd_demo model.bin image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE] [--matlab-pyramid]
+//            [--gtbox x1,y1,x2,y2[,overlap]]...
 //   pbd_demo model.bin image.raw width height channels perturb-features <responses-out.bin>
 //   pbd_demo model.bin image.raw width height channels oracle-responses <responses-in.bin>
 // deserialize -> distributeModel -> detect -> Candidate::sort, then prints the candidates (the
@@ -12,6 +13,16 @@
 #include <memory>
 #include "pbd_filestorage.hpp"
 using namespace pbd;
+
+// --gtbox x1,y1,x2,y2[,overlap] (anywhere, repeatable): testmodel_gtbox.m's protocol — per box the highest-scoring pose whose part centres'
+// box covers more than `overlap` of it (default 0.3; the last one given holds for every box), printed instead of the candidate list
+static std::vector<GtBox> g_gtbox;
+static double g_gt_overlap = 0.3;
+static void print_pose(const Candidate& c) {
+  printf("%.9g %d %d", c.score(), c.component(), c.level);
+  for (const Rect& r : c.parts()) printf(" %d,%d,%d,%d", r.x, r.y, r.width, r.height);
+  printf("\n");
+}
 
 // The stage interfaces process THEIR ARGUMENTS (include/IConvolutionEngine.hpp:56, include/DynamicProgram.hpp:74-75):
 //   perturb:  the feature pyramid is halved in place between pyramid() and pdf(); the responses of the first and the
@@ -81,11 +92,33 @@ static void run(Model& model, const Mat& im, bool stagewise, int special = 0, co
               for (int i = 0; i < t->rows * t->cols; ++i) sum += (++idx) * (unsigned long long)(unsigned)t->ptr<int32_t>()[i];
     printf("Tables: %llu\n", sum);
     pbd.dp().argmin(pbd.parts(), rootv, rooti, pbd.features().scales(), Ix, Iy, Ik, candidates);   // :89
+  } else if (!g_gtbox.empty()) {   // the selection runs on the GPU behind the detect: only the winners come back
+    std::vector<int> which;
+    std::vector<double> o;
+    pbd.detectGtBox(im, g_gtbox, g_gt_overlap, candidates, &which, &o);
+    for (size_t g = 0; g < g_gtbox.size(); ++g) {
+      printf("GtBox %zu (%g,%g,%g,%g) overlap > %g: ", g, g_gtbox[g].x1, g_gtbox[g].y1, g_gtbox[g].x2, g_gtbox[g].y2, g_gt_overlap);
+      if (which[g] < 0) { printf("none\n"); continue; }
+      printf("o %.17g: ", o[g]);
+      print_pose(candidates[which[g]]);
+    }
+    return;
   } else {
     Mat depth;
     pbd.detect(im, depth, candidates);
   }
   printf("Number of candidates: %ld\n", (long)candidates.size());
+  if (!g_gtbox.empty()) {          // stagewise: the host function on the candidates argmin() returned, in their order
+    std::vector<double> o;
+    const std::vector<int> which = Candidate::bestOverlap(candidates, g_gtbox, g_gt_overlap, &o);
+    for (size_t g = 0; g < g_gtbox.size(); ++g) {
+      printf("GtBox %zu (%g,%g,%g,%g) overlap > %g: ", g, g_gtbox[g].x1, g_gtbox[g].y1, g_gtbox[g].x2, g_gtbox[g].y2, g_gt_overlap);
+      if (which[g] < 0) { printf("none\n"); continue; }
+      printf("o %.17g: ", o[g]);
+      print_pose(candidates[which[g]]);
+    }
+    return;
+  }
   Candidate::sort(candidates);
   if (nms_parts) {
     if (stagewise) Candidate::nonMaximaSuppressionParts(candidates, *nms_parts, 1000);
@@ -160,6 +193,24 @@ int main(int argc, char** argv) {
       for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
       argc -= 2; --i;
     } else
+    if (std::string(argv[i]) == "--gtbox") {
+      double v[5] = {0, 0, 0, 0, g_gt_overlap};
+      int n = 0;
+      const char* p = i + 1 < argc ? argv[i + 1] : "";
+      while (*p && n < 5) {
+        char* end = nullptr;
+        v[n] = strtod(p, &end);
+        if (end == p || !(v[n] - v[n] == 0.0)) { n = -1; break; }
+        ++n;
+        p = *end == ',' ? end + 1 : end;
+        if (*end && *end != ',') { n = -1; break; }
+      }
+      if (n < 4 || *p || g_gtbox.size() >= PBD_GT_MAX) { printf("--gtbox x1,y1,x2,y2[,overlap]: finite numbers, at most %d boxes\n", PBD_GT_MAX); exit(-1); }
+      g_gtbox.push_back(GtBox{v[0], v[1], v[2], v[3]});
+      g_gt_overlap = v[4];
+      for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+      argc -= 2; --i;
+    } else
     if (std::string(argv[i]) == "--features") {
       if (i + 1 >= argc || !*argv[i + 1]) { printf("--features FILE\n"); exit(-1); }
       features_file = argv[i + 1];
@@ -177,7 +228,7 @@ int main(int argc, char** argv) {
       --argc; --i;
     }
   if (argc < 6 || argc > 8) {
-    printf("Usage: pbd_demo model_file image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE] [--nms-parts OVERLAP] [--matlab-pyramid]\n");
+    printf("Usage: pbd_demo model_file image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE] [--nms-parts OVERLAP] [--matlab-pyramid] [--gtbox x1,y1,x2,y2[,overlap]]...\n");
     exit(-1);
   }
   // determine the type of model to read (src/demo.cpp:63-82)
@@ -204,6 +255,7 @@ int main(int argc, char** argv) {
   try {
     if (part_scores && stagewise) { printf("--part-scores: the fused detect() only\n"); exit(-1); }
     if (features_file && special) { printf("--features: not with %s\n", mode.c_str()); exit(-1); }
+    if (!g_gtbox.empty() && (part_scores || nms_parts || features_file)) { printf("--gtbox: not with --part-scores, --nms-parts or --features\n"); exit(-1); }
     if (mode.find("double") != std::string::npos) run<double>(model, im, stagewise, 0, nullptr, part_scores, pad, features_file, nms_parts, matlab_pyramid);
     else run<float>(model, im, stagewise, special, special ? argv[7] : nullptr, part_scores, pad, features_file, nms_parts, matlab_pyramid);
   } catch (const Exception& e) {

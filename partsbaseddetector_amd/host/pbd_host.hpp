@@ -77,6 +77,9 @@ typedef std::vector<vectori> vector2Di;
 typedef std::vector<vector2Di> vector3Di;
 typedef std::vector<vectorf> vector2Df;
 
+// a ground-truth box of testmodel_gtbox.m: inclusive corners (x1, y1, x2, y2), as doubles (include/pbd_c.h "best pose per ground-truth box")
+struct GtBox { double x1, y1, x2, y2; };
+
 // ---- include/Candidate.hpp:56-111 ---------------------------------------------------------
 class Candidate {
   std::vector<Rect> parts_;
@@ -120,6 +123,10 @@ class Candidate {
   // matlab/detection/nms.m on sorted candidates (pbd_candidates_nms_parts): part by part and by the covering box, over the kept
   // detection's area, after a cut to the `top` best (1000: nms.m's; 0: none)
   static void nonMaximaSuppressionParts(std::vector<Candidate>& c, float overlap = 0.3f, int top = 1000);
+  // matlab/detection/bestoverlap.m (pbd_candidates_best_overlap): per gt box the index in `c` of the highest-scoring candidate whose
+  // box of part centres covers more than `overlap` of it, or -1; the first of equal scores.  o (may be null): the winners' overlaps
+  static std::vector<int> bestOverlap(const std::vector<Candidate>& c, const std::vector<GtBox>& gt, double overlap = 0.3,
+                                      std::vector<double>* o = nullptr);
 };
 typedef std::vector<Candidate> vectorCandidate;
 
@@ -778,6 +785,31 @@ class PartsBasedDetector {
     append_candidates(candidates, heads, boxes, locs, n, mp);
     attach_part_scores(candidates, n, mp);
   }
+  // testmodel_gtbox.m:17-21: detect at the model's threshold, then per gt box bestoverlap(box, gtbox, overlap) — on the GPU, where only
+  // the winners come home.  The chosen pose of every gt box that has one is appended to `candidates`; which[g] (may be null) = its index
+  // in `candidates` or -1, o[g] (may be null) its overlap.  RAW candidate mode, no depth stages, no per-part scores; 8-bit frames.
+  void detectGtBox(const Mat& im, const std::vector<GtBox>& gt, double overlap, vectorCandidate& candidates,
+                   std::vector<int>* which = nullptr, std::vector<double>* o = nullptr) {
+    if (!dev_) throw Exception(PBD_ERR_STATE, "detectGtBox() before distributeModel()");
+    if (im.depth() != PBD_8U) throw Exception(PBD_ERR_UNSUPPORTED, "gt boxes: 8-bit colour frames only");
+    const int mp = pbd_max_parts(dev_->h), ng = (int)gt.size();
+    std::vector<pbd_candidate_head> heads((size_t)std::max(ng, 1)), one(1);
+    std::vector<int32_t> boxes((size_t)std::max(ng, 1) * mp * 4), locs((size_t)std::max(ng, 1) * mp * 3);
+    std::vector<int> found((size_t)std::max(ng, 1), 0);
+    std::vector<double> ov((size_t)std::max(ng, 1), 0.0);
+    static_assert(sizeof(GtBox) == 4 * sizeof(double), "GtBox layout");
+    dev_->check(pbd_detect_gtbox_u8(dev_->h, im.ptr<uint8_t>(), im.cols, im.rows, im.channels(), (int)im.step(),
+                                    ng ? &gt[0].x1 : nullptr, ng, overlap, heads.data(), boxes.data(), locs.data(), found.data(), ov.data(), nullptr));
+    if (which) which->assign((size_t)ng, -1);
+    if (o) o->assign(ov.begin(), ov.begin() + ng);
+    for (int g = 0; g < ng; ++g) {
+      if (!found[g]) continue;
+      if (which) (*which)[g] = (int)candidates.size();
+      one[0] = heads[g];
+      append_candidates(candidates, one, std::vector<int32_t>(boxes.begin() + (size_t)g * mp * 4, boxes.begin() + (size_t)(g + 1) * mp * 4),
+                        std::vector<int32_t>(locs.begin() + (size_t)g * mp * 3, locs.begin() + (size_t)(g + 1) * mp * 3), 1, mp);
+    }
+  }
   // The feature vectors of `candidates` — records of the LAST frame's detect() / detectLatent(), or a selection of them — gathered by
   // the GPU from the frame's resident feature planes: what matlab/detection/detect.m:272-308 collects as ex.blocks.  blocks[i *
   // max_parts + p] (ids -1 beyond the record's parts), windows[(i * max_parts + p) * wmax ...]: part p's HOG window, [kh][kw * flen] at
@@ -841,6 +873,28 @@ inline void Candidate::nonMaximaSuppressionParts(std::vector<Candidate>& c, floa
   for (int k = 0; k < kept; ++k)
     if (heads[k].level != k) c[k] = c[heads[k].level];
   c.resize((size_t)kept);
+}
+
+inline std::vector<int> Candidate::bestOverlap(const std::vector<Candidate>& c, const std::vector<GtBox>& gt, double overlap, std::vector<double>* o) {
+  size_t mp = 1;
+  for (const Candidate& k : c) mp = std::max(mp, k.parts().size());
+  std::vector<pbd_candidate_head> heads(c.size());
+  std::vector<int32_t> boxes(c.size() * mp * 4, 0);
+  for (size_t n = 0; n < c.size(); ++n) {
+    heads[n] = pbd_candidate_head{c[n].score(), c[n].component(), c[n].level, (int)c[n].parts().size()};
+    for (size_t p = 0; p < c[n].parts().size(); ++p) {
+      const Rect& r = c[n].parts()[p];
+      int32_t* b = &boxes[(n * mp + p) * 4];
+      b[0] = r.x; b[1] = r.y; b[2] = r.width; b[3] = r.height;
+    }
+  }
+  std::vector<int> best(gt.size(), -1);
+  std::vector<double> ov(gt.size(), 0.0);
+  const int rc = pbd_candidates_best_overlap(heads.data(), boxes.data(), (int)c.size(), (int)mp, gt.empty() ? nullptr : &gt[0].x1, (int)gt.size(),
+                                             overlap, best.data(), ov.data());
+  if (rc != PBD_OK) throw Exception(rc, "Candidate::bestOverlap: finite gt boxes, overlap and scores, at most PBD_GT_MAX boxes");
+  if (o) *o = ov;
+  return best;
 }
 
 }  // namespace pbd
