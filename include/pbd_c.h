@@ -171,7 +171,8 @@ int pbd_abi_version(void);
  * pbd_candidates_features_f64 and pbd_candidates_features_dev (with the struct pbd_feature_block); and the part-wise NMS entry
  * points pbd_candidates_nms_parts, pbd_set_candidate_nms, pbd_group_set_candidate_nms and pbd_candidates_filter_parts; and the
  * best-pose-per-ground-truth-box entry points pbd_candidates_best_overlap, pbd_candidates_select_gt, pbd_detect_gtbox_u8,
- * pbd_detect_gtbox_dev_u8 and pbd_detect_batch_gtbox_u8 (with PBD_GT_MAX).                                                          */
+ * pbd_detect_gtbox_dev_u8 and pbd_detect_batch_gtbox_u8 (with PBD_GT_MAX); and the training example cache pbd_qp with its entry
+ * points pbd_qp_create, _destroy, _dims, _footprint, _write, _score[_dev], _lincomb[_dev], _keep, _get and _put.                    */
 
 /* ---- output record: include/Candidate.hpp:56-111 --------------------------
  * One candidate = head + max_parts boxes (x, y, width, height as cv::Rect)
@@ -952,6 +953,77 @@ int pbd_candidates_features_f64(pbd_handle* h, const pbd_candidate_head* heads, 
                                 pbd_feature_block* blocks, double* windows);
 int pbd_candidates_features_dev(pbd_handle* h, const pbd_candidate_head* heads, const int32_t* locs, int count,
                                 pbd_feature_block* d_blocks, void* d_windows);
+
+/* ---- training example cache: qp_write, score and lincomb on the GPU (ABI 5, additive) -------------------------------------------
+ * detect(im, model, thresh, bbox, overlap, id, label) of matlab/detection/detect.m hands every back-tracked pose to qp_write(ex)
+ * (matlab/learning/train.m:102), which appends it to the QP's cache of block-sparse examples; matlab/mex/score.cc and lincomb.cc sweep
+ * that cache.  pbd_qp is that cache, resident on the device: detections are written into it from the feature planes without leaving
+ * HBM, it is scored against a weight vector and combined linearly into one.  The coordinate-descent pass itself
+ * (matlab/mex/qp_one_sparse.cc, qp_opt.m, the loss) is OUT OF SCOPE: it is a serial chain through w and stays with a host solver,
+ * which reads the cache with pbd_qp_get and loads columns with pbd_qp_put.
+ *
+ * Dense index space: Model.feature_layout() of the binding — [biasw | defw (ndefs x 4) | the filters back to back in the caller's
+ *   order, each [kh][kw * flen]] —, length len.  len >= 2^24 is refused (PBD_ERR_UNSUPPORTED): block bounds are stored as floats,
+ *   as in MATLAB (train.m:59, qp.x is single).
+ * Example column: qp.x(:,i) verbatim (qp_write.m:46-68), k float32 values: x[0] = number of blocks, then per block i1, i2 (1-based
+ *   inclusive bounds into the dense space) and its i2 - i1 + 1 values; the tail is zero.  A column read back can be handed to the
+ *   compiled reference files.  k is sparselen of train.m:207-239 — 1 + 2 * blocks + values of a pose —, the maximum over the
+ *   components, each part counted at its largest mixture's filter (train.m counts the first mixture's).
+ * Block order: detect.m:272-308 — the root's bias, the root's window; then per later part, in part order, bias, deformation, window.
+ *   Ids, deformation values and window contents are exactly those of pbd_feature_block above (border rule, padded planes, the
+ *   handle's own feature values in T): the same device text gathers both (csrc/featvec_gather.hpp).  The window is laid out
+ *   [kh][kw][flen] like this port's filters, not MATLAB's column-major [sizy][sizx][flen].
+ * Standardisation (qp_write.m:49-72): C = label > 0 ? cpos : cneg; with label <= 0 every value v is negated first (a zero
+ *   becomes -0.0); the stored value is (float)((C * v) / wreg[j]) with v widened to double, evaluated in that order; d is the sum of
+ *   the squares of the unrounded double values (C * v) / wreg[j]; b = (float)(C * (1 - sum_blocks w0[j] . v)), v signed and
+ *   unscaled (qp_write.m:59 runs before :60).  MATLAB's x'*x has no defined order; this library's is fixed: a block's sum is 64
+ *   partial sums (partial t starts at +0.0 and adds the block's terms t, t + 64, ... in that order), folded s[t] += s[t + h] for
+ *   h = 32, 16, .. 1; d adds the blocks' sums to 0 in block order, and 1 has the blocks' sums subtracted in block order.  No
+ *   product is fused into a sum.  It does not depend on the launch, the capacity or the record's position in the call.
+ * Example id: five int32 (label, id, level, x_root, y_root), level and root location as the record carries them.  DEVIATION:
+ *   detect.m:273 stores round(x + sizx / 2); this port stores its root cell.  Ids are only ever compared for equality.  The
+ *   component is not part of it, as in MATLAB.
+ * Defaults (matlab/learning/model2vec.m): wreg = .01 at the root bias of every component, 1 elsewhere; w0 = .01 at elements 0 and 2 of
+ *   every deformation, 0 elsewhere.  The caller may pass their own (len doubles each; wreg finite and non-zero).
+ * Repeated blocks: a record whose blocks repeat a dense start index (two parts of the pose share a filter, def or bias id) hits
+ *   qp_write's assertion (:34-35): checked on the host before any launch, PBD_ERR_ARG with nothing written, for the whole call.
+ *
+ * pbd_qp is bound to the handle it was created from (model tables, scalar type, stream, device) and must be destroyed before it;
+ * pbd_group members are refused (PBD_ERR_UNSUPPORTED).  Indices are 0-based.  Errors are reported through the handle
+ * (pbd_last_error).  capacity >= 1 examples.
+ * pbd_qp_write: `count` host records (heads + locs, as pbd_candidates_features_dev: same preconditions and refusals) against the
+ *   handle's resident feature planes; appends min(count, capacity - n) examples — a full cache is no error (qp_write.m:21-23) —,
+ *   *written = that number.  A full cache returns at once: nothing is uploaded.  Otherwise the records' upload synchronises the
+ *   handle's stream (earlier work on it is done when the call returns); the kernel is then enqueued on that stream, not finished.
+ *   There is no scalar-type refusal (PBD_ERR_STATE of the _f64 entries elsewhere): no pbd_qp entry takes a pointer typed by the
+ *   handle's scalar — columns are float32, sums and weights double on float and double handles alike — so a mismatch cannot arise.
+ * pbd_qp_score (matlab/mex/score.cc): out[i] = the score of w on example inds[i] — each product rounded, added in storage order,
+ *   bit for bit what the compiled reference file computes; inds NULL: examples 0 .. n - 1.  _dev: device pointers, enqueued on the
+ *   handle's stream (inds are not range-checked there: the caller's business).
+ * pbd_qp_lincomb (matlab/mex/lincomb.cc): w_out = sum_i a[inds[i]] * x(:, inds[i]), w starting at zero, the examples added in the
+ *   order of inds (qp_refresh.m:16-17 sorts by a for a reason), each product rounded: bit for bit the reference file's.  a is
+ *   indexed by example, capacity doubles.  _dev as above.  No atomics, no tree: qp_one_sparse.cc branches on G > 1e-12 and on
+ *   A[i] == 0 && G >= 0, and a solver fed sums that vary with the launch is not reproducible.
+ * pbd_qp_keep (qp_prune.m:18-25): with inds strictly ascending, the kept examples become 0 .. n - 1 in that order.  An index table
+ *   is permuted; no column moves.
+ * pbd_qp_get: examples i0 .. i0 + n - 1 (i0 + n <= capacity: columns behind the cache's n can be read too) — x[n * k],
+ *   ids[n * 5], b[n], d[n], each may be NULL.  pbd_qp_put appends n columns made elsewhere (warped positives): every column's block
+ *   bounds are validated against len and k (PBD_ERR_ARG, nothing appended); more than 3 * max_parts blocks in a column — more than
+ *   any pose has — is PBD_ERR_UNSUPPORTED; beyond the capacity: PBD_ERR_CAPACITY, nothing appended.
+ * pbd_qp_footprint: device bytes held by the cache.                                                                               */
+typedef struct pbd_qp pbd_qp;
+int pbd_qp_create(pbd_handle* h, int capacity, double cpos, double cneg, const double* wreg, const double* w0, pbd_qp** qp);
+void pbd_qp_destroy(pbd_qp* qp);
+int pbd_qp_dims(const pbd_qp* qp, int* len, int* k, int* capacity, int* n);
+int pbd_qp_footprint(const pbd_qp* qp, size_t* bytes);
+int pbd_qp_write(pbd_qp* qp, const pbd_candidate_head* heads, const int32_t* locs, int count, int label, int id, int* written);
+int pbd_qp_score(pbd_qp* qp, const double* w, const int32_t* inds, int n, double* out);
+int pbd_qp_score_dev(pbd_qp* qp, const double* d_w, const int32_t* d_inds, int n, double* d_out);
+int pbd_qp_lincomb(pbd_qp* qp, const double* a, const int32_t* inds, int n, double* w_out);
+int pbd_qp_lincomb_dev(pbd_qp* qp, const double* d_a, const int32_t* d_inds, int n, double* d_w_out);
+int pbd_qp_keep(pbd_qp* qp, const int32_t* inds, int n);
+int pbd_qp_get(pbd_qp* qp, int i0, int n, float* x, int32_t* ids, float* b, double* d);
+int pbd_qp_put(pbd_qp* qp, int n, const float* x, const int32_t* ids, const float* b, const double* d);
 
 /* ---- instrumentation --------------------------------------------------------
  * GPU time (ms, hipEvent) of the stages of the last synchronous detect:

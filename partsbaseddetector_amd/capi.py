@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -63,6 +64,8 @@ EXPORTS = [
     "pbd_set_pyramid_kind", "pbd_get_pyramid_kind", "pbd_resize_area_f64", "pbd_reduce_f64",
     "pbd_candidates_best_overlap", "pbd_candidates_select_gt", "pbd_detect_gtbox_u8", "pbd_detect_gtbox_dev_u8",
     "pbd_detect_batch_gtbox_u8",
+    "pbd_qp_create", "pbd_qp_destroy", "pbd_qp_dims", "pbd_qp_footprint", "pbd_qp_write", "pbd_qp_score", "pbd_qp_score_dev",
+    "pbd_qp_lincomb", "pbd_qp_lincomb_dev", "pbd_qp_keep", "pbd_qp_get", "pbd_qp_put",
 ]
 PBD_ABI_VERSION = 5
 
@@ -146,6 +149,17 @@ def lib() -> C.CDLL:
         L.pbd_group_member.argtypes = [C.c_void_p, C.c_int]
         for name in EXPORTS:
             getattr(L, name)  # every declared symbol must be exported
+        L.pbd_qp_create.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pbd_qp_destroy.restype = None
+        L.pbd_qp_destroy.argtypes = [C.c_void_p]
+        L.pbd_qp_dims.argtypes = [C.c_void_p] * 5
+        L.pbd_qp_footprint.argtypes = [C.c_void_p, C.c_void_p]
+        L.pbd_qp_write.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        for name in ("pbd_qp_score", "pbd_qp_score_dev", "pbd_qp_lincomb", "pbd_qp_lincomb_dev"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.pbd_qp_keep.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.pbd_qp_get.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pbd_qp_put.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         if L.pbd_abi_version() != PBD_ABI_VERSION:
             raise ImportError(f"{LIB_PATH}: ABI version {L.pbd_abi_version()}, this binding is for {PBD_ABI_VERSION}")
         _lib = L
@@ -477,6 +491,11 @@ class Handle:
 
     def close(self):
         if getattr(self, "h", None):
+            for ref in getattr(self, "_caches", ()):   # the example caches created from this handle go first: they borrow its device
+                q = ref()
+                if q is not None:
+                    q.close()
+            self._caches = []
             self.L.pbd_destroy(self.h)
             self.h = None
 
@@ -1130,3 +1149,119 @@ def candidates_best_overlap(heads, boxes, gt, overlap=0.3):
     if rc:
         raise PbdError(rc, "pbd_candidates_best_overlap")
     return best, o
+
+
+def _vp(a):
+    return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+class QpCache:
+    """pbd_qp (include/pbd_c.h "training example cache"): the QP's cache of block-sparse examples on the device — qp_write.m,
+    matlab/mex/score.cc and lincomb.cc.  Bound to `handle`, whose close() closes the caches it still has.  The coordinate-descent pass is not here: a
+    host solver reads the cache with get() and loads columns with put()."""
+
+    def __init__(self, handle: Handle, capacity: int, cpos: float = 1.0, cneg: float = 1.0, wreg=None, w0=None):
+        self.handle, self.L = handle, handle.L
+        wreg = None if wreg is None else np.ascontiguousarray(wreg, np.float64)
+        w0 = None if w0 is None else np.ascontiguousarray(w0, np.float64)
+        size = handle.model.feature_layout()["size"]
+        for v in (wreg, w0):
+            if v is not None and v.size != size:
+                raise ValueError(f"wreg / w0 must have Model.feature_layout()['size'] = {size} elements")
+        self.q = C.c_void_p()
+        handle._chk(self.L.pbd_qp_create(handle.h, int(capacity), float(cpos), float(cneg), _vp(wreg), _vp(w0), C.byref(self.q)))
+        if not hasattr(handle, "_caches"):
+            handle._caches = []
+        handle._caches.append(weakref.ref(self))   # Handle.close() closes the caches it still has: nothing of theirs outlives it
+
+    def dims(self):
+        """(len, k, capacity, n): dense length, column length, capacity and examples held"""
+        v = [C.c_int() for _ in range(4)]
+        self.handle._chk(self.L.pbd_qp_dims(self.q, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def footprint(self) -> int:
+        b = C.c_size_t()
+        self.handle._chk(self.L.pbd_qp_footprint(self.q, C.byref(b)))
+        return b.value
+
+    def write(self, heads, locs, label: int, id: int) -> int:
+        """pbd_qp_write: the records (as Handle.candidates_features takes them) appended as examples; returns how many were."""
+        heads, lc = self.handle._records(heads, locs)
+        written = C.c_int(-1)
+        self.handle._chk(self.L.pbd_qp_write(self.q, heads.ctypes.data_as(C.c_void_p), _vp(lc), len(heads), int(label), int(id),
+                                             C.byref(written)))
+        return written.value
+
+    @staticmethod
+    def _inds(inds):
+        return None if inds is None else np.ascontiguousarray(inds, np.int32).ravel()
+
+    def score(self, w, inds=None) -> np.ndarray:
+        """pbd_qp_score: score.cc's w . x of the examples `inds` (None: all n), float64"""
+        length, _, _, n = self.dims()
+        w = np.ascontiguousarray(w, np.float64).ravel()
+        if w.size != length:
+            raise ValueError(f"w must have {length} elements")
+        inds = self._inds(inds)
+        cnt = n if inds is None else len(inds)
+        out = np.zeros(cnt, np.float64)
+        self.handle._chk(self.L.pbd_qp_score(self.q, _vp(w), _vp(inds), cnt, _vp(out)))
+        return out
+
+    def score_dev(self, d_w: int, d_inds: int, n: int, d_out: int) -> None:
+        """pbd_qp_score_dev: integer device pointers (d_inds 0: examples 0 .. n - 1); enqueued on the handle's stream"""
+        self.handle._chk(self.L.pbd_qp_score_dev(self.q, C.c_void_p(d_w), C.c_void_p(d_inds or None), int(n), C.c_void_p(d_out)))
+
+    def lincomb(self, a, inds=None) -> np.ndarray:
+        """pbd_qp_lincomb: lincomb.cc's sum of a[i] * x(:, i) over `inds`, in that order (None: all n); a: one value per example of
+        the capacity (shorter: padded with zeros)"""
+        length, _, cap, n = self.dims()
+        av = np.zeros(cap, np.float64)
+        a = np.asarray(a, np.float64).ravel()
+        if a.size > cap:
+            raise ValueError("a has more elements than the cache's capacity")
+        av[:a.size] = a
+        inds = self._inds(inds)
+        out = np.zeros(length, np.float64)
+        self.handle._chk(self.L.pbd_qp_lincomb(self.q, _vp(av), _vp(inds), n if inds is None else len(inds), _vp(out)))
+        return out
+
+    def lincomb_dev(self, d_a: int, d_inds: int, n: int, d_w_out: int) -> None:
+        self.handle._chk(self.L.pbd_qp_lincomb_dev(self.q, C.c_void_p(d_a), C.c_void_p(d_inds or None), int(n), C.c_void_p(d_w_out)))
+
+    def keep(self, inds) -> None:
+        """pbd_qp_keep: qp_prune.m's move — the examples `inds` (strictly ascending) become 0 .. len(inds) - 1"""
+        inds = self._inds(inds)
+        self.handle._chk(self.L.pbd_qp_keep(self.q, _vp(inds), len(inds)))
+
+    def get(self, i0: int = 0, n=None):
+        """pbd_qp_get: (x [n, k] float32, ids [n, 5] int32, b [n] float32, d [n] float64) of examples i0 .. i0 + n - 1 (None: up to
+        the cache's n)"""
+        _, k, _, have = self.dims()
+        n = max(have - i0, 0) if n is None else int(n)
+        x, ids = np.zeros((n, k), np.float32), np.zeros((n, 5), np.int32)
+        b, d = np.zeros(n, np.float32), np.zeros(n, np.float64)
+        self.handle._chk(self.L.pbd_qp_get(self.q, int(i0), n, _vp(x), _vp(ids), _vp(b), _vp(d)))
+        return x, ids, b, d
+
+    def put(self, x, ids=None, b=None, d=None) -> None:
+        """pbd_qp_put: appends columns made elsewhere (x [n, k]; ids / b / d default to zeros)"""
+        _, k, _, _ = self.dims()
+        x = np.ascontiguousarray(x, np.float32).reshape(-1, k)
+        n = len(x)
+        ids = np.zeros((n, 5), np.int32) if ids is None else np.ascontiguousarray(ids, np.int32).reshape(n, 5)
+        b = np.zeros(n, np.float32) if b is None else np.ascontiguousarray(b, np.float32).reshape(n)
+        d = np.zeros(n, np.float64) if d is None else np.ascontiguousarray(d, np.float64).reshape(n)
+        self.handle._chk(self.L.pbd_qp_put(self.q, n, _vp(x), _vp(ids), _vp(b), _vp(d)))
+
+    def close(self):
+        if getattr(self, "q", None):   # (a live cache implies a live handle: Handle.close() closes its caches before itself)
+            self.L.pbd_qp_destroy(self.q)
+        self.q = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -662,6 +662,28 @@ struct FeatVecArgs {
   void* windows;                                // T [n][mp][wmax], 16-byte aligned
 };
 void launch_featvec(const FeatVecArgs& a, int ts, hipStream_t s);
+// a feature-vector call in two steps (pbd_post.cpp), for the example cache's write: every refusal of pbd_candidates_features_dev with
+// nothing touching the device; then the tables and the first `count` (> 0) records on the device — everything of the launch but its
+// outputs (the upload synchronises the handle's stream)
+int pbd_i_fv_check(pbd_handle* h, const pbd_candidate_head* heads, const int32_t* locs, int count);
+int pbd_i_fv_upload(pbd_handle* h, const pbd_candidate_head* heads, const int32_t* locs, int count, FeatVecArgs* a);
+// training example cache (k_qp.hip, pbd_qp.cpp; include/pbd_c.h "training example cache")
+struct QpDev {
+  float* x;                 // [capacity][k]: the columns, qp.x verbatim
+  int* ids; float* b; double* d;   // [capacity][5], [capacity], [capacity]: by column
+  int* tab; int* nblk;      // [capacity][nbmax][3] (0-based dense start, length, offset of the values in the column), [capacity] blocks
+  int* slot;                // [capacity]: example -> column (pbd_qp_keep permutes this, no column moves)
+  int k, len, capacity, nbmax;
+};
+struct QpWriteArgs {
+  FeatVecArgs fv;           // the gather (blocks / windows unused): records fv.rec0 .. + fv.n - 1
+  QpDev q; int n0;          // record r becomes example n0 + r
+  const double* wreg; const double* w0; const int* foff;   // [len], [len], [nfilters] dense start of each filter
+  double C; int label, id;
+};
+void launch_qp_write(const QpWriteArgs& a, int ts, hipStream_t s);
+void launch_qp_score(const QpDev& q, const double* w, const int* inds, int n, double* out, hipStream_t s);
+void launch_qp_lincomb(const QpDev& q, const double* a, const int* inds, int n, double* w_out, hipStream_t s);
 void launch_gtbox(const GtBoxArgs& a, int gmax, hipStream_t s);   // k_gtbox.hip: gmax = the largest ngt
 // object clusters (k_cluster3d.hip)
 size_t cluster3d_slot_bytes(int pcap);

@@ -359,6 +359,7 @@ static int fv_tables(pbd_handle* h) {
 static const char* const kFvCompact =
     "feature vectors: this frame runs the compact memory plan (dp_mode 2, or automatic for large frames), whose min() reuses the "
     "memory of the feature planes the windows are read from";
+static int fv_upload(pbd_handle* h, const pbd_candidate_head* heads, const int32_t* locs, int count, FeatVecArgs* a);
 // every refusal of the three entry points, in the order of the part scores'; then the tables and the records on the device
 static int fv_begin(pbd_handle* h, const pbd_candidate_head* heads, const int32_t* locs, int count, const void* blocks, const void* windows,
                     int ts, FeatVecArgs* a) {
@@ -371,6 +372,11 @@ static int fv_begin(pbd_handle* h, const pbd_candidate_head* heads, const int32_
   if (!h->have_feat) return fail(h, PBD_ERR_STATE, h->compact ? kFvCompact : "feature vectors: features not computed");
   int rc = check_records(h, heads, locs, count);
   if (rc || count == 0) return rc;
+  return a ? fv_upload(h, heads, locs, count, a) : PBD_OK;   // (a null: the refusals alone, nothing touches the device)
+}
+// the tables and the first `count` records on the device; everything of the launch but its outputs
+static int fv_upload(pbd_handle* h, const pbd_candidate_head* heads, const int32_t* locs, int count, FeatVecArgs* a) {
+  int rc;
   ON_DEVICE(h);
   if ((rc = fv_tables(h))) return rc;
   const int mp = h->max_parts;
@@ -389,6 +395,12 @@ static int fv_begin(pbd_handle* h, const pbd_candidate_head* heads, const int32_
   A.mix0 = h->d_ps_mix0; A.mix = h->d_ps_mix; A.fmix = h->d_fv_mix;
   A.wmax = fv_wmax(h);
   return PBD_OK;
+}
+int pbd_i_fv_check(pbd_handle* h, const pbd_candidate_head* heads, const int32_t* locs, int count) {
+  return fv_begin(h, heads, locs, count, heads, heads, 0, nullptr);   // (no caller buffers to check: the cache owns the outputs)
+}
+int pbd_i_fv_upload(pbd_handle* h, const pbd_candidate_head* heads, const int32_t* locs, int count, FeatVecArgs* a) {
+  return fv_upload(h, heads, locs, count, a);
 }
 // the host variants: chunks of records through the staging buffer — a chunk's blocks, then (128-byte aligned) its windows
 static int fv_host(pbd_handle* h, const pbd_candidate_head* heads, const int32_t* locs, int count, pbd_feature_block* blocks, void* windows, int ts) {

@@ -477,3 +477,11 @@ class PartsBasedDetector:
         scatters them into Model.weight_vector()'s order."""
         heads, _, locs = Candidate._pack(candidates)
         return self.handle.candidates_features(heads, locs)
+
+    def writeExamples(self, candidates: List[Candidate], cache: "capi.QpCache", label: int, id: int) -> int:
+        """detect(im, model, thresh, [], 0, id, label)'s qp_write of every detection (matlab/learning/train.m:102): `candidates` (of
+        the LAST frame, or a selection of them) are appended to `cache` (capi.QpCache on this detector's handle) as standardised
+        block-sparse examples, gathered on the GPU from the frame's resident feature planes.  Returns how many were written: a full
+        cache takes no more and is no error."""
+        heads, _, locs = Candidate._pack(candidates)
+        return cache.write(heads, locs, label, id)

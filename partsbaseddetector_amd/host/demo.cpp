@@ -1,5 +1,5 @@
 // demo.cpp — the reference's canonical caller (src/demo.cpp:55-118) against the MI355X path:
-//   pbd_demo model.bin image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE] [--matlab-pyramid]
+//   pbd_demo model.bin image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE] [--examples FILE] [--matlab-pyramid]
 //            [--gtbox x1,y1,x2,y2[,overlap]]...
 //   pbd_demo model.bin image.raw width height channels perturb-features <responses-out.bin>
 //   pbd_demo model.bin image.raw width height channels oracle-responses <responses-in.bin>
@@ -17,6 +17,7 @@ using namespace pbd;
 // --gtbox x1,y1,x2,y2[,overlap] (anywhere, repeatable): testmodel_gtbox.m's protocol — per box the highest-scoring pose whose part centres'
 // box covers more than `overlap` of it (default 0.3; the last one given holds for every box), printed instead of the candidate list
 static std::vector<GtBox> g_gtbox;
+static const char* g_examples_file = nullptr;   // --examples FILE (anywhere): the detections as QP examples, written to FILE
 static double g_gt_overlap = 0.3;
 static void print_pose(const Candidate& c) {
   printf("%.9g %d %d", c.score(), c.component(), c.level);
@@ -154,6 +155,27 @@ static void run(Model& model, const Mat& im, bool stagewise, int special = 0, co
     fclose(f);
     printf("Features: %ld x %ld\n", (long)candidates.size(), (long)dim);
   }
+  if (g_examples_file) {   // --examples FILE: the sorted records as the QP's negative examples (label -1, id 0, Cneg 1): header n, k, len
+                           // (int64), then the n columns (k float32 each, qp.x verbatim), ids (5 int32 each), b (float32), d (float64)
+    auto cache = pbd.exampleCache(std::max<int>(1, (int)candidates.size()), 1.0, 1.0);
+    const int n = pbd.writeExamples(candidates, *cache, -1, 0);
+    int len = 0, k = 0;
+    cache->dims(&len, &k, nullptr, nullptr);
+    std::vector<float> x((size_t)n * k), b((size_t)n);
+    std::vector<int32_t> ids((size_t)n * 5);
+    std::vector<double> d((size_t)n);
+    cache->get(0, n, x.data(), ids.data(), b.data(), d.data());
+    FILE* f = fopen(g_examples_file, "wb");
+    if (!f) { fprintf(stderr, "cannot open %s\n", g_examples_file); exit(6); }
+    const long long hdr[3] = {n, k, len};
+    fwrite(hdr, sizeof(long long), 3, f);
+    fwrite(x.data(), sizeof(float), x.size(), f);
+    fwrite(ids.data(), sizeof(int32_t), ids.size(), f);
+    fwrite(b.data(), sizeof(float), b.size(), f);
+    fwrite(d.data(), sizeof(double), d.size(), f);
+    fclose(f);
+    printf("Examples: %d x %d\n", n, k);
+  }
   for (const Candidate& c : candidates) {
     printf("%.9g %d %d", c.score(), c.component(), c.level);
     for (const Rect& r : c.parts()) printf(" %d,%d,%d,%d", r.x, r.y, r.width, r.height);
@@ -211,6 +233,12 @@ int main(int argc, char** argv) {
       for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
       argc -= 2; --i;
     } else
+    if (std::string(argv[i]) == "--examples") {
+      if (i + 1 >= argc || !*argv[i + 1]) { printf("--examples FILE\n"); exit(-1); }
+      g_examples_file = argv[i + 1];
+      for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+      argc -= 2; --i;
+    } else
     if (std::string(argv[i]) == "--features") {
       if (i + 1 >= argc || !*argv[i + 1]) { printf("--features FILE\n"); exit(-1); }
       features_file = argv[i + 1];
@@ -228,7 +256,7 @@ int main(int argc, char** argv) {
       --argc; --i;
     }
   if (argc < 6 || argc > 8) {
-    printf("Usage: pbd_demo model_file image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE] [--nms-parts OVERLAP] [--matlab-pyramid] [--gtbox x1,y1,x2,y2[,overlap]]...\n");
+    printf("Usage: pbd_demo model_file image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE] [--examples FILE] [--nms-parts OVERLAP] [--matlab-pyramid] [--gtbox x1,y1,x2,y2[,overlap]]...\n");
     exit(-1);
   }
   // determine the type of model to read (src/demo.cpp:63-82)
@@ -255,6 +283,7 @@ int main(int argc, char** argv) {
   try {
     if (part_scores && stagewise) { printf("--part-scores: the fused detect() only\n"); exit(-1); }
     if (features_file && special) { printf("--features: not with %s\n", mode.c_str()); exit(-1); }
+    if (g_examples_file && (special || !g_gtbox.empty())) { printf("--examples: not with %s\n", special ? mode.c_str() : "--gtbox"); exit(-1); }
     if (!g_gtbox.empty() && (part_scores || nms_parts || features_file)) { printf("--gtbox: not with --part-scores, --nms-parts or --features\n"); exit(-1); }
     if (mode.find("double") != std::string::npos) run<double>(model, im, stagewise, 0, nullptr, part_scores, pad, features_file, nms_parts, matlab_pyramid);
     else run<float>(model, im, stagewise, special, special ? argv[7] : nullptr, part_scores, pad, features_file, nms_parts, matlab_pyramid);

@@ -829,6 +829,69 @@ class PartsBasedDetector {
     windows.assign(n * mp * wmax, (T)0);
     dev_->check(features_entry(heads.data(), locs.data(), (int)n, blocks.data(), windows.data()));
   }
+  // The QP's cache of block-sparse training examples on the device (include/pbd_c.h "training example cache"): qp_write.m's columns,
+  // matlab/mex/score.cc and lincomb.cc.  Holds the detector's device alive; the coordinate-descent pass is not part of it (a host
+  // solver reads the columns with get()).
+  class ExampleCache {
+    std::shared_ptr<Device> dev_;
+    pbd_qp* q_ = nullptr;
+    friend class PartsBasedDetector;
+   public:
+    ExampleCache(std::shared_ptr<Device> dev, int capacity, double cpos, double cneg, const double* wreg = nullptr, const double* w0 = nullptr)
+        : dev_(std::move(dev)) { dev_->check(pbd_qp_create(dev_->h, capacity, cpos, cneg, wreg, w0, &q_)); }
+    ~ExampleCache() { pbd_qp_destroy(q_); }
+    ExampleCache(const ExampleCache&) = delete;
+    ExampleCache& operator=(const ExampleCache&) = delete;
+    void dims(int* len, int* k, int* capacity, int* n) const { dev_->check(pbd_qp_dims(q_, len, k, capacity, n)); }
+    int size() const { int n = 0; dims(nullptr, nullptr, nullptr, &n); return n; }
+    int capacity() const { int c = 0; dims(nullptr, nullptr, &c, nullptr); return c; }
+    // score.cc: w (len values) on the examples `inds`; without inds: on all size() examples
+    void score(const std::vector<double>& w, const std::vector<int32_t>& inds, std::vector<double>& out) { score_(w, inds.data(), (int)inds.size(), out); }
+    void score(const std::vector<double>& w, std::vector<double>& out) { score_(w, nullptr, size(), out); }
+    // lincomb.cc: a[i] multiplies example i (shorter than the capacity: the rest counts as zero; longer: refused), summed in the
+    // order of `inds`; without inds: all size() examples in order
+    void lincomb(const std::vector<double>& a, const std::vector<int32_t>& inds, std::vector<double>& w) { lincomb_(a, inds.data(), (int)inds.size(), w); }
+    void lincomb(const std::vector<double>& a, std::vector<double>& w) { lincomb_(a, nullptr, size(), w); }
+    void keep(const std::vector<int32_t>& inds) { dev_->check(pbd_qp_keep(q_, inds.data(), (int)inds.size())); }
+    void get(int i0, int n, float* x, int32_t* ids, float* b, double* d) { dev_->check(pbd_qp_get(q_, i0, n, x, ids, b, d)); }
+    void put(int n, const float* x, const int32_t* ids, const float* b, const double* d) { dev_->check(pbd_qp_put(q_, n, x, ids, b, d)); }
+   private:
+    void score_(const std::vector<double>& w, const int32_t* inds, int n, std::vector<double>& out) {
+      int len = 0; dims(&len, nullptr, nullptr, nullptr);
+      if (w.size() != (size_t)len) throw Exception(PBD_ERR_ARG, "ExampleCache::score: w must have len elements");
+      out.assign((size_t)n, 0.0);
+      dev_->check(pbd_qp_score(q_, w.data(), inds, n, out.data()));
+    }
+    void lincomb_(const std::vector<double>& a, const int32_t* inds, int n, std::vector<double>& w) {
+      int len = 0, cap = 0; dims(&len, nullptr, &cap, nullptr);
+      if (a.size() > (size_t)cap) throw Exception(PBD_ERR_ARG, "ExampleCache::lincomb: a has more elements than the cache's capacity");
+      std::vector<double> av((size_t)cap, 0.0);   // pbd_qp_lincomb reads capacity doubles
+      std::copy(a.begin(), a.end(), av.begin());
+      w.assign((size_t)len, 0.0);
+      dev_->check(pbd_qp_lincomb(q_, av.data(), inds, n, w.data()));
+    }
+  };
+  std::unique_ptr<ExampleCache> exampleCache(int capacity, double cpos, double cneg, const double* wreg = nullptr, const double* w0 = nullptr) {
+    if (!dev_) throw Exception(PBD_ERR_STATE, "exampleCache() before distributeModel()");
+    return std::unique_ptr<ExampleCache>(new ExampleCache(dev_, capacity, cpos, cneg, wreg, w0));
+  }
+  // detect(im, model, thresh, [], 0, id, label)'s qp_write of every detection (matlab/learning/train.m:102): `candidates` (of the LAST
+  // frame, or a selection) appended to `cache` as standardised examples, on the GPU.  Returns how many were written (a full cache
+  // takes no more and is no error).
+  int writeExamples(const vectorCandidate& candidates, ExampleCache& cache, int label, int id) {
+    if (!dev_) throw Exception(PBD_ERR_STATE, "writeExamples() before distributeModel()");
+    const size_t n = candidates.size(), mp = (size_t)pbd_max_parts(dev_->h);
+    std::vector<pbd_candidate_head> heads(n);
+    std::vector<int32_t> locs(n * mp * 3, 0);
+    for (size_t i = 0; i < n; ++i) {
+      const Candidate& c = candidates[i];
+      heads[i].score = c.score(); heads[i].component = c.component(); heads[i].level = c.level; heads[i].nparts = (int32_t)c.parts().size();
+      std::copy(c.locs.begin(), c.locs.begin() + std::min(c.locs.size(), mp * 3), locs.begin() + i * mp * 3);
+    }
+    int written = 0;
+    dev_->check(pbd_qp_write(cache.q_, heads.data(), locs.data(), (int)n, label, id, &written));
+    return written;
+  }
  private:
   int features_entry(const pbd_candidate_head* hd, const int32_t* lc, int n, FeatureBlock* b, float* w) { return pbd_candidates_features(dev_->h, hd, lc, n, b, w); }
   int features_entry(const pbd_candidate_head* hd, const int32_t* lc, int n, FeatureBlock* b, double* w) { return pbd_candidates_features_f64(dev_->h, hd, lc, n, b, w); }

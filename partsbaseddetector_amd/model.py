@@ -205,6 +205,21 @@ class Model:
         return np.concatenate([np.asarray(self.biasw, np.float32).ravel(), np.asarray(self.defw, np.float32).ravel()] +
                               [np.asarray(f, np.float32).ravel() for f in self.filtersw]).astype(np.float64)
 
+    def qp_vectors(self):
+        """matlab/learning/model2vec.m in feature_layout()'s order: (w, wreg, w0, noneg) — the weights (float64), the regulariser
+        (.01 at the root bias of every component, 1 elsewhere), the weights' origin (.01 at elements 0 and 2 of every deformation, the
+        minimum quadratic deformation cost, 0 elsewhere) and the 0-based indices that must stay non-negative (those same elements,
+        uint32, deformation by deformation)."""
+        lay = self.feature_layout()
+        w = self.weight_vector()
+        wreg, w0 = np.ones(lay["size"], np.float64), np.zeros(lay["size"], np.float64)
+        nd = int(np.asarray(self.defw).size) // 4
+        noneg = (lay["deform"] + 4 * np.repeat(np.arange(nd), 2) + np.tile([0, 2], nd)).astype(np.uint32)
+        w0[noneg] = .01
+        for c in range(self.ncomponents):
+            wreg[lay["bias"] + int(self.biasid[c][0][0])] = .01
+        return w, wreg, w0, noneg
+
     def to_desc(self) -> pbd_model_desc:
         """Flatten into the C ABI descriptor (arrays kept alive on self).  Uniform banks only (pbd_create)."""
         kh = self.filtersw[0].shape[0]
