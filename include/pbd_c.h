@@ -172,7 +172,8 @@ int pbd_abi_version(void);
  * points pbd_candidates_nms_parts, pbd_set_candidate_nms, pbd_group_set_candidate_nms and pbd_candidates_filter_parts; and the
  * best-pose-per-ground-truth-box entry points pbd_candidates_best_overlap, pbd_candidates_select_gt, pbd_detect_gtbox_u8,
  * pbd_detect_gtbox_dev_u8 and pbd_detect_batch_gtbox_u8 (with PBD_GT_MAX); and the training example cache pbd_qp with its entry
- * points pbd_qp_create, _destroy, _dims, _footprint, _write, _score[_dev], _lincomb[_dev], _keep, _get and _put.                    */
+ * points pbd_qp_create, _destroy, _dims, _footprint, _write, _score[_dev], _lincomb[_dev], _keep, _get and _put; and the QP solver
+ * over that cache: pbd_qp_noneg, _fix, _state_put, _state_get, _pass, _one, _refresh, _loss, _opt, _prune and _weights.            */
 
 /* ---- output record: include/Candidate.hpp:56-111 --------------------------
  * One candidate = head + max_parts boxes (x, y, width, height as cv::Rect)
@@ -958,9 +959,9 @@ int pbd_candidates_features_dev(pbd_handle* h, const pbd_candidate_head* heads, 
  * detect(im, model, thresh, bbox, overlap, id, label) of matlab/detection/detect.m hands every back-tracked pose to qp_write(ex)
  * (matlab/learning/train.m:102), which appends it to the QP's cache of block-sparse examples; matlab/mex/score.cc and lincomb.cc sweep
  * that cache.  pbd_qp is that cache, resident on the device: detections are written into it from the feature planes without leaving
- * HBM, it is scored against a weight vector and combined linearly into one.  The coordinate-descent pass itself
- * (matlab/mex/qp_one_sparse.cc, qp_opt.m, the loss) is OUT OF SCOPE: it is a serial chain through w and stays with a host solver,
- * which reads the cache with pbd_qp_get and loads columns with pbd_qp_put.
+ * HBM, it is scored against a weight vector and combined linearly into one.  The coordinate-descent solver over it
+ * (matlab/mex/qp_one_sparse.cc, qp_one.m, qp_refresh.m, qp_opt.m with its loss, qp_prune.m, qp_w.m) is the "QP solver" section
+ * below: the columns never leave the device.  pbd_qp_get and pbd_qp_put remain for columns made or inspected elsewhere.
  *
  * Dense index space: Model.feature_layout() of the binding — [biasw | defw (ndefs x 4) | the filters back to back in the caller's
  *   order, each [kh][kw * flen]] —, length len.  len >= 2^24 is refused (PBD_ERR_UNSUPPORTED): block bounds are stored as floats,
@@ -1024,6 +1025,69 @@ int pbd_qp_lincomb_dev(pbd_qp* qp, const double* d_a, const int32_t* d_inds, int
 int pbd_qp_keep(pbd_qp* qp, const int32_t* inds, int n);
 int pbd_qp_get(pbd_qp* qp, int i0, int n, float* x, int32_t* ids, float* b, double* d);
 int pbd_qp_put(pbd_qp* qp, int n, const float* x, const int32_t* ids, const float* b, const double* d);
+
+/* ---- QP solver: qp_one_sparse.cc, qp_one.m, qp_refresh.m, qp_opt.m, qp_prune.m and qp_w.m on the cache (ABI 5, additive) ----------
+ * detect -> pbd_qp_write -> pbd_qp_opt -> pbd_qp_weights is a closed loop on the device: what crosses PCIe in a solver call is per
+ * example (a, sv, ids, b, a score), never a column, and the next model's weights come back once.  The calls are synchronous and
+ * finish on the handle's stream.
+ *
+ * State (device resident, allocated by the first call of this section — pbd_qp_footprint of a cache that never solves is unchanged):
+ *   a[capacity] double and sv[capacity] bytes, indexed by EXAMPLE; w[len] double; the scalars l, lb, lb_old, ub; noneg (p dense
+ *   indices); nfix (svfix = examples 0 .. nfix - 1).  It starts at a = 0, sv = 1 for the examples held and 0 behind them, w = 0,
+ *   scalars 0, no noneg, nfix = 0.  From then on examples appended by pbd_qp_write / pbd_qp_put get a = 0, sv = 1 (qp_write.m:74).
+ *   pbd_qp_keep renumbers examples and does NOT move a and sv (its caller does, as before); pbd_qp_prune moves them.
+ * pbd_qp_noneg: the dense indices whose weights are clamped at zero (Model.qp_vectors()[3] of the binding); an index outside
+ *   [0, len) is PBD_ERR_ARG.  pbd_qp_fix: nfix in [0, n], else PBD_ERR_ARG.
+ * pbd_qp_state_put: a and sv of examples 0 .. n - 1 (n <= capacity; either may be NULL).  pbd_qp_state_get: a[capacity],
+ *   sv[capacity], w[len], stats[4] = l, lb, lb_old, ub; any may be NULL.
+ * pbd_qp_pass: matlab/mex/qp_one_sparse.cc with C = 1 (qp_one.m:15) over the examples `order` — distinct, inside [0, n); a duplicate
+ *   or an index out of range is PBD_ERR_ARG, an empty cache PBD_ERR_STATE, a column of pbd_qp_put whose blocks overlap each other
+ *   PBD_ERR_UNSUPPORTED (the axpy has one writer per element), each with the state untouched.  *loss = the file's return value.
+ *   ONE workgroup runs the whole pass (one CU of the device, by construction: the pass is serial across examples, parallel within
+ *   one).  Everything scalar is the file's :171-253 line for line in double, nothing fused, MAX / MIN with the macros' operand order.
+ *   sumAlpha (:90-124) runs on the host before the launch: groups in memcmp order of the 20-byte id, ties in the order of `order`.
+ *   The sums use this library's order, the block sum stated above for d and b:
+ *     score(W, x): a block's products W[j] * (double)x go through the block sum; y starts at 0 and adds the blocks' sums in block order.
+ *     dot(x, x2): DEVIATION — the file's merge walk assumes ascending blocks, and this port's columns are in detect.m's order (bias,
+ *       window, bias, def, window ...), not ascending in the dense layout.  The library's dot is the complete one: for every block
+ *       of x in order, for every block of x2 in order, a non-empty intersection's products (double)x * (double)x2 go through the
+ *       block sum and are added to the result, which starts at 0, in that order.  On ascending columns where a block meets at most
+ *       one block of the other column this is the file's value in exact arithmetic.
+ *     add(W, x, dA): per element one rounded product dA * (double)x and one rounded sum; in the pair branch x, then x2 with -dA,
+ *       then the noneg clamp.
+ *     loss: err[0] + err[1] + ... left to right.
+ *   The result does not depend on the capacity, the columns the examples occupy or the launch.  DEVIATION from the reference in
+ *   bits, as for d and b: the file adds strictly left to right; exact comparisons (G > 1e-12, A[i] == 0, Ci >= C) may then fall
+ *   differently, so the trajectories are compared through the dual and primal bounds, not element by element.
+ * pbd_qp_refresh (qp_refresh.m): I = the examples with a > 0 over the capacity, sorted by a ascending, stable; none: example 0.
+ *   l = sum (double)b * a, each product rounded, added left to right in that order; w = pbd_qp_lincomb over I; the noneg clamp;
+ *   lb_old = lb; lb = l - w'w * .5.  w'w, which MATLAB leaves to the BLAS, is the block sum over the whole of w.
+ * pbd_qp_one (qp_one.m:15-139): the pass, the refresh, sv(svfix) = 1, lb_old = lb (after the refresh moved it, as the file does),
+ *   lb = l - w'w * .5, ub = w'w * .5 + loss.
+ * pbd_qp_loss (computeloss, qp_opt.m:56-86) over examples 0 .. n - 1: scores by pbd_qp_score; per id the largest slack if positive;
+ *   ids in ascending numeric lexicographic order of their five words (sortrows), the ids' terms added left to right.  DEVIATION:
+ *   MATLAB computes qp.b(I) - score(...) in single (single - double is single); the library computes (double)b - score in double.
+ * pbd_qp_opt (qp_opt.m): the refresh, the true upper bound, sv(0 .. n - 1) = 1, then up to max_iter times pbd_qp_one over a shuffle
+ *   of find(sv), the test lb > 0 && 1 - lb / min(qp.ub, ub) < tol, the true-ub check and the sv reset; finally qp.ub = ub.  *passes
+ *   = the number of pbd_qp_one calls.  randperm is replaced by a stated generator: find(sv) ascending in v[0 .. m - 1], then
+ *   for t = m - 1 .. 1: j = next() mod (t + 1), swap v[t], v[j]; next() is splitmix64 (state += 0x9E3779B97F4A7C15; z = state;
+ *   z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; return z ^ z >> 31) with state = seed at the
+ *   start of the call: one stream through the whole call.
+ * pbd_qp_prune (qp_prune.m): if sv is set over the whole capacity, sv = a > 0 and sv(svfix) = 1; I = find(sv) among the n examples
+ *   (none: PBD_ERR_STATE, nothing changed); pbd_qp_keep(I); a and sv move with their examples, sv = 1 on them, both 0 behind;
+ *   l and w rebuilt in index order (pbd_qp_lincomb with inds NULL), the clamp, lb = l - w'w * .5; lb_old is left alone.  *n = |I|.
+ * pbd_qp_weights (qp_w.m): w_out[len] = w ./ wreg + w0.                                                                            */
+int pbd_qp_noneg(pbd_qp* qp, const int32_t* idx, int p);
+int pbd_qp_fix(pbd_qp* qp, int nfix);
+int pbd_qp_state_put(pbd_qp* qp, const double* a, const unsigned char* sv, int n);
+int pbd_qp_state_get(pbd_qp* qp, double* a, unsigned char* sv, double* w, double* stats);
+int pbd_qp_pass(pbd_qp* qp, const int32_t* order, int n, double* loss);
+int pbd_qp_one(pbd_qp* qp, const int32_t* order, int n);
+int pbd_qp_refresh(pbd_qp* qp);
+int pbd_qp_loss(pbd_qp* qp, double* loss);
+int pbd_qp_opt(pbd_qp* qp, double tol, int max_iter, uint64_t seed, double* lb, double* ub, int* passes);
+int pbd_qp_prune(pbd_qp* qp, int* n);
+int pbd_qp_weights(pbd_qp* qp, double* w_out);
 
 /* ---- instrumentation --------------------------------------------------------
  * GPU time (ms, hipEvent) of the stages of the last synchronous detect:

@@ -66,6 +66,8 @@ EXPORTS = [
     "pbd_detect_batch_gtbox_u8",
     "pbd_qp_create", "pbd_qp_destroy", "pbd_qp_dims", "pbd_qp_footprint", "pbd_qp_write", "pbd_qp_score", "pbd_qp_score_dev",
     "pbd_qp_lincomb", "pbd_qp_lincomb_dev", "pbd_qp_keep", "pbd_qp_get", "pbd_qp_put",
+    "pbd_qp_noneg", "pbd_qp_fix", "pbd_qp_state_put", "pbd_qp_state_get", "pbd_qp_pass", "pbd_qp_one", "pbd_qp_refresh",
+    "pbd_qp_loss", "pbd_qp_opt", "pbd_qp_prune", "pbd_qp_weights",
 ]
 PBD_ABI_VERSION = 5
 
@@ -160,6 +162,17 @@ def lib() -> C.CDLL:
         L.pbd_qp_keep.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.pbd_qp_get.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pbd_qp_put.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pbd_qp_noneg.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.pbd_qp_fix.argtypes = [C.c_void_p, C.c_int]
+        L.pbd_qp_state_put.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.pbd_qp_state_get.argtypes = [C.c_void_p] * 5
+        L.pbd_qp_pass.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.pbd_qp_one.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.pbd_qp_refresh.argtypes = [C.c_void_p]
+        L.pbd_qp_loss.argtypes = [C.c_void_p, C.c_void_p]
+        L.pbd_qp_opt.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pbd_qp_prune.argtypes = [C.c_void_p, C.c_void_p]
+        L.pbd_qp_weights.argtypes = [C.c_void_p, C.c_void_p]
         if L.pbd_abi_version() != PBD_ABI_VERSION:
             raise ImportError(f"{LIB_PATH}: ABI version {L.pbd_abi_version()}, this binding is for {PBD_ABI_VERSION}")
         _lib = L
@@ -1157,8 +1170,9 @@ def _vp(a):
 
 class QpCache:
     """pbd_qp (include/pbd_c.h "training example cache"): the QP's cache of block-sparse examples on the device — qp_write.m,
-    matlab/mex/score.cc and lincomb.cc.  Bound to `handle`, whose close() closes the caches it still has.  The coordinate-descent pass is not here: a
-    host solver reads the cache with get() and loads columns with put()."""
+    matlab/mex/score.cc and lincomb.cc — and the coordinate-descent solver over it (qp_one_sparse.cc, qp_one.m, qp_refresh.m, qp_opt.m,
+    qp_prune.m, qp_w.m: noneg() .. weights() below), whose columns never leave the device.  Bound to `handle`, whose close() closes
+    the caches it still has."""
 
     def __init__(self, handle: Handle, capacity: int, cpos: float = 1.0, cneg: float = 1.0, wreg=None, w0=None):
         self.handle, self.L = handle, handle.L
@@ -1254,6 +1268,71 @@ class QpCache:
         b = np.zeros(n, np.float32) if b is None else np.ascontiguousarray(b, np.float32).reshape(n)
         d = np.zeros(n, np.float64) if d is None else np.ascontiguousarray(d, np.float64).reshape(n)
         self.handle._chk(self.L.pbd_qp_put(self.q, n, _vp(x), _vp(ids), _vp(b), _vp(d)))
+
+    # ---- the QP solver (include/pbd_c.h "QP solver") ----
+    def noneg(self, idx) -> None:
+        """pbd_qp_noneg: the dense indices clamped at zero (Model.qp_vectors()[3])"""
+        idx = np.ascontiguousarray(idx, np.int32).ravel()
+        self.handle._chk(self.L.pbd_qp_noneg(self.q, _vp(idx), len(idx)))
+
+    def fix(self, nfix: int) -> None:
+        """pbd_qp_fix: svfix = examples 0 .. nfix - 1"""
+        self.handle._chk(self.L.pbd_qp_fix(self.q, int(nfix)))
+
+    def state(self):
+        """pbd_qp_state_get: (a [capacity] float64, sv [capacity] uint8, w [len] float64, stats [4] = l, lb, lb_old, ub)"""
+        length, _, cap, _ = self.dims()
+        a, sv, w, st = np.zeros(cap), np.zeros(cap, np.uint8), np.zeros(length), np.zeros(4)
+        self.handle._chk(self.L.pbd_qp_state_get(self.q, _vp(a), _vp(sv), _vp(w), _vp(st)))
+        return a, sv, w, st
+
+    def set_state(self, a=None, sv=None) -> None:
+        """pbd_qp_state_put: a and / or sv of examples 0 .. len - 1"""
+        a = None if a is None else np.ascontiguousarray(a, np.float64).ravel()
+        sv = None if sv is None else np.ascontiguousarray(sv, np.uint8).ravel()
+        if a is not None and sv is not None and len(a) != len(sv):
+            raise ValueError("a and sv must have the same length")
+        n = len(a) if a is not None else (len(sv) if sv is not None else 0)
+        self.handle._chk(self.L.pbd_qp_state_put(self.q, _vp(a), _vp(sv), n))
+
+    def solve_pass(self, order) -> float:
+        """pbd_qp_pass: one qp_one_sparse.cc pass over the examples `order`; returns its loss"""
+        order = self._inds(order)
+        loss = C.c_double()
+        self.handle._chk(self.L.pbd_qp_pass(self.q, _vp(order), len(order), C.byref(loss)))
+        return loss.value
+
+    def one(self, order) -> None:
+        """pbd_qp_one: qp_one.m from its pass on — pass, refresh, sv(svfix) = 1, lb_old / lb / ub"""
+        order = self._inds(order)
+        self.handle._chk(self.L.pbd_qp_one(self.q, _vp(order), len(order)))
+
+    def refresh(self) -> None:
+        self.handle._chk(self.L.pbd_qp_refresh(self.q))
+
+    def loss(self) -> float:
+        """pbd_qp_loss: computeloss of qp_opt.m over all n examples"""
+        v = C.c_double()
+        self.handle._chk(self.L.pbd_qp_loss(self.q, C.byref(v)))
+        return v.value
+
+    def opt(self, tol: float = .05, max_iter: int = 1000, seed: int = 0):
+        """pbd_qp_opt: qp_opt.m's loop -> (lb, ub, passes)"""
+        lb, ub, passes = C.c_double(), C.c_double(), C.c_int()
+        self.handle._chk(self.L.pbd_qp_opt(self.q, float(tol), int(max_iter), int(seed), C.byref(lb), C.byref(ub), C.byref(passes)))
+        return lb.value, ub.value, passes.value
+
+    def prune(self) -> int:
+        """pbd_qp_prune: qp_prune.m -> the examples kept"""
+        n = C.c_int()
+        self.handle._chk(self.L.pbd_qp_prune(self.q, C.byref(n)))
+        return n.value
+
+    def weights(self) -> np.ndarray:
+        """pbd_qp_weights: qp_w.m's w ./ wreg + w0"""
+        out = np.zeros(self.dims()[0])
+        self.handle._chk(self.L.pbd_qp_weights(self.q, _vp(out)))
+        return out
 
     def close(self):
         if getattr(self, "q", None):   # (a live cache implies a live handle: Handle.close() closes its caches before itself)

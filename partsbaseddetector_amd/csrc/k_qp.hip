@@ -13,18 +13,12 @@
 // Products and sums are explicit __dmul_rn / __dadd_rn: nothing is fused.
 #include "pbd_internal.hpp"
 #include "featvec_gather.hpp"
+#include "qp_fold.hpp"
 
 #define QW_NT 256
 #define QW_WAVES (QW_NT / 64)
 #define QS_CH 64          // column elements a score wavefront stages per round
 #define QL_NT 256
-
-// the header's block sum: lane t holds partial t; folded s[t] += s[t + h], h = 32 .. 1; lane 0 has the sum
-__device__ __forceinline__ double qp_fold(double v) {
-#pragma unroll
-  for (int h = 32; h >= 1; h >>= 1) v = __dadd_rn(v, __shfl_down(v, h, 64));
-  return v;
-}
 
 // one block of the column by one wavefront: header, values, table entry and its two sums.  val(e): element e's value, double, unsigned
 template <typename F>

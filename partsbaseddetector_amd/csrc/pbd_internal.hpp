@@ -684,6 +684,18 @@ struct QpWriteArgs {
 void launch_qp_write(const QpWriteArgs& a, int ts, hipStream_t s);
 void launch_qp_score(const QpDev& q, const double* w, const int* inds, int n, double* out, hipStream_t s);
 void launch_qp_lincomb(const QpDev& q, const double* a, const int* inds, int n, double* w_out, hipStream_t s);
+// the QP solver's device state (k_qp_solve.hip, pbd_qp_solve.cpp; include/pbd_c.h "QP solver")
+enum { QP_STAT_L = 0, QP_STAT_WW = 1, QP_STAT_LOSS = 2, QP_STAT_N = 4 };
+struct QpSolveDev {
+  double* a; unsigned char* sv;   // [capacity] by example
+  double* w;                      // [len]
+  double* stat;                   // [QP_STAT_N]: l, w'w of the last refresh, the last pass's loss
+  double* idC; int* idP; int* idI; double* err; int* order;   // [capacity] the pass's scratch (sumAlpha's tables, by position in order)
+  double* scores;                 // [capacity] pbd_qp_loss's scores
+};
+void launch_qp_pass(const QpDev& q, const QpSolveDev& s, const int* noneg, int p, int n, hipStream_t st);
+void launch_qp_clamp_norm(const QpSolveDev& s, const int* noneg, int p, int len, hipStream_t st);
+void launch_qp_weights(const double* w, const double* wreg, const double* w0, int len, double* out, hipStream_t st);
 void launch_gtbox(const GtBoxArgs& a, int gmax, hipStream_t s);   // k_gtbox.hip: gmax = the largest ngt
 // object clusters (k_cluster3d.hip)
 size_t cluster3d_slot_bytes(int pcap);

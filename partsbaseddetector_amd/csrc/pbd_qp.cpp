@@ -3,46 +3,15 @@
 // handed in, and the pbd_qp_* entry points.  The cache borrows its handle's model, stream and device; errors go through the handle.
 #include <algorithm>
 #include <cmath>
-#include "pbd_internal.hpp"
-
-struct pbd_qp {
-  pbd_handle* h = nullptr;
-  QpDev dev{};
-  int n = 0;
-  double cpos = 0, cneg = 0;
-  double* d_wreg = nullptr; double* d_w0 = nullptr; int* d_foff = nullptr;
-  std::vector<int> slot;            // host copy of dev.slot
-  std::vector<int> foff;            // [nfilters] dense start of each filter, the caller's order
-  std::vector<void*> bufs;
-  size_t bytes = 0;
-};
+#include <utility>
+#include "pbd_qp.hpp"
 
 namespace {
-template <typename T> int qalloc(pbd_qp* q, T** p, size_t n) {
-  void* v = nullptr;
-  hipError_t e = hipMalloc(&v, sizeof(T) * std::max<size_t>(n, 1));
-  if (e != hipSuccess) return fail(q->h, PBD_ERR_HIP, std::string("example cache: hipMalloc: ") + hipGetErrorString(e));
-  q->bufs.push_back(v); q->bytes += sizeof(T) * std::max<size_t>(n, 1);
-  *p = (T*)v;
-  return PBD_OK;
-}
-// a scratch buffer of one call: freed when it goes out of scope
-struct Tmp {
-  void* p = nullptr;
-  ~Tmp() { if (p) hipFree(p); }
-  int get(pbd_handle* h, size_t bytes) {
-    hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 1));
-    return e == hipSuccess ? PBD_OK : fail(h, PBD_ERR_HIP, std::string("example cache: hipMalloc: ") + hipGetErrorString(e));
-  }
-};
+using namespace pbd_qp_detail;
 // size of the caller's filter n
 void filter_size(const pbd_handle* h, int n, int* kh, int* kw) {
   const int f = h->mixed && !h->fperm.empty() ? h->fperm[n] : n;
   *kh = h->mixed ? h->fkh[f] : h->md.kh; *kw = h->mixed ? h->fkw[f] : h->md.kw;
-}
-int finish(pbd_handle* h, const char* what) {
-  hipError_t e = hipStreamSynchronize(h->stream);
-  return e == hipSuccess ? PBD_OK : fail(h, PBD_ERR_HIP, std::string(what) + hipGetErrorString(e));
 }
 int check_inds(pbd_qp* q, const int32_t* inds, int n) {
   if (n < 0) return fail(q->h, PBD_ERR_ARG, "example cache: n < 0");
@@ -70,6 +39,14 @@ int check_column(const pbd_qp* q, const float* x, std::vector<int>& tab) {
     xp += 2 + ln;
   }
   return nb;
+}
+// do two blocks of one column share a dense element?  (the solver's pass adds a column into w with one writer per element)
+char blocks_overlap(const std::vector<int>& tab) {
+  std::vector<std::pair<int, int>> se;
+  for (size_t b = 0; b + 2 < tab.size(); b += 3) se.emplace_back(tab[b], tab[b] + tab[b + 1]);
+  std::sort(se.begin(), se.end());
+  for (size_t b = 1; b < se.size(); ++b) if (se[b].first < se[b - 1].second) return 1;
+  return 0;
 }
 }  // namespace
 
@@ -132,6 +109,7 @@ int pbd_qp_create(pbd_handle* h, int capacity, double cpos, double cneg, const d
   if (w0) std::copy(w0, w0 + len, v0.begin());
   else for (int dd = 0; dd < ndefs; ++dd) v0[(size_t)nbias + 4 * dd] = v0[(size_t)nbias + 4 * dd + 2] = .01;
   q->slot.resize(cap);
+  q->overlap.assign(cap, 0);
   for (size_t i = 0; i < cap; ++i) q->slot[i] = (int)i;
   hipError_t e = hipSuccess;
   auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
@@ -219,6 +197,9 @@ int pbd_qp_write(pbd_qp* q, const pbd_candidate_head* heads, const int32_t* locs
     a.C = label > 0 ? q->cpos : q->cneg; a.label = label; a.id = id;
     launch_qp_write(a, h->ts, h->stream);
     LAUNCHCHK(h, "example cache write");
+    for (int i = 0; i < n; ++i) q->overlap[q->slot[q->n + i]] = 0;   // (a record's blocks never overlap: the check above)
+    q->meta_dirty = true;
+    if ((rc = pbd_i_qp_appended(q, q->n, n))) return rc;
     q->n += n;
   }
   *written = n;
@@ -347,9 +328,13 @@ int pbd_qp_put(pbd_qp* q, int n, const float* x, const int32_t* ids, const float
     if (nbv[i]) HIPCHK(h, hipMemcpyAsync(q->dev.tab + c * nbm * 3, tabs[i].data(), sizeof(int) * 3 * nbv[i], hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(q->dev.nblk + c, &nbv[i], sizeof(int), hipMemcpyHostToDevice, h->stream));
   }
-  int rc = finish(h, "example cache put: ");   // (the tables are pageable: the copies are done when they go)
-  if (!rc) q->n += n;
-  return rc;
+  q->meta_dirty = true;
+  int rc = pbd_i_qp_appended(q, q->n, n);
+  if (!rc) rc = finish(h, "example cache put: ");   // (the tables are pageable: the copies are done when they go)
+  if (rc) return rc;
+  for (int i = 0; i < n; ++i) q->overlap[q->slot[q->n + i]] = blocks_overlap(tabs[i]);
+  q->n += n;
+  return PBD_OK;
 }
 
 }  // extern "C"

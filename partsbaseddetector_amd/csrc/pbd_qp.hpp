@@ -1,0 +1,60 @@
+// pbd_qp.hpp — the training example cache's host object, shared by pbd_qp.cpp (the cache) and pbd_qp_solve.cpp (the solver).
+#pragma once
+#include <algorithm>
+#include <string>
+#include <vector>
+#include "pbd_internal.hpp"
+
+// the solver's state (include/pbd_c.h "QP solver"): allocated by the first solver call, so a cache that never solves holds none of it
+struct QpSolveState {
+  bool have = false;
+  QpSolveDev dev{};                 // a, sv, w, stat, the pass's scratch
+  int* d_noneg = nullptr; int p = 0;
+  int nfix = 0;
+  double l = 0, lb = 0, lb_old = 0, ub = 0, ww = 0;   // host mirror of dev.stat, current after every solver call
+};
+
+struct pbd_qp {
+  pbd_handle* h = nullptr;
+  QpDev dev{};
+  int n = 0;
+  double cpos = 0, cneg = 0;
+  double* d_wreg = nullptr; double* d_w0 = nullptr; int* d_foff = nullptr;
+  std::vector<int> slot;            // host copy of dev.slot
+  std::vector<int> foff;            // [nfilters] dense start of each filter, the caller's order
+  std::vector<void*> bufs;
+  size_t bytes = 0;
+  // solver side
+  QpSolveState sol;
+  std::vector<char> overlap;        // [capacity] by column: a column put with blocks that overlap each other (never one of pbd_qp_write's)
+  std::vector<int> m_ids;           // [capacity][5] host mirror of dev.ids, by column; current while !meta_dirty
+  std::vector<float> m_b;           // [capacity]    host mirror of dev.b
+  bool meta_dirty = true;
+};
+
+namespace pbd_qp_detail {
+template <typename T> int qalloc(pbd_qp* q, T** p, size_t n) {
+  void* v = nullptr;
+  hipError_t e = hipMalloc(&v, sizeof(T) * std::max<size_t>(n, 1));
+  if (e != hipSuccess) return fail(q->h, PBD_ERR_HIP, std::string("example cache: hipMalloc: ") + hipGetErrorString(e));
+  q->bufs.push_back(v); q->bytes += sizeof(T) * std::max<size_t>(n, 1);
+  *p = (T*)v;
+  return PBD_OK;
+}
+// a scratch buffer of one call: freed when it goes out of scope
+struct Tmp {
+  void* p = nullptr;
+  ~Tmp() { if (p) hipFree(p); }
+  int get(pbd_handle* h, size_t bytes) {
+    hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 1));
+    return e == hipSuccess ? PBD_OK : fail(h, PBD_ERR_HIP, std::string("example cache: hipMalloc: ") + hipGetErrorString(e));
+  }
+};
+inline int finish(pbd_handle* h, const char* what) {
+  hipError_t e = hipStreamSynchronize(h->stream);
+  return e == hipSuccess ? PBD_OK : fail(h, PBD_ERR_HIP, std::string(what) + hipGetErrorString(e));
+}
+}  // namespace pbd_qp_detail
+
+// pbd_qp_solve.cpp: examples n0 .. n0 + n - 1 were appended — with solver state they start at a = 0, sv = 1 (qp_write.m:74)
+int pbd_i_qp_appended(pbd_qp* q, int n0, int n);

@@ -855,6 +855,33 @@ class PartsBasedDetector {
     void keep(const std::vector<int32_t>& inds) { dev_->check(pbd_qp_keep(q_, inds.data(), (int)inds.size())); }
     void get(int i0, int n, float* x, int32_t* ids, float* b, double* d) { dev_->check(pbd_qp_get(q_, i0, n, x, ids, b, d)); }
     void put(int n, const float* x, const int32_t* ids, const float* b, const double* d) { dev_->check(pbd_qp_put(q_, n, x, ids, b, d)); }
+    // ---- the QP solver over the cache (include/pbd_c.h "QP solver"): the columns stay on the device ----
+    void noneg(const std::vector<int32_t>& idx) { dev_->check(pbd_qp_noneg(q_, idx.data(), (int)idx.size())); }
+    void fix(int nfix) { dev_->check(pbd_qp_fix(q_, nfix)); }
+    struct SolverStats { double l, lb, lb_old, ub; };
+    // a and sv by example over the capacity, w over len; any may be nullptr
+    SolverStats state(std::vector<double>* a, std::vector<unsigned char>* sv, std::vector<double>* w) {
+      int len = 0, cap = 0; dims(&len, nullptr, &cap, nullptr);
+      if (a) a->assign((size_t)cap, 0.0);
+      if (sv) sv->assign((size_t)cap, 0);
+      if (w) w->assign((size_t)len, 0.0);
+      double st[4];
+      dev_->check(pbd_qp_state_get(q_, a ? a->data() : nullptr, sv ? sv->data() : nullptr, w ? w->data() : nullptr, st));
+      return SolverStats{st[0], st[1], st[2], st[3]};
+    }
+    void set_state(const double* a, const unsigned char* sv, int n) { dev_->check(pbd_qp_state_put(q_, a, sv, n)); }
+    // qp_one_sparse.cc over the examples `order` (distinct); returns its loss
+    double solve_pass(const std::vector<int32_t>& order) { double loss = 0; dev_->check(pbd_qp_pass(q_, order.data(), (int)order.size(), &loss)); return loss; }
+    void one(const std::vector<int32_t>& order) { dev_->check(pbd_qp_one(q_, order.data(), (int)order.size())); }
+    void refresh() { dev_->check(pbd_qp_refresh(q_)); }
+    double loss() { double v = 0; dev_->check(pbd_qp_loss(q_, &v)); return v; }
+    // qp_opt.m: returns the number of passes; the shuffle is the header's stated generator, seeded with `seed`
+    int opt(double tol, int max_iter, uint64_t seed, double* lb = nullptr, double* ub = nullptr) {
+      int passes = 0; dev_->check(pbd_qp_opt(q_, tol, max_iter, seed, lb, ub, &passes)); return passes;
+    }
+    int prune() { int n = 0; dev_->check(pbd_qp_prune(q_, &n)); return n; }
+    // qp_w.m: the next model's weights, w ./ wreg + w0 (Model.feature_layout() maps them back)
+    void weights(std::vector<double>& w) { int len = 0; dims(&len, nullptr, nullptr, nullptr); w.assign((size_t)len, 0.0); dev_->check(pbd_qp_weights(q_, w.data())); }
    private:
     void score_(const std::vector<double>& w, const int32_t* inds, int n, std::vector<double>& out) {
       int len = 0; dims(&len, nullptr, nullptr, nullptr);
