@@ -173,7 +173,9 @@ int pbd_abi_version(void);
  * best-pose-per-ground-truth-box entry points pbd_candidates_best_overlap, pbd_candidates_select_gt, pbd_detect_gtbox_u8,
  * pbd_detect_gtbox_dev_u8 and pbd_detect_batch_gtbox_u8 (with PBD_GT_MAX); and the training example cache pbd_qp with its entry
  * points pbd_qp_create, _destroy, _dims, _footprint, _write, _score[_dev], _lincomb[_dev], _keep, _get and _put; and the QP solver
- * over that cache: pbd_qp_noneg, _fix, _state_put, _state_get, _pass, _one, _refresh, _loss, _opt, _prune and _weights.            */
+ * over that cache: pbd_qp_noneg, _fix, _state_put, _state_get, _pass, _one, _refresh, _loss, _opt, _prune and _weights; and the
+ * warped positives: pbd_warp_geometry, pbd_warp_taps, pbd_warp_windows_u8, pbd_warp_windows_u8_f64, pbd_qp_write_warped_u8 and
+ * pbd_debug_warp_ms (with PBD_WARP_SKIPPED / _WRITTEN / _FULL).                                                                    */
 
 /* ---- output record: include/Candidate.hpp:56-111 --------------------------
  * One candidate = head + max_parts boxes (x, y, width, height as cv::Rect)
@@ -1088,6 +1090,66 @@ int pbd_qp_loss(pbd_qp* qp, double* loss);
 int pbd_qp_opt(pbd_qp* qp, double tol, int max_iter, uint64_t seed, double* lb, double* ub, int* passes);
 int pbd_qp_prune(pbd_qp* qp, int* n);
 int pbd_qp_weights(pbd_qp* qp, double* w_out);
+
+/* ---- warped positives: warppos.m and train.m's poswarp into the example cache (ABI 5, additive) ------------------------------------
+ * The first branch a training run executes (trainmodel.m:35, train.m:131-161 with warp = 1): every positive box is cropped with a
+ * replicated border, resized to the filter's size plus one cell on every side, its HOG taken and written as a two-block example.
+ * Here the crop, the resize, the HOG and the write run on the device: no window, feature plane or column crosses PCIe.
+ *
+ * Inputs: one 8-bit frame, cn 1 or 3 (a grey frame is replicated to three planes, warppos.m:18-20); n boxes (x1, y1, x2, y2) as
+ *   doubles in the .m files' 1-BASED INCLUSIVE pixel coordinates — pixel (1, 1) is im[0, 0]; the rounding below is not
+ *   shift-invariant at halves, so the convention is part of the definition —; a filter index of the handle (the caller's order):
+ *   kh x kw = pbd_get_filter_size, sbin the model's.
+ * Crop (warppos.m:21-27, subarray.m:10-17 with pad = 1), in double, in this order: padx = sbin * (x2 - x1 + 1) / (kw * sbin), pady
+ *   alike with kh; X1 = round(x1 - padx), X2 = round(x2 + padx), Y1, Y2 alike, round() rounding halves away from zero.  Window pixel
+ *   (i, j) is image pixel (clamp(Y1 + i, 1, H), clamp(X1 + j, 1, W)), widened to double.  The crop is never materialised: it is an
+ *   index clamp inside the resize's reads.
+ * Resize to oh = (kh + 2) * sbin, ow = (kw + 2) * sbin.  MATLAB's imresize is a binary; the definition is the documented contributions
+ *   algorithm, stated here.  Per axis, from n_in to n_out: s = n_out / n_in; width = s < 1 ? 2 / s : 2; P = ceil(width) + 2; for output
+ *   x = 1 .. n_out: u = x / s + 0.5 * (1 - 1 / s), left = floor(u - width / 2), taps p = 0 .. P - 1 at ind = left + p with weight
+ *   s * max(0, 1 - |s * (u - ind)|) for s < 1 (the antialiased form), max(0, 1 - |u - ind|) otherwise, each divided by the sum of the P
+ *   weights added left to right; source index aux[(ind - 1) mod 2 n_in] with aux = [1 .. n_in, n_in .. 1] (MATLAB's mirror).  The
+ *   axis with the smaller s goes first, a tie goes to rows (y).  An output element is the sum over ALL P taps, zero weights included:
+ *   each product rounded, added to +0.0 in ascending p, never fused.  The result is double, with no clamp.
+ *   DEVIATION: MATLAB's own summation order is unknown; this order is the library's.  Octave's imresize is a different function and
+ *   is not followed.  The weights are computed once, in double, on the host (pbd_warp_taps) and uploaded: the device multiplies by
+ *   exactly the numbers pbd_warp_taps returns.
+ * HOG: features(window, sbin) -> kh x kw x 32, by the kernel every pyramid level goes through, over the windows as level images of
+ *   PBD_DEPTH_64F, in the handle's scalar T — bit for bit what pbd_pyramid_image + pbd_get_level_features give for that window.
+ * Column (train.m:152-161, qp_write.m): two blocks, the bias block [1] at dense index `bias`, then the window [kh][kw][flen] at the
+ *   filter's dense start; label 1, so C = cpos; ids (1, id, 0, 0, 0).  Standardisation, d, b and the block sums are exactly those of
+ *   pbd_qp_write (the same device text); the solver's state of new examples is a = 0, sv = 1.
+ *
+ * pbd_warp_geometry, pbd_warp_taps: the planner, pure host code, callable without a GPU.  _geometry: rect[4] = X1, Y1, X2, Y2
+ *   (1-based, unclamped), *rows_first = 1 where y is resampled first, *py / *px = P of the axes; outputs may be NULL.  PBD_ERR_ARG: a
+ *   non-finite or inverted box (x2 < x1 or y2 < y1), kh / kw / sbin < 1; PBD_ERR_UNSUPPORTED: a crop side beyond 16384 pixels or a
+ *   coordinate beyond 2^30 in magnitude.  _taps: one axis — *ntaps = P, and with index / weight non-NULL, [n_out][P] 0-based source
+ *   indices inside the crop (mirror resolved) and normalised weights; `capacity` elements each, PBD_ERR_CAPACITY below n_out * P;
+ *   n_in, n_out in [1, 16384].
+ * pbd_warp_windows_u8 / _u8_f64 (float / double handles, PBD_ERR_STATE on the other): the stand-alone staging entry —
+ *   windows[n][oh][ow][3] as doubles and features[n][kh][kw][32] in T of all n boxes (either may be NULL).  Synchronous.
+ * pbd_qp_write_warped_u8: poswarp.  Boxes with (x2 - x1 + 1) * (y2 - y1 + 1) < min_area are skipped (train.m:139-143; the caller
+ *   computes min_area = prod(maxsize * sbin), train.m:135); of the others the first min(count, capacity - n) are written — a full cache
+ *   is no error — in box order; *written = that number; status[i] (may be NULL) = PBD_WARP_WRITTEN, PBD_WARP_SKIPPED or
+ *   PBD_WARP_FULL.  ids[i] is box i's id (NULL: i).  Synchronous: the examples are in the cache when the call returns.
+ * Refusals, each with a message and nothing written: PBD_ERR_ARG — a non-finite or inverted box, filter or bias out of range, a bad
+ *   frame argument, NaN min_area; PBD_ERR_UNSUPPORTED — pbd_group members, a crop side beyond the limit above, a frame of 2^31 bytes
+ *   or more, a filter whose window does not fit the cache's column length; PBD_ERR_STATE — a frame pending.  A repeated dense start
+ *   (qp_write.m:34-35) cannot arise: the bias block starts below nbias, every filter's at or above it.                              */
+#define PBD_WARP_SKIPPED 0
+#define PBD_WARP_WRITTEN 1
+#define PBD_WARP_FULL 2
+int pbd_warp_geometry(const double* box, int kh, int kw, int sbin, int32_t* rect, int32_t* rows_first, int32_t* py, int32_t* px);
+int pbd_warp_taps(int n_in, int n_out, int32_t* index, double* weight, int capacity, int32_t* ntaps);
+int pbd_warp_windows_u8(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride, const double* boxes, int n, int filter,
+                        double* windows, float* features);
+int pbd_warp_windows_u8_f64(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride, const double* boxes, int n, int filter,
+                            double* windows, double* features);
+int pbd_qp_write_warped_u8(pbd_qp* qp, const uint8_t* im, int w, int hgt, int cn, int stride, const double* boxes, const int32_t* ids,
+                           int n, int filter, int bias, double min_area, int32_t* status, int* written);
+/* the last pbd_warp_windows_* / pbd_qp_write_warped_u8 call's launches, in ms between events on the handle's stream, while
+ * pbd_set_profiling is on (zeros otherwise): [0] the two resample passes, [1] the HOG, [2] the write (0 for pbd_warp_windows_*) */
+int pbd_debug_warp_ms(const pbd_handle* h, float ms[3]);
 
 /* ---- instrumentation --------------------------------------------------------
  * GPU time (ms, hipEvent) of the stages of the last synchronous detect:

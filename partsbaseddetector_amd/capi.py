@@ -68,7 +68,10 @@ EXPORTS = [
     "pbd_qp_lincomb", "pbd_qp_lincomb_dev", "pbd_qp_keep", "pbd_qp_get", "pbd_qp_put",
     "pbd_qp_noneg", "pbd_qp_fix", "pbd_qp_state_put", "pbd_qp_state_get", "pbd_qp_pass", "pbd_qp_one", "pbd_qp_refresh",
     "pbd_qp_loss", "pbd_qp_opt", "pbd_qp_prune", "pbd_qp_weights",
+    "pbd_warp_geometry", "pbd_warp_taps", "pbd_warp_windows_u8", "pbd_warp_windows_u8_f64", "pbd_qp_write_warped_u8",
+    "pbd_debug_warp_ms",
 ]
+PBD_WARP_SKIPPED, PBD_WARP_WRITTEN, PBD_WARP_FULL = 0, 1, 2   # pbd_qp_write_warped_u8's status per box
 PBD_ABI_VERSION = 5
 
 
@@ -173,6 +176,13 @@ def lib() -> C.CDLL:
         L.pbd_qp_opt.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pbd_qp_prune.argtypes = [C.c_void_p, C.c_void_p]
         L.pbd_qp_weights.argtypes = [C.c_void_p, C.c_void_p]
+        L.pbd_warp_geometry.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pbd_warp_taps.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        for name in ("pbd_warp_windows_u8", "pbd_warp_windows_u8_f64"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_void_p]
+        L.pbd_qp_write_warped_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                             C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]
         if L.pbd_abi_version() != PBD_ABI_VERSION:
             raise ImportError(f"{LIB_PATH}: ABI version {L.pbd_abi_version()}, this binding is for {PBD_ABI_VERSION}")
         _lib = L
@@ -982,6 +992,25 @@ class Handle:
         self._chk(self.L.pbd_reduce_f64(self.h, _p(im, C.c_double), w, hgt, cn, _p(out, C.c_double), C.byref(ow), C.byref(oh)))
         return out[:oh.value * ow.value * cn].reshape((oh.value, ow.value) + ((cn,) if im.ndim == 3 else ())).copy()
 
+    def warp_windows(self, im: np.ndarray, boxes, filter: int):
+        """pbd_warp_windows_u8[_f64]: warppos.m's windows of the boxes ((x1, y1, x2, y2), 1-based inclusive) for filter `filter` and
+        their HOG -> (windows [n, oh, ow, 3] float64, features [n, kh, kw, 32] of the handle's dtype)"""
+        im, w, hgt, cn = _frame_u8(im)
+        boxes = np.ascontiguousarray(boxes, np.float64).reshape(-1, 4)
+        kh, kw = self.filter_size(filter)
+        sbin = self.model.sbin
+        win = np.zeros((len(boxes), (kh + 2) * sbin, (kw + 2) * sbin, 3), np.float64)
+        feat = np.zeros((len(boxes), kh, kw, 32), self.dtype)
+        self._chk(self._fn("pbd_warp_windows_u8")(self.h, _vp(im), w, hgt, cn, w * cn, _vp(boxes), len(boxes), int(filter), _vp(win),
+                                                 _vp(feat)))
+        return win, feat
+
+    def warp_ms(self):
+        """pbd_debug_warp_ms: (resample, hog, write) ms of the last warped-positives call, measured while set_profiling() is on"""
+        ms = (C.c_float * 3)()
+        self._chk(self.L.pbd_debug_warp_ms(self.h, ms))
+        return tuple(ms)
+
     def pyrdown(self, im: np.ndarray):
         im = np.ascontiguousarray(im, np.uint8)
         hgt, w = im.shape[:2]
@@ -1168,6 +1197,39 @@ def _vp(a):
     return None if a is None else C.c_void_p(a.ctypes.data)
 
 
+def _frame_u8(im):
+    """(contiguous uint8 array, w, hgt, cn) of an HxW or HxWxcn frame"""
+    im = np.ascontiguousarray(im, np.uint8)
+    hgt, w = im.shape[:2]
+    return im, w, hgt, 1 if im.ndim == 2 else im.shape[2]
+
+
+def warp_geometry(box, kh, kw, sbin):
+    """pbd_warp_geometry (host code, no GPU): the crop of warppos.m for a box (x1, y1, x2, y2), 1-based inclusive ->
+    dict(rect=(X1, Y1, X2, Y2), rows_first, py, px)"""
+    box = np.ascontiguousarray(box, np.float64).reshape(4)
+    rect = np.zeros(4, np.int32)
+    rf, py, px = C.c_int32(), C.c_int32(), C.c_int32()
+    rc = lib().pbd_warp_geometry(_vp(box), int(kh), int(kw), int(sbin), _vp(rect), C.byref(rf), C.byref(py), C.byref(px))
+    if rc != PBD_OK:
+        raise PbdError(rc, "pbd_warp_geometry")
+    return dict(rect=tuple(int(v) for v in rect), rows_first=bool(rf.value), py=py.value, px=px.value)
+
+
+def warp_taps(n_in, n_out):
+    """pbd_warp_taps (host code, no GPU): one axis of the bilinear resize from n_in to n_out -> (index [n_out, P] int32, 0-based inside
+    the crop with the mirror resolved; weight [n_out, P] float64, normalised)"""
+    P = C.c_int32()
+    rc = lib().pbd_warp_taps(int(n_in), int(n_out), None, None, 0, C.byref(P))
+    if rc != PBD_OK:
+        raise PbdError(rc, "pbd_warp_taps")
+    idx, w = np.zeros((n_out, P.value), np.int32), np.zeros((n_out, P.value), np.float64)
+    rc = lib().pbd_warp_taps(int(n_in), int(n_out), _vp(idx), _vp(w), idx.size, C.byref(P))
+    if rc != PBD_OK:
+        raise PbdError(rc, "pbd_warp_taps")
+    return idx, w
+
+
 class QpCache:
     """pbd_qp (include/pbd_c.h "training example cache"): the QP's cache of block-sparse examples on the device — qp_write.m,
     matlab/mex/score.cc and lincomb.cc — and the coordinate-descent solver over it (qp_one_sparse.cc, qp_one.m, qp_refresh.m, qp_opt.m,
@@ -1206,6 +1268,19 @@ class QpCache:
         self.handle._chk(self.L.pbd_qp_write(self.q, heads.ctypes.data_as(C.c_void_p), _vp(lc), len(heads), int(label), int(id),
                                              C.byref(written)))
         return written.value
+
+    def write_warped(self, im, boxes, filter: int, bias: int, min_area: float = 0.0, ids=None):
+        """pbd_qp_write_warped_u8: train.m's poswarp — the boxes ((x1, y1, x2, y2), 1-based inclusive) of the 8-bit frame cropped, resized,
+        HOGed and appended as positives [bias | window of `filter`] without leaving the device -> (written, status [n] int32:
+        PBD_WARP_WRITTEN / _SKIPPED (area below min_area) / _FULL).  ids: one id per box (None: the box's index)."""
+        im, w, hgt, cn = _frame_u8(im)
+        boxes = np.ascontiguousarray(boxes, np.float64).reshape(-1, 4)
+        ids = None if ids is None else np.ascontiguousarray(ids, np.int32).reshape(len(boxes))
+        status = np.full(len(boxes), -1, np.int32)
+        written = C.c_int(-1)
+        self.handle._chk(self.L.pbd_qp_write_warped_u8(self.q, _vp(im), w, hgt, cn, w * cn, _vp(boxes), _vp(ids), len(boxes), int(filter),
+                                                       int(bias), float(min_area), _vp(status), C.byref(written)))
+        return written.value, status
 
     @staticmethod
     def _inds(inds):

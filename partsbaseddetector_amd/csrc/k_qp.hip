@@ -6,6 +6,7 @@
 //   values) and the column stores coalesce; no unscaled window is staged in HBM.  The sums behind d and b follow the order the header
 //   states: per block 64 lane-strided partials and a halving fold, then the blocks in block order by one thread.  Nothing of that
 //   depends on the grid: a record's bits are the same wherever it lands.
+// k_qp_poswrite: a warped positive (k_warp.hip's window through k_hog) as a two-block column, one wavefront per example.
 // k_qp_score: one lane owns one example's serial add chain (score.cc's order); a wavefront stages its 64 columns through LDS in
 //   chunks with coalesced loads and each lane walks its own row (pitch 65: no bank conflict).  w is read through L2.
 // k_qp_lincomb: one thread per dense element walks inds in order; the per-example block table (written with the column) tells it
@@ -21,8 +22,8 @@
 #define QL_NT 256
 
 // one block of the column by one wavefront: header, values, table entry and its two sums.  val(e): element e's value, double, unsigned
-template <typename F>
-__device__ __forceinline__ void qp_block(const QpWriteArgs& a, float* col, int* tab, double* s_sum, int bi, int o, int start, int n,
+template <typename A, typename F>
+__device__ __forceinline__ void qp_block(const A& a, float* col, int* tab, double* s_sum, int bi, int o, int start, int n,
                                          bool neg, F val) {
   const int lane = threadIdx.x & 63;
   double sd = 0.0, sb = 0.0;
@@ -40,6 +41,16 @@ __device__ __forceinline__ void qp_block(const QpWriteArgs& a, float* col, int* 
     tab[bi * 3] = start; tab[bi * 3 + 1] = n; tab[bi * 3 + 2] = o + 2;
     s_sum[bi * 2] = sd; s_sum[bi * 2 + 1] = sb;
   }
+}
+
+// the column's block count, d and b from its blocks' sums, in block order, by one thread
+__device__ __forceinline__ void qp_column_sums(const QpDev& q, float* col, int col_i, int nb, const double* s_sum, double C) {
+  double d = 0.0, bias = 1.0;
+  for (int bi = 0; bi < nb; ++bi) { d = __dadd_rn(d, s_sum[bi * 2]); bias = __dsub_rn(bias, s_sum[bi * 2 + 1]); }
+  col[0] = (float)nb;
+  q.nblk[col_i] = nb;
+  q.d[col_i] = d;
+  q.b[col_i] = (float)__dmul_rn(C, bias);
 }
 
 template <typename T>
@@ -103,14 +114,7 @@ __global__ void __launch_bounds__(QW_NT) k_qp_write(QpWriteArgs a) {
       }
     for (int t = used + threadIdx.x; t < k; t += QW_NT) col[t] = 0.f;   // qp_write.m:46, the tail
     __syncthreads();
-    if (threadIdx.x == 0) {
-      double d = 0.0, bias = 1.0;
-      for (int bi = 0; bi < nb; ++bi) { d = __dadd_rn(d, s_sum[bi * 2]); bias = __dsub_rn(bias, s_sum[bi * 2 + 1]); }
-      col[0] = (float)nb;
-      a.q.nblk[col_i] = nb;
-      a.q.d[col_i] = d;
-      a.q.b[col_i] = (float)__dmul_rn(a.C, bias);
-    }
+    if (threadIdx.x == 0) qp_column_sums(a.q, col, col_i, nb, s_sum, a.C);
     if (threadIdx.x < 5) {
       const int t = threadIdx.x;
       a.q.ids[(size_t)col_i * 5 + t] = t == 0 ? a.label : t == 1 ? a.id : t == 2 ? lvl : t == 3 ? lc[0] : lc[1];
@@ -124,6 +128,30 @@ void launch_qp_write(const QpWriteArgs& a, int ts, hipStream_t s) {
   const size_t lds = sizeof(double) * 6 * (size_t)mp + sizeof(int) * (4 * (size_t)mp + 2);   // <= 16.4 KB (256 parts)
   if (ts == 8) hipLaunchKernelGGL(k_qp_write<double>, dim3(nb), dim3(QW_NT), lds, s, a);
   else hipLaunchKernelGGL(k_qp_write<float>, dim3(nb), dim3(QW_NT), lds, s, a);
+}
+
+// ---- qp_poswrite (train.m:152-161): a warped positive's column — the bias block [1], then its HOG window — from the feature buffer
+// the warp left on the device.  One wavefront per example; the blocks, their sums and the column's d and b are k_qp_write's text.
+template <typename T>
+__global__ void __launch_bounds__(64) k_qp_poswrite(QpPosArgs a) {
+  __shared__ double s_sum[4];
+  const int r = blockIdx.x, lane = threadIdx.x, k = a.q.k;
+  const int col_i = a.q.slot[a.n0 + r];
+  float* col = a.q.x + (size_t)k * col_i;
+  int* tab = a.q.tab + (size_t)col_i * a.q.nbmax * 3;
+  const T* feat = (const T*)a.feat + (size_t)r * a.wlen;
+  qp_block(a, col, tab, s_sum, 0, 1, a.bias_start, 1, false, [](int) { return 1.0; });
+  qp_block(a, col, tab, s_sum, 1, 4, a.filt_start, a.wlen, false, [&](int e) { return (double)feat[e]; });
+  for (int t = 6 + a.wlen + lane; t < k; t += 64) col[t] = 0.f;
+  __syncthreads();
+  if (lane == 0) qp_column_sums(a.q, col, col_i, 2, s_sum, a.C);
+  if (lane < 5) a.q.ids[(size_t)col_i * 5 + lane] = lane == 0 ? 1 : lane == 1 ? a.ids[r] : 0;
+}
+
+void launch_qp_poswrite(const QpPosArgs& a, int ts, hipStream_t s) {
+  if (a.n <= 0) return;
+  if (ts == 8) hipLaunchKernelGGL(k_qp_poswrite<double>, dim3(a.n), dim3(64), 0, s, a);
+  else hipLaunchKernelGGL(k_qp_poswrite<float>, dim3(a.n), dim3(64), 0, s, a);
 }
 
 // ---- score.cc ------------------------------------------------------------------------------------------------------------------

@@ -218,6 +218,7 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   bool profiling = false;
   hipEvent_t ev[8] = {};
   float stage_ms[6] = {0, 0, 0, 0, 0, 0};
+  float warp_ms[3] = {0, 0, 0};      // the last warped-positives call while profiling: resample passes, HOG, write (pbd_debug_warp_ms)
   hipEvent_t ev_dp0 = nullptr, ev_dp1 = nullptr;
   double dp_ms_sum = 0; int dp_frames = 0; bool dp_timer_on = true; bool dp_timed = false;   // DP events are recorded only while profiling
   hipGraphExec_t gexec = nullptr;   // pbd_options.graph: the frame's launches, captured once per geometry
@@ -682,6 +683,30 @@ struct QpWriteArgs {
   double C; int label, id;
 };
 void launch_qp_write(const QpWriteArgs& a, int ts, hipStream_t s);
+// a warped positive's column (train.m:152-161 qp_poswrite): window r of `feat` (T [n][wlen]) becomes example n0 + r with ids (1, ids[r], 0, 0, 0)
+struct QpPosArgs {
+  QpDev q; int n0, n;
+  const void* feat; const int* ids;
+  const double* wreg; const double* w0;
+  int bias_start, filt_start, wlen;   // dense starts of the two blocks, values of the window
+  double C;
+};
+void launch_qp_poswrite(const QpPosArgs& a, int ts, hipStream_t s);
+// warped positives (k_warp.hip, pbd_qp_warp.cpp; include/pbd_c.h "warped positives"): one box's crop + bilinear resize in two passes.
+// Tap tables are MatTap [P][n_out] — tap-major, so the lanes of consecutive outputs read consecutive taps —, si the 0-based source index
+// inside the crop with the mirror resolved (pbd_warp.cpp)
+struct WarpJob {
+  unsigned long long scr_off, win_off;   // doubles: the job's intermediate in the scratch, its window in the window buffer
+  unsigned long long ytap, xtap;         // first tap of its y table ([Py][oh]) and its x table ([Px][ow])
+  int X0, Y0, cw, ch;                    // the crop: the image pixel (0-based, unclamped) of its pixel (0, 0), and its size
+  int Py, Px, rows_first, pad;           // rows_first: the intermediate is [oh][cw][3] (y resampled), else [ch][ow][3] (x resampled)
+};
+struct WarpArgs {
+  const WarpJob* jobs; const MatTap* taps;
+  const uint8_t* im; int w, h, cn; size_t stride;   // the 8-bit frame on the device, rows `stride` bytes apart
+  double* scratch; double* win; int ow, oh;
+};
+void launch_warp(const WarpArgs& a, int njobs, unsigned max_first, hipStream_t s);   // max_first: elements of the largest intermediate
 void launch_qp_score(const QpDev& q, const double* w, const int* inds, int n, double* out, hipStream_t s);
 void launch_qp_lincomb(const QpDev& q, const double* a, const int* inds, int n, double* w_out, hipStream_t s);
 // the QP solver's device state (k_qp_solve.hip, pbd_qp_solve.cpp; include/pbd_c.h "QP solver")

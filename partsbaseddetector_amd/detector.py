@@ -485,3 +485,15 @@ class PartsBasedDetector:
         cache takes no more and is no error."""
         heads, _, locs = Candidate._pack(candidates)
         return cache.write(heads, locs, label, id)
+
+    def writeWarped(self, im: np.ndarray, boxes, cache: "capi.QpCache", filter: int = None, bias: int = None, ids=None):
+        """poswarp of matlab/learning/train.m:131-161: the positive boxes ((x1, y1, x2, y2), 1-based inclusive, of the 8-bit frame `im`)
+        warped to the root filter's size (warppos.m), HOGed and appended to `cache` as [bias | window] positives, all on the GPU.
+        filter / bias default to component 0's root (warppos.m:6, model.bias.i).  Boxes smaller than prod(maxsize * sbin) — the
+        largest filter height and width of the model, train.m:135 — are skipped.  -> (written, status per box)."""
+        m = self.handle.model
+        filter = int(m.filterid[0][0][0]) if filter is None else int(filter)
+        bias = int(m.biasid[0][0][0]) if bias is None else int(bias)
+        maxsize = m.filter_sizes().max(axis=0)
+        min_area = float(maxsize[0] * m.sbin) * float(maxsize[1] * m.sbin)
+        return cache.write_warped(im, boxes, filter, bias, min_area, ids)

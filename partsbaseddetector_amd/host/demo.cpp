@@ -19,6 +19,7 @@ using namespace pbd;
 static std::vector<GtBox> g_gtbox;
 static const char* g_examples_file = nullptr;   // --examples FILE (anywhere): the detections as QP examples, written to FILE
 static double g_gt_overlap = 0.3;
+static std::vector<GtBox> g_warp;               // --warp x1,y1,x2,y2 (anywhere, repeatable): the boxes as warped positives, dumped and nothing else
 static void print_pose(const Candidate& c) {
   printf("%.9g %d %d", c.score(), c.component(), c.level);
   for (const Rect& r : c.parts()) printf(" %d,%d,%d,%d", r.x, r.y, r.width, r.height);
@@ -44,6 +45,34 @@ static void run(Model& model, const Mat& im, bool stagewise, int special = 0, co
   if (matlab_pyramid) pbd.setPyramidKind(PBD_PYRAMID_MATLAB);
   pbd.distributeModel(model);
   vectorCandidate candidates;
+  if (!g_warp.empty()) {   // --warp: train.m's poswarp of the boxes at component 0's root filter and bias (Cpos 1), the columns dumped
+    const int filter = model.filterid()[0][0][0], bias = model.biasid()[0][0][0];
+    int mh = 0, mw = 0;
+    for (const Mat& f : model.filters()) { mh = std::max(mh, f.rows); mw = std::max(mw, f.cols / model.flen()); }
+    const double min_area = (double)(mh * model.binsize()) * (double)(mw * model.binsize());   // train.m:135
+    auto cache = pbd.exampleCache((int)g_warp.size(), 1.0, 1.0);
+    std::vector<int32_t> status;
+    const int n = cache->writeWarped(im, g_warp, filter, bias, min_area, &status);
+    int len = 0, k = 0;
+    cache->dims(&len, &k, nullptr, nullptr);
+    std::vector<float> x((size_t)n * k), b((size_t)n);
+    std::vector<int32_t> ids((size_t)n * 5);
+    std::vector<double> d((size_t)n);
+    cache->get(0, n, x.data(), ids.data(), b.data(), d.data());
+    printf("Warped positives: %d of %zu written, k %d, len %d, min area %g\n", n, g_warp.size(), k, len, min_area);
+    for (size_t i = 0, e = 0; i < g_warp.size(); ++i) {
+      printf("Box %zu (%g,%g,%g,%g): %s", i, g_warp[i].x1, g_warp[i].y1, g_warp[i].x2, g_warp[i].y2,
+             status[i] == PBD_WARP_WRITTEN ? "written" : status[i] == PBD_WARP_SKIPPED ? "skipped" : "full");
+      if (status[i] == PBD_WARP_WRITTEN) {
+        double sum = 0;   // position-weighted checksum of the column, for a comparison with another run
+        for (int t = 0; t < k; ++t) sum += (double)(t + 1) * (double)x[e * k + t];
+        printf(" id %d blocks %d b %.9g d %.17g checksum %.17g", ids[e * 5 + 1], (int)x[e * k], b[e], d[e], sum);
+        ++e;
+      }
+      printf("\n");
+    }
+    return;
+  }
   if (stagewise) {
     vectorMat pyramid;
     pbd.features().pyramid(im, pyramid);
@@ -233,6 +262,23 @@ int main(int argc, char** argv) {
       for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
       argc -= 2; --i;
     } else
+    if (std::string(argv[i]) == "--warp") {
+      double v[4] = {0, 0, 0, 0};
+      int n = 0;
+      const char* p = i + 1 < argc ? argv[i + 1] : "";
+      while (*p && n < 4) {
+        char* end = nullptr;
+        v[n] = strtod(p, &end);
+        if (end == p || !(v[n] - v[n] == 0.0)) { n = -1; break; }
+        ++n;
+        p = *end == ',' ? end + 1 : end;
+        if (*end && *end != ',') { n = -1; break; }
+      }
+      if (n < 4 || *p) { printf("--warp x1,y1,x2,y2: finite numbers, 1-based inclusive pixel coordinates\n"); exit(-1); }
+      g_warp.push_back(GtBox{v[0], v[1], v[2], v[3]});
+      for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+      argc -= 2; --i;
+    } else
     if (std::string(argv[i]) == "--examples") {
       if (i + 1 >= argc || !*argv[i + 1]) { printf("--examples FILE\n"); exit(-1); }
       g_examples_file = argv[i + 1];
@@ -256,7 +302,7 @@ int main(int argc, char** argv) {
       --argc; --i;
     }
   if (argc < 6 || argc > 8) {
-    printf("Usage: pbd_demo model_file image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE] [--examples FILE] [--nms-parts OVERLAP] [--matlab-pyramid] [--gtbox x1,y1,x2,y2[,overlap]]...\n");
+    printf("Usage: pbd_demo model_file image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE] [--examples FILE] [--nms-parts OVERLAP] [--matlab-pyramid] [--gtbox x1,y1,x2,y2[,overlap]]... [--warp x1,y1,x2,y2]...\n");
     exit(-1);
   }
   // determine the type of model to read (src/demo.cpp:63-82)
@@ -284,6 +330,7 @@ int main(int argc, char** argv) {
     if (part_scores && stagewise) { printf("--part-scores: the fused detect() only\n"); exit(-1); }
     if (features_file && special) { printf("--features: not with %s\n", mode.c_str()); exit(-1); }
     if (g_examples_file && (special || !g_gtbox.empty())) { printf("--examples: not with %s\n", special ? mode.c_str() : "--gtbox"); exit(-1); }
+    if (!g_warp.empty() && (special || stagewise || !g_gtbox.empty() || g_examples_file || features_file || part_scores || nms_parts)) { printf("--warp: on its own (or with double)\n"); exit(-1); }
     if (!g_gtbox.empty() && (part_scores || nms_parts || features_file)) { printf("--gtbox: not with --part-scores, --nms-parts or --features\n"); exit(-1); }
     if (mode.find("double") != std::string::npos) run<double>(model, im, stagewise, 0, nullptr, part_scores, pad, features_file, nms_parts, matlab_pyramid);
     else run<float>(model, im, stagewise, special, special ? argv[7] : nullptr, part_scores, pad, features_file, nms_parts, matlab_pyramid);

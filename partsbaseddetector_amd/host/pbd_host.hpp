@@ -882,6 +882,20 @@ class PartsBasedDetector {
     int prune() { int n = 0; dev_->check(pbd_qp_prune(q_, &n)); return n; }
     // qp_w.m: the next model's weights, w ./ wreg + w0 (Model.feature_layout() maps them back)
     void weights(std::vector<double>& w) { int len = 0; dims(&len, nullptr, nullptr, nullptr); w.assign((size_t)len, 0.0); dev_->check(pbd_qp_weights(q_, w.data())); }
+    // poswarp of matlab/learning/train.m:131-161 (include/pbd_c.h "warped positives"): the boxes (1-based inclusive) of the 8-bit frame
+    // warped to filter `filter`'s size (warppos.m), HOGed and appended as [bias | window] positives, all on the GPU.  Boxes below
+    // min_area (prod(maxsize * sbin), train.m:135) are skipped; status (optional): PBD_WARP_WRITTEN / _SKIPPED / _FULL per box; ids
+    // (optional): one id per box, else the box's index.  Returns how many were written.
+    int writeWarped(const Mat& im, const std::vector<GtBox>& boxes, int filter, int bias, double min_area, std::vector<int32_t>* status = nullptr,
+                    const std::vector<int32_t>* ids = nullptr) {
+      if (im.depth() != PBD_8U) throw Exception(PBD_ERR_UNSUPPORTED, "warped positives: 8-bit frames only");
+      if (ids && ids->size() != boxes.size()) throw Exception(PBD_ERR_ARG, "ExampleCache::writeWarped: one id per box");
+      if (status) status->assign(boxes.size(), -1);
+      int written = 0;
+      dev_->check(pbd_qp_write_warped_u8(q_, im.ptr<uint8_t>(), im.cols, im.rows, im.channels(), (int)im.step(), boxes.empty() ? nullptr : &boxes[0].x1,
+                                         ids ? ids->data() : nullptr, (int)boxes.size(), filter, bias, min_area, status ? status->data() : nullptr, &written));
+      return written;
+    }
    private:
     void score_(const std::vector<double>& w, const int32_t* inds, int n, std::vector<double>& out) {
       int len = 0; dims(&len, nullptr, nullptr, nullptr);

@@ -220,6 +220,27 @@ class Model:
             wreg[lay["bias"] + int(self.biasid[c][0][0])] = .01
         return w, wreg, w0, noneg
 
+    def with_weight_vector(self, w) -> "Model":
+        """matlab/learning/vec2model.m in feature_layout()'s order, the inverse of weight_vector(): a copy of this model whose biases,
+        deformations and filters are `w`'s elements (QpCache.weights() after a solve).  The model stores float32, so vec2model.m's
+        closing assertion w == model2vec(model) holds on float32-ROUNDED weights: with_weight_vector(w).weight_vector() equals
+        np.float32(w), and equals w exactly when w is float32-representable."""
+        import copy
+        lay = self.feature_layout()
+        w = np.asarray(w, np.float64).ravel()
+        if w.size != lay["size"]:
+            raise ValueError(f"w must have feature_layout()['size'] = {lay['size']} elements")
+        if not np.isfinite(w).all():
+            raise ValueError("w must be finite")
+        m = copy.copy(self)
+        m._keep = []
+        nb = int(np.asarray(self.biasw).size)
+        m.biasw = w[:nb].astype(np.float32)
+        m.defw = w[lay["deform"]:lay["deform"] + np.asarray(self.defw).size].astype(np.float32).reshape(np.asarray(self.defw).shape)
+        m.filtersw = [w[int(o):int(o) + np.asarray(f).size].astype(np.float32).reshape(np.asarray(f).shape)
+                      for o, f in zip(lay["filters"], self.filtersw)]
+        return m
+
     def to_desc(self) -> pbd_model_desc:
         """Flatten into the C ABI descriptor (arrays kept alive on self).  Uniform banks only (pbd_create)."""
         kh = self.filtersw[0].shape[0]
