@@ -620,7 +620,7 @@ int pbd_candidates_box3d(pbd_handle* h, const pbd_camera* cam, const void* depth
  * PBD_ERR_ARG.  PBD_ERR_STATE while a frame is pending; PBD_ERR_UNSUPPORTED for a pbd_group member.
  * pbd_get_box3d: after the detect / collect returned, frame `frame`'s results (entry i = the i-th record returned for that
  * frame; centres as for pbd_candidates_box3d, may be NULL); *count = its records (PBD_ERR_CAPACITY over `capacity`).
- * PBD_ERR_STATE after a frame that did not compute them (a plain frame, the setting off, a batch frame whose depth was NULL, a
+ * PBD_ERR_STATE after a frame that did not compute them (a plain frame, pbd_dp_argmin / pbd_dp_argbest, the setting off, a batch frame whose depth was NULL, a
  * frame out of range) or while a frame is pending; PBD_ERR_UNSUPPORTED for a pbd_group member.  Buffers are allocated on first
  * use and count in pbd_get_footprint.                                                                                        */
 int pbd_set_box3d(pbd_handle* h, int on, const pbd_camera* cam);
@@ -671,7 +671,7 @@ int pbd_candidates_cluster3d(pbd_handle* h, const void* cloud, int cw, int ch, i
  * pending; PBD_ERR_UNSUPPORTED for a pbd_group member.
  * pbd_get_cluster3d: after the detect / collect returned, frame `frame`'s results (entry i = the i-th record returned for that
  * frame; indices as for pbd_candidates_cluster3d); *count = its records (PBD_ERR_CAPACITY over `capacity`, or over
- * idx_capacity with *idx_total set).  PBD_ERR_STATE after a frame that computed no 3-D boxes or clusters, or while a frame is
+ * idx_capacity with *idx_total set).  PBD_ERR_STATE after a frame that computed no 3-D boxes or clusters (pbd_dp_argmin / pbd_dp_argbest among them), or while a frame is
  * pending; PBD_ERR_UNSUPPORTED for a pbd_group member.  Scratch (one whole frame's points per concurrent record) is allocated
  * on first use and counts in pbd_get_footprint.                                                                               */
 int pbd_set_cluster3d(pbd_handle* h, int on, float tolerance);

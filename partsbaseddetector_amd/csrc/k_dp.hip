@@ -970,15 +970,15 @@ __global__ __launch_bounds__(64) void k_backtrack(const int* __restrict__ count,
   }
 }
 
-void launch_backtrack(const int* count, const CandRec* rec, int capacity, const BackLevel* back, int ncomp,
-                      const int* parent, const int* plane0, const int* nparts, int max_parts, const int* mix_rows, char* out,
-                      size_t out_stride, int ts, const int* flat, const int* depth, int max_depth, int nflat,
-                      const unsigned long long* scr_base, const void* ix, const void* iy, int ptr_bytes, int correct_ptr,
-                      const int16_t* extx, const int16_t* exty, const unsigned long long* ext_base, int* count_out, int pad,
-                      const FoldJob* folds, const unsigned long long* pick, hipStream_t s) {   // pick != null: Ik is picked from the fold's kept scores, not read from planes
-  const int nblk = std::min(capacity, 2048);   // 8 blocks of one wavefront per CU; more candidates than that are taken in further sweeps
-  if (ts == 8) hipLaunchKernelGGL(k_backtrack<double>, dim3(nblk), dim3(64), 0, s, count, rec, capacity, back, ncomp, parent, plane0, nparts, max_parts, mix_rows, out, out_stride, flat, depth, max_depth, nflat, scr_base, ix, iy, ptr_bytes == 1, correct_ptr, extx, exty, ext_base, count_out, 1 + pad, (const char*)folds, pick);
-  else hipLaunchKernelGGL(k_backtrack<float>, dim3(nblk), dim3(64), 0, s, count, rec, capacity, back, ncomp, parent, plane0, nparts, max_parts, mix_rows, out, out_stride, flat, depth, max_depth, nflat, scr_base, ix, iy, ptr_bytes == 1, correct_ptr, extx, exty, ext_base, count_out, 1 + pad, (const char*)folds, pick);
+void launch_backtrack(const BacktrackArgs& a, int ts, hipStream_t s) {
+  const int nblk = std::min(a.capacity, 2048);   // 8 blocks of one wavefront per CU; more candidates than that are taken in further sweeps
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(nblk), dim3(64), 0, s, a.count, a.rec, a.capacity, a.back, a.ncomp, a.parent, a.plane0, a.nparts, a.max_parts, a.mix_rows,
+                       a.out, a.out_stride, a.flat, a.depth, a.max_depth, a.nflat, a.scr_base, a.ix, a.iy, a.ptr_bytes == 1, a.correct_ptr, a.extx, a.exty,
+                       a.ext_base, a.count_out, 1 + a.pad, (const char*)a.folds, a.pick);
+  };
+  if (ts == 8) launch(k_backtrack<double>);
+  else launch(k_backtrack<float>);
 }
 
 // ---------------------------------------------------------------------------

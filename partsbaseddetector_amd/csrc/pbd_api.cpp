@@ -202,7 +202,7 @@ static void mark_responses(pbd_handle* h) { h->have_resp = true; compact_mark_re
 // (the planes stay valid responses: pbd_get_level_response returns them masked, min() runs on them)
 static void mark_latent_mask(pbd_handle* h, int component) { h->lat_masked = true; h->lat_component = component; }
 static void mark_min(pbd_handle* h, bool timed) {
-  h->dp_timed = timed;
+  h->min_timed = timed;
   h->have_dp = h->min_ran = true;
   h->ik_lazy = h->fold;                 // fold plans: the Ik planes are not materialised (ensure_ik); the three-kernel structure's k_reduce has written them
   h->ext_ptr = h->root_dirty = false;   // back-tracking reads this min()'s own tables again, thresholded by it
@@ -409,15 +409,21 @@ static int run_pdf(pbd_handle* h) {
   return PBD_OK;
 }
 
+// k_root over the plan's root jobs into the hit list: the root tables written (rescan: read back) and the hits above thresh, under `mask`
+// (null: every cell) listed
+static void root_hits(pbd_handle* h, double thresh, int rescan, const uint8_t* mask) {
+  launch_root(h->d_rootjobs, h->d_rootblocks, h->n_rootblocks, thresh, h->d_cand_count, h->d_cand_rec, h->opt.max_candidates, h->ts,
+              h->d_foldjobs, h->d_biasw, rescan, h->fold_mix, mask, mask ? h->d_rootv : nullptr, h->stream);
+}
 // pbd_options.reserved[0] = sz > 0: nonMaximaSuppression(rootv, sz) of every (level, component) plane on the device, then the hits
 static void nms_and_rescan(pbd_handle* h) {
   hipMemsetAsync(h->d_nms_mask, 0, h->cells * (size_t)h->md.ncomponents, h->stream);
   launch_nms_roots(h->d_rootjobs, h->n_rootjobs, h->root_maxcells, h->d_rootv, h->ts, h->nms_sz, h->d_nms_mask, h->stream);
-  launch_root(h->d_rootjobs, h->d_rootblocks, h->n_rootblocks, (double)h->md.thresh, h->d_cand_count, h->d_cand_rec,
-              h->opt.max_candidates, h->ts, h->d_foldjobs, h->d_biasw, 1, h->fold_mix, h->d_nms_mask, h->d_rootv, h->stream);
+  root_hits(h, (double)h->md.thresh, 1, h->d_nms_mask);
 }
 
-static int run_dp_min(pbd_handle* h) {
+// latent: the frame takes no hit list from the threshold (FrameRoute::latent)
+static int run_dp_min(pbd_handle* h, bool latent = false) {
   const bool dpt = h->profiling && h->dp_timer_on;
   if (dpt) hipEventRecord(h->ev_dp0, h->stream);
   // one chain of rounds on the handle's stream.  fold: x pass (from round 1 on its loader folds the children's
@@ -434,13 +440,11 @@ static int run_dp_min(pbd_handle* h) {
     // score-map NMS in front of the back-tracking (src/nms.cpp:84-129; the reference's call site is commented out,
     // src/PartsBasedDetector.cpp:86): the root tables are written with no hit (threshold +inf), the block NMS runs on the
     // resident rootv planes, and the hit list is then compacted from (score > thresh) AND (local maximum)
-    launch_root(h->d_rootjobs, h->d_rootblocks, h->n_rootblocks, INFINITY, h->d_cand_count, h->d_cand_rec,
-                h->opt.max_candidates, h->ts, h->d_foldjobs, h->d_biasw, 0, h->fold_mix, nullptr, nullptr, h->stream);
+    root_hits(h, INFINITY, 0, nullptr);
     nms_and_rescan(h);
   } else
   // (a latent frame takes no hit list from the threshold — detect.m:20 —: k_latent_best writes its one candidate)
-  launch_root(h->d_rootjobs, h->d_rootblocks, h->n_rootblocks, h->lat_frame ? (double)INFINITY : (double)h->md.thresh, h->d_cand_count, h->d_cand_rec,
-              h->opt.max_candidates, h->ts, h->d_foldjobs, h->d_biasw, 0, h->fold_mix, nullptr, nullptr, h->stream);
+  root_hits(h, latent ? (double)INFINITY : (double)h->md.thresh, 0, nullptr);
   if (dpt) hipEventRecord(h->ev_dp1, h->stream);
   LAUNCHCHK(h, "DP min");
   mark_min(h, dpt);
@@ -579,57 +583,70 @@ static int run_latent_best(pbd_handle* h) {
   return PBD_OK;
 }
 
-static int run_argmin_enqueue(pbd_handle* h, bool filter = false) {
-  if (h->root_dirty) {   // root tables injected since min(): the hits are those of the tables now on the device
-    hipMemsetAsync(h->d_cand_count, 0, sizeof(int), h->stream);
-    if (h->nms_sz > 0) nms_and_rescan(h);
-    else
-    launch_root(h->d_rootjobs, h->d_rootblocks, h->n_rootblocks, (double)h->md.thresh, h->d_cand_count, h->d_cand_rec,
-                h->opt.max_candidates, h->ts, h->d_foldjobs, h->d_biasw, 1, h->fold_mix, nullptr, nullptr, h->stream);
-    h->root_dirty = false;
-  }
-  // Round 6: a handle that is not a member of an RCCL-gathering group lets the back-tracking kernel write the records and the count straight
-  // into its pinned host buffers (hipHostMalloc: device-mapped, coherent): no copy nodes behind the kernel, and never a second copy for
-  // records beyond a first block.  Group members keep the device buffer: the all-gather reads it.  In front of a post-stage (depth
-  // pruning, candidate filter: pbd_post.cpp) the records go to the device buffer it reads.
-  const int cm = filter ? pbd_i_cand_mode(h) : PBD_CAND_RAW;
-  h->out_filtered = cm != PBD_CAND_RAW;
-  const bool zf = filter && h->zf_frame && h->zf_on;
-  const bool post = zf || h->out_filtered;
-  const bool zero_copy = PBD_ARGMIN_ZERO_COPY && !h->d_gsend;
-  char* out = h->h_cand_out;
-  int* count_out = h->h_cand_count;
-  if (post || !zero_copy) {
-    out = post && (zf || h->d_gsend) ? h->d_cand_raw : h->d_cand_out;
-    count_out = nullptr;
-  }
-  const bool gt = filter && h->gt_frame;   // (its entries refuse every post-stage: cm is RAW, no depth)
-  if (gt) { out = h->d_cand_out; count_out = nullptr; }   // a device list: only the selection's winners reach the host
-  launch_backtrack(h->d_cand_count, h->d_cand_rec, h->opt.max_candidates, h->d_back, h->md.ncomponents, h->d_parent,
-                   h->d_plane0, h->d_nparts, h->max_parts, h->d_mix_rows, out, h->cand_stride, h->ts, h->d_flat,
-                   h->d_depth, h->max_depth, (int)h->parts.size(), h->d_scr_base, h->d_dt_ixT, h->d_dt_iy, h->dt_ptr_bytes,
-                   h->opt.dt_correct_ptr, h->ext_ptr ? h->d_extx : nullptr, h->d_exty, h->d_ext_base, count_out, h->pad,
-                   h->d_foldjobs, h->ik_lazy && !h->ext_ptr ? h->d_pick : nullptr, h->stream);
-  if (post) return pbd_i_post_enqueue(h, cm, zf, out);
-  if (gt) return pbd_i_gt_enqueue(h, out);
-  LAUNCHCHK(h, "argmin");
-  if (zero_copy) { h->pending = true; h->out_on_host = true; return PBD_OK; }
-  h->out_on_host = false;
-  // members of an RCCL-gathering group send a fixed block (pbd_group.cpp sizes its buffers for PBD_FIRST_COPY records)
-  if (h->d_gsend || h->first_copy < kFirstCopy * h->batch) h->first_copy = kFirstCopy * h->batch;
-  const int first = std::min(h->first_copy, h->opt.max_candidates);
-  if (h->d_gsend) {   // member of an RCCL-gathering pbd_group: pack {count, first records} for the all-gather instead of the D2H
-    HIPCHK(h, hipMemcpyAsync(h->d_gsend, h->d_cand_count, sizeof(int), hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_gsend + 16, h->d_cand_out, h->cand_stride * first, hipMemcpyDeviceToDevice, h->stream));
-  } else {
-    HIPCHK(h, hipMemcpyAsync(h->h_cand_count, h->d_cand_count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->h_cand_out, h->d_cand_out, h->cand_stride * first, hipMemcpyDeviceToHost, h->stream));
-  }
-  h->pending = true;
+// ---- the route of a frame on this handle (pbd_route.hpp) ----------------------------------------------------------------------
+static RouteSettings route_settings(const pbd_handle* h, const FrameJob& job) {
+  RouteSettings s;
+  s.cand_mode = pbd_i_cand_mode(h); s.cand_nms = h->cand_nms;
+  s.zf_on = h->zf_on; s.b3_on = h->b3_on; s.cl3_on = h->cl3_on; s.ps_on = h->ps_on;
+  s.compact = h->compact; s.member = h->d_gsend != nullptr; s.zero_copy = PBD_ARGMIN_ZERO_COPY != 0;
+  s.ps_compact_was = h->pf.ps_compact;
+  // a frame's own min() records the DP events while profiling (run_dp_min); a stage entry back-tracks the tables of whichever min() ran last
+  s.dp_timed = job.kind == FRAME_STAGE ? h->min_timed : h->profiling && h->dp_timer_on;
+  return s;
+}
+// The frame's route, computed once and outside any capture, and the ONE assignment of the pending frame, whole, for every way a frame is enqueued:
+// eager, replayed from the captured graph, by a stage entry (a failed enqueue flips pf.active back).  The kept results of the frame before go with it.
+static int begin_pending(pbd_handle* h, const FrameJob& job, FrameRoute* r) {
+  if (!route_frame(route_settings(h, job), job, r))
+    return fail(h, PBD_ERR_STATE, "internal: no route for this frame under the handle's settings (an entry should have refused it)");
+  h->pf = r->pending;
+  h->b3_ready = h->cl3_ready = h->ps_ready = false;
   return PBD_OK;
 }
 
-static int enqueue_stages(pbd_handle* h, const uint8_t* d_src, int stride) {
+// Back-tracking into the route's buffer, the route's post-stages behind it, then the records' way to the host.
+// Round 6: a handle that is not a member of an RCCL-gathering group lets the back-tracking kernel write the records and the count straight
+// into its pinned host buffers (hipHostMalloc: device-mapped, coherent): no copy nodes behind the kernel, and never a second copy for
+// records beyond a first block.  Group members keep the device buffer: the all-gather reads it.  In front of a post-stage (depth
+// pruning, candidate filter: pbd_post.cpp) the records go to the device buffer it reads.
+static int run_argmin_enqueue(pbd_handle* h, const FrameJob& job, const FrameRoute& r) {
+  if (h->root_dirty) {   // root tables injected since min(): the hits are those of the tables now on the device
+    hipMemsetAsync(h->d_cand_count, 0, sizeof(int), h->stream);
+    if (h->nms_sz > 0) nms_and_rescan(h);
+    else root_hits(h, (double)h->md.thresh, 1, nullptr);
+    h->root_dirty = false;
+  }
+  BacktrackArgs a{};
+  a.count = h->d_cand_count; a.rec = h->d_cand_rec; a.capacity = h->opt.max_candidates;
+  a.back = h->d_back; a.ncomp = h->md.ncomponents;
+  a.parent = h->d_parent; a.plane0 = h->d_plane0; a.nparts = h->d_nparts; a.max_parts = h->max_parts; a.mix_rows = h->d_mix_rows;
+  a.out = pbd_i_route_buf(h, r.bt.out); a.out_stride = h->cand_stride;
+  a.flat = h->d_flat; a.depth = h->d_depth; a.max_depth = h->max_depth; a.nflat = (int)h->parts.size();
+  a.scr_base = h->d_scr_base; a.ix = h->d_dt_ixT; a.iy = h->d_dt_iy; a.ptr_bytes = h->dt_ptr_bytes; a.correct_ptr = h->opt.dt_correct_ptr;
+  a.extx = h->ext_ptr ? h->d_extx : nullptr; a.exty = h->d_exty; a.ext_base = h->d_ext_base;
+  a.count_out = r.bt_host_count ? h->h_cand_count : nullptr; a.pad = h->pad;
+  a.folds = h->d_foldjobs; a.pick = h->ik_lazy && !h->ext_ptr ? h->d_pick : nullptr;
+  launch_backtrack(a, h->ts, h->stream);
+  int rc;
+  if ((r.zf.on || r.filter.on) && (rc = pbd_i_post_enqueue(h, job, r))) return rc;
+  if (r.gt && (rc = pbd_i_gt_enqueue(h, r))) return rc;
+  LAUNCHCHK(h, r.zf.on ? "argmin + depth filter" : r.filter.on ? "argmin + candidate filter" : r.gt ? "argmin + gt boxes" : "argmin");
+  if (r.count_d2h != CNT_NONE) HIPCHK(h, hipMemcpyAsync(h->h_cand_count, pbd_i_route_count(h, r.count_d2h), sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (!r.first_d2h && r.pack_count == CNT_NONE) return PBD_OK;
+  // a first block of DEV_OUT's records goes with the count; members of an RCCL-gathering group send a fixed block (pbd_group.cpp sizes
+  // its buffers for PBD_FIRST_COPY records)
+  if (r.pack_count != CNT_NONE || h->first_copy < kFirstCopy * h->batch) h->first_copy = kFirstCopy * h->batch;
+  const int first = std::min(h->first_copy, h->opt.max_candidates);
+  if (r.pack_count != CNT_NONE) {   // {count, first records} for the all-gather instead of the D2H; of a cf block, [1]: kept in frame 0
+    const int* count = pbd_i_route_count(h, r.pack_count) + (route_cf_block(r.pack_count) ? 1 : 0);
+    HIPCHK(h, hipMemcpyAsync(h->d_gsend, count, sizeof(int), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_gsend + 16, h->d_cand_out, h->cand_stride * first, hipMemcpyDeviceToDevice, h->stream));
+  } else
+    HIPCHK(h, hipMemcpyAsync(h->h_cand_out, h->d_cand_out, h->cand_stride * first, hipMemcpyDeviceToHost, h->stream));
+  return PBD_OK;
+}
+
+static int enqueue_stages(pbd_handle* h, const FrameJob& job, const FrameRoute& r, const uint8_t* d_src, int stride) {
   int rc;
   const bool prof = h->profiling;
   if (prof) hipEventRecord(h->ev[0], h->stream);
@@ -638,16 +655,16 @@ static int enqueue_stages(pbd_handle* h, const uint8_t* d_src, int stride) {
   if ((rc = run_hog(h))) return rc;
   if (prof) hipEventRecord(h->ev[2], h->stream);
   if ((rc = run_pdf(h))) return rc;
-  if (h->lat_frame && (rc = run_latent_mask(h, h->batch))) return rc;   // (a latent frame's stage times: the mask in pdf's, the best root in min()'s)
+  if (r.latent && (rc = run_latent_mask(h, h->batch))) return rc;   // (a latent frame's stage times: the mask in pdf's, the best root in min()'s)
   if (prof) hipEventRecord(h->ev[3], h->stream);
-  if ((rc = run_dp_min(h))) return rc;
-  if (h->lat_frame && (rc = run_latent_best(h))) return rc;
+  if ((rc = run_dp_min(h, r.latent))) return rc;
+  if (r.latent && (rc = run_latent_best(h))) return rc;
   if (prof) hipEventRecord(h->ev[4], h->stream);
-  if ((rc = run_argmin_enqueue(h, true))) return rc;
-  if (h->lat_frame) h->root_dirty = true;   // the hit list is the latent record: a later pbd_dp_argmin thresholds the root tables again
+  if ((rc = run_argmin_enqueue(h, job, r))) return rc;
+  if (r.latent) h->root_dirty = true;   // the hit list is the latent record: a later pbd_dp_argmin thresholds the root tables again
   if (prof) hipEventRecord(h->ev[5], h->stream);
-  if (h->ps_frame && (rc = pbd_i_run_part_scores(h))) return rc;
-  if (h->b3_frame && (rc = pbd_i_run_box3d(h))) return rc;
+  if (r.pending.ps && (rc = pbd_i_run_part_scores(h, r))) return rc;
+  if (r.pending.b3 && (rc = pbd_i_run_box3d(h, job, r))) return rc;
   return PBD_OK;
 }
 
@@ -657,24 +674,24 @@ static int enqueue_stages(pbd_handle* h, const uint8_t* d_src, int stride) {
 // and every later frame is ONE hipGraphLaunch.  The graph reads the frame from the handle's own image buffer, so
 // an image that lives elsewhere in HBM is copied there first (0.9 MB, on the same stream).  Profiling runs (stage
 // events) and level groups on extra streams use the eager path.
-int enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride) {
+static int enqueue_routed(pbd_handle* h, const FrameJob& job, const FrameRoute& r, const uint8_t* d_src, int stride) {
   const bool graphable = h->opt.graph && !h->profiling;   // (frames of any depth: the launches depend on the plan only; round 5 replayed 8-bit plans only)
-  int rc = pbd_i_post_buffers(h);
+  int rc = pbd_i_post_buffers(h, r);
   if (rc) return rc;
   // depth-carrying frames run eagerly: the depth pointers are per frame; a captured graph stays for plain frames
   // latent frames too: the mask stage and the best-root reduction are theirs alone, the captured graph stays the plain frames'
   // gt-box frames too: the selection behind the back-tracking is theirs alone
-  if (h->zf_frame || h->lat_frame || h->gt_frame) return enqueue_stages(h, d_src, stride);
+  if (job.kind != FRAME_PLAIN) return enqueue_stages(h, job, r, d_src, stride);
   if (!graphable || h->frames_on_plan == 0) {
     h->frames_on_plan++;
-    return enqueue_stages(h, d_src, stride);
+    return enqueue_stages(h, job, r, d_src, stride);
   }
   const size_t row = (size_t)h->fw * h->fcn * h->fesz;
   if (d_src != h->d_img && (rc = copy_rows(h, h->d_img, d_src, (size_t)stride, row, (size_t)h->fh * h->batch, hipMemcpyDeviceToDevice))) return rc;   // (strided sources: single frames only)
   if (!h->gexec) {
     hipGraph_t graph = nullptr;
     HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    rc = enqueue_stages(h, h->d_img, (int)row);
+    rc = enqueue_stages(h, job, r, h->d_img, (int)row);
     hipError_t e = hipStreamEndCapture(h->stream, &graph);
     if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
     if (e != hipSuccess) return fail(h, PBD_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
@@ -689,8 +706,21 @@ int enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride) {
   mark_features(h, h->split_parts != 0);
   mark_responses(h);
   mark_min(h, false);
-  h->pending = true;
   return PBD_OK;
+}
+int enqueue_all(pbd_handle* h, const FrameJob& job, const uint8_t* d_src, int stride) {
+  FrameRoute r;
+  int rc = begin_pending(h, job, &r);
+  if (!rc && (rc = enqueue_routed(h, job, r, d_src, stride))) h->pf.active = false;
+  return rc;
+}
+// pbd_dp_argmin, pbd_dp_argbest: the back-tracking of the resident tables as a frame of its own; it scores nothing and computes no boxes
+static int enqueue_stage_argmin(pbd_handle* h) {
+  const FrameJob job{FRAME_STAGE};
+  FrameRoute r;
+  int rc = begin_pending(h, job, &r);
+  if (!rc && (rc = run_argmin_enqueue(h, job, r))) h->pf.active = false;
+  return rc;
 }
 
 void read_stage_times(pbd_handle* h) {
@@ -775,7 +805,7 @@ int pbd_set_levels(pbd_handle* h, const int32_t* levels, int n) {
     set[levels[i]] = 1;
   }
   if (n > 0 && set.empty()) return fail(h, PBD_ERR_ARG, "empty level set");
-  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (h->pf.active) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
   hipStreamSynchronize(h->stream);
   h->level_set.swap(set);
   free_frame(h);   // the work tables are per geometry AND level set: re-planned on the next frame
@@ -785,7 +815,7 @@ int pbd_set_levels(pbd_handle* h, const int32_t* levels, int n) {
 int pbd_set_boundary_pad(pbd_handle* h, int pad) {
   if (!h) return PBD_ERR_ARG;
   if (pad < 0 || pad > 8) return fail(h, PBD_ERR_ARG, "boundary pad: 0 (off) .. 8 cells");
-  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (h->pf.active) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
   if (pad == h->pad) return PBD_OK;
   ON_DEVICE(h);
   hipStreamSynchronize(h->stream);
@@ -798,7 +828,7 @@ int pbd_get_boundary_pad(const pbd_handle* h) { return h ? h->pad : 0; }
 int pbd_set_pyramid_kind(pbd_handle* h, int kind) {
   if (!h) return PBD_ERR_ARG;
   if (kind != PBD_PYRAMID_OPENCV && kind != PBD_PYRAMID_MATLAB) return fail(h, PBD_ERR_ARG, "pyramid kind: PBD_PYRAMID_OPENCV or PBD_PYRAMID_MATLAB");
-  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (h->pf.active) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
   if (kind == h->pyr_kind) return PBD_OK;
   ON_DEVICE(h);
   hipStreamSynchronize(h->stream);
@@ -1196,7 +1226,7 @@ int pbd_set_dp_pointers(pbd_handle* h, int level, int component, int part, int p
   HIPCHK(h, hipMemcpy(h->d_extx + eo, xs.data(), HW * 2, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->d_exty + eo, ys.data(), HW * 2, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->d_pk + eo, ks.data(), HW, hipMemcpyHostToDevice));
-  // not mark_min: tables handed in, with or without a min() of this handle behind them (min_ran, root_dirty, dp_timed keep their values)
+  // not mark_min: tables handed in, with or without a min() of this handle behind them (min_ran, root_dirty, min_timed keep their values)
   h->ext_ptr = true;
   if (h->compact) {   // d_pk is the memory of the level images + features (and the first call's d_extx / d_exty allocation moved nothing, but the
                       // Ik write above went over them): pyramid() -> set_dp_pointers -> pdf() must not run on clobbered features
@@ -1228,7 +1258,7 @@ int pbd_get_stage_state(const pbd_handle* h, int32_t state[4]) {
 static int argmin_ready(pbd_handle* h) {
   if (!h->have_dp) return fail(h, PBD_ERR_STATE, "argmin() before min()");
   if (h->batch > 1) return fail(h, PBD_ERR_STATE, "the current plan is a batch of frames: its candidates come from pbd_detect_batch_collect");
-  if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
+  if (h->pf.active) return fail(h, PBD_ERR_STATE, "previous frame not collected");
   if (!h->min_ran) {   // tables handed in by the caller only: all of them, or back-tracking would walk uninitialised planes
     if (!all_active_set(h, h->ext_set, std::max(h->nplanes, 1)) && h->nplanes > 0)
       return fail(h, PBD_ERR_STATE, "argmin(): no min() on this frame and not every pointer table has been handed in (pbd_set_dp_pointers)");
@@ -1243,16 +1273,14 @@ int pbd_dp_argmin(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int3
   int ready = argmin_ready(h);
   if (ready) return ready;
   ON_DEVICE(h);
-  h->ps_frame = h->ps_ready = false;   // (the stage entry point scores nothing: pbd_candidates_part_scores does, on its records)
-  int rc = run_argmin_enqueue(h);
-  if (rc) { h->pending = false; return rc; }
-  return collect_frame(h, heads, boxes, locs, capacity, count);
+  int rc = enqueue_stage_argmin(h);
+  return rc ? rc : collect_frame(h, heads, boxes, locs, capacity, count);
 }
 
 // ---- latent detection: the two stage entry points ----------------------------------------------------------------------------
 int pbd_latent_mask(pbd_handle* h, const int32_t* truth, const int32_t* mix, int component, double overlap, int32_t* admissible) {
   if (!h) return PBD_ERR_ARG;
-  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (h->pf.active) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
   int rc = pbd_i_latent_check(h, truth, mix, 1, component, overlap);
   if (rc) return rc;
   if (h->fw == 0) return fail(h, PBD_ERR_STATE, "no frame geometry");
@@ -1285,13 +1313,11 @@ int pbd_dp_argbest(pbd_handle* h, pbd_candidate_head* head, int32_t* boxes, int3
   if ((rc = latent_tables(h))) return rc;
   if (!h->lat_masked)   // no mask on this frame's responses: every pair counts (the unconstrained best pose)
     HIPCHK(h, hipMemsetAsync(h->d_lat_flags, 1, (size_t)h->nvl * h->md.ncomponents * h->max_parts * sizeof(int), h->stream));
-  h->ps_frame = h->ps_ready = false;
   if ((rc = run_latent_best(h))) return rc;
   h->root_dirty = false;                      // the record is the best root of the tables now on the device, whoever wrote them
-  rc = run_argmin_enqueue(h);
+  rc = enqueue_stage_argmin(h);
   h->root_dirty = true;                       // ... and a later pbd_dp_argmin thresholds them again
-  if (rc) { h->pending = false; return rc; }
-  return collect_frame(h, head, boxes, locs, 1, found);
+  return rc ? rc : collect_frame(h, head, boxes, locs, 1, found);
 }
 
 // ---- stand-alone primitives -------------------------------------------------

@@ -16,7 +16,7 @@ int copy_rows(pbd_handle* h, void* dst, const void* src, size_t src_pitch, size_
 int enter_frame(pbd_handle* h, const FrameSource& s, bool detect) {
   int rc;
   if (s.z && (rc = pbd_i_depth_check(h, s.z->type, s.z->stride, s.w))) return rc;
-  if (detect && h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
+  if (detect && h->pf.active) return fail(h, PBD_ERR_STATE, "previous frame not collected");
   const int esz = depth_esz(s.depth);
   const size_t row = (size_t)s.w * s.cn * esz;
   if (s.depth == PBD_DEPTH_8U) {
@@ -36,47 +36,39 @@ int enter_frame(pbd_handle* h, const FrameSource& s, bool detect) {
   if (!detect) return PBD_OK;
   const uint8_t* d_src = s.on_device ? (const uint8_t*)s.one : h->d_img;
   const int stride = s.on_device ? s.stride : (int)row;
-  if (s.lat) {   // latent frames: the truth tables in front of the kernels like the image; the flag lives only across the enqueue
+  // what the frame is, once: the truth tables / gt boxes / depth images go in front of the kernels like the image
+  FrameJob job;
+  if (s.lat) {
+    job.kind = FRAME_LATENT;
     if ((rc = pbd_i_latent_begin(h, *s.lat, s.nframes))) return rc;
-    h->lat_frame = true;
-    rc = enqueue_all(h, d_src, stride);
-    h->lat_frame = false;
-    return rc;
-  }
-  if (s.gt) {    // gt-box frames: the boxes in front of the kernels like the image; the flag lives only across the enqueue
+  } else if (s.gt) {
+    job.kind = FRAME_GTBOX;
     if ((rc = pbd_i_gt_begin(h, *s.gt, s.nframes))) return rc;
-    h->gt_frame = true;
-    rc = enqueue_all(h, d_src, stride);
-    h->gt_frame = false;
-    return rc;
+  } else if (s.z) {
+    const DepthSource& z = *s.z;
+    job.kind = FRAME_DEPTH;
+    job.z = {(const char*)z.p, (size_t)z.stride, z.fbytes, s.w, s.hgt, z.has};
+    if (!z.on_device) {
+      const size_t zrow = (size_t)s.w * h->ts;
+      if ((rc = model_grow(h, &h->d_zimg, h->zimg_bytes, zrow * s.hgt))) return rc;
+      if ((rc = copy_rows(h, h->d_zimg, z.p, (size_t)z.stride, zrow, (size_t)s.hgt, hipMemcpyHostToDevice))) return rc;
+      job.z.img = h->d_zimg; job.z.pitch = zrow;
+    }
   }
-  if (!s.z) return enqueue_all(h, d_src, stride);
-  const DepthSource& z = *s.z;
-  h->zf_img = (const char*)z.p; h->zf_pitch = (size_t)z.stride;
-  if (!z.on_device) {
-    const size_t zrow = (size_t)s.w * h->ts;
-    if ((rc = model_grow(h, &h->d_zimg, h->zimg_bytes, zrow * s.hgt))) return rc;
-    if ((rc = copy_rows(h, h->d_zimg, z.p, (size_t)z.stride, zrow, (size_t)s.hgt, hipMemcpyHostToDevice))) return rc;
-    h->zf_img = h->d_zimg; h->zf_pitch = zrow;
-  }
-  h->zf_fbytes = z.fbytes; h->zf_has = z.has;
-  h->zf_frame = true;   // the frame carries depth (pbd_post.cpp): the flag lives only across the enqueue
-  rc = enqueue_all(h, d_src, stride);
-  h->zf_frame = false;
-  return rc;
+  return enqueue_all(h, job, d_src, stride);
 }
 
 // ---- collect ---------------------------------------------------------------------------------------------
 // frame finished on the stream: timers, and the records beyond the first block (rare) fetched into h_cand_out.
 // `found` = the device-side count (h_cand_count[0], or the count a group gather delivered).
 int pbd_i_finish_frame(pbd_handle* h, int found) {
-  h->pending = false;
-  if (h->dp_timed && h->have_dp) {
+  h->pf.active = false;
+  if (h->pf.dp_timed && h->have_dp) {
     float ms = 0;
     if (hipEventElapsedTime(&ms, h->ev_dp0, h->ev_dp1) == hipSuccess) { h->dp_ms_sum += ms; h->dp_frames++; }
   }
   const int n = std::min(found, h->opt.max_candidates);
-  const int first = h->out_on_host ? n : std::min(h->first_copy, h->opt.max_candidates);   // (zero-copy: every record is on the host already)
+  const int first = h->pf.on_host ? n : std::min(h->first_copy, h->opt.max_candidates);   // (zero-copy: every record is on the host already)
   if (n > first) {
     HIPCHK(h, hipMemcpyAsync(h->h_cand_out + h->cand_stride * first, h->d_cand_out + h->cand_stride * first,
                              h->cand_stride * (n - first), hipMemcpyDeviceToHost, h->stream));
@@ -116,7 +108,7 @@ int pbd_i_emit(pbd_handle* h, const std::vector<const char*>& recs, pbd_candidat
   return PBD_OK;
 }
 
-int pbd_i_found(const pbd_handle* h) { return h->out_filtered ? h->h_cf_cnt[1] : h->h_cand_count[0]; }
+int pbd_i_found(const pbd_handle* h) { return h->pf.filtered ? h->h_cf_cnt[1] : h->h_cand_count[0]; }
 
 // The pending frames' records -> the caller's arrays, frame f's at heads[f * capacity], boxes[f * capacity * max_parts * 4],
 // locs[f * capacity * max_parts * 3]; counts[f] = number found in frame f.  A single frame is a batch of one.  single (pbd_detect_collect,
@@ -129,8 +121,7 @@ struct GtOut { int* found; double* o; };
 static int collect_frames(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* counts, bool single,
                           const GtOut* gt = nullptr) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (h->gt_pending) {
-    h->gt_pending = false;
+  if (h->pf.gt) {
     const int nrec = h->h_cand_count[0];
     if (counts) *counts = nrec;
     int rc = pbd_i_finish_frame(h, nrec);
@@ -139,7 +130,7 @@ static int collect_frames(pbd_handle* h, pbd_candidate_head* heads, int32_t* box
     pbd_i_gt_gather(h, heads, boxes, locs, gt->found, gt->o);
     return PBD_OK;
   }
-  const bool filt = h->out_filtered;
+  const bool filt = h->pf.filtered;
   const int found = single ? pbd_i_found(h) : filt ? h->h_cf_cnt[0] : h->h_cand_count[0];
   if (single && counts) *counts = found;
   int rc = pbd_i_finish_frame(h, found);
@@ -155,26 +146,26 @@ static int collect_frames(pbd_handle* h, pbd_candidate_head* heads, int32_t* box
     per[((const pbd_candidate_head*)r)->level / n1].push_back(r);
   }
   int status = PBD_OK;
-  if (h->b3_frame) pbd_i_b3_begin(h, B);
-  if (h->ps_frame) pbd_i_ps_begin(h, B);
+  if (h->pf.b3) pbd_i_b3_begin(h, B);
+  if (h->pf.ps) pbd_i_ps_begin(h, B);
   std::vector<int> order;
   for (int f = 0; f < B; ++f) {
     if (counts) counts[f] = (int)per[f].size();
     pbd_candidate_head* hf = heads ? heads + (size_t)f * capacity : nullptr;
     rc = pbd_i_emit(h, per[f], hf, boxes ? boxes + (size_t)f * capacity * mp * 4 : nullptr, locs ? locs + (size_t)f * capacity * mp * 3 : nullptr, capacity, filt,
-                    h->b3_frame || h->ps_frame ? &order : nullptr);
+                    h->pf.b3 || h->pf.ps ? &order : nullptr);
     if (rc == PBD_ERR_CAPACITY && !single) { status = rc; continue; }
     if (rc) return rc;
-    if (h->b3_frame) pbd_i_b3_gather(h, f, per[f], order);
-    if (h->ps_frame) pbd_i_ps_gather(h, f, per[f], order);
+    if (h->pf.b3) pbd_i_b3_gather(h, f, per[f], order);
+    if (h->pf.ps) pbd_i_ps_gather(h, f, per[f], order);
     for (size_t i = 0; f && i < per[f].size(); ++i) hf[i].level -= f * n1;   // virtual level -> the frame's own pyramid level
   }
-  if (h->b3_frame && (rc = pbd_i_b3_end(h))) return rc;
+  if (h->pf.b3 && (rc = pbd_i_b3_end(h))) return rc;
   return status;
 }
 
 int collect_frame(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* count) {
-  if (!h->pending) return fail(h, PBD_ERR_STATE, "collect without a pending detect");
+  if (!h->pf.active) return fail(h, PBD_ERR_STATE, "collect without a pending detect");
   if (h->d_gsend) return fail(h, PBD_ERR_STATE, "handle belongs to an RCCL-gathering pbd_group: collect through the group");
   if (h->batch > 1) return fail(h, PBD_ERR_STATE, "a batch of frames is pending: collect it with pbd_detect_batch_collect");
   return collect_frames(h, heads, boxes, locs, capacity, count, true);
@@ -193,7 +184,7 @@ int pbd_detect_collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes,
 }
 int pbd_detect_batch_collect(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* counts) {
   if (!h || !heads || !counts || capacity < 0) return PBD_ERR_ARG;
-  if (!h->pending) return fail(h, PBD_ERR_STATE, "collect without a pending detect");
+  if (!h->pf.active) return fail(h, PBD_ERR_STATE, "collect without a pending detect");
   if (h->d_gsend) return fail(h, PBD_ERR_STATE, "handle belongs to an RCCL-gathering pbd_group: collect through the group");
   ON_DEVICE(h);
   int rc = collect_frames(h, heads, boxes, locs, capacity, counts, false);
@@ -287,7 +278,7 @@ int pbd_detect_batch_rgbd_u8(pbd_handle* h, const uint8_t* const* ims, const voi
   if ((!h->zf_on && !h->b3_on) || !has) return pbd_detect_batch_u8(h, ims, nframes, w, hgt, cn, stride, heads, boxes, locs, capacity, counts);
   int rc = pbd_i_depth_check(h, depth_type, dstride, w);
   if (rc) return rc;
-  if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
+  if (h->pf.active) return fail(h, PBD_ERR_STATE, "previous frame not collected");
   if (!ims || nframes < 1 || nframes > 64) return fail(h, PBD_ERR_ARG, "batch: 1..64 frames");
   ON_DEVICE(h);
   const size_t zrow = (size_t)w * h->ts, fb = zrow * hgt;
@@ -302,7 +293,7 @@ int pbd_detect_batch_rgbd_u8(pbd_handle* h, const uint8_t* const* ims, const voi
 // ---- latent detection: detect(im, model, thresh, bbox, overlap) of matlab/detection/detect.m ------------------------------------
 // The plain entries with a truth set per frame: one record (or none) per frame.  Arguments are checked before anything is planned.
 static int latent_enter(pbd_handle* h, FrameSource s, const int32_t* truth, const int32_t* mix, int component, double overlap) {
-  if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
+  if (h->pf.active) return fail(h, PBD_ERR_STATE, "previous frame not collected");
   int rc = pbd_i_latent_check(h, truth, mix, s.nframes, component, overlap);
   if (rc) return rc;
   const LatentSource ls{truth, mix, component, overlap};
@@ -334,7 +325,7 @@ int pbd_detect_batch_latent_u8(pbd_handle* h, const uint8_t* const* ims, int nfr
 // come home.  Arguments and settings are checked before anything is planned.
 static int gtbox_run(pbd_handle* h, FrameSource s, const double* gt, const int* ngt, double overlap, pbd_candidate_head* heads,
                      int32_t* boxes, int32_t* locs, int* found, double* o, int* nrecords) {
-  if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
+  if (h->pf.active) return fail(h, PBD_ERR_STATE, "previous frame not collected");
   int rc = pbd_i_gt_check(h, gt, ngt, s.nframes, overlap, true);
   if (rc) return rc;
   const GtSource gs{gt, ngt, overlap};
@@ -371,7 +362,7 @@ int pbd_detect_batch_gtbox_u8(pbd_handle* h, const uint8_t* const* ims, int nfra
 // im == NULL: back to the rule.  chosen: 1 = 256 lanes / 40 KB, 2 = 128 lanes / 25 KB, 0 = nothing to choose (double handles).
 int pbd_tune_plan(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride, int batch, int* chosen, double ms[2]) {
   if (!h) return PBD_ERR_ARG;
-  if (h->pending) return fail(h, PBD_ERR_STATE, "previous frame not collected");
+  if (h->pf.active) return fail(h, PBD_ERR_STATE, "previous frame not collected");
   // (a member of an RCCL-gathering group collects through the group only: the measurement's own collect() would fail with the frame
   //  left pending — ADVICE r05)
   if (h->d_gsend) return fail(h, PBD_ERR_STATE, "handle belongs to an RCCL-gathering pbd_group: tune a handle of its own");
@@ -381,7 +372,7 @@ int pbd_tune_plan(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int 
   ON_DEVICE(h);
   // the plan is dropped as a whole (buffers, stage flags, captured graph): a stage getter after pbd_tune_plan answers "no frame
   // geometry" AND the stage flags say so — nothing can run on the last measured geometry
-  auto drop_plan = [&]() { if (h->stream) hipStreamSynchronize(h->stream); h->pending = false; free_frame(h); };
+  auto drop_plan = [&]() { if (h->stream) hipStreamSynchronize(h->stream); h->pf.active = false; free_frame(h); };
   if (!im) { h->dt_geom = 0; drop_plan(); return PBD_OK; }
   if (h->ts != 4) return PBD_OK;
   if (batch < 1 || batch > 64) return fail(h, PBD_ERR_ARG, "batch: 1..64 frames");

@@ -142,10 +142,10 @@ static const char* rec_ptr(const pbd_group* g, int i, int j) {
 static void drain(pbd_group* g) {
   for (size_t i = 0; i < g->m.size(); ++i) {
     pbd_handle* h = g->m[i];
-    if (!h->pending) continue;
+    if (!h->pf.active) continue;
     hipSetDevice(g->dev[i]);
     hipStreamSynchronize(h->stream);
-    h->pending = false;
+    h->pf.active = false;
   }
   (void)hipGetLastError();
 }
@@ -261,7 +261,7 @@ int pbd_group_set_candidate_filter(pbd_group* g, int mode, float overlap) {
   if (!(mode == PBD_CAND_RAW || mode == PBD_CAND_SORT || mode == PBD_CAND_SORT_NMS) || !std::isfinite(overlap))
     return gfail(g, PBD_ERR_ARG, "candidate filter: mode PBD_CAND_RAW / _SORT / _SORT_NMS, finite overlap");
   for (pbd_handle* h : g->m)
-    if (h->pending) return gfail(g, PBD_ERR_STATE, "a frame is in flight");
+    if (h->pf.active) return gfail(g, PBD_ERR_STATE, "a frame is in flight");
   for (size_t i = 0; i < g->m.size(); ++i) {
     pbd_handle* h = g->m[i];
     if ((mode != h->cand_mode || overlap != h->cand_overlap) && h->gexec) {
@@ -280,7 +280,7 @@ int pbd_group_set_candidate_nms(pbd_group* g, int kind, int top) {
   if (!g) return PBD_ERR_ARG;
   if ((kind != PBD_NMS_PAINTED && kind != PBD_NMS_PARTS) || top < 0) return gfail(g, PBD_ERR_ARG, "candidate NMS: kind PBD_NMS_PAINTED / _PARTS, top >= 0");
   for (pbd_handle* h : g->m)
-    if (h->pending) return gfail(g, PBD_ERR_STATE, "a frame is in flight");
+    if (h->pf.active) return gfail(g, PBD_ERR_STATE, "a frame is in flight");
   for (size_t i = 0; i < g->m.size(); ++i) {
     pbd_handle* h = g->m[i];
     if ((kind != h->cand_nms || top != h->cand_top) && h->gexec) {
@@ -299,7 +299,7 @@ int pbd_group_set_boundary_pad(pbd_group* g, int pad) {
   if (!g) return PBD_ERR_ARG;
   if (pad < 0 || pad > 8) return gfail(g, PBD_ERR_ARG, "boundary pad: 0 (off) .. 8 cells");
   for (pbd_handle* h : g->m)
-    if (h->pending) return gfail(g, PBD_ERR_STATE, "a frame is in flight");
+    if (h->pf.active) return gfail(g, PBD_ERR_STATE, "a frame is in flight");
   for (size_t i = 0; i < g->m.size(); ++i) GMEMBER(g, i, pbd_set_boundary_pad(g->m[i], pad));
   return PBD_OK;   // (a level sharding of pbd_group_detect_u8 stays: the padding changes the levels' cell counts, not which levels there are)
 }
@@ -347,7 +347,7 @@ static int batch_impl(pbd_group* g, const uint8_t* const* ims, int nframes, int 
     std::vector<const char*> recs((size_t)g->found[i]);
     for (int j = 0; j < g->found[i]; ++j) recs[j] = rec_ptr(g, i, j);
     int r = pbd_i_emit(g->m[i], recs, heads + (size_t)f * capacity, boxes ? boxes + (size_t)f * capacity * mp * 4 : nullptr,
-                       locs ? locs + (size_t)f * capacity * mp * 3 : nullptr, capacity, g->m[i]->out_filtered);
+                       locs ? locs + (size_t)f * capacity * mp * 3 : nullptr, capacity, g->m[i]->pf.filtered);
     if (r == PBD_ERR_CAPACITY) { status = gfail(g, r, "frame " + std::to_string(f) + ": output capacity too small"); return PBD_OK; }
     if (r) return gfail(g, r, pbd_last_error(g->m[i]));
     return PBD_OK;

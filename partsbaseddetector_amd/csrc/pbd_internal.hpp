@@ -22,6 +22,7 @@
 
 #include "pbd_plan.hpp"
 #include "pbd_lds.hpp"
+#include "pbd_route.hpp"
 
 #ifndef PBD_ARGMIN_ZERO_COPY
 #define PBD_ARGMIN_ZERO_COPY 1   // k_backtrack writes candidates straight to the pinned host buffers (handles outside RCCL groups)
@@ -71,10 +72,6 @@ struct RecordSet {
   const int* count; int capacity;
   const int* cf; int nframes;   // non-null: k_cand_filter's counts; frame f's records at [cf[2+nf+f], +cf[2+f])
   int nlevels;                  // else frame of a record = level / nlevels (0: one frame)
-};
-// Frame f's depth image (element type T) at img + f * fbytes, w x h, rows pitch bytes apart; has: frames that carry depth (bit f)
-struct DepthFrames {
-  const char* img; size_t pitch, fbytes; int w, h; unsigned long long has;
 };
 #ifdef __HIPCC__
 // the frame record i belongs to; -1: none (filtered output beyond every frame's kept records)
@@ -206,9 +203,8 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   // candidates
   int* d_cand_count = nullptr; CandRec* d_cand_rec = nullptr;
   char* d_cand_out = nullptr; char* h_cand_out = nullptr; int* h_cand_count = nullptr;
-  bool out_on_host = false;                          // the last back-tracking wrote its records straight into h_cand_out (run_argmin_enqueue)
   size_t cand_stride = 0;
-  bool pending = false;
+  PendingFrame pf;           // the frame in flight (pbd_route.hpp): assigned whole by begin_pending (pbd_api.cpp), once per enqueue; everyone else flips pf.active
   int first_copy = 0;        // candidate records copied back together with the count (records): starts at PBD_FIRST_COPY per frame of the
                              // plan and grows to 1.25 x the largest count seen, so that the steady state is ONE D2H and no second sync
   char* d_gsend = nullptr;   // set by an RCCL-gathering pbd_group: {count, pad to 16 B, first records} block sent by ncclAllGather
@@ -220,7 +216,7 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   float stage_ms[6] = {0, 0, 0, 0, 0, 0};
   float warp_ms[3] = {0, 0, 0};      // the last warped-positives call while profiling: resample passes, HOG, write (pbd_debug_warp_ms)
   hipEvent_t ev_dp0 = nullptr, ev_dp1 = nullptr;
-  double dp_ms_sum = 0; int dp_frames = 0; bool dp_timer_on = true; bool dp_timed = false;   // DP events are recorded only while profiling
+  double dp_ms_sum = 0; int dp_frames = 0; bool dp_timer_on = true; bool min_timed = false;   // DP events are recorded only while profiling; min_timed: the last min() recorded them
   hipGraphExec_t gexec = nullptr;   // pbd_options.graph: the frame's launches, captured once per geometry
   int frames_on_plan = 0;           // frames enqueued since the last plan_frame
   std::vector<void*> frame_allocs;  // everything freed on re-plan
@@ -237,7 +233,6 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   int cand_mode = PBD_CAND_RAW; float cand_overlap = 0.f;
   bool in_group = false;     // member of a pbd_group: the group sets the filter
   bool cand_defer = false;   // member of a level-sharded pbd_group_detect_u8: unfiltered, the group filters the union on member 0
-  bool out_filtered = false; // the pending frame's records went through k_cand_filter (counts in h_cf_cnt / d_cf_cnt)
   char* d_cand_raw = nullptr;                           // back-tracking output of RCCL-gathering members when filtering
   unsigned long long* d_cf_keys = nullptr; unsigned* d_cf_idx = nullptr; int* d_cf_box = nullptr; uint8_t* d_cf_st = nullptr;
   // k_cand_filter's counts, B = frames of the plan: [0] the back-tracking's device count (all frames, before the filter), [1] kept in frame 0
@@ -253,8 +248,6 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   // depth-consistency pruning (pbd_set_depth_filter): k_zfilter.hip behind k_backtrack.  Named z* / zf*: d_depth and max_depth
   // above are the part tree's depth.  Allocated on the first depth-carrying frame with the setting on.
   bool zf_on = false; float zf_factor = 0.f;
-  bool zf_frame = false;            // the frame being enqueued carries depth (set by enter_frame around enqueue_all for a FrameSource with depth images)
-  const char* zf_img = nullptr; size_t zf_pitch = 0, zf_fbytes = 0; unsigned long long zf_has = 0;   // that frame's depth images
   int* d_zf_npart = nullptr; int* d_zf_par = nullptr; double* d_zf_thr = nullptr; float zf_thr_factor = 0.f;   // [ncomp], [ncomp * mp] x 2
   unsigned long long* d_zf_med = nullptr; unsigned* d_zf_large = nullptr;   // [capacity * mp] each
   int* d_zf_cnt = nullptr;          // [0] kept records, [1] boxes listed for k_zmed_large
@@ -263,15 +256,12 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   // 3-D boxes (pbd_set_box3d): k_box3d.hip behind the depth pruning and the candidate filter of depth-carrying frames.  Results
   // land in pinned host buffers indexed by record slot; the collect reorders them like the records it returns.
   bool b3_on = false; pbd_camera b3_cam{};
-  bool b3_frame = false;            // the pending frame computes boxes (its depth frames: zf_has)
-  unsigned long long b3_has = 0;
   pbd_box3d* h_b3 = nullptr; double* h_b3c = nullptr;   // [capacity], [capacity * mp * 3]: pinned
   bool b3_ready = false;            // results of the last collected frame, per frame in the order returned
   std::vector<std::vector<pbd_box3d>> b3_res; std::vector<std::vector<double>> b3_cen; std::vector<char> b3_res_on;
   // object clusters (pbd_set_cluster3d): k_cluster3d.hip right behind k_box3d.  Results per record slot (pinned); the kept
   // clusters' indices in a device pool claimed per record, gathered (and overflowing records run again) by the collect.
   bool cl3_on = false; float cl3_tol = 0.01f;
-  bool cl3_frame = false;           // the pending frame computes clusters (the frames of b3_has)
   Cl3Res* h_cl3 = nullptr;           // [capacity]: pinned
   char* d_cl3_scratch = nullptr; int cl3_slots = 0, cl3_pcap = 0;
   int* d_cl3_pool = nullptr; unsigned long long cl3_pool_cap = 0; unsigned long long* d_cl3_used = nullptr;
@@ -282,8 +272,6 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   // per-part scores (pbd_set_part_scores): k_partscore.hip behind the depth pruning and the candidate filter of EVERY frame (plain
   // and depth-carrying, eager and captured).  Results per record slot (pinned); the collect reorders them like the records.
   bool ps_on = false;
-  bool ps_frame = false;            // the pending frame computes them (setting on, and a plan that keeps the raw response planes)
-  bool ps_compact = false;          // ... it did not because the plan is the compact one (pbd_get_part_scores names it)
   struct PsMix* d_ps_mix = nullptr; int* d_ps_mix0 = nullptr;   // [flat mixtures], [flat parts + 1]: the model tables of k_partscore
   double* h_ps = nullptr;           // [capacity * mp * 3]: pinned
   bool ps_ready = false;            // results of the last collected frame, per frame in the order returned
@@ -296,7 +284,6 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   // latent detection (pbd_latent_mask / pbd_dp_argbest / pbd_detect_latent_*): k_latent.hip between pdf and min, and in front of the
   // back-tracking.  The work table, the flags and the block partials belong to the frame plan (built on the first latent use of a
   // plan); the truth / mixture tables are model-lifetime buffers, uploaded per frame in the frame's stream.
-  bool lat_frame = false;           // the frame being enqueued is a latent one (set by enter_frame around enqueue_all)
   bool lat_masked = false;          // the resident responses carry a mask and d_lat_flags its flags (until responses are produced again)
   int lat_component = -1; double lat_overlap = 0.0; bool lat_has_mix = false;
   LatJob* d_lat_jobs = nullptr; ReduceBlock* d_lat_blocks = nullptr; int n_lat_blocks = 0;
@@ -304,8 +291,6 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   int* d_lat_truth = nullptr; int* h_lat_truth = nullptr;   // [PBD_MAX_BATCH][max_parts][5]: 4 box ints per part of every frame, then the mixtures; h_: pinned
   // best pose per ground-truth box (pbd_detect_gtbox_*): k_gtbox.hip behind k_backtrack, which then writes into d_cand_out.  The planes
   // and the tables are model-lifetime buffers (first use); the winners' records, found and o land in pinned memory, slot f * PBD_GT_MAX + g.
-  bool gt_frame = false;            // the frame being enqueued is a gt-box one (set by enter_frame around enqueue_all)
-  bool gt_pending = false;          // ... and is the pending one: the collect returns the winners, not the records
   int gt_max = 0; double gt_overlap = 0.0;   // the largest ngt of the frame's or batch's frames
   double4* d_gt_cbox = nullptr; unsigned* d_gt_key = nullptr; unsigned long long* d_gt_rank = nullptr; int* d_gt_frame = nullptr;   // [capacity]
   double* d_gt = nullptr; double* h_gt = nullptr;   // [PBD_MAX_BATCH][PBD_GT_MAX][4], then the frames' ngt as ints; h_: pinned staging
@@ -454,7 +439,7 @@ int collect_frame(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int3
 // the plan and the stages (pbd_api.cpp)
 int plan_frame(pbd_handle* h, int w, int hgt, int cn, int batch = 1, int depth = PBD_DEPTH_8U);   // the frame plan of one geometry, kept while it repeats
 void free_frame(pbd_handle* h);                                             // drops the plan: buffers, stage state, captured graph
-int enqueue_all(pbd_handle* h, const uint8_t* d_src, int stride);           // all stages + argmin (+ post-stages), eager or as one graph launch
+int enqueue_all(pbd_handle* h, const FrameJob& job, const uint8_t* d_src, int stride);   // all stages + argmin (+ post-stages), eager or as one graph launch
 void read_stage_times(pbd_handle* h);
 int pbd_i_finish_frame(pbd_handle* h, int found);
 int pbd_i_emit(pbd_handle* h, const std::vector<const char*>& recs, pbd_candidate_head* heads, int32_t* boxes,
@@ -465,22 +450,26 @@ int pbd_i_emit(pbd_handle* h, const std::vector<const char*>& recs, pbd_candidat
 int pbd_i_latent_check(pbd_handle* h, const int32_t* truth, const int32_t* mix, int nframes, int component, double overlap);
 int pbd_i_latent_begin(pbd_handle* h, const LatentSource& s, int nframes);
 // best pose per ground-truth box (pbd_post.cpp): the argument checks of every entry (gt boxes of nframes frames; whole: the handle's
-// settings too), the buffers + the upload of the boxes in the handle's stream, the launch behind k_backtrack (records in `raw`), and
+// settings too), the buffers + the upload of the boxes in the handle's stream, the launch behind k_backtrack (records in the route's bt.out), and
 // the collect's copy of the winners: frame f's at heads[f * PBD_GT_MAX] etc., levels made the frame's own
 int pbd_i_gt_check(pbd_handle* h, const double* gt, const int* ngt, int nframes, double overlap, bool whole);
 int pbd_i_gt_begin(pbd_handle* h, const GtSource& s, int nframes);
-int pbd_i_gt_enqueue(pbd_handle* h, char* raw);
+int pbd_i_gt_enqueue(pbd_handle* h, const FrameRoute& r);
 void pbd_i_gt_gather(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int* found, double* o);
 int pbd_i_found(const pbd_handle* h);   // records the pending frame left on the host side (filtered: the kept count)
 #define PBD_FIRST_COPY 192   // candidate records fetched (or gathered) together with the count
 
 // ---- the post-stages behind back-tracking (pbd_post.cpp) ----------------------------------
 inline int pbd_i_cand_mode(const pbd_handle* h) { return h->cand_defer ? PBD_CAND_RAW : h->cand_mode; }   // the filter this handle runs
-int pbd_i_post_buffers(pbd_handle* h);   // enqueue_all, outside any capture: the frame's post-stage flags and buffers
-// behind launch_backtrack (into `raw`): depth pruning and / or the candidate filter (mode cm) into the output buffers
-int pbd_i_post_enqueue(pbd_handle* h, int cm, bool zf, char* raw);
-int pbd_i_run_box3d(pbd_handle* h);      // 3-D boxes (+ object clusters) of the frame's final records
-int pbd_i_run_part_scores(pbd_handle* h);   // per-part scores of the frame's final records
+// the handle's buffers behind the names of a route (pbd_route.hpp; the route itself: enqueue_all, pbd_api.cpp)
+char* pbd_i_route_buf(const pbd_handle* h, RouteBuf b);
+int* pbd_i_route_count(const pbd_handle* h, RouteCount c);
+RecordSet pbd_i_route_records(const pbd_handle* h, RouteBuf b, RouteCount c);   // the records in b, counted by c, as a kernel reads them
+int pbd_i_post_buffers(pbd_handle* h, const FrameRoute& r);   // enqueue_all, outside any capture: the buffers of the route's post-stages
+// behind launch_backtrack: the launches of the route's depth pruning and / or candidate filter
+int pbd_i_post_enqueue(pbd_handle* h, const FrameJob& job, const FrameRoute& r);
+int pbd_i_run_box3d(pbd_handle* h, const FrameJob& job, const FrameRoute& r);   // 3-D boxes (+ object clusters) of the frame's final records
+int pbd_i_run_part_scores(pbd_handle* h, const FrameRoute& r);   // per-part scores of the frame's final records
 void pbd_i_ps_begin(pbd_handle* h, int nframes);   // the collect: each frame's part scores in the order returned, like the 3-D boxes
 void pbd_i_ps_gather(pbd_handle* h, int f, const std::vector<const char*>& recs, const std::vector<int>& order);
 // the collect: each frame's 3-D boxes in the order returned (recs[order[i]]), then the clusters of the frames gathered
@@ -571,12 +560,19 @@ void launch_root(const RootJob* jobs, const ReduceBlock* blocks, int nblocks, do
                  int capacity, int ts, const FoldJob* folds, const float* biasw, int rescan, int fm, const uint8_t* nms_mask,
                  const char* rootv_base, hipStream_t s);
 void launch_nms_roots(const RootJob* jobs, int njobs, unsigned maxcells, const char* rootv_base, int ts, int sz, uint8_t* mask, hipStream_t s);
-void launch_backtrack(const int* count, const CandRec* rec, int capacity, const BackLevel* back, int ncomp,
-                      const int* parent, const int* plane0, const int* nparts, int max_parts, const int* mix_rows,
-                      char* out, size_t out_stride, int ts, const int* flat, const int* depth, int max_depth, int nflat,
-                      const unsigned long long* scr_base, const void* ix, const void* iy, int ptr_bytes, int correct_ptr,   // ix / iy: the DT's own planes, ptr_bytes wide (FrameLayout::ptr_bytes)
-                      const int16_t* extx, const int16_t* exty, const unsigned long long* ext_base, int* count_out, int pad,   // pad: the boundary padding (box origin)
-                      const FoldJob* folds, const unsigned long long* pick, hipStream_t s);   // pick != null: Ik picked from the fold's kept scores (fold_pick.hpp), not read from planes
+struct BacktrackArgs {   // (k_backtrack's own parameters keep their order: its first eight are preloaded)
+  const int* count; const CandRec* rec; int capacity;
+  const BackLevel* back; int ncomp;
+  const int* parent; const int* plane0; const int* nparts; int max_parts; const int* mix_rows;
+  char* out; size_t out_stride;
+  const int* flat; const int* depth; int max_depth, nflat;
+  const unsigned long long* scr_base;
+  const void* ix; const void* iy; int ptr_bytes, correct_ptr;   // ix / iy: the DT's own planes, ptr_bytes wide (FrameLayout::ptr_bytes)
+  const int16_t* extx; const int16_t* exty; const unsigned long long* ext_base;
+  int* count_out; int pad;      // pad: the boundary padding (box origin)
+  const FoldJob* folds; const unsigned long long* pick;   // pick != null: Ik picked from the fold's kept scores (fold_pick.hpp), not read from planes
+};
+void launch_backtrack(const BacktrackArgs& a, int ts, hipStream_t s);
 // fold plans: the Ik planes written from the children's kept scores (k_dp.hip: k_ik_fill); blocks: {index into pick / cells, first cell}
 void launch_ik_fill(const FoldJob* folds, const unsigned long long* pick, const ReduceBlock* blocks, int nblocks, const unsigned* cells, int ts, hipStream_t s);
 // latent detection (k_latent.hip): the overlap mask of every response plane; the best root over the admissible (level, component) pairs

@@ -367,7 +367,7 @@ static int fv_begin(pbd_handle* h, const pbd_candidate_head* heads, const int32_
   if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "feature vectors: pbd_group members are not supported");
   if (ts && ts != h->ts) return fail(h, PBD_ERR_STATE, ts == 4 ? "handle is PartsBasedDetector<double>: use the _f64 entry point"
                                                                : "handle is PartsBasedDetector<float>: use the float entry point");
-  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (h->pf.active) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
   if (h->fw == 0) return fail(h, PBD_ERR_STATE, "feature vectors: no frame planned");
   if (!h->have_feat) return fail(h, PBD_ERR_STATE, h->compact ? kFvCompact : "feature vectors: features not computed");
   int rc = check_records(h, heads, locs, count);
@@ -487,19 +487,15 @@ int pbd_i_gt_begin(pbd_handle* h, const GtSource& s, int nframes) {
   h->gt_overlap = s.overlap;
   return PBD_OK;
 }
-// behind launch_backtrack (into `raw`, a device list): the selection, its results straight into pinned memory; the records' count follows
+// behind launch_backtrack (into a device list): the selection, its results straight into pinned memory; the records' count follows
 // by a copy (the collect refuses an overflowed list: the selection would be incomplete)
-int pbd_i_gt_enqueue(pbd_handle* h, char* raw) {
+int pbd_i_gt_enqueue(pbd_handle* h, const FrameRoute& r) {
   GtBoxArgs a = gt_args(h, h->batch, h->gt_overlap);
-  a.in.p = raw; a.in.count = h->d_cand_count; a.in.capacity = h->opt.max_candidates; a.in.nlevels = h->nlevels;
+  a.in = pbd_i_route_records(h, r.bt.out, r.bt.out_count);
   a.gt = h->d_gt; a.ngt = (const int*)(h->d_gt + (size_t)PBD_MAX_BATCH * PBD_GT_MAX * 4);
   a.cbox = h->d_gt_cbox; a.key = h->d_gt_key; a.rank = h->d_gt_rank; a.frame = h->d_gt_frame;
   a.out = h->h_gt_out; a.found = h->h_gt_found; a.o = h->h_gt_o;
   launch_gtbox(a, h->gt_max, h->stream);
-  LAUNCHCHK(h, "argmin + gt boxes");
-  HIPCHK(h, hipMemcpyAsync(h->h_cand_count, h->d_cand_count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  h->pending = true; h->gt_pending = true;
-  h->out_on_host = true;   // (nothing of the records themselves is fetched)
   return PBD_OK;
 }
 // the collect (stream synchronised, the list did not overflow): the winners of every frame -> the caller's arrays
@@ -519,105 +515,95 @@ void pbd_i_gt_gather(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, i
 }
 
 // ---- behind the back-tracking ---------------------------------------------------------------------------------------------
-// the frame's final records (behind the depth pruning and the candidate filter), where the launches behind them read them
-static RecordSet final_records(const pbd_handle* h) {
+// the handle's buffers behind the route's names (pbd_route.hpp)
+char* pbd_i_route_buf(const pbd_handle* h, RouteBuf b) {
+  switch (b) {
+    case HOST_OUT: return h->h_cand_out;
+    case DEV_OUT: return h->d_cand_out;
+    case DEV_RAW: return h->d_cand_raw;
+    case DEV_ZF: return h->d_zf_out;
+    case DEV_CP_STAGE: return h->d_cp_stage;
+    case BUF_NONE: break;
+  }
+  return nullptr;
+}
+int* pbd_i_route_count(const pbd_handle* h, RouteCount c) {
+  switch (c) {
+    case CNT_DEV: return h->d_cand_count;
+    case CNT_DEV_ZF: return h->d_zf_cnt;
+    case CNT_HOST_CF: return h->h_cf_cnt;
+    case CNT_DEV_CF: return h->d_cf_cnt;
+    case CNT_DEV_CP: return h->d_cp_cnt;
+    case CNT_NONE: break;
+  }
+  return nullptr;
+}
+RecordSet pbd_i_route_records(const pbd_handle* h, RouteBuf b, RouteCount c) {
   RecordSet in{};
-  in.stride = h->cand_stride; in.mp = h->max_parts; in.capacity = h->opt.max_candidates;
+  in.p = pbd_i_route_buf(h, b); in.stride = h->cand_stride; in.mp = h->max_parts;
+  in.count = pbd_i_route_count(h, c); in.capacity = h->opt.max_candidates;
   in.nlevels = h->nlevels;
-  if (h->out_filtered) { in.p = h->h_cand_out; in.cf = h->h_cf_cnt; in.count = h->h_cf_cnt; in.nframes = h->batch; }
-  else if (h->zf_frame && h->zf_on) { in.p = h->h_cand_out; in.count = h->d_zf_cnt; }
-  else { in.p = (PBD_ARGMIN_ZERO_COPY && !h->d_gsend) ? h->h_cand_out : h->d_cand_out; in.count = h->d_cand_count; }
+  if (route_cf_block(c)) { in.cf = in.count; in.nframes = h->batch; }
   return in;
 }
 
-int pbd_i_post_buffers(pbd_handle* h) {
-  const int cm = pbd_i_cand_mode(h);
-  if (cm != PBD_CAND_RAW) {
-    int rc = cand_filter_buffers(h, cm == PBD_CAND_SORT_NMS && !parts_nms(h, cm));
-    if (!rc && parts_nms(h, cm)) rc = cand_parts_buffers(h);
-    if (rc) return rc;
+int pbd_i_post_buffers(pbd_handle* h, const FrameRoute& r) {
+  int rc = PBD_OK;
+  if (r.filter.on) {
+    rc = cand_filter_buffers(h, r.filter_mode == PBD_CAND_SORT_NMS);
+    if (!rc && r.parts.on) rc = cand_parts_buffers(h);
   }
-  h->out_filtered = cm != PBD_CAND_RAW;   // (a replayed graph does not pass through pbd_i_post_enqueue)
-  h->b3_ready = false; h->cl3_ready = false;
-  h->b3_frame = h->zf_frame && h->b3_on;
-  h->cl3_frame = h->b3_frame && h->cl3_on;
-  h->b3_has = h->b3_frame ? h->zf_has : 0;
-  h->ps_ready = false;
-  h->ps_compact = h->ps_on && h->compact;   // (the stale planes are never read: the step is skipped and the getter says why)
-  h->ps_frame = h->ps_on && !h->compact;
-  if (h->ps_frame) {
-    int rc = ps_buffers(h);
-    if (rc) return rc;
-  }
-  if (!h->zf_frame) return PBD_OK;
-  int rc = h->zf_on ? zf_buffers(h) : PBD_OK;
-  if (!rc && h->b3_frame) rc = b3_buffers(h);
-  if (!rc && h->cl3_frame) rc = cl3_buffers(h);
+  if (!rc && r.pending.ps) rc = ps_buffers(h);
+  if (!rc && r.zf.on) rc = zf_buffers(h);
+  if (!rc && r.pending.b3) rc = b3_buffers(h);
+  if (!rc && r.pending.cl3) rc = cl3_buffers(h);
   return rc;
 }
 
-int pbd_i_post_enqueue(pbd_handle* h, int cm, bool zf, char* raw) {
-  const bool dev_out = h->d_gsend != nullptr;   // member of an RCCL-gathering group (never a depth-pruning handle)
-  RecordSet in{};
-  in.p = raw; in.stride = h->cand_stride; in.mp = h->max_parts; in.count = h->d_cand_count; in.capacity = h->opt.max_candidates;
-  in.nlevels = h->nlevels;
-  if (zf) {
+int pbd_i_post_enqueue(pbd_handle* h, const FrameJob& job, const FrameRoute& r) {
+  if (r.zf.on) {
     // depth pruning: k_zfilter writes the kept records straight into the pinned host buffers (the count follows by a copy), or into
     // the buffer k_cand_filter then sorts (and suppresses) as usual
     HIPCHK(h, hipMemsetAsync(h->d_zf_cnt, 0, sizeof(int) * 2, h->stream));
     ZFilterArgs z{};
-    z.in = in;
-    z.z.img = h->zf_img; z.z.pitch = h->zf_pitch; z.z.fbytes = h->zf_fbytes; z.z.w = h->fw; z.z.h = h->fh; z.z.has = h->zf_has;
+    z.in = pbd_i_route_records(h, r.zf.in, r.zf.in_count);
+    z.z = job.z;
     z.npart = h->d_zf_npart; z.par = h->d_zf_par; z.thr = h->d_zf_thr;
-    z.med = h->d_zf_med; z.large = h->d_zf_large; z.nlarge = (unsigned*)(h->d_zf_cnt + 1); z.cnt = h->d_zf_cnt;
-    z.out = h->out_filtered ? h->d_zf_out : h->h_cand_out;
+    z.med = h->d_zf_med; z.large = h->d_zf_large; z.nlarge = (unsigned*)(h->d_zf_cnt + 1);
+    z.out = pbd_i_route_buf(h, r.zf.out); z.cnt = pbd_i_route_count(h, r.zf.out_count);
     launch_zfilter(z, h->ts, h->stream);
-    if (!h->out_filtered) HIPCHK(h, hipMemcpyAsync(h->h_cand_count, h->d_zf_cnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    in.p = h->d_zf_out; in.count = h->d_zf_cnt;
   }
-  if (h->out_filtered) {
+  if (r.filter.on) {
     // Candidate::sort (+ nonMaximaSuppression): k_cand_filter writes the kept records in final order + the per-frame counts — straight
     // into the pinned host buffers, or, for a member of an RCCL-gathering group, into the device buffer the all-gather block is packed from
     // With the part-wise NMS the kernel only sorts, into the staging buffer, and k_cand_parts writes what it would have written
-    const bool parts = parts_nms(h, cm);
-    CandFilterArgs a = cand_args(h, parts ? PBD_CAND_SORT : cm, h->cand_overlap, h->fw, h->fh);
-    a.in = in;
+    CandFilterArgs a = cand_args(h, r.filter_mode, h->cand_overlap, h->fw, h->fh);
+    a.in = pbd_i_route_records(h, r.filter.in, r.filter.in_count);
     a.back = h->d_back; a.rootv_base = h->d_rootv; a.gmask = h->d_cf_mask;
-    a.out = dev_out ? h->d_cand_out : h->h_cand_out;
-    a.cnt_out = dev_out ? h->d_cf_cnt : h->h_cf_cnt;
-    if (parts) {
-      CandPartsArgs p = cand_parts_args(h, h->cand_overlap, h->cand_top, h->opt.max_candidates);
-      p.in = h->d_cp_stage; p.cnt_in = h->d_cp_cnt;
-      p.rect = h->d_cp_rect; p.np = h->d_cp_np; p.kept = h->d_cp_kept; p.gbits = h->d_cp_bits;
-      p.out = a.out; p.cnt_out = a.cnt_out;
-      a.out = h->d_cp_stage; a.cnt_out = h->d_cp_cnt;
-      launch_cand_filter(a, h->batch, h->stream);
-      launch_cand_parts(p, h->batch, h->stream);
-    } else
+    a.out = pbd_i_route_buf(h, r.filter.out); a.cnt_out = pbd_i_route_count(h, r.filter.out_count);
     launch_cand_filter(a, h->batch, h->stream);
+    if (r.parts.on) {
+      CandPartsArgs p = cand_parts_args(h, h->cand_overlap, h->cand_top, h->opt.max_candidates);
+      p.in = pbd_i_route_buf(h, r.parts.in); p.cnt_in = pbd_i_route_count(h, r.parts.in_count);
+      p.rect = h->d_cp_rect; p.np = h->d_cp_np; p.kept = h->d_cp_kept; p.gbits = h->d_cp_bits;
+      p.out = pbd_i_route_buf(h, r.parts.out); p.cnt_out = pbd_i_route_count(h, r.parts.out_count);
+      launch_cand_parts(p, h->batch, h->stream);
+    }
   }
-  LAUNCHCHK(h, zf ? "argmin + depth filter" : "argmin + candidate filter");
-  h->pending = true;
-  h->out_on_host = !dev_out;
-  if (!dev_out) return PBD_OK;
-  h->first_copy = PBD_FIRST_COPY * h->batch;
-  const int first = std::min(h->first_copy, h->opt.max_candidates);
-  HIPCHK(h, hipMemcpyAsync(h->d_gsend, h->d_cf_cnt + 1, sizeof(int), hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->d_gsend + 16, h->d_cand_out, h->cand_stride * first, hipMemcpyDeviceToDevice, h->stream));
   return PBD_OK;
 }
 
 // the frame's final records (behind the depth pruning and the candidate filter) -> one box per record slot, pinned
-int pbd_i_run_box3d(pbd_handle* h) {
+int pbd_i_run_box3d(pbd_handle* h, const FrameJob& job, const FrameRoute& r) {
   Box3dArgs a{};
-  a.in = final_records(h);
-  a.z.img = h->zf_img; a.z.pitch = h->zf_pitch; a.z.fbytes = h->zf_fbytes; a.z.w = h->fw; a.z.h = h->fh; a.z.has = h->b3_has;
+  a.in = pbd_i_route_records(h, r.final_buf, r.final_count);
+  a.z = job.z;
   a.im_w = h->fw; a.im_h = h->fh; a.cam = h->b3_cam;
   b3_taps(a);
   a.out = h->h_b3; a.centres = h->h_b3c;
   launch_box3d(a, h->ts, h->stream);
   LAUNCHCHK(h, "box3d");
-  if (h->cl3_frame) {   // the object clusters of the same records, right behind
+  if (r.pending.cl3) {   // the object clusters of the same records, right behind
     Cluster3dArgs c{};
     c.in = a.in; c.z = a.z; c.pstride = h->ts;
     c.boxes = h->h_b3;
@@ -633,9 +619,9 @@ int pbd_i_run_box3d(pbd_handle* h) {
 }
 
 // the frame's final records -> three doubles per part and record slot, pinned
-int pbd_i_run_part_scores(pbd_handle* h) {
+int pbd_i_run_part_scores(pbd_handle* h, const FrameRoute& r) {
   PartScoreArgs a = ps_args(h);
-  a.in = final_records(h);
+  a.in = pbd_i_route_records(h, r.final_buf, r.final_count);
   a.out = h->h_ps;
   launch_partscore(a, h->ts, h->stream);
   LAUNCHCHK(h, "part scores");
@@ -665,7 +651,7 @@ void pbd_i_b3_begin(pbd_handle* h, int nframes) {
   h->cl3_res_on.assign((size_t)nframes, 0);
 }
 void pbd_i_b3_gather(pbd_handle* h, int f, const std::vector<const char*>& recs, const std::vector<int>& order) {
-  if (!((h->b3_has >> f) & 1ull)) return;
+  if (!((h->pf.b3_has >> f) & 1ull)) return;
   const size_t n = recs.size(), m3 = (size_t)h->max_parts * 3;
   std::vector<pbd_box3d>& o = h->b3_res[f];
   std::vector<double>& c = h->b3_cen[f];
@@ -674,13 +660,13 @@ void pbd_i_b3_gather(pbd_handle* h, int f, const std::vector<const char*>& recs,
     const size_t slot = (size_t)(recs[order[i]] - h->h_cand_out) / h->cand_stride;
     o[i] = h->h_b3[slot];
     memcpy(c.data() + i * m3, h->h_b3c + slot * m3, sizeof(double) * m3);
-    if (h->cl3_frame) h->cl3_slot[f].push_back((int)slot);
+    if (h->pf.cl3) h->cl3_slot[f].push_back((int)slot);
   }
   h->b3_res_on[f] = 1;
 }
 // the object clusters of the frames pbd_i_b3_gather listed (the collect synchronised the stream)
 int pbd_i_b3_end(pbd_handle* h) {
-  if (!h->cl3_frame) return PBD_OK;
+  if (!h->pf.cl3) return PBD_OK;
   std::vector<int> lst;
   const int nf = (int)h->cl3_slot.size();
   for (int f = 0; f < nf; ++f)
@@ -854,7 +840,7 @@ int pbd_set_candidate_filter(pbd_handle* h, int mode, float overlap) {
   if (!h) return PBD_ERR_ARG;
   if (!cand_mode_ok(mode, overlap)) return fail(h, PBD_ERR_ARG, "candidate filter: mode PBD_CAND_RAW / _SORT / _SORT_NMS, finite overlap");
   if (h->in_group) return fail(h, PBD_ERR_STATE, "handle belongs to a pbd_group: set the filter on the group");
-  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (h->pf.active) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
   if ((mode != h->cand_mode || overlap != h->cand_overlap) && h->gexec) {   // the filter's launch (or its absence) is part of a captured graph
     ON_DEVICE(h);
     drop_graph(h);
@@ -868,7 +854,7 @@ int pbd_set_candidate_nms(pbd_handle* h, int kind, int top) {
   if (!h) return PBD_ERR_ARG;
   if ((kind != PBD_NMS_PAINTED && kind != PBD_NMS_PARTS) || top < 0) return fail(h, PBD_ERR_ARG, "candidate NMS: kind PBD_NMS_PAINTED / _PARTS, top >= 0");
   if (h->in_group) return fail(h, PBD_ERR_STATE, "handle belongs to a pbd_group: set the NMS on the group");
-  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (h->pf.active) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
   if ((kind != h->cand_nms || top != h->cand_top) && h->gexec) {   // which kernels run behind the sort is part of a captured graph
     ON_DEVICE(h);
     drop_graph(h);
@@ -926,7 +912,7 @@ int pbd_set_depth_filter(pbd_handle* h, int on, float zfactor) {
   if (!h) return PBD_ERR_ARG;
   if (!std::isfinite(zfactor)) return fail(h, PBD_ERR_ARG, "depth filter: zfactor must be finite");
   if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "depth filter: pbd_group members are not supported (detect through a handle of its own)");
-  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (h->pf.active) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
   h->zf_on = on != 0;      // (depth-carrying frames never replay a captured graph: nothing captured depends on the setting)
   h->zf_factor = zfactor;
   return PBD_OK;
@@ -986,7 +972,7 @@ int pbd_set_box3d(pbd_handle* h, int on, const pbd_camera* cam) {
   if (!h) return PBD_ERR_ARG;
   if (on && !b3_cam_ok(cam)) return fail(h, PBD_ERR_ARG, "box3d: a camera with finite intrinsics and nonzero fx, fy");
   if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "box3d: pbd_group members are not supported (detect through a handle of its own)");
-  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (h->pf.active) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
   h->b3_on = on != 0;
   if (on) h->b3_cam = *cam;
   return PBD_OK;
@@ -995,7 +981,7 @@ int pbd_set_box3d(pbd_handle* h, int on, const pbd_camera* cam) {
 int pbd_get_box3d(pbd_handle* h, int frame, pbd_box3d* out, double* centres, int capacity, int* count) {
   if (!h || !count || capacity < 0 || (capacity > 0 && !out)) return PBD_ERR_ARG;
   if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "box3d: pbd_group members are not supported");
-  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (h->pf.active) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
   if (!h->b3_ready || frame < 0 || frame >= (int)h->b3_res_on.size() || !h->b3_res_on[frame])
     return fail(h, PBD_ERR_STATE, "box3d: the last frame did not compute 3-D boxes for this frame (plain entry point, setting off, or no depth)");
   const std::vector<pbd_box3d>& r = h->b3_res[frame];
@@ -1055,7 +1041,7 @@ int pbd_set_cluster3d(pbd_handle* h, int on, float tolerance) {
   if (!h) return PBD_ERR_ARG;
   if (on && !cl3_tol_ok(tolerance)) return fail(h, PBD_ERR_ARG, "cluster3d: a finite tolerance > 0");
   if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "cluster3d: pbd_group members are not supported (detect through a handle of its own)");
-  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (h->pf.active) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
   h->cl3_on = on != 0;
   if (on) h->cl3_tol = tolerance;
   return PBD_OK;
@@ -1074,7 +1060,7 @@ int pbd_get_cluster3d(pbd_handle* h, int frame, pbd_cluster3d* out, int capacity
                       int* idx_total) {
   if (!h || !count || capacity < 0 || (capacity > 0 && !out) || (indices && (idx_capacity < 0 || !idx_total))) return PBD_ERR_ARG;
   if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "cluster3d: pbd_group members are not supported");
-  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (h->pf.active) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
   if (!h->cl3_ready || frame < 0 || frame >= (int)h->cl3_res_on.size() || !h->cl3_res_on[frame])
     return fail(h, PBD_ERR_STATE, "cluster3d: the last frame did not compute object clusters for this frame (plain entry point, "
                                   "3-D boxes or clusters off, or no depth)");
@@ -1137,21 +1123,21 @@ int pbd_candidates_cluster3d(pbd_handle* h, const void* cloud, int cw, int ch, i
 int pbd_set_part_scores(pbd_handle* h, int on) {
   if (!h) return PBD_ERR_ARG;
   if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "part scores: pbd_group members are not supported (detect through a handle of its own)");
-  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (h->pf.active) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
   if ((on != 0) != h->ps_on && h->gexec) {   // the step's launch (or its absence) is part of a captured graph
     ON_DEVICE(h);
     drop_graph(h);
   }
   h->ps_on = on != 0;
-  if (!h->ps_on) h->ps_ready = h->ps_compact = false;
+  if (!h->ps_on) h->ps_ready = h->pf.ps_compact = false;   // (no frame is pending: the getter's answer follows the setting)
   return PBD_OK;
 }
 
 int pbd_get_part_scores(pbd_handle* h, int frame, pbd_part_score* out, int capacity, int* count) {
   if (!h || !count || capacity < 0 || (capacity > 0 && !out)) return PBD_ERR_ARG;
   if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "part scores: pbd_group members are not supported");
-  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
-  if (h->ps_compact) return fail(h, PBD_ERR_UNSUPPORTED, kPsCompact);
+  if (h->pf.active) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (h->pf.ps_compact) return fail(h, PBD_ERR_UNSUPPORTED, kPsCompact);
   if (!h->ps_ready || frame < 0 || frame >= (int)h->ps_res_on.size() || !h->ps_res_on[frame])
     return fail(h, PBD_ERR_STATE, "part scores: the last frame did not compute them for this frame (setting off, a stage entry point, or a frame out of range)");
   const std::vector<double>& r = h->ps_res[frame];
@@ -1167,7 +1153,7 @@ int pbd_candidates_part_scores(pbd_handle* h, const pbd_candidate_head* heads, c
   if (!h) return PBD_ERR_ARG;
   if (count < 0 || (count > 0 && (!heads || !locs || !out))) return fail(h, PBD_ERR_ARG, "heads / locs / out / count");
   if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "part scores: pbd_group members are not supported");
-  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (h->pf.active) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
   if (h->fw == 0) return fail(h, PBD_ERR_STATE, "part scores: no frame planned");
   if (!h->have_resp) return fail(h, PBD_ERR_STATE, h->compact ? kPsCompact : "part scores: responses not computed");
   const int mp = h->max_parts;
@@ -1252,7 +1238,7 @@ int pbd_candidates_select_gt(pbd_handle* h, const double* gt, int ngt, double ov
     if (!std::isfinite(heads[i].score)) return fail(h, PBD_ERR_ARG, "non-finite score: its order is undefined");
     if (heads[i].nparts < 0 || heads[i].nparts > h->max_parts) return fail(h, PBD_ERR_ARG, "nparts outside 0..max_parts");
   }
-  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (h->pf.active) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
   for (int g = 0; g < ngt; ++g) { best[g] = -1; o[g] = 0.0; }
   if (ngt == 0 || count == 0) return PBD_OK;
   ON_DEVICE(h);

@@ -42,7 +42,7 @@ int warp_check(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int str
   if (n < 0 || (n > 0 && !boxes)) return fail(h, PBD_ERR_ARG, "warped positives: boxes / n");
   if ((long long)stride * hgt >= (1ll << 31)) return fail(h, PBD_ERR_UNSUPPORTED, "warped positives: the frame has 2^31 bytes or more");
   if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "warped positives: pbd_group members are not supported");
-  if (h->pending) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (h->pf.active) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
   if (filter < 0 || filter >= h->md.nfilters) return fail(h, PBD_ERR_ARG, "warped positives: filter outside [0, nfilters)");
   int32_t kh, kw;
   pbd_get_filter_size(h, filter, &kh, &kw);

@@ -254,6 +254,47 @@ def test_single_frame_paths(gpu_required, person, dtype):
     h.close()
 
 
+@pytest.mark.parametrize("clusters", [False, True], ids=["box3d", "cluster3d"])
+def test_stage_entry_after_rgbd_frame_computes_no_boxes(gpu_required, person, clusters):
+    """pbd_dp_argmin on the plan an RGB-D frame left: a frame of its own that computes neither boxes nor clusters, so the getters
+    answer PBD_ERR_STATE (include/pbd_c.h) instead of the RGB-D frame's results mapped onto other records; its records are a fresh
+    handle's staged ones; the next RGB-D frame on the handle returns the first one's boxes again, in bits"""
+    im = make_image(1, W, H)
+    depth = scene(1, W, H)
+    h = capi.Handle(person)
+    h.set_box3d(True, CAM)
+    if clusters:
+        h.set_cluster3d(True)
+    res = h.detect_rgbd(im, depth)
+    assert len(res[0]) > 20
+    boxes = assert_frame(h, res, depth, what="first")
+    centres = h.get_box3d(0)[1]
+    cl = h.get_cluster3d(0) if clusters else None
+    staged = h.dp_argmin()
+    assert state_error(h)
+    if clusters:
+        with pytest.raises(capi.PbdError) as e:
+            h.get_cluster3d(0)
+        assert e.value.code == capi.PBD_ERR_STATE
+    fresh = capi.Handle(person)
+    fresh.pyramid(im); fresh.pdf(); fresh.dp_min()
+    exp = fresh.dp_argmin()
+    fresh.close()
+    assert len(staged[0]) == len(exp[0]) == len(res[0])
+    for k in range(3):
+        assert np.asarray(staged[k]).tobytes() == np.asarray(exp[k]).tobytes(), k
+    again = h.detect_rgbd(im, depth)
+    for k in range(3):
+        assert np.asarray(again[k]).tobytes() == np.asarray(res[k]).tobytes(), k
+    b2, c2 = h.get_box3d(0)
+    assert_boxes(b2, boxes, "again")
+    assert same_float(c2, centres) and all(same_float(b2[f], boxes[f]) for f in FIELDS)
+    if clusters:
+        cl2 = h.get_cluster3d(0)
+        assert all(same_float(cl2[0][f], cl[0][f]) for f in cl[0].dtype.names) and np.array_equal(cl2[1], cl[1])
+    h.close()
+
+
 @pytest.mark.parametrize("graph", [0, 1])
 @pytest.mark.parametrize("nb", [1, 4])
 def test_batches(gpu_required, person, graph, nb):

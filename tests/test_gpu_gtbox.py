@@ -220,6 +220,34 @@ def test_plain_frames_on_a_graph_handle_are_untouched(gpu_required, orc, frame):
     hd.close()
 
 
+@pytest.mark.parametrize("special", ["gtbox_raw", "rgbd_filtered"])
+def test_replayed_plain_frame_after_an_eager_special_frame(gpu_required, orc, frame, special):
+    """graph=1: plain frame (eager), plain frame (captured), one eager special frame — gt-box on a RAW handle, RGB-D with depth pruning
+    on a filtered one —, then a plain frame replayed from the graph: what the collect is told about the pending frame is the replayed
+    frame's own, not what the special frame left, so its records are the first plain frame's, in bits"""
+    model, im, _, gts = frame
+    hd = capi.Handle(model, graph=1, max_candidates=8192)
+    if special == "rgbd_filtered":
+        hd.set_candidate_filter(capi.PBD_CAND_SORT)      # (every record kept, in Candidate::sort's order: the frame stays a few hundred records)
+        hd.set_depth_filter(True, 0.03)
+    first = hd.detect(im, 8192)
+    captured = hd.detect(im, 8192)
+    assert len(first[0]) > 20
+    if special == "gtbox_raw":
+        got = hd.detect_gtbox(im, gts, OVERLAP)
+        _assert_winners(got, first, gts, what=special)
+    else:
+        depth = (2.0 + 0.001 * np.arange(W, dtype=np.float32))[None, :].repeat(H, 0)
+        depth[::7, ::5] = 0.0
+        pruned = hd.detect_rgbd(im, depth, 8192)
+        assert 0 < len(pruned[0]) <= len(first[0])
+    last = hd.detect(im, 8192)
+    for other in (captured, last):
+        for k in range(3):
+            assert np.asarray(other[k]).tobytes() == np.asarray(first[k]).tobytes(), (special, k)
+    hd.close()
+
+
 def test_refusals_and_capacity(gpu_required, orc, frame):
     model, im, _, gts = frame
     hd = capi.Handle(model, conv_mode=capi.PBD_CONV_EXACT, max_candidates=8192)
