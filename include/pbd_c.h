@@ -225,7 +225,12 @@ int pbd_set_stream(pbd_handle* h, void* hip_stream);
 
 /* PartsBasedDetector<T>::detect(im, candidates) (src/PartsBasedDetector.cpp:69-95).
  * `im` is a host pointer to an 8-bit image, cn = 1 or 3 (BGR interleaved),
- * stride in bytes.  Candidates are written in the order of a single-threaded
+ * stride in bytes.  Rows and strides, for every image `stride` and depth-image `dstride` of this header (host and device alike):
+ * row y starts at im + y * stride; only its first w * cn * element size bytes are read, so the bytes between rows may
+ * hold anything (an ROI of a larger frame, a pitched allocation) and the last row needs no padding: the buffer may end
+ * with the last pixel.  The base pointer needs no alignment beyond the element's.  stride < w * cn * element size (a
+ * negative one included), or one that is not a multiple of the element size, is PBD_ERR_ARG and leaves no frame pending.
+ * Candidates are written in the order of a single-threaded
  * reference run (level, component, row-major root location); at most
  * `capacity`; *count = number found (PBD_ERR_CAPACITY if > capacity).
  * heads[capacity], boxes[capacity][max_parts][4], locs[capacity][max_parts][3]

@@ -193,6 +193,45 @@ def _p(a, ct):
     return None if a is None else a.ctypes.data_as(C.POINTER(ct))
 
 
+def _strided_ok(a) -> bool:
+    """an HxW or HxWxcn array whose rows the library can read in place: dense inner axes, rows strides[0] >= w * cn * itemsize bytes
+    apart (a multiple of the itemsize).  An ROI of a larger frame, a pitched buffer and a contiguous array all are."""
+    if a.ndim not in (2, 3):
+        return False
+    isz = a.itemsize
+    cn = 1 if a.ndim == 2 else a.shape[2]
+    if a.strides[-1] != isz or (a.ndim == 3 and a.strides[1] != cn * isz):
+        return False
+    return a.strides[0] >= a.shape[1] * cn * isz and a.strides[0] % isz == 0
+
+
+def _frame(im, dtype=np.uint8):
+    """(array, w, hgt, cn, stride in bytes) of an HxW or HxWxcn frame; dtype=None: the array's own.  A strided view (_strided_ok) of the
+    right dtype is passed as it is — pointer array.ctypes.data, stride strides[0]; only the first w * cn * itemsize bytes of a row are
+    read —, anything else is copied contiguous.  A contiguous array gives stride w * cn * itemsize."""
+    a = np.asarray(im)
+    if (dtype is not None and a.dtype != np.dtype(dtype)) or a.flags["C_CONTIGUOUS"] or not _strided_ok(a):
+        a = np.ascontiguousarray(im, dtype)
+    hgt, w = a.shape[:2]
+    cn = 1 if a.ndim == 2 else a.shape[2]
+    return a, w, hgt, cn, (w * cn * a.itemsize if a.flags["C_CONTIGUOUS"] else a.strides[0])
+
+
+def _frames(frames, dtype=np.uint8):
+    """([arrays], stride) of the frames of a batch, which share one stride argument: strided views are passed as they are only when
+    all frames have one strides[0], else every frame is copied contiguous"""
+    fr = [_frame(f, dtype) for f in frames]
+    if len({f[4] for f in fr}) > 1:
+        fr = [_frame(np.ascontiguousarray(f[0]), dtype) for f in fr]
+    return [f[0] for f in fr], (fr[0][4] if fr else 0)
+
+
+def _depth_image(depth, dtype):
+    """(array, stride in bytes) of an HxW depth image of element type dtype, by _frame's rule"""
+    a, _, _, _, stride = _frame(depth, dtype)
+    return a, stride
+
+
 class Handle:
     """Owns one pbd_handle (one GPU, one stream)."""
 
@@ -284,21 +323,19 @@ class Handle:
         return np.dtype(np.float64 if self._f64 else np.float32)
 
     def _zimg(self, depth, dtype=None):
-        """(array, PBD_DEPTH_*, stride in bytes) of a 2-D depth image; dtype=None: the handle's T"""
+        """(array, PBD_DEPTH_*, stride in bytes) of a 2-D depth image (a strided view is passed as it is); dtype=None: the handle's T"""
         if depth is None:
             return None, DEPTH_OF[self.depth_dtype], 0
-        d = np.ascontiguousarray(depth, dtype if dtype is not None else self.depth_dtype)
-        return d, DEPTH_OF.get(d.dtype, 7), d.shape[1] * d.itemsize
+        d, ds = _depth_image(depth, dtype if dtype is not None else self.depth_dtype)
+        return d, DEPTH_OF.get(d.dtype, 7), ds
 
     def detect_rgbd(self, im: np.ndarray, depth, capacity=4096, depth_dtype=None):
         """pbd_detect_rgbd_u8: depth = an HxW array (converted to T unless depth_dtype is given), or None"""
-        im = np.ascontiguousarray(im, np.uint8)
-        hgt, w = im.shape[:2]
-        cn = 1 if im.ndim == 2 else im.shape[2]
+        im, w, hgt, cn, stride = _frame(im)
         d, dt, ds = self._zimg(depth, depth_dtype)
         heads, boxes, locs = self._bufs(capacity)
         cnt = C.c_int(0)
-        self._chk(self.L.pbd_detect_rgbd_u8(self.h, _p(im, C.c_uint8), w, hgt, cn, w * cn,
+        self._chk(self.L.pbd_detect_rgbd_u8(self.h, _p(im, C.c_uint8), w, hgt, cn, stride,
                                             None if d is None else d.ctypes.data_as(C.c_void_p), dt, ds,
                                             heads.ctypes.data_as(C.c_void_p), _p(boxes, C.c_int32), _p(locs, C.c_int32),
                                             capacity, C.byref(cnt)))
@@ -312,7 +349,7 @@ class Handle:
 
     def detect_batch_rgbd(self, frames, depths, capacity=4096, depth_dtype=None):
         """pbd_detect_batch_rgbd_u8: depths[f] an HxW array or None"""
-        frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+        frames, stride = _frames(frames)
         if not frames or len(depths) != len(frames) or any(f.shape != frames[0].shape for f in frames):
             raise ValueError("detect_batch_rgbd: one depth (or None) per frame, frames of one shape")
         hgt, w = frames[0].shape[:2]
@@ -321,10 +358,13 @@ class Handle:
         if any(z[0] is not None and z[0].shape != (hgt, w) for z in zs):
             raise ValueError("detect_batch_rgbd: depth images of the frames' size")
         dt = next((z[1] for z in zs if z[0] is not None), DEPTH_OF[self.depth_dtype])
+        if len({z[2] for z in zs if z[0] is not None}) > 1:   # one dstride for the batch: views of different strides are copied
+            zs = [z if z[0] is None else self._zimg(np.ascontiguousarray(z[0]), depth_dtype) for z in zs]
+        ds = next((z[2] for z in zs if z[0] is not None), w * np.dtype(self.depth_dtype if depth_dtype is None else depth_dtype).itemsize)
         ptrs = (C.c_void_p * len(frames))(*[f.ctypes.data for f in frames])
         dptrs = (C.c_void_p * len(frames))(*[None if z[0] is None else z[0].ctypes.data for z in zs])
         return self._batch_out(len(frames), capacity, lambda hd, bx, lc, cnt: self.L.pbd_detect_batch_rgbd_u8(
-            self.h, ptrs, dptrs, len(frames), w, hgt, cn, w * cn, dt, w * np.dtype(self.depth_dtype if depth_dtype is None else depth_dtype).itemsize,
+            self.h, ptrs, dptrs, len(frames), w, hgt, cn, stride, dt, ds,
             hd, bx, lc, capacity, cnt))
 
     def enqueue_batch_rgbd_dev(self, dptr: int, d_depths: int, nframes, w, hgt, cn, depth_type=None):
@@ -553,12 +593,10 @@ class Handle:
         return heads[:n].copy(), boxes[:n].copy(), locs[:n].copy()
 
     def detect(self, im: np.ndarray, capacity=4096):
-        im = np.ascontiguousarray(im, np.uint8)
-        hgt, w = im.shape[:2]
-        cn = 1 if im.ndim == 2 else im.shape[2]
+        im, w, hgt, cn, stride = _frame(im)
         heads, boxes, locs = self._bufs(capacity)
         cnt = C.c_int(0)
-        self._chk(self.L.pbd_detect_u8(self.h, _p(im, C.c_uint8), w, hgt, cn, w * cn,
+        self._chk(self.L.pbd_detect_u8(self.h, _p(im, C.c_uint8), w, hgt, cn, stride,
                                        heads.ctypes.data_as(C.c_void_p), _p(boxes, C.c_int32), _p(locs, C.c_int32),
                                        capacity, C.byref(cnt)))
         return self._out(heads, boxes, locs, cnt.value)
@@ -566,13 +604,11 @@ class Handle:
     def detect_image(self, im: np.ndarray, capacity=4096):
         """pbd_detect_image: the image in its own depth (uint8 / uint16 / float32 / float64 = CV_8U / 16U / 32F / 64F); other dtypes are refused
         by the library the way the reference refuses them (CV_Error(StsUnsupportedFormat))"""
-        im = np.ascontiguousarray(im)
-        hgt, w = im.shape[:2]
-        cn = 1 if im.ndim == 2 else im.shape[2]
+        im, w, hgt, cn, stride = _frame(im, None)
         depth = DEPTH_OF.get(im.dtype, 1 if im.dtype == np.int8 else 3 if im.dtype == np.int16 else 4 if im.dtype == np.int32 else 7)
         heads, boxes, locs = self._bufs(capacity)
         cnt = C.c_int(0)
-        self._chk(self.L.pbd_detect_image(self.h, im.ctypes.data_as(C.c_void_p), depth, w, hgt, cn, w * cn * im.itemsize,
+        self._chk(self.L.pbd_detect_image(self.h, im.ctypes.data_as(C.c_void_p), depth, w, hgt, cn, stride,
                                           heads.ctypes.data_as(C.c_void_p), _p(boxes, C.c_int32), _p(locs, C.c_int32),
                                           capacity, C.byref(cnt)))
         return self._out(heads, boxes, locs, cnt.value)
@@ -584,10 +620,8 @@ class Handle:
         if im is None:
             self._chk(self.L.pbd_tune_plan(self.h, None, 0, 0, 0, 0, 1, C.byref(chosen), ms))
             return 0, [0.0, 0.0]
-        im = np.ascontiguousarray(im, np.uint8)
-        hgt, w = im.shape[:2]
-        cn = 1 if im.ndim == 2 else im.shape[2]
-        self._chk(self.L.pbd_tune_plan(self.h, _p(im, C.c_uint8), w, hgt, cn, w * cn, int(batch), C.byref(chosen), ms))
+        im, w, hgt, cn, stride = _frame(im)
+        self._chk(self.L.pbd_tune_plan(self.h, _p(im, C.c_uint8), w, hgt, cn, stride, int(batch), C.byref(chosen), ms))
         return chosen.value, [ms[0], ms[1]]
 
     def detect_dev(self, dptr: int, w, hgt, cn, stride=None, capacity=4096):
@@ -603,12 +637,11 @@ class Handle:
 
     def enqueue(self, im: np.ndarray):
         """pbd_detect_enqueue_u8: asynchronous H2D of a host image (pinned for true asynchrony) + all kernels.
-        The array must stay alive until collect()."""
-        hgt, w = im.shape[:2]
-        cn = 1 if im.ndim == 2 else im.shape[2]
-        assert im.dtype == np.uint8 and im.flags["C_CONTIGUOUS"]
+        The array (contiguous, or a strided view as _frame passes it) must stay alive until collect()."""
+        assert im.dtype == np.uint8 and (im.flags["C_CONTIGUOUS"] or _strided_ok(im))   # read in place: never a copy
+        im, w, hgt, cn, stride = _frame(im)
         self._inflight_im = im
-        self._chk(self.L.pbd_detect_enqueue_u8(self.h, C.c_void_p(im.ctypes.data), w, hgt, cn, w * cn))
+        self._chk(self.L.pbd_detect_enqueue_u8(self.h, C.c_void_p(im.ctypes.data), w, hgt, cn, stride))
 
     def enqueue_host_ptr(self, ptr: int, w, hgt, cn, stride=None):
         """same from a raw host pointer (e.g. a torch pinned tensor's data_ptr())."""
@@ -624,7 +657,7 @@ class Handle:
     # ---- a batch of same-sized frames through this handle ------------------------------------
     def detect_batch(self, frames, capacity=4096):
         """pbd_detect_batch_u8: list of HxWxC uint8 frames -> list of (heads, boxes, locs), one per frame."""
-        frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+        frames, stride = _frames(frames)
         if not frames:
             raise ValueError("detect_batch: at least one frame")
         if any(f.shape != frames[0].shape for f in frames):   # the C side reads w * hgt * cn bytes behind every pointer
@@ -634,18 +667,18 @@ class Handle:
         cn = 1 if frames[0].ndim == 2 else frames[0].shape[2]
         ptrs = (C.c_void_p * len(frames))(*[f.ctypes.data for f in frames])
         return self._batch_out(len(frames), capacity, lambda hd, bx, lc, cnt: self.L.pbd_detect_batch_u8(
-            self.h, ptrs, len(frames), w, hgt, cn, w * cn, hd, bx, lc, capacity, cnt))
+            self.h, ptrs, len(frames), w, hgt, cn, stride, hd, bx, lc, capacity, cnt))
 
     def enqueue_batch_dev(self, dptr: int, nframes, w, hgt, cn):
         """frames back to back in device memory (tightly packed); collect with collect_batch"""
         self._nb = nframes
         self._chk(self.L.pbd_detect_batch_enqueue_dev_u8(self.h, C.c_void_p(dptr), nframes, w, hgt, cn))
 
-    def enqueue_batch_host_ptrs(self, ptrs, w, hgt, cn):
-        """host frames (raw pointers, e.g. pinned torch tensors); collect with collect_batch"""
+    def enqueue_batch_host_ptrs(self, ptrs, w, hgt, cn, stride=None):
+        """host frames (raw pointers, e.g. pinned torch tensors; one stride for all); collect with collect_batch"""
         self._nb = len(ptrs)
         arr = (C.c_void_p * len(ptrs))(*ptrs)
-        self._chk(self.L.pbd_detect_batch_enqueue_u8(self.h, arr, len(ptrs), w, hgt, cn, w * cn))
+        self._chk(self.L.pbd_detect_batch_enqueue_u8(self.h, arr, len(ptrs), w, hgt, cn, stride or w * cn))
 
     def collect_batch(self, capacity=4096):
         return self._batch_out(self._nb, capacity, lambda hd, bx, lc, cnt: self.L.pbd_detect_batch_collect(self.h, hd, bx, lc, capacity, cnt))
@@ -683,20 +716,16 @@ class Handle:
         self._cn = cn
 
     def pyramid(self, im: np.ndarray):
-        im = np.ascontiguousarray(im, np.uint8)
-        hgt, w = im.shape[:2]
-        cn = 1 if im.ndim == 2 else im.shape[2]
-        self._chk(self.L.pbd_pyramid_u8(self.h, _p(im, C.c_uint8), w, hgt, cn, w * cn))
+        im, w, hgt, cn, stride = _frame(im)
+        self._chk(self.L.pbd_pyramid_u8(self.h, _p(im, C.c_uint8), w, hgt, cn, stride))
         self._geo = self.geometry(w, hgt)
         self._cn = cn
         self._imdtype = np.dtype(np.uint8)
 
     def pyramid_image(self, im: np.ndarray):
         """pbd_pyramid_image: pyramid() for an image of any accepted depth (its numpy dtype)"""
-        im = np.ascontiguousarray(im)
-        hgt, w = im.shape[:2]
-        cn = 1 if im.ndim == 2 else im.shape[2]
-        self._chk(self.L.pbd_pyramid_image(self.h, im.ctypes.data_as(C.c_void_p), DEPTH_OF[im.dtype], w, hgt, cn, w * cn * im.itemsize))
+        im, w, hgt, cn, stride = _frame(im, None)
+        self._chk(self.L.pbd_pyramid_image(self.h, im.ctypes.data_as(C.c_void_p), DEPTH_OF[im.dtype], w, hgt, cn, stride))
         self._geo = self.geometry(w, hgt)
         self._cn = cn
         self._imdtype = im.dtype
@@ -836,13 +865,11 @@ class Handle:
 
     def detect_latent(self, im: np.ndarray, truth, overlap, mix=None, component=-1):
         """pbd_detect_latent_u8: (heads, boxes, locs) holding the best pose whose parts overlap `truth`, or none"""
-        im = np.ascontiguousarray(im, np.uint8)
-        hgt, w = im.shape[:2]
-        cn = 1 if im.ndim == 2 else im.shape[2]
+        im, w, hgt, cn, stride = _frame(im)
         tr, mx = self._latent_args(truth, mix)
         heads, boxes, locs = self._bufs(1)
         found = C.c_int(0)
-        self._chk(self.L.pbd_detect_latent_u8(self.h, _p(im, C.c_uint8), w, hgt, cn, w * cn, _p(tr, C.c_int32), _p(mx, C.c_int32),
+        self._chk(self.L.pbd_detect_latent_u8(self.h, _p(im, C.c_uint8), w, hgt, cn, stride, _p(tr, C.c_int32), _p(mx, C.c_int32),
                                               int(component), C.c_double(overlap), heads.ctypes.data_as(C.c_void_p),
                                               _p(boxes, C.c_int32), _p(locs, C.c_int32), C.byref(found)))
         return self._out(heads, boxes, locs, found.value)
@@ -860,7 +887,7 @@ class Handle:
 
     def detect_batch_latent(self, frames, truths, overlap, mixes=None, component=-1):
         """pbd_detect_batch_latent_u8: a truth set (and mixture set) per frame -> list of (heads, boxes, locs), one record or none each"""
-        frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+        frames, stride = _frames(frames)
         if not frames or len(truths) != len(frames) or any(f.shape != frames[0].shape for f in frames):
             raise ValueError("detect_batch_latent: one truth set per frame, frames of one shape")
         hgt, w = frames[0].shape[:2]
@@ -869,7 +896,7 @@ class Handle:
                                    None if mixes is None else np.stack([np.asarray(m, np.int32) for m in mixes]), len(frames))
         ptrs = (C.c_void_p * len(frames))(*[f.ctypes.data for f in frames])
         return self._batch_out(len(frames), 1, lambda hd, bx, lc, cnt: self.L.pbd_detect_batch_latent_u8(
-            self.h, ptrs, len(frames), w, hgt, cn, w * cn, _p(tr, C.c_int32), _p(mx, C.c_int32), int(component),
+            self.h, ptrs, len(frames), w, hgt, cn, stride, _p(tr, C.c_int32), _p(mx, C.c_int32), int(component),
             C.c_double(overlap), hd, bx, lc, cnt))
 
     # ---- best pose per ground-truth box (matlab/detection/testmodel_gtbox.m, bestoverlap.m) -------------------------------
@@ -891,13 +918,11 @@ class Handle:
     def detect_gtbox(self, im: np.ndarray, gt, overlap=0.3):
         """pbd_detect_gtbox_u8: per gt box (x1, y1, x2, y2) the best pose of the frame on it -> (heads, boxes, locs, found, o), one
         slot per box (zeros where found is 0); self.gt_records = the frame's records in front of the selection"""
-        im = np.ascontiguousarray(im, np.uint8)
-        hgt, w = im.shape[:2]
-        cn = 1 if im.ndim == 2 else im.shape[2]
+        im, w, hgt, cn, stride = _frame(im)
         gt = np.ascontiguousarray(gt, np.float64).reshape(-1, 4)
         heads, boxes, locs, found, o = self._gt_out(len(gt))
         nrec = C.c_int(0)
-        rc = self.L.pbd_detect_gtbox_u8(self.h, _p(im, C.c_uint8), w, hgt, cn, w * cn, _p(gt, C.c_double), len(gt), C.c_double(overlap),
+        rc = self.L.pbd_detect_gtbox_u8(self.h, _p(im, C.c_uint8), w, hgt, cn, stride, _p(gt, C.c_double), len(gt), C.c_double(overlap),
                                         heads.ctypes.data_as(C.c_void_p), _p(boxes, C.c_int32), _p(locs, C.c_int32),
                                         _p(found, C.c_int32), _p(o, C.c_double), C.byref(nrec))
         self.gt_records = nrec.value
@@ -919,7 +944,7 @@ class Handle:
     def detect_batch_gtbox(self, frames, gts, overlap=0.3):
         """pbd_detect_batch_gtbox_u8: the gt boxes of every frame (any number up to PBD_GT_MAX, also none) -> per frame what
         detect_gtbox returns"""
-        frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+        frames, stride = _frames(frames)
         if not frames or len(gts) != len(frames) or any(f.shape != frames[0].shape for f in frames):
             raise ValueError("detect_batch_gtbox: one set of gt boxes per frame, frames of one shape")
         gts = [np.asarray(g, np.float64).reshape(-1, 4) for g in gts]
@@ -935,7 +960,7 @@ class Handle:
         heads, boxes, locs, found, o = self._gt_out(nb * PBD_GT_MAX)
         ptrs = (C.c_void_p * nb)(*[f.ctypes.data for f in frames])
         nrec = C.c_int(0)
-        rc = self.L.pbd_detect_batch_gtbox_u8(self.h, ptrs, nb, w, hgt, cn, w * cn, _p(gt, C.c_double), _p(ngt, C.c_int32),
+        rc = self.L.pbd_detect_batch_gtbox_u8(self.h, ptrs, nb, w, hgt, cn, stride, _p(gt, C.c_double), _p(ngt, C.c_int32),
                                               C.c_double(overlap), heads.ctypes.data_as(C.c_void_p), _p(boxes, C.c_int32),
                                               _p(locs, C.c_int32), _p(found, C.c_int32), _p(o, C.c_double), C.byref(nrec))
         self.gt_records = nrec.value
@@ -953,22 +978,18 @@ class Handle:
         return out, ix, iy
 
     def hog(self, im: np.ndarray):
-        im = np.ascontiguousarray(im, np.uint8)
-        hgt, w = im.shape[:2]
-        cn = 1 if im.ndim == 2 else im.shape[2]
+        im, w, hgt, cn, stride = _frame(im)
         sb = self.model.sbin
         buf = np.zeros((hgt // sb + 2) * (w // sb + 2) * 32, self.dtype)
         a, b = C.c_int(0), C.c_int(0)
-        self._chk(self._fn("pbd_hog_u8")(self.h, _p(im, C.c_uint8), w, hgt, cn, w * cn, _p(buf, self._ct), C.byref(a),
+        self._chk(self._fn("pbd_hog_u8")(self.h, _p(im, C.c_uint8), w, hgt, cn, stride, _p(buf, self._ct), C.byref(a),
                                          C.byref(b)))
         return buf[: b.value * a.value * 32].reshape(b.value, a.value, 32).copy()
 
     def resize(self, im: np.ndarray, ow, oh):
-        im = np.ascontiguousarray(im, np.uint8)
-        hgt, w = im.shape[:2]
-        cn = 1 if im.ndim == 2 else im.shape[2]
+        im, w, hgt, cn, stride = _frame(im)
         out = np.zeros((oh, ow) + ((cn,) if cn > 1 else ()), np.uint8)
-        self._chk(self.L.pbd_resize_u8(self.h, _p(im, C.c_uint8), w, hgt, cn, w * cn, _p(out, C.c_uint8), ow, oh))
+        self._chk(self.L.pbd_resize_u8(self.h, _p(im, C.c_uint8), w, hgt, cn, stride, _p(out, C.c_uint8), ow, oh))
         return out
 
     def resize_area(self, im: np.ndarray, scale):
@@ -995,13 +1016,13 @@ class Handle:
     def warp_windows(self, im: np.ndarray, boxes, filter: int):
         """pbd_warp_windows_u8[_f64]: warppos.m's windows of the boxes ((x1, y1, x2, y2), 1-based inclusive) for filter `filter` and
         their HOG -> (windows [n, oh, ow, 3] float64, features [n, kh, kw, 32] of the handle's dtype)"""
-        im, w, hgt, cn = _frame_u8(im)
+        im, w, hgt, cn, stride = _frame(im)
         boxes = np.ascontiguousarray(boxes, np.float64).reshape(-1, 4)
         kh, kw = self.filter_size(filter)
         sbin = self.model.sbin
         win = np.zeros((len(boxes), (kh + 2) * sbin, (kw + 2) * sbin, 3), np.float64)
         feat = np.zeros((len(boxes), kh, kw, 32), self.dtype)
-        self._chk(self._fn("pbd_warp_windows_u8")(self.h, _vp(im), w, hgt, cn, w * cn, _vp(boxes), len(boxes), int(filter), _vp(win),
+        self._chk(self._fn("pbd_warp_windows_u8")(self.h, _vp(im), w, hgt, cn, stride, _vp(boxes), len(boxes), int(filter), _vp(win),
                                                  _vp(feat)))
         return win, feat
 
@@ -1012,11 +1033,9 @@ class Handle:
         return tuple(ms)
 
     def pyrdown(self, im: np.ndarray):
-        im = np.ascontiguousarray(im, np.uint8)
-        hgt, w = im.shape[:2]
-        cn = 1 if im.ndim == 2 else im.shape[2]
+        im, w, hgt, cn, stride = _frame(im)
         out = np.zeros(((hgt + 1) // 2, (w + 1) // 2) + ((cn,) if cn > 1 else ()), np.uint8)
-        self._chk(self.L.pbd_pyrdown_u8(self.h, _p(im, C.c_uint8), w, hgt, cn, w * cn, _p(out, C.c_uint8)))
+        self._chk(self.L.pbd_pyrdown_u8(self.h, _p(im, C.c_uint8), w, hgt, cn, stride, _p(out, C.c_uint8)))
         return out
 
     def nms_map(self, src: np.ndarray, sz: int):
@@ -1111,7 +1130,7 @@ class Group:
 
     def detect_batch(self, frames, capacity=4096):
         """frames: list of equal-sized uint8 images -> list of (heads, boxes, locs), frame f on member f % size."""
-        frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+        frames, stride = _frames(frames)
         n = len(frames)
         if not n or any(f.shape != frames[0].shape for f in frames):
             raise ValueError("detect_batch: one or more frames, all of the same shape")
@@ -1122,21 +1141,19 @@ class Group:
         boxes = np.zeros((n * capacity, self.max_parts, 4), np.int32)
         locs = np.zeros((n * capacity, self.max_parts, 3), np.int32)
         counts = np.zeros(n, np.int32)
-        self._chk(self.L.pbd_group_detect_batch_u8(self.g, ptrs, n, w, hgt, cn, w * cn, heads.ctypes.data_as(C.c_void_p),
+        self._chk(self.L.pbd_group_detect_batch_u8(self.g, ptrs, n, w, hgt, cn, stride, heads.ctypes.data_as(C.c_void_p),
                                                    _p(boxes, C.c_int32), _p(locs, C.c_int32), capacity, _p(counts, C.c_int32)))
         return [(heads[f * capacity: f * capacity + counts[f]].copy(), boxes[f * capacity: f * capacity + counts[f]].copy(),
                  locs[f * capacity: f * capacity + counts[f]].copy()) for f in range(n)]
 
     def detect(self, im, capacity=4096):
         """one frame, pyramid levels LPT-sharded over the members."""
-        im = np.ascontiguousarray(im, np.uint8)
-        hgt, w = im.shape[:2]
-        cn = 1 if im.ndim == 2 else im.shape[2]
+        im, w, hgt, cn, stride = _frame(im)
         heads = np.zeros(capacity, HEAD_DTYPE)
         boxes = np.zeros((capacity, self.max_parts, 4), np.int32)
         locs = np.zeros((capacity, self.max_parts, 3), np.int32)
         cnt = C.c_int(0)
-        self._chk(self.L.pbd_group_detect_u8(self.g, _p(im, C.c_uint8), w, hgt, cn, w * cn, heads.ctypes.data_as(C.c_void_p),
+        self._chk(self.L.pbd_group_detect_u8(self.g, _p(im, C.c_uint8), w, hgt, cn, stride, heads.ctypes.data_as(C.c_void_p),
                                              _p(boxes, C.c_int32), _p(locs, C.c_int32), capacity, C.byref(cnt)))
         return heads[:cnt.value].copy(), boxes[:cnt.value].copy(), locs[:cnt.value].copy()
 
@@ -1195,13 +1212,6 @@ def candidates_best_overlap(heads, boxes, gt, overlap=0.3):
 
 def _vp(a):
     return None if a is None else C.c_void_p(a.ctypes.data)
-
-
-def _frame_u8(im):
-    """(contiguous uint8 array, w, hgt, cn) of an HxW or HxWxcn frame"""
-    im = np.ascontiguousarray(im, np.uint8)
-    hgt, w = im.shape[:2]
-    return im, w, hgt, 1 if im.ndim == 2 else im.shape[2]
 
 
 def warp_geometry(box, kh, kw, sbin):
@@ -1273,12 +1283,12 @@ class QpCache:
         """pbd_qp_write_warped_u8: train.m's poswarp — the boxes ((x1, y1, x2, y2), 1-based inclusive) of the 8-bit frame cropped, resized,
         HOGed and appended as positives [bias | window of `filter`] without leaving the device -> (written, status [n] int32:
         PBD_WARP_WRITTEN / _SKIPPED (area below min_area) / _FULL).  ids: one id per box (None: the box's index)."""
-        im, w, hgt, cn = _frame_u8(im)
+        im, w, hgt, cn, stride = _frame(im)
         boxes = np.ascontiguousarray(boxes, np.float64).reshape(-1, 4)
         ids = None if ids is None else np.ascontiguousarray(ids, np.int32).reshape(len(boxes))
         status = np.full(len(boxes), -1, np.int32)
         written = C.c_int(-1)
-        self.handle._chk(self.L.pbd_qp_write_warped_u8(self.q, _vp(im), w, hgt, cn, w * cn, _vp(boxes), _vp(ids), len(boxes), int(filter),
+        self.handle._chk(self.L.pbd_qp_write_warped_u8(self.q, _vp(im), w, hgt, cn, stride, _vp(boxes), _vp(ids), len(boxes), int(filter),
                                                        int(bias), float(min_area), _vp(status), C.byref(written)))
         return written.value, status
 
