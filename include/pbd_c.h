@@ -1156,6 +1156,38 @@ int pbd_qp_write_warped_u8(pbd_qp* qp, const uint8_t* im, int w, int hgt, int cn
  * pbd_set_profiling is on (zeros otherwise): [0] the two resample passes, [1] the HOG, [2] the write (0 for pbd_warp_windows_*) */
 int pbd_debug_warp_ms(const pbd_handle* h, float ms[3]);
 
+/* ---- weight and threshold updates: vec2model.m on a live handle (ABI 5, additive) ---------------------------------------------------
+ * train.m:94,112: model = vec2model(qp_w, model), then detect(im, model, -1, ...) on the negatives with the new weights.  A pbd_qp cache
+ * reads the feature planes of the handle it was created on, so the new weights go INTO that handle; the cache's columns are features,
+ * not weights, and stay valid.
+ *
+ * A weight vector has Model.feature_layout()'s order — the order pbd_qp_weights returns and pbd_qp_create derives len from —:
+ *   [biasw | defw (ndefs x 4) | the filters back to back in the caller's filter order, each [kh][kw * flen]].
+ * The model stores float32: every element becomes (float)w[i], round to nearest even.  After a successful call the handle behaves in
+ * every entry point exactly like a handle freshly created from the same model with those weights, the same options and the same
+ * setters.  pbd_options.conv_mode's resolution is NOT repeated: pbd_get_conv_mode is constant over a handle's life.  A geometry chosen
+ * by pbd_tune_plan survives.  The frame plan is dropped (as after pbd_set_levels): stage getters answer PBD_ERR_STATE until the next frame.
+ *
+ * pbd_set_weights: a host vector.  pbd_set_weights_dev: a device vector on the handle's device.  pbd_get_weights: the handle's current
+ *   float32 weights, widened.  pbd_qp_apply_weights: the solver's resident w ./ wreg + w0 (pbd_qp_weights) into the cache's handle, with
+ *   no copy through the host; it needs what every solver entry needs.
+ * pbd_set_threshold: replaces the model's thresh for min(), argmin(), the score-map NMS and every detect path; any value but NaN
+ *   (train.m uses 0 for latent positives, -1 for mining, then the 5th percentile of the positives' scores).  A min() that is resident
+ *   keeps its root tables: the next argmin() thresholds them again.
+ * All are synchronous: the update is complete on return.
+ * Refusals, each with a message, changing nothing (a detect afterwards returns the bits it returned before):
+ *   PBD_ERR_ARG — a NULL argument; len other than the layout's size; an element that is not finite as a float32; a quadratic
+ *     deformation weight (elements 0 and 2 of a deformation a non-root part uses) that is zero as a float32; a NaN threshold.
+ *   PBD_ERR_UNSUPPORTED — a filter weight with |w| >= 3e38 on a PBD_CONV_SPLIT / PBD_CONV_SPLIT_F16 handle (as at pbd_create); a
+ *     pbd_group member.
+ *   PBD_ERR_STATE — a frame or batch in flight between enqueue and collect.                                                          */
+int pbd_set_weights(pbd_handle* h, const double* w, int len);
+int pbd_set_weights_dev(pbd_handle* h, const double* d_w, int len);
+int pbd_get_weights(const pbd_handle* h, double* w, int len);
+int pbd_qp_apply_weights(pbd_qp* qp);
+int pbd_set_threshold(pbd_handle* h, float thresh);
+int pbd_get_threshold(const pbd_handle* h, float* thresh);
+
 /* ---- instrumentation --------------------------------------------------------
  * GPU time (ms, hipEvent) of the stages of the last synchronous detect:
  * [0] image pyramid [1] HOG [2] pdf [3] dp min [4] argmin [5] total            */

@@ -6,6 +6,7 @@ the import of `lib()` raises, and `pbd_create` fails on a box without a GPU.
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
 import os
 import weakref
@@ -70,6 +71,7 @@ EXPORTS = [
     "pbd_qp_loss", "pbd_qp_opt", "pbd_qp_prune", "pbd_qp_weights",
     "pbd_warp_geometry", "pbd_warp_taps", "pbd_warp_windows_u8", "pbd_warp_windows_u8_f64", "pbd_qp_write_warped_u8",
     "pbd_debug_warp_ms",
+    "pbd_set_weights", "pbd_set_weights_dev", "pbd_get_weights", "pbd_qp_apply_weights", "pbd_set_threshold", "pbd_get_threshold",
 ]
 PBD_WARP_SKIPPED, PBD_WARP_WRITTEN, PBD_WARP_FULL = 0, 1, 2   # pbd_qp_write_warped_u8's status per box
 PBD_ABI_VERSION = 5
@@ -183,6 +185,11 @@ def lib() -> C.CDLL:
                                          C.c_void_p, C.c_void_p]
         L.pbd_qp_write_warped_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                              C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]
+        for name in ("pbd_set_weights", "pbd_set_weights_dev", "pbd_get_weights"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.pbd_qp_apply_weights.argtypes = [C.c_void_p]
+        L.pbd_set_threshold.argtypes = [C.c_void_p, C.c_float]
+        L.pbd_get_threshold.argtypes = [C.c_void_p, C.c_void_p]
         if L.pbd_abi_version() != PBD_ABI_VERSION:
             raise ImportError(f"{LIB_PATH}: ABI version {L.pbd_abi_version()}, this binding is for {PBD_ABI_VERSION}")
         _lib = L
@@ -279,6 +286,44 @@ class Handle:
             self.set_candidate_filter(*cand_filter)
         if cand_nms is not None:
             self.set_candidate_nms(*cand_nms)
+
+    # ---- weight and threshold updates (include/pbd_c.h "weight and threshold updates": vec2model.m on a live handle) ----
+    def set_weights(self, w):
+        """pbd_set_weights / pbd_set_weights_dev: the handle's weights replaced by `w` (Model.feature_layout() order, rounded to float32) —
+        a numpy vector, or a contiguous float64 torch tensor on the handle's device, which is read in place.  The handle then behaves
+        like one freshly created from model.with_weight_vector(w), which self.model becomes."""
+        if hasattr(w, "data_ptr"):
+            import torch
+            if w.dtype != torch.float64 or not w.is_cuda or not w.is_contiguous():
+                raise ValueError("a device weight vector must be a contiguous float64 tensor on the handle's device")
+            torch.cuda.current_stream(w.device).synchronize()   # the library reads it on the handle's own stream
+            self._chk(self.L.pbd_set_weights_dev(self.h, C.c_void_p(w.data_ptr()), int(w.numel())))
+        else:
+            w = np.ascontiguousarray(w, np.float64).ravel()
+            self._chk(self.L.pbd_set_weights(self.h, _vp(w), int(w.size)))
+        self._model_follows()
+
+    def _model_follows(self):
+        self.model = self.model.with_weight_vector(self.weights())
+
+    def weights(self) -> np.ndarray:
+        """pbd_get_weights: the handle's current float32 weights as float64, in Model.feature_layout() order"""
+        out = np.zeros(self.model.feature_layout()["size"], np.float64)
+        self._chk(self.L.pbd_get_weights(self.h, _vp(out), int(out.size)))
+        return out
+
+    def set_threshold(self, t: float):
+        """pbd_set_threshold: the model's thresh for every detect from now on (any value but NaN)"""
+        self._chk(self.L.pbd_set_threshold(self.h, float(t)))
+        self.model = copy.copy(self.model)
+        self.model.thresh = self.threshold
+
+    @property
+    def threshold(self) -> float:
+        """pbd_get_threshold"""
+        t = C.c_float()
+        self._chk(self.L.pbd_get_threshold(self.h, C.byref(t)))
+        return t.value
 
     def set_candidate_nms(self, kind, top=0):
         """pbd_set_candidate_nms: PBD_NMS_PAINTED / PBD_NMS_PARTS (top: 1000 = nms.m's cut, 0 = none) for the frames enqueued from now on."""
@@ -1418,6 +1463,11 @@ class QpCache:
         out = np.zeros(self.dims()[0])
         self.handle._chk(self.L.pbd_qp_weights(self.q, _vp(out)))
         return out
+
+    def apply_weights(self) -> None:
+        """pbd_qp_apply_weights: train.m's model = vec2model(qp_w, model) — weights() into the cache's handle, without leaving the device"""
+        self.handle._chk(self.L.pbd_qp_apply_weights(self.q))
+        self.handle._model_follows()
 
     def close(self):
         if getattr(self, "q", None):   # (a live cache implies a live handle: Handle.close() closes its caches before itself)

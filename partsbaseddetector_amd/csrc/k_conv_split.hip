@@ -34,10 +34,6 @@
 int conv_split_ntiles(int nf);
 #include "k_conv_split32.hpp"
 
-__host__ __device__ static inline unsigned bf16_rn_bits(unsigned u) {   // fp32 bits -> bfloat16 bits, round to nearest even (finite, below bfloat16's overflow threshold)
-  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-
 // ---- features -> three exact bfloat16 parts ([cell][split][32]); one thread = 8 consecutive channels of a cell ----
 __global__ __launch_bounds__(256) void k_feat_split(const float* __restrict__ feat, uint16_t* __restrict__ out, size_t ngroups) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;    // (cell, channel group g = i & 3)

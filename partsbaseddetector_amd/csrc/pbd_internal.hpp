@@ -717,6 +717,15 @@ struct QpSolveDev {
 void launch_qp_pass(const QpDev& q, const QpSolveDev& s, const int* noneg, int p, int n, hipStream_t st);
 void launch_qp_clamp_norm(const QpSolveDev& s, const int* noneg, int p, int len, hipStream_t st);
 void launch_qp_weights(const double* w, const double* wreg, const double* w0, int len, double* out, hipStream_t st);
+// weight updates (k_weights.hip, pbd_weights.cpp; include/pbd_c.h "weight and threshold updates").  stage: the model's float32 weights in
+// Model.feature_layout() order; src[n]: where filter n of the bank being packed starts in it
+void launch_weights_round(const double* w, int len, float* out, int* bad, hipStream_t s);   // *bad: the first index that is not finite as a float, or -1
+void launch_bank_pack(const float* stage, const int* src, int nf, int kh, int kw, int nfpad, void* wT, int ts, hipStream_t s);   // upload_bank's d_wT
+void launch_bank_split(const float* stage, const int* src, int nf, int kh, int kw, uint16_t* wS, hipStream_t s);                 // conv_split_filters
+void launch_bank_split16(const float* stage, const int* src, int nf, int kh, int kw, uint16_t* wS, float* oscale, hipStream_t s);   // conv_split16_filters
+// pbd_set_weights_dev's body, for pbd_qp_apply_weights too: every refusal of include/pbd_c.h, then the update, complete on return
+int pbd_i_set_weights_dev(pbd_handle* h, const double* d_w, int len);
+int pbd_i_ps_reweigh(pbd_handle* h);   // pbd_post.cpp: k_partscore's mixture table (-defw), if built, written again in place
 void launch_gtbox(const GtBoxArgs& a, int gmax, hipStream_t s);   // k_gtbox.hip: gmax = the largest ngt
 // object clusters (k_cluster3d.hip)
 size_t cluster3d_slot_bytes(int pcap);

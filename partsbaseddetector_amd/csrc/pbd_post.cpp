@@ -278,8 +278,7 @@ static int cl3_resolve(pbd_handle* h, Cluster3dArgs a, int src, int slots, Scrat
 
 // ---- per-part scores (k_partscore.hip) --------------------------------------------------------------------------------
 // the model tables (per flat mixture: response plane, bias base, anchor, negated deformation weights) and the pinned results
-static int ps_tables(pbd_handle* h) {
-  if (h->d_ps_mix) return PBD_OK;
+static std::vector<PsMix> ps_mix_table(const pbd_handle* h) {
   const size_t nm = h->filterid.size(), nfp = h->parts.size();
   std::vector<PsMix> mix(nm);
   for (size_t fp = 0; fp < nfp; ++fp)
@@ -291,10 +290,23 @@ static int ps_tables(pbd_handle* h) {
       M.ax = h->anchors[did * 2]; M.ay = h->anchors[did * 2 + 1];
       for (int k = 0; k < 4; ++k) M.w[k] = -h->defw[(size_t)did * 4 + k];
     }
+  return mix;
+}
+static int ps_tables(pbd_handle* h) {
+  if (h->d_ps_mix) return PBD_OK;
+  const size_t nfp = h->parts.size();
+  const std::vector<PsMix> mix = ps_mix_table(h);
   int rc;
-  if ((rc = model_alloc(h, &h->d_ps_mix0, nfp + 1)) || (rc = model_alloc(h, &h->d_ps_mix, nm))) return rc;
+  if ((rc = model_alloc(h, &h->d_ps_mix0, nfp + 1)) || (rc = model_alloc(h, &h->d_ps_mix, mix.size()))) return rc;
   HIPCHK(h, hipMemcpy(h->d_ps_mix0, h->mix_offset.data(), sizeof(int) * (nfp + 1), hipMemcpyHostToDevice));
-  HIPCHK(h, hipMemcpy(h->d_ps_mix, mix.data(), sizeof(PsMix) * nm, hipMemcpyHostToDevice));
+  HIPCHK(h, hipMemcpy(h->d_ps_mix, mix.data(), sizeof(PsMix) * mix.size(), hipMemcpyHostToDevice));
+  return PBD_OK;
+}
+// the handle's deformation weights have changed (pbd_weights.cpp): the mixture table, if it has been built, written again in place
+int pbd_i_ps_reweigh(pbd_handle* h) {
+  if (!h->d_ps_mix) return PBD_OK;
+  const std::vector<PsMix> mix = ps_mix_table(h);
+  HIPCHK(h, hipMemcpy(h->d_ps_mix, mix.data(), sizeof(PsMix) * mix.size(), hipMemcpyHostToDevice));
   return PBD_OK;
 }
 static int ps_buffers(pbd_handle* h) {

@@ -390,5 +390,18 @@ int pbd_qp_weights(pbd_qp* q, double* w_out) {
   return finish(h, "QP solver weights: ");
 }
 
+// train.m:94,112 model = vec2model(qp_w, model): the same w ./ wreg + w0 into a device temporary, then pbd_set_weights_dev on the cache's
+// handle.  The cache's columns are features, not weights: they stay valid.
+int pbd_qp_apply_weights(pbd_qp* q) {
+  SOLVER_ENTRY(q);
+  const size_t len = (size_t)q->dev.len;
+  Tmp t;
+  int rc;
+  if ((rc = t.get(h, sizeof(double) * len))) return rc;
+  launch_qp_weights(q->sol.dev.w, q->d_wreg, q->d_w0, (int)len, (double*)t.p, h->stream);
+  LAUNCHCHK(h, "QP solver weights");
+  return pbd_i_set_weights_dev(h, (const double*)t.p, (int)len);
+}
+
 }  // extern "C"
 #pragma GCC visibility pop

@@ -7,6 +7,12 @@
 // part is inf and the low part, x - inf, NaN.
 constexpr int SPLIT16_FEXP = 12;
 constexpr float SPLIT16_FMAX = 65520.0f / (float)(1 << SPLIT16_FEXP);
+// fp32 bits -> bfloat16 bits, round to nearest even (finite, below bfloat16's overflow threshold): the one definition of the features'
+// parts (k_feat_split), the filters' on the host (conv_split_filters) and the filters' on the device (k_bank_split, k_weights.hip)
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+static inline unsigned bf16_rn_bits(unsigned u) { return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16; }
 #ifdef __HIPCC__
 // PBD_CONV_SPLIT: v = h + m + l, three exact bfloat16 parts (round to nearest even, every subtraction exact); part q at sp[q * stride]
 __device__ __forceinline__ void feat_split_bf16(float v, uint16_t* sp, int stride) {

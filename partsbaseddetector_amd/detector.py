@@ -346,6 +346,28 @@ class PartsBasedDetector:
     def _ps(self):
         return self.handle.part_scores(0) if self._part_scores else None
 
+    @property
+    def model(self) -> Model:
+        """the model the detector runs now: distributeModel's, with the weights and the threshold set since"""
+        return self.handle.model
+
+    def setWeights(self, w) -> None:
+        """matlab/learning/vec2model.m on the live detector: its biases, deformations and filters become `w`'s elements (in
+        Model.feature_layout()'s order, rounded to float32) — a numpy vector or a float64 torch tensor on the detector's device.  Every
+        setter's state is kept, and so is an ExampleCache bound to this detector; self.model.weight_vector() agrees with the device."""
+        self.handle.set_weights(w)
+
+    def setThresh(self, t: float) -> None:
+        """The model's threshold for every detect from now on (train.m: 0 for latent positives, -1 for mining, then
+        Model.positive_threshold of the positives' scores)."""
+        self.handle.set_threshold(t)
+
+    def updateFrom(self, cache: "capi.QpCache") -> None:
+        """train.m:94,112 model = vec2model(qp_w, model): the solver's weights into this detector, without leaving the device"""
+        if cache.handle is not self.handle:
+            raise ValueError("updateFrom: the cache is bound to another detector")
+        cache.apply_weights()
+
     def setBoundingBoxes3D(self, camera=None) -> None:
         """camera = (fx, fy, cx, cy[, tx, ty]) or a capi.pbd_camera: every detect(im, depth) with a non-empty depth image attaches
         to each returned Candidate its `box3d` (Candidate::boundingBox3D projected as PointCloudClusterer::computeBoundingBoxes

@@ -692,6 +692,14 @@ class PartsBasedDetector {
     if (boundary_pad_) dev_->setBoundaryPad(boundary_pad_);
     if (pyramid_kind_ != PBD_PYRAMID_OPENCV) dev_->setPyramidKind(pyramid_kind_);
   }
+  // matlab/learning/vec2model.m on the live detector (include/pbd_c.h "weight and threshold updates"): biases, deformations and filters
+  // become w's elements (Model.feature_layout()'s order: [biasw | defw | the filters back to back], rounded to float32); every setter's
+  // state is kept, and so is an ExampleCache bound to this detector.  The Model object handed to distributeModel is not touched.
+  void setWeights(const std::vector<double>& w) { dev_->check(pbd_set_weights(dev_->h, w.data(), (int)w.size())); }
+  void weights(std::vector<double>& w, int len) { w.assign((size_t)len, 0.0); dev_->check(pbd_get_weights(dev_->h, w.data(), len)); }
+  // the model's threshold for every detect from now on (train.m: 0 for latent positives, -1 for mining, then the positives' 5th percentile)
+  void setThresh(float t) { dev_->check(pbd_set_threshold(dev_->h, t)); }
+  float thresh() const { float t = 0; dev_->check(pbd_get_threshold(dev_->h, &t)); return t; }
   // The image pyramid detect() builds its features on.  PBD_PYRAMID_OPENCV (the default): HOGFeatures<T>::pyramid, cv::resize and
   // cv::pyrDown in the pixel type (src/HOGFeatures.cpp:95-127).  PBD_PYRAMID_MATLAB: matlab/detection/featpyramid.m:13-34 — the frame
   // goes to double once, matlab/mex/resize.cc makes the first octave, matlab/mex/reduce.cc every further one — with its level count,
@@ -882,6 +890,9 @@ class PartsBasedDetector {
     int prune() { int n = 0; dev_->check(pbd_qp_prune(q_, &n)); return n; }
     // qp_w.m: the next model's weights, w ./ wreg + w0 (Model.feature_layout() maps them back)
     void weights(std::vector<double>& w) { int len = 0; dims(&len, nullptr, nullptr, nullptr); w.assign((size_t)len, 0.0); dev_->check(pbd_qp_weights(q_, w.data())); }
+    // train.m:94,112 model = vec2model(qp_w, model): weights() into the detector this cache is bound to, without leaving the device
+    // (include/pbd_c.h "weight and threshold updates"); the cache's columns stay valid
+    void applyWeights() { dev_->check(pbd_qp_apply_weights(q_)); }
     // poswarp of matlab/learning/train.m:131-161 (include/pbd_c.h "warped positives"): the boxes (1-based inclusive) of the 8-bit frame
     // warped to filter `filter`'s size (warppos.m), HOGed and appended as [bias | window] positives, all on the GPU.  Boxes below
     // min_area (prod(maxsize * sbin), train.m:135) are skipped; status (optional): PBD_WARP_WRITTEN / _SKIPPED / _FULL per box; ids

@@ -241,6 +241,16 @@ class Model:
                       for o, f in zip(lay["filters"], self.filtersw)]
         return m
 
+    @staticmethod
+    def positive_threshold(scores, q: float = 0.05) -> float:
+        """matlab/learning/train.m:117-118, r = sort(qp_scorepos()); model.thresh = r(ceil(length(r) * .05)): the score that a fraction
+        q of the positives fall at or below — the threshold a trained model ships with.  scores: the positives' raw scores
+        (QpCache.score(w, positives) / cpos), at least one."""
+        r = np.sort(np.asarray(scores, np.float64).ravel())
+        if r.size == 0:
+            raise ValueError("positive_threshold: no scores")
+        return float(r[max(int(np.ceil(r.size * np.float64(q))), 1) - 1])
+
     def to_desc(self) -> pbd_model_desc:
         """Flatten into the C ABI descriptor (arrays kept alive on self).  Uniform banks only (pbd_create)."""
         kh = self.filtersw[0].shape[0]
