@@ -175,7 +175,9 @@ int pbd_abi_version(void);
  * points pbd_qp_create, _destroy, _dims, _footprint, _write, _score[_dev], _lincomb[_dev], _keep, _get and _put; and the QP solver
  * over that cache: pbd_qp_noneg, _fix, _state_put, _state_get, _pass, _one, _refresh, _loss, _opt, _prune and _weights; and the
  * warped positives: pbd_warp_geometry, pbd_warp_taps, pbd_warp_windows_u8, pbd_warp_windows_u8_f64, pbd_qp_write_warped_u8 and
- * pbd_debug_warp_ms (with PBD_WARP_SKIPPED / _WRITTEN / _FULL).                                                                    */
+ * pbd_debug_warp_ms (with PBD_WARP_SKIPPED / _WRITTEN / _FULL); and the weight and threshold updates pbd_set_weights,
+ * pbd_set_weights_dev, pbd_get_weights, pbd_qp_apply_weights, pbd_set_threshold and pbd_get_threshold; and hard-negative mining:
+ * pbd_qp_mine_u8, pbd_qp_mine_dev_u8 and pbd_qp_mine_batch_u8 (with PBD_MINE_NONE / _ONE / _OPT).                                  */
 
 /* ---- output record: include/Candidate.hpp:56-111 --------------------------
  * One candidate = head + max_parts boxes (x, y, width, height as cv::Rect)
@@ -1187,6 +1189,63 @@ int pbd_get_weights(const pbd_handle* h, double* w, int len);
 int pbd_qp_apply_weights(pbd_qp* qp);
 int pbd_set_threshold(pbd_handle* h, float thresh);
 int pbd_get_threshold(const pbd_handle* h, float* thresh);
+
+/* ---- hard-negative mining: detections into the example cache (ABI 5, additive) ---------------------------------------------------------
+ * train.m:99-108 runs, once per negative image i, [box, model] = detect(im, model, -1, [], 0, i, -1): every detection above the
+ * threshold becomes an example of label -1 (detect.m:127-133 -> qp_write.m), the upper bound grows by its slack (detect.m:135), and the
+ * solver runs when the bounds have drifted apart (detect.m:148-149, optimize: 315-325).  pbd_qp_mine_* is that call on the cache's
+ * handle with the frame's records left on the device: the image goes in; per frame ONE small block comes out (the record count, the
+ * first record the write would refuse, the frame's sum S_f below).  No record crosses PCIe, in either direction.
+ *
+ * Detection.  The frame is detected exactly as pbd_detect_u8 / pbd_detect_dev_u8 / pbd_detect_batch_u8 would detect it on the cache's
+ *   handle: its threshold (pbd_set_threshold; train.m uses -1), candidate mode and NMS, boundary pad and pyramid kind all apply.  The
+ *   frame's final records are the ones the plain entry would have returned, in that order: PBD_CAND_RAW by (level, component, root
+ *   row, root column); SORT / SORT_NMS / PBD_NMS_PARTS the filter's output.  records[f] = their number for frame f.
+ * Write.  Label -1: C = cneg, values negated; id words (-1, id[f], level, x_root, y_root) with the frame's own level.  The first
+ *   min(total, capacity - n) records of the call, frame after frame and each frame's in record order, become examples n ...; their
+ *   bits — x, ids, b, d, the block table, the solver's a = 0 and sv = 1 — are the ones pbd_qp_write(heads, locs, count, -1, id) gives
+ *   for the same records.  written[f] = how many of frame f's records were written.  A full cache is no error (qp_write.m:21-23).
+ * Upper bound (detect.m:133-136).  EVERY record of the frame contributes, those a full cache refused included (qp_write.m:21-23
+ *   returns early; detect.m:135 still runs): t = cneg * max(1 + (double)score, 0), the sum and the product each rounded, nothing fused.
+ *   A frame's terms go through the block sum of the "training example cache" section over the frame's records in record order (64
+ *   lane-strided partials starting at +0.0, folded with h = 32 .. 1) to S_f; then ub = ub + S_f, one frame after the other, so a batch
+ *   and the same frames one by one give the same bits.  The solver's state is allocated as by any solver entry; its host mirror and
+ *   pbd_qp_state_get's stats[3] are current on return.
+ * Action (detect.m:148-149, :315-324), evaluated ONCE, after the call, on the state the call left:
+ *   lb < 0 || n == capacity -> PBD_MINE_OPT (n == capacity is also part of detect.m's outer trigger, :149); otherwise
+ *   1 - lb / ub > .05 -> PBD_MINE_ONE; otherwise PBD_MINE_NONE.  ub == 0 makes lb / ub an infinity or a NaN: IEEE is followed as MATLAB
+ *   follows it (a NaN compares false: PBD_MINE_NONE).  The library does not run the solver itself: the caller answers PBD_MINE_OPT with
+ *   pbd_qp_opt then pbd_qp_prune, PBD_MINE_ONE with pbd_qp_one, either with pbd_qp_apply_weights.
+ *   DEVIATION: detect.m tests after every (level, component) and may change the model in the middle of a frame; here the model is
+ *   constant over a call.  DEVIATION: detect.m:36,56 visits levels and components in a random permutation; here the order is the one
+ *   stated above.  (train.m:96's model.interval = 2 while mining stays the caller's: a handle's interval is fixed at pbd_create.)
+ * Validation.  A scan on the device validates every record before anything is written.  A record pbd_qp_write would refuse — a repeated
+ *   dense start (qp_write.m:34-35; the test is exact: parts that share an id only in mixtures the pose did not pick are accepted), a
+ *   part outside its level, a column longer than k — gets the whole call PBD_ERR_ARG: nothing is written, ub and n are unchanged, the
+ *   message names the first such record; records[f] holds the frames' counts, written[f] = 0.  A frame that overflows
+ *   pbd_options.max_candidates gets PBD_ERR_CAPACITY with the needed count in records[0], as pbd_detect_u8 reports it; nothing is
+ *   written, written[f] = 0.  DEVIATION for a batch: an overflowed list is truncated before the frames are told apart, so the needed
+ *   count is that of ALL frames of the batch together, in records[0], and records[1 ..] = 0 (pbd_detect_batch_u8's counts[] are
+ *   per frame only while the list did not overflow, too).  A refused call leaves *action as the caller had it.
+ * Other refusals, each with a message, changing nothing of the cache (but: a call refused behind its argument and setting checks —
+ *   the compact plan, an overflow, a bad record — has allocated the solver's state like any solver entry: a = 0 and sv = 1 for the
+ *   examples held, w = 0, l = lb = ub = 0, which is what pbd_qp_state_get answers on a cache that never solved):
+ *   PBD_ERR_UNSUPPORTED — pbd_group members; the compact memory plan; depth pruning, 3-D boxes, object clusters or per-part scores
+ *     switched on (the refusals of the gt-box frames), beyond what feature vectors already refuse.
+ *   PBD_ERR_STATE — a frame pending between enqueue and collect.
+ *   PBD_ERR_ARG — NULL arguments; bad frame arguments (as the plain entries); nframes outside 1..64.
+ * The call is synchronous.  On return no frame is pending, and the frame's feature planes are resident (the stage getters, and
+ *   pbd_candidates_features on records of a plain detect of the same frame, read them).  A caller who wants the mined records
+ *   themselves calls the plain detect.  Mining frames run eagerly (no graph replay), like latent and gt-box frames.                      */
+#define PBD_MINE_NONE 0
+#define PBD_MINE_ONE  1   /* detect.m:322-323: qp_one                         */
+#define PBD_MINE_OPT  2   /* detect.m:319-321: qp_opt, then qp_prune          */
+int pbd_qp_mine_u8(pbd_qp* qp, const uint8_t* im, int w, int hgt, int cn, int stride, int id,
+                   int* records, int* written, int* action);
+int pbd_qp_mine_dev_u8(pbd_qp* qp, const void* d_im, int w, int hgt, int cn, int stride, int id,
+                       int* records, int* written, int* action);
+int pbd_qp_mine_batch_u8(pbd_qp* qp, const uint8_t* const* ims, int nframes, int w, int hgt, int cn, int stride,
+                         const int32_t* ids, int32_t* records, int32_t* written, int* action);
 
 /* ---- instrumentation --------------------------------------------------------
  * GPU time (ms, hipEvent) of the stages of the last synchronous detect:

@@ -72,7 +72,9 @@ EXPORTS = [
     "pbd_warp_geometry", "pbd_warp_taps", "pbd_warp_windows_u8", "pbd_warp_windows_u8_f64", "pbd_qp_write_warped_u8",
     "pbd_debug_warp_ms",
     "pbd_set_weights", "pbd_set_weights_dev", "pbd_get_weights", "pbd_qp_apply_weights", "pbd_set_threshold", "pbd_get_threshold",
+    "pbd_qp_mine_u8", "pbd_qp_mine_dev_u8", "pbd_qp_mine_batch_u8",
 ]
+PBD_MINE_NONE, PBD_MINE_ONE, PBD_MINE_OPT = 0, 1, 2   # pbd_qp_mine_*'s action (detect.m:148-149, 315-324)
 PBD_WARP_SKIPPED, PBD_WARP_WRITTEN, PBD_WARP_FULL = 0, 1, 2   # pbd_qp_write_warped_u8's status per box
 PBD_ABI_VERSION = 5
 
@@ -190,6 +192,11 @@ def lib() -> C.CDLL:
         L.pbd_qp_apply_weights.argtypes = [C.c_void_p]
         L.pbd_set_threshold.argtypes = [C.c_void_p, C.c_float]
         L.pbd_get_threshold.argtypes = [C.c_void_p, C.c_void_p]
+        for name in ("pbd_qp_mine_u8", "pbd_qp_mine_dev_u8"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]
+        L.pbd_qp_mine_batch_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]
         if L.pbd_abi_version() != PBD_ABI_VERSION:
             raise ImportError(f"{LIB_PATH}: ABI version {L.pbd_abi_version()}, this binding is for {PBD_ABI_VERSION}")
         _lib = L
@@ -1416,6 +1423,13 @@ class QpCache:
         self.handle._chk(self.L.pbd_qp_state_get(self.q, _vp(a), _vp(sv), _vp(w), _vp(st)))
         return a, sv, w, st
 
+    def support(self) -> np.ndarray:
+        """pbd_qp_state_get for sv alone: the support-vector flags of the n examples held (capacity bytes over PCIe, nothing else)"""
+        _, _, cap, n = self.dims()
+        sv = np.zeros(cap, np.uint8)
+        self.handle._chk(self.L.pbd_qp_state_get(self.q, None, _vp(sv), None, None))
+        return sv[:n]
+
     def set_state(self, a=None, sv=None) -> None:
         """pbd_qp_state_put: a and / or sv of examples 0 .. len - 1"""
         a = None if a is None else np.ascontiguousarray(a, np.float64).ravel()
@@ -1468,6 +1482,50 @@ class QpCache:
         """pbd_qp_apply_weights: train.m's model = vec2model(qp_w, model) — weights() into the cache's handle, without leaving the device"""
         self.handle._chk(self.L.pbd_qp_apply_weights(self.q))
         self.handle._model_follows()
+
+    # ---- hard-negative mining (include/pbd_c.h "hard-negative mining") ----
+    def mine(self, im, id: int):
+        """pbd_qp_mine_u8: train.m:102's detect(im, model, -1, [], 0, id, -1) on the cache's handle — the frame is detected as
+        Handle.detect would detect it (the handle's threshold, candidate filter, pad and pyramid kind), its records stay on the device
+        and become examples of label -1, ub grows by every record's slack -> (records, written, action): the frame's records, how many
+        the cache had room for, and PBD_MINE_NONE / _ONE / _OPT: what detect.m would now run.  train.m:96's model.interval = 2 is the
+        caller's business: a handle's interval is fixed when it is created."""
+        im, w, hgt, cn, stride = _frame(im)
+        rec, wr, act = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+        rc = self.L.pbd_qp_mine_u8(self.q, _vp(im), w, hgt, cn, stride, int(id), C.byref(rec), C.byref(wr), C.byref(act))
+        self._mine_chk(rc, [rec.value])
+        return rec.value, wr.value, act.value
+
+    def mine_dev(self, dptr: int, w, hgt, cn, id: int, stride=None):
+        """pbd_qp_mine_dev_u8: the same on a frame in device memory (an integer device pointer), read in place"""
+        rec, wr, act = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+        rc = self.L.pbd_qp_mine_dev_u8(self.q, C.c_void_p(dptr), w, hgt, cn, w * cn if stride is None else int(stride), int(id),
+                                       C.byref(rec), C.byref(wr), C.byref(act))
+        self._mine_chk(rc, [rec.value])
+        return rec.value, wr.value, act.value
+
+    def mine_batch(self, ims, ids):
+        """pbd_qp_mine_batch_u8: same-sized frames as one batch -> (records [n] int32, written [n] int32, action); the examples and ub
+        are those of the frames mined one by one, in bits"""
+        frames, stride = _frames(ims)
+        ids = np.ascontiguousarray(ids, np.int32).ravel()
+        if not frames or len(ids) != len(frames) or any(f.shape != frames[0].shape for f in frames):
+            raise ValueError("mine_batch: one id per frame, frames of one shape")
+        hgt, w = frames[0].shape[:2]
+        cn = 1 if frames[0].ndim == 2 else frames[0].shape[2]
+        ptrs = (C.c_void_p * len(frames))(*[f.ctypes.data for f in frames])
+        rec, wr, act = np.full(len(frames), -1, np.int32), np.full(len(frames), -1, np.int32), C.c_int(-1)
+        rc = self.L.pbd_qp_mine_batch_u8(self.q, ptrs, len(frames), w, hgt, cn, stride, _vp(ids), _vp(rec), _vp(wr), C.byref(act))
+        self._mine_chk(rc, rec)
+        return rec, wr, act.value
+
+    def _mine_chk(self, rc, records):
+        if rc == PBD_ERR_CAPACITY:   # (the needed count travels with the error, as Handle.detect's does)
+            msg = self.L.pbd_last_error(self.handle.h).decode()
+            err = PbdError(rc, msg)
+            err.records = [int(r) for r in records]
+            raise err
+        self.handle._chk(rc)
 
     def close(self):
         if getattr(self, "q", None):   # (a live cache implies a live handle: Handle.close() closes its caches before itself)

@@ -6,6 +6,8 @@
 //   values) and the column stores coalesce; no unscaled window is staged in HBM.  The sums behind d and b follow the order the header
 //   states: per block 64 lane-strided partials and a halving fold, then the blocks in block order by one thread.  Nothing of that
 //   depends on the grid: a record's bits are the same wherever it lands.
+//   The records are the call's uploaded ones (pbd_qp_write) or a mining frame's, read where the back-tracking or the candidate filter
+//   left them, through the order k_qp_mine.hip made (QpWriteArgs::perm, ::ids): one text for both.
 // k_qp_poswrite: a warped positive (k_warp.hip's window through k_hog) as a two-block column, one wavefront per example.
 // k_qp_score: one lane owns one example's serial add chain (score.cc's order); a wavefront stages its 64 columns through LDS in
 //   chunks with coalesced loads and each lane walks its own row (pitch 65: no bank conflict).  w is read through L2.
@@ -63,7 +65,7 @@ __global__ void __launch_bounds__(QW_NT) k_qp_write(QpWriteArgs a) {
   int* s_bad = s_off + mp + 1;
   const T* feat = (const T*)fv.feat;
   for (int r = blockIdx.x; r < fv.n; r += gridDim.x) {
-    const char* rec = fv.in.p + fv.in.stride * (size_t)(fv.rec0 + r);
+    const char* rec = fv.in.p + fv.in.stride * (size_t)(a.perm ? a.perm[fv.rec0 + r] : fv.rec0 + r);
     const pbd_candidate_head* hd = (const pbd_candidate_head*)rec;
     const int c = hd->component, lvl = hd->level, np = hd->nparts;
     const bool rec_ok = fv_rec_ok(fv, hd);
@@ -117,7 +119,8 @@ __global__ void __launch_bounds__(QW_NT) k_qp_write(QpWriteArgs a) {
     if (threadIdx.x == 0) qp_column_sums(a.q, col, col_i, nb, s_sum, a.C);
     if (threadIdx.x < 5) {
       const int t = threadIdx.x;
-      a.q.ids[(size_t)col_i * 5 + t] = t == 0 ? a.label : t == 1 ? a.id : t == 2 ? lvl : t == 3 ? lc[0] : lc[1];
+      const int frame = a.nlevels ? lvl / a.nlevels : 0;   // (a mining batch: the frame's id, the frame's own level)
+      a.q.ids[(size_t)col_i * 5 + t] = t == 0 ? a.label : t == 1 ? (a.ids ? a.ids[frame] : a.id) : t == 2 ? lvl - frame * a.nlevels : t == 3 ? lc[0] : lc[1];
     }
     __syncthreads();   // the LDS tables are rewritten by the block's next record
   }

@@ -27,6 +27,9 @@ int enter_frame(pbd_handle* h, const FrameSource& s, bool detect) {
   }
   ON_DEVICE(h);
   if ((rc = plan_frame(h, s.w, s.hgt, s.cn, s.nframes, s.depth))) return rc;
+  if (s.mine && h->compact)   // (known once the geometry is planned; nothing has been uploaded or enqueued)
+    return fail(h, PBD_ERR_UNSUPPORTED, "mining: this frame runs the compact memory plan (dp_mode 2, or automatic for large frames), whose min() reuses "
+                                        "the memory of the feature planes the examples are read from");
   if (!s.on_device)   // on the handle's stream, in front of the kernels
     for (int f = 0; f < s.nframes; ++f) {
       const void* im = s.each ? s.each[f] : s.one;
@@ -44,6 +47,8 @@ int enter_frame(pbd_handle* h, const FrameSource& s, bool detect) {
   } else if (s.gt) {
     job.kind = FRAME_GTBOX;
     if ((rc = pbd_i_gt_begin(h, *s.gt, s.nframes))) return rc;
+  } else if (s.mine) {
+    job.kind = FRAME_MINE;
   } else if (s.z) {
     const DepthSource& z = *s.z;
     job.kind = FRAME_DEPTH;

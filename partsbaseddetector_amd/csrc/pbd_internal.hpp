@@ -295,6 +295,15 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   double4* d_gt_cbox = nullptr; unsigned* d_gt_key = nullptr; unsigned long long* d_gt_rank = nullptr; int* d_gt_frame = nullptr;   // [capacity]
   double* d_gt = nullptr; double* h_gt = nullptr;   // [PBD_MAX_BATCH][PBD_GT_MAX][4], then the frames' ngt as ints; h_: pinned staging
   char* h_gt_out = nullptr; int* h_gt_found = nullptr; double* h_gt_o = nullptr;   // [PBD_MAX_BATCH * PBD_GT_MAX] slots: pinned
+  // hard-negative mining (pbd_qp_mine_*): k_qp_mine.hip behind the back-tracking and the candidate filter, whose records stay in
+  // d_cand_out.  Model-lifetime buffers (first use): the records' order, the per-component "no two parts can
+  // share an id" flags, the frames' ids and the pinned block the scan answers in.
+  unsigned long long* d_mine_key = nullptr; int* d_mine_perm = nullptr;   // [capacity] each
+  int* d_mine_ids = nullptr; int* h_mine_ids = nullptr;                   // [PBD_MAX_BATCH] each; h_: pinned staging
+  int* d_mine_noshare = nullptr;                                           // [ncomp]
+  struct MineFrameOut* h_mine_out = nullptr;                               // [PBD_MAX_BATCH]: pinned
+  int mine_k = 0; double mine_cneg = 0.0;   // the calling cache's column length and C, for the scan of the frame being enqueued
+  RecordSet mine_in{};                      // where that frame's final records are (its route's final_buf / final_count)
 };
 #define PBD_MAX_BATCH 64
 
@@ -416,6 +425,7 @@ struct FrameSource {
   const DepthSource* z;           // RGB-D: the frame runs with the depth-carrying post-stages; else null
   const LatentSource* lat;        // latent detection: the frame is masked by these boxes and yields its best pose; else null
   const GtSource* gt;             // best pose per ground-truth box: the selection runs behind the back-tracking; else null
+  bool mine;                      // hard-negative mining (pbd_qp_mine_*): the final records stay on the device
 };
 // the three shapes of a source, by name (z: see above)
 inline FrameSource host_frame(const void* im, int w, int hgt, int cn, int stride, int depth, const DepthSource* z = nullptr) {
@@ -456,6 +466,8 @@ int pbd_i_gt_check(pbd_handle* h, const double* gt, const int* ngt, int nframes,
 int pbd_i_gt_begin(pbd_handle* h, const GtSource& s, int nframes);
 int pbd_i_gt_enqueue(pbd_handle* h, const FrameRoute& r);
 void pbd_i_gt_gather(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int* found, double* o);
+// hard-negative mining (pbd_qp_mine.cpp): behind the last post-stage of a FRAME_MINE job, the order and the scan of its final records
+int pbd_i_mine_enqueue(pbd_handle* h, const FrameRoute& r);
 int pbd_i_found(const pbd_handle* h);   // records the pending frame left on the host side (filtered: the kept count)
 #define PBD_FIRST_COPY 192   // candidate records fetched (or gathered) together with the count
 
@@ -664,6 +676,10 @@ void launch_featvec(const FeatVecArgs& a, int ts, hipStream_t s);
 // outputs (the upload synchronises the handle's stream)
 int pbd_i_fv_check(pbd_handle* h, const pbd_candidate_head* heads, const int32_t* locs, int count);
 int pbd_i_fv_upload(pbd_handle* h, const pbd_candidate_head* heads, const int32_t* locs, int count, FeatVecArgs* a);
+// the same launch over records that are on the device already: the tables (built on first use, outside any frame) and everything of
+// the launch but its records and its outputs
+int pbd_i_fv_tables(pbd_handle* h);
+void pbd_i_fv_args(const pbd_handle* h, FeatVecArgs* a);
 // training example cache (k_qp.hip, pbd_qp.cpp; include/pbd_c.h "training example cache")
 struct QpDev {
   float* x;                 // [capacity][k]: the columns, qp.x verbatim
@@ -677,8 +693,32 @@ struct QpWriteArgs {
   QpDev q; int n0;          // record r becomes example n0 + r
   const double* wreg; const double* w0; const int* foff;   // [len], [len], [nfilters] dense start of each filter
   double C; int label, id;
+  // a mining frame's records, where the back-tracking or the candidate filter left them (pbd_qp_write: all null / 0)
+  const int* perm;          // non-null: record fv.rec0 + r of the call is fv.in's record perm[fv.rec0 + r]
+  const int* ids;           // non-null: the id of a record of frame f is ids[f] ...
+  int nlevels;              // ... f = level / nlevels, and the level word is the frame's own level (0: one frame)
 };
 void launch_qp_write(const QpWriteArgs& a, int ts, hipStream_t s);
+// hard-negative mining (k_qp_mine.hip, pbd_qp_mine.cpp; include/pbd_c.h "hard-negative mining")
+enum { MINE_OK = 0, MINE_BAD_RECORD = 1, MINE_BAD_COLUMN = 2, MINE_BAD_REPEAT = 3 };
+struct MineFrameOut {       // what the scan answers per frame, in pinned memory
+  int count;                // the frame's final records
+  int bad, code;            // the first record (in record order) pbd_qp_write would refuse, and why (MINE_*); -1: none
+  int raw;                  // the back-tracking's count over all frames, before any filter (> capacity: overflow, nothing else is valid)
+  double S;                 // the block sum of the frame's terms cneg * max(1 + score, 0)
+};
+struct MineArgs {
+  RecordSet in;             // the final records of the frame or batch
+  int nframes, k;           // k: the cache's column length
+  FeatVecArgs fv;           // the model and plan tables of the gather (fv.in = in)
+  const int* noshare;       // [ncomp] 1: no two parts of the component can share a filter, def or bias id, whatever the pose picks
+  double cneg;
+  unsigned long long* key;  // [capacity] RAW: (virtual level, component, root y, root x), 16 bits each
+  int* perm;                // [capacity] the records in write order: frame after frame, a frame's in record order
+  MineFrameOut* out;        // [nframes]
+};
+void launch_qp_mine_order(const MineArgs& a, hipStream_t s);   // RAW records only: perm sorts them by key
+void launch_qp_mine_scan(const MineArgs& a, hipStream_t s);
 // a warped positive's column (train.m:152-161 qp_poswrite): window r of `feat` (T [n][wlen]) becomes example n0 + r with ids (1, ids[r], 0, 0, 0)
 struct QpPosArgs {
   QpDev q; int n0, n;

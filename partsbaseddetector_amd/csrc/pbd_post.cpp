@@ -398,15 +398,19 @@ static int fv_upload(pbd_handle* h, const pbd_candidate_head* heads, const int32
   for (size_t i = 0; i < n; ++i) pbd_rec_put(rec.data() + st * i, mp, heads, nullptr, locs, i);
   HIPCHK(h, hipMemcpyAsync(h->d_fv_rec, rec.data(), st * n, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));   // (`rec` goes out of scope; earlier work on the stream — the frame — is done too)
+  pbd_i_fv_args(h, a);
+  a->in.p = h->d_fv_rec; a->in.stride = st; a->in.mp = mp; a->in.capacity = count;
+  return PBD_OK;
+}
+int pbd_i_fv_tables(pbd_handle* h) { return fv_tables(h); }
+void pbd_i_fv_args(const pbd_handle* h, FeatVecArgs* a) {
   FeatVecArgs& A = *a;
   A = FeatVecArgs{};
-  A.in.p = h->d_fv_rec; A.in.stride = st; A.in.mp = mp; A.in.capacity = count;
   A.levels = h->d_levels; A.nvl = h->nvl; A.feat = h->d_feat;
   A.ncomp = h->md.ncomponents; A.nbias = (int)h->biasw.size(); A.nfilters = h->md.nfilters;
   A.nparts = h->d_nparts; A.parent = h->d_parent; A.flat = h->d_flat;
   A.mix0 = h->d_ps_mix0; A.mix = h->d_ps_mix; A.fmix = h->d_fv_mix;
   A.wmax = fv_wmax(h);
-  return PBD_OK;
 }
 int pbd_i_fv_check(pbd_handle* h, const pbd_candidate_head* heads, const int32_t* locs, int count) {
   return fv_begin(h, heads, locs, count, heads, heads, 0, nullptr);   // (no caller buffers to check: the cache owns the outputs)

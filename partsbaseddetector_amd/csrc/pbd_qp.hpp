@@ -58,3 +58,5 @@ inline int finish(pbd_handle* h, const char* what) {
 
 // pbd_qp_solve.cpp: examples n0 .. n0 + n - 1 were appended — with solver state they start at a = 0, sv = 1 (qp_write.m:74)
 int pbd_i_qp_appended(pbd_qp* q, int n0, int n);
+// pbd_qp_solve.cpp: the solver's state as any solver entry allocates it (pbd_qp_mine_* keeps ub there)
+int pbd_i_qp_ensure(pbd_qp* q);

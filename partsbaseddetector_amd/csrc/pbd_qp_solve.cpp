@@ -214,6 +214,8 @@ int pbd_i_qp_appended(pbd_qp* q, int n0, int n) {
   return PBD_OK;
 }
 
+int pbd_i_qp_ensure(pbd_qp* q) { return ensure(q); }
+
 #define SOLVER_ENTRY(q)                   \
   if (!(q)) return PBD_ERR_ARG;           \
   pbd_handle* h = (q)->h;                 \

@@ -23,7 +23,8 @@ enum FrameKind {
   FRAME_DEPTH,    // RGB-D: the depth-carrying post-stages run (z)
   FRAME_LATENT,   // masked by truth boxes, yields its best pose (its tables: pbd_i_latent_begin)
   FRAME_GTBOX,    // the selection per ground-truth box runs behind the back-tracking (its tables: pbd_i_gt_begin)
-  FRAME_STAGE     // pbd_dp_argmin / pbd_dp_argbest: the back-tracking of resident tables, no frame entry and no post-stage
+  FRAME_STAGE,    // pbd_dp_argmin / pbd_dp_argbest: the back-tracking of resident tables, no frame entry and no post-stage
+  FRAME_MINE      // pbd_qp_mine_*: the final records stay on the device for the example cache's scan and write; only a count comes back
 };
 struct FrameJob {
   FrameKind kind = FRAME_PLAIN;
@@ -105,9 +106,12 @@ inline bool route_frame(const RouteSettings& s, const FrameJob& job, FrameRoute*
   const bool filtered = cm != PBD_CAND_RAW;
   const bool zf = k == FRAME_DEPTH && s.zf_on;
   const bool post = zf || filtered;
-  const bool zero_copy = s.zero_copy && !s.member;
+  const bool mine = k == FRAME_MINE;
+  const bool dev = s.member || mine;   // the final records stay in DEV_OUT
+  const bool zero_copy = s.zero_copy && !dev;
   if (k == FRAME_GTBOX && (filtered || s.zf_on || s.b3_on || s.cl3_on || s.ps_on)) return false;   // pbd_i_gt_check
   if (s.member && (k == FRAME_DEPTH || k == FRAME_LATENT || k == FRAME_GTBOX || s.b3_on || s.ps_on)) return false;   // the setters and the latent / gt checks
+  if (mine && (s.member || s.compact || s.zf_on || s.b3_on || s.cl3_on || s.ps_on)) return false;   // pbd_qp_mine_*'s own refusals
 
   FrameRoute r;
   r.latent = k == FRAME_LATENT;
@@ -115,7 +119,7 @@ inline bool route_frame(const RouteSettings& s, const FrameJob& job, FrameRoute*
   r.bt.on = true;
   r.bt.out_count = CNT_DEV;
   if (r.gt) r.bt.out = DEV_OUT;
-  else if (post) r.bt.out = zf || s.member ? DEV_RAW : DEV_OUT;
+  else if (post) r.bt.out = zf || dev ? DEV_RAW : DEV_OUT;
   else if (zero_copy) { r.bt.out = HOST_OUT; r.bt_host_count = true; }
   else r.bt.out = DEV_OUT;
   const RouteStage* last = &r.bt;
@@ -125,22 +129,22 @@ inline bool route_frame(const RouteSettings& s, const FrameJob& job, FrameRoute*
   }
   if (filtered) {
     const bool parts = cm == PBD_CAND_SORT_NMS && s.cand_nms == PBD_NMS_PARTS;
-    const RouteBuf dst = s.member ? DEV_OUT : HOST_OUT;
-    const RouteCount dst_count = s.member ? CNT_DEV_CF : CNT_HOST_CF;
+    const RouteBuf dst = dev ? DEV_OUT : HOST_OUT;
+    const RouteCount dst_count = dev ? CNT_DEV_CF : CNT_HOST_CF;
     r.filter_mode = parts ? PBD_CAND_SORT : cm;
     r.filter = {true, last->out, last->out_count, parts ? DEV_CP_STAGE : dst, parts ? CNT_DEV_CP : dst_count};
     last = &r.filter;
     if (parts) { r.parts = {true, DEV_CP_STAGE, CNT_DEV_CP, dst, dst_count}; last = &r.parts; }
   }
   r.final_buf = last->out; r.final_count = last->out_count;
-  if (r.gt) r.count_d2h = CNT_DEV;                       // nothing of the records themselves is fetched
+  if (r.gt || mine) r.count_d2h = CNT_DEV;               // nothing of the records themselves is fetched
   else if (s.member) r.pack_count = r.final_count;
   else if (!route_on_host(r.final_buf)) { r.count_d2h = CNT_DEV; r.first_d2h = true; }
   else if (last == &r.zf) r.count_d2h = CNT_DEV_ZF;
 
   PendingFrame& p = r.pending;
   p.active = true;
-  p.on_host = r.gt || route_on_host(r.final_buf);
+  p.on_host = r.gt || mine || route_on_host(r.final_buf);   // (a mining frame: nothing for a collect to fetch)
   p.filtered = filtered;
   p.gt = r.gt;
   p.b3 = k == FRAME_DEPTH && s.b3_on;

@@ -519,3 +519,45 @@ class PartsBasedDetector:
         maxsize = m.filter_sizes().max(axis=0)
         min_area = float(maxsize[0] * m.sbin) * float(maxsize[1] * m.sbin)
         return cache.write_warped(im, boxes, filter, bias, min_area, ids)
+
+    def mineNegatives(self, images, cache: "capi.QpCache", first_id: int = 0, tol: float = .05, max_iter: int = 1000, seed: int = 0):
+        """matlab/learning/train.m:99-108 with detect.m's optimize at frame granularity: every image is mined into `cache`
+        (capi.QpCache.mine with id first_id + i: detected on this detector at its threshold — train.m uses -1, setThresh —, the records
+        written as negatives on the GPU, ub grown by their slack); on PBD_MINE_OPT the cache runs opt(tol, max_iter, seed) then prune(),
+        on PBD_MINE_ONE one() over a shuffle of find(sv) drawn as opt draws it; after either the weights go into this detector
+        (apply_weights).  Stops behind the image after which sum(sv) == capacity (train.m:105).  Returns (records, written, action) per
+        image mined.  Not done here: detect.m updates the model in the middle of a frame and visits levels and components in a random
+        order; and train.m:96's model.interval = 2 while mining stays the caller's business — a detector's interval is fixed by the
+        model it was given (distributeModel)."""
+        if cache.handle is not self.handle:
+            raise ValueError("mineNegatives: the cache is bound to another detector")
+        out = []
+        for i, im in enumerate(images):
+            rec, wr, act = cache.mine(im, first_id + i)
+            out.append((rec, wr, act))
+            if act == capi.PBD_MINE_OPT:
+                cache.opt(tol, max_iter, seed)
+                cache.prune()
+            elif act == capi.PBD_MINE_ONE:
+                cache.one(shuffled_support(cache, seed))
+            if act != capi.PBD_MINE_NONE:
+                cache.apply_weights()
+            if int(cache.support().sum()) == cache.dims()[2]:
+                break
+        return out
+
+
+def shuffled_support(cache: "capi.QpCache", seed: int = 0) -> np.ndarray:
+    """find(qp.sv) of the cache's examples, shuffled the way pbd_qp_opt shuffles its first pass: Fisher-Yates from the back, the
+    draws SplitMix64(seed) modulo the positions left"""
+    I = [int(i) for i in np.flatnonzero(cache.support())]
+    s, M = int(seed) & 0xFFFFFFFFFFFFFFFF, 0xFFFFFFFFFFFFFFFF
+    for u in range(len(I) - 1, 0, -1):
+        s = (s + 0x9E3779B97F4A7C15) & M
+        z = s
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M
+        z ^= z >> 31
+        j = z % (u + 1)
+        I[u], I[j] = I[j], I[u]
+    return np.asarray(I, np.int32)

@@ -1,6 +1,6 @@
 // demo.cpp — the reference's canonical caller (src/demo.cpp:55-118) against the MI355X path:
 //   pbd_demo model.bin image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE] [--examples FILE] [--matlab-pyramid]
-//            [--gtbox x1,y1,x2,y2[,overlap]]...
+//            [--gtbox x1,y1,x2,y2[,overlap]]... [--mine FILE]...
 //   pbd_demo model.bin image.raw width height channels perturb-features <responses-out.bin>
 //   pbd_demo model.bin image.raw width height channels oracle-responses <responses-in.bin>
 // deserialize -> distributeModel -> detect -> Candidate::sort, then prints the candidates (the
@@ -20,6 +20,9 @@ static std::vector<GtBox> g_gtbox;
 static const char* g_examples_file = nullptr;   // --examples FILE (anywhere): the detections as QP examples, written to FILE
 static double g_gt_overlap = 0.3;
 static std::vector<GtBox> g_warp;               // --warp x1,y1,x2,y2 (anywhere, repeatable): the boxes as warped positives, dumped and nothing else
+// --mine FILE (anywhere, repeatable): raw frames of the image's size mined as negatives (train.m:99-108) into a cache of 256 examples,
+// Cpos = Cneg = 1, ids 0, 1, ..., at the model's threshold; per frame the records, how many were written, and the action
+static std::vector<const char*> g_mine;
 static void print_pose(const Candidate& c) {
   printf("%.9g %d %d", c.score(), c.component(), c.level);
   for (const Rect& r : c.parts()) printf(" %d,%d,%d,%d", r.x, r.y, r.width, r.height);
@@ -71,6 +74,23 @@ static void run(Model& model, const Mat& im, bool stagewise, int special = 0, co
       }
       printf("\n");
     }
+    return;
+  }
+  if (!g_mine.empty()) {
+    std::vector<Mat> frames;
+    for (const char* name : g_mine) {
+      Mat fr(im.rows, im.cols, PBD_8U, im.channels());
+      const size_t bytes = (size_t)im.rows * im.cols * im.channels();
+      FILE* f = fopen(name, "rb");
+      if (!f || fread(fr.ptr<uint8_t>(), 1, bytes, f) != bytes) { printf("--mine %s: not found or not a frame of the image's size\n", name); exit(-4); }
+      fclose(f);
+      frames.push_back(fr);
+    }
+    auto cache = pbd.exampleCache(256, 1.0, 1.0);
+    const auto mined = cache->mineNegatives(frames);
+    for (size_t i = 0; i < mined.size(); ++i)
+      printf("Mine %zu: records %d written %d action %d\n", i, mined[i].records, mined[i].written, mined[i].action);
+    printf("Cache: %d of %d examples, ub %.17g\n", cache->size(), cache->capacity(), cache->state(nullptr, nullptr, nullptr).ub);
     return;
   }
   if (stagewise) {
@@ -279,6 +299,12 @@ int main(int argc, char** argv) {
       for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
       argc -= 2; --i;
     } else
+    if (std::string(argv[i]) == "--mine") {
+      if (i + 1 >= argc || !*argv[i + 1]) { printf("--mine FILE\n"); exit(-1); }
+      g_mine.push_back(argv[i + 1]);
+      for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+      argc -= 2; --i;
+    } else
     if (std::string(argv[i]) == "--examples") {
       if (i + 1 >= argc || !*argv[i + 1]) { printf("--examples FILE\n"); exit(-1); }
       g_examples_file = argv[i + 1];
@@ -302,7 +328,7 @@ int main(int argc, char** argv) {
       --argc; --i;
     }
   if (argc < 6 || argc > 8) {
-    printf("Usage: pbd_demo model_file image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE] [--examples FILE] [--nms-parts OVERLAP] [--matlab-pyramid] [--gtbox x1,y1,x2,y2[,overlap]]... [--warp x1,y1,x2,y2]...\n");
+    printf("Usage: pbd_demo model_file image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE] [--examples FILE] [--nms-parts OVERLAP] [--matlab-pyramid] [--gtbox x1,y1,x2,y2[,overlap]]... [--warp x1,y1,x2,y2]... [--mine FILE]...\n");
     exit(-1);
   }
   // determine the type of model to read (src/demo.cpp:63-82)
@@ -331,6 +357,7 @@ int main(int argc, char** argv) {
     if (features_file && special) { printf("--features: not with %s\n", mode.c_str()); exit(-1); }
     if (g_examples_file && (special || !g_gtbox.empty())) { printf("--examples: not with %s\n", special ? mode.c_str() : "--gtbox"); exit(-1); }
     if (!g_warp.empty() && (special || stagewise || !g_gtbox.empty() || g_examples_file || features_file || part_scores || nms_parts)) { printf("--warp: on its own (or with double)\n"); exit(-1); }
+    if (!g_mine.empty() && (special || stagewise || !g_gtbox.empty() || !g_warp.empty() || g_examples_file || features_file || part_scores)) { printf("--mine: on its own (or with double, --pad, --nms-parts, --matlab-pyramid)\n"); exit(-1); }
     if (!g_gtbox.empty() && (part_scores || nms_parts || features_file)) { printf("--gtbox: not with --part-scores, --nms-parts or --features\n"); exit(-1); }
     if (mode.find("double") != std::string::npos) run<double>(model, im, stagewise, 0, nullptr, part_scores, pad, features_file, nms_parts, matlab_pyramid);
     else run<float>(model, im, stagewise, special, special ? argv[7] : nullptr, part_scores, pad, features_file, nms_parts, matlab_pyramid);

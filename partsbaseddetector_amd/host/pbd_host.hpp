@@ -907,6 +907,53 @@ class PartsBasedDetector {
                                          ids ? ids->data() : nullptr, (int)boxes.size(), filter, bias, min_area, status ? status->data() : nullptr, &written));
       return written;
     }
+    // ---- hard-negative mining (include/pbd_c.h "hard-negative mining") ----
+    // train.m:102's detect(im, model, -1, [], 0, id, -1) on the detector this cache is bound to: the frame is detected as detect() would
+    // detect it (threshold — train.m uses -1, setThresh —, candidate filter, pad, pyramid kind), its records stay on the device and become
+    // negatives, ub grows by every record's slack.  action: PBD_MINE_NONE / _ONE / _OPT, what detect.m would now run.
+    struct Mined { int records, written, action; };
+    Mined mine(const Mat& im, int id) {
+      if (im.depth() != PBD_8U) throw Exception(PBD_ERR_UNSUPPORTED, "mining: 8-bit frames only");
+      Mined m{-1, -1, -1};
+      dev_->check(pbd_qp_mine_u8(q_, im.ptr<uint8_t>(), im.cols, im.rows, im.channels(), (int)im.step(), id, &m.records, &m.written, &m.action));
+      return m;
+    }
+    // find(qp.sv) shuffled as pbd_qp_opt shuffles its first pass: Fisher-Yates from the back, SplitMix64(seed) modulo the positions left
+    std::vector<int32_t> shuffledSupport(uint64_t seed) {
+      std::vector<unsigned char> sv;
+      state(nullptr, &sv, nullptr);
+      std::vector<int32_t> I;
+      for (int i = 0, n = size(); i < n; ++i) if (sv[i]) I.push_back(i);
+      uint64_t s = seed;
+      for (size_t u = I.size(); u-- > 1;) {
+        uint64_t z = (s += 0x9E3779B97F4A7C15ull);
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        z ^= z >> 31;
+        std::swap(I[u], I[(size_t)(z % (uint64_t)(u + 1))]);
+      }
+      return I;
+    }
+    // train.m:99-108 with detect.m's optimize at frame granularity: per image mine(); on PBD_MINE_OPT opt then prune, on PBD_MINE_ONE one()
+    // over shuffledSupport(seed); after either applyWeights(); stops behind the image after which sum(sv) == capacity (train.m:105).
+    // Not done here: mid-frame model updates, detect.m's random visiting order, and train.m:96's model.interval = 2 (a detector's interval
+    // is its model's).
+    std::vector<Mined> mineNegatives(const std::vector<Mat>& images, int first_id = 0, double tol = .05, int max_iter = 1000, uint64_t seed = 0) {
+      std::vector<Mined> out;
+      for (size_t i = 0; i < images.size(); ++i) {
+        out.push_back(mine(images[i], first_id + (int)i));
+        const int act = out.back().action;
+        if (act == PBD_MINE_OPT) { opt(tol, max_iter, seed); prune(); }
+        else if (act == PBD_MINE_ONE) one(shuffledSupport(seed));
+        if (act != PBD_MINE_NONE) applyWeights();
+        std::vector<unsigned char> sv;
+        state(nullptr, &sv, nullptr);
+        int nsv = 0;
+        for (int e = 0, n = size(); e < n; ++e) nsv += sv[e] != 0;
+        if (nsv == capacity()) break;
+      }
+      return out;
+    }
    private:
     void score_(const std::vector<double>& w, const int32_t* inds, int n, std::vector<double>& out) {
       int len = 0; dims(&len, nullptr, nullptr, nullptr);
