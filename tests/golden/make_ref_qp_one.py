@@ -1,12 +1,13 @@
-"""Writes tests/golden/ref_qp_one_v1.npz: the outputs of the COMPILED reference coordinate-descent pass — matlab/mex/qp_one_sparse.cc,
-read in place from the reference checkout — over consecutive passes of the cases of tests/qp_solve_cases.py.
+"""Writes tests/golden/ref_qp_one_v1.npz and ref_qp_one_v2.npz: the outputs of the COMPILED reference coordinate-descent pass —
+matlab/mex/qp_one_sparse.cc, read in place from the reference checkout — over consecutive passes of the cases of
+tests/qp_solve_cases.py: v1 holds CASES (free, binding), v2 holds LARGE_CASES (manyblock, manyids), every pass of both in full.
 
 Only outputs are stored, per case and pass: loss, a, w, sv, l.  The inputs are regenerated from seeds by the tests; the order of pass p
 is qp_solve_cases.next_order of the sv the compiled file left.  The file is compiled with tests/golden/ref_qp_one_driver.cpp (the
 accessor bodies of tests/golden/ref_qp_one_shim/mex.h and one extern "C" call, no arithmetic) into a temporary directory outside the
 tree: nothing compiled is kept.  -ffp-contract=off: no product is fused into a sum.
 
-    PBD_REFERENCE=<reference checkout> python tests/golden/make_ref_qp_one.py
+    PBD_REFERENCE=<reference checkout> python tests/golden/make_ref_qp_one.py [v1 | v2]      (neither: both files)
 """
 import ctypes as C
 import os
@@ -58,13 +59,15 @@ if __name__ == "__main__":
     ref = os.environ.get("PBD_REFERENCE")
     if not ref or not os.path.isfile(os.path.join(ref, "matlab", "mex", "qp_one_sparse.cc")):
         sys.exit("set PBD_REFERENCE to the reference checkout (matlab/mex/qp_one_sparse.cc)")
-    out = {}
+    files = {"v1": qp_solve_cases.CASES, "v2": qp_solve_cases.LARGE_CASES}
     with tempfile.TemporaryDirectory() as tmp:
         fn = build(ref, tmp)
-        for name, make in qp_solve_cases.CASES.items():
-            for p, r in run_case(fn, make()).items():
-                for key, v in r.items():
-                    out[f"{name}_{p}_{key}"] = v
-    path = os.path.join(HERE, "ref_qp_one_v1.npz")
-    np.savez_compressed(path, **out)
-    print(path, os.path.getsize(path), "bytes;", len(out), "arrays")
+        for version in sys.argv[1:] or sorted(files):
+            out = {}
+            for name, make in files[version].items():
+                for p, r in run_case(fn, make()).items():
+                    for key, v in r.items():
+                        out[f"{name}_{p}_{key}"] = v
+            path = os.path.join(HERE, f"ref_qp_one_{version}.npz")
+            np.savez_compressed(path, **out)
+            print(path, os.path.getsize(path), "bytes;", len(out), "arrays")

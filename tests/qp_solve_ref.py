@@ -50,7 +50,7 @@ class State:
 
 def new_counters():
     return dict(pair=0, clip_C_minus_Ai=0, clip_Ai2=0, clip_minus_Ai=0, clip_Ai2_minus_C=0, sv_clear=0, pg_zero=0, clamp=0, err=0,
-                single=0)
+                single=0, err_past_1024=0)      # (err_past_1024: non-zero entries of a pass's err at indices >= 1024)
 
 
 def score(W, col, summation):
@@ -218,6 +218,7 @@ def pass_ref(cache, st, order, summation="strided", dot="complete", cnt=None):
             if A[i] > 0:
                 idI[j] = i + 1
     st.l = L
+    cnt["err_past_1024"] += int(np.count_nonzero(err[1024:]))
     return F64(seq_sum(err))
 
 

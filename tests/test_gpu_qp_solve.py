@@ -1,6 +1,7 @@
 """The QP solver on the device (k_qp_solve.hip, pbd_qp_solve.cpp; include/pbd_c.h "QP solver") against tests/qp_solve_ref.py in the
 library's order (block sums, complete dot), bit for bit: the pass after every pass of every case, refresh / loss / one / prune / opt,
-columns written by pbd_qp_write (non-ascending blocks), the state of appended examples, qp_w.m, and every refusal with the state
+the same at 77 blocks a column, 1200 ids and 1600 noneg entries (qp_solve_cases.LARGE_CASES), columns written by pbd_qp_write
+(non-ascending blocks; the small tree's and the person model's 77), the state of appended examples, qp_w.m, and every refusal with the state
 untouched.  tests/test_qp_solve_cpu.py ties the same restatement, summing left to right, to the compiled reference file; the two
 orders meet again here through weak duality: each run's lower bound stays under the other's upper bound."""
 import ctypes as C
@@ -10,6 +11,7 @@ import pytest
 
 from partsbaseddetector_amd import capi
 from partsbaseddetector_amd.model import make_image, make_mixed_person_model, make_tree_model_k
+from tests import qp_ref
 from tests import qp_solve_cases as sc
 from tests import qp_solve_ref as sr
 
@@ -23,6 +25,11 @@ KEYS = ("loss", "a", "w", "sv", "l")
 @pytest.fixture(scope="module")
 def cases():
     return {name: make() for name, make in sc.CASES.items()}
+
+
+@pytest.fixture(scope="module")
+def large():
+    return {name: make() for name, make in sc.LARGE_CASES.items()}
 
 
 @pytest.fixture(scope="module")
@@ -115,10 +122,13 @@ def test_pass_is_invariant(handle, cases, capacity, junk, reload):
 
 # ---- 3. refresh, loss, one, prune, opt ---------------------------------------------------------------------------------------------------
 def test_one_loss_prune_and_opt_equal_the_restatement(handle, cases):
-    c = cases["binding"]
-    n, cap = len(c["x"]), 128
+    one_loss_prune_and_opt(handle, cases["binding"], 128)
+
+
+def one_loss_prune_and_opt(handle, c, cap, junk=0):
+    n = len(c["x"])
     cache = (c["x"], c["ids"], c["b"], c["d"])
-    q = load(handle, c, cap)
+    q = load(handle, c, cap, junk)
     length = q.dims()[0]
     st = sr.start_state(c, cap, length)
     sr.refresh_ref(cache, st, "strided")              # (load's refresh)
@@ -159,6 +169,59 @@ def test_one_loss_prune_and_opt_equal_the_restatement(handle, cases):
     assert sub - lb > 1e-6 * sub and ub - slb > 1e-6 * ub                 # separated by far more than rounding: no slack needed
     assert lb <= sub and slb <= ub
     q.close()
+
+
+# ---- 3b. beyond one trip of the kernels' loops: 77-block columns, 1200 ids, a noneg list of 1600 entries ---------------------------------
+def test_manyblock_passes_one_loss_prune_and_opt(handle, large):
+    """columns of 77 blocks (k_qp_pass's 16 wavefronts take five trips over them in the score, the axpy and the pair dot; k_qp_score and
+    k_qp_lincomb walk them in loss, refresh, prune and opt), behind junk columns in a cache of another capacity"""
+    c = large["manyblock"]
+    _, cnt = sr.run_passes(c, "strided", "complete")
+    print("manyblock counters", cnt)
+    assert cnt["pair"] > 0 and cnt["single"] > 0 and cnt["clamp"] > 0
+    assert {int(col[0]) for col in c["x"]} == {77}
+    run_case(handle, c, 301, junk=23)
+    one_loss_prune_and_opt(handle, c, 301, junk=23)
+
+
+def test_manyids_passes_refresh_and_loss(handle, large):
+    """1200 ids (the pass's loss is summed in chunks of 1024), a noneg list of 1600 entries (the clamp strides by the block size: 1024
+    in the pass, 256 in refresh), 2400 examples in loss and refresh"""
+    c = large["manyids"]
+    n, cap = len(c["x"]), 2500
+    cache = (c["x"], c["ids"], c["b"], c["d"])
+    q = load(handle, c, cap)
+    length = q.dims()[0]
+    st, cnt = sr.start_state(c, cap, length), sr.new_counters()
+    sr.refresh_ref(cache, st, "strided")              # (load's refresh: lb, which the refresh below moves to lb_old)
+    for p in range(c["passes"]):
+        order = sc.next_order(c, p, st.sv)
+        rloss = sr.pass_ref(cache, st, order, "strided", "complete", cnt)
+        loss = q.solve_pass(order)
+        assert np.array([loss]).tobytes() == np.array([rloss]).tobytes(), (p, loss, rloss)
+        check(q, dict(a=st.a, sv=st.sv, w=st.w, l=np.array([st.l])), ("manyids", p))
+    print("manyids counters", cnt, "noneg", len(c["noneg"]))
+    assert cnt["pair"] > 0 and cnt["single"] > 0 and cnt["clamp"] > 0 and cnt["err_past_1024"] > 0 and len(c["noneg"]) > 1024
+    # a state in which refresh has entries to clamp behind the first 256 and 1024 of the list
+    a = st.a.copy()
+    a[:n] = np.random.default_rng(9).uniform(0, 1, n) * (np.arange(n) % 3 > 0)
+    q.set_state(a, st.sv)
+    st.a = a.copy()
+    raw = qp_lincomb_sorted(cache, st)
+    neg = raw[c["noneg"]] < 0
+    assert neg[256:1024].any() and neg[1024:].any()
+    q.refresh()
+    sr.refresh_ref(cache, st, "strided")
+    ga, gsv, gw, gst = q.state()
+    assert gw.tobytes() == st.w.tobytes() and gst.tobytes() == st.stats().tobytes() and ga.tobytes() == st.a.tobytes()
+    assert np.array([q.loss()]).tobytes() == np.array([sr.loss_ref(cache, st, n)]).tobytes()
+    q.close()
+
+
+def qp_lincomb_sorted(cache, st):
+    """refresh's w before its clamp"""
+    I = np.flatnonzero(st.a > 0)
+    return qp_ref.lincomb_ref(cache[0], st.a, I[np.argsort(st.a[I], kind="stable")], len(st.w))
 
 
 # ---- 4. columns written by pbd_qp_write --------------------------------------------------------------------------------------------------
@@ -211,6 +274,61 @@ def test_written_columns_two_passes_and_a_refresh(gpu_required):
     assert q.weights().tobytes() == (w / wreg + w0).tobytes()
     q.close()
     h.close()
+
+
+def test_written_person_columns_two_passes_and_a_refresh(handle):
+    """what pbd_qp_write makes of poses of the person model: columns of 3 * 26 - 1 = 77 blocks in detect.m's (non-ascending) order.  C is
+    the restatement's choice: the largest of 2e-5, 1e-5, 5e-6, ... at which its two passes over the written columns run both the pair
+    and the single branch (2e-5, the first, on an MI355X; the test prints the one it used with the counters)"""
+    model, h = handle.model, handle
+    h.pyramid(make_image(3, SW, SH))
+    g = h.geometry(SW, SH)
+    rng = np.random.default_rng(4)
+    level = 1
+    cw, ch = int(g["cell_w"][level]), int(g["cell_h"][level])
+    n, np_ = 24, model.nparts(0)
+    assert np_ == 26
+    heads = np.zeros(n, capi.HEAD_DTYPE)
+    locs = np.zeros((n, model.max_parts, 3), np.int32)
+    roots = [(int(rng.integers(0, cw)), int(rng.integers(0, ch))) for _ in range(2)]
+    for i in range(n):
+        heads[i] = (0.0, 0, level, np_)
+        for p in range(np_):
+            x, y = roots[i % 2] if p == 0 else (int(rng.integers(0, cw)), int(rng.integers(0, ch)))   # two roots: ids are shared
+            locs[i, p] = (x, y, int(rng.integers(0, len(model.filterid[0][p]))))
+    _, wreg, w0, noneg = model.qp_vectors()
+    orders = [np.random.default_rng(p).permutation(n).astype(np.int32) for p in range(2)]
+    used = None
+    for C in [2e-5 / 2 ** t for t in range(10)]:
+        q = capi.QpCache(h, 32, C, C)
+        assert q.write(heads[:12], locs[:12], 1, 7) == 12 and q.write(heads[12:], locs[12:], -1, 8) == 12
+        q.noneg(noneg)
+        cache = q.get()
+        length, k, cap, _ = q.dims()
+        st, cnt = sr.State(cap, length, n, noneg), sr.new_counters()
+        for order in orders:
+            sr.pass_ref(cache, st, order, "strided", "complete", cnt)
+        if cnt["pair"] > 0 and cnt["single"] > 0:
+            used = C
+            break
+        q.close()
+    print("C used", used, "counters", cnt)
+    assert used is not None, cnt
+    assert (cache[0][:, 0] == 77).all() and len(np.unique(cache[1], axis=0)) == 4
+    starts = [[s for s, _, _ in sr.parse(col)] for col in cache[0]]
+    assert any(s != sorted(s) for s in starts)
+    st = sr.State(cap, length, n, noneg)
+    for p, order in enumerate(orders):
+        loss = q.solve_pass(order)
+        rloss = sr.pass_ref(cache, st, order, "strided", "complete")
+        a, sv, w, stats = q.state()
+        assert np.array([loss, stats[0]]).tobytes() == np.array([rloss, st.l]).tobytes(), (p, loss, rloss)
+        assert a.tobytes() == st.a.tobytes() and sv.tobytes() == st.sv.tobytes() and w.tobytes() == st.w.tobytes(), p
+    q.refresh()
+    sr.refresh_ref(cache, st, "strided")
+    a, sv, w, stats = q.state()
+    assert w.tobytes() == st.w.tobytes() and stats.tobytes() == st.stats().tobytes()
+    q.close()
 
 
 # ---- 5. appended examples, the footprint ---------------------------------------------------------------------------------------------------

@@ -64,7 +64,7 @@ def test_action(lb, ub, n, cap, want):
     assert mine_ref.action(lb, ub, n, cap) == want
 
 
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 1000])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 192, 193, 257, 1000, 2757])   # (192 / 193: where the scan's four-loads loop starts)
 def test_block_sum_against_fsum(n):
     rng = np.random.default_rng(n)
     scores = rng.normal(-1.0, 1.5, n).astype(np.float32)

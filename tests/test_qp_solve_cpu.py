@@ -1,6 +1,6 @@
 """The QP solver's chain of evidence on the CPU (include/pbd_c.h "QP solver"): tests/qp_solve_ref.py summing strictly left to right
 with the reference's merge-walk dot IS the compiled matlab/mex/qp_one_sparse.cc (tests/golden/ref_qp_one_v1.npz) in bits, over
-consecutive passes; the cases run every branch they claim; the library's order (block sums, complete dot) is told apart from it by the
+consecutive passes, and so on the large cases (ref_qp_one_v2.npz); the cases run every branch they claim; the library's order (block sums, complete dot) is told apart from it by the
 fixture; the complete dot is the right one where the merge walk is not; refresh / loss / prune / opt restated; and the entry points are
 declared, exported and bound.  tests/test_gpu_qp_solve.py closes the chain: library == strided / complete restatement in bits."""
 import ctypes as C
@@ -76,6 +76,70 @@ def test_cases_run_every_branch(cases, runs):
     # memcmp order of the ids differs from their numeric order
     by_bytes = sorted(range(len(sv)), key=lambda i: c["ids"][i].tobytes())
     assert [tuple(c["ids"][i]) for i in by_bytes] != sorted(tuple(r) for r in c["ids"])
+
+
+# ---- 2b. the large cases: 77-block columns; 1200 ids under a noneg list of 1600 entries ------------------------------------------------
+GOLDEN_V2 = os.path.join(os.path.dirname(__file__), "golden", "ref_qp_one_v2.npz")
+
+
+@pytest.fixture(scope="module")
+def large():
+    cases = {name: make() for name, make in sc.LARGE_CASES.items()}
+    return cases, {(name, s): sr.run_passes(c, s, d) for name, c in cases.items() for s, d in (("sequential", "merge"), ("strided", "complete"))}
+
+
+def test_large_cases_sequential_restatement_equals_the_compiled_reference(large):
+    golden = np.load(GOLDEN_V2)
+    cases, runs = large
+    assert os.path.getsize(GOLDEN_V2) <= max(os.path.getsize(os.path.join(os.path.dirname(GOLDEN_V2), f))
+                                             for f in os.listdir(os.path.dirname(GOLDEN_V2)) if f.endswith("_v1.npz"))
+    assert len(golden.files) == sum(5 * c["passes"] for c in cases.values())
+    for name, c in cases.items():
+        out, _ = runs[name, "sequential"]
+        assert len(out) == c["passes"]
+        for p, r in enumerate(out):
+            for key in KEYS:
+                g = golden[f"{name}_{p}_{key}"]
+                assert r[key].dtype == g.dtype and r[key].tobytes() == g.tobytes(), (name, p, key)
+        # and the fixture tells the library's order from it
+        lib = runs[name, "strided"][0]
+        assert any(r[key].tobytes() != golden[f"{name}_{p}_{key}"].tobytes() for p, r in enumerate(lib) for key in KEYS), name
+
+
+def test_large_cases_run_what_they_claim(large):
+    cases, runs = large
+    clips = ("clip_C_minus_Ai", "clip_Ai2", "clip_minus_Ai", "clip_Ai2_minus_C")
+    for name, c in cases.items():
+        for s in ("sequential", "strided"):
+            cnt = runs[name, s][1]
+            print(name, s, cnt)
+            assert cnt["pair"] > 0 and cnt["single"] > 0 and cnt["clamp"] > 0 and sum(cnt[k] for k in clips) > 0, (name, s, cnt)
+        # ascending blocks inside K / LEN: the merge walk is complete on them
+        for col in c["x"][:200]:
+            blocks = sr.parse(col)
+            assert all(s0 + n0 <= s1 for (s0, n0, _), (s1, _, _) in zip(blocks, blocks[1:])) and blocks[-1][0] + blocks[-1][1] <= LEN
+    mb, mi = cases["manyblock"], cases["manyids"]
+    assert len(mb["x"]) == 48 and mb["passes"] == 4 and {int(col[0]) for col in mb["x"]} == {77}         # 3 * 26 - 1 blocks, > 4 x 16
+    lens = [n for col in mb["x"] for _, n, _ in sr.parse(col)]
+    assert set(lens) == {1, 4, 63, 64, 65, 70} and lens.count(1) == 48 * 26 and lens.count(4) == 48 * 25
+    assert all(len(np.flatnonzero((mb["ids"] == r).all(axis=1))) == 4 for r in mb["ids"])
+    partial = 0                                      # same-id pairs whose windows intersect partially
+    for i in range(len(mb["x"])):
+        for j in np.flatnonzero((mb["ids"] == mb["ids"][i]).all(axis=1)):
+            if j > i:
+                for s, n, _ in sr.parse(mb["x"][i]):
+                    for s2, n2, _ in sr.parse(mb["x"][j]):
+                        lo, hi = max(s, s2), min(s + n, s2 + n2)
+                        partial += lo < hi and (hi - lo) < min(n, n2)
+    assert partial > 0
+    assert len(mi["x"]) == 2400 and mi["passes"] == 2 and len(np.unique(mi["ids"], axis=0)) == 1200
+    assert {int(col[0]) for col in mi["x"]} == {2} and {n for col in mi["x"] for _, n, _ in sr.parse(col)} == {1} | set(range(3, 40))
+    assert len(mi["noneg"]) >= 1500 and len(mi["noneg"]) > 1024 and len(np.unique(mi["noneg"])) == len(mi["noneg"])
+    for s in ("sequential", "strided"):
+        assert runs["manyids", s][1]["err_past_1024"] > 0              # the loss has terms beyond its first 1024 ids
+        # entries of noneg beyond the first 1024 are clamped: some w there is 0 after a pass and was not before it
+        w0, w1 = mi["w"][mi["noneg"][1024:]], runs["manyids", s][0][0]["w"][mi["noneg"][1024:]]
+        assert (w1 >= 0).all() and ((w1 == 0) & (w0 != 0)).any()
 
 
 # ---- 3. the fixture tells the two orders apart ------------------------------------------------------------------------------------------
