@@ -177,7 +177,9 @@ int pbd_abi_version(void);
  * warped positives: pbd_warp_geometry, pbd_warp_taps, pbd_warp_windows_u8, pbd_warp_windows_u8_f64, pbd_qp_write_warped_u8 and
  * pbd_debug_warp_ms (with PBD_WARP_SKIPPED / _WRITTEN / _FULL); and the weight and threshold updates pbd_set_weights,
  * pbd_set_weights_dev, pbd_get_weights, pbd_qp_apply_weights, pbd_set_threshold and pbd_get_threshold; and hard-negative mining:
- * pbd_qp_mine_u8, pbd_qp_mine_dev_u8 and pbd_qp_mine_batch_u8 (with PBD_MINE_NONE / _ONE / _OPT).                                  */
+ * pbd_qp_mine_u8, pbd_qp_mine_dev_u8 and pbd_qp_mine_batch_u8 (with PBD_MINE_NONE / _ONE / _OPT); and the latent positives:
+ * pbd_qp_write_latent_u8, pbd_qp_write_latent_dev_u8, pbd_qp_write_latent_batch_u8 and pbd_croppos (with the struct
+ * pbd_latent_example).                                                                                                              */
 
 /* ---- output record: include/Candidate.hpp:56-111 --------------------------
  * One candidate = head + max_parts boxes (x, y, width, height as cv::Rect)
@@ -1246,6 +1248,64 @@ int pbd_qp_mine_dev_u8(pbd_qp* qp, const void* d_im, int w, int hgt, int cn, int
                        int* records, int* written, int* action);
 int pbd_qp_mine_batch_u8(pbd_qp* qp, const uint8_t* const* ims, int nframes, int w, int hgt, int cn, int stride,
                          const int32_t* ids, int32_t* records, int32_t* written, int* action);
+
+/* ---- latent positives: poslatent into the example cache (ABI 5, additive) ----------------------------------------------------------------
+ * train.m:166-193 (poslatent) runs, once per positive image i, croppos and then detect(im, model, 0, bbox, overlap, i, 1): the best
+ * pose whose every part overlaps its box (detect.m:18-20, 60-101, 115-118) becomes ONE example of label +1 (detect.m:159-164 ->
+ * qp_write.m).  It is the path trainmodel.m takes for the final model (warp = 0).  pbd_qp_write_latent_* is that call on the cache's
+ * handle with the record left on the device: the image and the truth go in; per frame ONE fixed block comes out (the caller's
+ * pbd_latent_example of 32 bytes, filled from a 40-byte pinned slot the device writes).  No record crosses PCIe, in either direction; the example is written straight from the resident feature planes.
+ *
+ * Detection.  Exactly pbd_detect_latent_u8 / _dev_u8 / pbd_detect_batch_latent_u8 on the cache's handle: everything the "latent
+ *   detection" section states applies unchanged — truth convention, mask and skip rule, tie rule, pyramid kind and boundary pad, the
+ *   handle's candidate filter on the single record, all three dp_modes.  out[f]'s head fields are those of that entry's record (level:
+ *   the frame's own), score its score widened to double (exact).  found = 0 with PBD_OK where a frame has no pose: it writes nothing.
+ * Write.  Label +1: C = cpos, no value negated; id words (1, id[f], level, x_root, y_root) with the frame's own level.  The found
+ *   frames' records become examples n ..., in frame order, while the cache has room; their bits — x, ids, b, d, the block table, the
+ *   solver's a = 0 and sv = 1 — are the ones pbd_qp_write(head, locs, 1, 1, id) gives for the same record on the same resident planes.
+ *   written = 1 where the frame became an example; found = 1 with written = 0: the cache was full, which is no error (qp_write.m:21-23).
+ *   qp.ub does not move and there is no action to answer (detect.m:133,148 are ~latent).  Fixing the positives as permanent support
+ *   vectors (train.m:90-91) stays the caller's pbd_qp_fix.
+ * Validation.  A scan on the device validates every record before anything is written, by hard-negative mining's rule and with its
+ *   device text: a record pbd_qp_write would refuse — a repeated dense start (two parts of the pose sharing a def or bias id;
+ *   qp_write.m:34-35), a part outside its level, a column longer than k — gets the whole call PBD_ERR_ARG: nothing is written, n is
+ *   unchanged, the message names the frame; out[f].found and the head fields are filled, written = 0.
+ * Other refusals, each with a message and leaving the cache as it was — the union of latent detection's and mining's:
+ *   PBD_ERR_UNSUPPORTED — pbd_group members; the score-map NMS (reserved[0] > 0); a filter id shared between (component, part) slots
+ *     among the components searched; the compact memory plan (its min() reuses the memory of the feature planes the example is read
+ *     from); depth pruning, 3-D boxes, object clusters or per-part scores switched on.
+ *   PBD_ERR_STATE — a frame pending between enqueue and collect.
+ *   PBD_ERR_ARG — NULL arguments; the latent entries' bad arguments (negative width or height, overlap outside [0, 1), mix outside the
+ *     part's mixtures, component out of range); bad frame arguments (as the plain entries); nframes outside 1..64.
+ * The call is synchronous.  On return no frame is pending, and the frame's feature planes are resident (pbd_candidates_features on the
+ *   returned head reads them); the response planes carry the mask, as after any latent frame, and a plain detect afterwards is
+ *   untouched by it.  Latent frames run eagerly (no graph replay); plain frames and their captured graph are untouched.
+ * Batch: truth [nframes][max_parts][4], mix [nframes][max_parts] or NULL, ids [nframes], out [nframes]; frames of one size, as every
+ *   batch entry takes them.  The examples are those of the frames written one by one, in bits.
+ *
+ * pbd_croppos is croppos.m, host code like pbd_warp_geometry (no GPU is initialised).  truth: [nparts][4] in this ABI's convention,
+ *   (x, y, width, height), 0-based, covering x .. x + width.  In MATLAB's 1-based terms, in double, with MATLAB's round (halves away
+ *   from zero; pad is a multiple of 0.5): X1 = min x + 1, X2 = max(x + width) + 1, Y alike; pad = 0.5 * ((X2 - X1 + 1) + (Y2 - Y1 + 1));
+ *   x1 = max(1, round(X1 - pad)), x2 = min(w, round(X2 + pad)), y alike.  roi = (x1 - 1, y1 - 1, x2 - x1 + 1, y2 - y1 + 1): 0-based
+ *   corner, width and height in pixels of the crop.  truth_out (may be NULL, may be truth): the truth with x -= roi[0], y -= roi[1];
+ *   widths and heights unchanged.  An empty ROI (the truth wholly outside the w x hgt frame) is PBD_ERR_ARG, as are NULL truth / roi,
+ *   nparts < 1 and a negative width or height.  The crop itself is a view: im + roi[1] * stride + roi[0] * cn with the same stride.    */
+typedef struct pbd_latent_example {   /* 32 bytes */
+  int32_t found;      /* 1: the frame has a pose (pbd_detect_latent_u8's *found)                                       */
+  int32_t written;    /* 1: it became an example; 0 with found = 1: the cache was full, or the call was refused         */
+  int32_t component;  /* the record's head: component ...                                                              */
+  int32_t level;      /* ... pyramid level (the frame's own) ...                                                       */
+  int32_t x, y;       /* ... and root cell (locs[0][0], locs[0][1])                                                    */
+  double  score;      /* the record's score, widened exactly                                                           */
+} pbd_latent_example;
+int pbd_qp_write_latent_u8(pbd_qp* qp, const uint8_t* im, int w, int hgt, int cn, int stride, const int32_t* truth, const int32_t* mix,
+                           int component, double overlap, int id, pbd_latent_example* out);
+int pbd_qp_write_latent_dev_u8(pbd_qp* qp, const void* d_im, int w, int hgt, int cn, int stride, const int32_t* truth,
+                               const int32_t* mix, int component, double overlap, int id, pbd_latent_example* out);
+int pbd_qp_write_latent_batch_u8(pbd_qp* qp, const uint8_t* const* ims, int nframes, int w, int hgt, int cn, int stride,
+                                 const int32_t* truth, const int32_t* mix, int component, double overlap, const int32_t* ids,
+                                 pbd_latent_example* out /* [nframes] */);
+int pbd_croppos(const int32_t* truth, int nparts, int w, int hgt, int32_t roi[4], int32_t* truth_out);   /* host only */
 
 /* ---- instrumentation --------------------------------------------------------
  * GPU time (ms, hipEvent) of the stages of the last synchronous detect:

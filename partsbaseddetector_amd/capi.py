@@ -73,6 +73,7 @@ EXPORTS = [
     "pbd_debug_warp_ms",
     "pbd_set_weights", "pbd_set_weights_dev", "pbd_get_weights", "pbd_qp_apply_weights", "pbd_set_threshold", "pbd_get_threshold",
     "pbd_qp_mine_u8", "pbd_qp_mine_dev_u8", "pbd_qp_mine_batch_u8",
+    "pbd_qp_write_latent_u8", "pbd_qp_write_latent_dev_u8", "pbd_qp_write_latent_batch_u8", "pbd_croppos",
 ]
 PBD_MINE_NONE, PBD_MINE_ONE, PBD_MINE_OPT = 0, 1, 2   # pbd_qp_mine_*'s action (detect.m:148-149, 315-324)
 PBD_WARP_SKIPPED, PBD_WARP_WRITTEN, PBD_WARP_FULL = 0, 1, 2   # pbd_qp_write_warped_u8's status per box
@@ -117,6 +118,11 @@ class pbd_feature_block(C.Structure):
 FEATURE_BLOCK_DTYPE = np.dtype([("bias_id", np.int32), ("def_id", np.int32), ("filter_id", np.int32), ("kh", np.int32),
                                 ("kw", np.int32), ("reserved", np.int32), ("def", np.float64, (4,))])
 PBD_FEATVEC_STAGING_BYTES = 16 << 20
+
+
+# pbd_latent_example (include/pbd_c.h "latent positives"): one fixed block of 32 bytes per frame
+LATENT_EXAMPLE_DTYPE = np.dtype([("found", np.int32), ("written", np.int32), ("component", np.int32), ("level", np.int32),
+                                 ("x", np.int32), ("y", np.int32), ("score", np.float64)])
 
 
 CLUSTER3D_DTYPE = np.dtype([("cropped", np.int32), ("nclusters", np.int32), ("size", np.int32), ("first", np.int32),
@@ -197,6 +203,12 @@ def lib() -> C.CDLL:
                                          C.c_void_p]
         L.pbd_qp_mine_batch_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p]
+        for name in ("pbd_qp_write_latent_u8", "pbd_qp_write_latent_dev_u8"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                         C.c_double, C.c_int, C.c_void_p]
+        L.pbd_qp_write_latent_batch_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                   C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p]
+        L.pbd_croppos.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         if L.pbd_abi_version() != PBD_ABI_VERSION:
             raise ImportError(f"{LIB_PATH}: ABI version {L.pbd_abi_version()}, this binding is for {PBD_ABI_VERSION}")
         _lib = L
@@ -1292,6 +1304,20 @@ def warp_taps(n_in, n_out):
     return idx, w
 
 
+def croppos(truth, nparts, w, hgt):
+    """pbd_croppos (host code, no GPU): croppos.m for the first `nparts` truth boxes ((x, y, width, height), 0-based, covering
+    x .. x + width) of a w x hgt frame -> (roi (x, y, width, height) of the crop, truth_out [nparts, 4] relative to it).  The crop is
+    the view im[roi[1]:roi[1] + roi[3], roi[0]:roi[0] + roi[2]]."""
+    t = np.ascontiguousarray(np.asarray(truth, np.int32).reshape(-1, 4)[:int(nparts)])
+    if len(t) < int(nparts):
+        raise ValueError("croppos: fewer truth boxes than nparts")
+    roi, out = np.zeros(4, np.int32), np.zeros_like(t)
+    rc = lib().pbd_croppos(_vp(t), int(nparts), int(w), int(hgt), _vp(roi), _vp(out))
+    if rc != PBD_OK:
+        raise PbdError(rc, "pbd_croppos")
+    return tuple(int(v) for v in roi), out
+
+
 class QpCache:
     """pbd_qp (include/pbd_c.h "training example cache"): the QP's cache of block-sparse examples on the device — qp_write.m,
     matlab/mex/score.cc and lincomb.cc — and the coordinate-descent solver over it (qp_one_sparse.cc, qp_one.m, qp_refresh.m, qp_opt.m,
@@ -1518,6 +1544,47 @@ class QpCache:
         rc = self.L.pbd_qp_mine_batch_u8(self.q, ptrs, len(frames), w, hgt, cn, stride, _vp(ids), _vp(rec), _vp(wr), C.byref(act))
         self._mine_chk(rc, rec)
         return rec, wr, act.value
+
+    # ---- latent positives (include/pbd_c.h "latent positives") ----
+    def write_latent(self, im, truth, overlap, id: int, mix=None, component=-1):
+        """pbd_qp_write_latent_u8: train.m:187's detect(im, model, 0, bbox, overlap, id, 1) on the cache's handle — the frame is
+        detected as Handle.detect_latent would detect it, its pose stays on the device and becomes one example of label +1 -> the
+        frame's block, a LATENT_EXAMPLE_DTYPE record (found, written, component, level, x, y, score).  found = 0: no pose, nothing
+        written; found = 1, written = 0: the cache was full.  After a refused call the block is in `last_latent`."""
+        im, w, hgt, cn, stride = _frame(im)
+        tr, mx = self.handle._latent_args(truth, mix)
+        out = np.zeros(1, LATENT_EXAMPLE_DTYPE)
+        self.last_latent = out
+        self.handle._chk(self.L.pbd_qp_write_latent_u8(self.q, _vp(im), w, hgt, cn, stride, _vp(tr), _vp(mx), int(component),
+                                                       C.c_double(overlap), int(id), _vp(out)))
+        return out[0]
+
+    def write_latent_dev(self, dptr: int, w, hgt, cn, truth, overlap, id: int, mix=None, component=-1, stride=None):
+        """pbd_qp_write_latent_dev_u8: the same on a frame in device memory (an integer device pointer), read in place"""
+        tr, mx = self.handle._latent_args(truth, mix)
+        out = np.zeros(1, LATENT_EXAMPLE_DTYPE)
+        self.last_latent = out
+        self.handle._chk(self.L.pbd_qp_write_latent_dev_u8(self.q, C.c_void_p(dptr), w, hgt, cn, w * cn if stride is None else int(stride),
+                                                           _vp(tr), _vp(mx), int(component), C.c_double(overlap), int(id), _vp(out)))
+        return out[0]
+
+    def write_latent_batch(self, ims, truths, overlap, ids, mixes=None, component=-1):
+        """pbd_qp_write_latent_batch_u8: same-sized frames as one batch, a truth set (and mixture set) and an id per frame -> the
+        frames' blocks [n] (LATENT_EXAMPLE_DTYPE); the examples are those of the frames written one by one, in bits"""
+        frames, stride = _frames(ims)
+        ids = np.ascontiguousarray(ids, np.int32).ravel()
+        if not frames or len(ids) != len(frames) or len(truths) != len(frames) or any(f.shape != frames[0].shape for f in frames):
+            raise ValueError("write_latent_batch: one truth set and one id per frame, frames of one shape")
+        hgt, w = frames[0].shape[:2]
+        cn = 1 if frames[0].ndim == 2 else frames[0].shape[2]
+        tr, mx = self.handle._latent_args(np.stack([np.asarray(t, np.int32) for t in truths]),
+                                          None if mixes is None else np.stack([np.asarray(m, np.int32) for m in mixes]), len(frames))
+        ptrs = (C.c_void_p * len(frames))(*[f.ctypes.data for f in frames])
+        out = np.zeros(len(frames), LATENT_EXAMPLE_DTYPE)
+        self.last_latent = out
+        self.handle._chk(self.L.pbd_qp_write_latent_batch_u8(self.q, ptrs, len(frames), w, hgt, cn, stride, _vp(tr), _vp(mx),
+                                                             int(component), C.c_double(overlap), _vp(ids), _vp(out)))
+        return out
 
     def _mine_chk(self, rc, records):
         if rc == PBD_ERR_CAPACITY:   # (the needed count travels with the error, as Handle.detect's does)

@@ -14,6 +14,7 @@
 // Products and sums are explicit __dmul_rn / __dadd_rn: nothing is fused; no sum uses an atomic.
 #include "pbd_internal.hpp"
 #include "featvec_gather.hpp"
+#include "qp_record_check.hpp"
 #include "qp_fold.hpp"
 
 #define QM_NT 256
@@ -61,28 +62,9 @@ void launch_qp_mine_order(const MineArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_qp_mine_rank, dim3(nb < 2048 ? nb : 2048), dim3(QM_NT), 0, s, a);
 }
 
-// what pbd_qp_write refuses a record for: MINE_OK, or the first reason in its order of checks
-__device__ int mine_check(const MineArgs& a, const pbd_candidate_head* hd, const int* lc) {
-  const FeatVecArgs& fv = a.fv;
-  if (!fv_rec_ok(fv, hd)) return MINE_BAD_RECORD;
-  const int c = hd->component, lvl = hd->level, np = hd->nparts;
-  int off = 1;
-  for (int p = 0; p < np; ++p) {
-    const FvPart P = fv_part(fv, true, c, lvl, np, lc, p);
-    if (!P.ok) return MINE_BAD_RECORD;
-    off += (p == 0 ? 3 : 9) + 2 + P.kh * P.kw * PBD_FLEN;
-    if (off > a.k) return MINE_BAD_COLUMN;
-  }
-  if (a.noshare[c]) return MINE_OK;
-  // qp_write.m:34-35, exactly: the ids of the mixtures the pose picked, pairwise (rare: a component whose parts can share an id at all)
-  for (int p = 1; p < np; ++p) {
-    const FvPart P = fv_part(fv, true, c, lvl, np, lc, p);
-    for (int q = 0; q < p; ++q) {
-      const FvPart Q = fv_part(fv, true, c, lvl, np, lc, q);
-      if (P.filter_id == Q.filter_id || P.bias_id == Q.bias_id || (q > 0 && P.def_id == Q.def_id)) return MINE_BAD_REPEAT;
-    }
-  }
-  return MINE_OK;
+// what pbd_qp_write refuses a record for: MINE_OK, or the first reason in its order of checks (qp_record_check.hpp)
+__device__ __forceinline__ int mine_check(const MineArgs& a, const pbd_candidate_head* hd, const int* lc) {
+  return qp_record_check(a.fv, a.k, a.noshare, hd, lc);
 }
 
 __global__ void __launch_bounds__(QM_NT) k_qp_mine_scan(MineArgs a) {

@@ -27,8 +27,9 @@ int enter_frame(pbd_handle* h, const FrameSource& s, bool detect) {
   }
   ON_DEVICE(h);
   if ((rc = plan_frame(h, s.w, s.hgt, s.cn, s.nframes, s.depth))) return rc;
-  if (s.mine && h->compact)   // (known once the geometry is planned; nothing has been uploaded or enqueued)
-    return fail(h, PBD_ERR_UNSUPPORTED, "mining: this frame runs the compact memory plan (dp_mode 2, or automatic for large frames), whose min() reuses "
+  if ((s.mine || s.lat_write) && h->compact)   // (known once the geometry is planned; nothing has been uploaded or enqueued)
+    return fail(h, PBD_ERR_UNSUPPORTED, std::string(s.mine ? "mining" : "latent positives") +
+                                        ": this frame runs the compact memory plan (dp_mode 2, or automatic for large frames), whose min() reuses "
                                         "the memory of the feature planes the examples are read from");
   if (!s.on_device)   // on the handle's stream, in front of the kernels
     for (int f = 0; f < s.nframes; ++f) {
@@ -42,7 +43,7 @@ int enter_frame(pbd_handle* h, const FrameSource& s, bool detect) {
   // what the frame is, once: the truth tables / gt boxes / depth images go in front of the kernels like the image
   FrameJob job;
   if (s.lat) {
-    job.kind = FRAME_LATENT;
+    job.kind = s.lat_write ? FRAME_LATENT_WRITE : FRAME_LATENT;
     if ((rc = pbd_i_latent_begin(h, *s.lat, s.nframes))) return rc;
   } else if (s.gt) {
     job.kind = FRAME_GTBOX;

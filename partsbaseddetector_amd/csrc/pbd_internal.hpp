@@ -304,6 +304,9 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   struct MineFrameOut* h_mine_out = nullptr;                               // [PBD_MAX_BATCH]: pinned
   int mine_k = 0; double mine_cneg = 0.0;   // the calling cache's column length and C, for the scan of the frame being enqueued
   RecordSet mine_in{};                      // where that frame's final records are (its route's final_buf / final_count)
+  // latent positives (pbd_qp_write_latent_*): k_qp_latent.hip behind a latent frame's back-tracking; it shares mining's order, ids and
+  // noshare buffers and mine_k / mine_in, and answers in a pinned block of its own
+  struct LatentWriteOut* h_latw_out = nullptr;                             // [PBD_MAX_BATCH]: pinned
 };
 #define PBD_MAX_BATCH 64
 
@@ -426,6 +429,7 @@ struct FrameSource {
   const LatentSource* lat;        // latent detection: the frame is masked by these boxes and yields its best pose; else null
   const GtSource* gt;             // best pose per ground-truth box: the selection runs behind the back-tracking; else null
   bool mine;                      // hard-negative mining (pbd_qp_mine_*): the final records stay on the device
+  bool lat_write;                 // latent positives (pbd_qp_write_latent_*; with lat): the frame's pose stays on the device
 };
 // the three shapes of a source, by name (z: see above)
 inline FrameSource host_frame(const void* im, int w, int hgt, int cn, int stride, int depth, const DepthSource* z = nullptr) {
@@ -468,6 +472,9 @@ int pbd_i_gt_enqueue(pbd_handle* h, const FrameRoute& r);
 void pbd_i_gt_gather(pbd_handle* h, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int* found, double* o);
 // hard-negative mining (pbd_qp_mine.cpp): behind the last post-stage of a FRAME_MINE job, the order and the scan of its final records
 int pbd_i_mine_enqueue(pbd_handle* h, const FrameRoute& r);
+int pbd_i_mine_buffers(pbd_handle* h);   // the order, ids and noshare buffers (first use), shared with the latent positives
+// latent positives (pbd_qp_latent.cpp): behind the back-tracking (and the candidate filter) of a FRAME_LATENT_WRITE job, the scan of its poses
+int pbd_i_latent_write_enqueue(pbd_handle* h, const FrameRoute& r);
 int pbd_i_found(const pbd_handle* h);   // records the pending frame left on the host side (filtered: the kept count)
 #define PBD_FIRST_COPY 192   // candidate records fetched (or gathered) together with the count
 
@@ -719,6 +726,23 @@ struct MineArgs {
 };
 void launch_qp_mine_order(const MineArgs& a, hipStream_t s);   // RAW records only: perm sorts them by key
 void launch_qp_mine_scan(const MineArgs& a, hipStream_t s);
+// latent positives (k_qp_latent.hip, pbd_qp_latent.cpp; include/pbd_c.h "latent positives")
+struct LatentWriteOut {     // what the scan answers per frame, in pinned memory
+  int found;                // the frame has a pose
+  int code;                 // MINE_*: why pbd_qp_write would refuse its record (MINE_OK: it would not)
+  int component, level, x, y;   // the record's head: component, the frame's own level, root cell
+  int raw, reserved;        // the back-tracking's count over all frames (at most one record per frame)
+  double score;             // the record's score, widened exactly
+};
+struct LatentWriteArgs {
+  RecordSet in;             // the final records of the frame or batch: at most one per frame, not frame-aligned
+  int nframes, k;           // k: the cache's column length
+  FeatVecArgs fv;           // the model and plan tables of the gather (fv.in = in)
+  const int* noshare;       // [ncomp], as MineArgs::noshare
+  int* perm;                // [nframes] the found frames' records in frame order: what k_qp_write reads
+  LatentWriteOut* out;      // [nframes]
+};
+void launch_qp_latent_scan(const LatentWriteArgs& a, hipStream_t s);
 // a warped positive's column (train.m:152-161 qp_poswrite): window r of `feat` (T [n][wlen]) becomes example n0 + r with ids (1, ids[r], 0, 0, 0)
 struct QpPosArgs {
   QpDev q; int n0, n;

@@ -36,20 +36,6 @@ std::vector<int> noshare_table(const pbd_handle* h) {
   return out;
 }
 
-int mine_buffers(pbd_handle* h) {
-  int rc = pbd_i_fv_tables(h);
-  if (rc || h->d_mine_perm) return rc;
-  const size_t cap = (size_t)h->opt.max_candidates;
-  const std::vector<int> ns = noshare_table(h);
-  if ((rc = model_alloc(h, &h->d_mine_key, cap)) ||
-      (rc = model_alloc(h, &h->d_mine_ids, PBD_MAX_BATCH)) || (rc = model_alloc(h, &h->h_mine_ids, PBD_MAX_BATCH, true, false)) ||
-      (rc = model_alloc(h, &h->d_mine_noshare, ns.size())) || (rc = model_alloc(h, &h->h_mine_out, PBD_MAX_BATCH, true, false)) ||
-      (rc = model_alloc(h, &h->d_mine_perm, cap)))
-    return rc;
-  HIPCHK(h, hipMemcpy(h->d_mine_noshare, ns.data(), sizeof(int) * ns.size(), hipMemcpyHostToDevice));
-  return PBD_OK;
-}
-
 // detect.m:148-149, :315-324 on the state the call left.  ub == 0: lb / ub is +-inf or NaN as IEEE has it; NaN > .05 is false, as in MATLAB
 int mine_action(const pbd_qp* q) {
   const QpSolveState& S = q->sol;
@@ -75,7 +61,7 @@ int mine_run(pbd_qp* q, FrameSource s, const int32_t* ids, int32_t* records, int
   int rc;
   // (what can be refused from the arguments and the settings alone has been; the compact plan, an overflow and a bad record are known
   //  only once the frame has run.  The solver state allocated here starts at a = 0, sv = 1, ub = 0: what any solver entry would find)
-  if ((rc = pbd_i_qp_ensure(q)) || (rc = mine_buffers(h))) return rc;
+  if ((rc = pbd_i_qp_ensure(q)) || (rc = pbd_i_mine_buffers(h))) return rc;
   const int B = s.nframes;
   HIPCHK(h, hipStreamSynchronize(h->stream));   // (the pinned staging copy of the ids is read by the copy below)
   std::copy(ids, ids + B, h->h_mine_ids);
@@ -123,6 +109,21 @@ int mine_run(pbd_qp* q, FrameSource s, const int32_t* ids, int32_t* records, int
   return PBD_OK;
 }
 }  // namespace
+
+// the order, the ids and the per-component noshare flags: model-lifetime buffers, allocated on first use (pbd_qp_latent.cpp shares them)
+int pbd_i_mine_buffers(pbd_handle* h) {
+  int rc = pbd_i_fv_tables(h);
+  if (rc || h->d_mine_perm) return rc;
+  const size_t cap = (size_t)h->opt.max_candidates;
+  const std::vector<int> ns = noshare_table(h);
+  if ((rc = model_alloc(h, &h->d_mine_key, cap)) ||
+      (rc = model_alloc(h, &h->d_mine_ids, PBD_MAX_BATCH)) || (rc = model_alloc(h, &h->h_mine_ids, PBD_MAX_BATCH, true, false)) ||
+      (rc = model_alloc(h, &h->d_mine_noshare, ns.size())) || (rc = model_alloc(h, &h->h_mine_out, PBD_MAX_BATCH, true, false)) ||
+      (rc = model_alloc(h, &h->d_mine_perm, cap)))
+    return rc;
+  HIPCHK(h, hipMemcpy(h->d_mine_noshare, ns.data(), sizeof(int) * ns.size(), hipMemcpyHostToDevice));
+  return PBD_OK;
+}
 
 // behind the route's last post-stage (run_argmin_enqueue): the records' order (RAW) and the scan
 int pbd_i_mine_enqueue(pbd_handle* h, const FrameRoute& r) {

@@ -24,7 +24,8 @@ enum FrameKind {
   FRAME_LATENT,   // masked by truth boxes, yields its best pose (its tables: pbd_i_latent_begin)
   FRAME_GTBOX,    // the selection per ground-truth box runs behind the back-tracking (its tables: pbd_i_gt_begin)
   FRAME_STAGE,    // pbd_dp_argmin / pbd_dp_argbest: the back-tracking of resident tables, no frame entry and no post-stage
-  FRAME_MINE      // pbd_qp_mine_*: the final records stay on the device for the example cache's scan and write; only a count comes back
+  FRAME_MINE,     // pbd_qp_mine_*: the final records stay on the device for the example cache's scan and write; only a count comes back
+  FRAME_LATENT_WRITE   // pbd_qp_write_latent_*: a FRAME_LATENT whose pose stays on the device like a mining frame's records
 };
 struct FrameJob {
   FrameKind kind = FRAME_PLAIN;
@@ -106,15 +107,16 @@ inline bool route_frame(const RouteSettings& s, const FrameJob& job, FrameRoute*
   const bool filtered = cm != PBD_CAND_RAW;
   const bool zf = k == FRAME_DEPTH && s.zf_on;
   const bool post = zf || filtered;
-  const bool mine = k == FRAME_MINE;
+  const bool latw = k == FRAME_LATENT_WRITE;
+  const bool mine = k == FRAME_MINE || latw;   // the example cache reads the final records where they are
   const bool dev = s.member || mine;   // the final records stay in DEV_OUT
   const bool zero_copy = s.zero_copy && !dev;
   if (k == FRAME_GTBOX && (filtered || s.zf_on || s.b3_on || s.cl3_on || s.ps_on)) return false;   // pbd_i_gt_check
   if (s.member && (k == FRAME_DEPTH || k == FRAME_LATENT || k == FRAME_GTBOX || s.b3_on || s.ps_on)) return false;   // the setters and the latent / gt checks
-  if (mine && (s.member || s.compact || s.zf_on || s.b3_on || s.cl3_on || s.ps_on)) return false;   // pbd_qp_mine_*'s own refusals
+  if (mine && (s.member || s.compact || s.zf_on || s.b3_on || s.cl3_on || s.ps_on)) return false;   // pbd_qp_mine_*'s and pbd_qp_write_latent_*'s own refusals
 
   FrameRoute r;
-  r.latent = k == FRAME_LATENT;
+  r.latent = k == FRAME_LATENT || latw;
   r.gt = k == FRAME_GTBOX;
   r.bt.on = true;
   r.bt.out_count = CNT_DEV;

@@ -1,4 +1,4 @@
-// pbd_warp.cpp — the warped positives' planner (pbd_warp.hpp) and its two exported entries.  Host-only, double arithmetic in the
+// pbd_warp.cpp — the warped positives' planner (pbd_warp.hpp) and its two exported entries, and pbd_croppos (croppos.m).  Host-only, double arithmetic in the
 // order include/pbd_c.h states; built with -ffp-contract=off.
 #include <cmath>
 #include "pbd_warp.hpp"
@@ -78,6 +78,35 @@ int pbd_warp_taps(int n_in, int n_out, int32_t* index, double* weight, int capac
     if (index) index[i] = idx[i];
     if (weight) weight[i] = w[i];
   }
+  return PBD_OK;
+}
+
+// croppos.m: the crop around a positive's part boxes, in MATLAB's 1-based terms, in double, with MATLAB's round (std::round: halves
+// away from zero — pad is a multiple of 0.5, so halves occur, and round(a + 1) != round(a) + 1 for negative halves)
+int pbd_croppos(const int32_t* truth, int nparts, int w, int hgt, int32_t roi[4], int32_t* truth_out) {
+  if (!truth || !roi || nparts < 1 || w < 1 || hgt < 1) return PBD_ERR_ARG;
+  double X1 = 0, Y1 = 0, X2 = 0, Y2 = 0;
+  for (int p = 0; p < nparts; ++p) {
+    const int32_t* t = truth + (size_t)p * 4;
+    if (t[2] < 0 || t[3] < 0) return PBD_ERR_ARG;
+    const double x1 = (double)t[0] + 1, y1 = (double)t[1] + 1, x2 = (double)t[0] + (double)t[2] + 1, y2 = (double)t[1] + (double)t[3] + 1;
+    if (p == 0 || x1 < X1) X1 = x1;
+    if (p == 0 || y1 < Y1) Y1 = y1;
+    if (p == 0 || x2 > X2) X2 = x2;
+    if (p == 0 || y2 > Y2) Y2 = y2;
+  }
+  const double pad = 0.5 * ((X2 - X1 + 1) + (Y2 - Y1 + 1));
+  const double x1 = std::fmax(1.0, std::round(X1 - pad)), y1 = std::fmax(1.0, std::round(Y1 - pad));
+  const double x2 = std::fmin((double)w, std::round(X2 + pad)), y2 = std::fmin((double)hgt, std::round(Y2 + pad));
+  if (x2 < x1 || y2 < y1) return PBD_ERR_ARG;   // the truth lies wholly outside the frame: im(y1:y2, x1:x2, :) is empty
+  roi[0] = (int32_t)x1 - 1; roi[1] = (int32_t)y1 - 1; roi[2] = (int32_t)(x2 - x1) + 1; roi[3] = (int32_t)(y2 - y1) + 1;
+  if (truth_out)
+    for (int p = 0; p < nparts; ++p) {
+      const int32_t* t = truth + (size_t)p * 4;
+      int32_t* o = truth_out + (size_t)p * 4;
+      const int32_t tx = (int32_t)((int64_t)t[0] - roi[0]), ty = (int32_t)((int64_t)t[1] - roi[1]), tw = t[2], th = t[3];   // (truth_out may be truth itself)
+      o[0] = tx; o[1] = ty; o[2] = tw; o[3] = th;
+    }
   return PBD_OK;
 }
 

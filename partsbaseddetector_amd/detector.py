@@ -520,6 +520,34 @@ class PartsBasedDetector:
         min_area = float(maxsize[0] * m.sbin) * float(maxsize[1] * m.sbin)
         return cache.write_warped(im, boxes, filter, bias, min_area, ids)
 
+    def latentPositives(self, positives, cache: "capi.QpCache", overlap: float = 0.6, first_id: int = 1):
+        """poslatent of matlab/learning/train.m:166-193: every item (image, truth[, mix]) — truth [nparts, 4] rows of x, y, width,
+        height as detect() returns them — whose parts all have a box area (width + 1) * (height + 1) of at least prod(maxsize * sbin)
+        (the largest filter rows and columns of the model, train.m:170,179-182) is cropped around its boxes (croppos.m; the crop is a
+        view, nothing is copied), and the best pose overlapping them becomes one positive of `cache` without leaving the GPU
+        (capi.QpCache.write_latent).  The image id is the item's index, first_id + i (MATLAB: 1-based), skipped items included.
+        Returns (numpositives [ncomponents]: the found poses per component, blocks: per item its capi.LATENT_EXAMPLE_DTYPE record or
+        None where the item was skipped).  Fixing the positives as support vectors (train.m:90-91) stays the caller's cache.fix."""
+        if cache.handle is not self.handle:
+            raise ValueError("latentPositives: the cache is bound to another detector")
+        m = self.handle.model
+        maxsize = m.filter_sizes().max(axis=0)
+        minsize = float(maxsize[0] * m.sbin) * float(maxsize[1] * m.sbin)
+        counts, blocks = np.zeros(m.ncomponents, np.int64), []
+        for i, item in enumerate(positives):
+            im, truth = np.asarray(item[0]), np.asarray(item[1], np.int32).reshape(-1, 4)
+            mix = item[2] if len(item) > 2 else None
+            area = (truth[:, 2].astype(np.float64) + 1) * (truth[:, 3].astype(np.float64) + 1)
+            if np.any(area < minsize):
+                blocks.append(None)
+                continue
+            (x, y, w, h), tr = capi.croppos(truth, len(truth), im.shape[1], im.shape[0])
+            blk = cache.write_latent(im[y:y + h, x:x + w], tr, overlap, first_id + i, mix)
+            blocks.append(blk)
+            if blk["found"]:
+                counts[int(blk["component"])] += 1
+        return counts, blocks
+
     def mineNegatives(self, images, cache: "capi.QpCache", first_id: int = 0, tol: float = .05, max_iter: int = 1000, seed: int = 0):
         """matlab/learning/train.m:99-108 with detect.m's optimize at frame granularity: every image is mined into `cache`
         (capi.QpCache.mine with id first_id + i: detected on this detector at its threshold — train.m uses -1, setThresh —, the records

@@ -1,6 +1,6 @@
 // demo.cpp — the reference's canonical caller (src/demo.cpp:55-118) against the MI355X path:
 //   pbd_demo model.bin image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE] [--examples FILE] [--matlab-pyramid]
-//            [--gtbox x1,y1,x2,y2[,overlap]]... [--mine FILE]...
+//            [--gtbox x1,y1,x2,y2[,overlap]]... [--mine FILE]... [--poslatent FILE x,y,w,h[;x,y,w,h...]]...
 //   pbd_demo model.bin image.raw width height channels perturb-features <responses-out.bin>
 //   pbd_demo model.bin image.raw width height channels oracle-responses <responses-in.bin>
 // deserialize -> distributeModel -> detect -> Candidate::sort, then prints the candidates (the
@@ -23,6 +23,10 @@ static std::vector<GtBox> g_warp;               // --warp x1,y1,x2,y2 (anywhere,
 // --mine FILE (anywhere, repeatable): raw frames of the image's size mined as negatives (train.m:99-108) into a cache of 256 examples,
 // Cpos = Cneg = 1, ids 0, 1, ..., at the model's threshold; per frame the records, how many were written, and the action
 static std::vector<const char*> g_mine;
+// --poslatent FILE x,y,w,h[;...] (anywhere, repeatable): raw frames of the image's size as latent positives (train.m:166-193) — one truth
+// box per part, as detect() returns boxes — into a cache of 256 examples, Cpos = Cneg = 1, ids 1, 2, ..., overlap 0.6; per frame its block
+struct PosLatent { const char* file; std::vector<Rect> truth; };
+static std::vector<PosLatent> g_poslatent;
 static void print_pose(const Candidate& c) {
   printf("%.9g %d %d", c.score(), c.component(), c.level);
   for (const Rect& r : c.parts()) printf(" %d,%d,%d,%d", r.x, r.y, r.width, r.height);
@@ -91,6 +95,31 @@ static void run(Model& model, const Mat& im, bool stagewise, int special = 0, co
     for (size_t i = 0; i < mined.size(); ++i)
       printf("Mine %zu: records %d written %d action %d\n", i, mined[i].records, mined[i].written, mined[i].action);
     printf("Cache: %d of %d examples, ub %.17g\n", cache->size(), cache->capacity(), cache->state(nullptr, nullptr, nullptr).ub);
+    return;
+  }
+  if (!g_poslatent.empty()) {
+    std::vector<Mat> frames;
+    std::vector<typename PartsBasedDetector<T>::Positive> items;
+    for (const PosLatent& pl : g_poslatent) {
+      Mat fr(im.rows, im.cols, PBD_8U, im.channels());
+      const size_t bytes = (size_t)im.rows * im.cols * im.channels();
+      FILE* f = fopen(pl.file, "rb");
+      if (!f || fread(fr.ptr<uint8_t>(), 1, bytes, f) != bytes) { printf("--poslatent %s: not found or not a frame of the image's size\n", pl.file); exit(-4); }
+      fclose(f);
+      frames.push_back(fr);
+    }
+    for (size_t i = 0; i < frames.size(); ++i) items.push_back({&frames[i], g_poslatent[i].truth, {}});
+    auto cache = pbd.exampleCache(256, 1.0, 1.0);
+    std::vector<pbd_latent_example> blocks;
+    const std::vector<int> numpositives = pbd.latentPositives(items, *cache, 0.6, 1, &blocks);
+    for (size_t i = 0; i < blocks.size(); ++i) {
+      const pbd_latent_example& b = blocks[i];
+      if (b.found < 0) printf("Poslatent %zu: skipped (a box below the minimum area)\n", i);
+      else printf("Poslatent %zu: found %d written %d component %d level %d x %d y %d score %.17g\n", i, b.found, b.written, b.component, b.level, b.x, b.y, b.score);
+    }
+    printf("Positives per component:");
+    for (int c : numpositives) printf(" %d", c);
+    printf("\nCache: %d of %d examples\n", cache->size(), cache->capacity());
     return;
   }
   if (stagewise) {
@@ -305,6 +334,26 @@ int main(int argc, char** argv) {
       for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
       argc -= 2; --i;
     } else
+    if (std::string(argv[i]) == "--poslatent") {
+      if (i + 2 >= argc || !*argv[i + 1] || !*argv[i + 2]) { printf("--poslatent FILE x,y,w,h[;x,y,w,h...]\n"); exit(-1); }
+      PosLatent pl{argv[i + 1], {}};
+      const char* p = argv[i + 2];
+      bool ok = true;
+      while (ok && *p) {
+        long v[4] = {0, 0, 0, 0};
+        for (int n = 0; n < 4 && ok; ++n) {
+          char* end = nullptr;
+          v[n] = strtol(p, &end, 10);
+          ok = end != p && (n < 3 ? *end == ',' : (*end == ';' || !*end));
+          p = *end ? end + 1 : end;
+        }
+        if (ok) pl.truth.push_back(Rect{(int)v[0], (int)v[1], (int)v[2], (int)v[3]});
+      }
+      if (!ok || pl.truth.empty()) { printf("--poslatent FILE x,y,w,h[;x,y,w,h...]: one box of integers per part, as detect() returns boxes\n"); exit(-1); }
+      g_poslatent.push_back(pl);
+      for (int k = i; k + 3 < argc; ++k) argv[k] = argv[k + 3];
+      argc -= 3; --i;
+    } else
     if (std::string(argv[i]) == "--examples") {
       if (i + 1 >= argc || !*argv[i + 1]) { printf("--examples FILE\n"); exit(-1); }
       g_examples_file = argv[i + 1];
@@ -328,7 +377,7 @@ int main(int argc, char** argv) {
       --argc; --i;
     }
   if (argc < 6 || argc > 8) {
-    printf("Usage: pbd_demo model_file image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE] [--examples FILE] [--nms-parts OVERLAP] [--matlab-pyramid] [--gtbox x1,y1,x2,y2[,overlap]]... [--warp x1,y1,x2,y2]... [--mine FILE]...\n");
+    printf("Usage: pbd_demo model_file image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE] [--examples FILE] [--nms-parts OVERLAP] [--matlab-pyramid] [--gtbox x1,y1,x2,y2[,overlap]]... [--warp x1,y1,x2,y2]... [--mine FILE]... [--poslatent FILE x,y,w,h[;x,y,w,h...]]...\n");
     exit(-1);
   }
   // determine the type of model to read (src/demo.cpp:63-82)
@@ -358,6 +407,7 @@ int main(int argc, char** argv) {
     if (g_examples_file && (special || !g_gtbox.empty())) { printf("--examples: not with %s\n", special ? mode.c_str() : "--gtbox"); exit(-1); }
     if (!g_warp.empty() && (special || stagewise || !g_gtbox.empty() || g_examples_file || features_file || part_scores || nms_parts)) { printf("--warp: on its own (or with double)\n"); exit(-1); }
     if (!g_mine.empty() && (special || stagewise || !g_gtbox.empty() || !g_warp.empty() || g_examples_file || features_file || part_scores)) { printf("--mine: on its own (or with double, --pad, --nms-parts, --matlab-pyramid)\n"); exit(-1); }
+    if (!g_poslatent.empty() && (special || stagewise || !g_gtbox.empty() || !g_warp.empty() || !g_mine.empty() || g_examples_file || features_file || part_scores)) { printf("--poslatent: on its own (or with double, --pad, --nms-parts, --matlab-pyramid)\n"); exit(-1); }
     if (!g_gtbox.empty() && (part_scores || nms_parts || features_file)) { printf("--gtbox: not with --part-scores, --nms-parts or --features\n"); exit(-1); }
     if (mode.find("double") != std::string::npos) run<double>(model, im, stagewise, 0, nullptr, part_scores, pad, features_file, nms_parts, matlab_pyramid);
     else run<float>(model, im, stagewise, special, special ? argv[7] : nullptr, part_scores, pad, features_file, nms_parts, matlab_pyramid);

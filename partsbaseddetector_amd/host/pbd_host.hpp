@@ -678,6 +678,12 @@ class PartsBasedDetector {
   void distributeModel(Model& model) {             // src/PartsBasedDetector.cpp:102-127
     name_ = model.name();
     ncomponents_ = model.ncomponents();
+    min_area_ = 0;   // prod(maxsize * sbin), train.m:170: the largest filter rows and columns of the model
+    {
+      int mh = 0, mw = 0;
+      for (const Mat& f : model.filters()) { mh = std::max(mh, f.rows); mw = std::max(mw, f.cols / std::max(model.flen(), 1)); }
+      min_area_ = (double)(mh * model.binsize()) * (double)(mw * model.binsize());
+    }
     // DataType<T>::type selects the instantiation (:110,113-117)
     dev_ = std::make_shared<Device>(model, device_, conv_mode_, (int)DataType<T>::scalar, max_candidates_);
     features_.reset(new HipHOGFeatures(dev_, model.binsize(), model.nscales()));
@@ -918,6 +924,30 @@ class PartsBasedDetector {
       dev_->check(pbd_qp_mine_u8(q_, im.ptr<uint8_t>(), im.cols, im.rows, im.channels(), (int)im.step(), id, &m.records, &m.written, &m.action));
       return m;
     }
+    // ---- latent positives (include/pbd_c.h "latent positives") ----
+    // train.m:187's detect(im, model, 0, bbox, overlap, id, 1) on the detector this cache is bound to: the best pose whose every part
+    // overlaps its box in `truth` (as detectLatent takes them) stays on the device and becomes one example of label +1.  roi (optional;
+    // x, y, width, height as pbd_croppos gives it): the frame is that view of `im`, read in place; `truth` is then relative to it.
+    // found = 0: no pose, nothing written; found = 1, written = 0: the cache was full.
+    pbd_latent_example writeLatent(const Mat& im, const std::vector<Rect>& truth, double overlap, int id,
+                                   const std::vector<int>& mix = std::vector<int>(), int component = -1, const int32_t* roi = nullptr) {
+      if (im.depth() != PBD_8U) throw Exception(PBD_ERR_UNSUPPORTED, "latent positives: 8-bit frames only");
+      const int mp = pbd_max_parts(dev_->h), cn = im.channels();
+      std::vector<int32_t> tr((size_t)mp * 4, 0), mx((size_t)mp, -1);
+      for (size_t p = 0; p < truth.size() && p < (size_t)mp; ++p) {
+        tr[p * 4] = truth[p].x; tr[p * 4 + 1] = truth[p].y; tr[p * 4 + 2] = truth[p].width; tr[p * 4 + 3] = truth[p].height;
+      }
+      for (size_t p = 0; p < mix.size() && p < (size_t)mp; ++p) mx[p] = mix[p];
+      int x = 0, y = 0, w = im.cols, h = im.rows;
+      if (roi) {
+        x = roi[0]; y = roi[1]; w = roi[2]; h = roi[3];
+        if (x < 0 || y < 0 || w < 1 || h < 1 || x + w > im.cols || y + h > im.rows) throw Exception(PBD_ERR_ARG, "ExampleCache::writeLatent: roi outside the frame");
+      }
+      pbd_latent_example out{};
+      dev_->check(pbd_qp_write_latent_u8(q_, im.ptr<uint8_t>(y) + (size_t)x * cn, w, h, cn, (int)im.step(), tr.data(), mix.empty() ? nullptr : mx.data(),
+                                         component, overlap, id, &out));
+      return out;
+    }
     // find(qp.sv) shuffled as pbd_qp_opt shuffles its first pass: Fisher-Yates from the back, SplitMix64(seed) modulo the positions left
     std::vector<int32_t> shuffledSupport(uint64_t seed) {
       std::vector<unsigned char> sv;
@@ -991,7 +1021,39 @@ class PartsBasedDetector {
     dev_->check(pbd_qp_write(cache.q_, heads.data(), locs.data(), (int)n, label, id, &written));
     return written;
   }
+  // poslatent of matlab/learning/train.m:166-193: every item whose parts all have a box area (width + 1) * (height + 1) of at least
+  // prod(maxsize * sbin) is cropped around its boxes (croppos.m: a view, nothing is copied) and its best overlapping pose becomes one
+  // positive of `cache` on the GPU (ExampleCache::writeLatent).  The image id is first_id + the item's index (MATLAB: 1-based), skipped
+  // items included.  numpositives[c]: the found poses of component c; blocks (optional): per item its block, found = -1 where skipped.
+  struct Positive { const Mat* im; std::vector<Rect> truth; std::vector<int> mix; };
+  std::vector<int> latentPositives(const std::vector<Positive>& positives, ExampleCache& cache, double overlap = 0.6, int first_id = 1,
+                                   std::vector<pbd_latent_example>* blocks = nullptr) {
+    if (!dev_) throw Exception(PBD_ERR_STATE, "latentPositives() before distributeModel()");
+    std::vector<int> numpositives((size_t)ncomponents_, 0);
+    if (blocks) blocks->clear();
+    for (size_t i = 0; i < positives.size(); ++i) {
+      const Positive& P = positives[i];
+      pbd_latent_example blk{};
+      blk.found = -1;
+      bool small = P.truth.empty();
+      for (const Rect& r : P.truth) small = small || ((double)r.width + 1) * ((double)r.height + 1) < min_area_;
+      if (!small) {
+        std::vector<int32_t> tr(P.truth.size() * 4), out(P.truth.size() * 4);
+        for (size_t p = 0; p < P.truth.size(); ++p) { tr[p * 4] = P.truth[p].x; tr[p * 4 + 1] = P.truth[p].y; tr[p * 4 + 2] = P.truth[p].width; tr[p * 4 + 3] = P.truth[p].height; }
+        int32_t roi[4];
+        const int rc = pbd_croppos(tr.data(), (int)P.truth.size(), P.im->cols, P.im->rows, roi, out.data());
+        if (rc != PBD_OK) throw Exception(rc, "latentPositives: the truth boxes lie outside the frame, or have a negative size");
+        std::vector<Rect> rel(P.truth.size());
+        for (size_t p = 0; p < rel.size(); ++p) rel[p] = Rect{out[p * 4], out[p * 4 + 1], out[p * 4 + 2], out[p * 4 + 3]};
+        blk = cache.writeLatent(*P.im, rel, overlap, first_id + (int)i, P.mix, -1, roi);
+        if (blk.found && blk.component >= 0 && blk.component < ncomponents_) numpositives[(size_t)blk.component]++;
+      }
+      if (blocks) blocks->push_back(blk);
+    }
+    return numpositives;
+  }
  private:
+  double min_area_ = 0;   // prod(maxsize * sbin) of the distributed model: latentPositives' minimum part area (train.m:170)
   int features_entry(const pbd_candidate_head* hd, const int32_t* lc, int n, FeatureBlock* b, float* w) { return pbd_candidates_features(dev_->h, hd, lc, n, b, w); }
   int features_entry(const pbd_candidate_head* hd, const int32_t* lc, int n, FeatureBlock* b, double* w) { return pbd_candidates_features_f64(dev_->h, hd, lc, n, b, w); }
 };
