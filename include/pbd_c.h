@@ -90,7 +90,7 @@ enum {
                          v_mfma_f64_16x16x4_f64 for double handles             */
   PBD_CONV_SPLIT = 3, /* float handles, any kh x kw (x 32 channels): the fp32 products on the bf16 matrix units through EXACT
                          three-way splits (x = h + m + l, three bfloat16 of 8 significant bits; the six partial products above
-                         2^-24 relative on v_mfma_f32_32x32x16_bf16, fp32 accumulators): fp32 in, fp32 out, errors of the size of
+                         2^-24 relative on v_mfma_f32_16x16x32_bf16, fp32 accumulators): fp32 in, fp32 out, errors of the size of
                          PBD_CONV_MFMA's, on hardware the vector ALU does not share.  Weights must be finite
                          and below 3e38 in magnitude (bfloat16's range) — checked by pbd_create —, and so must features
                          handed in through pbd_set_level_features (HOG features are <= 0.4): an out-of-domain or non-finite
@@ -98,7 +98,7 @@ enum {
                          ordinary fp32)                                                                          */
   PBD_CONV_SPLIT_F16 = 4 /* opt-in, never what AUTO resolves to.  float handles: TWO binary16 parts per operand (11 significant
                          bits each, operands scaled by powers of two into binary16's range: features by 2^12, a bank's weights to
-                         max |w| 2^e in [2^13, 2^14)) and the THREE products above 2^-22 relative on v_mfma_f32_32x32x16_f16, fp32
+                         max |w| 2^e in [2^13, 2^14)) and the THREE products above 2^-22 relative on v_mfma_f32_16x16x32_f16, fp32
                          accumulators, responses scaled back exactly — half the matrix instructions of PBD_CONV_SPLIT.  Operands
                          are carried to 23 of their 24 bits; measured errors against fp64 on HOG features: those of
                          PBD_CONV_SPLIT.  Domain: |feature| < 15.99609375 = 65520 / 4096, where the scaled high part

@@ -6,23 +6,26 @@
 // products above 2^-24 relative (hh, hm, mh, hl, lh, mm) reproduce the fp32 product to fp32's own rounding
 // (tests/tools_split_products_study.py: max error against fp64 3.1e-7 on the person bank, 9.1e-7 for the fp32 MFMA chain of
 // k_conv_mfma16).  Why: fp32 MFMAs execute at the vector ALU's rate (157.3 TF is both peaks), so the bank and the distance
-// transforms queue for one pipe; v_mfma_f32_32x32x16_bf16 runs on the matrix cores at 16x that rate.
+// transforms queue for one pipe; the bf16 MFMAs run on the matrix cores at 16x that rate.  The shape is v_mfma_f32_16x16x32_bf16:
+// the bank runs at the chip's power limit on real operands, and the chip holds a higher clock on this shape than on 32x32x16 at the
+// same cycles per product (the 32x32x16 template is k_conv_split32_m32.hpp, tuning builds only).
 //
 // Implicit GEMM D[filter][cell] = sum over (tap, channel, product) — filters are the MFMA's A operand (rows), cells its B
-// operand (columns): an accumulator register then holds 32 cells of ONE response plane, and a store writes 64-byte row segments
-// without an LDS transpose.
+// operand (columns): an accumulator register then holds 16 cells of ONE response plane, and a store writes 64-byte row segments
+// without an LDS transpose.  One MFMA takes a tap's 32 channels (K = 32).
 //   * features: [cell][split][32 channels] bfloat16 in HBM (192 B per cell: k_feat_split, or k_hog's epilogue);
-//   * filters:  [tap][k-step (16 channels)][split][32-filter n-tile][k-group (8 channels)][32 filters][8] bfloat16 — ONE
-//     16-byte load per lane, k-step, split and n-tile, 1 KB contiguous per wavefront (host, once per model; L2-resident);
-//   * a workgroup = NW wavefronts = a 16 x 4 NW cell unit of a ConvTile (default NW = 4: the whole tile); every wavefront owns two
-//     32-cell M-tiles x NT (<= 5) 32-filter n-tiles = up to 160 accumulator registers, ONE wavefront per SIMD (the register file
-//     is the occupancy bound): per k-step 15 filter loads + 6 LDS reads feed 60 MFMAs of 32 cycles — the operand traffic of a
-//     64 x 160 register block is half the L1's rate where a 32 x 80 block saturates it (tests/tools/conv_split_probe.hip, round 4);
+//   * filters:  [tap][k-step (16 channels)][split][32-filter n-tile][k-group (8 channels)][32 filters][8] bfloat16 (host, once per
+//     model; L2-resident) — the layout of the 32x32x16 kernel, shared with k_weights.hip and the tuning variants: a lane loads the
+//     16 bytes of (filter lane & 15 of a 16-filter half, channel group lane >> 4 = k-step, k-group), a wavefront four 256-byte segments;
+//   * a workgroup = NW wavefronts = a 16 x 4 NW cell unit of a ConvTile (default NW = 4: the whole tile); every wavefront owns four
+//     16-cell M-tiles x 2 NT (<= 10) 16-filter tiles = up to 160 accumulator registers (40 accumulators of 4, in the accumulator
+//     file), ONE wavefront per SIMD (the register file is the occupancy bound): per tap 30 filter loads + 12 LDS reads feed 240
+//     MFMAs of 16 cycles — the 64 x 160 register block of the 32x32x16 kernel and the same 3 840 cycles;
 //   * the unit's halo tile sits in LDS as [split][cell][64 B], the four 16-byte channel groups of a cell XOR-swizzled with
-//     bits 2-3 of the cell index: the 16 lanes of a ds_read_b128 lane group read 16 consecutive cells -> 16 different
-//     16-byte bank slots (MI355X_MICROARCH.md, LDS: the lane groups are {0-3, 12-15, 20-27}, ...: the lane -> cell map of an
-//     M-tile is permuted so that each group IS one row of 16 cells);
-//   * the valid cells of a ragged unit are packed into M-tiles (level edges issue no MFMAs for cells that do not exist).
+//     bits 2-3 of the cell index.  A ds_read_b128 lane group ({0-3, 12-15, 20-27}, ...: MI355X_MICROARCH.md, LDS) holds eight
+//     columns of one channel group and eight of its neighbour: the columns of an M-tile are dealt to its cells by (cell & 3), so
+//     that the group's 16 reads fall on 16 different 16-byte bank slots on every row of a full-width unit (k_conv_split32.hpp);
+//   * the valid cells of a ragged unit are packed into M-tiles (level edges issue no MFMAs for an M-tile without a valid cell).
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
@@ -146,12 +149,14 @@ void conv_split16_filters(const float* filters, int nf, int kh, int kw, std::vec
   }
 }
 
-// The form a product handle launches — four wavefronts per workgroup = one 16 x 16 cell ConvTile, ONE workgroup per CU (298 registers per
-// wavefront), the next k-step's loads dealt out between this k-step's MFMAs (PIN = 2), groups of five n-tiles: 0.168 ms of pdf per frame in
-// batches of 8, 2 090-2 116 frames/s with three batches in flight.  One workgroup per CU leaves the CU's other LDS half and a quarter of its
+// The form a product handle launches — four wavefronts per workgroup = one 16 x 16 cell ConvTile, ONE workgroup per CU (304 registers per
+// wavefront: 144 + 160 accumulators; two 104-register distance-transform wavefronts still fit on the SIMD), the next step's filter loads
+// pinned between this step's MFMAs, groups of five n-tiles.  On the 16x16x32 shape, alternating with the 32x32x16 form on one MI355X
+// (profiles/split_bank_16x16x32/): 0.166-0.170 against 0.174-0.182 ms of pdf per frame in batches of 16, 2 540-2 571 against 2 411-2 450
+// frames/s with three batches in flight.  One workgroup per CU leaves the CU's other LDS half and a quarter of its
 // registers to a distance-transform block of another batch in flight, whose integer / fp64 vector work issues beside bf16 MFMAs
-// (tests/tools/mfma_valu_overlap_probe.hip: 0.5-0.75 of the shorter one hidden; fp32 FMAs: none).  What it was measured against:
-// k_conv_split_variants.hip (tune and probe libraries only).
+// (tests/tools/mfma_valu_overlap_probe.hip: 0.5-0.75 of the shorter one hidden; fp32 FMAs: none).  What the 32x32x16 form was measured
+// against: k_conv_split_variants.hip (tune and probe libraries only; its variant 9 is that form itself).
 // nf_stride > 0: a size group of a mixed bank (nf: the group's filters, nf_stride: the planes of a level block; tiles: the group's list)
 void launch_conv_split(const ConvTile* tiles, int ntiles, const LevelDev* levels, const uint16_t* feat_split, const uint16_t* wS,
                        float* resp, int nf, int kh, int kw, hipStream_t s, int nf_stride) {

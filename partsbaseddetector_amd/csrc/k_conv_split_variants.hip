@@ -8,7 +8,9 @@
 int conv_split_ntiles(int nf);   // k_conv_split.hip
 
 namespace conv_variants {   // own instantiations of the shared templates: no kernel handle shared with k_conv_split.hip
-#include "k_conv_split32.hpp"
+// the template on v_mfma_f32_32x32x16 (32-cell M-tiles, 32-filter n-tiles), which every form below was measured on — the product's until its
+// K loop moved to 16x16x32 (k_conv_split32.hpp): variant 9 runs it in the product's form
+#include "k_conv_split32_m32.hpp"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // k_conv_split32p — the 5 x 5 bank as a PERSISTENT workgroup with the tile staging hidden under the MFMAs.  In k_conv_split32
@@ -258,14 +260,16 @@ static void launch_conv_split_persistent(const ConvTile* tiles, int ntiles, cons
 
 }   // namespace conv_variants
 
-// PBD_SPLIT_VARIANT.  0 is the product's (k_conv_split.hip): four wavefronts per workgroup, the next k-step's loads dealt out between this
-// k-step's MFMAs, groups of five n-tiles.  Measured on the MI355X (profiles/r05*: pdf per frame
+// PBD_SPLIT_VARIANT.  0 (and 9) is the form that was the product's on this shape: four wavefronts per workgroup, the next k-step's loads dealt
+// out between this k-step's MFMAs, groups of five n-tiles.  Measured on the MI355X (profiles/r05*: pdf per frame
 // in batches of 8 / whole-pipeline frames per second with three batches in flight): 0.168 ms / 2 090-2 116; the same with the loads
 // issued as a block in front of the MFMAs 0.180 / 1 900; two-wavefront workgroups (16 x 8 cell units, two per CU) 0.174 / 1 830
 // and 0.186 / 1 830; hipcc's own schedule (loads sunk to their uses, 240 registers, two wavefronts per SIMD) 0.187 / 1 960 with
 // four wavefronts per workgroup, 0.225 / 1 685 with two.
 // 1 = loads as a block, 2 / 3 = the two-wavefront forms of 0 / 1, 4 / 5 = hipcc's schedule (4 / 2 wavefronts), 6 = the persistent kernel
 // (5 x 5 banks), 7 / 8 = groups of four / three n-tiles (+ remainder).  The binary16 bank (PBD_CONV_SPLIT_F16) has 4, 7 and 8.
+// 9 = the form that was the product's on the 32x32x16 shape (<4, 2, 3>, groups of five), to run beside the 16x16x32 product kernel.
+// Every variant here runs the 32x32x16 template.
 void launch_conv_split_variant(const pbd_handle* h, int variant) {
   using namespace conv_variants;
   const pbd_model_desc& m = h->md;
