@@ -16,7 +16,8 @@ w_n * 1 for channel 31, else 0) and a k-step's matrix instruction adds at most o
       mode drops m m by design); every scaled part is a normal binary16.
   kind "f64" adds AF: 24-bit features x 24-bit weights, a 48-bit product — exact in fp64 only (double handles).
   Placement: (t_n, c_n) rotate with n and with the round r; over the ROUNDS banks of a size every tap and channel occurs, every filter slot
-  sees all four 8-channel groups (both k-steps x both k-groups) in rounds 0-3 and channel 31 in the last round.
+  sees all four 8-channel groups (both k-steps x both k-groups) in rounds 0-3 and channel 31 in the last round — at a tap other than the
+  anchor, so that the weight meets the border's 1 (a 1 x 1 filter has the anchor only: no response of it reads outside the level).
 Family B — dense small integers (multiples of one unit u, sum |f| |w| / u < 2^24 over the worst window, border included): exact in any
   order, whole-K accumulation.  B1: 6-bit features x 4-bit weights; B2: 11-bit features x {0, +-1, +-2} 2^j; B3: 11-bit weights x {1, 2} 2^j."""
 import numpy as np
@@ -27,6 +28,16 @@ FRAMES = [(174, 161), (88, 299)]          # w x h; tests/test_exact_bank_cases_c
 BANKS = [(16, 5, 5), (33, 5, 5), (161, 5, 5), (33, 3, 3), (33, 9, 9), (33, 3, 7), (33, 6, 4)]   # (filters, kh, kw)
 MIXED_SIZES = [(3, 3)] * 20 + [(5, 5)] * 37 + [(3, 7)] * 12      # size groups of 20 / 37 / 12: both boundaries inside an n-tile
 ROUNDS = 5
+# The split banks' instantiation matrix (tests/test_gpu_split_bank_matrix.py; what these banks reach in k_conv_split32: tests/split_bank_census.py,
+# asserted by tests/test_split_bank_matrix_cpu.py).  32-filter n-tiles run in groups of five, then a remainder launch.
+MATRIX_FRAMES = [(76, 76), (33, 32)]      # w x h: levels 17 x 17 .. 4 x 4 (every count of M-tiles per wavefront) and 6 x 6, 4 x 5, 3 x 3
+MATRIX_BANKS = [(16, 6, 4), (65, 5, 5), (96, 6, 4), (97, 3, 7), (128, 2, 2), (160, 6, 4),      # first launches of 1, 3, 3, 4, 4, 5 n-tiles
+                (193, 3, 3), (225, 3, 3), (257, 3, 3), (321, 3, 3),                           # 5 + 2, 5 + 3, 5 + 4, two groups of 5 and 1 more
+                (17, 1, 1), (33, 1, 1), (17, 1, 2), (17, 2, 1), (33, 1, 2)]                   # the shortest K loops on 1 and 2 n-tiles
+MATRIX_MIXED = [(3, 3)] * 65 + [(5, 5)] * 97 + [(3, 7)] * 161 + [(6, 4)] * 16 + [(1, 1)] * 33     # size groups of 3, 4, 5 + 1, 1 and 2 n-tiles
+SWEEP_FRAME = (52, 52)                    # tests/test_gpu_filter_sizes.py: levels 11 x 11 .. 3 x 3, every one under a 16 x 16 unit
+SWEEP_FILTERS = 33
+SWEEP_SIZES = [(kh, kw) for kh in range(1, 10) for kw in range(1, 10)]      # include/pbd_c.h: kh, kw in 1..9
 BF16_EDGES = np.array([0x7FFF, 0x8000, 0x8001, 0x7F80, 0x807F, 0xFFFF], np.uint32)      # low 16 bits next to a bfloat16 rounding boundary
 F16_EDGES = np.array([0x0FFC, 0x1000, 0x1004, 0x0004, 0x1FFC, 0x0FF8], np.uint32)       # low 13 bits (22-bit mantissa) next to a binary16 one
 
@@ -34,6 +45,11 @@ F16_EDGES = np.array([0x0FFC, 0x1000, 0x1004, 0x0004, 0x1FFC, 0x0FF8], np.uint32
 def mixed_sizes():
     """MIXED_SIZES in a fixed shuffled order: the caller's filter order is not the library's size-sorted one"""
     return [MIXED_SIZES[i] for i in np.random.default_rng(5).permutation(len(MIXED_SIZES))]
+
+
+def matrix_mixed_sizes():
+    """MATRIX_MIXED in a fixed shuffled order"""
+    return [MATRIX_MIXED[i] for i in np.random.default_rng(6).permutation(len(MATRIX_MIXED))]
 
 
 def is_fp32(a):
@@ -143,8 +159,8 @@ def placements(sizes):
         for n, (kh, kw) in enumerate(sizes):
             k = r * nf + n
             tap[r, n] = (r * rank[n][1] + rank[n][0] + r) % (kh * kw)
-            if r == ROUNDS - 1:                                      # the border round: any tap but the anchor (which never leaves the level)
-                anchor = (kh // 2) * kw + kw // 2
+            if r == ROUNDS - 1 and kh * kw > 1:                      # the border round: any tap but the anchor (which never leaves the level);
+                anchor = (kh // 2) * kw + kw // 2                    # a one-tap filter has no other: its channel-31 weight meets in-level features only
                 tap[r, n] = tap[r, n] % (kh * kw - 1)
                 tap[r, n] += tap[r, n] >= anchor
             chan[r, n] = FLEN - 1 if r == ROUNDS - 1 else 8 * ((n + r) % 4) + (k // 4 + n // 32) % 8

@@ -51,10 +51,18 @@ def _oracle(orc, case, l, dtype):
 def test_reference_is_the_oracles(orc, sizes):
     """ref_pdf == oracle.orc.pdf_level, bit for bit, on every case of every kind: in float32 and float64 for the float banks' cases, in
     float32 for the binary16 bank's and in float64 for the double handles'"""
-    lv = _cpu_levels(orc)
+    _reference_is_the_oracles(orc, _cpu_levels(orc), sizes)
+
+
+def _only(cases, only):
+    return [c for c in cases if only is None or c.name.startswith(tuple(only))]
+
+
+def _reference_is_the_oracles(orc, lv, sizes, kinds=("f32", "f16", "f64"), only=None, build=X.build_cases, which=None):
+    """which: the levels compared (all); the oracle is one call per (case, level, scalar type), whatever the level's size"""
     for kind, dtypes in (("f32", (np.float32, np.float64)), ("f16", (np.float32,)), ("f64", (np.float64,))):
-        for case in X.build_cases(lv, sizes, kind):
-            for l in range(len(lv)):
+        for case in _only(build(lv, sizes, kind), only) if kind in kinds else ():
+            for l in which or range(len(lv)):
                 for dt in dtypes:
                     assert np.array_equal(_oracle(orc, case, l, dt).astype(np.float64), case.ref[l]), (kind, case.name, l, dt)
 
@@ -117,10 +125,16 @@ def test_exact_in_any_order(orc, sizes):
     """The model's retained products add up to ref_pdf exactly; family A: every subset sum of a response's non-zero partial products is an fp32
     number; family B: sum over the window of (sum of |parts| of f) x (sum of |parts| of w) < 2^24 units — no partial sum of any subset of part
     products, in any order, leaves the integers that fp32 holds exactly."""
-    lv = _cpu_levels(orc)
+    _exact_in_any_order(orc, _cpu_levels(orc), sizes)
+
+
+def _exact_in_any_order(orc, lv, sizes, only=None, models=None, build=X.build_cases):
+    """models: a dict that takes the family-A cases' SplitModel by (kind, case name), for _unnoticed on the same levels and bank"""
     for kind, _ in _kinds():
-        for case in X.build_cases(lv, sizes, kind):
+        for case in _only(build(lv, sizes, kind), only):
             m = SplitModel(case, kind)
+            if models is not None and case.delta is not None:
+                models[kind, case.name] = m
             for l in range(len(lv)):
                 assert np.array_equal(m.total(l), case.ref[l]), (kind, case.name, l)
                 if case.delta is not None:
@@ -134,21 +148,23 @@ def test_exact_in_any_order(orc, sizes):
                     assert worst < 2.0 ** 24, (kind, case.name, l, worst)
 
 
-def _unnoticed(orc, sizes, kind, families="A", drop=()):
-    """deletion -> the (filter, channel group) pairs at which NO family-A case tells the damaged bank from the reference"""
-    lv = _cpu_levels(orc)
-    cases = [c for c in X.build_cases(lv, sizes, kind, families) if not c.name.startswith(tuple(drop) or ("\0",))]
+def _unnoticed(orc, sizes, kind, families="A", drop=(), lv=None, models=None, build=X.build_cases):
+    """deletion -> the (filter, channel group) pairs at which NO family-A case tells the damaged bank from the reference.  (A one-tap filter
+    reads no cell outside the level: the border constant is no part of its responses, and nothing is asked of it there.)"""
+    lv = lv or _cpu_levels(orc)
+    cases = [c for c in build(lv, sizes, kind, families) if not c.name.startswith(tuple(drop) or ("\0",))]
     nf = len(sizes)
     seen = {}
     for case in cases:
         tap, chan = case.delta
-        for name, planes in SplitModel(case, kind).deletions().items():
+        for name, planes in (models[kind, case.name] if models else SplitModel(case, kind)).deletions().items():
             hit = np.zeros(nf, bool)
             for l in range(len(lv)):
                 hit |= (planes[l] != case.ref[l]).reshape(nf, -1).any(axis=1)
             seen.setdefault(name, set()).update((n, int(chan[n]) // 8) for n in np.flatnonzero(hit))
     want = {(n, g) for n in range(nf) for g in range(4)}
-    return {name: sorted((want if name != "border constant" else {(n, 3) for n in range(nf)}) - got) for name, got in seen.items()}
+    border = {(n, 3) for n in range(nf) if sizes[n][0] * sizes[n][1] > 1}
+    return {name: sorted((want if name != "border constant" else border) - got) for name, got in seen.items()}
 
 
 @pytest.mark.parametrize("kind,parts", _kinds(), ids=["bf16x6", "f16x3"])
@@ -157,7 +173,11 @@ def test_sensitivity(orc, sizes, kind, parts):
     """Delete, in the model, each retained partial product, each part of the features, each part of the weights and the border constant of
     channel 31: family A must then differ from ref_pdf at every (filter slot mod 32, n-tile) = filter and every 8-channel group (the border
     constant: channel 31's group)."""
-    missing = _unnoticed(orc, sizes, kind)
+    _sensitive(orc, sizes, kind)
+
+
+def _sensitive(orc, sizes, kind, lv=None, models=None, build=X.build_cases):
+    missing = _unnoticed(orc, sizes, kind, lv=lv, models=models, build=build)
     assert len(missing) == (13 if kind == "f32" else 8)
     assert not any(missing.values()), {k: v[:8] for k, v in missing.items() if v}
 
@@ -169,3 +189,61 @@ def test_sensitivity_needs_every_family(orc):
     for drop, lost in (("A1", "feature part 2"), ("A2", "weight part 2"), ("A3", "product f1 x w1")):
         missing = _unnoticed(orc, sizes, "f32", drop=(drop,))
         assert missing[lost], (drop, lost)
+
+
+# ---- the split banks' instantiation matrix and the sweep of the 81 filter sizes -----------------------------------------------------
+# (tests/test_gpu_split_bank_matrix.py, tests/test_gpu_filter_sizes.py: the same proofs on their banks, on the levels those tests run)
+MATRIX_IDS = [f"{nf}x{kh}x{kw}" for nf, kh, kw in X.MATRIX_BANKS] + ["mixed"]
+MATRIX_SIZES = [[(kh, kw)] * nf for nf, kh, kw in X.MATRIX_BANKS] + [X.matrix_mixed_sizes()]
+MATRIX_FAMILIES = ("A1", "A2", "A3", "B2")
+
+
+def _matrix_levels(orc):
+    """the matrix's second frame (6 x 6, 4 x 5, 3 x 3 cells); the sweep: the three smallest levels of its frame (6 x 6, 5 x 5, 3 x 3:
+    on fewer cells a corner tap of a 9 x 9 filter meets too few in-level features to notice every lost part).  As in _cpu_levels, the
+    properties proved here hold level by level, and the banks do not depend on the levels at all"""
+    return levels_of(orc, X.MATRIX_FRAMES[1])
+
+
+def _sweep_levels(orc):
+    return levels_of(orc, X.SWEEP_FRAME)[-3:]
+
+
+def _prove(orc, lv, sizes, kinds, only, oracle_levels=None):
+    """the three proofs above on one bank, its cases built once per kind"""
+    built = {}
+
+    def build(lv_, sizes_, kind, families="AB"):
+        assert lv_ is lv and sizes_ is sizes
+        if kind not in built:
+            built[kind] = X.build_cases(lv, sizes, kind)
+        return [c for c in built[kind] if c.name[0] in families]
+
+    _reference_is_the_oracles(orc, lv, sizes, kinds=kinds, only=only, build=build, which=oracle_levels)
+    models = {}
+    _exact_in_any_order(orc, lv, sizes, only=only, models=models, build=build)
+    for kind, _ in _kinds():
+        assert sum(k == kind for k, _ in models) == 3 * X.ROUNDS
+        _sensitive(orc, sizes, kind, lv=lv, models=models, build=build)
+
+
+def test_one_tap_filters_stay_in_the_level():
+    """a 1 x 1 filter's delta stays at its only tap, the anchor, in every round (the border round included); every other size keeps the
+    border round away from the anchor"""
+    tap, chan = X.placements([(1, 1)] * 17 + [(1, 2)] * 17 + [(2, 1)] * 17)
+    assert (tap[:, :17] == 0).all() and (chan[X.ROUNDS - 1] == X.FLEN - 1).all()
+    assert (tap[X.ROUNDS - 1, 17:34] == 0).all() and (tap[X.ROUNDS - 1, 34:] == 0).all()      # anchors (0, 1) and (1, 0): tap 1 of both
+
+
+@pytest.mark.parametrize("sizes", MATRIX_SIZES, ids=MATRIX_IDS)
+def test_matrix_banks_prove_themselves(orc, sizes):
+    """the reference is the oracle's, the cases are exact in any order under both split arithmetics, and a bank that loses one product, part
+    or the border constant differs at every filter and channel group — on the matrix's banks and families"""
+    _prove(orc, _matrix_levels(orc), sizes, ("f32", "f16"), MATRIX_FAMILIES)
+
+
+@pytest.mark.parametrize("kh,kw", X.SWEEP_SIZES, ids=[f"{kh}x{kw}" for kh, kw in X.SWEEP_SIZES])
+def test_sweep_sizes_prove_themselves(orc, kh, kw):
+    """the same for 33 filters of every documented size, for every kind of handle and every family (the oracle on the 6 x 6 level: cells
+    whose window leaves the level on one side, on two and, from 8 x 8 on, on all four)"""
+    _prove(orc, _sweep_levels(orc), [(kh, kw)] * X.SWEEP_FILTERS, ("f32", "f16", "f64"), None, oracle_levels=[0])

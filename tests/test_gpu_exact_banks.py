@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from partsbaseddetector_amd import capi
-from partsbaseddetector_amd.model import make_image, make_tree_model, make_wide_image
+from partsbaseddetector_amd.model import make_image, make_tree_model, make_tree_model_k, make_wide_image
 from tests import exact_bank_cases as X
 from tests.test_split_arith_cpu import split2_f16
 
@@ -36,7 +36,14 @@ def _cases(frame, sizes, kind):
 
 
 def _model(filters):
-    m = make_tree_model([-1] + [0] * (len(filters) - 1), 1, seed=1, sbin=X.SBIN, interval=X.INTERVAL)
+    """a star of one-mixture parts, one per filter; past the library's 256 parts per component: 256 parts, the first ones with two mixtures"""
+    nf, maxp = len(filters), 256
+    if nf <= maxp:
+        m = make_tree_model([-1] + [0] * (nf - 1), 1, seed=1, sbin=X.SBIN, interval=X.INTERVAL)
+    else:
+        assert nf <= 2 * maxp
+        m = make_tree_model_k([-1] + [0] * (maxp - 1), [2] * (nf - maxp) + [1] * (2 * maxp - nf), seed=1, sbin=X.SBIN, interval=X.INTERVAL)
+    assert len(m.filtersw) == nf
     m.filtersw = [np.ascontiguousarray(f, np.float32) for f in filters]
     return m
 
@@ -48,12 +55,13 @@ def _first_difference(got, want):
     return f"y {y} x {x}: got {g!r} (0x{g.view(bits):x}), want {w!r} (0x{w.view(bits):x})"
 
 
-def run_bank(bank, sizes, only=None):
-    """all cases of one bank geometry on both frames through begin_frame / set_level_features / pdf / level_response -> None, or the first
-    difference as text"""
+def run_bank(bank, sizes, only=None, frames=None):
+    """all cases of one bank geometry on both frames (frames: on those) through begin_frame / set_level_features / pdf / level_response ->
+    None, or the first difference as text"""
     mode, dtype, kind = BANKS[bank]
     sizes = tuple(map(tuple, sizes))
-    per_frame = [_cases(f, sizes, kind) for f in X.FRAMES]
+    frames = list(frames or X.FRAMES)
+    per_frame = [_cases(f, sizes, kind) for f in frames]
     for i, first in enumerate(per_frame[0]):
         if only and not first.name.startswith(tuple(only)):
             continue
@@ -61,7 +69,7 @@ def run_bank(bank, sizes, only=None):
         assert h.conv_mode == mode
         assert [h.filter_size(n) for n in range(len(sizes))] == list(sizes)
         try:
-            for frame, cases in zip(X.FRAMES, per_frame):
+            for frame, cases in zip(frames, per_frame):
                 case = cases[i]
                 assert all(np.array_equal(a, b) for a, b in zip(case.filters, first.filters))
                 h.begin_frame(frame[0], frame[1], 3)
