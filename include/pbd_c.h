@@ -179,7 +179,9 @@ int pbd_abi_version(void);
  * pbd_set_weights_dev, pbd_get_weights, pbd_qp_apply_weights, pbd_set_threshold and pbd_get_threshold; and hard-negative mining:
  * pbd_qp_mine_u8, pbd_qp_mine_dev_u8 and pbd_qp_mine_batch_u8 (with PBD_MINE_NONE / _ONE / _OPT); and the latent positives:
  * pbd_qp_write_latent_u8, pbd_qp_write_latent_dev_u8, pbd_qp_write_latent_batch_u8 and pbd_croppos (with the struct
- * pbd_latent_example).                                                                                                              */
+ * pbd_latent_example); and the evaluation ledger pbd_eval: pbd_eval_create, _destroy, _reset, _dims, _get, _add_pck_records,
+ * _add_apk_records, _pck_frame_u8, _pck_frame_batch_u8, _apk_frame_u8, _apk_frame_batch_u8, _pck and _apk, with the host-only
+ * definitions pbd_eval_keypoint_dist, _pck_host, _apk_match_host and _ap_host (PBD_EVAL_SCALE_LAST / _OWN).                            */
 
 /* ---- output record: include/Candidate.hpp:56-111 --------------------------
  * One candidate = head + max_parts boxes (x, y, width, height as cv::Rect)
@@ -1306,6 +1308,106 @@ int pbd_qp_write_latent_batch_u8(pbd_qp* qp, const uint8_t* const* ims, int nfra
                                  const int32_t* truth, const int32_t* mix, int component, double overlap, const int32_t* ids,
                                  pbd_latent_example* out /* [nframes] */);
 int pbd_croppos(const int32_t* truth, int nparts, int w, int hgt, int32_t roi[4], int32_t* truth_out);   /* host only */
+
+/* ---- evaluation ledger: matlab/evaluation/eval_pck.m, eval_apk.m and VOCap.m (ABI 5, additive) ---------------------------------------------
+ * What turns the output of the two test protocols — testmodel_gtbox.m (pbd_detect_gtbox_*) and testmodel.m (detect + nms.m,
+ * PBD_NMS_PARTS) — into the numbers a model is judged by.  A pbd_eval is bound to a handle as the example cache is: test frames go in with
+ * their annotated keypoints, per-instance keypoint distances (PCK) and per-detection true-positive flags (APK) accumulate on the device,
+ * per frame only counts and found flags come back, and at the end P doubles per metric: train -> pbd_qp_apply_weights -> evaluate on one
+ * handle.  Everything below is float64, the operations in the order written, never fused.  P = the ledger's number of keypoints; the
+ * keypoints of a pose are its P parts, in part order.
+ * Keypoint.  Part p of a record has box (x, y, w, h); its keypoint is the box centre of rule 1 of "best pose per ground-truth box":
+ *   x2 = x + w - 1, cx = .5 * x + .5 * x2, cy alike; exact.  (The reference tree holds no boxes-to-points conversion — the callers of
+ *   eval_pck / eval_apk were not vendored; this centre is the one bestoverlap.m:11-14 uses.)
+ * Distance (eval_pck.m:10, eval_apk.m:21): dx = cx - gx, dy = cy - gy; s = dx * dx + dy * dy (two rounded products, one rounded sum,
+ *   the x term first); d = sqrt(s), correctly rounded.
+ * PCK (eval_pck.m).  Instance n = 0 .. N-1 is one annotated person.  With a selected pose dist[n][p] = d of the pose's part p against
+ *   the person's point p; without one dist[n][p] = +Inf (our rule: eval_pck.m would fault on an empty box; the instance misses every
+ *   keypoint and stays in the denominator).  hit = dist[n][p] < thresh * s_n, strict, the product rounded once;
+ *   pck[p] = (double)hits_p / (double)N; N == 0: 0 / 0 = NaN.  Two scale rules, chosen when the result is asked for:
+ *   PBD_EVAL_SCALE_LAST: s_n = scale[N-1] for every n — eval_pck.m:13 taken literally, where gt(n) is read after the loop has ended;
+ *   PBD_EVAL_SCALE_OWN:  s_n = scale[n].
+ *   (eval_pck.m:3-5 and eval_apk.m:3-5 test nargin < 4 on three-argument functions: the reference's threshold is always 0.5.  Here it
+ *   is the caller's.)
+ * APK matching (eval_apk.m:14-36), independently per keypoint p and per frame.  The frame's detections are taken in the order (score
+ *   descending as the stored float, -0.0 == +0.0; ties by the given record order): MATLAB's stable sort(..., 'descend') restricted to the
+ *   frame.  For each detection: ngt == 0 -> false positive; else q_g = d(point_p, gtpoint[g][p]) / scale[g] (a rounded division), jmin =
+ *   the first index of the minimum; if q_jmin <= thresh and gt jmin is not yet taken for this p the detection is a true positive and gt
+ *   jmin becomes taken; in every other case it is a false positive.  A frame's flags depend on nothing outside the frame.
+ * APK result (eval_apk.m:7,38-43, VOCap.m).  All M detections of the ledger ordered by (score descending, sequence ascending; sequence =
+ *   frames in the order added, within a frame the given order); tpc, fpc the integer cumulative sums (fp = 1 - tp); npos = the sum of ngt
+ *   over every frame added, frames without detections included; rec = tpc / npos, prec = tpc / (fpc + tpc), one division each;
+ *   mrec = [0; rec; 1], mpre = [0; prec; 0] with the suffix maximum applied; ap = sum_{i=1..M+1} (mrec(i) - mrec(i-1)) * mpre(i) over ALL
+ *   i — a term whose mrec did not change is exactly +0.0, so this is the value of VOCap.m:8-9 — in the block-sum order of the "training
+ *   example cache" section (64 lane-strided partials starting at +0.0, i ascending, folded h = 32 .. 1).  M == 0: ap = 0.  npos == 0: IEEE
+ *   is followed as MATLAB follows it (rec = 0 / 0 = NaN, ap = NaN).
+ * Arguments.  Points, scales and thresholds must be finite, every scale > 0, ngt in 0..PBD_GT_MAX; scores of caller-supplied records
+ *   finite (their order is undefined otherwise): PBD_ERR_ARG.
+ *
+ * Host-only definitions (no GPU; pure host code like pbd_candidates_nms_parts):
+ *   pbd_eval_keypoint_dist   one record's boxes[nparts][4] against points[nparts][2] -> d[nparts].
+ *   pbd_eval_pck_host        dist[n][nparts] (+Inf allowed, NaN refused), scale[n], thresh, rule -> pck[nparts].
+ *   pbd_eval_apk_match_host  one frame: heads[count], boxes[count][max_parts][4] in the given order, points[ngt][nparts][2], scale[ngt]
+ *                            -> tp[count][nparts] (bytes, by given position).  A record with nparts != the argument: PBD_ERR_ARG.
+ *   pbd_eval_ap_host         score[m], tp[m][nparts], npos -> apk[nparts], and prec / rec [nparts][m] in sorted order (either may be NULL).
+ * The ledger.  pbd_eval_create(h, nparts, max_instances, max_detections, apk_thresh): PBD_ERR_ARG unless EVERY component of the handle's
+ *   model has nparts parts.  The matching threshold is the ledger's; the PCK threshold is an argument of pbd_eval_pck.  Device memory:
+ *   8 (P + 1) bytes per instance, 4 + 13 P bytes per detection, 8 per sort slot (max_detections rounded up to a power of two).
+ *   pbd_eval_reset empties it; pbd_eval_dims reports P, N, M, npos and the frames added; pbd_eval_get copies the ledger out for tests and
+ *   tools: dist[N][P], scale[N], score[M], tp[M][P] (any may be NULL).  pbd_eval_destroy before pbd_destroy.
+ * Adds.  Every add answers *needed (may be NULL) = the instances (PCK) or detections (APK) the ledger would hold after the call.  A call
+ *   that would overflow max_instances / max_detections adds NOTHING and answers PBD_ERR_CAPACITY: an evaluation that silently drops
+ *   detections is wrong (unlike qp_write.m's full cache).  Append positions are deterministic: the host knows ngt, a device scan
+ *   answers the frames' detection counts; no atomics.  All adds are synchronous.
+ *   pbd_eval_add_pck_records: the caller's ngt host records (heads[ngt], boxes[ngt][max_parts][4], max_parts = the handle's;
+ *     found[ngt]: person g has a pose) through the device kernels, appended as ngt instances.  pbd_eval_add_apk_records: ONE frame's
+ *     `count` records in the given order, matched against its ngt persons and appended as `count` rows.  A record (with a pose) whose
+ *     nparts != P refuses the whole call: PBD_ERR_ARG, nothing is added.
+ *   pbd_eval_pck_frame_u8 / _batch_u8: the frame runs exactly as pbd_detect_gtbox_u8 / pbd_detect_batch_gtbox_u8 would, with its
+ *     refusals, on the gt box [min x, min y, max x, max y] of every person's points (testmodel_gtbox.m:18-20; exact); a kernel behind the
+ *     selection reads the winners where it left them and appends the persons' columns in (frame, person) order.  found[g] = person g
+ *     has a pose; *nrecords as there.  Batch layout: points[nframes][PBD_GT_MAX][P][2], scale[nframes][PBD_GT_MAX], ngt[nframes],
+ *     found[nframes][PBD_GT_MAX].
+ *   pbd_eval_apk_frame_u8 / _batch_u8: the frame runs as pbd_detect_u8 / pbd_detect_batch_u8 would on the handle — its threshold,
+ *     candidate mode and NMS apply (testmodel.m: PBD_CAND_SORT_NMS with PBD_NMS_PARTS at 0.3) —, its final records stay on the device and
+ *     are reached by the route mining reads; RAW records are put into the plain entries' order by mining's order kernels; the matching
+ *     kernel appends the frame's (score, tp[P]) rows.  records[f] = the frame's final records.  Refusals are those of the mining entries
+ *     (group members, the compact memory plan, depth pruning, 3-D boxes, object clusters, per-part scores: PBD_ERR_UNSUPPORTED; a frame
+ *     pending: PBD_ERR_STATE; an overflow of pbd_options.max_candidates: PBD_ERR_CAPACITY with the needed count in records[0]).
+ *   Both kinds launch eagerly; like every special frame they leave plain frames and their captured graph untouched.  A _dev_u8 form is
+ *   not provided.
+ * Results.  pbd_eval_pck(ev, thresh, rule, pck[P]): one kernel counts per keypoint, for any threshold, with no re-detection.
+ *   pbd_eval_apk(ev, apk[P], prec, rec): prec / rec [P][M] in sorted order, either may be NULL.  Both equal the host definitions on
+ *   pbd_eval_get's arrays bit for bit.                                                                                                   */
+#define PBD_EVAL_SCALE_LAST 0
+#define PBD_EVAL_SCALE_OWN  1
+typedef struct pbd_eval pbd_eval;
+int pbd_eval_keypoint_dist(const int32_t* boxes, int nparts, const double* points, double* d);                      /* host only */
+int pbd_eval_pck_host(const double* dist, const double* scale, int n, int nparts, double thresh, int rule, double* pck);   /* host only */
+int pbd_eval_apk_match_host(const pbd_candidate_head* heads, const int32_t* boxes, int count, int max_parts, int nparts,
+                            const double* points, const double* scale, int ngt, double thresh, uint8_t* tp);         /* host only */
+int pbd_eval_ap_host(const float* score, const uint8_t* tp, int m, int nparts, long long npos, double* apk, double* prec,
+                     double* rec);                                                                                     /* host only */
+int pbd_eval_create(pbd_handle* h, int nparts, int max_instances, int max_detections, double apk_thresh, pbd_eval** ev);
+void pbd_eval_destroy(pbd_eval* ev);
+int pbd_eval_reset(pbd_eval* ev);
+int pbd_eval_dims(const pbd_eval* ev, int* nparts, int* n, int* m, long long* npos, int* frames);
+int pbd_eval_get(pbd_eval* ev, double* dist, double* scale, float* score, uint8_t* tp);
+int pbd_eval_add_pck_records(pbd_eval* ev, const pbd_candidate_head* heads, const int32_t* boxes, const int* found, const double* points,
+                             const double* scale, int ngt, int* needed);
+int pbd_eval_add_apk_records(pbd_eval* ev, const pbd_candidate_head* heads, const int32_t* boxes, int count, const double* points,
+                             const double* scale, int ngt, int* needed);
+int pbd_eval_pck_frame_u8(pbd_eval* ev, const uint8_t* im, int w, int hgt, int cn, int stride, const double* points, const double* scale,
+                          int ngt, double overlap, int* found, int* nrecords, int* needed);
+int pbd_eval_pck_frame_batch_u8(pbd_eval* ev, const uint8_t* const* ims, int nframes, int w, int hgt, int cn, int stride,
+                                const double* points, const double* scale, const int* ngt, double overlap, int* found, int* nrecords,
+                                int* needed);
+int pbd_eval_apk_frame_u8(pbd_eval* ev, const uint8_t* im, int w, int hgt, int cn, int stride, const double* points, const double* scale,
+                          int ngt, int* records, int* needed);
+int pbd_eval_apk_frame_batch_u8(pbd_eval* ev, const uint8_t* const* ims, int nframes, int w, int hgt, int cn, int stride,
+                                const double* points, const double* scale, const int* ngt, int32_t* records, int* needed);
+int pbd_eval_pck(pbd_eval* ev, double thresh, int rule, double* pck);
+int pbd_eval_apk(pbd_eval* ev, double* apk, double* prec, double* rec);
 
 /* ---- instrumentation --------------------------------------------------------
  * GPU time (ms, hipEvent) of the stages of the last synchronous detect:

@@ -74,7 +74,12 @@ EXPORTS = [
     "pbd_set_weights", "pbd_set_weights_dev", "pbd_get_weights", "pbd_qp_apply_weights", "pbd_set_threshold", "pbd_get_threshold",
     "pbd_qp_mine_u8", "pbd_qp_mine_dev_u8", "pbd_qp_mine_batch_u8",
     "pbd_qp_write_latent_u8", "pbd_qp_write_latent_dev_u8", "pbd_qp_write_latent_batch_u8", "pbd_croppos",
+    "pbd_eval_keypoint_dist", "pbd_eval_pck_host", "pbd_eval_apk_match_host", "pbd_eval_ap_host",
+    "pbd_eval_create", "pbd_eval_destroy", "pbd_eval_reset", "pbd_eval_dims", "pbd_eval_get", "pbd_eval_add_pck_records",
+    "pbd_eval_add_apk_records", "pbd_eval_pck_frame_u8", "pbd_eval_pck_frame_batch_u8", "pbd_eval_apk_frame_u8",
+    "pbd_eval_apk_frame_batch_u8", "pbd_eval_pck", "pbd_eval_apk",
 ]
+PBD_EVAL_SCALE_LAST, PBD_EVAL_SCALE_OWN = 0, 1   # pbd_eval_pck's scale rule: eval_pck.m:13 literally (the last instance's scale) / each instance's own
 PBD_MINE_NONE, PBD_MINE_ONE, PBD_MINE_OPT = 0, 1, 2   # pbd_qp_mine_*'s action (detect.m:148-149, 315-324)
 PBD_WARP_SKIPPED, PBD_WARP_WRITTEN, PBD_WARP_FULL = 0, 1, 2   # pbd_qp_write_warped_u8's status per box
 PBD_ABI_VERSION = 5
@@ -209,6 +214,25 @@ def lib() -> C.CDLL:
         L.pbd_qp_write_latent_batch_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                    C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p]
         L.pbd_croppos.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        V, I, D = C.c_void_p, C.c_int, C.c_double
+        L.pbd_eval_keypoint_dist.argtypes = [V, I, V, V]
+        L.pbd_eval_pck_host.argtypes = [V, V, I, I, D, I, V]
+        L.pbd_eval_apk_match_host.argtypes = [V, V, I, I, I, V, V, I, D, V]
+        L.pbd_eval_ap_host.argtypes = [V, V, I, I, C.c_longlong, V, V, V]
+        L.pbd_eval_create.argtypes = [V, I, I, I, D, V]
+        L.pbd_eval_destroy.restype = None
+        L.pbd_eval_destroy.argtypes = [V]
+        L.pbd_eval_reset.argtypes = [V]
+        L.pbd_eval_dims.argtypes = [V] * 6
+        L.pbd_eval_get.argtypes = [V] * 5
+        L.pbd_eval_add_pck_records.argtypes = [V, V, V, V, V, V, I, V]
+        L.pbd_eval_add_apk_records.argtypes = [V, V, V, I, V, V, I, V]
+        L.pbd_eval_pck_frame_u8.argtypes = [V, V, I, I, I, I, V, V, I, D, V, V, V]
+        L.pbd_eval_pck_frame_batch_u8.argtypes = [V, V, I, I, I, I, I, V, V, V, D, V, V, V]
+        L.pbd_eval_apk_frame_u8.argtypes = [V, V, I, I, I, I, V, V, I, V, V]
+        L.pbd_eval_apk_frame_batch_u8.argtypes = [V, V, I, I, I, I, I, V, V, V, V, V]
+        L.pbd_eval_pck.argtypes = [V, D, I, V]
+        L.pbd_eval_apk.argtypes = [V, V, V, V]
         if L.pbd_abi_version() != PBD_ABI_VERSION:
             raise ImportError(f"{LIB_PATH}: ABI version {L.pbd_abi_version()}, this binding is for {PBD_ABI_VERSION}")
         _lib = L
@@ -618,7 +642,7 @@ class Handle:
 
     def close(self):
         if getattr(self, "h", None):
-            for ref in getattr(self, "_caches", ()):   # the example caches created from this handle go first: they borrow its device
+            for ref in getattr(self, "_caches", ()):   # the example caches and evaluation ledgers created from this handle go first: they borrow its device
                 q = ref()
                 if q is not None:
                     q.close()
@@ -1597,6 +1621,218 @@ class QpCache:
     def close(self):
         if getattr(self, "q", None):   # (a live cache implies a live handle: Handle.close() closes its caches before itself)
             self.L.pbd_qp_destroy(self.q)
+        self.q = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- evaluation: eval_pck.m, eval_apk.m, VOCap.m (include/pbd_c.h "evaluation ledger") ------------------------------------------------
+def _persons(points, scale, P=None):
+    """(points [ngt, P, 2] float64, scale [ngt] float64) of one frame's annotated persons"""
+    scale = np.ascontiguousarray(scale, np.float64).reshape(-1)
+    points = np.ascontiguousarray(points, np.float64)
+    points = points.reshape(len(scale), -1, 2) if P is None else points.reshape(len(scale), P, 2)
+    return points, scale
+
+
+def eval_keypoint_dist(boxes, points):
+    """pbd_eval_keypoint_dist (host code, no GPU): one record's part boxes [P, 4] against points [P, 2] -> d [P]"""
+    boxes = np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
+    points = np.ascontiguousarray(points, np.float64).reshape(len(boxes), 2)
+    d = np.zeros(len(boxes), np.float64)
+    rc = lib().pbd_eval_keypoint_dist(_vp(boxes), len(boxes), _vp(points), _vp(d))
+    if rc != PBD_OK:
+        raise PbdError(rc, "pbd_eval_keypoint_dist")
+    return d
+
+
+def eval_pck_host(dist, scale, thresh=.5, rule=PBD_EVAL_SCALE_LAST):
+    """pbd_eval_pck_host (host code, no GPU): dist [N, P], scale [N] -> pck [P]"""
+    dist = np.ascontiguousarray(dist, np.float64)
+    scale = np.ascontiguousarray(scale, np.float64).reshape(-1)
+    if dist.ndim != 2 or len(dist) != len(scale):
+        raise ValueError("eval_pck_host: dist [N, P], scale [N]")
+    pck = np.zeros(dist.shape[1], np.float64)
+    rc = lib().pbd_eval_pck_host(_vp(dist), _vp(scale), len(scale), dist.shape[1], float(thresh), int(rule), _vp(pck))
+    if rc != PBD_OK:
+        raise PbdError(rc, "pbd_eval_pck_host")
+    return pck
+
+
+def eval_apk_match_host(heads, boxes, points, scale, nparts, thresh=.5):
+    """pbd_eval_apk_match_host (host code, no GPU): one frame's records in the given order against its persons -> tp [count, nparts] uint8"""
+    heads = np.ascontiguousarray(heads, HEAD_DTYPE)
+    boxes = np.ascontiguousarray(boxes, np.int32)
+    if boxes.ndim != 3 or boxes.shape[0] != len(heads) or boxes.shape[2] != 4:
+        raise ValueError("eval_apk_match_host: boxes [count, max_parts, 4]")
+    points, scale = _persons(points, scale, nparts)
+    tp = np.zeros((len(heads), nparts), np.uint8)
+    rc = lib().pbd_eval_apk_match_host(_vp(heads), _vp(boxes), len(heads), boxes.shape[1], int(nparts), _vp(points), _vp(scale), len(scale),
+                                       float(thresh), _vp(tp))
+    if rc != PBD_OK:
+        raise PbdError(rc, "pbd_eval_apk_match_host")
+    return tp
+
+
+def eval_ap_host(score, tp, npos, curves=False):
+    """pbd_eval_ap_host (host code, no GPU): score [M], tp [M, P], npos -> apk [P] (curves: also prec, rec [P, M] in sorted order)"""
+    score = np.ascontiguousarray(score, np.float32).reshape(-1)
+    tp = np.ascontiguousarray(tp, np.uint8)
+    if tp.ndim != 2 or tp.shape[0] != len(score):
+        raise ValueError("eval_ap_host: tp [M, P]")
+    P = tp.shape[1]
+    apk = np.zeros(P, np.float64)
+    prec, rec = (np.zeros((P, len(score)), np.float64), np.zeros((P, len(score)), np.float64)) if curves else (None, None)
+    rc = lib().pbd_eval_ap_host(_vp(score), _vp(tp), len(score), P, int(npos), _vp(apk), _vp(prec), _vp(rec))
+    if rc != PBD_OK:
+        raise PbdError(rc, "pbd_eval_ap_host")
+    return (apk, prec, rec) if curves else apk
+
+
+class Eval:
+    """pbd_eval (include/pbd_c.h "evaluation ledger"): per-instance keypoint distances (PCK) and per-detection true-positive flags (APK)
+    accumulated on the device.  Bound to `handle`, whose close() closes the ledgers it still has.  After PBD_ERR_CAPACITY the PbdError
+    carries .needed (instances or detections the ledger would have had to hold) and nothing was added."""
+
+    def __init__(self, handle: Handle, nparts: int, max_instances: int, max_detections: int, apk_thresh: float = .5):
+        self.handle, self.L, self.P = handle, handle.L, int(nparts)
+        self.q = C.c_void_p()
+        handle._chk(self.L.pbd_eval_create(handle.h, int(nparts), int(max_instances), int(max_detections), float(apk_thresh),
+                                           C.byref(self.q)))
+        if not hasattr(handle, "_caches"):
+            handle._caches = []
+        handle._caches.append(weakref.ref(self))
+
+    def _chk(self, rc, needed=None):
+        if rc == PBD_ERR_CAPACITY:
+            err = PbdError(rc, self.L.pbd_last_error(self.handle.h).decode())
+            err.needed = None if needed is None else needed.value
+            raise err
+        self.handle._chk(rc)
+
+    def dims(self):
+        """(P, N, M, npos, frames)"""
+        v = [C.c_int(), C.c_int(), C.c_int(), C.c_longlong(), C.c_int()]
+        self.handle._chk(self.L.pbd_eval_dims(self.q, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def reset(self):
+        self.handle._chk(self.L.pbd_eval_reset(self.q))
+
+    def get(self):
+        """the ledger: dict(dist [N, P], scale [N], score [M], tp [M, P])"""
+        P, N, M, _, _ = self.dims()
+        out = dict(dist=np.zeros((N, P), np.float64), scale=np.zeros(N, np.float64), score=np.zeros(M, np.float32),
+                   tp=np.zeros((M, P), np.uint8))
+        self.handle._chk(self.L.pbd_eval_get(self.q, _vp(out["dist"]), _vp(out["scale"]), _vp(out["score"]), _vp(out["tp"])))
+        return out
+
+    def add_pck_records(self, heads, boxes, found, points, scale):
+        """pbd_eval_add_pck_records: per person its selected pose (heads / boxes [ngt, max_parts, 4], found [ngt]) -> ngt instances"""
+        points, scale = _persons(points, scale, self.P)
+        heads = np.ascontiguousarray(heads, HEAD_DTYPE)
+        boxes = np.ascontiguousarray(boxes, np.int32)
+        found = np.ascontiguousarray(found, np.int32)
+        if not (len(heads) == len(found) == len(scale)) or boxes.shape != (len(scale), self.handle.max_parts, 4):
+            raise ValueError("add_pck_records: one record slot and one found flag per person, boxes [ngt, max_parts, 4]")
+        need = C.c_int(0)
+        self._chk(self.L.pbd_eval_add_pck_records(self.q, _vp(heads), _vp(boxes), _vp(found), _vp(points), _vp(scale), len(scale),
+                                                  C.byref(need)), need)
+
+    def add_apk_records(self, heads, boxes, points, scale):
+        """pbd_eval_add_apk_records: ONE frame's records in the given order against its persons -> len(heads) rows"""
+        points, scale = _persons(points, scale, self.P)
+        heads = np.ascontiguousarray(heads, HEAD_DTYPE)
+        boxes = np.ascontiguousarray(boxes, np.int32)
+        if boxes.shape != (len(heads), self.handle.max_parts, 4):
+            raise ValueError("add_apk_records: boxes [count, max_parts, 4]")
+        need = C.c_int(0)
+        self._chk(self.L.pbd_eval_add_apk_records(self.q, _vp(heads), _vp(boxes), len(heads), _vp(points), _vp(scale), len(scale),
+                                                  C.byref(need)), need)
+
+    def _batch_persons(self, frames, persons):
+        frames, stride = _frames(frames)
+        if not frames or len(persons) != len(frames) or any(f.shape != frames[0].shape for f in frames):
+            raise ValueError("evaluation batch: one (points, scale) pair per frame, frames of one shape")
+        nb = len(frames)
+        pts = np.zeros((nb, PBD_GT_MAX, self.P, 2), np.float64)
+        sc = np.zeros((nb, PBD_GT_MAX), np.float64)
+        ngt = np.zeros(nb, np.int32)
+        for f, (p, s) in enumerate(persons):
+            p, s = _persons(p, s, self.P)
+            if len(s) > PBD_GT_MAX:
+                raise ValueError("evaluation batch: at most PBD_GT_MAX persons per frame")
+            pts[f, :len(s)], sc[f, :len(s)], ngt[f] = p, s, len(s)
+        hgt, w = frames[0].shape[:2]
+        cn = 1 if frames[0].ndim == 2 else frames[0].shape[2]
+        ptrs = (C.c_void_p * nb)(*[f.ctypes.data for f in frames])
+        return frames, ptrs, nb, w, hgt, cn, stride, pts, sc, ngt
+
+    def pck_frame(self, im, points, scale, overlap=0.3):
+        """pbd_eval_pck_frame_u8: the frame as Handle.detect_gtbox on the persons' keypoint boxes -> found [ngt]; self.records = the
+        frame's records in front of the selection"""
+        im, w, hgt, cn, stride = _frame(im)
+        points, scale = _persons(points, scale, self.P)
+        found = np.zeros(len(scale), np.int32)
+        nrec, need = C.c_int(0), C.c_int(0)
+        rc = self.L.pbd_eval_pck_frame_u8(self.q, _vp(im), w, hgt, cn, stride, _vp(points), _vp(scale), len(scale), float(overlap),
+                                          _vp(found), C.byref(nrec), C.byref(need))
+        self.records = nrec.value
+        self._chk(rc, need)
+        return found
+
+    def pck_batch(self, frames, persons, overlap=0.3):
+        """pbd_eval_pck_frame_batch_u8: persons = [(points, scale)] per frame -> [found] per frame"""
+        frames, ptrs, nb, w, hgt, cn, stride, pts, sc, ngt = self._batch_persons(frames, persons)
+        found = np.zeros((nb, PBD_GT_MAX), np.int32)
+        nrec, need = C.c_int(0), C.c_int(0)
+        rc = self.L.pbd_eval_pck_frame_batch_u8(self.q, ptrs, nb, w, hgt, cn, stride, _vp(pts), _vp(sc), _vp(ngt), float(overlap),
+                                                _vp(found), C.byref(nrec), C.byref(need))
+        self.records = nrec.value
+        self._chk(rc, need)
+        return [found[f, :ngt[f]].copy() for f in range(nb)]
+
+    def apk_frame(self, im, points, scale) -> int:
+        """pbd_eval_apk_frame_u8: the frame as Handle.detect (threshold, candidate mode and NMS of the handle) -> its final records"""
+        im, w, hgt, cn, stride = _frame(im)
+        points, scale = _persons(points, scale, self.P)
+        rec, need = C.c_int(0), C.c_int(0)
+        rc = self.L.pbd_eval_apk_frame_u8(self.q, _vp(im), w, hgt, cn, stride, _vp(points), _vp(scale), len(scale), C.byref(rec),
+                                          C.byref(need))
+        self.records = [rec.value]
+        self._chk(rc, need)
+        return rec.value
+
+    def apk_batch(self, frames, persons):
+        """pbd_eval_apk_frame_batch_u8 -> records [nframes]"""
+        frames, ptrs, nb, w, hgt, cn, stride, pts, sc, ngt = self._batch_persons(frames, persons)
+        rec = np.zeros(nb, np.int32)
+        need = C.c_int(0)
+        rc = self.L.pbd_eval_apk_frame_batch_u8(self.q, ptrs, nb, w, hgt, cn, stride, _vp(pts), _vp(sc), _vp(ngt), _vp(rec), C.byref(need))
+        self.records = [int(r) for r in rec]
+        self._chk(rc, need)
+        return rec
+
+    def pck(self, thresh=.5, rule=PBD_EVAL_SCALE_LAST) -> np.ndarray:
+        out = np.zeros(self.P, np.float64)
+        self.handle._chk(self.L.pbd_eval_pck(self.q, float(thresh), int(rule), _vp(out)))
+        return out
+
+    def apk(self, curves=False):
+        """apk [P]; curves: (apk, prec [P, M], rec [P, M]) in sorted order"""
+        M = self.dims()[2]
+        out = np.zeros(self.P, np.float64)
+        prec, rec = (np.zeros((self.P, M), np.float64), np.zeros((self.P, M), np.float64)) if curves else (None, None)
+        self.handle._chk(self.L.pbd_eval_apk(self.q, _vp(out), _vp(prec), _vp(rec)))
+        return (out, prec, rec) if curves else out
+
+    def close(self):
+        if getattr(self, "q", None):   # (a live ledger implies a live handle: Handle.close() closes its ledgers before itself)
+            self.L.pbd_eval_destroy(self.q)
         self.q = None
 
     def __del__(self):

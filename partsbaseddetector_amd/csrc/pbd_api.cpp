@@ -632,6 +632,7 @@ static int run_argmin_enqueue(pbd_handle* h, const FrameJob& job, const FrameRou
   if (r.gt && (rc = pbd_i_gt_enqueue(h, r))) return rc;
   if (job.kind == FRAME_MINE && (rc = pbd_i_mine_enqueue(h, r))) return rc;
   if (job.kind == FRAME_LATENT_WRITE && (rc = pbd_i_latent_write_enqueue(h, r))) return rc;
+  if (job.kind == FRAME_EVAL && (rc = pbd_i_eval_enqueue(h, r))) return rc;
   LAUNCHCHK(h, r.zf.on ? "argmin + depth filter" : r.filter.on ? "argmin + candidate filter" : r.gt ? "argmin + gt boxes" : "argmin");
   if (r.count_d2h != CNT_NONE) HIPCHK(h, hipMemcpyAsync(h->h_cand_count, pbd_i_route_count(h, r.count_d2h), sizeof(int), hipMemcpyDeviceToHost, h->stream));
   if (!r.first_d2h && r.pack_count == CNT_NONE) return PBD_OK;

@@ -27,6 +27,9 @@ int enter_frame(pbd_handle* h, const FrameSource& s, bool detect) {
   }
   ON_DEVICE(h);
   if ((rc = plan_frame(h, s.w, s.hgt, s.cn, s.nframes, s.depth))) return rc;
+  if (s.eval && h->compact)   // (an evaluation frame is routed as a mining frame and refuses what that refuses)
+    return fail(h, PBD_ERR_UNSUPPORTED, "evaluation: this frame runs the compact memory plan (dp_mode 2, or automatic for large frames and batches), "
+                                        "which the mining route the records take refuses: add the frames one by one or in smaller batches");
   if ((s.mine || s.lat_write) && h->compact)   // (known once the geometry is planned; nothing has been uploaded or enqueued)
     return fail(h, PBD_ERR_UNSUPPORTED, std::string(s.mine ? "mining" : "latent positives") +
                                         ": this frame runs the compact memory plan (dp_mode 2, or automatic for large frames), whose min() reuses "
@@ -50,6 +53,8 @@ int enter_frame(pbd_handle* h, const FrameSource& s, bool detect) {
     if ((rc = pbd_i_gt_begin(h, *s.gt, s.nframes))) return rc;
   } else if (s.mine) {
     job.kind = FRAME_MINE;
+  } else if (s.eval) {
+    job.kind = FRAME_EVAL;
   } else if (s.z) {
     const DepthSource& z = *s.z;
     job.kind = FRAME_DEPTH;

@@ -307,6 +307,9 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   // latent positives (pbd_qp_write_latent_*): k_qp_latent.hip behind a latent frame's back-tracking; it shares mining's order, ids and
   // noshare buffers and mine_k / mine_in, and answers in a pinned block of its own
   struct LatentWriteOut* h_latw_out = nullptr;                             // [PBD_MAX_BATCH]: pinned
+  // evaluation frames (pbd_eval_apk_frame_*): k_eval_span behind the route's last post-stage; they share mining's order buffers and
+  // mine_in, and answer in a pinned block of their own
+  struct EvalFrameOut* h_eval_out = nullptr;                               // [PBD_MAX_BATCH]: pinned
 };
 #define PBD_MAX_BATCH 64
 
@@ -430,6 +433,7 @@ struct FrameSource {
   const GtSource* gt;             // best pose per ground-truth box: the selection runs behind the back-tracking; else null
   bool mine;                      // hard-negative mining (pbd_qp_mine_*): the final records stay on the device
   bool lat_write;                 // latent positives (pbd_qp_write_latent_*; with lat): the frame's pose stays on the device
+  bool eval;                      // an APK evaluation frame (pbd_eval_apk_frame_*): the final records stay on the device like a mining frame's
 };
 // the three shapes of a source, by name (z: see above)
 inline FrameSource host_frame(const void* im, int w, int hgt, int cn, int stride, int depth, const DepthSource* z = nullptr) {
@@ -475,6 +479,8 @@ int pbd_i_mine_enqueue(pbd_handle* h, const FrameRoute& r);
 int pbd_i_mine_buffers(pbd_handle* h);   // the order, ids and noshare buffers (first use), shared with the latent positives
 // latent positives (pbd_qp_latent.cpp): behind the back-tracking (and the candidate filter) of a FRAME_LATENT_WRITE job, the scan of its poses
 int pbd_i_latent_write_enqueue(pbd_handle* h, const FrameRoute& r);
+// evaluation (pbd_eval.cpp): behind the last post-stage of a FRAME_EVAL job, the order (RAW) and the per-frame spans of its final records
+int pbd_i_eval_enqueue(pbd_handle* h, const FrameRoute& r);
 int pbd_i_found(const pbd_handle* h);   // records the pending frame left on the host side (filtered: the kept count)
 #define PBD_FIRST_COPY 192   // candidate records fetched (or gathered) together with the count
 
@@ -743,6 +749,50 @@ struct LatentWriteArgs {
   LatentWriteOut* out;      // [nframes]
 };
 void launch_qp_latent_scan(const LatentWriteArgs& a, hipStream_t s);
+// evaluation ledger (k_eval.hip, pbd_eval.cpp; include/pbd_c.h "evaluation ledger")
+#define PBD_EVAL_ORDER_TILE 256    // keys of a frame's ordering staged in LDS at a time (k_eval_order)
+#define PBD_EVAL_SORT_TILE 1024    // keys of the global sort a workgroup orders in LDS; longer runs go through device memory
+struct EvalFrameOut { int count, start, raw, reserved; };   // k_eval_span per frame, in pinned memory: its final records are perm[start, start + count)
+struct EvalFrame { int start, count, ngt, goff; };           // a frame of an add: its rows [start, start + count) of the call, its persons [goff, goff + ngt)
+struct EvalSpanArgs {
+  RecordSet in; int nframes;
+  int* perm;                // [capacity] RAW: sorted by k_qp_mine_rank; filtered: written here, frame after frame
+  EvalFrameOut* out;        // [nframes]
+};
+struct EvalLedgerDev {
+  int P, ncap, mcap;
+  double* dist; double* scale;            // [ncap][P], [ncap]
+  float* score; unsigned char* tp;        // [mcap], [mcap][P]
+};
+struct EvalPckAddArgs {
+  EvalLedgerDev L; int n0;                // person (f, g) becomes instance n0 + frames[f].goff + g
+  const char* rec; size_t stride; int slots;   // its pose: the record at rec + stride * (f * slots + g), if found[f * slots + g]
+  const int* found;
+  const EvalFrame* frames;
+  const double* points; const double* scale;   // [persons][P][2], [persons]: the call's persons back to back
+};
+struct EvalApkAddArgs {
+  EvalLedgerDev L; int m0;                // position j of frame f becomes row m0 + frames[f].start + j
+  const char* rec; size_t stride; int mp;
+  const int* perm;                        // non-null: position j of frame f is record perm[frames[f].start + j]; else record frames[f].start + j
+  int* ord;                               // [rows of the call] ord[start + r] = the position matched r-th (score descending, ties by position)
+  const EvalFrame* frames;
+  const double* points; const double* scale;
+  double thresh;
+};
+struct EvalResultArgs {
+  EvalLedgerDev L; int n, m; long long npos;
+  unsigned long long* key; int n2;        // the global sort's keys, n2 = a power of two >= max(m, PBD_EVAL_SORT_TILE)
+  int* tpc; double* sm;                   // [P][mcap] each, in sorted order: cumulative true positives, suffix maximum of the precision
+  double* out;                            // [P]
+  double* prec; double* rec;              // [P][m] or null
+  double thresh; int rule;
+};
+void launch_eval_span(const EvalSpanArgs& a, hipStream_t s);
+void launch_eval_pck_add(const EvalPckAddArgs& a, int nframes, hipStream_t s);
+void launch_eval_apk_add(const EvalApkAddArgs& a, int nframes, int maxcount, hipStream_t s);   // the order, then the matching
+void launch_eval_pck(const EvalResultArgs& a, hipStream_t s);
+void launch_eval_apk(const EvalResultArgs& a, hipStream_t s);   // keys, sort, scan, suffix maximum, sum (+ the curves)
 // a warped positive's column (train.m:152-161 qp_poswrite): window r of `feat` (T [n][wlen]) becomes example n0 + r with ids (1, ids[r], 0, 0, 0)
 struct QpPosArgs {
   QpDev q; int n0, n;

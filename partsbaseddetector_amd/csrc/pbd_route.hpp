@@ -25,7 +25,8 @@ enum FrameKind {
   FRAME_GTBOX,    // the selection per ground-truth box runs behind the back-tracking (its tables: pbd_i_gt_begin)
   FRAME_STAGE,    // pbd_dp_argmin / pbd_dp_argbest: the back-tracking of resident tables, no frame entry and no post-stage
   FRAME_MINE,     // pbd_qp_mine_*: the final records stay on the device for the example cache's scan and write; only a count comes back
-  FRAME_LATENT_WRITE   // pbd_qp_write_latent_*: a FRAME_LATENT whose pose stays on the device like a mining frame's records
+  FRAME_LATENT_WRITE,  // pbd_qp_write_latent_*: a FRAME_LATENT whose pose stays on the device like a mining frame's records
+  FRAME_EVAL      // pbd_eval_apk_frame_*: routed as a mining frame; the evaluation ledger matches the final records where they are
 };
 struct FrameJob {
   FrameKind kind = FRAME_PLAIN;
@@ -108,7 +109,7 @@ inline bool route_frame(const RouteSettings& s, const FrameJob& job, FrameRoute*
   const bool zf = k == FRAME_DEPTH && s.zf_on;
   const bool post = zf || filtered;
   const bool latw = k == FRAME_LATENT_WRITE;
-  const bool mine = k == FRAME_MINE || latw;   // the example cache reads the final records where they are
+  const bool mine = k == FRAME_MINE || latw || k == FRAME_EVAL;   // the example cache (the evaluation ledger) reads the final records where they are
   const bool dev = s.member || mine;   // the final records stay in DEV_OUT
   const bool zero_copy = s.zero_copy && !dev;
   if (k == FRAME_GTBOX && (filtered || s.zf_on || s.b3_on || s.cl3_on || s.ps_on)) return false;   // pbd_i_gt_check

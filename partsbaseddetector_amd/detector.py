@@ -574,6 +574,53 @@ class PartsBasedDetector:
                 break
         return out
 
+    def evaluation(self, max_instances: int, max_detections: int, apk_thresh: float = .5) -> "Evaluation":
+        """An evaluation ledger on this detector's handle (include/pbd_c.h "evaluation ledger"): eval_pck.m / eval_apk.m / VOCap.m with
+        the records left on the device.  One keypoint per part: every component of the model must have the same number of parts."""
+        return Evaluation(capi.Eval(self.handle, self.model.nparts(0), max_instances, max_detections, apk_thresh))
+
+
+class Evaluation:
+    """matlab/evaluation on the GPU: test frames go in with their annotated persons (points [ngt, P, 2], scale [ngt]); per frame only
+    counts and found flags come back; pck() and apk() return P doubles each.  addPck runs testmodel_gtbox.m's protocol (the best pose
+    on every person's keypoint box), addApk testmodel.m's (the detector's threshold, candidate filter and NMS: setCandidateFilter(
+    PBD_CAND_SORT_NMS, 0.3) with setCandidateNms(PBD_NMS_PARTS, 1000) is nms.m)."""
+    SCALE_LAST, SCALE_OWN = capi.PBD_EVAL_SCALE_LAST, capi.PBD_EVAL_SCALE_OWN
+
+    def __init__(self, ledger: "capi.Eval"):
+        self.ledger = ledger
+
+    def addPck(self, im: np.ndarray, points, scale, overlap: float = 0.3) -> np.ndarray:
+        """-> found [ngt]: which persons have a pose"""
+        return self.ledger.pck_frame(im, points, scale, overlap)
+
+    def addPckBatch(self, frames, persons, overlap: float = 0.3):
+        """persons = [(points, scale)] per frame -> [found] per frame"""
+        return self.ledger.pck_batch(frames, persons, overlap)
+
+    def addApk(self, im: np.ndarray, points, scale) -> int:
+        """-> the frame's final records"""
+        return self.ledger.apk_frame(im, points, scale)
+
+    def addApkBatch(self, frames, persons) -> np.ndarray:
+        return self.ledger.apk_batch(frames, persons)
+
+    def pck(self, thresh: float = .5, rule: int = capi.PBD_EVAL_SCALE_LAST) -> np.ndarray:
+        """rule: SCALE_LAST is eval_pck.m:13 as written (the last instance's scale for all), SCALE_OWN each instance's own"""
+        return self.ledger.pck(thresh, rule)
+
+    def apk(self, curves: bool = False):
+        return self.ledger.apk(curves)
+
+    def reset(self) -> None:
+        self.ledger.reset()
+
+    def dims(self):
+        return self.ledger.dims()
+
+    def close(self) -> None:
+        self.ledger.close()
+
 
 def shuffled_support(cache: "capi.QpCache", seed: int = 0) -> np.ndarray:
     """find(qp.sv) of the cache's examples, shuffled the way pbd_qp_opt shuffles its first pass: Fisher-Yates from the back, the

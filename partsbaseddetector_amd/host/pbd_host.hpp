@@ -1004,6 +1004,105 @@ class PartsBasedDetector {
     if (!dev_) throw Exception(PBD_ERR_STATE, "exampleCache() before distributeModel()");
     return std::unique_ptr<ExampleCache>(new ExampleCache(dev_, capacity, cpos, cneg, wreg, w0));
   }
+  // ---- evaluation ledger (include/pbd_c.h "evaluation ledger"): matlab/evaluation/eval_pck.m, eval_apk.m and VOCap.m on the GPU ----
+  // Test frames go in with their annotated persons — points[ngt][P][2] and scale[ngt], P = the model's parts per component —; per frame
+  // only counts and found flags come back; pck() and apk() return P doubles each.  addPck is testmodel_gtbox.m's protocol (the best pose
+  // on every person's keypoint box), addApk testmodel.m's (this detector's threshold, candidate filter and NMS).  A call that would
+  // overflow the ledger throws PBD_ERR_CAPACITY and adds nothing.
+  class Evaluation {
+    std::shared_ptr<Device> dev_;
+    pbd_eval* e_ = nullptr;
+   public:
+    Evaluation(std::shared_ptr<Device> dev, int nparts, int max_instances, int max_detections, double apk_thresh) : dev_(std::move(dev)) {
+      dev_->check(pbd_eval_create(dev_->h, nparts, max_instances, max_detections, apk_thresh, &e_));
+    }
+    ~Evaluation() { pbd_eval_destroy(e_); }
+    Evaluation(const Evaluation&) = delete;
+    Evaluation& operator=(const Evaluation&) = delete;
+    struct Dims { int nparts, instances, detections, frames; long long npos; };
+    Dims dims() const { Dims d{}; dev_->check(pbd_eval_dims(e_, &d.nparts, &d.instances, &d.detections, &d.npos, &d.frames)); return d; }
+    void reset() { dev_->check(pbd_eval_reset(e_)); }
+    // -> found[ngt]: which persons have a pose
+    std::vector<int> addPck(const Mat& im, const std::vector<double>& points, const std::vector<double>& scale, double overlap = 0.3) {
+      if (im.depth() != PBD_8U) throw Exception(PBD_ERR_UNSUPPORTED, "evaluation: 8-bit frames only");
+      persons(points, scale);
+      std::vector<int> found(scale.size(), 0);
+      dev_->check(pbd_eval_pck_frame_u8(e_, im.ptr<uint8_t>(), im.cols, im.rows, im.channels(), (int)im.step(), points.data(), scale.data(),
+                                        (int)scale.size(), overlap, found.data(), nullptr, nullptr));
+      return found;
+    }
+    // -> the frame's final records
+    int addApk(const Mat& im, const std::vector<double>& points, const std::vector<double>& scale) {
+      if (im.depth() != PBD_8U) throw Exception(PBD_ERR_UNSUPPORTED, "evaluation: 8-bit frames only");
+      persons(points, scale);
+      int records = 0;
+      dev_->check(pbd_eval_apk_frame_u8(e_, im.ptr<uint8_t>(), im.cols, im.rows, im.channels(), (int)im.step(), points.data(), scale.data(),
+                                        (int)scale.size(), &records, nullptr));
+      return records;
+    }
+    // same-sized frames; points[f] / scale[f]: frame f's persons (at most PBD_GT_MAX).  -> found per frame / records per frame
+    std::vector<std::vector<int>> addPckBatch(const std::vector<Mat>& ims, const std::vector<std::vector<double>>& points,
+                                              const std::vector<std::vector<double>>& scale, double overlap = 0.3) {
+      Batch b(*this, ims, points, scale);
+      std::vector<int> found(ims.size() * PBD_GT_MAX, 0);
+      dev_->check(pbd_eval_pck_frame_batch_u8(e_, b.ptrs.data(), (int)ims.size(), ims[0].cols, ims[0].rows, ims[0].channels(), (int)ims[0].step(),
+                                              b.pts.data(), b.sc.data(), b.ngt.data(), overlap, found.data(), nullptr, nullptr));
+      std::vector<std::vector<int>> out(ims.size());
+      for (size_t f = 0; f < ims.size(); ++f) out[f].assign(found.begin() + f * PBD_GT_MAX, found.begin() + f * PBD_GT_MAX + b.ngt[f]);
+      return out;
+    }
+    std::vector<int32_t> addApkBatch(const std::vector<Mat>& ims, const std::vector<std::vector<double>>& points,
+                                     const std::vector<std::vector<double>>& scale) {
+      Batch b(*this, ims, points, scale);
+      std::vector<int32_t> records(ims.size(), 0);
+      dev_->check(pbd_eval_apk_frame_batch_u8(e_, b.ptrs.data(), (int)ims.size(), ims[0].cols, ims[0].rows, ims[0].channels(), (int)ims[0].step(),
+                                              b.pts.data(), b.sc.data(), b.ngt.data(), records.data(), nullptr));
+      return records;
+    }
+    // rule: PBD_EVAL_SCALE_LAST is eval_pck.m:13 as written (the last instance's scale for all), PBD_EVAL_SCALE_OWN each instance's own
+    std::vector<double> pck(double thresh = .5, int rule = PBD_EVAL_SCALE_LAST) {
+      std::vector<double> out((size_t)dims().nparts, 0.0);
+      dev_->check(pbd_eval_pck(e_, thresh, rule, out.data()));
+      return out;
+    }
+    // prec / rec (optional): [P][M] in sorted order
+    std::vector<double> apk(std::vector<double>* prec = nullptr, std::vector<double>* rec = nullptr) {
+      const Dims d = dims();
+      std::vector<double> out((size_t)d.nparts, 0.0);
+      if (prec) prec->assign((size_t)d.nparts * d.detections, 0.0);
+      if (rec) rec->assign((size_t)d.nparts * d.detections, 0.0);
+      dev_->check(pbd_eval_apk(e_, out.data(), prec ? prec->data() : nullptr, rec ? rec->data() : nullptr));
+      return out;
+    }
+    pbd_eval* ledger() { return e_; }
+   private:
+    void persons(const std::vector<double>& points, const std::vector<double>& scale) const {
+      if (points.size() != scale.size() * (size_t)dims().nparts * 2) throw Exception(PBD_ERR_ARG, "Evaluation: points[ngt][P][2] and scale[ngt]");
+    }
+    struct Batch {
+      std::vector<const uint8_t*> ptrs; std::vector<double> pts, sc; std::vector<int> ngt;
+      Batch(const Evaluation& e, const std::vector<Mat>& ims, const std::vector<std::vector<double>>& points, const std::vector<std::vector<double>>& scale) {
+        const size_t B = ims.size(), P = (size_t)e.dims().nparts;
+        if (!B || points.size() != B || scale.size() != B) throw Exception(PBD_ERR_ARG, "Evaluation: one points / scale vector per frame");
+        pts.assign(B * PBD_GT_MAX * P * 2, 0.0); sc.assign(B * PBD_GT_MAX, 0.0); ngt.assign(B, 0);
+        for (size_t f = 0; f < B; ++f) {
+          if (ims[f].depth() != PBD_8U || ims[f].cols != ims[0].cols || ims[f].rows != ims[0].rows || ims[f].channels() != ims[0].channels() ||
+              ims[f].step() != ims[0].step())
+            throw Exception(PBD_ERR_ARG, "Evaluation: a batch is 8-bit frames of one size and stride");
+          e.persons(points[f], scale[f]);
+          if (scale[f].size() > PBD_GT_MAX) throw Exception(PBD_ERR_ARG, "Evaluation: at most PBD_GT_MAX persons per frame");
+          ptrs.push_back(ims[f].ptr<uint8_t>());
+          ngt[f] = (int)scale[f].size();
+          std::copy(points[f].begin(), points[f].end(), pts.begin() + f * PBD_GT_MAX * P * 2);
+          std::copy(scale[f].begin(), scale[f].end(), sc.begin() + f * PBD_GT_MAX);
+        }
+      }
+    };
+  };
+  std::unique_ptr<Evaluation> evaluation(int nparts, int max_instances, int max_detections, double apk_thresh = .5) {
+    if (!dev_) throw Exception(PBD_ERR_STATE, "evaluation() before distributeModel()");
+    return std::unique_ptr<Evaluation>(new Evaluation(dev_, nparts, max_instances, max_detections, apk_thresh));
+  }
   // detect(im, model, thresh, [], 0, id, label)'s qp_write of every detection (matlab/learning/train.m:102): `candidates` (of the LAST
   // frame, or a selection) appended to `cache` as standardised examples, on the GPU.  Returns how many were written (a full cache
   // takes no more and is no error).
