@@ -1409,6 +1409,60 @@ int pbd_eval_apk_frame_batch_u8(pbd_eval* ev, const uint8_t* const* ims, int nfr
 int pbd_eval_pck(pbd_eval* ev, double thresh, int rule, double* pck);
 int pbd_eval_apk(pbd_eval* ev, double* apk, double* prec, double* rec);
 
+/* ---- part mixtures: matlab/learning/k_means.m and clusterparts.m (ABI 5, additive) ----------------------------------------------------------
+ * What a training run starts from (trainmodel.m:13-15): every part's positives are clustered by the part's offset from its parent, and the
+ * cluster of a positive is the part's mixture label there — the `mix` the latent entries take, the K of the model that buildmodel.m lays out
+ * (Model.build_model of the binding).  clusterparts.m runs R = 100 independent k-means per part from random starts and keeps the best: P * R
+ * small independent problems.  pbd_cluster_parts runs them on the device, one wavefront each, and needs no handle.
+ * k-means (k_means.m:71-114), float64, the operations in the order written, never fused.  X[n][m] points, c[k][m] centroids, labels 0-based.
+ *   One pass: D(i, t) = d with d = 0; d = d + (X(i, s) - c(t, s))^2, s ascending; [z, label] = min(D, [], 2) — NaN is ignored, the first of
+ *   equal minima wins; then c(t, :) = the mean of the points labelled t, each coordinate's sum divided by the count, and NaN in every
+ *   coordinate for a centroid without a point: it can never win again.  The loop runs while the labels changed, the labels before the
+ *   first pass being ones no pass gives (g0 = ones, gIdx = zeros): at least one pass, and two unless the cap ends it.  sumdist = sum(z) of
+ *   the last pass: measured against the centroids BEFORE that pass's update, as in the file; c is the file's, after it.
+ * DEVIATIONS from the file, each stated:
+ *   Sums.  The per-cluster coordinate sums and sum(z) use the block sum of the "training example cache" section over the point index i:
+ *     element i goes to partial i mod 64, i ascending, the partials start at +0.0, a point of another cluster adds nothing, folded
+ *     s[t] += s[t + h], h = 32 .. 1.  The file's sum and mean add left to right.  On data whose sums are exact (small integers) both give
+ *     the same bits.  The result does not depend on the launch.
+ *   Random starts.  X(ceil(rand(k,1)*n),:) becomes k draws row = next() mod n, c(t, :) = X(row, :), t ascending, next() the splitmix64 of
+ *     the "QP solver" section.  The stream of part p, trial r starts at state = seed ^ (0xD1B54A32D192ED03 * (uint64)(p * R + r + 1)).
+ *     Rows may repeat, as in the file: two equal centroids leave the later one without a point, and the NaN path above is taken.
+ *   Iteration cap.  max_iter in [1, PBD_CLUSTER_MAX_ITER], else PBD_ERR_ARG; k_means.m has none.  A trial whose labels still changed in
+ *     pass max_iter stops there, keeps its labels, centroids and sumdist, competes like any other, and is counted in *capped.
+ *   A cluster of one point.  k_means.m:103 is mean(X(gIdx==t,:)): for a single point (with m > 1) MATLAB's mean runs ALONG the 1 x m row,
+ *     and the scalar — the mean of the point's coordinates — is spread over c(t,:).  Here the centroid is the per-coordinate mean for any
+ *     count, so a cluster of one point has that point as its centroid.
+ * pbd_kmeans_host: one k-means.  c0[k][m] non-NULL: the k_means(X, C) form; NULL: the start is drawn from the generator at state0.
+ *   -> idx[n], and (each may be NULL) c[k][m], *sumdist, *iters = the passes run.  Any m >= 1.
+ * pbd_cluster_parts_host (clusterparts.m): def[P][n][2] = part p's position in positive i (Model.data_def of the binding); parent[P] 0-based,
+ *   -1 at part 0 only, parent < child; K[P] clusters per part.  X of part p = def[p] - def[parent[p]]; of the root: def[c] - def[0], c its
+ *   first child.  R trials per part with m = 2; the winner is the FIRST trial at the minimal sumdist (min as above).  -> idx[P][n], and (each
+ *   may be NULL) centres[P][PBD_CLUSTER_MAX_K][2] (the winner's centroids, NaN included; rows from K[p] on are +0.0), sumdist[P],
+ *   best_trial[P], trial_sumdist[P * R], trial_iters[P * R], *capped = capped trials over all parts.
+ * pbd_cluster_parts: the same on HIP device `device`: def goes up once, X is formed there (the subtraction is exact IEEE either way), a
+ *   wavefront per (part, trial) walks its points lane-strided — lane j owns partial j of the block sum — and a second launch picks the
+ *   winners; only idx, the centres and the per-part and per-trial scalars come back.  No workgroup waits on another and every loop is
+ *   bounded by max_iter.  Synchronous; the calling thread's current device is restored.  Every output equals pbd_cluster_parts_host bit
+ *   for bit.  PBD_ERR_HIP: no such device, or a HIP failure.
+ * Refusals, nothing computed: PBD_ERR_ARG — NULL def / parent / K / idx (X / idx), n < 1, P < 1, R < 1, m < 1, k or K[p] < 1, a parent
+ *   array not as above, a root without a child (the file's while loop runs off the end), a non-finite def, c0 or X, max_iter out of range;
+ *   PBD_ERR_UNSUPPORTED — k or K[p] > PBD_CLUSTER_MAX_K; P * R > PBD_CLUSTER_MAX_TRIALS (the device keeps 512 bytes of
+ *   centroids per trial: at most 512 MiB); P * R * n > PBD_CLUSTER_MAX_LABELS (the label bytes of all trials: below 2 GiB).  Beside these two
+ *   the device holds def and X (32 P n bytes), idx (4 P n) and 20 bytes per trial.                                                       */
+#define PBD_CLUSTER_MAX_K 32
+#define PBD_CLUSTER_MAX_ITER 10000
+#define PBD_CLUSTER_MAX_TRIALS 1048576
+#define PBD_CLUSTER_MAX_LABELS 2147483647ll
+int pbd_kmeans_host(const double* X, int n, int m, int k, const double* c0, uint64_t state0, int max_iter, int32_t* idx, double* c,
+                    double* sumdist, int* iters);                                                                         /* host only */
+int pbd_cluster_parts_host(const double* def, int n, int P, const int32_t* parent, const int32_t* K, int R, uint64_t seed, int max_iter,
+                           int32_t* idx, double* centres, double* sumdist, int32_t* best_trial, double* trial_sumdist,
+                           int32_t* trial_iters, int32_t* capped);                                                        /* host only */
+int pbd_cluster_parts(int device, const double* def, int n, int P, const int32_t* parent, const int32_t* K, int R, uint64_t seed,
+                      int max_iter, int32_t* idx, double* centres, double* sumdist, int32_t* best_trial, double* trial_sumdist,
+                      int32_t* trial_iters, int32_t* capped);
+
 /* ---- instrumentation --------------------------------------------------------
  * GPU time (ms, hipEvent) of the stages of the last synchronous detect:
  * [0] image pyramid [1] HOG [2] pdf [3] dp min [4] argmin [5] total            */

@@ -78,7 +78,9 @@ EXPORTS = [
     "pbd_eval_create", "pbd_eval_destroy", "pbd_eval_reset", "pbd_eval_dims", "pbd_eval_get", "pbd_eval_add_pck_records",
     "pbd_eval_add_apk_records", "pbd_eval_pck_frame_u8", "pbd_eval_pck_frame_batch_u8", "pbd_eval_apk_frame_u8",
     "pbd_eval_apk_frame_batch_u8", "pbd_eval_pck", "pbd_eval_apk",
+    "pbd_kmeans_host", "pbd_cluster_parts_host", "pbd_cluster_parts",
 ]
+PBD_CLUSTER_MAX_K, PBD_CLUSTER_MAX_ITER, PBD_CLUSTER_MAX_TRIALS, PBD_CLUSTER_MAX_LABELS = 32, 10000, 2 ** 20, 2 ** 31 - 1   # include/pbd_c.h "part mixtures"
 PBD_EVAL_SCALE_LAST, PBD_EVAL_SCALE_OWN = 0, 1   # pbd_eval_pck's scale rule: eval_pck.m:13 literally (the last instance's scale) / each instance's own
 PBD_MINE_NONE, PBD_MINE_ONE, PBD_MINE_OPT = 0, 1, 2   # pbd_qp_mine_*'s action (detect.m:148-149, 315-324)
 PBD_WARP_SKIPPED, PBD_WARP_WRITTEN, PBD_WARP_FULL = 0, 1, 2   # pbd_qp_write_warped_u8's status per box
@@ -233,6 +235,9 @@ def lib() -> C.CDLL:
         L.pbd_eval_apk_frame_batch_u8.argtypes = [V, V, I, I, I, I, I, V, V, V, V, V]
         L.pbd_eval_pck.argtypes = [V, D, I, V]
         L.pbd_eval_apk.argtypes = [V, V, V, V]
+        L.pbd_kmeans_host.argtypes = [V, I, I, I, V, C.c_uint64, I, V, V, V, V]
+        L.pbd_cluster_parts_host.argtypes = [V, I, I, V, V, I, C.c_uint64, I, V, V, V, V, V, V, V]
+        L.pbd_cluster_parts.argtypes = [I, V, I, I, V, V, I, C.c_uint64, I, V, V, V, V, V, V, V]
         if L.pbd_abi_version() != PBD_ABI_VERSION:
             raise ImportError(f"{LIB_PATH}: ABI version {L.pbd_abi_version()}, this binding is for {PBD_ABI_VERSION}")
         _lib = L
@@ -1840,3 +1845,60 @@ class Eval:
             self.close()
         except Exception:
             pass
+
+
+# ---- part mixtures: k_means.m, clusterparts.m (include/pbd_c.h "part mixtures") ------------------------------------------------------
+def kmeans_host(X, k=None, c0=None, state0=0, max_iter=1000):
+    """pbd_kmeans_host (host code, no GPU): X [n, m]; c0 [k, m]: the k_means(X, C) form, else k centroids drawn from the generator at
+    state0 -> dict(idx [n] int32 0-based, c [k, m] (NaN rows: empty clusters), sumdist, iters)"""
+    X = np.ascontiguousarray(X, np.float64)
+    if X.ndim != 2:
+        raise ValueError("kmeans_host: X [n, m]")
+    n, m = X.shape
+    if c0 is not None:
+        c0 = np.ascontiguousarray(c0, np.float64).reshape(-1, m)
+        k = len(c0)
+    if k is None:
+        raise ValueError("kmeans_host: k or c0")
+    idx, c = np.zeros(n, np.int32), np.zeros((max(int(k), 0), m), np.float64)
+    sd, it = C.c_double(), C.c_int()
+    rc = lib().pbd_kmeans_host(_vp(X), n, m, int(k), _vp(c0), int(state0) & (2 ** 64 - 1), int(max_iter), _vp(idx), _vp(c), C.byref(sd),
+                               C.byref(it))
+    if rc != PBD_OK:
+        raise PbdError(rc, "pbd_kmeans_host")
+    return dict(idx=idx, c=c, sumdist=sd.value, iters=it.value)
+
+
+def _cluster_parts(fn, name, lead, deffeat, parents, K, R, seed, max_iter):
+    deffeat = np.ascontiguousarray(deffeat, np.float64)
+    if deffeat.ndim != 3 or deffeat.shape[2] != 2:
+        raise ValueError(f"{name}: def [P, n, 2] (Model.data_def)")
+    P, n = deffeat.shape[:2]
+    parents = np.ascontiguousarray(parents, np.int32).reshape(-1)
+    K = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.int32), (P,)))
+    if len(parents) != P:
+        raise ValueError(f"{name}: one parent per part")
+    R = int(R)
+    out = dict(idx=np.zeros((P, n), np.int32), centres=np.zeros((P, PBD_CLUSTER_MAX_K, 2), np.float64), sumdist=np.zeros(P, np.float64),
+               best_trial=np.zeros(P, np.int32), trial_sumdist=np.zeros((P, max(R, 0)), np.float64),
+               trial_iters=np.zeros((P, max(R, 0)), np.int32))
+    capped = C.c_int32()
+    rc = fn(*lead, _vp(deffeat), n, P, _vp(parents), _vp(K), R, int(seed) & (2 ** 64 - 1), int(max_iter), _vp(out["idx"]),
+            _vp(out["centres"]), _vp(out["sumdist"]), _vp(out["best_trial"]), _vp(out["trial_sumdist"]), _vp(out["trial_iters"]),
+            C.byref(capped))
+    if rc != PBD_OK:
+        raise PbdError(rc, name)
+    out["capped"] = capped.value
+    return out
+
+
+def cluster_parts_host(deffeat, parents, K, R=100, seed=0, max_iter=1000):
+    """pbd_cluster_parts_host (host code, no GPU): clusterparts.m.  deffeat [P, n, 2] (Model.data_def), parents 0-based with -1 at the
+    root, K an int or one per part -> dict(idx [P, n] int32 0-based mixture labels, centres [P, PBD_CLUSTER_MAX_K, 2], sumdist [P],
+    best_trial [P], trial_sumdist [P, R], trial_iters [P, R], capped)"""
+    return _cluster_parts(lib().pbd_cluster_parts_host, "pbd_cluster_parts_host", (), deffeat, parents, K, R, seed, max_iter)
+
+
+def cluster_parts(deffeat, parents, K, R=100, seed=0, max_iter=1000, device=0):
+    """pbd_cluster_parts: cluster_parts_host on HIP device `device`, one wavefront per (part, trial); bit-identical outputs"""
+    return _cluster_parts(lib().pbd_cluster_parts, "pbd_cluster_parts", (int(device),), deffeat, parents, K, R, seed, max_iter)

@@ -793,6 +793,19 @@ void launch_eval_pck_add(const EvalPckAddArgs& a, int nframes, hipStream_t s);
 void launch_eval_apk_add(const EvalApkAddArgs& a, int nframes, int maxcount, hipStream_t s);   // the order, then the matching
 void launch_eval_pck(const EvalResultArgs& a, hipStream_t s);
 void launch_eval_apk(const EvalResultArgs& a, hipStream_t s);   // keys, sort, scan, suffix maximum, sum (+ the curves)
+// part mixtures (k_kmeans.hip, pbd_kmeans.cpp; include/pbd_c.h "part mixtures"): trial g = p * R + r
+struct KmeansArgs {
+  const double* def; double* X;            // [P][n][2]
+  const int* pa; const int* pb;            // [P]: X of part p = def[pa[p]] - def[pb[p]]
+  const int* K;                            // [P]
+  int n, P, R, max_iter;
+  unsigned long long seed;
+  unsigned char* lab;                      // [P * R][n] the trials' labels
+  double* tc;                              // [P * R][PBD_CLUSTER_MAX_K][2] the trials' centroids
+  double* tsum; int* titers; int* tcap;    // [P * R]
+  int* idx; double* centres; double* sumdist; int* best; int* pcap;   // the winners: [P][n], [P][PBD_CLUSTER_MAX_K][2], [P], [P], [P]
+};
+void launch_kmeans(const KmeansArgs& a, hipStream_t s);   // X, the trials, the winners
 // a warped positive's column (train.m:152-161 qp_poswrite): window r of `feat` (T [n][wlen]) becomes example n0 + r with ids (1, ids[r], 0, 0, 0)
 struct QpPosArgs {
   QpDev q; int n0, n;

@@ -1220,5 +1220,21 @@ inline std::vector<int> Candidate::bestOverlap(const std::vector<Candidate>& c, 
   return best;
 }
 
+// matlab/learning/clusterparts.m on the GPU (pbd_cluster_parts; needs no detector): def[P][n][2] the parts' positions (data_def.m),
+// parent 0-based with -1 at the root, K[p] clusters for part p, R k-means trials per part -> the positives' 0-based mixture labels
+// [P][n], what Positive::mix and buildmodel.m take.  Throws on the header's refusals.
+inline std::vector<int32_t> clusterParts(const std::vector<double>& def, int n, const std::vector<int32_t>& parent, const std::vector<int32_t>& K,
+                                         int R = 100, uint64_t seed = 0, int max_iter = 1000, int device = 0, int* capped = nullptr) {
+  const size_t P = parent.size();
+  if (n < 1 || K.size() != P || def.size() != P * (size_t)n * 2) throw Exception(PBD_ERR_ARG, "clusterParts: def[P][n][2], one parent and one K per part");
+  std::vector<int32_t> idx(P * (size_t)n);
+  int32_t cap = 0;
+  const int rc = pbd_cluster_parts(device, def.data(), n, (int)P, parent.data(), K.data(), R, seed, max_iter, idx.data(), nullptr, nullptr, nullptr,
+                                   nullptr, nullptr, &cap);
+  if (rc != PBD_OK) throw Exception(rc, "clusterParts: refused (include/pbd_c.h \"part mixtures\"), or a HIP failure");
+  if (capped) *capped = cap;
+  return idx;
+}
+
 }  // namespace pbd
 #endif  // PBD_HOST_HPP_

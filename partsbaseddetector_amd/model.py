@@ -5,6 +5,10 @@ fields with the same meaning, numpy instead of cv::Mat.  The reference's model
 files are an un-vendored submodule (.gitmodules:1-3), so benchmarks and tests
 use seeded synthetic models with the structure the reference's MATLAB side
 produces (matlab/learning/buildmodel.m:19-80): see SURVEY.md §8(d).
+
+init_model, data_def, merge_models and build_model are that MATLAB side itself
+(initmodel.m, data_def.m, mergemodels.m, buildmodel.m): with capi.cluster_parts
+(clusterparts.m) they make a model and its mixture labels from annotations.
 """
 from __future__ import annotations
 
@@ -417,6 +421,128 @@ def make_tree_model_k(parents, Ks, seed=1234, kh=5, kw=5, sbin=4, interval=10, t
                          rng.choice([1 / 32, 1 / 16], rows), rng.choice([-1 / 128, 0.0, 1 / 128], rows)], axis=1).astype(np.float32)
     return Model(filt, np.asarray(biasw, np.float32), anchors, defw.reshape(-1, 4), filterid, biasid, defid, [list(parents)],
                  interval, thresh, sbin, 18, flen, name)
+
+
+# ---- model assembly: what matlab/learning/trainmodel.m runs around the training rounds (INTEGRATION.md "From annotations to a model") ----
+def init_model(w, h, sbin, tsize=None) -> Model:
+    """matlab/learning/initmodel.m: the one-part model every part's warped training starts from.  w, h: the width and height
+    (x2 - x1 + 1, y2 - y1 + 1) of the first part's box in every positive.  The template is square: the 5th-percentile area
+    areas[floor(n * .05) - 1] of the sorted areas gives floor(sqrt(area) / sbin) cells a side, 32 features a cell; `tsize` = (rows,
+    cols[, 32]) overrides it.  One bias (0) and one zero filter; interval 10.  Fewer than 20 positives without tsize: ValueError (the
+    file indexes element 0 of a 1-based array)."""
+    if tsize is None:
+        areas = np.sort(np.asarray(h, np.float64).ravel() * np.asarray(w, np.float64).ravel())
+        at = int(np.floor(areas.size * 0.05))
+        if at < 1:
+            raise ValueError(f"init_model: {areas.size} positives — the 5th-percentile area needs at least 20 (or pass tsize)")
+        side = int(np.floor(np.sqrt(areas[at - 1]) / sbin))
+        tsize = (side, side, 32)
+    tsize = tuple(int(v) for v in tsize)
+    if len(tsize) == 2:
+        tsize += (32,)
+    if tsize[0] < 1 or tsize[1] < 1 or tsize[2] != 32:
+        raise ValueError(f"init_model: a template of {tsize[0]} x {tsize[1]} cells x {tsize[2]} features")
+    return Model([np.zeros((tsize[0], tsize[1] * 32), np.float32)], np.zeros(1, np.float32), np.zeros((0, 2), np.int32),
+                 np.zeros((0, 4), np.float32), [[[0]]], [[[0]]], [[[]]], [[-1]], 10, 0.0, int(sbin), 18, 32, "init")
+
+
+def data_def(points, w, h, maxsize) -> np.ndarray:
+    """matlab/learning/data_def.m: the parts' positions in HOG cells of the template.  points [n][P][2] (x, y) of part p in positive i;
+    w, h [n] as for init_model; maxsize = (rows, cols) of the template (init_model(...).filter_sizes()[0]).  -> [P][n][2] float64,
+    points / scale with scale_i = sqrt(w_i * h_i) / sqrt(maxsize[0] * maxsize[1]): the layout capi.cluster_parts takes."""
+    points = np.asarray(points, np.float64)
+    if points.ndim != 3 or points.shape[2] != 2:
+        raise ValueError("data_def: points [n, P, 2]")
+    w, h = np.asarray(w, np.float64).ravel(), np.asarray(h, np.float64).ravel()
+    if len(w) != len(points) or len(h) != len(points):
+        raise ValueError("data_def: one width and height per positive")
+    scale = np.sqrt(w * h) / np.sqrt(np.float64(int(maxsize[0]) * int(maxsize[1])))
+    return np.ascontiguousarray(np.transpose(points / scale[:, None, None], (1, 0, 2)))
+
+
+def merge_models(models) -> Model:
+    """matlab/learning/mergemodels.m in Model terms: the models' components, filters, biases and deformations appended in order, every
+    id of model j shifted by what models 0 .. j-1 hold.  The scalars (interval, sbin, ...) are the first model's, as in the file.
+    Every bias of every model is appended: mergemodels.m:12 writes model.bias(nb+1) inside its loop over i, which keeps only the last
+    bias of a model that has several; trainmodel.m passes one-bias models, where both agree."""
+    import copy
+    models = list(models)
+    if not models:
+        raise ValueError("merge_models: no models")
+    m = copy.copy(models[0])
+    m._keep = []
+    m.filtersw = [np.asarray(f, np.float32) for f in models[0].filtersw]
+    m.biasw = np.asarray(models[0].biasw, np.float32).ravel()
+    m.defw = np.asarray(models[0].defw, np.float32).reshape(-1, 4)
+    m.anchors = np.asarray(models[0].anchors, np.int32).reshape(-1, 2)
+    shift = lambda ids, by: [[[int(v) + by for v in mix] for mix in part] for part in ids]
+    m.filterid, m.biasid, m.defid = shift(m.filterid, 0), shift(m.biasid, 0), shift(m.defid, 0)
+    m.parentid = [list(c) for c in m.parentid]
+    for x in models[1:]:
+        nb, nf, nd = len(m.biasw), len(m.filtersw), len(m.defw)
+        m.biasw = np.concatenate([m.biasw, np.asarray(x.biasw, np.float32).ravel()])
+        m.filtersw = m.filtersw + [np.asarray(f, np.float32) for f in x.filtersw]
+        m.defw = np.concatenate([m.defw, np.asarray(x.defw, np.float32).reshape(-1, 4)])
+        m.anchors = np.concatenate([m.anchors, np.asarray(x.anchors, np.int32).reshape(-1, 2)])
+        m.filterid += shift(x.filterid, nf)
+        m.biasid += shift(x.biasid, nb)
+        m.defid += shift(x.defid, nd)
+        m.parentid += [list(c) for c in x.parentid]
+    return m
+
+
+def build_model(part_models, deffeat, idx, parents, interval=None, sbin=None, thresh=0.0, name="joint") -> Model:
+    """matlab/learning/buildmodel.m:19-80: the per-part models put together into the tree model the joint training starts from.
+    part_models[p]: part p's mixtures (merge_models of its K trained one-part models: filter k is mixture k's); deffeat [P][n][2]
+    (data_def); idx [P][n] the positives' 0-based mixture labels (capi.cluster_parts); parents 0-based, -1 at the root, parent < child.
+    Part p has max(idx[p]) + 1 mixtures.  Layout (make_tree_model_k's): the parts' filters back to back; one zero root bias; child p an
+    L x K block of zero biases, L its parent's count, biasid[p][k] = base + k * L; one deformation [.01 0 .01 0] per child mixture whose
+    anchor is round([mean x, mean y]) of child - parent over the positives labelled k — the differences summed left to right in
+    float64, rounded half away from zero as the file rounds it (round(mean + 1), then the loader's - 1: a mean of exactly -.5 gives 0).
+    ValueError: a label below the maximum that no positive carries (the file's anchor would be NaN), a part model with fewer filters
+    than the part has mixtures, parents not as above."""
+    deffeat = np.asarray(deffeat, np.float64)
+    idx = np.asarray(idx)
+    parents = [int(v) for v in parents]
+    P = len(parents)
+    if deffeat.ndim != 3 or deffeat.shape[0] != P or deffeat.shape[2] != 2 or idx.shape != deffeat.shape[:2] or len(part_models) != P:
+        raise ValueError("build_model: deffeat [P, n, 2], idx [P, n], one part model and one parent per part")
+    if P < 1 or parents[0] != -1 or any(not 0 <= parents[p] < p for p in range(1, P)):
+        raise ValueError("build_model: parents are 0-based with -1 at part 0 only and parent < child")
+    if idx.size == 0 or idx.min() < 0:
+        raise ValueError("build_model: labels are 0-based and every part has at least one positive")
+    Ks = [int(idx[p].max()) + 1 for p in range(P)]
+    filt, biasw, defw, anchors = [], [0.0], [], []
+    filterid, defid, biasid = [[]], [[]], [[]]
+    for p in range(P):
+        K = Ks[p]
+        if len(part_models[p].filtersw) < K:
+            raise ValueError(f"build_model: part {p} has {K} mixtures, its part model {len(part_models[p].filtersw)} filters")
+        if p == 0:
+            biasid[0].append([0])
+        else:
+            L = Ks[parents[p]]
+            biasid[0].append([len(biasw) + k * L for k in range(K)])
+            biasw += [0.0] * (K * L)
+        filterid[0].append([len(filt) + k for k in range(K)])
+        filt += [np.array(part_models[p].filtersw[k], np.float32) for k in range(K)]
+        if p == 0:
+            defid[0].append([])
+            continue
+        defid[0].append([len(defw) + k for k in range(K)])
+        for k in range(K):
+            sel = idx[p] == k
+            if not sel.any():
+                raise ValueError(f"build_model: no positive carries mixture {k} of part {p} (the anchor would be NaN)")
+            mean = [np.cumsum(deffeat[p][sel, a] - deffeat[parents[p]][sel, a])[-1] / np.float64(sel.sum()) for a in (0, 1)]
+            one = [v + 1.0 for v in mean]                                           # d.anchor = round([x+1 y+1 0])
+            anchors.append([int(np.copysign(np.floor(abs(v) + 0.5), v)) - 1 for v in one])   # ... and zeroIndex
+            defw.append([0.01, 0.0, 0.01, 0.0])
+    first = part_models[0]
+    return Model(filt, np.asarray(biasw, np.float32), np.asarray(anchors, np.int32).reshape(-1, 2),
+                 np.asarray(defw, np.float32).reshape(-1, 4), filterid, biasid, defid, [parents],
+                 first.interval if interval is None else int(interval), float(thresh), first.sbin if sbin is None else int(sbin),
+                 first.norient, first.flen, name)
 
 
 def make_person_model(seed=1234, K=6, thresh=0.0, interval=10, sbin=4) -> Model:
