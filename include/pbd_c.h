@@ -181,7 +181,9 @@ int pbd_abi_version(void);
  * pbd_qp_write_latent_u8, pbd_qp_write_latent_dev_u8, pbd_qp_write_latent_batch_u8 and pbd_croppos (with the struct
  * pbd_latent_example); and the evaluation ledger pbd_eval: pbd_eval_create, _destroy, _reset, _dims, _get, _add_pck_records,
  * _add_apk_records, _pck_frame_u8, _pck_frame_batch_u8, _apk_frame_u8, _apk_frame_batch_u8, _pck and _apk, with the host-only
- * definitions pbd_eval_keypoint_dist, _pck_host, _apk_match_host and _ap_host (PBD_EVAL_SCALE_LAST / _OWN).                            */
+ * definitions pbd_eval_keypoint_dist, _pck_host, _apk_match_host and _ap_host (PBD_EVAL_SCALE_LAST / _OWN); and the part mixtures
+ * pbd_kmeans_host, pbd_cluster_parts_host and pbd_cluster_parts; and the seams of one training round: pbd_set_interval,
+ * pbd_get_interval, pbd_qp_clear and pbd_qp_positive_threshold.                                                                      */
 
 /* ---- output record: include/Candidate.hpp:56-111 --------------------------
  * One candidate = head + max_parts boxes (x, y, width, height as cv::Rect)
@@ -1222,7 +1224,7 @@ int pbd_get_threshold(const pbd_handle* h, float* thresh);
  *   pbd_qp_opt then pbd_qp_prune, PBD_MINE_ONE with pbd_qp_one, either with pbd_qp_apply_weights.
  *   DEVIATION: detect.m tests after every (level, component) and may change the model in the middle of a frame; here the model is
  *   constant over a call.  DEVIATION: detect.m:36,56 visits levels and components in a random permutation; here the order is the one
- *   stated above.  (train.m:96's model.interval = 2 while mining stays the caller's: a handle's interval is fixed at pbd_create.)
+ *   stated above.  (train.m:96's model.interval = 2 while mining is pbd_set_interval, "one training round" below.)
  * Validation.  A scan on the device validates every record before anything is written.  A record pbd_qp_write would refuse — a repeated
  *   dense start (qp_write.m:34-35; the test is exact: parts that share an id only in mixtures the pose did not pick are accepted), a
  *   part outside its level, a column longer than k — gets the whole call PBD_ERR_ARG: nothing is written, ub and n are unchanged, the
@@ -1462,6 +1464,48 @@ int pbd_cluster_parts_host(const double* def, int n, int P, const int32_t* paren
 int pbd_cluster_parts(int device, const double* def, int n, int P, const int32_t* parent, const int32_t* K, int R, uint64_t seed,
                       int max_iter, int32_t* idx, double* centres, double* sumdist, int32_t* best_trial, double* trial_sumdist,
                       int32_t* trial_iters, int32_t* capped);
+
+/* ---- one training round: what train.m still needed around the entries above (ABI 5, additive) ------------------------------------------------
+ * train.m:73-121 is: qp.n = 0; the positives; fix, prune, opt, vec2model; model.interval = 2; mine the negatives; opt, vec2model; the
+ * threshold from the positives' scores; the interval back.  The sections above are its bodies.  These three are its seams, on the device:
+ * with them a round is the binding's train() (PartsBasedDetector<T>::train of the host layer) and moves no per-example data over PCIe.
+ *
+ * pbd_set_interval / pbd_get_interval (train.m:95-96,121: interval0 = model.interval; model.interval = 2; ...; model.interval = interval0).
+ *   interval in 1..16, the bound pbd_create checks.  The handle's model gets the new interval; the frame plan and any captured graph are
+ *   dropped, as pbd_set_weights and pbd_set_levels drop them (stage getters answer PBD_ERR_STATE until the next frame).  After a
+ *   successful call the handle behaves in every entry point exactly like a handle freshly created from the same model with that
+ *   interval, the same weights, threshold, options and setters: the results are the same in bits.  pbd_options.conv_mode's resolution is
+ *   NOT repeated; a geometry chosen by pbd_tune_plan survives (the rule of pbd_set_weights).  A bound pbd_qp or pbd_eval stays valid:
+ *   their columns and ledgers hold features and records, not geometry.  A frame with too few levels for the new interval is refused by
+ *   the next frame entry, with the message a fresh handle gives.  Setting the interval the handle has is PBD_OK and drops nothing.
+ *   Refusals, changing nothing (a detect afterwards returns the bits it returned before): PBD_ERR_ARG — an interval out of range;
+ *   PBD_ERR_UNSUPPORTED — a pbd_group member; PBD_ERR_STATE — a frame or batch in flight between enqueue and collect.
+ *   pbd_get_interval: the handle's current interval (0 for NULL).
+ * pbd_qp_clear (train.m:75: qp.n = 0).  The cache keeps its capacity, footprint, wreg, w0, cpos / cneg, noneg and binding, and holds no
+ *   example: columns, ids, b, d and the example -> column map are what pbd_qp_create left (pbd_qp_get behind n reads zeros again), and
+ *   the solver's state, where a solver entry has allocated it, is what pbd_qp_state_get answers on a cache that never solved: a = 0,
+ *   sv = 0, w = 0, l = lb = lb_old = ub = 0, nfix = 0.  A refill's bits are a new cache's.  Synchronous.
+ *   DEVIATION: train.m:75 resets qp.n alone, so MATLAB's iterations after the first start from stale qp.a, qp.sv and bounds; here the
+ *   cache is clean.  trainmodel.m only ever runs iter = 1, where the two agree.
+ * pbd_qp_positive_threshold (train.m:116-118 with qp_scorepos, :198-204): r = sort(score(qp.w + qp.w0 .* qp.wreg, qp.x, find(qp.i(1, 1:n)
+ *   == 1)) / qp.Cpos); thresh = r(ceil(length(r) * q)) — the threshold a trained model ships with (train.m: q = .05), from the resident
+ *   columns and the solver's resident w.  Steps, all on the device (k_qp_thresh.hip):
+ *     the examples whose first id word is 1, in ascending index order — a stream compaction, no atomic decides an order —, m of them;
+ *     w_eff[j] = w[j] + w0[j] * wreg[j], the product rounded, then the sum, nothing fused;
+ *     the selection's scores by the kernel pbd_qp_score_dev launches: the bits pbd_qp_score(w_eff, I) returns;
+ *     each score divided by cpos, one rounded division;
+ *     the element of ascending rank max(ceil(m * q), 1) - 1, the product in double (Model.positive_threshold's rule of the binding).  The
+ *       rank of a score is an exact count: the strictly smaller scores plus the equal scores at a smaller position.  Ties cannot change
+ *       the value.  (-0.0 and +0.0 compare equal, as in MATLAB's sort; which of the two zeros is returned is the position's.)
+ *       The count is O(m^2) comparisons for any m up to the capacity, as mining's record order is.
+ *   *thresh = that score, *npos = m: one double and one int come back (m once in between, for the launch sizes).  The cache, the
+ *   solver's a, sv, w and bounds are not changed.  It needs what every solver entry needs (the state is allocated if it is not).
+ *   Refusals: PBD_ERR_ARG — NULL thresh / npos, q outside (0, 1] or NaN, a score that is not finite (the message names the example's
+ *   index; the smallest one); PBD_ERR_STATE — m == 0 (an empty cache included).                                                        */
+int pbd_set_interval(pbd_handle* h, int interval);
+int pbd_get_interval(const pbd_handle* h);
+int pbd_qp_clear(pbd_qp* qp);
+int pbd_qp_positive_threshold(pbd_qp* qp, double q, double* thresh, int* npos);
 
 /* ---- instrumentation --------------------------------------------------------
  * GPU time (ms, hipEvent) of the stages of the last synchronous detect:

@@ -79,11 +79,13 @@ EXPORTS = [
     "pbd_eval_add_apk_records", "pbd_eval_pck_frame_u8", "pbd_eval_pck_frame_batch_u8", "pbd_eval_apk_frame_u8",
     "pbd_eval_apk_frame_batch_u8", "pbd_eval_pck", "pbd_eval_apk",
     "pbd_kmeans_host", "pbd_cluster_parts_host", "pbd_cluster_parts",
+    "pbd_set_interval", "pbd_get_interval", "pbd_qp_clear", "pbd_qp_positive_threshold",
 ]
 PBD_CLUSTER_MAX_K, PBD_CLUSTER_MAX_ITER, PBD_CLUSTER_MAX_TRIALS, PBD_CLUSTER_MAX_LABELS = 32, 10000, 2 ** 20, 2 ** 31 - 1   # include/pbd_c.h "part mixtures"
 PBD_EVAL_SCALE_LAST, PBD_EVAL_SCALE_OWN = 0, 1   # pbd_eval_pck's scale rule: eval_pck.m:13 literally (the last instance's scale) / each instance's own
 PBD_MINE_NONE, PBD_MINE_ONE, PBD_MINE_OPT = 0, 1, 2   # pbd_qp_mine_*'s action (detect.m:148-149, 315-324)
 PBD_WARP_SKIPPED, PBD_WARP_WRITTEN, PBD_WARP_FULL = 0, 1, 2   # pbd_qp_write_warped_u8's status per box
+QP_THRESH_BLOCK = 256   # lanes of a workgroup of k_qp_thresh.hip (QT_NT): pbd_qp_positive_threshold ranks that many scores per round
 PBD_ABI_VERSION = 5
 
 
@@ -238,6 +240,10 @@ def lib() -> C.CDLL:
         L.pbd_kmeans_host.argtypes = [V, I, I, I, V, C.c_uint64, I, V, V, V, V]
         L.pbd_cluster_parts_host.argtypes = [V, I, I, V, V, I, C.c_uint64, I, V, V, V, V, V, V, V]
         L.pbd_cluster_parts.argtypes = [I, V, I, I, V, V, I, C.c_uint64, I, V, V, V, V, V, V, V]
+        L.pbd_set_interval.argtypes = [V, I]
+        L.pbd_get_interval.argtypes = [V]
+        L.pbd_qp_clear.argtypes = [V]
+        L.pbd_qp_positive_threshold.argtypes = [V, D, V, V]
         if L.pbd_abi_version() != PBD_ABI_VERSION:
             raise ImportError(f"{LIB_PATH}: ABI version {L.pbd_abi_version()}, this binding is for {PBD_ABI_VERSION}")
         _lib = L
@@ -372,6 +378,19 @@ class Handle:
         t = C.c_float()
         self._chk(self.L.pbd_get_threshold(self.h, C.byref(t)))
         return t.value
+
+    # ---- the interval (include/pbd_c.h "one training round": train.m:95-96,121) ----
+    def set_interval(self, interval: int):
+        """pbd_set_interval: the pyramid's levels per octave from the next frame on (1..16).  The handle then behaves like one freshly
+        created from the same model with that interval, which self.model gets; a bound QpCache or Eval stays valid."""
+        self._chk(self.L.pbd_set_interval(self.h, int(interval)))
+        self.model = copy.copy(self.model)
+        self.model.interval = self.interval
+
+    @property
+    def interval(self) -> int:
+        """pbd_get_interval"""
+        return int(self.L.pbd_get_interval(self.h))
 
     def set_candidate_nms(self, kind, top=0):
         """pbd_set_candidate_nms: PBD_NMS_PAINTED / PBD_NMS_PARTS (top: 1000 = nms.m's cut, 0 = none) for the frames enqueued from now on."""
@@ -1538,13 +1557,26 @@ class QpCache:
         self.handle._chk(self.L.pbd_qp_apply_weights(self.q))
         self.handle._model_follows()
 
+    # ---- one training round (include/pbd_c.h "one training round") ----
+    def clear(self) -> None:
+        """pbd_qp_clear: train.m:75's qp.n = 0 — the cache keeps capacity, wreg, w0, noneg and binding and is otherwise a new cache's,
+        the solver's state (a, sv, w, the bounds, nfix) included"""
+        self.handle._chk(self.L.pbd_qp_clear(self.q))
+
+    def positive_threshold(self, q: float = .05):
+        """pbd_qp_positive_threshold: train.m:116-118 on the device — Model.positive_threshold(score(w + w0 * wreg, positives) / cpos,
+        q) with the solver's resident w, bit for bit -> (thresh, the number of positives)"""
+        t, m = C.c_double(), C.c_int()
+        self.handle._chk(self.L.pbd_qp_positive_threshold(self.q, float(q), C.byref(t), C.byref(m)))
+        return t.value, m.value
+
     # ---- hard-negative mining (include/pbd_c.h "hard-negative mining") ----
     def mine(self, im, id: int):
         """pbd_qp_mine_u8: train.m:102's detect(im, model, -1, [], 0, id, -1) on the cache's handle — the frame is detected as
         Handle.detect would detect it (the handle's threshold, candidate filter, pad and pyramid kind), its records stay on the device
         and become examples of label -1, ub grows by every record's slack -> (records, written, action): the frame's records, how many
-        the cache had room for, and PBD_MINE_NONE / _ONE / _OPT: what detect.m would now run.  train.m:96's model.interval = 2 is the
-        caller's business: a handle's interval is fixed when it is created."""
+        the cache had room for, and PBD_MINE_NONE / _ONE / _OPT: what detect.m would now run.  train.m:96's model.interval = 2 is
+        Handle.set_interval."""
         im, w, hgt, cn, stride = _frame(im)
         rec, wr, act = C.c_int(-1), C.c_int(-1), C.c_int(-1)
         rc = self.L.pbd_qp_mine_u8(self.q, _vp(im), w, hgt, cn, stride, int(id), C.byref(rec), C.byref(wr), C.byref(act))

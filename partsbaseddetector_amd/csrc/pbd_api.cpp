@@ -814,6 +814,22 @@ int pbd_set_levels(pbd_handle* h, const int32_t* levels, int n) {
   free_frame(h);   // the work tables are per geometry AND level set: re-planned on the next frame
   return PBD_OK;
 }
+// train.m:95-96,121 model.interval = 2 while mining (include/pbd_c.h "one training round"): the interval enters the frame plan alone —
+// the pyramid's geometry and job tables — so the plan and the captured graph are dropped and the next frame plans with the new one.
+// The weights, the banks, the tuned DT geometry (h->dt_geom) and every setter's state are not the interval's and stay.
+int pbd_set_interval(pbd_handle* h, int interval) {
+  if (!h) return PBD_ERR_ARG;
+  if (interval < 1 || interval > 16) return fail(h, PBD_ERR_ARG, "interval: 1..16 levels per octave");
+  if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, "interval: pbd_group members are not supported");
+  if (h->pf.active) return fail(h, PBD_ERR_STATE, "a frame is in flight: collect it first");
+  if (interval == h->md.interval) return PBD_OK;
+  ON_DEVICE(h);
+  hipStreamSynchronize(h->stream);
+  h->md.interval = interval;
+  free_frame(h);
+  return PBD_OK;
+}
+int pbd_get_interval(const pbd_handle* h) { return h ? h->md.interval : 0; }
 // Boundary padding (include/pbd_c.h): the plan — buffers, work tables, captured graph — is per padding, dropped like pbd_set_levels does
 int pbd_set_boundary_pad(pbd_handle* h, int pad) {
   if (!h) return PBD_ERR_ARG;

@@ -844,6 +844,13 @@ struct QpSolveDev {
 void launch_qp_pass(const QpDev& q, const QpSolveDev& s, const int* noneg, int p, int n, hipStream_t st);
 void launch_qp_clamp_norm(const QpSolveDev& s, const int* noneg, int p, int len, hipStream_t st);
 void launch_qp_weights(const double* w, const double* wreg, const double* w0, int len, double* out, hipStream_t st);
+// the positives' threshold (k_qp_thresh.hip, pbd_qp_solve.cpp; include/pbd_c.h "one training round")
+#define QT_NT 256                 // lanes of a workgroup of every kernel of the file; the rank kernel stages this many scores at a time
+struct QpThreshOut { double thresh; int bad; int m; };   // the order statistic; the first example with a non-finite score or -1; the positives
+void launch_qp_thresh_weff(const double* w, const double* w0, const double* wreg, int len, double* out, hipStream_t st);
+void launch_qp_thresh_select(const QpDev& q, int n, int* sel, QpThreshOut* out, hipStream_t st);             // sel[capacity], out->m
+void launch_qp_thresh_scale(double* s, const int* sel, int m, double cpos, QpThreshOut* out, hipStream_t st);   // s /= cpos, out->bad
+void launch_qp_thresh_rank(const double* s, int m, int rank, QpThreshOut* out, hipStream_t st);             // out->thresh
 // weight updates (k_weights.hip, pbd_weights.cpp; include/pbd_c.h "weight and threshold updates").  stage: the model's float32 weights in
 // Model.feature_layout() order; src[n]: where filter n of the bank being packed starts in it
 void launch_weights_round(const double* w, int len, float* out, int* bad, hipStream_t s);   // *bad: the first index that is not finite as a float, or -1

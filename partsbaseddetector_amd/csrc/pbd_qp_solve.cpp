@@ -405,5 +405,77 @@ int pbd_qp_apply_weights(pbd_qp* q) {
   return pbd_i_set_weights_dev(h, (const double*)t.p, (int)len);
 }
 
+// train.m:75 qp.n = 0.  The cache goes back to what pbd_qp_create left — columns, tables and the example -> column map included, so
+// that what pbd_qp_get reads behind n is a new cache's too — and the solver's state, where it exists, to a cache's that never solved.
+// Capacity, footprint, wreg, w0, cpos / cneg, noneg and the binding stay.
+int pbd_qp_clear(pbd_qp* q) {
+  if (!q) return PBD_ERR_ARG;
+  pbd_handle* h = q->h;
+  ON_DEVICE(h);
+  QpDev& D = q->dev;
+  const size_t cap = (size_t)D.capacity;
+  for (size_t i = 0; i < cap; ++i) q->slot[i] = (int)i;
+  HIPCHK(h, hipMemsetAsync(D.x, 0, sizeof(float) * cap * (size_t)D.k, h->stream));
+  HIPCHK(h, hipMemsetAsync(D.ids, 0, sizeof(int) * cap * 5, h->stream));
+  HIPCHK(h, hipMemsetAsync(D.b, 0, sizeof(float) * cap, h->stream));
+  HIPCHK(h, hipMemsetAsync(D.d, 0, sizeof(double) * cap, h->stream));
+  HIPCHK(h, hipMemsetAsync(D.tab, 0, sizeof(int) * cap * D.nbmax * 3, h->stream));
+  HIPCHK(h, hipMemsetAsync(D.nblk, 0, sizeof(int) * cap, h->stream));
+  HIPCHK(h, hipMemcpyAsync(D.slot, q->slot.data(), sizeof(int) * cap, hipMemcpyHostToDevice, h->stream));
+  QpSolveState& S = q->sol;
+  if (S.have) {
+    HIPCHK(h, hipMemsetAsync(S.dev.a, 0, sizeof(double) * cap, h->stream));
+    HIPCHK(h, hipMemsetAsync(S.dev.sv, 0, cap, h->stream));
+    HIPCHK(h, hipMemsetAsync(S.dev.w, 0, sizeof(double) * (size_t)D.len, h->stream));
+    HIPCHK(h, hipMemsetAsync(S.dev.stat, 0, sizeof(double) * QP_STAT_N, h->stream));
+  }
+  int rc = finish(h, "example cache clear: ");
+  if (rc) return rc;
+  S.l = S.lb = S.lb_old = S.ub = S.ww = 0;
+  S.nfix = 0;
+  q->overlap.assign(cap, 0);
+  q->meta_dirty = true;
+  q->n = 0;
+  return PBD_OK;
+}
+
+// train.m:116-118 with qp_scorepos (:198-204): the selection, w + w0 .* wreg, the scores, / Cpos and the order statistic all on the
+// device (k_qp_thresh.hip).  The selection and the scores borrow the pass's scratch (order, scores): nothing a getter answers moves.
+int pbd_qp_positive_threshold(pbd_qp* q, double frac, double* thresh, int* npos) {
+  SOLVER_ENTRY(q);
+  if (!thresh || !npos) return fail(h, PBD_ERR_ARG, "positive threshold: thresh / npos is NULL");
+  if (!(frac > 0.0) || !(frac <= 1.0)) return fail(h, PBD_ERR_ARG, "positive threshold: q must lie in (0, 1]");
+  if (q->n == 0) return fail(h, PBD_ERR_STATE, "positive threshold: the cache holds no positive example");
+  QpSolveDev& D = q->sol.dev;
+  const size_t len = (size_t)q->dev.len;
+  Tmp t;
+  int rc;
+  if ((rc = t.get(h, sizeof(double) * len + sizeof(QpThreshOut)))) return rc;
+  double* d_weff = (double*)t.p;
+  QpThreshOut* d_out = (QpThreshOut*)(d_weff + len);
+  QpThreshOut out{0.0, -1, 0};
+  HIPCHK(h, hipMemsetAsync(d_out, 0, sizeof(QpThreshOut), h->stream));
+  launch_qp_thresh_select(q->dev, q->n, D.order, d_out, h->stream);
+  launch_qp_thresh_weff(D.w, q->d_w0, q->d_wreg, (int)len, d_weff, h->stream);
+  LAUNCHCHK(h, "positive threshold");
+  HIPCHK(h, hipMemcpyAsync(&out.m, &d_out->m, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if ((rc = finish(h, "positive threshold: "))) return rc;
+  const int m = out.m;
+  if (m < 0 || m > q->n) return fail(h, PBD_ERR_HIP, "positive threshold: the selection's count is out of range");
+  if (m == 0) return fail(h, PBD_ERR_STATE, "positive threshold: the cache holds no positive example");
+  const int rank = std::min(std::max((int)std::ceil((double)m * frac), 1), m) - 1;   // Model.positive_threshold's rule
+  launch_qp_score(q->dev, d_weff, D.order, m, D.scores, h->stream);
+  launch_qp_thresh_scale(D.scores, D.order, m, q->cpos, d_out, h->stream);
+  launch_qp_thresh_rank(D.scores, m, rank, d_out, h->stream);
+  LAUNCHCHK(h, "positive threshold");
+  HIPCHK(h, hipMemcpyAsync(&out, d_out, sizeof(QpThreshOut), hipMemcpyDeviceToHost, h->stream));
+  if ((rc = finish(h, "positive threshold: "))) return rc;
+  if (out.bad >= 0)
+    return fail(h, PBD_ERR_ARG, "positive threshold: the score of example " + std::to_string(out.bad) + " is not finite");
+  *thresh = out.thresh;
+  *npos = m;
+  return PBD_OK;
+}
+
 }  // extern "C"
 #pragma GCC visibility pop

@@ -362,6 +362,16 @@ class PartsBasedDetector:
         Model.positive_threshold of the positives' scores)."""
         self.handle.set_threshold(t)
 
+    def setInterval(self, interval: int) -> None:
+        """train.m:95-96,121 model.interval = 2 on the live detector: the pyramid's levels per octave from the next frame on (1..16).
+        The detector then behaves like one given the same model with that interval; an ExampleCache bound to it stays valid."""
+        self.handle.set_interval(interval)
+
+    @property
+    def interval(self) -> int:
+        """the interval the detector runs now"""
+        return self.handle.interval
+
     def updateFrom(self, cache: "capi.QpCache") -> None:
         """train.m:94,112 model = vec2model(qp_w, model): the solver's weights into this detector, without leaving the device"""
         if cache.handle is not self.handle:
@@ -555,8 +565,7 @@ class PartsBasedDetector:
         on PBD_MINE_ONE one() over a shuffle of find(sv) drawn as opt draws it; after either the weights go into this detector
         (apply_weights).  Stops behind the image after which sum(sv) == capacity (train.m:105).  Returns (records, written, action) per
         image mined.  Not done here: detect.m updates the model in the middle of a frame and visits levels and components in a random
-        order; and train.m:96's model.interval = 2 while mining stays the caller's business — a detector's interval is fixed by the
-        model it was given (distributeModel)."""
+        order.  train.m:96's model.interval = 2 while mining is setInterval(2) around this call (train.train does it)."""
         if cache.handle is not self.handle:
             raise ValueError("mineNegatives: the cache is bound to another detector")
         out = []

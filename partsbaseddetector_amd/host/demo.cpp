@@ -1,6 +1,6 @@
 // demo.cpp — the reference's canonical caller (src/demo.cpp:55-118) against the MI355X path:
 //   pbd_demo model.bin image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE] [--examples FILE] [--matlab-pyramid]
-//            [--gtbox x1,y1,x2,y2[,overlap]]... [--mine FILE]... [--poslatent FILE x,y,w,h[;x,y,w,h...]]...
+//            [--gtbox x1,y1,x2,y2[,overlap]]... [--mine FILE]... [--poslatent FILE x,y,w,h[;x,y,w,h...]]... [--train]
 //   pbd_demo model.bin image.raw width height channels perturb-features <responses-out.bin>
 //   pbd_demo model.bin image.raw width height channels oracle-responses <responses-in.bin>
 // deserialize -> distributeModel -> detect -> Candidate::sort, then prints the candidates (the
@@ -27,6 +27,17 @@ static std::vector<const char*> g_mine;
 // box per part, as detect() returns boxes — into a cache of 256 examples, Cpos = Cneg = 1, ids 1, 2, ..., overlap 0.6; per frame its block
 struct PosLatent { const char* file; std::vector<Rect> truth; };
 static std::vector<PosLatent> g_poslatent;
+// --train (anywhere; with --poslatent and --mine): one latent round of train.m (PartsBasedDetector<T>::train, defaults: C .002, wpos 2,
+// overlap .6, capacity 30 per positive) over the --poslatent frames as positives and the --mine frames as negatives; one line per report field
+static bool g_train = false;
+static Mat read_frame(const char* what, const char* name, const Mat& im) {
+  Mat fr(im.rows, im.cols, PBD_8U, im.channels());
+  const size_t bytes = (size_t)im.rows * im.cols * im.channels();
+  FILE* f = fopen(name, "rb");
+  if (!f || fread(fr.ptr<uint8_t>(), 1, bytes, f) != bytes) { printf("%s %s: not found or not a frame of the image's size\n", what, name); exit(-4); }
+  fclose(f);
+  return fr;
+}
 static void print_pose(const Candidate& c) {
   printf("%.9g %d %d", c.score(), c.component(), c.level);
   for (const Rect& r : c.parts()) printf(" %d,%d,%d,%d", r.x, r.y, r.width, r.height);
@@ -78,6 +89,26 @@ static void run(Model& model, const Mat& im, bool stagewise, int special = 0, co
       }
       printf("\n");
     }
+    return;
+  }
+  if (g_train) {
+    std::vector<Mat> pos, neg;
+    for (const PosLatent& pl : g_poslatent) pos.push_back(read_frame("--poslatent", pl.file, im));
+    for (const char* name : g_mine) neg.push_back(read_frame("--mine", name, im));
+    std::vector<typename PartsBasedDetector<T>::Positive> items;
+    for (size_t i = 0; i < pos.size(); ++i) items.push_back({&pos[i], g_poslatent[i].truth, {}});
+    const auto report = pbd.train(items, neg);
+    for (size_t t = 0; t < report.size(); ++t) {
+      const auto& r = report[t];
+      printf("Train %zu numpositives:", t);
+      for (int c : r.numpositives) printf(" %d", c);
+      printf("\nTrain %zu n: %d %d %d\nTrain %zu sv: %d %d %d\n", t, r.n[0], r.n[1], r.n[2], t, r.sv[0], r.sv[1], r.sv[2]);
+      printf("Train %zu lb: %.17g\nTrain %zu ub: %.17g\nTrain %zu thresh: %.17g\n", t, r.lb, t, r.ub, t, (double)r.thresh);
+      printf("Train %zu mined:", t);
+      for (const auto& m : r.mined) printf(" %d,%d,%d", m.records, m.written, m.action);
+      printf("\nTrain %zu passes: %d %d\n", t, r.passes[0], r.passes[1]);
+    }
+    printf("Interval: %d\nThreshold: %.17g\n", pbd.interval(), (double)pbd.thresh());
     return;
   }
   if (!g_mine.empty()) {
@@ -371,13 +402,18 @@ int main(int argc, char** argv) {
       for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
       --argc; --i;
     } else
+    if (std::string(argv[i]) == "--train") {
+      g_train = true;
+      for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
+      --argc; --i;
+    } else
     if (std::string(argv[i]) == "--part-scores") {
       part_scores = true;
       for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
       --argc; --i;
     }
   if (argc < 6 || argc > 8) {
-    printf("Usage: pbd_demo model_file image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE] [--examples FILE] [--nms-parts OVERLAP] [--matlab-pyramid] [--gtbox x1,y1,x2,y2[,overlap]]... [--warp x1,y1,x2,y2]... [--mine FILE]... [--poslatent FILE x,y,w,h[;x,y,w,h...]]...\n");
+    printf("Usage: pbd_demo model_file image.raw width height channels [stagewise|double|stagewise-double] [--part-scores] [--pad N] [--features FILE] [--examples FILE] [--nms-parts OVERLAP] [--matlab-pyramid] [--gtbox x1,y1,x2,y2[,overlap]]... [--warp x1,y1,x2,y2]... [--mine FILE]... [--poslatent FILE x,y,w,h[;x,y,w,h...]]... [--train]\n");
     exit(-1);
   }
   // determine the type of model to read (src/demo.cpp:63-82)
@@ -406,8 +442,9 @@ int main(int argc, char** argv) {
     if (features_file && special) { printf("--features: not with %s\n", mode.c_str()); exit(-1); }
     if (g_examples_file && (special || !g_gtbox.empty())) { printf("--examples: not with %s\n", special ? mode.c_str() : "--gtbox"); exit(-1); }
     if (!g_warp.empty() && (special || stagewise || !g_gtbox.empty() || g_examples_file || features_file || part_scores || nms_parts)) { printf("--warp: on its own (or with double)\n"); exit(-1); }
-    if (!g_mine.empty() && (special || stagewise || !g_gtbox.empty() || !g_warp.empty() || g_examples_file || features_file || part_scores)) { printf("--mine: on its own (or with double, --pad, --nms-parts, --matlab-pyramid)\n"); exit(-1); }
-    if (!g_poslatent.empty() && (special || stagewise || !g_gtbox.empty() || !g_warp.empty() || !g_mine.empty() || g_examples_file || features_file || part_scores)) { printf("--poslatent: on its own (or with double, --pad, --nms-parts, --matlab-pyramid)\n"); exit(-1); }
+    if (g_train && (g_poslatent.empty() || special || stagewise || !g_gtbox.empty() || !g_warp.empty() || g_examples_file || features_file || part_scores)) { printf("--train: with --poslatent (the positives) and --mine (the negatives), or with double, --pad, --nms-parts, --matlab-pyramid\n"); exit(-1); }
+    if (!g_train && !g_mine.empty() && (special || stagewise || !g_gtbox.empty() || !g_warp.empty() || g_examples_file || features_file || part_scores)) { printf("--mine: on its own (or with double, --pad, --nms-parts, --matlab-pyramid)\n"); exit(-1); }
+    if (!g_train && !g_poslatent.empty() && (special || stagewise || !g_gtbox.empty() || !g_warp.empty() || !g_mine.empty() || g_examples_file || features_file || part_scores)) { printf("--poslatent: on its own (or with double, --pad, --nms-parts, --matlab-pyramid)\n"); exit(-1); }
     if (!g_gtbox.empty() && (part_scores || nms_parts || features_file)) { printf("--gtbox: not with --part-scores, --nms-parts or --features\n"); exit(-1); }
     if (mode.find("double") != std::string::npos) run<double>(model, im, stagewise, 0, nullptr, part_scores, pad, features_file, nms_parts, matlab_pyramid);
     else run<float>(model, im, stagewise, special, special ? argv[7] : nullptr, part_scores, pad, features_file, nms_parts, matlab_pyramid);

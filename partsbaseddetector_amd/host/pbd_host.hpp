@@ -363,6 +363,14 @@ class Device {
   void setBoundaryPad(int pad) { check(pbd_set_boundary_pad(h, pad)); }
   // the image pyramid under the features: PBD_PYRAMID_OPENCV (src/HOGFeatures.cpp:95-127) or PBD_PYRAMID_MATLAB (matlab/detection/featpyramid.m:13-34)
   void setPyramidKind(int kind) { check(pbd_set_pyramid_kind(h, kind)); }
+  // train.m:95-96,121 model.interval = 2 on the live handle: the levels per octave from the next frame on (1..16).  The plan is dropped,
+  // so nothing handed out earlier is resident any more.
+  void setInterval(int interval) {
+    check(pbd_set_interval(h, interval));
+    cell_w.clear(); cell_h.clear(); scales.clear();
+    fp_feat.clear(); fp_resp.clear(); fp_root.clear(); fp_tab.clear(); tables_resident = false;
+  }
+  int interval() const { return pbd_get_interval(h); }
 };
 
 // ---- include/IFeatures.hpp:49-73 --------------------------------------------------------------
@@ -684,6 +692,8 @@ class PartsBasedDetector {
       for (const Mat& f : model.filters()) { mh = std::max(mh, f.rows); mw = std::max(mw, f.cols / std::max(model.flen(), 1)); }
       min_area_ = (double)(mh * model.binsize()) * (double)(mw * model.binsize());
     }
+    nbias_ = (int)model.bias().size(); ndefs_ = (int)model.def().size();
+    root_filter_ = model.filterid()[0][0][0]; root_bias_ = model.biasid()[0][0][0];
     // DataType<T>::type selects the instantiation (:110,113-117)
     dev_ = std::make_shared<Device>(model, device_, conv_mode_, (int)DataType<T>::scalar, max_candidates_);
     features_.reset(new HipHOGFeatures(dev_, model.binsize(), model.nscales()));
@@ -706,6 +716,10 @@ class PartsBasedDetector {
   // the model's threshold for every detect from now on (train.m: 0 for latent positives, -1 for mining, then the positives' 5th percentile)
   void setThresh(float t) { dev_->check(pbd_set_threshold(dev_->h, t)); }
   float thresh() const { float t = 0; dev_->check(pbd_get_threshold(dev_->h, &t)); return t; }
+  // train.m:95-96,121 model.interval = 2 while mining: the pyramid's levels per octave from the next frame on (1..16).  The detector then
+  // behaves like one given the same model with that interval; an ExampleCache or Evaluation bound to it stays valid.
+  void setInterval(int interval) { dev_->setInterval(interval); }
+  int interval() const { return dev_->interval(); }
   // The image pyramid detect() builds its features on.  PBD_PYRAMID_OPENCV (the default): HOGFeatures<T>::pyramid, cv::resize and
   // cv::pyrDown in the pixel type (src/HOGFeatures.cpp:95-127).  PBD_PYRAMID_MATLAB: matlab/detection/featpyramid.m:13-34 — the frame
   // goes to double once, matlab/mex/resize.cc makes the first octave, matlab/mex/reduce.cc every further one — with its level count,
@@ -899,6 +913,23 @@ class PartsBasedDetector {
     // train.m:94,112 model = vec2model(qp_w, model): weights() into the detector this cache is bound to, without leaving the device
     // (include/pbd_c.h "weight and threshold updates"); the cache's columns stay valid
     void applyWeights() { dev_->check(pbd_qp_apply_weights(q_)); }
+    // ---- one training round (include/pbd_c.h "one training round") ----
+    // train.m:75 qp.n = 0: capacity, wreg, w0, noneg and binding stay; the rest, the solver's a, sv, w, bounds and nfix included, is a new cache's
+    void clear() { dev_->check(pbd_qp_clear(q_)); }
+    // train.m:116-118 on the device: the element of rank max(ceil(m * q), 1) - 1 of the m positives' sorted scores (w + w0 .* wreg) . x / cpos
+    double positiveThreshold(double q = .05, int* npos = nullptr) {
+      double t = 0; int m = 0;
+      dev_->check(pbd_qp_positive_threshold(q_, q, &t, &m));
+      if (npos) *npos = m;
+      return t;
+    }
+    int supportCount() {
+      std::vector<unsigned char> sv;
+      state(nullptr, &sv, nullptr);
+      int nsv = 0;
+      for (int e = 0, n = size(); e < n; ++e) nsv += sv[e] != 0;
+      return nsv;
+    }
     // poswarp of matlab/learning/train.m:131-161 (include/pbd_c.h "warped positives"): the boxes (1-based inclusive) of the 8-bit frame
     // warped to filter `filter`'s size (warppos.m), HOGed and appended as [bias | window] positives, all on the GPU.  Boxes below
     // min_area (prod(maxsize * sbin), train.m:135) are skipped; status (optional): PBD_WARP_WRITTEN / _SKIPPED / _FULL per box; ids
@@ -966,8 +997,8 @@ class PartsBasedDetector {
     }
     // train.m:99-108 with detect.m's optimize at frame granularity: per image mine(); on PBD_MINE_OPT opt then prune, on PBD_MINE_ONE one()
     // over shuffledSupport(seed); after either applyWeights(); stops behind the image after which sum(sv) == capacity (train.m:105).
-    // Not done here: mid-frame model updates, detect.m's random visiting order, and train.m:96's model.interval = 2 (a detector's interval
-    // is its model's).
+    // Not done here: mid-frame model updates and detect.m's random visiting order.  train.m:96's model.interval = 2 is the detector's
+    // setInterval(2) around this call (PartsBasedDetector::train does it).
     std::vector<Mined> mineNegatives(const std::vector<Mat>& images, int first_id = 0, double tol = .05, int max_iter = 1000, uint64_t seed = 0) {
       std::vector<Mined> out;
       for (size_t i = 0; i < images.size(); ++i) {
@@ -1151,7 +1182,87 @@ class PartsBasedDetector {
     }
     return numpositives;
   }
+  // ---- matlab/learning/train.m on the live detector (include/pbd_c.h "one training round") ----
+  // One call for train.m:73-121: per round cache.clear(); the positives — latent (warp == 0: latentPositives(overlap), ids 1, 2, ...) or
+  // warped (warp > 0: writeWarped of every box at component 0's root filter and bias, id i + 1, boxes below prod(maxsize * sbin)
+  // skipped) —; fix(n), prune, opt, applyWeights; interval0 = interval(), setInterval(2), setThresh(-1); mineNegatives with ids 1, 2, ...
+  // (it stops behind the image after which sum(sv) == capacity); opt, applyWeights; setThresh((float)positiveThreshold(.05));
+  // setInterval(interval0).  An exception from the interval change on restores the interval and the threshold before it goes on.
+  // The cache has cpos = C * wpos, cneg = C, model2vec.m's wreg and w0 (pbd_qp_create's defaults) and its noneg; capacity <= 0: the
+  // default 10 * (wpos + 1) * positives (train.m:30-31,46 without its 6 GB floor).  The trained weights and threshold are the detector's
+  // (weights(), thresh()); the Model object handed to distributeModel is not touched.
+  // Deviations from train.m, as the binding's train(): no 6 GB floor; clear() also resets the solver's a, sv and bounds (train.m:75 leaves
+  // stale ones for rounds after the first); and mineNegatives' — the model is constant over a frame, the level order is fixed, the
+  // shuffles are seeded.
+  struct WarpedPositive { const Mat* im; GtBox box; };   // box: (x1, y1, x2, y2), 1-based inclusive
+  struct TrainOptions { int iter = 1; double C = 0.002, wpos = 2, overlap = 0.6; int capacity = 0; double tol = .05; int max_iter = 1000; uint64_t seed = 0; };
+  struct TrainReport {
+    std::vector<int> numpositives;   // per component (warped: one entry, the examples written)
+    int n[3] = {0, 0, 0}, sv[3] = {0, 0, 0};   // examples and support vectors after the positives, after mining, after the last solve
+    double lb = 0, ub = 0;           // the last solve's bounds
+    float thresh = 0;                // as set
+    std::vector<typename ExampleCache::Mined> mined;   // per frame mined
+    int passes[2] = {0, 0};          // pbd_qp_one calls of the first and the last solve
+  };
+  std::vector<TrainReport> train(const std::vector<Positive>& positives, const std::vector<Mat>& negatives) { TrainOptions o; return train(positives, negatives, o); }
+  std::vector<TrainReport> train(const std::vector<Positive>& positives, const std::vector<Mat>& negatives, const TrainOptions& o) {
+    return train_(positives.size(), negatives, o, [&](ExampleCache& cache, TrainReport& r) {
+      r.numpositives = latentPositives(positives, cache, o.overlap);
+    });
+  }
+  std::vector<TrainReport> train(const std::vector<WarpedPositive>& positives, const std::vector<Mat>& negatives) { TrainOptions o; return train(positives, negatives, o); }
+  std::vector<TrainReport> train(const std::vector<WarpedPositive>& positives, const std::vector<Mat>& negatives, const TrainOptions& o) {
+    return train_(positives.size(), negatives, o, [&](ExampleCache& cache, TrainReport& r) {
+      for (size_t i = 0; i < positives.size(); ++i) {
+        const std::vector<int32_t> id(1, (int32_t)i + 1);
+        cache.writeWarped(*positives[i].im, std::vector<GtBox>(1, positives[i].box), root_filter_, root_bias_, min_area_, nullptr, &id);
+      }
+      r.numpositives.assign(1, cache.size());
+    });
+  }
  private:
+  template <typename F>
+  std::vector<TrainReport> train_(size_t npos, const std::vector<Mat>& negatives, const TrainOptions& o, F write_positives) {
+    if (!dev_) throw Exception(PBD_ERR_STATE, "train() before distributeModel()");
+    const int cap = o.capacity > 0 ? o.capacity : (int)(10 * (o.wpos + 1) * (double)npos);
+    auto cache = exampleCache(cap, o.C * o.wpos, o.C);
+    std::vector<int32_t> noneg;   // model2vec.m: elements 0 and 2 of every deformation
+    for (int d = 0; d < ndefs_; ++d) { noneg.push_back(nbias_ + 4 * d); noneg.push_back(nbias_ + 4 * d + 2); }
+    cache->noneg(noneg);
+    std::vector<TrainReport> report;
+    for (int t = 0; t < o.iter; ++t) {
+      TrainReport r;
+      auto count = [&](int at) { r.n[at] = cache->size(); r.sv[at] = cache->supportCount(); };
+      cache->clear();
+      write_positives(*cache, r);
+      count(0);
+      cache->fix(r.n[0]);
+      cache->prune();
+      r.passes[0] = cache->opt(o.tol, o.max_iter, o.seed);
+      cache->applyWeights();
+      const int interval0 = interval();
+      const float thresh0 = thresh();
+      try {
+        setInterval(2);
+        setThresh(-1.f);
+        r.mined = cache->mineNegatives(negatives, 1, o.tol, o.max_iter, o.seed);
+        count(1);
+        r.passes[1] = cache->opt(o.tol, o.max_iter, o.seed, &r.lb, &r.ub);
+        cache->applyWeights();
+        count(2);
+        r.thresh = (float)cache->positiveThreshold(.05);
+        setThresh(r.thresh);
+      } catch (...) {
+        setThresh(thresh0);
+        setInterval(interval0);
+        throw;
+      }
+      setInterval(interval0);
+      report.push_back(r);
+    }
+    return report;
+  }
+  int nbias_ = 0, ndefs_ = 0, root_filter_ = 0, root_bias_ = 0;   // of the distributed model: noneg's indices, writeWarped's defaults
   double min_area_ = 0;   // prod(maxsize * sbin) of the distributed model: latentPositives' minimum part area (train.m:170)
   int features_entry(const pbd_candidate_head* hd, const int32_t* lc, int n, FeatureBlock* b, float* w) { return pbd_candidates_features(dev_->h, hd, lc, n, b, w); }
   int features_entry(const pbd_candidate_head* hd, const int32_t* lc, int n, FeatureBlock* b, double* w) { return pbd_candidates_features_f64(dev_->h, hd, lc, n, b, w); }
