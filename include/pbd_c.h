@@ -183,7 +183,9 @@ int pbd_abi_version(void);
  * _add_apk_records, _pck_frame_u8, _pck_frame_batch_u8, _apk_frame_u8, _apk_frame_batch_u8, _pck and _apk, with the host-only
  * definitions pbd_eval_keypoint_dist, _pck_host, _apk_match_host and _ap_host (PBD_EVAL_SCALE_LAST / _OWN); and the part mixtures
  * pbd_kmeans_host, pbd_cluster_parts_host and pbd_cluster_parts; and the seams of one training round: pbd_set_interval,
- * pbd_get_interval, pbd_qp_clear and pbd_qp_positive_threshold.                                                                      */
+ * pbd_get_interval, pbd_qp_clear and pbd_qp_positive_threshold; and the pyramid store pbd_pyrstore: pbd_pyrstore_create, _destroy,
+ * _dims, _slot, _layout, _put_u8, _put_dev_u8, _put_batch_u8 and _get_level, with pbd_detect_stored, pbd_detect_batch_stored,
+ * pbd_qp_mine_stored and pbd_qp_mine_batch_stored (PBD_PYRSTORE_MAX_LEVELS).                                                         */
 
 /* ---- output record: include/Candidate.hpp:56-111 --------------------------
  * One candidate = head + max_parts boxes (x, y, width, height as cv::Rect)
@@ -1506,6 +1508,56 @@ int pbd_set_interval(pbd_handle* h, int interval);
 int pbd_get_interval(const pbd_handle* h);
 int pbd_qp_clear(pbd_qp* qp);
 int pbd_qp_positive_threshold(pbd_qp* qp, double q, double* thresh, int* npos);
+
+/* ---- pyramid store: detect and mine from resident feature pyramids (ABI 5, additive) -----------------------------------------------------
+ * A frame's HOG pyramid depends on (w, hgt, sbin, interval, pyramid kind, boundary pad, scalar type) and on nothing of the model's
+ * filters; a training of sum(K) + 2 rounds (trainmodel.m) mines the same negatives at interval 2 in every round, and two models with
+ * equal sbin / interval on one camera frame compute two identical pyramids.  A pbd_pyrstore is a device-resident array of slots, each
+ * holding the feature pyramid of ONE frame as the producer handle's front end (image pyramid, HOG, boundary ring) wrote it: level l's
+ * [ch][cw][32] block at level_off[l] elements, the levels back to back (pbd_pyrstore_layout) — the very block of the producer's
+ * feature buffer.  Any handle with the store's signature detects or mines from a slot instead of from an image.
+ *
+ * Signature: (device, sbin, interval, pyramid kind, boundary pad, scalar bytes 4 / 8, 32 channels), taken from `producer` at create
+ *   and fixed for the life of the store.  slot_bytes = total(max_w, max_h) * scalar bytes.  The store must be destroyed before its
+ *   producer; a consumer is bound to nothing.
+ * pbd_pyrstore_layout: host only, no GPU.  The geometry of the planner (HOGFeatures<T>::pyramid or featpyramid.m by `kind`, then the
+ *   padding): *nlevels, level_off[l] = the level's first element (level_off: NULL, or room for PBD_PYRSTORE_MAX_LEVELS), *total = all
+ *   elements = the sum of cw * ch * 32.  PBD_ERR_ARG: a frame too small for `interval` levels, or arguments out of the setters' ranges.
+ * Put (synchronous): the producer's own front end on the image, as pbd_pyramid_u8 runs it, then k_pyrstore_put copies the frame's
+ *   block into the slot and the slot records (w, hgt, cn).  Refused with the slot unchanged: PBD_ERR_CAPACITY — the frame's total
+ *   exceeds the slot; PBD_ERR_STATE — the producer's settings no longer equal the signature (the message names the field), or a frame
+ *   is pending on it; PBD_ERR_UNSUPPORTED — the producer is a pbd_group member, runs the compact memory plan or a level subset.
+ *   A batch put takes same-sized frames through the producer as one batch; frame f goes to slots[f].
+ * Consume: pbd_detect_stored / pbd_detect_batch_stored / pbd_qp_mine_stored / pbd_qp_mine_batch_stored are pbd_detect_u8 /
+ *   pbd_detect_batch_u8 / pbd_qp_mine_u8 / pbd_qp_mine_batch_u8 on the frame that was put, planned as the (w, hgt, cn) the put
+ *   recorded: ONE launch of k_pyrstore_load (features into the consumer's buffer, and the split banks' parts in the same pass) stands
+ *   where the image pyramid and HOG stood; everything behind it is the plain frame's.  The result equals the image entry's on the same
+ *   handle with the same image in every bit — records, counts, cache columns, ids, b, d, ub, records[], written[], action and the
+ *   error codes of an overflow or a bad record.  Model, bank, threshold, candidate mode, NMS and part scores are the consumer's own.
+ *   Stored frames run eagerly and leave a captured graph as it is.  Afterwards features, responses and min() are set and the level
+ *   images are NOT (pbd_get_level_image: PBD_ERR_STATE); the feature planes are resident for the getters and pbd_candidates_features.
+ *   The same slot may appear twice in a batch.
+ * Refusals, each with a message on the consumer, changing nothing:
+ *   PBD_ERR_ARG — NULL arguments; a slot out of range; nframes outside 1..64; slots of a batch that differ in (w, hgt, cn); a
+ *     signature field (sbin, interval, kind, pad, scalar) that differs: the message names the field and both values.
+ *   PBD_ERR_STATE — an empty slot; a frame pending.
+ *   PBD_ERR_UNSUPPORTED — pbd_group members; the compact memory plan; depth pruning, 3-D boxes, object clusters; another device.
+ * Not provided: latent, gt-box, evaluation, RGB-D and enqueue / collect entries from a store; puts of other than 8-bit frames.            */
+#define PBD_PYRSTORE_MAX_LEVELS 128
+typedef struct pbd_pyrstore pbd_pyrstore;
+int  pbd_pyrstore_create(pbd_handle* producer, int slots, int max_w, int max_h, pbd_pyrstore** out);
+void pbd_pyrstore_destroy(pbd_pyrstore* s);
+int  pbd_pyrstore_dims(const pbd_pyrstore* s, int* slots, int* sbin, int* interval, int* kind, int* pad, int* scalar_bytes, size_t* slot_bytes);
+int  pbd_pyrstore_slot(const pbd_pyrstore* s, int slot, int* w, int* hgt, int* cn, int* nlevels);   /* w = 0: empty */
+int  pbd_pyrstore_layout(int w, int hgt, int sbin, int interval, int kind, int pad, int* nlevels, long long* level_off, long long* total);  /* host only */
+int  pbd_pyrstore_put_u8(pbd_pyrstore* s, int slot, const uint8_t* im, int w, int hgt, int cn, int stride);
+int  pbd_pyrstore_put_dev_u8(pbd_pyrstore* s, int slot, const void* d_im, int w, int hgt, int cn, int stride);
+int  pbd_pyrstore_put_batch_u8(pbd_pyrstore* s, const int32_t* slots, const uint8_t* const* ims, int nframes, int w, int hgt, int cn, int stride);
+int  pbd_pyrstore_get_level(pbd_pyrstore* s, int slot, int level, void* out, size_t out_bytes);
+int  pbd_detect_stored(pbd_handle* h, pbd_pyrstore* s, int slot, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* count);
+int  pbd_detect_batch_stored(pbd_handle* h, pbd_pyrstore* s, const int32_t* slots, int nframes, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* counts);
+int  pbd_qp_mine_stored(pbd_qp* qp, pbd_pyrstore* s, int slot, int id, int* records, int* written, int* action);
+int  pbd_qp_mine_batch_stored(pbd_qp* qp, pbd_pyrstore* s, const int32_t* slots, int nframes, const int32_t* ids, int32_t* records, int32_t* written, int* action);
 
 /* ---- instrumentation --------------------------------------------------------
  * GPU time (ms, hipEvent) of the stages of the last synchronous detect:

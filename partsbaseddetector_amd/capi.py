@@ -80,7 +80,11 @@ EXPORTS = [
     "pbd_eval_apk_frame_batch_u8", "pbd_eval_pck", "pbd_eval_apk",
     "pbd_kmeans_host", "pbd_cluster_parts_host", "pbd_cluster_parts",
     "pbd_set_interval", "pbd_get_interval", "pbd_qp_clear", "pbd_qp_positive_threshold",
+    "pbd_pyrstore_create", "pbd_pyrstore_destroy", "pbd_pyrstore_dims", "pbd_pyrstore_slot", "pbd_pyrstore_layout",
+    "pbd_pyrstore_put_u8", "pbd_pyrstore_put_dev_u8", "pbd_pyrstore_put_batch_u8", "pbd_pyrstore_get_level",
+    "pbd_detect_stored", "pbd_detect_batch_stored", "pbd_qp_mine_stored", "pbd_qp_mine_batch_stored",
 ]
+PBD_PYRSTORE_MAX_LEVELS = 128   # room pbd_pyrstore_layout's level_off needs
 PBD_CLUSTER_MAX_K, PBD_CLUSTER_MAX_ITER, PBD_CLUSTER_MAX_TRIALS, PBD_CLUSTER_MAX_LABELS = 32, 10000, 2 ** 20, 2 ** 31 - 1   # include/pbd_c.h "part mixtures"
 PBD_EVAL_SCALE_LAST, PBD_EVAL_SCALE_OWN = 0, 1   # pbd_eval_pck's scale rule: eval_pck.m:13 literally (the last instance's scale) / each instance's own
 PBD_MINE_NONE, PBD_MINE_ONE, PBD_MINE_OPT = 0, 1, 2   # pbd_qp_mine_*'s action (detect.m:148-149, 315-324)
@@ -244,6 +248,20 @@ def lib() -> C.CDLL:
         L.pbd_get_interval.argtypes = [V]
         L.pbd_qp_clear.argtypes = [V]
         L.pbd_qp_positive_threshold.argtypes = [V, D, V, V]
+        L.pbd_pyrstore_create.argtypes = [V, I, I, I, V]
+        L.pbd_pyrstore_destroy.restype = None
+        L.pbd_pyrstore_destroy.argtypes = [V]
+        L.pbd_pyrstore_dims.argtypes = [V] * 8
+        L.pbd_pyrstore_slot.argtypes = [V, I, V, V, V, V]
+        L.pbd_pyrstore_layout.argtypes = [I, I, I, I, I, I, V, V, V]
+        for name in ("pbd_pyrstore_put_u8", "pbd_pyrstore_put_dev_u8"):
+            getattr(L, name).argtypes = [V, I, V, I, I, I, I]
+        L.pbd_pyrstore_put_batch_u8.argtypes = [V, V, V, I, I, I, I, I]
+        L.pbd_pyrstore_get_level.argtypes = [V, I, I, V, C.c_size_t]
+        L.pbd_detect_stored.argtypes = [V, V, I, V, V, V, I, V]
+        L.pbd_detect_batch_stored.argtypes = [V, V, V, I, V, V, V, I, V]
+        L.pbd_qp_mine_stored.argtypes = [V, V, I, I, V, V, V]
+        L.pbd_qp_mine_batch_stored.argtypes = [V, V, V, I, V, V, V, V]
         if L.pbd_abi_version() != PBD_ABI_VERSION:
             raise ImportError(f"{LIB_PATH}: ABI version {L.pbd_abi_version()}, this binding is for {PBD_ABI_VERSION}")
         _lib = L
@@ -765,6 +783,23 @@ class Handle:
         self._chk(self.L.pbd_detect_collect(self.h, heads.ctypes.data_as(C.c_void_p), _p(boxes, C.c_int32),
                                             _p(locs, C.c_int32), capacity, C.byref(cnt)))
         return self._out(heads, boxes, locs, cnt.value)
+
+    # ---- frames from a pyramid store (include/pbd_c.h "pyramid store") ---------------------
+    def detect_stored(self, store: "PyramidStore", slot: int, capacity=4096):
+        """pbd_detect_stored: detect() on the frame that was put into `slot` of `store` — the slot's feature pyramid is loaded where the
+        image pyramid and HOG ran; the result is detect(image)'s on this handle, in bits.  `slot` may be a StoredFrame."""
+        store, slot = _stored(store, slot)
+        heads, boxes, locs = self._bufs(capacity)
+        cnt = C.c_int(0)
+        self._chk(self.L.pbd_detect_stored(self.h, store.s, int(slot), heads.ctypes.data_as(C.c_void_p), _p(boxes, C.c_int32),
+                                           _p(locs, C.c_int32), capacity, C.byref(cnt)))
+        return self._out(heads, boxes, locs, cnt.value)
+
+    def detect_batch_stored(self, store: "PyramidStore", slots, capacity=4096):
+        """pbd_detect_batch_stored: detect_batch() on the frames of `slots` (same-sized; any order, repeats allowed)"""
+        sl = np.ascontiguousarray([int(getattr(x, "slot", x)) for x in slots], np.int32)
+        return self._batch_out(len(sl), capacity, lambda hd, bx, lc, cnt: self.L.pbd_detect_batch_stored(
+            self.h, store.s, _vp(sl), len(sl), hd, bx, lc, capacity, cnt))
 
     # ---- a batch of same-sized frames through this handle ------------------------------------
     def detect_batch(self, frames, capacity=4096):
@@ -1606,6 +1641,26 @@ class QpCache:
         self._mine_chk(rc, rec)
         return rec, wr, act.value
 
+    def mine_stored(self, store: "PyramidStore", slot: int, id: int):
+        """pbd_qp_mine_stored: mine() on the frame that was put into `slot` of `store` (or a StoredFrame): the same records, examples,
+        ub and action as mine(image, id) on this cache's handle, in bits — only the features come from the slot"""
+        store, slot = _stored(store, slot)
+        rec, wr, act = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+        rc = self.L.pbd_qp_mine_stored(self.q, store.s, int(slot), int(id), C.byref(rec), C.byref(wr), C.byref(act))
+        self._mine_chk(rc, [rec.value])
+        return rec.value, wr.value, act.value
+
+    def mine_batch_stored(self, store: "PyramidStore", slots, ids):
+        """pbd_qp_mine_batch_stored: mine_batch() on the frames of `slots` (same-sized), one id per slot"""
+        sl = np.ascontiguousarray([int(getattr(x, "slot", x)) for x in slots], np.int32)
+        ids = np.ascontiguousarray(ids, np.int32).ravel()
+        if not len(sl) or len(ids) != len(sl):
+            raise ValueError("mine_batch_stored: one id per slot")
+        rec, wr, act = np.full(len(sl), -1, np.int32), np.full(len(sl), -1, np.int32), C.c_int(-1)
+        rc = self.L.pbd_qp_mine_batch_stored(self.q, store.s, _vp(sl), len(sl), _vp(ids), _vp(rec), _vp(wr), C.byref(act))
+        self._mine_chk(rc, rec)
+        return rec, wr, act.value
+
     # ---- latent positives (include/pbd_c.h "latent positives") ----
     def write_latent(self, im, truth, overlap, id: int, mix=None, component=-1):
         """pbd_qp_write_latent_u8: train.m:187's detect(im, model, 0, bbox, overlap, id, 1) on the cache's handle — the frame is
@@ -1668,6 +1723,121 @@ class QpCache:
 
 
 # ---- evaluation: eval_pck.m, eval_apk.m, VOCap.m (include/pbd_c.h "evaluation ledger") ------------------------------------------------
+# ---- pyramid store (include/pbd_c.h "pyramid store") -------------------------------------------------------------------------------------
+def pyrstore_layout(w, hgt, sbin, interval, kind=PBD_PYRAMID_OPENCV, pad=0):
+    """pbd_pyrstore_layout (host only, no GPU): (nlevels, level_off [nlevels] int64 element offsets, total elements) of one frame's
+    feature pyramid; raises PbdError(PBD_ERR_ARG) for a frame too small for `interval` levels"""
+    n, total = C.c_int(0), C.c_longlong(0)
+    off = np.zeros(PBD_PYRSTORE_MAX_LEVELS, np.int64)
+    rc = lib().pbd_pyrstore_layout(int(w), int(hgt), int(sbin), int(interval), int(kind), int(pad), C.byref(n), _vp(off), C.byref(total))
+    if rc != PBD_OK:
+        raise PbdError(rc, "pbd_pyrstore_layout: no pyramid for this frame and these settings")
+    return n.value, off[:n.value].copy(), total.value
+
+
+class StoredFrame:
+    """One slot of a PyramidStore, as an item detectStored / mineNegatives / train() take where they take an image"""
+
+    def __init__(self, store: "PyramidStore", slot: int):
+        self.store, self.slot = store, int(slot)
+
+    def __repr__(self):
+        return f"StoredFrame(slot={self.slot})"
+
+
+def _stored(store, slot):
+    """(store, slot) from (store, slot) or (StoredFrame, None) / (store, StoredFrame)"""
+    if isinstance(store, StoredFrame):
+        return store.store, store.slot
+    if isinstance(slot, StoredFrame):
+        return slot.store, slot.slot
+    return store, slot
+
+
+class PyramidStore:
+    """pbd_pyrstore: `slots` device-resident feature pyramids, each of one frame as `handle` (the producer) computes it.  Any handle
+    on the same device whose sbin, interval, pyramid kind, boundary pad and dtype equal the producer's at this moment detects and mines
+    from a slot (Handle.detect_stored, QpCache.mine_stored) with the image entries' results, in bits.  Sized for frames of up to
+    max_w x max_h.  Close the store before its producer (Handle.close() does it for the stores it still has)."""
+
+    def __init__(self, handle: Handle, slots: int, max_w: int, max_h: int):
+        self.handle, self.L = handle, handle.L
+        self.s = C.c_void_p()
+        handle._chk(self.L.pbd_pyrstore_create(handle.h, int(slots), int(max_w), int(max_h), C.byref(self.s)))
+        if not hasattr(handle, "_caches"):
+            handle._caches = []
+        handle._caches.append(weakref.ref(self))   # Handle.close() closes what it still has: the store goes before its producer
+
+    def _chk(self, rc):
+        self.handle._chk(rc)
+
+    def dims(self):
+        """dict(slots, sbin, interval, kind, pad, scalar_bytes, slot_bytes): the store's size and signature"""
+        v = [C.c_int() for _ in range(6)]
+        b = C.c_size_t()
+        self._chk(self.L.pbd_pyrstore_dims(self.s, *[C.byref(x) for x in v], C.byref(b)))
+        return dict(zip(("slots", "sbin", "interval", "kind", "pad", "scalar_bytes"), (x.value for x in v)), slot_bytes=b.value)
+
+    def slot(self, slot: int):
+        """(w, hgt, cn, nlevels) of the frame in `slot`; w == 0: empty"""
+        v = [C.c_int() for _ in range(4)]
+        self._chk(self.L.pbd_pyrstore_slot(self.s, int(slot), *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def put(self, slot: int, im) -> StoredFrame:
+        """pbd_pyrstore_put_u8: the producer's pyramid of the 8-bit frame `im` into `slot` (synchronous)"""
+        im, w, hgt, cn, stride = _frame(im)
+        self._chk(self.L.pbd_pyrstore_put_u8(self.s, int(slot), _vp(im), w, hgt, cn, stride))
+        return StoredFrame(self, slot)
+
+    def put_dev(self, slot: int, dptr: int, w, hgt, cn, stride=None) -> StoredFrame:
+        """pbd_pyrstore_put_dev_u8: the same from a frame in device memory (an integer device pointer)"""
+        self._chk(self.L.pbd_pyrstore_put_dev_u8(self.s, int(slot), C.c_void_p(dptr), w, hgt, cn, w * cn if stride is None else int(stride)))
+        return StoredFrame(self, slot)
+
+    def put_batch(self, slots, ims):
+        """pbd_pyrstore_put_batch_u8: same-sized frames through the producer as one batch, frame f into slots[f]"""
+        frames, stride = _frames(ims)
+        sl = np.ascontiguousarray([int(x) for x in slots], np.int32)
+        if not frames or len(sl) != len(frames) or any(f.shape != frames[0].shape for f in frames):
+            raise ValueError("put_batch: one slot per frame, frames of one shape")
+        hgt, w = frames[0].shape[:2]
+        cn = 1 if frames[0].ndim == 2 else frames[0].shape[2]
+        ptrs = (C.c_void_p * len(frames))(*[f.ctypes.data for f in frames])
+        self._chk(self.L.pbd_pyrstore_put_batch_u8(self.s, _vp(sl), ptrs, len(frames), w, hgt, cn, stride))
+        return [StoredFrame(self, x) for x in sl]
+
+    def level(self, slot: int, level: int) -> np.ndarray:
+        """pbd_pyrstore_get_level: level `level` of the slot's pyramid, [ch][cw][32] in the producer's dtype"""
+        w, hgt, _, n = self.slot(slot)
+        if w == 0 or not 0 <= level < n:   # (the library words the refusal)
+            self._chk(self.L.pbd_pyrstore_get_level(self.s, int(slot), int(level), _vp(np.zeros(1)), 0))
+        d = self.dims()
+        _, off, total = pyrstore_layout(w, hgt, d["sbin"], d["interval"], d["kind"], d["pad"])
+        nel = int((off[level + 1] if level + 1 < n else total) - off[level])
+        dt = np.float64 if d["scalar_bytes"] == 8 else np.float32
+        g = self.handle.geometry(w, hgt)   # (the level's shape: the producer's geometry while its settings are still the store's)
+        shape = (int(g["cell_h"][level]), int(g["cell_w"][level]), 32) if level < g["nlevels"] else (0, 0, 32)
+        out = np.zeros(shape if shape[0] * shape[1] * 32 == nel else (nel // 32, 32), dt)
+        self._chk(self.L.pbd_pyrstore_get_level(self.s, int(slot), int(level), _vp(out), C.c_size_t(out.nbytes)))
+        return out
+
+    def frames(self):
+        """a StoredFrame per occupied slot, in slot order"""
+        return [StoredFrame(self, i) for i in range(self.dims()["slots"]) if self.slot(i)[0] > 0]
+
+    def close(self):
+        if getattr(self, "s", None):   # (a live store implies a live producer: Handle.close() closes its stores before itself)
+            self.L.pbd_pyrstore_destroy(self.s)
+        self.s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _persons(points, scale, P=None):
     """(points [ngt, P, 2] float64, scale [ngt] float64) of one frame's annotated persons"""
     scale = np.ascontiguousarray(scale, np.float64).reshape(-1)

@@ -355,6 +355,16 @@ static int run_hog(pbd_handle* h) {
   return PBD_OK;
 }
 
+// A pyramid-store frame's front end (include/pbd_c.h "pyramid store"): k_pyrstore_load writes the batch's features from the slots, and
+// the split banks' parts with them.  The level images are not produced: whatever d_pyr holds belongs to an earlier frame.
+static int run_stored_load(pbd_handle* h, const PyrCopyTable& t) {
+  launch_pyrstore_load(t, h->batch, h->split_parts ? h->d_feat_split : nullptr, h->split_parts, h->stream);
+  LAUNCHCHK(h, "pyramid store load");
+  h->have_pyr = false;
+  mark_features(h, true);
+  return PBD_OK;
+}
+
 // The split-product banks read the features as bfloat16 / binary16 parts: written by k_hog's epilogue; features handed in by the
 // caller (pbd_set_level_features) are split here, in front of the bank (a pass over 25 MB per frame)
 static void ensure_feat_split(pbd_handle* h) {
@@ -653,10 +663,15 @@ static int enqueue_stages(pbd_handle* h, const FrameJob& job, const FrameRoute& 
   int rc;
   const bool prof = h->profiling;
   if (prof) hipEventRecord(h->ev[0], h->stream);
+  if (job.stored) {   // a pyramid-store frame: its features (and the split banks' parts) come from the slots in one launch
+    if ((rc = run_stored_load(h, *job.stored))) return rc;
+    if (prof) { hipEventRecord(h->ev[1], h->stream); hipEventRecord(h->ev[2], h->stream); }   // (the load's time reads as the pyramid's)
+  } else {
   if ((rc = run_image_pyramid(h, d_src, stride))) return rc;
   if (prof) hipEventRecord(h->ev[1], h->stream);
   if ((rc = run_hog(h))) return rc;
   if (prof) hipEventRecord(h->ev[2], h->stream);
+  }
   if ((rc = run_pdf(h))) return rc;
   if (r.latent && (rc = run_latent_mask(h, h->batch))) return rc;   // (a latent frame's stage times: the mask in pdf's, the best root in min()'s)
   if (prof) hipEventRecord(h->ev[3], h->stream);
@@ -684,7 +699,8 @@ static int enqueue_routed(pbd_handle* h, const FrameJob& job, const FrameRoute& 
   // depth-carrying frames run eagerly: the depth pointers are per frame; a captured graph stays for plain frames
   // latent frames too: the mask stage and the best-root reduction are theirs alone, the captured graph stays the plain frames'
   // gt-box frames too: the selection behind the back-tracking is theirs alone
-  if (job.kind != FRAME_PLAIN) return enqueue_stages(h, job, r, d_src, stride);
+  // pyramid-store frames too: their front end is the load; frames_on_plan and the captured graph stay the plain frames'
+  if (job.kind != FRAME_PLAIN || job.stored) return enqueue_stages(h, job, r, d_src, stride);
   if (!graphable || h->frames_on_plan == 0) {
     h->frames_on_plan++;
     return enqueue_stages(h, job, r, d_src, stride);
@@ -724,6 +740,16 @@ static int enqueue_stage_argmin(pbd_handle* h) {
   int rc = begin_pending(h, job, &r);
   if (!rc && (rc = run_argmin_enqueue(h, job, r))) h->pf.active = false;
   return rc;
+}
+
+// pyramid(): the frame(s) of `s` planned and uploaded, then the level images and the HOG features enqueued (pbd_pyramid_image; a
+// pyramid-store put, whose frames may be a batch or on the device)
+int pbd_i_front_end(pbd_handle* h, const FrameSource& s) {
+  int rc = enter_frame(h, s, false);
+  if (rc) return rc;
+  const uint8_t* d_src = s.on_device ? (const uint8_t*)s.one : h->d_img;
+  if ((rc = run_image_pyramid(h, d_src, s.on_device ? s.stride : s.w * s.cn * h->fesz))) return rc;
+  return run_hog(h);
 }
 
 void read_stage_times(pbd_handle* h) {
@@ -899,10 +925,8 @@ int pbd_begin_frame(pbd_handle* h, int w, int hgt, int cn) {
 // pyramid() on a host image of any depth the reference accepts (src/HOGFeatures.cpp:136-146): level images + HOG features
 int pbd_pyramid_image(pbd_handle* h, const void* im, int depth, int w, int hgt, int cn, int stride) {
   if (!h || !im) return PBD_ERR_ARG;
-  int rc = enter_frame(h, host_frame(im, w, hgt, cn, stride, depth), false);
+  int rc = pbd_i_front_end(h, host_frame(im, w, hgt, cn, stride, depth));
   if (rc) return rc;
-  if ((rc = run_image_pyramid(h, h->d_img, w * cn * h->fesz))) return rc;
-  if ((rc = run_hog(h))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return PBD_OK;
 }

@@ -34,6 +34,13 @@ int enter_frame(pbd_handle* h, const FrameSource& s, bool detect) {
     return fail(h, PBD_ERR_UNSUPPORTED, std::string(s.mine ? "mining" : "latent positives") +
                                         ": this frame runs the compact memory plan (dp_mode 2, or automatic for large frames), whose min() reuses "
                                         "the memory of the feature planes the examples are read from");
+  PyrCopyTable stored_jobs;
+  if (s.stored) {
+    if (h->compact)
+      return fail(h, PBD_ERR_UNSUPPORTED, "pyramid store: this frame runs the compact memory plan (dp_mode 2, or automatic for large frames and batches), "
+                                          "which stored frames do not support");
+    if ((rc = pbd_i_stored_jobs(h, *s.stored, s.nframes, &stored_jobs))) return rc;
+  }
   if (!s.on_device)   // on the handle's stream, in front of the kernels
     for (int f = 0; f < s.nframes; ++f) {
       const void* im = s.each ? s.each[f] : s.one;
@@ -45,6 +52,7 @@ int enter_frame(pbd_handle* h, const FrameSource& s, bool detect) {
   const int stride = s.on_device ? s.stride : (int)row;
   // what the frame is, once: the truth tables / gt boxes / depth images go in front of the kernels like the image
   FrameJob job;
+  if (s.stored) job.stored = &stored_jobs;
   if (s.lat) {
     job.kind = s.lat_write ? FRAME_LATENT_WRITE : FRAME_LATENT;
     if ((rc = pbd_i_latent_begin(h, *s.lat, s.nframes))) return rc;

@@ -434,7 +434,26 @@ struct FrameSource {
   bool mine;                      // hard-negative mining (pbd_qp_mine_*): the final records stay on the device
   bool lat_write;                 // latent positives (pbd_qp_write_latent_*; with lat): the frame's pose stays on the device
   bool eval;                      // an APK evaluation frame (pbd_eval_apk_frame_*): the final records stay on the device like a mining frame's
+  const struct StoredSource* stored;   // pyramid store (pbd_detect_stored, pbd_qp_mine_stored): no image — frame f's features are slot slots[f]'s; else null
 };
+// ---- pyramid store (pbd_pyrstore.cpp, k_pyrstore.hip; include/pbd_c.h "pyramid store") ------------------------------------------
+// One streaming copy of `bytes` bytes (a multiple of 128: whole cells of 32 elements), 16-byte aligned at both ends; dst_cell: the
+// destination's first cell in the consumer's feature buffer (the split parts' index; the put does not read it)
+struct PyrCopyJob { const char* src; char* dst; unsigned long long bytes, dst_cell; };
+struct PyrCopyTable { PyrCopyJob j[64]; };   // by value in the kernel's arguments: one job per frame of a batch (PBD_MAX_BATCH)
+static_assert(sizeof(PyrCopyJob) == 32 && sizeof(PyrCopyTable) == 2048, "PyrCopyTable layout");
+struct StoredSource { const struct pbd_pyrstore* store; const int32_t* slots; };
+// enter_frame, on the planned frame: the job table of a stored source (slot f -> the block of frame f's virtual levels); refuses a plan
+// whose per-frame block is not the slot's
+int pbd_i_stored_jobs(pbd_handle* h, const StoredSource& s, int nframes, PyrCopyTable* t);
+// every refusal of a consumer entry that needs no plan, then the source of the frame(s): *st and *out stay the caller's (enter_frame reads them)
+int pbd_i_stored_source(pbd_handle* h, struct pbd_pyrstore* s, const int32_t* slots, int nframes, StoredSource* st, FrameSource* out);
+// the producer's front end of a put (pbd_api.cpp): enter_frame(.., false), the image pyramid and HOG (+ ring), enqueued on its stream
+int pbd_i_front_end(pbd_handle* h, const FrameSource& s);
+// njobs jobs, one launch.  load: into feat (the jobs' dst) and, split_parts = 3 / 2, the bank's bfloat16 / binary16 parts of the same
+// elements into split ([cell][part][32]) in the same pass; put: the copy alone
+void launch_pyrstore_load(const PyrCopyTable& t, int njobs, uint16_t* split, int split_parts, hipStream_t s);
+void launch_pyrstore_put(const PyrCopyTable& t, int njobs, hipStream_t s);
 // the three shapes of a source, by name (z: see above)
 inline FrameSource host_frame(const void* im, int w, int hgt, int cn, int stride, int depth, const DepthSource* z = nullptr) {
   return {false, im, nullptr, 1, w, hgt, cn, stride, depth, z};

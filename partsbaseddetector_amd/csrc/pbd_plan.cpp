@@ -103,6 +103,28 @@ void pad_geometry(int pad, int nlevels, Level* lv) {
     if (lv[l].cw > 0 && lv[l].ch > 0) { lv[l].cw += 2 * pad; lv[l].ch += 2 * pad; }
 }
 
+// include/pbd_c.h "pyramid store": the feature layout of ONE frame — the geometry above, the padding, and the levels' element offsets
+// back to back, which are plan_layout's cell_off * PBD_FLEN for a single frame.  Host only.
+extern "C" __attribute__((visibility("default")))
+int pbd_pyrstore_layout(int w, int hgt, int sbin, int interval, int kind, int pad, int* nlevels, long long* level_off, long long* total) {
+  if (!nlevels || !total) return PBD_ERR_ARG;
+  if (sbin <= 0 || interval < 1 || interval > 16 || pad < 0 || pad > 8 || (kind != PBD_PYRAMID_OPENCV && kind != PBD_PYRAMID_MATLAB)) return PBD_ERR_ARG;
+  if (w < 3 || hgt < 3) return PBD_ERR_ARG;
+  std::vector<Level> lv((size_t)PBD_MAX_LEVELS, Level{});
+  int n = 0;
+  if (kind == PBD_PYRAMID_MATLAB ? compute_geometry_matlab(w, hgt, sbin, interval, &n, lv.data()) : compute_geometry(w, hgt, sbin, interval, &n, lv.data()))
+    return PBD_ERR_ARG;
+  pad_geometry(pad, n, lv.data());
+  long long off = 0;
+  for (int l = 0; l < n; ++l) {
+    if (level_off) level_off[l] = off;
+    off += (long long)lv[l].cw * lv[l].ch * PBD_FLEN;
+  }
+  *nlevels = n;
+  *total = off;
+  return PBD_OK;
+}
+
 int depth_esz(int depth) { return depth == PBD_DEPTH_8U ? 1 : depth == PBD_DEPTH_16U ? 2 : depth == PBD_DEPTH_32F ? 4 : depth == PBD_DEPTH_64F ? 8 : 0; }
 
 // ---------------------------------------------------------------------------

@@ -162,6 +162,21 @@ int pbd_qp_mine_batch_u8(pbd_qp* q, const uint8_t* const* ims, int nframes, int 
   if (!q || !ims) return PBD_ERR_ARG;
   return mine_run(q, host_batch(ims, nframes, w, hgt, cn, stride), ids, records, written, action);
 }
+// the same from pyramid-store slots (include/pbd_c.h "pyramid store"): the store's refusals first, then mining's own
+int pbd_qp_mine_stored(pbd_qp* q, pbd_pyrstore* s, int slot, int id, int* records, int* written, int* action) {
+  if (!q || !s) return PBD_ERR_ARG;
+  const int32_t slots[1] = {slot}, ids[1] = {id};
+  StoredSource st; FrameSource src;
+  int rc = pbd_i_stored_source(q->h, s, slots, 1, &st, &src);
+  return rc ? rc : mine_run(q, src, ids, records, written, action);
+}
+int pbd_qp_mine_batch_stored(pbd_qp* q, pbd_pyrstore* s, const int32_t* slots, int nframes, const int32_t* ids, int32_t* records,
+                             int32_t* written, int* action) {
+  if (!q || !s || !slots) return PBD_ERR_ARG;
+  StoredSource st; FrameSource src;
+  int rc = pbd_i_stored_source(q->h, s, slots, nframes, &st, &src);
+  return rc ? rc : mine_run(q, src, ids, records, written, action);
+}
 
 }  // extern "C"
 #pragma GCC visibility pop

@@ -31,6 +31,8 @@ enum FrameKind {
 struct FrameJob {
   FrameKind kind = FRAME_PLAIN;
   DepthFrames z{};                      // FRAME_DEPTH: the depth images, on the device
+  const struct PyrCopyTable* stored = nullptr;   // non-null (FRAME_PLAIN / FRAME_MINE): the frame's features come from pyramid-store slots by
+                                        // this job table (k_pyrstore_load) instead of from the image pyramid and HOG; the frame runs eagerly
 };
 
 // record buffers and count blocks of the handle, by name (pbd_post.cpp: pbd_i_route_buf, pbd_i_route_count)

@@ -485,6 +485,20 @@ class PartsBasedDetector:
         out.extend(Candidate._unpack(*res, self._ps()))
         return out
 
+    def pyramidStore(self, slots: int, max_w: int, max_h: int) -> "capi.PyramidStore":
+        """A pyramid store with this detector as its producer (include/pbd_c.h "pyramid store"): `slots` device-resident feature
+        pyramids of frames up to max_w x max_h, computed once by put() and then detected (detectStored) or mined (mineNegatives, train)
+        by any detector on the same device with this one's sbin, interval, pyramid kind, boundary pad and dtype — whatever its model.
+        Close it before this detector's handle (the handle's close() does)."""
+        return capi.PyramidStore(self.handle, slots, max_w, max_h)
+
+    def detectStored(self, frame: "capi.StoredFrame", candidates: Optional[List[Candidate]] = None) -> List[Candidate]:
+        """detect() on a frame of a pyramid store: what detect(image) returns for the image that was put, in bits, without the image
+        pyramid and HOG.  No depth stages; with setPartScores on, the Candidates carry their parts' scores."""
+        out = candidates if candidates is not None else []
+        out.extend(Candidate._unpack(*self.handle.detect_stored(frame.store, frame.slot, self._cap), self._ps()))
+        return out
+
     def detect_latent(self, im: np.ndarray, truth, overlap: float, mix=None, component: int = -1) -> List[Candidate]:
         """detect(im, model, thresh, bbox, overlap) of matlab/detection/detect.m: the single highest-scoring pose whose every part
         overlaps its box in `truth` ([nparts, 4] rows of x, y, width, height as detect() returns them) by more than `overlap`
@@ -570,7 +584,8 @@ class PartsBasedDetector:
             raise ValueError("mineNegatives: the cache is bound to another detector")
         out = []
         for i, im in enumerate(images):
-            rec, wr, act = cache.mine(im, first_id + i)
+            # (an item that is a capi.StoredFrame is mined from its pyramid-store slot: the same records, examples and action in bits)
+            rec, wr, act = cache.mine_stored(im.store, im.slot, first_id + i) if isinstance(im, capi.StoredFrame) else cache.mine(im, first_id + i)
             out.append((rec, wr, act))
             if act == capi.PBD_MINE_OPT:
                 cache.opt(tol, max_iter, seed)

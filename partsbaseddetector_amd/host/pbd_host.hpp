@@ -791,6 +791,60 @@ class PartsBasedDetector {
     append_candidates(candidates, heads, boxes, locs, n, mp);
     attach_part_scores(candidates, n, mp);
   }
+  // ---- pyramid store (include/pbd_c.h "pyramid store") ----
+  // `slots` device-resident feature pyramids of frames up to max_w x max_h, each computed once by this detector (the producer) in put().
+  // Any detector on the same device whose sbin, interval, pyramid kind, boundary pad and T equal the producer's detects
+  // (detectStored) and mines (ExampleCache::mineStored) from a slot with the image entries' results, in bits, whatever its model.
+  // Holds the producer's device alive; destroyed before it.
+  class PyramidStore {
+    std::shared_ptr<Device> dev_;
+    pbd_pyrstore* s_ = nullptr;
+    friend class PartsBasedDetector;
+   public:
+    PyramidStore(std::shared_ptr<Device> dev, int slots, int max_w, int max_h) : dev_(std::move(dev)) {
+      dev_->check(pbd_pyrstore_create(dev_->h, slots, max_w, max_h, &s_));
+    }
+    ~PyramidStore() { pbd_pyrstore_destroy(s_); }
+    PyramidStore(const PyramidStore&) = delete;
+    PyramidStore& operator=(const PyramidStore&) = delete;
+    pbd_pyrstore* get() const { return s_; }
+    struct Dims { int slots, sbin, interval, kind, pad, scalar_bytes; size_t slot_bytes; };
+    Dims dims() const { Dims d{}; dev_->check(pbd_pyrstore_dims(s_, &d.slots, &d.sbin, &d.interval, &d.kind, &d.pad, &d.scalar_bytes, &d.slot_bytes)); return d; }
+    struct Slot { int w, hgt, cn, nlevels; };   // w == 0: empty
+    Slot slot(int i) const { Slot v{}; dev_->check(pbd_pyrstore_slot(s_, i, &v.w, &v.hgt, &v.cn, &v.nlevels)); return v; }
+    void put(int slot, const Mat& im) {
+      if (im.depth() != PBD_8U) throw Exception(PBD_ERR_UNSUPPORTED, "pyramid store: 8-bit frames only");
+      dev_->check(pbd_pyrstore_put_u8(s_, slot, im.ptr<uint8_t>(), im.cols, im.rows, im.channels(), (int)im.step()));
+    }
+    void putDev(int slot, const void* d_im, int w, int hgt, int cn, int stride) { dev_->check(pbd_pyrstore_put_dev_u8(s_, slot, d_im, w, hgt, cn, stride)); }
+    void putBatch(const std::vector<int32_t>& slots, const std::vector<Mat>& ims) {   // same-sized 8-bit frames with one row step
+      if (ims.empty() || slots.size() != ims.size()) throw Exception(PBD_ERR_ARG, "PyramidStore::putBatch: one slot per frame");
+      std::vector<const uint8_t*> p;
+      for (const Mat& m : ims) {
+        if (m.depth() != PBD_8U || m.cols != ims[0].cols || m.rows != ims[0].rows || m.channels() != ims[0].channels() || m.step() != ims[0].step())
+          throw Exception(PBD_ERR_ARG, "PyramidStore::putBatch: 8-bit frames of one size and row step");
+        p.push_back(m.ptr<uint8_t>());
+      }
+      dev_->check(pbd_pyrstore_put_batch_u8(s_, slots.data(), p.data(), (int)ims.size(), ims[0].cols, ims[0].rows, ims[0].channels(), (int)ims[0].step()));
+    }
+    // level `level` of the slot's pyramid: cw * ch * 32 elements of the producer's T; `elements` = the room in out
+    void level(int slot, int level, T* out, size_t elements) { dev_->check(pbd_pyrstore_get_level(s_, slot, level, out, elements * sizeof(T))); }
+  };
+  std::unique_ptr<PyramidStore> pyramidStore(int slots, int max_w, int max_h) {
+    if (!dev_) throw Exception(PBD_ERR_STATE, "pyramidStore() before distributeModel()");
+    return std::unique_ptr<PyramidStore>(new PyramidStore(dev_, slots, max_w, max_h));
+  }
+  // detect() on the frame that was put into `slot`: the image entry's candidates in bits, without the image pyramid and HOG
+  void detectStored(const PyramidStore& store, int slot, vectorCandidate& candidates) {
+    if (!dev_) throw Exception(PBD_ERR_STATE, "detectStored() before distributeModel()");
+    const int cap = dev_->max_candidates, mp = pbd_max_parts(dev_->h);
+    std::vector<pbd_candidate_head> heads(cap);
+    std::vector<int32_t> boxes((size_t)cap * mp * 4), locs((size_t)cap * mp * 3);
+    int n = 0;
+    dev_->check(pbd_detect_stored(dev_->h, store.get(), slot, heads.data(), boxes.data(), locs.data(), cap, &n));
+    append_candidates(candidates, heads, boxes, locs, n, mp);
+    attach_part_scores(candidates, n, mp);
+  }
   // detect(im, model, thresh, bbox, overlap) of matlab/detection/detect.m:18-23: the single highest-scoring pose whose every part
   // overlaps its box in `truth` (one cv::Rect per part, in the convention detect() returns: x .. x + width) by more than `overlap`
   // (in [0, 1)), appended to `candidates`; nothing is appended when no pose qualifies.  mix: empty = every mixture free, else per part
@@ -953,6 +1007,13 @@ class PartsBasedDetector {
       if (im.depth() != PBD_8U) throw Exception(PBD_ERR_UNSUPPORTED, "mining: 8-bit frames only");
       Mined m{-1, -1, -1};
       dev_->check(pbd_qp_mine_u8(q_, im.ptr<uint8_t>(), im.cols, im.rows, im.channels(), (int)im.step(), id, &m.records, &m.written, &m.action));
+      return m;
+    }
+    // the same on the frame that was put into `slot` of a pyramid store whose signature is this cache's detector's: mine(image, id)'s
+    // records, examples, ub and action in bits (include/pbd_c.h "pyramid store")
+    Mined mineStored(const PyramidStore& store, int slot, int id) {
+      Mined m{-1, -1, -1};
+      dev_->check(pbd_qp_mine_stored(q_, store.get(), slot, id, &m.records, &m.written, &m.action));
       return m;
     }
     // ---- latent positives (include/pbd_c.h "latent positives") ----

@@ -38,7 +38,8 @@ def train(model, positives, negatives, warp, iter=1, C=0.002, wpos=2, overlap=0.
                boxes below prod(maxsize * sbin) are skipped inside writeWarped).  warp == 0: items (image, truth[, mix]) with
                truth [nparts, 4] rows (x, y, width, height) as detect() returns boxes, and the optional mixture label per part
                (trainmodel.m:48-50), as PartsBasedDetector.latentPositives takes them (its skip, croppos and ids are in place).
-    negatives  8-bit images without the object.
+    negatives  8-bit images without the object; an item may be a capi.StoredFrame (a slot of a pyramid store whose signature is the
+               detector's at interval 2): it is mined from the slot, with the image's results in bits.
     C, wpos    cpos = C * wpos, cneg = C (train.m:69-70).  overlap: the minimum overlap of a latent positive's parts.
     capacity   examples the cache holds; default 10 * (wpos + 1) * len(positives) (train.m:30-31,46).
     tol, max_iter, seed   of every qp_opt (capi.QpCache.opt) and of the solver steps inside mining.
@@ -156,8 +157,38 @@ def _truth(box):
     return np.stack([c[:, 0] - 1, c[:, 1] - 1, c[:, 2] - c[:, 0], c[:, 3] - c[:, 1]], axis=1).astype(np.int32)
 
 
+_TRAIN_ARGS = ("iter", "C", "wpos", "overlap", "capacity", "tol", "max_iter", "seed", "dtype", "detector", "cache")   # train()'s own; the rest are the detector's
+
+
+def _share_negatives(model, negatives, train_options, make):
+    """train_model(share_pyramids=True): a producer detector on `model` at interval 2 (train.m:96: what every round mines at), with the
+    trainings' dtype, pyramid kind, boundary pad and device, and a pyramid store that holds every negative's pyramid, put once
+    -> (producer, store, [capi.StoredFrame per negative])"""
+    opts = {k: v for k, v in train_options.items() if k not in _TRAIN_ARGS}
+    det = make(model, train_options.get("dtype", np.float32), opts)
+    store = None
+    try:
+        det.setInterval(2)
+        shapes = [np.asarray(im).shape for im in negatives]
+        store = det.pyramidStore(max(len(negatives), 1), max([s[1] for s in shapes] + [1]), max([s[0] for s in shapes] + [1]))
+        return det, store, [store.put(i, im) for i, im in enumerate(negatives)]
+    except BaseException:
+        if store is not None:
+            store.close()
+        det.handle.close()
+        raise
+
+
+def _root_sizes(positives, parents):
+    """(w, h) of the root boxes point_to_box gives the positives: init_model's first two arguments"""
+    P = len(parents)
+    points = np.stack([np.asarray(it[1], np.float64).reshape(P, 2) for it in positives])
+    boxes = point_to_box(points, [int(v) for v in parents])
+    return boxes[:, 0, 2] - boxes[:, 0, 0] + 1, boxes[:, 0, 3] - boxes[:, 0, 1] + 1
+
+
 def train_model(positives, negatives, K, parents, sbin, tsize=None, R=100, cluster_seed=0, cluster_max_iter=1000, device=0,
-                _train=None, _cluster=None, **train_options):
+                share_pyramids=False, _train=None, _cluster=None, _producer=None, **train_options):
     """matlab/learning/trainmodel.m -> (model, reports).  positives = [(image, points [P, 2])] with the keypoints in the .m files'
     1-based pixel coordinates; negatives 8-bit images; K the mixtures per part (an int or one per part); parents 0-based with -1 at
     part 0 and parent < child; sbin the HOG cell size.  tsize = (rows, cols) overrides init_model's 5th-percentile template (needed
@@ -170,8 +201,23 @@ def train_model(positives, negatives, K, parents, sbin, tsize=None, R=100, clust
       train(joint, positives with mix = idx[:, i], negatives, warp=0), then train(that, positives without mix, negatives, warp=0)  :47-63
     reports: dict(parts={(p, k): report}, final1=report, final=report, idx=idx).  Nothing is cached on disk and no .mat file is read
     or written: the caller saves the Model with the writers it has.  The latent rounds take integer truth boxes (the ABI's): the
-    fractional corners are rounded half away from zero."""
+    fractional corners are rounded half away from zero.
+    share_pyramids=True: the sum(K) + 2 trainings mine the same negatives at interval 2, and a mining frame's pyramid does not depend
+    on the model: one producer detector (init_model's model, interval 2, the trainings' dtype, pyramid_kind, boundary_pad and device)
+    puts every negative ONCE into a pyramid store sized for the largest, and every train() receives capi.StoredFrame items instead
+    of the images — mineNegatives mines them from their slots with the images' results in bits.  The store and the
+    producer are closed on the way out, whatever happens.  The default stays False."""
     run = train if _train is None else _train
+    if share_pyramids:
+        negatives = list(negatives)
+        producer, store, stored = _share_negatives(init_model(*_root_sizes(positives, parents), sbin, tsize), negatives, train_options,
+                                                   _new_detector if _producer is None else _producer)
+        try:
+            return train_model(positives, stored, K, parents, sbin, tsize, R, cluster_seed, cluster_max_iter, device, False, _train, _cluster,
+                               None, **train_options)
+        finally:
+            store.close()
+            producer.handle.close()
     cluster = (lambda d, pa, k: capi.cluster_parts(d, pa, k, R, cluster_seed, cluster_max_iter, device)) if _cluster is None else _cluster
     parents = [int(v) for v in parents]
     P = len(parents)
