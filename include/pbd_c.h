@@ -185,7 +185,9 @@ int pbd_abi_version(void);
  * pbd_kmeans_host, pbd_cluster_parts_host and pbd_cluster_parts; and the seams of one training round: pbd_set_interval,
  * pbd_get_interval, pbd_qp_clear and pbd_qp_positive_threshold; and the pyramid store pbd_pyrstore: pbd_pyrstore_create, _destroy,
  * _dims, _slot, _layout, _put_u8, _put_dev_u8, _put_batch_u8 and _get_level, with pbd_detect_stored, pbd_detect_batch_stored,
- * pbd_qp_mine_stored and pbd_qp_mine_batch_stored (PBD_PYRSTORE_MAX_LEVELS).                                                         */
+ * pbd_qp_mine_stored and pbd_qp_mine_batch_stored (PBD_PYRSTORE_MAX_LEVELS); and the virtual positives: pbd_rotate_geometry,
+ * pbd_map_rotate_points, pbd_flip_points, pbd_augment_host_u8, pbd_augment_u8, pbd_augment_dev_u8, pbd_augment_last_error and
+ * pbd_qp_write_warped_dev_u8 (with the struct pbd_augment_op, PBD_ROT_* and PBD_AUGMENT_MAX_*).                                     */
 
 /* ---- output record: include/Candidate.hpp:56-111 --------------------------
  * One candidate = head + max_parts boxes (x, y, width, height as cv::Rect)
@@ -1558,6 +1560,87 @@ int  pbd_detect_stored(pbd_handle* h, pbd_pyrstore* s, int slot, pbd_candidate_h
 int  pbd_detect_batch_stored(pbd_handle* h, pbd_pyrstore* s, const int32_t* slots, int nframes, pbd_candidate_head* heads, int32_t* boxes, int32_t* locs, int capacity, int* counts);
 int  pbd_qp_mine_stored(pbd_qp* qp, pbd_pyrstore* s, int slot, int id, int* records, int* written, int* action);
 int  pbd_qp_mine_batch_stored(pbd_qp* qp, pbd_pyrstore* s, const int32_t* slots, int nframes, const int32_t* ids, int32_t* records, int32_t* written, int* action);
+
+/* ---- virtual positives: mirrored and rotated frames with their keypoints (ABI 5, additive) ---------------------------------------------
+ * The recipe trainmodel.m was written for takes every annotated image as it is, mirrored with the left and right parts swapped, and all
+ * of these rotated by a few angles, the keypoints carried along (matlab/globals.m:18-23 creates the imrotate/ and imflip/ caches,
+ * train.m:130,165: "we create virtual examples by flipping each image left to right").  matlab/learning/map_rotate_points.m maps the
+ * keypoints; the image side is a gather over pixels.  Both are defined here, once, in double: every operation below is one IEEE
+ * operation in the order written, never fused.
+ *
+ * Frame of reference: pixel index k (0-based) of an axis sits at coordinate k.  map_rotate_points.m is coordinate-agnostic (a point at
+ *   hiA maps to hiB); this is the frame in which image and points agree exactly, and every function of this section works in it.
+ *   DEVIATION from a caller who passes the .m files' 1-based keypoints straight in: subtract 1 before and add 1 after (the binding's
+ *   augment_positives does).
+ * pbd_rotate_geometry (map_rotate_points.m:21-35 as the file computes it): phi = (deg * pi) / 180, c = cos phi, s = sin phi by the
+ *   host's libm, once, on the host: the device never evaluates a trigonometric function, it multiplies by the numbers this call returns.
+ *   hiA = ((hgt - 1) / 2, (w - 1) / 2) as (row, col), loA = -hiA.  The forward map of a (row, col) pair (u, v) is
+ *   (u*c - v*s, u*s + v*c).  Of the file's two corners (loA_r, hiA_c) and (hiA_r, hiA_c): hiB_k = ceil(max |.| / 2) * 2 per axis k;
+ *   the canvas has 2 hiB_r + 1 rows and 2 hiB_c + 1 columns.  -> *out_w, *out_h, m[6] = {c, s, hiA_r, hiA_c, hiB_r, hiB_c}; each
+ *   may be NULL.  The file's quirks are kept: hiB is the extent rounded UP to an even number, so at 0 degrees an even side gets a
+ *   larger canvas with the image a fraction of a pixel off the grid (640 x 480 -> 641 x 481; a side of 30 -> 33), and an odd side n
+ *   keeps its size only where (n - 1) / 2 is even (29 -> 29, 31 -> 33); at +-90, 180 and 360 degrees cos and sin are not exactly
+ *   0 or +-1, and an extent one ulp above an even number adds two to hiB, four to the canvas side (37 x 29 at 90 degrees: 33 x 37,
+ *   not 29 x 37).
+ * pbd_map_rotate_points (map_rotate_points.m:37-46): pts[n][2] rows of (x, y) -> out[n][2] (out may be pts).  PBD_ROT_ORI2NEW:
+ *   u = y - hiA_r, v = x - hiA_c, out = (x: (u*s + v*c) + hiB_c, y: (u*c - v*s) + hiB_r).  PBD_ROT_NEW2ORI: u = y - hiB_r,
+ *   v = x - hiB_c, out = (x: (v*c - u*s) + hiA_c, y: (u*c + v*s) + hiA_r).  DEVIATION: tforminv inverts the matrix numerically; here
+ *   the inverse is the transpose.
+ * pbd_flip_points: out[p] = (w - 1 - x[mirror[p]], y[mirror[p]]): the mirrored frame's part p is the original's part mirror[p] (left
+ *   and right swapped).  mirror must be a permutation of 0..n-1; NULL is the identity.  out may be pts.
+ * The image: struct pbd_augment_op {flip, method, deg, rotate}; the mirror comes first, then the rotation.
+ *   Flip: F[y][x][ch] = in[y][w - 1 - x][ch] (flip == 0: F = in).  rotate == 0: the output is F, hgt rows of w pixels.
+ *   Rotation by deg: for output pixel (r, q) of the canvas, u = r - hiB_r, v = q - hiB_c, source row sr = (u*c + v*s) + hiA_r, source
+ *   column sc = (v*c - u*s) + hiA_c — NEW2ORI of the pixel.
+ *   PBD_ROT_NEAREST (imrotate's default): F at (floor(sr + 0.5), floor(sc + 0.5)); pixels outside the source are 0 (black).
+ *   PBD_ROT_BILINEAR: y0 = floor(sr), fy = sr - y0, x0 = floor(sc), fx = sc - x0; taps a00 = F[y0][x0], a01 = F[y0][x0 + 1],
+ *   a10 = F[y0 + 1][x0], a11 = F[y0 + 1][x0 + 1], a tap outside the source counting as 0.0;
+ *   value = (1 - fy) * ((1 - fx) * a00 + fx * a01) + fy * ((1 - fx) * a10 + fx * a11); byte = min(255, floor(value + 0.5)).
+ *   DEVIATION: imrotate's bilinear kernel and its fill are MATLAB binaries; this definition is the library's.
+ * pbd_augment_host_u8: the definition, on the host, one thread.  im: hgt rows of w pixels of cn channels, `stride` bytes apart;
+ *   outs[i]: op i's canvas, out_strides[i] bytes between rows.  Bytes of an output row beyond the canvas row are left untouched.
+ * pbd_augment_u8: the same on HIP device `device`, host in, host out.  pbd_augment_dev_u8: device in, device out: d_im is read in
+ *   place, d_outs is a HOST array of device pointers, written in place.  Both need no handle, are synchronous, and restore the calling
+ *   thread's device.  One launch of k_augment.hip serves all ops of the frame: a workgroup is one 64 x 4 output tile of one op, the
+ *   op's descriptor is wave-uniform, a lane does one pixel with all its channels; the result equals pbd_augment_host_u8 in every byte
+ *   (the same text, augment_core.hpp).  PBD_ERR_HIP: no such device, or a HIP failure (after the refusals below).
+ *   Streams: pbd_augment_dev_u8 reads d_im and writes d_outs on a non-blocking stream of its own, which waits for no other stream.
+ *   Whatever produced d_im, or still uses the d_outs buffers, on the caller's streams must be COMPLETE before the call (synchronise
+ *   the producing stream or the device); on return the canvases are complete and any stream may read them.
+ * Refusals, each with a message (pbd_augment_last_error: the calling thread's last one) and nothing written: PBD_ERR_ARG — NULL
+ *   pointers, cn other than 1 or 3, w or hgt < 1, a stride below w * cn, a non-finite deg, an unknown method of a rotating op, a
+ *   dir other than the two, a mirror that is no permutation, nops outside 1..PBD_AUGMENT_MAX_OPS, an out_stride below the canvas
+ *   row; PBD_ERR_UNSUPPORTED — a canvas side beyond PBD_AUGMENT_MAX_SIDE.
+ * pbd_qp_write_warped_dev_u8: pbd_qp_write_warped_u8 ("warped positives") with the frame read from device memory on the cache's
+ *   device: the upload becomes a device-to-device copy of the same rows; every refusal and every written bit is the same.  With it
+ *   and pbd_qp_write_latent_dev_u8 a virtual positive never has to leave the device.  Both read d_im on the handle's stream: the
+ *   caller's work that produces the frame must be complete before the call, as above.
+ * Not built: rotated negatives, other fills than black, 16-bit frames.                                                              */
+#define PBD_ROT_ORI2NEW 0
+#define PBD_ROT_NEW2ORI 1
+#define PBD_ROT_NEAREST 0
+#define PBD_ROT_BILINEAR 1
+#define PBD_AUGMENT_MAX_OPS 64
+#define PBD_AUGMENT_MAX_SIDE 16384
+typedef struct pbd_augment_op {
+  int32_t flip;      /* != 0: mirror left to right first                        */
+  int32_t method;    /* PBD_ROT_NEAREST / PBD_ROT_BILINEAR (read when rotating)  */
+  double deg;        /* the angle in degrees, map_rotate_points.m's `ang`        */
+  int32_t rotate;    /* 0: no rotation (the canvas is the frame's), != 0: by deg */
+  int32_t reserved;  /* 0                                                        */
+} pbd_augment_op;
+int pbd_rotate_geometry(int w, int hgt, double deg, int* out_w, int* out_h, double* m);                                  /* host only */
+int pbd_map_rotate_points(const double* pts, int n, int w, int hgt, double deg, int dir, double* out);                   /* host only */
+int pbd_flip_points(const double* pts, int n, int w, const int32_t* mirror, double* out);                                /* host only */
+int pbd_augment_host_u8(const uint8_t* im, int w, int hgt, int cn, int stride, const pbd_augment_op* ops, int nops, uint8_t* const* outs,
+                        const int* out_strides);                                                                         /* host only */
+int pbd_augment_u8(int device, const uint8_t* im, int w, int hgt, int cn, int stride, const pbd_augment_op* ops, int nops,
+                   uint8_t* const* outs, const int* out_strides);
+int pbd_augment_dev_u8(int device, const void* d_im, int w, int hgt, int cn, int stride, const pbd_augment_op* ops, int nops,
+                       void* const* d_outs, const int* out_strides);
+const char* pbd_augment_last_error(void);
+int pbd_qp_write_warped_dev_u8(pbd_qp* qp, const void* d_im, int w, int hgt, int cn, int stride, const double* boxes, const int32_t* ids,
+                               int n, int filter, int bias, double min_area, int32_t* status, int* written);
 
 /* ---- instrumentation --------------------------------------------------------
  * GPU time (ms, hipEvent) of the stages of the last synchronous detect:

@@ -83,7 +83,13 @@ EXPORTS = [
     "pbd_pyrstore_create", "pbd_pyrstore_destroy", "pbd_pyrstore_dims", "pbd_pyrstore_slot", "pbd_pyrstore_layout",
     "pbd_pyrstore_put_u8", "pbd_pyrstore_put_dev_u8", "pbd_pyrstore_put_batch_u8", "pbd_pyrstore_get_level",
     "pbd_detect_stored", "pbd_detect_batch_stored", "pbd_qp_mine_stored", "pbd_qp_mine_batch_stored",
+    "pbd_rotate_geometry", "pbd_map_rotate_points", "pbd_flip_points", "pbd_augment_host_u8", "pbd_augment_u8", "pbd_augment_dev_u8",
+    "pbd_augment_last_error", "pbd_qp_write_warped_dev_u8",
 ]
+# include/pbd_c.h "virtual positives"
+PBD_ROT_ORI2NEW, PBD_ROT_NEW2ORI = 0, 1
+PBD_ROT_NEAREST, PBD_ROT_BILINEAR = 0, 1
+PBD_AUGMENT_MAX_OPS, PBD_AUGMENT_MAX_SIDE = 64, 16384
 PBD_PYRSTORE_MAX_LEVELS = 128   # room pbd_pyrstore_layout's level_off needs
 PBD_CLUSTER_MAX_K, PBD_CLUSTER_MAX_ITER, PBD_CLUSTER_MAX_TRIALS, PBD_CLUSTER_MAX_LABELS = 32, 10000, 2 ** 20, 2 ** 31 - 1   # include/pbd_c.h "part mixtures"
 PBD_EVAL_SCALE_LAST, PBD_EVAL_SCALE_OWN = 0, 1   # pbd_eval_pck's scale rule: eval_pck.m:13 literally (the last instance's scale) / each instance's own
@@ -97,6 +103,11 @@ class pbd_options(C.Structure):
     _fields_ = [("device", C.c_int32), ("conv_mode", C.c_int32), ("max_candidates", C.c_int32),
                 ("dt_correct_ptr", C.c_int32), ("level_begin", C.c_int32), ("level_end", C.c_int32),
                 ("scalar_type", C.c_int32), ("graph", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class pbd_augment_op(C.Structure):
+    """one virtual copy of a frame (include/pbd_c.h "virtual positives"): the mirror first, then the rotation by `deg`"""
+    _fields_ = [("flip", C.c_int32), ("method", C.c_int32), ("deg", C.c_double), ("rotate", C.c_int32), ("reserved", C.c_int32)]
 
 
 class pbd_candidate_head(C.Structure):
@@ -262,6 +273,15 @@ def lib() -> C.CDLL:
         L.pbd_detect_batch_stored.argtypes = [V, V, V, I, V, V, V, I, V]
         L.pbd_qp_mine_stored.argtypes = [V, V, I, I, V, V, V]
         L.pbd_qp_mine_batch_stored.argtypes = [V, V, V, I, V, V, V, V]
+        L.pbd_rotate_geometry.argtypes = [I, I, D, V, V, V]
+        L.pbd_map_rotate_points.argtypes = [V, I, I, I, D, I, V]
+        L.pbd_flip_points.argtypes = [V, I, I, V, V]
+        L.pbd_augment_host_u8.argtypes = [V, I, I, I, I, V, I, V, V]
+        for name in ("pbd_augment_u8", "pbd_augment_dev_u8"):
+            getattr(L, name).argtypes = [I, V, I, I, I, I, V, I, V, V]
+        L.pbd_augment_last_error.restype = C.c_char_p
+        L.pbd_augment_last_error.argtypes = []
+        L.pbd_qp_write_warped_dev_u8.argtypes = L.pbd_qp_write_warped_u8.argtypes
         if L.pbd_abi_version() != PBD_ABI_VERSION:
             raise ImportError(f"{LIB_PATH}: ABI version {L.pbd_abi_version()}, this binding is for {PBD_ABI_VERSION}")
         _lib = L
@@ -1453,6 +1473,24 @@ class QpCache:
                                                        int(bias), float(min_area), _vp(status), C.byref(written)))
         return written.value, status
 
+    def write_warped_dev(self, dptr, w=None, hgt=None, cn=None, boxes=None, filter: int = 0, bias: int = 0, min_area: float = 0.0, ids=None,
+                         stride=None):
+        """pbd_qp_write_warped_dev_u8: write_warped on a frame in device memory — a DeviceFrame, or an integer device pointer with
+        w, hgt, cn (stride: bytes between rows, default w * cn) —, copied device to device; the same columns, status and refusals"""
+        if isinstance(dptr, DeviceFrame):
+            fr = dptr
+            fr.sync()
+            dptr, w, hgt, cn, stride = fr.dptr, fr.w, fr.hgt, fr.cn, fr.stride
+        boxes = np.ascontiguousarray(boxes, np.float64).reshape(-1, 4)
+        ids = None if ids is None else np.ascontiguousarray(ids, np.int32).reshape(len(boxes))
+        status = np.full(len(boxes), -1, np.int32)
+        written = C.c_int(-1)
+        self.handle._chk(self.L.pbd_qp_write_warped_dev_u8(self.q, C.c_void_p(dptr), int(w), int(hgt), int(cn),
+                                                           int(w) * int(cn) if stride is None else int(stride), _vp(boxes), _vp(ids),
+                                                           len(boxes), int(filter), int(bias), float(min_area), _vp(status),
+                                                           C.byref(written)))
+        return written.value, status
+
     @staticmethod
     def _inds(inds):
         return None if inds is None else np.ascontiguousarray(inds, np.int32).ravel()
@@ -2104,3 +2142,168 @@ def cluster_parts_host(deffeat, parents, K, R=100, seed=0, max_iter=1000):
 def cluster_parts(deffeat, parents, K, R=100, seed=0, max_iter=1000, device=0):
     """pbd_cluster_parts: cluster_parts_host on HIP device `device`, one wavefront per (part, trial); bit-identical outputs"""
     return _cluster_parts(lib().pbd_cluster_parts, "pbd_cluster_parts", (int(device),), deffeat, parents, K, R, seed, max_iter)
+
+
+# ---- virtual positives: map_rotate_points.m and the image operation (include/pbd_c.h "virtual positives") ------------------------------
+_ROT_METHODS = {"nearest": PBD_ROT_NEAREST, "bilinear": PBD_ROT_BILINEAR}
+
+
+def _aug_chk(rc, name):
+    if rc != PBD_OK:
+        raise PbdError(rc, f"{name}: {lib().pbd_augment_last_error().decode()}")
+
+
+def rotate_geometry(w, hgt, deg):
+    """pbd_rotate_geometry (host code, no GPU): map_rotate_points.m:21-35 for a w x hgt frame turned by deg degrees ->
+    dict(w, h: the canvas, m [6] float64 = (cos, sin, hiA_r, hiA_c, hiB_r, hiB_c))"""
+    ow, oh, m = C.c_int(), C.c_int(), np.zeros(6, np.float64)
+    _aug_chk(lib().pbd_rotate_geometry(int(w), int(hgt), float(deg), C.byref(ow), C.byref(oh), _vp(m)), "pbd_rotate_geometry")
+    return dict(w=ow.value, h=oh.value, m=m)
+
+
+def map_rotate_points(pts, w, hgt, deg, direction=PBD_ROT_ORI2NEW):
+    """pbd_map_rotate_points (host code, no GPU): rows (x, y) in the 0-based frame (pixel index k at coordinate k) of a w x hgt frame
+    mapped into its canvas at deg degrees (PBD_ROT_ORI2NEW) or back (PBD_ROT_NEW2ORI) -> [n, 2] float64"""
+    p = np.ascontiguousarray(pts, np.float64).reshape(-1, 2)
+    out = np.zeros_like(p)
+    _aug_chk(lib().pbd_map_rotate_points(_vp(p), len(p), int(w), int(hgt), float(deg), int(direction), _vp(out)), "pbd_map_rotate_points")
+    return out
+
+
+def flip_points(pts, w, mirror=None):
+    """pbd_flip_points (host code, no GPU): out[p] = (w - 1 - x[mirror[p]], y[mirror[p]]) in the 0-based frame; mirror: a permutation
+    of the parts (the left / right swap), None: the identity"""
+    p = np.ascontiguousarray(pts, np.float64).reshape(-1, 2)
+    mr = None if mirror is None else np.ascontiguousarray(mirror, np.int32).ravel()
+    if mr is not None and len(mr) != len(p):
+        raise ValueError("flip_points: one mirror entry per point")
+    out = np.zeros_like(p)
+    _aug_chk(lib().pbd_flip_points(_vp(p), len(p), int(w), _vp(mr), _vp(out)), "pbd_flip_points")
+    return out
+
+
+def augment_ops(specs):
+    """a pbd_augment_op array from specs (flip, deg[, method]): flip a bool, deg the angle in degrees or None for no rotation, method
+    "bilinear" (default) / "nearest" or a PBD_ROT_* value.  A pbd_augment_op array passes through."""
+    if isinstance(specs, C.Array) and getattr(specs, "_type_", None) is pbd_augment_op:
+        return specs
+    specs = list(specs)
+    ops = (pbd_augment_op * max(len(specs), 1))()
+    for i, sp in enumerate(specs):
+        if isinstance(sp, pbd_augment_op):
+            ops[i] = sp
+            continue
+        flip, deg = sp[0], sp[1]
+        method = sp[2] if len(sp) > 2 else "bilinear"
+        ops[i] = pbd_augment_op(int(bool(flip)), int(_ROT_METHODS.get(method, method)), 0.0 if deg is None else float(deg), int(deg is not None), 0)
+    ops.count = len(specs)
+    return ops
+
+
+def augment_canvas(w, hgt, op):
+    """(rows, cols) of op's output for a w x hgt frame"""
+    if not op.rotate:
+        return int(hgt), int(w)
+    g = rotate_geometry(w, hgt, op.deg)
+    return g["h"], g["w"]
+
+
+def _aug_views(bufs, canvases, cn):
+    return [b[:r, :c * cn].reshape((r, c) if cn == 1 else (r, c, cn)) for b, (r, c) in zip(bufs, canvases)]
+
+
+def _augment_np(fn, name, lead, im, specs, outs):
+    im, w, hgt, cn, stride = _frame(im)
+    ops = augment_ops(specs)
+    n = getattr(ops, "count", len(ops))
+    canv = [augment_canvas(w, hgt, ops[i]) for i in range(n)] if 0 < n <= PBD_AUGMENT_MAX_OPS else []
+    if outs is None:
+        outs = [np.zeros((r, c * cn), np.uint8) for r, c in canv]
+    if any(o.dtype != np.uint8 or o.ndim != 2 or not o.flags["C_CONTIGUOUS"] for o in outs):
+        raise ValueError(f"{name}: outs are C-contiguous 2-D uint8 arrays [rows, stride]")
+    ptrs = (C.c_void_p * max(len(outs), 1))(*[o.ctypes.data for o in outs])
+    strides = np.ascontiguousarray([o.shape[1] for o in outs] or [0], np.int32)
+    if any(o.shape[0] < r for o, (r, _) in zip(outs, canv)) or (canv and len(outs) != n):
+        raise ValueError(f"{name}: one output per op with at least the canvas' rows")
+    _aug_chk(fn(*lead, _vp(im), w, hgt, cn, stride, ops, n, ptrs, _vp(strides)), name)
+    return _aug_views(outs, canv, cn)
+
+
+def augment_host(im, specs, outs=None):
+    """pbd_augment_host_u8 (host code, no GPU): the virtual copies of the 8-bit frame `im` (HxW or HxWxcn, a strided view is read in
+    place), one per spec of augment_ops -> a list of uint8 arrays [rows, cols(, cn)].  outs: the caller's 2-D uint8 buffers
+    [rows, stride bytes], written in place (bytes beyond a canvas row stay); the result is then views into them."""
+    return _augment_np(lib().pbd_augment_host_u8, "pbd_augment_host_u8", (), im, specs, outs)
+
+
+def augment(im, specs, device=0, outs=None):
+    """pbd_augment_u8: augment_host on HIP device `device` (host in, host out, one launch for all specs); identical bytes"""
+    return _augment_np(lib().pbd_augment_u8, "pbd_augment_u8", (int(device),), im, specs, outs)
+
+
+class DeviceFrame:
+    """An 8-bit frame in device memory: hgt rows of w pixels of cn channels, `stride` bytes apart, from device pointer `dptr` on; `owner`
+    (a torch tensor, usually) is whatever keeps the allocation alive.  QpCache.write_warped_dev / write_latent_dev,
+    PartsBasedDetector.writeWarped / latentPositives and train() take one where they take an array."""
+
+    def __init__(self, dptr, w, hgt, cn, stride=None, owner=None):
+        self.dptr, self.w, self.hgt, self.cn = int(dptr), int(w), int(hgt), int(cn)
+        self.stride = self.w * self.cn if stride is None else int(stride)
+        self.owner = owner
+
+    @classmethod
+    def from_tensor(cls, t):
+        """a contiguous torch uint8 tensor [hgt, w] or [hgt, w, cn] on a GPU"""
+        if str(t.dtype) != "torch.uint8" or not t.is_cuda or not t.is_contiguous() or t.dim() not in (2, 3):
+            raise ValueError("DeviceFrame.from_tensor: a contiguous uint8 tensor [hgt, w(, cn)] on a GPU")
+        return cls(t.data_ptr(), t.shape[1], t.shape[0], 1 if t.dim() == 2 else t.shape[2], None, t)
+
+    @property
+    def shape(self):
+        return (self.hgt, self.w) if self.cn == 1 else (self.hgt, self.w, self.cn)
+
+    def crop(self, x, y, w, h):
+        """the view of columns x .. x + w - 1 and rows y .. y + h - 1: pointer arithmetic, nothing is copied"""
+        if x < 0 or y < 0 or w < 1 or h < 1 or x + w > self.w or y + h > self.hgt:
+            raise ValueError("DeviceFrame.crop: outside the frame")
+        return DeviceFrame(self.dptr + int(y) * self.stride + int(x) * self.cn, w, h, self.cn, self.stride, self.owner)
+
+    def sync(self):
+        """the library reads the frame on streams of its own: whatever the owner's device still has queued is waited for"""
+        if hasattr(self.owner, "is_cuda"):
+            import torch
+            torch.cuda.synchronize(self.owner.device)
+
+    def numpy(self):
+        """a host copy [hgt, w(, cn)] (the owner must be a torch tensor)"""
+        flat = self.owner.reshape(-1).cpu().numpy()
+        off = self.dptr - self.owner.data_ptr()
+        v = np.lib.stride_tricks.as_strided(flat[off:], (self.hgt, self.w, self.cn), (self.stride, self.cn, 1))
+        return np.ascontiguousarray(v if self.cn > 1 else v[:, :, 0])
+
+    def __repr__(self):
+        return f"DeviceFrame({self.w}x{self.hgt}x{self.cn}, stride={self.stride})"
+
+
+def augment_dev(frame, specs, device=None, outs=None):
+    """pbd_augment_dev_u8: the virtual copies of a frame that is in device memory — a DeviceFrame or a torch uint8 tensor
+    [hgt, w(, cn)] —, read in place and written into torch uint8 tensors on the same device -> a list of DeviceFrame that own them.
+    outs: the caller's 2-D uint8 tensors [rows, stride bytes] instead (bytes beyond a canvas row stay)."""
+    import torch
+    fr = frame if isinstance(frame, DeviceFrame) else DeviceFrame.from_tensor(frame)
+    ops = augment_ops(specs)
+    n = getattr(ops, "count", len(ops))
+    canv = [augment_canvas(fr.w, fr.hgt, ops[i]) for i in range(n)] if 0 < n <= PBD_AUGMENT_MAX_OPS else []
+    dev = fr.owner.device if hasattr(fr.owner, "device") else torch.device("cuda", 0 if device is None else int(device))
+    if outs is None:
+        outs = [torch.zeros((r, c * fr.cn), dtype=torch.uint8, device=dev) for r, c in canv]
+    if any(o.dtype != torch.uint8 or o.dim() != 2 or not o.is_contiguous() or not o.is_cuda for o in outs):
+        raise ValueError("augment_dev: outs are contiguous 2-D uint8 tensors [rows, stride] on the GPU")
+    if any(o.shape[0] < r for o, (r, _) in zip(outs, canv)) or (canv and len(outs) != n):
+        raise ValueError("augment_dev: one output per op with at least the canvas' rows")
+    ptrs = (C.c_void_p * max(len(outs), 1))(*[o.data_ptr() for o in outs])
+    strides = np.ascontiguousarray([o.shape[1] for o in outs] or [0], np.int32)
+    torch.cuda.synchronize(dev)   # (the fills above and whatever produced the source ran on torch's streams)
+    _aug_chk(lib().pbd_augment_dev_u8(dev.index or 0, C.c_void_p(fr.dptr), fr.w, fr.hgt, fr.cn, fr.stride, ops, n, ptrs, _vp(strides)),
+             "pbd_augment_dev_u8")
+    return [DeviceFrame(o.data_ptr(), c, r, fr.cn, o.shape[1], o) for o, (r, c) in zip(outs, canv)]

@@ -825,6 +825,14 @@ struct KmeansArgs {
   int* idx; double* centres; double* sumdist; int* best; int* pcap;   // the winners: [P][n], [P][PBD_CLUSTER_MAX_K][2], [P], [P], [P]
 };
 void launch_kmeans(const KmeansArgs& a, hipStream_t s);   // X, the trials, the winners
+// virtual positives (k_augment.hip, pbd_augment.cpp; include/pbd_c.h "virtual positives"): every op of one frame in one launch
+struct AugDesc;
+struct AugArgs {
+  const uint8_t* im; int w, h, cn; unsigned long long stride;   // the source, read in place
+  const AugDesc* desc; int nops;                                // [nops] in device memory
+  int max_rows, max_cols;                                       // the largest canvas: the grid
+};
+void launch_augment(const AugArgs& a, hipStream_t s);
 // a warped positive's column (train.m:152-161 qp_poswrite): window r of `feat` (T [n][wlen]) becomes example n0 + r with ids (1, ids[r], 0, 0, 0)
 struct QpPosArgs {
   QpDev q; int n0, n;

@@ -1,6 +1,6 @@
 // pbd_qp_warp.cpp — the warped positives' host side (include/pbd_c.h "warped positives"; planner: pbd_warp.cpp, kernels: k_warp.hip,
-// k_hog.hip, k_qp.hip): the frame's upload, the job and tap tables of the boxes, the three launches, and the entry points
-// pbd_warp_windows_u8[_f64] and pbd_qp_write_warped_u8.
+// k_hog.hip, k_qp.hip): the frame's upload (or the copy of its rows from device memory), the job and tap tables of the boxes, the three
+// launches, and the entry points pbd_warp_windows_u8[_f64], pbd_qp_write_warped_u8 and pbd_qp_write_warped_dev_u8.
 #include <algorithm>
 #include <cmath>
 #include "pbd_qp.hpp"
@@ -33,6 +33,7 @@ int hog_tile_side(int sbin, int ts) {
 struct WarpCall {
   int kh = 0, kw = 0, ow = 0, oh = 0;
   std::vector<WarpGeom> g;          // [n] every box of the call
+  hipMemcpyKind kind = hipMemcpyHostToDevice;   // where the frame's rows are copied from (pbd_qp_write_warped_dev_u8: the device)
   Tmp img, win, feat;
 };
 
@@ -70,7 +71,7 @@ int warp_run(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int strid
   const size_t rowb = (size_t)w * cn, nwin = (size_t)ow * oh * 3, wlen = (size_t)kh * kw * PBD_FLEN;
   int rc;
   if ((rc = c->img.get(h, rowb * hgt)) || (rc = c->win.get(h, sizeof(double) * nwin * m)) || (rc = c->feat.get(h, (size_t)h->ts * wlen * m))) return rc;
-  if ((rc = copy_rows(h, c->img.p, im, (size_t)stride, rowb, (size_t)hgt, hipMemcpyHostToDevice))) return rc;
+  if ((rc = copy_rows(h, c->img.p, im, (size_t)stride, rowb, (size_t)hgt, c->kind))) return rc;
   WarpArgs a{};
   a.im = (const uint8_t*)c->img.p; a.w = w; a.h = hgt; a.cn = cn; a.stride = rowb;
   a.win = (double*)c->win.p; a.ow = ow; a.oh = oh;
@@ -156,32 +157,14 @@ int warp_windows_(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int 
   if (features) HIPCHK(h, hipMemcpyAsync(features, c.feat.p, (size_t)ts * c.kh * c.kw * PBD_FLEN * (size_t)n, hipMemcpyDeviceToHost, h->stream));
   return finish(h, "warped positives: ");
 }
-}  // namespace
 
-#pragma GCC visibility push(default)
-extern "C" {
-
-int pbd_warp_windows_u8(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride, const double* boxes, int n, int filter,
-                        double* windows, float* features) {
-  return warp_windows_(h, im, w, hgt, cn, stride, boxes, n, filter, windows, features, 4);
-}
-int pbd_warp_windows_u8_f64(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride, const double* boxes, int n, int filter,
-                            double* windows, double* features) {
-  return warp_windows_(h, im, w, hgt, cn, stride, boxes, n, filter, windows, features, 8);
-}
-
-int pbd_debug_warp_ms(const pbd_handle* h, float ms[3]) {
-  if (!h || !ms) return PBD_ERR_ARG;
-  for (int i = 0; i < 3; ++i) ms[i] = h->warp_ms[i];
-  return PBD_OK;
-}
-
-int pbd_qp_write_warped_u8(pbd_qp* q, const uint8_t* im, int w, int hgt, int cn, int stride, const double* boxes, const int32_t* ids, int n,
-                           int filter, int bias, double min_area, int32_t* status, int* written) {
+int write_warped_(pbd_qp* q, const uint8_t* im, int w, int hgt, int cn, int stride, const double* boxes, const int32_t* ids, int n,
+                  int filter, int bias, double min_area, int32_t* status, int* written, hipMemcpyKind kind) {
   if (!q) return PBD_ERR_ARG;
   pbd_handle* h = q->h;
   if (!written) return fail(h, PBD_ERR_ARG, "example cache: written is NULL");
   WarpCall c;
+  c.kind = kind;
   int rc = warp_check(h, im, w, hgt, cn, stride, boxes, n, filter, &c);
   if (rc) return rc;
   if (bias < 0 || bias >= (int)h->biasw.size()) return fail(h, PBD_ERR_ARG, "warped positives: bias outside [0, nbias)");
@@ -228,6 +211,36 @@ int pbd_qp_write_warped_u8(pbd_qp* q, const uint8_t* im, int w, int hgt, int cn,
   q->n += m;
   *written = m;
   return PBD_OK;
+}
+}  // namespace
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int pbd_warp_windows_u8(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride, const double* boxes, int n, int filter,
+                        double* windows, float* features) {
+  return warp_windows_(h, im, w, hgt, cn, stride, boxes, n, filter, windows, features, 4);
+}
+int pbd_warp_windows_u8_f64(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride, const double* boxes, int n, int filter,
+                            double* windows, double* features) {
+  return warp_windows_(h, im, w, hgt, cn, stride, boxes, n, filter, windows, features, 8);
+}
+
+int pbd_debug_warp_ms(const pbd_handle* h, float ms[3]) {
+  if (!h || !ms) return PBD_ERR_ARG;
+  for (int i = 0; i < 3; ++i) ms[i] = h->warp_ms[i];
+  return PBD_OK;
+}
+
+int pbd_qp_write_warped_u8(pbd_qp* q, const uint8_t* im, int w, int hgt, int cn, int stride, const double* boxes, const int32_t* ids, int n,
+                           int filter, int bias, double min_area, int32_t* status, int* written) {
+  return write_warped_(q, im, w, hgt, cn, stride, boxes, ids, n, filter, bias, min_area, status, written, hipMemcpyHostToDevice);
+}
+// the frame already in device memory: the upload is a device-to-device copy of the same rows, everything else is the call above
+int pbd_qp_write_warped_dev_u8(pbd_qp* q, const void* d_im, int w, int hgt, int cn, int stride, const double* boxes, const int32_t* ids, int n,
+                               int filter, int bias, double min_area, int32_t* status, int* written) {
+  return write_warped_(q, (const uint8_t*)d_im, w, hgt, cn, stride, boxes, ids, n, filter, bias, min_area, status, written,
+                       hipMemcpyDeviceToDevice);
 }
 
 }  // extern "C"

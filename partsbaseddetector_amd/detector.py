@@ -536,12 +536,15 @@ class PartsBasedDetector:
         """poswarp of matlab/learning/train.m:131-161: the positive boxes ((x1, y1, x2, y2), 1-based inclusive, of the 8-bit frame `im`)
         warped to the root filter's size (warppos.m), HOGed and appended to `cache` as [bias | window] positives, all on the GPU.
         filter / bias default to component 0's root (warppos.m:6, model.bias.i).  Boxes smaller than prod(maxsize * sbin) — the
-        largest filter height and width of the model, train.m:135 — are skipped.  -> (written, status per box)."""
+        largest filter height and width of the model, train.m:135 — are skipped.  -> (written, status per box).  `im` may be a
+        capi.DeviceFrame: the frame is then read from device memory (capi.QpCache.write_warped_dev), with the same result in bits."""
         m = self.handle.model
         filter = int(m.filterid[0][0][0]) if filter is None else int(filter)
         bias = int(m.biasid[0][0][0]) if bias is None else int(bias)
         maxsize = m.filter_sizes().max(axis=0)
         min_area = float(maxsize[0] * m.sbin) * float(maxsize[1] * m.sbin)
+        if isinstance(im, capi.DeviceFrame):
+            return cache.write_warped_dev(im, boxes=boxes, filter=filter, bias=bias, min_area=min_area, ids=ids)
         return cache.write_warped(im, boxes, filter, bias, min_area, ids)
 
     def latentPositives(self, positives, cache: "capi.QpCache", overlap: float = 0.6, first_id: int = 1):
@@ -551,7 +554,9 @@ class PartsBasedDetector:
         view, nothing is copied), and the best pose overlapping them becomes one positive of `cache` without leaving the GPU
         (capi.QpCache.write_latent).  The image id is the item's index, first_id + i (MATLAB: 1-based), skipped items included.
         Returns (numpositives [ncomponents]: the found poses per component, blocks: per item its capi.LATENT_EXAMPLE_DTYPE record or
-        None where the item was skipped).  Fixing the positives as support vectors (train.m:90-91) stays the caller's cache.fix."""
+        None where the item was skipped).  Fixing the positives as support vectors (train.m:90-91) stays the caller's cache.fix.
+        An item's image may be a capi.DeviceFrame: the crop is then pointer arithmetic on its device pointer and the frame is read in
+        place (capi.QpCache.write_latent_dev), with the array item's result in bits."""
         if cache.handle is not self.handle:
             raise ValueError("latentPositives: the cache is bound to another detector")
         m = self.handle.model
@@ -559,14 +564,20 @@ class PartsBasedDetector:
         minsize = float(maxsize[0] * m.sbin) * float(maxsize[1] * m.sbin)
         counts, blocks = np.zeros(m.ncomponents, np.int64), []
         for i, item in enumerate(positives):
-            im, truth = np.asarray(item[0]), np.asarray(item[1], np.int32).reshape(-1, 4)
+            dev = isinstance(item[0], capi.DeviceFrame)
+            im, truth = item[0] if dev else np.asarray(item[0]), np.asarray(item[1], np.int32).reshape(-1, 4)
             mix = item[2] if len(item) > 2 else None
             area = (truth[:, 2].astype(np.float64) + 1) * (truth[:, 3].astype(np.float64) + 1)
             if np.any(area < minsize):
                 blocks.append(None)
                 continue
             (x, y, w, h), tr = capi.croppos(truth, len(truth), im.shape[1], im.shape[0])
-            blk = cache.write_latent(im[y:y + h, x:x + w], tr, overlap, first_id + i, mix)
+            if dev:
+                v = im.crop(x, y, w, h)
+                v.sync()
+                blk = cache.write_latent_dev(v.dptr, v.w, v.hgt, v.cn, tr, overlap, first_id + i, mix, stride=v.stride)
+            else:
+                blk = cache.write_latent(im[y:y + h, x:x + w], tr, overlap, first_id + i, mix)
             blocks.append(blk)
             if blk["found"]:
                 counts[int(blk["component"])] += 1

@@ -80,6 +80,10 @@ typedef std::vector<vectorf> vector2Df;
 // a ground-truth box of testmodel_gtbox.m: inclusive corners (x1, y1, x2, y2), as doubles (include/pbd_c.h "best pose per ground-truth box")
 struct GtBox { double x1, y1, x2, y2; };
 
+// an 8-bit frame in device memory (include/pbd_c.h "virtual positives"): rows of `cols` pixels of `channels` bytes, `step` bytes apart,
+// from the device pointer `data` on; the caller keeps the allocation alive
+struct DeviceFrame { const void* data; int rows, cols, channels; size_t step; };
+
 // ---- include/Candidate.hpp:56-111 ---------------------------------------------------------
 class Candidate {
   std::vector<Rect> parts_;
@@ -998,6 +1002,18 @@ class PartsBasedDetector {
                                          ids ? ids->data() : nullptr, (int)boxes.size(), filter, bias, min_area, status ? status->data() : nullptr, &written));
       return written;
     }
+    // the same from a frame in device memory (pbd_qp_write_warped_dev_u8): a virtual positive that pbd::augmentDevice left there.
+    // The frame is read on the detector's stream, which waits for no other: whatever produced it on the caller's streams must be
+    // complete before the call (pbd::augmentDevice is synchronous: its canvases are).
+    int writeWarped(const DeviceFrame& im, const std::vector<GtBox>& boxes, int filter, int bias, double min_area, std::vector<int32_t>* status = nullptr,
+                    const std::vector<int32_t>* ids = nullptr) {
+      if (ids && ids->size() != boxes.size()) throw Exception(PBD_ERR_ARG, "ExampleCache::writeWarped: one id per box");
+      if (status) status->assign(boxes.size(), -1);
+      int written = 0;
+      dev_->check(pbd_qp_write_warped_dev_u8(q_, im.data, im.cols, im.rows, im.channels, (int)im.step, boxes.empty() ? nullptr : &boxes[0].x1,
+                                             ids ? ids->data() : nullptr, (int)boxes.size(), filter, bias, min_area, status ? status->data() : nullptr, &written));
+      return written;
+    }
     // ---- hard-negative mining (include/pbd_c.h "hard-negative mining") ----
     // train.m:102's detect(im, model, -1, [], 0, id, -1) on the detector this cache is bound to: the frame is detected as detect() would
     // detect it (threshold — train.m uses -1, setThresh —, candidate filter, pad, pyramid kind), its records stay on the device and become
@@ -1406,6 +1422,53 @@ inline std::vector<int32_t> clusterParts(const std::vector<double>& def, int n, 
   if (rc != PBD_OK) throw Exception(rc, "clusterParts: refused (include/pbd_c.h \"part mixtures\"), or a HIP failure");
   if (capped) *capped = cap;
   return idx;
+}
+
+// ---- virtual positives (include/pbd_c.h "virtual positives"; need no detector) ----
+// matlab/learning/map_rotate_points.m: (x, y) rows in the 0-based frame of a w x hgt image into its canvas at `deg` degrees
+// (PBD_ROT_ORI2NEW) or back (PBD_ROT_NEW2ORI); pts = x0, y0, x1, y1, ...
+inline std::vector<double> mapRotatePoints(const std::vector<double>& pts, int w, int hgt, double deg, int dir = PBD_ROT_ORI2NEW) {
+  std::vector<double> out(pts.size());
+  const int rc = pts.size() % 2 ? PBD_ERR_ARG : pbd_map_rotate_points(pts.data(), (int)(pts.size() / 2), w, hgt, deg, dir, out.data());
+  if (rc != PBD_OK) throw Exception(rc, pts.size() % 2 ? "mapRotatePoints: (x, y) pairs" : pbd_augment_last_error());
+  return out;
+}
+// the keypoints of the mirrored frame: out[p] = (w - 1 - x[mirror[p]], y[mirror[p]]); an empty mirror is the identity
+inline std::vector<double> flipPoints(const std::vector<double>& pts, int w, const std::vector<int32_t>& mirror = std::vector<int32_t>()) {
+  std::vector<double> out(pts.size());
+  const bool bad = pts.size() % 2 || (!mirror.empty() && mirror.size() != pts.size() / 2);
+  const int rc = bad ? PBD_ERR_ARG : pbd_flip_points(pts.data(), (int)(pts.size() / 2), w, mirror.empty() ? nullptr : mirror.data(), out.data());
+  if (rc != PBD_OK) throw Exception(rc, bad ? "flipPoints: (x, y) pairs, one mirror entry per point" : pbd_augment_last_error());
+  return out;
+}
+// the virtual copies of an 8-bit frame, one per op (the mirror first, then the rotation), on HIP device `device` in one launch
+// (host = true: pbd_augment_host_u8, the same definition without a GPU, identical bytes)
+inline std::vector<Mat> augment(const Mat& im, const std::vector<pbd_augment_op>& ops, int device = 0, bool host = false) {
+  if (im.depth() != PBD_8U) throw Exception(PBD_ERR_UNSUPPORTED, "augment: 8-bit frames only");
+  std::vector<Mat> out(ops.size());
+  std::vector<uint8_t*> ptrs(ops.size());
+  std::vector<int> steps(ops.size());
+  for (size_t i = 0; i < ops.size(); ++i) {
+    int ow = im.cols, oh = im.rows;
+    if (ops[i].rotate && pbd_rotate_geometry(im.cols, im.rows, ops[i].deg, &ow, &oh, nullptr) != PBD_OK) throw Exception(PBD_ERR_ARG, pbd_augment_last_error());
+    out[i].create(oh, ow, PBD_8U, im.channels());
+    ptrs[i] = out[i].ptr<uint8_t>(); steps[i] = (int)out[i].step();
+  }
+  const int rc = host ? pbd_augment_host_u8(im.ptr<uint8_t>(), im.cols, im.rows, im.channels(), (int)im.step(), ops.data(), (int)ops.size(), ptrs.data(), steps.data())
+                      : pbd_augment_u8(device, im.ptr<uint8_t>(), im.cols, im.rows, im.channels(), (int)im.step(), ops.data(), (int)ops.size(), ptrs.data(), steps.data());
+  if (rc != PBD_OK) throw Exception(rc, pbd_augment_last_error());
+  return out;
+}
+// the same from device memory into device memory the caller allocated: outs[i] takes op i's canvas (pbd_rotate_geometry).  The library
+// works on a stream of its own, which waits for no other: whatever produced `im`, or still uses the outputs, on the caller's streams
+// must be complete before the call; on return the canvases are complete.
+inline void augmentDevice(const DeviceFrame& im, const std::vector<pbd_augment_op>& ops, const std::vector<DeviceFrame>& outs, int device = 0) {
+  if (outs.size() != ops.size()) throw Exception(PBD_ERR_ARG, "augmentDevice: one output per op");
+  std::vector<void*> ptrs(ops.size());
+  std::vector<int> steps(ops.size());
+  for (size_t i = 0; i < ops.size(); ++i) { ptrs[i] = const_cast<void*>(outs[i].data); steps[i] = (int)outs[i].step; }
+  const int rc = pbd_augment_dev_u8(device, im.data, im.cols, im.rows, im.channels, (int)im.step, ops.data(), (int)ops.size(), ptrs.data(), steps.data());
+  if (rc != PBD_OK) throw Exception(rc, pbd_augment_last_error());
 }
 
 }  // namespace pbd

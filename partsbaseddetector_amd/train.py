@@ -11,6 +11,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import capi
+from .augment import augment_positives
 from .detector import PartsBasedDetector
 from .model import Model, build_model, data_def, init_model, merge_models
 
@@ -34,7 +35,9 @@ def train(model, positives, negatives, warp, iter=1, C=0.002, wpos=2, overlap=0.
     """matlab/learning/train.m: `iter` rounds of a structured SVM with latent positives -> (model, report).
 
     model      the Model to start from (its interval, sbin and structure are kept; weights and threshold are trained).
-    positives  warp > 0: items (image, box) with box = (x1, y1, x2, y2), 1-based inclusive, of component 0's root (train.m's poswarp;
+    positives  an item's image is an 8-bit array or a capi.DeviceFrame (a frame in device memory, as augment_positives(...,
+               keep_on_device=True) returns them), read in place with the array's results in bits.
+               warp > 0: items (image, box) with box = (x1, y1, x2, y2), 1-based inclusive, of component 0's root (train.m's poswarp;
                boxes below prod(maxsize * sbin) are skipped inside writeWarped).  warp == 0: items (image, truth[, mix]) with
                truth [nparts, 4] rows (x, y, width, height) as detect() returns boxes, and the optional mixture label per part
                (trainmodel.m:48-50), as PartsBasedDetector.latentPositives takes them (its skip, croppos and ids are in place).
@@ -188,7 +191,8 @@ def _root_sizes(positives, parents):
 
 
 def train_model(positives, negatives, K, parents, sbin, tsize=None, R=100, cluster_seed=0, cluster_max_iter=1000, device=0,
-                share_pyramids=False, _train=None, _cluster=None, _producer=None, **train_options):
+                share_pyramids=False, _train=None, _cluster=None, _producer=None, mirror=None, degrees=(), augment_method="bilinear",
+                _augment=None, **train_options):
     """matlab/learning/trainmodel.m -> (model, reports).  positives = [(image, points [P, 2])] with the keypoints in the .m files'
     1-based pixel coordinates; negatives 8-bit images; K the mixtures per part (an int or one per part); parents 0-based with -1 at
     part 0 and parent < child; sbin the HOG cell size.  tsize = (rows, cols) overrides init_model's 5th-percentile template (needed
@@ -206,8 +210,16 @@ def train_model(positives, negatives, K, parents, sbin, tsize=None, R=100, clust
     on the model: one producer detector (init_model's model, interval 2, the trainings' dtype, pyramid_kind, boundary_pad and device)
     puts every negative ONCE into a pyramid store sized for the largest, and every train() receives capi.StoredFrame items instead
     of the images — mineNegatives mines them from their slots with the images' results in bits.  The store and the
-    producer are closed on the way out, whatever happens.  The default stays False."""
+    producer are closed on the way out, whatever happens.  The default stays False.
+    mirror= (a permutation of the parts: the left / right swap) and / or degrees= (angles): the positives are augmented first, on the
+    device — augment.augment_positives(positives, mirror, degrees, augment_method, device, keep_on_device=True): the originals, their
+    mirrors, and every one of those rotated by every angle, the virtual frames staying in device memory as capi.DeviceFrame items —,
+    and everything above runs over the longer list: the clusters are computed over the augmented keypoints, as the recipe does
+    (DESIGN.md 5.28).  With the defaults not one call changes."""
     run = train if _train is None else _train
+    if mirror is not None or len(degrees):
+        aug = augment_positives if _augment is None else _augment
+        positives = aug(positives, mirror=mirror, degrees=degrees, method=augment_method, device=device, keep_on_device=True)
     if share_pyramids:
         negatives = list(negatives)
         producer, store, stored = _share_negatives(init_model(*_root_sizes(positives, parents), sbin, tsize), negatives, train_options,
