@@ -1655,6 +1655,10 @@ int pbd_get_work(const pbd_handle* h, double work[6]);
 /* device memory held by the handle: the buffers and work tables of the current frame geometry (everything a
  * re-plan frees) and the model-sized allocations made at create.  Either pointer may be NULL.                     */
 int pbd_get_footprint(const pbd_handle* h, size_t* frame_bytes, size_t* model_bytes);
+/* device and pinned host memory the library holds in this process right now, over every handle, cache, ledger, store, group and
+ * call: the number of live buffers and their bytes (buffers that pbd_get_footprint leaves out included).  Compiled into every build.
+ * A call that keeps nothing leaves both where they were; destroying every object brings both back to zero.  Either pointer may be NULL. */
+int pbd_debug_live_allocs(long long* buffers, long long* bytes);
 /* Measure the planner's distance-transform block geometry on the caller's own frames instead of trusting its rule (float handles:
  * 256 lanes / 40 KB against 128 lanes / 25 KB per block; results are bit-identical under either): `batch` copies of the host image
  * per call (1 = single frames, the reference's call shape; > 1 = pbd_detect_batch_u8), 2 warm-up + 3 timed calls per geometry, the

@@ -85,6 +85,7 @@ EXPORTS = [
     "pbd_detect_stored", "pbd_detect_batch_stored", "pbd_qp_mine_stored", "pbd_qp_mine_batch_stored",
     "pbd_rotate_geometry", "pbd_map_rotate_points", "pbd_flip_points", "pbd_augment_host_u8", "pbd_augment_u8", "pbd_augment_dev_u8",
     "pbd_augment_last_error", "pbd_qp_write_warped_dev_u8",
+    "pbd_debug_live_allocs",
 ]
 # include/pbd_c.h "virtual positives"
 PBD_ROT_ORI2NEW, PBD_ROT_NEW2ORI = 0, 1
@@ -282,10 +283,18 @@ def lib() -> C.CDLL:
         L.pbd_augment_last_error.restype = C.c_char_p
         L.pbd_augment_last_error.argtypes = []
         L.pbd_qp_write_warped_dev_u8.argtypes = L.pbd_qp_write_warped_u8.argtypes
+        L.pbd_debug_live_allocs.argtypes = [V, V]
         if L.pbd_abi_version() != PBD_ABI_VERSION:
             raise ImportError(f"{LIB_PATH}: ABI version {L.pbd_abi_version()}, this binding is for {PBD_ABI_VERSION}")
         _lib = L
     return _lib
+
+
+def live_allocs():
+    """pbd_debug_live_allocs: (buffers, bytes) of device and pinned host memory the library holds in this process right now"""
+    n, b = C.c_longlong(0), C.c_longlong(0)
+    lib().pbd_debug_live_allocs(C.byref(n), C.byref(b))
+    return n.value, b.value
 
 
 def _p(a, ct):

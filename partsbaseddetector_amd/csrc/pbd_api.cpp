@@ -19,8 +19,8 @@
 // ---------------------------------------------------------------------------
 // The weights of one bank of nf filters of ONE size (the whole model, or one size group of a mixed bank) in every layout the filter-bank
 // kernels read: g.nfpad, g.d_wT (transposed, converted to T, the 16-byte B copies and the border cell), and for a split bank g.d_wS /
-// g.d_oscale.  *bytes: device bytes held.
-static int upload_bank(pbd_handle* h, const float* filt, int nf, int kh, int kw, SizeGroup& g, size_t* bytes) {
+// g.d_oscale.
+static int upload_bank(pbd_handle* h, const float* filt, int nf, int kh, int kw, SizeGroup& g) {
   const pbd_model_desc& m = h->md;
   g.kh = kh; g.kw = kw; g.nf = nf;
   // filters transposed to [tap][c][nfpad] (n contiguous): scalar loads in the VALU kernel,
@@ -50,7 +50,8 @@ static int upload_bank(pbd_handle* h, const float* filt, int nf, int kh, int kw,
         for (int c = 0; c < m.flen; ++c)
           wT[((size_t)(i * kw + j) * m.flen + c) * g.nfpad + n] =
               filt[(((size_t)n * kh + i) * kw + j) * m.flen + c];
-  HIPCHK(h, hipMalloc(&g.d_wT, wT.size() * h->ts));
+  int rc;
+  if ((rc = model_alloc(h, (char**)&g.d_wT, wT.size() * h->ts))) return rc;
   if (h->ts == 8) {   // filters convertTo(DataType<double>), src/PartsBasedDetector.cpp:113-117 (exact widening)
     std::vector<double> wd(wT.begin(), wT.end());
     // the double filter bank's 16-byte B layout replaces the (unused) float copy behind the border cell:
@@ -65,54 +66,47 @@ static int upload_bank(pbd_handle* h, const float* filt, int nf, int kh, int kw,
   } else {
     HIPCHK(h, hipMemcpy(g.d_wT, wT.data(), wT.size() * sizeof(float), hipMemcpyHostToDevice));
   }
-  size_t split_bytes = 0;
   if (h->split_parts) {   // the three exact bfloat16 parts of every weight (or two binary16 parts of the scaled weight), in the MFMA operand order of k_conv_split32
     std::vector<uint16_t> wS;
     if (h->split_parts == 3) conv_split_filters(filt, nf, kh, kw, wS);
     else {
       std::vector<float> osc;
       conv_split16_filters(filt, nf, kh, kw, wS, osc);
-      HIPCHK(h, hipMalloc((void**)&g.d_oscale, osc.size() * sizeof(float)));
+      if ((rc = model_alloc(h, &g.d_oscale, osc.size()))) return rc;
       HIPCHK(h, hipMemcpy(g.d_oscale, osc.data(), osc.size() * sizeof(float), hipMemcpyHostToDevice));
-      split_bytes += osc.size() * sizeof(float);
     }
-    split_bytes += wS.size() * sizeof(uint16_t);
-    HIPCHK(h, hipMalloc((void**)&g.d_wS, wS.size() * sizeof(uint16_t)));
+    if ((rc = model_alloc(h, &g.d_wS, wS.size()))) return rc;
     HIPCHK(h, hipMemcpy(g.d_wS, wS.data(), wS.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
   }
-  *bytes = wT.size() * h->ts + split_bytes;
   return PBD_OK;
 }
 
 static int upload_model(pbd_handle* h) {
   const pbd_model_desc& m = h->md;
-  size_t bank_bytes = 0;
+  int rc;
   if (!h->mixed) {
     SizeGroup g;
-    int rc = upload_bank(h, h->filters.data(), m.nfilters, m.kh, m.kw, g, &bank_bytes);
+    rc = upload_bank(h, h->filters.data(), m.nfilters, m.kh, m.kw, g);
     h->d_wT = g.d_wT; h->d_wS = g.d_wS; h->d_split_oscale = g.d_oscale; h->nfpad = g.nfpad;
     if (rc) return rc;
   } else {
     // size groups (plan_model): each uploaded as a uniform bank of its own
     size_t off = 0;
     for (SizeGroup& g : h->groups) {
-      size_t b = 0;
-      int rc = upload_bank(h, h->filters.data() + off, g.nf, g.kh, g.kw, g, &b);
-      if (rc) return rc;
-      bank_bytes += b;
+      if ((rc = upload_bank(h, h->filters.data() + off, g.nf, g.kh, g.kw, g))) return rc;
       off += (size_t)g.nf * g.kh * g.kw * m.flen;
     }
   }
   // orientation-snap table of the HOG kernel (k_hog.hip): 511 x 511 bytes, computed on the device by the reference's own
   // comparison chain in T
-  HIPCHK(h, hipMalloc(&h->d_hog_lut, hog_binlut_bytes()));
+  if ((rc = model_alloc(h, &h->d_hog_lut, hog_binlut_bytes()))) return rc;
   launch_hog_binlut(h->d_hog_lut, h->ts, h->stream);
   LAUNCHCHK(h, "HOG orientation table");
   HIPCHK(h, hipStreamSynchronize(h->stream));
   // biasw plus one trailing 0 (used by the stand-alone pbd_dt2d)
   std::vector<float> bw(h->biasw);
   bw.push_back(0.f);
-  HIPCHK(h, hipMalloc(&h->d_biasw, bw.size() * sizeof(float)));
+  if ((rc = model_alloc(h, &h->d_biasw, bw.size()))) return rc;
   HIPCHK(h, hipMemcpy(h->d_biasw, bw.data(), bw.size() * sizeof(float), hipMemcpyHostToDevice));
   const int nc = m.ncomponents, mp = h->max_parts;
   std::vector<int> par(nc * mp, 0), pl0(nc * mp, 0), npv(nc, 0), flt(nc * mp, 0), dep(nc * mp, 0);
@@ -128,13 +122,12 @@ static int upload_model(pbd_handle* h) {
       h->max_depth = std::max(h->max_depth, dep[c * mp + p]);
     }
   }
-  HIPCHK(h, hipMalloc(&h->d_flat, flt.size() * sizeof(int)));
-  HIPCHK(h, hipMalloc(&h->d_depth, dep.size() * sizeof(int)));
+  if ((rc = model_alloc(h, &h->d_flat, flt.size())) || (rc = model_alloc(h, &h->d_depth, dep.size()))) return rc;
   HIPCHK(h, hipMemcpy(h->d_flat, flt.data(), flt.size() * sizeof(int), hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->d_depth, dep.data(), dep.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(h, hipMalloc(&h->d_parent, par.size() * sizeof(int)));
-  HIPCHK(h, hipMalloc(&h->d_plane0, pl0.size() * sizeof(int)));
-  HIPCHK(h, hipMalloc(&h->d_nparts, npv.size() * sizeof(int)));
+  if ((rc = model_alloc(h, &h->d_parent, par.size())) || (rc = model_alloc(h, &h->d_plane0, pl0.size())) ||
+      (rc = model_alloc(h, &h->d_nparts, npv.size())))
+    return rc;
   HIPCHK(h, hipMemcpy(h->d_parent, par.data(), par.size() * sizeof(int), hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->d_plane0, pl0.data(), pl0.size() * sizeof(int), hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->d_nparts, npv.data(), npv.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -145,18 +138,16 @@ static int upload_model(pbd_handle* h) {
       const int fid = h->parts[fp].filterid[std::min(k, h->parts[fp].K - 1)];
       mix_rows[fp * PBD_MAX_MIX + k] = h->mixed ? h->fkh[fid] : m.kh;
     }
-  HIPCHK(h, hipMalloc(&h->d_mix_rows, mix_rows.size() * sizeof(int)));
+  if ((rc = model_alloc(h, &h->d_mix_rows, mix_rows.size()))) return rc;
   HIPCHK(h, hipMemcpy(h->d_mix_rows, mix_rows.data(), mix_rows.size() * sizeof(int), hipMemcpyHostToDevice));
   // candidates
   const int cap = h->opt.max_candidates;
   h->cand_stride = pbd_rec_bytes(mp);
-  HIPCHK(h, hipMalloc(&h->d_cand_count, sizeof(int)));
-  HIPCHK(h, hipMalloc(&h->d_cand_rec, sizeof(CandRec) * cap));
-  HIPCHK(h, hipMalloc(&h->d_cand_out, h->cand_stride * cap));
-  HIPCHK(h, hipHostMalloc((void**)&h->h_cand_out, h->cand_stride * cap));
-  HIPCHK(h, hipHostMalloc((void**)&h->h_cand_count, sizeof(int) * 4));
-  h->model_bytes = bank_bytes + hog_binlut_bytes() + bw.size() * sizeof(float) + (par.size() * 4 + npv.size()) * sizeof(int) + sizeof(int) +
-                   sizeof(CandRec) * cap + h->cand_stride * cap + mix_rows.size() * sizeof(int);
+  if ((rc = model_alloc(h, &h->d_cand_count, 1)) || (rc = model_alloc(h, &h->d_cand_rec, cap)) ||
+      (rc = model_alloc(h, &h->d_cand_out, h->cand_stride * cap)) ||
+      (rc = model_alloc(h, &h->h_cand_out, h->cand_stride * cap, true, false)) ||   // (the pinned candidate buffers are not part of the footprint)
+      (rc = model_alloc(h, &h->h_cand_count, 4, true, false)))
+    return rc;
   return PBD_OK;
 }
 
@@ -217,9 +208,7 @@ static void mark_min(pbd_handle* h, bool timed) {
 void free_frame(pbd_handle* h) {
   drop_graph(h);   // the captured launches point into the buffers freed below
   h->frames_on_plan = 0;
-  for (void* p : h->frame_allocs) hipFree(p);
   h->frame_allocs.clear();
-  h->frame_bytes = 0;
   h->d_extx = h->d_exty = nullptr; h->d_ext_base = nullptr; h->ext_ptr = false;
   h->d_cf_mask = nullptr; h->cf_mask_bytes = 0;
   h->d_ik_blocks = nullptr; h->d_ik_cells = nullptr; h->n_ik_blocks = 0;
@@ -616,7 +605,7 @@ static int begin_pending(pbd_handle* h, const FrameJob& job, FrameRoute* r) {
 
 // Back-tracking into the route's buffer, the route's post-stages behind it, then the records' way to the host.
 // Round 6: a handle that is not a member of an RCCL-gathering group lets the back-tracking kernel write the records and the count straight
-// into its pinned host buffers (hipHostMalloc: device-mapped, coherent): no copy nodes behind the kernel, and never a second copy for
+// into its pinned host buffers (device-mapped, coherent): no copy nodes behind the kernel, and never a second copy for
 // records beyond a first block.  Group members keep the device buffer: the all-gather reads it.  In front of a post-stage (depth
 // pruning, candidate filter: pbd_post.cpp) the records go to the device buffer it reads.
 static int run_argmin_enqueue(pbd_handle* h, const FrameJob& job, const FrameRoute& r) {
@@ -809,13 +798,7 @@ int pbd_destroy(pbd_handle* h) {
   if (!h) return PBD_ERR_ARG;
   if (h->stream) hipStreamSynchronize(h->stream);
   free_frame(h);
-  hipFree(h->d_wT); hipFree(h->d_wS); hipFree(h->d_split_oscale); hipFree(h->d_biasw); hipFree(h->d_hog_lut); hipFree(h->d_parent); hipFree(h->d_plane0); hipFree(h->d_nparts);
-  hipFree(h->d_flat); hipFree(h->d_depth); hipFree(h->d_mix_rows);
-  for (SizeGroup& g : h->groups) { hipFree(g.d_wT); hipFree(g.d_wS); hipFree(g.d_oscale); }
-  hipFree(h->d_cand_count); hipFree(h->d_cand_rec); hipFree(h->d_cand_out);
-  if (h->h_cand_out) hipHostFree(h->h_cand_out);
-  if (h->h_cand_count) hipHostFree(h->h_cand_count);
-  for (const pbd_handle::ModelBuf& b : h->model_allocs) { if (b.pinned) hipHostFree(b.p); else hipFree(b.p); }
+  h->model_allocs.clear();
   for (int i = 0; i < 8; ++i) if (h->ev[i]) hipEventDestroy(h->ev[i]);
   if (h->ev_dp0) hipEventDestroy(h->ev_dp0);
   if (h->ev_dp1) hipEventDestroy(h->ev_dp1);
@@ -1285,8 +1268,13 @@ int pbd_set_dp_pointers(pbd_handle* h, int level, int component, int part, int p
 }
 int pbd_get_footprint(const pbd_handle* h, size_t* frame_bytes, size_t* model_bytes) {
   if (!h) return PBD_ERR_ARG;
-  if (frame_bytes) *frame_bytes = h->frame_bytes;
-  if (model_bytes) *model_bytes = h->model_bytes;
+  if (frame_bytes) *frame_bytes = h->frame_allocs.bytes();
+  if (model_bytes) *model_bytes = h->model_allocs.bytes();
+  return PBD_OK;
+}
+int pbd_debug_live_allocs(long long* buffers, long long* bytes) {
+  if (buffers) *buffers = pbd_live_buffers.load();
+  if (bytes) *bytes = pbd_live_bytes.load();
   return PBD_OK;
 }
 int pbd_abi_version(void) { return PBD_ABI_VERSION; }
@@ -1380,8 +1368,12 @@ static int dt2d_(pbd_handle* h, const void* in, int rows, int cols, double ax, d
   char *d_in, *d_tmp, *d_sdt;
   char *d_ixT, *d_iy;
   const size_t pb = (size_t)dt_ptr_bytes_for(std::max(rows, cols));   // the pointer planes' width, as a frame plan chooses it: bytes while both passes' lines have byte links
-  HIPCHK(h, hipMalloc(&d_in, HW * ts)); HIPCHK(h, hipMalloc(&d_tmp, HW * ts)); HIPCHK(h, hipMalloc(&d_sdt, HW * ts));
-  HIPCHK(h, hipMalloc(&d_ixT, HW * pb)); HIPCHK(h, hipMalloc(&d_iy, HW * pb));
+  CallScratch s(h);   // (a refusal below gives the buffers back like every other way out)
+  static const char* const what = "pbd_dt2d: ";
+  int rc;
+  if ((rc = s.get(&d_in, HW * ts, what)) || (rc = s.get(&d_tmp, HW * ts, what)) || (rc = s.get(&d_sdt, HW * ts, what)) ||
+      (rc = s.get(&d_ixT, HW * pb, what)) || (rc = s.get(&d_iy, HW * pb, what)))
+    return rc;
   HIPCHK(h, hipMemcpyAsync(d_in, in, HW * ts, hipMemcpyHostToDevice, h->stream));
   DtMap maps[2] = {dt_map(d_in, d_tmp, d_ixT, 0.f, 0.f, osx, 1), dt_map(d_tmp, d_sdt, d_iy, 0.f, 0.f, osy, 0)};
   maps[0].a = ax; maps[0].b = bx; maps[0].r2a = 1.0 / (2.0 * ax);   // the caller's quadratics (not the model's -w)
@@ -1401,8 +1393,7 @@ static int dt2d_(pbd_handle* h, const void* in, int rows, int cols, double ax, d
   dt_mark_fused(tasks, maps, tsz);   // (the caller's quadratics: fused arithmetic only if they are converted floats)
   if (pb == 1) dt_mark_ptr8(tasks);
   DtMap* d_maps; DtTask* d_tasks;
-  HIPCHK(h, hipMalloc(&d_maps, sizeof(maps)));
-  HIPCHK(h, hipMalloc(&d_tasks, sizeof(DtTask) * tasks.size()));
+  if ((rc = s.get(&d_maps, 2, what)) || (rc = s.get(&d_tasks, tasks.size(), what))) return rc;
   HIPCHK(h, hipMemcpyAsync(d_maps, maps, sizeof(maps), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(d_tasks, tasks.data(), sizeof(DtTask) * tasks.size(), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));  // host staging buffers above are pageable
@@ -1429,8 +1420,6 @@ static int dt2d_(pbd_handle* h, const void* in, int rows, int cols, double ax, d
     if (ix) ix[i] = x;
     if (iy) iy[i] = y;
   }
-  hipFree(d_in); hipFree(d_tmp); hipFree(d_sdt); hipFree(d_ixT); hipFree(d_iy);
-  hipFree(d_maps); hipFree(d_tasks);
   if (left_domain)
     return fail(h, PBD_ERR_ARG, "the scores left the finite range in the x or the y pass (|y| + |a| d^2 + |b| d overflows): outside the distance transform's domain");
   return PBD_OK;
@@ -1461,15 +1450,18 @@ static int hog_u8_(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int
   std::vector<HogTile> tiles;
   for (int y = 0; y < L.ch; y += tc) for (int x = 0; x < L.cw; x += tc) tiles.push_back(HogTile{0, y, x, 0});
   uint8_t* d_im; char* d_feat; LevelDev* d_lv; HogTile* d_tiles;
-  HIPCHK(h, hipMalloc(&d_im, (size_t)w * hgt * cn)); HIPCHK(h, hipMalloc(&d_feat, (size_t)L.cw * L.ch * PBD_FLEN * ts));
-  HIPCHK(h, hipMalloc(&d_lv, sizeof(L))); HIPCHK(h, hipMalloc(&d_tiles, sizeof(HogTile) * tiles.size()));
+  CallScratch s(h);
+  static const char* const what = "pbd_hog_u8: ";
+  int rc;
+  if ((rc = s.get(&d_im, (size_t)w * hgt * cn, what)) || (rc = s.get(&d_feat, (size_t)L.cw * L.ch * PBD_FLEN * ts, what)) ||
+      (rc = s.get(&d_lv, 1, what)) || (rc = s.get(&d_tiles, tiles.size(), what)))
+    return rc;
   HIPCHK(h, hipMemcpy2D(d_im, (size_t)w * cn, im, stride, (size_t)w * cn, hgt, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(d_lv, &L, sizeof(L), hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(d_tiles, tiles.data(), sizeof(HogTile) * tiles.size(), hipMemcpyHostToDevice));
   launch_hog(d_tiles, (int)tiles.size(), d_lv, d_im, d_feat, ts, cn, sbin, tc, h->d_hog_lut, nullptr, 0, PBD_DEPTH_8U, h->stream);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemcpy(out, d_feat, (size_t)L.cw * L.ch * PBD_FLEN * ts, hipMemcpyDeviceToHost));
-  hipFree(d_im); hipFree(d_feat); hipFree(d_lv); hipFree(d_tiles);
   return PBD_OK;
 }
 int pbd_hog_u8(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int stride, float* out, int* cell_w, int* cell_h) {
@@ -1483,15 +1475,17 @@ int pbd_resize_u8(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int 
   if (!h || !im || !out || w <= 0 || hgt <= 0 || ow <= 0 || oh <= 0 || (cn != 1 && cn != 3) || stride < w * cn) return PBD_ERR_ARG;
   ON_DEVICE(h);
   uint8_t *d_im, *d_out;
-  HIPCHK(h, hipMalloc(&d_im, (size_t)w * hgt * cn)); HIPCHK(h, hipMalloc(&d_out, (size_t)ow * oh * cn));
+  CallScratch s(h);
+  static const char* const what = "pbd_resize_u8: ";
+  int rc;
+  if ((rc = s.get(&d_im, (size_t)w * hgt * cn, what)) || (rc = s.get(&d_out, (size_t)ow * oh * cn, what))) return rc;
   HIPCHK(h, hipMemcpy2D(d_im, (size_t)w * cn, im, stride, (size_t)w * cn, hgt, hipMemcpyHostToDevice));
   PyrJob job{0, 0, w, hgt, ow, oh}, *d_job;
-  HIPCHK(h, hipMalloc(&d_job, sizeof(job)));
+  if ((rc = s.get(&d_job, 1, what))) return rc;
   HIPCHK(h, hipMemcpy(d_job, &job, sizeof(job), hipMemcpyHostToDevice));
   launch_resize(d_job, 1, ow * oh, cn, w * cn, d_im, d_out, h->stream);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemcpy(out, d_out, (size_t)ow * oh * cn, hipMemcpyDeviceToHost));
-  hipFree(d_im); hipFree(d_out); hipFree(d_job);
   return PBD_OK;
 }
 
@@ -1500,15 +1494,17 @@ int pbd_pyrdown_u8(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int
   ON_DEVICE(h);
   const size_t sb = (size_t)w * hgt * cn, db = (size_t)((w + 1) / 2) * ((hgt + 1) / 2) * cn;
   uint8_t* d_buf;
-  HIPCHK(h, hipMalloc(&d_buf, sb + db));
+  CallScratch s(h);
+  static const char* const what = "pbd_pyrdown_u8: ";
+  int rc;
+  if ((rc = s.get(&d_buf, sb + db, what))) return rc;
   HIPCHK(h, hipMemcpy2D(d_buf, (size_t)w * cn, im, stride, (size_t)w * cn, hgt, hipMemcpyHostToDevice));
   PyrJob job{0, (unsigned long long)sb, w, hgt, (w + 1) / 2, (hgt + 1) / 2}, *d_job;
-  HIPCHK(h, hipMalloc(&d_job, sizeof(job)));
+  if ((rc = s.get(&d_job, 1, what))) return rc;
   HIPCHK(h, hipMemcpy(d_job, &job, sizeof(job), hipMemcpyHostToDevice));
   launch_pyrdown(d_job, 1, job.dw, job.dh, cn, d_buf, h->stream);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemcpy(out, d_buf + sb, db, hipMemcpyDeviceToHost));
-  hipFree(d_buf); hipFree(d_job);
   return PBD_OK;
 }
 
@@ -1524,8 +1520,12 @@ int pbd_resize_area_f64(pbd_handle* h, const double* im, int w, int hgt, int cn,
   const size_t sb = (size_t)w * hgt * cn * 8, db = (size_t)dw * dh * cn * 8;
   uint8_t *d_im, *d_out; MatRun* d_runs; MatTap* d_taps;
   MatJob job{0, 0, w, hgt, dw, dh, 0, dh}, *d_job;
-  HIPCHK(h, hipMalloc(&d_im, sb)); HIPCHK(h, hipMalloc(&d_out, db)); HIPCHK(h, hipMalloc(&d_job, sizeof(job)));
-  HIPCHK(h, hipMalloc(&d_runs, runs.size() * sizeof(MatRun))); HIPCHK(h, hipMalloc(&d_taps, taps.size() * sizeof(MatTap)));
+  CallScratch s(h);
+  static const char* const what = "pbd_resize_area_f64: ";
+  int rc;
+  if ((rc = s.get(&d_im, sb, what)) || (rc = s.get(&d_out, db, what)) || (rc = s.get(&d_job, 1, what)) ||
+      (rc = s.get(&d_runs, runs.size(), what)) || (rc = s.get(&d_taps, taps.size(), what)))
+    return rc;
   HIPCHK(h, hipMemcpy(d_im, im, sb, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(d_job, &job, sizeof(job), hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(d_runs, runs.data(), runs.size() * sizeof(MatRun), hipMemcpyHostToDevice));
@@ -1533,7 +1533,6 @@ int pbd_resize_area_f64(pbd_handle* h, const double* im, int w, int hgt, int cn,
   launch_resize_area(d_job, 1, dw * dh, d_runs, d_taps, cn, w * cn, true, d_im, d_out, h->stream);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemcpy(out, d_out, db, hipMemcpyDeviceToHost));
-  hipFree(d_im); hipFree(d_out); hipFree(d_job); hipFree(d_runs); hipFree(d_taps);
   *ow = dw; *oh = dh;
   return PBD_OK;
 }
@@ -1547,13 +1546,15 @@ int pbd_reduce_f64(pbd_handle* h, const double* im, int w, int hgt, int cn, doub
   const size_t sb = (size_t)w * hgt * cn * 8, db = (size_t)dw * dh * cn * 8;
   uint8_t* d_buf;
   MatJob job{0, (unsigned long long)sb, w, hgt, dw, dh, 0, 0}, *d_job;
-  HIPCHK(h, hipMalloc(&d_buf, sb + db)); HIPCHK(h, hipMalloc(&d_job, sizeof(job)));
+  CallScratch s(h);
+  static const char* const what = "pbd_reduce_f64: ";
+  int rc;
+  if ((rc = s.get(&d_buf, sb + db, what)) || (rc = s.get(&d_job, 1, what))) return rc;
   HIPCHK(h, hipMemcpy(d_buf, im, sb, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(d_job, &job, sizeof(job), hipMemcpyHostToDevice));
   launch_reduce_f64(d_job, 1, dw * dh, cn, d_buf, h->stream);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemcpy(out, d_buf + sb, db, hipMemcpyDeviceToHost));
-  hipFree(d_buf); hipFree(d_job);
   *ow = dw; *oh = dh;
   return PBD_OK;
 }
@@ -1563,12 +1564,13 @@ int pbd_nms_map(pbd_handle* h, const float* src, int rows, int cols, int sz, uin
   ON_DEVICE(h);
   float* d_src; uint8_t* d_dst;
   const size_t n = (size_t)rows * cols;
-  HIPCHK(h, hipMalloc(&d_src, n * 4)); HIPCHK(h, hipMalloc(&d_dst, n));
+  CallScratch s(h);
+  int rc;
+  if ((rc = s.get(&d_src, n, "pbd_nms_map: ")) || (rc = s.get(&d_dst, n, "pbd_nms_map: "))) return rc;
   HIPCHK(h, hipMemcpy(d_src, src, n * 4, hipMemcpyHostToDevice));
   launch_nms_map(d_src, rows, cols, sz, d_dst, h->stream);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemcpy(dst, d_dst, n, hipMemcpyDeviceToHost));
-  hipFree(d_src); hipFree(d_dst);
   return PBD_OK;
 }
 

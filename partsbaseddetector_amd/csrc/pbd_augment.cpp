@@ -6,26 +6,6 @@
 #include "augment_core.hpp"
 
 namespace {
-struct AugRun {
-  int prev = -1;
-  hipStream_t st = nullptr;
-  std::vector<void*> bufs;
-  hipError_t alloc(void** p, size_t bytes) {
-    void* q = nullptr;
-    const hipError_t e = hipMalloc(&q, bytes ? bytes : 1);
-    if (e == hipSuccess) bufs.push_back(q);
-    *p = q;
-    return e;
-  }
-  ~AugRun() {
-    if (st) hipStreamSynchronize(st);   // an error return may leave copies queued: nothing they touch goes away before they are done
-    for (void* b : bufs) hipFree(b);
-    if (st) hipStreamDestroy(st);
-    if (prev >= 0) hipSetDevice(prev);
-    (void)hipGetLastError();
-  }
-};
-
 // rows of row_bytes between two pitches: one flat copy where both are dense (copy_rows' rule)
 hipError_t copy2d(void* dst, size_t dpitch, const void* src, size_t spitch, size_t row_bytes, size_t rows, hipMemcpyKind kind, hipStream_t st) {
   if (dpitch == row_bytes && spitch == row_bytes) return hipMemcpyAsync(dst, src, row_bytes * rows, kind, st);
@@ -45,11 +25,10 @@ int augment_run(int device, const uint8_t* im, int w, int hgt, int cn, int strid
     (void)hipGetLastError();
     return aug_fail(PBD_ERR_HIP, "virtual positives: no such HIP device");
   }
-  AugRun run;
-  if (hipGetDevice(&run.prev) != hipSuccess) run.prev = -1;
+  DeviceRun run;
   AUGHIP(hipSetDevice(device));
   CLEAR_STICKY();
-  AUGHIP(hipStreamCreateWithFlags(&run.st, hipStreamNonBlocking));
+  AUGHIP(run.open());
 
   AugArgs a{};
   a.w = w; a.h = hgt; a.cn = cn; a.nops = nops;
@@ -57,10 +36,10 @@ int augment_run(int device, const uint8_t* im, int w, int hgt, int cn, int strid
   if (dev) {
     a.im = im; a.stride = (unsigned long long)stride;
   } else {
-    void* d_im;
+    uint8_t* d_im;
     AUGHIP(run.alloc(&d_im, rowb * hgt));
-    AUGHIP(copy2d(d_im, rowb, im, (size_t)stride, rowb, (size_t)hgt, hipMemcpyHostToDevice, run.st));
-    a.im = (const uint8_t*)d_im; a.stride = rowb;
+    AUGHIP(copy2d(d_im, rowb, im, (size_t)stride, rowb, (size_t)hgt, hipMemcpyHostToDevice, run.stream));
+    a.im = d_im; a.stride = rowb;
   }
   for (int i = 0; i < nops; ++i) {
     AugDesc& d = desc[i];
@@ -69,23 +48,22 @@ int augment_run(int device, const uint8_t* im, int w, int hgt, int cn, int strid
     if (dev) {
       d.out = outs[i]; d.out_stride = (unsigned long long)out_strides[i];
     } else {
-      void* o;
-      AUGHIP(run.alloc(&o, (size_t)d.rows * d.cols * cn));
-      d.out = (uint8_t*)o; d.out_stride = (unsigned long long)d.cols * cn;
+      AUGHIP(run.alloc(&d.out, (size_t)d.rows * d.cols * cn));
+      d.out_stride = (unsigned long long)d.cols * cn;
     }
   }
-  void* d_desc;
-  AUGHIP(run.alloc(&d_desc, sizeof(AugDesc) * (size_t)nops));
-  AUGHIP(hipMemcpyAsync(d_desc, desc, sizeof(AugDesc) * (size_t)nops, hipMemcpyHostToDevice, run.st));
-  a.desc = (const AugDesc*)d_desc;
-  launch_augment(a, run.st);
+  AugDesc* d_desc;
+  AUGHIP(run.alloc(&d_desc, (size_t)nops));
+  AUGHIP(hipMemcpyAsync(d_desc, desc, sizeof(AugDesc) * (size_t)nops, hipMemcpyHostToDevice, run.stream));
+  a.desc = d_desc;
+  launch_augment(a, run.stream);
   AUGHIP(hipGetLastError());
   if (!dev)
     for (int i = 0; i < nops; ++i) {
       const AugDesc& d = desc[i];   // (only the canvas row's bytes of an output row are written)
-      AUGHIP(copy2d(outs[i], (size_t)out_strides[i], d.out, (size_t)d.out_stride, (size_t)d.cols * cn, (size_t)d.rows, hipMemcpyDeviceToHost, run.st));
+      AUGHIP(copy2d(outs[i], (size_t)out_strides[i], d.out, (size_t)d.out_stride, (size_t)d.cols * cn, (size_t)d.rows, hipMemcpyDeviceToHost, run.stream));
     }
-  AUGHIP(hipStreamSynchronize(run.st));
+  AUGHIP(hipStreamSynchronize(run.stream));
   return PBD_OK;
 }
 }  // namespace

@@ -15,23 +15,18 @@ struct pbd_eval {
   double thresh = .5;
   unsigned long long* d_key = nullptr; int n2cap = 0;
   int* d_tpc = nullptr; double* d_sm = nullptr; double* d_out = nullptr;
-  std::vector<void*> bufs;
+  DevBufs bufs;
+  template <typename T> int alloc(T** p, size_t n) {
+    const hipError_t e = bufs.alloc(p, n);
+    return e == hipSuccess ? PBD_OK : fail(h, PBD_ERR_HIP, pbd_alloc_error("evaluation: ", e));
+  }
 };
 
 namespace {
-template <typename T> int ealloc(pbd_eval* ev, T** p, size_t n) {
-  void* v = nullptr;
-  hipError_t e = hipMalloc(&v, sizeof(T) * std::max<size_t>(n, 1));
-  if (e != hipSuccess) return fail(ev->h, PBD_ERR_HIP, std::string("evaluation: hipMalloc: ") + hipGetErrorString(e));
-  ev->bufs.push_back(v);
-  *p = (T*)v;
-  return PBD_OK;
-}
-// the small tables of one call: sections of one host blob, uploaded into one device buffer that lives until the call returns
+// the small tables of one call: sections of one host blob, uploaded into one device buffer of the call's scratch
 struct Blob {
   std::vector<char> host;
-  void* dev = nullptr;
-  ~Blob() { if (dev) hipFree(dev); }
+  char* dev = nullptr;
   size_t put(const void* p, size_t bytes) {   // -> the section's offset (16-byte aligned)
     const size_t off = (host.size() + 15) & ~(size_t)15;
     host.resize(off + bytes);
@@ -39,12 +34,12 @@ struct Blob {
     return off;
   }
   size_t room(size_t bytes) { return put(nullptr, bytes); }
-  int upload(pbd_handle* h) {
-    hipError_t e = hipMalloc(&dev, std::max<size_t>(host.size(), 16));
-    if (e == hipSuccess && !host.empty()) e = hipMemcpyAsync(dev, host.data(), host.size(), hipMemcpyHostToDevice, h->stream);
-    return e == hipSuccess ? PBD_OK : fail(h, PBD_ERR_HIP, std::string("evaluation: ") + hipGetErrorString(e));
+  int upload(CallScratch& s) {
+    dev = s.dev<char>(std::max<size_t>(host.size(), 16));
+    s.up(dev, host.data(), host.size());
+    return s.status("evaluation: ");
   }
-  template <typename T> T* at(size_t off) const { return (T*)((char*)dev + off); }
+  template <typename T> T* at(size_t off) const { return (T*)(dev + off); }
 };
 int finish(pbd_handle* h, const char* what) {
   hipError_t e = hipGetLastError();
@@ -99,12 +94,13 @@ int capacity_fail(pbd_handle* h, const char* what, long long need, int cap) {
 int pck_append(pbd_eval* ev, const char* rec, size_t stride, int slots, const int* found, int nframes, const double* points,
                const double* scale, const int* ngt) {
   pbd_handle* h = ev->h;
+  CallScratch s(h);
   Blob b;
   std::vector<EvalFrame> fr((size_t)nframes);
   const PersonTables t = put_persons(b, fr, ev->L.P, points, scale, ngt, slots);
   if (t.total > 0) {
     const size_t o_found = b.put(found, sizeof(int) * (size_t)nframes * slots);
-    int rc = b.upload(h);
+    int rc = b.upload(s);
     if (rc) return rc;
     EvalPckAddArgs a{};
     a.L = ev->L; a.n0 = ev->n;
@@ -156,13 +152,14 @@ int pck_run(pbd_eval* ev, const uint8_t* im, const uint8_t* const* ims, int nfra
 int apk_append(pbd_eval* ev, const char* rec, size_t stride, const int* perm, std::vector<EvalFrame>& fr, const double* points,
                const double* scale, const int* ngt, int slots) {
   pbd_handle* h = ev->h;
+  CallScratch s(h);
   Blob b;
   const PersonTables t = put_persons(b, fr, ev->L.P, points, scale, ngt, slots);
   int total = 0, maxcount = 0;
   for (const EvalFrame& f : fr) { total = std::max(total, f.start + f.count); maxcount = std::max(maxcount, f.count); }
   if (total > 0) {
     const size_t o_ord = b.room(sizeof(int) * (size_t)total);
-    int rc = b.upload(h);
+    int rc = b.upload(s);
     if (rc) return rc;
     EvalApkAddArgs a{};
     a.L = ev->L; a.m0 = ev->m;
@@ -255,9 +252,9 @@ int pbd_eval_create(pbd_handle* h, int nparts, int max_instances, int max_detect
   ev->n2cap = n2;
   const size_t P = (size_t)nparts, N = (size_t)max_instances, M = (size_t)max_detections;
   int rc;
-  if ((rc = ealloc(ev, &L.dist, N * P)) || (rc = ealloc(ev, &L.scale, N)) || (rc = ealloc(ev, &L.score, M)) || (rc = ealloc(ev, &L.tp, M * P)) ||
-      (rc = ealloc(ev, &ev->d_key, (size_t)n2)) || (rc = ealloc(ev, &ev->d_tpc, M * P)) || (rc = ealloc(ev, &ev->d_sm, M * P)) ||
-      (rc = ealloc(ev, &ev->d_out, P))) {
+  if ((rc = ev->alloc(&L.dist, N * P)) || (rc = ev->alloc(&L.scale, N)) || (rc = ev->alloc(&L.score, M)) || (rc = ev->alloc(&L.tp, M * P)) ||
+      (rc = ev->alloc(&ev->d_key, (size_t)n2)) || (rc = ev->alloc(&ev->d_tpc, M * P)) || (rc = ev->alloc(&ev->d_sm, M * P)) ||
+      (rc = ev->alloc(&ev->d_out, P))) {
     pbd_eval_destroy(ev);
     return rc;
   }
@@ -268,7 +265,6 @@ int pbd_eval_create(pbd_handle* h, int nparts, int max_instances, int max_detect
 void pbd_eval_destroy(pbd_eval* ev) {
   if (!ev) return;
   hipStreamSynchronize(ev->h->stream);   // (like pbd_destroy: the caller's current device is left alone)
-  for (void* p : ev->bufs) hipFree(p);
   delete ev;
 }
 
@@ -320,15 +316,11 @@ int pbd_eval_add_pck_records(pbd_eval* ev, const pbd_candidate_head* heads, cons
   const size_t st = h->cand_stride;
   std::vector<char> rec(st * (size_t)std::max(ngt, 1), 0);
   for (int g = 0; g < ngt; ++g) if (found[g]) pbd_rec_put(rec.data() + st * g, mp, heads, boxes, nullptr, (size_t)g);
-  void* d_rec = nullptr;
-  if (ngt > 0) {
-    HIPCHK(h, hipMalloc(&d_rec, rec.size()));
-    hipError_t e = hipMemcpyAsync(d_rec, rec.data(), rec.size(), hipMemcpyHostToDevice, h->stream);
-    if (e != hipSuccess) { hipFree(d_rec); return fail(h, PBD_ERR_HIP, std::string("evaluation: ") + hipGetErrorString(e)); }
-  }
-  rc = pck_append(ev, (const char*)d_rec, st, std::max(ngt, 1), found, 1, points, scale, &ngt);
-  if (d_rec) { hipStreamSynchronize(h->stream); hipFree(d_rec); }
-  return rc;
+  CallScratch s(h);
+  char* d_rec = s.dev<char>(ngt > 0 ? rec.size() : 0);
+  s.up(d_rec, rec.data(), ngt > 0 ? rec.size() : 0);
+  if ((rc = s.status("evaluation: "))) return rc;
+  return pck_append(ev, d_rec, st, std::max(ngt, 1), found, 1, points, scale, &ngt);
 }
 
 int pbd_eval_add_apk_records(pbd_eval* ev, const pbd_candidate_head* heads, const int32_t* boxes, int count, const double* points,
@@ -352,17 +344,13 @@ int pbd_eval_add_apk_records(pbd_eval* ev, const pbd_candidate_head* heads, cons
   const size_t st = h->cand_stride;
   std::vector<char> rec(st * (size_t)std::max(count, 1), 0);
   for (int i = 0; i < count; ++i) pbd_rec_put(rec.data() + st * i, mp, heads, boxes, nullptr, (size_t)i);
-  void* d_rec = nullptr;
-  if (count > 0) {
-    HIPCHK(h, hipMalloc(&d_rec, rec.size()));
-    hipError_t e = hipMemcpyAsync(d_rec, rec.data(), rec.size(), hipMemcpyHostToDevice, h->stream);
-    if (e != hipSuccess) { hipFree(d_rec); return fail(h, PBD_ERR_HIP, std::string("evaluation: ") + hipGetErrorString(e)); }
-  }
+  CallScratch s(h);
+  char* d_rec = s.dev<char>(count > 0 ? rec.size() : 0);
+  s.up(d_rec, rec.data(), count > 0 ? rec.size() : 0);
+  if ((rc = s.status("evaluation: "))) return rc;
   std::vector<EvalFrame> fr(1);
   fr[0].start = 0; fr[0].count = count;
-  rc = apk_append(ev, (const char*)d_rec, st, nullptr, fr, points, scale, &ngt, std::max(ngt, 1));
-  if (d_rec) { hipStreamSynchronize(h->stream); hipFree(d_rec); }
-  return rc;
+  return apk_append(ev, d_rec, st, nullptr, fr, points, scale, &ngt, std::max(ngt, 1));
 }
 
 int pbd_eval_pck_frame_u8(pbd_eval* ev, const uint8_t* im, int w, int hgt, int cn, int stride, const double* points, const double* scale,
@@ -415,20 +403,21 @@ int pbd_eval_apk(pbd_eval* ev, double* apk, double* prec, double* rec) {
   a.key = ev->d_key; a.tpc = ev->d_tpc; a.sm = ev->d_sm; a.out = ev->d_out;
   a.n2 = PBD_EVAL_SORT_TILE;
   while (a.n2 < ev->m) a.n2 <<= 1;
-  void* d_curves = nullptr;
+  CallScratch s(h);
   const int ncurves = (prec ? 1 : 0) + (rec ? 1 : 0);
   if (ncurves && M) {
-    HIPCHK(h, hipMalloc(&d_curves, sizeof(double) * P * M * ncurves));
-    if (prec) a.prec = (double*)d_curves;
-    if (rec) a.rec = (double*)d_curves + (prec ? P * M : 0);
+    double* d_curves = s.dev<double>(P * M * ncurves);
+    int rc = s.status("evaluation (APK): ");
+    if (rc) return rc;
+    if (prec) a.prec = d_curves;
+    if (rec) a.rec = d_curves + (prec ? P * M : 0);
   }
   launch_eval_apk(a, h->stream);
-  hipError_t e = hipMemcpyAsync(apk, ev->d_out, sizeof(double) * P, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess && a.prec) e = hipMemcpyAsync(prec, a.prec, sizeof(double) * P * M, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess && a.rec) e = hipMemcpyAsync(rec, a.rec, sizeof(double) * P * M, hipMemcpyDeviceToHost, h->stream);
-  int rc = e == hipSuccess ? finish(h, "evaluation (APK): ") : fail(h, PBD_ERR_HIP, std::string("evaluation (APK): ") + hipGetErrorString(e));
-  if (d_curves) { hipStreamSynchronize(h->stream); hipFree(d_curves); }
-  return rc;
+  s.launched();
+  s.down(apk, ev->d_out, sizeof(double) * P);
+  if (a.prec) s.down(prec, a.prec, sizeof(double) * P * M);
+  if (a.rec) s.down(rec, a.rec, sizeof(double) * P * M);
+  return s.finish("evaluation (APK): ");
 }
 
 }  // extern "C"

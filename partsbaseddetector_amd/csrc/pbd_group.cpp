@@ -59,6 +59,7 @@ struct pbd_group {
   std::vector<char*> d_send, d_recv;   // per member: its block / every member's block
   char* h_recv = nullptr;              // pinned, size() blocks (filled from member 0)
   size_t block = 0;                    // bytes of one {count, pad, first records} block
+  DevBufs mem;                         // the gather's buffers above
   int shard_w = 0, shard_h = 0, shard_cn = 0;   // geometry the members' level sets were computed for (0: all levels)
   int cand_mode = PBD_CAND_RAW; float cand_overlap = 0.f;   // pbd_group_set_candidate_filter
   int cand_nms = PBD_NMS_PAINTED; int cand_top = 0;         // pbd_group_set_candidate_nms
@@ -211,13 +212,13 @@ static int group_create(const pbd_model_desc* model, const int32_t* fsize, bool 
       g->d_send.assign(ndev, nullptr); g->d_recv.assign(ndev, nullptr);
       for (int i = 0; i < ndev; ++i) {
         GHIP(g, hipSetDevice(g->dev[i]));
-        GHIP(g, hipMalloc((void**)&g->d_send[i], g->block));
-        GHIP(g, hipMalloc((void**)&g->d_recv[i], g->block * ndev));
+        GHIP(g, g->mem.alloc(&g->d_send[i], g->block));
+        GHIP(g, g->mem.alloc(&g->d_recv[i], g->block * ndev));
         GHIP(g, hipMemset(g->d_send[i], 0, g->block));
         g->m[i]->d_gsend = g->d_send[i];
       }
       GHIP(g, hipSetDevice(g->dev[0]));
-      GHIP(g, hipHostMalloc((void**)&g->h_recv, g->block * ndev));
+      GHIP(g, g->mem.alloc(&g->h_recv, g->block * ndev, true));
       g->mode = PBD_GATHER_RCCL;
     } else if (gather_mode == PBD_GATHER_RCCL) {
       return gfail(g, PBD_ERR_RCCL, "PBD_GATHER_RCCL requested but " + why);
@@ -233,14 +234,12 @@ int pbd_group_destroy(pbd_group* g) {
     if (g->m[i]->stream) hipStreamSynchronize(g->m[i]->stream);
   }
   for (ncclComm_t c : g->comms) if (c) g->rccl.CommDestroy(c);
+  g->mem.clear();   // (every member's stream is idle)
   for (size_t i = 0; i < g->m.size(); ++i) {
     hipSetDevice(g->dev[i]);
-    if (i < g->d_send.size() && g->d_send[i]) hipFree(g->d_send[i]);
-    if (i < g->d_recv.size() && g->d_recv[i]) hipFree(g->d_recv[i]);
     g->m[i]->d_gsend = nullptr;
     pbd_destroy(g->m[i]);
   }
-  if (g->h_recv) hipHostFree(g->h_recv);
   if (g->rccl.so) dlclose(g->rccl.so);
   delete g;
   return PBD_OK;

@@ -23,6 +23,7 @@
 #include "pbd_plan.hpp"
 #include "pbd_lds.hpp"
 #include "pbd_route.hpp"
+#include "pbd_mem.hpp"
 
 #ifndef PBD_ARGMIN_ZERO_COPY
 #define PBD_ARGMIN_ZERO_COPY 1   // k_backtrack writes candidates straight to the pinned host buffers (handles outside RCCL groups)
@@ -219,10 +220,9 @@ struct pbd_handle : HostModel {   // the model (pbd_plan.hpp: validated descript
   double dp_ms_sum = 0; int dp_frames = 0; bool dp_timer_on = true; bool min_timed = false;   // DP events are recorded only while profiling; min_timed: the last min() recorded them
   hipGraphExec_t gexec = nullptr;   // pbd_options.graph: the frame's launches, captured once per geometry
   int frames_on_plan = 0;           // frames enqueued since the last plan_frame
-  std::vector<void*> frame_allocs;  // everything freed on re-plan
-  struct ModelBuf { void* p; size_t bytes; bool pinned; };
-  std::vector<ModelBuf> model_allocs;   // the post-stages' buffers (pbd_post.cpp model_alloc): held until pbd_destroy
-  size_t frame_bytes = 0, model_bytes = 0;   // device memory held for the frame plan / the model (pbd_get_footprint)
+  // device memory held for the frame plan (dev_alloc: everything freed on re-plan) and for the model (model_alloc: the uploaded model
+  // and the post-stages' buffers, held until pbd_destroy); pbd_get_footprint reads their bytes()
+  DevBufs frame_allocs, model_allocs;
   // pointer tables handed in by the caller (pbd_set_dp_pointers: a DynamicProgram::argmin fed tables that this handle's
   // min() did not produce): composed Ix / Iy per (level, component, plane), allocated on first use; back-tracking
   // reads them instead of the DT planes until the next min()
@@ -525,33 +525,19 @@ int pbd_i_b3_end(pbd_handle* h);
 int pbd_i_filter_host(pbd_handle* h, int mode, float overlap, int im_w, int im_h, char* recs, int count, int* kept,
                       int kind = PBD_NMS_PAINTED, int top = 0);
 int pbd_i_depth_check(pbd_handle* h, int depth_type, long long dstride, int w);   // a depth-carrying frame's depth arguments
-// Frame-plan buffers: counted in frame_bytes, freed on re-plan (pbd_api.cpp free_frame)
+// Frame-plan buffers: counted in the frame footprint, freed on re-plan (pbd_api.cpp free_frame)
 template <typename T>
 int dev_alloc(pbd_handle* h, T** p, size_t n) {
-  void* q = nullptr;
-  hipError_t e = hipMalloc(&q, (n > 1 ? n : 1) * sizeof(T));
-  if (e != hipSuccess) { h->err = std::string("hipMalloc: ") + hipGetErrorString(e); return PBD_ERR_HIP; }
-  h->frame_allocs.push_back(q);
-  h->frame_bytes += (n > 1 ? n : 1) * sizeof(T);
-  *p = (T*)q;
-  return PBD_OK;
+  const hipError_t e = h->frame_allocs.alloc(p, n);
+  return e == hipSuccess ? PBD_OK : fail(h, PBD_ERR_HIP, pbd_alloc_error("", e));
 }
-// Model-lifetime buffers (device, or pinned host): counted in model_bytes (counted = false: not part of the footprint), freed by
-// pbd_destroy
+// Model-lifetime buffers (device, or pinned host): counted in the model footprint (counted = false: not part of it), freed by pbd_destroy
 template <typename T>
 int model_alloc(pbd_handle* h, T** p, size_t n, bool pinned = false, bool counted = true) {
-  void* q = nullptr;
-  hipError_t e = pinned ? hipHostMalloc(&q, sizeof(T) * n) : hipMalloc(&q, sizeof(T) * n);
-  if (e != hipSuccess) return fail(h, PBD_ERR_HIP, std::string(pinned ? "hipHostMalloc: " : "hipMalloc: ") + hipGetErrorString(e));
-  h->model_allocs.push_back({q, counted ? sizeof(T) * n : 0, pinned});
-  h->model_bytes += h->model_allocs.back().bytes;
-  *p = (T*)q;
-  return PBD_OK;
+  const hipError_t e = h->model_allocs.alloc(p, n, pinned, counted);
+  return e == hipSuccess ? PBD_OK : fail(h, PBD_ERR_HIP, pbd_alloc_error("", e, pinned));
 }
-inline void model_free(pbd_handle* h, void* p) {
-  for (auto b = h->model_allocs.begin(); b != h->model_allocs.end(); ++b)
-    if (b->p == p) { if (b->pinned) hipHostFree(p); else hipFree(p); h->model_bytes -= b->bytes; h->model_allocs.erase(b); return; }
-}
+inline void model_free(pbd_handle* h, void* p) { h->model_allocs.release(p); }
 // *p holds `have` units; grown (not kept) to `need` units of n elements (n = 0: need elements)
 template <typename T, typename C>
 int model_grow(pbd_handle* h, T** p, C& have, C need, size_t n = 0) {

@@ -5,28 +5,6 @@
 #include "pbd_internal.hpp"
 #include "kmeans_core.hpp"
 
-namespace {
-struct KmeansRun {
-  int prev = -1;
-  hipStream_t st = nullptr;
-  std::vector<void*> bufs;
-  template <class T> hipError_t alloc(T** p, size_t n) {
-    void* q = nullptr;
-    const hipError_t e = hipMalloc(&q, (n ? n : 1) * sizeof(T));
-    if (e == hipSuccess) bufs.push_back(q);
-    *p = (T*)q;
-    return e;
-  }
-  ~KmeansRun() {
-    if (st) hipStreamSynchronize(st);   // an error return may leave copies queued: nothing they touch goes away before they are done
-    for (void* b : bufs) hipFree(b);
-    if (st) hipStreamDestroy(st);
-    if (prev >= 0) hipSetDevice(prev);
-    (void)hipGetLastError();
-  }
-};
-}  // namespace
-
 #define KMHIP(x) do { if ((x) != hipSuccess) return PBD_ERR_HIP; } while (0)
 
 #pragma GCC visibility push(default)
@@ -38,11 +16,10 @@ extern "C" int pbd_cluster_parts(int device, const double* def, int n, int P, co
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { (void)hipGetLastError(); return PBD_ERR_HIP; }
   std::vector<int> pcap((size_t)P);   // (declared before `run`: it outlives the stream that copies into it)
-  KmeansRun run;
-  if (hipGetDevice(&run.prev) != hipSuccess) run.prev = -1;
+  DeviceRun run;
   KMHIP(hipSetDevice(device));
   CLEAR_STICKY();
-  KMHIP(hipStreamCreateWithFlags(&run.st, hipStreamNonBlocking));
+  KMHIP(run.open());
 
   std::vector<int> pa((size_t)P), pb((size_t)P);
   for (int p = 0; p < P; ++p) km_pair(parent, P, p, &pa[p], &pb[p]);
@@ -66,21 +43,21 @@ extern "C" int pbd_cluster_parts(int device, const double* def, int n, int P, co
   KMHIP(run.alloc(&a.pcap, (size_t)P));
   a.def = d_def; a.pa = d_pa; a.pb = d_pb; a.K = d_K;
   a.n = n; a.P = P; a.R = R; a.max_iter = max_iter; a.seed = seed;
-  KMHIP(hipMemcpyAsync(d_def, def, ndef * sizeof(double), hipMemcpyHostToDevice, run.st));
-  KMHIP(hipMemcpyAsync(d_pa, pa.data(), (size_t)P * sizeof(int), hipMemcpyHostToDevice, run.st));
-  KMHIP(hipMemcpyAsync(d_pb, pb.data(), (size_t)P * sizeof(int), hipMemcpyHostToDevice, run.st));
-  KMHIP(hipMemcpyAsync(d_K, K, (size_t)P * sizeof(int), hipMemcpyHostToDevice, run.st));
-  launch_kmeans(a, run.st);
+  KMHIP(hipMemcpyAsync(d_def, def, ndef * sizeof(double), hipMemcpyHostToDevice, run.stream));
+  KMHIP(hipMemcpyAsync(d_pa, pa.data(), (size_t)P * sizeof(int), hipMemcpyHostToDevice, run.stream));
+  KMHIP(hipMemcpyAsync(d_pb, pb.data(), (size_t)P * sizeof(int), hipMemcpyHostToDevice, run.stream));
+  KMHIP(hipMemcpyAsync(d_K, K, (size_t)P * sizeof(int), hipMemcpyHostToDevice, run.stream));
+  launch_kmeans(a, run.stream);
   KMHIP(hipGetLastError());
 
-  KMHIP(hipMemcpyAsync(idx, a.idx, (size_t)P * n * sizeof(int32_t), hipMemcpyDeviceToHost, run.st));
-  KMHIP(hipMemcpyAsync(pcap.data(), a.pcap, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, run.st));
-  if (centres) KMHIP(hipMemcpyAsync(centres, a.centres, (size_t)P * nc * sizeof(double), hipMemcpyDeviceToHost, run.st));
-  if (sumdist) KMHIP(hipMemcpyAsync(sumdist, a.sumdist, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, run.st));
-  if (best_trial) KMHIP(hipMemcpyAsync(best_trial, a.best, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, run.st));
-  if (trial_sumdist) KMHIP(hipMemcpyAsync(trial_sumdist, a.tsum, trials * sizeof(double), hipMemcpyDeviceToHost, run.st));
-  if (trial_iters) KMHIP(hipMemcpyAsync(trial_iters, a.titers, trials * sizeof(int32_t), hipMemcpyDeviceToHost, run.st));
-  KMHIP(hipStreamSynchronize(run.st));
+  KMHIP(hipMemcpyAsync(idx, a.idx, (size_t)P * n * sizeof(int32_t), hipMemcpyDeviceToHost, run.stream));
+  KMHIP(hipMemcpyAsync(pcap.data(), a.pcap, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, run.stream));
+  if (centres) KMHIP(hipMemcpyAsync(centres, a.centres, (size_t)P * nc * sizeof(double), hipMemcpyDeviceToHost, run.stream));
+  if (sumdist) KMHIP(hipMemcpyAsync(sumdist, a.sumdist, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, run.stream));
+  if (best_trial) KMHIP(hipMemcpyAsync(best_trial, a.best, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, run.stream));
+  if (trial_sumdist) KMHIP(hipMemcpyAsync(trial_sumdist, a.tsum, trials * sizeof(double), hipMemcpyDeviceToHost, run.stream));
+  if (trial_iters) KMHIP(hipMemcpyAsync(trial_iters, a.titers, trials * sizeof(int32_t), hipMemcpyDeviceToHost, run.stream));
+  KMHIP(hipStreamSynchronize(run.stream));
   if (capped) {
     int c = 0;
     for (int p = 0; p < P; ++p) c += pcap[p];

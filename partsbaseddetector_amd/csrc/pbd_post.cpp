@@ -9,40 +9,6 @@
 #include "pbd_internal.hpp"
 #include "gt_overlap.hpp"
 
-// ---- the scratch of one stand-alone call ---------------------------------------------------------------------------------
-// Device and pinned buffers, freed when it goes out of scope; the first HIP error is kept and every later step is skipped.
-// Copies run on the handle's stream; finish() synchronises it once and reports the error under the caller's prefix.
-namespace {
-struct Scratch {
-  pbd_handle* h;
-  hipError_t e = hipSuccess;
-  std::vector<std::pair<void*, bool>> bufs;   // (buffer, pinned)
-  explicit Scratch(pbd_handle* hd) : h(hd) {}
-  ~Scratch() { for (auto& b : bufs) { if (b.second) hipHostFree(b.first); else hipFree(b.first); } }
-  bool ok() const { return e == hipSuccess; }
-  void chk(hipError_t r) { if (e == hipSuccess) e = r; }
-  template <typename T> T* alloc(size_t n, bool pinned) {   // n = 0: no buffer (nullptr)
-    void* p = nullptr;
-    if (!ok() || n == 0) return nullptr;
-    chk(pinned ? hipHostMalloc(&p, sizeof(T) * n) : hipMalloc(&p, sizeof(T) * n));
-    if (p) bufs.push_back({p, pinned});
-    return (T*)p;
-  }
-  template <typename T> T* dev(size_t n) { return alloc<T>(n, false); }
-  void up(void* d, const void* s, size_t bytes) { if (ok() && bytes) chk(hipMemcpyAsync(d, s, bytes, hipMemcpyHostToDevice, h->stream)); }
-  void up2d(void* d, size_t dpitch, const void* s, size_t spitch, size_t row, size_t rows) {
-    if (ok() && row && rows) chk(hipMemcpy2DAsync(d, dpitch, s, spitch, row, rows, hipMemcpyHostToDevice, h->stream));
-  }
-  void down(void* d, const void* s, size_t bytes) { if (ok() && bytes) chk(hipMemcpyAsync(d, s, bytes, hipMemcpyDeviceToHost, h->stream)); }
-  void zero(void* d, size_t bytes) { if (ok()) chk(hipMemsetAsync(d, 0, bytes, h->stream)); }
-  void launched() { if (ok()) chk(hipGetLastError()); }
-  int finish(const char* what) {
-    chk(hipStreamSynchronize(h->stream));
-    return ok() ? PBD_OK : fail(h, PBD_ERR_HIP, std::string(what) + hipGetErrorString(e));
-  }
-};
-}  // namespace
-
 // the depth image of a stand-alone call: NULL only with an empty size
 static int depth_image_args(pbd_handle* h, const void* depth, int dw, int dh, bool* empty) {
   if (dw < 0 || dh < 0 || (!depth && dw > 0 && dh > 0)) return fail(h, PBD_ERR_ARG, "depth image: NULL only with an empty size");
@@ -224,9 +190,9 @@ static int cl3_buffers(pbd_handle* h) {
 // indices one after the other in idx[].  Records whose indices did not fit the pool run again, alone, into a pool grown to what
 // they need (and at least what the launch claimed in all, so that the next launch fits): the handle's own pool, or (s_pool) one of
 // the caller's scratch.
-static int cl3_resolve(pbd_handle* h, Cluster3dArgs a, int src, int slots, Scratch* s_pool, const std::vector<int>& lst,
+static int cl3_resolve(pbd_handle* h, Cluster3dArgs a, int src, int slots, CallScratch* s_pool, const std::vector<int>& lst,
                        std::vector<pbd_cluster3d>& res, std::vector<int32_t>& idx) {
-  Scratch s(h);
+  CallScratch s(h);
   unsigned long long used = 0;
   s.down(&used, a.pool_used, sizeof(used));
   int rc = s.finish("cluster3d: ");
@@ -431,7 +397,7 @@ static int fv_host(pbd_handle* h, const pbd_candidate_head* heads, const int32_t
     const size_t n = std::min(chunk, (size_t)count - r0);
     a.rec0 = (int)r0; a.n = (int)n;
     a.blocks = (pbd_feature_block*)h->d_fv_stage; a.windows = d_win;
-    Scratch s(h);
+    CallScratch s(h);
     launch_featvec(a, h->ts, h->stream);
     s.launched();
     s.down((char*)blocks + r0 * bbytes, h->d_fv_stage, n * bbytes);
@@ -717,7 +683,7 @@ int pbd_i_filter_host(pbd_handle* h, int mode, float overlap, int im_w, int im_h
   }
   ON_DEVICE(h);
   const size_t st = h->cand_stride, n = (size_t)count, mask = cand_filter_mask_bytes(im_w, im_h);
-  Scratch s(h);
+  CallScratch s(h);
   char* d_in = s.dev<char>(st * n);
   char* d_out = s.dev<char>(st * n);
   int* d_cnt = s.dev<int>(5);
@@ -957,7 +923,7 @@ int pbd_candidates_depth_filter(pbd_handle* h, float zfactor, const void* depth,
   std::vector<int> npart, par; std::vector<double> thr;
   zf_table(h, zfactor, npart, par, thr);
   const int cnt3[3] = {count, 0, 0};
-  Scratch s(h);
+  CallScratch s(h);
   ZFilterArgs z{};
   z.in.p = s.dev<char>(st * n); z.in.capacity = count; z.in.stride = st; z.in.mp = mp; z.in.nlevels = 0;
   z.z.img = empty ? nullptr : s.dev<char>(row * dh); z.z.pitch = row; z.z.fbytes = 0; z.z.w = empty ? 0 : dw; z.z.h = empty ? 0 : dh; z.z.has = 1;
@@ -1031,7 +997,7 @@ int pbd_candidates_box3d(pbd_handle* h, const pbd_camera* cam, const void* depth
   const size_t st = h->cand_stride, n = (size_t)count, row = (size_t)dw * esz;
   std::vector<char> rec(st * n, 0);
   for (size_t i = 0; i < n; ++i) pbd_rec_put(rec.data() + st * i, mp, heads, boxes, nullptr, i);
-  Scratch s(h);
+  CallScratch s(h);
   Box3dArgs a{};
   a.in.p = s.dev<char>(st * n); a.in.stride = st; a.in.mp = mp; a.in.count = s.dev<int>(1); a.in.capacity = count; a.in.nlevels = 0;
   a.z.img = empty ? nullptr : s.dev<char>(row * dh); a.z.pitch = row; a.z.fbytes = 0; a.z.w = empty ? 0 : dw; a.z.h = empty ? 0 : dh; a.z.has = 1;
@@ -1108,7 +1074,7 @@ int pbd_candidates_cluster3d(pbd_handle* h, const void* cloud, int cw, int ch, i
   const size_t bytes = npts ? (size_t)(ch - 1) * row_stride + (size_t)(cw - 1) * point_stride + 12 : 0, n = (size_t)count;
   unsigned long long pool_cap = std::min<unsigned long long>((unsigned long long)count * (unsigned long long)npts, 4ull * (unsigned long long)pcap);
   pool_cap = std::max<unsigned long long>(pool_cap, 1);
-  Scratch s(h);
+  CallScratch s(h);
   Cluster3dArgs a{};
   a.in.count = s.dev<int>(1); a.in.capacity = count;
   a.z.img = s.dev<char>(bytes); a.z.pitch = (size_t)row_stride; a.z.w = cw; a.z.h = ch; a.z.has = 1; a.pstride = (size_t)point_stride;
@@ -1180,7 +1146,7 @@ int pbd_candidates_part_scores(pbd_handle* h, const pbd_candidate_head* heads, c
   const size_t st = h->cand_stride, n = (size_t)count, m3 = (size_t)mp * 3;
   std::vector<char> rec(st * n, 0);
   for (size_t i = 0; i < n; ++i) pbd_rec_put(rec.data() + st * i, mp, heads, nullptr, locs, i);
-  Scratch s(h);
+  CallScratch s(h);
   PartScoreArgs a = ps_args(h);
   a.in.p = s.dev<char>(st * n); a.in.stride = st; a.in.mp = mp; a.in.count = s.dev<int>(1); a.in.capacity = count; a.in.nlevels = 0;
   a.out = s.dev<double>(n * m3);
@@ -1262,7 +1228,7 @@ int pbd_candidates_select_gt(pbd_handle* h, const double* gt, int ngt, double ov
   const size_t st = h->cand_stride, n = (size_t)count;
   std::vector<char> rec(st * n, 0);
   for (size_t i = 0; i < n; ++i) pbd_rec_put(rec.data() + st * i, mp, heads, boxes, nullptr, i);
-  Scratch s(h);
+  CallScratch s(h);
   GtBoxArgs a = gt_args(h, 1, overlap);
   char* d_rec = s.dev<char>(st * n);
   int* d_cnt = s.dev<int>(2);

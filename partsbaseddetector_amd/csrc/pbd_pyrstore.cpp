@@ -13,7 +13,8 @@ struct pbd_pyrstore {
   int device = 0, sbin = 0, interval = 0, kind = 0, pad = 0, ts = 4;   // the signature (with PBD_FLEN)
   int nslots = 0, max_w = 0, max_h = 0;
   size_t slot_elems = 0;            // total(max_w, max_h)
-  char* d_mem = nullptr;            // [nslots][slot_elems] of T
+  DevBufs mem;
+  char* d_mem = nullptr;            // [nslots][slot_elems] of T: mem's one block
   struct Slot { int w = 0, h = 0, cn = 0, nlevels = 0; size_t total = 0; };
   std::vector<Slot> slots;
 };
@@ -140,10 +141,10 @@ int pbd_pyrstore_create(pbd_handle* producer, int slots, int max_w, int max_h, p
   s->sbin = h->md.sbin; s->interval = h->md.interval; s->kind = h->pyr_kind; s->pad = h->pad; s->ts = h->ts;
   s->nslots = slots; s->max_w = max_w; s->max_h = max_h; s->slot_elems = (size_t)total;
   s->slots.assign((size_t)slots, pbd_pyrstore::Slot{});
-  hipError_t e = hipMalloc((void**)&s->d_mem, slot_bytes(s) * (size_t)slots);
+  hipError_t e = s->mem.alloc(&s->d_mem, slot_bytes(s) * (size_t)slots);
   if (e != hipSuccess) {
     delete s;
-    return fail(h, PBD_ERR_HIP, std::string("pyramid store: hipMalloc: ") + hipGetErrorString(e));
+    return fail(h, PBD_ERR_HIP, pbd_alloc_error("pyramid store: ", e));
   }
   *out = s;
   return PBD_OK;
@@ -154,7 +155,6 @@ void pbd_pyrstore_destroy(pbd_pyrstore* s) {
   if (s->d_mem) {
     hipSetDevice(s->device);
     hipDeviceSynchronize();   // (a consumer's load may still read a slot on its own stream)
-    hipFree(s->d_mem);
   }
   delete s;
 }

@@ -95,10 +95,10 @@ int pbd_qp_create(pbd_handle* h, int capacity, double cpos, double cneg, const d
   D.k = (int)k; D.len = (int)len; D.capacity = capacity; D.nbmax = 3 * mp;
   const size_t cap = (size_t)capacity;
   int rc;
-  if ((rc = qalloc(q, &D.x, cap * (size_t)k)) || (rc = qalloc(q, &D.ids, cap * 5)) || (rc = qalloc(q, &D.b, cap)) ||
-      (rc = qalloc(q, &D.d, cap)) || (rc = qalloc(q, &D.tab, cap * D.nbmax * 3)) || (rc = qalloc(q, &D.nblk, cap)) ||
-      (rc = qalloc(q, &D.slot, cap)) || (rc = qalloc(q, &q->d_wreg, (size_t)len)) || (rc = qalloc(q, &q->d_w0, (size_t)len)) ||
-      (rc = qalloc(q, &q->d_foff, (size_t)nf))) {
+  if ((rc = q->alloc(&D.x, cap * (size_t)k)) || (rc = q->alloc(&D.ids, cap * 5)) || (rc = q->alloc(&D.b, cap)) ||
+      (rc = q->alloc(&D.d, cap)) || (rc = q->alloc(&D.tab, cap * D.nbmax * 3)) || (rc = q->alloc(&D.nblk, cap)) ||
+      (rc = q->alloc(&D.slot, cap)) || (rc = q->alloc(&q->d_wreg, (size_t)len)) || (rc = q->alloc(&q->d_w0, (size_t)len)) ||
+      (rc = q->alloc(&q->d_foff, (size_t)nf))) {
     pbd_qp_destroy(q);
     return rc;
   }
@@ -135,7 +135,6 @@ int pbd_qp_create(pbd_handle* h, int capacity, double cpos, double cneg, const d
 void pbd_qp_destroy(pbd_qp* q) {
   if (!q) return;
   hipStreamSynchronize(q->h->stream);   // (like pbd_destroy: the caller's current device is left alone)
-  for (void* p : q->bufs) hipFree(p);
   delete q;
 }
 
@@ -150,7 +149,7 @@ int pbd_qp_dims(const pbd_qp* q, int* len, int* k, int* capacity, int* n) {
 
 int pbd_qp_footprint(const pbd_qp* q, size_t* bytes) {
   if (!q || !bytes) return PBD_ERR_ARG;
-  *bytes = q->bytes;
+  *bytes = q->bufs.bytes();
   return PBD_OK;
 }
 
@@ -225,9 +224,10 @@ int pbd_qp_score(pbd_qp* q, const double* w, const int32_t* inds, int n, double*
   if (rc || n == 0) return rc;
   ON_DEVICE(h);
   const size_t len = (size_t)q->dev.len;
-  Tmp t;
-  if ((rc = t.get(h, sizeof(double) * (len + n) + sizeof(int) * n))) return rc;
-  double* d_w = (double*)t.p; double* d_out = d_w + len; int* d_inds = (int*)(d_out + n);
+  CallScratch t(h);
+  char* tp;
+  if ((rc = t.get(&tp, sizeof(double) * (len + n) + sizeof(int) * n, "example cache: "))) return rc;
+  double* d_w = (double*)tp; double* d_out = d_w + len; int* d_inds = (int*)(d_out + n);
   HIPCHK(h, hipMemcpyAsync(d_w, w, sizeof(double) * len, hipMemcpyHostToDevice, h->stream));
   if (inds) HIPCHK(h, hipMemcpyAsync(d_inds, inds, sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
   launch_qp_score(q->dev, d_w, inds ? d_inds : nullptr, n, d_out, h->stream);
@@ -254,9 +254,10 @@ int pbd_qp_lincomb(pbd_qp* q, const double* a, const int32_t* inds, int n, doubl
   if (rc) return rc;
   ON_DEVICE(h);
   const size_t len = (size_t)q->dev.len, cap = (size_t)q->dev.capacity;
-  Tmp t;
-  if ((rc = t.get(h, sizeof(double) * (len + cap) + sizeof(int) * std::max(n, 1)))) return rc;
-  double* d_w = (double*)t.p; double* d_a = d_w + len; int* d_inds = (int*)(d_a + cap);
+  CallScratch t(h);
+  char* tp;
+  if ((rc = t.get(&tp, sizeof(double) * (len + cap) + sizeof(int) * std::max(n, 1), "example cache: "))) return rc;
+  double* d_w = (double*)tp; double* d_a = d_w + len; int* d_inds = (int*)(d_a + cap);
   if (n > 0) HIPCHK(h, hipMemcpyAsync(d_a, a, sizeof(double) * cap, hipMemcpyHostToDevice, h->stream));
   if (inds && n > 0) HIPCHK(h, hipMemcpyAsync(d_inds, inds, sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
   launch_qp_lincomb(q->dev, d_a, inds ? d_inds : nullptr, n, d_w, h->stream);

@@ -22,8 +22,11 @@ struct pbd_qp {
   double* d_wreg = nullptr; double* d_w0 = nullptr; int* d_foff = nullptr;
   std::vector<int> slot;            // host copy of dev.slot
   std::vector<int> foff;            // [nfilters] dense start of each filter, the caller's order
-  std::vector<void*> bufs;
-  size_t bytes = 0;
+  DevBufs bufs;                     // everything the cache holds on the device (pbd_qp_footprint: its bytes)
+  template <typename T> int alloc(T** p, size_t n) {
+    const hipError_t e = bufs.alloc(p, n);
+    return e == hipSuccess ? PBD_OK : fail(h, PBD_ERR_HIP, pbd_alloc_error("example cache: ", e));
+  }
   // solver side
   QpSolveState sol;
   std::vector<char> overlap;        // [capacity] by column: a column put with blocks that overlap each other (never one of pbd_qp_write's)
@@ -33,23 +36,6 @@ struct pbd_qp {
 };
 
 namespace pbd_qp_detail {
-template <typename T> int qalloc(pbd_qp* q, T** p, size_t n) {
-  void* v = nullptr;
-  hipError_t e = hipMalloc(&v, sizeof(T) * std::max<size_t>(n, 1));
-  if (e != hipSuccess) return fail(q->h, PBD_ERR_HIP, std::string("example cache: hipMalloc: ") + hipGetErrorString(e));
-  q->bufs.push_back(v); q->bytes += sizeof(T) * std::max<size_t>(n, 1);
-  *p = (T*)v;
-  return PBD_OK;
-}
-// a scratch buffer of one call: freed when it goes out of scope
-struct Tmp {
-  void* p = nullptr;
-  ~Tmp() { if (p) hipFree(p); }
-  int get(pbd_handle* h, size_t bytes) {
-    hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 1));
-    return e == hipSuccess ? PBD_OK : fail(h, PBD_ERR_HIP, std::string("example cache: hipMalloc: ") + hipGetErrorString(e));
-  }
-};
 inline int finish(pbd_handle* h, const char* what) {
   hipError_t e = hipStreamSynchronize(h->stream);
   return e == hipSuccess ? PBD_OK : fail(h, PBD_ERR_HIP, std::string(what) + hipGetErrorString(e));

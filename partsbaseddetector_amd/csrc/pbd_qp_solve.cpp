@@ -19,9 +19,9 @@ int ensure(pbd_qp* q) {
   const size_t cap = (size_t)q->dev.capacity, len = (size_t)q->dev.len;
   QpSolveDev& D = S.dev;
   int rc;
-  if ((rc = qalloc(q, &D.a, cap)) || (rc = qalloc(q, &D.sv, cap)) || (rc = qalloc(q, &D.w, len)) || (rc = qalloc(q, &D.stat, QP_STAT_N)) ||
-      (rc = qalloc(q, &D.idC, cap)) || (rc = qalloc(q, &D.idP, cap)) || (rc = qalloc(q, &D.idI, cap)) || (rc = qalloc(q, &D.err, cap)) ||
-      (rc = qalloc(q, &D.order, cap)) || (rc = qalloc(q, &D.scores, cap)))
+  if ((rc = q->alloc(&D.a, cap)) || (rc = q->alloc(&D.sv, cap)) || (rc = q->alloc(&D.w, len)) || (rc = q->alloc(&D.stat, QP_STAT_N)) ||
+      (rc = q->alloc(&D.idC, cap)) || (rc = q->alloc(&D.idP, cap)) || (rc = q->alloc(&D.idI, cap)) || (rc = q->alloc(&D.err, cap)) ||
+      (rc = q->alloc(&D.order, cap)) || (rc = q->alloc(&D.scores, cap)))
     return rc;   // (what was allocated stays with the cache and is freed with it)
   HIPCHK(h, hipMemsetAsync(D.a, 0, sizeof(double) * cap, h->stream));
   HIPCHK(h, hipMemsetAsync(D.sv, 0, cap, h->stream));
@@ -237,15 +237,11 @@ int pbd_qp_noneg(pbd_qp* q, const int32_t* idx, int p) {
   QpSolveState& S = q->sol;
   int* d_new = nullptr;
   if (p > 0) {
-    if ((rc = qalloc(q, &d_new, (size_t)p))) return rc;
+    if ((rc = q->alloc(&d_new, (size_t)p))) return rc;
     HIPCHK(h, hipMemcpyAsync(d_new, idx, sizeof(int) * p, hipMemcpyHostToDevice, h->stream));
     if ((rc = finish(h, "QP solver noneg: "))) return rc;
   }
-  if (S.d_noneg) {   // the list this one replaces (every solver call is synchronous: nothing in flight reads it)
-    q->bufs.erase(std::find(q->bufs.begin(), q->bufs.end(), (void*)S.d_noneg));
-    q->bytes -= sizeof(int) * (size_t)S.p;
-    hipFree(S.d_noneg);
-  }
+  if (S.d_noneg) q->bufs.release(S.d_noneg);   // the list this one replaces (every solver call is synchronous: nothing in flight reads it)
   S.d_noneg = d_new; S.p = p;
   return PBD_OK;
 }
@@ -383,12 +379,13 @@ int pbd_qp_weights(pbd_qp* q, double* w_out) {
   SOLVER_ENTRY(q);
   if (!w_out) return fail(h, PBD_ERR_ARG, "QP solver weights: w_out is NULL");
   const size_t len = (size_t)q->dev.len;
-  Tmp t;
+  CallScratch t(h);
+  double* d_wq;
   int rc;
-  if ((rc = t.get(h, sizeof(double) * len))) return rc;
-  launch_qp_weights(q->sol.dev.w, q->d_wreg, q->d_w0, (int)len, (double*)t.p, h->stream);
+  if ((rc = t.get(&d_wq, len, "QP solver: "))) return rc;
+  launch_qp_weights(q->sol.dev.w, q->d_wreg, q->d_w0, (int)len, d_wq, h->stream);
   LAUNCHCHK(h, "QP solver weights");
-  HIPCHK(h, hipMemcpyAsync(w_out, t.p, sizeof(double) * len, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(w_out, d_wq, sizeof(double) * len, hipMemcpyDeviceToHost, h->stream));
   return finish(h, "QP solver weights: ");
 }
 
@@ -397,12 +394,13 @@ int pbd_qp_weights(pbd_qp* q, double* w_out) {
 int pbd_qp_apply_weights(pbd_qp* q) {
   SOLVER_ENTRY(q);
   const size_t len = (size_t)q->dev.len;
-  Tmp t;
+  CallScratch t(h);
+  double* d_wq;
   int rc;
-  if ((rc = t.get(h, sizeof(double) * len))) return rc;
-  launch_qp_weights(q->sol.dev.w, q->d_wreg, q->d_w0, (int)len, (double*)t.p, h->stream);
+  if ((rc = t.get(&d_wq, len, "QP solver: "))) return rc;
+  launch_qp_weights(q->sol.dev.w, q->d_wreg, q->d_w0, (int)len, d_wq, h->stream);
   LAUNCHCHK(h, "QP solver weights");
-  return pbd_i_set_weights_dev(h, (const double*)t.p, (int)len);
+  return pbd_i_set_weights_dev(h, d_wq, (int)len);
 }
 
 // train.m:75 qp.n = 0.  The cache goes back to what pbd_qp_create left — columns, tables and the example -> column map included, so
@@ -448,10 +446,11 @@ int pbd_qp_positive_threshold(pbd_qp* q, double frac, double* thresh, int* npos)
   if (q->n == 0) return fail(h, PBD_ERR_STATE, "positive threshold: the cache holds no positive example");
   QpSolveDev& D = q->sol.dev;
   const size_t len = (size_t)q->dev.len;
-  Tmp t;
+  CallScratch t(h);
+  char* tp;
   int rc;
-  if ((rc = t.get(h, sizeof(double) * len + sizeof(QpThreshOut)))) return rc;
-  double* d_weff = (double*)t.p;
+  if ((rc = t.get(&tp, sizeof(double) * len + sizeof(QpThreshOut), "positive threshold: "))) return rc;
+  double* d_weff = (double*)tp;
   QpThreshOut* d_out = (QpThreshOut*)(d_weff + len);
   QpThreshOut out{0.0, -1, 0};
   HIPCHK(h, hipMemsetAsync(d_out, 0, sizeof(QpThreshOut), h->stream));

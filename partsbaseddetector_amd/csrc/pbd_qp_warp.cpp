@@ -30,11 +30,15 @@ int hog_tile_side(int sbin, int ts) {
   return hog_lds_bytes(sbin, tc, ts, 24) > 150 * 1024 ? 0 : tc;
 }
 
+const char* const kWhat = "warped positives: ";
+
 struct WarpCall {
   int kh = 0, kw = 0, ow = 0, oh = 0;
   std::vector<WarpGeom> g;          // [n] every box of the call
   hipMemcpyKind kind = hipMemcpyHostToDevice;   // where the frame's rows are copied from (pbd_qp_write_warped_dev_u8: the device)
-  Tmp img, win, feat;
+  CallScratch mem;                  // the call's frame, windows and features
+  char *img = nullptr, *win = nullptr, *feat = nullptr;
+  explicit WarpCall(pbd_handle* h) : mem(h) {}
 };
 
 // every refusal of the two entries' shared arguments, and the boxes' geometry: nothing touches the device
@@ -70,11 +74,13 @@ int warp_run(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int strid
   if (m == 0) return PBD_OK;
   const size_t rowb = (size_t)w * cn, nwin = (size_t)ow * oh * 3, wlen = (size_t)kh * kw * PBD_FLEN;
   int rc;
-  if ((rc = c->img.get(h, rowb * hgt)) || (rc = c->win.get(h, sizeof(double) * nwin * m)) || (rc = c->feat.get(h, (size_t)h->ts * wlen * m))) return rc;
-  if ((rc = copy_rows(h, c->img.p, im, (size_t)stride, rowb, (size_t)hgt, c->kind))) return rc;
+  if ((rc = c->mem.get(&c->img, rowb * hgt, kWhat)) || (rc = c->mem.get(&c->win, sizeof(double) * nwin * m, kWhat)) ||
+      (rc = c->mem.get(&c->feat, (size_t)h->ts * wlen * m, kWhat)))
+    return rc;
+  if ((rc = copy_rows(h, c->img, im, (size_t)stride, rowb, (size_t)hgt, c->kind))) return rc;
   WarpArgs a{};
-  a.im = (const uint8_t*)c->img.p; a.w = w; a.h = hgt; a.cn = cn; a.stride = rowb;
-  a.win = (double*)c->win.p; a.ow = ow; a.oh = oh;
+  a.im = (const uint8_t*)c->img; a.w = w; a.h = hgt; a.cn = cn; a.stride = rowb;
+  a.win = (double*)c->win; a.ow = ow; a.oh = oh;
   std::vector<WarpJob> jobs;
   std::vector<MatTap> taps;
   std::vector<int32_t> ix; std::vector<double> wv;
@@ -104,12 +110,13 @@ int warp_run(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int strid
       jobs.push_back(j);
       scr += first; max_first = std::max(max_first, (unsigned)first);
     }
-    Tmp t_scr, t_tab;
+    CallScratch chunk(h);
+    double* d_scr; char* d_tab;
     const size_t jb = sizeof(WarpJob) * jobs.size();
-    if ((rc = t_scr.get(h, sizeof(double) * scr)) || (rc = t_tab.get(h, jb + sizeof(MatTap) * taps.size()))) return rc;
-    HIPCHK(h, hipMemcpyAsync(t_tab.p, jobs.data(), jb, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync((char*)t_tab.p + jb, taps.data(), sizeof(MatTap) * taps.size(), hipMemcpyHostToDevice, h->stream));
-    a.jobs = (const WarpJob*)t_tab.p; a.taps = (const MatTap*)((char*)t_tab.p + jb); a.scratch = (double*)t_scr.p;
+    if ((rc = chunk.get(&d_scr, scr, kWhat)) || (rc = chunk.get(&d_tab, jb + sizeof(MatTap) * taps.size(), kWhat))) return rc;
+    HIPCHK(h, hipMemcpyAsync(d_tab, jobs.data(), jb, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_tab + jb, taps.data(), sizeof(MatTap) * taps.size(), hipMemcpyHostToDevice, h->stream));
+    a.jobs = (const WarpJob*)d_tab; a.taps = (const MatTap*)(d_tab + jb); a.scratch = d_scr;
     EvTimer tm(h->profiling, h->stream);
     launch_warp(a, (int)jobs.size(), max_first, h->stream);
     tm.stop(h->stream);
@@ -126,13 +133,14 @@ int warp_run(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int strid
     lv[i] = LevelDev{ow, oh, kw + 2, kh + 2, kw, kh, (unsigned long long)i * nwin * sizeof(double), (unsigned long long)i * kh * kw};
     for (int y = 0; y < kh; y += tc) for (int x = 0; x < kw; x += tc) tiles.push_back(HogTile{i, y, x, 0});
   }
-  Tmp t_hog;
+  CallScratch t_hog(h);
+  char* d_hog;
   const size_t lb = sizeof(LevelDev) * lv.size();
-  if ((rc = t_hog.get(h, lb + sizeof(HogTile) * tiles.size()))) return rc;
-  HIPCHK(h, hipMemcpyAsync(t_hog.p, lv.data(), lb, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync((char*)t_hog.p + lb, tiles.data(), sizeof(HogTile) * tiles.size(), hipMemcpyHostToDevice, h->stream));
+  if ((rc = t_hog.get(&d_hog, lb + sizeof(HogTile) * tiles.size(), kWhat))) return rc;
+  HIPCHK(h, hipMemcpyAsync(d_hog, lv.data(), lb, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_hog + lb, tiles.data(), sizeof(HogTile) * tiles.size(), hipMemcpyHostToDevice, h->stream));
   EvTimer tm(h->profiling, h->stream);
-  launch_hog((const HogTile*)((char*)t_hog.p + lb), (int)tiles.size(), (const LevelDev*)t_hog.p, (const uint8_t*)c->win.p, c->feat.p, h->ts, 3, sbin,
+  launch_hog((const HogTile*)(d_hog + lb), (int)tiles.size(), (const LevelDev*)d_hog, (const uint8_t*)c->win, c->feat, h->ts, 3, sbin,
              tc, h->d_hog_lut, nullptr, 0, PBD_DEPTH_64F, h->stream);
   tm.stop(h->stream);
   LAUNCHCHK(h, "warped positives: features");
@@ -146,15 +154,15 @@ int warp_windows_(pbd_handle* h, const uint8_t* im, int w, int hgt, int cn, int 
   if (!h) return PBD_ERR_ARG;
   if (h->ts != ts) return fail(h, PBD_ERR_STATE, ts == 4 ? "handle is PartsBasedDetector<double>: use the _f64 entry point"
                                                          : "handle is PartsBasedDetector<float>: use the float entry point");
-  WarpCall c;
+  WarpCall c(h);
   int rc = warp_check(h, im, w, hgt, cn, stride, boxes, n, filter, &c);
   if (rc || n == 0) return rc;
   ON_DEVICE(h);
   std::vector<int> sel((size_t)n);
   for (int i = 0; i < n; ++i) sel[i] = i;
   if ((rc = warp_run(h, im, w, hgt, cn, stride, sel, &c))) return rc;
-  if (windows) HIPCHK(h, hipMemcpyAsync(windows, c.win.p, sizeof(double) * c.ow * c.oh * 3 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-  if (features) HIPCHK(h, hipMemcpyAsync(features, c.feat.p, (size_t)ts * c.kh * c.kw * PBD_FLEN * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  if (windows) HIPCHK(h, hipMemcpyAsync(windows, c.win, sizeof(double) * c.ow * c.oh * 3 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  if (features) HIPCHK(h, hipMemcpyAsync(features, c.feat, (size_t)ts * c.kh * c.kw * PBD_FLEN * (size_t)n, hipMemcpyDeviceToHost, h->stream));
   return finish(h, "warped positives: ");
 }
 
@@ -163,7 +171,7 @@ int write_warped_(pbd_qp* q, const uint8_t* im, int w, int hgt, int cn, int stri
   if (!q) return PBD_ERR_ARG;
   pbd_handle* h = q->h;
   if (!written) return fail(h, PBD_ERR_ARG, "example cache: written is NULL");
-  WarpCall c;
+  WarpCall c(h);
   c.kind = kind;
   int rc = warp_check(h, im, w, hgt, cn, stride, boxes, n, filter, &c);
   if (rc) return rc;
@@ -190,12 +198,12 @@ int write_warped_(pbd_qp* q, const uint8_t* im, int w, int hgt, int cn, int stri
   if ((rc = warp_run(h, im, w, hgt, cn, stride, sel, &c))) return rc;
   std::vector<int> idv((size_t)m);
   for (int i = 0; i < m; ++i) idv[i] = ids ? ids[sel[i]] : sel[i];
-  Tmp t_ids;
-  if ((rc = t_ids.get(h, sizeof(int) * (size_t)m))) return rc;
-  HIPCHK(h, hipMemcpyAsync(t_ids.p, idv.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, h->stream));
+  int* d_ids;
+  if ((rc = c.mem.get(&d_ids, (size_t)m, kWhat))) return rc;
+  HIPCHK(h, hipMemcpyAsync(d_ids, idv.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, h->stream));
   QpPosArgs a{};
   a.q = q->dev; a.n0 = q->n; a.n = m;
-  a.feat = c.feat.p; a.ids = (const int*)t_ids.p;
+  a.feat = c.feat; a.ids = d_ids;
   a.wreg = q->d_wreg; a.w0 = q->d_w0;
   a.bias_start = bias; a.filt_start = q->foff[filter]; a.wlen = wlen;
   a.C = q->cpos;

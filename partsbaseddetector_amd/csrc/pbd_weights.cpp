@@ -35,14 +35,6 @@ WeightLayout layout_of(const pbd_handle* h) {
   for (int f = 0; f < nf; ++f) { L.mirror[f] = m; m += L.size[f]; }
   return L;
 }
-struct DevTmp {   // a scratch buffer of one call
-  void* p = nullptr;
-  ~DevTmp() { if (p) hipFree(p); }
-  int get(pbd_handle* h, size_t bytes) {
-    hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
-    return e == hipSuccess ? PBD_OK : fail(h, PBD_ERR_HIP, std::string("weights: hipMalloc: ") + hipGetErrorString(e));
-  }
-};
 // the refusals every update shares, in front of anything that touches the device
 int check_update(pbd_handle* h, const char* what) {
   if (h->in_group) return fail(h, PBD_ERR_UNSUPPORTED, std::string(what) + ": pbd_group members are not supported");
@@ -58,21 +50,21 @@ int set_weights(pbd_handle* h, const double* w, int len, bool on_host) {
   int rc = check_update(h, "weights");
   if (rc) return rc;
   ON_DEVICE(h);
-  DevTmp up;
+  CallScratch tmp(h);
+  double* d_up = nullptr;
   if (on_host) {
-    if ((rc = up.get(h, sizeof(double) * L.len))) return rc;
-    HIPCHK(h, hipMemcpyAsync(up.p, w, sizeof(double) * L.len, hipMemcpyHostToDevice, h->stream));
+    if ((rc = tmp.get(&d_up, L.len, "weights: "))) return rc;
+    HIPCHK(h, hipMemcpyAsync(d_up, w, sizeof(double) * L.len, hipMemcpyHostToDevice, h->stream));
   }
-  const double* d_w = on_host ? (const double*)up.p : w;
+  const double* d_w = on_host ? d_up : w;
   // the float32 values and the validation word, in one buffer and one copy back: the host mirror and what the checks below read
-  DevTmp stage, src;
-  if ((rc = stage.get(h, sizeof(float) * (L.len + 1))) || (rc = src.get(h, sizeof(int) * L.start.size()))) return rc;
-  float* d_stage = (float*)stage.p;
+  float* d_stage; int* d_src;
+  if ((rc = tmp.get(&d_stage, L.len + 1, "weights: ")) || (rc = tmp.get(&d_src, L.start.size(), "weights: "))) return rc;
   launch_weights_round(d_w, len, d_stage, (int*)(d_stage + L.len), h->stream);
   LAUNCHCHK(h, "weights");
   std::vector<float> st(L.len + 1);
   HIPCHK(h, hipMemcpyAsync(st.data(), d_stage, sizeof(float) * st.size(), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(src.p, L.start.data(), sizeof(int) * L.start.size(), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_src, L.start.data(), sizeof(int) * L.start.size(), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   int bad;
   memcpy(&bad, &st[L.len], sizeof(int));
@@ -93,7 +85,6 @@ int set_weights(pbd_handle* h, const double* w, int len, bool on_host) {
   std::copy(st.begin(), st.begin() + L.nbias, h->biasw.begin());
   std::copy(defw, defw + L.ndef4, h->defw.begin());
   for (size_t f = 0; f < L.start.size(); ++f) std::copy(st.begin() + L.start[f], st.begin() + L.start[f] + L.size[f], h->filters.begin() + L.mirror[f]);
-  const int* d_src = (const int*)src.p;
   auto pack = [&](int n0, int nf, int kh, int kw, int nfpad, void* wT, uint16_t* wS, float* oscale) {
     launch_bank_pack(d_stage, d_src + n0, nf, kh, kw, nfpad, wT, h->ts, h->stream);
     if (h->split_parts == 3) launch_bank_split(d_stage, d_src + n0, nf, kh, kw, wS, h->stream);

@@ -38,7 +38,7 @@ def root_scores(model, w, hgt):
 
 
 class Plain:
-    """pbd_detect_u8 into preallocated arrays, then the host selection"""
+    """pbd_detect_u8 into arrays allocated once, then the host selection"""
     def __init__(self, model, graph):
         self.h = capi.Handle(model, graph=graph, max_candidates=CAP)
         self.heads, self.boxes, self.locs = self.h._bufs(CAP)
